@@ -15,7 +15,8 @@ share as ONE launch chain (rt_render_device_batch) and, by default, ships them i
 then carries the single-frame latency beside the throughput (config.frame_latency_ms, config.batch, config.exchange).
 
 Rank 0 prints one JSON line.  `value` = rays traced per second (1 ray = 1 Scene::intersect_all call:
-primary, shadow or bounce segment; counted exactly by the kernel in the framebuffer's .w channel).
+primary, shadow or bounce segment; counted exactly by the kernel in the framebuffer's .w channel).  A plain run sets up, warms up,
+times the K steps, writes --dump-outputs DIR if given and prints the line; everything below is measured only with --full.
 `roofline` prices the dominant kernel (wf_travq) against vector-instruction issue: the vector wave-instructions of one launch --
 step counts of the counting instantiation in THIS run x the static per-step instruction counts of the production code object
 (tools/static_counts.py, written by build()), each instruction weighted by its measured issue cost -- over that launch's
@@ -87,10 +88,10 @@ def parse():
     ap.add_argument("--gather-only", action="store_true",
                     help="N > 1: time the EXCHANGE alone -- the tiles are rendered once, the timed steps repeat the gather of the same buffers (no render); "
                          "the line's value is null and config.gather_only holds ms per gather and GB/s into the root")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip config.end_to_end (three runs of the rt_launcher program, ~1 s each)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip config.end_to_end (three runs of the rt_launcher program, ~1 s each)")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--large-steps", type=int, default=4, help="frames of the second timed point (cat 7680x4320, BASELINE config 5) in the same run; 0 = skip")
+    ap.add_argument("--large-steps", type=int, default=4, help="--full: frames of the second timed point (cat 7680x4320, BASELINE config 5) in the same run; 0 = skip")
     ap.add_argument("--share-gpu", action="store_true",
                     help="TEST: every rank renders on GPU 0 and the exchange runs over gloo (RCCL refuses several ranks on one device); rehearses the N-rank path on a one-GPU box")
     ap.add_argument("--renderer", default="hip", choices=["hip", "oracle"],
@@ -101,6 +102,14 @@ def parse():
                          "the next starts.  Several ranks: see --batch")
     ap.add_argument("--dump-frame", default="", help="rank 0 saves the (gathered) float4 frame of the first step as .npy (tests)")
     ap.add_argument("--check-frame", action="store_true", help="rank 0 renders the whole frame alone as well and reports whether the gathered frame equals it bit for bit")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the frame the last timed step produced to DIR/frame.npy (float32 [H, W, C]: linear RGB + rays per pixel in .w, "
+                         "or the RGB8 image as float32 with --gather rgb8); a frame above 64 MB is written as a fixed, seeded sample of its pixels "
+                         "(DIR/frame_sample.npy + DIR/frame_sample_pixels.npy, the flat pixel indices as float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: roofline (counting runs, a single-stream context), the 7680x4320 point, one frame in flight, "
+                         "host frame timings, config.end_to_end, cpu_baseline (+ reference_check), and with N > 1 config.sides and config.frame_latency_ms.  "
+                         "A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     return ap.parse_args()
 
 
@@ -784,7 +793,7 @@ def main():
     sync()
     rays_per_frame = rays_of(main_pt)
     # traversal work of one frame from the counting instantiation of the kernel, rank 0
-    counts = ctx.count_work(main_pt.p, detail=True) if (rank == 0 and not cpu_only) else None
+    counts = ctx.count_work(main_pt.p, detail=True) if (args.full and rank == 0 and not cpu_only) else None
     if args.dump_frame and rank == 0:
         np.save(args.dump_frame, (main_pt.frame if world > 1 else main_pt.local[:H]).cpu().numpy())
     frame_ok = None
@@ -794,8 +803,10 @@ def main():
         frame_ok = bool((got.view(np.uint32) == full.view(np.uint32)).all())
 
     elapsed, kernel_ms_max = timed(main_pt, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_frame(main_pt, H, world, rank, tiling, args.root))
     sides = None
-    if world > 1 and not args.gather_only:
+    if args.full and world > 1 and not args.gather_only:
         # the same steps once more with one side only, outside the timed region (same lanes, same buffers; every rank takes part: the exchange is collective):
         # what the ranks' own shares cost (the compute side of the strong scaling) and what the gather costs when nothing is rendered beside it
         pw, args.prewarm_ms = args.prewarm_ms, 0
@@ -806,7 +817,7 @@ def main():
                  "is": "the timed steps again with the exchange skipped / with the render skipped (max over ranks, same frames in flight): the two sides of ms_per_step, which overlaps them"}
 
     latency_ms = None
-    if world > 1 and not args.gather_only and not cpu_only:
+    if args.full and world > 1 and not args.gather_only and not cpu_only:
         # what the throughput figure does not say: ONE frame alone on this rank's share (rendered, gathered, assembled, then the next) -- the latency of a frame.  With
         # frames batched or in flight side by side `ms_per_step` is the rate frames COMPLETE at; a single frame of a 1/8 share cannot fill the chip and takes longer than 1/8
         lat_pt = Point(W, H, lanes=1)
@@ -817,7 +828,7 @@ def main():
         del lat_pt
 
     large = None
-    if args.large_steps > 0 and args.scene == "cpu" and not cpu_only and (W, H) == (1920, 1080):
+    if args.full and args.large_steps > 0 and args.scene == "cpu" and not cpu_only and (W, H) == (1920, 1080):
         # BASELINE config 5's size in the same run (the >= 7x tile-scaling claim is feasible there; `value` stays the 1080p metric)
         lp = Point(7680, 4320)
         lp.step()
@@ -829,7 +840,7 @@ def main():
                  "frames_in_flight": lp.n_lanes}
         del lp
     one_in_flight_ms = None
-    if world == 1 and not cpu_only and main_pt.n_lanes > 1:           # the same frames with every frame joined before the next one starts
+    if args.full and world == 1 and not cpu_only and main_pt.n_lanes > 1:   # the same frames with every frame joined before the next one starts
         p1 = Point(W, H, lanes=1)
         e1, _ = timed(p1, args.steps, 2)
         one_in_flight_ms = round(1e3 * e1 / args.steps, 4)
@@ -849,8 +860,9 @@ def main():
                           "rays_per_frame": rays_per_frame, "ranks": dist.get_world_size() if world > 1 else 1,
                           "frames_in_flight": main_pt.n_lanes, "prewarm_ms": args.prewarm_ms,
                           **({"frames_in_flight_is": "frames alternate between two device buffers on one context and one stream; each of frame k+1's two sub-frames "
-                                                     "follows the same sub-frame of frame k without a join in between (rt_ctx_set_pipelining); every frame is rendered in full",
-                              "ms_per_step_one_frame_in_flight": one_in_flight_ms} if one_in_flight_ms is not None else {}),
+                                                     "follows the same sub-frame of frame k without a join in between (rt_ctx_set_pipelining); every frame is rendered in full"}
+                             if (world == 1 and not cpu_only and main_pt.n_lanes > 1) else {}),
+                          **({"ms_per_step_one_frame_in_flight": one_in_flight_ms} if one_in_flight_ms is not None else {}),
                           "tiling": f"{TILE_ROWS}-row tiles interleaved over {world} rank(s)"
                           + (f", one gather ({backend}) of the {'RGB8' if rgb8 else 'float4'} tiles to {'a rotating root' if rotate else 'rank 0'} per "
                              f"{'batch of ' + str(main_pt.batch) + ' frames' if getattr(main_pt, 'bx', False) else 'frame'}" if world > 1 else ""),
@@ -887,14 +899,14 @@ def main():
                                             "note": "render skipped inside the timed region on purpose: this line measures the exchange, not the metric"}
         if large:
             res["config"]["large"] = large
-        if world == 1 and not cpu_only:
+        if args.full and world == 1 and not cpu_only:
             res["config"].update(host_frame_timings(rt, ctx, main_pt.p, W, H))
             if args.scene == "cpu" and not args.no_end_to_end:
                 try:
                     res["config"]["end_to_end"] = end_to_end(args.cpu_threads or host_cores())
                 except Exception as e:  # a timing extra: never takes the line down
                     res["config"]["end_to_end"] = {"skipped": str(e)}
-        if world == 1 and not args.no_cpu_baseline and not cpu_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not cpu_only:
             try:
                 res["cpu_baseline"] = cpu_baseline(args, rays_per_frame)
             except Exception as e:  # the baseline must never take the GPU number down with it
@@ -906,6 +918,34 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES_MAX = 64 * 10**6     # --dump-outputs: at most this much in all
+
+
+def last_frame(pt, H, world, rank, tiling, root_policy):
+    """The frame the LAST timed step produced, on the rank that holds it (None elsewhere): one GPU -- the tiles of the lane that step rendered into;
+    N ranks -- the frame the step's root assembled (a batch's frames are the same frame: same camera, same seed)."""
+    if world == 1:
+        return pt.lanes[(pt.n - 1) % pt.n_lanes].local[:H]
+    last_root = tiling.root_of(pt.nb - 1 if getattr(pt, "bx", False) else pt.n - 1, world, root_policy)
+    return pt.frame if rank == last_root else None
+
+
+def dump_outputs(d, frame):
+    """--dump-outputs: DIR/frame.npy as float32, or -- above DUMP_BYTES_MAX -- a fixed sample of its pixels (seed 0, sorted) and their flat indices."""
+    if frame is None:
+        return
+    a = np.ascontiguousarray(frame.cpu().numpy()).astype(np.float32, copy=False)
+    os.makedirs(d, exist_ok=True)
+    if a.nbytes <= DUMP_BYTES_MAX:
+        np.save(os.path.join(d, "frame.npy"), a)
+        return
+    px = a.reshape(-1, a.shape[-1])
+    n = DUMP_BYTES_MAX // (px.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+    np.save(os.path.join(d, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(d, "frame_sample_pixels.npy"), idx.astype(np.float64))
 
 
 def host_frame_timings(rt, ctx, p, W, H):

@@ -190,12 +190,50 @@ def make_materials():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def obj_text(rng, n_v=2247, n_vn=2152, n_vt=2032, n_f=3954):
+    """An OBJ in the layout of the cat's exporter (comment header, mtllib, `v  x y z` with four decimals, vn / vt blocks, g / usemtl / s,
+    `f v/vt/vn v/vt/vn v/vt/vn ` with a trailing blank, CRLF line ends) with the cat's counts but seeded numbers and faces of our own."""
+    L = ["# Wavefront OBJ written by oracle/make_golden.py", "# the layout of a 3ds Max export", "", "mtllib synthetic.mtl", "", "#", "# object synthetic_001", "#", ""]
+    v = np.round(rng.uniform(-32.0, 32.0, (n_v, 3)), 4)
+    v[rng.integers(0, n_v, 40), rng.integers(0, 3, 40)] = 0.0             # exact zeros, printed as 0.0000 / -0.0000 below
+    L += ["v  %.4f %.4f %.4f" % tuple(r) for r in v]
+    L[len(L) - 20] = "v  %.4f %.4f %.4f" % (-0.0, 7.0, -0.0)
+    L += ["# %d vertices" % n_v, ""]
+    L += ["vn %.4f %.4f %.4f" % tuple(r) for r in np.round(rng.uniform(-1, 1, (n_vn, 3)), 4)] + ["# %d vertex normals" % n_vn, ""]
+    L += ["vt %.4f %.4f %.4f" % tuple(r) for r in np.round(rng.uniform(0, 1, (n_vt, 3)) * [1, 1, 0], 4)] + ["# %d texture coords" % n_vt, ""]
+    L += ["g synthetic_001", "usemtl synthetic", "s off"]
+    for _ in range(n_f):
+        vi = rng.choice(n_v, 3, replace=False) + 1
+        L.append("f " + " ".join("%d/%d/%d" % (a, rng.integers(1, n_vt + 1), rng.integers(1, n_vn + 1)) for a in vi) + " ")
+    L += ["# %d faces" % n_f, "", ""]
+    return "\r\n".join(L).encode()
+
+
+def make_obj():
+    """tests/golden/ref_obj.npz alone (`python oracle/make_golden.py obj`): a seeded OBJ in the cat's exporter layout (obj_text()) and what the reference's own
+    TriangleMesh::readOBJ makes of it (`ref_harness mesh` with that file where the reference looks for the cat): the OBJ reader tests need no asset from outside."""
+    text = obj_text(np.random.default_rng(20261016))
+    tmp = tempfile.mkdtemp(prefix="rt_golden_")
+    try:
+        od = os.path.join(tmp, "cadnav.com_model", "Models_F0202A090"); os.makedirs(od)
+        with open(os.path.join(od, "cat.obj"), "wb") as f:
+            f.write(text)
+        md = os.path.join(tmp, "mesh"); os.makedirs(md)
+        print(run([HARNESS, "mesh", md], tmp).strip())
+        np.savez_compressed(os.path.join(GOLD, "ref_obj.npz"), obj_text=np.frombuffer(text, np.uint8),
+                            vertices=f32(os.path.join(md, "vertices.f32"), 3), tri_obj_order=i32(os.path.join(md, "tri_obj_order.i32"), 3))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     if not (os.path.exists(CPU) and os.path.exists(HARNESS)):
         raise SystemExit("build the reference first: make -C oracle ref")
     os.makedirs(GOLD, exist_ok=True)
     if len(sys.argv) > 1 and sys.argv[1] == "materials":
         return make_materials()
+    if len(sys.argv) > 1 and sys.argv[1] == "obj":
+        return make_obj()
     tmp = tempfile.mkdtemp(prefix="rt_golden_")
     try:
         with_cat = os.path.join(tmp, "with_cat"); os.makedirs(with_cat)
@@ -269,6 +307,7 @@ def main():
                             cfg=np.array([W, H, spp, b, stride], np.int32))
         print("stat done")
         make_materials()
+        make_obj()
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     for fn in sorted(os.listdir(GOLD)):

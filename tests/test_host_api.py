@@ -8,8 +8,9 @@ import pytest
 
 from raytracinggpu_amd import hostlib
 
+from .conftest import load_golden
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_OBJ = "/root/reference/cadnav.com_model/Models_F0202A090/cat.obj"
 LAUNCHER = os.path.join(ROOT, "raytracinggpu_amd", "rt_launcher")
 
 
@@ -44,12 +45,15 @@ def test_rescaled_bvh_matches_oracle(oracle, cat_golden):
     np.testing.assert_array_equal(bits(m.bvh_arr10), bits(o.bvh_array()))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_OBJ), reason="reference asset not present (GPU box)")
-def test_obj_reader_matches_reference_parser(cat_golden):
-    m = hostlib.HostMesh.from_obj(REF_OBJ)
+def test_obj_reader_matches_reference_parser(tmp_path):
+    """An OBJ in the cat's exporter layout and counts (tests/golden/ref_obj.npz, seeded numbers): what the reference's readOBJ made of it."""
+    g = load_golden("ref_obj.npz")
+    p = tmp_path / "cat.obj"
+    p.write_bytes(g["obj_text"].tobytes())
+    m = hostlib.HostMesh.from_obj(str(p))
     assert m.status == 0
-    np.testing.assert_array_equal(bits(m.vertices), bits(cat_golden["vertices"]))
-    np.testing.assert_array_equal(m.indices10[:, :3], cat_golden["tri_obj_order"])
+    np.testing.assert_array_equal(bits(m.vertices), bits(g["vertices"]))
+    np.testing.assert_array_equal(m.indices10[:, :3], g["tri_obj_order"])
 
 
 def test_obj_reader_forms_match_oracle_parser(oracle, tmp_path):

@@ -194,7 +194,7 @@ def test_bench_refuses_more_ranks_than_gpus_with_a_clear_message():
 def test_bench_two_ranks_on_the_one_gpu_frame_equals_single_device_frame(tmp_path):
     """--share-gpu: both ranks render on GPU 0 through the HIP path, gloo moves the tiles; the line reports the ranks the process group
     saw and that the gathered frame is bitwise the frame one context renders alone."""
-    r, line = _bench("--gpus", "2", "--share-gpu", "--check-frame", "--width", "640", "--height", "356", "--steps", "2", "--warmup", "1", "--large-steps", "0")
+    r, line = _bench("--gpus", "2", "--share-gpu", "--check-frame", "--width", "640", "--height", "356", "--steps", "2", "--warmup", "1", "--large-steps", "0", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert line["n_gpus"] == 2 and line["config"]["ranks"] == 2 and line["config"]["frame_equals_single_device_frame"] is True
     assert line["value"] > 0 and "roofline" in line
@@ -208,6 +208,50 @@ def test_bench_two_ranks_on_the_one_gpu_frame_equals_single_device_frame(tmp_pat
     r, line = _bench("--gpus", "3", "--share-gpu", "--check-frame", "--root", "rotate", "--gather", "f32", "--width", "640", "--height", "356", "--steps", "7", "--warmup", "2", "--large-steps", "0")
     assert r.returncode == 0, r.stderr[-2000:]
     assert line["config"]["batch"] == 3 and line["steps"] == 7 and line["config"]["frame_equals_single_device_frame"] is True and "rank k mod N" in line["config"]["root"]
+
+
+def test_bench_dump_outputs_is_the_last_timed_frame_gloo_cpu(oracle, oracle_cat, tmp_path):
+    """--dump-outputs DIR: the frame of the LAST timed step as float32, written by the rank that assembled it (--root rotate, four frames
+    stepped: rank 1); a plain line carries the headline only, --full adds the one-side timings (config.sides)."""
+    W, H, b = 96, 50, 1
+    d = tmp_path / "out"
+    r, line = _bench("--gpus", "2", "--renderer", "oracle", "--root", "rotate", "--width", str(W), "--height", str(H), "--bounces", str(b), "--steps", "3", "--warmup", "0",
+                     "--dump-outputs", str(d))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert line["steps"] == 3 and "ms_per_step" in line and "sides" not in line["config"] and "roofline" not in line
+    assert sorted(os.listdir(d)) == ["frame.npy"]
+    got = np.load(d / "frame.npy")
+    exp, _, _ = oracle.Scene.preset("cpu", oracle_cat).render(W, H, 1, b, want_rgb8=False)
+    assert got.dtype == np.float32 and got.shape == (H, W, 4)
+    np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
+    r, line = _bench("--gpus", "2", "--renderer", "oracle", "--width", str(W), "--height", str(H), "--bounces", str(b), "--steps", "2", "--warmup", "0", "--full")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert line["config"]["sides"]["compute_ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_one_gpu_plain_line_and_dump_outputs(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline fields and nothing measured beside them; --dump-outputs writes the frame of the last
+    timed step (two frames in flight: the lane that step rendered into), bit for bit the frame one context renders alone."""
+    import raytracinggpu_amd as rt
+    W, H = 640, 356
+    d = tmp_path / "out"
+    r, line = _bench("--gpus", "1", "--width", str(W), "--height", str(H), "--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+    assert r.returncode == 0, r.stderr[-2000:]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"roofline", "cpu_baseline"} & set(line) and not {"large", "end_to_end", "ms_per_step_one_frame_in_flight"} & set(line["config"])
+    got = np.load(d / "frame.npy")
+    ctx = rt.Context(0)
+    from raytracinggpu_amd import hostlib
+    v, t = rt.scenes.load_cat_arrays()
+    ctx.scene_upload(rt.scenes.spheres("cpu"), hostlib.build_mesh(v, t, albedo=rt.scenes.CAT_ALBEDO, object_slot=rt.scenes.mesh_slot("cpu")))
+    exp = ctx.render(rt.make_params(W, H, 1, 3, **rt.scenes.CPU_LAUNCHER))
+    ctx.close()
+    assert got.dtype == np.float32 and got.shape == (H, W, 4)
+    np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
+    assert int(got[..., 3].sum()) == line["config"]["rays_per_frame"]
 
 
 def test_assemble_is_the_inverse_of_the_partition():

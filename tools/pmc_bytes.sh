@@ -16,7 +16,7 @@ python3 - <<P
 import json
 d=json.load(open("$out/pmc_wf_advance.json"))["derived"]; print({k: d[k] for k in d if "hbm" in k})
 P
-python3 bench.py --no-cpu-baseline --no-end-to-end --large-steps 0 > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --no-cpu-baseline --no-end-to-end --large-steps 0 > $out/bench.json 2> $out/bench.err
 python3 - <<P
 import json
 b=json.load(open("$out/bench.json")); print(b["value"], b["ms_per_step"], [(k["kernel"], k["kernel_ms"]) for k in b["roofline"]["kernels"]])

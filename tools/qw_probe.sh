@@ -6,7 +6,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -3 $out/pytest.log
 fi
 for rep in 1 2; do for q in 0 1; do
-  RT_TRAVQ_QW=$q RT_TRAVQ_QW_COUNT=$q timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-end-to-end --large-steps 0 --dump-frame $out/f$q.npy > $out/b$q.json 2> $out/b$q.err || { tail -3 $out/b$q.err; exit 1; }
+  RT_TRAVQ_QW=$q RT_TRAVQ_QW_COUNT=$q timeout -k 10 120 python3 bench.py --full --no-cpu-baseline --no-end-to-end --large-steps 0 --dump-frame $out/f$q.npy > $out/b$q.json 2> $out/b$q.err || { tail -3 $out/b$q.err; exit 1; }
   python3 - <<P
 import json; b=json.load(open("$out/b$q.json")); r=b["roofline"]; s=r.get("steps_per_frame",{})
 print("qw=$q", b["ms_per_step"], b["config"].get("ms_per_step_one_frame_in_flight"), [(k["kernel"], k["kernel_ms"]) for k in r["kernels"]], "box_steps", s.get("box_steps"), "tri_steps", s.get("tri_steps"), "serial", s.get("serial_drains"), "box occ", r.get("box_step_lane_occupancy"), "grid", b["config"].get("grid_blocks"))

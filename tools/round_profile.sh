@@ -25,7 +25,7 @@ for grp in \
 done
 python3 tools/pmc_summary.py $out "wf_travq<false" > $out/pmc_wf_travq.json
 python3 tools/pmc_summary.py $out "wf_advance<false, false>" > $out/pmc_wf_advance.json
-python3 bench.py --steps 30 --warmup 5 > $out/bench_n1.json 2> $out/bench_n1.err
+python3 bench.py --full --steps 30 --warmup 5 > $out/bench_n1.json 2> $out/bench_n1.err
 rm -rf $out/t1 $out/t2 $out/p[0-9]*
 head -6 $out/bench_kernel_stats.csv; head -6 $out/single_stream_kernel_stats.csv
 python3 -c "
