@@ -346,11 +346,14 @@ int refresh_host_mesh(rt_ctx *ctx) {
 }
 
 // Several TriangleMesh objects in one scene (cpu:538-564): ONE tree for the traversal kernels.  Every mesh keeps the tree its own buildBVH made; the roots hang below synthetic
-// internal nodes whose boxes are the unions of their children (exact: min / max of floats).  What this preserves:
+// internal nodes whose boxes hold their children's (below).  What this preserves:
 //   * a mesh's triangles are tested iff the reference's own walk of that mesh reaches their leaf: the reference enters a mesh iff its root box is hit (cpu:279) and the
-//     synthetic nodes above a root are entered whenever any root below them is -- BoundingBox::intersect is monotone along nested boxes: per axis the two plane parameters of
-//     the larger box bracket the smaller box's (one rounding each of a monotone expression), an axis with u = 0 constrains neither box or both alike (the origin lies strictly inside
-//     both intervals or the smaller box is missed), and a NaN on the first axis makes the smaller box a miss already;
+//     synthetic nodes above a root are entered whenever any root below them is.  A synthetic box is the union of its children's boxes -- each taken per axis as
+//     [min(lo, hi), max(lo, hi)], what the swap of cpu:153-155 makes of an inverted box -- WIDENED by one float step on every face.  Then BoundingBox::intersect is monotone
+//     from a child to its synthetic parent: for u != 0 the parent's two plane parameters per axis bracket the child's (one rounding each of a monotone expression); for u = +-0
+//     the origin lies on no face of the parent, so the parent's axis gives (-inf, +inf) whenever the child's is not a miss (origin strictly inside) or NaN (origin on a face
+//     of the child: a miss on the first axis, skipped by min_element / max_element on the others).  The exact union is NOT enough: a child flat on y or z, the origin on
+//     that plane and u = -0 there give the child NaN, NaN (skipped) but a parent that shares the plane as a face NaN, -inf -- a miss (tests/test_box_nesting.py);
 //   * the synthetic tree is shaped so that the traversal order (right child first, cpu:291-292) reaches the meshes in OBJECT order, hence the visit-order triangle array holds them
 //     mesh after mesh and min over (t, triangle index) = min over (t, object position, scan rank): the winner of the reference's loop over the objects with its strict '<' (cpu:554).
 // real[k]: index into `meshes` of the k-th mesh with triangles, in object order.  Fills the combined arrays and f.m (which points into them).
@@ -414,7 +417,10 @@ int build_forest(rt_ctx *ctx, const rt_mesh *meshes, const std::vector<int> &rea
     for (size_t q = post.size(); q-- > 0;) {                            // children before parents: a synthetic node's index is larger than its parent's
         float *o = f.arr.data() + (size_t)post[q].self * 10;
         const float *l = f.arr.data() + (size_t)(int)o[0] * 10, *r = f.arr.data() + (size_t)(int)o[1] * 10;
-        for (int c = 0; c < 3; ++c) { o[2 + c] = std::min(l[2 + c], r[2 + c]); o[5 + c] = std::max(l[5 + c], r[5 + c]); }
+        for (int c = 0; c < 3; ++c) {
+            const float mn = std::min(std::min(l[2 + c], l[5 + c]), std::min(r[2 + c], r[5 + c])), mx = std::max(std::max(l[2 + c], l[5 + c]), std::max(r[2 + c], r[5 + c]));
+            o[2 + c] = std::nextafter(mn, -INFINITY); o[5 + c] = std::nextafter(mx, INFINITY);   // one float step outwards: see above
+        }
     }
     f.m = rt_mesh{};
     f.m.vertices = f.verts.data(); f.m.n_vertices = (int)nv; f.m.indices = f.idx.data(); f.m.index_stride = 3; f.m.n_triangles = (int)nt;
