@@ -183,8 +183,9 @@ int rt_scene_upload(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres, const 
  * (cpu:279); inside the library the trees hang below synthetic nodes whose boxes are the unions of their children, the triangles
  * are stored mesh after mesh in object order, and one traversal finds the minimum over (t, object position, scan rank) -- the
  * result of the reference's loop over the objects.  A mesh without triangles stays an object that is never hit (missing OBJ,
- * cpu:322-325).  Every kernel variant renders such scenes.  With more than one mesh that has triangles the per-mesh operations -- rt_mesh_set_normals, rt_mesh_rebuild* --
- * are refused (RT_ERR_UNSUPPORTED); rt_mesh_transform moves them all. */
+ * cpu:322-325).  Every kernel variant renders such scenes.  With more than one mesh that has triangles the plain per-mesh operations -- rt_mesh_set_normals, rt_mesh_rebuild* --
+ * are refused (RT_ERR_UNSUPPORTED) and rt_mesh_transform moves them all; rt_mesh_transform_of / rt_mesh_set_normals_of / rt_mesh_rebuild_of (below) address ONE mesh by
+ * its object_slot. */
 int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres, const rt_mesh *meshes, int n_meshes,
                            const rt_light *light, const rt_camera *camera);
 
@@ -382,6 +383,22 @@ int rt_mesh_build_stats(const rt_ctx *ctx, rt_build_stats *out);
  *     pass &indices[0].ni and stride 10).  Call after rt_scene_upload (a new upload drops them); NULL = flat again.
  *     rt_mesh_transform then moves the normals the way the reference's kernel does.  Wavefront variants only. ---------- */
 int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles);
+
+/* --- the same for ONE mesh of the scene (ABI 6, additive): the reference's classes give every TriangleMesh in Scene::objects its own normals and its own tree
+ *     (cpu_launcher.cpp:190-224, :538-564) and its transformMesh moves the arrays of one mesh (global_launcher.cu:932-946).  object_slot = rt_mesh.object_slot
+ *     at upload (the mesh's position in Scene::objects).  On a scene with one mesh each equals its plain entry; on a forest of several meshes:
+ *       transform_of    the mesh's vertices (its smooth normals too, translation added), its triangle records, then a refit of the whole forest (the synthetic union
+ *                       nodes above the meshes' roots widened by one float step per face, as an upload makes them: the layout equals a fresh upload of the moved meshes);
+ *       set_normals_of  nidx rows in the mesh's own triangle order (as uploaded, or as its last rt_mesh_rebuild_of reported), normal indices into its own array;
+ *                       NULL arrays = that mesh flat again; the other meshes keep their shading;
+ *       rebuild_of      mode as rt_mesh_rebuild_mode, over the mesh's triangles and current vertices; bvh_arr10_out (capacity (2 * n + 2) * 10 floats, n = the mesh's
+ *                       triangles), tri_order_out[n] and n_nodes_out are in the mesh's own index space -- what buildBVH makes of that TriangleMesh; every other mesh
+ *                       keeps its tree, vertices and boxes as the device holds them; the forest is re-laid out on the host (no device-side install).
+ *     RT_ERR_INVALID: object_slot outside the scene or a sphere's (scene unchanged).  A mesh without triangles: RT_OK, nothing happens.  RT_ERR_NO_SCENE: no upload,
+ *     or the last rt_scene_upload* failed.  Failures as the plain entries: a build error leaves the scene as it was. ------------------------------------------ */
+int rt_mesh_transform_of(rt_ctx *ctx, int object_slot, const float rotation[9], const float translation[3]);
+int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles);
+int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out);
 
 /* --- posed camera + progressive accumulation: the headless form of realtime_render.cu.  Camera
  *     {C, yaw, pitch} with Camera::rotate() (realtime_render.cu:803-861); ray generation and per-sample averaging of its

@@ -531,6 +531,30 @@ public:
                                   (int)(sizeof(TriangleIndices) / sizeof(int32_t)), (int)mesh.indices.size()), "rt_mesh_set_normals");
     }
     void use_flat_normals() { check(rt_mesh_set_normals(ctx_, nullptr, 0, nullptr, 3, 0), "rt_mesh_set_normals"); }
+    // The same for ONE TriangleMesh of the scene, found by its Geometry::id (its position in Scene::objects = rt_mesh.object_slot): the other meshes stay as they are
+    void transform_mesh_of(const TriangleMesh &mesh, const float rotation[9], const Vector &translation) {
+        const float t[3] = {translation[0], translation[1], translation[2]};
+        check(rt_mesh_transform_of(ctx_, mesh.id, rotation, t), "rt_mesh_transform_of");
+    }
+    void use_smooth_normals_of(const TriangleMesh &mesh) {
+        std::vector<float> n(mesh.normals.size() * 3);
+        for (size_t i = 0; i < mesh.normals.size(); ++i)
+            for (int k = 0; k < 3; ++k) n[3 * i + k] = mesh.normals[i][k];
+        check(rt_mesh_set_normals_of(ctx_, mesh.id, n.data(), (int)mesh.normals.size(), mesh.indices.empty() ? nullptr : &mesh.indices[0].ni,
+                                     (int)(sizeof(TriangleIndices) / sizeof(int32_t)), (int)mesh.indices.size()), "rt_mesh_set_normals_of");
+    }
+    void use_flat_normals_of(const TriangleMesh &mesh) { check(rt_mesh_set_normals_of(ctx_, mesh.id, nullptr, 0, nullptr, 3, 0), "rt_mesh_set_normals_of"); }
+    // buildBVH of that mesh on the device (mode: rt_bvh_mode): bvhTreeToArray's nodes in the mesh's own index space; *order (optional): position -> its triangle before the call
+    std::vector<float> rebuild_mesh_of(const TriangleMesh &mesh, int mode = RT_BVH_REFERENCE, std::vector<int32_t> *order = nullptr) {
+        const size_t nt = mesh.indices.size();
+        std::vector<float> arr((2 * nt + 2) * 10);
+        std::vector<int32_t> ord(nt);
+        int32_t n_nodes = 0;
+        check(rt_mesh_rebuild_of(ctx_, mesh.id, mode, arr.data(), ord.data(), &n_nodes), "rt_mesh_rebuild_of");
+        arr.resize((size_t)n_nodes * 10);
+        if (order) *order = std::move(ord);
+        return arr;
+    }
     // Camera{C, yaw, pitch} (realtime_render.cu:803-861) and disp() (:1243-1290) without the window: one accumulated frame
     std::vector<unsigned char> progressive_frame(const RenderSettings &s, const rt_camera_pose &pose, std::vector<float> *display = nullptr) {
         rt_params p = params(s);

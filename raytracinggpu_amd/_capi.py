@@ -25,7 +25,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_progressive_frames",
            "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_scene_upload_meshes", "rt_render_multi",
            "rt_render_multi_device", "rt_render_multi_rgb8", "rt_multi_get_stats",
-           "rt_stats_enable", "rt_ctx_set_pipelining", "rt_render_async", "rt_wait", "rt_trace_rays", "rt_mesh_rebuild", "rt_mesh_rebuild_mode", "rt_mesh_build_stats", "rt_host_alloc", "rt_host_free", "rt_device_alloc", "rt_device_free", "rt_device_to_host", "rt_kat_sphere", "rt_kat_sqrt", "rt_kat_box", "rt_kat_triangle", "rt_kat_mesh", "rt_kat_layout_hash"]
+           "rt_stats_enable", "rt_ctx_set_pipelining", "rt_render_async", "rt_wait", "rt_trace_rays", "rt_mesh_rebuild", "rt_mesh_rebuild_mode", "rt_mesh_build_stats", "rt_host_alloc", "rt_host_free", "rt_device_alloc", "rt_device_free", "rt_device_to_host", "rt_kat_sphere", "rt_kat_sqrt", "rt_kat_box", "rt_kat_triangle", "rt_kat_mesh", "rt_kat_layout_hash",
+           "rt_mesh_transform_of", "rt_mesh_set_normals_of", "rt_mesh_rebuild_of"]
 MAX_DEVICES = 16
 
 
@@ -189,6 +190,9 @@ def load():
     L.rt_mesh_rebuild.argtypes = [vp, fp3, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rt_mesh_rebuild_mode.argtypes = [vp, C.c_int, fp3, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rt_mesh_build_stats.argtypes = [vp, C.POINTER(BuildStats)]
+    L.rt_mesh_transform_of.argtypes = [vp, C.c_int, fp3, fp3]
+    L.rt_mesh_set_normals_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int]
+    L.rt_mesh_rebuild_of.argtypes = [vp, C.c_int, C.c_int, fp3, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_host_free.argtypes = [vp]
     L.rt_kat_sphere.argtypes = [vp, fp3, C.c_int, fp3]
@@ -421,19 +425,29 @@ class Context:
                                 (int(v) for v in w.steps)))
         return out
 
-    def mesh_transform(self, rotation, translation):
-        """Device-side `transform` kernel (global_launcher.cu:340-365) on the uploaded mesh + triangle precompute + BVH refit."""
+    def mesh_transform(self, rotation, translation, object_slot=None):
+        """Device-side `transform` kernel (global_launcher.cu:340-365) on the uploaded mesh + triangle precompute + BVH refit.
+        object_slot: move only the mesh at that position in Scene::objects (rt_mesh_transform_of); None = every mesh (rt_mesh_transform)."""
         r = np.ascontiguousarray(rotation, np.float32).reshape(9)
         t = np.ascontiguousarray(translation, np.float32).reshape(3)
-        self._check(self._L.rt_mesh_transform(self._h, r.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_float))))
+        rp, tp = r.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_float))
+        if object_slot is None:
+            self._check(self._L.rt_mesh_transform(self._h, rp, tp))
+        else:
+            self._check(self._L.rt_mesh_transform_of(self._h, int(object_slot), rp, tp))
 
-    def mesh_rebuild(self, n_triangles, mode="reference"):
+    def mesh_rebuild(self, n_triangles, mode="reference", object_slot=None):
         """Device-side BVH build over the uploaded triangles and the current device vertices -> (bvh_arr10 [n_nodes, 10], order [n_triangles]).
-        mode "reference": TriangleMesh::buildBVH bit for bit; "lbvh": Morton sort + parallel hierarchy, leaves cut by the surface-area heuristic (at most 32 triangles)."""
+        mode "reference": TriangleMesh::buildBVH bit for bit; "lbvh": Morton sort + parallel hierarchy, leaves cut by the surface-area heuristic (at most 32 triangles).
+        object_slot: rebuild only the mesh at that position (rt_mesh_rebuild_of); n_triangles is then that mesh's count and the outputs are in its own index space."""
         arr = np.zeros(((2 * n_triangles + 2), 10), np.float32)
         order = np.zeros(n_triangles, np.int32)
         n = C.c_int32(0)
-        self._check(self._L.rt_mesh_rebuild_mode(self._h, BVH_MODES[mode], arr.ctypes.data_as(C.POINTER(C.c_float)), order.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        ap, op = arr.ctypes.data_as(C.POINTER(C.c_float)), order.ctypes.data_as(C.POINTER(C.c_int32))
+        if object_slot is None:
+            self._check(self._L.rt_mesh_rebuild_mode(self._h, BVH_MODES[mode], ap, op, C.byref(n)))
+        else:
+            self._check(self._L.rt_mesh_rebuild_of(self._h, int(object_slot), BVH_MODES[mode], ap, op, C.byref(n)))
         return arr[:n.value].copy(), order
 
     def build_stats(self):
@@ -441,15 +455,22 @@ class Context:
         self._check(self._L.rt_mesh_build_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in BuildStats._fields_}
 
-    def mesh_set_normals(self, normals, nidx):
-        """Smooth shading: vertex normals + per-triangle (ni, nj, nk) rows in the order of the uploaded indices; None = flat."""
+    def mesh_set_normals(self, normals, nidx, object_slot=None):
+        """Smooth shading: vertex normals + per-triangle (ni, nj, nk) rows in the order of the uploaded indices; None = flat.
+        object_slot: only the mesh at that position, rows in its own triangle order (rt_mesh_set_normals_of); None = the scene's one mesh."""
         if normals is None:
-            self._check(self._L.rt_mesh_set_normals(self._h, None, 0, None, 3, 0))
+            if object_slot is None:
+                self._check(self._L.rt_mesh_set_normals(self._h, None, 0, None, 3, 0))
+            else:
+                self._check(self._L.rt_mesh_set_normals_of(self._h, int(object_slot), None, 0, None, 3, 0))
             return
         n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
         ix = np.ascontiguousarray(nidx, np.int32).reshape(-1, 3)
-        self._check(self._L.rt_mesh_set_normals(self._h, n.ctypes.data_as(C.POINTER(C.c_float)), len(n),
-                                                ix.ctypes.data_as(C.POINTER(C.c_int32)), 3, len(ix)))
+        np_, ip = n.ctypes.data_as(C.POINTER(C.c_float)), ix.ctypes.data_as(C.POINTER(C.c_int32))
+        if object_slot is None:
+            self._check(self._L.rt_mesh_set_normals(self._h, np_, len(n), ip, 3, len(ix)))
+        else:
+            self._check(self._L.rt_mesh_set_normals_of(self._h, int(object_slot), np_, len(n), ip, 3, len(ix)))
 
     def render_pose(self, params, pose):
         """One frame with realtime_render.cu's posed camera and per-sample averaging (no accumulation)."""

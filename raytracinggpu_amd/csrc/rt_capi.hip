@@ -132,6 +132,7 @@ int rt_device_name(const rt_ctx *ctx, char *buf, size_t buflen) {
 int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres, const rt_mesh *meshes, int n_meshes,
                            const rt_light *light, const rt_camera *camera) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    ctx->parts_valid = false;                                            // (the per-mesh records describe the scene this call installs, or none)
     if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(ctx, RT_ERR_INVALID, "bad sphere array");
     if (n_meshes < 0 || (n_meshes > 0 && !meshes)) return fail(ctx, RT_ERR_INVALID, "bad mesh array");
     if (!light || !camera) return fail(ctx, RT_ERR_INVALID, "light/camera is NULL");
@@ -177,10 +178,13 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     std::vector<int> real;                                               // meshes with something to traverse, in object order
     for (int k = 0; k < n_meshes; ++k) if (meshes[order[k]].n_triangles > 0 && meshes[order[k]].n_nodes > 0) real.push_back(order[k]);
     int rc;
+    std::vector<rt_ctx::MeshPart> parts;
     if (real.size() <= 1) {
         // the reference's own scenes: one mesh (or none; a mesh without triangles is an object that is never hit, cpu:322-325)
         const rt_mesh *one = real.empty() ? (n_meshes > 0 ? &meshes[order[0]] : nullptr) : &meshes[real[0]];
         rc = install_scene(ctx, sc, one);
+        if (!real.empty()) parts.push_back({one->object_slot, 0, one->n_vertices, 0, one->n_triangles, 0, one->n_nodes, false});
+        ctx->forest_arr.clear();
     } else {
         Forest f;
         if ((rc = build_forest(ctx, meshes, real, f)) != RT_OK) return rc;
@@ -190,9 +194,18 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
             if (r >= 0 && order[k] == real[r]) { offs[k] = f.tri_off[r]; --r; }
             else offs[k] = offs[k + 1];
         }
-        rc = install_scene(ctx, sc, &f.m, &offs);
+        rc = install_scene(ctx, sc, &f.m, &offs, (int)real.size() - 1);
+        for (size_t k = 0; k < real.size(); ++k) {
+            const rt_mesh &m = meshes[real[k]];
+            parts.push_back({m.object_slot, f.voff[k], m.n_vertices, f.tri_off[k], m.n_triangles, f.noff[k], m.n_nodes, false});
+        }
+        ctx->forest_arr = std::move(f.arr);
     }
-    if (rc == RT_OK) { ctx->n_real_meshes = (int)real.size(); ctx->real_obj = real.empty() ? -1 : meshes[real[0]].object_slot; }
+    if (rc == RT_OK) {
+        ctx->n_real_meshes = (int)real.size(); ctx->real_obj = real.empty() ? -1 : meshes[real[0]].object_slot;
+        ctx->parts = std::move(parts);
+        ctx->parts_valid = true;
+    }
     pc.lap("rt_scene_upload (layouts, hipMalloc, copies)");
     return rc;
 }

@@ -135,7 +135,21 @@ struct rt_ctx {
     bool q16_topo_ok = false;                                       // the tree's shape allows them (leaf sizes, node count, boxes nest)
     bool qw_topo_ok = false;                                        // ... and no leaf is empty: places 0 and 2 of a quad must hold a node (the pairs cope with an empty leaf)
     int real_obj = -1;                                              // object position of the (first) mesh with triangles, -1 = none
-    int n_real_meshes = 0;                                          // meshes WITH triangles in the scene: with more than one the tree in use is a forest (build_forest) and the per-mesh operations are refused
+    int n_real_meshes = 0;                                          // meshes WITH triangles in the scene: with more than one the tree in use is a forest (build_forest) and the plain per-mesh operations are refused (the *_of entries address one mesh)
+    // The per-mesh entries (rt_mesh_*_of): one record per mesh with triangles, in object order.  Filled only by an upload (or a rebuild) that returned RT_OK and
+    // invalidated at the top of every rt_scene_upload*: after a failed upload the entries answer RT_ERR_NO_SCENE instead of acting on the previous scene's ranges.
+    struct MeshPart {
+        int obj;                                                    // object slot (position in Scene::objects)
+        int voff, nv;                                               // vertex range in `verts`
+        int tri_off, nt;                                            // triangle range in the uploaded order (tidx_up, up_indices)
+        int noff, nn;                                               // node range in forest_arr (bvh_arr10 indices)
+        bool smooth;                                                // its entries of `nrm` are set (rt_mesh_set_normals_of)
+    };
+    std::vector<MeshPart> parts;
+    bool parts_valid = false;
+    std::vector<float> forest_arr;                                  // the forest's bvh_arr10 as installed (build_forest): topology and triangle ranges of every mesh (boxes: see pre_of)
+    std::vector<int> pre_of;                                        // forest_arr index -> pre-order index of the same node on the device (node_lo / node_hi hold its current box)
+    int n_syn = 0, syn[rtk::kMaxSynthetic] = {};                    // the forest's synthetic union nodes (pre-order indices): refit_kernel widens them as build_forest does
     DevBuf node_lo, node_hi, nodes2, nodesq, nodesb, q2thr, tri, verts, tidx, scratch_rgba, scratch_rgb8, work, queue;
     int n_cus = 0;
     DevBuf wfM, wfT, wfLS, wfSID, wfSamp;                     // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)

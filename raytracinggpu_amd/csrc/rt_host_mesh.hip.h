@@ -1,6 +1,60 @@
 // rt_host_mesh.hip.h -- host side, part 4 of 4 (inside rt_capi.hip's extern "C" block): the entry points that change the uploaded mesh on the device -- smooth normals,
-// transform + refit, rebuild of the reference's tree, the LBVH builder and its device-side install.
+// transform + refit, rebuild of the reference's tree, the LBVH builder and its device-side install; and the same for ONE mesh of a forest (rt_mesh_*_of).
 #pragma once
+
+// Every node box recomputed for the tree in use (refit_kernel: the forest's synthetic nodes widened as build_forest makes them), the root box and the box filter's
+// scene-wide quantities fetched, the fixed-point nodes derived again.  A whole-forest pass: the quantisation grid hangs on the root box.
+static int refit_and_requantize(rt_ctx *ctx) {
+    rtk::Scene &sc = ctx->scene;
+    rtk::RefitArgs a{};
+    a.node_lo = static_cast<float4 *>(ctx->node_lo.p); a.node_hi = static_cast<float4 *>(ctx->node_hi.p);
+    a.nodes2 = static_cast<float4 *>(ctx->nodes2.p); a.nodesq = static_cast<float4 *>(ctx->nodesq.p); a.nodesb = static_cast<float4 *>(ctx->nodesb.p);
+    a.q2thr = static_cast<const int *>(ctx->q2thr.p); a.left_of = static_cast<const int *>(ctx->left_dev.p);
+    a.lvl_nodes = static_cast<const int *>(ctx->lvl_nodes.p); a.lvl_off = static_cast<const int *>(ctx->lvl_off.p);
+    a.tidx = static_cast<const int4 *>(ctx->tidx.p); a.verts = static_cast<const float4 *>(ctx->verts.p);
+    a.n_nodes = sc.n_nodes; a.n_levels = ctx->n_levels;
+    a.n_syn = ctx->n_syn;
+    for (int k = 0; k < ctx->n_syn; ++k) a.syn[k] = ctx->syn[k];
+    hipLaunchKernelGGL(rtk::refit_kernel, dim3(1), dim3(1024), 0, own_stream(ctx), a);
+    RT_HIP(ctx, hipGetLastError());
+    // the root box travels as a kernel argument (uniform root-box pre-test): fetch the refitted one
+    float4 root[2];
+    RT_HIP(ctx, hipMemcpyAsync(&root[0], ctx->node_lo.p, sizeof(float4), hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipMemcpyAsync(&root[1], ctx->node_hi.p, sizeof(float4), hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    sc.root_lo = root[0]; sc.root_hi = root[1];
+    // the refitted root box contains every node's (unions, bottom-up): it bounds the magnitudes wf_travq's box filter needs
+    const float rv[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
+    bool fast = true;
+    float bm[3];
+    for (int k = 0; k < 3; ++k) {
+        if (!(rv[k] <= rv[k + 3]) || !(std::fabs(rv[k]) < 1e8f) || !(std::fabs(rv[k + 3]) < 1e8f)) fast = false;
+        bm[k] = std::max(std::fabs(rv[k]), std::fabs(rv[k + 3]));
+    }
+    sc.bmx = bm[0]; sc.bmy = bm[1]; sc.bmz = bm[2];
+    sc.fast_box = fast ? 1 : 0;
+    return requantize(ctx, own_stream(ctx));                                          // the fixed-point pairs follow the refitted boxes (same topology: q16_topo_ok stands; unions nest)
+}
+
+// The per-mesh entries' common prologue: the record of the mesh at object_slot -- nullptr for a mesh without triangles, which the entries accept as a no-op.
+static int find_part(rt_ctx *ctx, int object_slot, rt_ctx::MeshPart *&part) {
+    part = nullptr;
+    if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
+    const rtk::Scene &sc = ctx->scene;
+    if (object_slot < 0 || object_slot >= sc.n_objects) return fail(ctx, RT_ERR_INVALID, "object_slot %d outside [0,%d)", object_slot, sc.n_objects);
+    bool mesh = false;
+    for (int k = 0; k < sc.n_meshes; ++k) mesh = mesh || sc.mesh[k].obj == object_slot;
+    if (!mesh) return fail(ctx, RT_ERR_INVALID, "object_slot %d holds a sphere, not a TriangleMesh", object_slot);
+    for (rt_ctx::MeshPart &p : ctx->parts) if (p.obj == object_slot) part = &p;
+    return RT_OK;
+}
+
+// [vb, ve): the triangles (visit order) of the mesh at object position obj -- the forest stores them mesh after mesh (rtk::MeshRec)
+static void visit_range(const rtk::Scene &sc, int obj, int &vb, int &ve) {
+    vb = ve = 0;
+    for (int k = 0; k < sc.n_meshes; ++k)
+        if (sc.mesh[k].obj == obj) { vb = sc.mesh[k].tri_begin; ve = k + 1 < sc.n_meshes ? sc.mesh[k + 1].tri_begin : sc.n_tris; }
+}
 
 int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
@@ -8,7 +62,11 @@ int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, co
     if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    if (!normals_xyz || !nidx) { ctx->scene.nrm = nullptr; return RT_OK; }          // back to flat shading
+    if (!normals_xyz || !nidx) {                                                  // back to flat shading (every mesh)
+        ctx->scene.nrm = nullptr; ctx->scene.smooth_mask = 0;
+        for (rt_ctx::MeshPart &p : ctx->parts) p.smooth = false;
+        return RT_OK;
+    }
     if (ctx->n_real_meshes > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: smooth normals are set for ONE TriangleMesh", ctx->n_real_meshes);
     if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
     if (ctx->scene.mesh_slot < 0) return fail(ctx, RT_ERR_INVALID, "the scene has no mesh");
@@ -26,6 +84,8 @@ int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, co
     int rc = upload(ctx, ctx->nrm, nr.data(), nr.size() * sizeof(float4));
     if (rc != RT_OK) return rc;
     ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
+    ctx->scene.smooth_mask = ctx->real_obj >= 0 ? 1 << ctx->real_obj : 0;             // the scene's one mesh
+    for (rt_ctx::MeshPart &p : ctx->parts) p.smooth = true;
     return RT_OK;
 }
 
@@ -47,36 +107,12 @@ int rt_mesh_transform(rt_ctx *ctx, const float rotation[9], const float translat
                            static_cast<float4 *>(ctx->nrm.p), 3 * sc.n_tris, m);
     hipLaunchKernelGGL(rtk::retri_kernel, dim3((unsigned)((sc.n_tris + 255) / 256)), dim3(256), 0, own_stream(ctx),
                        static_cast<const int4 *>(ctx->tidx.p), static_cast<const float4 *>(ctx->verts.p), static_cast<float4 *>(ctx->tri.p), sc.n_tris);
-    rtk::RefitArgs a{};
-    a.node_lo = static_cast<float4 *>(ctx->node_lo.p); a.node_hi = static_cast<float4 *>(ctx->node_hi.p);
-    a.nodes2 = static_cast<float4 *>(ctx->nodes2.p); a.nodesq = static_cast<float4 *>(ctx->nodesq.p); a.nodesb = static_cast<float4 *>(ctx->nodesb.p);
-    a.q2thr = static_cast<const int *>(ctx->q2thr.p); a.left_of = static_cast<const int *>(ctx->left_dev.p);
-    a.lvl_nodes = static_cast<const int *>(ctx->lvl_nodes.p); a.lvl_off = static_cast<const int *>(ctx->lvl_off.p);
-    a.tidx = static_cast<const int4 *>(ctx->tidx.p); a.verts = static_cast<const float4 *>(ctx->verts.p);
-    a.n_nodes = sc.n_nodes; a.n_levels = ctx->n_levels;
-    hipLaunchKernelGGL(rtk::refit_kernel, dim3(1), dim3(1024), 0, own_stream(ctx), a);
-    RT_HIP(ctx, hipGetLastError());
-    // the root box travels as a kernel argument (uniform root-box pre-test): fetch the refitted one
-    float4 root[2];
-    RT_HIP(ctx, hipMemcpyAsync(&root[0], ctx->node_lo.p, sizeof(float4), hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipMemcpyAsync(&root[1], ctx->node_hi.p, sizeof(float4), hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    sc.root_lo = root[0]; sc.root_hi = root[1];
-    // the refitted root box contains every node's (unions, bottom-up): it bounds the magnitudes wf_travq's box filter needs
-    const float rv[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
-    bool fast = true;
-    float bm[3];
-    for (int a = 0; a < 3; ++a) {
-        if (!(rv[a] <= rv[a + 3]) || !(std::fabs(rv[a]) < 1e8f) || !(std::fabs(rv[a + 3]) < 1e8f)) fast = false;
-        bm[a] = std::max(std::fabs(rv[a]), std::fabs(rv[a + 3]));
-    }
-    sc.bmx = bm[0]; sc.bmy = bm[1]; sc.bmz = bm[2];
-    sc.fast_box = fast ? 1 : 0;
-    return requantize(ctx, own_stream(ctx));                                          // the fixed-point pairs follow the refitted boxes (same topology: q16_topo_ok stands; unions nest)
+    return refit_and_requantize(ctx);
 }
 
 // TriangleMesh::buildBVH on the device, bit for bit (rt_bvhbuild.hip.h): leaves the flat tree in ctx->bb_arr and the triangle order in ctx->bb_idx
-static int rebuild_reference_tree(rt_ctx *ctx, const int nt, int &n_nodes_out) {
+// (up_off: the mesh's first triangle in tidx_up -- a forest's member; its vertex indices are global, the outputs are local to the mesh)
+static int rebuild_reference_tree(rt_ctx *ctx, const int nt, int &n_nodes_out, const int up_off = 0) {
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t cap = 2 * (size_t)nt + 2;                                          // nodes: every split makes two
     int rc;
@@ -88,7 +124,7 @@ static int rebuild_reference_tree(rt_ctx *ctx, const int nt, int &n_nodes_out) {
         (rc = ensure(ctx, ctx->bb_pre, cap * sizeof(int))) != RT_OK || (rc = ensure(ctx, ctx->bb_arr, cap * 10 * sizeof(float))) != RT_OK)
         return rc;
     rtk::BuildArgs a{};
-    a.verts = static_cast<const float4 *>(ctx->verts.p); a.tidx_up = static_cast<const int4 *>(ctx->tidx_up.p);
+    a.verts = static_cast<const float4 *>(ctx->verts.p); a.tidx_up = static_cast<const int4 *>(ctx->tidx_up.p) + up_off;
     a.idx = static_cast<int *>(ctx->bb_idx.p); a.cnt = static_cast<int *>(ctx->bb_cnt.p);
     a.ptr_a = static_cast<int *>(ctx->bb_pa.p); a.ptr_b = static_cast<int *>(ctx->bb_pb.p); a.tmp = static_cast<int *>(ctx->bb_tmp.p);
     int *ni = static_cast<int *>(ctx->bb_nodes_i.p);
@@ -129,7 +165,7 @@ static int rebuild_reference_tree(rt_ctx *ctx, const int nt, int &n_nodes_out) {
 }
 
 // The LBVH builder (rt_lbvh.hip.h): Morton sort + parallel hierarchy emission, leaves cut by the surface-area heuristic (at most kLbvhLeaf = 32 triangles); same outputs
-static int rebuild_lbvh_tree(rt_ctx *ctx, const int nt, int &n_nodes_out) {
+static int rebuild_lbvh_tree(rt_ctx *ctx, const int nt, int &n_nodes_out, const int up_off = 0) {
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t q = own_stream(ctx);
     const size_t n = (size_t)nt, nc = 2 * n - 1;
@@ -156,7 +192,7 @@ static int rebuild_lbvh_tree(rt_ctx *ctx, const int nt, int &n_nodes_out) {
     // the leaf cut's triangle cost: kLbvhCt (wf_travq's step times on 64-byte pairs) for small trees; 1.0 for trees that will use the 32-byte fixed-point pairs, where a box test is
     // cheaper still but a triangle's 48-byte gather is not (swept on 524 288 / 2 M triangles: Ct 1.0 / 1.6 / 2.5 / 4 / 8 = 2.77 / 2.84 / 2.99 / 3.04 / 3.06 and 8.21 / 8.40 / 8.72 / 8.73 / 8.80 ms per frame)
     a.ct = ctx->knobs.lbvh_ct > 0.f ? ctx->knobs.lbvh_ct : (nt >= kQ16AutoNodes ? 1.0f : rtk::kLbvhCt); a.cb = rtk::kLbvhCb;
-    a.verts = static_cast<const float4 *>(ctx->verts.p); a.tidx_up = static_cast<const int4 *>(ctx->tidx_up.p); a.n = nt;
+    a.verts = static_cast<const float4 *>(ctx->verts.p); a.tidx_up = static_cast<const int4 *>(ctx->tidx_up.p) + up_off; a.n = nt;
     a.bounds = reinterpret_cast<unsigned int *>(base + o_small); a.stats = reinterpret_cast<int *>(base + o_small + 32);
     a.keys = reinterpret_cast<unsigned long long *>(base + o_keys); a.vals = reinterpret_cast<int *>(base + o_vals);
     a.left = reinterpret_cast<int *>(base + o_left); a.right = reinterpret_cast<int *>(base + o_right); a.parent = reinterpret_cast<int *>(base + o_parent);
@@ -280,7 +316,8 @@ static int install_lbvh_device(rt_ctx *ctx, const rtk::Scene &old, const int n_n
     if ((rc = upload(ctx, ctx->lvl_off, lvl_off.data(), lvl_off.size() * sizeof(int))) != RT_OK) return rc;
     ctx->n_levels = maxd + 1;
     rtk::Scene sc = old;
-    sc.nrm = nullptr;
+    sc.nrm = nullptr; sc.smooth_mask = 0;
+    ctx->n_syn = 0;                                                              // (one mesh: no synthetic nodes)
     sc.n_nodes = n_nodes; sc.n_tris = (int)n;
     mesh_table_single(sc, ctx->real_obj);
     sc.root_lo = root[0]; sc.root_hi = root[1];
@@ -392,6 +429,200 @@ int rt_mesh_rebuild_mode(rt_ctx *ctx, int mode, float *bvh_arr10_out, int32_t *t
 
 int rt_mesh_rebuild(rt_ctx *ctx, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
     return rt_mesh_rebuild_mode(ctx, RT_BVH_REFERENCE, bvh_arr10_out, tri_order_out, n_nodes_out);
+}
+
+// ---- ONE mesh of the scene, addressed by its object slot (the reference's TriangleMesh in Scene::objects: its own vertices, normals and tree).  On a scene with one
+// mesh these are the plain entries; on a forest they act on the mesh's ranges and leave every other mesh as the device holds it.
+
+int rt_mesh_transform_of(rt_ctx *ctx, int object_slot, const float rotation[9], const float translation[3]) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!rotation || !translation) return fail(ctx, RT_ERR_INVALID, "rotation/translation is NULL");
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!p) return RT_OK;                                                           // a mesh without triangles: nothing to move
+    if (ctx->n_real_meshes <= 1) return rt_mesh_transform(ctx, rotation, translation);
+    rtk::Scene &sc = ctx->scene;
+    int vb, ve;
+    visit_range(sc, object_slot, vb, ve);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    rtk::Mat3 m;
+    for (int k = 0; k < 9; ++k) m.r[k] = rotation[k];
+    for (int k = 0; k < 3; ++k) m.t[k] = translation[k];
+    hipStream_t q = own_stream(ctx);
+    // the reference's transformMesh on this mesh's arrays (global_launcher.cu:932-946): its vertices, its normals (translation added, global_launcher.cu:357-363), its triangle records
+    hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((p->nv + 255) / 256)), dim3(256), 0, q, static_cast<float4 *>(ctx->verts.p) + p->voff, p->nv, m);
+    if (ve > vb) {
+        if (p->smooth && sc.nrm != nullptr)
+            hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((3 * (ve - vb) + 255) / 256)), dim3(256), 0, q, static_cast<float4 *>(ctx->nrm.p) + 3 * (size_t)vb, 3 * (ve - vb), m);
+        hipLaunchKernelGGL(rtk::retri_kernel, dim3((unsigned)((ve - vb + 255) / 256)), dim3(256), 0, q,
+                           static_cast<const int4 *>(ctx->tidx.p) + vb, static_cast<const float4 *>(ctx->verts.p), static_cast<float4 *>(ctx->tri.p) + 3 * (size_t)vb, ve - vb);
+    }
+    RT_HIP(ctx, hipGetLastError());
+    return refit_and_requantize(ctx);
+}
+
+int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!p) return RT_OK;
+    if (ctx->n_real_meshes <= 1) return rt_mesh_set_normals(ctx, normals_xyz, n_normals, nidx, index_stride, n_triangles);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    rtk::Scene &sc = ctx->scene;
+    const int bit = 1 << object_slot;
+    if (!normals_xyz || !nidx) {                                                    // this mesh flat again
+        p->smooth = false;
+        sc.smooth_mask &= ~bit;
+        if (sc.smooth_mask == 0) sc.nrm = nullptr;                                  // no smooth mesh left: the frames take the flat branch as before
+        return RT_OK;
+    }
+    if (n_normals <= 0 || index_stride < 3) return fail(ctx, RT_ERR_INVALID, "bad normal array sizes");
+    if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
+    int vb, ve;
+    visit_range(sc, object_slot, vb, ve);
+    std::vector<float4> nr(3 * (size_t)(ve - vb));
+    for (int t = vb; t < ve; ++t) {
+        const int src = ctx->tri_perm[t] - p->tri_off;                              // the mesh's own triangle index, uploaded order
+        if (src < 0 || src >= p->nt) return fail(ctx, RT_ERR_INTERNAL, "forest layout: visit rank %d is not a triangle of object %d", t, object_slot);
+        if (src >= n_triangles) return fail(ctx, RT_ERR_INVALID, "n_triangles %d does not cover the mesh at object_slot %d (%d triangles)", n_triangles, object_slot, p->nt);
+        for (int k = 0; k < 3; ++k) {
+            const int ni = nidx[(size_t)src * index_stride + k];
+            if (ni < 0 || ni >= n_normals) return fail(ctx, RT_ERR_INVALID, "triangle %d references normal %d outside [0,%d)", src, ni, n_normals);
+            nr[3 * (size_t)(t - vb) + k] = make_float4(normals_xyz[3 * (size_t)ni], normals_xyz[3 * (size_t)ni + 1], normals_xyz[3 * (size_t)ni + 2], 0.f);
+        }
+    }
+    // one buffer for the forest (3 normals per triangle, visit order); the entries of a flat mesh are never read
+    const size_t bytes = 3 * (size_t)sc.n_tris * sizeof(float4);
+    if (sc.nrm == nullptr) {
+        if (int rc = ensure(ctx, ctx->nrm, bytes); rc != RT_OK) return rc;
+        RT_HIP(ctx, hipMemset(ctx->nrm.p, 0, bytes));
+    }
+    if (!nr.empty()) RT_HIP(ctx, hipMemcpy(static_cast<float4 *>(ctx->nrm.p) + 3 * (size_t)vb, nr.data(), nr.size() * sizeof(float4), hipMemcpyHostToDevice));
+    p->smooth = true;
+    sc.smooth_mask |= bit;
+    sc.nrm = static_cast<const float4 *>(ctx->nrm.p);
+    return RT_OK;
+}
+
+int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (mode != RT_BVH_REFERENCE && mode != RT_BVH_LBVH) return fail(ctx, RT_ERR_INVALID, "unknown BVH mode %d", mode);
+    rt_ctx::MeshPart *pp = nullptr;
+    if (int rc = find_part(ctx, object_slot, pp); rc != RT_OK) return rc;
+    if (n_nodes_out) *n_nodes_out = 0;
+    if (!pp) return RT_OK;                                                          // a mesh without triangles: nothing to build
+    if (ctx->n_real_meshes <= 1) return rt_mesh_rebuild_mode(ctx, mode, bvh_arr10_out, tri_order_out, n_nodes_out);
+    const rt_ctx::MeshPart P = *pp;
+    const std::vector<rt_ctx::MeshPart> parts = ctx->parts;
+    const rtk::Scene old = ctx->scene;
+    const int K = (int)parts.size();
+    if (ctx->forest_arr.size() != (size_t)old.n_nodes * 10 || ctx->pre_of.size() != (size_t)old.n_nodes || K != ctx->n_real_meshes)
+        return fail(ctx, RT_ERR_INTERNAL, "forest records do not match the tree in use");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t q = own_stream(ctx);
+    int rc;
+    int n_nodes = 0;
+    ctx->build = rt_build_stats{};
+    hipEvent_t e0 = ctx->ev_t0, e1 = ctx->ev_t1;                                    // (the tone-mapping events are free here: nothing else runs on the stream)
+    RT_HIP(ctx, hipEventRecord(e0, q));
+    // this mesh's triangles only (tidx_up + tri_off); the builders read the vertices as they are on the device now
+    if (mode == RT_BVH_LBVH && P.nt > 4) rc = rebuild_lbvh_tree(ctx, P.nt, n_nodes, P.tri_off);
+    else { mode = RT_BVH_REFERENCE; rc = rebuild_reference_tree(ctx, P.nt, n_nodes, P.tri_off); }
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipEventRecord(e1, q));
+    RT_HIP(ctx, hipEventSynchronize(e1));
+    RT_HIP(ctx, hipEventElapsedTime(&ctx->build.device_build_ms, e0, e1));
+    ctx->have_tonemap_time = false;
+    ctx->build.mode = mode; ctx->build.n_nodes = n_nodes; ctx->build.n_triangles = P.nt;
+    const auto t_install = std::chrono::steady_clock::now();
+    if ((rc = refresh_host_mesh(ctx)) != RT_OK) return rc;
+    // what the device holds: the new tree and order, every vertex, every node box (the other meshes keep theirs: refitted or as uploaded), the normals
+    std::vector<float> arr((size_t)n_nodes * 10);
+    std::vector<int> order(P.nt);
+    std::vector<float4> hv(old.n_verts), nlo(old.n_nodes), nhi(old.n_nodes), old_nrm;
+    RT_HIP(ctx, hipMemcpyAsync(arr.data(), ctx->bb_arr.p, arr.size() * sizeof(float), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipMemcpyAsync(order.data(), ctx->bb_idx.p, order.size() * sizeof(int), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipMemcpyAsync(hv.data(), ctx->verts.p, hv.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipMemcpyAsync(nlo.data(), ctx->node_lo.p, nlo.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipMemcpyAsync(nhi.data(), ctx->node_hi.p, nhi.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
+    if (old.nrm != nullptr) {
+        old_nrm.resize((size_t)old.n_tris * 3);
+        RT_HIP(ctx, hipMemcpyAsync(old_nrm.data(), ctx->nrm.p, old_nrm.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
+    }
+    RT_HIP(ctx, hipStreamSynchronize(q));
+    // every mesh in its own index space, in object order, as build_forest takes them from rt_scene_upload_meshes
+    std::vector<std::vector<float>> vx(K), ar(K);
+    std::vector<std::vector<int32_t>> ix(K);
+    std::vector<rt_mesh> ms(K);
+    std::vector<int> real(K);
+    for (int k = 0; k < K; ++k) {
+        const rt_ctx::MeshPart &Q = parts[k];
+        const bool me = Q.obj == P.obj;
+        vx[k].resize((size_t)Q.nv * 3);
+        for (int i = 0; i < Q.nv; ++i) { const float4 v = hv[(size_t)Q.voff + i]; vx[k][3 * (size_t)i] = v.x; vx[k][3 * (size_t)i + 1] = v.y; vx[k][3 * (size_t)i + 2] = v.z; }
+        ix[k].resize((size_t)Q.nt * 3);
+        for (int t = 0; t < Q.nt; ++t) {
+            const int src = me ? order[t] : t;                                      // the rebuilt mesh: its triangles in the builder's order
+            for (int c = 0; c < 3; ++c) ix[k][3 * (size_t)t + c] = ctx->up_indices[3 * ((size_t)Q.tri_off + src) + c] - Q.voff;
+        }
+        if (me) {
+            ar[k] = arr;
+        } else {                                                                    // its tree as installed, the boxes the device holds now
+            ar[k].resize((size_t)Q.nn * 10);
+            for (int n = 0; n < Q.nn; ++n) {
+                const float *a = ctx->forest_arr.data() + ((size_t)Q.noff + n) * 10;
+                float *o = ar[k].data() + (size_t)n * 10;
+                const int x = ctx->pre_of[(size_t)Q.noff + n];
+                o[0] = a[0] == -1.f ? -1.f : (float)((int)a[0] - Q.noff); o[1] = a[1] == -1.f ? -1.f : (float)((int)a[1] - Q.noff);
+                o[2] = nlo[x].x; o[3] = nlo[x].y; o[4] = nlo[x].z; o[5] = nhi[x].x; o[6] = nhi[x].y; o[7] = nhi[x].z;
+                o[8] = (float)((int)a[8] - Q.tri_off); o[9] = (float)((int)a[9] - Q.tri_off);
+            }
+        }
+        rt_mesh &m = ms[k];
+        m = rt_mesh{};
+        m.vertices = vx[k].data(); m.n_vertices = Q.nv; m.indices = ix[k].data(); m.index_stride = 3; m.n_triangles = Q.nt;
+        m.bvh_arr10 = ar[k].data(); m.n_nodes = (int)(ar[k].size() / 10);
+        m.object_slot = Q.obj;                                                      // (albedo and material stay in the scene's mesh table, which `sc` carries over)
+        real[k] = k;
+    }
+    Forest f;
+    if ((rc = build_forest(ctx, ms.data(), real, f)) != RT_OK) return rc;
+    std::vector<int> offs(old.n_meshes + 1, f.tri_off[K]);                         // as rt_scene_upload_meshes: table entry -> first triangle (a mesh without triangles: the next real one's)
+    for (int k = old.n_meshes - 1, r = K - 1; k >= 0; --k) {
+        if (r >= 0 && old.mesh[k].obj == parts[r].obj) { offs[k] = f.tri_off[r]; --r; }
+        else offs[k] = offs[k + 1];
+    }
+    const std::vector<int> old_perm = ctx->tri_perm;                               // old visit order -> old uploaded order
+    rtk::Scene sc = old;
+    sc.n_nodes = sc.n_tris = sc.n_verts = 0; sc.nrm = nullptr;
+    ctx->parts_valid = false;
+    if ((rc = install_scene(ctx, sc, &f.m, &offs, K - 1)) != RT_OK) return rc;
+    ctx->parts = parts;                                                             // vertex and triangle ranges keep their sizes; the rebuilt mesh's node count changes
+    for (int k = 0; k < K; ++k) { ctx->parts[k].noff = f.noff[k]; ctx->parts[k].nn = ms[k].n_nodes; }
+    ctx->forest_arr = std::move(f.arr);
+    ctx->parts_valid = true;
+    if (!old_nrm.empty()) {                                                        // smooth normals travel with their triangles, every mesh's
+        std::vector<int> old_visit_of(ctx->n_up_tris, -1);
+        for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
+        std::vector<float4> nn(ctx->tri_perm.size() * 3, make_float4(0, 0, 0, 0));
+        for (size_t t = 0; t < ctx->tri_perm.size(); ++t) {
+            const int g = ctx->tri_perm[t];
+            const int g_old = g >= P.tri_off && g < P.tri_off + P.nt ? P.tri_off + order[g - P.tri_off] : g;
+            const int ov = old_visit_of[g_old];
+            for (int k = 0; k < 3; ++k) if (ov >= 0) nn[3 * t + k] = old_nrm[3 * (size_t)ov + k];
+        }
+        if ((rc = upload(ctx, ctx->nrm, nn.data(), nn.size() * sizeof(float4))) != RT_OK) return rc;
+        ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
+    }
+    if (bvh_arr10_out) memcpy(bvh_arr10_out, arr.data(), arr.size() * sizeof(float));
+    if (tri_order_out) memcpy(tri_order_out, order.data(), order.size() * sizeof(int));
+    if (n_nodes_out) *n_nodes_out = n_nodes;
+    ctx->build.install_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_install).count();
+    return RT_OK;
 }
 
 int rt_mesh_build_stats(const rt_ctx *ctx, rt_build_stats *out) {

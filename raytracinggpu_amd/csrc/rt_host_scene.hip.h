@@ -13,10 +13,12 @@ inline h3 hcross(h3 a, h3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * 
 // Converts the reference's bvhTreeToArray layout (optimized.cu:512-534) into traversal order.
 // The reference pops the right child first (cpu:291-292 push left then right), so the
 // pre-order here descends right before left.
+// pre_of (optional): bvh_arr10 index -> traversal-order index.
 int build_threaded(rt_ctx *ctx, const rt_mesh *m, std::vector<float4> &lo, std::vector<float4> &hi, std::vector<int> &perm,
-                   std::vector<int> &left_of) {
+                   std::vector<int> &left_of, std::vector<int> *pre_of = nullptr) {
     const int n = m->n_nodes;
     perm.clear();
+    if (pre_of) pre_of->assign(n, -1);
     left_of.assign(n, -1);                                        // internal nodes: traversal-order index of the LEFT child
     lo.assign(n, make_float4(0, 0, 0, 0));
     hi.assign(n, make_float4(0, 0, 0, 0));
@@ -34,6 +36,7 @@ int build_threaded(rt_ctx *ctx, const rt_mesh *m, std::vector<float4> &lo, std::
             if (seen[it.ref]) return fail(ctx, RT_ERR_INVALID, "bvh_arr10: node %d reached twice (not a tree)", it.ref);
             seen[it.ref] = 1;
             it.out = emitted++;
+            if (pre_of) (*pre_of)[it.ref] = it.out;
             const int left = (int)a[0], right = (int)a[1];
             const int ts = (int)a[8], te = (int)a[9];
             if (ts < 0 || te < ts || te > m->n_triangles)
@@ -135,14 +138,16 @@ void mesh_table_single(rtk::Scene &sc, int real_obj) {
 
 // sc: spheres (with their object ids), light, camera and the mesh table (object ids, materials; sc.mesh_slot = the first mesh object's position or -1) filled in by the caller.
 // mesh: the geometry to traverse -- one TriangleMesh as uploaded, or the forest build_forest made of several (tri_offsets[k] = first triangle of table entry k in mesh->indices,
-// n_meshes + 1 entries) -- or nullptr.
-int install_scene(rt_ctx *ctx, rtk::Scene sc, const rt_mesh *mesh, const std::vector<int> *tri_offsets = nullptr) {
+// n_meshes + 1 entries; its first n_syn nodes are the synthetic union nodes) -- or nullptr.
+int install_scene(rt_ctx *ctx, rtk::Scene sc, const rt_mesh *mesh, const std::vector<int> *tri_offsets = nullptr, int n_syn = 0) {
     PhaseClock pc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->stream_) RT_HIP(ctx, hipStreamSynchronize(ctx->stream_));   // (renders issued on a caller's stream are the caller's to order)
     ctx->have_scene = false;
     ctx->host_mesh_stale = false;                                     // what follows rewrites tri_perm / up_indices
     ctx->tri_perm.clear();
+    ctx->n_syn = 0;
+    ctx->pre_of.clear();
     std::vector<float4> lo, hi, tri, verts;
     std::vector<int4> tidx;
     std::vector<int> left_of;
@@ -155,8 +160,11 @@ int install_scene(rt_ctx *ctx, rtk::Scene sc, const rt_mesh *mesh, const std::ve
             return fail(ctx, RT_ERR_INVALID, "mesh array pointer is NULL");
         if (mesh->n_nodes >= (1 << 24)) return fail(ctx, RT_ERR_INVALID, "node indices are stored as floats: < 2^24 nodes");
         std::vector<int> perm;
-        int rc = build_threaded(ctx, mesh, lo, hi, perm, left_of);
+        int rc = build_threaded(ctx, mesh, lo, hi, perm, left_of, tri_offsets ? &ctx->pre_of : nullptr);
         if (rc != RT_OK) return rc;
+        if (n_syn < 0 || n_syn > rtk::kMaxSynthetic || n_syn > mesh->n_nodes) return fail(ctx, RT_ERR_INTERNAL, "forest with %d synthetic nodes", n_syn);
+        for (int k = 0; tri_offsets && k < n_syn; ++k) ctx->syn[k] = ctx->pre_of[k];   // (build_forest puts them first)
+        ctx->n_syn = tri_offsets ? n_syn : 0;
         if (perm.size() >= ((size_t)1 << 31)) return fail(ctx, RT_ERR_INVALID, "too many leaf triangles");
         for (int t = 0; t < mesh->n_triangles; ++t) {
             const int32_t *ix = mesh->indices + (size_t)t * mesh->index_stride;
@@ -361,6 +369,7 @@ struct Forest {
     std::vector<float> verts, arr;
     std::vector<int32_t> idx;
     std::vector<int> tri_off;                                           // per real mesh: first triangle in idx (+ the total at the end)
+    std::vector<int> voff, noff;                                        // ... first vertex in verts, first node in arr (+ the totals)
     rt_mesh m{};
 };
 int build_forest(rt_ctx *ctx, const rt_mesh *meshes, const std::vector<int> &real, Forest &f) {
@@ -426,6 +435,7 @@ int build_forest(rt_ctx *ctx, const rt_mesh *meshes, const std::vector<int> &rea
     f.m.vertices = f.verts.data(); f.m.n_vertices = (int)nv; f.m.indices = f.idx.data(); f.m.index_stride = 3; f.m.n_triangles = (int)nt;
     f.m.bvh_arr10 = f.arr.data(); f.m.n_nodes = (int)nn;
     f.m.object_slot = meshes[real[0]].object_slot;
+    f.voff = voff; f.noff = noff;
     return RT_OK;
 }
 

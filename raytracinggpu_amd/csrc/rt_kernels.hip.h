@@ -86,6 +86,7 @@ struct Scene {
     const float4 *verts;
     const int4 *tidx;
     int n_nodes, n_tris, n_verts;
+    int smooth_mask;          // bit k: object k (a mesh) shades with nrm; the others keep the flat normal (fills the padding in front of root_lo: the struct's size is unchanged)
     float4 root_lo, root_hi;   // node 0 again, as kernel arguments (SGPRs) for the uniform root-box pre-test
 };
 

@@ -8,6 +8,9 @@
 //                     compute_bbox of its triangles (cpu:180-188: INF-initialised std::min / std::max), an internal
 //                     node's box the union of its children's, which is compute_bbox of its whole range.  One workgroup
 //                     walks the levels bottom-up (the tree has a few thousand nodes; this is a step before the hot path).
+//                     The synthetic union nodes of a forest (rt_host_scene.hip.h build_forest) are recomputed the way
+//                     build_forest makes them: per axis the min / max over both children's lo AND hi, then one float
+//                     step outwards on every face -- so a refitted forest is laid out as a fresh upload of the moved meshes.
 // The reference never refits (its transform variant has no BVH and buildBVH runs once on the host); rebuilding on the
 // host after a transform remains possible through rt_scene_upload.
 #pragma once
@@ -40,13 +43,33 @@ __global__ __launch_bounds__(256) void retri_kernel(const int4 *__restrict__ tid
     tri[3 * (size_t)t + 2] = make_float4(e2.z, N.x, N.y, N.z);
 }
 
+constexpr int kMaxSynthetic = kMaxMeshes - 1;               // a forest of K <= 16 meshes has K - 1 synthetic nodes
+
 struct RefitArgs {
     float4 *node_lo, *node_hi, *nodes2, *nodesq, *nodesb;   // the node layouts (pre-order SoA, pre-order interleaved, breadth-first as boxes and as centre / half extent)
     const int *q2thr, *left_of, *lvl_nodes, *lvl_off;
     const int4 *tidx;
     const float4 *verts;
     int n_nodes, n_levels;
+    int n_syn;                                              // the forest's synthetic nodes (pre-order indices); 0 for one mesh
+    int syn[kMaxSynthetic];
 };
+
+// std::nextafter(x, -inf) / (x, +inf) on the bits (no denormal flush can touch them): what build_forest does on the host
+__device__ __forceinline__ float step_down(float x) {
+    if (x != x || x == -INFINITY) return x;
+    if (x == 0.f) return __int_as_float((int)0x80000001);
+    const int b = __float_as_int(x);
+    return __int_as_float(x > 0.f ? b - 1 : b + 1);
+}
+__device__ __forceinline__ float step_up(float x) {
+    if (x != x || x == INFINITY) return x;
+    if (x == 0.f) return __int_as_float(1);
+    const int b = __float_as_int(x);
+    return __int_as_float(x > 0.f ? b + 1 : b - 1);
+}
+__device__ __forceinline__ float fmin_std(float a, float b) { return b < a ? b : a; }   // std::min
+__device__ __forceinline__ float fmax_std(float a, float b) { return a < b ? b : a; }   // std::max
 
 __global__ __launch_bounds__(1024) void refit_kernel(const RefitArgs a) {
     for (int L = a.n_levels - 1; L >= 0; --L) {
@@ -67,6 +90,16 @@ __global__ __launch_bounds__(1024) void refit_kernel(const RefitArgs a) {
                 }
             } else {                                                   // internal: children x + 1 and left_of[x] (one level down: done)
                 const int c[2] = {x + 1, a.left_of[x]};
+                bool syn = false;
+                for (int j = 0; j < a.n_syn; ++j) syn |= a.syn[j] == x;
+                if (syn) {                                             // build_forest's union: min / max over lo and hi of the left child, then of the right one; one step outwards
+                    const float4 l0 = a.node_lo[c[1]], h0 = a.node_hi[c[1]], l1 = a.node_lo[c[0]], h1 = a.node_hi[c[0]];
+                    lo.x = step_down(fmin_std(fmin_std(l0.x, h0.x), fmin_std(l1.x, h1.x))); hi.x = step_up(fmax_std(fmax_std(l0.x, h0.x), fmax_std(l1.x, h1.x)));
+                    lo.y = step_down(fmin_std(fmin_std(l0.y, h0.y), fmin_std(l1.y, h1.y))); hi.y = step_up(fmax_std(fmax_std(l0.y, h0.y), fmax_std(l1.y, h1.y)));
+                    lo.z = step_down(fmin_std(fmin_std(l0.z, h0.z), fmin_std(l1.z, h1.z))); hi.z = step_up(fmax_std(fmax_std(l0.z, h0.z), fmax_std(l1.z, h1.z)));
+                    a.node_lo[x] = lo; a.node_hi[x] = hi;
+                    continue;
+                }
                 for (int j = 0; j < 2; ++j) {
                     const float4 cl = a.node_lo[c[j]], ch = a.node_hi[c[j]];
                     mn.x = cl.x < mn.x ? cl.x : mn.x; mn.y = cl.y < mn.y ? cl.y : mn.y; mn.z = cl.z < mn.z ? cl.z : mn.z;

@@ -632,7 +632,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             if (win >= 0) {                                           // a miss is black (cpu:571): nothing to emit
                 const f3 P = O + t_min * u;                           // cpu:560
                 f3 N;
-                if (tri_win >= 0 && sc.nrm != nullptr) {              // get_smooth_normal, realtime_render.cu:221-245
+                if (tri_win >= 0 && sc.nrm != nullptr && ((sc.smooth_mask >> win) & 1)) {              // get_smooth_normal (of a smooth mesh), realtime_render.cu:221-245
                     const float4 q0 = sc.tri[3 * tri_win], q1 = sc.tri[3 * tri_win + 1], q2 = sc.tri[3 * tri_win + 2];
                     const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x), Nt = mk(q2.y, q2.z, q2.w);
                     const float beta = dot(e2, cross(A - O, u)) / dot(u, Nt);

@@ -1,0 +1,338 @@
+"""ONE mesh of a multi-mesh scene moved, shaded smooth or rebuilt (rt_mesh_transform_of / rt_mesh_set_normals_of / rt_mesh_rebuild_of) against the CPU oracle, which keeps
+every TriangleMesh of Scene::objects with its own vertices, normals and tree (cpu_launcher.cpp:190-224, :538-564).  -m gpu.
+
+The scene is two_cats of tests/material_scenes.py: a diffuse cat at object slot 3 and a smaller mirror cat at slot 7 among six walls.  sigma == 0: flat frames are
+compared bit for bit in every channel, smooth ones as test_gpu_parity.py test_smooth_normals compares them."""
+import numpy as np
+import pytest
+
+import raytracinggpu_amd as rt
+from . import material_scenes as ms
+from .test_gpu_parity import TOL, linf, values_equal
+from .test_gpu_tree_shapes import _forest_rays
+
+pytestmark = pytest.mark.gpu
+
+A, B = 3, 7                                                             # the two cats' object slots
+W, H = 320, 200
+R1 = np.array([[0.9553365, 0, 0.29552022], [0, 1, 0], [-0.29552022, 0, 0.9553365]], np.float32)
+T1 = (0.5, 0.25, -0.5)
+c, s = np.float32(np.cos(1.1)), np.float32(np.sin(1.1))
+R2 = np.array([[1, 0, 0], [0, c, -s], [0, s, c]], np.float32)          # a strong rotation about x
+T2 = (-2.0, 1.5, 3.0)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c_ = rt.Context(0)
+    yield c_
+    c_.close()
+
+
+def _frames_equal(got, exp):
+    np.testing.assert_array_equal(got[..., :3].view(np.uint32), exp[..., :3].view(np.uint32))
+    np.testing.assert_array_equal(got[..., 3], exp[..., 3])
+
+
+def _params(b, variant="auto", n=1):
+    return rt.make_params(W, H, n, b, variant=variant, **rt.scenes.CPU_LAUNCHER)
+
+
+def _vertex_normals(v, t):
+    """per-vertex normals as test_gpu_parity.py test_smooth_normals computes them"""
+    v = np.asarray(v, np.float64)
+    fn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    vn = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(vn, t[:, k], fn)
+    return (vn / np.maximum(np.linalg.norm(vn, axis=1, keepdims=True), 1e-20)).astype(np.float32)
+
+
+def _setup(cat_golden):
+    v, t = cat_golden["vertices"], cat_golden["tri_obj_order"]
+    spheres, meshes = ms.capi_scene("two_cats", v, t)
+    return v, t, spheres, meshes
+
+
+def _oracle(oracle, v, t, ops=None, normals=()):
+    """two_cats in the oracle; ops[slot] = callables applied to that mesh after its build (transform / refit / build_bvh / set_bvh); normals: slots shaded smooth
+    (normals set before the build, as the device receives them in the uploaded order)"""
+    ops = ops or {}
+    osc, oms = oracle.Scene(), {}
+    for pos, o in enumerate(ms.describe("two_cats", v)):
+        if o[0] == "sphere":
+            osc.add_sphere(o[1], o[2], o[3])
+            continue
+        m = oracle.Mesh.from_arrays(o[1], t, albedo=o[2]).set_material(o[3], o[4], o[5])
+        if pos in normals:
+            m.set_normals(_vertex_normals(o[1], np.asarray(t)), t)
+        m.build_bvh()
+        for op in ops.get(pos, ()):
+            op(m)
+        osc.add_mesh(m)
+        oms[pos] = m
+    return osc, oms
+
+
+def _moved(R, T):
+    return lambda m: m.transform(R, T).refit()
+
+
+def _fresh_hashes(oracle, spheres, meshes, oms):
+    """layout hashes of a fresh upload of the oracle's meshes as they are now (vertices, triangle order, boxes)"""
+    fresh = []
+    for d in meshes:
+        om = oms[d["object_slot"]]
+        fresh.append(dict(d, vertices=om.vertices, indices=om.triangles, bvh_arr10=om.bvh_array()))
+    c_ = rt.Context(0)
+    try:
+        c_.scene_upload(spheres, fresh)
+        return c_.layout_hash(), c_
+    except Exception:
+        c_.close()
+        raise
+
+
+def _check_rays(ctx, oracle, oms, seed):
+    """rt_trace_rays through the forest in use (meshes only) against the oracle's loop over the same meshes: hit, P = O + t u and N bit for bit -- camera-like rays,
+    axis-parallel ones, +-0 components, origins on the union box's faces and on the meshes' lowest planes"""
+    osc = oracle.Scene()
+    for om in oms:
+        osc.add_mesh(om)
+    members = [dict(vertices=om.vertices) for om in oms]
+    allv = np.concatenate([m["vertices"] for m in members])
+    planes = [(a, float(m["vertices"][:, a].min())) for m in members for a in range(3)]
+    rays = _forest_rays(np.random.default_rng(seed), members, planes, n=4000 + 100 * len(planes))
+    assert np.isfinite(allv).all()
+    exp = [osc.intersect_all(rays[i, :3], rays[i, 3:], 1e-4) for i in range(len(rays))]
+    eh = np.array([e[0] for e in exp])
+    eP = np.array([e[2] for e in exp], np.float32)
+    eN = np.array([e[3] for e in exp], np.float32)
+    assert eh.sum() >= 50 and (~eh).sum() >= 50
+    for variant in ("wavefront_queue", "path", "wavefront"):
+        got = ctx.trace_rays(rays, 1e-4, variant)
+        gP = (rays[:, :3] + (got[:, 1:2] * rays[:, 3:]).astype(np.float32)).astype(np.float32)
+        bad = np.flatnonzero(((got[:, 0] != 0) != eh) | (eh & ((gP.view(np.uint32) != eP.view(np.uint32)).any(1) | (got[:, 2:5].view(np.uint32) != eN.view(np.uint32)).any(1))))
+        assert len(bad) == 0, (variant, len(bad), rays[bad[:3]].tolist())
+
+
+def test_transform_one_mesh_equals_the_oracle(ctx, oracle, cat_golden):
+    """each cat moved alone: frames of b = 0 and 2 through auto / wavefront / path / lockstep bit for bit, the work counts, the 4-wide step; then the other cat moved too"""
+    v, t, spheres, meshes = _setup(cat_golden)
+    for slot in (A, B):
+        ctx.scene_upload(spheres, meshes)
+        ctx.mesh_transform(R1, T1, object_slot=slot)
+        osc, _ = _oracle(oracle, v, t, {slot: [_moved(R1, T1)]})
+        for b in (0, 2):
+            exp, _, cnt = osc.render(W, H, 1, b, want_rgb8=False)
+            for variant in ("auto", "wavefront", "path", "lockstep"):
+                _frames_equal(ctx.render(_params(b, variant)), exp)
+            work = ctx.count_work(_params(b))
+            assert work["rays"] == cnt["rays"] and work["tri_tests"] == cnt["tri_tests"], (slot, b)
+        assert ctx.stats_after_render(_params(1))["travq_mode"] == 2
+        other = B if slot == A else A                                   # the second move composes with the first
+        ctx.mesh_transform(R2, T2, object_slot=other)
+        osc2, _ = _oracle(oracle, v, t, {slot: [_moved(R1, T1)], other: [_moved(R2, T2)]})
+        for b in (0, 2):
+            exp, _, _ = osc2.render(W, H, 1, b, want_rgb8=False)
+            _frames_equal(ctx.render(_params(b)), exp)
+
+
+def test_refit_keeps_the_unions_widened(ctx, oracle, cat_golden):
+    """after a per-mesh or an all-mesh transform the device layout equals a fresh upload of the moved forest (the synthetic nodes one float step wider than the union
+    of their children, as build_forest makes them); one-mesh scenes: transform_of is the plain entry; rays through the moved forest bit for bit"""
+    v, t, spheres, meshes = _setup(cat_golden)
+    ctx.scene_upload(spheres, meshes)
+    ctx.mesh_transform(R1, T1, object_slot=A)
+    _, oms = _oracle(oracle, v, t, {A: [_moved(R1, T1)]})
+    want, fresh = _fresh_hashes(oracle, spheres, meshes, oms)
+    try:
+        assert ctx.layout_hash() == want
+        _frames_equal(ctx.render(_params(2)), fresh.render(_params(2)))
+    finally:
+        fresh.close()
+    # the plain entry on the forest: every mesh moves, the unions stay widened
+    ctx.scene_upload(spheres, meshes)
+    ctx.mesh_transform(R2, T2)
+    _, oms = _oracle(oracle, v, t, {A: [_moved(R2, T2)], B: [_moved(R2, T2)]})
+    want, fresh = _fresh_hashes(oracle, spheres, meshes, oms)
+    fresh.close()
+    assert ctx.layout_hash() == want
+    # rays through a forest moved mesh by mesh: hit, P and N bit for bit against the oracle's loop over the meshes (axis-parallel, +-0 components, origins on faces)
+    ctx.scene_upload([], [dict(m, object_slot=j) for j, m in enumerate(meshes)])   # (the meshes alone: A at 0, B at 1)
+    ctx.mesh_transform(R1, T1, object_slot=0)
+    ctx.mesh_transform(R2, T2, object_slot=1)
+    _, oms = _oracle(oracle, v, t, {A: [_moved(R1, T1)], B: [_moved(R2, T2)]})
+    _check_rays(ctx, oracle, [oms[A], oms[B]], 61)
+    # a scene with one mesh: the per-mesh entry is the plain one
+    one = [d for d in meshes if d["object_slot"] == A]
+    ctx.scene_upload(spheres, one)
+    ctx.mesh_transform(R2, T2, object_slot=A)
+    h_of, f_of = ctx.layout_hash(), ctx.render(_params(2))
+    ctx.scene_upload(spheres, one)
+    ctx.mesh_transform(R2, T2)
+    assert ctx.layout_hash() == h_of
+    _frames_equal(ctx.render(_params(2)), f_of)
+
+
+def test_smooth_normals_on_one_mesh(ctx, oracle, cat_golden):
+    """smooth shading on one cat, then on the other, then on both: direct lighting bit for bit, two bounces within TOL, the ray counts equal; lockstep refused;
+    the moved normals of a moved cat; flat again gives back the flat frame"""
+    v, t, spheres, meshes = _setup(cat_golden)
+    by_slot = {d["object_slot"]: d for d in meshes}
+    ctx.scene_upload(spheres, meshes)
+    flat = ctx.render(_params(0))
+
+    def set_smooth(slot):
+        d = by_slot[slot]
+        ctx.mesh_set_normals(_vertex_normals(d["vertices"], np.asarray(t)), d["indices"][:, :3], object_slot=slot)
+
+    for slots in ((A,), (B,), (A, B)):
+        ctx.scene_upload(spheres, meshes)
+        for slot in slots:
+            set_smooth(slot)
+        osc, _ = _oracle(oracle, v, t, normals=slots)
+        exp0, _, _ = osc.render(W, H, 1, 0, want_rgb8=False)
+        for variant in ("auto", "wavefront", "path"):
+            got = ctx.render(_params(0, variant))
+            assert values_equal(got[..., :3], exp0[..., :3]).all(), (slots, variant)
+            np.testing.assert_array_equal(got[..., 3], exp0[..., 3])
+        if A in slots:                                                  # (the mirror cat shows no shading of its own at b = 0)
+            assert (got[..., :3] != flat[..., :3]).any()
+        exp2, _, _ = osc.render(W, H, 2, 2, want_rgb8=False)
+        got2 = ctx.render(_params(2, n=2))
+        assert linf(oracle, got2, exp2) <= TOL, slots
+        np.testing.assert_array_equal(got2[..., 3], exp2[..., 3])
+        with pytest.raises(rt.RtError) as e:
+            ctx.render(_params(0, "lockstep"))
+        assert e.value.code == -5
+    # a smooth cat moved: its normals move with it (translation added, as the reference's kernel does)
+    ctx.scene_upload(spheres, meshes)
+    set_smooth(A)
+    ctx.mesh_transform(R1, T1, object_slot=A)
+    osc, _ = _oracle(oracle, v, t, {A: [_moved(R1, T1)]}, normals=(A,))
+    exp, _, _ = osc.render(W, H, 1, 0, want_rgb8=False)
+    got = ctx.render(_params(0))
+    assert values_equal(got[..., :3], exp[..., :3]).all()
+    np.testing.assert_array_equal(got[..., 3], exp[..., 3])
+    # flat again: the flat forest's frame
+    ctx.scene_upload(spheres, meshes)
+    set_smooth(A)
+    set_smooth(B)
+    ctx.mesh_set_normals(None, None, object_slot=A)
+    ctx.mesh_set_normals(None, None, object_slot=B)
+    np.testing.assert_array_equal(ctx.render(_params(0)).view(np.uint32), flat.view(np.uint32))
+    ctx.render(_params(0, "lockstep"))                                  # no smooth mesh left: every variant again
+
+
+def test_rebuild_one_mesh(ctx, oracle, cat_golden):
+    """cat B moved, cat A moved far and rebuilt: the tree and order buildBVH gives the moved A, bit for bit; the frame with B still on its refitted tree; smooth normals
+    of A travel with its triangles; the LBVH tree handed to the oracle gives the same rays and frame"""
+    v, t, spheres, meshes = _setup(cat_golden)
+    by_slot = {d["object_slot"]: d for d in meshes}
+    t_up = np.asarray(by_slot[A]["indices"])[:, :3]
+    nt = len(t_up)
+    ctx.scene_upload(spheres, meshes)
+    ctx.mesh_transform(R1, T1, object_slot=B)
+    ctx.mesh_transform(R2, T2, object_slot=A)
+    arr, order = ctx.mesh_rebuild(nt, "reference", object_slot=A)
+    osc, oms = _oracle(oracle, v, t, {A: [lambda m: m.transform(R2, T2).build_bvh()], B: [_moved(R1, T1)]})
+    np.testing.assert_array_equal(arr.view(np.uint32), oms[A].bvh_array().view(np.uint32))
+    np.testing.assert_array_equal(t_up[order], oms[A].triangles)
+    for b in (0, 2):
+        exp, _, cnt = osc.render(W, H, 1, b, want_rgb8=False)
+        for variant in ("auto", "path"):
+            _frames_equal(ctx.render(_params(b, variant)), exp)
+        work = ctx.count_work(_params(b))
+        assert work["rays"] == cnt["rays"] and work["tri_tests"] == cnt["tri_tests"]
+    assert ctx.stats_after_render(_params(1))["travq_mode"] == 2
+    # then the other cat, on the forest the first rebuild left (its node ranges moved with A's new node count)
+    arr_b, order_b = ctx.mesh_rebuild(nt, "reference", object_slot=B)
+    osc, oms = _oracle(oracle, v, t, {A: [lambda m: m.transform(R2, T2).build_bvh()], B: [lambda m: m.transform(R1, T1).build_bvh()]})
+    np.testing.assert_array_equal(arr_b.view(np.uint32), oms[B].bvh_array().view(np.uint32))
+    np.testing.assert_array_equal(np.asarray(by_slot[B]["indices"])[:, :3][order_b], oms[B].triangles)
+    exp, _, _ = osc.render(W, H, 1, 2, want_rgb8=False)
+    _frames_equal(ctx.render(_params(2)), exp)
+    # smooth normals on A survive the rebuild (they move with the transform, then travel with their triangles)
+    vnA = _vertex_normals(by_slot[A]["vertices"], np.asarray(t))
+    ctx.scene_upload(spheres, meshes)
+    ctx.mesh_set_normals(vnA, t_up, object_slot=A)
+    ctx.mesh_transform(R1, T1, object_slot=B)
+    ctx.mesh_transform(R2, T2, object_slot=A)
+    arr, order = ctx.mesh_rebuild(nt, "reference", object_slot=A)
+    osc, _ = _oracle(oracle, v, t, {A: [lambda m: m.transform(R2, T2).build_bvh()], B: [_moved(R1, T1)]}, normals=(A,))
+    exp, _, _ = osc.render(W, H, 1, 0, want_rgb8=False)
+    got = ctx.render(_params(0))
+    assert values_equal(got[..., :3], exp[..., :3]).all()
+    np.testing.assert_array_equal(got[..., 3], exp[..., 3])
+    # ... and normals set after a rebuild take their rows in the order it reported
+    ctx.scene_upload(spheres, meshes)
+    ctx.mesh_set_normals(vnA, t_up, object_slot=A)
+    ctx.mesh_transform(R1, T1, object_slot=B)
+    _, order = ctx.mesh_rebuild(nt, "reference", object_slot=A)
+    before = ctx.render(_params(0))
+    ctx.mesh_set_normals(vnA, t_up[order], object_slot=A)
+    np.testing.assert_array_equal(ctx.render(_params(0)).view(np.uint32), before.view(np.uint32))
+    # LBVH: the tree it returns, given to the oracle, walks to the same hits and frame
+    ctx.scene_upload(spheres, meshes)
+    ctx.mesh_transform(R1, T1, object_slot=B)
+    ctx.mesh_transform(R2, T2, object_slot=A)
+    arr, order = ctx.mesh_rebuild(nt, "lbvh", object_slot=A)
+    assert len(arr) > 1 and sorted(order.tolist()) == list(range(nt))
+    _, oms = _oracle(oracle, v, t, {A: [lambda m: m.transform(R2, T2)], B: [_moved(R1, T1)]})
+    vA = oms[A].vertices
+    osc = oracle.Scene()
+    for pos, o in enumerate(ms.describe("two_cats", v)):
+        if o[0] == "sphere":
+            osc.add_sphere(o[1], o[2], o[3])
+        elif pos == A:
+            osc_meshes = [oracle.Mesh.from_arrays(vA, oms[A].triangles[order], albedo=o[2]).set_material(o[3], o[4], o[5]).set_bvh(arr)]
+            osc.add_mesh(osc_meshes[0])
+        else:
+            osc.add_mesh(oms[B])
+    for b in (0, 2):
+        exp, _, _ = osc.render(W, H, 1, b, want_rgb8=False)
+        _frames_equal(ctx.render(_params(b)), exp)
+    assert ctx.stats_after_render(_params(1))["travq_mode"] == 2       # leaves of at most 32 triangles: the 4-wide step takes the forest
+    ctx.scene_upload([], [dict(m, object_slot=j) for j, m in enumerate(meshes)])   # the rays: the meshes alone, A at 0, B at 1, the same steps
+    ctx.mesh_transform(R1, T1, object_slot=1)
+    ctx.mesh_transform(R2, T2, object_slot=0)
+    arr2, order2 = ctx.mesh_rebuild(nt, "lbvh", object_slot=0)
+    np.testing.assert_array_equal(arr2.view(np.uint32), arr.view(np.uint32))
+    np.testing.assert_array_equal(order2, order)
+    _check_rays(ctx, oracle, [osc_meshes[0], oms[B]], 62)
+
+
+def test_refusals_leave_the_scene_untouched(ctx, cat_golden):
+    """a sphere's slot or one outside the scene: RT_ERR_INVALID, layout and frame unchanged; a mesh without triangles: nothing happens; after a failed upload: RT_ERR_NO_SCENE"""
+    v, t, spheres, meshes = _setup(cat_golden)
+    empty = dict(vertices=np.zeros((0, 3), np.float32), indices=np.zeros((0, 10), np.int32), bvh_arr10=np.zeros((0, 10), np.float32), object_slot=8)
+    ctx.scene_upload(spheres, meshes + [empty])
+    h0, f0 = ctx.layout_hash(), ctx.render(_params(1))
+    nt = len(t)
+    vn = np.zeros((4, 3), np.float32)
+    ix = np.zeros((nt, 3), np.int32)
+    for slot in (0, 5, -1, 9, 16):                                      # walls at 0 and 5; 9 objects in all
+        for call in (lambda: ctx.mesh_transform(R1, T1, object_slot=slot), lambda: ctx.mesh_set_normals(vn, ix, object_slot=slot),
+                     lambda: ctx.mesh_rebuild(nt, object_slot=slot)):
+            with pytest.raises(rt.RtError) as e:
+                call()
+            assert e.value.code == -1, slot
+    ctx.mesh_transform(R1, T1, object_slot=8)
+    ctx.mesh_set_normals(vn, ix[:0], object_slot=8)
+    arr, _ = ctx.mesh_rebuild(0, object_slot=8)
+    assert len(arr) == 0
+    assert ctx.layout_hash() == h0
+    _frames_equal(ctx.render(_params(1)), f0)
+    bad = [dict(d) for d in meshes]
+    ix_bad = np.array(bad[1]["indices"], copy=True)
+    ix_bad[5, 1] = len(bad[1]["vertices"]) + 3                         # a vertex index out of range: build_forest refuses the upload
+    bad[1]["indices"] = ix_bad
+    with pytest.raises(rt.RtError) as e:
+        ctx.scene_upload(spheres, bad)
+    assert e.value.code == -1
+    for call in (lambda: ctx.mesh_transform(R1, T1, object_slot=A), lambda: ctx.mesh_set_normals(vn, ix, object_slot=A),
+                 lambda: ctx.mesh_rebuild(nt, object_slot=A)):
+        with pytest.raises(rt.RtError) as e:
+            call()
+        assert e.value.code == -4
