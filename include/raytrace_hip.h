@@ -400,6 +400,45 @@ int rt_mesh_transform_of(rt_ctx *ctx, int object_slot, const float rotation[9], 
 int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles);
 int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out);
 
+/* --- textured meshes (ABI 6, additive): MTL's map_Kd over OBJ's per-corner vt.  The albedo of a hit on a textured mesh is
+ *     mesh albedo (.) sampled texel (Kd x map_Kd), a per-channel binary32 product with the mesh albedo first; it replaces the albedo
+ *     of the fold (cpu:624, 642) and nothing else: the mesh stays diffuse, mirror or glass by its rt_mesh fields.  Every operation below
+ *     is one IEEE binary32 rounding in the order written (the library is built with -ffp-contract=off), so a float32 model reproduces it:
+ *       uv       alpha, beta, gamma exactly as smooth shading computes them (beta = dot(e2, cross(A - O, u)) / dot(u, N), gamma = -dot(e1, ...) /
+ *                dot(u, N), alpha = 1 - beta - gamma; A, e1 = B - A, e2 = C - A, N = e1 x e2 of the hit triangle, (O, u) the ray), then
+ *                uv = (alpha uv_a + beta uv_b) + gamma uv_c per component;
+ *       texel    8-bit RGB or RGBA, width x height texels, the first row given is the TOP of the image, alpha is never read; a channel's
+ *                value is decode[byte] (256 floats from the caller; NULL = byte / 255.0f, correctly rounded);
+ *       nearest  x = floor(u W), y = floor((1 - v) H);
+ *       bilinear s = u W - 0.5, t = (1 - v) H - 0.5, x0 = floor(s), fx = s - x0, y0 = floor(t), fy = t - y0, x1 = x0 + 1, y1 = y0 + 1;
+ *                value = (T(x0,y0) (1 - fx) + T(x1,y0) fx) (1 - fy) + (T(x0,y1) (1 - fx) + T(x1,y1) fx) fy;
+ *       wrap     on the integer indices: repeat = non-negative modulo, clamp = into [0, W - 1] / [0, H - 1];
+ *       range    a coordinate (u W, (1 - v) H, s or t) that is NaN or outside [-2^31, 2^31) gives index 0 and fraction 0 (before the wrap).
+ *     So a texture whose every texel decodes to c renders exactly as the untextured mesh with albedo fl(albedo c) (nearest filtering).
+ *     uvs: n_uvs x 2 floats (OBJ vt); uvidx: the UV indices of triangle t's three corners at uvidx[t * index_stride .. + 2], triangles in the
+ *     mesh's uploaded order (or as its last rebuild reported; for a TriangleIndices array pass &indices[0].uvi and stride 10).  The library
+ *     copies everything.  uvs, uvidx or tex NULL: the mesh untextured again (rt_mesh_set_texture: every mesh).  rt_scene_upload* clears all
+ *     textures; rt_mesh_transform* keep the UVs (they belong to the corners); rt_mesh_rebuild* carry them with their triangles.
+ *     RT_ERR_INVALID, nothing changed: a bad object_slot or a sphere's, a UV index outside [0, n_uvs), n_triangles below the mesh's count,
+ *     width or height <= 0, channels other than 3 / 4, an unknown filter or wrap.  A mesh without triangles: RT_OK, nothing happens.
+ *     Variants: those that run wf_advance -- auto, wavefront, wavefront_lds, wavefront_queue, lds_* (frames, batches, poses, progressive
+ *     frames, num_rays > 1); a textured scene makes path, lockstep and global return RT_ERR_UNSUPPORTED.  rt_multi_* contexts stay
+ *     untextured.  Spheres are never textured. --------------------------------------------------------------------------------------- */
+typedef enum rt_tex_filter { RT_TEX_NEAREST = 0, RT_TEX_BILINEAR = 1 } rt_tex_filter;
+typedef enum rt_tex_wrap { RT_TEX_REPEAT = 0, RT_TEX_CLAMP = 1 } rt_tex_wrap;
+typedef struct rt_texture {
+    const uint8_t *texels;         /* height rows of width texels, top row first, channels bytes each */
+    int32_t        width, height, channels;
+    int32_t        filter, wrap;   /* rt_tex_filter, rt_tex_wrap                                       */
+    const float   *decode;         /* 256 floats, or NULL = byte / 255                                  */
+} rt_texture;
+int rt_mesh_set_texture(rt_ctx *ctx, const float *uvs, int n_uvs, const int32_t *uvidx, int index_stride, int n_triangles, const rt_texture *tex);
+int rt_mesh_set_texture_of(rt_ctx *ctx, int object_slot, const float *uvs, int n_uvs, const int32_t *uvidx, int index_stride, int n_triangles, const rt_texture *tex);
+/* known answers of the texture lookup: rays (n x 6: O, u) through the production traversal (wf_travq), then the device function the
+ * shading kernel calls for the hit.  out: n x 8 = (object slot of the mesh hit or -1, triangle index in that mesh's uploaded order, t,
+ * u, v, albedo rgb); an untextured mesh reports uv = (0, 0) and its own albedo, a miss (-1, -1, 1e9, 0, ...). */
+int rt_kat_surface(rt_ctx *ctx, const float *rays, int n, float tri_tmin, float *out);
+
 /* --- posed camera + progressive accumulation: the headless form of realtime_render.cu.  Camera
  *     {C, yaw, pitch} with Camera::rotate() (realtime_render.cu:803-861); ray generation and per-sample averaging of its
  *     KernelLaunch (:1100-1134: u_center = C + bz*z + bx*X + by*Y, outcolor += color * (1./num_rays)); accumulation and

@@ -555,6 +555,18 @@ public:
         if (order) *order = std::move(ord);
         return arr;
     }
+    // map_Kd (MTL Kd x map_Kd) on the mesh: its own `uvs` and TriangleIndices::uvi,uvj,uvk; texels: h rows of w texels, top row first, channels (3 / 4) bytes
+    // each; decode: 256 floats or nullptr (byte / 255).  Every face needs its vt: a face without one (uvi = -1) is refused here, before the library sees it
+    void use_texture(const TriangleMesh &mesh, const uint8_t *texels, int w, int h, int channels, rt_tex_filter filter = RT_TEX_NEAREST,
+                     rt_tex_wrap wrap = RT_TEX_REPEAT, const float *decode = nullptr) {
+        texture_(mesh, false, texels, w, h, channels, filter, wrap, decode);
+    }
+    void use_texture_of(const TriangleMesh &mesh, const uint8_t *texels, int w, int h, int channels, rt_tex_filter filter = RT_TEX_NEAREST,
+                        rt_tex_wrap wrap = RT_TEX_REPEAT, const float *decode = nullptr) {
+        texture_(mesh, true, texels, w, h, channels, filter, wrap, decode);
+    }
+    void use_untextured() { check(rt_mesh_set_texture(ctx_, nullptr, 0, nullptr, 3, 0, nullptr), "rt_mesh_set_texture"); }
+    void use_untextured_of(const TriangleMesh &mesh) { check(rt_mesh_set_texture_of(ctx_, mesh.id, nullptr, 0, nullptr, 3, 0, nullptr), "rt_mesh_set_texture_of"); }
     // Camera{C, yaw, pitch} (realtime_render.cu:803-861) and disp() (:1243-1290) without the window: one accumulated frame
     std::vector<unsigned char> progressive_frame(const RenderSettings &s, const rt_camera_pose &pose, std::vector<float> *display = nullptr) {
         rt_params p = params(s);
@@ -582,6 +594,18 @@ private:
         DeviceBuffer &operator=(const DeviceBuffer &) = delete;
     };
     void check(int rc, const char *what) { if (rc != RT_OK) throw Error(rc, std::string(what) + ": " + rt_last_error(ctx_)); }
+    void texture_(const TriangleMesh &mesh, bool of, const uint8_t *texels, int w, int h, int channels, rt_tex_filter filter, rt_tex_wrap wrap, const float *decode) {
+        for (size_t t = 0; t < mesh.indices.size(); ++t)
+            if (mesh.indices[t].uvi < 0 || mesh.indices[t].uvj < 0 || mesh.indices[t].uvk < 0)
+                throw Error(RT_ERR_INVALID, "use_texture: face " + std::to_string(t) + " of the mesh has no vt (uvi/uvj/uvk = -1)");
+        std::vector<float> uv(mesh.uvs.size() * 2);
+        for (size_t i = 0; i < mesh.uvs.size(); ++i) { uv[2 * i] = mesh.uvs[i][0]; uv[2 * i + 1] = mesh.uvs[i][1]; }
+        const rt_texture tex{texels, w, h, channels, filter, wrap, decode};
+        const int32_t *ix = mesh.indices.empty() ? nullptr : &mesh.indices[0].uvi;
+        const int stride = (int)(sizeof(TriangleIndices) / sizeof(int32_t)), nt = (int)mesh.indices.size(), nu = (int)mesh.uvs.size();
+        if (of) check(rt_mesh_set_texture_of(ctx_, mesh.id, uv.data(), nu, ix, stride, nt, &tex), "rt_mesh_set_texture_of");
+        else check(rt_mesh_set_texture(ctx_, uv.data(), nu, ix, stride, nt, &tex), "rt_mesh_set_texture");
+    }
     rt_ctx *ctx_ = nullptr;
 };
 

@@ -26,7 +26,7 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_scene_upload_meshes", "rt_render_multi",
            "rt_render_multi_device", "rt_render_multi_rgb8", "rt_multi_get_stats",
            "rt_stats_enable", "rt_ctx_set_pipelining", "rt_render_async", "rt_wait", "rt_trace_rays", "rt_mesh_rebuild", "rt_mesh_rebuild_mode", "rt_mesh_build_stats", "rt_host_alloc", "rt_host_free", "rt_device_alloc", "rt_device_free", "rt_device_to_host", "rt_kat_sphere", "rt_kat_sqrt", "rt_kat_box", "rt_kat_triangle", "rt_kat_mesh", "rt_kat_layout_hash",
-           "rt_mesh_transform_of", "rt_mesh_set_normals_of", "rt_mesh_rebuild_of"]
+           "rt_mesh_transform_of", "rt_mesh_set_normals_of", "rt_mesh_rebuild_of", "rt_mesh_set_texture", "rt_mesh_set_texture_of", "rt_kat_surface"]
 MAX_DEVICES = 16
 
 
@@ -92,6 +92,15 @@ class BuildStats(C.Structure):
 
 
 BVH_MODES = {"reference": 0, "lbvh": 1}
+
+
+class Texture(C.Structure):
+    _fields_ = [("texels", C.POINTER(C.c_uint8)), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("filter", C.c_int32), ("wrap", C.c_int32), ("decode", C.POINTER(C.c_float))]
+
+
+TEX_FILTERS = {"nearest": 0, "bilinear": 1}
+TEX_WRAPS = {"repeat": 0, "clamp": 1}
 
 
 class KatCounts(C.Structure):
@@ -193,6 +202,9 @@ def load():
     L.rt_mesh_transform_of.argtypes = [vp, C.c_int, fp3, fp3]
     L.rt_mesh_set_normals_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int]
     L.rt_mesh_rebuild_of.argtypes = [vp, C.c_int, C.c_int, fp3, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.rt_mesh_set_texture.argtypes = [vp, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
+    L.rt_mesh_set_texture_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
+    L.rt_kat_surface.argtypes = [vp, fp3, C.c_int, C.c_float, fp3]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_host_free.argtypes = [vp]
     L.rt_kat_sphere.argtypes = [vp, fp3, C.c_int, fp3]
@@ -471,6 +483,41 @@ class Context:
             self._check(self._L.rt_mesh_set_normals(self._h, np_, len(n), ip, 3, len(ix)))
         else:
             self._check(self._L.rt_mesh_set_normals_of(self._h, int(object_slot), np_, len(n), ip, 3, len(ix)))
+
+    def mesh_set_texture(self, uvs, uvidx, texels, filter="nearest", wrap="repeat", decode=None, object_slot=None):
+        """map_Kd of a textured mesh (rt_mesh_set_texture[_of]): uvs [n, 2] (OBJ vt), uvidx [n_triangles, 3] per-corner UV indices in the order of the
+        uploaded indices, texels uint8 [height, width, 3 or 4] (top row first), filter "nearest" / "bilinear", wrap "repeat" / "clamp" (or the
+        enum values), decode: 256 floats (None = byte / 255).  uvs or texels None = untextured again.  object_slot: only the mesh at that position."""
+        fn = (lambda *a: self._L.rt_mesh_set_texture(self._h, *a)) if object_slot is None else (lambda *a: self._L.rt_mesh_set_texture_of(self._h, int(object_slot), *a))
+        if uvs is None or texels is None:
+            self._check(fn(None, 0, None, 3, 0, None))
+            return
+        uv = np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+        ix = np.ascontiguousarray(uvidx, np.int32).reshape(-1, 3)
+        tx = np.ascontiguousarray(texels, np.uint8)
+        if tx.ndim != 3:
+            raise ValueError("texels: [height, width, channels] uint8")
+        tex = Texture()
+        tex.texels = tx.ctypes.data_as(C.POINTER(C.c_uint8))
+        tex.height, tex.width, tex.channels = tx.shape
+        tex.filter = TEX_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        tex.wrap = TEX_WRAPS[wrap] if isinstance(wrap, str) else int(wrap)
+        dec = None
+        if decode is not None:
+            dec = np.ascontiguousarray(decode, np.float32).reshape(-1)
+            if dec.size != 256:
+                raise ValueError("decode: 256 floats")
+            tex.decode = dec.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(fn(uv.ctypes.data_as(C.POINTER(C.c_float)), len(uv), ix.ctypes.data_as(C.POINTER(C.c_int32)), 3, len(ix), C.byref(tex)))
+
+    def kat_surface(self, rays, tri_tmin=1e-4):
+        """rt_kat_surface: rays [n, 6] through the production traversal, then the shading kernel's texture lookup -> [n, 8]
+        (object slot or -1, triangle in its mesh's uploaded order, t, u, v, albedo rgb)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((rays.shape[0], 8), np.float32)
+        self._check(self._L.rt_kat_surface(self._h, rays.ctypes.data_as(C.POINTER(C.c_float)), rays.shape[0], C.c_float(tri_tmin),
+                                           out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def render_pose(self, params, pose):
         """One frame with realtime_render.cu's posed camera and per-sample averaging (no accumulation)."""

@@ -113,6 +113,11 @@ struct rt_ctx {
     bool have_scene = false, have_kernel_time = false, have_tonemap_time = false;
     rtk::Scene scene{};
     DevBuf nrm;                                                     // smooth shading: 3 normals per triangle, visit order
+    // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
+    // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.
+    DevBuf tex_uv, tex_table, tex_img[rtk::kMaxObjects];
+    rtk::TexDesc tex_desc[rtk::kMaxObjects] = {};
+    int tex_mask = 0;
     std::vector<int> tri_perm;                                       // visit order -> triangle index in the uploaded (BVH-order) arrays
     std::vector<int> up_indices;                                     // vertex indices of the uploaded triangles, 3 per triangle
     int n_up_tris = 0;
@@ -153,6 +158,7 @@ struct rt_ctx {
     DevBuf node_lo, node_hi, nodes2, nodesq, nodesb, q2thr, tri, verts, tidx, scratch_rgba, scratch_rgb8, work, queue;
     int n_cus = 0;
     DevBuf wfM, wfT, wfLS, wfSID, wfSamp;                     // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
+    DevBuf wfALB;                                                   // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
     DevBuf wfQR;                                                    // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp, pathT;                                         // wf_path with num_rays > 1: per-sample colours, running sum
     DevBuf dbgbuf;                                                  // -DRT_DEBUG builds: per-wave traversal records
@@ -268,6 +274,15 @@ int ensure(rt_ctx *ctx, DevBuf &b, size_t bytes) {
     RT_HIP(ctx, hipMalloc(&b.p, bytes ? bytes : 16));
     b.bytes = bytes ? bytes : 16;
     return RT_OK;
+}
+
+// what wf_advance_tex and kat_surface_kernel read of the textures (ALB: set per launch)
+rtk::TexScene tex_scene(const rt_ctx *ctx) {
+    rtk::TexScene ts{};
+    ts.uv = static_cast<const float2 *>(ctx->tex_uv.p);
+    ts.desc = static_cast<const rtk::TexDesc *>(ctx->tex_table.p);
+    ts.mask = ctx->tex_mask;
+    return ts;
 }
 
 // Host -> device, complete on return.  (hipMemcpy = the NULL stream.  Round 6 tried the context's own stream instead, to spare a C++ program one hardware queue: the ~27 ms the

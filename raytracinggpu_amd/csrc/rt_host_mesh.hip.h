@@ -56,6 +56,23 @@ static void visit_range(const rtk::Scene &sc, int obj, int &vb, int &ve) {
         if (sc.mesh[k].obj == obj) { vb = sc.mesh[k].tri_begin; ve = k + 1 < sc.n_meshes ? sc.mesh[k + 1].tri_begin : sc.n_tris; }
 }
 
+// Textured meshes across a re-layout (the rebuild entries): the UVs the device holds in visit order before install_scene, and after it new visit rank t takes the
+// UVs of old visit rank old_visit[t] (-1: none) -- as the smooth normals travel with their triangles.
+static int tex_read_uv(rt_ctx *ctx, int n_tris, std::vector<float2> &uv) {
+    uv.clear();
+    if (ctx->tex_mask == 0 || n_tris <= 0) return RT_OK;
+    uv.resize(3 * (size_t)n_tris);
+    RT_HIP(ctx, hipMemcpy(uv.data(), ctx->tex_uv.p, uv.size() * sizeof(float2), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+static int tex_relayout(rt_ctx *ctx, const std::vector<float2> &old_uv, const std::vector<int> &old_visit) {
+    if (ctx->tex_mask == 0 || old_uv.empty() || old_visit.empty()) return RT_OK;
+    std::vector<float2> nu(3 * old_visit.size(), make_float2(0.f, 0.f));
+    for (size_t t = 0; t < old_visit.size(); ++t)
+        if (old_visit[t] >= 0) for (int k = 0; k < 3; ++k) nu[3 * t + k] = old_uv[3 * (size_t)old_visit[t] + k];
+    return upload(ctx, ctx->tex_uv, nu.data(), nu.size() * sizeof(float2));
+}
+
 int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     RT_OWN_STREAM(ctx);
@@ -371,7 +388,7 @@ int rt_mesh_rebuild_mode(rt_ctx *ctx, int mode, float *bvh_arr10_out, int32_t *t
     ctx->build.mode = mode; ctx->build.n_nodes = n_nodes; ctx->build.n_triangles = nt;
     const auto t_install = std::chrono::steady_clock::now();
     int *const order_dev = static_cast<int *>(ctx->bb_idx.p);
-    if (mode == RT_BVH_LBVH && old.nrm == nullptr && !ctx->lbvh_host_install && ctx->build.max_depth <= 56) {
+    if (mode == RT_BVH_LBVH && old.nrm == nullptr && ctx->tex_mask == 0 && !ctx->lbvh_host_install && ctx->build.max_depth <= 56) {   // (normals and UVs travel on the host path)
         // the kernels' formats straight from the builder's arrays; the flat tree and the order travel to the host only if the caller asks
         if ((rc = install_lbvh_device(ctx, old, n_nodes)) != RT_OK) return rc;
         if (bvh_arr10_out) RT_HIP(ctx, hipMemcpyAsync(bvh_arr10_out, ctx->bb_arr.p, (size_t)n_nodes * 10 * sizeof(float), hipMemcpyDeviceToHost, q));
@@ -397,6 +414,8 @@ int rt_mesh_rebuild_mode(rt_ctx *ctx, int mode, float *bvh_arr10_out, int32_t *t
         RT_HIP(ctx, hipMemcpyAsync(old_nrm.data(), ctx->nrm.p, old_nrm.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
     }
     RT_HIP(ctx, hipStreamSynchronize(q));
+    std::vector<float2> old_uv;
+    if ((rc = tex_read_uv(ctx, old.n_tris, old_uv)) != RT_OK) return rc;
     std::vector<float> vx((size_t)nv * 3);
     for (int i = 0; i < nv; ++i) { vx[3 * (size_t)i] = hv[i].x; vx[3 * (size_t)i + 1] = hv[i].y; vx[3 * (size_t)i + 2] = hv[i].z; }
     std::vector<int32_t> ix((size_t)nt * 3);
@@ -419,6 +438,12 @@ int rt_mesh_rebuild_mode(rt_ctx *ctx, int mode, float *bvh_arr10_out, int32_t *t
         }
         if ((rc = upload(ctx, ctx->nrm, nn.data(), nn.size() * sizeof(float4))) != RT_OK) return rc;
         ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
+    }
+    if (!old_uv.empty()) {                                                         // UVs travel with their triangles
+        std::vector<int> old_visit_of(nt, -1), old_visit(ctx->tri_perm.size());
+        for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
+        for (size_t t = 0; t < ctx->tri_perm.size(); ++t) old_visit[t] = old_visit_of[order[ctx->tri_perm[t]]];
+        if ((rc = tex_relayout(ctx, old_uv, old_visit)) != RT_OK) return rc;
     }
     if (bvh_arr10_out) memcpy(bvh_arr10_out, arr.data(), arr.size() * sizeof(float));
     if (tri_order_out) memcpy(tri_order_out, order.data(), order.size() * sizeof(int));
@@ -554,6 +579,8 @@ int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_
         RT_HIP(ctx, hipMemcpyAsync(old_nrm.data(), ctx->nrm.p, old_nrm.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
     }
     RT_HIP(ctx, hipStreamSynchronize(q));
+    std::vector<float2> old_uv;
+    if ((rc = tex_read_uv(ctx, old.n_tris, old_uv)) != RT_OK) return rc;
     // every mesh in its own index space, in object order, as build_forest takes them from rt_scene_upload_meshes
     std::vector<std::vector<float>> vx(K), ar(K);
     std::vector<std::vector<int32_t>> ix(K);
@@ -617,6 +644,15 @@ int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_
         }
         if ((rc = upload(ctx, ctx->nrm, nn.data(), nn.size() * sizeof(float4))) != RT_OK) return rc;
         ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
+    }
+    if (!old_uv.empty()) {                                                         // UVs travel with their triangles, every textured mesh's
+        std::vector<int> old_visit_of(ctx->n_up_tris, -1), old_visit(ctx->tri_perm.size());
+        for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
+        for (size_t t = 0; t < ctx->tri_perm.size(); ++t) {
+            const int g = ctx->tri_perm[t];
+            old_visit[t] = old_visit_of[g >= P.tri_off && g < P.tri_off + P.nt ? P.tri_off + order[g - P.tri_off] : g];
+        }
+        if ((rc = tex_relayout(ctx, old_uv, old_visit)) != RT_OK) return rc;
     }
     if (bvh_arr10_out) memcpy(bvh_arr10_out, arr.data(), arr.size() * sizeof(float));
     if (tri_order_out) memcpy(tri_order_out, order.data(), order.size() * sizeof(int));

@@ -40,17 +40,35 @@ __global__ __launch_bounds__(256) void trace_close_kernel(const Scene sc, const 
     o[0] = 1.f; o[1] = __uint_as_float((unsigned int)(m >> 32)); o[2] = N.x; o[3] = N.y; o[4] = N.z;
 }
 
+// rt_kat_surface: the mesh hit of each ray (the production traversal's result) and what wf_advance_tex makes of it -- tex_albedo, the one device function both call.
+// out[r] = (object slot or -1, triangle in its mesh's uploaded order, t, u, v, albedo rgb); an untextured mesh reports uv (0, 0) and its constant albedo.
+__global__ __launch_bounds__(256) void kat_surface_kernel(const Scene sc, const TexScene ts, const unsigned long long *__restrict__ M, const float *__restrict__ rays,
+                                                          const int *__restrict__ visit2local, int n, float *__restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const unsigned long long m = M[r];
+    float *o = out + 8 * (size_t)r;
+    if (m == WF_NOHIT) { o[0] = -1.f; o[1] = -1.f; o[2] = 1e9f; o[3] = o[4] = o[5] = o[6] = o[7] = 0.f; return; }
+    const int tri = (int)(unsigned int)m;
+    const int obj = mesh_obj_of_tri(sc, tri);
+    const float *p = rays + 6 * (size_t)r;
+    const f3 O = mk(p[0], p[1], p[2]), u = mk(p[3], p[4], p[5]);
+    float2 uv = make_float2(0.f, 0.f);
+    f3 alb;
+    if ((ts.mask >> obj) & 1) {
+        alb = tex_albedo(sc, ts, obj, tri, tri_bary(sc, tri, O, u), uv);
+    } else {
+        const Material mt = material_of(sc, obj);
+        alb = mk(mt.ar, mt.ag, mt.ab);
+    }
+    o[0] = (float)obj; o[1] = (float)visit2local[tri]; o[2] = __uint_as_float((unsigned int)(m >> 32));
+    o[3] = uv.x; o[4] = uv.y; o[5] = alb.x; o[6] = alb.y; o[7] = alb.z;
+}
+
 }  // namespace rtk
 
-extern "C" int rt_trace_rays(rt_ctx *ctx, const float *rays, int n, float tri_tmin, int variant, float *out) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
-    if (n < 0 || (n > 0 && (!rays || !out))) return fail(ctx, RT_ERR_INVALID, "bad ray batch");
-    if (n >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "at most 2^28 rays per call");
-    if (variant == RT_VARIANT_AUTO) variant = RT_VARIANT_WAVEFRONT_QUEUE;
-    if (variant != RT_VARIANT_WAVEFRONT_QUEUE && variant != RT_VARIANT_WAVEFRONT && variant != RT_VARIANT_PATH)
-        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_trace_rays runs the traversal of variant wavefront_queue (wf_travq), wavefront (wf_trav) or path (wf_path)");
-    if (n == 0) return RT_OK;
+// The caller's rays (din: n x 6 floats on the device) through the production traversal of `variant`; M: bits(t) << 32 | triangle (visit order) per ray, WF_NOHIT if none
+static int trace_to_m(rt_ctx *ctx, const float *din, int n, float tri_tmin, int variant, unsigned long long *&M) {
     const rtk::Scene &sc = ctx->scene;
     if (variant == RT_VARIANT_WAVEFRONT_QUEUE && (sc.n_nodes + 2 >= (1 << rtk::kQNodeBits) || !ctx->travq_ok)) variant = RT_VARIANT_WAVEFRONT;
     if (variant == RT_VARIANT_PATH && sc.n_nodes + 2 >= (1 << rtk::kPNodeBits)) variant = RT_VARIANT_WAVEFRONT;
@@ -59,13 +77,11 @@ extern "C" int rt_trace_rays(rt_ctx *ctx, const float *rays, int n, float tri_tm
     hipStream_t q = own_stream(ctx);
     const Knobs &kn = ctx->knobs;
     const bool have_mesh = sc.mesh_slot >= 0 && sc.n_nodes > 0;
-    DevBuf din, dout;
     int rc;
-    auto done = [&](int code) { din.release(); dout.release(); return code; };
-    if ((rc = upload(ctx, din, rays, (size_t)n * 6 * sizeof(float))) != RT_OK || (rc = ensure(ctx, dout, (size_t)n * 5 * sizeof(float))) != RT_OK) return done(rc);
+    auto done = [&](int code) { return code; };
     rtk::Frame fr{};
     fr.tri_tmin = tri_tmin; fr.segs = 1; fr.spp = 1; fr.W = 1; fr.H = 1; fr.n_rows = 1; fr.tile_rows = 1; fr.tile_step = 1; fr.out_tile_step = 1;
-    unsigned long long *M = nullptr;
+    M = nullptr;
     if (variant == RT_VARIANT_PATH) {
         // the fused kernel: items = the rays, in wf_path's own launch geometry (launch_render, RT_VARIANT_PATH)
         constexpr int wpb = rtk::kQBlock / 64;
@@ -78,7 +94,7 @@ extern "C" int rt_trace_rays(rt_ctx *ctx, const float *rays, int n, float tri_tm
         ps.n_groups = ps.n_paths / 4;
         if ((rc = ensure(ctx, ctx->wfM, (size_t)ps.n_paths * 8)) != RT_OK) return done(rc);
         M = static_cast<unsigned long long *>(ctx->wfM.p);
-        ps.ext_rays = static_cast<const float *>(din.p); ps.ext_out = M; ps.n_ext = n;
+        ps.ext_rays = din; ps.ext_out = M; ps.n_ext = n;
         int64_t tblocks = std::max<int64_t>(1, (int64_t)ctx->n_cus * bpc) * kn.path_oversub;
         const int min_groups = kn.min_groups * wpb;
         int64_t groups_per_block = (ps.n_groups + tblocks - 1) / tblocks;
@@ -122,17 +138,70 @@ extern "C" int rt_trace_rays(rt_ctx *ctx, const float *rays, int n, float tri_tm
         st.M = M = static_cast<unsigned long long *>(ctx->wfM.p);
         st.init_m = queue ? 0 : 1;
         st.epoch = 0; st.nonce = 0;
-        hipLaunchKernelGGL(rtk::trace_emit_kernel, dim3((unsigned)((2 * st.n_paths + 255) / 256)), dim3(256), 0, q, sc, st, static_cast<const float *>(din.p), n);
+        hipLaunchKernelGGL(rtk::trace_emit_kernel, dim3((unsigned)((2 * st.n_paths + 255) / 256)), dim3(256), 0, q, sc, st, din, n);
         if (have_mesh) {
             if (queue) hipLaunchKernelGGL(travq_fn(false, qR, false, false, sc.nodesh != nullptr, qw), dim3((unsigned)tblocks), dim3(tb), trav_lds, q, sc, fr, st, qcap, 0, kn.q_low * (qR == 128 ? 2 : 1),
                                           (kn.q_minfree >= 1 && kn.q_minfree <= qR) ? kn.q_minfree : qR / 4);
             else hipLaunchKernelGGL((rtk::wf_trav<false, false>), dim3((unsigned)tblocks), dim3(tb), trav_lds, q, sc, fr, st);
         }
     }
-    hipLaunchKernelGGL(rtk::trace_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, sc, M, n, static_cast<float *>(dout.p));
+    return RT_OK;
+}
+
+extern "C" int rt_trace_rays(rt_ctx *ctx, const float *rays, int n, float tri_tmin, int variant, float *out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (n < 0 || (n > 0 && (!rays || !out))) return fail(ctx, RT_ERR_INVALID, "bad ray batch");
+    if (n >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "at most 2^28 rays per call");
+    if (variant == RT_VARIANT_AUTO) variant = RT_VARIANT_WAVEFRONT_QUEUE;
+    if (variant != RT_VARIANT_WAVEFRONT_QUEUE && variant != RT_VARIANT_WAVEFRONT && variant != RT_VARIANT_PATH)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_trace_rays runs the traversal of variant wavefront_queue (wf_travq), wavefront (wf_trav) or path (wf_path)");
+    if (n == 0) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_OWN_STREAM(ctx);
+    hipStream_t q = own_stream(ctx);
+    DevBuf din, dout;
+    int rc;
+    auto done = [&](int code) { din.release(); dout.release(); return code; };
+    if ((rc = upload(ctx, din, rays, (size_t)n * 6 * sizeof(float))) != RT_OK || (rc = ensure(ctx, dout, (size_t)n * 5 * sizeof(float))) != RT_OK) return done(rc);
+    unsigned long long *M = nullptr;
+    if ((rc = trace_to_m(ctx, static_cast<const float *>(din.p), n, tri_tmin, variant, M)) != RT_OK) return done(rc);
+    hipLaunchKernelGGL(rtk::trace_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, ctx->scene, M, n, static_cast<float *>(dout.p));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, q);
     if (e == hipSuccess) e = hipStreamSynchronize(q);
     if (e != hipSuccess) return done(fail(ctx, RT_ERR_HIP, "rt_trace_rays: %s", hipGetErrorString(e)));
+    return done(RT_OK);
+}
+
+extern "C" int rt_kat_surface(rt_ctx *ctx, const float *rays, int n, float tri_tmin, float *out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
+    if (n < 0 || (n > 0 && (!rays || !out))) return fail(ctx, RT_ERR_INVALID, "bad ray batch");
+    if (n >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "at most 2^28 rays per call");
+    if (n == 0) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_OWN_STREAM(ctx);
+    if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
+    hipStream_t q = own_stream(ctx);
+    // visit rank -> the triangle's index in its own mesh's uploaded order
+    std::vector<int> local(std::max<size_t>(ctx->tri_perm.size(), 1), -1);
+    for (size_t t = 0; t < ctx->tri_perm.size(); ++t) {
+        const int g = ctx->tri_perm[t];
+        for (const rt_ctx::MeshPart &p : ctx->parts) if (g >= p.tri_off && g < p.tri_off + p.nt) local[t] = g - p.tri_off;
+    }
+    DevBuf din, dout, dloc;
+    int rc;
+    auto done = [&](int code) { din.release(); dout.release(); dloc.release(); return code; };
+    if ((rc = upload(ctx, din, rays, (size_t)n * 6 * sizeof(float))) != RT_OK || (rc = ensure(ctx, dout, (size_t)n * 8 * sizeof(float))) != RT_OK ||
+        (rc = upload(ctx, dloc, local.data(), local.size() * sizeof(int))) != RT_OK) return done(rc);
+    unsigned long long *M = nullptr;
+    if ((rc = trace_to_m(ctx, static_cast<const float *>(din.p), n, tri_tmin, RT_VARIANT_WAVEFRONT_QUEUE, M)) != RT_OK) return done(rc);
+    hipLaunchKernelGGL(rtk::kat_surface_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, ctx->scene, tex_scene(ctx), M, static_cast<const float *>(din.p),
+                       static_cast<const int *>(dloc.p), n, static_cast<float *>(dout.p));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    if (e != hipSuccess) return done(fail(ctx, RT_ERR_HIP, "rt_kat_surface: %s", hipGetErrorString(e)));
     return done(RT_OK);
 }

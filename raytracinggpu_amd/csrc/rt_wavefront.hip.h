@@ -512,8 +512,82 @@ finished:
     wf_flush_work<STATS>(fr, wk);
 }
 
+// ---- textured meshes (rt_mesh_set_texture[_of], raytrace_hip.h) ----------------------------------------------
+// A texture is the first material property that changes from one hit to the next: a diffuse segment of a textured mesh stores its albedo
+// (mesh albedo (.) sampled texel, MTL's Kd x map_Kd) in ALB when it is shaded and the fold reads it there (SID == kSidTextured) instead of
+// looking the object's constant albedo up.  Only wf_advance_tex carries this code; frames without a textured mesh run wf_advance unchanged.
+constexpr int kMaxObjects = 16;              // RT_MAX_OBJECTS: the texture table is indexed by object id
+constexpr int kSidTextured = 0xfe;           // SID of a textured diffuse segment (object ids are < kMaxObjects, 0xff = not diffuse)
+struct TexDesc {                             // the texture of one object
+    const uint8_t *texels;                   // h rows of w texels, top row first, ch (3 or 4) bytes each; alpha is never read
+    const float *decode;                     // 256 floats: the channel value of a byte
+    int w, h, ch, filter, wrap, pad;         // filter 0 nearest / 1 bilinear, wrap 0 repeat / 1 clamp
+};
+struct TexScene {
+    const float2 *uv;                        // 3 per triangle (corners a, b, c = the vertices of its record), visit order; read for textured meshes only
+    const TexDesc *desc;                     // [kMaxObjects] by object id (device memory: read with a per-lane index)
+    float4 *ALB;                             // albedo of textured diffuse segment d of path i: ALB[d * n_paths + i]
+    int mask;                                // bit k: object k is a textured mesh
+};
+// alpha, beta, gamma of triangle `tri` for the ray (O, u): the expressions of the smooth-normal branch of wf_advance_path (get_smooth_normal, realtime_render.cu:221-245)
+struct Bary { float alpha, beta, gamma; };
+__device__ __forceinline__ Bary tri_bary(const Scene &sc, int tri, f3 O, f3 u) {
+    const float4 q0 = sc.tri[3 * tri], q1 = sc.tri[3 * tri + 1], q2 = sc.tri[3 * tri + 2];
+    const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x), Nt = mk(q2.y, q2.z, q2.w);
+    Bary b;
+    b.beta = dot(e2, cross(A - O, u)) / dot(u, Nt);
+    b.gamma = -dot(e1, cross(A - O, u)) / dot(u, Nt);
+    b.alpha = 1 - b.beta - b.gamma;
+    return b;
+}
+// floor of a texel coordinate as an int, and the fraction c - floor(c).  A coordinate outside [-2^31, 2^31) -- NaN and +-inf included -- is index 0 with fraction 0.
+__device__ __forceinline__ int tex_floor(float c, float &frac) {
+    const bool ok = c >= -2147483648.f && c < 2147483648.f;
+    const float f = floorf(c);
+    frac = ok ? c - f : 0.f;
+    return ok ? (int)f : 0;
+}
+__device__ __forceinline__ int tex_wrap(int i, int n, int wrap) {
+    if (wrap != 0) return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);        // clamp
+    const int r = i % n;                                               // repeat: non-negative modulo
+    return r < 0 ? r + n : r;
+}
+__device__ __forceinline__ f3 tex_texel(const TexDesc &td, int x, int y) {
+    const uint8_t *p = td.texels + ((size_t)y * (size_t)td.w + (size_t)x) * (size_t)td.ch;
+    return mk(td.decode[p[0]], td.decode[p[1]], td.decode[p[2]]);
+}
+// the texture at (u, v): nearest x = floor(u W), y = floor((1 - v) H); bilinear from s = u W - 0.5, t = (1 - v) H - 0.5 -- every operation one binary32 rounding
+__device__ __forceinline__ f3 tex_sample(const TexDesc &td, float u, float v) {
+    const float W = (float)td.w, H = (float)td.h;
+    float fx, fy;
+    if (td.filter == 0) {
+        const int x = tex_wrap(tex_floor(u * W, fx), td.w, td.wrap), y = tex_wrap(tex_floor((1.f - v) * H, fy), td.h, td.wrap);
+        return tex_texel(td, x, y);
+    }
+    const int x0 = tex_floor(u * W - 0.5f, fx), y0 = tex_floor((1.f - v) * H - 0.5f, fy);
+    const int xa = tex_wrap(x0, td.w, td.wrap), xb = tex_wrap(x0 + 1, td.w, td.wrap);
+    const int ya = tex_wrap(y0, td.h, td.wrap), yb = tex_wrap(y0 + 1, td.h, td.wrap);
+    const f3 t00 = tex_texel(td, xa, ya), t10 = tex_texel(td, xb, ya), t01 = tex_texel(td, xa, yb), t11 = tex_texel(td, xb, yb);
+    const float gx = 1.f - fx, gy = 1.f - fy;
+    return mk((t00.x * gx + t10.x * fx) * gy + (t01.x * gx + t11.x * fx) * fy,
+              (t00.y * gx + t10.y * fx) * gy + (t01.y * gx + t11.y * fx) * fy,
+              (t00.z * gx + t10.z * fx) * gy + (t01.z * gx + t11.z * fx) * fy);
+}
+// albedo of a hit on triangle `tri` of textured object `obj`: uv = (alpha uv_a + beta uv_b) + gamma uv_c, then mesh albedo (.) texture(uv).  wf_advance_tex and
+// rt_kat_surface call this one function.
+__device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, int obj, int tri, const Bary &b, float2 &uv) {
+    const float2 ua = ts.uv[3 * tri], ub = ts.uv[3 * tri + 1], uc = ts.uv[3 * tri + 2];
+    uv.x = (b.alpha * ua.x + b.beta * ub.x) + b.gamma * uc.x;
+    uv.y = (b.alpha * ua.y + b.beta * ub.y) + b.gamma * uc.y;
+    const TexDesc td = ts.desc[obj];
+    const f3 s = tex_sample(td, uv.x, uv.y);
+    const Material m = material_of(sc, obj);
+    return mk(m.ar * s.x, m.ag * s.y, m.ab * s.z);
+}
+
 // ---- wf_advance: close the queries, shade, emit the next rays -----------------------------------------------
 // FIRST: the launch that opens the chain's samples -- camera rays (cpu:699-709) instead of closing queries.
+// TEX (wf_advance_tex, never FIRST): textured meshes -- the albedo of a textured diffuse hit goes to ts.ALB and the fold reads it from there.
 // The samples of a pixel are independent paths (the reference's loop cpu:701-712 carries nothing but the sum): a chain traces
 // several of them at once as items, each writes its colour, and path_reduce adds the colours in sample order.
 // code-object markers (labels, not instructions): tools/static_counts.py cuts the production instantiation into regions at them -- what a path pays for, region by region
@@ -522,8 +596,8 @@ finished:
 #else
 #define ADV_MARK(name) asm volatile("rt_mark_adv_" name "_%=:" ::)
 #endif
-template <bool STATS, bool FIRST>
-__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk) {
+template <bool STATS, bool FIRST, bool TEX = false>
+__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts) {
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
@@ -632,12 +706,15 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             if (win >= 0) {                                           // a miss is black (cpu:571): nothing to emit
                 const f3 P = O + t_min * u;                           // cpu:560
                 f3 N;
+                Bary bary{0.f, 0.f, 0.f};                             // (TEX) the smooth-normal branch's barycentrics, shared with the texture lookup
+                bool have_bary = false;
                 if (tri_win >= 0 && sc.nrm != nullptr && ((sc.smooth_mask >> win) & 1)) {              // get_smooth_normal (of a smooth mesh), realtime_render.cu:221-245
                     const float4 q0 = sc.tri[3 * tri_win], q1 = sc.tri[3 * tri_win + 1], q2 = sc.tri[3 * tri_win + 2];
                     const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x), Nt = mk(q2.y, q2.z, q2.w);
                     const float beta = dot(e2, cross(A - O, u)) / dot(u, Nt);
                     const float gamma = -dot(e1, cross(A - O, u)) / dot(u, Nt);
                     const float alpha = 1 - beta - gamma;
+                    if (TEX) { bary.alpha = alpha; bary.beta = beta; bary.gamma = gamma; have_bary = true; }
                     const float4 na = sc.nrm[3 * tri_win], nb = sc.nrm[3 * tri_win + 1], nc = sc.nrm[3 * tri_win + 2];
                     N = normalize((alpha * mk(na.x, na.y, na.z) + beta * mk(nb.x, nb.y, nb.z)) + gamma * mk(nc.x, nc.y, nc.z));
                 } else if (tri_win >= 0) {
@@ -695,6 +772,13 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     emitX = true;
                     x_moot = st.anyhit && __float_as_uint(lvis) == 0u;
                     sid = win;
+                    if (TEX && tri_win >= 0 && ((ts.mask >> win) & 1)) {   // a textured mesh: this segment's albedo, evaluated once, for the fold
+                        if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
+                        float2 uv;
+                        const f3 alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
+                        ts.ALB[(size_t)d * st.n_paths + i] = make_float4(alb.x, alb.y, alb.z, 0.f);
+                        sid = kSidTextured;
+                    }
                     ADV_MARK("diffuse_end");
                     if (d + 1 < fr.segs) {                            // the bounce ray (cpu:627-642): needs r1, r2 and N only
                         ADV_MARK("bounce_begin");
@@ -739,10 +823,17 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         for (int k = nseg - 1; k >= 0; --k) {
             const int sid = st.SID[(size_t)k * st.n_paths + i];
             if (sid != 0xff) {
+                if (TEX && sid == kSidTextured) {                     // the albedo the segment stored when it was shaded
+                    const float l = st.LS[(size_t)k * st.n_paths + i];
+                    const float4 a = ts.ALB[(size_t)k * st.n_paths + i];
+                    const f3 alb = mk(a.x, a.y, a.z);
+                    ans = (l * alb) / PI_F + alb * ans;
+                } else {
                 const Material m = material_of(sc, sid);
                 const float l = st.LS[(size_t)k * st.n_paths + i];
                 const f3 alb = mk(m.ar, m.ag, m.ab);
                 ans = (l * alb) / PI_F + alb * ans;
+                }
             }
         }
         if (st.samp_out != nullptr) {                                 // more than one sample per pixel: path_reduce sums in sample order
@@ -792,8 +883,16 @@ template <bool STATS, bool FIRST>
 __global__ __launch_bounds__(256, 8) void wf_advance(const Scene sc, const Frame fr, const WfState st) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
-    if (i < st.n_paths) wf_advance_path<STATS, FIRST>(sc, fr, st, i, wk);
+    if (i < st.n_paths) wf_advance_path<STATS, FIRST>(sc, fr, st, i, wk, TexScene{});
     wf_flush_work<STATS>(fr, wk);                                     // every lane of the wave arrives here (wave-level sums)
+}
+// the same for a scene with a textured mesh (the launches after the first: wf_advance<STATS, true> shades nothing)
+template <bool STATS>
+__global__ __launch_bounds__(256, 8) void wf_advance_tex(const Scene sc, const Frame fr, const WfState st, const TexScene ts) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<STATS, false, true>(sc, fr, st, i, wk, ts);
+    wf_flush_work<STATS>(fr, wk);
 }
 
 }  // namespace rtk
