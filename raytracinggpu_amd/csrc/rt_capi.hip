@@ -180,35 +180,8 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     PhaseClock pc;
     std::vector<int> real;                                               // meshes with something to traverse, in object order
     for (int k = 0; k < n_meshes; ++k) if (meshes[order[k]].n_triangles > 0 && meshes[order[k]].n_nodes > 0) real.push_back(order[k]);
-    int rc;
-    std::vector<rt_ctx::MeshPart> parts;
-    if (real.size() <= 1) {
-        // the reference's own scenes: one mesh (or none; a mesh without triangles is an object that is never hit, cpu:322-325)
-        const rt_mesh *one = real.empty() ? (n_meshes > 0 ? &meshes[order[0]] : nullptr) : &meshes[real[0]];
-        rc = install_scene(ctx, sc, one);
-        if (!real.empty()) parts.push_back({one->object_slot, 0, one->n_vertices, 0, one->n_triangles, 0, one->n_nodes, false});
-        ctx->forest_arr.clear();
-    } else {
-        Forest f;
-        if ((rc = build_forest(ctx, meshes, real, f)) != RT_OK) return rc;
-        // table entry of every mesh -> first triangle in the forest's index array (a mesh without triangles: the next real mesh's)
-        std::vector<int> offs(n_meshes + 1, f.tri_off[real.size()]);
-        for (int k = n_meshes - 1, r = (int)real.size() - 1; k >= 0; --k) {
-            if (r >= 0 && order[k] == real[r]) { offs[k] = f.tri_off[r]; --r; }
-            else offs[k] = offs[k + 1];
-        }
-        rc = install_scene(ctx, sc, &f.m, &offs, (int)real.size() - 1);
-        for (size_t k = 0; k < real.size(); ++k) {
-            const rt_mesh &m = meshes[real[k]];
-            parts.push_back({m.object_slot, f.voff[k], m.n_vertices, f.tri_off[k], m.n_triangles, f.noff[k], m.n_nodes, false});
-        }
-        ctx->forest_arr = std::move(f.arr);
-    }
-    if (rc == RT_OK) {
-        ctx->n_real_meshes = (int)real.size(); ctx->real_obj = real.empty() ? -1 : meshes[real[0]].object_slot;
-        ctx->parts = std::move(parts);
-        ctx->parts_valid = true;
-    }
+    // the reference's own scenes hold one mesh (or none; a mesh without triangles is an object that is never hit, cpu:322-325)
+    const int rc = install_meshes(ctx, sc, meshes, real, n_meshes > 0 ? &meshes[order[0]] : nullptr);
     pc.lap("rt_scene_upload (layouts, hipMalloc, copies)");
     return rc;
 }

@@ -139,10 +139,10 @@ struct rt_ctx {
     int q16_leaf_shift = 0;                                         // where a leaf's triangle count sits in its payload word (rtk::q16_leaf_shift), 0 = leaves too large
     bool q16_topo_ok = false;                                       // the tree's shape allows them (leaf sizes, node count, boxes nest)
     bool qw_topo_ok = false;                                        // ... and no leaf is empty: places 0 and 2 of a quad must hold a node (the pairs cope with an empty leaf)
-    int real_obj = -1;                                              // object position of the (first) mesh with triangles, -1 = none
-    int n_real_meshes = 0;                                          // meshes WITH triangles in the scene: with more than one the tree in use is a forest (build_forest) and the plain per-mesh operations are refused (the *_of entries address one mesh)
-    // The per-mesh entries (rt_mesh_*_of): one record per mesh with triangles, in object order.  Filled only by an upload (or a rebuild) that returned RT_OK and
-    // invalidated at the top of every rt_scene_upload*: after a failed upload the entries answer RT_ERR_NO_SCENE instead of acting on the previous scene's ranges.
+    // One record per mesh WITH triangles, in object order: the only description of the scene's meshes (a one-mesh scene is a forest of one, without a synthetic node).
+    // Invariant: whenever have_scene is true, `parts` (and, for more than one part, forest_arr / pre_of) describe ctx->scene.  With more than one part the plain
+    // rt_mesh_set_normals / rebuild / set_texture are refused (the *_of entries address one mesh).  parts_valid: the last rt_scene_upload* (or rebuild) returned RT_OK; it is
+    // cleared at the top of every rt_scene_upload*, so that after a failed upload the *_of and texture entries answer RT_ERR_NO_SCENE (the plain entries look at have_scene alone).
     struct MeshPart {
         int obj;                                                    // object slot (position in Scene::objects)
         int voff, nv;                                               // vertex range in `verts`

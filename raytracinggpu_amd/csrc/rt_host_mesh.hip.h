@@ -1,5 +1,7 @@
-// rt_host_mesh.hip.h -- host side, part 4 of 4 (inside rt_capi.hip's extern "C" block): the entry points that change the uploaded mesh on the device -- smooth normals,
-// transform + refit, rebuild of the reference's tree, the LBVH builder and its device-side install; and the same for ONE mesh of a forest (rt_mesh_*_of).
+// rt_host_mesh.hip.h -- host side, part 4 of 4 (inside rt_capi.hip's extern "C" block): the entry points that change the uploaded meshes on the device -- smooth normals,
+// transform + refit, rebuild of the reference's tree, the LBVH builder and its device-side install.  ctx->parts is the one record of the meshes and a one-mesh scene is a forest
+// of one: every operation has ONE body, written over MeshPart ranges, and the public entries (plain: the scene's one mesh, for transform every mesh; rt_mesh_*_of: the mesh at an
+// object slot) check their own preconditions and call it.  Only the device-side LBVH install is special to a scene of one mesh.
 #pragma once
 
 // Every node box recomputed for the tree in use (refit_kernel: the forest's synthetic nodes widened as build_forest makes them), the root box and the box filter's
@@ -56,21 +58,44 @@ static void visit_range(const rtk::Scene &sc, int obj, int &vb, int &ve) {
         if (sc.mesh[k].obj == obj) { vb = sc.mesh[k].tri_begin; ve = k + 1 < sc.n_meshes ? sc.mesh[k + 1].tri_begin : sc.n_tris; }
 }
 
-// Textured meshes across a re-layout (the rebuild entries): the UVs the device holds in visit order before install_scene, and after it new visit rank t takes the
-// UVs of old visit rank old_visit[t] (-1: none) -- as the smooth normals travel with their triangles.
-static int tex_read_uv(rt_ctx *ctx, int n_tris, std::vector<float2> &uv) {
-    uv.clear();
-    if (ctx->tex_mask == 0 || n_tris <= 0) return RT_OK;
-    uv.resize(3 * (size_t)n_tris);
-    RT_HIP(ctx, hipMemcpy(uv.data(), ctx->tex_uv.p, uv.size() * sizeof(float2), hipMemcpyDeviceToHost));
+// One part's per-corner attribute (normals, UVs) in visit order: out[3 * (t - vb) + k] = the caller's index for corner k of the triangle at visit rank t of the part's range
+// [vb, ...); the caller's rows are in the part's own uploaded triangle order.  `what` names the attribute in the message; indices lie in [0, n_vals).
+static int gather_corners(rt_ctx *ctx, const rt_ctx::MeshPart &p, const char *what, const int32_t *idx, int index_stride, int n_triangles, int n_vals, int &vb, std::vector<int> &out) {
+    if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
+    int ve;
+    visit_range(ctx->scene, p.obj, vb, ve);
+    out.resize(3 * (size_t)(ve - vb));
+    for (int t = vb; t < ve; ++t) {
+        const int src = ctx->tri_perm[t] - p.tri_off;                               // the mesh's own triangle index, uploaded order
+        if (src < 0 || src >= p.nt) return fail(ctx, RT_ERR_INTERNAL, "visit rank %d is not a triangle of object %d", t, p.obj);
+        if (src >= n_triangles) return fail(ctx, RT_ERR_INVALID, "n_triangles %d does not cover the mesh at object_slot %d (%d triangles)", n_triangles, p.obj, p.nt);
+        for (int k = 0; k < 3; ++k) {
+            const int i = idx[(size_t)src * index_stride + k];
+            if (i < 0 || i >= n_vals) return fail(ctx, RT_ERR_INVALID, "triangle %d references %s %d outside [0,%d)", src, what, i, n_vals);
+            out[3 * (size_t)(t - vb) + k] = i;
+        }
+    }
     return RT_OK;
 }
-static int tex_relayout(rt_ctx *ctx, const std::vector<float2> &old_uv, const std::vector<int> &old_visit) {
-    if (ctx->tex_mask == 0 || old_uv.empty() || old_visit.empty()) return RT_OK;
-    std::vector<float2> nu(3 * old_visit.size(), make_float2(0.f, 0.f));
-    for (size_t t = 0; t < old_visit.size(); ++t)
-        if (old_visit[t] >= 0) for (int k = 0; k < 3; ++k) nu[3 * t + k] = old_uv[3 * (size_t)old_visit[t] + k];
-    return upload(ctx, ctx->tex_uv, nu.data(), nu.size() * sizeof(float2));
+
+// Smooth normals of one part: its range of `nrm` (one buffer for the scene, 3 normals per triangle in visit order; the entries of a flat mesh are never read) and its bit
+static int set_part_normals(rt_ctx *ctx, rt_ctx::MeshPart &p, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles) {
+    int vb;
+    std::vector<int> ni;
+    if (int rc = gather_corners(ctx, p, "normal", nidx, index_stride, n_triangles, n_normals, vb, ni); rc != RT_OK) return rc;
+    std::vector<float4> nr(ni.size());
+    for (size_t i = 0; i < ni.size(); ++i) nr[i] = make_float4(normals_xyz[3 * (size_t)ni[i]], normals_xyz[3 * (size_t)ni[i] + 1], normals_xyz[3 * (size_t)ni[i] + 2], 0.f);
+    rtk::Scene &sc = ctx->scene;
+    const size_t bytes = 3 * (size_t)sc.n_tris * sizeof(float4);
+    if (sc.nrm == nullptr) {
+        if (int rc = ensure(ctx, ctx->nrm, bytes); rc != RT_OK) return rc;
+        RT_HIP(ctx, hipMemset(ctx->nrm.p, 0, bytes));
+    }
+    if (!nr.empty()) RT_HIP(ctx, hipMemcpy(static_cast<float4 *>(ctx->nrm.p) + 3 * (size_t)vb, nr.data(), nr.size() * sizeof(float4), hipMemcpyHostToDevice));
+    p.smooth = true;
+    sc.smooth_mask |= 1 << p.obj;
+    sc.nrm = static_cast<const float4 *>(ctx->nrm.p);
+    return RT_OK;
 }
 
 int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles) {
@@ -84,26 +109,56 @@ int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, co
         for (rt_ctx::MeshPart &p : ctx->parts) p.smooth = false;
         return RT_OK;
     }
-    if (ctx->n_real_meshes > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: smooth normals are set for ONE TriangleMesh", ctx->n_real_meshes);
-    if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
+    if (ctx->parts.size() > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: smooth normals are set for ONE TriangleMesh", (int)ctx->parts.size());
     if (ctx->scene.mesh_slot < 0) return fail(ctx, RT_ERR_INVALID, "the scene has no mesh");
     if (n_normals <= 0 || index_stride < 3) return fail(ctx, RT_ERR_INVALID, "bad normal array sizes");
-    std::vector<float4> nr(ctx->tri_perm.size() * 3);
-    for (size_t t = 0; t < ctx->tri_perm.size(); ++t) {
-        const int src = ctx->tri_perm[t];
-        if (src < 0 || src >= n_triangles) return fail(ctx, RT_ERR_INVALID, "n_triangles %d does not cover the uploaded mesh", n_triangles);
-        for (int k = 0; k < 3; ++k) {
-            const int ni = nidx[(size_t)src * index_stride + k];
-            if (ni < 0 || ni >= n_normals) return fail(ctx, RT_ERR_INVALID, "triangle %d references normal %d outside [0,%d)", src, ni, n_normals);
-            nr[3 * t + k] = make_float4(normals_xyz[3 * (size_t)ni], normals_xyz[3 * (size_t)ni + 1], normals_xyz[3 * (size_t)ni + 2], 0.f);
-        }
+    if (ctx->parts.empty()) return RT_OK;                                         // a mesh without triangles: never hit, nothing to shade
+    return set_part_normals(ctx, ctx->parts[0], normals_xyz, n_normals, nidx, index_stride, n_triangles);
+}
+
+int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!p) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    if (!normals_xyz || !nidx) {                                                    // this mesh flat again
+        rtk::Scene &sc = ctx->scene;
+        p->smooth = false;
+        sc.smooth_mask &= ~(1 << object_slot);
+        if (sc.smooth_mask == 0) sc.nrm = nullptr;                                  // no smooth mesh left: the frames take the flat branch as before
+        return RT_OK;
     }
-    int rc = upload(ctx, ctx->nrm, nr.data(), nr.size() * sizeof(float4));
-    if (rc != RT_OK) return rc;
-    ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
-    ctx->scene.smooth_mask = ctx->real_obj >= 0 ? 1 << ctx->real_obj : 0;             // the scene's one mesh
-    for (rt_ctx::MeshPart &p : ctx->parts) p.smooth = true;
-    return RT_OK;
+    if (n_normals <= 0 || index_stride < 3) return fail(ctx, RT_ERR_INVALID, "bad normal array sizes");
+    return set_part_normals(ctx, *p, normals_xyz, n_normals, nidx, index_stride, n_triangles);
+}
+
+// The reference's transformMesh (global_launcher.cu:932-946) on the parts [first, last): each part's vertices, its normals if it is smooth (rotated AND translated, as the
+// reference's kernel does: global_launcher.cu:357-363; a flat part's slots of `nrm` are read by nothing and rewritten whole when it turns smooth), the triangle records of its
+// visit range; then the whole-forest refit.
+static int transform_parts(rt_ctx *ctx, size_t first, size_t last, const float rotation[9], const float translation[3]) {
+    rtk::Scene &sc = ctx->scene;
+    if (sc.n_nodes <= 0 || sc.n_verts <= 0) return RT_OK;                           // no mesh, or no triangle in any leaf: nothing to move or refit
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    rtk::Mat3 m;
+    for (int k = 0; k < 9; ++k) m.r[k] = rotation[k];
+    for (int k = 0; k < 3; ++k) m.t[k] = translation[k];
+    hipStream_t q = own_stream(ctx);
+    for (size_t k = first; k < last; ++k) {
+        const rt_ctx::MeshPart &p = ctx->parts[k];
+        int vb, ve;
+        visit_range(sc, p.obj, vb, ve);
+        hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((p.nv + 255) / 256)), dim3(256), 0, q, static_cast<float4 *>(ctx->verts.p) + p.voff, p.nv, m);
+        if (ve <= vb) continue;
+        if (p.smooth && sc.nrm != nullptr)
+            hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((3 * (ve - vb) + 255) / 256)), dim3(256), 0, q, static_cast<float4 *>(ctx->nrm.p) + 3 * (size_t)vb, 3 * (ve - vb), m);
+        hipLaunchKernelGGL(rtk::retri_kernel, dim3((unsigned)((ve - vb + 255) / 256)), dim3(256), 0, q,
+                           static_cast<const int4 *>(ctx->tidx.p) + vb, static_cast<const float4 *>(ctx->verts.p), static_cast<float4 *>(ctx->tri.p) + 3 * (size_t)vb, ve - vb);
+    }
+    RT_HIP(ctx, hipGetLastError());
+    return refit_and_requantize(ctx);
 }
 
 int rt_mesh_transform(rt_ctx *ctx, const float rotation[9], const float translation[3]) {
@@ -111,20 +166,18 @@ int rt_mesh_transform(rt_ctx *ctx, const float rotation[9], const float translat
     RT_OWN_STREAM(ctx);
     if (!rotation || !translation) return fail(ctx, RT_ERR_INVALID, "rotation/translation is NULL");
     if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
-    rtk::Scene &sc = ctx->scene;
-    if (sc.mesh_slot < 0 || sc.n_nodes <= 0 || sc.n_verts <= 0) return RT_OK;     // no mesh: nothing to move
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    rtk::Mat3 m;
-    for (int k = 0; k < 9; ++k) m.r[k] = rotation[k];
-    for (int k = 0; k < 3; ++k) m.t[k] = translation[k];
-    hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((sc.n_verts + 255) / 256)), dim3(256), 0, own_stream(ctx),
-                       static_cast<float4 *>(ctx->verts.p), sc.n_verts, m);
-    if (sc.nrm != nullptr)      // the reference's kernel rotates the normals and ADDS the translation to them as well (global_launcher.cu:357-363)
-        hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((3 * sc.n_tris + 255) / 256)), dim3(256), 0, own_stream(ctx),
-                           static_cast<float4 *>(ctx->nrm.p), 3 * sc.n_tris, m);
-    hipLaunchKernelGGL(rtk::retri_kernel, dim3((unsigned)((sc.n_tris + 255) / 256)), dim3(256), 0, own_stream(ctx),
-                       static_cast<const int4 *>(ctx->tidx.p), static_cast<const float4 *>(ctx->verts.p), static_cast<float4 *>(ctx->tri.p), sc.n_tris);
-    return refit_and_requantize(ctx);
+    return transform_parts(ctx, 0, ctx->parts.size(), rotation, translation);      // every mesh
+}
+
+int rt_mesh_transform_of(rt_ctx *ctx, int object_slot, const float rotation[9], const float translation[3]) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!rotation || !translation) return fail(ctx, RT_ERR_INVALID, "rotation/translation is NULL");
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!p) return RT_OK;                                                           // a mesh without triangles: nothing to move
+    const size_t k = p - ctx->parts.data();
+    return transform_parts(ctx, k, k + 1, rotation, translation);
 }
 
 // TriangleMesh::buildBVH on the device, bit for bit (rt_bvhbuild.hip.h): leaves the flat tree in ctx->bb_arr and the triangle order in ctx->bb_idx
@@ -264,7 +317,7 @@ static int rebuild_lbvh_tree(rt_ctx *ctx, const int nt, int &n_nodes_out, const 
 }
 
 // The render kernels' formats from the LBVH builder's arrays, on the device (rt_lbvh.hip.h, second half): what install_scene does on the
-// host for an uploaded tree.  `old`: the scene in use (spheres, light, camera, albedo, mesh slot carry over).
+// host for an uploaded tree.  A scene of ONE part only (the builder ran over the whole of tidx_up).  `old`: the scene in use (spheres, light, camera, albedo, mesh slot carry over).
 static int install_lbvh_device(rt_ctx *ctx, const rtk::Scene &old, const int n_nodes) {
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t q = own_stream(ctx);
@@ -336,7 +389,8 @@ static int install_lbvh_device(rt_ctx *ctx, const rtk::Scene &old, const int n_n
     sc.nrm = nullptr; sc.smooth_mask = 0;
     ctx->n_syn = 0;                                                              // (one mesh: no synthetic nodes)
     sc.n_nodes = n_nodes; sc.n_tris = (int)n;
-    mesh_table_single(sc, ctx->real_obj);
+    mesh_table_single(sc, ctx->parts[0].obj);
+    ctx->parts[0].nn = n_nodes;                                                  // (the part's vertex and triangle ranges stay)
     sc.root_lo = root[0]; sc.root_hi = root[1];
     bool fast = true;
     const float rv[6] = {root[0].x, root[0].y, root[0].z, root[1].x, root[1].y, root[1].z};
@@ -360,192 +414,36 @@ static int install_lbvh_device(rt_ctx *ctx, const rtk::Scene &old, const int n_n
     return requantize(ctx, q);
 }
 
-int rt_mesh_rebuild_mode(rt_ctx *ctx, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (mode != RT_BVH_REFERENCE && mode != RT_BVH_LBVH) return fail(ctx, RT_ERR_INVALID, "unknown BVH mode %d", mode);
-    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
-    if (n_nodes_out) *n_nodes_out = 0;
-    const rtk::Scene old = ctx->scene;
-    const int nt = ctx->n_up_tris, nv = old.n_verts;
-    if (ctx->n_real_meshes > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: a rebuild works on ONE TriangleMesh (upload the rebuilt meshes again)", ctx->n_real_meshes);
-    if (old.mesh_slot < 0 || ctx->real_obj < 0 || nt <= 0 || nv <= 0) return RT_OK;  // no mesh: nothing to build
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t q = own_stream(ctx);
-    int rc;
-    int n_nodes = 0;
-    ctx->build = rt_build_stats{};
-    hipEvent_t e0 = ctx->ev_t0, e1 = ctx->ev_t1;                                    // (the tone-mapping events are free here: nothing else runs on the stream)
-    RT_HIP(ctx, hipEventRecord(e0, q));
-    // a mesh of a single leaf's worth of triangles is a single leaf in either mode (cpu:217: fewer than five triangles are never split)
-    if (mode == RT_BVH_LBVH && nt > 4) rc = rebuild_lbvh_tree(ctx, nt, n_nodes);
-    else { mode = RT_BVH_REFERENCE; rc = rebuild_reference_tree(ctx, nt, n_nodes); }
-    if (rc != RT_OK) return rc;
-    RT_HIP(ctx, hipEventRecord(e1, q));
-    RT_HIP(ctx, hipEventSynchronize(e1));
-    RT_HIP(ctx, hipEventElapsedTime(&ctx->build.device_build_ms, e0, e1));
-    ctx->have_tonemap_time = false;                                                 // (the borrowed events no longer bracket a tone mapping)
-    ctx->build.mode = mode; ctx->build.n_nodes = n_nodes; ctx->build.n_triangles = nt;
-    const auto t_install = std::chrono::steady_clock::now();
-    int *const order_dev = static_cast<int *>(ctx->bb_idx.p);
-    if (mode == RT_BVH_LBVH && old.nrm == nullptr && ctx->tex_mask == 0 && !ctx->lbvh_host_install && ctx->build.max_depth <= 56) {   // (normals and UVs travel on the host path)
-        // the kernels' formats straight from the builder's arrays; the flat tree and the order travel to the host only if the caller asks
-        if ((rc = install_lbvh_device(ctx, old, n_nodes)) != RT_OK) return rc;
-        if (bvh_arr10_out) RT_HIP(ctx, hipMemcpyAsync(bvh_arr10_out, ctx->bb_arr.p, (size_t)n_nodes * 10 * sizeof(float), hipMemcpyDeviceToHost, q));
-        if (tri_order_out) RT_HIP(ctx, hipMemcpyAsync(tri_order_out, order_dev, (size_t)nt * sizeof(int), hipMemcpyDeviceToHost, q));
-        RT_HIP(ctx, hipStreamSynchronize(q));
-        if (n_nodes_out) *n_nodes_out = n_nodes;
-        ctx->build.install_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_install).count();
-        ctx->build.install_on_device = 1;
-        return RT_OK;
+// old_visit[t]: the visit rank, before a rebuild of part P re-laid the scene out, of the triangle now at visit rank t (-1: it had none).  old_perm: tri_perm as it was;
+// order: the builder's order of P's triangles (new uploaded index -> old one, both in P's own space); the other parts keep their uploaded order.
+static std::vector<int> old_visit_ranks(const rt_ctx *ctx, const std::vector<int> &old_perm, const rt_ctx::MeshPart &P, const std::vector<int> &order) {
+    std::vector<int> old_visit_of(ctx->n_up_tris, -1), old_visit(ctx->tri_perm.size());
+    for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
+    for (size_t t = 0; t < old_visit.size(); ++t) {
+        const int g = ctx->tri_perm[t];
+        old_visit[t] = old_visit_of[g >= P.tri_off && g < P.tri_off + P.nt ? P.tri_off + order[g - P.tri_off] : g];
     }
-    if ((rc = refresh_host_mesh(ctx)) != RT_OK) return rc;                          // the host path below starts from up_indices / tri_perm
-    // The tree is built.  The O(n) re-layout for the kernels (traversal order, visit-order triangle records, sibling pairs, refit
-    // levels) reuses the upload path on the host: ~30 bytes per triangle over PCIe each way.
-    std::vector<float> arr((size_t)n_nodes * 10);
-    std::vector<int> order(nt);
-    std::vector<float4> hv(nv);
-    RT_HIP(ctx, hipMemcpyAsync(arr.data(), ctx->bb_arr.p, arr.size() * sizeof(float), hipMemcpyDeviceToHost, q));
-    RT_HIP(ctx, hipMemcpyAsync(order.data(), order_dev, order.size() * sizeof(int), hipMemcpyDeviceToHost, q));
-    RT_HIP(ctx, hipMemcpyAsync(hv.data(), ctx->verts.p, hv.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
-    std::vector<float4> old_nrm;
-    if (old.nrm != nullptr) {
-        old_nrm.resize((size_t)old.n_tris * 3);
-        RT_HIP(ctx, hipMemcpyAsync(old_nrm.data(), ctx->nrm.p, old_nrm.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
-    }
-    RT_HIP(ctx, hipStreamSynchronize(q));
-    std::vector<float2> old_uv;
-    if ((rc = tex_read_uv(ctx, old.n_tris, old_uv)) != RT_OK) return rc;
-    std::vector<float> vx((size_t)nv * 3);
-    for (int i = 0; i < nv; ++i) { vx[3 * (size_t)i] = hv[i].x; vx[3 * (size_t)i + 1] = hv[i].y; vx[3 * (size_t)i + 2] = hv[i].z; }
-    std::vector<int32_t> ix((size_t)nt * 3);
-    for (int t = 0; t < nt; ++t) for (int k = 0; k < 3; ++k) ix[3 * (size_t)t + k] = ctx->up_indices[3 * (size_t)order[t] + k];
-    const std::vector<int> old_perm = ctx->tri_perm;                               // old visit order -> old uploaded order
-    rt_mesh m{};
-    m.vertices = vx.data(); m.n_vertices = nv; m.indices = ix.data(); m.index_stride = 3; m.n_triangles = nt;
-    m.bvh_arr10 = arr.data(); m.n_nodes = n_nodes;
-    m.object_slot = ctx->real_obj;                                                  // (albedo and material stay in the scene's mesh table, which `sc` carries over)
-    rtk::Scene sc = old;
-    sc.n_nodes = sc.n_tris = sc.n_verts = 0; sc.nrm = nullptr;
-    if ((rc = install_scene(ctx, sc, &m)) != RT_OK) return rc;
-    if (!old_nrm.empty()) {                                                        // smooth normals travel with their triangles
-        std::vector<int> old_visit_of(nt, -1);
-        for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
-        std::vector<float4> nn(ctx->tri_perm.size() * 3);
-        for (size_t t = 0; t < ctx->tri_perm.size(); ++t) {
-            const int ov = old_visit_of[order[ctx->tri_perm[t]]];
-            for (int k = 0; k < 3; ++k) nn[3 * t + k] = ov >= 0 ? old_nrm[3 * (size_t)ov + k] : make_float4(0, 0, 0, 0);
-        }
-        if ((rc = upload(ctx, ctx->nrm, nn.data(), nn.size() * sizeof(float4))) != RT_OK) return rc;
-        ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
-    }
-    if (!old_uv.empty()) {                                                         // UVs travel with their triangles
-        std::vector<int> old_visit_of(nt, -1), old_visit(ctx->tri_perm.size());
-        for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
-        for (size_t t = 0; t < ctx->tri_perm.size(); ++t) old_visit[t] = old_visit_of[order[ctx->tri_perm[t]]];
-        if ((rc = tex_relayout(ctx, old_uv, old_visit)) != RT_OK) return rc;
-    }
-    if (bvh_arr10_out) memcpy(bvh_arr10_out, arr.data(), arr.size() * sizeof(float));
-    if (tri_order_out) memcpy(tri_order_out, order.data(), order.size() * sizeof(int));
-    if (n_nodes_out) *n_nodes_out = n_nodes;
-    ctx->build.install_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_install).count();
-    return RT_OK;
+    return old_visit;
 }
 
-int rt_mesh_rebuild(rt_ctx *ctx, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
-    return rt_mesh_rebuild_mode(ctx, RT_BVH_REFERENCE, bvh_arr10_out, tri_order_out, n_nodes_out);
+// A per-corner attribute (smooth normals, UVs) travels with its triangles: new visit rank t takes the three entries of old visit rank old_visit[t], zeros where it had none
+// (a template inside the entry points' extern "C" block: C++ linkage said aloud)
+extern "C++" template <class T> static std::vector<T> carry_corners(const std::vector<T> &old, const std::vector<int> &old_visit) {
+    std::vector<T> out(3 * old_visit.size());                                       // (value-initialised: zeros)
+    for (size_t t = 0; t < old_visit.size(); ++t)
+        if (old_visit[t] >= 0) for (int k = 0; k < 3; ++k) out[3 * t + k] = old[3 * (size_t)old_visit[t] + k];
+    return out;
 }
 
-// ---- ONE mesh of the scene, addressed by its object slot (the reference's TriangleMesh in Scene::objects: its own vertices, normals and tree).  On a scene with one
-// mesh these are the plain entries; on a forest they act on the mesh's ranges and leave every other mesh as the device holds it.
-
-int rt_mesh_transform_of(rt_ctx *ctx, int object_slot, const float rotation[9], const float translation[3]) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (!rotation || !translation) return fail(ctx, RT_ERR_INVALID, "rotation/translation is NULL");
-    rt_ctx::MeshPart *p = nullptr;
-    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
-    if (!p) return RT_OK;                                                           // a mesh without triangles: nothing to move
-    if (ctx->n_real_meshes <= 1) return rt_mesh_transform(ctx, rotation, translation);
-    rtk::Scene &sc = ctx->scene;
-    int vb, ve;
-    visit_range(sc, object_slot, vb, ve);
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    rtk::Mat3 m;
-    for (int k = 0; k < 9; ++k) m.r[k] = rotation[k];
-    for (int k = 0; k < 3; ++k) m.t[k] = translation[k];
-    hipStream_t q = own_stream(ctx);
-    // the reference's transformMesh on this mesh's arrays (global_launcher.cu:932-946): its vertices, its normals (translation added, global_launcher.cu:357-363), its triangle records
-    hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((p->nv + 255) / 256)), dim3(256), 0, q, static_cast<float4 *>(ctx->verts.p) + p->voff, p->nv, m);
-    if (ve > vb) {
-        if (p->smooth && sc.nrm != nullptr)
-            hipLaunchKernelGGL(rtk::transform_kernel, dim3((unsigned)((3 * (ve - vb) + 255) / 256)), dim3(256), 0, q, static_cast<float4 *>(ctx->nrm.p) + 3 * (size_t)vb, 3 * (ve - vb), m);
-        hipLaunchKernelGGL(rtk::retri_kernel, dim3((unsigned)((ve - vb + 255) / 256)), dim3(256), 0, q,
-                           static_cast<const int4 *>(ctx->tidx.p) + vb, static_cast<const float4 *>(ctx->verts.p), static_cast<float4 *>(ctx->tri.p) + 3 * (size_t)vb, ve - vb);
-    }
-    RT_HIP(ctx, hipGetLastError());
-    return refit_and_requantize(ctx);
-}
-
-int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    rt_ctx::MeshPart *p = nullptr;
-    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
-    if (!p) return RT_OK;
-    if (ctx->n_real_meshes <= 1) return rt_mesh_set_normals(ctx, normals_xyz, n_normals, nidx, index_stride, n_triangles);
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    rtk::Scene &sc = ctx->scene;
-    const int bit = 1 << object_slot;
-    if (!normals_xyz || !nidx) {                                                    // this mesh flat again
-        p->smooth = false;
-        sc.smooth_mask &= ~bit;
-        if (sc.smooth_mask == 0) sc.nrm = nullptr;                                  // no smooth mesh left: the frames take the flat branch as before
-        return RT_OK;
-    }
-    if (n_normals <= 0 || index_stride < 3) return fail(ctx, RT_ERR_INVALID, "bad normal array sizes");
-    if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
-    int vb, ve;
-    visit_range(sc, object_slot, vb, ve);
-    std::vector<float4> nr(3 * (size_t)(ve - vb));
-    for (int t = vb; t < ve; ++t) {
-        const int src = ctx->tri_perm[t] - p->tri_off;                              // the mesh's own triangle index, uploaded order
-        if (src < 0 || src >= p->nt) return fail(ctx, RT_ERR_INTERNAL, "forest layout: visit rank %d is not a triangle of object %d", t, object_slot);
-        if (src >= n_triangles) return fail(ctx, RT_ERR_INVALID, "n_triangles %d does not cover the mesh at object_slot %d (%d triangles)", n_triangles, object_slot, p->nt);
-        for (int k = 0; k < 3; ++k) {
-            const int ni = nidx[(size_t)src * index_stride + k];
-            if (ni < 0 || ni >= n_normals) return fail(ctx, RT_ERR_INVALID, "triangle %d references normal %d outside [0,%d)", src, ni, n_normals);
-            nr[3 * (size_t)(t - vb) + k] = make_float4(normals_xyz[3 * (size_t)ni], normals_xyz[3 * (size_t)ni + 1], normals_xyz[3 * (size_t)ni + 2], 0.f);
-        }
-    }
-    // one buffer for the forest (3 normals per triangle, visit order); the entries of a flat mesh are never read
-    const size_t bytes = 3 * (size_t)sc.n_tris * sizeof(float4);
-    if (sc.nrm == nullptr) {
-        if (int rc = ensure(ctx, ctx->nrm, bytes); rc != RT_OK) return rc;
-        RT_HIP(ctx, hipMemset(ctx->nrm.p, 0, bytes));
-    }
-    if (!nr.empty()) RT_HIP(ctx, hipMemcpy(static_cast<float4 *>(ctx->nrm.p) + 3 * (size_t)vb, nr.data(), nr.size() * sizeof(float4), hipMemcpyHostToDevice));
-    p->smooth = true;
-    sc.smooth_mask |= bit;
-    sc.nrm = static_cast<const float4 *>(ctx->nrm.p);
-    return RT_OK;
-}
-
-int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (mode != RT_BVH_REFERENCE && mode != RT_BVH_LBVH) return fail(ctx, RT_ERR_INVALID, "unknown BVH mode %d", mode);
-    rt_ctx::MeshPart *pp = nullptr;
-    if (int rc = find_part(ctx, object_slot, pp); rc != RT_OK) return rc;
-    if (n_nodes_out) *n_nodes_out = 0;
-    if (!pp) return RT_OK;                                                          // a mesh without triangles: nothing to build
-    if (ctx->n_real_meshes <= 1) return rt_mesh_rebuild_mode(ctx, mode, bvh_arr10_out, tri_order_out, n_nodes_out);
-    const rt_ctx::MeshPart P = *pp;
+// Part pi rebuilt in `mode` over its triangles (tidx_up + tri_off) and the vertices as they are on the device now; every other part keeps its tree, with the boxes the device
+// holds (refitted or as uploaded).  The outputs are in the part's own index space.
+static int rebuild_part(rt_ctx *ctx, size_t pi, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
     const std::vector<rt_ctx::MeshPart> parts = ctx->parts;
+    const rt_ctx::MeshPart P = parts[pi];
     const rtk::Scene old = ctx->scene;
     const int K = (int)parts.size();
-    if (ctx->forest_arr.size() != (size_t)old.n_nodes * 10 || ctx->pre_of.size() != (size_t)old.n_nodes || K != ctx->n_real_meshes)
+    const bool was_valid = ctx->parts_valid;
+    if (K > 1 && (ctx->forest_arr.size() != (size_t)old.n_nodes * 10 || ctx->pre_of.size() != (size_t)old.n_nodes))
         return fail(ctx, RT_ERR_INTERNAL, "forest records do not match the tree in use");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t q = own_stream(ctx);
@@ -554,41 +452,60 @@ int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_
     ctx->build = rt_build_stats{};
     hipEvent_t e0 = ctx->ev_t0, e1 = ctx->ev_t1;                                    // (the tone-mapping events are free here: nothing else runs on the stream)
     RT_HIP(ctx, hipEventRecord(e0, q));
-    // this mesh's triangles only (tidx_up + tri_off); the builders read the vertices as they are on the device now
+    // a mesh of a single leaf's worth of triangles is a single leaf in either mode (cpu:217: fewer than five triangles are never split)
     if (mode == RT_BVH_LBVH && P.nt > 4) rc = rebuild_lbvh_tree(ctx, P.nt, n_nodes, P.tri_off);
     else { mode = RT_BVH_REFERENCE; rc = rebuild_reference_tree(ctx, P.nt, n_nodes, P.tri_off); }
     if (rc != RT_OK) return rc;
     RT_HIP(ctx, hipEventRecord(e1, q));
     RT_HIP(ctx, hipEventSynchronize(e1));
     RT_HIP(ctx, hipEventElapsedTime(&ctx->build.device_build_ms, e0, e1));
-    ctx->have_tonemap_time = false;
+    ctx->have_tonemap_time = false;                                                 // (the borrowed events no longer bracket a tone mapping)
     ctx->build.mode = mode; ctx->build.n_nodes = n_nodes; ctx->build.n_triangles = P.nt;
     const auto t_install = std::chrono::steady_clock::now();
-    if ((rc = refresh_host_mesh(ctx)) != RT_OK) return rc;
-    // what the device holds: the new tree and order, every vertex, every node box (the other meshes keep theirs: refitted or as uploaded), the normals
+    int *const order_dev = static_cast<int *>(ctx->bb_idx.p);
+    // (normals and UVs travel on the host path; so does a forest: no device-side install of several meshes)
+    if (K == 1 && mode == RT_BVH_LBVH && old.nrm == nullptr && ctx->tex_mask == 0 && !ctx->lbvh_host_install && ctx->build.max_depth <= 56) {
+        // the kernels' formats straight from the builder's arrays; the flat tree and the order travel to the host only if the caller asks
+        if ((rc = install_lbvh_device(ctx, old, n_nodes)) != RT_OK) return rc;
+        if (bvh_arr10_out) RT_HIP(ctx, hipMemcpyAsync(bvh_arr10_out, ctx->bb_arr.p, (size_t)n_nodes * 10 * sizeof(float), hipMemcpyDeviceToHost, q));
+        if (tri_order_out) RT_HIP(ctx, hipMemcpyAsync(tri_order_out, order_dev, (size_t)P.nt * sizeof(int), hipMemcpyDeviceToHost, q));
+        RT_HIP(ctx, hipStreamSynchronize(q));
+        if (n_nodes_out) *n_nodes_out = n_nodes;
+        ctx->build.install_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_install).count();
+        ctx->build.install_on_device = 1;
+        return RT_OK;
+    }
+    if ((rc = refresh_host_mesh(ctx)) != RT_OK) return rc;                          // the host path below starts from up_indices / tri_perm
+    // The tree is built.  The O(n) re-layout for the kernels (traversal order, visit-order triangle records, sibling pairs, refit levels) reuses the upload path on the
+    // host: ~30 bytes per triangle over PCIe each way.  What the device holds: the new tree and order, every vertex, the normals and UVs, and for a forest every node box.
     std::vector<float> arr((size_t)n_nodes * 10);
     std::vector<int> order(P.nt);
-    std::vector<float4> hv(old.n_verts), nlo(old.n_nodes), nhi(old.n_nodes), old_nrm;
+    std::vector<float4> hv(old.n_verts), nlo(K > 1 ? old.n_nodes : 0), nhi(nlo.size()), old_nrm;
     RT_HIP(ctx, hipMemcpyAsync(arr.data(), ctx->bb_arr.p, arr.size() * sizeof(float), hipMemcpyDeviceToHost, q));
-    RT_HIP(ctx, hipMemcpyAsync(order.data(), ctx->bb_idx.p, order.size() * sizeof(int), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipMemcpyAsync(order.data(), order_dev, order.size() * sizeof(int), hipMemcpyDeviceToHost, q));
     RT_HIP(ctx, hipMemcpyAsync(hv.data(), ctx->verts.p, hv.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
-    RT_HIP(ctx, hipMemcpyAsync(nlo.data(), ctx->node_lo.p, nlo.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
-    RT_HIP(ctx, hipMemcpyAsync(nhi.data(), ctx->node_hi.p, nhi.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
+    if (!nlo.empty()) {
+        RT_HIP(ctx, hipMemcpyAsync(nlo.data(), ctx->node_lo.p, nlo.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
+        RT_HIP(ctx, hipMemcpyAsync(nhi.data(), ctx->node_hi.p, nhi.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
+    }
     if (old.nrm != nullptr) {
         old_nrm.resize((size_t)old.n_tris * 3);
         RT_HIP(ctx, hipMemcpyAsync(old_nrm.data(), ctx->nrm.p, old_nrm.size() * sizeof(float4), hipMemcpyDeviceToHost, q));
     }
     RT_HIP(ctx, hipStreamSynchronize(q));
     std::vector<float2> old_uv;
-    if ((rc = tex_read_uv(ctx, old.n_tris, old_uv)) != RT_OK) return rc;
-    // every mesh in its own index space, in object order, as build_forest takes them from rt_scene_upload_meshes
+    if (ctx->tex_mask != 0 && old.n_tris > 0) {
+        old_uv.resize(3 * (size_t)old.n_tris);
+        RT_HIP(ctx, hipMemcpy(old_uv.data(), ctx->tex_uv.p, old_uv.size() * sizeof(float2), hipMemcpyDeviceToHost));
+    }
+    // every mesh in its own index space, in object order, as rt_scene_upload_meshes receives them
     std::vector<std::vector<float>> vx(K), ar(K);
     std::vector<std::vector<int32_t>> ix(K);
     std::vector<rt_mesh> ms(K);
     std::vector<int> real(K);
     for (int k = 0; k < K; ++k) {
         const rt_ctx::MeshPart &Q = parts[k];
-        const bool me = Q.obj == P.obj;
+        const bool me = k == (int)pi;
         vx[k].resize((size_t)Q.nv * 3);
         for (int i = 0; i < Q.nv; ++i) { const float4 v = hv[(size_t)Q.voff + i]; vx[k][3 * (size_t)i] = v.x; vx[k][3 * (size_t)i + 1] = v.y; vx[k][3 * (size_t)i + 2] = v.z; }
         ix[k].resize((size_t)Q.nt * 3);
@@ -596,9 +513,7 @@ int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_
             const int src = me ? order[t] : t;                                      // the rebuilt mesh: its triangles in the builder's order
             for (int c = 0; c < 3; ++c) ix[k][3 * (size_t)t + c] = ctx->up_indices[3 * ((size_t)Q.tri_off + src) + c] - Q.voff;
         }
-        if (me) {
-            ar[k] = arr;
-        } else {                                                                    // its tree as installed, the boxes the device holds now
+        if (!me) {                                                                  // its tree as installed, the boxes the device holds now
             ar[k].resize((size_t)Q.nn * 10);
             for (int n = 0; n < Q.nn; ++n) {
                 const float *a = ctx->forest_arr.data() + ((size_t)Q.noff + n) * 10;
@@ -612,53 +527,59 @@ int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_
         rt_mesh &m = ms[k];
         m = rt_mesh{};
         m.vertices = vx[k].data(); m.n_vertices = Q.nv; m.indices = ix[k].data(); m.index_stride = 3; m.n_triangles = Q.nt;
-        m.bvh_arr10 = ar[k].data(); m.n_nodes = (int)(ar[k].size() / 10);
+        m.bvh_arr10 = me ? arr.data() : ar[k].data(); m.n_nodes = me ? n_nodes : Q.nn;
         m.object_slot = Q.obj;                                                      // (albedo and material stay in the scene's mesh table, which `sc` carries over)
         real[k] = k;
-    }
-    Forest f;
-    if ((rc = build_forest(ctx, ms.data(), real, f)) != RT_OK) return rc;
-    std::vector<int> offs(old.n_meshes + 1, f.tri_off[K]);                         // as rt_scene_upload_meshes: table entry -> first triangle (a mesh without triangles: the next real one's)
-    for (int k = old.n_meshes - 1, r = K - 1; k >= 0; --k) {
-        if (r >= 0 && old.mesh[k].obj == parts[r].obj) { offs[k] = f.tri_off[r]; --r; }
-        else offs[k] = offs[k + 1];
     }
     const std::vector<int> old_perm = ctx->tri_perm;                               // old visit order -> old uploaded order
     rtk::Scene sc = old;
     sc.n_nodes = sc.n_tris = sc.n_verts = 0; sc.nrm = nullptr;
-    ctx->parts_valid = false;
-    if ((rc = install_scene(ctx, sc, &f.m, &offs, K - 1)) != RT_OK) return rc;
-    ctx->parts = parts;                                                             // vertex and triangle ranges keep their sizes; the rebuilt mesh's node count changes
-    for (int k = 0; k < K; ++k) { ctx->parts[k].noff = f.noff[k]; ctx->parts[k].nn = ms[k].n_nodes; }
-    ctx->forest_arr = std::move(f.arr);
-    ctx->parts_valid = true;
-    if (!old_nrm.empty()) {                                                        // smooth normals travel with their triangles, every mesh's
-        std::vector<int> old_visit_of(ctx->n_up_tris, -1);
-        for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
-        std::vector<float4> nn(ctx->tri_perm.size() * 3, make_float4(0, 0, 0, 0));
-        for (size_t t = 0; t < ctx->tri_perm.size(); ++t) {
-            const int g = ctx->tri_perm[t];
-            const int g_old = g >= P.tri_off && g < P.tri_off + P.nt ? P.tri_off + order[g - P.tri_off] : g;
-            const int ov = old_visit_of[g_old];
-            for (int k = 0; k < 3; ++k) if (ov >= 0) nn[3 * t + k] = old_nrm[3 * (size_t)ov + k];
+    if ((rc = install_meshes(ctx, sc, ms.data(), real)) != RT_OK) return rc;
+    ctx->parts_valid = was_valid;                                                   // (a plain rebuild after a failed upload does not make the *_of entries answer again)
+    for (int k = 0; k < K; ++k) ctx->parts[k].smooth = parts[k].smooth;            // ranges keep their sizes; the rebuilt mesh's node count changed
+    if (!old_nrm.empty() || !old_uv.empty()) {                                     // smooth normals and UVs travel with their triangles, every mesh's
+        const std::vector<int> old_visit = old_visit_ranks(ctx, old_perm, P, order);
+        if (!old_nrm.empty()) {
+            const std::vector<float4> nn = carry_corners(old_nrm, old_visit);
+            if ((rc = upload(ctx, ctx->nrm, nn.data(), nn.size() * sizeof(float4))) != RT_OK) return rc;
+            ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
         }
-        if ((rc = upload(ctx, ctx->nrm, nn.data(), nn.size() * sizeof(float4))) != RT_OK) return rc;
-        ctx->scene.nrm = static_cast<const float4 *>(ctx->nrm.p);
-    }
-    if (!old_uv.empty()) {                                                         // UVs travel with their triangles, every textured mesh's
-        std::vector<int> old_visit_of(ctx->n_up_tris, -1), old_visit(ctx->tri_perm.size());
-        for (size_t t = 0; t < old_perm.size(); ++t) old_visit_of[old_perm[t]] = (int)t;
-        for (size_t t = 0; t < ctx->tri_perm.size(); ++t) {
-            const int g = ctx->tri_perm[t];
-            old_visit[t] = old_visit_of[g >= P.tri_off && g < P.tri_off + P.nt ? P.tri_off + order[g - P.tri_off] : g];
+        if (!old_uv.empty()) {
+            const std::vector<float2> nu = carry_corners(old_uv, old_visit);
+            if ((rc = upload(ctx, ctx->tex_uv, nu.data(), nu.size() * sizeof(float2))) != RT_OK) return rc;
         }
-        if ((rc = tex_relayout(ctx, old_uv, old_visit)) != RT_OK) return rc;
     }
     if (bvh_arr10_out) memcpy(bvh_arr10_out, arr.data(), arr.size() * sizeof(float));
     if (tri_order_out) memcpy(tri_order_out, order.data(), order.size() * sizeof(int));
     if (n_nodes_out) *n_nodes_out = n_nodes;
     ctx->build.install_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_install).count();
     return RT_OK;
+}
+
+int rt_mesh_rebuild_mode(rt_ctx *ctx, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (mode != RT_BVH_REFERENCE && mode != RT_BVH_LBVH) return fail(ctx, RT_ERR_INVALID, "unknown BVH mode %d", mode);
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (n_nodes_out) *n_nodes_out = 0;
+    if (ctx->parts.size() > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: a rebuild works on ONE TriangleMesh (upload the rebuilt meshes again)", (int)ctx->parts.size());
+    if (ctx->parts.empty()) return RT_OK;                                           // no mesh: nothing to build
+    return rebuild_part(ctx, 0, mode, bvh_arr10_out, tri_order_out, n_nodes_out);
+}
+
+int rt_mesh_rebuild(rt_ctx *ctx, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
+    return rt_mesh_rebuild_mode(ctx, RT_BVH_REFERENCE, bvh_arr10_out, tri_order_out, n_nodes_out);
+}
+
+int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (mode != RT_BVH_REFERENCE && mode != RT_BVH_LBVH) return fail(ctx, RT_ERR_INVALID, "unknown BVH mode %d", mode);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (n_nodes_out) *n_nodes_out = 0;
+    if (!p) return RT_OK;                                                           // a mesh without triangles: nothing to build
+    return rebuild_part(ctx, p - ctx->parts.data(), mode, bvh_arr10_out, tri_order_out, n_nodes_out);
 }
 
 int rt_mesh_build_stats(const rt_ctx *ctx, rt_build_stats *out) {

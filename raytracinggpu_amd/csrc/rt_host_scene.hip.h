@@ -131,7 +131,7 @@ int requantize(rt_ctx *ctx, hipStream_t q) {
     return RT_OK;
 }
 
-// the triangle ranges of the scene's mesh table when at most ONE mesh has triangles (object position real_obj): a mesh without triangles is an empty range at its place in the order
+// the triangle ranges of the scene's mesh table when at most ONE mesh has triangles (object position real_obj, -1 = none): a mesh without triangles is an empty range at its place in the order
 void mesh_table_single(rtk::Scene &sc, int real_obj) {
     for (int k = 0; k < sc.n_meshes; ++k) sc.mesh[k].tri_begin = sc.mesh[k].obj <= real_obj ? 0 : sc.n_tris;
 }
@@ -437,6 +437,37 @@ int build_forest(rt_ctx *ctx, const rt_mesh *meshes, const std::vector<int> &rea
     f.m.object_slot = meshes[real[0]].object_slot;
     f.voff = voff; f.noff = noff;
     return RT_OK;
+}
+
+// The step rt_scene_upload_meshes and the rebuild entries share: the meshes real[] of `meshes` (those with triangles, object order) become the tree in use -- one mesh as it
+// stands (its arrays are read where they are, no copy), several as a forest -- and ctx->parts / forest_arr describe what was installed.  sc: as for install_scene;
+// if_none: what a scene without a real mesh installs (a mesh without triangles, or nullptr).
+int install_meshes(rt_ctx *ctx, const rtk::Scene &sc, const rt_mesh *meshes, const std::vector<int> &real, const rt_mesh *if_none = nullptr) {
+    const int K = (int)real.size();
+    Forest f;                                                           // (K <= 1: stays empty, every offset is 0)
+    int rc;
+    ctx->parts_valid = false;
+    if (K <= 1) {                                                       // build_forest would take a lone mesh's root for a synthetic node
+        rc = install_scene(ctx, sc, K ? &meshes[real[0]] : if_none);
+    } else {
+        if ((rc = build_forest(ctx, meshes, real, f)) != RT_OK) return rc;
+        // table entry of every mesh -> first triangle in the forest's index array (a mesh without triangles: the next real mesh's)
+        std::vector<int> offs(sc.n_meshes + 1, f.tri_off[K]);
+        for (int k = sc.n_meshes - 1, r = K - 1; k >= 0; --k) {
+            if (r >= 0 && sc.mesh[k].obj == meshes[real[r]].object_slot) { offs[k] = f.tri_off[r]; --r; }
+            else offs[k] = offs[k + 1];
+        }
+        rc = install_scene(ctx, sc, &f.m, &offs, K - 1);
+    }
+    if (!ctx->have_scene) return rc;                                    // (nothing installed: parts keep describing nothing in use)
+    ctx->parts.clear();
+    for (int k = 0; k < K; ++k) {
+        const rt_mesh &m = meshes[real[k]];
+        ctx->parts.push_back({m.object_slot, K > 1 ? f.voff[k] : 0, m.n_vertices, K > 1 ? f.tri_off[k] : 0, m.n_triangles, K > 1 ? f.noff[k] : 0, m.n_nodes, false});
+    }
+    ctx->forest_arr = std::move(f.arr);
+    ctx->parts_valid = rc == RT_OK;
+    return rc;
 }
 
 }  // namespace

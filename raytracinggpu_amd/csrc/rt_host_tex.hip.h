@@ -1,6 +1,6 @@
 // rt_host_tex.hip.h -- host side (inside rt_capi.hip's extern "C" block): textured meshes.  rt_mesh_set_texture[_of] store a mesh's per-corner UVs in visit order
 // (as rt_mesh_set_normals[_of] store normals), its texels as 8-bit bytes and its decode table on the device, and set its bit in tex_mask: frames then run
-// wf_advance_tex (rt_wavefront.hip.h).  rt_mesh_rebuild* carry the UVs with their triangles (rt_host_mesh.hip.h); rt_mesh_transform* leave them alone.
+// wf_advance_tex (rt_wavefront.hip.h).  rt_mesh_rebuild* carry the UVs with their triangles (rt_host_mesh.hip.h, which also has the gather both share); rt_mesh_transform* leave them alone.
 #pragma once
 
 static_assert(rtk::kMaxObjects == RT_MAX_OBJECTS, "the texture table is indexed by object id");
@@ -26,27 +26,17 @@ int rt_mesh_set_texture_of(rt_ctx *ctx, int object_slot, const float *uvs, int n
     const size_t n_texels = (size_t)tex->width * (size_t)tex->height;
     if (n_texels >= ((size_t)1 << 31) / 4) return fail(ctx, RT_ERR_INVALID, "texture of %d x %d texels: at most 2^29 texels", tex->width, tex->height);
     if (!p) return RT_OK;                                                           // a mesh without triangles: never hit, nothing to texture
-    if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
     const rtk::Scene &sc = ctx->scene;
-    int vb, ve;
-    visit_range(sc, object_slot, vb, ve);
-    std::vector<float2> uv(3 * (size_t)(ve - vb));
-    for (int t = vb; t < ve; ++t) {
-        const int src = ctx->tri_perm[t] - p->tri_off;                              // the mesh's own triangle index, uploaded order
-        if (src < 0 || src >= p->nt) return fail(ctx, RT_ERR_INTERNAL, "visit rank %d is not a triangle of object %d", t, object_slot);
-        if (src >= n_triangles) return fail(ctx, RT_ERR_INVALID, "n_triangles %d does not cover the mesh at object_slot %d (%d triangles)", n_triangles, object_slot, p->nt);
-        for (int k = 0; k < 3; ++k) {
-            const int ui = uvidx[(size_t)src * index_stride + k];
-            if (ui < 0 || ui >= n_uvs) return fail(ctx, RT_ERR_INVALID, "triangle %d references UV %d outside [0,%d)", src, ui, n_uvs);
-            uv[3 * (size_t)(t - vb) + k] = make_float2(uvs[2 * (size_t)ui], uvs[2 * (size_t)ui + 1]);
-        }
-    }
+    int vb, rc;
+    std::vector<int> ui;
+    if ((rc = gather_corners(ctx, *p, "UV", uvidx, index_stride, n_triangles, n_uvs, vb, ui)) != RT_OK) return rc;
+    std::vector<float2> uv(ui.size());
+    for (size_t i = 0; i < ui.size(); ++i) uv[i] = make_float2(uvs[2 * (size_t)ui[i]], uvs[2 * (size_t)ui[i] + 1]);
     // the decode table (NULL: byte / 255, one correctly rounded division) and the texels, one buffer per object
     std::vector<uint8_t> img(1024 + n_texels * tex->channels);
     float *dec = reinterpret_cast<float *>(img.data());
     for (int b = 0; b < 256; ++b) dec[b] = tex->decode ? tex->decode[b] : (float)b / 255.0f;
     memcpy(img.data() + 1024, tex->texels, n_texels * tex->channels);
-    int rc;
     if ((rc = ensure(ctx, ctx->tex_uv, 3 * (size_t)std::max(sc.n_tris, 1) * sizeof(float2))) != RT_OK) return rc;
     if ((rc = upload(ctx, ctx->tex_img[object_slot], img.data(), img.size())) != RT_OK) return rc;
     if (!uv.empty()) RT_HIP(ctx, hipMemcpy(static_cast<float2 *>(ctx->tex_uv.p) + 3 * (size_t)vb, uv.data(), uv.size() * sizeof(float2), hipMemcpyHostToDevice));
@@ -66,7 +56,7 @@ int rt_mesh_set_texture(rt_ctx *ctx, const float *uvs, int n_uvs, const int32_t 
         ctx->tex_mask = 0;
         return RT_OK;
     }
-    if (ctx->n_real_meshes > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: a texture is set for ONE TriangleMesh (rt_mesh_set_texture_of)", ctx->n_real_meshes);
-    if (ctx->real_obj < 0) return fail(ctx, RT_ERR_INVALID, "the scene has no mesh");
-    return rt_mesh_set_texture_of(ctx, ctx->real_obj, uvs, n_uvs, uvidx, index_stride, n_triangles, tex);
+    if (ctx->parts.size() > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: a texture is set for ONE TriangleMesh (rt_mesh_set_texture_of)", (int)ctx->parts.size());
+    if (ctx->parts.empty()) return fail(ctx, RT_ERR_INVALID, "the scene has no mesh");
+    return rt_mesh_set_texture_of(ctx, ctx->parts[0].obj, uvs, n_uvs, uvidx, index_stride, n_triangles, tex);
 }

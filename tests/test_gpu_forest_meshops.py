@@ -303,6 +303,45 @@ def test_rebuild_one_mesh(ctx, oracle, cat_golden):
     _check_rays(ctx, oracle, [osc_meshes[0], oms[B]], 62)
 
 
+def test_one_mesh_scene_per_mesh_entries_are_the_plain_ones(ctx, cat_golden):
+    """a scene with one mesh: set_normals_of and rebuild_of (both modes, flat and with smooth normals to carry) leave the layout, the returned tree and order, the install
+    path and the frame of the plain entries after a fresh upload, bit for bit"""
+    v, t, spheres, meshes = _setup(cat_golden)
+    one = [d for d in meshes if d["object_slot"] == A]
+    t_up = np.asarray(one[0]["indices"])[:, :3]
+    nt = len(t_up)
+    vn = _vertex_normals(one[0]["vertices"], np.asarray(t))
+
+    def run(slot):
+        out = {}
+        ctx.scene_upload(spheres, one)
+        ctx.mesh_set_normals(vn, t_up, object_slot=slot)
+        out["normals"] = (ctx.layout_hash(), ctx.render(_params(0)))
+        for mode in ("reference", "lbvh"):
+            for smooth in (False, True):
+                ctx.scene_upload(spheres, one)
+                ctx.mesh_transform(R1, T1, object_slot=slot)
+                if smooth:
+                    ctx.mesh_set_normals(vn, t_up, object_slot=slot)
+                arr, order = ctx.mesh_rebuild(nt, mode, object_slot=slot)
+                out[mode, smooth] = (ctx.layout_hash(), arr, order, ctx.build_stats()["install_on_device"], ctx.render(_params(0 if smooth else 2)))
+        return out
+
+    plain, of = run(None), run(A)
+    assert of["normals"][0] == plain["normals"][0]
+    np.testing.assert_array_equal(of["normals"][1].view(np.uint32), plain["normals"][1].view(np.uint32))
+    for key in (k for k in plain if k != "normals"):
+        (h_p, arr_p, order_p, dev_p, f_p), (h_o, arr_o, order_o, dev_o, f_o) = plain[key], of[key]
+        assert h_o == h_p, key
+        assert arr_o.shape == arr_p.shape and len(arr_p) > 1, key
+        np.testing.assert_array_equal(arr_o.view(np.uint32), arr_p.view(np.uint32))
+        np.testing.assert_array_equal(order_o, order_p)
+        assert sorted(order_p.tolist()) == list(range(nt)), key
+        assert dev_o == dev_p, key
+        np.testing.assert_array_equal(f_o.view(np.uint32), f_p.view(np.uint32))
+    assert (plain["normals"][1][..., :3] != plain["reference", False][4][..., :3]).any()   # (the frames do depend on what was set)
+
+
 def test_refusals_leave_the_scene_untouched(ctx, cat_golden):
     """a sphere's slot or one outside the scene: RT_ERR_INVALID, layout and frame unchanged; a mesh without triangles: nothing happens; after a failed upload: RT_ERR_NO_SCENE"""
     v, t, spheres, meshes = _setup(cat_golden)
