@@ -219,16 +219,12 @@ int rt_render_device_batch(rt_ctx *ctx, const rt_params *p, const rt_rows *rows,
             if (o < oj + bytes && oj < o + bytes) return fail(ctx, RT_ERR_INVALID, "frames %d and %d render into overlapping buffers", j, k);
         }
         lo = (!lo || o < lo) ? o : lo; hi = (!hi || o + bytes > hi) ? o + bytes : hi;
-        // cpu:694 `-W / (2 * tan(alpha/2))` for this frame's camera (evaluated as launch_render_chunk evaluates the uploaded camera's)
+        // cpu:694 `-W / (2 * tan(alpha/2))` for this frame's camera (evaluated as make_frame evaluates the uploaded camera's)
         bt.f[k] = rtk::BatchFrame{f.camera.position[0], f.camera.position[1], f.camera.position[2],
                                   -(float)p->width / (2 * (float)std::tan((double)(f.camera.fov / 2))), f.seed, 0, static_cast<float4 *>(f.out_rgba_dev)};
     }
     // one chunk: the batch exists for SMALL shares (a share too big for one chunk fills the chip by itself: render its frames one by one)
-    rt_ctx::Pipe &pl = ctx->pipe;
-    pl.prev_valid = pl.valid; pl.valid = false;
-    pl.call_chunk = 0; pl.call_chunks = 1; pl.open_parts = 0;
-    struct ClearBetween { rt_ctx::Pipe &p; ~ClearBetween() { p.between.clear(); p.between_overflow = false; } } clear_between{pl};
-    pl.call_lo = lo; pl.call_hi = hi;                                // (the frames' buffers and whatever lies between them: conservative for the pipelining rule)
+    const BetweenGuard between = begin_render_call(ctx->pipe, lo, hi);   // (the frames' buffers and whatever lies between them: conservative for the pipelining rule)
     return launch_render_chunk(ctx, p, rows, frames[0].out_rgba_dev, q_, nullptr, nullptr, true, true, &bt);
 }
 
@@ -279,7 +275,7 @@ int rt_render_async(rt_ctx *ctx, const rt_params *p, int slot, void *out_host, i
     if (ctx->slot_pending[slot]) RT_HIP(ctx, hipStreamWaitEvent(own_stream(ctx), ctx->slot_done[slot], 0));
     rt_rows rows{0, p->height, p->height, 1};
     // frames alternate between the two slots: with the sub-frames' chains on their own streams frame k+1 follows frame k chain by chain
-    // (launch_render_chunk); what its kernels must not overtake -- the slot's previous copy -- is handed to the chains directly
+    // (start_chains); what its kernels must not overtake -- the slot's previous copy -- is handed to the chains directly
     const bool pipe_was = ctx->pipe.on;
     ctx->pipe.on = ctx->knobs.async_pipeline != 0;
     ctx->pipe.extra_wait = ctx->slot_pending[slot] ? ctx->slot_done[slot] : nullptr;

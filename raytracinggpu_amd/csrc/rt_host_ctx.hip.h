@@ -133,7 +133,6 @@ struct rt_ctx {
     DevBuf nodesh, tri2leaf;                                        // 16-bit fixed-point sibling pairs and the triangle -> leaf table (rt_qnodes.hip.h)
     DevBuf leaflh;                                                  // (lo, hi) of each triangle's leaf, by triangle (the flagged-leaf check of the fixed-point kernels)
     DevBuf nodesw, qdp_parent, qdp_cnt, qdp_g, qdp_ch;              // 4-wide fixed-point nodes (RT_TRAVQ_QW) and the scratch of the DP that picks which four nodes a quad holds (rt_qnodes.hip.h)
-    int travq_blocks_per_cu_qw[2] = {0, 0};                         // [STATS]
     unsigned chain_nonce[8] = {};                                   // launch chains started so far, PER SUB-FRAME (WfState::nonce): every part owns its own region of the ray queue, so each
                                                                     // region must cycle through all four values (one context-wide counter gave a part only two of them with two parts: ADVICE round 4)
     int q16_leaf_shift = 0;                                         // where a leaf's triangle count sits in its payload word (rtk::q16_leaf_shift), 0 = leaves too large
@@ -166,13 +165,15 @@ struct rt_ctx {
     DevBuf accum;                                                   // progressive mode: sum of the frames so far (float4 per pixel)
     int prog_frames = 0, prog_w = 0, prog_h = 0;
     uint64_t qf_sig = 0;                                            // layout the queue flags were last zeroed for
-    int trav_blocks_per_cu[4] = {0, 0, 0, 0};
-    int travq_blocks_per_cu[6] = {0, 0, 0, 0, 0, 0};   // [STATS + 2 * (R == 32) + 4 * (R == 128)]
+    // workgroups per CU of the kernels whose grid is sized by it (blocks_per_cu: asked once, 0 = not yet), each slot + STATS: wf_trav; wf_travq (+ 2 * (R == 32) + 4 * (R == 128));
+    // its 4-wide form; render_persistent
+    enum { kOccTrav = 0, kOccTravq = 2, kOccTravqQw = 8, kOccPersist = 10, kOccSlots = 12 };
+    int occ_blocks[kOccSlots] = {};
     static constexpr int kMaxParts = 8;
     hipStream_t part_stream[kMaxParts] = {};
     hipEvent_t part_ev[kMaxParts] = {};
     hipEvent_t fork_ev = nullptr;
-    // Chains on streams of their own (launch_render_chunk): consecutive chunks of one call -- and, with rt_ctx_set_pipelining, consecutive
+    // Chains on streams of their own (start_chains / end_chains): consecutive chunks of one call -- and, with rt_ctx_set_pipelining, consecutive
     // frames into different buffers -- follow each other per sub-frame without a join in between.
     struct Pipe {
         bool on = false;                   // rt_ctx_set_pipelining: frames of consecutive calls may overlap
@@ -208,7 +209,6 @@ struct rt_ctx {
     hipEvent_t ev_trav[2 * kMaxTravEvents] = {};
     hipEvent_t ev_adv[2 * kMaxTravEvents] = {};                     // ... and of the uniform kernel's launches (rt_stats_enable)
     int n_trav_events = 0, n_adv_events = 0, adv_paths = 0;
-    int persist_blocks_per_cu[2] = {0, 0};   // [STATS]
     rt_stats stats{};
     std::string err;
     char name[256] = {0};

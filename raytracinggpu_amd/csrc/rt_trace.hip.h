@@ -1,5 +1,5 @@
 // rt_trace.hip.h -- rt_trace_rays: a batch of explicit rays through the PRODUCTION traversal launches.
-// Included at the end of rt_capi.hip (same translation unit: it uses the launch geometry of launch_render).
+// Included at the end of rt_capi.hip (same translation unit: it uses the traversal plan and launch geometry of the render path, plan_trav / wf_geometry / path_geometry).
 //
 // TriangleMesh::intersect (cpu_launcher.cpp:238-313; optimized.cu:220-285) is callable with ANY ray; in the render path rays reach
 // the traversal kernels only through the uniform kernels (camera rays, bounce and shadow rays), which never produce a zero or
@@ -76,74 +76,44 @@ static int trace_to_m(rt_ctx *ctx, const float *din, int n, float tri_tmin, int 
     RT_OWN_STREAM(ctx);
     hipStream_t q = own_stream(ctx);
     const Knobs &kn = ctx->knobs;
-    const bool have_mesh = sc.mesh_slot >= 0 && sc.n_nodes > 0;
     int rc;
-    auto done = [&](int code) { return code; };
     rtk::Frame fr{};
     fr.tri_tmin = tri_tmin; fr.segs = 1; fr.spp = 1; fr.W = 1; fr.H = 1; fr.n_rows = 1; fr.tile_rows = 1; fr.tile_step = 1; fr.out_tile_step = 1;
     M = nullptr;
     if (variant == RT_VARIANT_PATH) {
-        // the fused kernel: items = the rays, in wf_path's own launch geometry (launch_render, RT_VARIANT_PATH)
-        constexpr int wpb = rtk::kQBlock / 64;
-        const size_t lds = (size_t)wpb * rtk::PCarve::bytes(1) + 16;
+        // the fused kernel: items = the rays, in wf_path's own launch geometry (path_geometry, as launch_path uses it)
+        const size_t lds = (size_t)(rtk::kQBlock / 64) * rtk::PCarve::bytes(1) + 16;
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtk::wf_path<false>, rtk::kQBlock, lds) != hipSuccess || nb < 1) return done(fail(ctx, RT_ERR_UNSUPPORTED, "wf_path does not fit a CU"));
-        const int bpc = std::min(kn.path_bpc, nb);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtk::wf_path<false>, rtk::kQBlock, lds) != hipSuccess || nb < 1) return fail(ctx, RT_ERR_UNSUPPORTED, "wf_path does not fit a CU");
         rtk::PathState ps{};
         ps.n_paths = (n + 63) / 64 * 64; ps.tiles_x = 1; ps.samp0 = 0; ps.n_samp = 1; ps.samp_out = nullptr;
         ps.n_groups = ps.n_paths / 4;
-        if ((rc = ensure(ctx, ctx->wfM, (size_t)ps.n_paths * 8)) != RT_OK) return done(rc);
+        if ((rc = ensure(ctx, ctx->wfM, (size_t)ps.n_paths * 8)) != RT_OK) return rc;
         M = static_cast<unsigned long long *>(ctx->wfM.p);
         ps.ext_rays = din; ps.ext_out = M; ps.n_ext = n;
-        int64_t tblocks = std::max<int64_t>(1, (int64_t)ctx->n_cus * bpc) * kn.path_oversub;
-        const int min_groups = kn.min_groups * wpb;
-        int64_t groups_per_block = (ps.n_groups + tblocks - 1) / tblocks;
-        if (groups_per_block < min_groups) { tblocks = std::max<int64_t>(1, (ps.n_groups + min_groups - 1) / min_groups); groups_per_block = (ps.n_groups + tblocks - 1) / tblocks; }
-        ps.log2S = 0;
-        while ((2 << ps.log2S) <= groups_per_block && ps.log2S < 16) ++ps.log2S;
-        const int S = 1 << ps.log2S;
-        ps.Q = (ps.n_groups + S - 1) / S;
-        ps.slots_per_block = (int)((((int64_t)S * ps.Q * 4 + tblocks - 1) / tblocks + 3) / 4 * 4);
-        int qcap = rtk::kPStack;
-        if (kn.travq_cap >= 128 && kn.travq_cap < qcap) qcap = kn.travq_cap;
+        const int64_t tblocks = path_geometry(kn, ctx->n_cus, std::min(kn.path_bpc, nb), 1, ps);
         RT_HIP(ctx, hipMemsetAsync(M, 0xff, (size_t)ps.n_paths * 8, q));      // rays the kernel never reaches (none) would read as no hit
-        hipLaunchKernelGGL(rtk::wf_path<false>, dim3((unsigned)tblocks), dim3(rtk::kQBlock), lds, q, sc, fr, ps, qcap, kn.path_low, kn.path_shade_min);
+        hipLaunchKernelGGL(rtk::wf_path<false>, dim3((unsigned)tblocks), dim3(rtk::kQBlock), lds, q, sc, fr, ps, capped_stack(kn, rtk::kPStack), kn.path_low, kn.path_shade_min);
     } else {
-        const bool queue = variant == RT_VARIANT_WAVEFRONT_QUEUE;
-        const int qR = kn.travq_R;
-        const bool qw = queue && sc.nodesw != nullptr && qR == 64;    // the 4-wide BOX step, as a frame would run it (RT_TRAVQ_QW)
-        int qcap = travq_stack_cap(qR, qw);
-        if (kn.travq_cap >= 128 && kn.travq_cap < qcap) qcap = kn.travq_cap;   // tests: force the serial drain
-        const int tb = queue ? travq_block_threads(qR) : rtk::kTravBlock;
-        const int wpb = tb / 64;
-        const size_t trav_lds = queue ? (size_t)wpb * travq_carve_bytes(qR, qw) + 16 : (size_t)(rtk::kTravBlock / 64) * rtk::TravCarve<512, 8>::kBytes + 16;
-        int bpc = 0;
-        if (queue) {
-            RT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, travq_fn(false, qR, false, false, qw, qw), tb, trav_lds));
-            bpc = std::min(bpc > 0 ? bpc : 1, (kn.bpc5 ? 20 : 16) / (tb / 64));
-        } else {
-            RT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, rtk::wf_trav<false, false>, rtk::kTravBlock, trav_lds));
-            if (bpc < 1) bpc = 1;
-        }
+        // the traversal launch of a frame of a default context (plan_trav without RT_TRAVQ_LDS staging), one sub-frame
+        Variant v{};
+        v.variant = v.asked = variant;
+        TravPlan t;
+        if ((rc = plan_trav(ctx, v, false, 0, t)) != RT_OK) return rc;
         rtk::WfState st{};
         st.n_paths = ((n + 1) / 2 + 1) / 2 * 2;                       // 2 n_paths ray slots >= n, a multiple of 4
         st.n_px = st.n_paths; st.tiles_x = 1;
-        int64_t tblocks = 0;
-        wf_geometry(kn, ctx->n_cus, bpc, 1, wpb, queue, st, tblocks);
+        const int64_t tblocks = wf_geometry(kn, ctx->n_cus, t.bpc, 1, t.wpb, t.queue, st);
         const size_t q_slots = (size_t)st.slots_per_block * (size_t)tblocks;
-        if ((rc = ensure(ctx, ctx->wfM, 2 * (size_t)st.n_paths * 8)) != RT_OK || (rc = ensure(ctx, ctx->wfQR, q_slots * 32)) != RT_OK) return done(rc);
+        if ((rc = ensure(ctx, ctx->wfM, 2 * (size_t)st.n_paths * 8)) != RT_OK || (rc = ensure(ctx, ctx->wfQR, q_slots * 32)) != RT_OK) return rc;
         RT_HIP(ctx, hipMemsetAsync(ctx->wfQR.p, 0, q_slots * 32, q));    // padding slots carry no ray
         ctx->qf_sig = 0;                                               // the render path zeroes its own layout again
         st.QR = static_cast<float4 *>(ctx->wfQR.p);
         st.M = M = static_cast<unsigned long long *>(ctx->wfM.p);
-        st.init_m = queue ? 0 : 1;
+        st.init_m = t.queue ? 0 : 1;
         st.epoch = 0; st.nonce = 0;
         hipLaunchKernelGGL(rtk::trace_emit_kernel, dim3((unsigned)((2 * st.n_paths + 255) / 256)), dim3(256), 0, q, sc, st, din, n);
-        if (have_mesh) {
-            if (queue) hipLaunchKernelGGL(travq_fn(false, qR, false, false, sc.nodesh != nullptr, qw), dim3((unsigned)tblocks), dim3(tb), trav_lds, q, sc, fr, st, qcap, 0, kn.q_low * (qR == 128 ? 2 : 1),
-                                          (kn.q_minfree >= 1 && kn.q_minfree <= qR) ? kn.q_minfree : qR / 4);
-            else hipLaunchKernelGGL((rtk::wf_trav<false, false>), dim3((unsigned)tblocks), dim3(tb), trav_lds, q, sc, fr, st);
-        }
+        if (t.have_mesh) launch_trav(t, tblocks, q, sc, fr, st);
     }
     return RT_OK;
 }
