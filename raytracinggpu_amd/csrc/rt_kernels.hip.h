@@ -407,15 +407,19 @@ __device__ __forceinline__ Material material_of(const Scene &sc, int obj) {
 }
 __device__ __forceinline__ f3 sphere_centre_of(const Scene &sc, int obj) { const float4 a = sc.obj_a[obj]; return mk(a.x, a.y, a.z); }
 
+}  // namespace rtk
+
+#include "rt_shade.hip.h"     // the arithmetic of one path step, shared by the four render kernels
+
+namespace rtk {
+
 // Scene::getColor, cpu:566-648, made iterative: the path is walked front to back recording for each
 // diffuse segment the scalar l (cpu:623) and the object id, then folded back to front exactly as the
-// recursion returns (color = direct + albedo (.) child, cpu:642-644).  Mirror/refraction segments return
-// the child unchanged (cpu:579,594,601) and a miss returns black (cpu:571).
+// recursion returns (fold_segment).  Mirror/refraction segments return the child unchanged (cpu:579,594,601)
+// and a miss returns black (cpu:571).  The branches' arithmetic: rt_shade.hip.h.
 // lstack: per-lane LDS column, lstack[d * kBlockThreads].
 template <bool STATS>
 __device__ __forceinline__ f3 get_color(const Scene &sc, const Frame &fr, f3 O, f3 u, uint32_t hs, float *lstack, float &rays, Work &wk) {
-    const float PI_F = (float)3.14159265358979323846;
-    const double PI_D = 3.14159265358979323846;
     const f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
     float refr = 1.f;             // Ray::refraction_index, cpu:100
     uint64_t ids = 0;             // 4 bits of object id per segment
@@ -427,57 +431,20 @@ __device__ __forceinline__ f3 get_color(const Scene &sc, const Frame &fr, f3 O, 
         if (!intersect_all<STATS>(sc, O, u, fr.tri_tmin, P, N, id, wk)) break;
         nseg = d + 1;
         const Material m = material_of(sc, id);
-        if (m.mirror) {                                             // cpu:573-579
-            O = P + fr.eps * N;
-            u = u - (2 * dot(u, N)) * N;
-        } else if (m.n_in != m.n_out) {                             // cpu:580-604
-            float ratio;
-            const bool out2in = refr == m.n_out;
-            if (out2in) ratio = m.n_out / m.n_in;
-            else { ratio = m.n_in / m.n_out; N = -N; }
-            const float un = dot(u, N);
-            if (((out2in && refr > m.n_in) || (!out2in && refr > m.n_out)) && (ratio * ratio) * (1 - un * un) > 1) {
-                O = P + fr.eps * N;
-                u = u - (2 * un) * N;
-            } else {
-                O = P - fr.eps * N;
-                const f3 Nc = (-rt_sqrtf(1 - (ratio * ratio) * (1 - un * un))) * N;
-                const f3 Tc = ratio * (u - un * N);
-                u = Nc + Tc;
-                refr = out2in ? m.n_in : m.n_out;
-            }
-        } else {                                                    // cpu:605-645
+        if (m.mirror) {
+            mirror_step(fr.eps, P, N, O, u);
+        } else if (m.n_in != m.n_out) {
+            refr = refract_step(m, refr, fr.eps, P, N, O, u).refr_after;
+        } else {                                                    // diffuse: shadow ray, direct term, bounce
             const f3 Pa = P + fr.eps * N;
-            const f3 toL = L - Pa;
-            const f3 sdir = normalize(toL);   // = toL / sqrt(norm2(toL))           // NORMED_VEC, cpu:30,614
+            const f3 sdir = shadow_dir(L, Pa);
             f3 Pp, Np; int ids_;
             rays += 1.f;
             (void)intersect_all<STATS>(sc, Pa, sdir, fr.tri_tmin, Pp, Np, ids_, wk);
-            float l = 0.f;
-            if (!(norm2(Pp - Pa) <= norm2(L - Pa))) {               // cpu:615
-                const f3 wl = normalize(L - P);
-                const float dn = dot(N, wl);
-                const float mx = (dn < 0.f) ? 0.f : dn;             // std::max(dn, 0.f)
-                l = (float)((double)sc.intensity / (4 * PI_D * (double)norm2(L - P)) * (double)mx);   // cpu:623
-            }
-            lstack[d * kBlockThreads] = l;
+            lstack[d * kBlockThreads] = light_hidden(Pa, Pp, L) ? 0.f : direct_term(sc, L, P, N);
             ids |= (uint64_t)(id & 15) << (4 * d);
             diffuse_mask |= 1u << d;
-            const float r1 = uniform01(hs, (uint32_t)d, 0);         // cpu:628-629
-            const float r2 = uniform01(hs, (uint32_t)d, 1);
-            double sn, cs;
-            rt_sincos_2pi(2 * PI_D * (double)r1, sn, cs);
-            const float s1 = rt_sqrtf(1 - r2);
-            const float x = (float)(cs * (double)s1);               // cpu:630
-            const float y = (float)(sn * (double)s1);               // cpu:631
-            const float zz = rt_sqrtf(r2);                        // cpu:632
-            // T1 = normalize((-Ny, Nx, 0)) if Nx != 0 && Ny != 0 else normalize((-Nz, 0, Nx)) (cpu:634-638): two quotients, the third component is +0 / n
-            const bool t1a = N.y != 0 && N.x != 0;
-            float t1p, t1q, t1z;
-            normalize_pq0(t1a ? -N.y : -N.z, N.x, t1p, t1q, t1z);
-            const f3 T1 = t1a ? mk(t1p, t1q, t1z) : mk(t1p, t1z, t1q);
-            const f3 T2 = cross(N, T1);
-            u = x * T1 + y * T2 + zz * N;                           // cpu:641
+            u = cosine_bounce(N, hs, d);
             O = Pa;
             refr = 1.f;                                             // Ray(P_adjusted, random_direction), cpu:642
         }
@@ -486,10 +453,7 @@ __device__ __forceinline__ f3 get_color(const Scene &sc, const Frame &fr, f3 O, 
     for (int d = nseg - 1; d >= 0; --d) {
         if (diffuse_mask & (1u << d)) {
             const Material m = material_of(sc, (int)((ids >> (4 * d)) & 15));
-            const float l = lstack[d * kBlockThreads];
-            const f3 alb = mk(m.ar, m.ag, m.ab);
-            const f3 direct = (l * alb) / PI_F;                     // cpu:624
-            ans = direct + alb * ans;                               // cpu:642,644
+            ans = fold_segment(ans, lstack[d * kBlockThreads], mk(m.ar, m.ag, m.ab));
         }
     }
     return ans;
@@ -508,31 +472,19 @@ __global__ __launch_bounds__(kBlockThreads) void render_kernel(const Scene sc, c
     const int wave = tid >> 6, lane = tid & 63;
     const int px = blockIdx.x * kTileW + wave * 8 + (lane & 7);
     const int lrow = blockIdx.y * kTileH + (lane >> 3);
-    const int row = fr.row0 + (lrow / fr.tile_rows) * fr.tile_rows * fr.tile_step + (lrow % fr.tile_rows);
+    const int row = image_row(fr, lrow);
     const bool active = px < fr.W && lrow < fr.n_rows && row < fr.H;
     Work wk;
     float rays = 0.f;
     if (active) {
     float *lstack = smem + tid;
 
-    // cpu:699: +0.5/-0.5 are double literals, narrowed by the Vector constructor
-    const f3 uc = mk((float)((double)((float)px - (float)fr.W / 2) + 0.5),
-                     (float)((double)((float)fr.H / 2 - (float)row) - 0.5), fr.z);
     const f3 C = mk(sc.camx, sc.camy, sc.camz);
-    const uint32_t pixel = (uint32_t)row * (uint32_t)fr.W + (uint32_t)px;
-    const uint32_t hp = mix32(pixel ^ mix32(fr.seed));
+    const uint32_t hp = pixel_hash(fr, row, px, fr.seed);
     f3 total = mk(0, 0, 0);
     for (int s = 0; s < fr.spp; ++s) {
-        const uint32_t hs = mix32(hp ^ ((uint32_t)s * 0x9E3779B1U));
-        f3 uu = uc;
-        if (fr.sigma != 0.f) {   // cpu:705-707; with sigma == 0 the jitter is exactly +-0 and uc is unchanged
-            const float r1 = uniform01(hs, 0, 2), r2 = uniform01(hs, 0, 3);
-            const float bm = fr.sigma * rt_sqrtf(-2 * logf(r1));
-            double sn, cs;
-            rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r2, sn, cs);
-            uu = uc + mk((float)((double)bm * cs), (float)((double)bm * sn), 0.f);
-        }
-        const f3 u = normalize(uu);
+        const uint32_t hs = sample_hash(hp, s);
+        const f3 u = jitter_dir(fr, pixel_dir(fr, px, row, fr.z), hs);
         const f3 col = get_color<STATS>(sc, fr, C, u, hs, lstack, rays, wk);
         total = total + col;
     }

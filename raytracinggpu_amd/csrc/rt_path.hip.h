@@ -1,7 +1,7 @@
 // rt_path.hip.h -- wf_path: the whole per-pixel render in ONE persistent launch (variant RT_VARIANT_PATH, the default).
 //
 // Replaces KernelLaunch (optimized.cu:670-772) / the pixel loop of cpu_launcher.cpp:693-718 including Scene::getColor
-// (cpu:566-648), Scene::intersect_all (cpu:545-564) and TriangleMesh::intersect (cpu:238-313).
+// (its branches' arithmetic: rt_shade.hip.h), Scene::intersect_all (cpu:545-564) and TriangleMesh::intersect (cpu:238-313).
 //
 // The wavefront pipeline (rt_wavefront.hip.h) alternates a traversal kernel with a uniform shading kernel and streams
 // every path's state through HBM between them: per frame 11 dependent launches per sub-frame and ~3 GB of path-state
@@ -163,8 +163,6 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                 // (alive paths without entries are ready; this point is not reachable with alive paths)
             }
             if (n_ready >= kShadeMin || (idle && n_ready > 0)) {
-                const float PI_F = (float)3.14159265358979323846;
-                const double PI_D = 3.14159265358979323846;
                 const f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
                 float4 S = make_float4(0, 0, 0, 1.f);
                 int item = -1;
@@ -180,7 +178,6 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                     px = (tile % ps.tiles_x) * 8 + (p & 7);
                     lrow = (tile / ps.tiles_x) * 8 + (p >> 3);
                 };
-                auto image_row = [&]() { return fr.row0 + (lrow / fr.tile_rows) * fr.tile_rows * fr.tile_step + (lrow % fr.tile_rows); };
                 // the sample is finished: its colour `ans` and ray count leave the CU (cpu:711-713)
                 auto write_result = [&](f3 ans, float rays) {
                     if (ps.samp_out != nullptr) {
@@ -206,7 +203,7 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                     int d = (F.x >> PF_DEPTH_SHIFT) & PF_DEPTH_MASK;          // segment of the continuation ray in flight
                     int nrays = (F.x >> PF_RAYS_SHIFT) & PF_RAYS_MASK;
                     float refr = S.w;
-                    // ---- (1) the shadow ray of segment d-1's hit came back: direct light or not (cpu:615) ----
+                    // ---- (1) the shadow ray of segment d-1's hit came back: direct light or not ----
                     if (F.x & PF_HASX) {
                         const float4 x0 = tabC[P + lane];
                         const float2 x1 = tabD[P + lane];
@@ -216,11 +213,9 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                             const unsigned long long m = best[P + lane];
                             if (m != WF_NOHIT) { const float tm = __uint_as_float((unsigned int)(m >> 32)); if (tm < t_min) t_min = tm; }
                         }
-                        const f3 Pp = Oxr + t_min * uxr;                      // cpu:560 (Ox is P_adjusted)
-                        const bool lit = !(norm2(Pp - Oxr) <= norm2(L - Oxr));   // cpu:615
-                        lsq[(d - 1) * P + lane] = lit ? pL[lane] : 0.f;
+                        lsq[(d - 1) * P + lane] = light_hidden(Oxr, uxr, t_min, L) ? 0.f : pL[lane];   // (Ox is P_adjusted)
                     }
-                    // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit (cpu:570-614) ----
+                    // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit ----
                     if (F.x & PF_HASY) {
                         const float4 r0 = tabC[lane];
                         const float2 r1 = tabD[lane];
@@ -239,79 +234,38 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                         }
                         if (win >= 0) {                                       // a miss is black (cpu:571): nothing to emit
                             const f3 Pt = O + t_min * u;                      // cpu:560
-                            f3 N;
-                            if (tri_win >= 0 && sc.nrm != nullptr && ((sc.smooth_mask >> win) & 1)) {          // get_smooth_normal (of a smooth mesh), realtime_render.cu:221-245
-                                PQ_CHECK(tri_win >= 0 && tri_win < sc.n_tris, 2, tri_win = 0);
-                                const float4 q0 = sc.tri[3 * tri_win], q1 = sc.tri[3 * tri_win + 1], q2 = sc.tri[3 * tri_win + 2];
-                                const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x), Nt = mk(q2.y, q2.z, q2.w);
-                                const float beta = dot(e2, cross(A - O, u)) / dot(u, Nt);
-                                const float gamma = -dot(e1, cross(A - O, u)) / dot(u, Nt);
-                                const float alpha = 1 - beta - gamma;
-                                const float4 na = sc.nrm[3 * tri_win], nb = sc.nrm[3 * tri_win + 1], nc = sc.nrm[3 * tri_win + 2];
-                                N = normalize((alpha * mk(na.x, na.y, na.z) + beta * mk(nb.x, nb.y, nb.z)) + gamma * mk(nc.x, nc.y, nc.z));
+                            f3 N;                                             // hit_normal's choice (rt_shade.hip.h), each read of sc.tri behind its index check
+                            if (smooth_hit(sc, win, tri_win)) {
+                                PQ_CHECK(tri_win < sc.n_tris, 2, tri_win = 0);
+                                Bary bary;
+                                N = smooth_normal(sc, tri_win, O, u, bary);
                             } else if (tri_win >= 0) {
-                                PQ_CHECK(tri_win >= 0 && tri_win < sc.n_tris, 2, tri_win = 0);
-                                const float4 q2 = sc.tri[3 * tri_win + 2];
-                                N = normalize(mk(q2.y, q2.z, q2.w));          // cpu:308
+                                PQ_CHECK(tri_win < sc.n_tris, 2, tri_win = 0);
+                                N = flat_normal(sc, tri_win);
                             } else {
-                                N = normalize(Pt - sphere_centre_of(sc, win));  // cpu:524-525
+                                N = sphere_normal(sc, win, Pt);
                             }
                             const Material m = material_of(sc, win);
                             bool cont = false;                                // a continuation ray of segment d+1 was built in (O,u)
-                            if (m.mirror) {                                   // cpu:573-579
-                                O = Pt + fr.eps * N;
-                                u = u - (2 * dot(u, N)) * N;
+                            if (m.mirror) {
+                                mirror_step(fr.eps, Pt, N, O, u);
                                 cont = true;
-                            } else if (m.n_in != m.n_out) {                   // cpu:580-604
-                                float ratio;
-                                const bool out2in = refr == m.n_out;
-                                if (out2in) ratio = m.n_out / m.n_in;
-                                else { ratio = m.n_in / m.n_out; N = -N; }
-                                const float un = dot(u, N);
-                                if (((out2in && refr > m.n_in) || (!out2in && refr > m.n_out)) && (ratio * ratio) * (1 - un * un) > 1) {
-                                    O = Pt + fr.eps * N;
-                                    u = u - (2 * un) * N;
-                                } else {
-                                    O = Pt - fr.eps * N;
-                                    const f3 Nc = (-rt_sqrtf(1 - (ratio * ratio) * (1 - un * un))) * N;
-                                    const f3 Tc = ratio * (u - un * N);
-                                    u = Nc + Tc;
-                                    refr = out2in ? m.n_in : m.n_out;
-                                }
+                            } else if (m.n_in != m.n_out) {
+                                refr = refract_step(m, refr, fr.eps, Pt, N, O, u).refr_after;
                                 cont = true;
-                            } else {                                          // cpu:605-642: diffuse
+                            } else {                                          // diffuse
                                 const f3 Pa = Pt + fr.eps * N;
-                                const f3 toL = L - Pa;
-                                Ox = Pa; ux = normalize(toL);   // = toL / sqrt(norm2(toL))     // NORMED_VEC, cpu:614: the shadow ray of segment d
+                                Ox = Pa; ux = shadow_dir(L, Pa);              // the shadow ray of segment d
                                 emitX = true;
                                 nrays += 1;
-                                // its direct term if the light turns out to be visible (cpu:620-623), kept until the shadow ray is back
-                                const f3 wl = normalize(L - Pt);
-                                const float dn = dot(N, wl);
-                                const float mx = (dn < 0.f) ? 0.f : dn;
-                                pL[lane] = (float)((double)sc.intensity / (4 * PI_D * (double)norm2(L - Pt)) * (double)mx);
+                                // its direct term if the light turns out to be visible, kept until the shadow ray is back
+                                pL[lane] = direct_term(sc, L, Pt, N);
                                 const uint64_t ids = ((uint64_t)(uint32_t)F.w << 32 | (uint32_t)F.z) | (uint64_t)(win & 15) << (4 * d);
                                 F.z = (int)(uint32_t)ids; F.w = (int)(uint32_t)(ids >> 32);
                                 F.y |= 1 << d;
-                                if (d + 1 < fr.segs) {                        // the bounce ray (cpu:627-642): needs r1, r2 and N only
-                                    const int row = image_row();
-                                    const uint32_t hp = mix32(((uint32_t)row * (uint32_t)fr.W + (uint32_t)px) ^ mix32(fr.seed));
-                                    const uint32_t hs = mix32(hp ^ ((uint32_t)samp * 0x9E3779B1U));
-                                    const float r1u = uniform01(hs, (uint32_t)d, 0);
-                                    const float r2u = uniform01(hs, (uint32_t)d, 1);
-                                    double sn, cs;
-                                    rt_sincos_2pi(2 * PI_D * (double)r1u, sn, cs);
-                                    const float s1f = rt_sqrtf(1 - r2u);
-                                    const float x = (float)(cs * (double)s1f);
-                                    const float y = (float)(sn * (double)s1f);
-                                    const float zz = rt_sqrtf(r2u);
-                                    // T1 = normalize((-Ny, Nx, 0)) if Nx != 0 && Ny != 0 else normalize((-Nz, 0, Nx)) (cpu:634-638): two quotients, the third component is +0 / n
-                                    const bool t1a = N.y != 0 && N.x != 0;
-                                    float t1p, t1q, t1z;
-                                    normalize_pq0(t1a ? -N.y : -N.z, N.x, t1p, t1q, t1z);
-                                    const f3 T1 = t1a ? mk(t1p, t1q, t1z) : mk(t1p, t1z, t1q);
-                                    const f3 T2 = cross(N, T1);
-                                    u = x * T1 + y * T2 + zz * N;
+                                if (d + 1 < fr.segs) {                        // the bounce ray: needs the sample's key and N only
+                                    const int row = image_row(fr, lrow);
+                                    u = cosine_bounce(N, sample_hash(pixel_hash(fr, row, px, fr.seed), samp), d);
                                     O = Pa;
                                     refr = 1.f;                               // Ray(P_adjusted, random_direction): index 1
                                     cont = true;
@@ -327,16 +281,14 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                     S.w = refr;
                     if (emitX || emitY) {
                         F.x = PF_ALIVE | (emitX ? PF_HASX : 0) | (emitY ? PF_HASY : 0) | (d << PF_DEPTH_SHIFT) | (nrays << PF_RAYS_SHIFT);
-                    } else {   // nothing in flight: fold the path back to front (cpu:642-644) and hand the sample over (cpu:711)
+                    } else {   // nothing in flight: fold the path back to front and hand the sample over (cpu:711)
                         f3 ans = mk(0, 0, 0);
                         const int nseg = d < fr.segs ? d : fr.segs;
                         const uint64_t ids = (uint64_t)(uint32_t)F.w << 32 | (uint32_t)F.z;
                         for (int k = nseg - 1; k >= 0; --k) {
                             if (F.y & (1 << k)) {
                                 const Material m = material_of(sc, (int)((ids >> (4 * k)) & 15));
-                                const float l = lsq[k * P + lane];
-                                const f3 alb = mk(m.ar, m.ag, m.ab);
-                                ans = (l * alb) / PI_F + alb * ans;
+                                ans = fold_segment(ans, lsq[k * P + lane], mk(m.ar, m.ag, m.ab));
                             }
                         }
                         write_result(ans, (float)nrays);
@@ -344,7 +296,7 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                         F = make_int4(0, 0, 0, 0);
                     }
                 }
-                // ---- (3) free path slots take the next pixels of the workgroup's share: camera ray (cpu:699-709) ----
+                // ---- (3) free path slots take the next pixels of the workgroup's share: camera ray ----
                 const bool want = ready && !alive && !drained;
                 const unsigned long long wm = __ballot(want);
                 if (wm != 0ull) {
@@ -372,29 +324,9 @@ __global__ __launch_bounds__(kQBlock, 2) void wf_path(const Scene sc, const Fram
                             if (valid && fr.segs <= 0) {                       // optimized.cu convention with num_bounce 0: black
                                 write_result(mk(0, 0, 0), 0.f);
                             } else if (valid) {
-                                const int row = image_row();
-                                // cpu:699: +0.5/-0.5 are double literals, narrowed by the Vector constructor
-                                const f3 uc = mk((float)((double)((float)px - (float)fr.W / 2) + 0.5),
-                                                 (float)((double)((float)fr.H / 2 - (float)row) - 0.5), fr.z);
-                                f3 ucm = uc;
-                                if (fr.cam_mode == 1) {   // realtime:1115: cam.C + cam.bz * z + cam.bx * X + cam.by * Y
-                                    const f3 Cc = mk(sc.camx, sc.camy, sc.camz), Bx = mk(fr.bx[0], fr.bx[1], fr.bx[2]), By = mk(fr.by[0], fr.by[1], fr.by[2]), Bz = mk(fr.bz[0], fr.bz[1], fr.bz[2]);
-                                    const f3 a = Cc + mk(Bz.x * fr.z, Bz.y * fr.z, Bz.z * fr.z);
-                                    const f3 b = a + mk(Bx.x * uc.x, Bx.y * uc.x, Bx.z * uc.x);
-                                    ucm = b + mk(By.x * uc.y, By.y * uc.y, By.z * uc.y);
-                                }
-                                f3 uu = ucm;
-                                if (fr.sigma != 0.f) {   // cpu:705-707; with sigma == 0 the jitter is exactly +-0
-                                    const uint32_t hp = mix32(((uint32_t)row * (uint32_t)fr.W + (uint32_t)px) ^ mix32(fr.seed));
-                                    const uint32_t hs = mix32(hp ^ ((uint32_t)samp * 0x9E3779B1U));
-                                    const float r1 = uniform01(hs, 0, 2), r2 = uniform01(hs, 0, 3);
-                                    const float bm = fr.sigma * rt_sqrtf(-2 * logf(r1));
-                                    double sn, cs;
-                                    rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r2, sn, cs);
-                                    uu = ucm + mk((float)((double)bm * cs), (float)((double)bm * sn), 0.f);
-                                }
+                                const int row = image_row(fr, lrow);
                                 Oy = mk(sc.camx, sc.camy, sc.camz);
-                                uy = normalize(uu);
+                                uy = camera_dir(fr, Oy, fr.z, px, row, sample_hash(pixel_hash(fr, row, px, fr.seed), samp));
                                 emitY = true;
                                 alive = true;
                                 F = make_int4(PF_ALIVE | PF_HASY | (1 << PF_RAYS_SHIFT), 0, 0, 0);   // segment 0, one ray

@@ -7,14 +7,15 @@
 //
 //     NEXT  -> START -> BOX* -> TRI* -> ... -> HIT | SHADE -> START ... -> NEXT
 //
-//   NEXT   close the previous path (back-to-front fold, cpu:642-644), write the pixel when its samples
-//          are done (float4 store), pull a new pixel from the global queue, build the camera ray (cpu:699-709)
+//   NEXT   close the previous path (back-to-front fold), write the pixel when its samples
+//          are done (float4 store), pull a new pixel from the global queue, build the camera ray
 //   START  begin a nearest-hit query: the spheres that precede the mesh in Scene::objects (cpu:549-558)
 //   BOX    one BoundingBox::intersect of the stackless traversal (cpu:146-157, 284-293)
 //   TRI    one moller_trumbore of the current leaf (cpu:226-236, 295-305)
-//   HIT    end of a path-segment query: remaining spheres, P/N (cpu:560-562), material branch (cpu:573-611),
+//   HIT    end of a path-segment query: remaining spheres, P/N (cpu:560-562), material branch,
 //          emits the shadow ray or the reflected/refracted ray
-//   SHADE  end of a shadow query: direct light (cpu:615-625), cosine-weighted bounce ray (cpu:627-642)
+//   SHADE  end of a shadow query: direct light, cosine-weighted bounce ray
+//   (the arithmetic of NEXT, HIT and SHADE: rt_shade.hip.h)
 //
 // and the wave executes, each iteration, the micro-op most lanes are waiting for (one __ballot per
 // phase, s_bcnt1, scalar branch).  Lanes never wait for another pixel's ray to finish, only for their own
@@ -62,8 +63,6 @@ __global__ __launch_bounds__(kPBlock) void render_persistent(const Scene sc, con
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     float *lstack = smem + tid;                 // lstack[d * kPBlock]
-    const float PI_F = (float)3.14159265358979323846;
-    const double PI_D = 3.14159265358979323846;
     const f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
     const f3 Cam = mk(sc.camx, sc.camy, sc.camz);
     const int n_nodes = sc.n_nodes;
@@ -176,36 +175,18 @@ __global__ __launch_bounds__(kPBlock) void render_persistent(const Scene sc, con
                 } else {
                     const f3 P = O + t_min * u;                          // cpu:560
                     f3 N;
-                    if (mesh_won) N = normalize(Nb);                     // cpu:308
-                    else {
-                        N = normalize(P - sphere_centre_of(sc, win));    // cpu:524-525
-                    }
+                    if (mesh_won) N = normalize(Nb);                     // cpu:308 (the winner's e1 x e2 comes out of the walk)
+                    else N = sphere_normal(sc, win, P);
                     const Material m = material_of(sc, win);
                     bool next_segment = true;
-                    if (m.mirror) {                                      // cpu:573-579
-                        O = P + fr.eps * N;
-                        u = u - (2 * dot(u, N)) * N;
-                    } else if (m.n_in != m.n_out) {                      // cpu:580-604
-                        float ratio;
-                        const bool out2in = refr == m.n_out;
-                        if (out2in) ratio = m.n_out / m.n_in;
-                        else { ratio = m.n_in / m.n_out; N = -N; }
-                        const float un = dot(u, N);
-                        if (((out2in && refr > m.n_in) || (!out2in && refr > m.n_out)) && (ratio * ratio) * (1 - un * un) > 1) {
-                            O = P + fr.eps * N;
-                            u = u - (2 * un) * N;
-                        } else {
-                            O = P - fr.eps * N;
-                            const f3 Nc = (-rt_sqrtf(1 - (ratio * ratio) * (1 - un * un))) * N;
-                            const f3 Tc = ratio * (u - un * N);
-                            u = Nc + Tc;
-                            refr = out2in ? m.n_in : m.n_out;
-                        }
-                    } else {                                             // cpu:605-614: shadow ray
+                    if (m.mirror) {
+                        mirror_step(fr.eps, P, N, O, u);
+                    } else if (m.n_in != m.n_out) {
+                        refr = refract_step(m, refr, fr.eps, P, N, O, u).refr_after;
+                    } else {                                             // diffuse: the shadow ray first
                         Ps = P; Ns = N; sid = win;
                         const f3 Pa = P + fr.eps * N;
-                        const f3 toL = L - Pa;
-                        u = normalize(toL);   // = toL / sqrt(norm2(toL))                  // NORMED_VEC
+                        u = shadow_dir(L, Pa);
                         O = Pa;
                         shadow = true;
                         next_segment = false;
@@ -220,34 +201,12 @@ __global__ __launch_bounds__(kPBlock) void render_persistent(const Scene sc, con
         } else if (sel == PH_SHADE) {
             if (phase == PH_SHADE) {
                 if (many && tm < t_min) t_min = tm;                      // (a shadow ray needs the nearest hit's value only: ties do not matter)
-                const f3 Pp = O + t_min * u;                             // cpu:560 (O is P_adjusted)
-                float l = 0.f;
-                if (!(norm2(Pp - O) <= norm2(L - O))) {                  // cpu:615
-                    const f3 wl = normalize(L - Ps);
-                    const float dn = dot(Ns, wl);
-                    const float mx = (dn < 0.f) ? 0.f : dn;
-                    l = (float)((double)sc.intensity / (4 * PI_D * (double)norm2(L - Ps)) * (double)mx);   // cpu:623
-                }
-                lstack[d * kPBlock] = l;
+                lstack[d * kPBlock] = light_hidden(O, u, t_min, L) ? 0.f : direct_term(sc, L, Ps, Ns);   // (O is P_adjusted)
                 ids |= (uint64_t)(sid & 15) << (4 * d);
                 dmask |= 1u << d;
                 shadow = false;
-                if (d + 1 < fr.segs) {                                   // the bounce ray (cpu:627-642)
-                    const float r1 = uniform01(hs, (uint32_t)d, 0);
-                    const float r2 = uniform01(hs, (uint32_t)d, 1);
-                    double sn, cs;
-                    rt_sincos_2pi(2 * PI_D * (double)r1, sn, cs);
-                    const float s1 = rt_sqrtf(1 - r2);
-                    const float x = (float)(cs * (double)s1);
-                    const float y = (float)(sn * (double)s1);
-                    const float zz = rt_sqrtf(r2);
-                    // T1 = normalize((-Ny, Nx, 0)) if Nx != 0 && Ny != 0 else normalize((-Nz, 0, Nx)) (cpu:634-638): two quotients, the third component is +0 / n
-                    const bool t1a = Ns.y != 0 && Ns.x != 0;
-                    float t1p, t1q, t1z;
-                    normalize_pq0(t1a ? -Ns.y : -Ns.z, Ns.x, t1p, t1q, t1z);
-                    const f3 T1 = t1a ? mk(t1p, t1q, t1z) : mk(t1p, t1z, t1q);
-                    const f3 T2 = cross(Ns, T1);
-                    u = x * T1 + y * T2 + zz * Ns;
+                if (d + 1 < fr.segs) {                                   // the bounce ray
+                    u = cosine_bounce(Ns, hs, d);
                     refr = 1.f;                                          // O stays P_adjusted
                     d = d + 1;
                     phase = PH_START;
@@ -258,15 +217,13 @@ __global__ __launch_bounds__(kPBlock) void render_persistent(const Scene sc, con
             }
         } else {   // PH_NEXT
             if (phase == PH_NEXT) {
-                if (path_open) {   // fold the finished path back to front (cpu:642-644) and accumulate (cpu:711)
+                if (path_open) {   // fold the finished path back to front and accumulate (cpu:711)
                     f3 ans = mk(0, 0, 0);
                     const int nseg = d < fr.segs ? d : fr.segs;
                     for (int k = nseg - 1; k >= 0; --k) {
                         if (dmask & (1u << k)) {
                             const Material m = material_of(sc, (int)((ids >> (4 * k)) & 15));
-                            const float l = lstack[k * kPBlock];
-                            const f3 alb = mk(m.ar, m.ag, m.ab);
-                            ans = (l * alb) / PI_F + alb * ans;
+                            ans = fold_segment(ans, lstack[k * kPBlock], mk(m.ar, m.ag, m.ab));
                         }
                     }
                     total = total + ans;
@@ -298,26 +255,14 @@ __global__ __launch_bounds__(kPBlock) void render_persistent(const Scene sc, con
                         if (px < fr.W && lrow < fr.n_rows) {
                             have_pixel = true;
                             samp = 0; total = mk(0, 0, 0); rays = 0.f;
-                            const int row = fr.row0 + (lrow / fr.tile_rows) * fr.tile_rows * fr.tile_step + (lrow % fr.tile_rows);
-                            hp = mix32(((uint32_t)row * (uint32_t)fr.W + (uint32_t)px) ^ mix32(fr.seed));
+                            hp = pixel_hash(fr, image_row(fr, lrow), px, fr.seed);
                         }   // else: a slot of an edge tile outside the image; draw again next time
                     }
                 }
             }
-            if (phase == PH_NEXT && have_pixel && samp < fr.spp) {       // camera ray of sample `samp` (cpu:699-709)
-                const int row = fr.row0 + (lrow / fr.tile_rows) * fr.tile_rows * fr.tile_step + (lrow % fr.tile_rows);
-                const f3 uc = mk((float)((double)((float)px - (float)fr.W / 2) + 0.5),
-                                 (float)((double)((float)fr.H / 2 - (float)row) - 0.5), fr.z);
-                hs = mix32(hp ^ ((uint32_t)samp * 0x9E3779B1U));
-                f3 uu = uc;
-                if (fr.sigma != 0.f) {
-                    const float r1 = uniform01(hs, 0, 2), r2 = uniform01(hs, 0, 3);
-                    const float bm = fr.sigma * rt_sqrtf(-2 * logf(r1));
-                    double sn, cs;
-                    rt_sincos_2pi(2 * PI_D * (double)r2, sn, cs);
-                    uu = uc + mk((float)((double)bm * cs), (float)((double)bm * sn), 0.f);
-                }
-                u = normalize(uu);
+            if (phase == PH_NEXT && have_pixel && samp < fr.spp) {       // camera ray of sample `samp`
+                hs = sample_hash(hp, samp);
+                u = jitter_dir(fr, pixel_dir(fr, px, image_row(fr, lrow), fr.z), hs);
                 O = Cam;
                 d = 0; refr = 1.f; ids = 0; dmask = 0; shadow = false;
                 path_open = true;

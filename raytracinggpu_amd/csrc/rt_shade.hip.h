@@ -1,0 +1,157 @@
+// rt_shade.hip.h -- the arithmetic of one path step, written once for the four render structures.
+//
+// Scene::getColor (cpu_launcher.cpp:566-648) and the camera ray (cpu:699-709) as functions over values.  The render kernels -- render_kernel
+// (rt_kernels.hip.h), render_persistent (rt_persistent.hip.h), wf_advance (rt_wavefront.hip.h), wf_path (rt_path.hip.h) -- keep their own control
+// flow and state (a loop over segments, a phase machine, queue records in HBM, tables in LDS) and call these for everything they compute alike,
+// so a material rule is changed in one place and the four stay bit-identical by construction.  No function here knows its caller.  Every
+// expression keeps the operand order and the single roundings of the reference (DESIGN.md "Numerics").
+//
+// Included by rt_kernels.hip.h once the vector, RNG, Scene, Frame and Material definitions it needs are visible.
+#pragma once
+
+namespace rtk {
+
+// ---- pixels and samples ----
+// image row of local row `lrow` of a (sub-)frame: rows come in tiles of tile_rows, every tile_step-th tile of the image from row0 on
+__device__ __forceinline__ int image_row(const Frame &fr, int lrow) {
+    return fr.row0 + (lrow / fr.tile_rows) * fr.tile_rows * fr.tile_step + (lrow % fr.tile_rows);
+}
+// the counter RNG's key of a pixel, and of its sample `samp` (DESIGN.md "RNG"): keyed by the GLOBAL pixel, so a tile of a frame draws what the whole frame draws
+__device__ __forceinline__ uint32_t pixel_hash(const Frame &fr, int row, int px, uint32_t seed) {
+    return mix32(((uint32_t)row * (uint32_t)fr.W + (uint32_t)px) ^ mix32(seed));
+}
+__device__ __forceinline__ uint32_t sample_hash(uint32_t hp, int samp) { return mix32(hp ^ ((uint32_t)samp * 0x9E3779B1U)); }
+
+// The camera ray's direction, cpu:699-709, in three parts.  pixel_dir: pixel (px, row) seen from the camera of cpu_launcher (z = -W / (2 tan(fov / 2)): looking down -z).
+__device__ __forceinline__ f3 pixel_dir(const Frame &fr, int px, int row, float z) {
+    // cpu:699: +0.5/-0.5 are double literals, narrowed by the Vector constructor
+    return mk((float)((double)((float)px - (float)fr.W / 2) + 0.5), (float)((double)((float)fr.H / 2 - (float)row) - 0.5), z);
+}
+// ... seen from a posed camera at C with the basis of the Frame, realtime:1115: cam.C + cam.bz * z + cam.bx * X + cam.by * Y (the position is part of the direction there)
+__device__ __forceinline__ f3 posed_dir(const Frame &fr, f3 C, f3 uc) {
+    const f3 Bx = mk(fr.bx[0], fr.bx[1], fr.bx[2]), By = mk(fr.by[0], fr.by[1], fr.by[2]), Bz = mk(fr.bz[0], fr.bz[1], fr.bz[2]);
+    const f3 a = C + mk(Bz.x * uc.z, Bz.y * uc.z, Bz.z * uc.z);
+    const f3 b = a + mk(Bx.x * uc.x, Bx.y * uc.x, Bx.z * uc.x);
+    return b + mk(By.x * uc.y, By.y * uc.y, By.z * uc.y);
+}
+// ... moved by the anti-aliasing jitter of cpu:705-707 (Box-Muller from dims 2, 3 of the sample's key hs) and normalised (cpu:709).  With sigma == 0 the jitter is
+// exactly +-0 and the direction is unchanged: the key is not read.
+__device__ __forceinline__ f3 jitter_dir(const Frame &fr, f3 v, uint32_t hs) {
+    if (fr.sigma != 0.f) {
+        const float r1 = uniform01(hs, 0, 2), r2 = uniform01(hs, 0, 3);
+        const float bm = fr.sigma * rt_sqrtf(-2 * logf(r1));
+        double sn, cs;
+        rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r2, sn, cs);
+        v = v + mk((float)((double)bm * cs), (float)((double)bm * sn), 0.f);
+    }
+    return normalize(v);
+}
+// The whole of it for a Frame that may carry a pose (cam_mode 1).  The kernels that the host never hands a pose (render_kernel, render_persistent) compose
+// jitter_dir(pixel_dir) themselves: the pose branch costs them registers (one wave of occupancy in render_persistent's counting instantiation).
+__device__ __forceinline__ f3 camera_dir(const Frame &fr, f3 C, float z, int px, int row, uint32_t hs) {
+    f3 v = pixel_dir(fr, px, row, z);
+    if (fr.cam_mode == 1) v = posed_dir(fr, C, v);
+    return jitter_dir(fr, v, hs);
+}
+
+// ---- the hit ----
+// alpha, beta, gamma of triangle `tri` (visit order) for the ray (O, u): get_smooth_normal's expressions (realtime_render.cu:221-245).  The smooth normal, the
+// texture lookup (tex_albedo, rt_wavefront.hip.h) and rt_kat_surface read these.
+struct Bary { float alpha, beta, gamma; };
+__device__ __forceinline__ Bary tri_bary(const Scene &sc, int tri, f3 O, f3 u) {
+    const float4 q0 = sc.tri[3 * tri], q1 = sc.tri[3 * tri + 1], q2 = sc.tri[3 * tri + 2];
+    const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x), Nt = mk(q2.y, q2.z, q2.w);
+    Bary b;
+    b.beta = dot(e2, cross(A - O, u)) / dot(u, Nt);
+    b.gamma = -dot(e1, cross(A - O, u)) / dot(u, Nt);
+    b.alpha = 1 - b.beta - b.gamma;
+    return b;
+}
+// The unit normal of a hit, three ways.  Does object `win`, hit on triangle `tri_win` (visit order; < 0: a sphere), shade with interpolated vertex normals?
+__device__ __forceinline__ bool smooth_hit(const Scene &sc, int win, int tri_win) { return tri_win >= 0 && sc.nrm != nullptr && ((sc.smooth_mask >> win) & 1); }
+// get_smooth_normal (realtime_render.cu:221-245) for the ray (O, u); hands back the barycentrics it formed
+__device__ __forceinline__ f3 smooth_normal(const Scene &sc, int tri, f3 O, f3 u, Bary &bary) {
+    bary = tri_bary(sc, tri, O, u);
+    const float4 na = sc.nrm[3 * tri], nb = sc.nrm[3 * tri + 1], nc = sc.nrm[3 * tri + 2];
+    return normalize((bary.alpha * mk(na.x, na.y, na.z) + bary.beta * mk(nb.x, nb.y, nb.z)) + bary.gamma * mk(nc.x, nc.y, nc.z));
+}
+__device__ __forceinline__ f3 flat_normal(const Scene &sc, int tri) { const float4 q2 = sc.tri[3 * tri + 2]; return normalize(mk(q2.y, q2.z, q2.w)); }   // cpu:308
+__device__ __forceinline__ f3 sphere_normal(const Scene &sc, int obj, f3 P) { return normalize(P - sphere_centre_of(sc, obj)); }                      // cpu:524-525
+// ... and the choice between them for the hit P of ray (O, u).  (wf_path spells the same choice out around its index checks; as one call there it costs scalar
+// registers: 14 more kernel-argument reloads, 1.6 % of its frame time.)
+__device__ __forceinline__ f3 hit_normal(const Scene &sc, int win, int tri_win, f3 O, f3 u, f3 P, Bary &bary, bool &have_bary) {
+    have_bary = smooth_hit(sc, win, tri_win);
+    if (have_bary) return smooth_normal(sc, tri_win, O, u, bary);
+    return tri_win >= 0 ? flat_normal(sc, tri_win) : sphere_normal(sc, win, P);
+}
+
+// ---- Scene::getColor's branches ----
+// cpu:573-579: the ray (O, u) that hit a mirror at P with normal N becomes the reflected ray
+__device__ __forceinline__ void mirror_step(float eps, f3 P, f3 N, f3 &O, f3 &u) {
+    O = P + eps * N;
+    u = u - (2 * dot(u, N)) * N;
+}
+// cpu:580-604: the same at a surface with n_in != n_out, for a ray whose Ray::refraction_index is `refr`: total reflection, or the refracted ray.  crossed: the ray
+// went through the surface, and its index is now refr_after = out2in ? n_in : n_out (out2in: it came from the n_out side).
+struct Refraction { bool crossed, out2in; float refr_after; };
+__device__ __forceinline__ Refraction refract_step(const Material &m, float refr, float eps, f3 P, f3 N, f3 &O, f3 &u) {
+    Refraction r;
+    float ratio;
+    r.out2in = refr == m.n_out;
+    if (r.out2in) ratio = m.n_out / m.n_in;
+    else { ratio = m.n_in / m.n_out; N = -N; }
+    const float un = dot(u, N);
+    if (((r.out2in && refr > m.n_in) || (!r.out2in && refr > m.n_out)) && (ratio * ratio) * (1 - un * un) > 1) {
+        O = P + eps * N;
+        u = u - (2 * un) * N;
+        r.crossed = false;
+        r.refr_after = refr;
+    } else {
+        O = P - eps * N;
+        const f3 Nc = (-rt_sqrtf(1 - (ratio * ratio) * (1 - un * un))) * N;
+        const f3 Tc = ratio * (u - un * N);
+        u = Nc + Tc;
+        r.crossed = true;
+        r.refr_after = r.out2in ? m.n_in : m.n_out;
+    }
+    return r;
+}
+
+// cpu:614: the shadow ray from P_adjusted to the light, NORMED_VEC (cpu:30): (L - Pa) / nl with nl = sqrt(norm2(L - Pa))
+__device__ __forceinline__ f3 shadow_dir(f3 L, f3 Pa, float &nl) { return normalize(L - Pa, nl); }
+__device__ __forceinline__ f3 shadow_dir(f3 L, f3 Pa) { float nl; return shadow_dir(L, Pa, nl); }
+// cpu:615: is the light hidden from P_adjusted, given the shadow ray's nearest hit point Pp (cpu:560) -- or its ray (Pa, u) and the hit's t?
+__device__ __forceinline__ bool light_hidden(f3 Pa, f3 Pp, f3 L) { return norm2(Pp - Pa) <= norm2(L - Pa); }
+__device__ __forceinline__ bool light_hidden(f3 Pa, f3 u, float t, f3 L) { return light_hidden(Pa, Pa + t * u, L); }
+// cpu:620-623: the scalar l of a diffuse hit at P with normal N under a visible light (the quotient and the product in binary64, as the reference's promotions make them)
+__device__ __forceinline__ float direct_term(const Scene &sc, f3 L, f3 P, f3 N) {
+    const f3 wl = normalize(L - P);
+    const float dn = dot(N, wl);
+    const float mx = (dn < 0.f) ? 0.f : dn;                           // std::max(dn, 0.f)
+    return (float)((double)sc.intensity / (4 * 3.14159265358979323846 * (double)norm2(L - P)) * (double)mx);   // cpu:623
+}
+// cpu:627-641: the cosine-weighted direction about N of segment d's bounce, from the sample key's dims 0, 1 at depth d
+__device__ __forceinline__ f3 cosine_bounce(f3 N, uint32_t hs, int d) {
+    const float r1 = uniform01(hs, (uint32_t)d, 0);                   // cpu:628-629
+    const float r2 = uniform01(hs, (uint32_t)d, 1);
+    double sn, cs;
+    rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r1, sn, cs);
+    const float s1 = rt_sqrtf(1 - r2);
+    const float x = (float)(cs * (double)s1);                         // cpu:630
+    const float y = (float)(sn * (double)s1);                         // cpu:631
+    const float zz = rt_sqrtf(r2);                                    // cpu:632
+    // T1 = normalize((-Ny, Nx, 0)) if Nx != 0 && Ny != 0 else normalize((-Nz, 0, Nx)) (cpu:634-638): two quotients, the third component is +0 / n
+    const bool t1a = N.y != 0 && N.x != 0;
+    float t1p, t1q, t1z;
+    normalize_pq0(t1a ? -N.y : -N.z, N.x, t1p, t1q, t1z);
+    const f3 T1 = t1a ? mk(t1p, t1q, t1z) : mk(t1p, t1z, t1q);
+    const f3 T2 = cross(N, T1);
+    return x * T1 + y * T2 + zz * N;                                  // cpu:641
+}
+// cpu:624, 642-644: the colour of a path from a diffuse segment on -- its direct light l * albedo / pi plus albedo (.) the colour `ans` of what follows it
+__device__ __forceinline__ f3 fold_segment(f3 ans, float l, f3 alb) {
+    const float PI_F = (float)3.14159265358979323846;
+    return (l * alb) / PI_F + alb * ans;
+}
+
+}  // namespace rtk

@@ -3,7 +3,7 @@
 // The per-pixel render of cpu_launcher.cpp:693-718 / KernelLaunch (optimized.cu:670-772) split by
 // divergence behaviour instead of by pixel:
 //
-//   wf_advance<FIRST>  one lane per pixel, uniform: camera ray of sample s (cpu:699-709), its ray/sphere tests
+//   wf_advance<FIRST>  one lane per pixel, uniform: camera ray of sample s, its ray/sphere tests
 //              (cpu:512-527) and the mesh's root-box test (cpu:279); path record initialised
 //   wf_travq   (rt_travq.hip.h; the pipeline's traversal kernel by default) the BVH traversal as a per-wave work stack of
 //              (ray slot, sibling pair) entries: BoundingBox::intersect cpu:146-157, moller_trumbore cpu:226-236, traversal
@@ -13,9 +13,9 @@
 //              scrambled, share of the rays; when that runs out busy lanes hand parts of their traversal
 //              to idle lanes (see "work splitting" below).
 //   wf_advance one lane per pixel, uniform: closes the query (Scene::intersect_all cpu:545-564), then
-//              Scene::getColor's branch for it -- material / shadow ray (cpu:573-614) or direct light +
-//              cosine bounce (cpu:615-642) -- writes the next ray with its sphere and root-box tests, or
-//              folds the finished path (cpu:642-644), accumulates the sample (cpu:711) and, after the last
+//              Scene::getColor's branch for it -- material / shadow ray or direct light + cosine bounce
+//              (the arithmetic of each: rt_shade.hip.h) -- writes the next ray with its sphere and root-box
+//              tests, or folds the finished path, accumulates the sample (cpu:711) and, after the last
 //              sample, stores the pixel as one float4 (cpu:713)
 //
 // A shadow ray and the continuation (bounce / mirror / refraction) ray that leave the same hit point do not
@@ -529,17 +529,6 @@ struct TexScene {
     float4 *ALB;                             // albedo of textured diffuse segment d of path i: ALB[d * n_paths + i]
     int mask;                                // bit k: object k is a textured mesh
 };
-// alpha, beta, gamma of triangle `tri` for the ray (O, u): the expressions of the smooth-normal branch of wf_advance_path (get_smooth_normal, realtime_render.cu:221-245)
-struct Bary { float alpha, beta, gamma; };
-__device__ __forceinline__ Bary tri_bary(const Scene &sc, int tri, f3 O, f3 u) {
-    const float4 q0 = sc.tri[3 * tri], q1 = sc.tri[3 * tri + 1], q2 = sc.tri[3 * tri + 2];
-    const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x), Nt = mk(q2.y, q2.z, q2.w);
-    Bary b;
-    b.beta = dot(e2, cross(A - O, u)) / dot(u, Nt);
-    b.gamma = -dot(e1, cross(A - O, u)) / dot(u, Nt);
-    b.alpha = 1 - b.beta - b.gamma;
-    return b;
-}
 // floor of a texel coordinate as an int, and the fraction c - floor(c).  A coordinate outside [-2^31, 2^31) -- NaN and +-inf included -- is index 0 with fraction 0.
 __device__ __forceinline__ int tex_floor(float c, float &frac) {
     const bool ok = c >= -2147483648.f && c < 2147483648.f;
@@ -586,7 +575,7 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 }
 
 // ---- wf_advance: close the queries, shade, emit the next rays -----------------------------------------------
-// FIRST: the launch that opens the chain's samples -- camera rays (cpu:699-709) instead of closing queries.
+// FIRST: the launch that opens the chain's samples -- camera rays instead of closing queries.
 // TEX (wf_advance_tex, never FIRST): textured meshes -- the albedo of a textured diffuse hit goes to ts.ALB and the fold reads it from there.
 // The samples of a pixel are independent paths (the reference's loop cpu:701-712 carries nothing but the sum): a chain traces
 // several of them at once as items, each writes its colour, and path_reduce adds the colours in sample order.
@@ -604,8 +593,6 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     const float4 y1 = FIRST ? kDead : st.QR[2 * (size_t)qy + 1];      // (u.y, u.z, flag word, t of the nearest sphere) of the continuation ray in flight
     const int F = __float_as_int(y1.z);
     if (!FIRST && !(F & PF_ALIVE)) return;                            // finished (or padding): its queue flags are already 0
-    const float PI_F = (float)3.14159265358979323846;
-    const double PI_D = 3.14159265358979323846;
     const f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
     int refr_code = FIRST ? 0 : (F >> PQ_REFR_SHIFT) & 63;            // Ray::refraction_index = 1 (cpu:100)
     int d = 0, nrays = 0;
@@ -632,35 +619,15 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     }
     wf_decode(st, fr, i - s_rel * st.n_px, px, lrow, valid);
     valid = valid && samp < fr.spp && in_batch;                       // the last chain of a frame may be short of samples
-    const int row = fr.row0 + (lrow / fr.tile_rows) * fr.tile_rows * fr.tile_step + (lrow % fr.tile_rows);
+    const int row = image_row(fr, lrow);
 
     if (FIRST) {
         if (!valid) { st.QR[2 * (size_t)qy + 1] = kDead; return; }       // (the X slot of a pixel outside the frame is never written: zero from the layout's memset)
         if (fr.segs <= 0) {
             finished = true;                                          // optimized.cu convention with num_bounce 0: black
         } else {
-            // cpu:699: +0.5/-0.5 are double literals, narrowed by the Vector constructor
-            const f3 uc = mk((float)((double)((float)px - (float)fr.W / 2) + 0.5),
-                             (float)((double)((float)fr.H / 2 - (float)row) - 0.5), fr_z);
-            f3 ucm = uc;
-            if (fr.cam_mode == 1) {   // realtime:1115: cam.C + cam.bz * z + cam.bx * X + cam.by * Y (the position is part of the direction there)
-                const f3 Cc = mk(camx, camy, camz), Bx = mk(fr.bx[0], fr.bx[1], fr.bx[2]), By = mk(fr.by[0], fr.by[1], fr.by[2]), Bz = mk(fr.bz[0], fr.bz[1], fr.bz[2]);
-                const f3 a = Cc + mk(Bz.x * fr_z, Bz.y * fr_z, Bz.z * fr_z);
-                const f3 b = a + mk(Bx.x * uc.x, Bx.y * uc.x, Bx.z * uc.x);
-                ucm = b + mk(By.x * uc.y, By.y * uc.y, By.z * uc.y);
-            }
-            f3 uu = ucm;
-            if (fr.sigma != 0.f) {   // cpu:705-707; with sigma == 0 the jitter is exactly +-0
-                const uint32_t hp = mix32(((uint32_t)row * (uint32_t)fr.W + (uint32_t)px) ^ mix32(fr_seed));
-                const uint32_t hs = mix32(hp ^ ((uint32_t)samp * 0x9E3779B1U));
-                const float r1 = uniform01(hs, 0, 2), r2 = uniform01(hs, 0, 3);
-                const float bm = fr.sigma * rt_sqrtf(-2 * logf(r1));
-                double sn, cs;
-                rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r2, sn, cs);
-                uu = ucm + mk((float)((double)bm * cs), (float)((double)bm * sn), 0.f);
-            }
             Oy = mk(camx, camy, camz);
-            uy = normalize(uu);
+            uy = camera_dir(fr, Oy, fr_z, px, row, sample_hash(pixel_hash(fr, row, px, fr_seed), samp));
             emitY = true;                                             // continuation ray of segment 0
             nrays = 1;
         }
@@ -668,7 +635,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         ADV_MARK("closex_begin");
         d = (F >> PF_DEPTH_SHIFT) & PF_DEPTH_MASK;                    // segment of the continuation ray in flight
         nrays = (F >> PF_RAYS_SHIFT) & PF_RAYS_MASK;
-        // ---- (1) the shadow ray of segment d-1's hit came back: direct light or not (cpu:615) ----
+        // ---- (1) the shadow ray of segment d-1's hit came back: direct light or not (light_hidden) ----
         // cpu:615 compares |P' - P_adj|^2, P' = P_adj + t_min u, with |L - P_adj|^2; it is monotone in t_min (every rounding involved is),
         // so it holds iff it holds for the nearest sphere (decided when the ray was emitted: PF_XSPHERE) or for the nearest triangle
         if (F & PF_HASX) {
@@ -678,14 +645,13 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 if (m != WF_NOHIT) {
                     const float4 x0 = st.QR[2 * (size_t)qx], x1 = st.QR[2 * (size_t)qx + 1];
                     const f3 Oxr = mk(x0.x, x0.y, x0.z), uxr = mk(x0.w, x1.x, x1.y);
-                    const f3 Pp = Oxr + __uint_as_float((unsigned int)(m >> 32)) * uxr;   // cpu:560 (Ox is P_adjusted)
-                    shadowed = norm2(Pp - Oxr) <= norm2(L - Oxr);
+                    shadowed = light_hidden(Oxr, uxr, __uint_as_float((unsigned int)(m >> 32)), L);   // (Ox is P_adjusted)
                 }
             }
             if (shadowed) st.LS[(size_t)(d - 1) * st.n_paths + i] = 0.f;               // the l stored when the segment was shaded does not count
         }
         ADV_MARK("closex_end");
-        // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit (cpu:570-614) ----
+        // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit ----
         if (F & PF_HASY) {
             ADV_MARK("closey_begin");
             const float4 r0 = st.QR[2 * (size_t)qy];
@@ -705,63 +671,30 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             }
             if (win >= 0) {                                           // a miss is black (cpu:571): nothing to emit
                 const f3 P = O + t_min * u;                           // cpu:560
-                f3 N;
-                Bary bary{0.f, 0.f, 0.f};                             // (TEX) the smooth-normal branch's barycentrics, shared with the texture lookup
+                Bary bary{0.f, 0.f, 0.f};                             // (TEX) the smooth normal's barycentrics, shared with the texture lookup
                 bool have_bary = false;
-                if (tri_win >= 0 && sc.nrm != nullptr && ((sc.smooth_mask >> win) & 1)) {              // get_smooth_normal (of a smooth mesh), realtime_render.cu:221-245
-                    const float4 q0 = sc.tri[3 * tri_win], q1 = sc.tri[3 * tri_win + 1], q2 = sc.tri[3 * tri_win + 2];
-                    const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x), Nt = mk(q2.y, q2.z, q2.w);
-                    const float beta = dot(e2, cross(A - O, u)) / dot(u, Nt);
-                    const float gamma = -dot(e1, cross(A - O, u)) / dot(u, Nt);
-                    const float alpha = 1 - beta - gamma;
-                    if (TEX) { bary.alpha = alpha; bary.beta = beta; bary.gamma = gamma; have_bary = true; }
-                    const float4 na = sc.nrm[3 * tri_win], nb = sc.nrm[3 * tri_win + 1], nc = sc.nrm[3 * tri_win + 2];
-                    N = normalize((alpha * mk(na.x, na.y, na.z) + beta * mk(nb.x, nb.y, nb.z)) + gamma * mk(nc.x, nc.y, nc.z));
-                } else if (tri_win >= 0) {
-                    const float4 q2 = sc.tri[3 * tri_win + 2];
-                    N = normalize(mk(q2.y, q2.z, q2.w));              // cpu:308
-                } else {
-                    N = normalize(P - sphere_centre_of(sc, win));     // cpu:524-525
-                }
+                const f3 N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
                 const Material m = material_of(sc, win);
                 ADV_MARK("closey_end");
                 bool cont = false;                                    // a continuation ray of segment d+1 was built in (O,u)
-                if (m.mirror) {                                       // cpu:573-579
-                    O = P + fr.eps * N;
-                    u = u - (2 * dot(u, N)) * N;
+                if (m.mirror) {
+                    mirror_step(fr.eps, P, N, O, u);
                     cont = true;
-                } else if (m.n_in != m.n_out) {                       // cpu:580-604
-                    float ratio;
+                } else if (m.n_in != m.n_out) {
                     float refr = 1.f;                                 // the ray's index: 1, or the n_in / n_out of the surface it last crossed
                     if (refr_code != 0) { const Material mr = material_of(sc, (refr_code >> 1) - 1); refr = (refr_code & 1) ? mr.n_out : mr.n_in; }
-                    const bool out2in = refr == m.n_out;
-                    if (out2in) ratio = m.n_out / m.n_in;
-                    else { ratio = m.n_in / m.n_out; N = -N; }
-                    const float un = dot(u, N);
-                    if (((out2in && refr > m.n_in) || (!out2in && refr > m.n_out)) && (ratio * ratio) * (1 - un * un) > 1) {
-                        O = P + fr.eps * N;
-                        u = u - (2 * un) * N;
-                    } else {
-                        O = P - fr.eps * N;
-                        const f3 Nc = (-rt_sqrtf(1 - (ratio * ratio) * (1 - un * un))) * N;
-                        const f3 Tc = ratio * (u - un * N);
-                        u = Nc + Tc;
-                        refr_code = (win + 1) << 1 | (out2in ? 0 : 1);    // refr = out2in ? m.n_in : m.n_out
-                    }
+                    const Refraction r = refract_step(m, refr, fr.eps, P, N, O, u);
+                    if (r.crossed) refr_code = (win + 1) << 1 | (r.out2in ? 0 : 1);    // refr = out2in ? m.n_in : m.n_out
                     cont = true;
-                } else {                                              // cpu:605-642: diffuse
+                } else {                                              // diffuse
                     ADV_MARK("diffuse_begin");
                     const f3 Pa = P + fr.eps * N;
-                    const f3 toL = L - Pa;
                     float nl;
-                    Ox = Pa; ux = normalize(toL, nl);   // = toL / nl, nl = sqrt(norm2(toL))     // NORMED_VEC, cpu:614: the shadow ray of segment d
+                    Ox = Pa; ux = shadow_dir(L, Pa, nl);                // the shadow ray of segment d
                     x_bound = wf_anyhit_bound(Pa, nl);
                     nrays += 1;
-                    // the segment's direct term if the light turns out to be visible (cpu:620-623); kept until the shadow ray is back
-                    const f3 wl = normalize(L - P);
-                    const float dn = dot(N, wl);
-                    const float mx = (dn < 0.f) ? 0.f : dn;
-                    const float lvis = (float)((double)sc.intensity / (4 * PI_D * (double)norm2(L - P)) * (double)mx);
+                    // the segment's direct term if the light turns out to be visible; kept until the shadow ray is back
+                    const float lvis = direct_term(sc, L, P, N);
                     st.LS[(size_t)d * st.n_paths + i] = lvis;
                     // A surface that faces away from the light (mx = 0) has the direct term +0 whether the light is visible or not: shaded, cpu:616 stores the literal 0; lit,
                     // cpu:623 computes l = +0 -- the same 32 bits (a NaN or a -0 from a degenerate light is not +0 and keeps its ray).  The reference still calls intersect_all
@@ -780,25 +713,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         sid = kSidTextured;
                     }
                     ADV_MARK("diffuse_end");
-                    if (d + 1 < fr.segs) {                            // the bounce ray (cpu:627-642): needs r1, r2 and N only
+                    if (d + 1 < fr.segs) {                            // the bounce ray: needs the sample's key and N only
                         ADV_MARK("bounce_begin");
-                        const uint32_t hp = mix32(((uint32_t)row * (uint32_t)fr.W + (uint32_t)px) ^ mix32(fr_seed));
-                        const uint32_t hs = mix32(hp ^ ((uint32_t)samp * 0x9E3779B1U));
-                        const float r1u = uniform01(hs, (uint32_t)d, 0);
-                        const float r2u = uniform01(hs, (uint32_t)d, 1);
-                        double sn, cs;
-                        rt_sincos_2pi(2 * PI_D * (double)r1u, sn, cs);
-                        const float s1f = rt_sqrtf(1 - r2u);
-                        const float x = (float)(cs * (double)s1f);
-                        const float y = (float)(sn * (double)s1f);
-                        const float zz = rt_sqrtf(r2u);
-                        // T1 = normalize((-Ny, Nx, 0)) if Nx != 0 && Ny != 0 else normalize((-Nz, 0, Nx)) (cpu:634-638): two quotients, the third component is +0 / n
-                        const bool t1a = N.y != 0 && N.x != 0;
-                        float t1p, t1q, t1z;
-                        normalize_pq0(t1a ? -N.y : -N.z, N.x, t1p, t1q, t1z);
-                        const f3 T1 = t1a ? mk(t1p, t1q, t1z) : mk(t1p, t1z, t1q);
-                        const f3 T2 = cross(N, T1);
-                        u = x * T1 + y * T2 + zz * N;
+                        u = cosine_bounce(N, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d);
                         O = Pa;
                         refr_code = 0;                                // Ray(P_adjusted, random_direction): index 1
                         cont = true;
@@ -816,24 +733,22 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         finished = !(emitX || emitY);
     }
 
-    if (finished) {   // nothing in flight: fold the path back to front (cpu:642-644), accumulate the sample (cpu:711)
+    if (finished) {   // nothing in flight: fold the path back to front, accumulate the sample (cpu:711)
         ADV_MARK("fold_begin");
         f3 ans = mk(0, 0, 0);
         const int nseg = d < fr.segs ? d : fr.segs;
         for (int k = nseg - 1; k >= 0; --k) {
             const int sid = st.SID[(size_t)k * st.n_paths + i];
             if (sid != 0xff) {
+                f3 alb;
                 if (TEX && sid == kSidTextured) {                     // the albedo the segment stored when it was shaded
-                    const float l = st.LS[(size_t)k * st.n_paths + i];
                     const float4 a = ts.ALB[(size_t)k * st.n_paths + i];
-                    const f3 alb = mk(a.x, a.y, a.z);
-                    ans = (l * alb) / PI_F + alb * ans;
+                    alb = mk(a.x, a.y, a.z);
                 } else {
-                const Material m = material_of(sc, sid);
-                const float l = st.LS[(size_t)k * st.n_paths + i];
-                const f3 alb = mk(m.ar, m.ag, m.ab);
-                ans = (l * alb) / PI_F + alb * ans;
+                    const Material m = material_of(sc, sid);
+                    alb = mk(m.ar, m.ag, m.ab);
                 }
+                ans = fold_segment(ans, st.LS[(size_t)k * st.n_paths + i], alb);
             }
         }
         if (st.samp_out != nullptr) {                                 // more than one sample per pixel: path_reduce sums in sample order
@@ -860,9 +775,8 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     float t_sph = 0.f;
     if (emitX) {
         const float tS = hx.t;                                        // only the value of the shadow ray's nearest hit matters
-        const f3 Pp = Ox + tS * ux;                                   // cpu:560
         flags |= PF_HASX;
-        if (!x_moot && norm2(Pp - Ox) <= norm2(L - Ox)) flags |= PQ_XSPHERE;      // cpu:615 holds for the sphere already: whatever the mesh says, the segment is shaded (the comparison is monotone in t)
+        if (!x_moot && light_hidden(Ox, ux, tS, L)) flags |= PQ_XSPHERE;      // cpu:615 holds for the sphere already: whatever the mesh says, the segment is shaded (the comparison is monotone in t)
         // ... so with any-hit on that ray is not traced through the mesh at all (intersect_all does: a run that counts the reference's work has any-hit off)
         if (!x_moot && (!(flags & PQ_XSPHERE) || !st.anyhit) && wf_root_test<STATS>(sc, st, rx, Ox, ux, wk)) {   // only then does anybody read the record: the traversal, and this kernel if the mesh is hit
             flags |= PF_MESHX;

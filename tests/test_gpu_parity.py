@@ -404,6 +404,11 @@ def test_jitter_sigma_0p2_matches_oracle(ctx, oracle, oracle_cat, cat_golden):
     assert linf(oracle, got, exp) <= TOL
     assert same > 0.99
     np.testing.assert_array_equal(got[..., 3], exp[..., 3])
+    # every render structure draws the jitter from the one camera_dir (rt_shade.hip.h): the same frame, bit for bit, colour and ray counts
+    for variant in VARIANTS:
+        other = ctx.render(rt.make_params(320, 200, 4, 2, variant=variant, **kw))
+        print(f"sigma=0.2 {variant}: values that differ from the default variant's {int((~values_equal(other, got)).sum())}")
+        assert values_equal(other, got).all(), variant
     # jitter really moves the samples: the image differs from the sigma = 0 one along edges
     plain = ctx.render(rt.make_params(320, 200, 4, 2, **rt.scenes.CPU_LAUNCHER))
     assert (plain[..., :3] != got[..., :3]).any()
@@ -489,6 +494,10 @@ def test_posed_camera_and_progressive_accumulation(ctx, oracle, oracle_cat, cat_
             assert linf(oracle, got, exp) <= TOL
             assert values_equal(got[..., :3], exp[..., :3]).mean() > 0.99
             np.testing.assert_array_equal(got[..., 3], exp[..., 3])
+            # the fused kernel, the other one with a pose path: the same frame, bit for bit
+            fused = ctx.render_pose(rt.make_params(W, H, spp, b, variant="path", **dict(kw, seed=seed)), pose)
+            print(f"pose frame {frame} path: values that differ from the default variant's {int((~values_equal(fused, got)).sum())}")
+            assert values_equal(fused, got).all()
             # the library's own accumulation of the SAME frames, replayed by the oracle's accumulate: bit-exact floats
             disp, rgb8 = ctx.progressive_frame(rt.make_params(W, H, spp, b, **kw), pose)
             assert ctx.progressive_frames() == frame
