@@ -214,6 +214,49 @@ typedef struct rt_frame_desc {
 } rt_frame_desc;
 int rt_render_device_batch(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const rt_frame_desc *frames, int n_frames, void *stream);
 
+/* --- an ANIMATED scene (ABI 6, additive): the light and the spheres of the scene in use, changed in place.  realtime_render.cu moves them between two frames
+ *     of a running sequence with two one-thread kernels, MoveLightSource (:1072-1090) and MoveObject (:1092-1098); here they are the part of the scene that lives
+ *     in the kernels' arguments, so an edit is a host-side store: no mesh is re-sent or re-laid out, and smooth normals, textures, device-side transforms and
+ *     rebuilt trees stay as they are (rt_kat_layout_hash does not change) -- where a new rt_scene_upload* would drop all of them.
+ *       get / set_light   Scene::L and Scene::intensity (cpu:650-651);
+ *       get / set_sphere  the sphere at position object_slot of Scene::objects (as rt_mesh.object_slot and MoveObject's `index` count): geometry AND material;
+ *       move_sphere       MoveObject: C' = C + v * dt per component in binary32, the product first (two roundings) -- reproducible exactly;
+ *       move_light        MoveLightSource: get, rt_light_orbit, set;
+ *       rt_light_orbit    (host function, no context) the light turned about the y axis through the origin: radius = sqrtf(x * x + z * z) (the reference's
+ *                         powf(d, 2) as d * d), angle = atan2f(z, x) + angular_speed * dt, x' = radius * cosf(angle), z' = radius * sinf(angle), y and the
+ *                         intensity untouched; binary32 throughout, with the host's C library.  The reference evaluates it with CUDA's device functions, which no
+ *                         test here can run: like the posed camera this row is unpinned (x', z' are held to the formula in binary64 within 16 * 2^-24 * radius).
+ *     Contract: after any sequence of these calls every render entry (rt_render*, _device, _batch, _async, _pose*, rt_progressive_frame, rt_trace_rays,
+ *     rt_count_work; every rt_variant) produces, bit for bit, what it produces after rt_scene_upload* of the same meshes with the edited light / spheres:
+ *     what an upload derives from a sphere (R * R as one binary32 product, the per-object centre, mirror bit, albedo and indices) is derived again by the same code.
+ *     A frame uses the scene as it is when its render call is made: kernel arguments are captured at launch, so an edit between two frames in flight
+ *     (rt_ctx_set_pipelining, rt_render_async) needs no synchronisation.  Progressive accumulation is the caller's to reset (rt_progressive_reset; buffer_reset,
+ *     realtime:1246-1250).  RT_ERR_INVALID, scene unchanged: object_slot outside the scene or a mesh's.  RT_ERR_NO_SCENE: no upload, or the last rt_scene_upload*
+ *     failed.  rt_multi_* contexts have no such entries: upload again. ------------------------------------------------------------------------------------ */
+int rt_scene_get_light(const rt_ctx *ctx, rt_light *out);
+int rt_scene_set_light(rt_ctx *ctx, const rt_light *light);
+int rt_scene_get_sphere(const rt_ctx *ctx, int object_slot, rt_sphere *out);
+int rt_scene_set_sphere(rt_ctx *ctx, int object_slot, const rt_sphere *sphere);
+int rt_scene_move_light(rt_ctx *ctx, float angular_speed, float dt);                       /* MoveLightSource, realtime:1072-1090 (dt there: 2e-2f) */
+int rt_scene_move_sphere(rt_ctx *ctx, int object_slot, const float v[3], float dt);        /* MoveObject, realtime:1092-1098 (dt there: 0.2)         */
+int rt_light_orbit(const rt_light *in, float angular_speed, float dt, rt_light *out);      /* in == out is allowed                                    */
+
+/* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
+ *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
+ *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =
+ *     frames[k].seed -- ray counts (.w) included.  n_spheres must equal the uploaded count (RT_ERR_INVALID); every other rule of rt_render_device_batch holds
+ *     (num_rays 1, wavefront variants, RT_MAX_BATCH, distinct buffers; textured and smooth-shaded scenes render).  scenes == NULL is rt_render_device_batch.  The
+ *     uploaded scene is not changed (rt_scene_get_light answers as before).  Frames of a plain batch and lone frames run the kernels they ran: only an
+ *     animated batch reads the per-frame table.  Not per frame: sphere materials, the sphere count, meshes (rt_scene_set_sphere / rt_mesh_transform between
+ *     batches).  Replaces n x (MoveLightSource, MoveObject, KernelLaunch + sync; realtime_render.cu disp()). */
+typedef struct rt_sphere_pose { float center[3]; float radius; } rt_sphere_pose;
+typedef struct rt_frame_scene {    /* what differs from the uploaded scene in ONE frame of a batch */
+    rt_light       light;
+    rt_sphere_pose spheres[RT_MAX_SPHERES];
+} rt_frame_scene;
+int rt_render_device_batch_scenes(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const rt_frame_desc *frames,
+                                  const rt_frame_scene *scenes, int n_spheres, int n_frames, void *stream);
+
 /* --- tonemap: cpu:714-716 (gamma 1/2.2 in binary64, min 255, truncate) ------- */
 int rt_tonemap_device(rt_ctx *ctx, const void *rgba_dev, int64_t n_pixels, void *rgb8_dev, void *stream);
 /* render + tonemap + D2H of the interleaved RGB8 image (what stbi_write_png gets, cpu:719) */

@@ -567,6 +567,25 @@ public:
     }
     void use_untextured() { check(rt_mesh_set_texture(ctx_, nullptr, 0, nullptr, 3, 0, nullptr), "rt_mesh_set_texture"); }
     void use_untextured_of(const TriangleMesh &mesh) { check(rt_mesh_set_texture_of(ctx_, mesh.id, nullptr, 0, nullptr, 3, 0, nullptr), "rt_mesh_set_texture_of"); }
+    // The light and the spheres of the UPLOADED scene, changed in place (rt_scene_set_* / rt_scene_move_*: MoveLightSource and MoveObject of realtime_render.cu:1072-1098):
+    // no mesh is re-sent, smooth normals, textures, transforms and rebuilt trees stay.  They change what the device renders only, never the caller's Scene object:
+    // keep that in step yourself (scene.L = ...; sphere.C = ...) if a later upload() is to start from the same state.  A sphere is found by its Geometry::id.
+    void set_light(const Vector &L, float intensity) {
+        const rt_light l{{L[0], L[1], L[2]}, intensity};
+        check(rt_scene_set_light(ctx_, &l), "rt_scene_set_light");
+    }
+    void set_sphere(const Sphere &s) {
+        rt_sphere r;
+        for (int k = 0; k < 3; ++k) { r.center[k] = s.C[k]; r.albedo[k] = s.albedo[k]; }
+        r.radius = s.R; r.mirror = s.mirror ? 1 : 0;
+        r.in_refraction_index = s.in_refraction_index; r.out_refraction_index = s.out_refraction_index;
+        check(rt_scene_set_sphere(ctx_, s.id, &r), "rt_scene_set_sphere");
+    }
+    void move_light(float angular_speed, float dt = 2e-2f) { check(rt_scene_move_light(ctx_, angular_speed, dt), "rt_scene_move_light"); }
+    void move_object(int index, const Vector &v, float dt = 0.2f) {
+        const float vv[3] = {v[0], v[1], v[2]};
+        check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");
+    }
     // Camera{C, yaw, pitch} (realtime_render.cu:803-861) and disp() (:1243-1290) without the window: one accumulated frame
     std::vector<unsigned char> progressive_frame(const RenderSettings &s, const rt_camera_pose &pose, std::vector<float> *display = nullptr) {
         rt_params p = params(s);

@@ -26,7 +26,9 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_scene_upload_meshes", "rt_render_multi",
            "rt_render_multi_device", "rt_render_multi_rgb8", "rt_multi_get_stats",
            "rt_stats_enable", "rt_ctx_set_pipelining", "rt_render_async", "rt_wait", "rt_trace_rays", "rt_mesh_rebuild", "rt_mesh_rebuild_mode", "rt_mesh_build_stats", "rt_host_alloc", "rt_host_free", "rt_device_alloc", "rt_device_free", "rt_device_to_host", "rt_kat_sphere", "rt_kat_sqrt", "rt_kat_box", "rt_kat_triangle", "rt_kat_mesh", "rt_kat_layout_hash",
-           "rt_mesh_transform_of", "rt_mesh_set_normals_of", "rt_mesh_rebuild_of", "rt_mesh_set_texture", "rt_mesh_set_texture_of", "rt_kat_surface"]
+           "rt_mesh_transform_of", "rt_mesh_set_normals_of", "rt_mesh_rebuild_of", "rt_mesh_set_texture", "rt_mesh_set_texture_of", "rt_kat_surface",
+           "rt_scene_get_light", "rt_scene_set_light", "rt_scene_get_sphere", "rt_scene_set_sphere", "rt_scene_move_light", "rt_scene_move_sphere", "rt_light_orbit",
+           "rt_render_device_batch_scenes"]
 MAX_DEVICES = 16
 
 
@@ -72,6 +74,16 @@ class FrameDesc(C.Structure):
 
 
 MAX_BATCH = 16
+MAX_SPHERES = 16
+
+
+class SpherePose(C.Structure):
+    _fields_ = [("center", C.c_float * 3), ("radius", C.c_float)]
+
+
+class FrameScene(C.Structure):
+    """what differs from the uploaded scene in one frame of an animated batch (rt_frame_scene)"""
+    _fields_ = [("light", Light), ("spheres", SpherePose * MAX_SPHERES)]
 
 
 class Work(C.Structure):
@@ -205,6 +217,14 @@ def load():
     L.rt_mesh_set_texture.argtypes = [vp, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_mesh_set_texture_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_kat_surface.argtypes = [vp, fp3, C.c_int, C.c_float, fp3]
+    L.rt_scene_get_light.argtypes = [vp, C.POINTER(Light)]
+    L.rt_scene_set_light.argtypes = [vp, C.POINTER(Light)]
+    L.rt_scene_get_sphere.argtypes = [vp, C.c_int, C.POINTER(Sphere)]
+    L.rt_scene_set_sphere.argtypes = [vp, C.c_int, C.POINTER(Sphere)]
+    L.rt_scene_move_light.argtypes = [vp, C.c_float, C.c_float]
+    L.rt_scene_move_sphere.argtypes = [vp, C.c_int, fp3, C.c_float]
+    L.rt_light_orbit.argtypes = [C.POINTER(Light), C.c_float, C.c_float, C.POINTER(Light)]
+    L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_host_free.argtypes = [vp]
     L.rt_kat_sphere.argtypes = [vp, fp3, C.c_int, fp3]
@@ -246,6 +266,17 @@ def camera_basis(pose):
     if rc != RT_OK:
         raise RtError(rc, "rt_camera_basis")
     return out
+
+
+def light_orbit(light, angular_speed, dt=2e-2):
+    """rt_light_orbit: MoveLightSource's motion (realtime_render.cu:1072-1090) of light = (position, intensity), as the library computes it -> (position, intensity)."""
+    a, b = Light(), Light()
+    a.position[:] = light[0]
+    a.intensity = light[1]
+    rc = load().rt_light_orbit(C.byref(a), C.c_float(angular_speed), C.c_float(dt), C.byref(b))
+    if rc != RT_OK:
+        raise RtError(rc, "rt_light_orbit")
+    return tuple(float(x) for x in b.position), float(b.intensity)
 
 
 def device_count():
@@ -371,8 +402,10 @@ class Context:
         self._check(self._L.rt_render_device(self._h, C.byref(params), C.byref(rows), C.c_void_p(out_ptr),
                                              C.c_void_p(stream) if stream else None))
 
-    def render_device_batch(self, params, rows, frames, stream=None):
-        """rt_render_device_batch: `frames` = iterable of (out_ptr, camera_position, fov or None, seed); ONE launch chain traces them all (num_rays == 1)."""
+    def render_device_batch(self, params, rows, frames, stream=None, scenes=None):
+        """rt_render_device_batch: `frames` = iterable of (out_ptr, camera_position, fov or None, seed); ONE launch chain traces them all (num_rays == 1).
+        scenes: per frame (light, [(centre, radius), ...]) with light = (position, intensity) and one pose per uploaded sphere, in the uploaded order: the frame's own
+        light and sphere poses (rt_render_device_batch_scenes); None = the uploaded scene in every frame."""
         frames = list(frames)
         arr = (FrameDesc * max(len(frames), 1))()
         for d, (ptr, pos, fov, seed) in zip(arr, frames):
@@ -380,7 +413,58 @@ class Context:
             d.camera.fov = np.float32(np.pi / 3) if fov is None else np.float32(fov)
             d.seed = int(seed)
             d.out_rgba_dev = int(ptr)
-        self._check(self._L.rt_render_device_batch(self._h, C.byref(params), C.byref(rows), arr, len(frames), C.c_void_p(stream) if stream else None))
+        if scenes is None:
+            self._check(self._L.rt_render_device_batch(self._h, C.byref(params), C.byref(rows), arr, len(frames), C.c_void_p(stream) if stream else None))
+            return
+        scenes = list(scenes)
+        if len(scenes) != len(frames):
+            raise ValueError("scenes: one (light, sphere poses) per frame")
+        n_sph = len(scenes[0][1]) if scenes else 0
+        sarr = (FrameScene * max(len(scenes), 1))()
+        for d, (light, poses) in zip(sarr, scenes):
+            poses = list(poses)
+            if len(poses) != n_sph or n_sph > MAX_SPHERES:
+                raise ValueError("scenes: every frame poses the same (uploaded) spheres")
+            d.light.position[:] = light[0]
+            d.light.intensity = light[1]
+            for q, (centre, radius) in zip(d.spheres, poses):
+                q.center[:] = centre
+                q.radius = radius
+        self._check(self._L.rt_render_device_batch_scenes(self._h, C.byref(params), C.byref(rows), arr, sarr, n_sph, len(frames), C.c_void_p(stream) if stream else None))
+
+    # --- the light and the spheres of the scene in use, edited in place (rt_scene_*): no mesh work, smooth normals / textures / transforms / rebuilt trees stay
+    def light(self):
+        """rt_scene_get_light -> (position, intensity)"""
+        l = Light()
+        self._check(self._L.rt_scene_get_light(self._h, C.byref(l)))
+        return tuple(float(x) for x in l.position), float(l.intensity)
+
+    def set_light(self, position, intensity):
+        l = Light()
+        l.position[:] = position
+        l.intensity = intensity
+        self._check(self._L.rt_scene_set_light(self._h, C.byref(l)))
+
+    def sphere(self, object_slot):
+        """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""
+        s = Sphere()
+        self._check(self._L.rt_scene_get_sphere(self._h, int(object_slot), C.byref(s)))
+        return (tuple(float(x) for x in s.center), float(s.radius), tuple(float(x) for x in s.albedo), int(s.mirror),
+                float(s.in_refraction_index), float(s.out_refraction_index))
+
+    def set_sphere(self, object_slot, sphere):
+        """rt_scene_set_sphere: geometry and material of the sphere at position object_slot of Scene::objects; sphere as scene_upload takes it"""
+        arr = _marshal_scene([sphere], None, ((0.0, 0.0, 0.0), 0.0), ((0.0, 0.0, 0.0), None))[0]
+        self._check(self._L.rt_scene_set_sphere(self._h, int(object_slot), C.byref(arr[0])))
+
+    def move_light(self, angular_speed, dt=2e-2):
+        """MoveLightSource (realtime_render.cu:1072-1090)"""
+        self._check(self._L.rt_scene_move_light(self._h, C.c_float(angular_speed), C.c_float(dt)))
+
+    def move_sphere(self, object_slot, v, dt=0.2):
+        """MoveObject (realtime_render.cu:1092-1098): C += v * dt"""
+        vv = np.ascontiguousarray(v, np.float32).reshape(3)
+        self._check(self._L.rt_scene_move_sphere(self._h, int(object_slot), vv.ctypes.data_as(C.POINTER(C.c_float)), C.c_float(dt)))
 
     def render_async(self, params, out, slot=0, rgb8=False):
         """rt_render_async: whole frame into device buffer `slot` (0 / 1), device-to-host copy into `out` on the copy stream;

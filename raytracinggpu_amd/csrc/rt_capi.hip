@@ -105,7 +105,7 @@ int rt_ctx_destroy(rt_ctx *ctx) {
     ctx->wfM.release(); ctx->wfT.release(); ctx->wfLS.release(); ctx->wfSID.release(); ctx->wfSamp.release(); ctx->wfALB.release();
     ctx->tex_uv.release(); ctx->tex_table.release();
     for (DevBuf &b : ctx->tex_img) b.release();
-    ctx->wfQR.release(); ctx->accum.release(); ctx->dbgbuf.release(); ctx->batch_dev.release();
+    ctx->wfQR.release(); ctx->accum.release(); ctx->dbgbuf.release(); ctx->batch_dev.release(); ctx->anim_dev.release();
     ctx->pathSamp.release(); ctx->pathT.release(); ctx->tidx_up.release();
     for (DevBuf *b : {&ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp, &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev}) b->release();
     for (hipEvent_t &e : ctx->ev_trav) if (e) (void)hipEventDestroy(e);
@@ -164,17 +164,13 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     int pos = 0;
     for (int i = 0; i < n_spheres; ++i) {
         while (pos < n_objects && taken[pos]) ++pos;
-        const rt_sphere &s = spheres[i];
-        sc.sph[i] = {s.center[0], s.center[1], s.center[2], s.radius, s.radius * s.radius, pos};   // R * R: one binary32 product (-ffp-contract=off), as cpu:513
-        sc.obj_a[pos] = make_float4(s.center[0], s.center[1], s.center[2], __builtin_bit_cast(float, (int)(s.mirror ? 1 : 0)));
-        sc.obj_b[pos] = make_float4(s.albedo[0], s.albedo[1], s.albedo[2], 0.f);
-        sc.obj_n[pos] = make_float2(s.in_refraction_index, s.out_refraction_index);
+        put_sphere(sc, i, pos, spheres[i]);
         ++pos;
     }
     sc.n_spheres = n_spheres;
     sc.n_objects = n_objects;
     sc.mesh_slot = n_meshes > 0 ? sc.mesh[0].obj : -1;
-    sc.Lx = light->position[0]; sc.Ly = light->position[1]; sc.Lz = light->position[2]; sc.intensity = light->intensity;
+    put_light(sc, *light);
     sc.camx = camera->position[0]; sc.camy = camera->position[1]; sc.camz = camera->position[2]; sc.fov = camera->fov;
 
     PhaseClock pc;
@@ -199,6 +195,11 @@ int rt_render_device(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, void 
 }
 
 int rt_render_device_batch(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const rt_frame_desc *frames, int n_frames, void *stream) {
+    return rt_render_device_batch_scenes(ctx, p, rows, frames, nullptr, 0, n_frames, stream);
+}
+
+int rt_render_device_batch_scenes(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const rt_frame_desc *frames, const rt_frame_scene *scenes, int n_spheres,
+                                  int n_frames, void *stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     const hipStream_t q_ = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
     if (!q_) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
@@ -206,6 +207,12 @@ int rt_render_device_batch(rt_ctx *ctx, const rt_params *p, const rt_rows *rows,
     if (n_frames < 1 || n_frames > RT_MAX_BATCH) return fail(ctx, RT_ERR_INVALID, "n_frames %d outside [1,%d]", n_frames, RT_MAX_BATCH);
     if (p->num_rays != 1) return fail(ctx, RT_ERR_UNSUPPORTED, "a batch renders one sample per pixel and frame (num_rays = %d)", p->num_rays);
     if (p->width <= 0 || p->height <= 0) return fail(ctx, RT_ERR_INVALID, "width/height must be positive");
+    if (scenes && ctx->have_scene && n_spheres != ctx->scene.n_spheres)
+        return fail(ctx, RT_ERR_INVALID, "n_spheres %d is not the uploaded scene's %d", n_spheres, ctx->scene.n_spheres);
+    // the frames' own lights and sphere poses as the store kernel takes them (rt_frame_scene and rtk::AnimSrc are the same 16 + 16 * RT_MAX_SPHERES bytes)
+    static_assert(sizeof(rt_frame_scene) == sizeof(rtk::AnimSrc) && RT_MAX_SPHERES == rtk::kMaxSpheres, "rt_frame_scene is copied into rtk::AnimSrc");
+    std::vector<rtk::AnimSrc> anim(scenes ? n_frames : 0);
+    if (scenes) memcpy(anim.data(), scenes, anim.size() * sizeof(rtk::AnimSrc));
     rtk::Batch bt{};
     bt.n = n_frames;
     const uint8_t *lo = nullptr, *hi = nullptr;
@@ -225,7 +232,7 @@ int rt_render_device_batch(rt_ctx *ctx, const rt_params *p, const rt_rows *rows,
     }
     // one chunk: the batch exists for SMALL shares (a share too big for one chunk fills the chip by itself: render its frames one by one)
     const BetweenGuard between = begin_render_call(ctx->pipe, lo, hi);   // (the frames' buffers and whatever lies between them: conservative for the pipelining rule)
-    return launch_render_chunk(ctx, p, rows, frames[0].out_rgba_dev, q_, nullptr, nullptr, true, true, &bt);
+    return launch_render_chunk(ctx, p, rows, frames[0].out_rgba_dev, q_, nullptr, nullptr, true, true, &bt, scenes ? anim.data() : nullptr);
 }
 
 int rt_render(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, float *out_rgba_host) {
@@ -375,6 +382,7 @@ int rt_count_work(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, r
 
 #include "rt_host_mesh.hip.h"     // rt_mesh_set_normals / transform / rebuild (reference tree, LBVH)
 #include "rt_host_tex.hip.h"      // rt_mesh_set_texture[_of]
+#include "rt_host_edit.hip.h"     // rt_scene_get / set / move: the light and the spheres of the scene in use
 
 int rt_camera_basis(const rt_camera_pose *pose, float bx[3], float by[3], float bz[3]) {
     if (!pose || !bx || !by || !bz) return fail(nullptr, RT_ERR_INVALID, "bad arguments");

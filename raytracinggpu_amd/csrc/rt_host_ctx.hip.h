@@ -162,6 +162,7 @@ struct rt_ctx {
     DevBuf pathSamp, pathT;                                         // wf_path with num_rays > 1: per-sample colours, running sum
     DevBuf dbgbuf;                                                  // -DRT_DEBUG builds: per-wave traversal records
     DevBuf batch_dev;                                               // rt_render_device_batch: the frames' descriptors, one copy per sub-frame
+    DevBuf anim_dev;                                                // rt_render_device_batch_scenes: the frames' lights and sphere poses (rtk::AnimFrame), one copy per sub-frame
     DevBuf accum;                                                   // progressive mode: sum of the frames so far (float4 per pixel)
     int prog_frames = 0, prog_w = 0, prog_h = 0;
     uint64_t qf_sig = 0;                                            // layout the queue flags were last zeroed for

@@ -1,0 +1,94 @@
+// rt_host_edit.hip.h -- the light and the spheres of the scene in use, edited in place: MoveLightSource / MoveObject of realtime_render.cu:1072-1098 and the
+// general set / get they are instances of.  The light and the spheres live in rtk::Scene alone -- a kernel argument, copied at every launch (make_frame) -- so an edit is a
+// host-side store into ctx->scene: no device memory is touched, nothing derived from a mesh is looked at, and a frame already enqueued keeps the values its launches captured.
+// Included inside rt_capi.hip's extern "C" block.
+
+static int edit_scene_check(rt_ctx *ctx) {
+    if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
+    return RT_OK;
+}
+// index into Scene::sph of the sphere at position object_slot of Scene::objects; -1: outside the scene, or a mesh's position
+static int sphere_at(const rtk::Scene &sc, int object_slot) {
+    for (int k = 0; k < sc.n_spheres; ++k) if (sc.sph[k].obj == object_slot) return k;
+    return -1;
+}
+
+int rt_light_orbit(const rt_light *in, float angular_speed, float dt, rt_light *out) {
+    if (!in || !out) return fail(nullptr, RT_ERR_INVALID, "light in / out is NULL");
+    // realtime:1078-1088 with C = (0, 0, 0), every operation in binary32 in the order written there (powf(x, 2) = x * x)
+    const float Cx = 0.f, Cz = 0.f;
+    const float dx = Cx - in->position[0], dz = Cz - in->position[2];
+    const float radius = sqrtf(dx * dx + dz * dz);
+    const float current = atan2f(in->position[2] - Cz, in->position[0] - Cx);
+    const float angle = current + angular_speed * dt;
+    rt_light l = *in;
+    l.position[0] = Cx + radius * cosf(angle);
+    l.position[2] = Cz + radius * sinf(angle);
+    *out = l;
+    return RT_OK;
+}
+
+int rt_scene_get_light(const rt_ctx *ctx, rt_light *out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);                               // (the error text is the only thing written)
+    if (!out) return fail(c, RT_ERR_INVALID, "out is NULL");
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    const rtk::Scene &sc = ctx->scene;
+    *out = rt_light{{sc.Lx, sc.Ly, sc.Lz}, sc.intensity};
+    return RT_OK;
+}
+
+int rt_scene_set_light(rt_ctx *ctx, const rt_light *light) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!light) return fail(ctx, RT_ERR_INVALID, "light is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    put_light(ctx->scene, *light);
+    return RT_OK;
+}
+
+int rt_scene_get_sphere(const rt_ctx *ctx, int object_slot, rt_sphere *out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!out) return fail(c, RT_ERR_INVALID, "out is NULL");
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    const rtk::Scene &sc = ctx->scene;
+    const int k = sphere_at(sc, object_slot);
+    if (k < 0) return fail(c, RT_ERR_INVALID, "object_slot %d is not a sphere of the scene (%d objects)", object_slot, sc.n_objects);
+    const rtk::Sphere &s = sc.sph[k];
+    const float4 a = sc.obj_a[object_slot], b = sc.obj_b[object_slot];
+    const float2 n = sc.obj_n[object_slot];
+    *out = rt_sphere{{s.cx, s.cy, s.cz}, s.R, {b.x, b.y, b.z}, __builtin_bit_cast(int, a.w), n.x, n.y};
+    return RT_OK;
+}
+
+int rt_scene_set_sphere(rt_ctx *ctx, int object_slot, const rt_sphere *sphere) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!sphere) return fail(ctx, RT_ERR_INVALID, "sphere is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    const int k = sphere_at(ctx->scene, object_slot);
+    if (k < 0) return fail(ctx, RT_ERR_INVALID, "object_slot %d is not a sphere of the scene (%d objects)", object_slot, ctx->scene.n_objects);
+    put_sphere(ctx->scene, k, object_slot, *sphere);
+    return RT_OK;
+}
+
+int rt_scene_move_light(rt_ctx *ctx, float angular_speed, float dt) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_light l;
+    int rc = rt_scene_get_light(ctx, &l);
+    if (rc == RT_OK) rc = rt_light_orbit(&l, angular_speed, dt, &l);
+    if (rc == RT_OK) rc = rt_scene_set_light(ctx, &l);
+    return rc;
+}
+
+int rt_scene_move_sphere(rt_ctx *ctx, int object_slot, const float v[3], float dt) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!v) return fail(ctx, RT_ERR_INVALID, "v is NULL");
+    rt_sphere s;
+    int rc = rt_scene_get_sphere(ctx, object_slot, &s);
+    if (rc != RT_OK) return rc;
+    for (int a = 0; a < 3; ++a) {                                        // sp->C = sp->C + v * dt (realtime:1096): the product, then the sum, each rounded to binary32
+        const float step = v[a] * dt;
+        s.center[a] = s.center[a] + step;
+    }
+    return rt_scene_set_sphere(ctx, object_slot, &s);
+}

@@ -184,10 +184,12 @@ int resolve_variant(rt_ctx *ctx, int variant, const rt_camera_pose *pose, bool b
 }
 
 // One chunk of a render call, as every pipeline's launch function gets it.  work_dev: rt_count_work (the counting instantiations run); batch: rt_render_device_batch; rec_begin: this
-// chunk opens the call's kernel-time bracket (ev_k0); nseg = max(segs, 1); scn: per-launch copy (a pose moves the camera)
+// chunk opens the call's kernel-time bracket (ev_k0); nseg = max(segs, 1); scn: per-launch copy (a pose moves the camera); anim: rt_render_device_batch_scenes -- light and sphere
+// poses of each of the batch's frames
 struct Chunk {
     const rt_params *p; const rt_rows *rows; hipStream_t stream; unsigned long long *work_dev; const rtk::Batch *batch; bool rec_begin; int segs, nseg;
     rtk::Frame fr; rtk::Scene scn;
+    const rtk::AnimSrc *anim = nullptr;
 };
 void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Chunk &c) {
     const rt_params *p = c.p;
@@ -420,7 +422,7 @@ void launch_trav(const TravPlan &t, int64_t tblocks, hipStream_t q, const rtk::S
 
 // One sub-frame of the wavefront pipeline: its rows, its path state, its traversal / wf_advance grids, where its first path / queue slot / pixel slot lies in the buffers
 // all sub-frames share, its frames of a batch
-struct WfPart { rtk::Frame fr; rtk::WfState st; int64_t tblocks; unsigned pblocks; size_t base, qbase, pxbase; int batch0, batch_n; };
+struct WfPart { rtk::Frame fr; rtk::WfState st; int64_t tblocks; unsigned pblocks; size_t base, qbase, pxbase; int batch0, batch_n; rtk::AnimFrame *anim; };
 struct WfCut {
     std::vector<WfPart> pv;
     int tiles_x, chunk;             // chunk: samples (frames of a batch) a launch chain traces at once
@@ -506,6 +508,8 @@ int size_wavefront(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool &qr_grown) 
     // chain is ordered behind the previous chain of its stream, so the copy is never rewritten under a running kernel, and nothing has to wait on the caller's stream -- a batch
     // takes the relaxed start of rt_ctx_set_pipelining like a frame does
     if (c.batch && (rc = ensure(ctx, ctx->batch_dev, rt_ctx::kMaxParts * rtk::kMaxBatch * sizeof(rtk::BatchFrame))) != RT_OK) return rc;
+    // ... and so do the per-frame lights and sphere poses of an animated batch (68 KB: every sub-frame's block holds kMaxBatch frames, a chain writes its first batch_n)
+    if (c.anim && (rc = ensure(ctx, ctx->anim_dev, rt_ctx::kMaxParts * rtk::kMaxBatch * sizeof(rtk::AnimFrame))) != RT_OK) return rc;
     return RT_OK;
 }
 
@@ -612,8 +616,17 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
         for (int k = 0; k < pt.batch_n; ++k) bj.f[k] = c.batch->f[pt.batch0 + k];
         hipLaunchKernelGGL(rtk::batch_store_kernel, dim3(1), dim3(64), 0, q, bj, const_cast<rtk::BatchFrame *>(pt.st.batch));
     }
+    const bool anim = c.batch && c.anim;                          // their lights and spheres too: kAnimStore frames' records fit one launch's arguments
+    for (int k0 = 0; anim && k0 < pt.batch_n; k0 += rtk::kAnimStore) {
+        rtk::AnimStore as{};
+        as.n = std::min(rtk::kAnimStore, pt.batch_n - k0); as.n_spheres = c.scn.n_spheres;
+        for (int k = 0; k < c.scn.n_spheres; ++k) as.obj[k] = c.scn.sph[k].obj;
+        for (int k = 0; k < as.n; ++k) as.f[k] = c.anim[pt.batch0 + k0 + k];
+        hipLaunchKernelGGL(rtk::anim_store_kernel, dim3(1), dim3(rtk::kAnimStore * rtk::kMaxSpheres), 0, q, as, pt.anim + k0);
+    }
     const auto begin = counting ? rtk::wf_advance<true, true> : rtk::wf_advance<false, true>;
-    hipLaunchKernelGGL(begin, pg, pb, 0, q, c.scn, pt.fr, pt.st);
+    if (anim) hipLaunchKernelGGL(rtk::wf_advance_anim<true>, pg, pb, 0, q, c.scn, pt.fr, pt.st, static_cast<const rtk::AnimFrame *>(pt.anim));
+    else hipLaunchKernelGGL(begin, pg, pb, 0, q, c.scn, pt.fr, pt.st);
     const auto advance = counting ? rtk::wf_advance<true, false> : rtk::wf_advance<false, false>;
     const auto advance_tex = counting ? rtk::wf_advance_tex<true> : rtk::wf_advance_tex<false>;
     const bool timed = ctx->stats_on && j == 0 && s + w.chunk >= fr.spp;   // on request (rt_stats_enable): time part 0's launches of the last chain
@@ -632,7 +645,10 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
         if (tex) {
             rtk::TexScene ts = tex_scene(ctx);
             ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg;   // ALB[d * n_paths + i] inside the part's block, as LS
-            hipLaunchKernelGGL(advance_tex, pg, pb, 0, q, c.scn, pt.fr, pt.st, ts);
+            if (anim) hipLaunchKernelGGL(rtk::wf_advance_tex_anim, pg, pb, 0, q, c.scn, pt.fr, pt.st, ts, static_cast<const rtk::AnimFrame *>(pt.anim));
+            else hipLaunchKernelGGL(advance_tex, pg, pb, 0, q, c.scn, pt.fr, pt.st, ts);
+        } else if (anim) {
+            hipLaunchKernelGGL(rtk::wf_advance_anim<false>, pg, pb, 0, q, c.scn, pt.fr, pt.st, static_cast<const rtk::AnimFrame *>(pt.anim));
         } else {
             hipLaunchKernelGGL(advance, pg, pb, 0, q, c.scn, pt.fr, pt.st);
         }
@@ -669,6 +685,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
         st.SID = static_cast<unsigned char *>(ctx->wfSID.p) + pt.base * (size_t)c.nseg;
         st.batch = c.batch ? static_cast<rtk::BatchFrame *>(ctx->batch_dev.p) + j * rtk::kMaxBatch : nullptr;
         st.n_batch = c.batch ? pt.batch_n : 0;
+        w.pv[j].anim = c.anim ? static_cast<rtk::AnimFrame *>(ctx->anim_dev.p) + j * rtk::kMaxBatch : nullptr;
         st.anyhit = (kn.anyhit && (c.work_dev == nullptr || t.qw)) ? 1 : 0;   // a run that counts the REFERENCE's work (the float-pair counting instantiation) traces every shadow ray to the end
     }
     ctx->stats.lds_bytes = (int)t.lds; ctx->stats.block_threads = t.tb; ctx->stats.grid_blocks = (int)w.pv[0].tblocks; ctx->stats.parts = parts; ctx->stats.travq_mode = t.travq_mode;
@@ -696,7 +713,8 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
 // One chunk of rows (launch_render below cuts big frames into cache-sized chunks): checks, which renderer (resolve_variant), the frame, that renderer's launches.
 // rec_begin / rec_end: this chunk opens / closes the call's kernel-time bracket (ev_k0 / ev_k1).
 int launch_render_chunk(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, void *out_dev, hipStream_t stream,
-                        unsigned long long *work_dev, const rt_camera_pose *pose, bool rec_begin, bool rec_end, const rtk::Batch *batch = nullptr) {
+                        unsigned long long *work_dev, const rt_camera_pose *pose, bool rec_begin, bool rec_end, const rtk::Batch *batch = nullptr,
+                        const rtk::AnimSrc *anim = nullptr) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
     int segs = 0;
@@ -713,7 +731,7 @@ int launch_render_chunk(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, vo
     Variant v;
     if ((rc = resolve_variant(ctx, p->variant, pose, batch != nullptr, v)) != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    Chunk c{p, rows, stream, work_dev, batch, rec_begin, segs, segs > 0 ? segs : 1, {}, {}};
+    Chunk c{p, rows, stream, work_dev, batch, rec_begin, segs, segs > 0 ? segs : 1, {}, {}, batch ? anim : nullptr};
     make_frame(ctx, out_dev, pose, c);
     ctx->stats.pixels = (uint64_t)rows->n_rows * p->width;
     ctx->stats.travq_mode = -1;

@@ -132,6 +132,16 @@ int requantize(rt_ctx *ctx, hipStream_t q) {
 }
 
 // the triangle ranges of the scene's mesh table when at most ONE mesh has triangles (object position real_obj, -1 = none): a mesh without triangles is an empty range at its place in the order
+// Everything the kernels read of sphere k (array order) at position `pos` of Scene::objects, and of the light: rt_scene_upload* and the in-place edits
+// (rt_scene_set_sphere / rt_scene_set_light) derive it here, so an edited scene is the uploaded one bit for bit
+void put_sphere(rtk::Scene &sc, int k, int pos, const rt_sphere &s) {
+    sc.sph[k] = {s.center[0], s.center[1], s.center[2], s.radius, s.radius * s.radius, pos};   // R * R: one binary32 product (-ffp-contract=off), as cpu:513
+    sc.obj_a[pos] = make_float4(s.center[0], s.center[1], s.center[2], __builtin_bit_cast(float, (int)(s.mirror ? 1 : 0)));
+    sc.obj_b[pos] = make_float4(s.albedo[0], s.albedo[1], s.albedo[2], 0.f);
+    sc.obj_n[pos] = make_float2(s.in_refraction_index, s.out_refraction_index);
+}
+void put_light(rtk::Scene &sc, const rt_light &l) { sc.Lx = l.position[0]; sc.Ly = l.position[1]; sc.Lz = l.position[2]; sc.intensity = l.intensity; }
+
 void mesh_table_single(rtk::Scene &sc, int real_obj) {
     for (int k = 0; k < sc.n_meshes; ++k) sc.mesh[k].tri_begin = sc.mesh[k].obj <= real_obj ? 0 : sc.n_tris;
 }

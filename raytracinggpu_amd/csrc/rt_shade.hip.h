@@ -124,12 +124,13 @@ __device__ __forceinline__ f3 shadow_dir(f3 L, f3 Pa) { float nl; return shadow_
 __device__ __forceinline__ bool light_hidden(f3 Pa, f3 Pp, f3 L) { return norm2(Pp - Pa) <= norm2(L - Pa); }
 __device__ __forceinline__ bool light_hidden(f3 Pa, f3 u, float t, f3 L) { return light_hidden(Pa, Pa + t * u, L); }
 // cpu:620-623: the scalar l of a diffuse hit at P with normal N under a visible light (the quotient and the product in binary64, as the reference's promotions make them)
-__device__ __forceinline__ float direct_term(const Scene &sc, f3 L, f3 P, f3 N) {
+__device__ __forceinline__ float direct_term(float intensity, f3 L, f3 P, f3 N) {
     const f3 wl = normalize(L - P);
     const float dn = dot(N, wl);
     const float mx = (dn < 0.f) ? 0.f : dn;                           // std::max(dn, 0.f)
-    return (float)((double)sc.intensity / (4 * 3.14159265358979323846 * (double)norm2(L - P)) * (double)mx);   // cpu:623
+    return (float)((double)intensity / (4 * 3.14159265358979323846 * (double)norm2(L - P)) * (double)mx);   // cpu:623
 }
+__device__ __forceinline__ float direct_term(const Scene &sc, f3 L, f3 P, f3 N) { return direct_term(sc.intensity, L, P, N); }
 // cpu:627-641: the cosine-weighted direction about N of segment d's bounce, from the sample key's dims 0, 1 at depth d
 __device__ __forceinline__ f3 cosine_bounce(f3 N, uint32_t hs, int d) {
     const float r1 = uniform01(hs, (uint32_t)d, 0);                   // cpu:628-629

@@ -91,6 +91,38 @@ __global__ void batch_store_kernel(const Batch bt, BatchFrame *__restrict__ dst)
     if (k < kMaxBatch) dst[k] = bt.f[k < bt.n ? k : 0];               // (constant trip structure: one lane per descriptor)
 }
 
+// An ANIMATED batch (rt_render_device_batch_scenes): besides its camera every frame has its own light and its own sphere poses -- MoveLightSource / MoveObject
+// (realtime_render.cu:1072-1098) between the frames of a sequence.  Everything else of the scene (materials, object positions, meshes) is the uploaded Scene of the kernel
+// arguments.  The table lives next to the BatchFrame descriptors under the same protocol (one copy per sub-frame, written at the head of that sub-frame's own chain) and is read
+// by wf_advance's animated instantiations alone, through the frame's wave-uniform address: the light and sph[] by scalar loads, ctr[] with the hit object's id.
+struct AnimFrame {
+    float Lx, Ly, Lz, intensity;             // Scene::L, Scene::intensity of this frame
+    float4 sph[kMaxSpheres];                 // (centre, R2 = R * R as one binary32 product) of sphere k, in the order of Scene::sph
+    float4 ctr[kMaxSpheres];                 // the same centres by OBJECT id (Scene::obj_a's xyz; a mesh's entry is 0)
+};
+// The caller's records of kAnimStore frames per launch: 16 frames of 16 + 16 * 16 bytes do not fit the 4 KB of a kernel's arguments
+constexpr int kAnimStore = 8;
+struct AnimPose { float cx, cy, cz, R; };
+struct AnimSrc { float Lx, Ly, Lz, intensity; AnimPose s[kMaxSpheres]; };
+struct AnimStore { int n, n_spheres, obj[kMaxSpheres]; AnimSrc f[kAnimStore]; };
+static_assert(sizeof(AnimStore) + sizeof(void *) <= 4096, "anim_store_kernel's arguments must fit 4 KB");
+// one lane per (frame, k): sphere k's record and the centre of OBJECT k, of frames [0, as.n) of this launch
+__global__ __launch_bounds__(kAnimStore * kMaxSpheres) void anim_store_kernel(const AnimStore as, AnimFrame *__restrict__ dst) {
+    const int f = threadIdx.x / kMaxSpheres, k = threadIdx.x % kMaxSpheres;
+    if (f >= as.n) return;
+    const AnimSrc &src = as.f[f];
+    AnimFrame &d = dst[f];
+    if (k == 0) { d.Lx = src.Lx; d.Ly = src.Ly; d.Lz = src.Lz; d.intensity = src.intensity; }
+    float4 rec = make_float4(0.f, 0.f, 0.f, 0.f), c = rec;
+    for (int j = 0; j < as.n_spheres; ++j) {
+        const AnimPose s = src.s[j];
+        if (j == k) rec = make_float4(s.cx, s.cy, s.cz, s.R * s.R);   // R * R: one binary32 product, as rt_scene_upload forms it (cpu:513)
+        if (as.obj[j] == k) c = make_float4(s.cx, s.cy, s.cz, 0.f);
+    }
+    d.sph[k] = rec;
+    d.ctr[k] = c;
+}
+
 // Path state of the wavefront pipeline, in HBM.  A ray lives in ONE place: its 32-byte record in the traversal queue (slot order;
 // the four rays of a group are one 128-byte line), which the uniform kernel writes when it emits the ray, the traversal kernel
 // reads, and the next uniform launch reads back to compute the hit point.  The record's two spare words hold the PATH's state as
@@ -153,15 +185,25 @@ __device__ __forceinline__ SphereNear spheres_near1(const Scene &sc, f3 O, f3 u)
     }
     return h;
 }
-__device__ __forceinline__ void spheres_near2(const Scene &sc, f3 O, f3 uy, bool on_y, f3 ux, bool on_x, SphereNear &hy, SphereNear &hx) {
+// (sphere_at(k): sphere k of the scene -- Scene::sph, or the pose a frame of an animated batch gives it)
+template <class SphereAt>
+__device__ __forceinline__ void spheres_near2(int n_spheres, SphereAt sphere_at, f3 O, f3 uy, bool on_y, f3 ux, bool on_x, SphereNear &hy, SphereNear &hx) {
     hy.t = 1e9f; hy.obj = -1;
     hx = hy;
-    for (int k = 0; k < sc.n_spheres; ++k) {
-        const SphereOrigin so = sphere_origin(sc.sph[k], O);
+    for (int k = 0; k < n_spheres; ++k) {
+        const auto &s = sphere_at(k);
+        const SphereOrigin so = sphere_origin(s, O);
         float t;
-        if (on_y && sphere_dir(sc.sph[k], so, O, uy, t)) { if (t < hy.t) { hy.t = t; hy.obj = sc.sph[k].obj; } }
-        if (on_x && sphere_dir(sc.sph[k], so, O, ux, t)) { if (t < hx.t) { hx.t = t; hx.obj = sc.sph[k].obj; } }
+        if (on_y && sphere_dir(s, so, O, uy, t)) { if (t < hy.t) { hy.t = t; hy.obj = s.obj; } }
+        if (on_x && sphere_dir(s, so, O, ux, t)) { if (t < hx.t) { hx.t = t; hx.obj = s.obj; } }
     }
+}
+__device__ __forceinline__ void spheres_near2(const Scene &sc, f3 O, f3 uy, bool on_y, f3 ux, bool on_x, SphereNear &hy, SphereNear &hx) {
+    spheres_near2(sc.n_spheres, [&](int k) -> const Sphere & { return sc.sph[k]; }, O, uy, on_y, ux, on_x, hy, hx);
+}
+// ... with the spheres where this frame of an animated batch has them (AnimFrame::sph: centre and R2; which object a sphere is does not change)
+__device__ __forceinline__ void spheres_near2(const Scene &sc, const float4 *__restrict__ pose, f3 O, f3 uy, bool on_y, f3 ux, bool on_x, SphereNear &hy, SphereNear &hx) {
+    spheres_near2(sc.n_spheres, [&](int k) { const float4 c = pose[k]; return Sphere{c.x, c.y, c.z, 0.f, c.w, sc.sph[k].obj}; }, O, uy, on_y, ux, on_x, hy, hx);
 }
 // inverse of wf_slot_to_path: the traversal slot of ray r
 __device__ __forceinline__ int wf_ray_to_slot(const WfState &st, int r) {
@@ -577,6 +619,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 // ---- wf_advance: close the queries, shade, emit the next rays -----------------------------------------------
 // FIRST: the launch that opens the chain's samples -- camera rays instead of closing queries.
 // TEX (wf_advance_tex, never FIRST): textured meshes -- the albedo of a textured diffuse hit goes to ts.ALB and the fold reads it from there.
+// ANIM (wf_advance_anim, wf_advance_tex_anim; batches only): the frame's light and sphere poses come from anim[frame] instead of the Scene -- the same device functions on
+// other operands; the other instantiations never look at `anim`.
 // The samples of a pixel are independent paths (the reference's loop cpu:701-712 carries nothing but the sum): a chain traces
 // several of them at once as items, each writes its colour, and path_reduce adds the colours in sample order.
 // code-object markers (labels, not instructions): tools/static_counts.py cuts the production instantiation into regions at them -- what a path pays for, region by region
@@ -585,15 +629,15 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #else
 #define ADV_MARK(name) asm volatile("rt_mark_adv_" name "_%=:" ::)
 #endif
-template <bool STATS, bool FIRST, bool TEX = false>
-__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts) {
+template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false>
+__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr) {
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
     const float4 y1 = FIRST ? kDead : st.QR[2 * (size_t)qy + 1];      // (u.y, u.z, flag word, t of the nearest sphere) of the continuation ray in flight
     const int F = __float_as_int(y1.z);
     if (!FIRST && !(F & PF_ALIVE)) return;                            // finished (or padding): its queue flags are already 0
-    const f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
+    f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
     int refr_code = FIRST ? 0 : (F >> PQ_REFR_SHIFT) & 63;            // Ray::refraction_index = 1 (cpu:100)
     int d = 0, nrays = 0;
     bool emitY = false, emitX = false, finished = false;
@@ -609,6 +653,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     float4 *fr_out = fr.out;
     int samp = st.samp0 + s_rel;
     bool in_batch = true;
+    int af_k = 0;                                                     // (ANIM) this wave's frame in the table
     if (st.n_batch > 0) {
         const int f = __builtin_amdgcn_readfirstlane(s_rel);
         in_batch = f < st.n_batch;
@@ -616,7 +661,11 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         camx = b.camx; camy = b.camy; camz = b.camz;
         fr_z = b.z; fr_seed = b.seed; fr_out = b.out;
         samp = 0;
+        if (ANIM) af_k = f & (kMaxBatch - 1);
     }
+    const AnimFrame *const af = ANIM ? anim + af_k : nullptr;         // wave-uniform
+    float intensity = sc.intensity;
+    if (ANIM) { L = mk(af->Lx, af->Ly, af->Lz); intensity = af->intensity; }
     wf_decode(st, fr, i - s_rel * st.n_px, px, lrow, valid);
     valid = valid && samp < fr.spp && in_batch;                       // the last chain of a frame may be short of samples
     const int row = image_row(fr, lrow);
@@ -673,7 +722,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 const f3 P = O + t_min * u;                           // cpu:560
                 Bary bary{0.f, 0.f, 0.f};                             // (TEX) the smooth normal's barycentrics, shared with the texture lookup
                 bool have_bary = false;
-                const f3 N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
+                f3 N;
+                if (ANIM && tri_win < 0) { const float4 c = af->ctr[win]; N = normalize(P - mk(c.x, c.y, c.z)); }   // sphere_normal (cpu:524-525) about this frame's centre
+                else N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
                 const Material m = material_of(sc, win);
                 ADV_MARK("closey_end");
                 bool cont = false;                                    // a continuation ray of segment d+1 was built in (O,u)
@@ -694,7 +745,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     x_bound = wf_anyhit_bound(Pa, nl);
                     nrays += 1;
                     // the segment's direct term if the light turns out to be visible; kept until the shadow ray is back
-                    const float lvis = direct_term(sc, L, P, N);
+                    const float lvis = ANIM ? direct_term(intensity, L, P, N) : direct_term(sc, L, P, N);
                     st.LS[(size_t)d * st.n_paths + i] = lvis;
                     // A surface that faces away from the light (mx = 0) has the direct term +0 whether the light is visible or not: shaded, cpu:616 stores the literal 0; lit,
                     // cpu:623 computes l = +0 -- the same 32 bits (a NaN or a -0 from a degenerate light is not +0 and keeps its ray).  The reference still calls intersect_all
@@ -770,7 +821,8 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     int flags = PF_ALIVE | (d << PF_DEPTH_SHIFT) | (nrays << PF_RAYS_SHIFT) | (refr_code << PQ_REFR_SHIFT) | (int)((unsigned)st.nonce << PQ_NONCE_SHIFT);
     SphereNear h, hx;
     ADV_MARK("spheres_begin");
-    spheres_near2(sc, emitX ? Ox : Oy, uy, emitY, ux, emitX && !x_moot, h, hx);   // a shadow ray and a bounce ray leave the same point (Oy == Ox == P_adjusted)
+    if (ANIM) spheres_near2(sc, af->sph, emitX ? Ox : Oy, uy, emitY, ux, emitX && !x_moot, h, hx);
+    else spheres_near2(sc, emitX ? Ox : Oy, uy, emitY, ux, emitX && !x_moot, h, hx);   // a shadow ray and a bounce ray leave the same point (Oy == Ox == P_adjusted)
     ADV_MARK("spheres_end");
     float t_sph = 0.f;
     if (emitX) {
@@ -807,6 +859,18 @@ __global__ __launch_bounds__(256, 8) void wf_advance_tex(const Scene sc, const F
     Work wk;
     if (i < st.n_paths) wf_advance_path<STATS, false, true>(sc, fr, st, i, wk, ts);
     wf_flush_work<STATS>(fr, wk);
+}
+// the two for a frame of an animated batch (a batch never counts work: no STATS form)
+template <bool FIRST>
+__global__ __launch_bounds__(256, 8) void wf_advance_anim(const Scene sc, const Frame fr, const WfState st, const AnimFrame *__restrict__ anim) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, FIRST, false, true>(sc, fr, st, i, wk, TexScene{}, anim);
+}
+__global__ __launch_bounds__(256, 8) void wf_advance_tex_anim(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const AnimFrame *__restrict__ anim) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, false, true, true>(sc, fr, st, i, wk, ts, anim);
 }
 
 }  // namespace rtk

@@ -204,10 +204,13 @@ def main():
         raise SystemExit("static_counts: wf_travq<false, 64, false, false, true, true> (the 4-wide BOX step) not found in the assembly")
     res["wf_travq_qw"] = travq_qw_counts(tw)
     for name, mangled in (("wf_advance", "_ZN3rtk10wf_advanceILb0ELb0EEEvNS_5SceneENS_5FrameENS_7WfStateE"),
-                          ("wf_advance_first", "_ZN3rtk10wf_advanceILb0ELb1EEEvNS_5SceneENS_5FrameENS_7WfStateE")):
+                          ("wf_advance_first", "_ZN3rtk10wf_advanceILb0ELb1EEEvNS_5SceneENS_5FrameENS_7WfStateE"),
+                          # the same regions of the instantiation an animated batch runs (rt_render_device_batch_scenes): what the per-frame light and spheres cost
+                          ("wf_advance_anim", "_ZN3rtk15wf_advance_animILb0EEEvNS_5SceneENS_5FrameENS_7WfStateEPKNS_9AnimFrameE"),
+                          ("wf_advance_anim_first", "_ZN3rtk15wf_advance_animILb1EEEvNS_5SceneENS_5FrameENS_7WfStateEPKNS_9AnimFrameE")):
         t = kernel_text(asm, mangled)
         if t:
-            res[name] = advance_counts(t) if name == "wf_advance" else {"whole_kernel": count(t)}
+            res[name] = advance_counts(t) if name in ("wf_advance", "wf_advance_anim") else {"whole_kernel": count(t)}
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
         json.dump(res, f, indent=1)
