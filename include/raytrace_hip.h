@@ -499,6 +499,42 @@ int rt_progressive_reset(rt_ctx *ctx);
 int rt_progressive_frame(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, float *display_rgba_host, uint8_t *rgb8_host);
 int rt_progressive_frames(const rt_ctx *ctx, int *frames);
 
+/* --- first-hit feature buffers (G-buffer) and an edge-avoiding denoiser (ABI 6, additive).  A frame of one sample per pixel is noise; the remedy that needs
+ *     no further frames is a filter guided by what the camera ray of each pixel hit first.
+ *     rt_render_aov*: for every pixel of `rows` the pixel-centre camera ray -- the fixed camera of cpu:694-699 (pose == NULL) or the posed camera of
+ *     rt_render_pose; p->sigma, num_rays, num_bounce, seed and variant are ignored -- is intersected with the scene exactly as Scene::intersect_all does
+ *     (cpu:545-564: all spheres and all meshes in object order, strict '<', p->tri_tmin at the leaves; the meshes through the production traversal).  Output:
+ *     THREE dense planes of n_rows * width float4, consecutive in one buffer (plane i starts at byte i * n_rows * width * 16):
+ *       plane 0  .xyz = the unit normal Scene::getColor shades the hit with (sphere, flat triangle, or interpolated where normals are set),
+ *                .w   = the object id (position in Scene::objects) as a float, -1 on a miss;
+ *       plane 1  .xyz = the hit point P = O + t u (cpu:560), .w = 1 on a hit, 0 on a miss;
+ *       plane 2  .xyz = the albedo the shading step uses: the object's, or mesh albedo (.) texture sample on a textured mesh; .w = 0.
+ *     A miss writes zeros in every .xyz.  The FIRST hit is recorded whatever its material: a mirror or glass object reports itself, not what it reflects or
+ *     refracts.  The call reads the scene as a render call does, keeps its own queue (it may be issued between two frames in flight), and is asynchronous on
+ *     `stream` (NULL = the context's own).  rt_render_aov copies the planes to the host; rows == NULL = the whole frame.
+ *     rt_denoise*: n_passes passes of the a-trous filter over a width x height float4 colour frame (.w = the ray count, as rt_render* writes it) guided by the
+ *     three planes of the same frame.  The arithmetic is the contract -- binary32, one rounding per operation, no contraction.  Pass k = 0 .. n_passes - 1,
+ *     step s = 2^k, input frame C (the colour, then the previous pass's output); pixel p = (x, y) with id_p, N_p, P_p, A_p from the planes:
+ *       id_p == -1: out = C_p.  Otherwise, for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = (x + dx s, y + dy s), skipped if outside the image or id_q != id_p:
+ *         h  = H[|dy|] * H[|dx|], H = {3/8, 1/4, 1/16};
+ *         dn = (N_p.x - N_q.x)^2 + (N_p.y - N_q.y)^2 + (N_p.z - N_q.z)^2, summed left to right; da (albedos) and dc (C_p.rgb, C_q.rgb) in the same form;
+ *         e  = N_p.x (P_q.x - P_p.x) + N_p.y (P_q.y - P_p.y) + N_p.z (P_q.z - P_p.z), dp = e e: q's squared distance from p's tangent plane;
+ *         wn = max(0, 1 - dn k_normal), wp, wa likewise with k_position, k_albedo; wc with k_color 4^k (the colour tolerance halves per pass);
+ *         a k_* of exactly 0 makes its term exactly 1;
+ *         w  = h wn wp wa wc, multiplied left to right; the tap counts only if w > 0 (a NaN guide does not spread): S += w C_q.rgb, W += w;
+ *       out.rgb = S / W (correctly rounded; the centre tap always contributes 9/64), out.w = C_p.w.
+ *     RT_ERR_INVALID, output untouched: n_passes outside [1, RT_DENOISE_MAX_PASSES], an output that overlaps the colour frame or the planes, a NULL pointer,
+ *     width or height <= 0.  Whole frames only: a row share of a tiled multi-GPU frame lacks the 2 (2^n_passes - 1)-row halo -- denoise the gathered frame. --- */
+#define RT_DENOISE_MAX_PASSES 8
+typedef struct rt_denoise_params {
+    int32_t n_passes;              /* 1 .. RT_DENOISE_MAX_PASSES                                    */
+    float   k_normal, k_position, k_albedo, k_color;
+} rt_denoise_params;
+int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_aov_dev, void *stream);
+int rt_render_aov(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, float *out_aov_host);
+int rt_denoise_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, int width, int height, const rt_denoise_params *dp, void *out_rgba_dev, void *stream);
+int rt_denoise(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, int width, int height, const rt_denoise_params *dp, float *out_rgba_host);
+
 /* --- one host process, several devices (SURVEY 8b rt_render_multi; the reference uses the implicit device 0,
  *     optimized.cu:828-856).  The frame is cut into RT_MULTI_TILE_ROWS-row tiles, tile k -> device k mod n
  *     (interleaved); the scene is replicated; every device renders its tiles; each peer pushes them over

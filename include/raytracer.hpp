@@ -595,6 +595,21 @@ public:
         return image;
     }
     void progressive_reset() { check(rt_progressive_reset(ctx_), "rt_progressive_reset"); }   // buffer_reset
+    // The G-buffer of the frame's pixel-centre camera rays (rt_render_aov): three planes of H * W float4 -- (normal, object id or -1), (hit point, 1 / 0),
+    // (albedo, 0) -- of the FIRST hit, whatever its material.  pose: the posed camera of progressive_frame, nullptr = the uploaded one.
+    std::vector<float> render_aov(const RenderSettings &s, const rt_camera_pose *pose = nullptr) {
+        const rt_params p = params(s);
+        std::vector<float> planes((size_t)3 * s.W * s.H * 4);
+        check(rt_render_aov(ctx_, &p, pose, nullptr, planes.data()), "rt_render_aov");
+        return planes;
+    }
+    // ... and the edge-avoiding a-trous filter they guide (rt_denoise): color = W * H float4 as render_float gives it, aov = render_aov of the same frame
+    std::vector<float> denoise(const std::vector<float> &color, const std::vector<float> &aov, int W, int H, const rt_denoise_params &dp) {
+        if (color.size() != (size_t)W * H * 4 || aov.size() != 3 * color.size()) throw Error(RT_ERR_INVALID, "denoise: color is W * H float4, aov three such planes");
+        std::vector<float> out(color.size());
+        check(rt_denoise(ctx_, color.data(), aov.data(), W, H, &dp, out.data()), "rt_denoise");
+        return out;
+    }
 
     static rt_params params(const RenderSettings &s) {
         rt_params p{};

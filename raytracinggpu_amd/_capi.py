@@ -28,7 +28,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_stats_enable", "rt_ctx_set_pipelining", "rt_render_async", "rt_wait", "rt_trace_rays", "rt_mesh_rebuild", "rt_mesh_rebuild_mode", "rt_mesh_build_stats", "rt_host_alloc", "rt_host_free", "rt_device_alloc", "rt_device_free", "rt_device_to_host", "rt_kat_sphere", "rt_kat_sqrt", "rt_kat_box", "rt_kat_triangle", "rt_kat_mesh", "rt_kat_layout_hash",
            "rt_mesh_transform_of", "rt_mesh_set_normals_of", "rt_mesh_rebuild_of", "rt_mesh_set_texture", "rt_mesh_set_texture_of", "rt_kat_surface",
            "rt_scene_get_light", "rt_scene_set_light", "rt_scene_get_sphere", "rt_scene_set_sphere", "rt_scene_move_light", "rt_scene_move_sphere", "rt_light_orbit",
-           "rt_render_device_batch_scenes"]
+           "rt_render_device_batch_scenes",
+           "rt_render_aov_device", "rt_render_aov", "rt_denoise_device", "rt_denoise"]
 MAX_DEVICES = 16
 
 
@@ -121,6 +122,24 @@ class KatCounts(C.Structure):
 
 class CameraPose(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("yaw", C.c_float), ("pitch", C.c_float), ("fov", C.c_float)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("n_passes", C.c_int32), ("k_normal", C.c_float), ("k_position", C.c_float), ("k_albedo", C.c_float), ("k_color", C.c_float)]
+
+
+# The defaults of make_denoise_params: chosen by the experiment of DESIGN.md section 5.7 (RMSE of a 1-sample frame against a 1024-sample one, cat and sphere scenes).
+# k_color weighs squared differences of LINEAR colour, so it scales with 1 / light intensity^2: 5e-12 suits the reference's light (3e10, colours up to ~1e6).
+DENOISE_DEFAULTS = dict(n_passes=3, k_normal=2.0, k_position=0.25, k_albedo=16.0, k_color=5e-12)
+
+
+def make_denoise_params(n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_color=None):
+    """rt_denoise_params; None = the default of DENOISE_DEFAULTS.  A k of 0 switches its term off."""
+    given = dict(n_passes=n_passes, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_color=k_color)
+    d = DenoiseParams()
+    for name, v in given.items():
+        setattr(d, name, DENOISE_DEFAULTS[name] if v is None else v)
+    return d
 
 
 def make_pose(position=(0.0, 0.0, 55.0), yaw=0.0, pitch=0.3, fov=None):
@@ -225,6 +244,10 @@ def load():
     L.rt_scene_move_sphere.argtypes = [vp, C.c_int, fp3, C.c_float]
     L.rt_light_orbit.argtypes = [C.POINTER(Light), C.c_float, C.c_float, C.POINTER(Light)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
+    L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
+    L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
+    L.rt_denoise_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(DenoiseParams), vp, vp]
+    L.rt_denoise.argtypes = [vp, fp3, fp3, C.c_int, C.c_int, C.POINTER(DenoiseParams), fp3]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_host_free.argtypes = [vp]
     L.rt_kat_sphere.argtypes = [vp, fp3, C.c_int, fp3]
@@ -602,6 +625,44 @@ class Context:
         self._check(self._L.rt_kat_surface(self._h, rays.ctypes.data_as(C.POINTER(C.c_float)), rays.shape[0], C.c_float(tri_tmin),
                                            out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    # --- first-hit feature buffers and the edge-avoiding filter they guide (rt_render_aov*, rt_denoise*)
+    def render_aov(self, params, pose=None, rows=None):
+        """rt_render_aov: the G-buffer of the pixel-centre camera rays -> [3, n_rows, W, 4] float32: plane 0 (normal, object id or -1), plane 1 (hit point, 1 / 0),
+        plane 2 (albedo, 0).  pose: a CameraPose (None = the uploaded camera); rows: a Rows (None = the whole frame).  The first hit, whatever its material."""
+        n_rows = params.height if rows is None else rows.n_rows
+        out = np.zeros((3, max(n_rows, 0), params.width, 4), np.float32)
+        self._check(self._L.rt_render_aov(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(rows) if rows is not None else None,
+                                          out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_aov_device(self, params, out_ptr, pose=None, rows=None, stream=None):
+        """rt_render_aov_device: the same three planes into device memory (3 * n_rows * W float4), asynchronous on `stream`."""
+        whole = Rows(0, params.height, max(params.height, 1), 1)
+        self._check(self._L.rt_render_aov_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(whole if rows is None else rows),
+                                                 C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def denoise(self, color, aov, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_color=None, out=None):
+        """rt_denoise: the a-trous filter over color [H, W, 4] guided by aov [3, H, W, 4] (render_aov of the same frame) -> [H, W, 4].  Parameters as
+        make_denoise_params.  out: optional preallocated result; it must not share memory with an input."""
+        color = np.ascontiguousarray(color, np.float32)
+        aov = np.ascontiguousarray(aov, np.float32)
+        if color.ndim != 3 or color.shape[2] != 4 or aov.shape != (3,) + color.shape:
+            raise RtError(-1, f"denoise: color {color.shape} must be [H, W, 4] and aov {aov.shape} [3, H, W, 4] of the same frame")
+        if out is None:
+            out = np.zeros_like(color)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != color.shape:
+            raise RtError(-1, f"denoise: out must be a contiguous float32 array of shape {color.shape}")
+        dp = make_denoise_params(n_passes, k_normal, k_position, k_albedo, k_color)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_denoise(self._h, color.ctypes.data_as(fp), aov.ctypes.data_as(fp), color.shape[1], color.shape[0], C.byref(dp), out.ctypes.data_as(fp)))
+        return out
+
+    def denoise_device(self, color_ptr, aov_ptr, width, height, out_ptr, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_color=None, stream=None):
+        """rt_denoise_device: device pointers (a frame of rt_render_device, the planes of render_aov_device, the result), asynchronous on `stream`."""
+        dp = make_denoise_params(n_passes, k_normal, k_position, k_albedo, k_color)
+        self._check(self._L.rt_denoise_device(self._h, C.c_void_p(color_ptr), C.c_void_p(aov_ptr), int(width), int(height), C.byref(dp), C.c_void_p(out_ptr),
+                                              C.c_void_p(stream) if stream else None))
 
     def render_pose(self, params, pose):
         """One frame with realtime_render.cu's posed camera and per-sample averaging (no accumulation)."""

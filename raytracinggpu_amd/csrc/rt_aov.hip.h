@@ -1,0 +1,125 @@
+// rt_aov.hip.h -- rt_render_aov[_device]: the first-hit feature buffers (G-buffer) of a frame, for the edge-avoiding filter of rt_denoise.hip.h.
+// Included at the end of rt_capi.hip, after rt_trace.hip.h (same translation unit: it runs the traversal launch of rt_trace_rays, trace_queue).
+//
+// One ray per pixel of the rows: the pixel-centre camera ray (camera_dir with sigma = 0: no sample key is read), intersected with the scene as
+// Scene::intersect_all does (cpu_launcher.cpp:545-564): every sphere by the sphere search of wf_advance (spheres_near2), the meshes by the production
+// traversal (wf_travq with the launch plan of a frame), the two joined by mesh_beats_sphere -- the strict '<' in object order.  The normal is hit_normal, the
+// albedo the object's or tex_albedo's: the device functions of rt_shade.hip.h / rt_wavefront.hip.h the render kernels call, so the planes hold the very values
+// the first segment of a path is shaded with.  Nothing here touches the render path's state: the queue and the results live in buffers of their own.
+#pragma once
+
+namespace rtk {
+
+// the camera ray of AOV item r: pixel (r % W) of local row (r / W)
+__device__ __forceinline__ void aov_ray(const Scene &sc, const Frame &fr, int r, f3 &O, f3 &u) {
+    const int lrow = r / fr.W, px = r - lrow * fr.W;
+    O = mk(sc.camx, sc.camy, sc.camz);
+    u = camera_dir(fr, O, fr.z, px, image_row(fr, lrow), 0u);      // fr.sigma == 0: the key is not read
+}
+
+// trace_emit_kernel with the rays made here: one lane per ray slot pair, rays r < n are the pixels', the rest of the 2 n_paths slots carry no ray
+__global__ __launch_bounds__(256) void aov_emit_kernel(const Scene sc, const Frame fr, const WfState st, int n) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= 2 * st.n_paths) return;
+    const int q = wf_ray_to_slot(st, r);
+    bool need = false;
+    f3 O = mk(0, 0, 0), u = mk(0, 0, 1);
+    if (r < n) {
+        aov_ray(sc, fr, r, O, u);
+        if (sc.mesh_slot >= 0 && sc.n_nodes > 0) need = slab_filtered(sc.root_lo, sc.root_hi, O, u, ray_inv(u));   // wf_emit_ray's root-box test
+    }
+    st.M[r] = WF_NOHIT;
+    st.QR[2 * (size_t)q] = make_float4(O.x, O.y, O.z, u.x);
+    st.QR[2 * (size_t)q + 1] = make_float4(u.y, u.z, __int_as_float(need ? PQ_TRAV : 0), 0.f);
+}
+
+// closes the query as wf_advance closes a continuation ray's and writes the three planes (n float4 each, consecutive)
+__global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Frame fr, const TexScene ts, const unsigned long long *__restrict__ M, int n, float4 *__restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    f3 O, u;
+    aov_ray(sc, fr, r, O, u);
+    SphereNear hy, hx;
+    spheres_near2(sc, O, u, true, u, false, hy, hx);
+    float t_min = hy.t;
+    int win = hy.obj, tri_win = -1;
+    const unsigned long long m = M[r];
+    if (m != WF_NOHIT) {
+        const float tm = __uint_as_float((unsigned int)(m >> 32));
+        const int mobj = mesh_obj_of_tri(sc, (int)(unsigned int)m);
+        if (mesh_beats_sphere(t_min, win, tm, mobj)) { t_min = tm; win = mobj; tri_win = (int)(unsigned int)m; }
+    }
+    float4 o0 = make_float4(0.f, 0.f, 0.f, -1.f), o1 = make_float4(0.f, 0.f, 0.f, 0.f), o2 = o1;
+    if (win >= 0) {
+        const f3 P = O + t_min * u;                                   // cpu:560
+        Bary bary{0.f, 0.f, 0.f};
+        bool have_bary = false;
+        const f3 N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
+        f3 alb;
+        if (tri_win >= 0 && ((ts.mask >> win) & 1)) {
+            if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
+            float2 uv;
+            alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
+        } else {
+            const Material mt = material_of(sc, win);
+            alb = mk(mt.ar, mt.ag, mt.ab);
+        }
+        o0 = make_float4(N.x, N.y, N.z, (float)win);
+        o1 = make_float4(P.x, P.y, P.z, 1.f);
+        o2 = make_float4(alb.x, alb.y, alb.z, 0.f);
+    }
+    out[r] = o0;
+    out[(size_t)n + r] = o1;
+    out[2 * (size_t)n + r] = o2;
+}
+
+}  // namespace rtk
+
+extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_aov_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (!p || !rows || !out_aov_dev) return fail(ctx, RT_ERR_INVALID, "params/rows/out is NULL");
+    if (p->width <= 0 || p->height <= 0) return fail(ctx, RT_ERR_INVALID, "width/height must be positive");
+    if (rows->n_rows < 0 || rows->row0 < 0 || rows->tile_rows <= 0 || rows->tile_step <= 0) return fail(ctx, RT_ERR_INVALID, "bad row specification");
+    if (rows->n_rows == 0) return RT_OK;
+    const int64_t last = rows->n_rows - 1;
+    const int64_t last_row = rows->row0 + (last / rows->tile_rows) * rows->tile_rows * (int64_t)rows->tile_step + (last % rows->tile_rows);
+    if (last_row >= p->height) return fail(ctx, RT_ERR_INVALID, "rows reach image row %lld >= height %d", (long long)last_row, p->height);
+    const int64_t n64 = (int64_t)rows->n_rows * p->width;
+    if (n64 >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "at most 2^28 pixels per call");
+    const int n = (int)n64;
+    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
+    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // the frame of a render call with these parameters (make_frame: camera distance, pose, rows), without the jitter
+    Chunk c{p, rows, q, nullptr, nullptr, false, 1, 1, {}, {}, nullptr};
+    make_frame(ctx, out_aov_dev, pose, c);
+    c.fr.sigma = 0.f;
+    if (ctx->pipe.on) {                                                // (see Pipe::between: a pipelined frame must not start behind this write)
+        if (ctx->pipe.between.size() >= 64) ctx->pipe.between_overflow = true;
+        else { const uint8_t *a = static_cast<const uint8_t *>(out_aov_dev); ctx->pipe.between.push_back({a, a + 3 * (size_t)n * sizeof(float4), q}); }
+    }
+    unsigned long long *M = nullptr;
+    int rc = trace_queue(ctx, n, p->tri_tmin, RT_VARIANT_WAVEFRONT_QUEUE, q, ctx->aovM, ctx->aovQR, M, [&](const rtk::WfState &st, dim3 g, dim3 b) {
+        hipLaunchKernelGGL(rtk::aov_emit_kernel, g, b, 0, q, c.scn, c.fr, st, n);
+    });
+    if (rc != RT_OK) return rc;
+    hipLaunchKernelGGL(rtk::aov_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, c.scn, c.fr, tex_scene(ctx), M, n, static_cast<float4 *>(out_aov_dev));
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" int rt_render_aov(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, float *out_aov_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!p || !out_aov_host) return fail(ctx, RT_ERR_INVALID, "params/out is NULL");
+    const rt_rows whole{0, p->height, p->height > 0 ? p->height : 1, 1};
+    if (!rows) rows = &whole;
+    const size_t bytes = 3 * (size_t)(rows->n_rows > 0 ? rows->n_rows : 0) * (p->width > 0 ? p->width : 0) * sizeof(float4);
+    int rc = ensure(ctx, ctx->aov_out, bytes);
+    if (rc != RT_OK) return rc;
+    if ((rc = rt_render_aov_device(ctx, p, pose, rows, ctx->aov_out.p, nullptr)) != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(out_aov_host, ctx->aov_out.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    return RT_OK;
+}

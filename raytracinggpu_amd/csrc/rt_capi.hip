@@ -107,6 +107,7 @@ int rt_ctx_destroy(rt_ctx *ctx) {
     for (DevBuf &b : ctx->tex_img) b.release();
     ctx->wfQR.release(); ctx->accum.release(); ctx->dbgbuf.release(); ctx->batch_dev.release(); ctx->anim_dev.release();
     ctx->pathSamp.release(); ctx->pathT.release(); ctx->tidx_up.release();
+    ctx->aovM.release(); ctx->aovQR.release(); ctx->aov_out.release(); ctx->dn_tmp.release(); ctx->dn_io.release();
     for (DevBuf *b : {&ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp, &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev}) b->release();
     for (hipEvent_t &e : ctx->ev_trav) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t &e : ctx->ev_adv) if (e) (void)hipEventDestroy(e);
@@ -480,7 +481,8 @@ int rt_ctx_selfcheck(rt_ctx *ctx) {
                             &ctx->scratch_rgba, &ctx->scratch_rgb8, &ctx->work, &ctx->queue, &ctx->wfM, &ctx->wfT, &ctx->wfLS, &ctx->wfSID, &ctx->wfSamp,
                             &ctx->wfQR, &ctx->pathSamp, &ctx->pathT, &ctx->accum, &ctx->left_dev, &ctx->lvl_nodes, &ctx->lvl_off, &ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp,
                             &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev,
-                            &ctx->slot_rgba[0], &ctx->slot_rgba[1], &ctx->slot_rgb8[0], &ctx->slot_rgb8[1], &ctx->wfALB, &ctx->tex_uv, &ctx->tex_table};
+                            &ctx->slot_rgba[0], &ctx->slot_rgba[1], &ctx->slot_rgb8[0], &ctx->slot_rgb8[1], &ctx->wfALB, &ctx->tex_uv, &ctx->tex_table,
+                            &ctx->aovM, &ctx->aovQR, &ctx->aov_out, &ctx->dn_tmp, &ctx->dn_io};
     for (const DevBuf *b : bufs) {
         if (!b->p) continue;
         hipPointerAttribute_t at{};
@@ -563,3 +565,5 @@ int rt_get_stats(rt_ctx *ctx, rt_stats *stats) {
 #include "rt_multi.hip.h"
 #include "rt_kat.hip.h"
 #include "rt_trace.hip.h"
+#include "rt_aov.hip.h"
+#include "rt_denoise.hip.h"

@@ -1,0 +1,174 @@
+// rt_denoise.hip.h -- rt_denoise[_device]: the edge-avoiding a-trous filter over a colour frame, guided by the planes of rt_render_aov (rt_aov.hip.h).
+// Included at the end of rt_capi.hip.
+//
+// Pass k (step s = 2^k) is one launch: a 5x5 B3-spline stencil with holes, every tap weighted by how well its first hit agrees with the centre's -- same object,
+// normal, tangent plane, albedo, colour (raytrace_hip.h states the formula; it is the contract: binary32, one rounding per operation, taps in row-major order,
+// tests/denoise_model.py is its numpy twin).
+// How a pass runs: a stencil with holes of s never leaves the pixels that share (x mod s, y mod s), so the image is s x s independent sub-images on which the stencil
+// is the DENSE 5x5 one.  A workgroup takes a tile of kDnTileW x kDnTileH pixels of one sub-image, one lane per pixel, brings the tile's four planes with a halo of 2
+// sub-image pixels into LDS once (plane after plane: N|id, P, albedo, colour; 27 KiB, whatever s is) and reads its 25 taps from there as ds_read_b128s: 6.75 global
+// 16-byte loads per pixel instead of 100.  For s > 1 those loads and the store are strided by 16 s bytes; the workgroups of the s x-phases of one tile are numbered
+// next to each other and the numbering keeps neighbours on one XCD, so the rest of every line they fetch is used from the same L2.  (Loading the taps directly --
+// coalesced rows through L1, no LDS -- measured 280-340 us per 1080p pass at s >= 4 against 82 us for the tiled s = 1 pass: DESIGN.md section 5.7.)
+// A tap whose object id differs is dropped before its other three records are looked at.
+#pragma once
+#include "rt_div.h"
+
+namespace rtk {
+
+constexpr int kDnTileW = 32, kDnTileH = 8;           // 256 lanes; a wave = rows 2 w, 2 w + 1 of the tile
+constexpr int kDnHalo = 2;                           // in pixels of the sub-image
+constexpr int kDnTw = kDnTileW + 2 * kDnHalo, kDnTh = kDnTileH + 2 * kDnHalo;
+constexpr int kDnXcds = 8;                           // consecutive workgroup ids go round the XCDs
+
+struct DnParams { float k_normal, k_position, k_albedo, k_color; };   // k_color already scaled by 4^k
+
+__device__ __forceinline__ float dn_sqdiff(float4 a, float4 b) {
+    const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
+    return (x * x + y * y) + z * z;
+}
+// max(0, 1 - d k); a k of exactly 0 makes the term exactly 1, whatever d is
+__device__ __forceinline__ float dn_term(float d, float k) { return k == 0.f ? 1.f : fmaxf(0.f, 1.f - d * k); }
+
+// The pixel's filtered value.  fetch(plane, dx, dy): record `plane` (0 N|id, 1 P, 2 albedo, 3 colour) of the pixel (x + dx s, y + dy s), which lies inside the image.
+template <class Fetch>
+__device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, const DnParams &k, Fetch fetch) {
+    const float4 Np = fetch(0, 0, 0), Cp = fetch(3, 0, 0);
+    if (Np.w == -1.f) return Cp;                                      // a miss: nothing to guide the filter
+    const float4 Pp = fetch(1, 0, 0), Ap = fetch(2, 0, 0);
+    const float Hk[3] = {0.375f, 0.25f, 0.0625f};
+    float Sx = 0.f, Sy = 0.f, Sz = 0.f, Wt = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * s, qy = y + dy * s;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const float4 Nq = fetch(0, dx, dy);
+            if (Nq.w != Np.w) continue;                               // another object (or a miss)
+            const float h = Hk[dy < 0 ? -dy : dy] * Hk[dx < 0 ? -dx : dx];
+            float w = h * dn_term(dn_sqdiff(Np, Nq), k.k_normal);
+            if (k.k_position != 0.f) {
+                const float4 Pq = fetch(1, dx, dy);
+                const float e = (Np.x * (Pq.x - Pp.x) + Np.y * (Pq.y - Pp.y)) + Np.z * (Pq.z - Pp.z);
+                w = w * fmaxf(0.f, 1.f - (e * e) * k.k_position);
+            }                                                         // (else: times exactly 1)
+            if (k.k_albedo != 0.f) w = w * fmaxf(0.f, 1.f - dn_sqdiff(Ap, fetch(2, dx, dy)) * k.k_albedo);
+            const float4 Cq = fetch(3, dx, dy);
+            w = w * dn_term(dn_sqdiff(Cp, Cq), k.k_color);
+            if (w > 0.f) {                                            // (false for a NaN weight: a NaN guide does not spread)
+                Sx = Sx + w * Cq.x; Sy = Sy + w * Cq.y; Sz = Sz + w * Cq.z;
+                Wt = Wt + w;
+            }
+        }
+    }
+    // S / W, correctly rounded: three numerators over one denominator (rt_div.h), the literal quotient outside the shared sequence's range
+    const float r1 = div_refine(Wt, __builtin_amdgcn_rcpf(Wt));
+    float ox = div_by(Sx, Wt, r1), oy = div_by(Sy, Wt, r1), oz = div_by(Sz, Wt, r1);
+    const bool fast = div_in_range(Wt) && div_in_range(Sx) && div_in_range(Sy) && div_in_range(Sz);
+    if (__builtin_expect(__ballot(!fast) != 0ull, 0)) {
+        if (!fast) { ox = Sx / Wt; oy = Sy / Wt; oz = Sz / Wt; }
+    }
+    return make_float4(ox, oy, oz, Cp.w);
+}
+
+// g: the three guide planes (W * H float4 each, consecutive), C: the pass's input frame.  tiles_x, tiles_y: tiles of a sub-image; n_blocks = tiles_x * tiles_y * s * s.
+__global__ __launch_bounds__(kDnTileW * kDnTileH) void denoise_pass_kernel(const float4 *__restrict__ C, const float4 *__restrict__ g, float4 *__restrict__ out,
+                                                                            int W, int H, int s, int tiles_x, int tiles_y, int n_blocks, const DnParams k) {
+    __shared__ float4 dn_tile[4 * kDnTw * kDnTh];    // [4 planes][kDnTh rows][kDnTw]: neighbouring lanes read neighbouring 16 bytes
+    // workgroup id -> work item: ids b, b + 8, b + 16 .. run on one XCD and take consecutive items (the grid is padded to a multiple of kDnXcds)
+    const int per_xcd = (int)gridDim.x / kDnXcds;
+    const int item = ((int)blockIdx.x % kDnXcds) * per_xcd + (int)blockIdx.x / kDnXcds;
+    if (item >= n_blocks) return;                                     // (the whole workgroup: no barrier is left behind)
+    // item = ((tile_y * s + phase_y) * tiles_x + tile_x) * s + phase_x: the x-phases of a tile are neighbours
+    const int phase_x = item % s, i1 = item / s;
+    const int tile_x = i1 % tiles_x, i2 = i1 / tiles_x;
+    const int phase_y = i2 % s, tile_y = i2 / s;
+    const size_t plane = (size_t)W * (size_t)H;
+    const int tx = threadIdx.x & (kDnTileW - 1), ty = threadIdx.x / kDnTileW;
+    const int sx0 = tile_x * kDnTileW - kDnHalo, sy0 = tile_y * kDnTileH - kDnHalo;   // the LDS tile's origin, in sub-image pixels
+    for (int i = threadIdx.x; i < kDnTw * kDnTh; i += kDnTileW * kDnTileH) {
+        const int ly = i / kDnTw, lx = i - ly * kDnTw;
+        const int qx = (sx0 + lx) * s + phase_x, qy = (sy0 + ly) * s + phase_y;
+        if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;         // never read: the taps test the image's bounds themselves
+        const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) dn_tile[p * kDnTw * kDnTh + i] = g[(size_t)p * plane + q];
+        dn_tile[3 * kDnTw * kDnTh + i] = C[q];
+    }
+    __syncthreads();
+    const int x = (tile_x * kDnTileW + tx) * s + phase_x, y = (tile_y * kDnTileH + ty) * s + phase_y;
+    if (x >= W || y >= H) return;
+    const int centre = (ty + kDnHalo) * kDnTw + tx + kDnHalo;        // a tap at (dx s, dy s) is the sub-image's neighbour (dx, dy)
+    out[(size_t)y * W + x] = dn_pixel(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; });
+}
+
+}  // namespace rtk
+
+// do [a, a + na) and [b, b + nb) share a byte?
+static bool dn_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uint8_t *x = static_cast<const uint8_t *>(a), *y = static_cast<const uint8_t *>(b);
+    return x < y + nb && y < x + na;
+}
+
+static int dn_check(rt_ctx *ctx, const void *color, const void *aov, int width, int height, const rt_denoise_params *dp, const void *out) {
+    if (!color || !aov || !dp || !out) return fail(ctx, RT_ERR_INVALID, "color/aov/params/out is NULL");
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "width/height must be positive, at most 2^28 pixels");
+    if (dp->n_passes < 1 || dp->n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", dp->n_passes, RT_DENOISE_MAX_PASSES);
+    return RT_OK;
+}
+
+extern "C" int rt_denoise_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, int width, int height, const rt_denoise_params *dp, void *out_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = dn_check(ctx, color_dev, aov_dev, width, height, dp, out_dev);
+    if (rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    if (dn_overlap(out_dev, bytes, color_dev, bytes) || dn_overlap(out_dev, bytes, aov_dev, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
+    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
+    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (dp->n_passes > 1 && (rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
+    if (ctx->pipe.on) {                                                // (see Pipe::between: a pipelined frame must not overtake this read of a frame / write of an image)
+        if (ctx->pipe.between.size() + 2 > 64) ctx->pipe.between_overflow = true;
+        else {
+            const uint8_t *a = static_cast<const uint8_t *>(color_dev), *b = static_cast<const uint8_t *>(out_dev);
+            ctx->pipe.between.push_back({a, a + bytes, q});
+            ctx->pipe.between.push_back({b, b + bytes, q});
+        }
+    }
+    // the passes alternate between the output and one buffer of the context so that the last one lands in the output
+    const float4 *src = static_cast<const float4 *>(color_dev);
+    for (int k = 0; k < dp->n_passes; ++k) {
+        float4 *dst = static_cast<float4 *>(((dp->n_passes - 1 - k) & 1) ? ctx->dn_tmp.p : out_dev);
+        const int s = 1 << k;
+        const rtk::DnParams kp{dp->k_normal, dp->k_position, dp->k_albedo, dp->k_color * (float)(1 << (2 * k))};   // 4^k: an exact scale
+        // tiles of the largest sub-image (phase 0): ceil(ceil(W / s) / tile)
+        const int tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
+        const int64_t n_blocks = (int64_t)tiles_x * tiles_y * s * s;
+        const int64_t grid = (n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds;
+        hipLaunchKernelGGL(rtk::denoise_pass_kernel, dim3((unsigned)grid), dim3(rtk::kDnTileW * rtk::kDnTileH), 0, q, src, static_cast<const float4 *>(aov_dev), dst,
+                           width, height, s, tiles_x, tiles_y, (int)n_blocks, kp);
+        src = dst;
+    }
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" int rt_denoise(rt_ctx *ctx, const float *color_host, const float *aov_host, int width, int height, const rt_denoise_params *dp, float *out_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    int rc = dn_check(ctx, color_host, aov_host, width, height, dp, out_host);
+    if (rc != RT_OK) return rc;
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    if (dn_overlap(out_host, bytes, color_host, bytes) || dn_overlap(out_host, bytes, aov_host, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
+    // one buffer: colour, the three planes, the result
+    if ((rc = ensure(ctx, ctx->dn_io, 5 * bytes)) != RT_OK) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->dn_io.p);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipMemcpyAsync(base, color_host, bytes, hipMemcpyHostToDevice, own_stream(ctx)));
+    RT_HIP(ctx, hipMemcpyAsync(base + bytes, aov_host, 3 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
+    if ((rc = rt_denoise_device(ctx, base, base + bytes, width, height, dp, base + 4 * bytes, nullptr)) != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(out_host, base + 4 * bytes, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    return RT_OK;
+}

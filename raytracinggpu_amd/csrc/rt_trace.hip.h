@@ -67,54 +67,68 @@ __global__ __launch_bounds__(256) void kat_surface_kernel(const Scene sc, const 
 
 }  // namespace rtk
 
+// n ray slots through the traversal launch of a frame of a default context (plan_trav without RT_TRAVQ_LDS staging, one sub-frame) on stream q, with the traversal results
+// in bufM and the queue in bufQR.  emit(st, grid, block): the launch that writes every one of the 2 st.n_paths slots' records and M entries (trace_emit_kernel's contract).
+// M: bits(t) << 32 | triangle (visit order) per ray, WF_NOHIT if none.  variant: wavefront_queue (wf_travq) or wavefront (wf_trav).
+template <class Emit>
+static int trace_queue(rt_ctx *ctx, int n, float tri_tmin, int variant, hipStream_t q, DevBuf &bufM, DevBuf &bufQR, unsigned long long *&M, Emit emit) {
+    const rtk::Scene &sc = ctx->scene;
+    if (variant == RT_VARIANT_WAVEFRONT_QUEUE && (sc.n_nodes + 2 >= (1 << rtk::kQNodeBits) || !ctx->travq_ok)) variant = RT_VARIANT_WAVEFRONT;
+    const Knobs &kn = ctx->knobs;
+    int rc;
+    rtk::Frame fr{};
+    fr.tri_tmin = tri_tmin; fr.segs = 1; fr.spp = 1; fr.W = 1; fr.H = 1; fr.n_rows = 1; fr.tile_rows = 1; fr.tile_step = 1; fr.out_tile_step = 1;
+    Variant v{};
+    v.variant = v.asked = variant;
+    TravPlan t;
+    if ((rc = plan_trav(ctx, v, false, 0, t)) != RT_OK) return rc;
+    rtk::WfState st{};
+    st.n_paths = ((n + 1) / 2 + 1) / 2 * 2;                           // 2 n_paths ray slots >= n, a multiple of 4
+    st.n_px = st.n_paths; st.tiles_x = 1;
+    const int64_t tblocks = wf_geometry(kn, ctx->n_cus, t.bpc, 1, t.wpb, t.queue, st);
+    const size_t q_slots = (size_t)st.slots_per_block * (size_t)tblocks;
+    if ((rc = ensure(ctx, bufM, 2 * (size_t)st.n_paths * 8)) != RT_OK || (rc = ensure(ctx, bufQR, q_slots * 32)) != RT_OK) return rc;
+    RT_HIP(ctx, hipMemsetAsync(bufQR.p, 0, q_slots * 32, q));        // padding slots carry no ray
+    st.QR = static_cast<float4 *>(bufQR.p);
+    st.M = M = static_cast<unsigned long long *>(bufM.p);
+    st.init_m = t.queue ? 0 : 1;
+    st.epoch = 0; st.nonce = 0;
+    emit(st, dim3((unsigned)((2 * st.n_paths + 255) / 256)), dim3(256));
+    if (t.have_mesh) launch_trav(t, tblocks, q, sc, fr, st);
+    return RT_OK;
+}
+
 // The caller's rays (din: n x 6 floats on the device) through the production traversal of `variant`; M: bits(t) << 32 | triangle (visit order) per ray, WF_NOHIT if none
 static int trace_to_m(rt_ctx *ctx, const float *din, int n, float tri_tmin, int variant, unsigned long long *&M) {
     const rtk::Scene &sc = ctx->scene;
-    if (variant == RT_VARIANT_WAVEFRONT_QUEUE && (sc.n_nodes + 2 >= (1 << rtk::kQNodeBits) || !ctx->travq_ok)) variant = RT_VARIANT_WAVEFRONT;
     if (variant == RT_VARIANT_PATH && sc.n_nodes + 2 >= (1 << rtk::kPNodeBits)) variant = RT_VARIANT_WAVEFRONT;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_OWN_STREAM(ctx);
     hipStream_t q = own_stream(ctx);
     const Knobs &kn = ctx->knobs;
+    M = nullptr;
+    if (variant != RT_VARIANT_PATH) {
+        ctx->qf_sig = 0;                                               // the queue is the render path's: it zeroes its own layout again
+        return trace_queue(ctx, n, tri_tmin, variant, q, ctx->wfM, ctx->wfQR, M, [&](const rtk::WfState &st, dim3 g, dim3 b) {
+            hipLaunchKernelGGL(rtk::trace_emit_kernel, g, b, 0, q, sc, st, din, n);
+        });
+    }
+    // the fused kernel: items = the rays, in wf_path's own launch geometry (path_geometry, as launch_path uses it)
     int rc;
     rtk::Frame fr{};
     fr.tri_tmin = tri_tmin; fr.segs = 1; fr.spp = 1; fr.W = 1; fr.H = 1; fr.n_rows = 1; fr.tile_rows = 1; fr.tile_step = 1; fr.out_tile_step = 1;
-    M = nullptr;
-    if (variant == RT_VARIANT_PATH) {
-        // the fused kernel: items = the rays, in wf_path's own launch geometry (path_geometry, as launch_path uses it)
-        const size_t lds = (size_t)(rtk::kQBlock / 64) * rtk::PCarve::bytes(1) + 16;
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtk::wf_path<false>, rtk::kQBlock, lds) != hipSuccess || nb < 1) return fail(ctx, RT_ERR_UNSUPPORTED, "wf_path does not fit a CU");
-        rtk::PathState ps{};
-        ps.n_paths = (n + 63) / 64 * 64; ps.tiles_x = 1; ps.samp0 = 0; ps.n_samp = 1; ps.samp_out = nullptr;
-        ps.n_groups = ps.n_paths / 4;
-        if ((rc = ensure(ctx, ctx->wfM, (size_t)ps.n_paths * 8)) != RT_OK) return rc;
-        M = static_cast<unsigned long long *>(ctx->wfM.p);
-        ps.ext_rays = din; ps.ext_out = M; ps.n_ext = n;
-        const int64_t tblocks = path_geometry(kn, ctx->n_cus, std::min(kn.path_bpc, nb), 1, ps);
-        RT_HIP(ctx, hipMemsetAsync(M, 0xff, (size_t)ps.n_paths * 8, q));      // rays the kernel never reaches (none) would read as no hit
-        hipLaunchKernelGGL(rtk::wf_path<false>, dim3((unsigned)tblocks), dim3(rtk::kQBlock), lds, q, sc, fr, ps, capped_stack(kn, rtk::kPStack), kn.path_low, kn.path_shade_min);
-    } else {
-        // the traversal launch of a frame of a default context (plan_trav without RT_TRAVQ_LDS staging), one sub-frame
-        Variant v{};
-        v.variant = v.asked = variant;
-        TravPlan t;
-        if ((rc = plan_trav(ctx, v, false, 0, t)) != RT_OK) return rc;
-        rtk::WfState st{};
-        st.n_paths = ((n + 1) / 2 + 1) / 2 * 2;                       // 2 n_paths ray slots >= n, a multiple of 4
-        st.n_px = st.n_paths; st.tiles_x = 1;
-        const int64_t tblocks = wf_geometry(kn, ctx->n_cus, t.bpc, 1, t.wpb, t.queue, st);
-        const size_t q_slots = (size_t)st.slots_per_block * (size_t)tblocks;
-        if ((rc = ensure(ctx, ctx->wfM, 2 * (size_t)st.n_paths * 8)) != RT_OK || (rc = ensure(ctx, ctx->wfQR, q_slots * 32)) != RT_OK) return rc;
-        RT_HIP(ctx, hipMemsetAsync(ctx->wfQR.p, 0, q_slots * 32, q));    // padding slots carry no ray
-        ctx->qf_sig = 0;                                               // the render path zeroes its own layout again
-        st.QR = static_cast<float4 *>(ctx->wfQR.p);
-        st.M = M = static_cast<unsigned long long *>(ctx->wfM.p);
-        st.init_m = t.queue ? 0 : 1;
-        st.epoch = 0; st.nonce = 0;
-        hipLaunchKernelGGL(rtk::trace_emit_kernel, dim3((unsigned)((2 * st.n_paths + 255) / 256)), dim3(256), 0, q, sc, st, din, n);
-        if (t.have_mesh) launch_trav(t, tblocks, q, sc, fr, st);
-    }
+    const size_t lds = (size_t)(rtk::kQBlock / 64) * rtk::PCarve::bytes(1) + 16;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rtk::wf_path<false>, rtk::kQBlock, lds) != hipSuccess || nb < 1) return fail(ctx, RT_ERR_UNSUPPORTED, "wf_path does not fit a CU");
+    rtk::PathState ps{};
+    ps.n_paths = (n + 63) / 64 * 64; ps.tiles_x = 1; ps.samp0 = 0; ps.n_samp = 1; ps.samp_out = nullptr;
+    ps.n_groups = ps.n_paths / 4;
+    if ((rc = ensure(ctx, ctx->wfM, (size_t)ps.n_paths * 8)) != RT_OK) return rc;
+    M = static_cast<unsigned long long *>(ctx->wfM.p);
+    ps.ext_rays = din; ps.ext_out = M; ps.n_ext = n;
+    const int64_t tblocks = path_geometry(kn, ctx->n_cus, std::min(kn.path_bpc, nb), 1, ps);
+    RT_HIP(ctx, hipMemsetAsync(M, 0xff, (size_t)ps.n_paths * 8, q));      // rays the kernel never reaches (none) would read as no hit
+    hipLaunchKernelGGL(rtk::wf_path<false>, dim3((unsigned)tblocks), dim3(rtk::kQBlock), lds, q, sc, fr, ps, capped_stack(kn, rtk::kPStack), kn.path_low, kn.path_shade_min);
     return RT_OK;
 }
 

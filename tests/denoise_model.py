@@ -1,0 +1,108 @@
+"""Reference model of rt_denoise and of the pixel-centre camera ray of rt_render_aov (test infrastructure, like tests/texture_model.py).
+
+numpy binary32 throughout: every operation one rounding, in the order include/raytrace_hip.h states, so the device's frames are held to it bit for bit.  The 25
+taps of a pass are vectorised over the image; the order in which they are accumulated (dy outer, dx inner) is the contract's."""
+import numpy as np
+
+F = np.float32
+H3 = np.array([0.375, 0.25, 0.0625], np.float32)
+
+
+def _sqdiff(a, b):
+    x, y, z = a[..., 0] - b[..., 0], a[..., 1] - b[..., 1], a[..., 2] - b[..., 2]
+    return (x * x + y * y) + z * z
+
+
+def _term(d, k):
+    """max(0, 1 - d k); a k of exactly 0 makes the term exactly 1 (no operation at all)"""
+    k = F(k)
+    if k == 0:
+        return None
+    return np.maximum(F(0), F(1) - d * k)
+
+
+def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color):
+    """One pass with step s over the colour frame C [H, W, 4], guided by aov [3, H, W, 4]; k_color already carries its 4^k."""
+    C = np.ascontiguousarray(C, np.float32)
+    aov = np.ascontiguousarray(aov, np.float32)
+    Hh, W = C.shape[:2]
+    N, ID, P, A = aov[0, ..., :3], aov[0, ..., 3], aov[1, ..., :3], aov[2, ..., :3]
+    ys, xs = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
+    S = np.zeros((Hh, W, 3), np.float32)
+    Wt = np.zeros((Hh, W), np.float32)
+    with np.errstate(all="ignore"):
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                qy, qx = ys + dy * s, xs + dx * s
+                inside = (qy >= 0) & (qy < Hh) & (qx >= 0) & (qx < W)
+                qy, qx = np.clip(qy, 0, Hh - 1), np.clip(qx, 0, W - 1)
+                ok = inside & (ID[qy, qx] == ID)
+                w = np.full((Hh, W), H3[abs(dy)] * H3[abs(dx)], np.float32)
+                t = _term(_sqdiff(N, N[qy, qx]), k_normal)
+                if t is not None:
+                    w = w * t
+                if F(k_position) != 0:
+                    Pq = P[qy, qx]
+                    e = (N[..., 0] * (Pq[..., 0] - P[..., 0]) + N[..., 1] * (Pq[..., 1] - P[..., 1])) + N[..., 2] * (Pq[..., 2] - P[..., 2])
+                    w = w * _term(e * e, k_position)
+                t = _term(_sqdiff(A, A[qy, qx]), k_albedo)
+                if t is not None:
+                    w = w * t
+                Cq = C[qy, qx, :3]
+                t = _term(_sqdiff(C[..., :3], Cq), k_color)
+                if t is not None:
+                    w = w * t
+                take = ok & (w > 0)                                    # False for a NaN weight
+                S = np.where(take[..., None], S + w[..., None] * Cq, S)
+                Wt = np.where(take, Wt + w, Wt)
+        rgb = S / Wt[..., None]
+    out = C.copy()
+    hit = ID != F(-1)
+    out[hit, :3] = rgb[hit]
+    assert out.dtype == np.float32
+    return out
+
+
+def denoise(C, aov, n_passes, k_normal, k_position, k_albedo, k_color):
+    """rt_denoise: pass k = 0 .. n_passes - 1 with step 2^k; the colour term's k is k_color 4^k."""
+    assert 1 <= n_passes <= 8
+    out = np.ascontiguousarray(C, np.float32)
+    for k in range(n_passes):
+        out = denoise_pass(out, aov, 1 << k, k_normal, k_position, k_albedo, F(k_color) * F(4 ** k))
+    return out
+
+
+# ---- the camera ray of rt_render_aov: the pixel centre, cpu_launcher.cpp:694-709 with sigma = 0 (or realtime_render.cu:1112-1115 for a pose) ----
+def camera_rays(W, H, cam=(0.0, 0.0, 55.0), fov=None, rows=None, basis=None):
+    """-> (O [3], u [n_rows, W, 3]) in binary32.  rows: image row indices (None = all); basis = (bx, by, bz) of a posed camera (the position is `cam`)."""
+    fov = F(np.pi / 3) if fov is None else F(fov)
+    z = -F(W) / (F(2) * F(np.tan(np.float64(fov / F(2)))))
+    rows = np.arange(H) if rows is None else np.asarray(rows)
+    j = np.arange(W, dtype=np.float32)[None, :]
+    i = rows.astype(np.float32)[:, None]
+    x = ((j - F(W) / F(2)).astype(np.float64) + 0.5).astype(np.float32) + np.zeros_like(i)
+    y = ((F(H) / F(2) - i).astype(np.float64) - 0.5).astype(np.float32) + np.zeros_like(j)
+    v = np.stack([x, y, np.full_like(x, z)], axis=-1)
+    O = np.asarray(cam, np.float32)
+    if basis is not None:
+        bx, by, bz = (np.asarray(b, np.float32) for b in basis)
+        v = ((O + bz * v[..., 2:3]) + bx * v[..., 0:1]) + by * v[..., 1:2]
+    n = np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+    u = v / n[..., None]
+    assert u.dtype == np.float32
+    return O, u
+
+
+def oracle_aov(scene, albedos, W, H, tri_tmin=1e-4, **camera):
+    """The planes rt_render_aov writes, from the oracle's Scene::intersect_all: albedos[id] = the object's albedo.  -> [3, n_rows, W, 4]"""
+    O, u = camera_rays(W, H, **camera)
+    out = np.zeros((3,) + u.shape[:2] + (4,), np.float32)
+    out[0, ..., 3] = -1
+    for r in range(u.shape[0]):
+        for c in range(W):
+            hit, oid, P, N = scene.intersect_all(O, u[r, c], tri_tmin)
+            if hit:
+                out[0, r, c, :3], out[0, r, c, 3] = N, oid
+                out[1, r, c, :3], out[1, r, c, 3] = P, 1
+                out[2, r, c, :3] = albedos[oid]
+    return out
