@@ -535,6 +535,72 @@ int rt_render_aov(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, c
 int rt_denoise_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, int width, int height, const rt_denoise_params *dp, void *out_rgba_dev, void *stream);
 int rt_denoise(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, int width, int height, const rt_denoise_params *dp, float *out_rgba_host);
 
+/* --- temporal accumulation with reprojection, and the filter guided by variance (ABI 6, additive): the spatiotemporal half of the denoiser (SVGF).  A moving
+ *     scene never gets more than one sample per pixel from rt_progressive_frame; the planes of rt_render_aov* hold what reusing earlier frames needs.  The caller
+ *     owns all state: per frame it keeps the planes and the history it was given, and hands them back as "previous" with the next frame.
+ *     rt_temporal_accumulate*: inputs -- the current width x height colour frame C (float4, .w = rays), the current planes (planes 0 and 1 are read; the albedo
+ *     plane is not an input), the previous frame's planes 0 and 1 (2 * width * height float4), the previous history, a reprojection record.  Output: the new
+ *     HISTORY, two dense planes of width * height float4, consecutive:
+ *       history plane 0  .xyz = the accumulated colour, .w = C_p.w (the current frame's ray count);
+ *       history plane 1  (m1, m2, n, V) = the first and second moment of the luminance l = (0.2126 r + 0.7152 g) + 0.0722 b, the history length, the variance.
+ *     prev_aov == NULL and prev_history == NULL (both or neither): the first frame, or a cut; nobody has history.  `rp` (required with a previous frame):
+ *       posed == 0: the previous camera is `camera` (cpu:694-699); posed == 1: it is `pose` with the basis of rt_camera_basis.  The POSED CAMERA adds its
+ *       position INTO the ray direction (realtime_render.cu:1115: u = normalize(C + bz z + bx X + by Y), ray origin C): the projection below inverts exactly
+ *       that, not a textbook camera;
+ *       motion: NULL = nothing moved, else RT_MAX_OBJECTS records indexed by object id, each the rigid motion "previous from current" of that object:
+ *       P_prev = rotation (3 x 3, row-major) P_cur + translation (a sphere moved by rt_scene_move_sphere: identity, previous centre - current centre; a mesh moved
+ *       by rt_mesh_transform_of(R, T): R^T, -R^T T);
+ *       no_history_mask: bit i set = object i never reuses history (mirror and glass report themselves in the planes, not what they show: mask them).
+ *     The arithmetic is the contract -- binary32, one rounding per operation, no contraction, sums left to right, quotients correctly rounded.  Constants from
+ *     the record: O = the previous camera's position; (bx, by, bz) = its basis, the identity when posed == 0; z = -(float)width / (2 (float)tan((double)(fov / 2)));
+ *     posed: cx = O.bx, cy = O.by, b = O.bz + z, each dot (O.x b.x + O.y b.y) + O.z b.z; fixed: cx = cy = 0, b = z.  Pixel p = (x, y), id_p = plane 0 .w:
+ *       id_p == -1 (a miss): history 0 = C_p, history 1 = (0, 0, 0, 0).  Otherwise l = l(C_p) and, to begin with, n = 1, colour = C_p.rgb, m1 = l, m2 = l l.
+ *       If a previous frame is given and bit id_p of the mask is clear:
+ *         motion != NULL: P' = ((R0 P.x + R1 P.y) + R2 P.z) + T0 (rows 1, 2 likewise), N' = (R0 N.x + R1 N.y) + R2 N.z; motion == NULL: P' = P_p, N' = N_p;
+ *         d = P' - O;  k = b / ((d.x bz.x + d.y bz.y) + d.z bz.z);  X = ((d.x bx.x + d.y bx.y) + d.z bx.z) k - cx;  Y likewise with by, cy;
+ *         gx = X + (float)width / 2,  gy = (float)height / 2 - Y   (previous pixel (i, j)'s centre is gx = i + 0.5, gy = j + 0.5);
+ *         no history unless k > 0 (else P' is behind the camera) and -1 <= gx <= width and -1 <= gy <= height;
+ *         ix = floor(gx), iy = floor(gy) (the nearest previous pixel, round half up); jx = ix + 1 if gx - floor(gx) >= 0.5 else ix - 1; jy likewise;
+ *         the taps q = (ix, iy), (jx, iy), (ix, jy), (jx, jy) in this order; the FIRST valid one wins.  q is valid when it lies inside the image, id_q == id_p,
+ *         (N'.x N_q.x + N'.y N_q.y) + N'.z N_q.z >= min_normal_dot, and e e <= max_plane_dist max_plane_dist with
+ *         e = (N'.x (P_q.x - P'.x) + N'.y (P_q.y - P'.y)) + N'.z (P_q.z - P'.z)   (N_q, P_q: the PREVIOUS planes).  Nearest, not bilinear: with nothing moving
+ *         the history is exactly the running mean and does not blur.
+ *         With a valid tap (H_q, (m1_q, m2_q, n_q, .) = the previous history at q): n = min(n_q + 1, (float)max_history), a = max(1 / n, alpha_min),
+ *         colour = H_q + a (C_p - H_q) per channel, m1 = m1_q + a (l - m1_q), m2 = m2_q + a (l l - m2_q).
+ *       V = max(0, m2 - m1 m1).  While n < 4 it is replaced by the spatial estimate: over dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), the CURRENT frame's pixels
+ *       q = (x + dx, y + dy) inside the image with id_q == id_p: s1 += l(C_q), s2 += l(C_q) l(C_q), c += 1; V = max(0, s2 / c - (s1 / c) (s1 / c)).
+ *       history 0 = (colour, C_p.w), history 1 = (m1, m2, n, V).
+ *     rt_denoise_var*: rt_denoise's passes over history plane 0, with the colour term driven by the variance and the variance filtered along.  Pass k, step
+ *     s = 2^k, input colour C (history plane 0, then the previous pass's output) and variance V (history plane 1 .w, then the previous pass's): everything as
+ *     stated for rt_denoise except
+ *         wc = 1 if dl dl == 0, else max(0, 1 - (dl dl) / D),  dl = l(C_p) - l(C_q),  D = k_sigma V_p + var_floor   (replaces the k_color 4^k term);
+ *         and with every tap taken (w > 0): SV += (w w) V_q;   V_out = SV / (W W);   a miss keeps its V.
+ *     k_sigma has no unit; var_floor is in the caller's colour units squared.  Output: the filtered colour alone (.w = the history's).
+ *     RT_ERR_INVALID, output untouched: a NULL required pointer; an output that overlaps any input; width or height <= 0; max_history < 1; previous planes
+ *     without previous history or the reverse; a previous frame without `rp`; n_passes outside [1, RT_DENOISE_MAX_PASSES].  Whole frames only. --- */
+typedef struct rt_temporal_params {
+    int32_t max_history;           /* >= 1: the history length stops growing here (a = 1 / n stops shrinking)      */
+    float   alpha_min;             /* the least weight of the current frame; 0 = the running mean up to max_history */
+    float   min_normal_dot;        /* N' . N_q at least this                                                        */
+    float   max_plane_dist;        /* |N' . (P_q - P')| at most this, in scene units                                */
+} rt_temporal_params;
+typedef struct rt_motion { float rotation[9]; float translation[3]; } rt_motion;   /* previous = rotation (row-major) current + translation */
+typedef struct rt_reproject {
+    int32_t          posed;        /* 0: `camera` is the previous camera, 1: `pose` is                              */
+    rt_camera        camera;
+    rt_camera_pose   pose;
+    uint32_t         no_history_mask;
+    const rt_motion *motion;       /* RT_MAX_OBJECTS records by object id, or NULL: everything is static            */
+} rt_reproject;
+typedef struct rt_denoise_var_params {
+    int32_t n_passes;              /* 1 .. RT_DENOISE_MAX_PASSES                                                    */
+    float   k_normal, k_position, k_albedo, k_sigma, var_floor;
+} rt_denoise_var_params;
+int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, const void *prev_aov_dev, const void *prev_history_dev, int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, void *out_history_dev, void *stream);
+int rt_temporal_accumulate(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, const float *prev_aov_host, const float *prev_history_host, int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, float *out_history_host);
+int rt_denoise_var_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_denoise_var_params *vp, void *out_rgba_dev, void *stream);
+int rt_denoise_var(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_denoise_var_params *vp, float *out_rgba_host);
+
 /* --- one host process, several devices (SURVEY 8b rt_render_multi; the reference uses the implicit device 0,
  *     optimized.cu:828-856).  The frame is cut into RT_MULTI_TILE_ROWS-row tiles, tile k -> device k mod n
  *     (interleaved); the scene is replicated; every device renders its tiles; each peer pushes them over

@@ -610,6 +610,26 @@ public:
         check(rt_denoise(ctx_, color.data(), aov.data(), W, H, &dp, out.data()), "rt_denoise");
         return out;
     }
+    // Temporal accumulation (rt_temporal_accumulate): the history -- two planes of W * H float4: colour | rays, (m1, m2, history length, variance) -- of this frame
+    // from its colour and planes and the previous frame's planes and history (both empty: the first frame, rp may be nullptr).  The caller keeps the state.
+    std::vector<float> temporal_accumulate(const std::vector<float> &color, const std::vector<float> &aov, const std::vector<float> &prev_aov, const std::vector<float> &prev_history,
+                                           int W, int H, const rt_temporal_params &tp, const rt_reproject *rp) {
+        const size_t n = (size_t)W * H * 4;
+        if (color.size() != n || aov.size() < 2 * n || prev_aov.empty() != prev_history.empty() || (!prev_aov.empty() && (prev_aov.size() < 2 * n || prev_history.size() != 2 * n)))
+            throw Error(RT_ERR_INVALID, "temporal_accumulate: color is W * H float4, the planes at least two such, a history exactly two");
+        std::vector<float> out(2 * n);
+        check(rt_temporal_accumulate(ctx_, color.data(), aov.data(), prev_aov.empty() ? nullptr : prev_aov.data(), prev_history.empty() ? nullptr : prev_history.data(), W, H, &tp, rp,
+                                     out.data()), "rt_temporal_accumulate");
+        return out;
+    }
+    // ... and the a-trous filter whose colour term is measured against that history's variance (rt_denoise_var) -> the filtered colour, W * H float4
+    std::vector<float> denoise_var(const std::vector<float> &history, const std::vector<float> &aov, int W, int H, const rt_denoise_var_params &vp) {
+        const size_t n = (size_t)W * H * 4;
+        if (history.size() != 2 * n || aov.size() != 3 * n) throw Error(RT_ERR_INVALID, "denoise_var: history is two planes of W * H float4, aov three");
+        std::vector<float> out(n);
+        check(rt_denoise_var(ctx_, history.data(), aov.data(), W, H, &vp, out.data()), "rt_denoise_var");
+        return out;
+    }
 
     static rt_params params(const RenderSettings &s) {
         rt_params p{};

@@ -29,7 +29,9 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_mesh_transform_of", "rt_mesh_set_normals_of", "rt_mesh_rebuild_of", "rt_mesh_set_texture", "rt_mesh_set_texture_of", "rt_kat_surface",
            "rt_scene_get_light", "rt_scene_set_light", "rt_scene_get_sphere", "rt_scene_set_sphere", "rt_scene_move_light", "rt_scene_move_sphere", "rt_light_orbit",
            "rt_render_device_batch_scenes",
-           "rt_render_aov_device", "rt_render_aov", "rt_denoise_device", "rt_denoise"]
+           "rt_render_aov_device", "rt_render_aov", "rt_denoise_device", "rt_denoise",
+           "rt_temporal_accumulate_device", "rt_temporal_accumulate", "rt_denoise_var_device", "rt_denoise_var"]
+MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
 
@@ -142,6 +144,99 @@ def make_denoise_params(n_passes=None, k_normal=None, k_position=None, k_albedo=
     return d
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_int32), ("alpha_min", C.c_float), ("min_normal_dot", C.c_float), ("max_plane_dist", C.c_float)]
+
+
+class Motion(C.Structure):
+    _fields_ = [("rotation", C.c_float * 9), ("translation", C.c_float * 3)]
+
+
+class Reproject(C.Structure):
+    _fields_ = [("posed", C.c_int32), ("camera", Camera), ("pose", CameraPose), ("no_history_mask", C.c_uint32), ("motion", C.POINTER(Motion))]
+
+
+class DenoiseVarParams(C.Structure):
+    _fields_ = [("n_passes", C.c_int32), ("k_normal", C.c_float), ("k_position", C.c_float), ("k_albedo", C.c_float), ("k_sigma", C.c_float), ("var_floor", C.c_float)]
+
+
+# The defaults of make_temporal_params / make_denoise_var_params.  max_history 32 with alpha_min 0: the running mean of up to 32 frames;
+# min_normal_dot 0.9 and max_plane_dist 0.5 scene units: the tolerances of rt_denoise's own normal and plane terms (weight 0 at |dN|^2 = 0.5, at 2 units), tightened
+# because a wrong reuse stays in the history.  k_sigma has no unit (the tolerance in units of the pixel's own variance); var_floor 0: nothing tied to the light.
+TEMPORAL_DEFAULTS = dict(max_history=32, alpha_min=0.0, min_normal_dot=0.9, max_plane_dist=0.5)
+DENOISE_VAR_DEFAULTS = dict(n_passes=3, k_normal=2.0, k_position=0.25, k_albedo=16.0, k_sigma=16.0, var_floor=0.0)
+
+
+def make_temporal_params(max_history=None, alpha_min=None, min_normal_dot=None, max_plane_dist=None):
+    """rt_temporal_params; None = the default of TEMPORAL_DEFAULTS."""
+    given = dict(max_history=max_history, alpha_min=alpha_min, min_normal_dot=min_normal_dot, max_plane_dist=max_plane_dist)
+    t = TemporalParams()
+    for name, v in given.items():
+        setattr(t, name, TEMPORAL_DEFAULTS[name] if v is None else v)
+    return t
+
+
+def make_denoise_var_params(n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None):
+    """rt_denoise_var_params; None = the default of DENOISE_VAR_DEFAULTS.  A k_normal / k_position / k_albedo of 0 switches its term off."""
+    given = dict(n_passes=n_passes, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_sigma=k_sigma, var_floor=var_floor)
+    d = DenoiseVarParams()
+    for name, v in given.items():
+        setattr(d, name, DENOISE_VAR_DEFAULTS[name] if v is None else v)
+    return d
+
+
+def static_motion():
+    """[MAX_OBJECTS, 12] float32: the motion table in which nothing moved (rotation = identity, translation = 0); row i = object i's rotation[9] | translation[3]."""
+    m = np.zeros((MAX_OBJECTS, 12), np.float32)
+    m[:, 0] = m[:, 4] = m[:, 8] = 1
+    return m
+
+
+def motion_from_spheres(previous, current, motion=None):
+    """The motion table of spheres that were translated between two frames: previous / current = the spheres of the two frames in object order (tuples as
+    scene_upload takes them, or bare centres); translation = previous centre - current centre, in binary32.  motion: a table to fill in (default: static_motion())."""
+    m = static_motion() if motion is None else motion
+    if len(previous) != len(current) or len(current) > MAX_OBJECTS:
+        raise RtError(-1, "motion_from_spheres: two lists of the same spheres, at most %d" % MAX_OBJECTS)
+    centre = lambda s: np.asarray(s[0] if np.ndim(s[0]) else s, np.float32)
+    for i, (a, b) in enumerate(zip(previous, current)):
+        m[i, 9:] = centre(a) - centre(b)
+    return m
+
+
+def motion_from_mesh_transform(rotation, translation, object_slot, motion=None):
+    """The motion record of the mesh at object_slot after mesh_transform(rotation, translation, object_slot) (v' = R v + T): its inverse, v = R^T v' - R^T T, with
+    R^T T formed in binary32 as (R0 T.x + R3 T.y) + R6 T.z.  motion: a table to fill in (default: static_motion())."""
+    m = static_motion() if motion is None else motion
+    r = np.ascontiguousarray(rotation, np.float32).reshape(3, 3)
+    t = np.ascontiguousarray(translation, np.float32).reshape(3)
+    rt_ = np.ascontiguousarray(r.T)
+    m[object_slot, :9] = rt_.reshape(9)
+    m[object_slot, 9:] = -((rt_[:, 0] * t[0] + rt_[:, 1] * t[1]) + rt_[:, 2] * t[2])
+    return m
+
+
+def make_reproject(camera=None, pose=None, motion=None, no_history_mask=0):
+    """rt_reproject: the previous frame's camera -- pose (a CameraPose) if given, else camera = (position, fov), None = the default camera of scene_upload -- the
+    motion table ([MAX_OBJECTS, 12] as static_motion() lays it out, None = everything static) and the mask of objects that never reuse history.  The record keeps the table alive."""
+    r = Reproject()
+    if pose is not None:
+        r.posed = 1
+        r.pose = pose
+    else:
+        pos, fov = camera if camera is not None else ((0.0, 0.0, 55.0), None)
+        r.camera.position[:] = pos
+        r.camera.fov = np.float32(np.pi / 3) if fov is None else fov
+    r.no_history_mask = int(no_history_mask)
+    if motion is not None:
+        m = np.ascontiguousarray(motion, np.float32)
+        if m.shape != (MAX_OBJECTS, 12):
+            raise RtError(-1, f"make_reproject: motion {m.shape} must be [{MAX_OBJECTS}, 12]")
+        r._table = m
+        r.motion = m.ctypes.data_as(C.POINTER(Motion))
+    return r
+
+
 def make_pose(position=(0.0, 0.0, 55.0), yaw=0.0, pitch=0.3, fov=None):
     """Camera() of realtime_render.cu:805-810 (C = (0,0,55), yaw 0, pitch 0.3); Scene::pov = PI / 2 (realtime:1021)."""
     q = CameraPose()
@@ -248,6 +343,10 @@ def load():
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
     L.rt_denoise_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(DenoiseParams), vp, vp]
     L.rt_denoise.argtypes = [vp, fp3, fp3, C.c_int, C.c_int, C.POINTER(DenoiseParams), fp3]
+    L.rt_temporal_accumulate_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), vp, vp]
+    L.rt_temporal_accumulate.argtypes = [vp, fp3, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), fp3]
+    L.rt_denoise_var_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(DenoiseVarParams), vp, vp]
+    L.rt_denoise_var.argtypes = [vp, fp3, fp3, C.c_int, C.c_int, C.POINTER(DenoiseVarParams), fp3]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_host_free.argtypes = [vp]
     L.rt_kat_sphere.argtypes = [vp, fp3, C.c_int, fp3]
@@ -663,6 +762,65 @@ class Context:
         dp = make_denoise_params(n_passes, k_normal, k_position, k_albedo, k_color)
         self._check(self._L.rt_denoise_device(self._h, C.c_void_p(color_ptr), C.c_void_p(aov_ptr), int(width), int(height), C.byref(dp), C.c_void_p(out_ptr),
                                               C.c_void_p(stream) if stream else None))
+
+    # --- temporal accumulation and the variance-guided filter (rt_temporal_accumulate*, rt_denoise_var*)
+    def temporal_accumulate(self, color, aov, prev_aov=None, prev_history=None, reproject=None, params=None, out=None):
+        """rt_temporal_accumulate: color [H, W, 4] and aov [3 or 2, H, W, 4] of the current frame, prev_aov [>= 2, H, W, 4] and prev_history [2, H, W, 4] of the previous
+        one (both None: the first frame), reproject = make_reproject(...), params = make_temporal_params(...) -> the new history [2, H, W, 4]: plane 0 colour | rays,
+        plane 1 (m1, m2, history length, variance).  out: optional preallocated result; it must not share memory with an input."""
+        color = np.ascontiguousarray(color, np.float32)
+        aov = np.ascontiguousarray(aov, np.float32)
+        if color.ndim != 3 or color.shape[2] != 4 or aov.ndim != 4 or aov.shape[0] < 2 or aov.shape[1:] != color.shape:
+            raise RtError(-1, f"temporal_accumulate: color {color.shape} must be [H, W, 4] and aov {aov.shape} [3, H, W, 4] of the same frame")
+        fp = C.POINTER(C.c_float)
+        pa = ph = None
+        if prev_aov is not None:
+            prev_aov = np.ascontiguousarray(prev_aov, np.float32)
+            if prev_aov.ndim != 4 or prev_aov.shape[0] < 2 or prev_aov.shape[1:] != color.shape:
+                raise RtError(-1, f"temporal_accumulate: prev_aov {prev_aov.shape} must be [3, H, W, 4] of the same frame size")
+            pa = prev_aov.ctypes.data_as(fp)
+        if prev_history is not None:
+            prev_history = np.ascontiguousarray(prev_history, np.float32)
+            if prev_history.shape != (2,) + color.shape:
+                raise RtError(-1, f"temporal_accumulate: prev_history {prev_history.shape} must be [2, H, W, 4] of the same frame size")
+            ph = prev_history.ctypes.data_as(fp)
+        if out is None:
+            out = np.zeros((2,) + color.shape, np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (2,) + color.shape:
+            raise RtError(-1, f"temporal_accumulate: out must be a contiguous float32 array of shape {(2,) + color.shape}")
+        tp = make_temporal_params() if params is None else params
+        self._check(self._L.rt_temporal_accumulate(self._h, color.ctypes.data_as(fp), aov.ctypes.data_as(fp), pa, ph, color.shape[1], color.shape[0], C.byref(tp),
+                                                   C.byref(reproject) if reproject is not None else None, out.ctypes.data_as(fp)))
+        return out
+
+    def temporal_accumulate_device(self, color_ptr, aov_ptr, prev_aov_ptr, prev_history_ptr, width, height, out_ptr, reproject=None, params=None, stream=None):
+        """rt_temporal_accumulate_device: device pointers (0 / None for the previous pair = the first frame), asynchronous on `stream`."""
+        tp = make_temporal_params() if params is None else params
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._L.rt_temporal_accumulate_device(self._h, opt(color_ptr), opt(aov_ptr), opt(prev_aov_ptr), opt(prev_history_ptr), int(width), int(height), C.byref(tp),
+                                                          C.byref(reproject) if reproject is not None else None, opt(out_ptr), C.c_void_p(stream) if stream else None))
+
+    def denoise_var(self, history, aov, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None, out=None):
+        """rt_denoise_var: the a-trous filter over history [2, H, W, 4] (temporal_accumulate's) guided by aov [3, H, W, 4], the colour term measured against the
+        history's variance -> the filtered colour [H, W, 4].  Parameters as make_denoise_var_params."""
+        history = np.ascontiguousarray(history, np.float32)
+        aov = np.ascontiguousarray(aov, np.float32)
+        if history.ndim != 4 or history.shape[0] != 2 or history.shape[3] != 4 or aov.shape != (3,) + history.shape[1:]:
+            raise RtError(-1, f"denoise_var: history {history.shape} must be [2, H, W, 4] and aov {aov.shape} [3, H, W, 4] of the same frame")
+        if out is None:
+            out = np.zeros(history.shape[1:], np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != history.shape[1:]:
+            raise RtError(-1, f"denoise_var: out must be a contiguous float32 array of shape {history.shape[1:]}")
+        vp_ = make_denoise_var_params(n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_denoise_var(self._h, history.ctypes.data_as(fp), aov.ctypes.data_as(fp), history.shape[2], history.shape[1], C.byref(vp_), out.ctypes.data_as(fp)))
+        return out
+
+    def denoise_var_device(self, history_ptr, aov_ptr, width, height, out_ptr, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None, stream=None):
+        """rt_denoise_var_device: device pointers (a history of temporal_accumulate_device, the planes, the result), asynchronous on `stream`."""
+        vp_ = make_denoise_var_params(n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor)
+        self._check(self._L.rt_denoise_var_device(self._h, C.c_void_p(history_ptr), C.c_void_p(aov_ptr), int(width), int(height), C.byref(vp_), C.c_void_p(out_ptr),
+                                                  C.c_void_p(stream) if stream else None))
 
     def render_pose(self, params, pose):
         """One frame with realtime_render.cu's posed camera and per-sample averaging (no accumulation)."""

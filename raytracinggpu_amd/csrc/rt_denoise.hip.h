@@ -11,6 +11,11 @@
 // next to each other and the numbering keeps neighbours on one XCD, so the rest of every line they fetch is used from the same L2.  (Loading the taps directly --
 // coalesced rows through L1, no LDS -- measured 280-340 us per 1080p pass at s >= 4 against 82 us for the tiled s = 1 pass: DESIGN.md section 5.7.)
 // A tap whose object id differs is dropped before its other three records are looked at.
+//
+// rt_denoise_var[_device] is the same kernel's second instantiation (VAR): the colour term is measured against the pixel's own variance -- the history of
+// rt_temporal.hip.h carries it -- instead of k_color, and the variance is filtered along: a fifth plane of one float per pixel rides in the LDS tile (28.7 KiB),
+// read from .w of history plane 1 on pass 0 and from a float plane of the context between passes.  The plain instantiation is instruction for instruction what it
+// was before the parameter existed (its argument list is the same: the VAR arguments are a parameter pack that is empty for it).
 #pragma once
 #include "rt_div.h"
 
@@ -21,7 +26,10 @@ constexpr int kDnHalo = 2;                           // in pixels of the sub-ima
 constexpr int kDnTw = kDnTileW + 2 * kDnHalo, kDnTh = kDnTileH + 2 * kDnHalo;
 constexpr int kDnXcds = 8;                           // consecutive workgroup ids go round the XCDs
 
-struct DnParams { float k_normal, k_position, k_albedo, k_color; };   // k_color already scaled by 4^k
+struct DnParams { float k_normal, k_position, k_albedo, k_color; };   // k_color already scaled by 4^k (VAR: not read)
+// the VAR instantiation's own arguments: the variance plane read (v_stride floats apart: 4 = .w of a float4 plane, 1 = a float plane), the one written (or nullptr)
+struct DnVar { const float *v_in; float *v_out; int v_stride; float k_sigma, var_floor; };
+__device__ __forceinline__ float dn_lum(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 
 __device__ __forceinline__ float dn_sqdiff(float4 a, float4 b) {
     const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
@@ -31,10 +39,20 @@ __device__ __forceinline__ float dn_sqdiff(float4 a, float4 b) {
 __device__ __forceinline__ float dn_term(float d, float k) { return k == 0.f ? 1.f : fmaxf(0.f, 1.f - d * k); }
 
 // The pixel's filtered value.  fetch(plane, dx, dy): record `plane` (0 N|id, 1 P, 2 albedo, 3 colour) of the pixel (x + dx s, y + dy s), which lies inside the image.
-template <class Fetch>
-__device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, const DnParams &k, Fetch fetch) {
+// VAR: fetch_v(dx, dy) is that pixel's variance, kv the variance term's two constants, v_out the filtered variance.
+template <bool VAR, class Fetch, class FetchV>
+__device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, const DnParams &k, Fetch fetch, FetchV fetch_v, float k_sigma, float var_floor, float &v_out) {
     const float4 Np = fetch(0, 0, 0), Cp = fetch(3, 0, 0);
+    float lp = 0.f, D = 0.f, Dr = 0.f, Sv = 0.f;
+    bool d_fast = false;
+    if constexpr (VAR) v_out = fetch_v(0, 0);
     if (Np.w == -1.f) return Cp;                                      // a miss: nothing to guide the filter
+    if constexpr (VAR) {
+        lp = dn_lum(Cp);
+        D = k_sigma * v_out + var_floor;                              // the colour tolerance, in the colour's own units squared
+        Dr = div_refine(D, __builtin_amdgcn_rcpf(D));
+        d_fast = div_in_range(D);
+    }
     const float4 Pp = fetch(1, 0, 0), Ap = fetch(2, 0, 0);
     const float Hk[3] = {0.375f, 0.25f, 0.0625f};
     float Sx = 0.f, Sy = 0.f, Sz = 0.f, Wt = 0.f;
@@ -55,10 +73,20 @@ __device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, co
             }                                                         // (else: times exactly 1)
             if (k.k_albedo != 0.f) w = w * fmaxf(0.f, 1.f - dn_sqdiff(Ap, fetch(2, dx, dy)) * k.k_albedo);
             const float4 Cq = fetch(3, dx, dy);
-            w = w * dn_term(dn_sqdiff(Cp, Cq), k.k_color);
+            if constexpr (VAR) {
+                const float dl = lp - dn_lum(Cq), dl2 = dl * dl;
+                if (dl2 != 0.f) {                                     // (equal luminance: the term is exactly 1, no quotient is formed)
+                    float qd = div_by(dl2, D, Dr);
+                    if (!(d_fast && div_in_range(dl2))) qd = dl2 / D;
+                    w = w * fmaxf(0.f, 1.f - qd);
+                }
+            } else {
+                w = w * dn_term(dn_sqdiff(Cp, Cq), k.k_color);
+            }
             if (w > 0.f) {                                            // (false for a NaN weight: a NaN guide does not spread)
                 Sx = Sx + w * Cq.x; Sy = Sy + w * Cq.y; Sz = Sz + w * Cq.z;
                 Wt = Wt + w;
+                if constexpr (VAR) Sv = Sv + (w * w) * fetch_v(dx, dy);
             }
         }
     }
@@ -69,13 +97,25 @@ __device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, co
     if (__builtin_expect(__ballot(!fast) != 0ull, 0)) {
         if (!fast) { ox = Sx / Wt; oy = Sy / Wt; oz = Sz / Wt; }
     }
+    if constexpr (VAR) {                                              // the variance of the weighted mean: sum w^2 V / (sum w)^2
+        const float W2 = Wt * Wt;
+        float ov = div_by(Sv, W2, div_refine(W2, __builtin_amdgcn_rcpf(W2)));
+        if (!(div_in_range(Sv) && div_in_range(W2))) ov = Sv / W2;
+        v_out = ov;
+    }
     return make_float4(ox, oy, oz, Cp.w);
 }
 
 // g: the three guide planes (W * H float4 each, consecutive), C: the pass's input frame.  tiles_x, tiles_y: tiles of a sub-image; n_blocks = tiles_x * tiles_y * s * s.
+// VAR: one more argument, a DnVar (the pack is empty for the plain filter, whose argument list is the one it always had).
+template <bool VAR, class... Var>
 __global__ __launch_bounds__(kDnTileW * kDnTileH) void denoise_pass_kernel(const float4 *__restrict__ C, const float4 *__restrict__ g, float4 *__restrict__ out,
-                                                                            int W, int H, int s, int tiles_x, int tiles_y, int n_blocks, const DnParams k) {
+                                                                            int W, int H, int s, int tiles_x, int tiles_y, int n_blocks, const DnParams k, const Var... var) {
+    static_assert(sizeof...(Var) == (VAR ? 1 : 0), "the VAR instantiation takes one DnVar");
     __shared__ float4 dn_tile[4 * kDnTw * kDnTh];    // [4 planes][kDnTh rows][kDnTw]: neighbouring lanes read neighbouring 16 bytes
+    __shared__ float dn_var[VAR ? kDnTw * kDnTh : 1];                 // VAR: the variance of the same pixels
+    [[maybe_unused]] DnVar kv{nullptr, nullptr, 1, 0.f, 0.f};
+    if constexpr (VAR) kv = (var, ...);
     // workgroup id -> work item: ids b, b + 8, b + 16 .. run on one XCD and take consecutive items (the grid is padded to a multiple of kDnXcds)
     const int per_xcd = (int)gridDim.x / kDnXcds;
     const int item = ((int)blockIdx.x % kDnXcds) * per_xcd + (int)blockIdx.x / kDnXcds;
@@ -95,12 +135,16 @@ __global__ __launch_bounds__(kDnTileW * kDnTileH) void denoise_pass_kernel(const
 #pragma unroll
         for (int p = 0; p < 3; ++p) dn_tile[p * kDnTw * kDnTh + i] = g[(size_t)p * plane + q];
         dn_tile[3 * kDnTw * kDnTh + i] = C[q];
+        if constexpr (VAR) dn_var[i] = kv.v_in[q * (size_t)kv.v_stride];
     }
     __syncthreads();
     const int x = (tile_x * kDnTileW + tx) * s + phase_x, y = (tile_y * kDnTileH + ty) * s + phase_y;
     if (x >= W || y >= H) return;
     const int centre = (ty + kDnHalo) * kDnTw + tx + kDnHalo;        // a tap at (dx s, dy s) is the sub-image's neighbour (dx, dy)
-    out[(size_t)y * W + x] = dn_pixel(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; });
+    float v = 0.f;
+    out[(size_t)y * W + x] = dn_pixel<VAR>(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; },
+                                           [&](int dx, int dy) -> float { return dn_var[VAR ? centre + dy * kDnTw + dx : 0]; }, kv.k_sigma, kv.var_floor, v);
+    if constexpr (VAR) { if (kv.v_out) kv.v_out[(size_t)y * W + x] = v; }
 }
 
 }  // namespace rtk
@@ -146,7 +190,7 @@ extern "C" int rt_denoise_device(rt_ctx *ctx, const void *color_dev, const void 
         const int tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
         const int64_t n_blocks = (int64_t)tiles_x * tiles_y * s * s;
         const int64_t grid = (n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds;
-        hipLaunchKernelGGL(rtk::denoise_pass_kernel, dim3((unsigned)grid), dim3(rtk::kDnTileW * rtk::kDnTileH), 0, q, src, static_cast<const float4 *>(aov_dev), dst,
+        hipLaunchKernelGGL(rtk::denoise_pass_kernel<false>, dim3((unsigned)grid), dim3(rtk::kDnTileW * rtk::kDnTileH), 0, q, src, static_cast<const float4 *>(aov_dev), dst,
                            width, height, s, tiles_x, tiles_y, (int)n_blocks, kp);
         src = dst;
     }
@@ -169,6 +213,74 @@ extern "C" int rt_denoise(rt_ctx *ctx, const float *color_host, const float *aov
     RT_HIP(ctx, hipMemcpyAsync(base + bytes, aov_host, 3 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
     if ((rc = rt_denoise_device(ctx, base, base + bytes, width, height, dp, base + 4 * bytes, nullptr)) != RT_OK) return rc;
     RT_HIP(ctx, hipMemcpyAsync(out_host, base + 4 * bytes, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    return RT_OK;
+}
+
+// ---- rt_denoise_var*: the VAR instantiation over a history of rt_temporal_accumulate ----
+static int dnv_check(rt_ctx *ctx, const void *history, const void *aov, int width, int height, const rt_denoise_var_params *vp, const void *out) {
+    if (!history || !aov || !vp || !out) return fail(ctx, RT_ERR_INVALID, "history/aov/params/out is NULL");
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "width/height must be positive, at most 2^28 pixels");
+    if (vp->n_passes < 1 || vp->n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", vp->n_passes, RT_DENOISE_MAX_PASSES);
+    return RT_OK;
+}
+
+extern "C" int rt_denoise_var_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_denoise_var_params *vp, void *out_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = dnv_check(ctx, history_dev, aov_dev, width, height, vp, out_dev);
+    if (rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    if (dn_overlap(out_dev, bytes, history_dev, 2 * bytes) || dn_overlap(out_dev, bytes, aov_dev, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
+    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
+    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (vp->n_passes > 1) {
+        if ((rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
+        if ((rc = ensure(ctx, ctx->dnv_var[0], npix * sizeof(float))) != RT_OK) return rc;
+        if (vp->n_passes > 2 && (rc = ensure(ctx, ctx->dnv_var[1], npix * sizeof(float))) != RT_OK) return rc;
+    }
+    if (ctx->pipe.on) {                                                // (see Pipe::between)
+        if (ctx->pipe.between.size() + 2 > 64) ctx->pipe.between_overflow = true;
+        else {
+            const uint8_t *a = static_cast<const uint8_t *>(history_dev), *b = static_cast<const uint8_t *>(out_dev);
+            ctx->pipe.between.push_back({a, a + 2 * bytes, q});
+            ctx->pipe.between.push_back({b, b + bytes, q});
+        }
+    }
+    // colour as in rt_denoise_device; the variance goes from .w of history plane 1 through the context's two float planes, and the last pass writes none
+    const float4 *src = static_cast<const float4 *>(history_dev);
+    const rtk::DnParams kp{vp->k_normal, vp->k_position, vp->k_albedo, 0.f};
+    for (int k = 0; k < vp->n_passes; ++k) {
+        float4 *dst = static_cast<float4 *>(((vp->n_passes - 1 - k) & 1) ? ctx->dn_tmp.p : out_dev);
+        const int s = 1 << k;
+        rtk::DnVar kv{k == 0 ? reinterpret_cast<const float *>(static_cast<const float4 *>(history_dev) + npix) + 3 : static_cast<const float *>(ctx->dnv_var[(k - 1) & 1].p),
+                      k == vp->n_passes - 1 ? nullptr : static_cast<float *>(ctx->dnv_var[k & 1].p), k == 0 ? 4 : 1, vp->k_sigma, vp->var_floor};
+        const int tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
+        const int64_t n_blocks = (int64_t)tiles_x * tiles_y * s * s;
+        const int64_t grid = (n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds;
+        hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnVar>), dim3((unsigned)grid), dim3(rtk::kDnTileW * rtk::kDnTileH), 0, q, src, static_cast<const float4 *>(aov_dev), dst,
+                           width, height, s, tiles_x, tiles_y, (int)n_blocks, kp, kv);
+        src = dst;
+    }
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" int rt_denoise_var(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_denoise_var_params *vp, float *out_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    int rc = dnv_check(ctx, history_host, aov_host, width, height, vp, out_host);
+    if (rc != RT_OK) return rc;
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    if (dn_overlap(out_host, bytes, history_host, 2 * bytes) || dn_overlap(out_host, bytes, aov_host, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
+    // one buffer: the history's two planes, the three guide planes, the result
+    if ((rc = ensure(ctx, ctx->dn_io, 6 * bytes)) != RT_OK) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->dn_io.p);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipMemcpyAsync(base, history_host, 2 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
+    RT_HIP(ctx, hipMemcpyAsync(base + 2 * bytes, aov_host, 3 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
+    if ((rc = rt_denoise_var_device(ctx, base, base + 2 * bytes, width, height, vp, base + 5 * bytes, nullptr)) != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(out_host, base + 5 * bytes, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
     RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
     return RT_OK;
 }
