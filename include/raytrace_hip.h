@@ -524,7 +524,9 @@ int rt_progressive_frames(const rt_ctx *ctx, int *frames);
  *         w  = h wn wp wa wc, multiplied left to right; the tap counts only if w > 0 (a NaN guide does not spread): S += w C_q.rgb, W += w;
  *       out.rgb = S / W (correctly rounded; the centre tap always contributes 9/64), out.w = C_p.w.
  *     RT_ERR_INVALID, output untouched: n_passes outside [1, RT_DENOISE_MAX_PASSES], an output that overlaps the colour frame or the planes, a NULL pointer,
- *     width or height <= 0.  Whole frames only: a row share of a tiled multi-GPU frame lacks the 2 (2^n_passes - 1)-row halo -- denoise the gathered frame. --- */
+ *     width or height <= 0, 2^28 pixels or more, or a frame so thin that a pass would need 2^31 workgroups (a pass tiles each of its s x s sub-images by 32 x 8:
+ *     one or two pixels of width and more than 2^27 - 1024 rows with n_passes 8, one pixel and more than 2^28 - 512 rows with n_passes 7; rt_denoise_var likewise).
+ *     Whole frames only: a row share of a tiled multi-GPU frame lacks the 2 (2^n_passes - 1)-row halo -- denoise the gathered frame. --- */
 #define RT_DENOISE_MAX_PASSES 8
 typedef struct rt_denoise_params {
     int32_t n_passes;              /* 1 .. RT_DENOISE_MAX_PASSES                                    */
@@ -576,6 +578,14 @@ int rt_denoise(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host,
  *         wc = 1 if dl dl == 0, else max(0, 1 - (dl dl) / D),  dl = l(C_p) - l(C_q),  D = k_sigma V_p + var_floor   (replaces the k_color 4^k term);
  *         and with every tap taken (w > 0): SV += (w w) V_q;   V_out = SV / (W W);   a miss keeps its V.
  *     k_sigma has no unit; var_floor is in the caller's colour units squared.  Output: the filtered colour alone (.w = the history's).
+ *     NON-FINITE INPUTS (all three entries).  min and max above are IEEE minNum and maxNum: of a NaN and a number they give the number; comparisons with a NaN are
+ *     false.  So a NaN distance (a NaN in a normal, a position, an albedo, a variance, or in a colour while k_color != 0) makes its term 0 and the tap weigh nothing:
+ *     a NaN in a guide or a colour changes no OTHER pixel, unless k_color == 0 in rt_denoise, where a non-finite colour is summed into every pixel whose stencil
+ *     takes it (rt_denoise_var's luminance term always weighs it 0).  A pixel whose own weights all vanish -- its own N, P or A is NaN, or its colour is non-finite while k_color != 0 -- is 0 / 0 = NaN in .rgb.
+ *     A variance of NaN or 0 with var_floor 0 leaves the taps of equal luminance (the pixel itself among them); the filtered variance carries NaN and Inf on.
+ *     rt_temporal_accumulate: a NaN in N', P', gx or gy reuses no history; a NaN n_q gives n = max_history; NaN moments, or a non-finite colour among the neighbours of the spatial estimate, give V = max(0, NaN) = 0; a NaN in the
+ *     previous history's colour or moments is blended like a number and so stays in that surface point's history until its tap is rejected.  Non-finite history is
+ *     not rejected.  The sign and payload of a NaN written are not specified.
  *     RT_ERR_INVALID, output untouched: a NULL required pointer; an output that overlaps any input; width or height <= 0; max_history < 1; previous planes
  *     without previous history or the reverse; a previous frame without `rp`; n_passes outside [1, RT_DENOISE_MAX_PASSES].  Whole frames only. --- */
 typedef struct rt_temporal_params {

@@ -155,10 +155,24 @@ static bool dn_overlap(const void *a, size_t na, const void *b, size_t nb) {
     return x < y + nb && y < x + na;
 }
 
+// Does every pass's grid fit a launch (fewer than 2^31 workgroups, which is also what the kernel's int item arithmetic holds)?  Tiles round every sub-image up, so
+// thin frames cost most.  Below 2^28 pixels: the widest frame, 2^28 - 1 by 1, is ceil(2^21 / 32) x 1 tiles x 128 x 128 = 2^30 workgroups at step 128 and fits; the
+// highest, 1 by 2^28 - 1, is 1 x ceil(2^21 / 8) tiles x 128 x 128 = 2^32 there (8-row tiles against 32-pixel ones) and already 2^31 at step 64, and does not.  What
+// is refused: one or two pixels of width with n_passes 8 from 2^27 - 1023 rows on, one pixel of width with n_passes 7 from 2^28 - 511 rows on.
+static bool dn_grids_fit(int width, int height, int n_passes) {
+    for (int k = 0; k < n_passes; ++k) {
+        const int s = 1 << k;
+        const int64_t tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
+        if (tiles_x * tiles_y * s * s + rtk::kDnXcds > (int64_t)INT32_MAX) return false;
+    }
+    return true;
+}
+
 static int dn_check(rt_ctx *ctx, const void *color, const void *aov, int width, int height, const rt_denoise_params *dp, const void *out) {
     if (!color || !aov || !dp || !out) return fail(ctx, RT_ERR_INVALID, "color/aov/params/out is NULL");
     if (width <= 0 || height <= 0 || (int64_t)width * height >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "width/height must be positive, at most 2^28 pixels");
     if (dp->n_passes < 1 || dp->n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", dp->n_passes, RT_DENOISE_MAX_PASSES);
+    if (!dn_grids_fit(width, height, dp->n_passes)) return fail(ctx, RT_ERR_INVALID, "a %d x %d frame needs 2^31 or more workgroups in one of %d passes", width, height, dp->n_passes);
     return RT_OK;
 }
 
@@ -222,6 +236,7 @@ static int dnv_check(rt_ctx *ctx, const void *history, const void *aov, int widt
     if (!history || !aov || !vp || !out) return fail(ctx, RT_ERR_INVALID, "history/aov/params/out is NULL");
     if (width <= 0 || height <= 0 || (int64_t)width * height >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "width/height must be positive, at most 2^28 pixels");
     if (vp->n_passes < 1 || vp->n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", vp->n_passes, RT_DENOISE_MAX_PASSES);
+    if (!dn_grids_fit(width, height, vp->n_passes)) return fail(ctx, RT_ERR_INVALID, "a %d x %d frame needs 2^31 or more workgroups in one of %d passes", width, height, vp->n_passes);
     return RT_OK;
 }
 

@@ -1,7 +1,8 @@
 """Reference model of rt_denoise and of the pixel-centre camera ray of rt_render_aov (test infrastructure, like tests/texture_model.py).
 
 numpy binary32 throughout: every operation one rounding, in the order include/raytrace_hip.h states, so the device's frames are held to it bit for bit.  The 25
-taps of a pass are vectorised over the image; the order in which they are accumulated (dy outer, dx inner) is the contract's."""
+taps of a pass are vectorised over the image; the order in which they are accumulated (dy outer, dx inner) is the contract's.  max is maxNum (np.fmax), as the
+header states; tests/scalar_filter_reference.py is the same contract as plain loops, and tests/test_synthetic_filters_model.py holds this model to it."""
 import numpy as np
 
 F = np.float32
@@ -18,11 +19,47 @@ def _term(d, k):
     k = F(k)
     if k == 0:
         return None
-    return np.maximum(F(0), F(1) - d * k)
+    return np.fmax(F(0), F(1) - d * k)                               # maxNum, as the kernel's fmaxf: a NaN distance gives a term of 0
 
 
-def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color):
-    """One pass with step s over the colour frame C [H, W, 4], guided by aov [3, H, W, 4]; k_color already carries its 4^k."""
+DIV_LO, DIV_HI = F(2.0 ** -60), F(2.0 ** 60)                          # rt_div.h's kDivLo, kDivHi
+
+
+def div_in_range(x):
+    """rt_div.h's div_in_range: where the shared sequence is the quotient; False for NaN"""
+    with np.errstate(all="ignore"):
+        return (np.abs(x) >= DIV_LO) & (np.abs(x) <= DIV_HI)
+
+
+class TapStats:
+    """What the taps of one pass did, per pixel, for the stats= of the models: which far taps (2 s away along a row, along a column) were taken, whether a tap was dropped by its id,
+    whether taps came from both sides of a seam of the kernel's 32 x 8 tiles of a sub-image."""
+    TILE_W, TILE_H = 32, 8
+
+    def __init__(self, Hh, W, s):
+        self.s = s
+        self.ys, self.xs = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
+        self.far_x, self.far_y, self.dropped, self.own, self.other = (np.zeros((Hh, W), bool) for _ in range(5))
+
+    def tap(self, dx, dy, inside, ok, take, qx, qy):
+        if abs(dx) == 2 and dy == 0:
+            self.far_x |= take
+        if abs(dy) == 2 and dx == 0:
+            self.far_y |= take
+        self.dropped |= inside & ~ok
+        same = (qx // self.s // self.TILE_W == self.xs // self.s // self.TILE_W) & (qy // self.s // self.TILE_H == self.ys // self.s // self.TILE_H)
+        self.own |= take & same
+        self.other |= take & ~same
+
+    def counts(self, hit, fast):
+        """fast: the pixels whose every quotient took the shared sequence"""
+        n = lambda m: int((m & hit).sum())
+        return dict(far_x=n(self.far_x), far_y=n(self.far_y), dropped_by_id=n(self.dropped), across_seam=n(self.own & self.other), shared=n(fast), literal=n(~fast))
+
+
+def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color, stats=None):
+    """One pass with step s over the colour frame C [H, W, 4], guided by aov [3, H, W, 4]; k_color already carries its 4^k.  stats: an optional dict that receives,
+    under the key s, TapStats.counts of this pass."""
     C = np.ascontiguousarray(C, np.float32)
     aov = np.ascontiguousarray(aov, np.float32)
     Hh, W = C.shape[:2]
@@ -30,6 +67,7 @@ def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color):
     ys, xs = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
     S = np.zeros((Hh, W, 3), np.float32)
     Wt = np.zeros((Hh, W), np.float32)
+    ts = TapStats(Hh, W, s) if stats is not None else None
     with np.errstate(all="ignore"):
         for dy in range(-2, 3):
             for dx in range(-2, 3):
@@ -53,22 +91,29 @@ def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color):
                 if t is not None:
                     w = w * t
                 take = ok & (w > 0)                                    # False for a NaN weight
+                if ts is not None:
+                    ts.tap(dx, dy, inside, ok, take, qx, qy)
                 S = np.where(take[..., None], S + w[..., None] * Cq, S)
                 Wt = np.where(take, Wt + w, Wt)
         rgb = S / Wt[..., None]
     out = C.copy()
     hit = ID != F(-1)
     out[hit, :3] = rgb[hit]
+    if ts is not None:
+        stats[s] = ts.counts(hit, div_in_range(Wt) & div_in_range(S).all(-1))
     assert out.dtype == np.float32
     return out
 
 
-def denoise(C, aov, n_passes, k_normal, k_position, k_albedo, k_color):
-    """rt_denoise: pass k = 0 .. n_passes - 1 with step 2^k; the colour term's k is k_color 4^k."""
+def denoise(C, aov, n_passes, k_normal, k_position, k_albedo, k_color, stats=None, keep=None):
+    """rt_denoise: pass k = 0 .. n_passes - 1 with step 2^k; the colour term's k is k_color 4^k.  stats: see denoise_pass.  keep: an optional dict that receives
+    the output of every pass, keyed by the number of passes run (what a call with that n_passes gives)."""
     assert 1 <= n_passes <= 8
     out = np.ascontiguousarray(C, np.float32)
     for k in range(n_passes):
-        out = denoise_pass(out, aov, 1 << k, k_normal, k_position, k_albedo, F(k_color) * F(4 ** k))
+        out = denoise_pass(out, aov, 1 << k, k_normal, k_position, k_albedo, F(k_color) * F(4 ** k), stats=stats)
+        if keep is not None:
+            keep[k + 1] = out
     return out
 
 

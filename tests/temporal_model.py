@@ -1,11 +1,11 @@
 """Reference model of rt_temporal_accumulate and rt_denoise_var (test infrastructure, like tests/denoise_model.py).
 
 numpy binary32 throughout: every operation one rounding, in the order include/raytrace_hip.h states, so the device's histories and frames are held to it bit for bit.
-The four reprojection taps and the 25 taps of a pass are vectorised over the image; their order (the first valid tap wins; dy outer, dx inner) is the contract's."""
+The four reprojection taps and the 25 taps of a pass are vectorised over the image; their order (the first valid tap wins; dy outer, dx inner) is the contract's.  min and max are minNum and maxNum (np.fmin, np.fmax), as the header states."""
 import numpy as np
 
 import raytracinggpu_amd as rt
-from .denoise_model import H3, _sqdiff, _term
+from .denoise_model import H3, TapStats, _sqdiff, _term, div_in_range
 
 F = np.float32
 
@@ -59,9 +59,10 @@ def project(Pm, W, H, camera=None, pose=None):
 
 
 def accumulate(C, aov, prev_aov=None, prev_history=None, camera=None, pose=None, motion=None, mask=0, max_history=32, alpha_min=0.0, min_normal_dot=0.9,
-               max_plane_dist=0.5, taps=None):
+               max_plane_dist=0.5, taps=None, stats=None):
     """rt_temporal_accumulate -> the history [2, H, W, 4].  taps: an optional dict that receives `q` [H, W, 2] = the previous pixel (x, y) each pixel took its
-    history from, (-1, -1) where it took none."""
+    history from, (-1, -1) where it took none.  stats: an optional dict that receives how many pixels took each branch of the reprojection (the keys are listed in
+    tests/synthetic_planes.py, REPROJECTION_MINIMUMS) and `n`, the history lengths written, as {value: pixels}."""
     C = np.ascontiguousarray(C, np.float32)
     aov = np.ascontiguousarray(aov, np.float32)
     Hh, W = C.shape[:2]
@@ -72,6 +73,8 @@ def accumulate(C, aov, prev_aov=None, prev_history=None, camera=None, pose=None,
     col = C[..., :3].copy()
     m1, m2 = l.copy(), l * l
     took = np.full((Hh, W, 2), -1, np.int64)
+    st = {} if stats is None else stats
+    fast = np.ones((Hh, W), bool)                                      # every quotient of the pixel took rt_div.h's shared sequence
     with np.errstate(all="ignore"):
         if prev_aov is not None:
             pa = np.ascontiguousarray(prev_aov, np.float32)
@@ -79,15 +82,27 @@ def accumulate(C, aov, prev_aov=None, prev_history=None, camera=None, pose=None,
             pN, pID, pP = pa[0, ..., :3], pa[0, ..., 3], pa[1, ..., :3]
             Pm, Nm = moved(aov, motion)
             k, gx, gy = project(Pm, W, Hh, camera, pose)
+            O, _, _, bz, _, _, b = camera_constants(W, camera, pose)
             idi = np.where(hit, ID, 0).astype(np.int64)
             masked = ((int(mask) >> (idi & 31)) & 1).astype(bool)
-            cand = hit & ~masked & (k > 0) & (gx >= F(-1)) & (gx <= F(W)) & (gy >= F(-1)) & (gy <= F(Hh))
+            live = hit & ~masked
+            bounds = [gx >= F(-1), gx <= F(W), gy >= F(-1), gy <= F(Hh)]
+            cand = live & (k > 0) & bounds[0] & bounds[1] & bounds[2] & bounds[3]
+            fast &= ~live | (div_in_range(b) & div_in_range(_dot(Pm - O, bz)))
+            st["k_not_positive"] = int((live & ~(k > 0)).sum())
+            for i, name in enumerate(("gx_below", "gx_above", "gy_below", "gy_above")):
+                st[name + "_alone"] = int((live & (k > 0) & ~bounds[i] & np.logical_and.reduce([bounds[j] for j in range(4) if j != i])).sum())
+            st["gx_in_minus1_0"] = int((cand & (gx < F(0))).sum())
+            st["gx_in_wminus1_w"] = int((cand & (gx > F(W - 1))).sum())
             gx, gy = np.where(cand, gx, F(0)), np.where(cand, gy, F(0))
             fx, fy = np.floor(gx), np.floor(gy)
             ix, iy = fx.astype(np.int64), fy.astype(np.int64)
+            st["half_x"], st["half_y"] = int((cand & (gx - fx == F(0.5))).sum()), int((cand & (gy - fy == F(0.5))).sum())
             jx = np.where(gx - fx >= F(0.5), ix + 1, ix - 1)
             jy = np.where(gy - fy >= F(0.5), iy + 1, iy - 1)
             found = np.zeros((Hh, W), bool)
+            first_outside = np.zeros((Hh, W), bool)
+            alone = {name: np.zeros((Hh, W), bool) for name in ("id", "normal", "plane")}
             mpd2 = F(max_plane_dist) * F(max_plane_dist)
             for t in range(4):
                 qx, qy = (jx if t & 1 else ix), (jy if t & 2 else iy)
@@ -96,17 +111,34 @@ def accumulate(C, aov, prev_aov=None, prev_history=None, camera=None, pose=None,
                 Nq, Pq = pN[qyc, qxc], pP[qyc, qxc]
                 nd = (Nm[..., 0] * Nq[..., 0] + Nm[..., 1] * Nq[..., 1]) + Nm[..., 2] * Nq[..., 2]
                 e = (Nm[..., 0] * (Pq[..., 0] - Pm[..., 0]) + Nm[..., 1] * (Pq[..., 1] - Pm[..., 1])) + Nm[..., 2] * (Pq[..., 2] - Pm[..., 2])
-                valid = cand & ~found & inside & (pID[qyc, qxc] == ID) & (nd >= F(min_normal_dot)) & (e * e <= mpd2)
+                looked = cand & ~found & inside
+                ok_id, ok_n, ok_p = pID[qyc, qxc] == ID, nd >= F(min_normal_dot), e * e <= mpd2
+                valid = looked & ok_id & ok_n & ok_p
+                alone["id"] |= looked & ~ok_id & ok_n & ok_p
+                alone["normal"] |= looked & ok_id & ~ok_n & ok_p
+                alone["plane"] |= looked & ok_id & ok_n & ~ok_p
+                if t == 0:
+                    first_outside = cand & ~inside
                 H0, H1 = ph[0][qyc, qxc], ph[1][qyc, qxc]
-                nn = np.minimum(H1[..., 2] + F(1), F(max_history))
-                al = np.maximum(F(1) / nn, F(alpha_min))
+                nn = np.fmin(H1[..., 2] + F(1), F(max_history))       # minNum and maxNum, as the kernel's fminf and fmaxf: a NaN n_q gives max_history
+                al = np.fmax(F(1) / nn, F(alpha_min))
+                fast &= ~valid | div_in_range(nn)
                 col = np.where(valid[..., None], H0[..., :3] + al[..., None] * (C[..., :3] - H0[..., :3]), col)
                 m1 = np.where(valid, H1[..., 0] + al * (l - H1[..., 0]), m1)
                 m2 = np.where(valid, H1[..., 1] + al * (l * l - H1[..., 1]), m2)
                 n = np.where(valid, nn, n)
                 took[valid] = np.stack([qx, qy], axis=-1)[valid]
+                st[f"tap{t}"] = int(valid.sum())
+                st[f"alpha_is_alpha_min_tap{t}"] = int((valid & (F(1) / nn < F(alpha_min))).sum())
                 found |= valid
-        var = np.maximum(F(0), m2 - m1 * m1)
+            st["no_tap_valid"] = int((cand & ~found).sum())
+            st["first_outside_later_inside"] = int((first_outside & found).sum())
+            st["alpha_min_above"] = sum(st.pop(f"alpha_is_alpha_min_tap{t}") for t in range(4))
+            st["alpha_min_below"] = int(found.sum()) - st["alpha_min_above"]
+            st["reprojected"] = int(found.sum())
+            for name, m in alone.items():
+                st[name + "_alone"] = int(m.sum())
+        var = np.fmax(F(0), m2 - m1 * m1)
         # the spatial estimate while the history is short: the 5 x 5 current-frame neighbours of the same object
         ys, xs = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
         s1, s2, cnt = (np.zeros((Hh, W), np.float32) for _ in range(3))
@@ -121,7 +153,11 @@ def accumulate(C, aov, prev_aov=None, prev_history=None, camera=None, pose=None,
                 s2 = np.where(ok, s2 + lq * lq, s2)
                 cnt = np.where(ok, cnt + F(1), cnt)
         e1, e2 = s1 / cnt, s2 / cnt
-        var = np.where(n < F(4), np.maximum(F(0), e2 - e1 * e1), var)
+        var = np.where(n < F(4), np.fmax(F(0), e2 - e1 * e1), var)
+        fast &= ~(n < F(4)) | (div_in_range(s1) & div_in_range(s2))
+    st["shared"], st["literal"] = int((fast & hit).sum()), int((~fast & hit).sum())
+    vals, cts = np.unique(n[hit & (n == n)], return_counts=True)
+    st["n"] = {float(v): int(c) for v, c in zip(vals, cts)}
     out = np.zeros((2, Hh, W, 4), np.float32)
     out[0] = C
     out[0, ..., :3][hit] = col[hit]
@@ -133,8 +169,8 @@ def accumulate(C, aov, prev_aov=None, prev_history=None, camera=None, pose=None,
     return out
 
 
-def denoise_var_pass(C, V, aov, s, k_normal, k_position, k_albedo, k_sigma, var_floor):
-    """One pass with step s over colour C [H, W, 4] and variance V [H, W] -> (colour, variance)."""
+def denoise_var_pass(C, V, aov, s, k_normal, k_position, k_albedo, k_sigma, var_floor, stats=None):
+    """One pass with step s over colour C [H, W, 4] and variance V [H, W] -> (colour, variance).  stats: as denoise_model.denoise_pass."""
     C = np.ascontiguousarray(C, np.float32)
     V = np.ascontiguousarray(V, np.float32)
     aov = np.ascontiguousarray(aov, np.float32)
@@ -145,6 +181,8 @@ def denoise_var_pass(C, V, aov, s, k_normal, k_position, k_albedo, k_sigma, var_
     Wt = np.zeros((Hh, W), np.float32)
     Sv = np.zeros((Hh, W), np.float32)
     L = lum(C)
+    ts = TapStats(Hh, W, s) if stats is not None else None
+    fast = np.ones((Hh, W), bool)
     with np.errstate(all="ignore"):
         D = F(k_sigma) * V + F(var_floor)
         for dy in range(-2, 3):
@@ -166,8 +204,11 @@ def denoise_var_pass(C, V, aov, s, k_normal, k_position, k_albedo, k_sigma, var_
                     w = w * t
                 dl = L - L[qy, qx]
                 dl2 = dl * dl
-                w = np.where(dl2 == 0, w, w * np.maximum(F(0), F(1) - dl2 / D))          # equal luminance: the term is exactly 1
+                w = np.where(dl2 == 0, w, w * np.fmax(F(0), F(1) - dl2 / D))             # equal luminance: the term is exactly 1
                 take = ok & (w > 0)                                    # False for a NaN weight
+                if ts is not None:
+                    ts.tap(dx, dy, inside, ok, take, qx, qy)
+                    fast &= ~(ok & (dl2 != 0)) | (div_in_range(D) & div_in_range(dl2))
                 Cq = C[qy, qx, :3]
                 S = np.where(take[..., None], S + w[..., None] * Cq, S)
                 Wt = np.where(take, Wt + w, Wt)
@@ -176,6 +217,9 @@ def denoise_var_pass(C, V, aov, s, k_normal, k_position, k_albedo, k_sigma, var_
         vo = Sv / (Wt * Wt)
     out = C.copy()
     hit = ID != F(-1)
+    if ts is not None:
+        with np.errstate(all="ignore"):
+            stats[s] = ts.counts(hit, fast & div_in_range(Wt) & div_in_range(S).all(-1) & div_in_range(Sv) & div_in_range(Wt * Wt))
     out[hit, :3] = rgb[hit]
     Vo = V.copy()
     Vo[hit] = vo[hit]
@@ -183,11 +227,14 @@ def denoise_var_pass(C, V, aov, s, k_normal, k_position, k_albedo, k_sigma, var_
     return out, Vo
 
 
-def denoise_var(history, aov, n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor):
-    """rt_denoise_var: pass k = 0 .. n_passes - 1 with step 2^k over history plane 0, the variance starting as .w of history plane 1 -> the filtered colour."""
+def denoise_var(history, aov, n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor, stats=None, keep=None):
+    """rt_denoise_var: pass k = 0 .. n_passes - 1 with step 2^k over history plane 0, the variance starting as .w of history plane 1 -> the filtered colour.
+    stats, keep: as denoise_model.denoise."""
     assert 1 <= n_passes <= 8
     history = np.ascontiguousarray(history, np.float32)
     out, V = history[0], history[1, ..., 3]
     for k in range(n_passes):
-        out, V = denoise_var_pass(out, V, aov, 1 << k, k_normal, k_position, k_albedo, k_sigma, var_floor)
+        out, V = denoise_var_pass(out, V, aov, 1 << k, k_normal, k_position, k_albedo, k_sigma, var_floor, stats=stats)
+        if keep is not None:
+            keep[k + 1] = out
     return out
