@@ -611,6 +611,46 @@ int rt_temporal_accumulate(rt_ctx *ctx, const float *color_rgba_host, const floa
 int rt_denoise_var_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_denoise_var_params *vp, void *out_rgba_dev, void *stream);
 int rt_denoise_var(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_denoise_var_params *vp, float *out_rgba_host);
 
+/* --- the planes of the first DIFFUSE surface, and filtering irradiance instead of colour (ABI 6, additive).  The specular branches of Scene::getColor
+ *     (cpu:573-604) draw no random number -- reflection, total reflection or refraction, no Fresnel coin -- so the chain of the pixel-centre ray from the camera to
+ *     its first diffuse surface is a function of the scene alone, the colour is handed through it unchanged, and that surface's albedo factors out of the pixel:
+ *     pixel = albedo (.) (l / pi + what follows) (cpu:624, 642-644), as at a diffuse first hit.
+ *     rt_render_aov_surface*: rays, rows, stream, pipelining and errors as rt_render_aov*; p->eps and p->tri_tmin are read; sigma, num_rays, num_bounce, seed,
+ *     variant and depth_convention are ignored.  Per pixel: (O, u) = the camera ray, refr = 1, k = 0; repeat:
+ *       intersect as Scene::intersect_all does (as rt_render_aov*); a miss ends the chain as a MISS;
+ *       a hit object that is neither a mirror nor has n_in != n_out ends it DIFFUSE;
+ *       otherwise, with k == max_specular, it ends EXHAUSTED, and that specular hit is the one recorded;
+ *       otherwise the ray goes on as getColor continues it -- a mirror: O = P + eps N, u = u - (2 (u.N)) N; any other: cpu:580-604 with the ray's index refr
+ *       (total reflection, or refraction and refr = n_in or n_out) -- and k = k + 1.
+ *     N is the normal getColor shades the hit with for the segment's OWN ray, the albedo the object's or the texture's at the arriving segment's barycentrics.
+ *     Output: three planes in the layout of rt_render_aov*, so whatever reads three consecutive planes takes them as they are:
+ *       plane 0  .xyz = N of the recorded hit, .w = the PATH CODE, an exact small float: id when k == 0, else id + 16 first_id + 256 k (id: the recorded hit's
+ *                object, first_id: the camera ray's first hit; at most 4095); -1 on a miss after any number of segments.  The filters' "same object" test becomes
+ *                "same surface seen the same way": a wall seen directly, in the mirror and through the glass sphere carries three codes.  code mod 16 is the
+ *                object, floor(code / 256) the chain length;
+ *       plane 1  .xyz = the recorded hit point, .w = 1 on a hit, 0 on a miss;
+ *       plane 2  .xyz = the recorded hit's albedo, .w = 1 when the chain ended DIFFUSE -- there the albedo factors out of the pixel -- and 0 otherwise.
+ *     A miss writes zeros in every .xyz.  max_specular == 0 gives the planes of rt_render_aov* word for word except plane 2 .w.  The call runs max_specular + 1
+ *     traversal launches whatever the scene and reads nothing back in between.  max_specular outside [0, RT_MAX_SEGMENTS - 1]: RT_ERR_INVALID, output untouched.
+ *     rt_demodulate* / rt_modulate*: a colour frame of n_pixels float4 and three planes of n_pixels float4, of which plane 2 is read.  In binary32, for pixel p
+ *     with colour C and A = plane 2:
+ *       A.w != 1: out = C (with the planes of rt_render_aov*, whose plane 2 .w is 0, both calls are the identity; nothing is divided by a mirror's black albedo);
+ *       otherwise per channel c: d = max(A.c, albedo_floor) (maxNum); d > 0: demodulate gives C.c / d, correctly rounded, modulate gives C.c * d; d not > 0 (zero,
+ *       negative or NaN): the channel passes through both ways.  .w passes through.
+ *     out == color exactly (in place) is allowed.  RT_ERR_INVALID, output untouched: any other overlap of the output with an input, a NULL pointer, n_pixels <= 0
+ *     or >= 2^28.
+ *     THE PIPELINE these are for: surface planes -> rt_demodulate -> rt_denoise / rt_denoise_var with the surface planes as the guide and k_albedo = 0 ->
+ *     rt_modulate with the same planes and floor.
+ *     rt_temporal_accumulate* keeps taking the FIRST-HIT planes of rt_render_aov*: a hit point seen in a mirror does not reproject like a surface point, and
+ *     no_history_mask is indexed by object id, not by path code (reprojecting the virtual image is not provided).  The history may be accumulated on demodulated
+ *     colour as long as the planes that demodulate a frame are the surface planes of that same frame. --- */
+int rt_render_aov_surface_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, int max_specular, void *out_aov_dev, void *stream);
+int rt_render_aov_surface(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, int max_specular, float *out_aov_host);
+int rt_demodulate_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, int64_t n_pixels, float albedo_floor, void *out_rgba_dev, void *stream);
+int rt_demodulate(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, int64_t n_pixels, float albedo_floor, float *out_rgba_host);
+int rt_modulate_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, int64_t n_pixels, float albedo_floor, void *out_rgba_dev, void *stream);
+int rt_modulate(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, int64_t n_pixels, float albedo_floor, float *out_rgba_host);
+
 /* --- one host process, several devices (SURVEY 8b rt_render_multi; the reference uses the implicit device 0,
  *     optimized.cu:828-856).  The frame is cut into RT_MULTI_TILE_ROWS-row tiles, tile k -> device k mod n
  *     (interleaved); the scene is replicated; every device renders its tiles; each peer pushes them over

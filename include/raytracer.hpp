@@ -630,6 +630,28 @@ public:
         check(rt_denoise_var(ctx_, history.data(), aov.data(), W, H, &vp, out.data()), "rt_denoise_var");
         return out;
     }
+    // The same three planes for the first DIFFUSE surface of each pixel, followed through at most max_specular mirror / glass segments (rt_render_aov_surface):
+    // plane 0 .w is the path code (id, or id + 16 first_id + 256 k; -1 a miss), plane 2 .w is 1 where the chain ended diffuse and the albedo factors out of the pixel.
+    std::vector<float> render_aov_surface(const RenderSettings &s, int max_specular, const rt_camera_pose *pose = nullptr) {
+        const rt_params p = params(s);
+        std::vector<float> planes((size_t)3 * s.W * s.H * 4);
+        check(rt_render_aov_surface(ctx_, &p, pose, nullptr, max_specular, planes.data()), "rt_render_aov_surface");
+        return planes;
+    }
+    // ... and the albedo of their plane 2 divided out of a colour frame before it is filtered (rt_demodulate), multiplied back in after (rt_modulate): color = n float4,
+    // aov = three planes of n float4; the same planes and floor both ways
+    std::vector<float> demodulate(const std::vector<float> &color, const std::vector<float> &aov, float albedo_floor = 0.f) {
+        if (color.empty() || color.size() % 4 != 0 || aov.size() != 3 * color.size()) throw Error(RT_ERR_INVALID, "demodulate: color is n float4, aov three such planes");
+        std::vector<float> out(color.size());
+        check(rt_demodulate(ctx_, color.data(), aov.data(), (int64_t)(color.size() / 4), albedo_floor, out.data()), "rt_demodulate");
+        return out;
+    }
+    std::vector<float> modulate(const std::vector<float> &color, const std::vector<float> &aov, float albedo_floor = 0.f) {
+        if (color.empty() || color.size() % 4 != 0 || aov.size() != 3 * color.size()) throw Error(RT_ERR_INVALID, "modulate: color is n float4, aov three such planes");
+        std::vector<float> out(color.size());
+        check(rt_modulate(ctx_, color.data(), aov.data(), (int64_t)(color.size() / 4), albedo_floor, out.data()), "rt_modulate");
+        return out;
+    }
 
     static rt_params params(const RenderSettings &s) {
         rt_params p{};

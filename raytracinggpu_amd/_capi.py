@@ -30,7 +30,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_scene_get_light", "rt_scene_set_light", "rt_scene_get_sphere", "rt_scene_set_sphere", "rt_scene_move_light", "rt_scene_move_sphere", "rt_light_orbit",
            "rt_render_device_batch_scenes",
            "rt_render_aov_device", "rt_render_aov", "rt_denoise_device", "rt_denoise",
-           "rt_temporal_accumulate_device", "rt_temporal_accumulate", "rt_denoise_var_device", "rt_denoise_var"]
+           "rt_temporal_accumulate_device", "rt_temporal_accumulate", "rt_denoise_var_device", "rt_denoise_var",
+           "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -347,6 +348,12 @@ def load():
     L.rt_temporal_accumulate.argtypes = [vp, fp3, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), fp3]
     L.rt_denoise_var_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(DenoiseVarParams), vp, vp]
     L.rt_denoise_var.argtypes = [vp, fp3, fp3, C.c_int, C.c_int, C.POINTER(DenoiseVarParams), fp3]
+    L.rt_render_aov_surface_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), C.c_int, vp, vp]
+    L.rt_render_aov_surface.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), C.c_int, fp3]
+    L.rt_demodulate_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, vp, vp]
+    L.rt_demodulate.argtypes = [vp, fp3, fp3, C.c_int64, C.c_float, fp3]
+    L.rt_modulate_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, vp, vp]
+    L.rt_modulate.argtypes = [vp, fp3, fp3, C.c_int64, C.c_float, fp3]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_host_free.argtypes = [vp]
     L.rt_kat_sphere.argtypes = [vp, fp3, C.c_int, fp3]
@@ -821,6 +828,68 @@ class Context:
         vp_ = make_denoise_var_params(n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor)
         self._check(self._L.rt_denoise_var_device(self._h, C.c_void_p(history_ptr), C.c_void_p(aov_ptr), int(width), int(height), C.byref(vp_), C.c_void_p(out_ptr),
                                                   C.c_void_p(stream) if stream else None))
+
+    # --- the planes of the first diffuse surface, and the albedo divided out of / multiplied into a frame (rt_render_aov_surface*, rt_demodulate*, rt_modulate*)
+    def render_aov_surface(self, params, max_specular, pose=None, rows=None):
+        """rt_render_aov_surface: the planes of render_aov for the first DIFFUSE surface of each pixel, reached through at most max_specular mirror / glass
+        segments -> [3, n_rows, W, 4] float32: plane 0 (normal, path code or -1: see decode_path), plane 1 (hit point, 1 / 0), plane 2 (albedo, 1 where the chain
+        ended on a diffuse surface -- the albedo factors out of the pixel there -- else 0)."""
+        n_rows = params.height if rows is None else rows.n_rows
+        out = np.zeros((3, max(n_rows, 0), params.width, 4), np.float32)
+        self._check(self._L.rt_render_aov_surface(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(rows) if rows is not None else None,
+                                                  int(max_specular), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_aov_surface_device(self, params, max_specular, out_ptr, pose=None, rows=None, stream=None):
+        """rt_render_aov_surface_device: the same three planes into device memory (3 * n_rows * W float4), asynchronous on `stream`."""
+        whole = Rows(0, params.height, max(params.height, 1), 1)
+        self._check(self._L.rt_render_aov_surface_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(whole if rows is None else rows),
+                                                         int(max_specular), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def decode_path(code):
+        """The path code of plane 0 .w of render_aov_surface -> (id, first_id, k): the recorded object, the camera ray's first hit, the specular segments between
+        them (k == 0: first_id is id itself).  A miss (-1) -> (-1, -1, 0).  Arrays decode elementwise."""
+        c = np.asarray(code).astype(np.int64)
+        miss = c < 0
+        k = np.where(miss, 0, c // 256)
+        ident = np.where(miss, -1, c % 16)
+        first = np.where(miss, -1, np.where(k == 0, ident, (c // 16) % 16))
+        if np.ndim(code) == 0:
+            return int(ident), int(first), int(k)
+        return ident, first, k
+
+    def _modulate(self, name, color, aov, albedo_floor, out):
+        color = np.ascontiguousarray(color, np.float32)
+        aov = np.ascontiguousarray(aov, np.float32)
+        if color.ndim < 1 or color.shape[-1] != 4 or aov.shape != (3,) + color.shape:
+            raise RtError(-1, f"{name}: color {color.shape} must be [..., 4] and aov {aov.shape} [3, ..., 4] of the same frame")
+        if out is None:
+            out = np.zeros_like(color)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != color.shape:
+            raise RtError(-1, f"{name}: out must be a contiguous float32 array of shape {color.shape}")
+        fp = C.POINTER(C.c_float)
+        self._check(getattr(self._L, "rt_" + name)(self._h, color.ctypes.data_as(fp), aov.ctypes.data_as(fp), color.size // 4, float(albedo_floor), out.ctypes.data_as(fp)))
+        return out
+
+    def demodulate(self, color, aov, albedo_floor=0.0, out=None):
+        """rt_demodulate: color [H, W, 4] with the albedo of aov [3, H, W, 4] plane 2 divided out where its .w is 1 (the planes of render_aov_surface; those of
+        render_aov make it the identity) -> [H, W, 4].  A channel whose max(albedo, albedo_floor) is not > 0 passes through.  out may be color itself."""
+        return self._modulate("demodulate", color, aov, albedo_floor, out)
+
+    def modulate(self, color, aov, albedo_floor=0.0, out=None):
+        """rt_modulate: the inverse of demodulate with the same planes and floor: the albedo multiplied back in."""
+        return self._modulate("modulate", color, aov, albedo_floor, out)
+
+    def demodulate_device(self, color_ptr, aov_ptr, n_pixels, out_ptr, albedo_floor=0.0, stream=None):
+        """rt_demodulate_device: device pointers (a frame, three planes of n_pixels float4, the result -- color_ptr itself or disjoint), asynchronous on `stream`."""
+        self._check(self._L.rt_demodulate_device(self._h, C.c_void_p(color_ptr), C.c_void_p(aov_ptr), int(n_pixels), float(albedo_floor), C.c_void_p(out_ptr),
+                                                 C.c_void_p(stream) if stream else None))
+
+    def modulate_device(self, color_ptr, aov_ptr, n_pixels, out_ptr, albedo_floor=0.0, stream=None):
+        """rt_modulate_device: as demodulate_device, multiplying."""
+        self._check(self._L.rt_modulate_device(self._h, C.c_void_p(color_ptr), C.c_void_p(aov_ptr), int(n_pixels), float(albedo_floor), C.c_void_p(out_ptr),
+                                               C.c_void_p(stream) if stream else None))
 
     def render_pose(self, params, pose):
         """One frame with realtime_render.cu's posed camera and per-sample averaging (no accumulation)."""

@@ -75,8 +75,9 @@ __global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Fr
 
 }  // namespace rtk
 
-extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_aov_dev, void *stream) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+// what rt_render_aov_device and rt_render_aov_surface_device ask of their arguments alike; n: the pixels of the rows (0: nothing to do)
+static int aov_check(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const void *out_aov_dev, int &n) {
+    n = 0;
     if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
     if (!p || !rows || !out_aov_dev) return fail(ctx, RT_ERR_INVALID, "params/rows/out is NULL");
     if (p->width <= 0 || p->height <= 0) return fail(ctx, RT_ERR_INVALID, "width/height must be positive");
@@ -87,7 +88,29 @@ extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_ca
     if (last_row >= p->height) return fail(ctx, RT_ERR_INVALID, "rows reach image row %lld >= height %d", (long long)last_row, p->height);
     const int64_t n64 = (int64_t)rows->n_rows * p->width;
     if (n64 >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "at most 2^28 pixels per call");
-    const int n = (int)n64;
+    n = (int)n64;
+    return RT_OK;
+}
+// the host forms: the planes of device(rows, planes on the device) copied out; rows == NULL = the whole frame
+template <class Device>
+static int aov_to_host(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, float *out_aov_host, Device device) {
+    RT_OWN_STREAM(ctx);
+    if (!p || !out_aov_host) return fail(ctx, RT_ERR_INVALID, "params/out is NULL");
+    const rt_rows whole{0, p->height, p->height > 0 ? p->height : 1, 1};
+    if (!rows) rows = &whole;
+    const size_t bytes = 3 * (size_t)(rows->n_rows > 0 ? rows->n_rows : 0) * (p->width > 0 ? p->width : 0) * sizeof(float4);
+    int rc = ensure(ctx, ctx->aov_out, bytes);
+    if (rc != RT_OK) return rc;
+    if ((rc = device(rows, ctx->aov_out.p)) != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(out_aov_host, ctx->aov_out.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    return RT_OK;
+}
+
+extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_aov_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int n;
+    if (int rc = aov_check(ctx, p, rows, out_aov_dev, n); rc != RT_OK || n == 0) return rc;
     const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
     if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -111,15 +134,5 @@ extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_ca
 
 extern "C" int rt_render_aov(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, float *out_aov_host) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (!p || !out_aov_host) return fail(ctx, RT_ERR_INVALID, "params/out is NULL");
-    const rt_rows whole{0, p->height, p->height > 0 ? p->height : 1, 1};
-    if (!rows) rows = &whole;
-    const size_t bytes = 3 * (size_t)(rows->n_rows > 0 ? rows->n_rows : 0) * (p->width > 0 ? p->width : 0) * sizeof(float4);
-    int rc = ensure(ctx, ctx->aov_out, bytes);
-    if (rc != RT_OK) return rc;
-    if ((rc = rt_render_aov_device(ctx, p, pose, rows, ctx->aov_out.p, nullptr)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_aov_host, ctx->aov_out.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return aov_to_host(ctx, p, rows, out_aov_host, [&](const rt_rows *r, void *dev) { return rt_render_aov_device(ctx, p, pose, r, dev, nullptr); });
 }

@@ -107,7 +107,7 @@ int rt_ctx_destroy(rt_ctx *ctx) {
     for (DevBuf &b : ctx->tex_img) b.release();
     ctx->wfQR.release(); ctx->accum.release(); ctx->dbgbuf.release(); ctx->batch_dev.release(); ctx->anim_dev.release();
     ctx->pathSamp.release(); ctx->pathT.release(); ctx->tidx_up.release();
-    ctx->aovM.release(); ctx->aovQR.release(); ctx->aov_out.release(); ctx->dn_tmp.release(); ctx->dn_io.release(); ctx->dnv_var[0].release(); ctx->dnv_var[1].release(); ctx->tp_io.release();
+    ctx->aovM.release(); ctx->aovQR.release(); ctx->aov_out.release(); ctx->aov_state.release(); ctx->dn_tmp.release(); ctx->dn_io.release(); ctx->dnv_var[0].release(); ctx->dnv_var[1].release(); ctx->tp_io.release();
     for (DevBuf *b : {&ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp, &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev}) b->release();
     for (hipEvent_t &e : ctx->ev_trav) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t &e : ctx->ev_adv) if (e) (void)hipEventDestroy(e);
@@ -482,7 +482,7 @@ int rt_ctx_selfcheck(rt_ctx *ctx) {
                             &ctx->wfQR, &ctx->pathSamp, &ctx->pathT, &ctx->accum, &ctx->left_dev, &ctx->lvl_nodes, &ctx->lvl_off, &ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp,
                             &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev,
                             &ctx->slot_rgba[0], &ctx->slot_rgba[1], &ctx->slot_rgb8[0], &ctx->slot_rgb8[1], &ctx->wfALB, &ctx->tex_uv, &ctx->tex_table,
-                            &ctx->aovM, &ctx->aovQR, &ctx->aov_out, &ctx->dn_tmp, &ctx->dn_io, &ctx->dnv_var[0], &ctx->dnv_var[1], &ctx->tp_io};
+                            &ctx->aovM, &ctx->aovQR, &ctx->aov_out, &ctx->aov_state, &ctx->dn_tmp, &ctx->dn_io, &ctx->dnv_var[0], &ctx->dnv_var[1], &ctx->tp_io};
     for (const DevBuf *b : bufs) {
         if (!b->p) continue;
         hipPointerAttribute_t at{};
@@ -566,5 +566,7 @@ int rt_get_stats(rt_ctx *ctx, rt_stats *stats) {
 #include "rt_kat.hip.h"
 #include "rt_trace.hip.h"
 #include "rt_aov.hip.h"
+#include "rt_aov_surface.hip.h"
 #include "rt_denoise.hip.h"
 #include "rt_temporal.hip.h"
+#include "rt_demodulate.hip.h"

@@ -164,6 +164,7 @@ struct rt_ctx {
     DevBuf batch_dev;                                               // rt_render_device_batch: the frames' descriptors, one copy per sub-frame
     DevBuf anim_dev;                                                // rt_render_device_batch_scenes: the frames' lights and sphere poses (rtk::AnimFrame), one copy per sub-frame
     DevBuf aovM, aovQR, aov_out;                                    // rt_render_aov*: traversal results and ray queue of its own (the render path's are never touched), the host form's planes
+    DevBuf aov_state;                                               // rt_render_aov_surface*: one record per pixel between the rounds of its chain (rtk::SurfState)
     DevBuf dn_tmp, dn_io;                                           // rt_denoise*: the ping-pong frame of the passes; the host form's colour + planes + result
     DevBuf dnv_var[2], tp_io;                                       // rt_denoise_var*: the variance planes between passes; rt_temporal_accumulate: the host form's nine planes
     DevBuf accum;                                                   // progressive mode: sum of the frames so far (float4 per pixel)

@@ -70,32 +70,47 @@ __global__ __launch_bounds__(256) void kat_surface_kernel(const Scene sc, const 
 // n ray slots through the traversal launch of a frame of a default context (plan_trav without RT_TRAVQ_LDS staging, one sub-frame) on stream q, with the traversal results
 // in bufM and the queue in bufQR.  emit(st, grid, block): the launch that writes every one of the 2 st.n_paths slots' records and M entries (trace_emit_kernel's contract).
 // M: bits(t) << 32 | triangle (visit order) per ray, WF_NOHIT if none.  variant: wavefront_queue (wf_travq) or wavefront (wf_trav).
+// TraceLaunch: that launch, kept, for a caller that rewrites the records in place and traverses them again (trace_again: rt_render_aov_surface's rounds).
+struct TraceLaunch { TravPlan t; rtk::Frame fr; rtk::WfState st; int64_t tblocks; };
 template <class Emit>
-static int trace_queue(rt_ctx *ctx, int n, float tri_tmin, int variant, hipStream_t q, DevBuf &bufM, DevBuf &bufQR, unsigned long long *&M, Emit emit) {
+static int trace_queue(rt_ctx *ctx, int n, float tri_tmin, int variant, hipStream_t q, DevBuf &bufM, DevBuf &bufQR, TraceLaunch &tl, Emit emit) {
     const rtk::Scene &sc = ctx->scene;
     if (variant == RT_VARIANT_WAVEFRONT_QUEUE && (sc.n_nodes + 2 >= (1 << rtk::kQNodeBits) || !ctx->travq_ok)) variant = RT_VARIANT_WAVEFRONT;
     const Knobs &kn = ctx->knobs;
     int rc;
-    rtk::Frame fr{};
+    rtk::Frame &fr = tl.fr;
+    fr = rtk::Frame{};
     fr.tri_tmin = tri_tmin; fr.segs = 1; fr.spp = 1; fr.W = 1; fr.H = 1; fr.n_rows = 1; fr.tile_rows = 1; fr.tile_step = 1; fr.out_tile_step = 1;
     Variant v{};
     v.variant = v.asked = variant;
-    TravPlan t;
+    TravPlan &t = tl.t;
     if ((rc = plan_trav(ctx, v, false, 0, t)) != RT_OK) return rc;
-    rtk::WfState st{};
+    rtk::WfState &st = tl.st;
+    st = rtk::WfState{};
     st.n_paths = ((n + 1) / 2 + 1) / 2 * 2;                           // 2 n_paths ray slots >= n, a multiple of 4
     st.n_px = st.n_paths; st.tiles_x = 1;
-    const int64_t tblocks = wf_geometry(kn, ctx->n_cus, t.bpc, 1, t.wpb, t.queue, st);
+    const int64_t tblocks = tl.tblocks = wf_geometry(kn, ctx->n_cus, t.bpc, 1, t.wpb, t.queue, st);
     const size_t q_slots = (size_t)st.slots_per_block * (size_t)tblocks;
     if ((rc = ensure(ctx, bufM, 2 * (size_t)st.n_paths * 8)) != RT_OK || (rc = ensure(ctx, bufQR, q_slots * 32)) != RT_OK) return rc;
     RT_HIP(ctx, hipMemsetAsync(bufQR.p, 0, q_slots * 32, q));        // padding slots carry no ray
     st.QR = static_cast<float4 *>(bufQR.p);
-    st.M = M = static_cast<unsigned long long *>(bufM.p);
+    st.M = static_cast<unsigned long long *>(bufM.p);
     st.init_m = t.queue ? 0 : 1;
     st.epoch = 0; st.nonce = 0;
     emit(st, dim3((unsigned)((2 * st.n_paths + 255) / 256)), dim3(256));
     if (t.have_mesh) launch_trav(t, tblocks, q, sc, fr, st);
     return RT_OK;
+}
+template <class Emit>
+static int trace_queue(rt_ctx *ctx, int n, float tri_tmin, int variant, hipStream_t q, DevBuf &bufM, DevBuf &bufQR, unsigned long long *&M, Emit emit) {
+    TraceLaunch tl;
+    const int rc = trace_queue(ctx, n, tri_tmin, variant, q, bufM, bufQR, tl, emit);
+    if (rc == RT_OK) M = tl.st.M;
+    return rc;
+}
+// the traversal launch of tl once more, over the records its queue holds now (every ray's M entry initialised by whoever wrote them, as an emitter does)
+static void trace_again(rt_ctx *ctx, const TraceLaunch &tl, hipStream_t q) {
+    if (tl.t.have_mesh) launch_trav(tl.t, tl.tblocks, q, ctx->scene, tl.fr, tl.st);
 }
 
 // The caller's rays (din: n x 6 floats on the device) through the production traversal of `variant`; M: bits(t) << 32 | triangle (visit order) per ray, WF_NOHIT if none
