@@ -733,6 +733,28 @@ class Context:
         return out
 
     # --- first-hit feature buffers and the edge-avoiding filter they guide (rt_render_aov*, rt_denoise*)
+    @staticmethod
+    def _f32(a, shape_ok, message):
+        """a as a contiguous float32 array whose shape passes shape_ok, else RtError(-1, message)"""
+        a = np.ascontiguousarray(a, np.float32)
+        if not shape_ok(a.shape):
+            raise RtError(-1, message)
+        return a
+
+    @staticmethod
+    def _out(name, out, shape):
+        """the optional preallocated result of `name`: a contiguous float32 array of `shape` (None: a new one, zeroed)"""
+        if out is None:
+            return np.zeros(shape, np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != shape:
+            raise RtError(-1, f"{name}: out must be a contiguous float32 array of shape {shape}")
+        return out
+
+    @staticmethod
+    def _rows_or_whole(params, rows):
+        """rows, or the Rows of the whole frame: what the *_aov*_device entries take when the caller names none"""
+        return Rows(0, params.height, max(params.height, 1), 1) if rows is None else rows
+
     def render_aov(self, params, pose=None, rows=None):
         """rt_render_aov: the G-buffer of the pixel-centre camera rays -> [3, n_rows, W, 4] float32: plane 0 (normal, object id or -1), plane 1 (hit point, 1 / 0),
         plane 2 (albedo, 0).  pose: a CameraPose (None = the uploaded camera); rows: a Rows (None = the whole frame).  The first hit, whatever its material."""
@@ -744,21 +766,16 @@ class Context:
 
     def render_aov_device(self, params, out_ptr, pose=None, rows=None, stream=None):
         """rt_render_aov_device: the same three planes into device memory (3 * n_rows * W float4), asynchronous on `stream`."""
-        whole = Rows(0, params.height, max(params.height, 1), 1)
-        self._check(self._L.rt_render_aov_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(whole if rows is None else rows),
+        self._check(self._L.rt_render_aov_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(self._rows_or_whole(params, rows)),
                                                  C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
     def denoise(self, color, aov, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_color=None, out=None):
         """rt_denoise: the a-trous filter over color [H, W, 4] guided by aov [3, H, W, 4] (render_aov of the same frame) -> [H, W, 4].  Parameters as
         make_denoise_params.  out: optional preallocated result; it must not share memory with an input."""
-        color = np.ascontiguousarray(color, np.float32)
-        aov = np.ascontiguousarray(aov, np.float32)
-        if color.ndim != 3 or color.shape[2] != 4 or aov.shape != (3,) + color.shape:
-            raise RtError(-1, f"denoise: color {color.shape} must be [H, W, 4] and aov {aov.shape} [3, H, W, 4] of the same frame")
-        if out is None:
-            out = np.zeros_like(color)
-        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != color.shape:
-            raise RtError(-1, f"denoise: out must be a contiguous float32 array of shape {color.shape}")
+        bad = f"denoise: color {np.shape(color)} must be [H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
+        color = self._f32(color, lambda s: len(s) == 3 and s[2] == 4, bad)
+        aov = self._f32(aov, lambda s: s == (3,) + color.shape, bad)
+        out = self._out("denoise", out, color.shape)
         dp = make_denoise_params(n_passes, k_normal, k_position, k_albedo, k_color)
         fp = C.POINTER(C.c_float)
         self._check(self._L.rt_denoise(self._h, color.ctypes.data_as(fp), aov.ctypes.data_as(fp), color.shape[1], color.shape[0], C.byref(dp), out.ctypes.data_as(fp)))
@@ -775,26 +792,20 @@ class Context:
         """rt_temporal_accumulate: color [H, W, 4] and aov [3 or 2, H, W, 4] of the current frame, prev_aov [>= 2, H, W, 4] and prev_history [2, H, W, 4] of the previous
         one (both None: the first frame), reproject = make_reproject(...), params = make_temporal_params(...) -> the new history [2, H, W, 4]: plane 0 colour | rays,
         plane 1 (m1, m2, history length, variance).  out: optional preallocated result; it must not share memory with an input."""
-        color = np.ascontiguousarray(color, np.float32)
-        aov = np.ascontiguousarray(aov, np.float32)
-        if color.ndim != 3 or color.shape[2] != 4 or aov.ndim != 4 or aov.shape[0] < 2 or aov.shape[1:] != color.shape:
-            raise RtError(-1, f"temporal_accumulate: color {color.shape} must be [H, W, 4] and aov {aov.shape} [3, H, W, 4] of the same frame")
+        bad = f"temporal_accumulate: color {np.shape(color)} must be [H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
+        color = self._f32(color, lambda s: len(s) == 3 and s[2] == 4, bad)
+        planes_ok = lambda s: len(s) == 4 and s[0] >= 2 and s[1:] == color.shape                     # two planes or more of this frame's size
+        aov = self._f32(aov, planes_ok, bad)
         fp = C.POINTER(C.c_float)
         pa = ph = None
         if prev_aov is not None:
-            prev_aov = np.ascontiguousarray(prev_aov, np.float32)
-            if prev_aov.ndim != 4 or prev_aov.shape[0] < 2 or prev_aov.shape[1:] != color.shape:
-                raise RtError(-1, f"temporal_accumulate: prev_aov {prev_aov.shape} must be [3, H, W, 4] of the same frame size")
+            prev_aov = self._f32(prev_aov, planes_ok, f"temporal_accumulate: prev_aov {np.shape(prev_aov)} must be [3, H, W, 4] of the same frame size")
             pa = prev_aov.ctypes.data_as(fp)
         if prev_history is not None:
-            prev_history = np.ascontiguousarray(prev_history, np.float32)
-            if prev_history.shape != (2,) + color.shape:
-                raise RtError(-1, f"temporal_accumulate: prev_history {prev_history.shape} must be [2, H, W, 4] of the same frame size")
+            prev_history = self._f32(prev_history, lambda s: s == (2,) + color.shape,
+                                     f"temporal_accumulate: prev_history {np.shape(prev_history)} must be [2, H, W, 4] of the same frame size")
             ph = prev_history.ctypes.data_as(fp)
-        if out is None:
-            out = np.zeros((2,) + color.shape, np.float32)
-        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != (2,) + color.shape:
-            raise RtError(-1, f"temporal_accumulate: out must be a contiguous float32 array of shape {(2,) + color.shape}")
+        out = self._out("temporal_accumulate", out, (2,) + color.shape)
         tp = make_temporal_params() if params is None else params
         self._check(self._L.rt_temporal_accumulate(self._h, color.ctypes.data_as(fp), aov.ctypes.data_as(fp), pa, ph, color.shape[1], color.shape[0], C.byref(tp),
                                                    C.byref(reproject) if reproject is not None else None, out.ctypes.data_as(fp)))
@@ -810,14 +821,10 @@ class Context:
     def denoise_var(self, history, aov, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None, out=None):
         """rt_denoise_var: the a-trous filter over history [2, H, W, 4] (temporal_accumulate's) guided by aov [3, H, W, 4], the colour term measured against the
         history's variance -> the filtered colour [H, W, 4].  Parameters as make_denoise_var_params."""
-        history = np.ascontiguousarray(history, np.float32)
-        aov = np.ascontiguousarray(aov, np.float32)
-        if history.ndim != 4 or history.shape[0] != 2 or history.shape[3] != 4 or aov.shape != (3,) + history.shape[1:]:
-            raise RtError(-1, f"denoise_var: history {history.shape} must be [2, H, W, 4] and aov {aov.shape} [3, H, W, 4] of the same frame")
-        if out is None:
-            out = np.zeros(history.shape[1:], np.float32)
-        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != history.shape[1:]:
-            raise RtError(-1, f"denoise_var: out must be a contiguous float32 array of shape {history.shape[1:]}")
+        bad = f"denoise_var: history {np.shape(history)} must be [2, H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
+        history = self._f32(history, lambda s: len(s) == 4 and s[0] == 2 and s[3] == 4, bad)
+        aov = self._f32(aov, lambda s: s == (3,) + history.shape[1:], bad)
+        out = self._out("denoise_var", out, history.shape[1:])
         vp_ = make_denoise_var_params(n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor)
         fp = C.POINTER(C.c_float)
         self._check(self._L.rt_denoise_var(self._h, history.ctypes.data_as(fp), aov.ctypes.data_as(fp), history.shape[2], history.shape[1], C.byref(vp_), out.ctypes.data_as(fp)))
@@ -842,8 +849,7 @@ class Context:
 
     def render_aov_surface_device(self, params, max_specular, out_ptr, pose=None, rows=None, stream=None):
         """rt_render_aov_surface_device: the same three planes into device memory (3 * n_rows * W float4), asynchronous on `stream`."""
-        whole = Rows(0, params.height, max(params.height, 1), 1)
-        self._check(self._L.rt_render_aov_surface_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(whole if rows is None else rows),
+        self._check(self._L.rt_render_aov_surface_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(self._rows_or_whole(params, rows)),
                                                          int(max_specular), C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
     @staticmethod
@@ -860,14 +866,10 @@ class Context:
         return ident, first, k
 
     def _modulate(self, name, color, aov, albedo_floor, out):
-        color = np.ascontiguousarray(color, np.float32)
-        aov = np.ascontiguousarray(aov, np.float32)
-        if color.ndim < 1 or color.shape[-1] != 4 or aov.shape != (3,) + color.shape:
-            raise RtError(-1, f"{name}: color {color.shape} must be [..., 4] and aov {aov.shape} [3, ..., 4] of the same frame")
-        if out is None:
-            out = np.zeros_like(color)
-        if out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != color.shape:
-            raise RtError(-1, f"{name}: out must be a contiguous float32 array of shape {color.shape}")
+        bad = f"{name}: color {np.shape(color)} must be [..., 4] and aov {np.shape(aov)} [3, ..., 4] of the same frame"
+        color = self._f32(color, lambda s: len(s) >= 1 and s[-1] == 4, bad)
+        aov = self._f32(aov, lambda s: s == (3,) + color.shape, bad)
+        out = self._out(name, out, color.shape)
         fp = C.POINTER(C.c_float)
         self._check(getattr(self._L, "rt_" + name)(self._h, color.ctypes.data_as(fp), aov.ctypes.data_as(fp), color.size // 4, float(albedo_floor), out.ctypes.data_as(fp)))
         return out

@@ -1,5 +1,6 @@
 // rt_aov.hip.h -- rt_render_aov[_device]: the first-hit feature buffers (G-buffer) of a frame, for the edge-avoiding filter of rt_denoise.hip.h.
-// Included at the end of rt_capi.hip, after rt_trace.hip.h (same translation unit: it runs the traversal launch of rt_trace_rays, trace_queue).
+// Included at the end of rt_capi.hip, after rt_trace.hip.h (same translation unit: it runs the traversal launch of rt_trace_rays, trace_queue; the host half uses
+// rt_host_post.hip.h).  The device functions and the host prologue here are rt_aov_surface.hip.h's too.
 //
 // One ray per pixel of the rows: the pixel-centre camera ray (camera_dir with sigma = 0: no sample key is read), intersected with the scene as
 // Scene::intersect_all does (cpu_launcher.cpp:545-564): every sphere by the sphere search of wf_advance (spheres_near2), the meshes by the production
@@ -15,6 +16,32 @@ __device__ __forceinline__ void aov_ray(const Scene &sc, const Frame &fr, int r,
     const int lrow = r / fr.W, px = r - lrow * fr.W;
     O = mk(sc.camx, sc.camy, sc.camz);
     u = camera_dir(fr, O, fr.z, px, image_row(fr, lrow), 0u);      // fr.sigma == 0: the key is not read
+}
+
+// Closes the query of ray (O, u) as wf_advance closes a continuation ray's: every sphere by spheres_near2, m the traversal's result word for the meshes, the two joined
+// by mesh_beats_sphere.  obj < 0: a miss; tri < 0: a sphere.
+struct AovHit { float t; int obj, tri; };
+__device__ __forceinline__ AovHit aov_close_query(const Scene &sc, f3 O, f3 u, unsigned long long m) {
+    SphereNear hy, hx;
+    spheres_near2(sc, O, u, true, u, false, hy, hx);
+    AovHit h{hy.t, hy.obj, -1};
+    if (m != WF_NOHIT) {
+        const float tm = __uint_as_float((unsigned int)(m >> 32));
+        const int mobj = mesh_obj_of_tri(sc, (int)(unsigned int)m);
+        if (mesh_beats_sphere(h.t, h.obj, tm, mobj)) { h.t = tm; h.obj = mobj; h.tri = (int)(unsigned int)m; }
+    }
+    return h;
+}
+
+// the albedo the planes record for hit h of ray (O, u): the object's, or tex_albedo's on a textured mesh (bary: hit_normal's, where it made them)
+__device__ __forceinline__ f3 aov_albedo(const Scene &sc, const TexScene &ts, const AovHit &h, f3 O, f3 u, Bary bary, bool have_bary) {
+    if (h.tri >= 0 && ((ts.mask >> h.obj) & 1)) {
+        if (!have_bary) bary = tri_bary(sc, h.tri, O, u);
+        float2 uv;
+        return tex_albedo(sc, ts, h.obj, h.tri, bary, uv);
+    }
+    const Material mt = material_of(sc, h.obj);
+    return mk(mt.ar, mt.ag, mt.ab);
 }
 
 // trace_emit_kernel with the rays made here: one lane per ray slot pair, rays r < n are the pixels', the rest of the 2 n_paths slots carry no ray
@@ -39,32 +66,15 @@ __global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Fr
     if (r >= n) return;
     f3 O, u;
     aov_ray(sc, fr, r, O, u);
-    SphereNear hy, hx;
-    spheres_near2(sc, O, u, true, u, false, hy, hx);
-    float t_min = hy.t;
-    int win = hy.obj, tri_win = -1;
-    const unsigned long long m = M[r];
-    if (m != WF_NOHIT) {
-        const float tm = __uint_as_float((unsigned int)(m >> 32));
-        const int mobj = mesh_obj_of_tri(sc, (int)(unsigned int)m);
-        if (mesh_beats_sphere(t_min, win, tm, mobj)) { t_min = tm; win = mobj; tri_win = (int)(unsigned int)m; }
-    }
+    const AovHit h = aov_close_query(sc, O, u, M[r]);
     float4 o0 = make_float4(0.f, 0.f, 0.f, -1.f), o1 = make_float4(0.f, 0.f, 0.f, 0.f), o2 = o1;
-    if (win >= 0) {
-        const f3 P = O + t_min * u;                                   // cpu:560
+    if (h.obj >= 0) {
+        const f3 P = O + h.t * u;                                     // cpu:560
         Bary bary{0.f, 0.f, 0.f};
         bool have_bary = false;
-        const f3 N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
-        f3 alb;
-        if (tri_win >= 0 && ((ts.mask >> win) & 1)) {
-            if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
-            float2 uv;
-            alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
-        } else {
-            const Material mt = material_of(sc, win);
-            alb = mk(mt.ar, mt.ag, mt.ab);
-        }
-        o0 = make_float4(N.x, N.y, N.z, (float)win);
+        const f3 N = hit_normal(sc, h.obj, h.tri, O, u, P, bary, have_bary);
+        const f3 alb = aov_albedo(sc, ts, h, O, u, bary, have_bary);
+        o0 = make_float4(N.x, N.y, N.z, (float)h.obj);
         o1 = make_float4(P.x, P.y, P.z, 1.f);
         o2 = make_float4(alb.x, alb.y, alb.z, 0.f);
     }
@@ -87,7 +97,7 @@ static int aov_check(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const
     const int64_t last_row = rows->row0 + (last / rows->tile_rows) * rows->tile_rows * (int64_t)rows->tile_step + (last % rows->tile_rows);
     if (last_row >= p->height) return fail(ctx, RT_ERR_INVALID, "rows reach image row %lld >= height %d", (long long)last_row, p->height);
     const int64_t n64 = (int64_t)rows->n_rows * p->width;
-    if (n64 >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "at most 2^28 pixels per call");
+    if (n64 >= kPostMaxPixels) return fail(ctx, RT_ERR_INVALID, "at most 2^28 pixels per call");
     n = (int)n64;
     return RT_OK;
 }
@@ -99,35 +109,33 @@ static int aov_to_host(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, flo
     const rt_rows whole{0, p->height, p->height > 0 ? p->height : 1, 1};
     if (!rows) rows = &whole;
     const size_t bytes = 3 * (size_t)(rows->n_rows > 0 ? rows->n_rows : 0) * (p->width > 0 ? p->width : 0) * sizeof(float4);
-    int rc = ensure(ctx, ctx->aov_out, bytes);
-    if (rc != RT_OK) return rc;
-    if ((rc = device(rows, ctx->aov_out.p)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_aov_host, ctx->aov_out.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return staged(ctx, {}, 0, bytes, out_aov_host, [&](uint8_t *d) { return device(rows, d); });
+}
+
+// What the two device entries do alike, up to the camera rays' traversal: the argument checks (n == 0 with RT_OK: nothing to do, nothing was issued), the stream,
+// aov_state for state_bytes per pixel (rt_render_aov_surface's record between its rounds; 0: none), the frame of a render call with these parameters (make_frame: camera distance, pose, rows) without the jitter, the pipelining note -- a pipelined frame must not start
+// behind the write of the planes -- and aov_emit_kernel through the queue launch.
+struct AovCall { int n; hipStream_t q; rtk::Scene scn; rtk::Frame fr; TraceLaunch tl; };
+static int aov_begin(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_aov_dev, void *stream, size_t state_bytes, AovCall &a) {
+    int rc = aov_check(ctx, p, rows, out_aov_dev, a.n);
+    if (rc != RT_OK || a.n == 0) return rc;
+    if ((rc = call_stream(ctx, stream, a.q)) != RT_OK) return rc;
+    if (state_bytes && (rc = ensure(ctx, ctx->aov_state, (size_t)a.n * state_bytes)) != RT_OK) return rc;
+    Chunk c{p, rows, a.q, nullptr, nullptr, false, 1, 1, {}, {}, nullptr};
+    make_frame(ctx, out_aov_dev, pose, c);
+    c.fr.sigma = 0.f;
+    a.scn = c.scn; a.fr = c.fr;
+    note_between(ctx, a.q, {{out_aov_dev, 3 * (size_t)a.n * sizeof(float4)}});
+    return trace_queue(ctx, a.n, p->tri_tmin, RT_VARIANT_WAVEFRONT_QUEUE, a.q, ctx->aovM, ctx->aovQR, a.tl, [&](const rtk::WfState &st, dim3 g, dim3 b) {
+        hipLaunchKernelGGL(rtk::aov_emit_kernel, g, b, 0, a.q, a.scn, a.fr, st, a.n);
+    });
 }
 
 extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_aov_dev, void *stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    int n;
-    if (int rc = aov_check(ctx, p, rows, out_aov_dev, n); rc != RT_OK || n == 0) return rc;
-    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    // the frame of a render call with these parameters (make_frame: camera distance, pose, rows), without the jitter
-    Chunk c{p, rows, q, nullptr, nullptr, false, 1, 1, {}, {}, nullptr};
-    make_frame(ctx, out_aov_dev, pose, c);
-    c.fr.sigma = 0.f;
-    if (ctx->pipe.on) {                                                // (see Pipe::between: a pipelined frame must not start behind this write)
-        if (ctx->pipe.between.size() >= 64) ctx->pipe.between_overflow = true;
-        else { const uint8_t *a = static_cast<const uint8_t *>(out_aov_dev); ctx->pipe.between.push_back({a, a + 3 * (size_t)n * sizeof(float4), q}); }
-    }
-    unsigned long long *M = nullptr;
-    int rc = trace_queue(ctx, n, p->tri_tmin, RT_VARIANT_WAVEFRONT_QUEUE, q, ctx->aovM, ctx->aovQR, M, [&](const rtk::WfState &st, dim3 g, dim3 b) {
-        hipLaunchKernelGGL(rtk::aov_emit_kernel, g, b, 0, q, c.scn, c.fr, st, n);
-    });
-    if (rc != RT_OK) return rc;
-    hipLaunchKernelGGL(rtk::aov_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, c.scn, c.fr, tex_scene(ctx), M, n, static_cast<float4 *>(out_aov_dev));
+    AovCall a;
+    if (int rc = aov_begin(ctx, p, pose, rows, out_aov_dev, stream, 0, a); rc != RT_OK || a.n == 0) return rc;
+    hipLaunchKernelGGL(rtk::aov_close_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, a.q, a.scn, a.fr, tex_scene(ctx), a.tl.st.M, a.n, static_cast<float4 *>(out_aov_dev));
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }

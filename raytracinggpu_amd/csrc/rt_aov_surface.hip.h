@@ -1,5 +1,6 @@
 // rt_aov_surface.hip.h -- rt_render_aov_surface[_device]: the feature buffers of the first DIFFUSE surface a pixel shows, reached through mirrors and glass.
-// Included at the end of rt_capi.hip, after rt_aov.hip.h (same translation unit: it reuses aov_emit_kernel and the traversal launch of trace_queue).
+// Included at the end of rt_capi.hip, after rt_aov.hip.h: the step kernel is built from its device functions (aov_close_query, aov_albedo), the entry
+// starts with its host prologue (aov_begin: aov_emit_kernel through the traversal launch of trace_queue).
 //
 // The specular branches of Scene::getColor (cpu_launcher.cpp:573-604) draw no random number: reflection, total reflection or refraction, whichever the ray's index
 // and the surface decide.  The pixel-centre camera ray's chain to its first diffuse surface is therefore a function of the scene alone, and along it the colour is
@@ -33,24 +34,16 @@ __global__ __launch_bounds__(256) void aov_surface_step_kernel(const Scene sc, c
     const size_t q = (size_t)wf_ray_to_slot(st, r);
     const float4 r0 = st.QR[2 * q], r1 = st.QR[2 * q + 1];                // the segment's ray, as the traversal read it
     f3 O = mk(r0.x, r0.y, r0.z), u = mk(r0.w, r1.x, r1.y);
-    SphereNear hy, hx;
-    spheres_near2(sc, O, u, true, u, false, hy, hx);
-    float t_min = hy.t;
-    int win = hy.obj, tri_win = -1;
-    const unsigned long long m = st.M[r];
-    if (m != WF_NOHIT) {
-        const float tm = __uint_as_float((unsigned int)(m >> 32));
-        const int mobj = mesh_obj_of_tri(sc, (int)(unsigned int)m);
-        if (mesh_beats_sphere(t_min, win, tm, mobj)) { t_min = tm; win = mobj; tri_win = (int)(unsigned int)m; }
-    }
+    const AovHit h = aov_close_query(sc, O, u, st.M[r]);
+    const int win = h.obj;
     if (FIRST) s.first_id = win;
     float4 o0 = make_float4(0.f, 0.f, 0.f, -1.f), o1 = make_float4(0.f, 0.f, 0.f, 0.f), o2 = o1;   // a miss, after any number of segments
     bool cont = false;
     if (win >= 0) {
-        const f3 P = O + t_min * u;                                       // cpu:560
+        const f3 P = O + h.t * u;                                       // cpu:560
         Bary bary{0.f, 0.f, 0.f};
         bool have_bary = false;
-        const f3 N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
+        const f3 N = hit_normal(sc, win, h.tri, O, u, P, bary, have_bary);
         const Material mt = material_of(sc, win);
         const bool specular = mt.mirror || mt.n_in != mt.n_out;
         if (!LAST && specular && s.k < max_specular) {                    // cpu:573-604: the chain goes on
@@ -59,12 +52,7 @@ __global__ __launch_bounds__(256) void aov_surface_step_kernel(const Scene sc, c
             s.k += 1;
             cont = true;
         } else {                                                          // diffuse, or the bound is reached: this hit is the one recorded
-            f3 alb = mk(mt.ar, mt.ag, mt.ab);
-            if (tri_win >= 0 && ((ts.mask >> win) & 1)) {
-                if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
-                float2 uv;
-                alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
-            }
+            const f3 alb = aov_albedo(sc, ts, h, O, u, bary, have_bary);
             const int code = s.k == 0 ? win : win + 16 * s.first_id + 256 * s.k;   // the path code: at most 15 + 240 + 256 * 15 = 4095, exact in binary32
             o0 = make_float4(N.x, N.y, N.z, (float)code);
             o1 = make_float4(P.x, P.y, P.z, 1.f);
@@ -95,35 +83,18 @@ __global__ __launch_bounds__(256) void aov_surface_step_kernel(const Scene sc, c
 extern "C" int rt_render_aov_surface_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, int max_specular, void *out_aov_dev, void *stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     if (max_specular < 0 || max_specular > RT_MAX_SEGMENTS - 1) return fail(ctx, RT_ERR_INVALID, "max_specular %d outside [0,%d]", max_specular, RT_MAX_SEGMENTS - 1);
-    int n;
-    if (int rc = aov_check(ctx, p, rows, out_aov_dev, n); rc != RT_OK || n == 0) return rc;
-    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if (max_specular > 0 && (rc = ensure(ctx, ctx->aov_state, (size_t)n * sizeof(rtk::SurfState))) != RT_OK) return rc;
-    Chunk c{p, rows, q, nullptr, nullptr, false, 1, 1, {}, {}, nullptr};
-    make_frame(ctx, out_aov_dev, pose, c);
-    c.fr.sigma = 0.f;
-    if (ctx->pipe.on) {                                                // (see Pipe::between: a pipelined frame must not start behind this write)
-        if (ctx->pipe.between.size() >= 64) ctx->pipe.between_overflow = true;
-        else { const uint8_t *a = static_cast<const uint8_t *>(out_aov_dev); ctx->pipe.between.push_back({a, a + 3 * (size_t)n * sizeof(float4), q}); }
-    }
-    // round 0: the camera rays, through the queue launch of rt_render_aov
-    TraceLaunch tl;
-    if ((rc = trace_queue(ctx, n, p->tri_tmin, RT_VARIANT_WAVEFRONT_QUEUE, q, ctx->aovM, ctx->aovQR, tl, [&](const rtk::WfState &st, dim3 g, dim3 b) {
-            hipLaunchKernelGGL(rtk::aov_emit_kernel, g, b, 0, q, c.scn, c.fr, st, n);
-        })) != RT_OK) return rc;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    AovCall a;                                                            // round 0: the camera rays, through the queue launch of rt_render_aov
+    if (int rc = aov_begin(ctx, p, pose, rows, out_aov_dev, stream, max_specular > 0 ? sizeof(rtk::SurfState) : 0, a); rc != RT_OK || a.n == 0) return rc;
+    const dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
     const rtk::TexScene ts = tex_scene(ctx);
     rtk::SurfState *state = static_cast<rtk::SurfState *>(ctx->aov_state.p);
     float4 *out = static_cast<float4 *>(out_aov_dev);
     for (int k = 0; k <= max_specular; ++k) {
-        if (k > 0) trace_again(ctx, tl, q);                               // the records the step kernel left: live ones carry PQ_TRAV, as an emitter's do
+        if (k > 0) trace_again(ctx, a.tl, a.q);                              // the records the step kernel left: live ones carry PQ_TRAV, as an emitter's do
         const bool first = k == 0, final = k == max_specular;
         auto step = first ? (final ? rtk::aov_surface_step_kernel<true, true> : rtk::aov_surface_step_kernel<true, false>)
                           : (final ? rtk::aov_surface_step_kernel<false, true> : rtk::aov_surface_step_kernel<false, false>);
-        hipLaunchKernelGGL(step, grid, block, 0, q, c.scn, ts, tl.st, p->eps, max_specular, n, state, out);
+        hipLaunchKernelGGL(step, grid, block, 0, a.q, a.scn, ts, a.tl.st, p->eps, max_specular, a.n, state, out);
     }
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "rt_host_ctx.hip.h"      // rt_ctx, knobs, buffers, errors
+#include "rt_host_post.hip.h"     // what the device entries and the post-process stages share: the call's stream, the pipelining note, checks, host-form staging
 #include "rt_host_scene.hip.h"    // scene upload: layouts, fixed-point nodes, forests
 #include "rt_host_render.hip.h"   // frames as launches
 
@@ -107,7 +108,7 @@ int rt_ctx_destroy(rt_ctx *ctx) {
     for (DevBuf &b : ctx->tex_img) b.release();
     ctx->wfQR.release(); ctx->accum.release(); ctx->dbgbuf.release(); ctx->batch_dev.release(); ctx->anim_dev.release();
     ctx->pathSamp.release(); ctx->pathT.release(); ctx->tidx_up.release();
-    ctx->aovM.release(); ctx->aovQR.release(); ctx->aov_out.release(); ctx->aov_state.release(); ctx->dn_tmp.release(); ctx->dn_io.release(); ctx->dnv_var[0].release(); ctx->dnv_var[1].release(); ctx->tp_io.release();
+    ctx->aovM.release(); ctx->aovQR.release(); ctx->aov_state.release(); ctx->dn_tmp.release(); ctx->dnv_var[0].release(); ctx->dnv_var[1].release(); ctx->post_io.release();
     for (DevBuf *b : {&ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp, &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev}) b->release();
     for (hipEvent_t &e : ctx->ev_trav) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t &e : ctx->ev_adv) if (e) (void)hipEventDestroy(e);
@@ -190,8 +191,8 @@ int rt_scene_upload(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres, const 
 
 int rt_render_device(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, void *out_rgba_dev, void *stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    const hipStream_t q_ = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q_) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
+    hipStream_t q_;
+    if (int rc = call_stream(ctx, stream, q_); rc != RT_OK) return rc;
     return launch_render(ctx, p, rows, out_rgba_dev, q_);
 }
 
@@ -202,8 +203,8 @@ int rt_render_device_batch(rt_ctx *ctx, const rt_params *p, const rt_rows *rows,
 int rt_render_device_batch_scenes(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const rt_frame_desc *frames, const rt_frame_scene *scenes, int n_spheres,
                                   int n_frames, void *stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    const hipStream_t q_ = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q_) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
+    hipStream_t q_;
+    if (int rc = call_stream(ctx, stream, q_); rc != RT_OK) return rc;
     if (!p || !rows || !frames) return fail(ctx, RT_ERR_INVALID, "params / rows / frames is NULL");
     if (n_frames < 1 || n_frames > RT_MAX_BATCH) return fail(ctx, RT_ERR_INVALID, "n_frames %d outside [1,%d]", n_frames, RT_MAX_BATCH);
     if (p->num_rays != 1) return fail(ctx, RT_ERR_UNSUPPORTED, "a batch renders one sample per pixel and frame (num_rays = %d)", p->num_rays);
@@ -323,8 +324,8 @@ int rt_wait(rt_ctx *ctx, int slot) {
 
 int rt_tonemap_device(rt_ctx *ctx, const void *rgba_dev, int64_t n_pixels, void *rgb8_dev, void *stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    const hipStream_t q_ = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q_) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
+    hipStream_t q_;
+    if (int rc = call_stream(ctx, stream, q_); rc != RT_OK) return rc;
     return launch_tonemap(ctx, rgba_dev, n_pixels, rgb8_dev, q_);
 }
 
@@ -407,8 +408,8 @@ int rt_render_pose(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, 
 
 int rt_render_pose_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_rgba_dev, void *stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    const hipStream_t q_ = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q_) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
+    hipStream_t q_;
+    if (int rc = call_stream(ctx, stream, q_); rc != RT_OK) return rc;
     if (!pose) return fail(ctx, RT_ERR_INVALID, "pose is NULL");
     return launch_render(ctx, p, rows, out_rgba_dev, q_, nullptr, pose);
 }
@@ -482,7 +483,7 @@ int rt_ctx_selfcheck(rt_ctx *ctx) {
                             &ctx->wfQR, &ctx->pathSamp, &ctx->pathT, &ctx->accum, &ctx->left_dev, &ctx->lvl_nodes, &ctx->lvl_off, &ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp,
                             &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev,
                             &ctx->slot_rgba[0], &ctx->slot_rgba[1], &ctx->slot_rgb8[0], &ctx->slot_rgb8[1], &ctx->wfALB, &ctx->tex_uv, &ctx->tex_table,
-                            &ctx->aovM, &ctx->aovQR, &ctx->aov_out, &ctx->aov_state, &ctx->dn_tmp, &ctx->dn_io, &ctx->dnv_var[0], &ctx->dnv_var[1], &ctx->tp_io};
+                            &ctx->aovM, &ctx->aovQR, &ctx->aov_state, &ctx->dn_tmp, &ctx->dnv_var[0], &ctx->dnv_var[1], &ctx->post_io};
     for (const DevBuf *b : bufs) {
         if (!b->p) continue;
         hipPointerAttribute_t at{};
@@ -565,7 +566,7 @@ int rt_get_stats(rt_ctx *ctx, rt_stats *stats) {
 #include "rt_multi.hip.h"
 #include "rt_kat.hip.h"
 #include "rt_trace.hip.h"
-#include "rt_aov.hip.h"
+#include "rt_aov.hip.h"           // the order matters from here on: each of the next three uses what the one before it defines (their headers say what)
 #include "rt_aov_surface.hip.h"
 #include "rt_denoise.hip.h"
 #include "rt_temporal.hip.h"

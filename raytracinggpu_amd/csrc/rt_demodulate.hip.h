@@ -1,5 +1,5 @@
 // rt_demodulate.hip.h -- rt_demodulate[_device] / rt_modulate[_device]: divide the recorded surface's albedo out of a colour frame, multiply it back in.
-// Included at the end of rt_capi.hip, after rt_aov_surface.hip.h, whose plane 2 it reads.
+// Included at the end of rt_capi.hip (same translation unit: the host half uses rt_host_post.hip.h); it reads plane 2 of rt_aov_surface.hip.h.
 //
 // Scene::getColor makes a pixel whose chain ends on a diffuse surface exactly albedo (.) (l / pi + what follows) (fold_segment, cpu:624, 642-644): the noise is in the
 // second factor.  A filter that runs between the two calls works on that factor, and a texture's detail -- all of it in the first -- comes back untouched.
@@ -50,9 +50,9 @@ __global__ __launch_bounds__(256) void demodulate_kernel(const float4 *C, const 
 
 static int dm_check(rt_ctx *ctx, const void *color, const void *aov, int64_t n_pixels, const void *out) {
     if (!color || !aov || !out) return fail(ctx, RT_ERR_INVALID, "color/aov/out is NULL");
-    if (n_pixels <= 0 || n_pixels >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "n_pixels must be positive and below 2^28");
+    if (n_pixels <= 0 || n_pixels >= kPostMaxPixels) return fail(ctx, RT_ERR_INVALID, "n_pixels must be positive and below 2^28");
     const size_t bytes = (size_t)n_pixels * sizeof(float4);
-    if ((out != color && dn_overlap(out, bytes, color, bytes)) || dn_overlap(out, bytes, aov, 3 * bytes))
+    if ((out != color && overlaps(out, bytes, color, bytes)) || overlaps(out, bytes, aov, 3 * bytes))
         return fail(ctx, RT_ERR_INVALID, "the output overlaps an input (only out == color, in place, is allowed)");
     return RT_OK;
 }
@@ -64,17 +64,9 @@ static int dm_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, in
     if (rc != RT_OK) return rc;
     const int n = (int)n_pixels;
     const size_t bytes = (size_t)n * sizeof(float4);
-    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->pipe.on) {                                                // (see Pipe::between: a pipelined frame must not overtake this read of a frame / write of an image)
-        if (ctx->pipe.between.size() + 2 > 64) ctx->pipe.between_overflow = true;
-        else {
-            const uint8_t *a = static_cast<const uint8_t *>(color_dev), *b = static_cast<const uint8_t *>(out_dev);
-            ctx->pipe.between.push_back({a, a + bytes, q});
-            ctx->pipe.between.push_back({b, b + bytes, q});
-        }
-    }
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+    note_between(ctx, q, {{color_dev, bytes}, {out_dev, bytes}});     // a pipelined frame must not overtake this read of a frame / write of an image
     hipLaunchKernelGGL(rtk::demodulate_kernel<DIVIDE>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, static_cast<const float4 *>(color_dev),
                        static_cast<const float4 *>(aov_dev) + 2 * (size_t)n, static_cast<float4 *>(out_dev), n, albedo_floor);
     RT_HIP(ctx, hipGetLastError());
@@ -85,19 +77,12 @@ template <bool DIVIDE>
 static int dm_host(rt_ctx *ctx, const float *color_host, const float *aov_host, int64_t n_pixels, float albedo_floor, float *out_host) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     RT_OWN_STREAM(ctx);
-    int rc = dm_check(ctx, color_host, aov_host, n_pixels, out_host);
+    const int rc = dm_check(ctx, color_host, aov_host, n_pixels, out_host);
     if (rc != RT_OK) return rc;
     const size_t bytes = (size_t)n_pixels * sizeof(float4);
-    // one buffer: colour (filtered in place), the three planes
-    if ((rc = ensure(ctx, ctx->dn_io, 4 * bytes)) != RT_OK) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->dn_io.p);
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipMemcpyAsync(base, color_host, bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    RT_HIP(ctx, hipMemcpyAsync(base + bytes, aov_host, 3 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    if ((rc = dm_device<DIVIDE>(ctx, base, base + bytes, n_pixels, albedo_floor, base, nullptr)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_host, base, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    // colour (filtered in place: the result is where it was), the three planes
+    return staged(ctx, {{color_host, bytes}, {aov_host, 3 * bytes}}, 0, bytes, out_host,
+                  [&](uint8_t *d) { return dm_device<DIVIDE>(ctx, d, d + bytes, n_pixels, albedo_floor, d, nullptr); });
 }
 
 extern "C" int rt_demodulate_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, int64_t n_pixels, float albedo_floor, void *out_rgba_dev, void *stream) {

@@ -1,5 +1,5 @@
 // rt_denoise.hip.h -- rt_denoise[_device]: the edge-avoiding a-trous filter over a colour frame, guided by the planes of rt_render_aov (rt_aov.hip.h).
-// Included at the end of rt_capi.hip.
+// Included at the end of rt_capi.hip, after rt_aov_surface.hip.h (same translation unit: the host half uses rt_host_post.hip.h).
 //
 // Pass k (step s = 2^k) is one launch: a 5x5 B3-spline stencil with holes, every tap weighted by how well its first hit agrees with the centre's -- same object,
 // normal, tangent plane, albedo, colour (raytrace_hip.h states the formula; it is the contract: binary32, one rounding per operation, taps in row-major order,
@@ -17,6 +17,7 @@
 // read from .w of history plane 1 on pass 0 and from a float plane of the context between passes.  The plain instantiation is instruction for instruction what it
 // was before the parameter existed (its argument list is the same: the VAR arguments are a parameter pack that is empty for it).
 #pragma once
+#include <type_traits>
 #include "rt_div.h"
 
 namespace rtk {
@@ -29,7 +30,8 @@ constexpr int kDnXcds = 8;                           // consecutive workgroup id
 struct DnParams { float k_normal, k_position, k_albedo, k_color; };   // k_color already scaled by 4^k (VAR: not read)
 // the VAR instantiation's own arguments: the variance plane read (v_stride floats apart: 4 = .w of a float4 plane, 1 = a float plane), the one written (or nullptr)
 struct DnVar { const float *v_in; float *v_out; int v_stride; float k_sigma, var_floor; };
-__device__ __forceinline__ float dn_lum(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+// Rec. 709 luminance, in this order of operations (rt_temporal.hip.h measures its moments with it too)
+__device__ __forceinline__ float lum709(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 
 __device__ __forceinline__ float dn_sqdiff(float4 a, float4 b) {
     const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
@@ -48,7 +50,7 @@ __device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, co
     if constexpr (VAR) v_out = fetch_v(0, 0);
     if (Np.w == -1.f) return Cp;                                      // a miss: nothing to guide the filter
     if constexpr (VAR) {
-        lp = dn_lum(Cp);
+        lp = lum709(Cp);
         D = k_sigma * v_out + var_floor;                              // the colour tolerance, in the colour's own units squared
         Dr = div_refine(D, __builtin_amdgcn_rcpf(D));
         d_fast = div_in_range(D);
@@ -74,7 +76,7 @@ __device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, co
             if (k.k_albedo != 0.f) w = w * fmaxf(0.f, 1.f - dn_sqdiff(Ap, fetch(2, dx, dy)) * k.k_albedo);
             const float4 Cq = fetch(3, dx, dy);
             if constexpr (VAR) {
-                const float dl = lp - dn_lum(Cq), dl2 = dl * dl;
+                const float dl = lp - lum709(Cq), dl2 = dl * dl;
                 if (dl2 != 0.f) {                                     // (equal luminance: the term is exactly 1, no quotient is formed)
                     float qd = div_by(dl2, D, Dr);
                     if (!(d_fast && div_in_range(dl2))) qd = dl2 / D;
@@ -98,10 +100,7 @@ __device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, co
         if (!fast) { ox = Sx / Wt; oy = Sy / Wt; oz = Sz / Wt; }
     }
     if constexpr (VAR) {                                              // the variance of the weighted mean: sum w^2 V / (sum w)^2
-        const float W2 = Wt * Wt;
-        float ov = div_by(Sv, W2, div_refine(W2, __builtin_amdgcn_rcpf(W2)));
-        if (!(div_in_range(Sv) && div_in_range(W2))) ov = Sv / W2;
-        v_out = ov;
+        v_out = div_quot(Sv, Wt * Wt);
     }
     return make_float4(ox, oy, oz, Cp.w);
 }
@@ -149,10 +148,13 @@ __global__ __launch_bounds__(kDnTileW * kDnTileH) void denoise_pass_kernel(const
 
 }  // namespace rtk
 
-// do [a, a + na) and [b, b + nb) share a byte?
-static bool dn_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uint8_t *x = static_cast<const uint8_t *>(a), *y = static_cast<const uint8_t *>(b);
-    return x < y + nb && y < x + na;
+// The grid of pass k (step s = 2^k): the tiles of the largest sub-image (phase 0), ceil(ceil(W / s) / tile) each way, and n_blocks = tiles_x * tiles_y * s * s workgroups
+// with work; the launch pads n_blocks to a multiple of kDnXcds.
+struct DnGrid { int64_t tiles_x, tiles_y, n_blocks; };
+static DnGrid dn_grid(int width, int height, int k) {
+    const int s = 1 << k;
+    const int64_t tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
+    return {tiles_x, tiles_y, tiles_x * tiles_y * s * s};
 }
 
 // Does every pass's grid fit a launch (fewer than 2^31 workgroups, which is also what the kernel's int item arithmetic holds)?  Tiles round every sub-image up, so
@@ -160,142 +162,89 @@ static bool dn_overlap(const void *a, size_t na, const void *b, size_t nb) {
 // highest, 1 by 2^28 - 1, is 1 x ceil(2^21 / 8) tiles x 128 x 128 = 2^32 there (8-row tiles against 32-pixel ones) and already 2^31 at step 64, and does not.  What
 // is refused: one or two pixels of width with n_passes 8 from 2^27 - 1023 rows on, one pixel of width with n_passes 7 from 2^28 - 511 rows on.
 static bool dn_grids_fit(int width, int height, int n_passes) {
-    for (int k = 0; k < n_passes; ++k) {
-        const int s = 1 << k;
-        const int64_t tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
-        if (tiles_x * tiles_y * s * s + rtk::kDnXcds > (int64_t)INT32_MAX) return false;
-    }
+    for (int k = 0; k < n_passes; ++k)
+        if (dn_grid(width, height, k).n_blocks + rtk::kDnXcds > (int64_t)INT32_MAX) return false;
     return true;
 }
 
-static int dn_check(rt_ctx *ctx, const void *color, const void *aov, int width, int height, const rt_denoise_params *dp, const void *out) {
-    if (!color || !aov || !dp || !out) return fail(ctx, RT_ERR_INVALID, "color/aov/params/out is NULL");
-    if (width <= 0 || height <= 0 || (int64_t)width * height >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "width/height must be positive, at most 2^28 pixels");
-    if (dp->n_passes < 1 || dp->n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", dp->n_passes, RT_DENOISE_MAX_PASSES);
-    if (!dn_grids_fit(width, height, dp->n_passes)) return fail(ctx, RT_ERR_INVALID, "a %d x %d frame needs 2^31 or more workgroups in one of %d passes", width, height, dp->n_passes);
+// What both filters and both forms ask of their arguments.  in: the colour frame (in_planes 1, in_name "color") or the history (2, "history"); n_passes: the
+// parameters' (read by the caller only where params is not NULL).  The output may share no byte with an input.
+static int dn_check(rt_ctx *ctx, const char *in_name, const void *in, int in_planes, const void *aov, int width, int height, const void *params, int n_passes, const void *out) {
+    if (!in || !aov || !params || !out) return fail(ctx, RT_ERR_INVALID, "%s/aov/params/out is NULL", in_name);
+    if (int rc = check_frame_size(ctx, width, height); rc != RT_OK) return rc;
+    if (n_passes < 1 || n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", n_passes, RT_DENOISE_MAX_PASSES);
+    if (!dn_grids_fit(width, height, n_passes)) return fail(ctx, RT_ERR_INVALID, "a %d x %d frame needs 2^31 or more workgroups in one of %d passes", width, height, n_passes);
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    if (overlaps(out, bytes, in, in_planes * bytes) || overlaps(out, bytes, aov, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
     return RT_OK;
+}
+
+// The two filters: VAR false = rt_denoise* over a colour frame, true = rt_denoise_var* over a history of rt_temporal_accumulate (two planes; the variance is .w of plane 1).
+template <bool VAR> using DnUserParams = std::conditional_t<VAR, rt_denoise_var_params, rt_denoise_params>;
+template <bool VAR> constexpr int kDnInPlanes = VAR ? 2 : 1;
+
+template <bool VAR>
+static int dn_device(rt_ctx *ctx, const void *in_dev, const void *aov_dev, int width, int height, const DnUserParams<VAR> *dp, void *out_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = dn_check(ctx, VAR ? "history" : "color", in_dev, kDnInPlanes<VAR>, aov_dev, width, height, dp, dp ? dp->n_passes : 0, out_dev);
+    if (rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    const int n_passes = dp->n_passes;
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+    if (n_passes > 1) {
+        if ((rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
+        if constexpr (VAR) {
+            if ((rc = ensure(ctx, ctx->dnv_var[0], npix * sizeof(float))) != RT_OK) return rc;
+            if (n_passes > 2 && (rc = ensure(ctx, ctx->dnv_var[1], npix * sizeof(float))) != RT_OK) return rc;
+        }
+    }
+    note_between(ctx, q, {{in_dev, kDnInPlanes<VAR> * bytes}, {out_dev, bytes}});   // a pipelined frame must not overtake this read of a frame / write of an image
+    // the passes alternate between the output and one buffer of the context so that the last one lands in the output.  VAR: the variance goes from .w of history
+    // plane 1 through the context's two float planes, and the last pass writes none
+    const float4 *src = static_cast<const float4 *>(in_dev), *guide = static_cast<const float4 *>(aov_dev);
+    const dim3 block(rtk::kDnTileW * rtk::kDnTileH);
+    for (int k = 0; k < n_passes; ++k) {
+        float4 *dst = static_cast<float4 *>(((n_passes - 1 - k) & 1) ? ctx->dn_tmp.p : out_dev);
+        const int s = 1 << k;
+        const DnGrid g = dn_grid(width, height, k);
+        const dim3 grid((unsigned)((g.n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds));
+        if constexpr (VAR) {
+            const rtk::DnParams kp{dp->k_normal, dp->k_position, dp->k_albedo, 0.f};
+            const rtk::DnVar kv{k == 0 ? reinterpret_cast<const float *>(static_cast<const float4 *>(in_dev) + npix) + 3 : static_cast<const float *>(ctx->dnv_var[(k - 1) & 1].p),
+                                k == n_passes - 1 ? nullptr : static_cast<float *>(ctx->dnv_var[k & 1].p), k == 0 ? 4 : 1, dp->k_sigma, dp->var_floor};
+            hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnVar>), grid, block, 0, q, src, guide, dst, width, height, s, (int)g.tiles_x, (int)g.tiles_y, (int)g.n_blocks, kp, kv);
+        } else {
+            const rtk::DnParams kp{dp->k_normal, dp->k_position, dp->k_albedo, dp->k_color * (float)(1 << (2 * k))};   // 4^k: an exact scale
+            hipLaunchKernelGGL(rtk::denoise_pass_kernel<false>, grid, block, 0, q, src, guide, dst, width, height, s, (int)g.tiles_x, (int)g.tiles_y, (int)g.n_blocks, kp);
+        }
+        src = dst;
+    }
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// the host forms: the input's planes, the three guide planes, the result
+template <bool VAR>
+static int dn_host(rt_ctx *ctx, const float *in_host, const float *aov_host, int width, int height, const DnUserParams<VAR> *dp, float *out_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    const int rc = dn_check(ctx, VAR ? "history" : "color", in_host, kDnInPlanes<VAR>, aov_host, width, height, dp, dp ? dp->n_passes : 0, out_host);
+    if (rc != RT_OK) return rc;
+    const size_t bytes = (size_t)width * height * sizeof(float4), in_bytes = kDnInPlanes<VAR> * bytes;
+    return staged(ctx, {{in_host, in_bytes}, {aov_host, 3 * bytes}}, in_bytes + 3 * bytes, bytes, out_host,
+                  [&](uint8_t *d) { return dn_device<VAR>(ctx, d, d + in_bytes, width, height, dp, d + in_bytes + 3 * bytes, nullptr); });
 }
 
 extern "C" int rt_denoise_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, int width, int height, const rt_denoise_params *dp, void *out_dev, void *stream) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    int rc = dn_check(ctx, color_dev, aov_dev, width, height, dp, out_dev);
-    if (rc != RT_OK) return rc;
-    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
-    if (dn_overlap(out_dev, bytes, color_dev, bytes) || dn_overlap(out_dev, bytes, aov_dev, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
-    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    if (dp->n_passes > 1 && (rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
-    if (ctx->pipe.on) {                                                // (see Pipe::between: a pipelined frame must not overtake this read of a frame / write of an image)
-        if (ctx->pipe.between.size() + 2 > 64) ctx->pipe.between_overflow = true;
-        else {
-            const uint8_t *a = static_cast<const uint8_t *>(color_dev), *b = static_cast<const uint8_t *>(out_dev);
-            ctx->pipe.between.push_back({a, a + bytes, q});
-            ctx->pipe.between.push_back({b, b + bytes, q});
-        }
-    }
-    // the passes alternate between the output and one buffer of the context so that the last one lands in the output
-    const float4 *src = static_cast<const float4 *>(color_dev);
-    for (int k = 0; k < dp->n_passes; ++k) {
-        float4 *dst = static_cast<float4 *>(((dp->n_passes - 1 - k) & 1) ? ctx->dn_tmp.p : out_dev);
-        const int s = 1 << k;
-        const rtk::DnParams kp{dp->k_normal, dp->k_position, dp->k_albedo, dp->k_color * (float)(1 << (2 * k))};   // 4^k: an exact scale
-        // tiles of the largest sub-image (phase 0): ceil(ceil(W / s) / tile)
-        const int tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
-        const int64_t n_blocks = (int64_t)tiles_x * tiles_y * s * s;
-        const int64_t grid = (n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds;
-        hipLaunchKernelGGL(rtk::denoise_pass_kernel<false>, dim3((unsigned)grid), dim3(rtk::kDnTileW * rtk::kDnTileH), 0, q, src, static_cast<const float4 *>(aov_dev), dst,
-                           width, height, s, tiles_x, tiles_y, (int)n_blocks, kp);
-        src = dst;
-    }
-    RT_HIP(ctx, hipGetLastError());
-    return RT_OK;
+    return dn_device<false>(ctx, color_dev, aov_dev, width, height, dp, out_dev, stream);
 }
-
 extern "C" int rt_denoise(rt_ctx *ctx, const float *color_host, const float *aov_host, int width, int height, const rt_denoise_params *dp, float *out_host) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    int rc = dn_check(ctx, color_host, aov_host, width, height, dp, out_host);
-    if (rc != RT_OK) return rc;
-    const size_t bytes = (size_t)width * height * sizeof(float4);
-    if (dn_overlap(out_host, bytes, color_host, bytes) || dn_overlap(out_host, bytes, aov_host, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
-    // one buffer: colour, the three planes, the result
-    if ((rc = ensure(ctx, ctx->dn_io, 5 * bytes)) != RT_OK) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->dn_io.p);
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipMemcpyAsync(base, color_host, bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    RT_HIP(ctx, hipMemcpyAsync(base + bytes, aov_host, 3 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    if ((rc = rt_denoise_device(ctx, base, base + bytes, width, height, dp, base + 4 * bytes, nullptr)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_host, base + 4 * bytes, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return dn_host<false>(ctx, color_host, aov_host, width, height, dp, out_host);
 }
-
-// ---- rt_denoise_var*: the VAR instantiation over a history of rt_temporal_accumulate ----
-static int dnv_check(rt_ctx *ctx, const void *history, const void *aov, int width, int height, const rt_denoise_var_params *vp, const void *out) {
-    if (!history || !aov || !vp || !out) return fail(ctx, RT_ERR_INVALID, "history/aov/params/out is NULL");
-    if (width <= 0 || height <= 0 || (int64_t)width * height >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "width/height must be positive, at most 2^28 pixels");
-    if (vp->n_passes < 1 || vp->n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", vp->n_passes, RT_DENOISE_MAX_PASSES);
-    if (!dn_grids_fit(width, height, vp->n_passes)) return fail(ctx, RT_ERR_INVALID, "a %d x %d frame needs 2^31 or more workgroups in one of %d passes", width, height, vp->n_passes);
-    return RT_OK;
-}
-
 extern "C" int rt_denoise_var_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_denoise_var_params *vp, void *out_dev, void *stream) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    int rc = dnv_check(ctx, history_dev, aov_dev, width, height, vp, out_dev);
-    if (rc != RT_OK) return rc;
-    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
-    if (dn_overlap(out_dev, bytes, history_dev, 2 * bytes) || dn_overlap(out_dev, bytes, aov_dev, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
-    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    if (vp->n_passes > 1) {
-        if ((rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
-        if ((rc = ensure(ctx, ctx->dnv_var[0], npix * sizeof(float))) != RT_OK) return rc;
-        if (vp->n_passes > 2 && (rc = ensure(ctx, ctx->dnv_var[1], npix * sizeof(float))) != RT_OK) return rc;
-    }
-    if (ctx->pipe.on) {                                                // (see Pipe::between)
-        if (ctx->pipe.between.size() + 2 > 64) ctx->pipe.between_overflow = true;
-        else {
-            const uint8_t *a = static_cast<const uint8_t *>(history_dev), *b = static_cast<const uint8_t *>(out_dev);
-            ctx->pipe.between.push_back({a, a + 2 * bytes, q});
-            ctx->pipe.between.push_back({b, b + bytes, q});
-        }
-    }
-    // colour as in rt_denoise_device; the variance goes from .w of history plane 1 through the context's two float planes, and the last pass writes none
-    const float4 *src = static_cast<const float4 *>(history_dev);
-    const rtk::DnParams kp{vp->k_normal, vp->k_position, vp->k_albedo, 0.f};
-    for (int k = 0; k < vp->n_passes; ++k) {
-        float4 *dst = static_cast<float4 *>(((vp->n_passes - 1 - k) & 1) ? ctx->dn_tmp.p : out_dev);
-        const int s = 1 << k;
-        rtk::DnVar kv{k == 0 ? reinterpret_cast<const float *>(static_cast<const float4 *>(history_dev) + npix) + 3 : static_cast<const float *>(ctx->dnv_var[(k - 1) & 1].p),
-                      k == vp->n_passes - 1 ? nullptr : static_cast<float *>(ctx->dnv_var[k & 1].p), k == 0 ? 4 : 1, vp->k_sigma, vp->var_floor};
-        const int tiles_x = ((width + s - 1) / s + rtk::kDnTileW - 1) / rtk::kDnTileW, tiles_y = ((height + s - 1) / s + rtk::kDnTileH - 1) / rtk::kDnTileH;
-        const int64_t n_blocks = (int64_t)tiles_x * tiles_y * s * s;
-        const int64_t grid = (n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds;
-        hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnVar>), dim3((unsigned)grid), dim3(rtk::kDnTileW * rtk::kDnTileH), 0, q, src, static_cast<const float4 *>(aov_dev), dst,
-                           width, height, s, tiles_x, tiles_y, (int)n_blocks, kp, kv);
-        src = dst;
-    }
-    RT_HIP(ctx, hipGetLastError());
-    return RT_OK;
+    return dn_device<true>(ctx, history_dev, aov_dev, width, height, vp, out_dev, stream);
 }
-
 extern "C" int rt_denoise_var(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_denoise_var_params *vp, float *out_host) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    int rc = dnv_check(ctx, history_host, aov_host, width, height, vp, out_host);
-    if (rc != RT_OK) return rc;
-    const size_t bytes = (size_t)width * height * sizeof(float4);
-    if (dn_overlap(out_host, bytes, history_host, 2 * bytes) || dn_overlap(out_host, bytes, aov_host, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
-    // one buffer: the history's two planes, the three guide planes, the result
-    if ((rc = ensure(ctx, ctx->dn_io, 6 * bytes)) != RT_OK) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->dn_io.p);
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipMemcpyAsync(base, history_host, 2 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    RT_HIP(ctx, hipMemcpyAsync(base + 2 * bytes, aov_host, 3 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    if ((rc = rt_denoise_var_device(ctx, base, base + 2 * bytes, width, height, vp, base + 5 * bytes, nullptr)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_host, base + 5 * bytes, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return dn_host<true>(ctx, history_host, aov_host, width, height, vp, out_host);
 }

@@ -41,4 +41,13 @@ RT_DIV_HD float div_by(float n, float d, float r1) {
 // the range in which the shared sequence IS the correctly rounded quotient (see above); false for NaN
 RT_DIV_HD bool div_in_range(float x) { return fabsf(x) >= kDivLo && fabsf(x) <= kDivHi; }
 
+#if defined(__HIPCC__)
+// one quotient n / d, correctly rounded: the sequence above, the literal quotient outside its range
+__device__ __forceinline__ float div_quot(float n, float d) {
+    float q = div_by(n, d, div_refine(d, __builtin_amdgcn_rcpf(d)));
+    if (!(div_in_range(n) && div_in_range(d))) q = n / d;
+    return q;
+}
+#endif
+
 }  // namespace rtk

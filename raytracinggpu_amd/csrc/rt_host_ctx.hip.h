@@ -163,10 +163,11 @@ struct rt_ctx {
     DevBuf dbgbuf;                                                  // -DRT_DEBUG builds: per-wave traversal records
     DevBuf batch_dev;                                               // rt_render_device_batch: the frames' descriptors, one copy per sub-frame
     DevBuf anim_dev;                                                // rt_render_device_batch_scenes: the frames' lights and sphere poses (rtk::AnimFrame), one copy per sub-frame
-    DevBuf aovM, aovQR, aov_out;                                    // rt_render_aov*: traversal results and ray queue of its own (the render path's are never touched), the host form's planes
+    DevBuf aovM, aovQR;                                             // rt_render_aov*: traversal results and ray queue of its own (the render path's are never touched)
     DevBuf aov_state;                                               // rt_render_aov_surface*: one record per pixel between the rounds of its chain (rtk::SurfState)
-    DevBuf dn_tmp, dn_io;                                           // rt_denoise*: the ping-pong frame of the passes; the host form's colour + planes + result
-    DevBuf dnv_var[2], tp_io;                                       // rt_denoise_var*: the variance planes between passes; rt_temporal_accumulate: the host form's nine planes
+    DevBuf dn_tmp;                                                  // rt_denoise*: the ping-pong frame of the passes
+    DevBuf dnv_var[2];                                              // rt_denoise_var*: the variance planes between passes
+    DevBuf post_io;                                                 // the host forms of rt_render_aov*, rt_denoise*, rt_temporal_accumulate, rt_[de]modulate: inputs and result (staged, rt_host_post.hip.h)
     DevBuf accum;                                                   // progressive mode: sum of the frames so far (float4 per pixel)
     int prog_frames = 0, prog_w = 0, prog_h = 0;
     uint64_t qf_sig = 0;                                            // layout the queue flags were last zeroed for

@@ -807,12 +807,7 @@ int launch_tonemap(rt_ctx *ctx, const void *rgba_dev, int64_t npix, void *rgb8_d
     if (npix == 0) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t quads = (npix + 3) / 4;
-    if (ctx->pipe.on && ctx->pipe.between.size() >= 64) ctx->pipe.between_overflow = true;   // more ranges than are kept: the next render call takes the full fork
-    if (ctx->pipe.on && ctx->pipe.between.size() < 64) {              // (see Pipe::between)
-        const uint8_t *a = static_cast<const uint8_t *>(rgba_dev), *b = static_cast<const uint8_t *>(rgb8_dev);
-        ctx->pipe.between.push_back({a, a + (size_t)npix * sizeof(float4), stream});
-        ctx->pipe.between.push_back({b, b + (size_t)npix * 3, stream});
-    }
+    note_between(ctx, stream, {{rgba_dev, (size_t)npix * sizeof(float4)}, {rgb8_dev, (size_t)npix * 3}});   // a pipelined frame must not overtake this read of a frame / write of an image
     RT_HIP(ctx, hipEventRecord(ctx->ev_t0, stream));
     hipLaunchKernelGGL(rtk::tonemap_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream,
                        static_cast<const float4 *>(rgba_dev), npix, static_cast<uint8_t *>(rgb8_dev));

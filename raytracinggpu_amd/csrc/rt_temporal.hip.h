@@ -1,5 +1,5 @@
 // rt_temporal.hip.h -- rt_temporal_accumulate[_device]: reproject the previous frame's history onto the current frame and blend (the temporal half of SVGF).
-// Included at the end of rt_capi.hip, beside rt_denoise.hip.h, whose variance-guided instantiation reads what this writes.
+// Included at the end of rt_capi.hip, after rt_denoise.hip.h: the kernel measures luminance with its lum709, and its variance-guided instantiation reads what this writes.
 //
 // The caller owns every buffer: the current colour frame and planes (rt_render*, rt_render_aov*), the previous frame's planes 0 and 1, the previous history, the
 // new history (two float4 planes: colour | rays, then luminance moments | history length | variance).  Per pixel with a hit: the hit point and normal are taken
@@ -27,14 +27,6 @@ struct TpArgs {
     int have_prev, have_motion;
 };
 
-__device__ __forceinline__ float tp_lum(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
-// n / d, correctly rounded: rt_div.h's sequence, the literal quotient outside its range
-__device__ __forceinline__ float tp_quot(float n, float d) {
-    float q = div_by(n, d, div_refine(d, __builtin_amdgcn_rcpf(d)));
-    if (!(div_in_range(n) && div_in_range(d))) q = n / d;
-    return q;
-}
-
 __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *__restrict__ C, const float4 *__restrict__ g, const float4 *__restrict__ pg,
                                                                    const float4 *__restrict__ ph, float4 *__restrict__ out, int W, int H, const TpArgs a, const TpMotions mt) {
     const size_t plane = (size_t)W * (size_t)H;
@@ -44,7 +36,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *
     const float4 Cp = C[i], Np = g[i];
     float4 o0 = Cp, o1 = make_float4(0.f, 0.f, 0.f, 0.f);             // a miss: a copy, no history, no variance
     if (Np.w != -1.f) {
-        const float lp = tp_lum(Cp);
+        const float lp = lum709(Cp);
         float n = 1.f, cr = Cp.x, cg = Cp.y, cb = Cp.z, m1 = lp, m2 = lp * lp;
         const int id = (int)Np.w;
         if (a.have_prev && !((a.mask >> (id & 31)) & 1u)) {
@@ -61,7 +53,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *
             }
             // the previous camera's image-plane coordinates of P': d = k^-1 (o + bz z + bx X + by Y)
             const float dx = px - a.o[0], dy = py - a.o[1], dz = pz - a.o[2];
-            const float k = tp_quot(a.b, (dx * a.bz[0] + dy * a.bz[1]) + dz * a.bz[2]);
+            const float k = div_quot(a.b, (dx * a.bz[0] + dy * a.bz[1]) + dz * a.bz[2]);
             const float X = ((dx * a.bx[0] + dy * a.bx[1]) + dz * a.bx[2]) * k - a.cx;
             const float Y = ((dx * a.by[0] + dy * a.by[1]) + dz * a.by[2]) * k - a.cy;
             const float gx = X + a.half_w, gy = a.half_h - Y;         // pixel (px, row)'s centre is (px + 0.5, row + 0.5) here
@@ -82,7 +74,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *
                     if (!(e * e <= a.max_pd2)) continue;
                     const float4 H0 = ph[q], H1 = ph[plane + q];
                     n = fminf(H1.z + 1.f, a.max_hist);
-                    const float al = fmaxf(tp_quot(1.f, n), a.alpha_min);
+                    const float al = fmaxf(div_quot(1.f, n), a.alpha_min);
                     cr = H0.x + al * (Cp.x - H0.x); cg = H0.y + al * (Cp.y - H0.y); cb = H0.z + al * (Cp.z - H0.z);
                     m1 = H1.x + al * (lp - H1.x);
                     m2 = H1.y + al * (lp * lp - H1.y);
@@ -102,7 +94,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *
                     if (qx < 0 || qx >= W) continue;
                     const size_t q = (size_t)qy * (size_t)W + (size_t)qx;
                     if (g[q].w != Np.w) continue;
-                    const float l = tp_lum(C[q]);
+                    const float l = lum709(C[q]);
                     s1 = s1 + l; s2 = s2 + l * l; cnt = cnt + 1.f;
                 }
             }
@@ -126,13 +118,13 @@ static int tp_check(rt_ctx *ctx, const void *color, const void *aov, const void 
     if (!color || !aov || !tp || !out) return fail(ctx, RT_ERR_INVALID, "color/aov/params/out is NULL");
     if ((prev_aov == nullptr) != (prev_hist == nullptr)) return fail(ctx, RT_ERR_INVALID, "the previous planes and the previous history come together or not at all");
     if (prev_aov && !rp) return fail(ctx, RT_ERR_INVALID, "a previous frame needs a reprojection record");
-    if (width <= 0 || height <= 0 || (int64_t)width * height >= (1 << 28)) return fail(ctx, RT_ERR_INVALID, "width/height must be positive, at most 2^28 pixels");
+    if (int rc = check_frame_size(ctx, width, height); rc != RT_OK) return rc;
     if (tp->max_history < 1) return fail(ctx, RT_ERR_INVALID, "max_history %d < 1", tp->max_history);
     return RT_OK;
 }
 static bool tp_aliased(const void *color, const void *aov, const void *prev_aov, const void *prev_hist, size_t bytes, const void *out) {
-    return dn_overlap(out, 2 * bytes, color, bytes) || dn_overlap(out, 2 * bytes, aov, 2 * bytes) ||
-           (prev_aov && (dn_overlap(out, 2 * bytes, prev_aov, 2 * bytes) || dn_overlap(out, 2 * bytes, prev_hist, 2 * bytes)));   // (tp_check: both or neither)
+    return overlaps(out, 2 * bytes, color, bytes) || overlaps(out, 2 * bytes, aov, 2 * bytes) ||
+           (prev_aov && (overlaps(out, 2 * bytes, prev_aov, 2 * bytes) || overlaps(out, 2 * bytes, prev_hist, 2 * bytes)));   // (tp_check: both or neither)
 }
 
 extern "C" int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, const void *prev_aov_dev, const void *prev_history_dev, int width, int height,
@@ -142,9 +134,8 @@ extern "C" int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_dev,
     if (rc != RT_OK) return rc;
     const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
     if (tp_aliased(color_dev, aov_dev, prev_aov_dev, prev_history_dev, bytes, out_history_dev)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
-    const hipStream_t q = stream ? static_cast<hipStream_t>(stream) : own_stream(ctx);
-    if (!q) return fail(ctx, RT_ERR_HIP, "the context's stream: %s", ctx->err.c_str());
-    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
     rtk::TpArgs a{};
     rtk::TpMotions mt{};
     a.bx[0] = a.by[1] = a.bz[2] = 1.f;
@@ -172,14 +163,7 @@ extern "C" int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_dev,
             }
         }
     }
-    if (ctx->pipe.on) {                                                // (see Pipe::between: a pipelined frame must not overtake this read of a frame / write of a history)
-        if (ctx->pipe.between.size() + 2 > 64) ctx->pipe.between_overflow = true;
-        else {
-            const uint8_t *c = static_cast<const uint8_t *>(color_dev), *o = static_cast<const uint8_t *>(out_history_dev);
-            ctx->pipe.between.push_back({c, c + bytes, q});
-            ctx->pipe.between.push_back({o, o + 2 * bytes, q});
-        }
-    }
+    note_between(ctx, q, {{color_dev, bytes}, {out_history_dev, 2 * bytes}});   // a pipelined frame must not overtake this read of a frame / write of a history
     hipLaunchKernelGGL(rtk::temporal_accumulate_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, q, static_cast<const float4 *>(color_dev), static_cast<const float4 *>(aov_dev),
                        static_cast<const float4 *>(prev_aov_dev), static_cast<const float4 *>(prev_history_dev), static_cast<float4 *>(out_history_dev), width, height, a, mt);
     RT_HIP(ctx, hipGetLastError());
@@ -194,19 +178,9 @@ extern "C" int rt_temporal_accumulate(rt_ctx *ctx, const float *color_host, cons
     if (rc != RT_OK) return rc;
     const size_t bytes = (size_t)width * height * sizeof(float4);
     if (tp_aliased(color_host, aov_host, prev_aov_host, prev_history_host, bytes, out_history_host)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
-    // one buffer: colour, planes 0 and 1, the previous planes 0 and 1, the previous history, the new history
-    if ((rc = ensure(ctx, ctx->tp_io, 9 * bytes)) != RT_OK) return rc;
-    uint8_t *base = static_cast<uint8_t *>(ctx->tp_io.p);
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    RT_HIP(ctx, hipMemcpyAsync(base, color_host, bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    RT_HIP(ctx, hipMemcpyAsync(base + bytes, aov_host, 2 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    if (prev_aov_host) {
-        RT_HIP(ctx, hipMemcpyAsync(base + 3 * bytes, prev_aov_host, 2 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-        RT_HIP(ctx, hipMemcpyAsync(base + 5 * bytes, prev_history_host, 2 * bytes, hipMemcpyHostToDevice, own_stream(ctx)));
-    }
-    if ((rc = rt_temporal_accumulate_device(ctx, base, base + bytes, prev_aov_host ? base + 3 * bytes : nullptr, prev_aov_host ? base + 5 * bytes : nullptr, width, height, tp, rp,
-                                            base + 7 * bytes, nullptr)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_history_host, base + 7 * bytes, 2 * bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    // colour, planes 0 and 1, the previous planes 0 and 1, the previous history (room kept on a first frame), the new history
+    const float *pa = prev_aov_host, *ph = prev_history_host;
+    return staged(ctx, {{color_host, bytes}, {aov_host, 2 * bytes}, {pa, 2 * bytes}, {ph, 2 * bytes}}, 7 * bytes, 2 * bytes, out_history_host, [&](uint8_t *d) {
+        return rt_temporal_accumulate_device(ctx, d, d + bytes, pa ? d + 3 * bytes : nullptr, pa ? d + 5 * bytes : nullptr, width, height, tp, rp, d + 7 * bytes, nullptr);
+    });
 }
