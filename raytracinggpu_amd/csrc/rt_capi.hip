@@ -18,7 +18,9 @@
 #include <chrono>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rt_host_ctx.hip.h"      // rt_ctx, knobs, buffers, errors
@@ -59,17 +61,17 @@ int rt_ctx_create(rt_ctx **out, int device_id) {
     pc.lap("hipSetDevice");
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device_id);
     pc.lap("hipGetDeviceProperties");
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_k0);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_k1);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_t0);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_t1);
-    for (hipEvent_t &ev : ctx->ev_trav) if (e == hipSuccess) e = hipEventCreate(&ev);
-    for (hipEvent_t &ev : ctx->ev_adv) if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming);
-    for (int k = 0; k < rt_ctx::kSlots; ++k) if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->slot_half[k], hipEventDisableTiming);
+    if (e == hipSuccess) e = ctx->ev_k0.create();
+    if (e == hipSuccess) e = ctx->ev_k1.create();
+    if (e == hipSuccess) e = ctx->ev_t0.create();
+    if (e == hipSuccess) e = ctx->ev_t1.create();
+    for (Event &ev : ctx->ev_trav) if (e == hipSuccess) e = ev.create();
+    for (Event &ev : ctx->ev_adv) if (e == hipSuccess) e = ev.create();
+    if (e == hipSuccess) e = ctx->fork_ev.create(hipEventDisableTiming);
+    for (int k = 0; k < rt_ctx::kSlots; ++k) if (e == hipSuccess) e = ctx->slot_half[k].create(hipEventDisableTiming);
     for (int k = 0; k < rt_ctx::kSlots; ++k) {
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->slot_rendered[k], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->slot_done[k], hipEventDisableTiming);
+        if (e == hipSuccess) e = ctx->slot_rendered[k].create(hipEventDisableTiming);
+        if (e == hipSuccess) e = ctx->slot_done[k].create(hipEventDisableTiming);
     }
     if (e != hipSuccess) {
         int code = fail(nullptr, RT_ERR_HIP, "context creation: %s", hipGetErrorString(e));
@@ -90,38 +92,7 @@ int rt_ctx_create(rt_ctx **out, int device_id) {
 
 int rt_ctx_destroy(rt_ctx *ctx) {
     if (!ctx) return RT_OK;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream_) (void)hipStreamSynchronize(ctx->stream_);
-    for (hipStream_t q : ctx->part_stream) if (q) (void)hipStreamSynchronize(q);   // sub-frame chains of frames issued on a caller's stream
-    if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-    if (ctx->copy_stream2) { (void)hipStreamSynchronize(ctx->copy_stream2); (void)hipStreamDestroy(ctx->copy_stream2); }
-    for (int k = 0; k < rt_ctx::kSlots; ++k) if (ctx->slot_half[k]) (void)hipEventDestroy(ctx->slot_half[k]);
-    for (int k = 0; k < rt_ctx::kSlots; ++k) {
-        ctx->slot_rgba[k].release(); ctx->slot_rgb8[k].release();
-        if (ctx->slot_rendered[k]) (void)hipEventDestroy(ctx->slot_rendered[k]);
-        if (ctx->slot_done[k]) (void)hipEventDestroy(ctx->slot_done[k]);
-    }
-    ctx->node_lo.release(); ctx->node_hi.release(); ctx->nodes2.release(); ctx->nodesq.release(); ctx->nodesb.release(); ctx->nodesh.release(); ctx->tri2leaf.release(); ctx->nodesw.release(); ctx->leaflh.release(); ctx->qdp_parent.release(); ctx->qdp_cnt.release(); ctx->qdp_g.release(); ctx->qdp_ch.release(); ctx->q2thr.release(); ctx->left_dev.release(); ctx->lvl_nodes.release(); ctx->lvl_off.release(); ctx->nrm.release(); ctx->tri.release(); ctx->verts.release(); ctx->tidx.release();
-    ctx->scratch_rgba.release(); ctx->scratch_rgb8.release(); ctx->work.release(); ctx->queue.release();
-    ctx->wfM.release(); ctx->wfT.release(); ctx->wfLS.release(); ctx->wfSID.release(); ctx->wfSamp.release(); ctx->wfALB.release();
-    ctx->tex_uv.release(); ctx->tex_table.release();
-    for (DevBuf &b : ctx->tex_img) b.release();
-    ctx->wfQR.release(); ctx->accum.release(); ctx->dbgbuf.release(); ctx->batch_dev.release(); ctx->anim_dev.release();
-    ctx->pathSamp.release(); ctx->pathT.release(); ctx->tidx_up.release();
-    ctx->aovM.release(); ctx->aovQR.release(); ctx->aov_state.release(); ctx->dn_tmp.release(); ctx->dnv_var[0].release(); ctx->dnv_var[1].release(); ctx->post_io.release();
-    for (DevBuf *b : {&ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp, &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev}) b->release();
-    for (hipEvent_t &e : ctx->ev_trav) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : ctx->ev_adv) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : ctx->part_ev) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t &q : ctx->part_stream) if (q) (void)hipStreamDestroy(q);
-    if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
-    for (hipEvent_t &e : ctx->pipe.fork2) if (e) (void)hipEventDestroy(e);
-    if (ctx->ev_k0) (void)hipEventDestroy(ctx->ev_k0);
-    if (ctx->ev_k1) (void)hipEventDestroy(ctx->ev_k1);
-    if (ctx->ev_t0) (void)hipEventDestroy(ctx->ev_t0);
-    if (ctx->ev_t1) (void)hipEventDestroy(ctx->ev_t1);
-    if (ctx->stream_) (void)hipStreamDestroy(ctx->stream_);
-    delete ctx;
+    delete ctx;                                                      // ~rt_ctx waits for the context's streams, the members release themselves
     return RT_OK;
 }
 
@@ -238,21 +209,11 @@ int rt_render_device_batch_scenes(rt_ctx *ctx, const rt_params *p, const rt_rows
 }
 
 int rt_render(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, float *out_rgba_host) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (!p) return fail(ctx, RT_ERR_INVALID, "params is NULL");
-    if (row_begin < 0 || row_end < row_begin || row_end > p->height) return fail(ctx, RT_ERR_INVALID, "bad row range [%d,%d)", row_begin, row_end);
-    if (!out_rgba_host) return fail(ctx, RT_ERR_INVALID, "output pointer is NULL");
-    const int n = row_end - row_begin;
-    const size_t bytes = (size_t)n * (p->width > 0 ? p->width : 0) * sizeof(float4);
-    int rc = ensure(ctx, ctx->scratch_rgba, bytes);
+    rt_rows rows; int64_t npix;
+    int rc = host_rows(ctx, p, row_begin, row_end, out_rgba_host, rows, npix);
     if (rc != RT_OK) return rc;
-    rt_rows rows{row_begin, n, n > 0 ? n : 1, 1};
-    rc = launch_render(ctx, p, &rows, ctx->scratch_rgba.p, own_stream(ctx));
-    if (rc != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_rgba_host, ctx->scratch_rgba.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    if ((rc = launch_render(ctx, p, &rows, ctx->scratch_rgba.p, own_stream(ctx))) != RT_OK) return rc;
+    return copy_back(ctx, out_rgba_host, ctx->scratch_rgba.p, (size_t)npix * sizeof(float4));
 }
 
 int rt_ctx_set_pipelining(rt_ctx *ctx, int on) {
@@ -330,48 +291,34 @@ int rt_tonemap_device(rt_ctx *ctx, const void *rgba_dev, int64_t n_pixels, void 
 }
 
 int rt_render_rgb8(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, uint8_t *out_rgb8_host) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (!p) return fail(ctx, RT_ERR_INVALID, "params is NULL");
-    if (row_begin < 0 || row_end < row_begin || row_end > p->height) return fail(ctx, RT_ERR_INVALID, "bad row range [%d,%d)", row_begin, row_end);
-    if (!out_rgb8_host) return fail(ctx, RT_ERR_INVALID, "output pointer is NULL");
-    const int n = row_end - row_begin;
-    const int64_t npix = (int64_t)n * (p->width > 0 ? p->width : 0);
     PhaseClock pc;
-    int rc = ensure(ctx, ctx->scratch_rgba, (size_t)npix * sizeof(float4));
+    rt_rows rows; int64_t npix;
+    int rc = host_rows(ctx, p, row_begin, row_end, out_rgb8_host, rows, npix);
     if (rc != RT_OK) return rc;
     if ((rc = ensure(ctx, ctx->scratch_rgb8, (size_t)npix * 3 + 16)) != RT_OK) return rc;
     pc.lap("rt_render_rgb8: frame buffers (hipMalloc)");
-    rt_rows rows{row_begin, n, n > 0 ? n : 1, 1};
     if ((rc = launch_render(ctx, p, &rows, ctx->scratch_rgba.p, own_stream(ctx))) != RT_OK) return rc;
     pc.lap("rt_render_rgb8: enqueue (path state, code object)");
     if ((rc = launch_tonemap(ctx, ctx->scratch_rgba.p, npix, ctx->scratch_rgb8.p, own_stream(ctx))) != RT_OK) return rc;
     if (pc.on) { RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx))); pc.lap("rt_render_rgb8: kernels (wait)"); }
-    RT_HIP(ctx, hipMemcpyAsync(out_rgb8_host, ctx->scratch_rgb8.p, (size_t)npix * 3, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    if ((rc = copy_back(ctx, out_rgb8_host, ctx->scratch_rgb8.p, (size_t)npix * 3)) != RT_OK) return rc;
     pc.lap("rt_render_rgb8: copy to the host");
     return RT_OK;
 }
 
 int rt_count_work(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, rt_work *out) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (!p || !out) return fail(ctx, RT_ERR_INVALID, "params/out is NULL");
-    if (row_begin < 0 || row_end < row_begin || row_end > p->height) return fail(ctx, RT_ERR_INVALID, "bad row range [%d,%d)", row_begin, row_end);
-    const int n = row_end - row_begin;
-    int rc = ensure(ctx, ctx->scratch_rgba, (size_t)n * (p->width > 0 ? p->width : 0) * sizeof(float4));
+    rt_rows rows; int64_t npix;
+    int rc = host_rows(ctx, p, row_begin, row_end, out, rows, npix);
     if (rc != RT_OK) return rc;
     if ((rc = ensure(ctx, ctx->work, 24 * sizeof(unsigned long long))) != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, hipMemsetAsync(ctx->work.p, 0, 24 * sizeof(unsigned long long), own_stream(ctx)));
-    rt_rows rows{row_begin, n, n > 0 ? n : 1, 1};
     rc = launch_render(ctx, p, &rows, ctx->scratch_rgba.p, own_stream(ctx), static_cast<unsigned long long *>(ctx->work.p));
     if (rc != RT_OK) return rc;
     unsigned long long h[24];
     RT_HIP(ctx, hipMemcpyAsync(h, ctx->work.p, sizeof(h), hipMemcpyDeviceToHost, own_stream(ctx)));
-    std::vector<float> fb((size_t)n * (size_t)p->width * 4);
-    RT_HIP(ctx, hipMemcpyAsync(fb.data(), ctx->scratch_rgba.p, fb.size() * sizeof(float), hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    std::vector<float> fb((size_t)npix * 4);
+    if ((rc = copy_back(ctx, fb.data(), ctx->scratch_rgba.p, fb.size() * sizeof(float))) != RT_OK) return rc;
     double rays = 0;                                  // .w of every pixel = rays traced for it (exact in binary32)
     for (size_t k = 3; k < fb.size(); k += 4) rays += fb[k];
     out->rays = (uint64_t)rays; out->box_tests = h[1]; out->nodes = h[2]; out->tri_tests = h[3];
@@ -393,17 +340,12 @@ int rt_camera_basis(const rt_camera_pose *pose, float bx[3], float by[3], float 
 }
 
 int rt_render_pose(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, float *out_rgba_host) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    if (!p || !pose || !out_rgba_host) return fail(ctx, RT_ERR_INVALID, "params/pose/out is NULL");
-    const size_t bytes = (size_t)(p->height > 0 ? p->height : 0) * (p->width > 0 ? p->width : 0) * sizeof(float4);
-    int rc = ensure(ctx, ctx->scratch_rgba, bytes);
+    rt_rows rows; int64_t npix;
+    int rc = host_rows(ctx, p, 0, p ? p->height : 0, out_rgba_host, rows, npix);
     if (rc != RT_OK) return rc;
-    rt_rows rows{0, p->height, p->height > 0 ? p->height : 1, 1};
+    if (!pose) return fail(ctx, RT_ERR_INVALID, "pose is NULL");
     if ((rc = launch_render(ctx, p, &rows, ctx->scratch_rgba.p, own_stream(ctx), nullptr, pose)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_rgba_host, ctx->scratch_rgba.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return copy_back(ctx, out_rgba_host, ctx->scratch_rgba.p, (size_t)npix * sizeof(float4));
 }
 
 int rt_render_pose_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, void *out_rgba_dev, void *stream) {
@@ -455,9 +397,7 @@ int rt_progressive_frame(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *
     RT_HIP(ctx, hipGetLastError());
     ctx->prog_frames = frame_no;
     if (display_rgba_host) RT_HIP(ctx, hipMemcpyAsync(display_rgba_host, display, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    if (rgb8_host) RT_HIP(ctx, hipMemcpyAsync(rgb8_host, ctx->scratch_rgb8.p, (size_t)npix * 3, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return copy_back(ctx, rgb8_host, ctx->scratch_rgb8.p, rgb8_host ? (size_t)npix * 3 : 0);
 }
 
 int rt_host_alloc(void **ptr, size_t bytes) {
@@ -478,13 +418,7 @@ int rt_host_free(void *ptr) {
 int rt_ctx_selfcheck(rt_ctx *ctx) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    const DevBuf *bufs[] = {&ctx->node_lo, &ctx->node_hi, &ctx->nodes2, &ctx->nodesq, &ctx->nodesb, &ctx->q2thr, &ctx->tri, &ctx->verts, &ctx->tidx, &ctx->tidx_up, &ctx->nrm,
-                            &ctx->scratch_rgba, &ctx->scratch_rgb8, &ctx->work, &ctx->queue, &ctx->wfM, &ctx->wfT, &ctx->wfLS, &ctx->wfSID, &ctx->wfSamp,
-                            &ctx->wfQR, &ctx->pathSamp, &ctx->pathT, &ctx->accum, &ctx->left_dev, &ctx->lvl_nodes, &ctx->lvl_off, &ctx->bb_idx, &ctx->bb_cnt, &ctx->bb_pa, &ctx->bb_pb, &ctx->bb_tmp,
-                            &ctx->bb_nodes_i, &ctx->bb_nodes_f, &ctx->bb_counter, &ctx->bb_lvl, &ctx->bb_size, &ctx->bb_pre, &ctx->bb_arr, &ctx->lb_pool, &ctx->lb_pool2, &ctx->perm_dev,
-                            &ctx->slot_rgba[0], &ctx->slot_rgba[1], &ctx->slot_rgb8[0], &ctx->slot_rgb8[1], &ctx->wfALB, &ctx->tex_uv, &ctx->tex_table,
-                            &ctx->aovM, &ctx->aovQR, &ctx->aov_state, &ctx->dn_tmp, &ctx->dnv_var[0], &ctx->dnv_var[1], &ctx->post_io};
-    for (const DevBuf *b : bufs) {
+    for (const DevBuf *b : ctx->bufs) {
         if (!b->p) continue;
         hipPointerAttribute_t at{};
         RT_HIP(ctx, hipPointerGetAttributes(&at, b->p));
@@ -515,9 +449,7 @@ int rt_device_to_host(rt_ctx *ctx, void *dst_host, const void *src_dev, size_t b
     RT_OWN_STREAM(ctx);
     if (bytes && (!dst_host || !src_dev)) return fail(ctx, RT_ERR_INVALID, "bad copy arguments");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    if (bytes) RT_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return copy_back(ctx, dst_host, src_dev, bytes);
 }
 
 int rt_synchronize(rt_ctx *ctx) {

@@ -1,15 +1,51 @@
-// rt_host_ctx.hip.h -- host side of libraytrace_hip.so, part 1 of 4 (textually included by rt_capi.hip, one translation unit): the context (rt_ctx), its knobs
-// (environment variables read once per context), device buffers, error reporting, the stream a call runs on when the caller passes none.
+// rt_host_ctx.hip.h -- host side of libraytrace_hip.so, part 1 of 4 (textually included by rt_capi.hip, one translation unit): the owning handles (DevBuf, Event, Stream:
+// whoever declares one owns it, its destructor gives it back), the context (rt_ctx: its buffers list themselves in rt_ctx::bufs as they are declared, ~rt_ctx waits for
+// the context's streams and the members do the rest), its knobs (environment variables read once per context), error reporting, the stream a call runs on when the
+// caller passes none.
 #pragma once
 
 namespace {
 
 thread_local std::string g_last_error;
 
+// Device memory.  A context's buffer is declared `DevBuf x{bufs};` and is thereby on the list rt_ctx_selfcheck walks; a temporary takes the default constructor.
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    explicit DevBuf(std::vector<DevBuf *> &list) { list.push_back(this); }
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~DevBuf() { release(); }
     void release() { if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "a DevBuf owns its memory: it moves, it is never copied");
+
+// N buffers of a context (the elements of a plain array member could not each be handed the list)
+template <int N>
+struct DevBufs {
+    DevBuf b[N];
+    explicit DevBufs(std::vector<DevBuf *> &list) { for (DevBuf &x : b) list.push_back(&x); }
+    DevBuf &operator[](int k) { return b[k]; }
+};
+
+// An event / a stream of the owner's: null until create(), which returns the runtime's status; reads as the raw handle wherever one is expected.
+struct Event {
+    hipEvent_t h = nullptr;
+    Event() = default;
+    Event(const Event &) = delete; Event &operator=(const Event &) = delete;
+    ~Event() { if (h) (void)hipEventDestroy(h); }
+    hipError_t create(unsigned flags = hipEventDefault) { const hipError_t e = hipEventCreateWithFlags(&h, flags); if (e != hipSuccess) h = nullptr; return e; }
+    operator hipEvent_t() const { return h; }
+};
+struct Stream {
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete; Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (h) (void)hipStreamDestroy(h); }
+    hipError_t create() { const hipError_t e = hipStreamCreateWithFlags(&h, hipStreamNonBlocking); if (e != hipSuccess) h = nullptr; return e; }
+    hipError_t create(int priority) { const hipError_t e = hipStreamCreateWithPriority(&h, hipStreamNonBlocking, priority); if (e != hipSuccess) h = nullptr; return e; }
+    operator hipStream_t() const { return h; }
 };
 
 }  // namespace
@@ -108,31 +144,33 @@ static Knobs read_knobs() {
 struct rt_ctx {
     int device = 0;
     Knobs knobs;
-    hipStream_t stream_ = nullptr;                                   // the context's own stream: created when first needed (own_stream)
-    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+    Stream stream_;                                                  // the context's own stream: created when first needed (own_stream)
+    Event ev_k0, ev_k1, ev_t0, ev_t1;
+    std::vector<DevBuf *> bufs;                                      // every device buffer of the context: each one's declaration below puts it here (rt_ctx_selfcheck)
     bool have_scene = false, have_kernel_time = false, have_tonemap_time = false;
     rtk::Scene scene{};
-    DevBuf nrm;                                                     // smooth shading: 3 normals per triangle, visit order
+    DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.
-    DevBuf tex_uv, tex_table, tex_img[rtk::kMaxObjects];
+    DevBuf tex_uv{bufs}, tex_table{bufs};
+    DevBufs<rtk::kMaxObjects> tex_img{bufs};
     rtk::TexDesc tex_desc[rtk::kMaxObjects] = {};
     int tex_mask = 0;
     std::vector<int> tri_perm;                                       // visit order -> triangle index in the uploaded (BVH-order) arrays
     std::vector<int> up_indices;                                     // vertex indices of the uploaded triangles, 3 per triangle
     int n_up_tris = 0;
-    DevBuf tidx_up;                                                  // the same on the device (int4 per triangle)
-    DevBuf bb_idx, bb_cnt, bb_pa, bb_pb, bb_tmp, bb_nodes_i, bb_nodes_f, bb_counter, bb_lvl, bb_size, bb_pre, bb_arr;   // device BVH build scratch
-    DevBuf left_dev, lvl_nodes, lvl_off;                             // tree topology for the device-side refit
-    DevBuf lb_pool, lb_pool2, perm_dev;                              // LBVH builder / layout scratch (rt_lbvh.hip.h), carved pools; visit rank -> uploaded index on the device
+    DevBuf tidx_up{bufs};                                             // the same on the device (int4 per triangle)
+    DevBuf bb_idx{bufs}, bb_cnt{bufs}, bb_pa{bufs}, bb_pb{bufs}, bb_tmp{bufs}, bb_nodes_i{bufs}, bb_nodes_f{bufs}, bb_counter{bufs}, bb_lvl{bufs}, bb_size{bufs}, bb_pre{bufs}, bb_arr{bufs};   // device BVH build scratch
+    DevBuf left_dev{bufs}, lvl_nodes{bufs}, lvl_off{bufs};           // tree topology for the device-side refit
+    DevBuf lb_pool{bufs}, lb_pool2{bufs}, perm_dev{bufs};            // LBVH builder / layout scratch (rt_lbvh.hip.h), carved pools; visit rank -> uploaded index on the device
     rtk::LbvhArgs lb_args{};                                         // the builder's arrays of the last LBVH build (valid until the next one)
     bool host_mesh_stale = false;                                    // tri_perm / up_indices describe an older layout: the device copies (perm_dev, tidx_up) are current
     int lbvh_host_install = 0;                                       // RT_LBVH_HOST_INSTALL=1: re-lay an LBVH tree out on the host, as the reference-mode rebuild does (tests compare the two)
     rt_build_stats build{};                                          // what the last rt_mesh_rebuild_mode did
     int n_levels = 0;
-    DevBuf nodesh, tri2leaf;                                        // 16-bit fixed-point sibling pairs and the triangle -> leaf table (rt_qnodes.hip.h)
-    DevBuf leaflh;                                                  // (lo, hi) of each triangle's leaf, by triangle (the flagged-leaf check of the fixed-point kernels)
-    DevBuf nodesw, qdp_parent, qdp_cnt, qdp_g, qdp_ch;              // 4-wide fixed-point nodes (RT_TRAVQ_QW) and the scratch of the DP that picks which four nodes a quad holds (rt_qnodes.hip.h)
+    DevBuf nodesh{bufs}, tri2leaf{bufs};                            // 16-bit fixed-point sibling pairs and the triangle -> leaf table (rt_qnodes.hip.h)
+    DevBuf leaflh{bufs};                                            // (lo, hi) of each triangle's leaf, by triangle (the flagged-leaf check of the fixed-point kernels)
+    DevBuf nodesw{bufs}, qdp_parent{bufs}, qdp_cnt{bufs}, qdp_g{bufs}, qdp_ch{bufs};   // 4-wide fixed-point nodes (RT_TRAVQ_QW) and the scratch of the DP that picks which four nodes a quad holds (rt_qnodes.hip.h)
     unsigned chain_nonce[8] = {};                                   // launch chains started so far, PER SUB-FRAME (WfState::nonce): every part owns its own region of the ray queue, so each
                                                                     // region must cycle through all four values (one context-wide counter gave a part only two of them with two parts: ADVICE round 4)
     int q16_leaf_shift = 0;                                         // where a leaf's triangle count sits in its payload word (rtk::q16_leaf_shift), 0 = leaves too large
@@ -154,21 +192,21 @@ struct rt_ctx {
     std::vector<float> forest_arr;                                  // the forest's bvh_arr10 as installed (build_forest): topology and triangle ranges of every mesh (boxes: see pre_of)
     std::vector<int> pre_of;                                        // forest_arr index -> pre-order index of the same node on the device (node_lo / node_hi hold its current box)
     int n_syn = 0, syn[rtk::kMaxSynthetic] = {};                    // the forest's synthetic union nodes (pre-order indices): refit_kernel widens them as build_forest does
-    DevBuf node_lo, node_hi, nodes2, nodesq, nodesb, q2thr, tri, verts, tidx, scratch_rgba, scratch_rgb8, work, queue;
+    DevBuf node_lo{bufs}, node_hi{bufs}, nodes2{bufs}, nodesq{bufs}, nodesb{bufs}, q2thr{bufs}, tri{bufs}, verts{bufs}, tidx{bufs}, scratch_rgba{bufs}, scratch_rgb8{bufs}, work{bufs}, queue{bufs};
     int n_cus = 0;
-    DevBuf wfM, wfT, wfLS, wfSID, wfSamp;                     // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
-    DevBuf wfALB;                                                   // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
-    DevBuf wfQR;                                                    // traversal queue in slot order: the rays (32 B each)
-    DevBuf pathSamp, pathT;                                         // wf_path with num_rays > 1: per-sample colours, running sum
-    DevBuf dbgbuf;                                                  // -DRT_DEBUG builds: per-wave traversal records
-    DevBuf batch_dev;                                               // rt_render_device_batch: the frames' descriptors, one copy per sub-frame
-    DevBuf anim_dev;                                                // rt_render_device_batch_scenes: the frames' lights and sphere poses (rtk::AnimFrame), one copy per sub-frame
-    DevBuf aovM, aovQR;                                             // rt_render_aov*: traversal results and ray queue of its own (the render path's are never touched)
-    DevBuf aov_state;                                               // rt_render_aov_surface*: one record per pixel between the rounds of its chain (rtk::SurfState)
-    DevBuf dn_tmp;                                                  // rt_denoise*: the ping-pong frame of the passes
-    DevBuf dnv_var[2];                                              // rt_denoise_var*: the variance planes between passes
-    DevBuf post_io;                                                 // the host forms of rt_render_aov*, rt_denoise*, rt_temporal_accumulate, rt_[de]modulate: inputs and result (staged, rt_host_post.hip.h)
-    DevBuf accum;                                                   // progressive mode: sum of the frames so far (float4 per pixel)
+    DevBuf wfM{bufs}, wfT{bufs}, wfLS{bufs}, wfSID{bufs}, wfSamp{bufs};   // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
+    DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
+    DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
+    DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum
+    DevBuf dbgbuf{bufs};                                            // -DRT_DEBUG builds: per-wave traversal records
+    DevBuf batch_dev{bufs};                                         // rt_render_device_batch: the frames' descriptors, one copy per sub-frame
+    DevBuf anim_dev{bufs};                                          // rt_render_device_batch_scenes: the frames' lights and sphere poses (rtk::AnimFrame), one copy per sub-frame
+    DevBuf aovM{bufs}, aovQR{bufs};                                 // rt_render_aov*: traversal results and ray queue of its own (the render path's are never touched)
+    DevBuf aov_state{bufs};                                         // rt_render_aov_surface*: one record per pixel between the rounds of its chain (rtk::SurfState)
+    DevBuf dn_tmp{bufs};                                            // rt_denoise*: the ping-pong frame of the passes
+    DevBufs<2> dnv_var{bufs};                                        // rt_denoise_var*: the variance planes between passes
+    DevBuf post_io{bufs};                                           // the host forms of rt_render_aov*, rt_denoise*, rt_temporal_accumulate, rt_[de]modulate: inputs and result (staged, rt_host_post.hip.h)
+    DevBuf accum{bufs};                                             // progressive mode: sum of the frames so far (float4 per pixel)
     int prog_frames = 0, prog_w = 0, prog_h = 0;
     uint64_t qf_sig = 0;                                            // layout the queue flags were last zeroed for
     // workgroups per CU of the kernels whose grid is sized by it (blocks_per_cu: asked once, 0 = not yet), each slot + STATS: wf_trav; wf_travq (+ 2 * (R == 32) + 4 * (R == 128));
@@ -176,14 +214,14 @@ struct rt_ctx {
     enum { kOccTrav = 0, kOccTravq = 2, kOccTravqQw = 8, kOccPersist = 10, kOccSlots = 12 };
     int occ_blocks[kOccSlots] = {};
     static constexpr int kMaxParts = 8;
-    hipStream_t part_stream[kMaxParts] = {};
-    hipEvent_t part_ev[kMaxParts] = {};
-    hipEvent_t fork_ev = nullptr;
+    Stream part_stream[kMaxParts];
+    Event part_ev[kMaxParts];
+    Event fork_ev;
     // Chains on streams of their own (start_chains / end_chains): consecutive chunks of one call -- and, with rt_ctx_set_pipelining, consecutive
     // frames into different buffers -- follow each other per sub-frame without a join in between.
     struct Pipe {
         bool on = false;                   // rt_ctx_set_pipelining: frames of consecutive calls may overlap
-        hipEvent_t fork2[2] = {};          // the caller's stream at the start of this call / of the previous one
+        Event fork2[2];                    // the caller's stream at the start of this call / of the previous one
         int cur = 0;
         bool valid = false, prev_valid = false;   // the call before this one ended with its chains on their own streams (joined into `stream`)
         int open_parts = 0;                // chains of an earlier chunk of THIS call that have not been joined into the caller's stream
@@ -205,19 +243,31 @@ struct rt_ctx {
     bool trav_attr_set = false;
     bool stats_on = false;                                          // rt_stats_enable: bracket the traversal launches with timing events (production frames record none)
     static constexpr int kSlots = 2;                                // rt_render_async: double-buffered device frames, one copy stream
-    DevBuf slot_rgba[kSlots], slot_rgb8[kSlots];
-    hipEvent_t slot_rendered[kSlots] = {}, slot_done[kSlots] = {};
+    DevBufs<kSlots> slot_rgba{bufs}, slot_rgb8{bufs};
+    Event slot_rendered[kSlots], slot_done[kSlots];
     bool slot_pending[kSlots] = {false, false};
-    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr;      // two copy streams: the halves of a frame go out through two DMA engines
-    hipEvent_t slot_half[kSlots] = {};
+    Stream copy_stream, copy_stream2;                               // two copy streams: the halves of a frame go out through two DMA engines
+    Event slot_half[kSlots];
     bool travq_ok = true;                                           // the uploaded tree fits wf_travq's entry formats (leaf sizes, triangle offsets)
     static constexpr int kMaxTravEvents = 2 * RT_MAX_SEGMENTS;
-    hipEvent_t ev_trav[2 * kMaxTravEvents] = {};
-    hipEvent_t ev_adv[2 * kMaxTravEvents] = {};                     // ... and of the uniform kernel's launches (rt_stats_enable)
+    Event ev_trav[2 * kMaxTravEvents];
+    Event ev_adv[2 * kMaxTravEvents];                               // ... and of the uniform kernel's launches (rt_stats_enable)
     int n_trav_events = 0, n_adv_events = 0, adv_paths = 0;
     rt_stats stats{};
     std::string err;
     char name[256] = {0};
+
+    rt_ctx() = default;
+    rt_ctx(const rt_ctx &) = delete; rt_ctx &operator=(const rt_ctx &) = delete;   // (bufs points at the members; a context lives on the heap from rt_ctx_create to rt_ctx_destroy)
+    // Ordering, not ownership: nothing of the context is given back while one of its streams still runs -- its own, the sub-frame chains of frames issued on a caller's
+    // stream, the copies of rt_render_async.  The members then release themselves.
+    ~rt_ctx() {
+        (void)hipSetDevice(device);
+        if (stream_) (void)hipStreamSynchronize(stream_);
+        for (hipStream_t q : part_stream) if (q) (void)hipStreamSynchronize(q);
+        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+        if (copy_stream2) (void)hipStreamSynchronize(copy_stream2);
+    }
 };
 
 namespace {
@@ -228,8 +278,8 @@ namespace {
 hipStream_t own_stream(rt_ctx *ctx) {
     if (!ctx->stream_) {
         (void)hipSetDevice(ctx->device);
-        const hipError_t e = hipStreamCreateWithFlags(&ctx->stream_, hipStreamNonBlocking);
-        if (e != hipSuccess) { ctx->stream_ = nullptr; (void)hipGetLastError(); ctx->err = std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e); g_last_error = ctx->err; }
+        const hipError_t e = ctx->stream_.create();
+        if (e != hipSuccess) { (void)hipGetLastError(); ctx->err = std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e); g_last_error = ctx->err; }
     }
     return ctx->stream_;   // nullptr: the entry points fail with RT_ERR_HIP (RT_OWN_STREAM) rather than fall back to the legacy default stream
 }

@@ -1,6 +1,7 @@
 // rt_host_post.hip.h -- host side of libraytrace_hip.so (textually included by rt_capi.hip, one translation unit, after rt_host_ctx.hip.h and before everything that issues
 // work): what the device entries and the post-process stages (rt_aov*.hip.h, rt_denoise.hip.h, rt_temporal.hip.h, rt_demodulate.hip.h) share -- the stream a call runs on,
-// the note a pipelined render needs of it, the argument checks they have in common, and the staging of a host form through one buffer of the context.
+// the note a pipelined render needs of it, the argument checks they have in common, the copy to the host that ends a host form, the opening of the render entries' row-range host forms, and the staging
+// of a post-process host form through one buffer of the context.
 #pragma once
 #include <initializer_list>
 
@@ -42,6 +43,26 @@ int check_frame_size(rt_ctx *ctx, int width, int height) {
     return RT_OK;
 }
 
+// Device -> host on the context's stream (which exists: RT_OWN_STREAM), complete on return: how a host form ends.  bytes == 0: only the wait.
+int copy_back(rt_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes) {
+    if (bytes) RT_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    return RT_OK;
+}
+
+// How the host forms over the image rows [row_begin, row_end) open (rt_render, rt_render_rgb8, rt_count_work; rt_render_pose: every row): the arguments, the context's
+// stream, scratch_rgba with room for the rows.  rows: the range as one tile; npix: its pixels.  `out` is only looked at for NULL.
+int host_rows(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, const void *out, rt_rows &rows, int64_t &npix) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!p || !out) return fail(ctx, RT_ERR_INVALID, "params/out is NULL");
+    if (row_begin < 0 || row_end < row_begin || row_end > p->height) return fail(ctx, RT_ERR_INVALID, "bad row range [%d,%d)", row_begin, row_end);
+    const int n = row_end - row_begin;
+    npix = (int64_t)n * (p->width > 0 ? p->width : 0);
+    rows = rt_rows{row_begin, n, n > 0 ? n : 1, 1};
+    return ensure(ctx, ctx->scratch_rgba, (size_t)npix * sizeof(float4));
+}
+
 // A host form on top of its device form.  One buffer of the context (post_io: every host form synchronises before it returns, so no two hold it at once) takes the
 // input segments one behind the other (a segment without a pointer keeps its room and is not copied) and the result, out_bytes at out_off; device(base) issues the
 // device form on the context's stream over that buffer; then the result goes to out_host and the stream is waited for.
@@ -60,9 +81,7 @@ int staged(rt_ctx *ctx, std::initializer_list<HostSeg> in, size_t out_off, size_
         off += s.bytes;
     }
     if ((rc = device(base)) != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(out_host, base + out_off, out_bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
-    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
-    return RT_OK;
+    return copy_back(ctx, out_host, base + out_off, out_bytes);
 }
 
 }  // namespace

@@ -225,9 +225,9 @@ int need_part_streams(rt_ctx *ctx, int parts, bool chain0 = false) {
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
             const int pr = (ctx->knobs.part_prio && (j & 1)) ? hi : 0;       // (never the LOW class for a chain: the classes do prioritise, and a low chain next to a high one runs after it, not beside it)
-            RT_HIP(ctx, hipStreamCreateWithPriority(&ctx->part_stream[j], hipStreamNonBlocking, pr));
+            RT_HIP(ctx, ctx->part_stream[j].create(pr));
         }
-        if (!ctx->part_ev[j]) RT_HIP(ctx, hipEventCreateWithFlags(&ctx->part_ev[j], hipEventDisableTiming));
+        if (!ctx->part_ev[j]) RT_HIP(ctx, ctx->part_ev[j].create(hipEventDisableTiming));
     }
     return RT_OK;
 }
@@ -235,8 +235,8 @@ int need_copy_streams(rt_ctx *ctx, bool second) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
     const int pr = ctx->knobs.copy_prio > 0 ? lo : ctx->knobs.copy_prio < 0 ? hi : 0;   // (fixed; RT_COPY_PRIO was an environment knob until round 5) 1 = the low-priority class' queue pool, -1 = the high one
-    if (!ctx->copy_stream) RT_HIP(ctx, hipStreamCreateWithPriority(&ctx->copy_stream, hipStreamNonBlocking, pr));
-    if (second && !ctx->copy_stream2) RT_HIP(ctx, hipStreamCreateWithPriority(&ctx->copy_stream2, hipStreamNonBlocking, pr));
+    if (!ctx->copy_stream) RT_HIP(ctx, ctx->copy_stream.create(pr));
+    if (second && !ctx->copy_stream2) RT_HIP(ctx, ctx->copy_stream2.create(pr));
     return RT_OK;
 }
 
@@ -548,7 +548,7 @@ int start_chains(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool qr_grown, boo
     hipEvent_t start_ev = ctx->fork_ev;
     bool fork = parts > 1;
     if (own0) {
-        if (!pl.fork2[0]) { RT_HIP(ctx, hipEventCreateWithFlags(&pl.fork2[0], hipEventDisableTiming)); RT_HIP(ctx, hipEventCreateWithFlags(&pl.fork2[1], hipEventDisableTiming)); }
+        if (!pl.fork2[0]) { RT_HIP(ctx, pl.fork2[0].create(hipEventDisableTiming)); RT_HIP(ctx, pl.fork2[1].create(hipEventDisableTiming)); }
         if (pl.call_chunk == 0) {
             const bool disjoint = pl.call_hi <= pl.out_lo || pl.out_hi <= pl.call_lo;
             bool hazard = pl.between_overflow;                       // a library call younger than the previous render call touches this frame's buffer (or: too many to tell)

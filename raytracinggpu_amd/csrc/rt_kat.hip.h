@@ -189,7 +189,7 @@ int kat_run(rt_ctx *ctx, const float *in, int n, int width, float *out, int owid
     DevBuf din, dout, dcnt;
     int rc;
     if ((rc = upload(ctx, din, in, (size_t)n * width * sizeof(float))) != RT_OK || (rc = ensure(ctx, dout, (size_t)n * owidth * sizeof(float))) != RT_OK ||
-        (rc = ensure(ctx, dcnt, 4 * sizeof(unsigned long long))) != RT_OK) { din.release(); dout.release(); dcnt.release(); return rc; }
+        (rc = ensure(ctx, dcnt, 4 * sizeof(unsigned long long))) != RT_OK) return rc;
     hipError_t e = hipMemsetAsync(dcnt.p, 0, 4 * sizeof(unsigned long long), own_stream(ctx));
     if (e == hipSuccess) {
         launch(static_cast<const float *>(din.p), static_cast<float *>(dout.p), static_cast<unsigned long long *>(dcnt.p), dim3((unsigned)((n + 255) / 256)), dim3(256));
@@ -199,7 +199,6 @@ int kat_run(rt_ctx *ctx, const float *in, int n, int width, float *out, int owid
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, (size_t)n * owidth * sizeof(float), hipMemcpyDeviceToHost, own_stream(ctx));
     if (e == hipSuccess) e = hipMemcpyAsync(h, dcnt.p, sizeof(h), hipMemcpyDeviceToHost, own_stream(ctx));
     if (e == hipSuccess) e = hipStreamSynchronize(own_stream(ctx));
-    din.release(); dout.release(); dcnt.release();
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "KAT launch: %s", hipGetErrorString(e));
     if (counts) { counts->n = (uint64_t)n; counts->box_decided = h[0]; counts->box_literal = h[1]; counts->tri_decided = h[2]; counts->tri_literal = h[3]; }
     return RT_OK;
@@ -259,8 +258,7 @@ int rt_kat_layout_hash(rt_ctx *ctx, uint64_t out[4]) {
         out[k] = 0;
         if (!src[k] || sc.n_nodes <= 0) continue;
         h.resize(bytes[k]);
-        RT_HIP(ctx, hipMemcpyAsync(h.data(), src[k], bytes[k], hipMemcpyDeviceToHost, own_stream(ctx)));
-        RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+        if (int rc = copy_back(ctx, h.data(), src[k], bytes[k]); rc != RT_OK) return rc;
         uint64_t x = 0xcbf29ce484222325ull;
         for (unsigned char c : h) x = (x ^ c) * 0x100000001b3ull;
         out[k] = x ? x : 1;

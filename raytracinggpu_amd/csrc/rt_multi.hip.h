@@ -102,18 +102,31 @@ struct MultiWorker {
     }
 };
 
+struct CtxDelete { void operator()(rt_ctx *c) const { rt_ctx_destroy(c); } };
 struct rt_multi {
     int n = 0;
     MultiWorker *worker[RT_MAX_DEVICES] = {};   // worker[k] submits device k's work (k >= 1)
-    rt_ctx *ctx[RT_MAX_DEVICES] = {};
+    std::unique_ptr<rt_ctx, CtxDelete> ctx[RT_MAX_DEVICES];   // declared before the buffers and events below, which live on the contexts' devices: destroyed after them
     DevBuf local[RT_MAX_DEVICES];           // dense tiles of device k (on device k)
     DevBuf local8[RT_MAX_DEVICES], rays_k[RT_MAX_DEVICES];   // RGB8 gather: tonemapped tiles and ray count of device k (on device k)
     int peer_access[RT_MAX_DEVICES] = {};   // 1: device k writes into the root's memory directly (peer access), 0: staged by the runtime, -1: k is the root's device
     DevBuf stage, frame, rays;              // on the root device (device of ctx[0])
-    hipEvent_t done[RT_MAX_DEVICES] = {};   // device k's tiles have arrived on the root
-    hipEvent_t g0 = nullptr, g1 = nullptr;
+    Event done[RT_MAX_DEVICES];             // device k's tiles have arrived on the root
+    Event g0, g1;
     rt_multi_stats stats{};
     std::string err;
+
+    rt_multi() = default;
+    rt_multi(const rt_multi &) = delete; rt_multi &operator=(const rt_multi &) = delete;
+    // Ordering, not ownership: no submit thread is left, and no context's stream still runs, when the members release themselves
+    ~rt_multi() {
+        for (int k = 1; k < RT_MAX_DEVICES; ++k) if (worker[k]) { worker[k]->stop(); delete worker[k]; }
+        for (int k = 0; k < n; ++k) {
+            if (!ctx[k]) continue;
+            (void)hipSetDevice(ctx[k]->device);
+            if (ctx[k]->stream_) (void)hipStreamSynchronize(ctx[k]->stream_);
+        }
+    }
 };
 
 namespace {
@@ -143,7 +156,7 @@ int multi_render(rt_multi *m, const rt_params *p, void *out_dev_on_root, void *o
     const auto t_begin = std::chrono::steady_clock::now();
     const int n = m->n, W = p->width, H = p->height, R = RT_MULTI_TILE_ROWS;
     const int n_tiles = (H + R - 1) / R;
-    rt_ctx *root = m->ctx[0];
+    rt_ctx *root = m->ctx[0].get();
     size_t off[RT_MAX_DEVICES + 1] = {0};
     int nrows[RT_MAX_DEVICES] = {0};
     for (int k = 0; k < n; ++k) {
@@ -158,21 +171,21 @@ int multi_render(rt_multi *m, const rt_params *p, void *out_dev_on_root, void *o
     if ((rc = ensure(root, m->stage, stage_off(n) + 16)) != RT_OK || (rc = ensure(root, m->rays, 8)) != RT_OK ||
         (!out_dev_on_root && (rc = ensure(root, m->frame, frame_bytes)) != RT_OK)) { m->err = root->err; return rc; }
     for (int k = 0; k < n; ++k)                                             // every device's own stream must exist: no silent fall-back to stream 0
-        if (!own_stream(m->ctx[k])) return mfail(m, RT_ERR_HIP, "device %d: the context's stream: %s", m->ctx[k]->device, m->ctx[k]->err.c_str());
+        if (!own_stream(m->ctx[k].get())) return mfail(m, RT_ERR_HIP, "device %d: the context's stream: %s", m->ctx[k]->device, m->ctx[k]->err.c_str());
     RT_MHIP(m, hipSetDevice(root->device));
     RT_MHIP(m, hipMemsetAsync(m->rays.p, 0, 8, own_stream(root)));
     // 1. every device renders its tiles; peers push them to the root as soon as they are done.  A failure part-way
     //    leaves work in flight on the devices already launched: drain them before returning, so that the caller may
     //    free or reuse its buffers and the next call starts from idle streams.
     auto drain = [&](int launched) {
-        for (int j = 0; j < launched; ++j) { (void)hipSetDevice(m->ctx[j]->device); (void)hipStreamSynchronize(own_stream(m->ctx[j])); }
+        for (int j = 0; j < launched; ++j) { (void)hipSetDevice(m->ctx[j]->device); (void)hipStreamSynchronize(own_stream(m->ctx[j].get())); }
         (void)hipSetDevice(root->device);
     };
     // each device's submission: returns a status, leaves its text in err_k[k] (the submit threads have their own thread-local error)
     int rc_k[RT_MAX_DEVICES] = {};
     std::string err_k[RT_MAX_DEVICES];
     auto submit = [&](int k) -> int {
-        rt_ctx *c = m->ctx[k];
+        rt_ctx *c = m->ctx[k].get();
         int r;
         hipError_t e = hipSetDevice(c->device);
         if (e != hipSuccess) { err_k[k] = std::string("hipSetDevice: ") + hipGetErrorString(e); return RT_ERR_HIP; }
@@ -239,8 +252,8 @@ int multi_render(rt_multi *m, const rt_params *p, void *out_dev_on_root, void *o
         for (int k = 0; k < n; ++k) {
             unsigned long long rk = 0;
             RT_MHIP(m, hipSetDevice(m->ctx[k]->device));
-            RT_MHIP(m, hipMemcpyAsync(&rk, m->rays_k[k].p, 8, hipMemcpyDeviceToHost, own_stream(m->ctx[k])));
-            RT_MHIP(m, hipStreamSynchronize(own_stream(m->ctx[k])));
+            RT_MHIP(m, hipMemcpyAsync(&rk, m->rays_k[k].p, 8, hipMemcpyDeviceToHost, own_stream(m->ctx[k].get())));
+            RT_MHIP(m, hipStreamSynchronize(own_stream(m->ctx[k].get())));
             rays += rk;
         }
         RT_MHIP(m, hipSetDevice(root->device));
@@ -253,7 +266,7 @@ int multi_render(rt_multi *m, const rt_params *p, void *out_dev_on_root, void *o
     RT_MHIP(m, hipEventElapsedTime(&m->stats.gather_ms, m->g0, m->g1));
     for (int k = 0; k < n; ++k) {
         rt_stats s{};
-        if ((rc = rt_get_stats(m->ctx[k], &s)) != RT_OK) { m->err = m->ctx[k]->err; return rc; }
+        if ((rc = rt_get_stats(m->ctx[k].get(), &s)) != RT_OK) { m->err = m->ctx[k]->err; return rc; }
         m->stats.kernel_ms[k] = s.kernel_ms;
         m->stats.device_id[k] = m->ctx[k]->device;
     }
@@ -274,18 +287,20 @@ int rt_multi_create(rt_multi **out, const int *device_ids, int n_devices) {
     if (!m) return mfail(nullptr, RT_ERR_INVALID, "out of host memory");
     m->n = n_devices;
     for (int k = 0; k < n_devices; ++k) {
-        const int rc = rt_ctx_create(&m->ctx[k], device_ids[k]);
+        rt_ctx *c = nullptr;
+        const int rc = rt_ctx_create(&c, device_ids[k]);
         if (rc != RT_OK) { rt_multi_destroy(m); return rc; }
+        m->ctx[k].reset(c);
         m->ctx[k]->knobs.part_prio = 1;                                  // several contexts in one process: see Knobs::part_prio
     }
     for (int k = 1; k < n_devices; ++k) { m->worker[k] = new MultiWorker(); m->worker[k]->start(); }
     m->peer_access[0] = -1;                                               // the root itself
     hipError_t e = hipSetDevice(m->ctx[0]->device);
-    if (e == hipSuccess) e = hipEventCreate(&m->g0);
-    if (e == hipSuccess) e = hipEventCreate(&m->g1);
+    if (e == hipSuccess) e = m->g0.create();
+    if (e == hipSuccess) e = m->g1.create();
     for (int k = 1; k < n_devices && e == hipSuccess; ++k) {
         e = hipSetDevice(m->ctx[k]->device);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->done[k], hipEventDisableTiming);
+        if (e == hipSuccess) e = m->done[k].create(hipEventDisableTiming);
         m->peer_access[k] = -1;                                                            // same device as the root: a local copy
         if (e == hipSuccess && m->ctx[k]->device != m->ctx[0]->device) {
             int can = 0;
@@ -304,22 +319,6 @@ int rt_multi_create(rt_multi **out, const int *device_ids, int n_devices) {
 
 int rt_multi_destroy(rt_multi *m) {
     if (!m) return RT_OK;
-    for (int k = 1; k < RT_MAX_DEVICES; ++k) if (m->worker[k]) { m->worker[k]->stop(); delete m->worker[k]; m->worker[k] = nullptr; }
-    if (m->ctx[0]) {
-        (void)hipSetDevice(m->ctx[0]->device);
-        if (m->ctx[0]->stream_) (void)hipStreamSynchronize(m->ctx[0]->stream_);
-        m->stage.release(); m->frame.release(); m->rays.release();
-        if (m->g0) (void)hipEventDestroy(m->g0);
-        if (m->g1) (void)hipEventDestroy(m->g1);
-    }
-    for (int k = 0; k < m->n; ++k) {
-        if (!m->ctx[k]) continue;
-        (void)hipSetDevice(m->ctx[k]->device);
-        if (m->ctx[k]->stream_) (void)hipStreamSynchronize(m->ctx[k]->stream_);
-        m->local[k].release(); m->local8[k].release(); m->rays_k[k].release();
-        if (m->done[k]) (void)hipEventDestroy(m->done[k]);
-        rt_ctx_destroy(m->ctx[k]);
-    }
     delete m;
     return RT_OK;
 }
@@ -330,7 +329,7 @@ int rt_multi_scene_upload_meshes(rt_multi *m, const rt_sphere *spheres, int n_sp
                                  const rt_light *light, const rt_camera *camera) {
     if (!m) return mfail(nullptr, RT_ERR_INVALID, "multi context is NULL");
     for (int k = 0; k < m->n; ++k) {
-        const int rc = rt_scene_upload_meshes(m->ctx[k], spheres, n_spheres, meshes, n_meshes, light, camera);
+        const int rc = rt_scene_upload_meshes(m->ctx[k].get(), spheres, n_spheres, meshes, n_meshes, light, camera);
         if (rc != RT_OK) { m->err = m->ctx[k]->err; return rc; }
     }
     return RT_OK;

@@ -161,16 +161,15 @@ extern "C" int rt_trace_rays(rt_ctx *ctx, const float *rays, int n, float tri_tm
     hipStream_t q = own_stream(ctx);
     DevBuf din, dout;
     int rc;
-    auto done = [&](int code) { din.release(); dout.release(); return code; };
-    if ((rc = upload(ctx, din, rays, (size_t)n * 6 * sizeof(float))) != RT_OK || (rc = ensure(ctx, dout, (size_t)n * 5 * sizeof(float))) != RT_OK) return done(rc);
+    if ((rc = upload(ctx, din, rays, (size_t)n * 6 * sizeof(float))) != RT_OK || (rc = ensure(ctx, dout, (size_t)n * 5 * sizeof(float))) != RT_OK) return rc;
     unsigned long long *M = nullptr;
-    if ((rc = trace_to_m(ctx, static_cast<const float *>(din.p), n, tri_tmin, variant, M)) != RT_OK) return done(rc);
+    if ((rc = trace_to_m(ctx, static_cast<const float *>(din.p), n, tri_tmin, variant, M)) != RT_OK) return rc;
     hipLaunchKernelGGL(rtk::trace_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, ctx->scene, M, n, static_cast<float *>(dout.p));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, q);
     if (e == hipSuccess) e = hipStreamSynchronize(q);
-    if (e != hipSuccess) return done(fail(ctx, RT_ERR_HIP, "rt_trace_rays: %s", hipGetErrorString(e)));
-    return done(RT_OK);
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "rt_trace_rays: %s", hipGetErrorString(e));
+    return RT_OK;
 }
 
 extern "C" int rt_kat_surface(rt_ctx *ctx, const float *rays, int n, float tri_tmin, float *out) {
@@ -191,16 +190,15 @@ extern "C" int rt_kat_surface(rt_ctx *ctx, const float *rays, int n, float tri_t
     }
     DevBuf din, dout, dloc;
     int rc;
-    auto done = [&](int code) { din.release(); dout.release(); dloc.release(); return code; };
     if ((rc = upload(ctx, din, rays, (size_t)n * 6 * sizeof(float))) != RT_OK || (rc = ensure(ctx, dout, (size_t)n * 8 * sizeof(float))) != RT_OK ||
-        (rc = upload(ctx, dloc, local.data(), local.size() * sizeof(int))) != RT_OK) return done(rc);
+        (rc = upload(ctx, dloc, local.data(), local.size() * sizeof(int))) != RT_OK) return rc;
     unsigned long long *M = nullptr;
-    if ((rc = trace_to_m(ctx, static_cast<const float *>(din.p), n, tri_tmin, RT_VARIANT_WAVEFRONT_QUEUE, M)) != RT_OK) return done(rc);
+    if ((rc = trace_to_m(ctx, static_cast<const float *>(din.p), n, tri_tmin, RT_VARIANT_WAVEFRONT_QUEUE, M)) != RT_OK) return rc;
     hipLaunchKernelGGL(rtk::kat_surface_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, ctx->scene, tex_scene(ctx), M, static_cast<const float *>(din.p),
                        static_cast<const int *>(dloc.p), n, static_cast<float *>(dout.p));
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, (size_t)n * 8 * sizeof(float), hipMemcpyDeviceToHost, q);
     if (e == hipSuccess) e = hipStreamSynchronize(q);
-    if (e != hipSuccess) return done(fail(ctx, RT_ERR_HIP, "rt_kat_surface: %s", hipGetErrorString(e)));
-    return done(RT_OK);
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "rt_kat_surface: %s", hipGetErrorString(e));
+    return RT_OK;
 }
