@@ -68,7 +68,7 @@ __host__ __device__ inline float lbvh_fkey_inv(unsigned int k) {
 __device__ __forceinline__ f3 lbvh_centroid(const LbvhArgs &a, int t) {
     const int4 ix = a.tidx_up[t];
     const float4 A = a.verts[ix.x], B = a.verts[ix.y], C = a.verts[ix.z];
-    return mk((A.x + B.x + C.x) * (1.f / 3.f), (A.y + B.y + C.y) * (1.f / 3.f), (A.z + B.z + C.z) * (1.f / 3.f));   // quality only: any rounding will do
+    return mk((A.x + B.x + C.x) * (1.f / 3.f), (A.y + B.y + C.y) * (1.f / 3.f), (A.z + B.z + C.z) * (1.f / 3.f));   // ((A + B) + C) * float(1 / 3): this rounding is pinned, with the rest of the builder, by tests/lbvh_model.py
 }
 
 __global__ __launch_bounds__(256) void lbvh_bounds_kernel(const LbvhArgs a) {

@@ -9,6 +9,8 @@ import pytest
 
 import raytracinggpu_amd as rt
 from raytracinggpu_amd import hostlib
+from .lbvh_fixtures import displaced_grid as _displaced_grid
+from .lbvh_model import check_tree as _check_tree
 from .test_gpu_parity import _synthetic_mesh, values_equal
 
 pytestmark = pytest.mark.gpu
@@ -20,36 +22,6 @@ def ctx():
     c = rt.Context(0)
     yield c
     c.close()
-
-
-def _check_tree(arr, order, n_tris):
-    """A proper tree in the reference's flat layout: every node reachable once, leaves of 1..32 triangles covering [0, n) exactly."""
-    n = len(arr)
-    assert sorted(order.tolist()) == list(range(n_tris))
-    seen = np.zeros(n, bool)
-    covered = np.zeros(n_tris, np.int32)
-    stack = [0]
-    leaves = 0
-    while stack:
-        k = stack.pop()
-        assert 0 <= k < n and not seen[k]
-        seen[k] = True
-        l, r, s, e = int(arr[k, 0]), int(arr[k, 1]), int(arr[k, 8]), int(arr[k, 9])
-        assert 0 <= s < e <= n_tris
-        assert (arr[k, 2:5] <= arr[k, 5:8]).all()
-        if l < 0:
-            assert r < 0 and e - s <= 32
-            covered[s:e] += 1
-            leaves += 1
-        else:
-            assert e - s > 2
-            for c in (l, r):                                            # children nest inside the parent, ranges partition the parent's
-                assert (arr[c, 2:5] >= arr[k, 2:5]).all() and (arr[c, 5:8] <= arr[k, 5:8]).all()
-            assert {int(arr[l, 8]), int(arr[r, 8])} >= {s} and {int(arr[l, 9]), int(arr[r, 9])} >= {e}
-            assert int(arr[l, 9]) - int(arr[l, 8]) + int(arr[r, 9]) - int(arr[r, 8]) == e - s
-            stack += [l, r]
-    assert seen.all() and (covered == 1).all()
-    return leaves
 
 
 def _lbvh_against_oracle(ctx, oracle, v, tris_uploaded, W, H, bounces=(0, 2), counters=True):
@@ -167,17 +139,6 @@ def test_lbvh_large_mesh_bit_exact_and_much_less_work(ctx, oracle, n, monkeypatc
     assert own["rays"] == work["rays"] and own["tri_tests"] >= work["tri_tests"]
     assert 0 < own["steps"]["box_steps"] * 64 * 4 < 2 * work["box_tests"] and own["steps"]["serial_drains"] == 0
     assert owns["1"]["rays"] == work["rays"] and owns["1"]["tri_tests"] <= own["tri_tests"] and owns["1"]["steps"]["serial_drains"] == 0
-
-
-def _displaced_grid(n, seed=11):
-    rng = np.random.default_rng(seed)
-    gx, gz = np.meshgrid(np.linspace(-18, 18, n), np.linspace(-14, 22, n), indexing="ij")
-    gy = -9.0 + 3.0 * np.sin(gx * 0.45) * np.cos(gz * 0.38) + 0.15 * rng.standard_normal((n, n))
-    v = np.stack([gx, gy, gz], -1).reshape(-1, 3).astype(np.float32)
-    i, j = np.meshgrid(np.arange(n - 1), np.arange(n - 1), indexing="ij")
-    a = (i * n + j).reshape(-1)
-    t = np.concatenate([np.stack([a, a + 1, a + n], 1), np.stack([a + 1, a + n + 1, a + n], 1)]).astype(np.int32)
-    return v, t
 
 
 @pytest.mark.parametrize("qw", ["default", "0"])
