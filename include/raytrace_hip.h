@@ -578,11 +578,29 @@ int rt_denoise(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host,
  *         wc = 1 if dl dl == 0, else max(0, 1 - (dl dl) / D),  dl = l(C_p) - l(C_q),  D = k_sigma V_p + var_floor   (replaces the k_color 4^k term);
  *         and with every tap taken (w > 0): SV += (w w) V_q;   V_out = SV / (W W);   a miss keeps its V.
  *     k_sigma has no unit; var_floor is in the caller's colour units squared.  Output: the filtered colour alone (.w = the history's).
+ *     rt_svgf_filter*: rt_denoise_var's inputs (the two history planes of rt_temporal_accumulate*, three guide planes) and its passes, with two switches that finish
+ *     SVGF.  Same contract: binary32, one rounding per operation, no contraction, sums left to right with dy outer and dx inner, quotients correctly rounded.  Pass k
+ *     (step s = 2^k) is rt_denoise_var's pass word for word, except:
+ *       PRE-FILTER (prefilter == 1).  For a pixel p with id_p != -1, over the pass's input variance V: for dy = -1 .. 1 (outer), dx = -1 .. 1 (inner),
+ *       q = (x + dx s, y + dy s), skipped if outside the image or id_q != id_p:
+ *         g = G[|dy|] * G[|dx|], G = {1/2, 1/4}   (1/4, 1/8, 1/16: exact);   SG += g V_q;   WG += g;
+ *         Vg = SG / WG;   D = k_sigma Vg + var_floor   (replaces D = k_sigma V_p + var_floor).
+ *       The taps are the pass's own sub-image neighbours: pass 0 is the textbook 3 x 3 Gaussian, later passes smooth at their own step a variance the earlier
+ *       passes have already filtered at theirs (a deviation from implementations that always use step 1).  Only D changes: the variance carried to the next pass
+ *       is still V_out = SV / (W W) over the unfiltered V_q.
+ *       FEEDBACK (feedback_pass == f >= 0).  out_history is a complete history, fit to be the next rt_temporal_accumulate*'s prev_history: plane 0 = (.rgb of pass
+ *       f's output, .w of the input history's plane 0); plane 1 = the input history's plane 1, bit for bit -- moments, length and variance stay those of the raw
+ *       luminance; only colour is fed back.
+ *     With prefilter == 0 and feedback_pass == -1 the output is rt_denoise_var's bit for bit.  out_history is NULL exactly when feedback_pass == -1.
+ *     RT_ERR_INVALID, both outputs untouched: any other combination of out_history and feedback_pass; prefilter outside {0, 1}; feedback_pass outside
+ *     [-1, n_passes - 1]; everything rt_denoise_var* refuses; any overlap of either output with an input or with the other output.
  *     NON-FINITE INPUTS (all three entries).  min and max above are IEEE minNum and maxNum: of a NaN and a number they give the number; comparisons with a NaN are
  *     false.  So a NaN distance (a NaN in a normal, a position, an albedo, a variance, or in a colour while k_color != 0) makes its term 0 and the tap weigh nothing:
  *     a NaN in a guide or a colour changes no OTHER pixel, unless k_color == 0 in rt_denoise, where a non-finite colour is summed into every pixel whose stencil
  *     takes it (rt_denoise_var's luminance term always weighs it 0).  A pixel whose own weights all vanish -- its own N, P or A is NaN, or its colour is non-finite while k_color != 0 -- is 0 / 0 = NaN in .rgb.
  *     A variance of NaN or 0 with var_floor 0 leaves the taps of equal luminance (the pixel itself among them); the filtered variance carries NaN and Inf on.
+ *     rt_svgf_filter's Gaussian excludes no tap for a non-finite V_q: a NaN variance makes Vg and so D NaN for up to nine pixels (the pixels of its object within
+ *     one step of it), which then keep only their taps of equal luminance; an Inf variance makes their D Inf (or NaN where k_sigma == 0) likewise.
  *     rt_temporal_accumulate: a NaN in N', P', gx or gy reuses no history; a NaN n_q gives n = max_history; NaN moments, or a non-finite colour among the neighbours of the spatial estimate, give V = max(0, NaN) = 0; a NaN in the
  *     previous history's colour or moments is blended like a number and so stays in that surface point's history until its tap is rejected.  Non-finite history is
  *     not rejected.  The sign and payload of a NaN written are not specified.
@@ -610,6 +628,14 @@ int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_rgba_dev, const
 int rt_temporal_accumulate(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, const float *prev_aov_host, const float *prev_history_host, int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, float *out_history_host);
 int rt_denoise_var_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_denoise_var_params *vp, void *out_rgba_dev, void *stream);
 int rt_denoise_var(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_denoise_var_params *vp, float *out_rgba_host);
+typedef struct rt_svgf_params {
+    int32_t n_passes;              /* 1 .. RT_DENOISE_MAX_PASSES                                                    */
+    int32_t feedback_pass;         /* -1: none; else 0 .. n_passes - 1: this pass's colour goes into out_history    */
+    int32_t prefilter;             /* 0 or 1: the 3 x 3 Gaussian of the variance drives the colour term             */
+    float   k_normal, k_position, k_albedo, k_sigma, var_floor;
+} rt_svgf_params;                  /* 32 bytes */
+int rt_svgf_filter_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_svgf_params *sp, void *out_rgba_dev, void *out_history_dev, void *stream);
+int rt_svgf_filter(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_svgf_params *sp, float *out_rgba_host, float *out_history_host);
 
 /* --- the planes of the first DIFFUSE surface, and filtering irradiance instead of colour (ABI 6, additive).  The specular branches of Scene::getColor
  *     (cpu:573-604) draw no random number -- reflection, total reflection or refraction, no Fresnel coin -- so the chain of the pixel-centre ray from the camera to

@@ -630,6 +630,17 @@ public:
         check(rt_denoise_var(ctx_, history.data(), aov.data(), W, H, &vp, out.data()), "rt_denoise_var");
         return out;
     }
+    // ... and that filter with SVGF's two switches (rt_svgf_filter): the 3 x 3 Gaussian of the variance in the colour tolerance (sp.prefilter) and pass
+    // sp.feedback_pass's colour handed back as a history for the next temporal_accumulate.  out_history: filled with that history (two planes) when
+    // sp.feedback_pass >= 0 and must be nullptr otherwise -> the filtered colour, W * H float4
+    std::vector<float> svgf_filter(const std::vector<float> &history, const std::vector<float> &aov, int W, int H, const rt_svgf_params &sp, std::vector<float> *out_history = nullptr) {
+        const size_t n = (size_t)W * H * 4;
+        if (history.size() != 2 * n || aov.size() != 3 * n) throw Error(RT_ERR_INVALID, "svgf_filter: history is two planes of W * H float4, aov three");
+        std::vector<float> out(n);
+        if (out_history) out_history->resize(2 * n);
+        check(rt_svgf_filter(ctx_, history.data(), aov.data(), W, H, &sp, out.data(), out_history ? out_history->data() : nullptr), "rt_svgf_filter");
+        return out;
+    }
     // The same three planes for the first DIFFUSE surface of each pixel, followed through at most max_specular mirror / glass segments (rt_render_aov_surface):
     // plane 0 .w is the path code (id, or id + 16 first_id + 256 k; -1 a miss), plane 2 .w is 1 where the chain ended diffuse and the albedo factors out of the pixel.
     std::vector<float> render_aov_surface(const RenderSettings &s, int max_specular, const rt_camera_pose *pose = nullptr) {

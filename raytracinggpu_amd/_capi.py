@@ -31,6 +31,7 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_render_device_batch_scenes",
            "rt_render_aov_device", "rt_render_aov", "rt_denoise_device", "rt_denoise",
            "rt_temporal_accumulate_device", "rt_temporal_accumulate", "rt_denoise_var_device", "rt_denoise_var",
+           "rt_svgf_filter_device", "rt_svgf_filter",
            "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
@@ -183,6 +184,26 @@ def make_denoise_var_params(n_passes=None, k_normal=None, k_position=None, k_alb
     d = DenoiseVarParams()
     for name, v in given.items():
         setattr(d, name, DENOISE_VAR_DEFAULTS[name] if v is None else v)
+    return d
+
+
+class SvgfParams(C.Structure):
+    _fields_ = [("n_passes", C.c_int32), ("feedback_pass", C.c_int32), ("prefilter", C.c_int32),
+                ("k_normal", C.c_float), ("k_position", C.c_float), ("k_albedo", C.c_float), ("k_sigma", C.c_float), ("var_floor", C.c_float)]
+
+
+# The defaults of make_svgf_params: rt_denoise_var's weights, and the two switches as the table of DESIGN.md section 5.10 decided them -- the pre-filter alone had the
+# least error on all three sequences; feeding pass 0 back gained on the baseline on two of them, on the pre-filter alone on none, and lost on the sphere scene.
+SVGF_DEFAULTS = dict(DENOISE_VAR_DEFAULTS, feedback_pass=-1, prefilter=1)
+
+
+def make_svgf_params(n_passes=None, feedback_pass=None, prefilter=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None):
+    """rt_svgf_params; None = the default of SVGF_DEFAULTS.  feedback_pass -1 = no history is written; prefilter 0 / 1."""
+    given = dict(n_passes=n_passes, feedback_pass=feedback_pass, prefilter=prefilter, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_sigma=k_sigma,
+                 var_floor=var_floor)
+    d = SvgfParams()
+    for name, v in given.items():
+        setattr(d, name, SVGF_DEFAULTS[name] if v is None else v)
     return d
 
 
@@ -348,6 +369,8 @@ def load():
     L.rt_temporal_accumulate.argtypes = [vp, fp3, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), fp3]
     L.rt_denoise_var_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(DenoiseVarParams), vp, vp]
     L.rt_denoise_var.argtypes = [vp, fp3, fp3, C.c_int, C.c_int, C.POINTER(DenoiseVarParams), fp3]
+    L.rt_svgf_filter_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(SvgfParams), vp, vp, vp]
+    L.rt_svgf_filter.argtypes = [vp, fp3, fp3, C.c_int, C.c_int, C.POINTER(SvgfParams), fp3, fp3]
     L.rt_render_aov_surface_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), C.c_int, vp, vp]
     L.rt_render_aov_surface.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), C.c_int, fp3]
     L.rt_demodulate_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, vp, vp]
@@ -355,6 +378,9 @@ def load():
     L.rt_modulate_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, vp, vp]
     L.rt_modulate.argtypes = [vp, fp3, fp3, C.c_int64, C.c_float, fp3]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
+    L.rt_device_alloc.argtypes = [vp, C.POINTER(vp), C.c_size_t]
+    L.rt_device_free.argtypes = [vp]
+    L.rt_device_to_host.argtypes = [vp, vp, vp, C.c_size_t]
     L.rt_host_free.argtypes = [vp]
     L.rt_kat_sphere.argtypes = [vp, fp3, C.c_int, fp3]
     L.rt_kat_sqrt.argtypes = [vp, fp3, C.c_int, fp3]
@@ -836,6 +862,29 @@ class Context:
         self._check(self._L.rt_denoise_var_device(self._h, C.c_void_p(history_ptr), C.c_void_p(aov_ptr), int(width), int(height), C.byref(vp_), C.c_void_p(out_ptr),
                                                   C.c_void_p(stream) if stream else None))
 
+    def svgf_filter(self, history, aov, params=None, out=None, out_history=None):
+        """rt_svgf_filter: denoise_var's inputs, params = make_svgf_params(...) -> (the filtered colour [H, W, 4], the history [2, H, W, 4] to hand the next
+        temporal_accumulate as prev_history -- None when params.feedback_pass is -1).  out, out_history: optional preallocated results."""
+        bad = f"svgf_filter: history {np.shape(history)} must be [2, H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
+        history = self._f32(history, lambda s: len(s) == 4 and s[0] == 2 and s[3] == 4, bad)
+        aov = self._f32(aov, lambda s: s == (3,) + history.shape[1:], bad)
+        sp = make_svgf_params() if params is None else params
+        out = self._out("svgf_filter", out, history.shape[1:])
+        if sp.feedback_pass != -1 or out_history is not None:
+            out_history = self._out("svgf_filter", out_history, history.shape)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_svgf_filter(self._h, history.ctypes.data_as(fp), aov.ctypes.data_as(fp), history.shape[2], history.shape[1], C.byref(sp), out.ctypes.data_as(fp),
+                                           out_history.ctypes.data_as(fp) if out_history is not None else None))
+        return out, out_history
+
+    def svgf_filter_device(self, history_ptr, aov_ptr, width, height, out_ptr, out_history_ptr=None, params=None, stream=None):
+        """rt_svgf_filter_device: device pointers (a history of temporal_accumulate_device, the planes, the result, the fed-back history or 0 / None), asynchronous
+        on `stream`."""
+        sp = make_svgf_params() if params is None else params
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._L.rt_svgf_filter_device(self._h, opt(history_ptr), opt(aov_ptr), int(width), int(height), C.byref(sp), opt(out_ptr), opt(out_history_ptr),
+                                                  C.c_void_p(stream) if stream else None))
+
     # --- the planes of the first diffuse surface, and the albedo divided out of / multiplied into a frame (rt_render_aov_surface*, rt_demodulate*, rt_modulate*)
     def render_aov_surface(self, params, max_specular, pose=None, rows=None):
         """rt_render_aov_surface: the planes of render_aov for the first DIFFUSE surface of each pixel, reached through at most max_specular mirror / glass
@@ -897,6 +946,27 @@ class Context:
         """One frame with realtime_render.cu's posed camera and per-sample averaging (no accumulation)."""
         out = np.empty((params.height, params.width, 4), np.float32)
         self._check(self._L.rt_render_pose(self._h, C.byref(params), C.byref(pose), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_pose_device(self, params, pose, out_ptr, rows=None, stream=None):
+        """rt_render_pose_device: render_pose's frame into device memory (rows: a Rows, None = the whole frame), asynchronous on `stream`."""
+        self._check(self._L.rt_render_pose_device(self._h, C.byref(params), C.byref(pose), C.byref(self._rows_or_whole(params, rows)), C.c_void_p(out_ptr),
+                                                  C.c_void_p(stream) if stream else None))
+
+    def device_alloc(self, n_bytes):
+        """rt_device_alloc: n_bytes of memory on the context's device -> its address (free it with device_free)."""
+        p = C.c_void_p()
+        self._check(self._L.rt_device_alloc(self._h, C.byref(p), int(n_bytes)))
+        return p.value
+
+    def device_free(self, ptr):
+        if ptr:
+            self._check(self._L.rt_device_free(C.c_void_p(ptr)))
+
+    def device_to_host(self, ptr, shape):
+        """rt_device_to_host: float32 device memory -> a new array of `shape`, after everything on the context's own stream."""
+        out = np.empty(shape, np.float32)
+        self._check(self._L.rt_device_to_host(self._h, out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), out.nbytes))
         return out
 
     def progressive_reset(self):

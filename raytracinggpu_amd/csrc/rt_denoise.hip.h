@@ -16,6 +16,12 @@
 // rt_temporal.hip.h carries it -- instead of k_color, and the variance is filtered along: a fifth plane of one float per pixel rides in the LDS tile (28.7 KiB),
 // read from .w of history plane 1 on pass 0 and from a float plane of the context between passes.  The plain instantiation is instruction for instruction what it
 // was before the parameter existed (its argument list is the same: the VAR arguments are a parameter pack that is empty for it).
+//
+// rt_svgf_filter[_device] is the third instantiation (VAR with a DnSvgf pack): rt_denoise_var's pass with two switches.  PRE-FILTER: the colour tolerance D is
+// formed from the 3 x 3 Gaussian of the variance over the pass's own sub-image neighbours of the same object -- nine floats that are in dn_var already, one quotient
+// more per pixel and pass, no global load, no byte of LDS more.  FEEDBACK: pass f's colour is plane 0 of a second history the caller hands to the next accumulation.  It costs no pass
+// over the colour: pass f writes there INSTEAD of the ping-pong buffer and pass f + 1 reads from there (the last pass, which must land in the output, writes both);
+// the lanes of pass f copy their pixel's plane-1 record along.  .w and the miss pixels come out right by themselves: every pass hands C_p.w and a miss's C_p through.
 #pragma once
 #include <type_traits>
 #include "rt_div.h"
@@ -30,6 +36,9 @@ constexpr int kDnXcds = 8;                           // consecutive workgroup id
 struct DnParams { float k_normal, k_position, k_albedo, k_color; };   // k_color already scaled by 4^k (VAR: not read)
 // the VAR instantiation's own arguments: the variance plane read (v_stride floats apart: 4 = .w of a float4 plane, 1 = a float plane), the one written (or nullptr)
 struct DnVar { const float *v_in; float *v_out; int v_stride; float k_sigma, var_floor; };
+// the SVGF instantiation's: those, the pre-filter switch, and for the feedback pass (else all nullptr) a second frame to write the pass's colour into (fb_out; nullptr
+// where the pass's own `out` is the history already) and the history's plane 1 to copy, record for record (h1_in -> h1_out)
+struct DnSvgf { DnVar v; int prefilter; float4 *fb_out; const float4 *h1_in; float4 *h1_out; };
 // Rec. 709 luminance, in this order of operations (rt_temporal.hip.h measures its moments with it too)
 __device__ __forceinline__ float lum709(float4 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 
@@ -42,8 +51,10 @@ __device__ __forceinline__ float dn_term(float d, float k) { return k == 0.f ? 1
 
 // The pixel's filtered value.  fetch(plane, dx, dy): record `plane` (0 N|id, 1 P, 2 albedo, 3 colour) of the pixel (x + dx s, y + dy s), which lies inside the image.
 // VAR: fetch_v(dx, dy) is that pixel's variance, kv the variance term's two constants, v_out the filtered variance.
-template <bool VAR, class Fetch, class FetchV>
-__device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, const DnParams &k, Fetch fetch, FetchV fetch_v, float k_sigma, float var_floor, float &v_out) {
+// PRE (the SVGF instantiation) with prefilter != 0: D comes from the 3 x 3 Gaussian of the variance instead of V_p; v_out does not change.
+template <bool VAR, bool PRE = false, class Fetch, class FetchV>
+__device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, const DnParams &k, Fetch fetch, FetchV fetch_v, float k_sigma, float var_floor, float &v_out,
+                                           [[maybe_unused]] int prefilter = 0) {
     const float4 Np = fetch(0, 0, 0), Cp = fetch(3, 0, 0);
     float lp = 0.f, D = 0.f, Dr = 0.f, Sv = 0.f;
     bool d_fast = false;
@@ -51,7 +62,27 @@ __device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, co
     if (Np.w == -1.f) return Cp;                                      // a miss: nothing to guide the filter
     if constexpr (VAR) {
         lp = lum709(Cp);
-        D = k_sigma * v_out + var_floor;                              // the colour tolerance, in the colour's own units squared
+        float Vd = v_out;
+        if constexpr (PRE) {
+            if (prefilter) {                                          // (wave-uniform)
+                const float Gk[2] = {0.5f, 0.25f};
+                float Sg = 0.f, Wg = 0.f;
+#pragma unroll
+                for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int qx = x + dx * s, qy = y + dy * s;
+                        if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                        if (fetch(0, dx, dy).w != Np.w) continue;
+                        const float g = Gk[dy < 0 ? -dy : dy] * Gk[dx < 0 ? -dx : dx];
+                        Sg = Sg + g * fetch_v(dx, dy);
+                        Wg = Wg + g;
+                    }
+                }
+                Vd = div_quot(Sg, Wg);                                // (the centre always counts: Wg >= 1/4)
+            }
+        }
+        D = k_sigma * Vd + var_floor;                                 // the colour tolerance, in the colour's own units squared
         Dr = div_refine(D, __builtin_amdgcn_rcpf(D));
         d_fast = div_in_range(D);
     }
@@ -106,15 +137,18 @@ __device__ __forceinline__ float4 dn_pixel(int x, int y, int W, int H, int s, co
 }
 
 // g: the three guide planes (W * H float4 each, consecutive), C: the pass's input frame.  tiles_x, tiles_y: tiles of a sub-image; n_blocks = tiles_x * tiles_y * s * s.
-// VAR: one more argument, a DnVar (the pack is empty for the plain filter, whose argument list is the one it always had).
+// VAR: one more argument, a DnVar or a DnSvgf (the pack is empty for the plain filter, whose argument list is the one it always had).
 template <bool VAR, class... Var>
 __global__ __launch_bounds__(kDnTileW * kDnTileH) void denoise_pass_kernel(const float4 *__restrict__ C, const float4 *__restrict__ g, float4 *__restrict__ out,
                                                                             int W, int H, int s, int tiles_x, int tiles_y, int n_blocks, const DnParams k, const Var... var) {
-    static_assert(sizeof...(Var) == (VAR ? 1 : 0), "the VAR instantiation takes one DnVar");
+    static_assert(sizeof...(Var) == (VAR ? 1 : 0), "the VAR instantiation takes one DnVar or DnSvgf");
+    constexpr bool SVGF = (std::is_same_v<Var, DnSvgf> || ...);
     __shared__ float4 dn_tile[4 * kDnTw * kDnTh];    // [4 planes][kDnTh rows][kDnTw]: neighbouring lanes read neighbouring 16 bytes
     __shared__ float dn_var[VAR ? kDnTw * kDnTh : 1];                 // VAR: the variance of the same pixels
     [[maybe_unused]] DnVar kv{nullptr, nullptr, 1, 0.f, 0.f};
-    if constexpr (VAR) kv = (var, ...);
+    [[maybe_unused]] DnSvgf ks{kv, 0, nullptr, nullptr, nullptr};
+    if constexpr (SVGF) { ks = (var, ...); kv = ks.v; }
+    else if constexpr (VAR) kv = (var, ...);
     // workgroup id -> work item: ids b, b + 8, b + 16 .. run on one XCD and take consecutive items (the grid is padded to a multiple of kDnXcds)
     const int per_xcd = (int)gridDim.x / kDnXcds;
     const int item = ((int)blockIdx.x % kDnXcds) * per_xcd + (int)blockIdx.x / kDnXcds;
@@ -141,6 +175,16 @@ __global__ __launch_bounds__(kDnTileW * kDnTileH) void denoise_pass_kernel(const
     if (x >= W || y >= H) return;
     const int centre = (ty + kDnHalo) * kDnTw + tx + kDnHalo;        // a tap at (dx s, dy s) is the sub-image's neighbour (dx, dy)
     float v = 0.f;
+    if constexpr (SVGF) {
+        const size_t pix = (size_t)y * W + x;
+        const float4 c = dn_pixel<true, true>(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; },
+                                              [&](int dx, int dy) -> float { return dn_var[centre + dy * kDnTw + dx]; }, kv.k_sigma, kv.var_floor, v, ks.prefilter);
+        out[pix] = c;
+        if (ks.fb_out) ks.fb_out[pix] = c;
+        if (ks.h1_out) ks.h1_out[pix] = ks.h1_in[pix];
+        if (kv.v_out) kv.v_out[pix] = v;
+        return;
+    }
     out[(size_t)y * W + x] = dn_pixel<VAR>(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; },
                                            [&](int dx, int dy) -> float { return dn_var[VAR ? centre + dy * kDnTw + dx : 0]; }, kv.k_sigma, kv.var_floor, v);
     if constexpr (VAR) { if (kv.v_out) kv.v_out[(size_t)y * W + x] = v; }
@@ -236,6 +280,78 @@ static int dn_host(rt_ctx *ctx, const float *in_host, const float *aov_host, int
                   [&](uint8_t *d) { return dn_device<VAR>(ctx, d, d + in_bytes, width, height, dp, d + in_bytes + 3 * bytes, nullptr); });
 }
 
+// rt_svgf_filter*: rt_denoise_var's passes through the SVGF instantiation.  Where the passes write: the last one into the output; pass f (the feedback pass) into plane 0
+// of the second history -- and, where f is the last pass, into both; the others alternate between the output and the context's ping-pong frame, counted back from the
+// last pass behind f and from pass f - 1 before it, so that no pass reads the frame it writes and nothing is written into the second history after pass f.
+// Plane 1 of the second history is copied by pass f's lanes: 6.5 - 8.2 us of a 1080p call against 14.8 us for a device-to-device copy on the stream.
+static int svgf_check(rt_ctx *ctx, const void *in, const void *aov, int width, int height, const rt_svgf_params *sp, const void *out, const void *out_history) {
+    int rc = dn_check(ctx, "history", in, 2, aov, width, height, sp, sp ? sp->n_passes : 0, out);
+    if (rc != RT_OK) return rc;
+    if (sp->prefilter != 0 && sp->prefilter != 1) return fail(ctx, RT_ERR_INVALID, "prefilter %d is neither 0 nor 1", sp->prefilter);
+    if (sp->feedback_pass < -1 || sp->feedback_pass >= sp->n_passes) return fail(ctx, RT_ERR_INVALID, "feedback_pass %d outside [-1,%d]", sp->feedback_pass, sp->n_passes - 1);
+    if ((sp->feedback_pass == -1) != (out_history == nullptr)) return fail(ctx, RT_ERR_INVALID, "out_history goes with feedback_pass >= 0, and only with it");
+    if (out_history) {
+        const size_t bytes = (size_t)width * height * sizeof(float4);
+        if (overlaps(out_history, 2 * bytes, in, 2 * bytes) || overlaps(out_history, 2 * bytes, aov, 3 * bytes) || overlaps(out_history, 2 * bytes, out, bytes))
+            return fail(ctx, RT_ERR_INVALID, "out_history overlaps an input or the output");
+    }
+    return RT_OK;
+}
+
+static int svgf_device(rt_ctx *ctx, const void *in_dev, const void *aov_dev, int width, int height, const rt_svgf_params *sp, void *out_dev, void *out_history_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = svgf_check(ctx, in_dev, aov_dev, width, height, sp, out_dev, out_history_dev);
+    if (rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    const int n_passes = sp->n_passes, f = sp->feedback_pass;
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+    // 0: the output, 1: the context's frame, 2: plane 0 of the second history
+    int where[RT_DENOISE_MAX_PASSES];
+    bool tmp = false;
+    for (int k = 0; k < n_passes; ++k) {
+        // (before pass f: counted back from pass f - 1, which takes the output -- or the context's frame where pass f is the last one and takes the output itself)
+        where[k] = k == n_passes - 1 ? 0 : k == f ? 2 : k > f ? (n_passes - 1 - k) & 1 : (f - 1 - k + (f == n_passes - 1)) & 1;
+        tmp = tmp || where[k] == 1;
+    }
+    if (tmp && (rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
+    if (n_passes > 1 && (rc = ensure(ctx, ctx->dnv_var[0], npix * sizeof(float))) != RT_OK) return rc;
+    if (n_passes > 2 && (rc = ensure(ctx, ctx->dnv_var[1], npix * sizeof(float))) != RT_OK) return rc;
+    if (out_history_dev) note_between(ctx, q, {{in_dev, 2 * bytes}, {out_dev, bytes}, {out_history_dev, 2 * bytes}});
+    else note_between(ctx, q, {{in_dev, 2 * bytes}, {out_dev, bytes}});
+    const float4 *hist = static_cast<const float4 *>(in_dev), *src = hist, *guide = static_cast<const float4 *>(aov_dev);
+    float4 *fb = static_cast<float4 *>(out_history_dev), *const frames[3] = {static_cast<float4 *>(out_dev), static_cast<float4 *>(ctx->dn_tmp.p), fb};
+    const dim3 block(rtk::kDnTileW * rtk::kDnTileH);
+    for (int k = 0; k < n_passes; ++k) {
+        float4 *dst = frames[where[k]];
+        const DnGrid g = dn_grid(width, height, k);
+        const dim3 grid((unsigned)((g.n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds));
+        const rtk::DnParams kp{sp->k_normal, sp->k_position, sp->k_albedo, 0.f};
+        const rtk::DnSvgf ks{{k == 0 ? reinterpret_cast<const float *>(hist + npix) + 3 : static_cast<const float *>(ctx->dnv_var[(k - 1) & 1].p),
+                              k == n_passes - 1 ? nullptr : static_cast<float *>(ctx->dnv_var[k & 1].p), k == 0 ? 4 : 1, sp->k_sigma, sp->var_floor},
+                             sp->prefilter, k == f && dst != fb ? fb : nullptr, k == f ? hist + npix : nullptr, k == f ? fb + npix : nullptr};
+        hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnSvgf>), grid, block, 0, q, src, guide, dst, width, height, 1 << k, (int)g.tiles_x, (int)g.tiles_y, (int)g.n_blocks, kp, ks);
+        src = dst;
+    }
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// the host form: the history, the planes, room for the second history (used with feedback only), the filtered frame
+static int svgf_host(rt_ctx *ctx, const float *in_host, const float *aov_host, int width, int height, const rt_svgf_params *sp, float *out_host, float *out_history_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    const int rc = svgf_check(ctx, in_host, aov_host, width, height, sp, out_host, out_history_host);
+    if (rc != RT_OK) return rc;
+    const size_t bytes = (size_t)width * height * sizeof(float4), fb_bytes = out_history_host ? 2 * bytes : 0, out_off = 5 * bytes + fb_bytes;
+    return staged(ctx, {{in_host, 2 * bytes}, {aov_host, 3 * bytes}, {nullptr, fb_bytes}}, out_off, bytes, out_host, [&](uint8_t *d) {
+        const int r = svgf_device(ctx, d, d + 2 * bytes, width, height, sp, d + out_off, out_history_host ? d + 5 * bytes : nullptr, nullptr);
+        if (r != RT_OK || !out_history_host) return r;
+        RT_HIP(ctx, hipMemcpyAsync(out_history_host, d + 5 * bytes, fb_bytes, hipMemcpyDeviceToHost, own_stream(ctx)));   // (staged waits for the stream)
+        return (int)RT_OK;
+    });
+}
+
 extern "C" int rt_denoise_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, int width, int height, const rt_denoise_params *dp, void *out_dev, void *stream) {
     return dn_device<false>(ctx, color_dev, aov_dev, width, height, dp, out_dev, stream);
 }
@@ -247,4 +363,10 @@ extern "C" int rt_denoise_var_device(rt_ctx *ctx, const void *history_dev, const
 }
 extern "C" int rt_denoise_var(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_denoise_var_params *vp, float *out_host) {
     return dn_host<true>(ctx, history_host, aov_host, width, height, vp, out_host);
+}
+extern "C" int rt_svgf_filter_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_svgf_params *sp, void *out_dev, void *out_history_dev, void *stream) {
+    return svgf_device(ctx, history_dev, aov_dev, width, height, sp, out_dev, out_history_dev, stream);
+}
+extern "C" int rt_svgf_filter(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_svgf_params *sp, float *out_host, float *out_history_host) {
+    return svgf_host(ctx, history_host, aov_host, width, height, sp, out_host, out_history_host);
 }

@@ -211,9 +211,10 @@ def main():
         t = kernel_text(asm, mangled)
         if t:
             res[name] = advance_counts(t) if name in ("wf_advance", "wf_advance_anim") else {"whole_kernel": count(t)}
-    # the first-hit planes, the a-trous filter's two instantiations and the temporal accumulation (rt_aov.hip.h, rt_denoise.hip.h, rt_temporal.hip.h): whole kernels
+    # the first-hit planes, the a-trous filter's three instantiations and the temporal accumulation (rt_aov.hip.h, rt_denoise.hip.h, rt_temporal.hip.h): whole kernels
     for name, pattern in (("aov_emit", r"^(_ZN3rtk15aov_emit_kernel\w*):"), ("aov_close", r"^(_ZN3rtk16aov_close_kernel\w*):"),
-                          ("denoise_pass", r"^(_ZN3rtk19denoise_pass_kernelILb0E\w*):"), ("denoise_var_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1E\w*):"),
+                          ("denoise_pass", r"^(_ZN3rtk19denoise_pass_kernelILb0E\w*):"), ("denoise_var_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_5DnVarEE\w*):"),
+                          ("svgf_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_6DnSvgfEE\w*):"),
                           ("temporal_accumulate", r"^(_ZN3rtk26temporal_accumulate_kernel\w*):")):
         mm = re.search(pattern, asm, re.M)
         if not mm:
@@ -231,6 +232,7 @@ def main():
     print("static_counts: denoise pass (valu / lds / vmem): %d / %d / %d" % tuple(res["denoise_pass"]["whole_kernel"][c] for c in ("valu", "lds", "vmem")))
     print("static_counts: variance-guided pass: %d / %d / %d, temporal accumulation: %d / %d / %d" % tuple(
         res[k]["whole_kernel"][c] for k in ("denoise_var_pass", "temporal_accumulate") for c in ("valu", "lds", "vmem")))
+    print("static_counts: SVGF pass (pre-filter and feedback switches): %d / %d / %d" % tuple(res["svgf_pass"]["whole_kernel"][c] for c in ("valu", "lds", "vmem")))
     t = res["wf_travq"]
     print("static_counts: wf_travq per step: BOX %d valu (weight %d) %d salu + leaf pushes %d / %d | TRI %d (%d) %d + %.0f per t-division block | round %d (%d) %d | fetch %d | retire %d | head+dispatch %d" % (
         t["box"]["valu"], t["box"]["valu_weight"], t["box"]["salu"], t["lpush"]["valu"], t["lpush2"]["valu"], t["tri"]["valu"], t["tri"]["valu_weight"], t["tri"]["salu"], t["tdiv"]["valu"],
