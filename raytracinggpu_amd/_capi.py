@@ -137,13 +137,16 @@ class DenoiseParams(C.Structure):
 DENOISE_DEFAULTS = dict(n_passes=3, k_normal=2.0, k_position=0.25, k_albedo=16.0, k_color=5e-12)
 
 
+def _filled(params, defaults, **given):
+    """params with every given field set: to its value, or to defaults[name] where that is None"""
+    for name, v in given.items():
+        setattr(params, name, defaults[name] if v is None else v)
+    return params
+
+
 def make_denoise_params(n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_color=None):
     """rt_denoise_params; None = the default of DENOISE_DEFAULTS.  A k of 0 switches its term off."""
-    given = dict(n_passes=n_passes, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_color=k_color)
-    d = DenoiseParams()
-    for name, v in given.items():
-        setattr(d, name, DENOISE_DEFAULTS[name] if v is None else v)
-    return d
+    return _filled(DenoiseParams(), DENOISE_DEFAULTS, n_passes=n_passes, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_color=k_color)
 
 
 class TemporalParams(C.Structure):
@@ -180,11 +183,8 @@ def make_temporal_params(max_history=None, alpha_min=None, min_normal_dot=None, 
 
 def make_denoise_var_params(n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None):
     """rt_denoise_var_params; None = the default of DENOISE_VAR_DEFAULTS.  A k_normal / k_position / k_albedo of 0 switches its term off."""
-    given = dict(n_passes=n_passes, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_sigma=k_sigma, var_floor=var_floor)
-    d = DenoiseVarParams()
-    for name, v in given.items():
-        setattr(d, name, DENOISE_VAR_DEFAULTS[name] if v is None else v)
-    return d
+    return _filled(DenoiseVarParams(), DENOISE_VAR_DEFAULTS, n_passes=n_passes, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_sigma=k_sigma,
+                   var_floor=var_floor)
 
 
 class SvgfParams(C.Structure):
@@ -199,12 +199,8 @@ SVGF_DEFAULTS = dict(DENOISE_VAR_DEFAULTS, feedback_pass=-1, prefilter=1)
 
 def make_svgf_params(n_passes=None, feedback_pass=None, prefilter=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None):
     """rt_svgf_params; None = the default of SVGF_DEFAULTS.  feedback_pass -1 = no history is written; prefilter 0 / 1."""
-    given = dict(n_passes=n_passes, feedback_pass=feedback_pass, prefilter=prefilter, k_normal=k_normal, k_position=k_position, k_albedo=k_albedo, k_sigma=k_sigma,
-                 var_floor=var_floor)
-    d = SvgfParams()
-    for name, v in given.items():
-        setattr(d, name, SVGF_DEFAULTS[name] if v is None else v)
-    return d
+    return _filled(SvgfParams(), SVGF_DEFAULTS, n_passes=n_passes, feedback_pass=feedback_pass, prefilter=prefilter, k_normal=k_normal, k_position=k_position,
+                   k_albedo=k_albedo, k_sigma=k_sigma, var_floor=var_floor)
 
 
 def static_motion():
@@ -844,12 +840,16 @@ class Context:
         self._check(self._L.rt_temporal_accumulate_device(self._h, opt(color_ptr), opt(aov_ptr), opt(prev_aov_ptr), opt(prev_history_ptr), int(width), int(height), C.byref(tp),
                                                           C.byref(reproject) if reproject is not None else None, opt(out_ptr), C.c_void_p(stream) if stream else None))
 
+    def _history_and_aov(self, name, history, aov):
+        """the inputs of denoise_var and svgf_filter as float32 arrays: history [2, H, W, 4] and aov [3, H, W, 4] of the same frame"""
+        bad = f"{name}: history {np.shape(history)} must be [2, H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
+        history = self._f32(history, lambda s: len(s) == 4 and s[0] == 2 and s[3] == 4, bad)
+        return history, self._f32(aov, lambda s: s == (3,) + history.shape[1:], bad)
+
     def denoise_var(self, history, aov, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_sigma=None, var_floor=None, out=None):
         """rt_denoise_var: the a-trous filter over history [2, H, W, 4] (temporal_accumulate's) guided by aov [3, H, W, 4], the colour term measured against the
         history's variance -> the filtered colour [H, W, 4].  Parameters as make_denoise_var_params."""
-        bad = f"denoise_var: history {np.shape(history)} must be [2, H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
-        history = self._f32(history, lambda s: len(s) == 4 and s[0] == 2 and s[3] == 4, bad)
-        aov = self._f32(aov, lambda s: s == (3,) + history.shape[1:], bad)
+        history, aov = self._history_and_aov("denoise_var", history, aov)
         out = self._out("denoise_var", out, history.shape[1:])
         vp_ = make_denoise_var_params(n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor)
         fp = C.POINTER(C.c_float)
@@ -865,9 +865,7 @@ class Context:
     def svgf_filter(self, history, aov, params=None, out=None, out_history=None):
         """rt_svgf_filter: denoise_var's inputs, params = make_svgf_params(...) -> (the filtered colour [H, W, 4], the history [2, H, W, 4] to hand the next
         temporal_accumulate as prev_history -- None when params.feedback_pass is -1).  out, out_history: optional preallocated results."""
-        bad = f"svgf_filter: history {np.shape(history)} must be [2, H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
-        history = self._f32(history, lambda s: len(s) == 4 and s[0] == 2 and s[3] == 4, bad)
-        aov = self._f32(aov, lambda s: s == (3,) + history.shape[1:], bad)
+        history, aov = self._history_and_aov("svgf_filter", history, aov)
         sp = make_svgf_params() if params is None else params
         out = self._out("svgf_filter", out, history.shape[1:])
         if sp.feedback_pass != -1 or out_history is not None:

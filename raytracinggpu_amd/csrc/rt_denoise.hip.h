@@ -174,20 +174,16 @@ __global__ __launch_bounds__(kDnTileW * kDnTileH) void denoise_pass_kernel(const
     const int x = (tile_x * kDnTileW + tx) * s + phase_x, y = (tile_y * kDnTileH + ty) * s + phase_y;
     if (x >= W || y >= H) return;
     const int centre = (ty + kDnHalo) * kDnTw + tx + kDnHalo;        // a tap at (dx s, dy s) is the sub-image's neighbour (dx, dy)
+    const size_t pix = (size_t)y * W + x;
     float v = 0.f;
+    const float4 c = dn_pixel<VAR, SVGF>(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; },
+                                         [&](int dx, int dy) -> float { return dn_var[VAR ? centre + dy * kDnTw + dx : 0]; }, kv.k_sigma, kv.var_floor, v, ks.prefilter);
+    out[pix] = c;
     if constexpr (SVGF) {
-        const size_t pix = (size_t)y * W + x;
-        const float4 c = dn_pixel<true, true>(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; },
-                                              [&](int dx, int dy) -> float { return dn_var[centre + dy * kDnTw + dx]; }, kv.k_sigma, kv.var_floor, v, ks.prefilter);
-        out[pix] = c;
         if (ks.fb_out) ks.fb_out[pix] = c;
         if (ks.h1_out) ks.h1_out[pix] = ks.h1_in[pix];
-        if (kv.v_out) kv.v_out[pix] = v;
-        return;
     }
-    out[(size_t)y * W + x] = dn_pixel<VAR>(x, y, W, H, s, k, [&](int p, int dx, int dy) -> float4 { return dn_tile[p * kDnTw * kDnTh + centre + dy * kDnTw + dx]; },
-                                           [&](int dx, int dy) -> float { return dn_var[VAR ? centre + dy * kDnTw + dx : 0]; }, kv.k_sigma, kv.var_floor, v);
-    if constexpr (VAR) { if (kv.v_out) kv.v_out[(size_t)y * W + x] = v; }
+    if constexpr (VAR) { if (kv.v_out) kv.v_out[pix] = v; }
 }
 
 }  // namespace rtk
@@ -211,162 +207,158 @@ static bool dn_grids_fit(int width, int height, int n_passes) {
     return true;
 }
 
-// What both filters and both forms ask of their arguments.  in: the colour frame (in_planes 1, in_name "color") or the history (2, "history"); n_passes: the
-// parameters' (read by the caller only where params is not NULL).  The output may share no byte with an input.
-static int dn_check(rt_ctx *ctx, const char *in_name, const void *in, int in_planes, const void *aov, int width, int height, const void *params, int n_passes, const void *out) {
-    if (!in || !aov || !params || !out) return fail(ctx, RT_ERR_INVALID, "%s/aov/params/out is NULL", in_name);
-    if (int rc = check_frame_size(ctx, width, height); rc != RT_OK) return rc;
-    if (n_passes < 1 || n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", n_passes, RT_DENOISE_MAX_PASSES);
-    if (!dn_grids_fit(width, height, n_passes)) return fail(ctx, RT_ERR_INVALID, "a %d x %d frame needs 2^31 or more workgroups in one of %d passes", width, height, n_passes);
-    const size_t bytes = (size_t)width * height * sizeof(float4);
-    if (overlaps(out, bytes, in, in_planes * bytes) || overlaps(out, bytes, aov, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
+// One call of the family, whichever of the six entries it came through: rt_denoise* over a colour frame (Plain), rt_denoise_var* over a history of
+// rt_temporal_accumulate (Var: two planes, the variance is .w of plane 1), rt_svgf_filter* (Svgf: Var with the two switches).  Everything below dn_call is written once.
+enum class DnKind { Plain, Var, Svgf };
+struct DnCall {
+    DnKind kind;
+    const void *in, *aov;                            // in: the colour frame (Plain) or the history
+    int width, height;
+    const void *params;                              // the entry's own structure, looked at for NULL only: dn_call has copied its fields
+    void *out, *out_history;                         // out_history: Svgf with feedback, else nullptr
+    int n_passes = 0;
+    float k_normal = 0.f, k_position = 0.f, k_albedo = 0.f, k_color = 0.f, k_sigma = 0.f, var_floor = 0.f;   // k_color: Plain; k_sigma, var_floor: the other two
+    int prefilter = 0, feedback_pass = -1;           // (Svgf's)
+    int in_planes() const { return kind == DnKind::Plain ? 1 : 2; }
+};
+static DnCall dn_call(const void *in, const void *aov, int width, int height, const rt_denoise_params *dp, void *out) {
+    DnCall c{DnKind::Plain, in, aov, width, height, dp, out, nullptr};
+    if (dp) c.n_passes = dp->n_passes, c.k_normal = dp->k_normal, c.k_position = dp->k_position, c.k_albedo = dp->k_albedo, c.k_color = dp->k_color;
+    return c;
+}
+static DnCall dn_call(const void *in, const void *aov, int width, int height, const rt_denoise_var_params *vp, void *out) {
+    DnCall c{DnKind::Var, in, aov, width, height, vp, out, nullptr};
+    if (vp) c.n_passes = vp->n_passes, c.k_normal = vp->k_normal, c.k_position = vp->k_position, c.k_albedo = vp->k_albedo, c.k_sigma = vp->k_sigma, c.var_floor = vp->var_floor;
+    return c;
+}
+static DnCall dn_call(const void *in, const void *aov, int width, int height, const rt_svgf_params *sp, void *out, void *out_history) {
+    DnCall c{DnKind::Svgf, in, aov, width, height, sp, out, out_history};
+    if (sp) {
+        c.n_passes = sp->n_passes, c.k_normal = sp->k_normal, c.k_position = sp->k_position, c.k_albedo = sp->k_albedo, c.k_sigma = sp->k_sigma, c.var_floor = sp->var_floor;
+        c.prefilter = sp->prefilter, c.feedback_pass = sp->feedback_pass;
+    }
+    return c;
+}
+
+// What every entry and both forms ask of their arguments.  No output may share a byte with an input or with the other output.
+static int dn_check(rt_ctx *ctx, const DnCall &c) {
+    if (!c.in || !c.aov || !c.params || !c.out) return fail(ctx, RT_ERR_INVALID, "%s/aov/params/out is NULL", c.kind == DnKind::Plain ? "color" : "history");
+    if (int rc = check_frame_size(ctx, c.width, c.height); rc != RT_OK) return rc;
+    if (c.n_passes < 1 || c.n_passes > RT_DENOISE_MAX_PASSES) return fail(ctx, RT_ERR_INVALID, "n_passes %d outside [1,%d]", c.n_passes, RT_DENOISE_MAX_PASSES);
+    if (!dn_grids_fit(c.width, c.height, c.n_passes))
+        return fail(ctx, RT_ERR_INVALID, "a %d x %d frame needs 2^31 or more workgroups in one of %d passes", c.width, c.height, c.n_passes);
+    const size_t bytes = (size_t)c.width * c.height * sizeof(float4);
+    if (overlaps(c.out, bytes, c.in, c.in_planes() * bytes) || overlaps(c.out, bytes, c.aov, 3 * bytes)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
+    if (c.kind != DnKind::Svgf) return RT_OK;
+    if (c.prefilter != 0 && c.prefilter != 1) return fail(ctx, RT_ERR_INVALID, "prefilter %d is neither 0 nor 1", c.prefilter);
+    if (c.feedback_pass < -1 || c.feedback_pass >= c.n_passes) return fail(ctx, RT_ERR_INVALID, "feedback_pass %d outside [-1,%d]", c.feedback_pass, c.n_passes - 1);
+    if ((c.feedback_pass == -1) != (c.out_history == nullptr)) return fail(ctx, RT_ERR_INVALID, "out_history goes with feedback_pass >= 0, and only with it");
+    if (c.out_history && (overlaps(c.out_history, 2 * bytes, c.in, 2 * bytes) || overlaps(c.out_history, 2 * bytes, c.aov, 3 * bytes) || overlaps(c.out_history, 2 * bytes, c.out, bytes)))
+        return fail(ctx, RT_ERR_INVALID, "out_history overlaps an input or the output");
     return RT_OK;
 }
 
-// The two filters: VAR false = rt_denoise* over a colour frame, true = rt_denoise_var* over a history of rt_temporal_accumulate (two planes; the variance is .w of plane 1).
-template <bool VAR> using DnUserParams = std::conditional_t<VAR, rt_denoise_var_params, rt_denoise_params>;
-template <bool VAR> constexpr int kDnInPlanes = VAR ? 2 : 1;
+// What pass k reads and writes; v is what the Var (v.v alone) and Svgf instantiations are handed (Plain: not looked at).
+struct DnPass { const float4 *src; float4 *dst; rtk::DnSvgf v; };
 
-template <bool VAR>
-static int dn_device(rt_ctx *ctx, const void *in_dev, const void *aov_dev, int width, int height, const DnUserParams<VAR> *dp, void *out_dev, void *stream) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    int rc = dn_check(ctx, VAR ? "history" : "color", in_dev, kDnInPlanes<VAR>, aov_dev, width, height, dp, dp ? dp->n_passes : 0, out_dev);
-    if (rc != RT_OK) return rc;
-    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
-    const int n_passes = dp->n_passes;
-    hipStream_t q;
-    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
-    if (n_passes > 1) {
-        if ((rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
-        if constexpr (VAR) {
-            if ((rc = ensure(ctx, ctx->dnv_var[0], npix * sizeof(float))) != RT_OK) return rc;
-            if (n_passes > 2 && (rc = ensure(ctx, ctx->dnv_var[1], npix * sizeof(float))) != RT_OK) return rc;
-        }
-    }
-    note_between(ctx, q, {{in_dev, kDnInPlanes<VAR> * bytes}, {out_dev, bytes}});   // a pipelined frame must not overtake this read of a frame / write of an image
-    // the passes alternate between the output and one buffer of the context so that the last one lands in the output.  VAR: the variance goes from .w of history
-    // plane 1 through the context's two float planes, and the last pass writes none
-    const float4 *src = static_cast<const float4 *>(in_dev), *guide = static_cast<const float4 *>(aov_dev);
-    const dim3 block(rtk::kDnTileW * rtk::kDnTileH);
-    for (int k = 0; k < n_passes; ++k) {
-        float4 *dst = static_cast<float4 *>(((n_passes - 1 - k) & 1) ? ctx->dn_tmp.p : out_dev);
-        const int s = 1 << k;
-        const DnGrid g = dn_grid(width, height, k);
-        const dim3 grid((unsigned)((g.n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds));
-        if constexpr (VAR) {
-            const rtk::DnParams kp{dp->k_normal, dp->k_position, dp->k_albedo, 0.f};
-            const rtk::DnVar kv{k == 0 ? reinterpret_cast<const float *>(static_cast<const float4 *>(in_dev) + npix) + 3 : static_cast<const float *>(ctx->dnv_var[(k - 1) & 1].p),
-                                k == n_passes - 1 ? nullptr : static_cast<float *>(ctx->dnv_var[k & 1].p), k == 0 ? 4 : 1, dp->k_sigma, dp->var_floor};
-            hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnVar>), grid, block, 0, q, src, guide, dst, width, height, s, (int)g.tiles_x, (int)g.tiles_y, (int)g.n_blocks, kp, kv);
-        } else {
-            const rtk::DnParams kp{dp->k_normal, dp->k_position, dp->k_albedo, dp->k_color * (float)(1 << (2 * k))};   // 4^k: an exact scale
-            hipLaunchKernelGGL(rtk::denoise_pass_kernel<false>, grid, block, 0, q, src, guide, dst, width, height, s, (int)g.tiles_x, (int)g.tiles_y, (int)g.n_blocks, kp);
-        }
-        src = dst;
-    }
-    RT_HIP(ctx, hipGetLastError());
-    return RT_OK;
-}
-
-// the host forms: the input's planes, the three guide planes, the result
-template <bool VAR>
-static int dn_host(rt_ctx *ctx, const float *in_host, const float *aov_host, int width, int height, const DnUserParams<VAR> *dp, float *out_host) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    RT_OWN_STREAM(ctx);
-    const int rc = dn_check(ctx, VAR ? "history" : "color", in_host, kDnInPlanes<VAR>, aov_host, width, height, dp, dp ? dp->n_passes : 0, out_host);
-    if (rc != RT_OK) return rc;
-    const size_t bytes = (size_t)width * height * sizeof(float4), in_bytes = kDnInPlanes<VAR> * bytes;
-    return staged(ctx, {{in_host, in_bytes}, {aov_host, 3 * bytes}}, in_bytes + 3 * bytes, bytes, out_host,
-                  [&](uint8_t *d) { return dn_device<VAR>(ctx, d, d + in_bytes, width, height, dp, d + in_bytes + 3 * bytes, nullptr); });
-}
-
-// rt_svgf_filter*: rt_denoise_var's passes through the SVGF instantiation.  Where the passes write: the last one into the output; pass f (the feedback pass) into plane 0
+// The plan of a checked call's passes, and the context's buffers it needs.  Where the passes write: the last one into the output; pass f (the feedback pass) into plane 0
 // of the second history -- and, where f is the last pass, into both; the others alternate between the output and the context's ping-pong frame, counted back from the
-// last pass behind f and from pass f - 1 before it, so that no pass reads the frame it writes and nothing is written into the second history after pass f.
-// Plane 1 of the second history is copied by pass f's lanes: 6.5 - 8.2 us of a 1080p call against 14.8 us for a device-to-device copy on the stream.
-static int svgf_check(rt_ctx *ctx, const void *in, const void *aov, int width, int height, const rt_svgf_params *sp, const void *out, const void *out_history) {
-    int rc = dn_check(ctx, "history", in, 2, aov, width, height, sp, sp ? sp->n_passes : 0, out);
-    if (rc != RT_OK) return rc;
-    if (sp->prefilter != 0 && sp->prefilter != 1) return fail(ctx, RT_ERR_INVALID, "prefilter %d is neither 0 nor 1", sp->prefilter);
-    if (sp->feedback_pass < -1 || sp->feedback_pass >= sp->n_passes) return fail(ctx, RT_ERR_INVALID, "feedback_pass %d outside [-1,%d]", sp->feedback_pass, sp->n_passes - 1);
-    if ((sp->feedback_pass == -1) != (out_history == nullptr)) return fail(ctx, RT_ERR_INVALID, "out_history goes with feedback_pass >= 0, and only with it");
-    if (out_history) {
-        const size_t bytes = (size_t)width * height * sizeof(float4);
-        if (overlaps(out_history, 2 * bytes, in, 2 * bytes) || overlaps(out_history, 2 * bytes, aov, 3 * bytes) || overlaps(out_history, 2 * bytes, out, bytes))
-            return fail(ctx, RT_ERR_INVALID, "out_history overlaps an input or the output");
-    }
-    return RT_OK;
-}
-
-static int svgf_device(rt_ctx *ctx, const void *in_dev, const void *aov_dev, int width, int height, const rt_svgf_params *sp, void *out_dev, void *out_history_dev, void *stream) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    int rc = svgf_check(ctx, in_dev, aov_dev, width, height, sp, out_dev, out_history_dev);
-    if (rc != RT_OK) return rc;
-    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
-    const int n_passes = sp->n_passes, f = sp->feedback_pass;
-    hipStream_t q;
-    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+// last pass behind f and from pass f - 1 before it, so that no pass reads the frame it writes and nothing is written into the second history after pass f.  Without
+// feedback (f = -1) that is the plain alternation that ends in the output.  The variance goes from .w of history plane 1 through the context's two float planes, and the
+// last pass writes none.  Plane 1 of the second history is copied by pass f's lanes: 6.5 - 8.2 us of a 1080p call against 14.8 us for a device-to-device copy on the
+// stream.
+static int dn_plan(rt_ctx *ctx, const DnCall &c, DnPass *pass) {
+    const size_t npix = (size_t)c.width * c.height;
+    const int n = c.n_passes, f = c.feedback_pass;
+    const bool var = c.kind != DnKind::Plain;
     // 0: the output, 1: the context's frame, 2: plane 0 of the second history
-    int where[RT_DENOISE_MAX_PASSES];
+    int where[RT_DENOISE_MAX_PASSES], rc;
     bool tmp = false;
-    for (int k = 0; k < n_passes; ++k) {
+    for (int k = 0; k < n; ++k) {
         // (before pass f: counted back from pass f - 1, which takes the output -- or the context's frame where pass f is the last one and takes the output itself)
-        where[k] = k == n_passes - 1 ? 0 : k == f ? 2 : k > f ? (n_passes - 1 - k) & 1 : (f - 1 - k + (f == n_passes - 1)) & 1;
+        where[k] = k == n - 1 ? 0 : k == f ? 2 : k > f ? (n - 1 - k) & 1 : (f - 1 - k + (f == n - 1)) & 1;
         tmp = tmp || where[k] == 1;
     }
-    if (tmp && (rc = ensure(ctx, ctx->dn_tmp, bytes)) != RT_OK) return rc;
-    if (n_passes > 1 && (rc = ensure(ctx, ctx->dnv_var[0], npix * sizeof(float))) != RT_OK) return rc;
-    if (n_passes > 2 && (rc = ensure(ctx, ctx->dnv_var[1], npix * sizeof(float))) != RT_OK) return rc;
-    if (out_history_dev) note_between(ctx, q, {{in_dev, 2 * bytes}, {out_dev, bytes}, {out_history_dev, 2 * bytes}});
-    else note_between(ctx, q, {{in_dev, 2 * bytes}, {out_dev, bytes}});
-    const float4 *hist = static_cast<const float4 *>(in_dev), *src = hist, *guide = static_cast<const float4 *>(aov_dev);
-    float4 *fb = static_cast<float4 *>(out_history_dev), *const frames[3] = {static_cast<float4 *>(out_dev), static_cast<float4 *>(ctx->dn_tmp.p), fb};
+    if (tmp && (rc = ensure(ctx, ctx->dn_tmp, npix * sizeof(float4))) != RT_OK) return rc;
+    if (var && n > 1 && (rc = ensure(ctx, ctx->dnv_var[0], npix * sizeof(float))) != RT_OK) return rc;
+    if (var && n > 2 && (rc = ensure(ctx, ctx->dnv_var[1], npix * sizeof(float))) != RT_OK) return rc;
+    const float4 *in = static_cast<const float4 *>(c.in);
+    float4 *fb = static_cast<float4 *>(c.out_history), *const frames[3] = {static_cast<float4 *>(c.out), static_cast<float4 *>(ctx->dn_tmp.p), fb};
+    for (int k = 0; k < n; ++k) {
+        DnPass &p = pass[k];
+        p.src = k == 0 ? in : pass[k - 1].dst;
+        p.dst = frames[where[k]];
+        if (!var) continue;
+        p.v = {{k == 0 ? reinterpret_cast<const float *>(in + npix) + 3 : static_cast<const float *>(ctx->dnv_var[(k - 1) & 1].p),
+                k == n - 1 ? nullptr : static_cast<float *>(ctx->dnv_var[k & 1].p), k == 0 ? 4 : 1, c.k_sigma, c.var_floor},
+               c.prefilter, k == f && p.dst != fb ? fb : nullptr, k == f ? in + npix : nullptr, k == f ? fb + npix : nullptr};
+    }
+    return RT_OK;
+}
+
+static int dn_device(rt_ctx *ctx, const DnCall &c, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = dn_check(ctx, c);
+    if (rc != RT_OK) return rc;
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+    DnPass pass[RT_DENOISE_MAX_PASSES] = {};
+    if ((rc = dn_plan(ctx, c, pass)) != RT_OK) return rc;
+    const size_t bytes = (size_t)c.width * c.height * sizeof(float4);
+    // a pipelined frame must not overtake this read of a frame / write of an image
+    if (c.out_history) note_between(ctx, q, {{c.in, c.in_planes() * bytes}, {c.out, bytes}, {c.out_history, 2 * bytes}});
+    else note_between(ctx, q, {{c.in, c.in_planes() * bytes}, {c.out, bytes}});
+    const float4 *guide = static_cast<const float4 *>(c.aov);
     const dim3 block(rtk::kDnTileW * rtk::kDnTileH);
-    for (int k = 0; k < n_passes; ++k) {
-        float4 *dst = frames[where[k]];
-        const DnGrid g = dn_grid(width, height, k);
+    for (int k = 0; k < c.n_passes; ++k) {
+        const DnPass &p = pass[k];
+        const int s = 1 << k;
+        const DnGrid g = dn_grid(c.width, c.height, k);
         const dim3 grid((unsigned)((g.n_blocks + rtk::kDnXcds - 1) / rtk::kDnXcds * rtk::kDnXcds));
-        const rtk::DnParams kp{sp->k_normal, sp->k_position, sp->k_albedo, 0.f};
-        const rtk::DnSvgf ks{{k == 0 ? reinterpret_cast<const float *>(hist + npix) + 3 : static_cast<const float *>(ctx->dnv_var[(k - 1) & 1].p),
-                              k == n_passes - 1 ? nullptr : static_cast<float *>(ctx->dnv_var[k & 1].p), k == 0 ? 4 : 1, sp->k_sigma, sp->var_floor},
-                             sp->prefilter, k == f && dst != fb ? fb : nullptr, k == f ? hist + npix : nullptr, k == f ? fb + npix : nullptr};
-        hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnSvgf>), grid, block, 0, q, src, guide, dst, width, height, 1 << k, (int)g.tiles_x, (int)g.tiles_y, (int)g.n_blocks, kp, ks);
-        src = dst;
+        const rtk::DnParams kp{c.k_normal, c.k_position, c.k_albedo, c.kind == DnKind::Plain ? c.k_color * (float)(1 << (2 * k)) : 0.f};   // 4^k: an exact scale
+        const int tiles_x = (int)g.tiles_x, tiles_y = (int)g.tiles_y, n_blocks = (int)g.n_blocks;
+        switch (c.kind) {                                             // (Svgf first: the code object holds the instantiations in the order they are named here, and keeps its order)
+        case DnKind::Svgf: hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnSvgf>), grid, block, 0, q, p.src, guide, p.dst, c.width, c.height, s, tiles_x, tiles_y, n_blocks, kp, p.v); break;
+        case DnKind::Plain: hipLaunchKernelGGL(rtk::denoise_pass_kernel<false>, grid, block, 0, q, p.src, guide, p.dst, c.width, c.height, s, tiles_x, tiles_y, n_blocks, kp); break;
+        case DnKind::Var: hipLaunchKernelGGL((rtk::denoise_pass_kernel<true, rtk::DnVar>), grid, block, 0, q, p.src, guide, p.dst, c.width, c.height, s, tiles_x, tiles_y, n_blocks, kp, p.v.v); break;
+        }
     }
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
 
-// the host form: the history, the planes, room for the second history (used with feedback only), the filtered frame
-static int svgf_host(rt_ctx *ctx, const float *in_host, const float *aov_host, int width, int height, const rt_svgf_params *sp, float *out_host, float *out_history_host) {
+// the host form: the input's planes, the three guide planes, room for the second history (with feedback only), the result
+static int dn_host(rt_ctx *ctx, const DnCall &c) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     RT_OWN_STREAM(ctx);
-    const int rc = svgf_check(ctx, in_host, aov_host, width, height, sp, out_host, out_history_host);
+    const int rc = dn_check(ctx, c);
     if (rc != RT_OK) return rc;
-    const size_t bytes = (size_t)width * height * sizeof(float4), fb_bytes = out_history_host ? 2 * bytes : 0, out_off = 5 * bytes + fb_bytes;
-    return staged(ctx, {{in_host, 2 * bytes}, {aov_host, 3 * bytes}, {nullptr, fb_bytes}}, out_off, bytes, out_host, [&](uint8_t *d) {
-        const int r = svgf_device(ctx, d, d + 2 * bytes, width, height, sp, d + out_off, out_history_host ? d + 5 * bytes : nullptr, nullptr);
-        if (r != RT_OK || !out_history_host) return r;
-        RT_HIP(ctx, hipMemcpyAsync(out_history_host, d + 5 * bytes, fb_bytes, hipMemcpyDeviceToHost, own_stream(ctx)));   // (staged waits for the stream)
+    const size_t bytes = (size_t)c.width * c.height * sizeof(float4), in_bytes = c.in_planes() * bytes, fb_off = in_bytes + 3 * bytes, fb_bytes = c.out_history ? 2 * bytes : 0;
+    return staged(ctx, {{c.in, in_bytes}, {c.aov, 3 * bytes}, {nullptr, fb_bytes}}, fb_off + fb_bytes, bytes, c.out, [&](uint8_t *d) {
+        DnCall dc = c;
+        dc.in = d, dc.aov = d + in_bytes, dc.out = d + fb_off + fb_bytes, dc.out_history = c.out_history ? d + fb_off : nullptr;
+        const int r = dn_device(ctx, dc, nullptr);
+        if (r != RT_OK || !c.out_history) return r;
+        RT_HIP(ctx, hipMemcpyAsync(c.out_history, d + fb_off, fb_bytes, hipMemcpyDeviceToHost, own_stream(ctx)));   // (staged waits for the stream)
         return (int)RT_OK;
     });
 }
 
 extern "C" int rt_denoise_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, int width, int height, const rt_denoise_params *dp, void *out_dev, void *stream) {
-    return dn_device<false>(ctx, color_dev, aov_dev, width, height, dp, out_dev, stream);
+    return dn_device(ctx, dn_call(color_dev, aov_dev, width, height, dp, out_dev), stream);
 }
 extern "C" int rt_denoise(rt_ctx *ctx, const float *color_host, const float *aov_host, int width, int height, const rt_denoise_params *dp, float *out_host) {
-    return dn_host<false>(ctx, color_host, aov_host, width, height, dp, out_host);
+    return dn_host(ctx, dn_call(color_host, aov_host, width, height, dp, out_host));
 }
 extern "C" int rt_denoise_var_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_denoise_var_params *vp, void *out_dev, void *stream) {
-    return dn_device<true>(ctx, history_dev, aov_dev, width, height, vp, out_dev, stream);
+    return dn_device(ctx, dn_call(history_dev, aov_dev, width, height, vp, out_dev), stream);
 }
 extern "C" int rt_denoise_var(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_denoise_var_params *vp, float *out_host) {
-    return dn_host<true>(ctx, history_host, aov_host, width, height, vp, out_host);
+    return dn_host(ctx, dn_call(history_host, aov_host, width, height, vp, out_host));
 }
 extern "C" int rt_svgf_filter_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_svgf_params *sp, void *out_dev, void *out_history_dev, void *stream) {
-    return svgf_device(ctx, history_dev, aov_dev, width, height, sp, out_dev, out_history_dev, stream);
+    return dn_device(ctx, dn_call(history_dev, aov_dev, width, height, sp, out_dev, out_history_dev), stream);
 }
 extern "C" int rt_svgf_filter(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_svgf_params *sp, float *out_host, float *out_history_host) {
-    return svgf_host(ctx, history_host, aov_host, width, height, sp, out_host, out_history_host);
+    return dn_host(ctx, dn_call(history_host, aov_host, width, height, sp, out_host, out_history_host));
 }

@@ -57,17 +57,43 @@ class TapStats:
         return dict(far_x=n(self.far_x), far_y=n(self.far_y), dropped_by_id=n(self.dropped), across_seam=n(self.own & self.other), shared=n(fast), literal=n(~fast))
 
 
-def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color, stats=None):
-    """One pass with step s over the colour frame C [H, W, 4], guided by aov [3, H, W, 4]; k_color already carries its 4^k.  stats: an optional dict that receives,
-    under the key s, TapStats.counts of this pass."""
-    C = np.ascontiguousarray(C, np.float32)
-    aov = np.ascontiguousarray(aov, np.float32)
+def lum(c):
+    """Rec. 709 luminance, in the kernel's order of operations"""
+    return (F(0.2126) * c[..., 0] + F(0.7152) * c[..., 1]) + F(0.0722) * c[..., 2]
+
+
+def color_term(C, k_color):
+    """The colour term of rt_denoise for atrous_pass: the squared colour difference against k_color (which already carries its 4^k)."""
+    return lambda qy, qx: (_term(_sqdiff(C[..., :3], C[qy, qx, :3]), k_color), None)
+
+
+def luminance_term(C, D):
+    """The colour term of rt_denoise_var and rt_svgf_filter for atrous_pass: the squared luminance difference over the pixel's tolerance D [H, W]."""
+    L = lum(C)
+
+    def term(qy, qx):
+        dl = L - L[qy, qx]
+        dl2 = dl * dl
+        # equal luminance: the term is exactly 1 and no quotient is formed; else the quotient is rt_div.h's shared sequence where D and dl2 are in its range
+        return np.where(dl2 == 0, F(1), np.fmax(F(0), F(1) - dl2 / D)), (dl2 != 0) & ~(div_in_range(D) & div_in_range(dl2))
+    return term
+
+
+def atrous_pass(C, aov, s, k_normal, k_position, k_albedo, color, V=None, carry=None, stats=None):
+    """One 5 x 5 pass with step s over the colour frame C [H, W, 4], guided by aov [3, H, W, 4]: the pass of all three filters.  color(qy, qx) -> (the colour
+    term of the taps at [qy, qx], or None for exactly 1; the taps whose term formed a literal quotient, or None).  V [H, W]: the variance, filtered along from
+    the values `carry` (V itself unless given) that the taps bring; then the result is (colour, variance), else the colour.  stats: an optional dict that
+    receives, under the key s, TapStats.counts of this pass."""
     Hh, W = C.shape[:2]
     N, ID, P, A = aov[0, ..., :3], aov[0, ..., 3], aov[1, ..., :3], aov[2, ..., :3]
     ys, xs = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
     S = np.zeros((Hh, W, 3), np.float32)
     Wt = np.zeros((Hh, W), np.float32)
+    Sv = np.zeros((Hh, W), np.float32)
+    if V is not None and carry is None:
+        carry = V
     ts = TapStats(Hh, W, s) if stats is not None else None
+    fast = np.ones((Hh, W), bool)
     with np.errstate(all="ignore"):
         for dy in range(-2, 3):
             for dx in range(-2, 3):
@@ -86,23 +112,43 @@ def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color, stats=None)
                 t = _term(_sqdiff(A, A[qy, qx]), k_albedo)
                 if t is not None:
                     w = w * t
-                Cq = C[qy, qx, :3]
-                t = _term(_sqdiff(C[..., :3], Cq), k_color)
+                t, literal = color(qy, qx)
                 if t is not None:
                     w = w * t
                 take = ok & (w > 0)                                    # False for a NaN weight
                 if ts is not None:
                     ts.tap(dx, dy, inside, ok, take, qx, qy)
+                    if literal is not None:
+                        fast &= ~(ok & literal)
+                Cq = C[qy, qx, :3]
                 S = np.where(take[..., None], S + w[..., None] * Cq, S)
                 Wt = np.where(take, Wt + w, Wt)
+                if V is not None:
+                    Sv = np.where(take, Sv + (w * w) * carry[qy, qx], Sv)
         rgb = S / Wt[..., None]
+        vo = Sv / (Wt * Wt)
+        fast &= div_in_range(Wt) & div_in_range(S).all(-1)
+        if V is not None:
+            fast &= div_in_range(Sv) & div_in_range(Wt * Wt)
     out = C.copy()
     hit = ID != F(-1)
     out[hit, :3] = rgb[hit]
     if ts is not None:
-        stats[s] = ts.counts(hit, div_in_range(Wt) & div_in_range(S).all(-1))
+        stats[s] = ts.counts(hit, fast)
     assert out.dtype == np.float32
-    return out
+    if V is None:
+        return out
+    Vo = V.copy()
+    Vo[hit] = vo[hit]
+    assert Vo.dtype == np.float32
+    return out, Vo
+
+
+def denoise_pass(C, aov, s, k_normal, k_position, k_albedo, k_color, stats=None):
+    """One pass with step s over the colour frame C [H, W, 4], guided by aov [3, H, W, 4]; k_color already carries its 4^k.  stats: an optional dict that receives,
+    under the key s, TapStats.counts of this pass."""
+    C = np.ascontiguousarray(C, np.float32)
+    return atrous_pass(C, np.ascontiguousarray(aov, np.float32), s, k_normal, k_position, k_albedo, color_term(C, k_color), stats=stats)
 
 
 def denoise(C, aov, n_passes, k_normal, k_position, k_albedo, k_color, stats=None, keep=None):

@@ -1,12 +1,11 @@
-"""Reference model of rt_svgf_filter (test infrastructure, like tests/temporal_model.py, whose pass this one restates with the two switches).
+"""Reference model of rt_svgf_filter (test infrastructure, like tests/temporal_model.py, whose pass -- denoise_model.atrous_pass -- this one runs with the two switches).
 
 numpy binary32 throughout: every operation one rounding, in the order include/raytrace_hip.h states (dy outer, dx inner, sums left to right; numpy's binary32 quotient is
 the correctly rounded one).  `mutant` (tests only) names one wrong reading of the header that a kernel could plausibly implement; tests/test_svgf_model.py shows that each
 changes the bits of the synthetic case."""
 import numpy as np
 
-from . import temporal_model as tm
-from .denoise_model import H3, _sqdiff, _term
+from .denoise_model import atrous_pass, luminance_term
 
 F = np.float32
 G3 = (F(0.5), F(0.25))
@@ -48,14 +47,7 @@ def svgf_pass(C, V, aov, s, prefilter, k_normal, k_position, k_albedo, k_sigma, 
     C = np.ascontiguousarray(C, np.float32)
     V = np.ascontiguousarray(V, np.float32)
     aov = np.ascontiguousarray(aov, np.float32)
-    Hh, W = C.shape[:2]
-    N, ID, P, A = aov[0, ..., :3], aov[0, ..., 3], aov[1, ..., :3], aov[2, ..., :3]
-    ys, xs = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
-    S = np.zeros((Hh, W, 3), np.float32)
-    Wt = np.zeros((Hh, W), np.float32)
-    Sv = np.zeros((Hh, W), np.float32)
-    L = tm.lum(C)
-    hit = ID != F(-1)
+    ID = aov[0, ..., 3]
     with np.errstate(all="ignore"):
         Vd = V
         if prefilter:
@@ -63,43 +55,11 @@ def svgf_pass(C, V, aov, s, prefilter, k_normal, k_position, k_albedo, k_sigma, 
             Vd = gaussian_variance(V, ID, s, stats=st, mutant=mutant)
             if stats is not None:
                 D0, D1 = F(k_sigma) * V + F(var_floor), F(k_sigma) * Vd + F(var_floor)
-                st["d_changed"] = int((hit & (D0.view(np.uint32) != D1.view(np.uint32))).sum())
+                st["d_changed"] = int(((ID != F(-1)) & (D0.view(np.uint32) != D1.view(np.uint32))).sum())
                 stats[s] = st
-        Vc = Vd if mutant == "carry_vg" else V                         # (the variance the taps carry on: the unfiltered one)
         D = F(k_sigma) * Vd + F(var_floor)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                qy, qx = ys + dy * s, xs + dx * s
-                inside = (qy >= 0) & (qy < Hh) & (qx >= 0) & (qx < W)
-                qy, qx = np.clip(qy, 0, Hh - 1), np.clip(qx, 0, W - 1)
-                ok = inside & (ID[qy, qx] == ID)
-                w = np.full((Hh, W), H3[abs(dy)] * H3[abs(dx)], np.float32)
-                t = _term(_sqdiff(N, N[qy, qx]), k_normal)
-                if t is not None:
-                    w = w * t
-                if F(k_position) != 0:
-                    Pq = P[qy, qx]
-                    e = (N[..., 0] * (Pq[..., 0] - P[..., 0]) + N[..., 1] * (Pq[..., 1] - P[..., 1])) + N[..., 2] * (Pq[..., 2] - P[..., 2])
-                    w = w * _term(e * e, k_position)
-                t = _term(_sqdiff(A, A[qy, qx]), k_albedo)
-                if t is not None:
-                    w = w * t
-                dl = L - L[qy, qx]
-                dl2 = dl * dl
-                w = np.where(dl2 == 0, w, w * np.fmax(F(0), F(1) - dl2 / D))             # equal luminance: the term is exactly 1
-                take = ok & (w > 0)                                    # False for a NaN weight
-                Cq = C[qy, qx, :3]
-                S = np.where(take[..., None], S + w[..., None] * Cq, S)
-                Wt = np.where(take, Wt + w, Wt)
-                Sv = np.where(take, Sv + (w * w) * Vc[qy, qx], Sv)
-        rgb = S / Wt[..., None]
-        vo = Sv / (Wt * Wt)
-    out = C.copy()
-    out[hit, :3] = rgb[hit]
-    Vo = V.copy()
-    Vo[hit] = vo[hit]
-    assert out.dtype == np.float32 and Vo.dtype == np.float32
-    return out, Vo
+    # (the variance the taps carry on: the unfiltered one)
+    return atrous_pass(C, aov, s, k_normal, k_position, k_albedo, luminance_term(C, D), V=V, carry=Vd if mutant == "carry_vg" else V)
 
 
 def svgf_filter(history, aov, n_passes, feedback_pass, prefilter, k_normal, k_position, k_albedo, k_sigma, var_floor, stats=None, keep=None, mutant=None):

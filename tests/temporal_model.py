@@ -5,13 +5,9 @@ The four reprojection taps and the 25 taps of a pass are vectorised over the ima
 import numpy as np
 
 import raytracinggpu_amd as rt
-from .denoise_model import H3, TapStats, _sqdiff, _term, div_in_range
+from .denoise_model import atrous_pass, div_in_range, lum, luminance_term
 
 F = np.float32
-
-
-def lum(c):
-    return (F(0.2126) * c[..., 0] + F(0.7152) * c[..., 1]) + F(0.0722) * c[..., 2]
 
 
 def _dot(a, b):
@@ -173,58 +169,9 @@ def denoise_var_pass(C, V, aov, s, k_normal, k_position, k_albedo, k_sigma, var_
     """One pass with step s over colour C [H, W, 4] and variance V [H, W] -> (colour, variance).  stats: as denoise_model.denoise_pass."""
     C = np.ascontiguousarray(C, np.float32)
     V = np.ascontiguousarray(V, np.float32)
-    aov = np.ascontiguousarray(aov, np.float32)
-    Hh, W = C.shape[:2]
-    N, ID, P, A = aov[0, ..., :3], aov[0, ..., 3], aov[1, ..., :3], aov[2, ..., :3]
-    ys, xs = np.meshgrid(np.arange(Hh), np.arange(W), indexing="ij")
-    S = np.zeros((Hh, W, 3), np.float32)
-    Wt = np.zeros((Hh, W), np.float32)
-    Sv = np.zeros((Hh, W), np.float32)
-    L = lum(C)
-    ts = TapStats(Hh, W, s) if stats is not None else None
-    fast = np.ones((Hh, W), bool)
     with np.errstate(all="ignore"):
         D = F(k_sigma) * V + F(var_floor)
-        for dy in range(-2, 3):
-            for dx in range(-2, 3):
-                qy, qx = ys + dy * s, xs + dx * s
-                inside = (qy >= 0) & (qy < Hh) & (qx >= 0) & (qx < W)
-                qy, qx = np.clip(qy, 0, Hh - 1), np.clip(qx, 0, W - 1)
-                ok = inside & (ID[qy, qx] == ID)
-                w = np.full((Hh, W), H3[abs(dy)] * H3[abs(dx)], np.float32)
-                t = _term(_sqdiff(N, N[qy, qx]), k_normal)
-                if t is not None:
-                    w = w * t
-                if F(k_position) != 0:
-                    Pq = P[qy, qx]
-                    e = (N[..., 0] * (Pq[..., 0] - P[..., 0]) + N[..., 1] * (Pq[..., 1] - P[..., 1])) + N[..., 2] * (Pq[..., 2] - P[..., 2])
-                    w = w * _term(e * e, k_position)
-                t = _term(_sqdiff(A, A[qy, qx]), k_albedo)
-                if t is not None:
-                    w = w * t
-                dl = L - L[qy, qx]
-                dl2 = dl * dl
-                w = np.where(dl2 == 0, w, w * np.fmax(F(0), F(1) - dl2 / D))             # equal luminance: the term is exactly 1
-                take = ok & (w > 0)                                    # False for a NaN weight
-                if ts is not None:
-                    ts.tap(dx, dy, inside, ok, take, qx, qy)
-                    fast &= ~(ok & (dl2 != 0)) | (div_in_range(D) & div_in_range(dl2))
-                Cq = C[qy, qx, :3]
-                S = np.where(take[..., None], S + w[..., None] * Cq, S)
-                Wt = np.where(take, Wt + w, Wt)
-                Sv = np.where(take, Sv + (w * w) * V[qy, qx], Sv)
-        rgb = S / Wt[..., None]
-        vo = Sv / (Wt * Wt)
-    out = C.copy()
-    hit = ID != F(-1)
-    if ts is not None:
-        with np.errstate(all="ignore"):
-            stats[s] = ts.counts(hit, fast & div_in_range(Wt) & div_in_range(S).all(-1) & div_in_range(Sv) & div_in_range(Wt * Wt))
-    out[hit, :3] = rgb[hit]
-    Vo = V.copy()
-    Vo[hit] = vo[hit]
-    assert out.dtype == np.float32 and Vo.dtype == np.float32
-    return out, Vo
+    return atrous_pass(C, np.ascontiguousarray(aov, np.float32), s, k_normal, k_position, k_albedo, luminance_term(C, D), V=V, stats=stats)
 
 
 def denoise_var(history, aov, n_passes, k_normal, k_position, k_albedo, k_sigma, var_floor, stats=None, keep=None):

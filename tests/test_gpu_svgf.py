@@ -2,7 +2,7 @@
 
 tests/test_svgf_model.py proves on the CPU that the synthetic inputs used here reach the pre-filter (D changed, Gaussian taps skipped for each reason) and that the
 listed faults would change their bits.  Here: the four switch combinations at 1, 3 and 5 passes with the first and the last pass fed back; frames around the 32 x 8
-tile and with partly empty sub-images; a rendered four-frame chain through the device entries on a second stream, with the fed-back history as the next frame's
+tile and with partly empty sub-images; every pass count from 1 to 6 with every feedback pass (and the two other filters, which share the pass plan); a rendered four-frame chain through the device entries on a second stream, with the fed-back history as the next frame's
 previous one; SvgfSequence against those explicit calls; every refusal; NaN and Inf planted in the variance; the pipelining note of both outputs.
 
 Planted non-finite values follow _same of test_gpu_synthetic_filters.py: NaN exactly where the model has NaN (sign and payload not compared), bit-equal elsewhere."""
@@ -15,6 +15,7 @@ import pytest
 
 import raytracinggpu_amd as rt
 from raytracinggpu_amd import _capi
+from . import denoise_model as dm
 from . import svgf_model as sm
 from . import synthetic_planes as sp
 from . import temporal_model as tm
@@ -56,6 +57,7 @@ def _check(ctx, hist, aov, n, f, pre, finite=True, msg=""):
 
 
 SYNTHETIC = synthetic()
+KD = [_capi.DENOISE_DEFAULTS[name] for name in ("k_normal", "k_position", "k_albedo", "k_color")]   # rt_denoise's, as K is rt_denoise_var's
 
 
 @pytest.mark.parametrize("n", [1, 3, 5])
@@ -79,6 +81,24 @@ def test_sizes_where_tiles_and_sub_images_go_wrong(ctx, w, h):
         _check(ctx, p["history"], p["aov"], 4, f, 1, msg=f" {w} x {h},")
     _check(ctx, p["history"], p["aov"], 4, 1, 0, msg=f" {w} x {h},")
     _check(ctx, p["history"], p["aov"], 1, 0, 1, msg=f" {w} x {h},")
+
+
+def test_every_pass_count_and_feedback_pass(ctx):
+    """The pass plan of rt_denoise.hip.h, which all three filters run through: every n_passes in 1 .. 6 with every feedback_pass, on one context, so that its frame and
+    its variance planes are reused from call to call.  33 x 9 is one pixel over a tile each way, and at step 32 most sub-images are a single pixel.  A pass that read
+    the frame it writes, or wrote into the second history after the feedback pass, would change the bits; the 27 expected results differ from each other, so taking the
+    wrong pass's frame would too."""
+    p = sp.planes(33, 9, 333)
+    hist, aov = p["history"], p["aov"]
+    expected = set()
+    for n in range(1, 7):
+        for f in range(-1, n):
+            _check(ctx, hist, aov, n, f, 1, msg=" 33 x 9,")
+            exp, exp_h = sm.svgf_filter(hist, aov, n, f, 1, *K)
+            expected.add(exp.tobytes() + (b"" if exp_h is None else exp_h.tobytes()))
+        _same(ctx.denoise_var(hist, aov, n_passes=n), tm.denoise_var(hist, aov, n, *K), True, f"rt_denoise_var, n_passes {n}")
+        _same(ctx.denoise(p["color"], aov, n_passes=n), dm.denoise(p["color"], aov, n, *KD), True, f"rt_denoise, n_passes {n}")
+    assert len(expected) == 27
 
 
 def test_nan_and_inf_in_the_variance_spread_to_d_and_no_further(ctx):
