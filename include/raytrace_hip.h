@@ -677,6 +677,45 @@ int rt_demodulate(rt_ctx *ctx, const float *color_rgba_host, const float *aov_ho
 int rt_modulate_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, int64_t n_pixels, float albedo_floor, void *out_rgba_dev, void *stream);
 int rt_modulate(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, int64_t n_pixels, float albedo_floor, float *out_rgba_host);
 
+/* --- guided upsampling: trace at 1 / f of the resolution, rebuild at full resolution (ABI 6, additive).  A SPEED KNOB, not a quality feature: a quarter (f = 2) or
+ *     a sixteenth (f = 4) of the rays for a larger error than the same chain at full resolution (DESIGN.md section 5.11 has both); nothing uses it unless asked.
+ *     The noisy colour is traced at w x h = (width / f) x (height / f); the planes of rt_render_aov[_surface]* are taken at both resolutions (the full-resolution
+ *     ones cost one traversal round of camera rays and shade nothing).  With the camera's z = -W / (2 tan(fov / 2)) the low-resolution pixel (i, j) looks exactly
+ *     through the common corner of its f x f full-resolution pixels: the two sets of planes describe one image plane.
+ *     rt_upsample*: width x height is the FULL resolution.  low: n_planes consecutive planes of w x h float4 (1: a colour frame; 2: a history, both planes of
+ *     rt_temporal_accumulate*).  low_aov, aov: three-plane buffers as rt_render_aov* writes them at the low and at the full resolution; planes 0 and 1 are read,
+ *     plane 2 is not.  out: n_planes planes of width x height float4.  The arithmetic is the contract -- binary32, one rounding per operation, no contraction, sums
+ *     left to right, quotients correctly rounded.  Full-resolution pixel p = (x, y) with id_p, N_p, P_p from `aov`:
+ *       gx = ((float)x + 0.5f) / (float)f - 0.5f,  ix = floor(gx),  fx = gx - floor(gx);  gy, iy, fy likewise from y;
+ *       the taps, in this order: q = (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1); bx = 1 - fx for the left column and fx for the right, by likewise for
+ *       the upper and the lower row, b = bx by;
+ *       a tap is skipped if it lies outside the w x h image or id_q != id_p (a miss matches a miss); otherwise, with N_q, P_q from `low_aov`,
+ *         dn = (N_p.x - N_q.x)^2 + (N_p.y - N_q.y)^2 + (N_p.z - N_q.z)^2 and e = N_p.x (P_q.x - P_p.x) + N_p.y (P_q.y - P_p.y) + N_p.z (P_q.z - P_p.z), dp = e e,
+ *         exactly as rt_denoise forms them;  wn = max(0, 1 - dn k_normal), wp = max(0, 1 - dp k_position); a k_* of exactly 0 makes its term exactly 1;
+ *         w = b wn wp, multiplied left to right; the tap COUNTS only if w > 0: S_i += w L_q for every plane i and channel, W += w;
+ *       if no tap counted (W == 0): the four taps are taken again and every tap inside the image counts with w = b, whatever the guides say -- plain bilinear
+ *       (at least one of them has b > 0; one with b == 0, which f = 3 has, still adds 0 L_q and may be the first counted tap);
+ *       out = S / W per channel, except plane 0's .w, which is the .w of the first counted tap: a ray count stays exact.
+ *     A pixel that is a miss is upsampled like any other, among the misses of its footprint.
+ *     NON-FINITE INPUTS: as for the filters above, max is maxNum and comparisons with a NaN are false.  A NaN in N_q or P_q, or an id_q of NaN, makes that tap weigh
+ *     nothing; a pixel whose own N_p, P_p or id_p is NaN counts no tap and takes the plain bilinear value.  A non-finite VALUE L_q is summed like a number into every
+ *     pixel that counts its tap (Inf - Inf and 0 Inf give NaN) and changes no other pixel.  The sign and payload of a NaN written are not specified.
+ *     RT_ERR_INVALID, output untouched: a NULL pointer; factor outside [2, 4]; n_planes outside [1, 2]; width or height <= 0 or no multiple of factor; 2^28
+ *     full-resolution pixels or more; an output that overlaps any input (low_aov and aov counted with their three planes).
+ *     THE TWO PIPELINES this serves (f = factor; history stays at the low resolution throughout):
+ *       A: the whole chain at w x h -- render, planes, rt_temporal_accumulate, rt_svgf_filter -- then rt_upsample with n_planes = 1 on the filtered frame;
+ *       B: render, planes and rt_temporal_accumulate at w x h, then rt_upsample with n_planes = 2 on the history, then rt_svgf_filter at full resolution with the
+ *          full-resolution planes.  The upsampled history serves that one frame's filter and is never fed back (a fed-back history of B is at full resolution: drop it).
+ *     In both, rt_demodulate runs at the low resolution with the low planes BEFORE the upsample and rt_modulate at full resolution with the full planes AFTER it:
+ *     irradiance is what is interpolated, and a texture's detail comes back from the full-resolution albedo plane.  That is why the weights have no albedo term. --- */
+typedef struct rt_upsample_params {
+    int32_t factor;                /* f: 2, 3 or 4                                                                  */
+    int32_t n_planes;              /* 1: a colour frame; 2: a history (both planes of rt_temporal_accumulate)       */
+    float   k_normal, k_position;
+} rt_upsample_params;              /* 16 bytes */
+int rt_upsample_device(rt_ctx *ctx, const void *low_dev, const void *low_aov_dev, const void *aov_dev, int width, int height, const rt_upsample_params *up, void *out_dev, void *stream);
+int rt_upsample(rt_ctx *ctx, const float *low_host, const float *low_aov_host, const float *aov_host, int width, int height, const rt_upsample_params *up, float *out_host);
+
 /* --- one host process, several devices (SURVEY 8b rt_render_multi; the reference uses the implicit device 0,
  *     optimized.cu:828-856).  The frame is cut into RT_MULTI_TILE_ROWS-row tiles, tile k -> device k mod n
  *     (interleaved); the scene is replicated; every device renders its tiles; each peer pushes them over

@@ -32,7 +32,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_render_aov_device", "rt_render_aov", "rt_denoise_device", "rt_denoise",
            "rt_temporal_accumulate_device", "rt_temporal_accumulate", "rt_denoise_var_device", "rt_denoise_var",
            "rt_svgf_filter_device", "rt_svgf_filter",
-           "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate"]
+           "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate",
+           "rt_upsample_device", "rt_upsample"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -201,6 +202,20 @@ def make_svgf_params(n_passes=None, feedback_pass=None, prefilter=None, k_normal
     """rt_svgf_params; None = the default of SVGF_DEFAULTS.  feedback_pass -1 = no history is written; prefilter 0 / 1."""
     return _filled(SvgfParams(), SVGF_DEFAULTS, n_passes=n_passes, feedback_pass=feedback_pass, prefilter=prefilter, k_normal=k_normal, k_position=k_position,
                    k_albedo=k_albedo, k_sigma=k_sigma, var_floor=var_floor)
+
+
+class UpsampleParams(C.Structure):
+    _fields_ = [("factor", C.c_int32), ("n_planes", C.c_int32), ("k_normal", C.c_float), ("k_position", C.c_float)]
+
+
+# The defaults of make_upsample_params: the filters' own normal and plane tolerances (DESIGN.md section 5.11 measured the guided upsample with them).
+UPSAMPLE_DEFAULTS = dict(k_normal=DENOISE_VAR_DEFAULTS["k_normal"], k_position=DENOISE_VAR_DEFAULTS["k_position"])
+
+
+def make_upsample_params(factor, n_planes=1, k_normal=None, k_position=None):
+    """rt_upsample_params: factor 2 .. 4, n_planes 1 (a colour frame) or 2 (a history); None = the default of UPSAMPLE_DEFAULTS.  A k of 0 switches its term off."""
+    u = UpsampleParams(int(factor), int(n_planes))
+    return _filled(u, UPSAMPLE_DEFAULTS, k_normal=k_normal, k_position=k_position)
 
 
 def static_motion():
@@ -373,6 +388,8 @@ def load():
     L.rt_demodulate.argtypes = [vp, fp3, fp3, C.c_int64, C.c_float, fp3]
     L.rt_modulate_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, vp, vp]
     L.rt_modulate.argtypes = [vp, fp3, fp3, C.c_int64, C.c_float, fp3]
+    L.rt_upsample_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(UpsampleParams), vp, vp]
+    L.rt_upsample.argtypes = [vp, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(UpsampleParams), fp3]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_device_alloc.argtypes = [vp, C.POINTER(vp), C.c_size_t]
     L.rt_device_free.argtypes = [vp]
@@ -938,6 +955,31 @@ class Context:
     def modulate_device(self, color_ptr, aov_ptr, n_pixels, out_ptr, albedo_floor=0.0, stream=None):
         """rt_modulate_device: as demodulate_device, multiplying."""
         self._check(self._L.rt_modulate_device(self._h, C.c_void_p(color_ptr), C.c_void_p(aov_ptr), int(n_pixels), float(albedo_floor), C.c_void_p(out_ptr),
+                                               C.c_void_p(stream) if stream else None))
+
+    # --- guided upsampling of a frame or a history traced at 1 / factor of the resolution (rt_upsample*)
+    def upsample(self, low, low_aov, aov, factor, k_normal=None, k_position=None, out=None):
+        """rt_upsample: low [h, w, 4] (a colour frame) or [2, h, w, 4] (a history of temporal_accumulate), low_aov [3, h, w, 4] and aov [3, factor h, factor w, 4]
+        (render_aov at both resolutions) -> the frame [H, W, 4] or the history [2, H, W, 4] at full resolution.  Parameters as make_upsample_params."""
+        bad = (f"upsample: low {np.shape(low)} must be [h, w, 4] or [2, h, w, 4], low_aov {np.shape(low_aov)} [3, h, w, 4] and aov {np.shape(aov)} "
+               f"[3, {factor} h, {factor} w, 4]")
+        low = self._f32(low, lambda s: len(s) in (3, 4) and s[-1] == 4 and (len(s) == 3 or s[0] == 2), bad)
+        n_planes, (h, w) = (1 if low.ndim == 3 else 2), low.shape[-3:-1]
+        low_aov = self._f32(low_aov, lambda s: s == (3, h, w, 4), bad)
+        aov = self._f32(aov, lambda s: s == (3, h * int(factor), w * int(factor), 4), bad)
+        out = self._out("upsample", out, low.shape[:-3] + aov.shape[1:])
+        up = make_upsample_params(factor, n_planes, k_normal, k_position)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_upsample(self._h, low.ctypes.data_as(fp), low_aov.ctypes.data_as(fp), aov.ctypes.data_as(fp), aov.shape[2], aov.shape[1], C.byref(up),
+                                        out.ctypes.data_as(fp)))
+        return out
+
+    def upsample_device(self, low_ptr, low_aov_ptr, aov_ptr, width, height, factor, out_ptr, n_planes=1, k_normal=None, k_position=None, stream=None):
+        """rt_upsample_device: device pointers (n_planes planes at (width / factor) x (height / factor), the planes at that and at the full resolution, the
+        n_planes full-resolution planes of the result), asynchronous on `stream`.  width, height: the FULL resolution."""
+        up = make_upsample_params(factor, n_planes, k_normal, k_position)
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._L.rt_upsample_device(self._h, opt(low_ptr), opt(low_aov_ptr), opt(aov_ptr), int(width), int(height), C.byref(up), opt(out_ptr),
                                                C.c_void_p(stream) if stream else None))
 
     def render_pose(self, params, pose):

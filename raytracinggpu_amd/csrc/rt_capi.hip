@@ -503,3 +503,4 @@ int rt_get_stats(rt_ctx *ctx, rt_stats *stats) {
 #include "rt_denoise.hip.h"
 #include "rt_temporal.hip.h"
 #include "rt_demodulate.hip.h"
+#include "rt_upsample.hip.h"

@@ -1,25 +1,46 @@
 """SvgfSequence: the per-frame denoising chain and the buffers it swaps, over the device entry points of a Context.
 
 render -> render_aov_device -> temporal_accumulate_device -> svgf_filter_device on one stream.  The accumulation of frame t takes as its previous history what the
-filter of frame t - 1 fed back (svgf_filter's out_history; the accumulated history itself when the parameters feed nothing back), and the planes of frame t - 1."""
-from ._capi import CameraPose, RtError, make_reproject, make_svgf_params, make_temporal_params
+filter of frame t - 1 fed back (svgf_filter's out_history; the accumulated history itself when the parameters feed nothing back), and the planes of frame t - 1.
+
+upsample = f in 2 .. 4 (off by default: a speed knob that costs quality) traces and accumulates at 1 / f of the resolution and rebuilds the
+full-resolution frame with upsample_device, guided by full-resolution planes rendered once per frame:
+  filter_at="low"  (pipeline A)  the whole chain at the low resolution, then the filtered frame is upsampled;
+  filter_at="full" (pipeline B)  the accumulated history is upsampled (both planes) and svgf_filter_device runs at full resolution.
+History, previous planes, reprojection, motion tables and cut all stay at the low resolution, as without the option."""
+from ._capi import CameraPose, Params, RtError, make_reproject, make_svgf_params, make_temporal_params
 
 
 class SvgfSequence:
-    """Owns two histories (the accumulated one and the one handed on), two sets of planes, a colour frame and an output, all from the context's device allocator.
+    """Owns two histories (the accumulated one and the one handed on), two sets of planes, a colour frame and an output, all from the context's device allocator;
+    with upsample > 1 those are at the low resolution, and the full-resolution planes and the frame (A) or history (B) between the two resolutions come on top.
 
     ctx: a Context with its scene uploaded.  svgf = make_svgf_params(...), temporal = make_temporal_params(...) (None: the defaults).  camera: the fixed camera
-    (position, fov) the scene was uploaded with, for frames without a pose (None: scene_upload's default).  stream: the stream of every call (None: the context's)."""
+    (position, fov) the scene was uploaded with, for frames without a pose (None: scene_upload's default).  stream: the stream of every call (None: the context's).
+    upsample, filter_at: see the module; up_k_normal, up_k_position: the upsample's weights (None: UPSAMPLE_DEFAULTS)."""
 
-    def __init__(self, ctx, width, height, svgf=None, temporal=None, camera=None, stream=None):
+    def __init__(self, ctx, width, height, svgf=None, temporal=None, camera=None, stream=None, upsample=1, filter_at="low", up_k_normal=None, up_k_position=None):
         self.ctx, self.width, self.height, self.stream = ctx, int(width), int(height), stream
         self.svgf = make_svgf_params() if svgf is None else svgf
         self.temporal = make_temporal_params() if temporal is None else temporal
         self.camera = camera
-        frame = self.width * self.height * 16
+        self.upsample, self.filter_at, self.up_k = int(upsample), filter_at, (up_k_normal, up_k_position)
+        f = self.upsample
+        if f < 1 or f > 4 or filter_at not in ("low", "full"):
+            raise RtError(-1, f"SvgfSequence: upsample {upsample} must be 1 .. 4 and filter_at {filter_at!r} 'low' or 'full'")
+        if self.width % f or self.height % f:
+            raise RtError(-1, f"SvgfSequence: {self.width} x {self.height} is no multiple of upsample {f}")
+        if f > 1 and filter_at == "full" and self.svgf.feedback_pass >= 0:
+            raise RtError(-1, "SvgfSequence: filter_at='full' filters an upsampled history, which is never fed back: feedback_pass must be -1")
+        self.low_width, self.low_height = self.width // f, self.height // f
+        frame, full = self.low_width * self.low_height * 16, self.width * self.height * 16
         self._ptrs = []
         try:
-            self.color, self.out, self.accumulated, self.history, *self.planes = (self._alloc(n * frame) for n in (1, 1, 2, 2, 3, 3))
+            self.color, self.accumulated, self.history, *self.planes = (self._alloc(n * frame) for n in (1, 2, 2, 3, 3))
+            self.out = self._alloc(full)
+            if f > 1:
+                self.full_planes = self._alloc(3 * full)
+                self.between = self._alloc(frame if filter_at == "low" else 2 * full)   # A: the filtered low-resolution frame; B: the upsampled history
         except RtError:
             self.close()
             raise
@@ -32,11 +53,16 @@ class SvgfSequence:
 
     def frame(self, params, pose=None, motion=None, no_history_mask=0, cut=False):
         """One frame of the chain -> the device address of the filtered frame (self.out: width x height float4, valid until the next call; asynchronous on the
-        stream).  params: the frame's render parameters (a new seed per frame); pose: its CameraPose (None: the uploaded camera); motion: the table "previous from
-        current" of what moved since the previous frame (None: nothing); cut=True, and the first call, use no previous frame."""
+        stream).  params: the frame's render parameters at the FULL resolution (a new seed per frame; with upsample > 1 the low-resolution ones are these with the
+        size divided); pose: its CameraPose (None: the uploaded camera); motion: the table "previous from current" of what moved since the previous frame (None:
+        nothing); cut=True, and the first call, use no previous frame."""
         if (params.width, params.height) != (self.width, self.height):
             raise RtError(-1, f"SvgfSequence.frame: params are {params.width} x {params.height}, the sequence {self.width} x {self.height}")
-        c, s, W, H = self.ctx, self.stream, self.width, self.height
+        c, s, W, H, f = self.ctx, self.stream, self.low_width, self.low_height, self.upsample
+        full = params
+        if f > 1:
+            params = Params.from_buffer_copy(full)
+            params.width, params.height = W, H
         planes, previous = self.planes
         if pose is not None:
             c.render_pose_device(params, pose, self.color, stream=s)
@@ -48,11 +74,21 @@ class SvgfSequence:
         else:
             rp = make_reproject(camera=self.camera, pose=self._previous_pose, motion=motion, no_history_mask=no_history_mask)
             c.temporal_accumulate_device(self.color, planes, previous, self.history, W, H, self.accumulated, reproject=rp, params=self.temporal, stream=s)
-        if self.svgf.feedback_pass >= 0:
-            c.svgf_filter_device(self.accumulated, planes, W, H, self.out, self.history, params=self.svgf, stream=s)
-        else:                                                          # nothing is fed back: the accumulated history is the one handed on
-            c.svgf_filter_device(self.accumulated, planes, W, H, self.out, None, params=self.svgf, stream=s)
+        if f > 1:
+            c.render_aov_device(full, self.full_planes, pose=pose, stream=s)
+        if f > 1 and self.filter_at == "full":                         # B: the history goes up, the filter runs on it at full resolution
+            c.upsample_device(self.accumulated, planes, self.full_planes, self.width, self.height, f, self.between, 2, *self.up_k, stream=s)
+            c.svgf_filter_device(self.between, self.full_planes, self.width, self.height, self.out, None, params=self.svgf, stream=s)
             self.accumulated, self.history = self.history, self.accumulated
+        else:
+            filtered = self.out if f == 1 else self.between
+            if self.svgf.feedback_pass >= 0:
+                c.svgf_filter_device(self.accumulated, planes, W, H, filtered, self.history, params=self.svgf, stream=s)
+            else:                                                      # nothing is fed back: the accumulated history is the one handed on
+                c.svgf_filter_device(self.accumulated, planes, W, H, filtered, None, params=self.svgf, stream=s)
+                self.accumulated, self.history = self.history, self.accumulated
+            if f > 1:                                                  # A: the filtered frame goes up
+                c.upsample_device(filtered, planes, self.full_planes, self.width, self.height, f, self.out, 1, *self.up_k, stream=s)
         self.planes = [previous, planes]
         self._have_previous = True
         self._previous_pose = None if pose is None else CameraPose.from_buffer_copy(pose)
