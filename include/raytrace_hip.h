@@ -716,6 +716,49 @@ typedef struct rt_upsample_params {
 int rt_upsample_device(rt_ctx *ctx, const void *low_dev, const void *low_aov_dev, const void *aov_dev, int width, int height, const rt_upsample_params *up, void *out_dev, void *stream);
 int rt_upsample(rt_ctx *ctx, const float *low_host, const float *low_aov_host, const float *aov_host, int width, int height, const rt_upsample_params *up, float *out_host);
 
+/* --- a responsive history: a fast history beside the long one, and the long one clamped to it (ABI 6, additive; history rectification, "anti-lag").  The
+ *     accumulation accepts a previous pixel that shows the same object, normal and tangent plane; none of these changes when the LIGHT moves or a moving object drags
+ *     its shadow over a wall, so an old shadow lingers for up to max_history frames.  A second history of a few frames follows such a change quickly; where the long
+ *     history has left the band the fast one spans in the pixel's neighbourhood it is clamped into it and made as short as the fast one, so that it converges again.
+ *     Pure post-processing; rt_temporal_accumulate* and every other entry are unchanged.  DESIGN.md section 5.12 has the measurements and the defaults.
+ *     rt_temporal_accumulate_fast*: rt_temporal_accumulate* with an input prev_fast (one plane of width * height float4, given exactly when prev_history is given, NULL
+ *     otherwise), an output out_fast (one such plane) and fast_history >= 1.  out_history is word for word what rt_temporal_accumulate* writes for the same inputs.
+ *     The fast plane is (Fr, Fg, Fb, n_f).  It takes the SAME tap q the long history took -- one reprojection, not a second search:
+ *       tap q accepted (F_q = prev_fast at q):  n_f = min(F_q.w + 1, (float)fast_history),  a_f = max(1 / n_f, alpha_min),  F = F_q.rgb + a_f (C_p.rgb - F_q.rgb);
+ *       no tap, the first frame, an object masked by no_history_mask:  F = C_p.rgb, n_f = 1;      a miss:  (C_p.rgb, 0).
+ *     Same contract: binary32, one rounding per operation, the quotient correctly rounded, min and max are minNum and maxNum (a NaN F_q.w gives n_f = fast_history).
+ *     RT_ERR_INVALID, both outputs untouched: everything rt_temporal_accumulate* refuses; out_fast NULL; prev_fast without prev_history or the reverse;
+ *     fast_history < 1; either output overlapping any input (prev_fast among them) or the other output.
+ *     rt_history_rectify*: inputs -- the history just written (two planes), the fast plane just written, the current planes (only plane 0, normal | id, is read), the
+ *     parameters.  Output: a history (two planes).  Pixel p = (x, y) with id_p = plane 0 .w, H0_p = (H.rgb, rays), H1_p = (m1, m2, n, V), F_p = (F.rgb, n_f):
+ *       id_p == -1 (a miss), or H1_p.z <= F_p.w (the long history holds nothing older than the fast one):  a copy, every word.   (A NaN on either side of <=: no copy.)
+ *       Otherwise, over the (2 radius + 1)^2 window, dy = -radius .. radius (outer), dx = -radius .. radius (inner), q = (x + dx, y + dy) inside the image with
+ *       id_q == id_p -- the pixel itself always counts, whatever its id:
+ *         per channel c:  s1_c += F_q.c;   s2_c += F_q.c F_q.c;   cnt += 1;
+ *         mu_c = s1_c / cnt;   e2_c = s2_c / cnt;   sg_c = sqrt(max(0, e2_c - mu_c mu_c))   (quotients and root correctly rounded);
+ *         lo_c = mu_c - k_clamp sg_c;   hi_c = mu_c + k_clamp sg_c;   H'_c = min(max(H_c, lo_c), hi_c).
+ *       If no channel moved (H'_c == H_c for all three):  a copy, every word.
+ *       Else:  plane 0 = (H', H0_p.w);   n' = F_p.w;   d = l(H') - l(H)  (l: the luminance of rt_temporal_accumulate);   m1' = m1 + d;
+ *              m2' = m2 + (m1' m1' - m1 m1);   plane 1 = (m1', m2', n', V).
+ *     A clamped pixel's history is only as long as the fast one, so the next frames blend it at 1 / (n_f + 1) and it converges again; shifting both moments keeps
+ *     m2 - m1 m1, the variance the filter reads, where it was.  k_clamp == 0 makes the band the point mu.
+ *     NON-FINITE INPUTS, from minNum / maxNum and the comparisons alone (nothing is special-cased): a NaN H_c is replaced by lo_c (a NaN never equals itself: the
+ *     pixel counts as moved); a NaN F_q.c in the window makes mu_c, lo_c and hi_c NaN and leaves H_c as it is; a +-Inf F_q.c makes mu_c that Inf and sg_c =
+ *     sqrt(max(0, NaN)) = 0, so every pixel whose window holds it is clamped to the Inf; a NaN id_p matches no neighbour and the window is the pixel alone; NaN moments
+ *     are shifted like numbers.  The sign and payload of a NaN written are not specified.
+ *     out == history EXACTLY (in place) is allowed: a pixel reads and writes its own two records only.  RT_ERR_INVALID, output untouched: a NULL pointer; radius
+ *     outside [1, 3]; k_clamp negative or NaN; width or height <= 0 or 2^28 pixels or more; any other overlap of the output with an input.
+ *     THE SEQUENCE per frame: rt_temporal_accumulate_fast -> rt_history_rectify in place on the accumulated history -> rt_svgf_filter (or rt_upsample with n_planes = 2
+ *     in pipeline B); the rectified history and the fast plane are next frame's prev_history and prev_fast.  A cut passes neither. --- */
+typedef struct rt_rectify_params {
+    int32_t radius;                /* 1 .. 3: the window is (2 radius + 1)^2 pixels                                 */
+    float   k_clamp;               /* >= 0: the band is the mean +- k_clamp standard deviations of the fast colour  */
+} rt_rectify_params;               /* 8 bytes */
+int rt_temporal_accumulate_fast_device(rt_ctx *ctx, const void *color_rgba_dev, const void *aov_dev, const void *prev_aov_dev, const void *prev_history_dev, const void *prev_fast_dev, int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, int fast_history, void *out_history_dev, void *out_fast_dev, void *stream);
+int rt_temporal_accumulate_fast(rt_ctx *ctx, const float *color_rgba_host, const float *aov_host, const float *prev_aov_host, const float *prev_history_host, const float *prev_fast_host, int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, int fast_history, float *out_history_host, float *out_fast_host);
+int rt_history_rectify_device(rt_ctx *ctx, const void *history_dev, const void *fast_dev, const void *aov_dev, int width, int height, const rt_rectify_params *rp, void *out_history_dev, void *stream);
+int rt_history_rectify(rt_ctx *ctx, const float *history_host, const float *fast_host, const float *aov_host, int width, int height, const rt_rectify_params *rp, float *out_history_host);
+
 /* --- one host process, several devices (SURVEY 8b rt_render_multi; the reference uses the implicit device 0,
  *     optimized.cu:828-856).  The frame is cut into RT_MULTI_TILE_ROWS-row tiles, tile k -> device k mod n
  *     (interleaved); the scene is replicated; every device renders its tiles; each peer pushes them over

@@ -641,6 +641,30 @@ public:
         check(rt_svgf_filter(ctx_, history.data(), aov.data(), W, H, &sp, out.data(), out_history ? out_history->data() : nullptr), "rt_svgf_filter");
         return out;
     }
+    // Temporal accumulation that also keeps the short history (rt_temporal_accumulate_fast): temporal_accumulate's arguments, the previous fast plane (W * H float4,
+    // empty exactly when prev_history is) and the fast history's length limit -> the history, word for word temporal_accumulate's; out_fast: the new fast plane
+    std::vector<float> temporal_accumulate_fast(const std::vector<float> &color, const std::vector<float> &aov, const std::vector<float> &prev_aov, const std::vector<float> &prev_history,
+                                                const std::vector<float> &prev_fast, int W, int H, const rt_temporal_params &tp, const rt_reproject *rp, int fast_history,
+                                                std::vector<float> &out_fast) {
+        const size_t n = (size_t)W * H * 4;
+        if (color.size() != n || aov.size() < 2 * n || prev_aov.empty() != prev_history.empty() || prev_fast.empty() != prev_history.empty() ||
+            (!prev_aov.empty() && (prev_aov.size() < 2 * n || prev_history.size() != 2 * n || prev_fast.size() != n)))
+            throw Error(RT_ERR_INVALID, "temporal_accumulate_fast: color and a fast plane are W * H float4, the planes at least two such, a history exactly two");
+        std::vector<float> out(2 * n);
+        out_fast.resize(n);
+        check(rt_temporal_accumulate_fast(ctx_, color.data(), aov.data(), prev_aov.empty() ? nullptr : prev_aov.data(), prev_history.empty() ? nullptr : prev_history.data(),
+                                          prev_fast.empty() ? nullptr : prev_fast.data(), W, H, &tp, rp, fast_history, out.data(), out_fast.data()), "rt_temporal_accumulate_fast");
+        return out;
+    }
+    // ... and that history clamped to the band of the fast one over each pixel's window (rt_history_rectify): where the long history lags behind a change the
+    // reprojection cannot see (a moving light, a moving shadow) it is pulled to the fast one and shortened -> the rectified history, two planes
+    std::vector<float> history_rectify(const std::vector<float> &history, const std::vector<float> &fast, const std::vector<float> &aov, int W, int H, const rt_rectify_params &rp) {
+        const size_t n = (size_t)W * H * 4;
+        if (history.size() != 2 * n || fast.size() != n || aov.size() < n) throw Error(RT_ERR_INVALID, "history_rectify: history is two planes of W * H float4, fast one, aov at least one");
+        std::vector<float> out(2 * n);
+        check(rt_history_rectify(ctx_, history.data(), fast.data(), aov.data(), W, H, &rp, out.data()), "rt_history_rectify");
+        return out;
+    }
     // The same three planes for the first DIFFUSE surface of each pixel, followed through at most max_specular mirror / glass segments (rt_render_aov_surface):
     // plane 0 .w is the path code (id, or id + 16 first_id + 256 k; -1 a miss), plane 2 .w is 1 where the chain ended diffuse and the albedo factors out of the pixel.
     std::vector<float> render_aov_surface(const RenderSettings &s, int max_specular, const rt_camera_pose *pose = nullptr) {

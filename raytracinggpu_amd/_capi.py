@@ -33,7 +33,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_temporal_accumulate_device", "rt_temporal_accumulate", "rt_denoise_var_device", "rt_denoise_var",
            "rt_svgf_filter_device", "rt_svgf_filter",
            "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate",
-           "rt_upsample_device", "rt_upsample"]
+           "rt_upsample_device", "rt_upsample",
+           "rt_temporal_accumulate_fast_device", "rt_temporal_accumulate_fast", "rt_history_rectify_device", "rt_history_rectify"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -218,6 +219,22 @@ def make_upsample_params(factor, n_planes=1, k_normal=None, k_position=None):
     return _filled(u, UPSAMPLE_DEFAULTS, k_normal=k_normal, k_position=k_position)
 
 
+class RectifyParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("k_clamp", C.c_float)]
+
+
+# The defaults of make_rectify_params and of SvgfSequence's fast_history: the row of the scan of DESIGN.md section 5.12 with the least error on the moving-light
+# sequence after the light starts to move, among those that lose least on the two static sequences.
+RECTIFY_DEFAULTS = dict(radius=1, k_clamp=1.0)
+FAST_HISTORY_DEFAULT = 4
+
+
+def make_rectify_params(radius=None, k_clamp=None):
+    """rt_rectify_params: the window is (2 radius + 1)^2 pixels, radius 1 .. 3; the band is the fast history's mean +- k_clamp standard deviations over it, k_clamp >= 0;
+    None = the default of RECTIFY_DEFAULTS."""
+    return _filled(RectifyParams(), RECTIFY_DEFAULTS, radius=radius, k_clamp=k_clamp)
+
+
 def static_motion():
     """[MAX_OBJECTS, 12] float32: the motion table in which nothing moved (rotation = identity, translation = 0); row i = object i's rotation[9] | translation[3]."""
     m = np.zeros((MAX_OBJECTS, 12), np.float32)
@@ -390,6 +407,10 @@ def load():
     L.rt_modulate.argtypes = [vp, fp3, fp3, C.c_int64, C.c_float, fp3]
     L.rt_upsample_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(UpsampleParams), vp, vp]
     L.rt_upsample.argtypes = [vp, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(UpsampleParams), fp3]
+    L.rt_temporal_accumulate_fast_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), C.c_int, vp, vp, vp]
+    L.rt_temporal_accumulate_fast.argtypes = [vp, fp3, fp3, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), C.c_int, fp3, fp3]
+    L.rt_history_rectify_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(RectifyParams), vp, vp]
+    L.rt_history_rectify.argtypes = [vp, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(RectifyParams), fp3]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_device_alloc.argtypes = [vp, C.POINTER(vp), C.c_size_t]
     L.rt_device_free.argtypes = [vp]
@@ -899,6 +920,59 @@ class Context:
         opt = lambda p: C.c_void_p(p) if p else None
         self._check(self._L.rt_svgf_filter_device(self._h, opt(history_ptr), opt(aov_ptr), int(width), int(height), C.byref(sp), opt(out_ptr), opt(out_history_ptr),
                                                   C.c_void_p(stream) if stream else None))
+
+    # --- the fast history beside the long one, and the long one clamped to it (rt_temporal_accumulate_fast*, rt_history_rectify*)
+    def temporal_accumulate_fast(self, color, aov, prev_aov=None, prev_history=None, prev_fast=None, reproject=None, params=None, fast_history=None, out=None, out_fast=None):
+        """rt_temporal_accumulate_fast: temporal_accumulate's inputs and prev_fast [H, W, 4] (given exactly when prev_history is) -> (the history [2, H, W, 4], word for
+        word temporal_accumulate's, and the fast plane [H, W, 4]: colour | fast history length, at most fast_history -- None: FAST_HISTORY_DEFAULT)."""
+        bad = f"temporal_accumulate_fast: color {np.shape(color)} must be [H, W, 4] and aov {np.shape(aov)} [3, H, W, 4] of the same frame"
+        color = self._f32(color, lambda s: len(s) == 3 and s[2] == 4, bad)
+        planes_ok = lambda s: len(s) == 4 and s[0] >= 2 and s[1:] == color.shape
+        aov = self._f32(aov, planes_ok, bad)
+        fp = C.POINTER(C.c_float)
+        given = []
+        for name, a, ok in (("prev_aov", prev_aov, planes_ok), ("prev_history", prev_history, lambda s: s == (2,) + color.shape), ("prev_fast", prev_fast, lambda s: s == color.shape)):
+            if a is not None:
+                a = self._f32(a, ok, f"temporal_accumulate_fast: {name} {np.shape(a)} does not fit a frame of {color.shape}")
+            given.append(a)
+        out = self._out("temporal_accumulate_fast", out, (2,) + color.shape)
+        out_fast = self._out("temporal_accumulate_fast", out_fast, color.shape)
+        tp = make_temporal_params() if params is None else params
+        self._check(self._L.rt_temporal_accumulate_fast(self._h, color.ctypes.data_as(fp), aov.ctypes.data_as(fp), *(None if a is None else a.ctypes.data_as(fp) for a in given),
+                                                        color.shape[1], color.shape[0], C.byref(tp), C.byref(reproject) if reproject is not None else None,
+                                                        FAST_HISTORY_DEFAULT if fast_history is None else int(fast_history), out.ctypes.data_as(fp), out_fast.ctypes.data_as(fp)))
+        return out, out_fast
+
+    def temporal_accumulate_fast_device(self, color_ptr, aov_ptr, prev_aov_ptr, prev_history_ptr, prev_fast_ptr, width, height, out_ptr, out_fast_ptr, reproject=None, params=None,
+                                        fast_history=None, stream=None):
+        """rt_temporal_accumulate_fast_device: device pointers (0 / None for the previous three = the first frame), asynchronous on `stream`."""
+        tp = make_temporal_params() if params is None else params
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._L.rt_temporal_accumulate_fast_device(self._h, opt(color_ptr), opt(aov_ptr), opt(prev_aov_ptr), opt(prev_history_ptr), opt(prev_fast_ptr), int(width),
+                                                               int(height), C.byref(tp), C.byref(reproject) if reproject is not None else None,
+                                                               FAST_HISTORY_DEFAULT if fast_history is None else int(fast_history), opt(out_ptr), opt(out_fast_ptr),
+                                                               C.c_void_p(stream) if stream else None))
+
+    def history_rectify(self, history, fast, aov, params=None, out=None):
+        """rt_history_rectify: history [2, H, W, 4] and fast [H, W, 4] of temporal_accumulate_fast, aov [>= 1, H, W, 4] (plane 0 is read), params =
+        make_rectify_params(...) -> the rectified history [2, H, W, 4].  out: optional preallocated result; it may be `history` itself (in place)."""
+        bad = f"history_rectify: history {np.shape(history)} must be [2, H, W, 4], fast {np.shape(fast)} [H, W, 4] and aov {np.shape(aov)} [1 or more, H, W, 4] of the same frame"
+        history = self._f32(history, lambda s: len(s) == 4 and s[0] == 2 and s[3] == 4, bad)
+        fast = self._f32(fast, lambda s: s == history.shape[1:], bad)
+        aov = self._f32(aov, lambda s: len(s) == 4 and s[0] >= 1 and s[1:] == history.shape[1:], bad)
+        out = self._out("history_rectify", out, history.shape)
+        rp = make_rectify_params() if params is None else params
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_history_rectify(self._h, history.ctypes.data_as(fp), fast.ctypes.data_as(fp), aov.ctypes.data_as(fp), history.shape[2], history.shape[1],
+                                               C.byref(rp), out.ctypes.data_as(fp)))
+        return out
+
+    def history_rectify_device(self, history_ptr, fast_ptr, aov_ptr, width, height, out_ptr, params=None, stream=None):
+        """rt_history_rectify_device: device pointers (out_ptr == history_ptr: in place), asynchronous on `stream`."""
+        rp = make_rectify_params() if params is None else params
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._L.rt_history_rectify_device(self._h, opt(history_ptr), opt(fast_ptr), opt(aov_ptr), int(width), int(height), C.byref(rp), opt(out_ptr),
+                                                      C.c_void_p(stream) if stream else None))
 
     # --- the planes of the first diffuse surface, and the albedo divided out of / multiplied into a frame (rt_render_aov_surface*, rt_demodulate*, rt_modulate*)
     def render_aov_surface(self, params, max_specular, pose=None, rows=None):

@@ -504,3 +504,4 @@ int rt_get_stats(rt_ctx *ctx, rt_stats *stats) {
 #include "rt_temporal.hip.h"
 #include "rt_demodulate.hip.h"
 #include "rt_upsample.hip.h"
+#include "rt_rectify.hip.h"        // after rt_temporal.hip.h: it clamps the history that rt_temporal_accumulate_fast writes

@@ -27,17 +27,26 @@ struct TpArgs {
     int have_prev, have_motion;
 };
 
+// FAST (rt_temporal_accumulate_fast*): the second, short history rides on the SAME accepted tap; its three arguments -- the previous fast plane, the new one, the
+// length limit -- exist in that instantiation alone, so temporal_accumulate_kernel<false> has the arguments and the instructions the kernel always had.
+struct TpFast { const float4 *__restrict__ pf; float4 *__restrict__ of; float fast_hist; };
+template <bool FAST, class... Fast>
 __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *__restrict__ C, const float4 *__restrict__ g, const float4 *__restrict__ pg,
-                                                                   const float4 *__restrict__ ph, float4 *__restrict__ out, int W, int H, const TpArgs a, const TpMotions mt) {
+                                                                   const float4 *__restrict__ ph, float4 *__restrict__ out, int W, int H, const TpArgs a, const TpMotions mt,
+                                                                   const Fast... fast) {
+    static_assert(sizeof...(Fast) == (FAST ? 1 : 0), "the fast instantiation takes one TpFast");
     const size_t plane = (size_t)W * (size_t)H;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= plane) return;
     const int y = (int)(i / (size_t)W), x = (int)(i - (size_t)y * W);
     const float4 Cp = C[i], Np = g[i];
     float4 o0 = Cp, o1 = make_float4(0.f, 0.f, 0.f, 0.f);             // a miss: a copy, no history, no variance
+    [[maybe_unused]] float4 f0;
+    if constexpr (FAST) f0 = make_float4(Cp.x, Cp.y, Cp.z, 0.f);      // a miss: the colour, no history
     if (Np.w != -1.f) {
         const float lp = lum709(Cp);
         float n = 1.f, cr = Cp.x, cg = Cp.y, cb = Cp.z, m1 = lp, m2 = lp * lp;
+        if constexpr (FAST) f0.w = 1.f;
         const int id = (int)Np.w;
         if (a.have_prev && !((a.mask >> (id & 31)) & 1u)) {
             const float4 Pp = g[plane + i];
@@ -78,6 +87,13 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *
                     cr = H0.x + al * (Cp.x - H0.x); cg = H0.y + al * (Cp.y - H0.y); cb = H0.z + al * (Cp.z - H0.z);
                     m1 = H1.x + al * (lp - H1.x);
                     m2 = H1.y + al * (lp * lp - H1.y);
+                    if constexpr (FAST) {                             // the fast history of the same tap, its own length and weight
+                        const TpFast &f = (fast, ...);
+                        const float4 Fq = f.pf[q];
+                        const float nf = fminf(Fq.w + 1.f, f.fast_hist);
+                        const float af = fmaxf(div_quot(1.f, nf), a.alpha_min);
+                        f0 = make_float4(Fq.x + af * (Cp.x - Fq.x), Fq.y + af * (Cp.y - Fq.y), Fq.z + af * (Cp.z - Fq.z), nf);
+                    }
                     break;
                 }
             }
@@ -108,6 +124,7 @@ __global__ __launch_bounds__(256) void temporal_accumulate_kernel(const float4 *
     }
     out[i] = o0;
     out[plane + i] = o1;
+    if constexpr (FAST) (fast, ...).of[i] = f0;
 }
 
 }  // namespace rtk
@@ -127,21 +144,12 @@ static bool tp_aliased(const void *color, const void *aov, const void *prev_aov,
            (prev_aov && (overlaps(out, 2 * bytes, prev_aov, 2 * bytes) || overlaps(out, 2 * bytes, prev_hist, 2 * bytes)));   // (tp_check: both or neither)
 }
 
-extern "C" int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, const void *prev_aov_dev, const void *prev_history_dev, int width, int height,
-                                             const rt_temporal_params *tp, const rt_reproject *rp, void *out_history_dev, void *stream) {
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
-    int rc = tp_check(ctx, color_dev, aov_dev, prev_aov_dev, prev_history_dev, width, height, tp, rp, out_history_dev);
-    if (rc != RT_OK) return rc;
-    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
-    if (tp_aliased(color_dev, aov_dev, prev_aov_dev, prev_history_dev, bytes, out_history_dev)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
-    hipStream_t q;
-    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
-    rtk::TpArgs a{};
-    rtk::TpMotions mt{};
+// the kernels' arguments from the parameters and the reprojection record
+static void tp_args(int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, bool have_prev, rtk::TpArgs &a, rtk::TpMotions &mt) {
     a.bx[0] = a.by[1] = a.bz[2] = 1.f;
     a.half_w = (float)width / 2; a.half_h = (float)height / 2;
     a.max_hist = (float)tp->max_history; a.alpha_min = tp->alpha_min; a.min_ndot = tp->min_normal_dot; a.max_pd2 = tp->max_plane_dist * tp->max_plane_dist;
-    a.have_prev = prev_aov_dev != nullptr;
+    a.have_prev = have_prev;
     if (a.have_prev) {
         a.mask = rp->no_history_mask;
         if (rp->posed) {                                              // make_frame's posed camera
@@ -163,8 +171,22 @@ extern "C" int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_dev,
             }
         }
     }
+}
+
+extern "C" int rt_temporal_accumulate_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, const void *prev_aov_dev, const void *prev_history_dev, int width, int height,
+                                             const rt_temporal_params *tp, const rt_reproject *rp, void *out_history_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = tp_check(ctx, color_dev, aov_dev, prev_aov_dev, prev_history_dev, width, height, tp, rp, out_history_dev);
+    if (rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    if (tp_aliased(color_dev, aov_dev, prev_aov_dev, prev_history_dev, bytes, out_history_dev)) return fail(ctx, RT_ERR_INVALID, "the output overlaps an input");
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+    rtk::TpArgs a{};
+    rtk::TpMotions mt{};
+    tp_args(width, height, tp, rp, prev_aov_dev != nullptr, a, mt);
     note_between(ctx, q, {{color_dev, bytes}, {out_history_dev, 2 * bytes}});   // a pipelined frame must not overtake this read of a frame / write of a history
-    hipLaunchKernelGGL(rtk::temporal_accumulate_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, q, static_cast<const float4 *>(color_dev), static_cast<const float4 *>(aov_dev),
+    hipLaunchKernelGGL(rtk::temporal_accumulate_kernel<false>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, q, static_cast<const float4 *>(color_dev), static_cast<const float4 *>(aov_dev),
                        static_cast<const float4 *>(prev_aov_dev), static_cast<const float4 *>(prev_history_dev), static_cast<float4 *>(out_history_dev), width, height, a, mt);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
@@ -182,5 +204,60 @@ extern "C" int rt_temporal_accumulate(rt_ctx *ctx, const float *color_host, cons
     const float *pa = prev_aov_host, *ph = prev_history_host;
     return staged(ctx, {{color_host, bytes}, {aov_host, 2 * bytes}, {pa, 2 * bytes}, {ph, 2 * bytes}}, 7 * bytes, 2 * bytes, out_history_host, [&](uint8_t *d) {
         return rt_temporal_accumulate_device(ctx, d, d + bytes, pa ? d + 3 * bytes : nullptr, pa ? d + 5 * bytes : nullptr, width, height, tp, rp, d + 7 * bytes, nullptr);
+    });
+}
+
+// ---- rt_temporal_accumulate_fast[_device]: the same call with a second, short history beside the long one (raytrace_hip.h; what rt_history_rectify clamps to) ----
+// what the fast form checks on top of tp_check, and tp_aliased extended to the two new buffers: no output over an input, nor over the other output
+static int tpf_check(rt_ctx *ctx, const void *color, const void *aov, const void *prev_aov, const void *prev_hist, const void *prev_fast, int width, int height,
+                     const rt_temporal_params *tp, const rt_reproject *rp, int fast_history, const void *out, const void *out_fast) {
+    if (!out_fast) return fail(ctx, RT_ERR_INVALID, "out_fast is NULL");
+    if (int rc = tp_check(ctx, color, aov, prev_aov, prev_hist, width, height, tp, rp, out); rc != RT_OK) return rc;
+    if ((prev_fast == nullptr) != (prev_hist == nullptr)) return fail(ctx, RT_ERR_INVALID, "the previous fast plane comes exactly when the previous history does");
+    if (fast_history < 1) return fail(ctx, RT_ERR_INVALID, "fast_history %d < 1", fast_history);
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    if (tp_aliased(color, aov, prev_aov, prev_hist, bytes, out) || (prev_fast && overlaps(out, 2 * bytes, prev_fast, bytes)) || overlaps(out, 2 * bytes, out_fast, bytes) ||
+        overlaps(out_fast, bytes, color, bytes) || overlaps(out_fast, bytes, aov, 2 * bytes) ||
+        (prev_aov && (overlaps(out_fast, bytes, prev_aov, 2 * bytes) || overlaps(out_fast, bytes, prev_hist, 2 * bytes) || overlaps(out_fast, bytes, prev_fast, bytes))))
+        return fail(ctx, RT_ERR_INVALID, "an output overlaps an input or the other output");
+    return RT_OK;
+}
+
+extern "C" int rt_temporal_accumulate_fast_device(rt_ctx *ctx, const void *color_dev, const void *aov_dev, const void *prev_aov_dev, const void *prev_history_dev,
+                                                  const void *prev_fast_dev, int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, int fast_history,
+                                                  void *out_history_dev, void *out_fast_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = tpf_check(ctx, color_dev, aov_dev, prev_aov_dev, prev_history_dev, prev_fast_dev, width, height, tp, rp, fast_history, out_history_dev, out_fast_dev);
+    if (rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height, bytes = npix * sizeof(float4);
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+    rtk::TpArgs a{};
+    rtk::TpMotions mt{};
+    tp_args(width, height, tp, rp, prev_aov_dev != nullptr, a, mt);
+    note_between(ctx, q, {{color_dev, bytes}, {out_history_dev, 2 * bytes}, {out_fast_dev, bytes}});
+    hipLaunchKernelGGL((rtk::temporal_accumulate_kernel<true, rtk::TpFast>), dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, q, static_cast<const float4 *>(color_dev),
+                       static_cast<const float4 *>(aov_dev), static_cast<const float4 *>(prev_aov_dev), static_cast<const float4 *>(prev_history_dev),
+                       static_cast<float4 *>(out_history_dev), width, height, a, mt, rtk::TpFast{static_cast<const float4 *>(prev_fast_dev), static_cast<float4 *>(out_fast_dev), (float)fast_history});
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" int rt_temporal_accumulate_fast(rt_ctx *ctx, const float *color_host, const float *aov_host, const float *prev_aov_host, const float *prev_history_host,
+                                           const float *prev_fast_host, int width, int height, const rt_temporal_params *tp, const rt_reproject *rp, int fast_history,
+                                           float *out_history_host, float *out_fast_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    int rc = tpf_check(ctx, color_host, aov_host, prev_aov_host, prev_history_host, prev_fast_host, width, height, tp, rp, fast_history, out_history_host, out_fast_host);
+    if (rc != RT_OK) return rc;
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    // rt_temporal_accumulate's seven planes, the previous fast plane (room kept on a first frame), the new fast plane, the new history
+    const float *pa = prev_aov_host, *ph = prev_history_host, *pf = prev_fast_host;
+    return staged(ctx, {{color_host, bytes}, {aov_host, 2 * bytes}, {pa, 2 * bytes}, {ph, 2 * bytes}, {pf, bytes}}, 9 * bytes, 2 * bytes, out_history_host, [&](uint8_t *d) {
+        const int r = rt_temporal_accumulate_fast_device(ctx, d, d + bytes, pa ? d + 3 * bytes : nullptr, pa ? d + 5 * bytes : nullptr, pa ? d + 7 * bytes : nullptr, width, height,
+                                                         tp, rp, fast_history, d + 9 * bytes, d + 8 * bytes, nullptr);
+        if (r != RT_OK) return r;
+        RT_HIP(ctx, hipMemcpyAsync(out_fast_host, d + 8 * bytes, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));   // (staged waits for the stream)
+        return (int)RT_OK;
     });
 }

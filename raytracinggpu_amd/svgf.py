@@ -7,8 +7,12 @@ upsample = f in 2 .. 4 (off by default: a speed knob that costs quality, DESIGN.
 full-resolution frame with upsample_device, guided by full-resolution planes rendered once per frame:
   filter_at="low"  (pipeline A)  the whole chain at the low resolution, then the filtered frame is upsampled;
   filter_at="full" (pipeline B)  the accumulated history is upsampled (both planes) and svgf_filter_device runs at full resolution.
-History, previous planes, reprojection, motion tables and cut all stay at the low resolution, as without the option."""
-from ._capi import CameraPose, Params, RtError, make_reproject, make_svgf_params, make_temporal_params
+History, previous planes, reprojection, motion tables and cut all stay at the low resolution, as without the option.
+
+rectify = make_rectify_params(...) (off by default) keeps a fast history beside the long one (temporal_accumulate_fast_device) and clamps the accumulated history to it
+in place (history_rectify_device) before the filter, or before the upsample of pipeline B: the chain then follows a light or a shadow that moves (DESIGN.md section
+5.12).  The fast plane lives at the low resolution with the rest of the state."""
+from ._capi import FAST_HISTORY_DEFAULT, CameraPose, Params, RtError, make_reproject, make_svgf_params, make_temporal_params
 
 
 class SvgfSequence:
@@ -17,14 +21,17 @@ class SvgfSequence:
 
     ctx: a Context with its scene uploaded.  svgf = make_svgf_params(...), temporal = make_temporal_params(...) (None: the defaults).  camera: the fixed camera
     (position, fov) the scene was uploaded with, for frames without a pose (None: scene_upload's default).  stream: the stream of every call (None: the context's).
-    upsample, filter_at: see the module; up_k_normal, up_k_position: the upsample's weights (None: UPSAMPLE_DEFAULTS)."""
+    upsample, filter_at: see the module; up_k_normal, up_k_position: the upsample's weights (None: UPSAMPLE_DEFAULTS).  rectify: None, or the RectifyParams of the
+    clamp (the sequence then owns two fast planes more and swaps them); fast_history: the fast history's length limit."""
 
-    def __init__(self, ctx, width, height, svgf=None, temporal=None, camera=None, stream=None, upsample=1, filter_at="low", up_k_normal=None, up_k_position=None):
+    def __init__(self, ctx, width, height, svgf=None, temporal=None, camera=None, stream=None, upsample=1, filter_at="low", up_k_normal=None, up_k_position=None,
+                 rectify=None, fast_history=FAST_HISTORY_DEFAULT):
         self.ctx, self.width, self.height, self.stream = ctx, int(width), int(height), stream
         self.svgf = make_svgf_params() if svgf is None else svgf
         self.temporal = make_temporal_params() if temporal is None else temporal
         self.camera = camera
         self.upsample, self.filter_at, self.up_k = int(upsample), filter_at, (up_k_normal, up_k_position)
+        self.rectify, self.fast_history = rectify, int(fast_history)
         f = self.upsample
         if f < 1 or f > 4 or filter_at not in ("low", "full"):
             raise RtError(-1, f"SvgfSequence: upsample {upsample} must be 1 .. 4 and filter_at {filter_at!r} 'low' or 'full'")
@@ -41,6 +48,8 @@ class SvgfSequence:
             if f > 1:
                 self.full_planes = self._alloc(3 * full)
                 self.between = self._alloc(frame if filter_at == "low" else 2 * full)   # A: the filtered low-resolution frame; B: the upsampled history
+            if rectify is not None:
+                self.fast, self.previous_fast = self._alloc(frame), self._alloc(frame)
         except RtError:
             self.close()
             raise
@@ -69,11 +78,17 @@ class SvgfSequence:
         else:
             c.render_device(params, c._rows_or_whole(params, None), self.color, stream=s)
         c.render_aov_device(params, planes, pose=pose, stream=s)
-        if cut or not self._have_previous:
+        first = cut or not self._have_previous
+        rp = None if first else make_reproject(camera=self.camera, pose=self._previous_pose, motion=motion, no_history_mask=no_history_mask)
+        if self.rectify is None and first:
             c.temporal_accumulate_device(self.color, planes, None, None, W, H, self.accumulated, params=self.temporal, stream=s)
-        else:
-            rp = make_reproject(camera=self.camera, pose=self._previous_pose, motion=motion, no_history_mask=no_history_mask)
+        elif self.rectify is None:
             c.temporal_accumulate_device(self.color, planes, previous, self.history, W, H, self.accumulated, reproject=rp, params=self.temporal, stream=s)
+        else:                                                          # the fast history beside the long one, then the long one clamped to it, in place
+            c.temporal_accumulate_fast_device(self.color, planes, None if first else previous, None if first else self.history, None if first else self.previous_fast, W, H,
+                                              self.accumulated, self.fast, reproject=rp, params=self.temporal, fast_history=self.fast_history, stream=s)
+            c.history_rectify_device(self.accumulated, self.fast, planes, W, H, self.accumulated, params=self.rectify, stream=s)
+            self.fast, self.previous_fast = self.previous_fast, self.fast
         if f > 1:
             c.render_aov_device(full, self.full_planes, pose=pose, stream=s)
         if f > 1 and self.filter_at == "full":                         # B: the history goes up, the filter runs on it at full resolution

@@ -215,9 +215,13 @@ def main():
     for name, pattern in (("aov_emit", r"^(_ZN3rtk15aov_emit_kernel\w*):"), ("aov_close", r"^(_ZN3rtk16aov_close_kernel\w*):"),
                           ("denoise_pass", r"^(_ZN3rtk19denoise_pass_kernelILb0E\w*):"), ("denoise_var_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_5DnVarEE\w*):"),
                           ("svgf_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_6DnSvgfEE\w*):"),
-                          ("temporal_accumulate", r"^(_ZN3rtk26temporal_accumulate_kernel\w*):"),
+                          ("temporal_accumulate", r"^(_ZN3rtk26temporal_accumulate_kernelILb0E\w*):"),
                           # the guided upsample, one and two planes (rt_upsample.hip.h)
-                          ("upsample_1", r"^(_ZN3rtk15upsample_kernelILi1E\w*):"), ("upsample_2", r"^(_ZN3rtk15upsample_kernelILi2E\w*):")):
+                          ("upsample_1", r"^(_ZN3rtk15upsample_kernelILi1E\w*):"), ("upsample_2", r"^(_ZN3rtk15upsample_kernelILi2E\w*):"),
+                          # the accumulation that also keeps the fast history, and the clamp to it for each radius (rt_temporal.hip.h, rt_rectify.hip.h)
+                          ("temporal_accumulate_fast", r"^(_ZN3rtk26temporal_accumulate_kernelILb1E\w*):"),
+                          ("history_rectify_1", r"^(_ZN3rtk22history_rectify_kernelILi1E\w*):"), ("history_rectify_2", r"^(_ZN3rtk22history_rectify_kernelILi2E\w*):"),
+                          ("history_rectify_3", r"^(_ZN3rtk22history_rectify_kernelILi3E\w*):")):
         mm = re.search(pattern, asm, re.M)
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
@@ -237,6 +241,8 @@ def main():
     print("static_counts: SVGF pass (pre-filter and feedback switches): %d / %d / %d" % tuple(res["svgf_pass"]["whole_kernel"][c] for c in ("valu", "lds", "vmem")))
     print("static_counts: guided upsample, 1 plane / 2 planes (valu / lds / vmem): %d / %d / %d, %d / %d / %d" % tuple(
         res[k]["whole_kernel"][c] for k in ("upsample_1", "upsample_2") for c in ("valu", "lds", "vmem")))
+    print("static_counts: accumulation with the fast history: %d / %d / %d, rectify radius 1 / 2 / 3: %d / %d / %d, %d / %d / %d, %d / %d / %d" % tuple(
+        res[k]["whole_kernel"][c] for k in ("temporal_accumulate_fast", "history_rectify_1", "history_rectify_2", "history_rectify_3") for c in ("valu", "lds", "vmem")))
     t = res["wf_travq"]
     print("static_counts: wf_travq per step: BOX %d valu (weight %d) %d salu + leaf pushes %d / %d | TRI %d (%d) %d + %.0f per t-division block | round %d (%d) %d | fetch %d | retire %d | head+dispatch %d" % (
         t["box"]["valu"], t["box"]["valu_weight"], t["box"]["salu"], t["lpush"]["valu"], t["lpush2"]["valu"], t["tri"]["valu"], t["tri"]["valu_weight"], t["tri"]["salu"], t["tdiv"]["valu"],
