@@ -34,7 +34,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_svgf_filter_device", "rt_svgf_filter",
            "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate",
            "rt_upsample_device", "rt_upsample",
-           "rt_temporal_accumulate_fast_device", "rt_temporal_accumulate_fast", "rt_history_rectify_device", "rt_history_rectify"]
+           "rt_temporal_accumulate_fast_device", "rt_temporal_accumulate_fast", "rt_history_rectify_device", "rt_history_rectify",
+           "rt_dead_channel_counts"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -345,6 +346,7 @@ def load():
     L.rt_tonemap_device.argtypes = [vp, vp, C.c_int64, vp, vp]
     L.rt_render_rgb8.argtypes = [vp, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     L.rt_count_work.argtypes = [vp, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(Work)]
+    L.rt_dead_channel_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_synchronize.argtypes = [vp]
     L.rt_ctx_selfcheck.argtypes = [vp]
     L.rt_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -705,6 +707,9 @@ class Context:
         if not detail:
             return out
         out.update(box_literal=int(w.box_literal), tri_literal=int(w.tri_literal))
+        dc = (C.c_uint64 * 4)()
+        self._check(self._L.rt_dead_channel_counts(self._h, dc))
+        out["dead_channels"] = dict(zip(("trav_continuation", "trav_shadow", "elided", "unsure"), (int(v) for v in dc)))   # rt_dead_channel_counts
         out["steps"] = dict(zip(("iterations", "refill_passes", "refill_rounds", "fetches", "tri_steps", "box_steps", "literal_box_fallbacks", "serial_drains",
                                  "tdiv_blocks", "leaf_push_blocks", "leaf_push2_blocks", "anyhit_stop_steps"),
                                 (int(v) for v in w.steps)))

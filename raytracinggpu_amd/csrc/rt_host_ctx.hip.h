@@ -68,6 +68,8 @@ struct Knobs {
     int quad_sel = 1;          // RT_TRAVQ_QSEL=0: the quads of the 4-wide step take every other level of the tree (A/B; default: the four nodes a surface-area DP picks, rt_qnodes.hip.h)
     int anyhit = 1;            // RT_TRAVQ_ANYHIT=0: shadow rays are traced to the end like every other ray (A/B, cross-check; default: the fixed-point traversal kernels stop a shadow ray at the
                                // first accepted triangle that certainly shades, rt_wavefront.hip.h wf_anyhit_bound).  Bit-exact either way
+    int dead_channels = 1;     // RT_DEAD_CHANNELS=0: a diffuse segment whose three colour channels are dead (a zero albedo component earlier on the path in each) still traces its
+                               // shadow ray (A/B, cross-check; default: with any-hit on it does not, rt_wavefront.hip.h wf_dead_channels).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
     int qw_count = 0;          // RT_TRAVQ_QW_COUNT=1: rt_count_work runs the 4-wide kernel's counting instantiation (its own step counters; the box / node counts then describe
                                // THAT kernel, not the reference's traversal)
@@ -118,6 +120,7 @@ static Knobs read_knobs() {
     if (geti("RT_AUTO_LOCKSTEP", v)) k.auto_lockstep = v != 0;
     if (geti("RT_TRAVQ_QSEL", v)) k.quad_sel = v != 0;
     if (geti("RT_TRAVQ_ANYHIT", v)) k.anyhit = v != 0;
+    if (geti("RT_DEAD_CHANNELS", v)) k.dead_channels = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;
     { const char *e = getenv("RT_CHUNK_MPX"); if (e && *e) { const double d = atof(e); if (d >= 0 && d < 1e4) k.chunk_mpx = d; } }
@@ -195,6 +198,8 @@ struct rt_ctx {
     DevBuf node_lo{bufs}, node_hi{bufs}, nodes2{bufs}, nodesq{bufs}, nodesb{bufs}, q2thr{bufs}, tri{bufs}, verts{bufs}, tidx{bufs}, scratch_rgba{bufs}, scratch_rgb8{bufs}, work{bufs}, queue{bufs};
     int n_cus = 0;
     DevBuf wfM{bufs}, wfT{bufs}, wfLS{bufs}, wfSID{bufs}, wfSamp{bufs};   // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
+    DevBuf wfDCH{bufs};                                             // ... the dead-channel byte of each path (wf_dead_channels)
+    unsigned long long dead_counts[4] = {};                          // of the last rt_count_work: rt_dead_channel_counts
     DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
     DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum

@@ -498,7 +498,7 @@ int size_wavefront(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool &qr_grown) 
 #endif
     if ((rc = ensure(ctx, ctx->wfM, 2 * np * 8)) != RT_OK ||
         (rc = ensure(ctx, ctx->wfT, (samples ? w.px : 1) * 16)) != RT_OK || (rc = ensure(ctx, ctx->wfSamp, (samples ? np : 1) * 16)) != RT_OK ||
-        (rc = ensure(ctx, ctx->wfSID, np * nseg)) != RT_OK || (rc = ensure(ctx, ctx->wfLS, np * 4 * nseg)) != RT_OK)
+        (rc = ensure(ctx, ctx->wfSID, np * nseg)) != RT_OK || (rc = ensure(ctx, ctx->wfDCH, np)) != RT_OK || (rc = ensure(ctx, ctx->wfLS, np * 4 * nseg)) != RT_OK)
         return rc;
     if (ctx->tex_mask != 0 && (rc = ensure(ctx, ctx->wfALB, np * 16 * nseg)) != RT_OK) return rc;   // a textured mesh: the per-segment albedo store of wf_advance_tex
     const size_t had = ctx->wfQR.bytes;
@@ -683,10 +683,12 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
         st.samp_out = fr.spp > 1 ? static_cast<float4 *>(ctx->wfSamp.p) + pt.base : nullptr;
         st.LS = static_cast<float *>(ctx->wfLS.p) + pt.base * (size_t)c.nseg;   // LS[d * n_paths + i] inside the part's block
         st.SID = static_cast<unsigned char *>(ctx->wfSID.p) + pt.base * (size_t)c.nseg;
+        st.DCH = static_cast<unsigned char *>(ctx->wfDCH.p) + pt.base;
         st.batch = c.batch ? static_cast<rtk::BatchFrame *>(ctx->batch_dev.p) + j * rtk::kMaxBatch : nullptr;
         st.n_batch = c.batch ? pt.batch_n : 0;
         w.pv[j].anim = c.anim ? static_cast<rtk::AnimFrame *>(ctx->anim_dev.p) + j * rtk::kMaxBatch : nullptr;
         st.anyhit = (kn.anyhit && (c.work_dev == nullptr || t.qw)) ? 1 : 0;   // a run that counts the REFERENCE's work (the float-pair counting instantiation) traces every shadow ray to the end
+        st.deadch = (st.anyhit && kn.dead_channels) ? 1 : 0;
     }
     ctx->stats.lds_bytes = (int)t.lds; ctx->stats.block_threads = t.tb; ctx->stats.grid_blocks = (int)w.pv[0].tblocks; ctx->stats.parts = parts; ctx->stats.travq_mode = t.travq_mode;
     if ((rc = start_chains(ctx, c, w, qr_grown, own0)) != RT_OK) return rc;

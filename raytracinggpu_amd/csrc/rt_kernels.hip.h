@@ -112,7 +112,7 @@ __device__ __forceinline__ size_t out_index(const Frame &fr, int lrow, int px) {
 }
 
 // per-lane traversal work counters (STATS instantiation only; SURVEY 8d accounting)
-struct Work { uint32_t box = 0, nodes = 0, tris = 0, rays = 0, lit_box = 0, lit_tri = 0; };   // lit_*: tests decided by the literal divisions (filter undecided)
+struct Work { uint32_t box = 0, nodes = 0, tris = 0, rays = 0, lit_box = 0, lit_tri = 0, trav_y = 0, trav_x = 0, dead_elided = 0, dead_unsure = 0; };   // lit_*: tests decided by the literal divisions (filter undecided)
 
 struct f3 { float x, y, z; };
 __device__ __forceinline__ f3 mk(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }

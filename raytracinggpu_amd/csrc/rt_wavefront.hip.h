@@ -78,6 +78,41 @@ __device__ __forceinline__ float wf_anyhit_bound(f3 Pa, float nl) {
     return (nl > 1e-12f && nl < 1e30f) ? b : -__builtin_inff();      // (above 1e-12 no square that matters to the budget is denormal; a finite nl is below 1.9e19 anyway: beyond it |L - Pa|^2 is +inf)
 }
 
+// DEAD CHANNELS of a path.  The fold is, per channel, ans_k = fl(fl(fl(l_k alb_k) / pi) + fl(alb_k ans_{k+1})) (fold_segment), back to front.  A channel c is DEAD from the
+// first diffuse segment m whose albedo in c is +0 (the bits: a -0, a denormal or a NaN is not): whatever later segments hand up, segment m passes on
+// fl(fl(l_m (+0)) / pi) + fl((+0) x) = +0 + (+-0) = +0 -- if l_m has a clear sign bit and is finite, and x = ans_{m+1}[c] is finite.  A diffuse segment j whose three channels
+// are dead (its own albedo counted) has a shadow ray that decides only between l_j = lvis and l_j = +0, and neither value can reach the pixel: with any-hit on the ray is
+// not traced (x_moot below, the rule of the direct term that is +0 either way with a second reason) and LS keeps lvis.  The pixel is the same 96 bits if, in the chain the
+// reference folds (W: every elided l_j is lvis_j or +0) and in the chain the kernel folds (A: every elided l_j = lvis_j), each dead channel arrives at its segment m as a
+// finite x.  The argument:
+//   (1) what is known when the ray is emitted is GUARDED there: a segment counts (kills channels, keeps the mask) only if its lvis and its three albedo components have a
+//       clear sign bit and are finite -- as unsigned integers, below 0x7f800000, which rules out negative numbers, -0, inf and every NaN at once.  A segment that fails
+//       clears the mask (wf_dead_channels): kills before it are forgotten, so between a kill m and a later elided segment j every operand is non-negative and finite.
+//       (An albedo above 1 is admitted: it can only make the chain grow, which (2) covers.)  A channel killed AT j needs nothing else: x is the same in both chains.
+//   (2) with non-negative operands every rounding is monotone, so 0 <= W <= A intermediate by intermediate.  If every ans of chain A is below 2^126, its products l alb
+//       (at most pi (1 + 2^-22) times the quotient, which the sum bounds) are below 2^128: nothing in A overflows, so nothing in W does, every x is finite and non-negative
+//       in both, and the dead channels are +0 in both.  Below m the two chains fold the same numbers.
+// Outside the guarantee, because it is not known at emission: a path with an elided ray in which a LATER segment has a negative, -0, inf or NaN operand, or whose chain A
+// reaches 2^126 in some channel (the reference's pixel is then of that magnitude, inf or NaN as well).  Such a path is traced no differently; the fold of the counting
+// instantiation recognises it (wf_fold_bounded fails on a path whose state byte says a ray was elided) and counts it (rt_dead_channel_counts: unsure), conservatively: it
+// checks every diffuse segment of the path, also those before the first kill.  tests/test_dead_channels.py restates guard, fold and check in numpy binary32.
+// State: one byte per path, WfState::DCH[i] (bits 0..2: the dead channels, bit 3: a ray was elided), zeroed by wf_advance<FIRST>, read by every diffuse segment and written
+// when it changes (at most 4 times per path): 1 B written per path and chain, <= 1 B read per path and launch.  (Bit 21 of the Y slot's flag word is NOT free for it: wf_travq
+// tests PQ_ANYHIT on every record it fetches, continuation rays included, and would take the nearest sphere's t for an any-hit bound.)
+constexpr unsigned kFoldFinite = 0x7f800000u;               // bits of +inf: a float whose bits are below it, as an unsigned integer, is finite with a clear sign bit
+constexpr unsigned kFoldBound = 0x7e800000u;                // bits of 2^126
+__device__ __forceinline__ unsigned wf_umax3(f3 v) { return max(max(__float_as_uint(v.x), __float_as_uint(v.y)), __float_as_uint(v.z)); }
+// the dead channels after a diffuse segment with albedo alb and direct term lvis, given those before it
+__device__ __forceinline__ int wf_dead_channels(int dead, f3 alb, float lvis) {
+    const bool good = wf_umax3(alb) < kFoldFinite && __float_as_uint(lvis) < kFoldFinite;
+    const int kill = (__float_as_uint(alb.x) == 0u ? 1 : 0) | (__float_as_uint(alb.y) == 0u ? 2 : 0) | (__float_as_uint(alb.z) == 0u ? 4 : 0);
+    return good ? (dead | kill) : 0;
+}
+// (2) for one folded segment: its operands and its result
+__device__ __forceinline__ bool wf_fold_bounded(f3 ans, float l, f3 alb) {
+    return __float_as_uint(l) < kFoldFinite && wf_umax3(alb) < kFoldFinite && wf_umax3(ans) < kFoldBound;
+}
+
 // A BATCH of frames in one launch chain (rt_render_device_batch): the items of a chain are (frame f, pixel slot) pairs -- the machinery that traces several samples of a pixel
 // as parallel items (n_paths = n_px x items per pixel), with a camera, a seed and an output buffer PER FRAME instead of per-sample colours to reduce.  A rank that renders a
 // small share of a frame (1/8 of 1920x1080 = 0.26 Mpixel) fills the chip with K frames' worth of paths per launch instead of K chains on K streams.  Only wf_advance reads it.
@@ -154,6 +189,8 @@ struct WfState {
     // round trip brings flag and record
     float4 *QR;               // [2 slots] record of slot q: QR[2q] = (O.xyz, u.x), QR[2q+1] = (u.y, u.z, bits(W0), W1).  Y slot (ray r < n_paths): W0 = the path's
                               // flag word (PF_* | PQ_*; 0 = no path), W1 = t of the Y ray's nearest sphere; X slot: W0 = PQ_TRAV | depth | chain number (| PQ_ANYHIT: W1 = the any-hit bound), written only when the ray needs traversal
+    unsigned char *DCH;       // [n_paths] dead channels of path i (bits 0..2) and whether one of its shadow rays was elided for them (bit 3); wf_advance<FIRST> zeroes it (deadch only)
+    int deadch;               // any-hit is on and so is the dead-channel rule: a diffuse segment whose three channels are dead does not trace its shadow ray (wf_dead_channels)
 };
 
 // n / d for 0 <= n < 2^32 with m = floor(2^32 / d) from the host: the estimate mulhi(n, m) is the quotient or one below it
@@ -231,11 +268,17 @@ template <bool STATS>
 __device__ __forceinline__ void wf_flush_work(const Frame &fr, Work &wk) {
     if (STATS) {
         const uint32_t b = wave_sum(wk.box), n = wave_sum(wk.nodes), t = wave_sum(wk.tris), lb = wave_sum(wk.lit_box), lt = wave_sum(wk.lit_tri);
+        // rays handed to the traversal (continuation, shadow), shadow rays the dead-channel rule elided, paths outside its guarantee: rt_dead_channel_counts
+        const uint32_t ty = wave_sum(wk.trav_y), tx = wave_sum(wk.trav_x), de = wave_sum(wk.dead_elided), du = wave_sum(wk.dead_unsure);
         if ((threadIdx.x & 63) == 0) {
             atomicAdd(&fr.work[1], (unsigned long long)b);
             atomicAdd(&fr.work[2], (unsigned long long)n); atomicAdd(&fr.work[3], (unsigned long long)t);
             if (lb) atomicAdd(&fr.work[5], (unsigned long long)lb);
             if (lt) atomicAdd(&fr.work[6], (unsigned long long)lt);
+            if (ty) atomicAdd(&fr.work[20], (unsigned long long)ty);
+            if (tx) atomicAdd(&fr.work[21], (unsigned long long)tx);
+            if (de) atomicAdd(&fr.work[22], (unsigned long long)de);
+            if (du) atomicAdd(&fr.work[23], (unsigned long long)du);
         }
     }
 }
@@ -642,7 +685,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     int d = 0, nrays = 0;
     bool emitY = false, emitX = false, finished = false;
     float x_bound = -__builtin_inff();                                // any-hit bound of the shadow ray (wf_anyhit_bound)
-    bool x_moot = false;                                              // the shadow ray's answer cannot reach the pixel (direct term +0 either way)
+    bool x_moot = false;                                              // the shadow ray's answer cannot reach the pixel (direct term +0 either way, or every channel dead)
     f3 Oy = mk(0, 0, 0), uy = mk(0, 0, 1), Ox = mk(0, 0, 0), ux = mk(0, 0, 1);
     int px, lrow; bool valid;
     int s_rel = 0;
@@ -672,6 +715,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
 
     if (FIRST) {
         if (!valid) { st.QR[2 * (size_t)qy + 1] = kDead; return; }       // (the X slot of a pixel outside the frame is never written: zero from the layout's memset)
+        if (st.deadch) st.DCH[i] = 0;                                  // no channel of the new path is dead
         if (fr.segs <= 0) {
             finished = true;                                          // optimized.cu convention with num_bounce 0: black
         } else {
@@ -756,12 +800,24 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     emitX = true;
                     x_moot = st.anyhit && __float_as_uint(lvis) == 0u;
                     sid = win;
+                    f3 alb = mk(m.ar, m.ag, m.ab);                    // the albedo the fold will use
                     if (TEX && tri_win >= 0 && ((ts.mask >> win) & 1)) {   // a textured mesh: this segment's albedo, evaluated once, for the fold
                         if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
                         float2 uv;
-                        const f3 alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
+                        alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
                         ts.ALB[(size_t)d * st.n_paths + i] = make_float4(alb.x, alb.y, alb.z, 0.f);
                         sid = kSidTextured;
+                    }
+                    // Every channel dead, this segment's albedo counted: lvis or +0, the pixel is the same (wf_dead_channels) -- moot for a second reason
+                    if (st.deadch) {
+                        const int was = st.DCH[i];
+                        int now = (was & 8) | wf_dead_channels(was & 7, alb, lvis);
+                        if ((now & 7) == 7 && !x_moot) {
+                            x_moot = true;
+                            now |= 8;
+                            if (STATS) wk.dead_elided++;
+                        }
+                        if (now != was) st.DCH[i] = (unsigned char)now;
                     }
                     ADV_MARK("diffuse_end");
                     if (d + 1 < fr.segs) {                            // the bounce ray: needs the sample's key and N only
@@ -787,6 +843,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     if (finished) {   // nothing in flight: fold the path back to front, accumulate the sample (cpu:711)
         ADV_MARK("fold_begin");
         f3 ans = mk(0, 0, 0);
+        bool fold_sure = true;                                        // (counting instantiation) every folded segment passed wf_fold_bounded
         const int nseg = d < fr.segs ? d : fr.segs;
         for (int k = nseg - 1; k >= 0; --k) {
             const int sid = st.SID[(size_t)k * st.n_paths + i];
@@ -799,9 +856,12 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     const Material m = material_of(sc, sid);
                     alb = mk(m.ar, m.ag, m.ab);
                 }
-                ans = fold_segment(ans, st.LS[(size_t)k * st.n_paths + i], alb);
+                const float l = st.LS[(size_t)k * st.n_paths + i];
+                ans = fold_segment(ans, l, alb);
+                if (STATS && !wf_fold_bounded(ans, l, alb)) fold_sure = false;
             }
         }
+        if (STATS && !fold_sure && st.deadch && (st.DCH[i] & 8)) wk.dead_unsure++;   // a ray of this path was elided and its chain leaves what the elision was argued for
         if (st.samp_out != nullptr) {                                 // more than one sample per pixel: path_reduce sums in sample order
             st.samp_out[i] = make_float4(ans.x, ans.y, ans.z, (float)nrays);
         } else {                                                      // one sample: T = 0 + ans, out = T / n (cpu:711-713 + the framebuffer store)
@@ -832,6 +892,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         // ... so with any-hit on that ray is not traced through the mesh at all (intersect_all does: a run that counts the reference's work has any-hit off)
         if (!x_moot && (!(flags & PQ_XSPHERE) || !st.anyhit) && wf_root_test<STATS>(sc, st, rx, Ox, ux, wk)) {   // only then does anybody read the record: the traversal, and this kernel if the mesh is hit
             flags |= PF_MESHX;
+            if (STATS) wk.trav_x++;
             st.QR[2 * (size_t)qx] = make_float4(Ox.x, Ox.y, Ox.z, ux.x);
             st.QR[2 * (size_t)qx + 1] = make_float4(ux.y, ux.z, __int_as_float((int)((unsigned)(PQ_TRAV | (st.anyhit ? PQ_ANYHIT : 0) | (d << PF_DEPTH_SHIFT)) | (unsigned)st.nonce << PQ_NONCE_SHIFT)), x_bound);
         }
@@ -839,7 +900,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     if (emitY) {
         t_sph = h.t;
         flags |= PF_HASY | (((h.obj + 1) & 31) << PQ_WIN_SHIFT);
-        if (wf_root_test<STATS>(sc, st, i, Oy, uy, wk)) flags |= PF_MESHY | PQ_TRAV;
+        if (wf_root_test<STATS>(sc, st, i, Oy, uy, wk)) { flags |= PF_MESHY | PQ_TRAV; if (STATS) wk.trav_y++; }
     }
     st.QR[2 * (size_t)qy] = make_float4(Oy.x, Oy.y, Oy.z, uy.x);    // whole sectors also when no continuation ray leaves (then nobody reads this half)
     st.QR[2 * (size_t)qy + 1] = make_float4(emitY ? uy.y : 0.f, emitY ? uy.z : 0.f, __int_as_float(flags), t_sph);   // the path's state travels with its Y slot
