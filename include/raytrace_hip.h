@@ -290,8 +290,9 @@ typedef struct rt_work {
 int rt_count_work(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, rt_work *out);
 /* Of the last rt_count_work of the default pipeline: continuation rays and shadow rays handed to the mesh traversal (they passed the root box), shadow rays not
  * traced because every colour channel of their path was dead (a diffuse surface with a zero albedo component in each channel earlier on the path: neither answer can
- * change the pixel; RT_DEAD_CHANNELS=0 traces them), and paths with such a ray whose fold left the range the rule's exactness is argued for (0 in
- * any scene with finite non-negative albedos and colours below 2^126).  The rule needs any-hit: the last two are 0 unless RT_TRAVQ_QW_COUNT=1. */
+ * change the pixel; RT_DEAD_CHANNELS=0 traces them; only surfaces with albedo components in [0, 1] and a direct term below 2^96 count), and paths with
+ * such a ray whose fold met a negative or non-finite operand or a colour of 2^126 and more (a statistic: their pixels are the reference's all the same; 0 in any scene
+ * with finite non-negative albedos and colours below 2^126).  The rule needs any-hit: the last two are 0 unless RT_TRAVQ_QW_COUNT=1. */
 int rt_dead_channel_counts(rt_ctx *ctx, uint64_t out[4]);
 
 int rt_synchronize(rt_ctx *ctx);

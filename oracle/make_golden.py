@@ -226,6 +226,42 @@ def make_obj():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+FUZZ_SEEDS, FUZZ_W, FUZZ_H = range(8), 32, 24
+
+
+def fuzz_scene(family, seed):
+    """scene(family, seed) of tests/scene_fuzz.py as the fixture holds it: 32 x 24, one sample, the family's own num_bounce, and the reference's own eps
+    (a literal 1e-3 in Scene::getColor, cpu:575, 582, 610: the scenes of `light_edge` that ask for 0 or 1e-6 are held to the reference at 1e-3)"""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from tests import scene_fuzz
+    return scene_fuzz.resized(scene_fuzz.scene(family, seed), FUZZ_W, FUZZ_H, spp=1, eps=1e-3)
+
+
+def make_fuzz():
+    """tests/golden/ref_fuzz.npz alone (`python oracle/make_golden.py fuzz`): seeds 0 to 7 of every family of tests/scene_fuzz.py through the reference's own
+    Sphere, TriangleMesh, Scene and Scene::getColor (`ref_harness fuzz`, one process per scene: single thread, mt19937(0)); the packed descriptions and the frames."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from tests import scene_fuzz
+    keys = [(f, k) for f in scene_fuzz.FAMILIES for k in FUZZ_SEEDS]
+    packed = [scene_fuzz.pack(fuzz_scene(f, k)) for f, k in keys]
+    tmp = tempfile.mkdtemp(prefix="rt_golden_")
+    try:
+        src = os.path.join(tmp, "scenes.f32")
+        np.concatenate([np.array([len(packed)], np.float32)] + packed).astype("<f4").tofile(src)
+        out = {}
+        for i, (f, k) in enumerate(keys):
+            dst = os.path.join(tmp, "frame.f32")
+            run([HARNESS, "fuzz", src, str(i), dst], tmp, {"OMP_NUM_THREADS": "1"})
+            out[f"{f}_{k}_desc"] = packed[i]
+            out[f"{f}_{k}_frame"] = f32(dst).reshape(FUZZ_H, FUZZ_W, 3)
+        np.savez_compressed(os.path.join(GOLD, "ref_fuzz.npz"), **out)
+        print("fuzz", len(keys), "scenes", os.path.getsize(os.path.join(GOLD, "ref_fuzz.npz")), "bytes")
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     if not (os.path.exists(CPU) and os.path.exists(HARNESS)):
         raise SystemExit("build the reference first: make -C oracle ref")
@@ -234,6 +270,8 @@ def main():
         return make_materials()
     if len(sys.argv) > 1 and sys.argv[1] == "obj":
         return make_obj()
+    if len(sys.argv) > 1 and sys.argv[1] == "fuzz":
+        return make_fuzz()
     tmp = tempfile.mkdtemp(prefix="rt_golden_")
     try:
         with_cat = os.path.join(tmp, "with_cat"); os.makedirs(with_cat)
@@ -308,6 +346,7 @@ def main():
         print("stat done")
         make_materials()
         make_obj()
+        make_fuzz()
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     for fn in sorted(os.listdir(GOLD)):

@@ -21,6 +21,15 @@ class Counters(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class Census(C.Structure):
+    """or_census: how often getColor / intersect_all took each branch over a frame"""
+    _fields_ = [(k, C.c_uint64) for k in ("camera_miss", "mirror", "out2in", "in2out", "total_reflection", "diffuse", "shadow_miss", "shaded", "lit",
+                                          "lit_mx_zero", "lit_l_bad", "equal_t", "last_segment")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class Params(C.Structure):
     _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("num_rays", C.c_int32), ("num_bounce", C.c_int32),
                 ("row_begin", C.c_int32), ("row_end", C.c_int32),
@@ -82,6 +91,7 @@ def lib():
     L.or_uniform.argtypes = [C.c_uint32] * 5
     L.or_uniform.restype = C.c_float
     L.or_render.argtypes = [vp, C.POINTER(Params), fp, C.POINTER(C.c_uint8), C.POINTER(Counters)]
+    L.or_render_census.argtypes = [vp, C.POINTER(Params), fp, C.POINTER(C.c_uint8), C.POINTER(Counters), C.POINTER(Census)]
     L.or_tonemap.argtypes = [fp, C.c_int, C.POINTER(C.c_uint8)]
     L.or_max_threads.restype = C.c_int
     L.or_camera_basis.argtypes = [C.c_float, C.c_float, fp, fp, fp]
@@ -259,8 +269,9 @@ class Scene:
 
     def render(self, W, H, num_rays=1, num_bounce=0, rows=None, sigma=0.0, eps=1e-3, tri_tmin=1e-4,
                fov=None, cam=(0, 0, 55), seed=123456, threads=0, rng_mode=0, stride=1, want_rgb8=True,
-               tile_rows=0, tile_step=0, pose=None):
-        """pose = (yaw, pitch): realtime_render.cu's camera and per-sample averaging."""
+               tile_rows=0, tile_step=0, pose=None, census=False):
+        """pose = (yaw, pitch): realtime_render.cu's camera and per-sample averaging.
+        census=True: the third result is the branch census of the frame (Census.as_dict()) instead of the work counters."""
         p = Params()
         if pose is not None:
             p.cam_mode, p.yaw, p.pitch = 1, pose[0], pose[1]
@@ -280,12 +291,12 @@ class Scene:
         nc = (W + st - 1) // st
         rgba = np.zeros((nr, nc, 4), np.float32)
         rgb8 = np.zeros((nr, nc, 3), np.uint8) if want_rgb8 else None
-        cnt = Counters()
-        rc = lib().or_render(self.h, C.byref(p), rgba.ctypes.data_as(C.POINTER(C.c_float)),
-                             rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgb8 else None, C.byref(cnt))
+        cnt, cen = Counters(), Census()
+        rc = lib().or_render_census(self.h, C.byref(p), rgba.ctypes.data_as(C.POINTER(C.c_float)),
+                                    rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgb8 else None, C.byref(cnt), C.byref(cen) if census else None)
         if rc != 0:
             raise ValueError("or_render: bad parameters")
-        return rgba, rgb8, cnt.as_dict()
+        return rgba, rgb8, (cen.as_dict() if census else cnt.as_dict())
 
 
 def camera_basis(yaw, pitch):

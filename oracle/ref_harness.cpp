@@ -279,8 +279,80 @@ static int cmd_stat(int W, int H, int num_rays, int num_bounce, int stride, cons
     return 0;
 }
 
+/* Generated scenes (tests/scene_fuzz.py pack(), written by make_golden.py `fuzz`): a stream of float32 -- the number of scenes, then per scene
+ * [W H spp num_bounce eps tri_tmin cam(3) light(3) intensity n_spheres mesh_slot], n_spheres rows of [centre(3) radius albedo(3) mirror n_in n_out] and, where mesh_slot >= 0,
+ * [albedo(3) mirror n_in n_out nv nt] vertices(3 nv) triangles(3 nt).  Each scene is built from the reference's own Sphere, TriangleMesh and Scene (the mesh at position
+ * mesh_slot of Scene::objects) and Scene::getColor is dumped per pixel as cmd_render does: single thread, the mt19937(0) stream.  One run renders one scene, so that
+ * every frame starts at the head of that stream (the generator is a thread_local static of the reference's uniform()).  eps and tri_tmin are the reference's literals
+ * (1e-3, 1e-4f): a scene that asks for others is refused. */
+static std::vector<float> fuzz_frame(const float *&p) {
+    const int W = (int)p[0], H = (int)p[1], spp = (int)p[2], num_bounce = (int)p[3];
+    if (p[4] != 1e-3f || p[5] != 1e-4f) { fprintf(stderr, "fuzz: eps / tri_tmin are not the reference's\n"); exit(2); }
+    Vector C(p[6], p[7], p[8]);
+    Scene s;
+    s.L = Vector(p[9], p[10], p[11]);
+    s.intensity = p[12];
+    const int n_spheres = (int)p[13], mesh_slot = (int)p[14];
+    p += 15;
+    const float *sph = p;
+    p += 10 * n_spheres;
+    TriangleMesh *mesh = nullptr;
+    if (mesh_slot >= 0) {
+        mesh = new TriangleMesh();
+        mesh->albedo = Vector(p[0], p[1], p[2]);
+        mesh->mirror = p[3] != 0; mesh->in_refraction_index = p[4]; mesh->out_refraction_index = p[5];
+        const int nv = (int)p[6], nt = (int)p[7];
+        p += 8;
+        for (int k = 0; k < nv; k++, p += 3) mesh->vertices.push_back(Vector(p[0], p[1], p[2]));
+        for (int k = 0; k < nt; k++, p += 3) mesh->indices.push_back(TriangleIndices((int)p[0], (int)p[1], (int)p[2]));
+        mesh->buildBVH(&(mesh->bvh), 0, mesh->indices.size());
+    }
+    for (int k = 0, pos = 0; k < n_spheres || (mesh && pos <= mesh_slot); pos++) {
+        if (mesh && pos == mesh_slot) { s.addObject(mesh); continue; }
+        const float *q = sph + 10 * k++;
+        s.addObject(new Sphere(Vector(q[0], q[1], q[2]), q[3], Vector(q[4], q[5], q[6]), q[7] != 0, q[8], q[9]));
+    }
+    float alpha = PI / 3;
+    float z = -W / (2 * tan(alpha / 2));
+    std::vector<float> col;
+    for (int i = 0; i < H; i++) {
+        for (int j = 0; j < W; j++) {
+            unsigned int seed = omp_get_thread_num();
+            Vector u_center((float)j - (float)W / 2 + 0.5, (float)H / 2 - i - 0.5, z);
+            Vector color_total(0, 0, 0);
+            for (int t = 0; t < spp; t++) {
+                float sigma = 0;
+                float r1 = uniform(seed);
+                float r2 = uniform(seed);
+                Vector u = u_center + Vector(sigma * sqrt(-2 * log(r1)) * cos(2 * PI * r2), sigma * sqrt(-2 * log(r1)) * sin(2 * PI * r2), 0);
+                u.normalize();
+                Vector color = s.getColor(Ray(C, u), num_bounce);
+                color_total = color_total + color;
+            }
+            Vector color_avg = color_total / spp;
+            for (int k = 0; k < 3; k++) col.push_back(color_avg[k]);
+        }
+    }
+    return col;
+}
+
+/* fuzz <file> <index> <out>: the frame of scene <index> of the file */
+static int cmd_fuzz(const std::string &in, int index, const std::string &out) {
+    std::vector<float> data = slurp(in);
+    const float *p = data.data() + 1;
+    if (data.empty() || index < 0 || index >= (int)data[0]) { fprintf(stderr, "fuzz: no such scene\n"); return 2; }
+    for (int k = 0; k < index; k++) {                    /* skip the scenes before it */
+        const int n_spheres = (int)p[13], mesh_slot = (int)p[14];
+        p += 15 + 10 * n_spheres;
+        if (mesh_slot >= 0) p += 8 + 3 * (int)p[6] + 3 * (int)p[7];
+    }
+    std::vector<float> col = fuzz_frame(p);
+    dump(out, col.data(), col.size() * 4);
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) { fprintf(stderr, "usage: ref_harness mesh|kat|render|stat ...\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: ref_harness mesh|kat|render|stat|fuzz ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "mesh" && argc == 3) return cmd_mesh(argv[2]);
     if (cmd == "kat" && argc == 3) return cmd_kat(argv[2]);
@@ -288,6 +360,7 @@ int main(int argc, char **argv) {
         return cmd_render(argv[2], atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), atoi(argv[7]), argv[8]);
     if (cmd == "stat" && argc == 8)
         return cmd_stat(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), argv[7]);
+    if (cmd == "fuzz" && argc == 5) return cmd_fuzz(argv[2], atoi(argv[3]), argv[4]);
     fprintf(stderr, "bad arguments\n");
     return 2;
 }

@@ -586,7 +586,14 @@ int or_scene_add_mesh(or_scene *s, or_mesh *m) {
 void or_scene_set_light(or_scene *s, const float L[3], float intensity) { s->L = V(L[0], L[1], L[2]); s->intensity = intensity; }
 
 /* cpu:545-564 */
-static int intersect_all(const or_scene *s, const ray *r, float tri_tmin, vec *P, vec *N, int *objectId, or_counters *cnt) {
+/* the branch census (or_census): written beside the arithmetic, never read by it; NULL = not counted */
+#define CEN(c, field) do { if (c) (c)->field++; } while (0)
+static inline void cen_add(or_census *c, const or_census *d) {
+    uint64_t *a = (uint64_t *)c; const uint64_t *b = (const uint64_t *)d;
+    for (size_t k = 0; k < sizeof(or_census) / sizeof(uint64_t); k++) a[k] += b[k];
+}
+
+static int intersect_all(const or_scene *s, const ray *r, float tri_tmin, vec *P, vec *N, int *objectId, or_counters *cnt, or_census *cen) {
     float t_min = (float)OR_INF;
     int id_min = -1;
     vec N_min = V(0, 0, 0);
@@ -597,6 +604,7 @@ static int intersect_all(const or_scene *s, const ray *r, float tri_tmin, vec *P
         vec N_tmp = V(0, 0, 0);
         int ok = g->is_mesh ? mesh_intersect(g->mesh, r, tri_tmin, &t, &N_tmp, cnt)
                             : sphere_intersect(g->C, g->Rr, r, &t, &N_tmp);
+        if (ok && t == t_min) CEN(cen, equal_t);                    /* the strict '<' below keeps the earlier object */
         if (ok && t < t_min) {
             t_min = t;
             id_min = g->id;
@@ -613,7 +621,7 @@ int or_scene_intersect_all(const or_scene *s, const float O[3], const float u[3]
     or_counters local = {0, 0, 0, 0, 0};
     ray r = R(V(O[0], O[1], O[2]), V(u[0], u[1], u[2]), 1.f);
     vec p, n; int id;
-    int hit = intersect_all(s, &r, tri_tmin, &p, &n, &id, &local);
+    int hit = intersect_all(s, &r, tri_tmin, &p, &n, &id, &local, NULL);
     for (int k = 0; k < 3; k++) { P[k] = p.d[k]; N[k] = n.d[k]; }
     *object_id = id;
     if (cnt) cnt_add(cnt, &local);
@@ -663,7 +671,7 @@ static float mt_uniform(mt19937 *g) {
     return r;
 }
 
-typedef struct { uint32_t seed, pixel, sample; float eps, tri_tmin; or_counters *cnt; mt19937 *mt; } trace_ctx;
+typedef struct { uint32_t seed, pixel, sample; float eps, tri_tmin; or_counters *cnt; mt19937 *mt; or_census *cen; } trace_ctx;
 static inline float rng(const trace_ctx *c, uint32_t depth, uint32_t dim) {
     if (c->mt) return mt_uniform(c->mt);
     return or_uniform(c->seed, c->pixel, c->sample, depth, dim);
@@ -674,11 +682,14 @@ static vec get_color(const or_scene *s, ray in, int ray_depth, uint32_t depth_in
     if (ray_depth < 0) return V(0.f, 0.f, 0.f);                     /* cpu:567 */
     vec P, N;
     int sphere_id = -1;
-    int inter = intersect_all(s, &in, c->tri_tmin, &P, &N, &sphere_id, c->cnt);
+    int inter = intersect_all(s, &in, c->tri_tmin, &P, &N, &sphere_id, c->cnt, c->cen);
     vec color = V(0, 0, 0);
+    if (ray_depth == 0) CEN(c->cen, last_segment);
+    if (!inter && depth_index == 0) CEN(c->cen, camera_miss);
     if (inter) {
         const geometry *g = &s->objects[sphere_id];
         if (g->mirror) {                                            /* cpu:573-579 */
+            CEN(c->cen, mirror);
             float epsilon = c->eps;
             vec P_adjusted = vadd(P, smul(epsilon, N));
             vec new_direction = vsub(in.u, smul(2 * dot(in.u, N), N));
@@ -696,9 +707,11 @@ static vec get_color(const or_scene *s, ray in, int ray_depth, uint32_t depth_in
             if (((out2in && in.refraction_index > g->in_refraction_index) ||
                  (!out2in && in.refraction_index > g->out_refraction_index)) &&
                 SQR(refract_ratio) * (1 - SQR(dot(in.u, N))) > 1) {
+                CEN(c->cen, total_reflection);
                 return get_color(s, R(vadd(P, smul(epsilon, N)), vsub(in.u, smul(2 * dot(in.u, N), N)), in.refraction_index),
                                  ray_depth - 1, depth_index + 1, c);
             }
+            if (out2in) CEN(c->cen, out2in); else CEN(c->cen, in2out);
             vec P_adjusted = vsub(P, smul(epsilon, N));
             vec N_component = smul(-sqrtf(1 - SQR(refract_ratio) * (1 - SQR(dot(in.u, N)))), N);
             vec T_component = smul(refract_ratio, vsub(in.u, smul(dot(in.u, N), N)));
@@ -713,9 +726,11 @@ static vec get_color(const or_scene *s, ray in, int ray_depth, uint32_t depth_in
             vec direct_color, indirect_color;
             vec to_light = vsub(s->L, P_adjusted);
             ray shadow = R(P_adjusted, vdivs(to_light, norm(to_light)), 1.f);   /* NORMED_VEC, cpu:30,614 */
-            (void)intersect_all(s, &shadow, c->tri_tmin, &P_prime, &N_prime, &sphere_id_shadow, c->cnt);
+            CEN(c->cen, diffuse);
+            if (!intersect_all(s, &shadow, c->tri_tmin, &P_prime, &N_prime, &sphere_id_shadow, c->cnt, c->cen)) CEN(c->cen, shadow_miss);
             if (norm2(vsub(P_prime, P_adjusted)) <= norm2(vsub(s->L, P_adjusted))) {
                 direct_color = V(0, 0, 0);
+                CEN(c->cen, shaded);
             } else {
                 vec wlight = normalize(vsub(s->L, P));
                 /* cpu:623: PI is a double literal => evaluated in binary64, narrowed to float l */
@@ -723,6 +738,9 @@ static vec get_color(const or_scene *s, ray in, int ray_depth, uint32_t depth_in
                 float l = (float)((double)s->intensity / (4 * OR_PI * (double)norm2(vsub(s->L, P))) * (double)mx);
                 /* cpu:624: (l*albedo) / float(PI) */
                 direct_color = vdivs(smul(l, g->albedo), (float)OR_PI);
+                CEN(c->cen, lit);
+                if (mx == 0) CEN(c->cen, lit_mx_zero);
+                if (!(l >= 0) || l - l != 0) CEN(c->cen, lit_l_bad);
             }
             float r1 = rng(c, depth_index, 0);                      /* cpu:628-629 */
             float r2 = rng(c, depth_index, 1);
@@ -746,7 +764,7 @@ static vec get_color(const or_scene *s, ray in, int ray_depth, uint32_t depth_in
 void or_scene_get_color(const or_scene *s, const float O[3], const float u[3], int ray_depth, float eps, float tri_tmin,
                         uint32_t seed, uint32_t pixel, uint32_t sample, float out_rgb[3], or_counters *cnt) {
     or_counters local = {0, 0, 0, 0, 0};
-    trace_ctx c = {seed, pixel, sample, eps, tri_tmin, &local, NULL};
+    trace_ctx c = {seed, pixel, sample, eps, tri_tmin, &local, NULL, NULL};
     vec col = get_color(s, R(V(O[0], O[1], O[2]), V(u[0], u[1], u[2]), 1.f), ray_depth, 0, &c);
     out_rgb[0] = col.d[0]; out_rgb[1] = col.d[1]; out_rgb[2] = col.d[2];
     if (cnt) cnt_add(cnt, &local);
@@ -816,6 +834,10 @@ void or_progressive_accumulate(float *accum, const float *frame, int npix, int f
 
 /* main's pixel loop, cpu:693-718 */
 int or_render(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *out_rgb8, or_counters *cnt) {
+    return or_render_census(s, p, out_rgba, out_rgb8, cnt, NULL);
+}
+
+int or_render_census(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *out_rgb8, or_counters *cnt, or_census *census) {
     const int W = p->W, H = p->H;
     if (W <= 0 || H <= 0 || p->num_rays <= 0 || p->row_begin < 0 || p->row_end > H || p->row_begin > p->row_end) return -1;
     const int stride = p->stride > 1 ? p->stride : 1;
@@ -838,6 +860,8 @@ int or_render(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *o
     if (p->cam_mode == 1) or_camera_basis(p->yaw, p->pitch, cbx, cby, cbz);
     const vec Bx = V(cbx[0], cbx[1], cbx[2]), By = V(cby[0], cby[1], cby[2]), Bz = V(cbz[0], cbz[1], cbz[2]);
     or_counters total = {0, 0, 0, 0, 0};
+    or_census cen_total;
+    memset(&cen_total, 0, sizeof(cen_total));
     int nthreads = 1;
 #ifdef _OPENMP
     nthreads = p->threads > 0 ? p->threads : omp_get_max_threads();
@@ -848,6 +872,8 @@ int or_render(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *o
 #pragma omp parallel num_threads(nthreads)
     {
         or_counters local = {0, 0, 0, 0, 0};
+        or_census cen_local;                                        /* per thread, like the work counters */
+        memset(&cen_local, 0, sizeof(cen_local));
 #pragma omp for schedule(dynamic, 1)
         for (int ii = 0; ii < nrows; ii++) {
             const int i = rowlist[ii];
@@ -863,7 +889,7 @@ int or_render(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *o
                 uint64_t rays_before = local.rays;
                 uint32_t pixel = (uint32_t)i * (uint32_t)W + (uint32_t)j;
                 for (int t = 0; t < p->num_rays; t++) {
-                    trace_ctx c = {p->seed, pixel, (uint32_t)t, p->eps, p->tri_tmin, &local, mt};
+                    trace_ctx c = {p->seed, pixel, (uint32_t)t, p->eps, p->tri_tmin, &local, mt, census ? &cen_local : NULL};
                     float sigma = p->sigma;
                     float r1 = rng(&c, 0, 2);                                   /* cpu:705-706 */
                     float r2 = rng(&c, 0, 3);
@@ -889,9 +915,10 @@ int or_render(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *o
             }
         }
 #pragma omp critical
-        cnt_add(&total, &local);
+        { cnt_add(&total, &local); cen_add(&cen_total, &cen_local); }
     }
     free(rowlist);
     if (cnt) *cnt = total;
+    if (census) *census = cen_total;
     return 0;
 }

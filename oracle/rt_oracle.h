@@ -34,6 +34,24 @@ typedef struct or_counters {
     uint64_t tri_tests;   /* moller_trumbore calls                            */
 } or_counters;
 
+/* branch census of one frame: how often Scene::getColor (cpu:566-648) and Scene::intersect_all (cpu:545-564) took each branch.  Counted beside the
+ * arithmetic and never read by it (or_render and or_render_census write the same frame); one set per thread, summed at the end.  All uint64_t. */
+typedef struct or_census {
+    uint64_t camera_miss;       /* a camera ray (segment 0) hit nothing                                         */
+    uint64_t mirror;            /* cpu:573                                                                      */
+    uint64_t out2in;            /* cpu:580-603, refracted from outside in                                       */
+    uint64_t in2out;            /* ... from inside out (any ray whose index is not the object's n_out)          */
+    uint64_t total_reflection;  /* cpu:593                                                                      */
+    uint64_t diffuse;           /* cpu:605                                                                      */
+    uint64_t shadow_miss;       /* the shadow ray hit nothing: P' = O + 1e9 u (cpu:560, 614)                    */
+    uint64_t shaded;            /* cpu:617: |P' - P_adj|^2 <= |L - P_adj|^2, direct term 0                      */
+    uint64_t lit;               /* cpu:619-625                                                                  */
+    uint64_t lit_mx_zero;       /* lit with max(dot(N, wlight), 0) == 0                                         */
+    uint64_t lit_l_bad;         /* lit with l negative, infinite or NaN                                         */
+    uint64_t equal_t;           /* cpu:554 met ok && t == t_min: the earlier object keeps the hit               */
+    uint64_t last_segment;      /* getColor traced a segment with ray_depth == 0 (segment num_bounce + 1)       */
+} or_census;
+
 typedef struct or_params {
     int32_t W, H;            /* image size (reference hard-codes 512x512, cpu:661) */
     int32_t num_rays;        /* argv[1], samples per pixel (cpu:659)               */
@@ -136,6 +154,9 @@ float or_uniform(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t depth,
 int or_render(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *out_rgb8,
               or_counters *cnt);
 /* the same tonemap applied to an existing float framebuffer (cpu:714-716) */
+/* or_render, and the branch census of the frame in *census (may be NULL) */
+int or_render_census(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *out_rgb8,
+                     or_counters *cnt, or_census *census);
 void or_tonemap(const float *rgba, int npix, uint8_t *out_rgb8);
 
 int or_max_threads(void);

@@ -82,33 +82,37 @@ __device__ __forceinline__ float wf_anyhit_bound(f3 Pa, float nl) {
 // first diffuse segment m whose albedo in c is +0 (the bits: a -0, a denormal or a NaN is not): whatever later segments hand up, segment m passes on
 // fl(fl(l_m (+0)) / pi) + fl((+0) x) = +0 + (+-0) = +0 -- if l_m has a clear sign bit and is finite, and x = ans_{m+1}[c] is finite.  A diffuse segment j whose three channels
 // are dead (its own albedo counted) has a shadow ray that decides only between l_j = lvis and l_j = +0, and neither value can reach the pixel: with any-hit on the ray is
-// not traced (x_moot below, the rule of the direct term that is +0 either way with a second reason) and LS keeps lvis.  The pixel is the same 96 bits if, in the chain the
-// reference folds (W: every elided l_j is lvis_j or +0) and in the chain the kernel folds (A: every elided l_j = lvis_j), each dead channel arrives at its segment m as a
-// finite x.  The argument:
-//   (1) what is known when the ray is emitted is GUARDED there: a segment counts (kills channels, keeps the mask) only if its lvis and its three albedo components have a
-//       clear sign bit and are finite -- as unsigned integers, below 0x7f800000, which rules out negative numbers, -0, inf and every NaN at once.  A segment that fails
-//       clears the mask (wf_dead_channels): kills before it are forgotten, so between a kill m and a later elided segment j every operand is non-negative and finite.
-//       (An albedo above 1 is admitted: it can only make the chain grow, which (2) covers.)  A channel killed AT j needs nothing else: x is the same in both chains.
-//   (2) with non-negative operands every rounding is monotone, so 0 <= W <= A intermediate by intermediate.  If every ans of chain A is below 2^126, its products l alb
-//       (at most pi (1 + 2^-22) times the quotient, which the sum bounds) are below 2^128: nothing in A overflows, so nothing in W does, every x is finite and non-negative
-//       in both, and the dead channels are +0 in both.  Below m the two chains fold the same numbers.
-// Outside the guarantee, because it is not known at emission: a path with an elided ray in which a LATER segment has a negative, -0, inf or NaN operand, or whose chain A
-// reaches 2^126 in some channel (the reference's pixel is then of that magnitude, inf or NaN as well).  Such a path is traced no differently; the fold of the counting
-// instantiation recognises it (wf_fold_bounded fails on a path whose state byte says a ray was elided) and counts it (rt_dead_channel_counts: unsure), conservatively: it
-// checks every diffuse segment of the path, also those before the first kill.  tests/test_dead_channels.py restates guard, fold and check in numpy binary32.
+// not traced (x_moot below, the rule of the direct term that is +0 either way with a second reason) and LS keeps lvis.  The pixel is the same (NaN for NaN) if, in the chain
+// the reference folds (W: every elided l_j is lvis_j or +0) and in the chain the kernel folds (A: every elided l_j = lvis_j), each dead channel arrives at its kill m with an
+// x that is finite in both chains or in neither (0 x is then NaN in both).  The argument rests on what is known when the ray is emitted and on nothing else:
+//   (1) the GUARD: a segment counts (kills channels, keeps the mask) only if its three albedo components lie in [+0, 1] and its lvis in [+0, 2^96) -- as unsigned integers,
+//       bits <= 0x3f800000 and < 0x6f800000, which rules out negative numbers, -0, inf and every NaN at once.  A segment that fails clears the mask (wf_dead_channels): kills
+//       before it are forgotten, so a run of segments from the earliest kill in use to the last elided segment after it holds guarded segments only.
+//   (2) inside such a run the two chains differ by the elided direct terms alone, and what enters the run from below (Z, the ans of the segment after it) is the same in
+//       both: deeper runs hand up what they were handed (each channel passes a kill of its own run).  Z non-finite: both chains carry an inf of one sign or a NaN through the
+//       run (alb Z is the same product in both, a finite direct term changes neither), so x is non-finite in both.  Z finite: a product with an albedo <= 1 cannot
+//       overflow, and a sum cannot either -- a direct term below 2^96 / pi is less than half an ulp of anything from 2^127 on and leaves it as it is, and below 2^127 the
+//       sum stays below 2^127 + 2^96 -- so x is finite in both and the dead channels are +0 in both.  Above the run the two chains fold the same numbers.
+// An albedo above 1 or a direct term of 2^96 and more was admitted by the first version of the guard, which then needed "no ans of chain A reaches 2^126" on top, a condition
+// nobody can know at emission: a light of 3e38 over walls of albedo 4 took chain A to inf where the reference's stayed finite (NaN against +0 in 346 words of a 64 x 48
+// frame, tests/test_gpu_scene_fuzz.py light_edge seed 19).  The counting instantiation still reports paths with an elided ray whose fold leaves that old range
+// (wf_fold_bounded, rt_dead_channel_counts: unsure) -- a statistic now, their pixels are the reference's.  tests/test_dead_channels.py restates guard and fold in numpy
+// binary32 and compares every chain with an elided ray.
 // State: one byte per path, WfState::DCH[i] (bits 0..2: the dead channels, bit 3: a ray was elided), zeroed by wf_advance<FIRST>, read by every diffuse segment and written
 // when it changes (at most 4 times per path): 1 B written per path and chain, <= 1 B read per path and launch.  (Bit 21 of the Y slot's flag word is NOT free for it: wf_travq
 // tests PQ_ANYHIT on every record it fetches, continuation rays included, and would take the nearest sphere's t for an any-hit bound.)
+constexpr unsigned kDeadAlbedoMax = 0x3f800000u;            // bits of 1: the largest albedo component of a segment that counts
+constexpr unsigned kDeadDirectEnd = 0x6f800000u;            // bits of 2^96: a segment that counts has its direct term below it
 constexpr unsigned kFoldFinite = 0x7f800000u;               // bits of +inf: a float whose bits are below it, as an unsigned integer, is finite with a clear sign bit
 constexpr unsigned kFoldBound = 0x7e800000u;                // bits of 2^126
 __device__ __forceinline__ unsigned wf_umax3(f3 v) { return max(max(__float_as_uint(v.x), __float_as_uint(v.y)), __float_as_uint(v.z)); }
 // the dead channels after a diffuse segment with albedo alb and direct term lvis, given those before it
 __device__ __forceinline__ int wf_dead_channels(int dead, f3 alb, float lvis) {
-    const bool good = wf_umax3(alb) < kFoldFinite && __float_as_uint(lvis) < kFoldFinite;
+    const bool good = wf_umax3(alb) <= kDeadAlbedoMax && __float_as_uint(lvis) < kDeadDirectEnd;
     const int kill = (__float_as_uint(alb.x) == 0u ? 1 : 0) | (__float_as_uint(alb.y) == 0u ? 2 : 0) | (__float_as_uint(alb.z) == 0u ? 4 : 0);
     return good ? (dead | kill) : 0;
 }
-// (2) for one folded segment: its operands and its result
+// (statistic) one folded segment inside the range the first version of the rule was argued for: its operands and its result
 __device__ __forceinline__ bool wf_fold_bounded(f3 ans, float l, f3 alb) {
     return __float_as_uint(l) < kFoldFinite && wf_umax3(alb) < kFoldFinite && wf_umax3(ans) < kFoldBound;
 }

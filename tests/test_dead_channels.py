@@ -3,15 +3,18 @@ brute force on the CPU.
 
 The fold of a path is, per channel and back to front,  ans_k = fl(fl(fl(l_k alb_k) / pi) + fl(alb_k ans_{k+1}))  (fold_segment, cpu:624, 642-644).  A channel is dead
 from the first diffuse segment whose albedo in it is +0; a diffuse segment whose three channels are dead does not trace its shadow ray and keeps l = lvis where the
-reference has lvis or +0.  The claim: wherever the guard known at emission admits the elision AND the kernel's own chain stays inside the range the fold checks
-(operands finite with a clear sign bit, every ans below 2^126), the pixel is the same 96 bits.  That is a claim about IEEE arithmetic, so it is tested here without a
-GPU, on chains of up to 17 segments with albedo components from {+0, -0, denormal, tiny, 0.25, 1, > 1, negative, inf, NaN} and direct terms from denormal to 2^127,
-inf, NaN and negative."""
+reference has lvis or +0.  The claim: wherever the guard known at emission admits the elision (albedo components in [+0, 1] and a direct term in [+0, 2^96) from the kill
+to the elided segment) the pixel is the reference's, NaN for NaN -- whatever the rest of the path holds.  That is a claim about IEEE arithmetic, so it is tested here
+without a GPU, on chains of up to 17 segments with albedo components from {+0, -0, denormal, tiny, 0.25, 1, > 1, negative, inf, NaN} and direct terms from denormal to
+2^127, inf, NaN and negative.  (The first version of the guard admitted every finite non-negative operand and held only while the kernel's own chain stayed below 2^126,
+which the fold still checks as a statistic: `sure` below.)"""
 import numpy as np
 
 f32 = np.float32
 PI_F = f32(3.14159265358979323846)
 FINITE = np.uint32(0x7f800000)          # kFoldFinite: bits of +inf
+ALBEDO_MAX = np.uint32(0x3f800000)      # kDeadAlbedoMax: bits of 1
+DIRECT_END = np.uint32(0x6f800000)      # kDeadDirectEnd: bits of 2^96
 BOUND = np.uint32(0x7e800000)           # kFoldBound: bits of 2^126
 MAX_SEG = 17                            # RT_MAX_SEGMENTS + 1 launches: depth 0..16
 
@@ -20,9 +23,14 @@ def _bits(x):
     return np.ascontiguousarray(x, f32).view(np.uint32)
 
 
+def guard(alb, lvis):
+    """the segment counts: albedo components in [+0, 1], direct term in [+0, 2^96)"""
+    return (_bits(alb).max(-1) <= ALBEDO_MAX) & (_bits(lvis) < DIRECT_END)
+
+
 def dead_channels(dead, alb, lvis):
     """wf_dead_channels: the mask after a diffuse segment (alb [n, 3], lvis [n]) given the mask before it"""
-    good = (_bits(alb).max(-1) < FINITE) & (_bits(lvis) < FINITE)
+    good = guard(alb, lvis)
     kill = ((_bits(alb) == 0) * np.array([1, 2, 4])).sum(-1)
     return np.where(good, dead | kill, 0)
 
@@ -102,9 +110,11 @@ def _chains(rng, n, odd):
     return diffuse, _albedo(rng, (n, S, 3), odd), _direct(rng, (n, S), odd), rng.random((n, S)) < 0.5
 
 
-def _assert_same_where_guaranteed(got, exp, elided, sure):
-    use = elided.any(1) & sure
-    np.testing.assert_array_equal(_bits(got[use]), _bits(exp[use]))
+def _assert_same_where_elided(got, exp, elided):
+    """every chain with an elided ray, inside the fold's old range or not: the same bits, or NaN in both"""
+    use = elided.any(1)
+    same = (_bits(got) == _bits(exp)) | (np.isnan(got) & np.isnan(exp))
+    assert same[use].all(), (got[use & ~same.all(1)][:4], exp[use & ~same.all(1)][:4])
     return use
 
 
@@ -115,22 +125,26 @@ def test_elided_rays_cannot_change_a_bit_of_the_colour():
         for _ in range(2):
             diffuse, alb, lvis, hidden = _chains(rng, 200_000, odd)
             got, exp, elided, sure = both_worlds(diffuse, alb, lvis, hidden)
-            use = _assert_same_where_guaranteed(got, exp, elided, sure)
+            use = _assert_same_where_elided(got, exp, elided)
             n_use += int(use.sum())
             n_changed += int((use & (elided & hidden & (lvis != 0)).any(1)).sum())      # the kernel folded an l the reference does not have
             n_unsure += int((elided.any(1) & ~sure).sum())
-    print("chains inside the guarantee with an elided ray:", n_use, "of them folded with an l the reference does not have:", n_changed, "outside:", n_unsure)
+    print("chains with an elided ray:", n_use, "of them folded with an l the reference does not have:", n_changed, "outside the fold's old range:", n_unsure)
     assert n_use > 50_000 and n_changed > 25_000, (n_use, n_changed)
-    assert n_unsure > 1000, n_unsure                                  # the generator reaches what the fold's check is for
+    assert n_unsure > 1000, n_unsure                                  # the generator reaches overflow, negative and non-finite operands beside an elided ray
 
 
 def test_what_the_guard_refuses():
-    """a segment with a negative, -0, inf or NaN albedo component or direct term kills nothing and clears the mask; +0 alone kills; an albedo above 1 is admitted"""
+    """a segment with a negative, -0, inf or NaN albedo component or direct term, an albedo component above 1 or a direct term of 2^96 and more kills nothing and clears
+    the mask; +0 alone kills"""
     one = np.ones(1, f32)
     z = f32(0)
     assert dead_channels(np.array([0]), np.array([[z, 1, z]], f32), one)[0] == 5
     assert dead_channels(np.array([2]), np.array([[z, 1, z]], f32), one)[0] == 7
-    assert dead_channels(np.array([2]), np.array([[z, 7.5, z]], f32), one)[0] == 7
+    assert dead_channels(np.array([7]), np.array([[z, 7.5, z]], f32), one)[0] == 0
+    assert dead_channels(np.array([7]), np.array([[z, np.nextafter(f32(1), f32(2)), z]], f32), one)[0] == 0
+    assert dead_channels(np.array([2]), np.array([[z, 1, z]], f32), np.array([np.nextafter(f32(2.0 ** 96), f32(0))], f32))[0] == 7
+    assert dead_channels(np.array([7]), np.array([[z, 1, z]], f32), np.array([2.0 ** 96], f32))[0] == 0
     assert dead_channels(np.array([2]), np.array([[z, 1e-45, z]], f32), one)[0] == 7           # a denormal kills nothing, but it is a good operand
     assert dead_channels(np.array([0]), np.array([[1e-45, 1e-45, 1e-45]], f32), one)[0] == 0
     for bad in (-0.0, -1.0, np.inf, -np.inf, np.nan):
@@ -141,8 +155,7 @@ def test_what_the_guard_refuses():
     rng = np.random.default_rng(7)
     diffuse, alb, lvis, _ = _chains(rng, 200_000, 0.2)
     elided = emit(diffuse, alb, lvis)
-    good = (_bits(alb).max(-1) < FINITE) & (_bits(lvis) < FINITE)
-    assert elided.any() and not (elided & ~good).any()
+    assert elided.any() and not (elided & ~guard(alb, lvis)).any()
 
 
 def test_every_channel_needs_its_own_kill():
@@ -158,19 +171,27 @@ def test_every_channel_needs_its_own_kill():
     assert emit(mirror, np.array([[red, green, green, grey]], f32), lvis).tolist() == [[False, False, True, True]]   # the mirror segment's albedo counts for nothing
 
 
-def test_outside_the_guarantee_the_bits_can_differ_and_the_fold_says_so():
-    """segment 0 kills every channel, segment 1's ray is elided and the light hidden; what segments 2 and 3 hand up is 3.5 x 2^126, and segment 1's own direct term takes
-    the kernel's chain past 2^128 where the reference's stays finite: NaN against +0 at segment 0 -- and the fold's check fails, at 2^126 already"""
+def test_the_path_that_overflowed_under_the_first_guard_keeps_its_ray():
+    """segment 0 kills every channel; what segments 2 and 3 hand up is 3.5 x 2^126, and segment 1's own direct term (1.9 x 2^127, the light hidden) would take the kernel's
+    chain past 2^128 where the reference's stays finite: NaN against +0 at segment 0 under a guard that admits any finite operand.  Segment 1 fails the guard (a direct
+    term of 2^96 and more), its ray is traced, and so are those behind it: the bits are the reference's."""
     diffuse = np.ones((1, 4), bool)
     alb = np.array([[(0, 0, 0), (1, 1, 1), (2, 2, 2), (1, 1, 1)]], f32)
     lvis = np.array([[1.0, 1.9 * 2.0 ** 127, 1.9 * 2.0 ** 126, 1.8 * 2.0 ** 127]], f32)
     hidden = np.array([[False, True, False, False]])
     got, exp, elided, sure = both_worlds(diffuse, alb, lvis, hidden)
-    assert elided.tolist() == [[True, True, True, True]] and not sure[0]
-    assert np.isnan(got).all() and (_bits(exp) == 0).all()
-    # the same path with direct terms the check accepts: identical
-    got, exp, elided, sure = both_worlds(diffuse, alb, (lvis * f32(2.0 ** -8)).astype(f32), hidden)
-    assert sure[0] and (_bits(got) == _bits(exp)).all()
+    assert elided.tolist() == [[True, False, False, False]]
+    assert (_bits(exp) == 0).all() and (_bits(got) == 0).all()
+    # with every ray elided, as the first guard did: NaN, and the fold's range check says so
+    got, _ = fold(diffuse, alb, lvis)
+    assert np.isnan(got).all() and not fold(diffuse, alb, lvis)[1][0]
+    # a huge chain BELOW a guarded run (albedo 1, direct terms below 2^96) changes nothing: the elided terms are less than half an ulp of it
+    alb = np.array([[(0, 0, 0), (1, 1, 1), (1, 1, 1), (1, 1, 1)]], f32)
+    lvis = np.array([[1.0, 1.9 * 2.0 ** 95, 1.9 * 2.0 ** 95, 1.99 * 2.0 ** 127]], f32)
+    hidden = np.array([[False, True, True, False]])
+    got, exp, elided, sure = both_worlds(diffuse, alb, lvis, hidden)
+    assert elided.tolist() == [[True, True, True, False]] and not sure[0]
+    assert (_bits(got) == _bits(exp)).all() and (_bits(got) == 0).all()
 
 
 def test_the_guard_admits_the_benchmark_scene():
@@ -185,7 +206,7 @@ def test_the_guard_admits_the_benchmark_scene():
     lvis = (scenes.LIGHT[1] / (4 * np.pi * r2) * np.maximum(rng.uniform(-1, 1, (n, S)), 0)).astype(f32)
     diffuse = np.ones((n, S), bool)
     hidden = rng.random((n, S)) < 0.5
-    assert ((_bits(alb).max(-1) < FINITE) & (_bits(lvis) < FINITE)).all()
+    assert guard(alb, lvis).all()
     got, exp, elided, sure = both_worlds(diffuse, alb, lvis, hidden)
     assert sure.all()
     assert float(np.abs(got).max()) < 2.0 ** 60                       # 66 binades below the bound
