@@ -1,6 +1,7 @@
 // host_capi.cpp -- C exports of include/raytracer_host.h over the C++ host API (raytracer.hpp).
 #include "../../../include/raytracer_host.h"
 #include "../../../include/raytracer.hpp"
+#include "../rt_qrows.h"
 
 using namespace raytracer;
 
@@ -55,5 +56,25 @@ void rth_mesh_get_bvh_array(const rth_mesh *m, float *o) {
     if (!m->arr.empty()) std::memcpy(o, m->arr.data(), m->arr.size() * sizeof(float));
 }
 int rth_write_png(const char *path, int W, int H, const uint8_t *rgb) { return write_png(path, W, H, rgb) ? 0 : -1; }
+
+// the device's window arithmetic (rt_qrows.h) on the host, as wf_travq's fetch uses it: workgroup b of `tblocks` looks at window slots b * share + k, k < its share's length
+int64_t rth_qrows_enumerate(int n_paths, int log2S, int Q, int tblocks, int which, int32_t info[4], int32_t *blk_len, int32_t *slots, int64_t cap) {
+    using namespace rtk;
+    const int S = 1 << log2S;
+    const QRows w = which == 1 ? qrows_y(n_paths, log2S, Q) : which == 2 ? qrows_x(n_paths, log2S, Q) : QRows{0, 0, 0u};
+    const int64_t total = w.rows != 0 ? qrows_slots(w, Q) : (int64_t)S * Q * 4;
+    const int share = qrows_share(total, tblocks);
+    info[0] = w.row0; info[1] = w.rows; info[2] = share; info[3] = (int32_t)total;
+    int64_t n = 0;
+    for (int b = 0; b < tblocks; ++b) {
+        const int len = w.rows != 0 ? qrows_share_len(total, share, b) : share;        // no window: every workgroup scans a whole share, padding included
+        if (blk_len) blk_len[b] = len;
+        for (int k = 0; k < len; ++k, ++n) {
+            const int64_t v = (int64_t)b * share + k;
+            if (slots && n < cap) slots[n] = w.rows != 0 ? qrows_slot(w, log2S, (int)v) : (int32_t)v;
+        }
+    }
+    return n;
+}
 
 }  // extern "C"

@@ -70,6 +70,8 @@ struct Knobs {
                                // first accepted triangle that certainly shades, rt_wavefront.hip.h wf_anyhit_bound).  Bit-exact either way
     int dead_channels = 1;     // RT_DEAD_CHANNELS=0: a diffuse segment whose three colour channels are dead (a zero albedo component earlier on the path in each) still traces its
                                // shadow ray (A/B, cross-check; default: with any-hit on it does not, rt_wavefront.hip.h wf_dead_channels).  Bit-exact either way
+    int travq_rows = 1;        // RT_TRAVQ_ROWS=0: every wf_travq launch scans the whole queue (A/B, cross-check; default: the first launch of a chain enumerates the rows that hold continuation
+                               // rays only and the last the rows that hold shadow rays only, rt_qrows.h).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
     int qw_count = 0;          // RT_TRAVQ_QW_COUNT=1: rt_count_work runs the 4-wide kernel's counting instantiation (its own step counters; the box / node counts then describe
                                // THAT kernel, not the reference's traversal)
@@ -121,6 +123,7 @@ static Knobs read_knobs() {
     if (geti("RT_TRAVQ_QSEL", v)) k.quad_sel = v != 0;
     if (geti("RT_TRAVQ_ANYHIT", v)) k.anyhit = v != 0;
     if (geti("RT_DEAD_CHANNELS", v)) k.dead_channels = v != 0;
+    if (geti("RT_TRAVQ_ROWS", v)) k.travq_rows = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;
     { const char *e = getenv("RT_CHUNK_MPX"); if (e && *e) { const double d = atof(e); if (d >= 0 && d < 1e4) k.chunk_mpx = d; } }

@@ -637,7 +637,14 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
             pt.st.dbg = (kn.debug_trav != -2 && it == kn.debug_trav) ? static_cast<unsigned long long *>(ctx->dbgbuf.p) : nullptr;
 #endif
             if (timed) RT_HIP(ctx, hipEventRecord(ctx->ev_trav[2 * it], q));
-            launch_trav(t, pt.tblocks, q, c.scn, pt.fr, pt.st);
+            // wf_travq's first launch can meet no shadow ray (their records carry depth >= 1, this launch looks for depth 0) and its last no continuation ray (emitted with
+            // depth <= segs - 1 only): those launches enumerate the rows of the queue that hold the other kind (rt_qrows.h) -- the same grid, shares of the window
+            rtk::WfState tst = pt.st;
+            if (t.queue && kn.travq_rows && (it == 0 || it == c.segs)) {
+                tst.win = it == 0 ? rtk::qrows_y(tst.n_paths, tst.log2S, tst.Q) : rtk::qrows_x(tst.n_paths, tst.log2S, tst.Q);
+                if (tst.win.rows != 0) tst.slots_per_block = rtk::qrows_share(rtk::qrows_slots(tst.win, tst.Q), pt.tblocks);
+            }
+            launch_trav(t, pt.tblocks, q, c.scn, pt.fr, tst);
             if (timed) { RT_HIP(ctx, hipEventRecord(ctx->ev_trav[2 * it + 1], q)); ctx->n_trav_events = it + 1; }
             pt.st.dbg = nullptr;
         }

@@ -329,7 +329,9 @@ __global__ __launch_bounds__((LDSN || LDSV) ? 1024 : kQBlock, (LDSN || LDSV || k
     auto best = [&](unsigned int sb) -> unsigned long long * { return reinterpret_cast<unsigned long long *>(wl + Carve::kTabD + sb + 8); };
     auto bandw = [&](unsigned int sb) -> float & { return *reinterpret_cast<float *>(wl + Carve::kTabA + sb + 12); };      // row A's .w: the ray's band; -inf = the slot is dead (any-hit)
     const unsigned int my_sb0 = (unsigned int)lane << 4;           // lane l owns ray slot l (bank 0) and l + 64 (bank 1, R = 128): row offsets
-    if (tid == 0) *blk_cur = 0;
+    // the cursor's 16 bytes hold the launch's row window too (rt_qrows.h): its three words are wanted once per fetch and only by the first and the last launch of a chain --
+    // in LDS they cost the loop no scalar register (the kernel uses every one it can have: a value more is a spill into vector lanes in the BOX step)
+    if (tid == 0) { blk_cur[0] = 0; blk_cur[1] = st.win.rows; blk_cur[2] = (int)st.win.rows_m; blk_cur[3] = st.win.row0; }
     for (int k = 0; k < NT; ++k) marks[lane + 64 * k] = 0;
     for (int b = 0; b < NB; ++b) if (lane + 64 * b < R) *pend(my_sb0 + 1024u * b) = 0;
     if (LDSN) for (int k = tid; k < 2 * n_lds; k += (int)blockDim.x) lnodes[k] = sc.nodesb[k];
@@ -341,7 +343,8 @@ __global__ __launch_bounds__((LDSN || LDSV) ? 1024 : kQBlock, (LDSN || LDSV || k
     // kind = triangle count << 11 (0 for an empty leaf)
     const unsigned char *const nodes = reinterpret_cast<const unsigned char *>(sc.nodesb);
     const size_t blk_base = (size_t)blockIdx.x * (size_t)st.slots_per_block;
-    const int blk_n = st.slots_per_block;
+    // a row window (rt_qrows.h): blk_base + k is then a slot of the WINDOW, mapped to its queue slot where it is fetched, and the shares past the window's end are short or empty
+    const int blk_n = st.win.rows != 0 ? qrows_share_len(qrows_slots(st.win, st.Q), st.slots_per_block, (int)blockIdx.x) : st.slots_per_block;
     int stage_n = 0, stage_used = 0;              // wave-uniform: staged records and how many of them have been given a slot
     float4 sp0 = make_float4(0, 0, 0, 0);         // staged record of this lane (registers; sidx[k] = lane of the k-th staged record)
     float2 sp1 = make_float2(0, 0);
@@ -457,11 +460,13 @@ __global__ __launch_bounds__((LDSN || LDSV) ? 1024 : kQBlock, (LDSN || LDSV || k
                     WQ_MARK("fetch_begin");
                     int base = 0;
                     if (lane == 0) base = atomicAdd(blk_cur, 64);
+                    const int win_rows = __builtin_amdgcn_readfirstlane(blk_cur[1]);   // 0: no window (with the cursor: one wait for both)
                     base = __builtin_amdgcn_readfirstlane(base);
                     if (base + 64 >= blk_n) { drained = true; if (dbg_on && !dbg_tdrain) dbg_tdrain = __builtin_amdgcn_s_memrealtime(); }
                     spf = 0;
                     if (base + lane < blk_n) {
-                        const size_t q = (size_t)blk_base + (size_t)(base + lane);
+                        size_t q = (size_t)blk_base + (size_t)(base + lane);
+                        if (__builtin_expect(win_rows != 0, 0)) q = (size_t)qrows_slot(QRows{blk_cur[3], win_rows, (unsigned int)blk_cur[2]}, st.log2S, (int)q);
                         const float4 qb = st.QR[2 * q + 1];             // the slot's 32-byte record: flag and ray in one round trip
                         sp0 = st.QR[2 * q]; sp1 = make_float2(qb.x, qb.y);
                         spf = wq_live(__float_as_int(qb.z), st.epoch, st.nonce) ? wf_slot_to_path(st, (int)q) + 1 : 0;   // ray + 1 if the slot's record is live for this launch

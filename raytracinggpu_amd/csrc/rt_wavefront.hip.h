@@ -36,6 +36,7 @@
 // and sub-results meet in one 64-bit atomic min on (bits(t) << 32 | index).  Results stay bit-identical.
 #pragma once
 #include "rt_kernels.hip.h"
+#include "rt_qrows.h"
 
 namespace rtk {
 
@@ -195,6 +196,7 @@ struct WfState {
                               // flag word (PF_* | PQ_*; 0 = no path), W1 = t of the Y ray's nearest sphere; X slot: W0 = PQ_TRAV | depth | chain number (| PQ_ANYHIT: W1 = the any-hit bound), written only when the ray needs traversal
     unsigned char *DCH;       // [n_paths] dead channels of path i (bits 0..2) and whether one of its shadow rays was elided for them (bit 3); wf_advance<FIRST> zeroes it (deadch only)
     int deadch;               // any-hit is on and so is the dead-channel rule: a diffuse segment whose three channels are dead does not trace its shadow ray (wf_dead_channels)
+    QRows win;                // wf_travq: the rows of the queue this launch enumerates (rt_qrows.h; slots_per_block is then a share of the window); all zero = every row, the slot index as it is
 };
 
 // n / d for 0 <= n < 2^32 with m = floor(2^32 / d) from the host: the estimate mulhi(n, m) is the quotient or one below it

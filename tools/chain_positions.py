@@ -1,0 +1,34 @@
+"""Per-position averages of a launch chain's kernels from a rocprofv3 kernel trace (CPU only).
+
+`rocprofv3 --kernel-trace --stats` averages wf_travq and wf_advance over the five launches of the headline's chain, which differ by a factor of three; this splits the trace
+by queue, restarts the position at every wf_advance<FIRST> and averages each position on its own -- what the first and the last launch of the chain cost.
+
+usage: python tools/chain_positions.py DIR   (DIR: what rocprofv3 -d wrote; reads the first *kernel_trace.csv below it)"""
+import collections
+import csv
+import glob
+import sys
+
+fs = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)
+if not fs:
+    raise SystemExit("no kernel trace under " + sys.argv[1])
+per = collections.defaultdict(list)
+for r in csv.DictReader(open(fs[0])):
+    per[r.get("Queue_Id", "0")].append(r)
+acc = {"wf_travq": collections.defaultdict(list), "wf_advance": collections.defaultdict(list)}
+for rs in per.values():
+    rs.sort(key=lambda r: int(r["Start_Timestamp"]))
+    kt = ka = -1
+    for r in rs:
+        name, dur = r["Kernel_Name"], int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+        if "wf_advance<false, true>" in name:
+            kt = ka = 0
+        elif kt >= 0 and "wf_travq" in name:
+            acc["wf_travq"][kt].append(dur)
+            kt += 1
+        elif ka >= 0 and "wf_advance" in name:
+            acc["wf_advance"][ka].append(dur)
+            ka += 1
+for kind, a in acc.items():
+    print("%s by position in the chain, average / fastest us (launches): %s" % (
+        kind, ", ".join("%d: %.1f / %.1f (%d)" % (k, sum(v) / len(v) / 1e3, min(v) / 1e3, len(v)) for k, v in sorted(a.items()))))
