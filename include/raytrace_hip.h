@@ -224,8 +224,9 @@ int rt_render_device_batch(rt_ctx *ctx, const rt_params *p, const rt_rows *rows,
  *       move_light        MoveLightSource: get, rt_light_orbit, set;
  *       rt_light_orbit    (host function, no context) the light turned about the y axis through the origin: radius = sqrtf(x * x + z * z) (the reference's
  *                         powf(d, 2) as d * d), angle = atan2f(z, x) + angular_speed * dt, x' = radius * cosf(angle), z' = radius * sinf(angle), y and the
- *                         intensity untouched; binary32 throughout, with the host's C library.  The reference evaluates it with CUDA's device functions, which no
- *                         test here can run: like the posed camera this row is unpinned (x', z' are held to the formula in binary64 within 16 * 2^-24 * radius).
+ *                         intensity untouched; binary32 throughout, with the host's C library.  Pinned: MoveLightSource itself, run as a host function with the same C library, gives the
+ *                         same bits for 100 lights and a chain of 20 steps (tests/golden/ref_realtime.npz, tests/test_realtime_pinned.py; MoveObject likewise); x', z' are also
+ *                         held to the formula in binary64 within 16 * 2^-24 * radius.
  *     Contract: after any sequence of these calls every render entry (rt_render*, _device, _batch, _async, _pose*, rt_progressive_frame, rt_trace_rays,
  *     rt_count_work; every rt_variant) produces, bit for bit, what it produces after rt_scene_upload* of the same meshes with the edited light / spheres:
  *     what an upload derives from a sphere (R * R as one binary32 product, the per-object centre, mirror bit, albedo and indices) is derived again by the same code.
@@ -492,8 +493,16 @@ int rt_kat_surface(rt_ctx *ctx, const float *rays, int n, float tri_tmin, float 
  *     {C, yaw, pitch} with Camera::rotate() (realtime_render.cu:803-861); ray generation and per-sample averaging of its
  *     KernelLaunch (:1100-1134: u_center = C + bz*z + bx*X + by*Y, outcolor += color * (1./num_rays)); accumulation and
  *     display of :1136-1147 (accumbuffer += frame; display = accumbuffer / framenumber; powf(c, 1/2.2f)); the frame's RNG
- *     seed is WangHash(framenumber) (:1190-1197, :1268).  Wavefront variants only.  Parity: checked against the oracle's
- *     restatement; the reference program itself (CUDA + GL, cuRAND) cannot be run, so this row is unpinned. ----------- */
+ *     seed is WangHash(framenumber) (:1190-1197, :1268).  Wavefront variants only.  Parity: PINNED.  The reference's own
+ *     Camera::rotate and KernelLaunch, run as host functions, wrote tests/golden/ref_realtime.npz (the basis, every camera
+ *     ray of small frames with and without jitter, the 8-bit output around every code boundary); the oracle and
+ *     rt_camera_basis equal it bit for bit (tests/test_realtime_pinned.py), the device equals it through smooth normals of
+ *     those rays and through the oracle (tests/test_gpu_realtime_pinned.py).
+ *     ONE RECORDED DEVIATION, rt_render_pose and everything posed: z = -W / (2 tan(fov / 2)) uses the CORRECTLY ROUNDED
+ *     binary32 tangent (binary64 tan, narrowed), as the fixed camera does where g++ folds cpu:694; realtime:1112 calls tanf
+ *     at run time, which is not correctly rounded and may differ between C libraries.  Of the fovs pi / 2, pi / 3, 1.0 and
+ *     0.7 the two differ at pi / 3 alone (0x1.279a74p-1 here, 0x1.279a76p-1 from glibc's tanf); there the rays equal the
+ *     reference's once z is the reference's. ----------- */
 typedef struct rt_camera_pose { float position[3]; float yaw; float pitch; float fov; } rt_camera_pose;
 int rt_camera_basis(const rt_camera_pose *pose, float bx[3], float by[3], float bz[3]);   /* Camera::rotate(), host */
 /* one frame with the posed camera (no accumulation): full frame to host / rows to device memory */

@@ -13,6 +13,9 @@ What it does
   * runs oracle/_ref/ref_harness (oracle/ref_harness.cpp + the reference TU) to dump
     the parsed mesh, the BVH, primitive known-answer tests, float renders (direct
     lighting, and mt19937(0)-replayable stochastic renders) and a statistical mean;
+  * runs oracle/_ref/realtime_harness (oracle/realtime_harness.cpp + the device code of the reference's
+    realtime_render.cu as host functions) for the posed camera, the progressive output, smooth normals,
+    the transform kernel and the motions (`realtime`; oracle/realtime_fixture.py);
   * packs everything as numpy .npz (no pickles) under tests/golden/.
 
 The fixtures are data: inputs and the reference's outputs.  No reference source
@@ -262,7 +265,24 @@ def make_fuzz():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def make_realtime():
+    """tests/golden/ref_realtime.npz alone (`python oracle/make_golden.py realtime`): the posed camera and its rays, the progressive output, smooth normals, the
+    `transform` kernel and the light's and spheres' motions as the device code of the reference's realtime_render.cu computes them, run as host functions by
+    oracle/_ref/realtime_harness; inputs and the run are oracle/realtime_fixture.py's.  The same bytes on every run."""
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    import realtime_fixture
+    if not os.path.exists(realtime_fixture.HARNESS):
+        raise SystemExit("build the reference first: make -C oracle ref")
+    path = os.path.join(GOLD, "ref_realtime.npz")
+    realtime_fixture.save(path, realtime_fixture.build())
+    print("realtime", os.path.getsize(path), "bytes", hashlib.sha256(open(path, "rb").read()).hexdigest())
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "realtime":
+        os.makedirs(GOLD, exist_ok=True)
+        return make_realtime()
     if not (os.path.exists(CPU) and os.path.exists(HARNESS)):
         raise SystemExit("build the reference first: make -C oracle ref")
     os.makedirs(GOLD, exist_ok=True)
@@ -347,6 +367,7 @@ def main():
         make_materials()
         make_obj()
         make_fuzz()
+        make_realtime()
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     for fn in sorted(os.listdir(GOLD)):

@@ -72,11 +72,14 @@ def lib():
     for n in ("or_mesh_num_vertices", "or_mesh_num_triangles", "or_mesh_num_nodes", "or_mesh_max_depth"):
         getattr(L, n).argtypes = [vp]
     L.or_mesh_get_vertices.argtypes = [vp, fp]
+    L.or_mesh_num_normals.argtypes = [vp]
+    L.or_mesh_get_normals.argtypes = [vp, fp]
     L.or_mesh_get_triangles.argtypes = [vp, C.POINTER(C.c_int32)]
     L.or_mesh_bvh_to_array.argtypes = [vp, fp]
     L.or_mesh_set_albedo.argtypes = [vp, C.c_float, C.c_float, C.c_float]
     L.or_mesh_set_material.argtypes = [vp, C.c_int, C.c_float, C.c_float]
     L.or_mesh_intersect.argtypes = [vp, fp, fp, C.c_float, fp, fp, C.POINTER(Counters)]
+    L.or_mesh_intersect_tri.argtypes = [vp, fp, fp, C.c_float, fp, fp, C.POINTER(C.c_int)]
     L.or_sphere_intersect.argtypes = [fp, C.c_float, fp, fp, fp, fp]
     L.or_box_intersect.argtypes = [fp, fp, fp, fp]
     L.or_moller_trumbore.argtypes = [fp, fp, fp, fp, fp, fp, fp]
@@ -98,6 +101,9 @@ def lib():
     L.or_wang_hash.argtypes = [C.c_uint32]
     L.or_wang_hash.restype = C.c_uint32
     L.or_progressive_accumulate.argtypes = [fp, fp, C.c_int, C.c_int, fp, C.POINTER(C.c_uint8)]
+    L.or_posed_ray.argtypes = [C.c_int, C.c_int, C.c_float, fp, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp, fp]
+    L.or_light_orbit.argtypes = [fp, C.c_float, C.c_float, fp]
+    L.or_sphere_move.argtypes = [fp, fp, C.c_float, fp]
     _lib = L
     return L
 
@@ -174,7 +180,7 @@ class Mesh:
         return self
 
     def transform(self, rotation, translation):
-        """global_launcher.cu's `transform` kernel on the vertices (row-major 3x3, then translation)."""
+        """The `transform` kernel (global_launcher.cu = realtime:415-432) on the vertices and the shading normals (row-major 3x3, then translation)."""
         r, rp = _f(np.asarray(rotation, np.float32).reshape(9)); t, tp = _f(translation)
         lib().or_mesh_transform(self.h, rp, tp)
         return self
@@ -188,6 +194,13 @@ class Mesh:
         n = lib().or_mesh_num_vertices(self.h)
         a = np.zeros((n, 3), np.float32)
         lib().or_mesh_get_vertices(self.h, a.ctypes.data_as(C.POINTER(C.c_float)))
+        return a
+
+    @property
+    def shading_normals(self):
+        n = lib().or_mesh_num_normals(self.h)
+        a = np.zeros((n, 3), np.float32)
+        lib().or_mesh_get_normals(self.h, a.ctypes.data_as(C.POINTER(C.c_float)))
         return a
 
     @property
@@ -215,6 +228,13 @@ class Mesh:
         t = C.c_float(0); N = np.zeros(3, np.float32)
         hit = lib().or_mesh_intersect(self.h, Op, up, tri_tmin, C.byref(t), N.ctypes.data_as(C.POINTER(C.c_float)), None)
         return bool(hit), t.value, N
+
+    def intersect_tri(self, O, u, tri_tmin=1e-4):
+        """intersect(), and the winning triangle's position in the mesh's CURRENT triangle order (self.triangles); -1 on a miss"""
+        O_, Op = _f(O); u_, up = _f(u)
+        t = C.c_float(0); N = np.zeros(3, np.float32); tri = C.c_int(-1)
+        hit = lib().or_mesh_intersect_tri(self.h, Op, up, tri_tmin, C.byref(t), N.ctypes.data_as(C.POINTER(C.c_float)), C.byref(tri))
+        return bool(hit), t.value, N, tri.value
 
 
 class Scene:
@@ -303,6 +323,30 @@ def camera_basis(yaw, pitch):
     """Camera::rotate() of realtime_render.cu:823-846 -> (bx, by, bz)."""
     out = [np.zeros(3, np.float32) for _ in range(3)]
     lib().or_camera_basis(yaw, pitch, *[o.ctypes.data_as(C.POINTER(C.c_float)) for o in out])
+    return out
+
+
+def posed_ray(W, H, fov, cam, yaw, pitch, x, y, r1, r2, sigma=0.2, z=None):
+    """The camera ray KernelLaunch builds for pixel (x, y) (realtime:1112-1128) -> (O, u); z: use this z instead of -W / (2 tan(fov / 2))."""
+    c, cp = _f(cam)
+    O = np.zeros(3, np.float32); u = np.zeros(3, np.float32)
+    fpt = C.POINTER(C.c_float)
+    zz = None if z is None else C.byref(C.c_float(z))
+    lib().or_posed_ray(W, H, fov, cp, yaw, pitch, sigma, x, y, r1, r2, C.cast(zz, fpt) if zz is not None else None, O.ctypes.data_as(fpt), u.ctypes.data_as(fpt))
+    return O, u
+
+
+def light_orbit(L, angular_speed, dt):
+    """MoveLightSource (realtime:1072-1090) -> the new position"""
+    l, lp = _f(L); out = np.zeros(3, np.float32)
+    lib().or_light_orbit(lp, angular_speed, dt, out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+def sphere_move(Cc, v, dt):
+    """MoveObject (realtime:1092-1098) -> the new centre"""
+    c, cp = _f(Cc); v_, vp_ = _f(v); out = np.zeros(3, np.float32)
+    lib().or_sphere_move(cp, vp_, dt, out.ctypes.data_as(C.POINTER(C.c_float)))
     return out
 
 

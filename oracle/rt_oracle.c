@@ -263,6 +263,11 @@ void or_mesh_set_normals(or_mesh *m, const float *normals_xyz, int n, const int3
     for (int i = 0; i < m->nt; i++) { m->indices[i].ni = nidx[3 * i]; m->indices[i].nj = nidx[3 * i + 1]; m->indices[i].nk = nidx[3 * i + 2]; }
 }
 
+int or_mesh_num_normals(const or_mesh *m) { return m->n_shading_normals; }
+void or_mesh_get_normals(const or_mesh *m, float *out_xyz) {
+    for (int i = 0; i < m->n_shading_normals; i++) { out_xyz[3 * i] = m->normals[i].d[0]; out_xyz[3 * i + 1] = m->normals[i].d[1]; out_xyz[3 * i + 2] = m->normals[i].d[2]; }
+}
+
 /* opt:297-301 */
 void or_mesh_rescale(or_mesh *m, float scale, const float offset[3]) {
     for (int i = 0; i < m->nv; i++) m->vertices[i] = vadd(vmuls(m->vertices[i], scale), V(offset[0], offset[1], offset[2]));
@@ -442,7 +447,7 @@ static inline int moller_trumbore(vec A, vec B, vec C, vec *N, const ray *r, flo
 /* cpu:277-311 (ENABLE_BVH).  "Hit" is restated as "some triangle accepted":
  * the reference returns t_min != INF with INF a double (always true),
  * which Scene::intersect_all neutralises through t < t_min (cpu:554). */
-static int mesh_intersect(const or_mesh *m, const ray *r, float tri_tmin, float *t, vec *N, or_counters *cnt) {
+static int mesh_intersect_tri(const or_mesh *m, const ray *r, float tri_tmin, float *t, vec *N, or_counters *cnt, int *tri) {
     if (!m->bvh) return 0;
     cnt->box_tests++;
     if (!bbox_intersect(&m->bvh->bb, r)) return 0;                 /* cpu:279 */
@@ -494,7 +499,20 @@ static int mesh_intersect(const or_mesh *m, const ray *r, float tri_tmin, float 
         *N = normalize(vadd(vadd(smul(alpha, Na), smul(beta, Nb)), smul(gamma, Nc)));
     }
     *t = t_min;
+    if (tri) *tri = idx_min;
     return 1;
+}
+static int mesh_intersect(const or_mesh *m, const ray *r, float tri_tmin, float *t, vec *N, or_counters *cnt) {
+    return mesh_intersect_tri(m, r, tri_tmin, t, N, cnt, NULL);
+}
+
+int or_mesh_intersect_tri(const or_mesh *m, const float O[3], const float u[3], float tri_tmin, float *t, float N[3], int *tri) {
+    or_counters local = {0, 0, 0, 0, 0};
+    ray r = R(V(O[0], O[1], O[2]), V(u[0], u[1], u[2]), 1.f);
+    vec n = V(0, 0, 0); float tt = 0; int id = -1;
+    int hit = mesh_intersect_tri(m, &r, tri_tmin, &tt, &n, &local, &id);
+    if (hit) { *t = tt; N[0] = n.d[0]; N[1] = n.d[1]; N[2] = n.d[2]; if (tri) *tri = id; }
+    return hit;
 }
 
 int or_mesh_intersect(const or_mesh *m, const float O[3], const float u[3], float tri_tmin, float *t, float N[3], or_counters *cnt) {
@@ -832,6 +850,60 @@ void or_progressive_accumulate(float *accum, const float *frame, int npix, int f
     }
 }
 
+/* MoveLightSource, realtime_render.cu:1072-1090, with its C = (0, 0, 0): every operation in binary32, powf(., 2) as written there */
+void or_light_orbit(const float L[3], float angular_speed, float dt, float out[3]) {
+    const float Cx = 0.f, Cz = 0.f;
+    const float radius = sqrtf(powf(Cx - L[0], 2) + powf(Cz - L[2], 2));
+    const float current = atan2f(L[2] - Cz, L[0] - Cx);
+    const float angle = current + angular_speed * dt;
+    const float x = Cx + radius * cosf(angle), y = L[1], z = Cz + radius * sinf(angle);
+    out[0] = x; out[1] = y; out[2] = z;
+}
+
+/* MoveObject, realtime_render.cu:1092-1098: sp->C = sp->C + v * dt, the product and the sum each rounded to binary32 */
+void or_sphere_move(const float C[3], const float v[3], float dt, float out[3]) {
+    const vec r = vadd(V(C[0], C[1], C[2]), vmuls(V(v[0], v[1], v[2]), dt));
+    out[0] = r.d[0]; out[1] = r.d[1]; out[2] = r.d[2];
+}
+
+/* cpu:694 `-W / (2 * tan(alpha/2))`: alpha is a compile-time constant in the reference, so g++ -O3
+ * folds tan(float) with MPFR => the CORRECTLY ROUNDED binary32 tangent (0x1.279a74p-1 for pi/3/2),
+ * whereas glibc's run-time tanf returns 0x1.279a76p-1.  binary64 tan narrowed to binary32 reproduces
+ * the folded value (pinned by tests/golden/ref_render.npz; DESIGN.md hazard H12).  realtime:1112 evaluates the same
+ * expression at RUN time (tanf); the correctly rounded value is kept for the posed camera too -- a recorded deviation,
+ * DESIGN.md "Numerics": tests/test_realtime_pinned.py holds every fov at which the two agree bit for bit. */
+static inline float camera_z(int W, float alpha) { return -W / (2 * (float)tan((double)(alpha / 2))); }
+
+/* the centre of pixel (j, i) on the image plane: cpu:699 (cam_mode 0), realtime:1115 (cam_mode 1) */
+static inline vec camera_u_center(int W, int H, int j, int i, float z, int cam_mode, vec Cc, vec Bx, vec By, vec Bz) {
+    /* cpu:699: the +0.5 / -0.5 are double literals, narrowed by Vector(float,...) */
+    vec u_center = V((float)((double)((float)j - (float)W / 2) + 0.5),
+                     (float)((double)((float)H / 2 - (float)i) - 0.5), z);
+    if (cam_mode == 1)   /* realtime:1115: cam.C + cam.bz * z + cam.bx * (x - W/2 + 0.5) + cam.by * (H/2 - y - 0.5) */
+        u_center = vadd(vadd(vadd(Cc, vmuls(Bz, z)), vmuls(Bx, u_center.d[0])), vmuls(By, u_center.d[1]));
+    return u_center;
+}
+
+/* the jittered, normalised direction: cpu:705-709 = realtime:1123-1128 */
+static inline vec camera_jitter(vec u_center, float sigma, float r1, float r2) {
+    /* cpu:707: sigma*sqrt(-2*log(r1)) in float, cos/sin(2*PI*r2) in double */
+    float bm = sigma * sqrtf(-2 * logf(r1));
+    vec jit = V((float)((double)bm * cos(2 * OR_PI * (double)r2)),
+                (float)((double)bm * sin(2 * OR_PI * (double)r2)), 0);
+    return normalize(vadd(u_center, jit));
+}
+
+void or_posed_ray(int W, int H, float fov, const float cam[3], float yaw, float pitch, float sigma, int x, int y, float r1, float r2,
+                  const float *z_given, float O[3], float u[3]) {
+    float bx[3], by[3], bz[3];
+    or_camera_basis(yaw, pitch, bx, by, bz);
+    const vec Cc = V(cam[0], cam[1], cam[2]);
+    const float z = z_given ? *z_given : camera_z(W, fov);
+    const vec uc = camera_u_center(W, H, x, y, z, 1, Cc, V(bx[0], bx[1], bx[2]), V(by[0], by[1], by[2]), V(bz[0], bz[1], bz[2]));
+    const vec d = camera_jitter(uc, sigma, r1, r2);
+    for (int k = 0; k < 3; k++) { O[k] = Cc.d[k]; u[k] = d.d[k]; }
+}
+
 /* main's pixel loop, cpu:693-718 */
 int or_render(const or_scene *s, const or_params *p, float *out_rgba, uint8_t *out_rgb8, or_counters *cnt) {
     return or_render_census(s, p, out_rgba, out_rgb8, cnt, NULL);
@@ -850,11 +922,7 @@ int or_render_census(const or_scene *s, const or_params *p, float *out_rgba, uin
         rowlist[nrows++] = r;
     }
     const float alpha = p->fov;
-    /* cpu:694 `-W / (2 * tan(alpha/2))`: alpha is a compile-time constant in the reference, so g++ -O3
-     * folds tan(float) with MPFR => the CORRECTLY ROUNDED binary32 tangent (0x1.279a74p-1 for pi/3/2),
-     * whereas glibc's run-time tanf returns 0x1.279a76p-1.  binary64 tan narrowed to binary32 reproduces
-     * the folded value (pinned by tests/golden/ref_render.npz; DESIGN.md hazard H12). */
-    const float z = -W / (2 * (float)tan((double)(alpha / 2)));
+    const float z = camera_z(W, alpha);
     const vec Cc = V(p->cam[0], p->cam[1], p->cam[2]);
     float cbx[3] = {1, 0, 0}, cby[3] = {0, 1, 0}, cbz[3] = {0, 0, -1};
     if (p->cam_mode == 1) or_camera_basis(p->yaw, p->pitch, cbx, cby, cbz);
@@ -879,11 +947,7 @@ int or_render_census(const or_scene *s, const or_params *p, float *out_rgba, uin
             const int i = rowlist[ii];
             for (int jj = 0; jj < ncols; jj++) {
                 const int j = jj * stride;
-                /* cpu:699: the +0.5 / -0.5 are double literals, narrowed by Vector(float,...) */
-                vec u_center = V((float)((double)((float)j - (float)W / 2) + 0.5),
-                                 (float)((double)((float)H / 2 - (float)i) - 0.5), z);
-                if (p->cam_mode == 1)   /* realtime:1115: cam.C + cam.bz * z + cam.bx * (x - W/2 + 0.5) + cam.by * (H/2 - y - 0.5) */
-                    u_center = vadd(vadd(vadd(Cc, vmuls(Bz, z)), vmuls(Bx, u_center.d[0])), vmuls(By, u_center.d[1]));
+                const vec u_center = camera_u_center(W, H, j, i, z, p->cam_mode, Cc, Bx, By, Bz);
                 const float inv_n = (float)(1. / p->num_rays);           /* realtime:1131 color * (1./num_rays) */
                 vec color_total = V(0, 0, 0);
                 uint64_t rays_before = local.rays;
@@ -893,11 +957,7 @@ int or_render_census(const or_scene *s, const or_params *p, float *out_rgba, uin
                     float sigma = p->sigma;
                     float r1 = rng(&c, 0, 2);                                   /* cpu:705-706 */
                     float r2 = rng(&c, 0, 3);
-                    /* cpu:707: sigma*sqrt(-2*log(r1)) in float, cos/sin(2*PI*r2) in double */
-                    float bm = sigma * sqrtf(-2 * logf(r1));
-                    vec jit = V((float)((double)bm * cos(2 * OR_PI * (double)r2)),
-                                (float)((double)bm * sin(2 * OR_PI * (double)r2)), 0);
-                    vec u = normalize(vadd(u_center, jit));
+                    vec u = camera_jitter(u_center, sigma, r1, r2);
                     vec color = get_color(s, R(Cc, u, 1.f), p->num_bounce, 0, &c);
                     color_total = vadd(color_total, p->cam_mode == 1 ? vmuls(color, inv_n) : color);
                 }

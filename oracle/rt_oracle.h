@@ -76,7 +76,7 @@ typedef struct or_params {
     int32_t cam_mode;        /* 0: cpu_launcher's fixed camera (cpu:694-699)
                                 1: realtime_render.cu's posed camera and per-sample averaging
                                    (KernelLaunch realtime:1100-1134, Camera realtime:803-861);
-                                   parity UNPINNED: that program cannot be built here (CUDA + GL)  */
+                                   the camera ray is PINNED by tests/golden/ref_realtime.npz        */
     float   yaw, pitch;      /* cam_mode 1: Camera::yaw / Camera::pitch                          */
 } or_params;
 
@@ -89,12 +89,16 @@ void     or_mesh_free(or_mesh *m);
 int      or_mesh_read_obj(or_mesh *m, const char *path, float scale, const float offset[3]);
 /* replace geometry by explicit arrays (already transformed vertices, OBJ order) */
 void     or_mesh_set_arrays(or_mesh *m, const float *verts_xyz, int nv, const int32_t *tri_vidx, int nt);
-/* smooth shading (parity unpinned: realtime_render.cu:221-245 get_smooth_normal): vertex normals and the
+/* smooth shading (realtime_render.cu:221-245 get_smooth_normal, pinned by tests/golden/ref_realtime.npz): vertex normals and the
  * triangles' ni,nj,nk (3 per triangle, in the mesh's current triangle order); NULL switches back to flat shading */
 void     or_mesh_set_normals(or_mesh *m, const float *normals_xyz, int n_normals, const int32_t *nidx);
+/* the shading normals as they are now (or_mesh_transform moves them) */
+int      or_mesh_num_normals(const or_mesh *m);
+void     or_mesh_get_normals(const or_mesh *m, float *out_xyz);
 /* TriangleMeshHost::rescale (optimized.cu:297-301) */
 void     or_mesh_rescale(or_mesh *m, float scale, const float offset[3]);
-/* the `transform` kernel of global_launcher.cu:340-365 on the vertices (rotation matrix row-major, then translation) */
+/* the `transform` kernel of global_launcher.cu:340-365 = realtime_render.cu:415-432 on the vertices AND the shading normals (rotation matrix row-major,
+ * then translation, which the kernel adds to the normals too); pinned by tests/golden/ref_realtime.npz */
 void     or_mesh_transform(or_mesh *m, const float rotation[9], const float translation[3]);
 /* keep the BVH's topology and triangle order, recompute every node's box (compute_bbox, cpu:180-188) */
 void     or_mesh_refit(or_mesh *m);
@@ -118,6 +122,9 @@ void     or_mesh_set_material(or_mesh *m, int mirror, float n_in, float n_out);
 /* TriangleMesh::intersect (cpu:238-313, ENABLE_BVH branch). returns hit flag */
 int      or_mesh_intersect(const or_mesh *m, const float O[3], const float u[3], float tri_tmin,
                            float *t, float N[3], or_counters *cnt);
+/* the same, and *tri = the winning triangle's position in the mesh's CURRENT triangle order (or_mesh_get_triangles) */
+int      or_mesh_intersect_tri(const or_mesh *m, const float O[3], const float u[3], float tri_tmin,
+                               float *t, float N[3], int *tri);
 
 /* ---- primitives ---- */
 /* Sphere::intersect (cpu:512-527) */
@@ -161,7 +168,8 @@ void or_tonemap(const float *rgba, int npix, uint8_t *out_rgb8);
 
 int or_max_threads(void);
 
-/* ---- realtime_render.cu pieces (parity unpinned, see cam_mode) ---- */
+/* ---- realtime_render.cu pieces.  Parity status: PINNED by tests/golden/ref_realtime.npz, which oracle/realtime_harness.cpp writes by
+ * running that program's own device code as host functions (tests/test_realtime_pinned.py); one recorded deviation, the tangent of or_posed_ray ---- */
 /* Camera::rotate() (realtime:823-846): orthonormal basis from yaw and pitch */
 void or_camera_basis(float yaw, float pitch, float bx[3], float by[3], float bz[3]);
 /* WangHash (realtime:1190-1197): the per-frame RNG seed */
@@ -169,6 +177,15 @@ uint32_t or_wang_hash(uint32_t a);
 /* accumbuffer += frame; display = accumbuffer / framenumber (cutil_math: a * (1.0f / s)); 8-bit image =
  * (unsigned char)min(powf(c, 1 / 2.2f), 255.) (realtime:1136-1147).  accum/frame/display: npix * 4 floats */
 void or_progressive_accumulate(float *accum, const float *frame, int npix, int framenumber, float *display, uint8_t *out_rgb8);
+/* the camera ray of pixel (x, y) that KernelLaunch builds (realtime:1112-1128) from the pose, the jitter's two uniforms r1, r2 and sigma (0.2f there):
+ * the code or_render runs with cam_mode 1.  z = -W / (2 tan(fov / 2)) with the CORRECTLY ROUNDED binary32 tangent where the reference calls tanf at
+ * run time (a recorded deviation, DESIGN.md "Numerics"); z_given != NULL: that z instead */
+void or_posed_ray(int W, int H, float fov, const float cam[3], float yaw, float pitch, float sigma, int x, int y, float r1, float r2,
+                  const float *z_given, float O[3], float u[3]);
+/* MoveLightSource (realtime:1072-1090): the light turned about the y axis through the origin by angular_speed * dt */
+void or_light_orbit(const float L[3], float angular_speed, float dt, float out[3]);
+/* MoveObject (realtime:1092-1098): C + v * dt */
+void or_sphere_move(const float C[3], const float v[3], float dt, float out[3]);
 
 #ifdef __cplusplus
 }

@@ -478,7 +478,7 @@ def test_config5_7680x4320_eight_way_tiles_are_bitwise_the_full_frame(ctx, oracl
 def test_posed_camera_and_progressive_accumulation(ctx, oracle, oracle_cat, cat_golden):
     """SURVEY 8f2 (headless realtime_render.cu): posed camera {C, yaw, pitch} with the reference's ray generation and
     per-sample averaging, frame seeds WangHash(frame), accumbuffer / framenumber display.  Checked against the oracle's
-    restatement (the CUDA + GL program itself cannot run here: this row's parity is unpinned)."""
+    restatement, which tests/test_realtime_pinned.py pins to that program's own device code (tests/golden/ref_realtime.npz)."""
     upload(ctx, "cpu", cat_golden)
     W, H, spp, b = 256, 160, 2, 2
     kw = dict(rt.scenes.CPU_LAUNCHER, sigma=0.2)
@@ -651,8 +651,7 @@ def test_device_mesh_transform_and_refit(ctx, oracle, cat_golden):
 
 def test_smooth_normals(ctx, oracle, cat_golden):
     """interpolated vertex normals (get_smooth_normal, realtime_render.cu:221-245) replace the flat normal of
-    the winning triangle.  Against the oracle's restatement (parity unpinned: the reference programs that do this are
-    CUDA-only): bit-exact direct lighting, bounces within tolerance, also after a device-side transform (which moves the
+    the winning triangle.  Against the oracle's restatement (pinned to get_smooth_normal itself by tests/test_realtime_pinned.py): bit-exact direct lighting, bounces within tolerance, also after a device-side transform (which moves the
     normals the way the reference's kernel does, translation included)."""
     v = cat_golden["vertices"].astype(np.float64)
     t_obj, t_bvh = cat_golden["tri_obj_order"], cat_golden["tri_bvh_order"]

@@ -149,7 +149,7 @@ void use(Renderer &r, Scene &scene, const Sphere &s) {
 def test_light_orbit_follows_the_reference_formula():
     """rt_light_orbit: y and the intensity come back bit for bit; x and z agree with MoveLightSource's formula evaluated in binary64 within 16 * 2^-24 * radius -- a handful of
     binary32 roundings of C-library functions good to an ulp, the angle's error scaled by the radius (a numpy float32 restatement stays within 6.3 of these units over 2e5
-    lights of this range).  The reference runs the formula with CUDA's device functions: this row is unpinned."""
+    lights of this range).  (Bit for bit against MoveLightSource itself: tests/test_realtime_pinned.py.)"""
     rng = np.random.default_rng(5)
     n = 20000
     pos = rng.uniform(-100, 100, (n, 3)).astype(np.float32)
