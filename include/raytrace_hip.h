@@ -295,6 +295,12 @@ int rt_count_work(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, r
  * such a ray whose fold met a negative or non-finite operand or a colour of 2^126 and more (a statistic: their pixels are the reference's all the same; 0 in any scene
  * with finite non-negative albedos and colours below 2^126).  The rule needs any-hit: the last two are 0 unless RT_TRAVQ_QW_COUNT=1. */
 int rt_dead_channel_counts(rt_ctx *ctx, uint64_t out[4]);
+/* The first-hit cache of the default pipeline: with sigma == 0 the camera ray of a pixel does not depend on the sample, so the mesh hits of a still
+ * camera's primary rays are traced once per context and kept until the camera, the frame geometry, the row share, tri_tmin, the traversal form, the stream or the mesh
+ * changes (RT_FIRST_HIT_CACHE=0 traces them in every chain; frames are the same bit for bit).  Since the context was created: launch chains that did not enqueue
+ * their first traversal launch, chains whose first launch filled the cache, chains that were not eligible (jittered camera, batch, counting run, rt_stats_enable,
+ * another pipeline, no mesh, knob off), and key comparisons that emptied a filled cache. */
+int rt_first_hit_cache_counts(const rt_ctx *ctx, uint64_t out[4]);
 
 int rt_synchronize(rt_ctx *ctx);
 int rt_get_stats(rt_ctx *ctx, rt_stats *stats);        /* waits for the last render to finish */

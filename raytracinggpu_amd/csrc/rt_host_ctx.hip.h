@@ -72,6 +72,8 @@ struct Knobs {
                                // shadow ray (A/B, cross-check; default: with any-hit on it does not, rt_wavefront.hip.h wf_dead_channels).  Bit-exact either way
     int travq_rows = 1;        // RT_TRAVQ_ROWS=0: every wf_travq launch scans the whole queue (A/B, cross-check; default: the first launch of a chain enumerates the rows that hold continuation
                                // rays only and the last the rows that hold shadow rays only, rt_qrows.h).  Bit-exact either way
+    int first_hit_cache = 1;   // RT_FIRST_HIT_CACHE=0: every chain traces its camera rays (A/B, cross-check, and the figure of a moving camera; default: a still camera's primary mesh hits
+                               // are traced once and kept, rt_host_render.hip.h FirstHit).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
     int qw_count = 0;          // RT_TRAVQ_QW_COUNT=1: rt_count_work runs the 4-wide kernel's counting instantiation (its own step counters; the box / node counts then describe
                                // THAT kernel, not the reference's traversal)
@@ -124,6 +126,7 @@ static Knobs read_knobs() {
     if (geti("RT_TRAVQ_ANYHIT", v)) k.anyhit = v != 0;
     if (geti("RT_DEAD_CHANNELS", v)) k.dead_channels = v != 0;
     if (geti("RT_TRAVQ_ROWS", v)) k.travq_rows = v != 0;
+    if (geti("RT_FIRST_HIT_CACHE", v)) k.first_hit_cache = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;
     { const char *e = getenv("RT_CHUNK_MPX"); if (e && *e) { const double d = atof(e); if (d >= 0 && d < 1e4) k.chunk_mpx = d; } }
@@ -203,6 +206,24 @@ struct rt_ctx {
     DevBuf wfM{bufs}, wfT{bufs}, wfLS{bufs}, wfSID{bufs}, wfSamp{bufs};   // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
     DevBuf wfDCH{bufs};                                             // ... the dead-channel byte of each path (wf_dead_channels)
     unsigned long long dead_counts[4] = {};                          // of the last rt_count_work: rt_dead_channel_counts
+    // The FIRST-HIT CACHE: the traversal results of the camera rays, one word per pixel slot of each sub-frame at its pxbase.  With sigma == 0 a camera
+    // ray is a function of camera, frame geometry and pixel, and its nearest triangle of that ray, the mesh, its tree and tri_tmin: everything in FirstHit::Key.  The chain's
+    // first wf_travq launch writes wfM0 instead of wfM (a fill), the wf_advance that closes segment 0 reads it, and a chain that finds its part filled under the same key does
+    // not enqueue that launch at all (a skip).  Every field is compared as bits; mesh_gen is bumped by every entry that can change a triangle, the visit order or the tree.
+    DevBuf wfM0{bufs};
+    uint64_t mesh_gen = 0;
+    struct FirstHit {
+        struct Key {
+            uint64_t mesh_gen; const void *buf;
+            uint32_t cam[3], z, tri_tmin, basis[9];
+            int cam_mode, W, H, row0, n_rows, tile_rows, tile_step, parts, variant, travq_mode;
+            struct Part { int n_px, tiles_x, row0, n_rows, tile_step, pad; uint64_t pxbase; const void *stream; } part[8];
+        } key;
+        bool valid = false;                  // key describes what the filled parts of wfM0 hold
+        bool filled[8] = {};                 // part j's words were written by a launch enqueued under `key`, on key.part[j].stream
+        uint64_t counts[4] = {};             // chains that skipped launch 0 / filled / were ineligible; key misses after a valid fill (rt_first_hit_cache_counts)
+        FirstHit() { memset(&key, 0, sizeof(key)); }
+    } fh;
     DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
     DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum

@@ -7,6 +7,7 @@
 // Every node box recomputed for the tree in use (refit_kernel: the forest's synthetic nodes widened as build_forest makes them), the root box and the box filter's
 // scene-wide quantities fetched, the fixed-point nodes derived again.  A whole-forest pass: the quantisation grid hangs on the root box.
 static int refit_and_requantize(rt_ctx *ctx) {
+    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
     rtk::Scene &sc = ctx->scene;
     rtk::RefitArgs a{};
     a.node_lo = static_cast<float4 *>(ctx->node_lo.p); a.node_hi = static_cast<float4 *>(ctx->node_hi.p);
@@ -140,6 +141,7 @@ int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xy
 // visit range; then the whole-forest refit.
 static int transform_parts(rt_ctx *ctx, size_t first, size_t last, const float rotation[9], const float translation[3]) {
     rtk::Scene &sc = ctx->scene;
+    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
     if (sc.n_nodes <= 0 || sc.n_verts <= 0) return RT_OK;                           // no mesh, or no triangle in any leaf: nothing to move or refit
     RT_HIP(ctx, hipSetDevice(ctx->device));
     rtk::Mat3 m;
@@ -319,6 +321,7 @@ static int rebuild_lbvh_tree(rt_ctx *ctx, const int nt, int &n_nodes_out, const 
 // The render kernels' formats from the LBVH builder's arrays, on the device (rt_lbvh.hip.h, second half): what install_scene does on the
 // host for an uploaded tree.  A scene of ONE part only (the builder ran over the whole of tidx_up).  `old`: the scene in use (spheres, light, camera, albedo, mesh slot carry over).
 static int install_lbvh_device(rt_ctx *ctx, const rtk::Scene &old, const int n_nodes) {
+    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t q = own_stream(ctx);
     const rtk::LbvhArgs &a = ctx->lb_args;
@@ -440,6 +443,7 @@ extern "C++" template <class T> static std::vector<T> carry_corners(const std::v
 static int rebuild_part(rt_ctx *ctx, size_t pi, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
     const std::vector<rt_ctx::MeshPart> parts = ctx->parts;
     const rt_ctx::MeshPart P = parts[pi];
+    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
     const rtk::Scene old = ctx->scene;
     const int K = (int)parts.size();
     const bool was_valid = ctx->parts_valid;

@@ -188,6 +188,9 @@ struct WfState {
     unsigned long long *dbg;  // optional per-wave debug record (-DRT_DEBUG)
     int anyhit;               // shadow rays carry their any-hit bound (PQ_ANYHIT): the fixed-point instantiations of wf_travq stop a shadow ray at the first accepted triangle that certainly
                               // shades; a shadow ray that a sphere shades already is not traced through the mesh; a shadow ray whose segment has the direct term +0 either way is not traced
+    int m0;                   // first-hit cache (rt_host_ctx.hip.h FirstHit), set in two launches of an eligible chain and zero in every other: M is the part's block of the cache, one word per
+                              // PIXEL SLOT.  wf_advance<FIRST>: only the items of the chain's first sample are handed to the traversal; the launch that closes segment 0: the Y result of item i
+                              // is M[i - s_rel * n_px].  (The field sits in what was padding before `batch`: no kernel's argument layout moves.)
     const BatchFrame *batch;  // rt_render_device_batch: n_batch frame descriptors in device memory (item i belongs to frame i / n_px); nullptr / 0 = the launch's own camera, seed, output
     int n_batch;
     // traversal queue: the rays in TRAVERSAL-SLOT order, so that the slots a traversal workgroup owns are contiguous and one
@@ -761,7 +764,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             float t_min = y1.w;
             int win = ((F >> PQ_WIN_SHIFT) & 31) - 1, tri_win = -1;
             if (F & PF_MESHY) {
-                const unsigned long long m = st.M[i];
+                const unsigned long long m = st.M[st.m0 ? i - s_rel * st.n_px : i];   // (m0: the camera ray's result, kept per pixel slot)
                 if (m != WF_NOHIT) {
                     const float tm = __uint_as_float((unsigned int)(m >> 32));
                     const int mobj = mesh_obj_of_tri(sc, (int)(unsigned int)m);   // the meshes' own winner: minimum over (t, object position, scan rank) by the order the triangles are stored in
@@ -906,7 +909,11 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     if (emitY) {
         t_sph = h.t;
         flags |= PF_HASY | (((h.obj + 1) & 31) << PQ_WIN_SHIFT);
-        if (wf_root_test<STATS>(sc, st, i, Oy, uy, wk)) { flags |= PF_MESHY | PQ_TRAV; if (STATS) wk.trav_y++; }
+        if (wf_root_test<STATS>(sc, st, i, Oy, uy, wk)) {
+            flags |= PF_MESHY | PQ_TRAV;
+            if (FIRST && st.m0 && s_rel != 0) flags &= ~PQ_TRAV;      // the same camera ray as the first sample's item of this pixel slot: closed from its word, never fetched by the traversal
+            if (STATS) wk.trav_y++;
+        }
     }
     st.QR[2 * (size_t)qy] = make_float4(Oy.x, Oy.y, Oy.z, uy.x);    // whole sectors also when no continuation ray leaves (then nobody reads this half)
     st.QR[2 * (size_t)qy + 1] = make_float4(emitY ? uy.y : 0.f, emitY ? uy.z : 0.f, __int_as_float(flags), t_sph);   // the path's state travels with its Y slot

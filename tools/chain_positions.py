@@ -24,7 +24,7 @@ for rs in per.values():
         if "wf_advance<false, true>" in name:
             kt = ka = 0
         elif kt >= 0 and "wf_travq" in name:
-            acc["wf_travq"][kt].append(dur)
+            acc["wf_travq"][ka].append(dur)                      # the launch before wf_advance number ka: a chain that skipped its first traversal launch (first-hit cache) has none at 0
             kt += 1
         elif ka >= 0 and "wf_advance" in name:
             acc["wf_advance"][ka].append(dur)
