@@ -780,6 +780,61 @@ int rt_temporal_accumulate_fast(rt_ctx *ctx, const float *color_rgba_host, const
 int rt_history_rectify_device(rt_ctx *ctx, const void *history_dev, const void *fast_dev, const void *aov_dev, int width, int height, const rt_rectify_params *rp, void *out_history_dev, void *stream);
 int rt_history_rectify(rt_ctx *ctx, const float *history_host, const float *fast_host, const float *aov_host, int width, int height, const rt_rectify_params *rp, float *out_history_host);
 
+/* --- adaptive sampling: per-pixel sample counts, traced as a compacted list (ABI 6, additive).  rt_params.num_rays spends samples uniformly; the denoising chain
+ *     knows where a frame is bad (a pixel revealed this frame has n = 1 and a guessed variance).  These entries put samples where a caller, or a history, asks for
+ *     them, at the cost of the paths actually traced.  Nothing else reads them; DESIGN.md section 5.13 has the measurements.
+ *     rt_render_counts*: counts is width * height bytes, pixel (x, y) at counts[y * width + x]; out (and base) are whole frames of width * height float4.  With
+ *     c = counts[y * width + x]: pixel (x, y) of out holds, bit for bit and .w included, what rt_render_device writes there for the same scene and p with
+ *     p->num_rays = c -- with a pose, what rt_render_pose_device writes, its inv_n = (float)(1. / c) weighting per pixel.  (Sample s of a pixel does not depend on
+ *     num_rays, samples are independent paths, and they are added in sample order.)
+ *       With base == NULL a pixel with c == 0 is (0, 0, 0, 0).
+ *       p->num_rays is not read.  sigma, depth_convention, num_bounce, eps, tri_tmin and seed are honoured as elsewhere (segments <= 0: black).
+ *       Counts above RT_MAX_SAMPLE_COUNT are read as RT_MAX_SAMPLE_COUNT.
+ *       With base != NULL the caller promises that base is the whole frame rt_render_device / rt_render_pose_device wrote for this p, pose and scene with
+ *       num_rays = 1.  Pixels with c <= 1 are copied from it; pixels with c >= 2 trace only samples 1 .. c - 1 and start their sum from base.  The result is the
+ *       same bits as without base: a one-sample frame stores (0 + a0) / 1.  out == base is allowed: each pixel is read and written by one lane.
+ *       Whole frames only (no rt_rows).  Variant RT_VARIANT_AUTO or RT_VARIANT_WAVEFRONT_QUEUE (here AUTO always means the work-stack pipeline); any other variant,
+ *       or a tree that pipeline cannot take, returns RT_ERR_UNSUPPORTED.  Several meshes, materials, smooth normals, textured meshes and device-transformed or
+ *       rebuilt meshes render as in rt_render_device.  Not supported: batches, rt_multi_*, the async slots, progressive accumulation, rt_count_work.
+ *       The first-hit cache is neither read, filled nor invalidated: rt_first_hit_cache_counts does not move.
+ *       RT_ERR_INVALID, outputs untouched: a NULL ctx, p, counts or out; out overlapping counts; base overlapping out without being out; width or height <= 0;
+ *       2^26 pixel slots (8 x 8 tiles x 64) or more; whatever rt_render_device refuses of p.
+ *       THE ENTRY WAITS ON THE STREAM ONCE: the pixels' samples are laid out as a list by three small launches (sums per workgroup, a scan of those, the scatter),
+ *       and the host reads the list's length back (4 bytes) to size the launch chains.  Everything else is asynchronous on `stream`.  A list longer than one
+ *       chain's state may hold (RT_PATH_SAMP_MB, 2^29 paths) is cut into consecutive chains; rt_render_counts_info: of the context's last rt_render_counts* call,
+ *       out[0] samples traced, [1] launch chains, [2] pixel slots, [3] paths of the largest chain.
+ *     rt_sample_counts*: counts from a history -- elementwise over plane 1 of rt_temporal_accumulate*, (m1, m2, n, V) per pixel (history is the two-plane buffer;
+ *     plane 0 is not read).  The arithmetic is the contract: binary32, one rounding per operation, the quotient correctly rounded, min / max are IEEE minNum / maxNum:
+ *       n == 0 (a miss):  count = 1
+ *       e_n   = (n < (float)short_history) ? (float)(new_surface_samples - 1) : 0
+ *       rel   = V / (m1 m1 + lum_floor)
+ *       e_v   = floor(k_rel rel), taken as 0 unless it compares >= 1 (so a NaN gives 0)
+ *       count = 1 + min((float)(max_samples - 1), max(e_n, e_v))
+ *     A NaN n is neither a miss nor short (e_n = 0); an infinite rel asks for max_samples.  RT_ERR_INVALID, counts untouched: max_samples outside
+ *     [1, RT_MAX_SAMPLE_COUNT], new_surface_samples outside [1, max_samples], short_history < 0, a NULL pointer, width or height <= 0 or 2^28 pixels or more, counts
+ *     overlapping the history.
+ *     THE SEQUENCE per frame (SvgfSequence(adaptive=...)): render one sample -> planes -> rt_temporal_accumulate -> rt_sample_counts on the accumulated history ->
+ *     rt_render_counts with base = out = the colour frame -> rt_temporal_accumulate again, from the same previous history into the same buffer -> the filter.  The
+ *     history blends a 4-sample pixel like a 1-sample one (no per-sample weights).
+ *     rt_kat_sample_plan (test interface): the list of `counts` alone, samples [first_sample, c) of every pixel, first_sample 0 or 1.  offs_out (or NULL):
+ *     tiles_x * tiles_y * 64 + 1 offsets in pixel-slot order (8 x 8 tiles, row-major tiles, row-major inside a tile); items_out (or NULL): *n_items_out records
+ *     (x, y, sample), slot-major then sample -- the caller sizes it from its counts; span_out (or NULL): [0] the pixel slots one workgroup of the scan covers,
+ *     [1] the slots one round of the scan of workgroup sums covers. --- */
+#define RT_MAX_SAMPLE_COUNT 64
+typedef struct rt_sample_count_params {
+    int32_t max_samples;           /* 1 .. RT_MAX_SAMPLE_COUNT: no pixel gets more                                  */
+    int32_t short_history;         /* a pixel whose history is shorter than this many frames is newly revealed      */
+    int32_t new_surface_samples;   /* 1 .. max_samples: what such a pixel gets                                      */
+    float   k_rel, lum_floor;      /* extra samples per unit of relative variance V / (m1^2 + lum_floor)            */
+    int32_t reserved;
+} rt_sample_count_params;          /* 24 bytes */
+int rt_render_counts_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose /* NULL: the uploaded camera */, const uint8_t *counts_dev, const void *base_rgba_dev /* or NULL */, void *out_rgba_dev, void *stream);
+int rt_render_counts(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const uint8_t *counts_host, const float *base_rgba_host, float *out_rgba_host);
+int rt_render_counts_info(const rt_ctx *ctx, uint64_t out[4]);
+int rt_sample_counts_device(rt_ctx *ctx, const void *history_dev, int width, int height, const rt_sample_count_params *cp, uint8_t *counts_dev, void *stream);
+int rt_sample_counts(rt_ctx *ctx, const float *history_host, int width, int height, const rt_sample_count_params *cp, uint8_t *counts_host);
+int rt_kat_sample_plan(rt_ctx *ctx, const uint8_t *counts_host, int width, int height, int first_sample, uint32_t *offs_out, int32_t *items_out, uint64_t *n_items_out, int32_t span_out[2]);
+
 /* --- one host process, several devices (SURVEY 8b rt_render_multi; the reference uses the implicit device 0,
  *     optimized.cu:828-856).  The frame is cut into RT_MULTI_TILE_ROWS-row tiles, tile k -> device k mod n
  *     (interleaved); the scene is replicated; every device renders its tiles; each peer pushes them over

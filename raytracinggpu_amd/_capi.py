@@ -35,7 +35,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate",
            "rt_upsample_device", "rt_upsample",
            "rt_temporal_accumulate_fast_device", "rt_temporal_accumulate_fast", "rt_history_rectify_device", "rt_history_rectify",
-           "rt_dead_channel_counts", "rt_first_hit_cache_counts"]
+           "rt_dead_channel_counts", "rt_first_hit_cache_counts",
+           "rt_render_counts_device", "rt_render_counts", "rt_render_counts_info", "rt_sample_counts_device", "rt_sample_counts", "rt_kat_sample_plan"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -236,6 +237,23 @@ def make_rectify_params(radius=None, k_clamp=None):
     return _filled(RectifyParams(), RECTIFY_DEFAULTS, radius=radius, k_clamp=k_clamp)
 
 
+class SampleCountParams(C.Structure):
+    _fields_ = [("max_samples", C.c_int32), ("short_history", C.c_int32), ("new_surface_samples", C.c_int32), ("k_rel", C.c_float), ("lum_floor", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+MAX_SAMPLE_COUNT = 64
+# The defaults of make_sample_count_params: the row of the table of DESIGN.md section 5.13 chosen there.
+SAMPLE_COUNT_DEFAULTS = dict(max_samples=4, short_history=2, new_surface_samples=4, k_rel=0.0, lum_floor=1e-4)
+
+
+def make_sample_count_params(max_samples=None, short_history=None, new_surface_samples=None, k_rel=None, lum_floor=None):
+    """rt_sample_count_params: a pixel whose history is shorter than short_history frames gets new_surface_samples samples, any other 1 + floor(k_rel V / (m1^2 +
+    lum_floor)), none more than max_samples (1 .. MAX_SAMPLE_COUNT); None = the default of SAMPLE_COUNT_DEFAULTS."""
+    return _filled(SampleCountParams(), SAMPLE_COUNT_DEFAULTS, max_samples=max_samples, short_history=short_history, new_surface_samples=new_surface_samples,
+                   k_rel=k_rel, lum_floor=lum_floor)
+
+
 def static_motion():
     """[MAX_OBJECTS, 12] float32: the motion table in which nothing moved (rotation = identity, translation = 0); row i = object i's rotation[9] | translation[3]."""
     m = np.zeros((MAX_OBJECTS, 12), np.float32)
@@ -414,6 +432,13 @@ def load():
     L.rt_temporal_accumulate_fast.argtypes = [vp, fp3, fp3, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), C.c_int, fp3, fp3]
     L.rt_history_rectify_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(RectifyParams), vp, vp]
     L.rt_history_rectify.argtypes = [vp, fp3, fp3, fp3, C.c_int, C.c_int, C.POINTER(RectifyParams), fp3]
+    u8p = C.POINTER(C.c_uint8)
+    L.rt_render_counts_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), vp, vp, vp, vp]
+    L.rt_render_counts.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), u8p, fp3, fp3]
+    L.rt_render_counts_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rt_sample_counts_device.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(SampleCountParams), vp, vp]
+    L.rt_sample_counts.argtypes = [vp, fp3, C.c_int, C.c_int, C.POINTER(SampleCountParams), u8p]
+    L.rt_kat_sample_plan.argtypes = [vp, u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.rt_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.rt_device_alloc.argtypes = [vp, C.POINTER(vp), C.c_size_t]
     L.rt_device_free.argtypes = [vp]
@@ -1068,6 +1093,75 @@ class Context:
         opt = lambda p: C.c_void_p(p) if p else None
         self._check(self._L.rt_upsample_device(self._h, opt(low_ptr), opt(low_aov_ptr), opt(aov_ptr), int(width), int(height), C.byref(up), opt(out_ptr),
                                                C.c_void_p(stream) if stream else None))
+
+    # --- adaptive sampling: per-pixel sample counts traced as a compacted list, and counts from a history (rt_render_counts*, rt_sample_counts*)
+    @staticmethod
+    def _u8(name, a, shape):
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.uint8 or a.shape != shape:
+            raise RtError(-1, f"{name}: counts {a.shape} {a.dtype} must be a uint8 array of shape {shape}")
+        return a
+
+    def render_counts(self, params, counts, pose=None, base=None, out=None):
+        """rt_render_counts: counts [H, W] uint8 -> the frame [H, W, 4] float32 whose pixel (x, y) is that of a frame with num_rays = counts[y, x] (0: zeros; above
+        MAX_SAMPLE_COUNT: MAX_SAMPLE_COUNT).  base: the one-sample frame of the same params, pose and scene (pixels with a count <= 1 are copied from it, the others
+        trace samples 1 ..); out: optional preallocated result, which may be `base`.  params.num_rays is not read."""
+        shape = (params.height, params.width)
+        counts = self._u8("render_counts", counts, shape)
+        if base is not None:
+            base = self._f32(base, lambda s: s == shape + (4,), f"render_counts: base {np.shape(base)} must be {shape + (4,)}")
+        out = self._out("render_counts", out, shape + (4,))
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_render_counts(self._h, C.byref(params), C.byref(pose) if pose is not None else None, counts.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             base.ctypes.data_as(fp) if base is not None else None, out.ctypes.data_as(fp)))
+        return out
+
+    def render_counts_device(self, params, counts_ptr, out_ptr, pose=None, base_ptr=None, stream=None):
+        """rt_render_counts_device: device pointers (counts: H * W bytes; base_ptr == out_ptr: in place).  Waits on `stream` once (the list's length comes back to
+        the host), the rest is asynchronous."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._L.rt_render_counts_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, opt(counts_ptr), opt(base_ptr), opt(out_ptr),
+                                                    C.c_void_p(stream) if stream else None))
+
+    def render_counts_info(self):
+        """rt_render_counts_info: of the last render_counts* call -> dict(items, chains, slots, chain_paths)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._L.rt_render_counts_info(self._h, out))
+        return dict(items=int(out[0]), chains=int(out[1]), slots=int(out[2]), chain_paths=int(out[3]))
+
+    def sample_counts(self, history, params=None):
+        """rt_sample_counts: history [2, H, W, 4] of temporal_accumulate (plane 1 is read), params = make_sample_count_params(...) -> counts [H, W] uint8."""
+        history = self._f32(history, lambda s: len(s) == 4 and s[0] == 2 and s[3] == 4, f"sample_counts: history {np.shape(history)} must be [2, H, W, 4]")
+        cp = make_sample_count_params() if params is None else params
+        out = np.zeros(history.shape[1:3], np.uint8)
+        self._check(self._L.rt_sample_counts(self._h, history.ctypes.data_as(C.POINTER(C.c_float)), history.shape[2], history.shape[1], C.byref(cp),
+                                             out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def sample_counts_device(self, history_ptr, width, height, counts_ptr, params=None, stream=None):
+        """rt_sample_counts_device: device pointers (history: two planes; counts: H * W bytes), asynchronous on `stream`."""
+        cp = make_sample_count_params() if params is None else params
+        opt = lambda p: C.c_void_p(p) if p else None
+        self._check(self._L.rt_sample_counts_device(self._h, opt(history_ptr), int(width), int(height), C.byref(cp), opt(counts_ptr), C.c_void_p(stream) if stream else None))
+
+    def kat_sample_plan(self, counts, first_sample=0):
+        """rt_kat_sample_plan: counts [H, W] uint8 -> (offs [slots + 1] uint32 in pixel-slot order, items [n, 3] int32 of (x, y, sample), span (slots per workgroup,
+        slots per round of the scan of workgroup sums))."""
+        counts = np.ascontiguousarray(counts)
+        if counts.dtype != np.uint8 or counts.ndim != 2:
+            raise RtError(-1, f"kat_sample_plan: counts {counts.shape} {counts.dtype} must be a [H, W] uint8 array")
+        H, W = counts.shape
+        slots = ((W + 7) // 8) * ((H + 7) // 8) * 64
+        n_max = int(np.maximum(np.minimum(counts, MAX_SAMPLE_COUNT).astype(np.int64) - int(first_sample), 0).sum())
+        offs, items = np.zeros(slots + 1, np.uint32), np.zeros((n_max, 3), np.int32)
+        n, span = C.c_uint64(), (C.c_int32 * 2)()
+        cp = counts.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._check(self._L.rt_kat_sample_plan(self._h, cp, W, H, int(first_sample), None, None, C.byref(n), None))   # the length first: `items` is sized from the counts
+        if n.value != n_max:
+            raise RtError(-6, f"kat_sample_plan: the plan holds {n.value} items, the counts {n_max}")
+        self._check(self._L.rt_kat_sample_plan(self._h, cp, W, H, int(first_sample), offs.ctypes.data_as(C.POINTER(C.c_uint32)), items.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               C.byref(n), span))
+        return offs, items, (int(span[0]), int(span[1]))
 
     def render_pose(self, params, pose):
         """One frame with realtime_render.cu's posed camera and per-sample averaging (no accumulation)."""

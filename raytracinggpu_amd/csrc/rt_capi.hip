@@ -11,6 +11,7 @@
 #include "rt_qnodes.hip.h"
 #include "rt_bvhbuild.hip.h"
 #include "rt_lbvh.hip.h"
+#include "rt_adaptive.hip.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -368,6 +369,102 @@ int rt_render_pose_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose 
     if (int rc = call_stream(ctx, stream, q_); rc != RT_OK) return rc;
     if (!pose) return fail(ctx, RT_ERR_INVALID, "pose is NULL");
     return launch_render(ctx, p, rows, out_rgba_dev, q_, nullptr, pose);
+}
+
+// ---- adaptive sampling (rt_adaptive.hip.h; the launches: rt_host_render.hip.h) ----
+static int counts_check(rt_ctx *ctx, const rt_params *p, const void *counts, const void *base, const void *out) {
+    if (!p || !counts || !out) return fail(ctx, RT_ERR_INVALID, "params / counts / out is NULL");
+    if (p->width <= 0 || p->height <= 0) return fail(ctx, RT_ERR_INVALID, "width/height must be positive");
+    const size_t npix = (size_t)p->width * p->height;
+    if (overlaps(out, npix * sizeof(float4), counts, npix)) return fail(ctx, RT_ERR_INVALID, "the output overlaps the counts");
+    if (base && base != out && overlaps(out, npix * sizeof(float4), base, npix * sizeof(float4))) return fail(ctx, RT_ERR_INVALID, "base must be the output itself or clear of it");
+    return RT_OK;
+}
+
+int rt_render_counts_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const uint8_t *counts_dev, const void *base_rgba_dev, void *out_rgba_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = counts_check(ctx, p, counts_dev, base_rgba_dev, out_rgba_dev); rc != RT_OK) return rc;
+    hipStream_t q_;
+    if (int rc = call_stream(ctx, stream, q_); rc != RT_OK) return rc;
+    return launch_render_counts(ctx, p, pose, counts_dev, base_rgba_dev, out_rgba_dev, q_);
+}
+
+int rt_render_counts(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const uint8_t *counts_host, const float *base_rgba_host, float *out_rgba_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (int rc = counts_check(ctx, p, counts_host, base_rgba_host, out_rgba_host); rc != RT_OK) return rc;
+    const size_t npix = (size_t)p->width * p->height, frame = npix * sizeof(float4);
+    // the frame (base staged into it: the device form runs in place), then the counts
+    return staged(ctx, {{base_rgba_host, frame}, {counts_host, npix}}, 0, frame, out_rgba_host, [&](uint8_t *d) {
+        return rt_render_counts_device(ctx, p, pose, d + frame, base_rgba_host ? d : nullptr, d, nullptr);
+    });
+}
+
+int rt_render_counts_info(const rt_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
+    for (int k = 0; k < 4; ++k) out[k] = ctx->ad_info[k];
+    return RT_OK;
+}
+
+static int sample_counts_check(rt_ctx *ctx, const void *history, int width, int height, const rt_sample_count_params *cp, const void *counts) {
+    if (!history || !cp || !counts) return fail(ctx, RT_ERR_INVALID, "history / params / counts is NULL");
+    if (int rc = check_frame_size(ctx, width, height); rc != RT_OK) return rc;
+    if (cp->max_samples < 1 || cp->max_samples > RT_MAX_SAMPLE_COUNT) return fail(ctx, RT_ERR_INVALID, "max_samples %d outside [1,%d]", cp->max_samples, RT_MAX_SAMPLE_COUNT);
+    if (cp->new_surface_samples < 1 || cp->new_surface_samples > cp->max_samples)
+        return fail(ctx, RT_ERR_INVALID, "new_surface_samples %d outside [1, max_samples = %d]", cp->new_surface_samples, cp->max_samples);
+    if (cp->short_history < 0) return fail(ctx, RT_ERR_INVALID, "short_history %d < 0", cp->short_history);
+    return RT_OK;
+}
+
+int rt_sample_counts_device(rt_ctx *ctx, const void *history_dev, int width, int height, const rt_sample_count_params *cp, uint8_t *counts_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int rc = sample_counts_check(ctx, history_dev, width, height, cp, counts_dev);
+    if (rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height;
+    if (overlaps(counts_dev, npix, history_dev, 2 * npix * sizeof(float4))) return fail(ctx, RT_ERR_INVALID, "the counts overlap the history");
+    hipStream_t q;
+    if ((rc = call_stream(ctx, stream, q)) != RT_OK) return rc;
+    const rtk::SampleCountArgs a{(float)(cp->max_samples - 1), (float)cp->short_history, (float)(cp->new_surface_samples - 1), cp->k_rel, cp->lum_floor};
+    note_between(ctx, q, {{history_dev, 2 * npix * sizeof(float4)}, {counts_dev, npix}});
+    hipLaunchKernelGGL(rtk::sample_counts_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, q, static_cast<const float4 *>(history_dev) + npix, (int64_t)npix, a, counts_dev);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+int rt_sample_counts(rt_ctx *ctx, const float *history_host, int width, int height, const rt_sample_count_params *cp, uint8_t *counts_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (int rc = sample_counts_check(ctx, history_host, width, height, cp, counts_host); rc != RT_OK) return rc;
+    const size_t npix = (size_t)width * height, hist = 2 * npix * sizeof(float4);
+    return staged(ctx, {{history_host, hist}}, hist, npix, counts_host, [&](uint8_t *d) { return rt_sample_counts_device(ctx, d, width, height, cp, d + hist, nullptr); });
+}
+
+int rt_kat_sample_plan(rt_ctx *ctx, const uint8_t *counts_host, int width, int height, int first_sample, uint32_t *offs_out, int32_t *items_out, uint64_t *n_items_out,
+                       int32_t span_out[2]) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!counts_host || !n_items_out) return fail(ctx, RT_ERR_INVALID, "counts / n_items_out is NULL");
+    if (width <= 0 || height <= 0) return fail(ctx, RT_ERR_INVALID, "width/height must be positive");
+    if (first_sample < 0 || first_sample > 1) return fail(ctx, RT_ERR_INVALID, "first_sample must be 0 or 1");
+    if (span_out) { span_out[0] = rtk::kPlanBlock; span_out[1] = rtk::kPlanBlock * rtk::kPlanLevel; }
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    DevBuf dc;
+    int rc = upload(ctx, dc, counts_host, (size_t)width * height);
+    if (rc != RT_OK) return rc;
+    rtk::PlanArgs pa;
+    uint64_t total = 0;
+    if ((rc = plan_samples(ctx, static_cast<const uint8_t *>(dc.p), width, height, first_sample, true, own_stream(ctx), pa, total)) != RT_OK) return rc;
+    *n_items_out = total;
+    if (offs_out) RT_HIP(ctx, hipMemcpyAsync(offs_out, ctx->adOffs.p, ((size_t)pa.n_slots + 1) * 4, hipMemcpyDeviceToHost, own_stream(ctx)));
+    std::vector<uint32_t> rec(items_out ? total : 0);
+    if ((rc = copy_back(ctx, rec.data(), ctx->adItems.p, rec.size() * 4)) != RT_OK) return rc;
+    for (size_t k = 0; k < rec.size(); ++k) {                           // decoded: (x, y, sample)
+        const int slot = (int)(rec[k] >> rtk::kItemShift), tile = slot >> 6, q = slot & 63;
+        items_out[3 * k] = (tile % pa.tiles_x) * 8 + (q & 7);
+        items_out[3 * k + 1] = (tile / pa.tiles_x) * 8 + (q >> 3);
+        items_out[3 * k + 2] = (int32_t)(rec[k] & 63u);
+    }
+    return RT_OK;
 }
 
 int rt_progressive_reset(rt_ctx *ctx) {

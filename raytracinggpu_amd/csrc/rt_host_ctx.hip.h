@@ -236,6 +236,13 @@ struct rt_ctx {
     DevBufs<2> dnv_var{bufs};                                        // rt_denoise_var*: the variance planes between passes
     DevBuf post_io{bufs};                                           // the host forms of rt_render_aov*, rt_denoise*, rt_temporal_accumulate, rt_[de]modulate: inputs and result (staged, rt_host_post.hip.h)
     DevBuf accum{bufs};                                             // progressive mode: sum of the frames so far (float4 per pixel)
+    // rt_render_counts* (rt_adaptive.hip.h): the plan's workgroup totals and their offsets, offs[] and the item records; the list chains' own ray queue (the dense
+    // chains' queue, its zero fill and its chain numbers are never touched) and the running sums of a list cut into several chains.  The rest of a list chain's
+    // state is the dense chain's buffers (wfM, wfSamp, wfLS, wfSID, wfDCH, wfALB)
+    DevBuf adTot{bufs}, adOffs{bufs}, adItems{bufs}, adQR{bufs}, adT{bufs};
+    uint64_t ad_qf_sig = 0;                                         // layout adQR was last zeroed for
+    unsigned ad_nonce = 0;                                          // list chains started so far (WfState::nonce)
+    uint64_t ad_info[4] = {};                                       // of the last rt_render_counts*: items traced, chains, pixel slots, paths of the largest chain (rt_render_counts_info)
     int prog_frames = 0, prog_w = 0, prog_h = 0;
     uint64_t qf_sig = 0;                                            // layout the queue flags were last zeroed for
     // workgroups per CU of the kernels whose grid is sized by it (blocks_per_cu: asked once, 0 = not yet), each slot + STATS: wf_trav; wf_travq (+ 2 * (R == 32) + 4 * (R == 128));

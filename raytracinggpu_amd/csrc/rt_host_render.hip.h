@@ -864,6 +864,135 @@ int launch_render(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, void *ou
     return RT_OK;
 }
 
+// ---- adaptive sampling (rt_adaptive.hip.h): per-pixel sample counts traced as a compacted list ----
+// The plan of the counts of a width x height frame on stream q: ctx->adOffs takes the n_slots + 1 offsets and, with want_items, ctx->adItems the `total` item records.
+// The host needs the total to size the list: it reads it back between the scan and the scatter -- ONE wait on the stream.
+int plan_samples(rt_ctx *ctx, const uint8_t *counts_dev, int width, int height, int first, bool want_items, hipStream_t q, rtk::PlanArgs &pa, uint64_t &total) {
+    const int tiles_x = (width + 7) / 8;
+    const int64_t n_slots = (int64_t)tiles_x * ((height + 7) / 8) * 64;
+    if (n_slots >= rtk::kPlanMaxSlots) return fail(ctx, RT_ERR_INVALID, "image too large: %lld pixel slots (limit 2^26)", (long long)n_slots);
+    pa = rtk::PlanArgs{counts_dev, width, height, tiles_x, (int)n_slots, first};
+    const int n_blocks = (int)((n_slots + rtk::kPlanBlock - 1) / rtk::kPlanBlock);
+    int rc;
+    if ((rc = ensure(ctx, ctx->adTot, (2 * (size_t)n_blocks + 1) * 4)) != RT_OK || (rc = ensure(ctx, ctx->adOffs, ((size_t)n_slots + 1) * 4)) != RT_OK) return rc;
+    unsigned int *const tot = static_cast<unsigned int *>(ctx->adTot.p), *const off = tot + n_blocks, *const total_dev = off + n_blocks;
+    hipLaunchKernelGGL(rtk::sample_plan_totals, dim3((unsigned)n_blocks), dim3(rtk::kPlanBlock), 0, q, pa, tot);
+    hipLaunchKernelGGL(rtk::sample_plan_scan, dim3(1), dim3(rtk::kPlanLevel), 0, q, static_cast<const unsigned int *>(tot), n_blocks, off, total_dev);
+    RT_HIP(ctx, hipGetLastError());
+    unsigned int h = 0;
+    RT_HIP(ctx, hipMemcpyAsync(&h, total_dev, sizeof(h), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipStreamSynchronize(q));
+    total = h;
+    if (want_items && (rc = ensure(ctx, ctx->adItems, ((size_t)total + 64) * 4)) != RT_OK) return rc;
+    hipLaunchKernelGGL(rtk::sample_plan_scatter, dim3((unsigned)n_blocks), dim3(rtk::kPlanBlock), 0, q, pa, static_cast<const unsigned int *>(off),
+                       static_cast<const unsigned int *>(total_dev), static_cast<unsigned int *>(ctx->adOffs.p), want_items ? static_cast<unsigned int *>(ctx->adItems.p) : nullptr);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// rt_render_counts_device: the plan, then the list cut into consecutive chains at multiples of 64 items (a chain's state stays under RT_PATH_SAMP_MB and 2^29 paths, as a
+// dense chain's), each chain one sub-frame on the caller's stream -- wf_advance_list<FIRST>, (wf_travq, wf_advance_list) x (segments + 1), sample_fold.  The chains never
+// look at the first-hit cache (m0 = 0; rt_ctx::fh is not touched) and enumerate every row of their queue.  No items: no chain, and the fold still writes the frame.
+int launch_render_counts(rt_ctx *ctx, const rt_params *p_in, const rt_camera_pose *pose, const uint8_t *counts_dev, const void *base_dev, void *out_dev, hipStream_t stream) {
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    const Knobs &kn = ctx->knobs;
+    rt_params p = *p_in;
+    p.num_rays = 1;                                                   // (not read: every pixel has its own)
+    int segs = 0, rc;
+    if ((rc = check_params(ctx, &p, segs)) != RT_OK) return rc;
+    if (p.variant != RT_VARIANT_AUTO && p.variant != RT_VARIANT_WAVEFRONT_QUEUE)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "per-pixel sample counts need the work-stack wavefront pipeline (variant auto or wavefront_queue)");
+    Variant v;
+    if ((rc = resolve_variant(ctx, RT_VARIANT_WAVEFRONT_QUEUE, pose, false, v)) != RT_OK) return rc;
+    if (v.variant != RT_VARIANT_WAVEFRONT_QUEUE) return fail(ctx, RT_ERR_UNSUPPORTED, "the uploaded tree does not fit the work-stack traversal kernel");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const uint8_t *out_lo = static_cast<const uint8_t *>(out_dev);
+    const BetweenGuard between = begin_render_call(ctx->pipe, out_lo, out_lo + (size_t)p.width * p.height * sizeof(float4));   // (Pipe::valid stays false: the next frame takes the full fork)
+    const rt_rows rows{0, p.height, p.height, 1};
+    Chunk c{&p, &rows, stream, nullptr, nullptr, false, segs, segs > 0 ? segs : 1, {}, {}, nullptr};
+    make_frame(ctx, out_dev, pose, c);
+    TravPlan t;
+    if ((rc = plan_trav(ctx, v, false, kn.travq_lds, t)) != RT_OK) return rc;
+    rtk::PlanArgs pa;
+    uint64_t total = 0;
+    if ((rc = plan_samples(ctx, counts_dev, p.width, p.height, base_dev ? 1 : 0, true, stream, pa, total)) != RT_OK) return rc;
+    // the chains: equal sizes, multiples of 64
+    const int64_t per_item = 16 + 16 + 64 + 16 + 5 * (int64_t)c.nseg;
+    const int64_t cmax = std::max<int64_t>(64, std::min<int64_t>(kn.path_samp_bytes / per_item, ((int64_t)1 << 29) - 64) / 64 * 64);
+    const int64_t n_chains = ((int64_t)total + cmax - 1) / cmax;
+    const int64_t per = n_chains > 0 ? (((int64_t)total + n_chains - 1) / n_chains + 63) / 64 * 64 : 0;
+    const size_t np = (size_t)per, nseg = (size_t)c.nseg;
+    const bool tex = ctx->tex_mask != 0;
+    auto geometry = [&](int64_t n_items, rtk::WfState &st) {          // n_paths and the traversal launch's shares of one chain -> its grid
+        st = rtk::WfState{};
+        st.tiles_x = pa.tiles_x; st.tiles_x_m = rtk::wf_div_magic(pa.tiles_x);
+        st.n_paths = (int)((n_items + 63) / 64 * 64);
+        st.n_px = st.n_paths; st.n_px_m = rtk::wf_div_magic(st.n_paths);
+        return wf_geometry(kn, ctx->n_cus, t.bpc, 1, t.wpb, t.queue && !t.qlds, st);
+    };
+    size_t q_slots = 0;
+    for (const int64_t n : {std::min<int64_t>(per, (int64_t)total), (int64_t)total - (n_chains - 1) * per}) {   // the first chain's size and the last one's
+        if (n_chains == 0) break;
+        rtk::WfState st;
+        const int64_t tb = geometry(n, st);
+        q_slots = std::max(q_slots, (size_t)st.slots_per_block * (size_t)tb);
+    }
+    bool qr_grown = false;
+    if (n_chains > 0) {
+        if ((rc = ensure(ctx, ctx->wfM, 2 * np * 8)) != RT_OK || (rc = ensure(ctx, ctx->wfSamp, np * 16)) != RT_OK || (rc = ensure(ctx, ctx->wfSID, np * nseg)) != RT_OK ||
+            (rc = ensure(ctx, ctx->wfDCH, np)) != RT_OK || (rc = ensure(ctx, ctx->wfLS, np * 4 * nseg)) != RT_OK)
+            return rc;
+        if (tex && (rc = ensure(ctx, ctx->wfALB, np * 16 * nseg)) != RT_OK) return rc;
+        if (n_chains > 1 && (rc = ensure(ctx, ctx->adT, (size_t)pa.n_slots * 16)) != RT_OK) return rc;
+        const size_t had = ctx->adQR.bytes;
+        if ((rc = ensure(ctx, ctx->adQR, q_slots * 32)) != RT_OK) return rc;
+        qr_grown = ctx->adQR.bytes != had;
+    }
+    rtk::FoldArgs fa{pa, static_cast<const unsigned int *>(ctx->adOffs.p), static_cast<const float4 *>(ctx->wfSamp.p), static_cast<const float4 *>(base_dev),
+                     static_cast<float4 *>(ctx->adT.p), 0u, 0u, 1};
+    const dim3 fg((unsigned)((pa.n_slots + 255) / 256)), fb(256);
+    if (n_chains == 0) hipLaunchKernelGGL(rtk::sample_fold, fg, fb, 0, stream, c.fr, fa);
+    for (int64_t k = 0; k < n_chains; ++k) {
+        const int64_t i0 = k * per, n = std::min<int64_t>(per, (int64_t)total - i0);
+        rtk::WfState st;
+        const int64_t tblocks = geometry(n, st);
+        uint64_t sig = 0xcbf29ce484222325ull;
+        for (uint64_t x : {(uint64_t)st.n_paths, (uint64_t)st.log2S, (uint64_t)st.Q, (uint64_t)st.slots_per_block, (uint64_t)tblocks}) sig = (sig ^ x) * 0x100000001b3ull;
+        if (qr_grown || ctx->ad_qf_sig != sig) {                      // padding slots are never written by the kernels: zero once per layout (as start_chains does)
+            RT_HIP(ctx, hipMemsetAsync(ctx->adQR.p, 0, ctx->adQR.bytes, stream));
+            ctx->ad_qf_sig = sig;
+            qr_grown = false;
+        }
+        st.QR = static_cast<float4 *>(ctx->adQR.p);
+        st.M = static_cast<unsigned long long *>(ctx->wfM.p);
+        st.samp_out = static_cast<float4 *>(ctx->wfSamp.p);
+        st.LS = static_cast<float *>(ctx->wfLS.p);
+        st.SID = static_cast<unsigned char *>(ctx->wfSID.p);
+        st.DCH = static_cast<unsigned char *>(ctx->wfDCH.p);
+        st.anyhit = kn.anyhit ? 1 : 0;
+        st.deadch = (st.anyhit && kn.dead_channels) ? 1 : 0;
+        st.nonce = (int)(++ctx->ad_nonce & (unsigned)rtk::PQ_NONCE_MASK);
+        const rtk::WfList list{static_cast<const unsigned int *>(ctx->adItems.p) + i0, (int)n};
+        const dim3 pg((unsigned)((st.n_paths + kn.adv_block - 1) / kn.adv_block)), pb(kn.adv_block);
+        hipLaunchKernelGGL(rtk::wf_advance_list<true>, pg, pb, 0, stream, c.scn, c.fr, st, list);
+        for (int it = 0; it < (segs > 0 ? segs + 1 : 0); ++it) {
+            st.epoch = it;
+            if (t.have_mesh) launch_trav(t, tblocks, stream, c.scn, c.fr, st);
+            if (tex) {
+                rtk::TexScene ts = tex_scene(ctx);
+                ts.ALB = static_cast<float4 *>(ctx->wfALB.p);
+                hipLaunchKernelGGL(rtk::wf_advance_list_tex, pg, pb, 0, stream, c.scn, c.fr, st, ts, list);
+            } else {
+                hipLaunchKernelGGL(rtk::wf_advance_list<false>, pg, pb, 0, stream, c.scn, c.fr, st, list);
+            }
+        }
+        fa.i0 = (unsigned int)i0; fa.i1 = (unsigned int)(i0 + n); fa.last = k + 1 == n_chains ? 1 : 0;
+        hipLaunchKernelGGL(rtk::sample_fold, fg, fb, 0, stream, c.fr, fa);
+    }
+    RT_HIP(ctx, hipGetLastError());
+    ctx->ad_info[0] = total; ctx->ad_info[1] = (uint64_t)n_chains; ctx->ad_info[2] = (uint64_t)pa.n_slots; ctx->ad_info[3] = (uint64_t)np;
+    return RT_OK;
+}
 
 int launch_tonemap(rt_ctx *ctx, const void *rgba_dev, int64_t npix, void *rgb8_dev, hipStream_t stream) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");

@@ -673,6 +673,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 // TEX (wf_advance_tex, never FIRST): textured meshes -- the albedo of a textured diffuse hit goes to ts.ALB and the fold reads it from there.
 // ANIM (wf_advance_anim, wf_advance_tex_anim; batches only): the frame's light and sphere poses come from anim[frame] instead of the Scene -- the same device functions on
 // other operands; the other instantiations never look at `anim`.
+// LIST (wf_advance_list, wf_advance_list_tex: rt_adaptive.hip.h): the chain's items are a list of (pixel slot, sample) records instead of the grid "pixel slot x sample" --
+// pixel, sample and validity come from list.items[i]; every item writes samp_out[i]; the other instantiations never look at `list`.
 // The samples of a pixel are independent paths (the reference's loop cpu:701-712 carries nothing but the sum): a chain traces
 // several of them at once as items, each writes its colour, and path_reduce adds the colours in sample order.
 // code-object markers (labels, not instructions): tools/static_counts.py cuts the production instantiation into regions at them -- what a path pays for, region by region
@@ -681,8 +683,13 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #else
 #define ADV_MARK(name) asm volatile("rt_mark_adv_" name "_%=:" ::)
 #endif
-template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false>
-__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr) {
+struct WfList {
+    const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
+    int n;                       // items of this chain (n_paths is n rounded up to 64)
+};
+template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false>
+__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr,
+                                                const WfList &list = WfList{}) {
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
@@ -720,6 +727,12 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     if (ANIM) { L = mk(af->Lx, af->Ly, af->Lz); intensity = af->intensity; }
     wf_decode(st, fr, i - s_rel * st.n_px, px, lrow, valid);
     valid = valid && samp < fr.spp && in_batch;                       // the last chain of a frame may be short of samples
+    if (LIST) {                                                       // the item's record instead (a list chain has n_px == n_paths: s_rel is 0); its last wave may end in padding
+        const unsigned int rec = i < list.n ? list.items[i] : 0u;
+        samp = (int)(rec & 63u);
+        wf_decode(st, fr, (int)(rec >> 6), px, lrow, valid);
+        valid = valid && i < list.n;
+    }
     const int row = image_row(fr, lrow);
 
     if (FIRST) {
@@ -871,7 +884,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             }
         }
         if (STATS && !fold_sure && st.deadch && (st.DCH[i] & 8)) wk.dead_unsure++;   // a ray of this path was elided and its chain leaves what the elision was argued for
-        if (st.samp_out != nullptr) {                                 // more than one sample per pixel: path_reduce sums in sample order
+        if (st.samp_out != nullptr) {                                 // more than one sample per pixel: path_reduce (a list chain: sample_fold) sums in sample order
             st.samp_out[i] = make_float4(ans.x, ans.y, ans.z, (float)nrays);
         } else {                                                      // one sample: T = 0 + ans, out = T / n (cpu:711-713 + the framebuffer store)
             float4 t = make_float4(0, 0, 0, 0);

@@ -11,7 +11,12 @@ History, previous planes, reprojection, motion tables and cut all stay at the lo
 
 rectify = make_rectify_params(...) (off by default) keeps a fast history beside the long one (temporal_accumulate_fast_device) and clamps the accumulated history to it
 in place (history_rectify_device) before the filter, or before the upsample of pipeline B: the chain then follows a light or a shadow that moves (DESIGN.md section
-5.12).  The fast plane lives at the low resolution with the rest of the state."""
+5.12).  The fast plane lives at the low resolution with the rest of the state.
+
+adaptive = make_sample_count_params(...) (off by default; only at upsample == 1) spends more samples where the history says the frame is bad: after the accumulation
+sample_counts_device turns the accumulated history into per-pixel counts, render_counts_device adds the missing samples to the colour frame in place (base = the
+one-sample frame), and the accumulation runs again from the same previous history into the same buffer; then the chain goes on as without the option (DESIGN.md
+section 5.13).  render_counts_device waits on the stream once per frame."""
 from ._capi import FAST_HISTORY_DEFAULT, CameraPose, Params, RtError, make_reproject, make_svgf_params, make_temporal_params
 
 
@@ -22,21 +27,25 @@ class SvgfSequence:
     ctx: a Context with its scene uploaded.  svgf = make_svgf_params(...), temporal = make_temporal_params(...) (None: the defaults).  camera: the fixed camera
     (position, fov) the scene was uploaded with, for frames without a pose (None: scene_upload's default).  stream: the stream of every call (None: the context's).
     upsample, filter_at: see the module; up_k_normal, up_k_position: the upsample's weights (None: UPSAMPLE_DEFAULTS).  rectify: None, or the RectifyParams of the
-    clamp (the sequence then owns two fast planes more and swaps them); fast_history: the fast history's length limit."""
+    clamp (the sequence then owns two fast planes more and swaps them); fast_history: the fast history's length limit.  adaptive: None, or the SampleCountParams of
+    the per-pixel sample counts (the sequence then owns a plane of counts, one byte per pixel)."""
 
     def __init__(self, ctx, width, height, svgf=None, temporal=None, camera=None, stream=None, upsample=1, filter_at="low", up_k_normal=None, up_k_position=None,
-                 rectify=None, fast_history=FAST_HISTORY_DEFAULT):
+                 rectify=None, fast_history=FAST_HISTORY_DEFAULT, adaptive=None):
         self.ctx, self.width, self.height, self.stream = ctx, int(width), int(height), stream
         self.svgf = make_svgf_params() if svgf is None else svgf
         self.temporal = make_temporal_params() if temporal is None else temporal
         self.camera = camera
         self.upsample, self.filter_at, self.up_k = int(upsample), filter_at, (up_k_normal, up_k_position)
         self.rectify, self.fast_history = rectify, int(fast_history)
+        self.adaptive = adaptive
         f = self.upsample
         if f < 1 or f > 4 or filter_at not in ("low", "full"):
             raise RtError(-1, f"SvgfSequence: upsample {upsample} must be 1 .. 4 and filter_at {filter_at!r} 'low' or 'full'")
         if self.width % f or self.height % f:
             raise RtError(-1, f"SvgfSequence: {self.width} x {self.height} is no multiple of upsample {f}")
+        if adaptive is not None and f != 1:
+            raise RtError(-1, f"SvgfSequence: adaptive sampling runs at upsample == 1 only (upsample = {f})")
         if f > 1 and filter_at == "full" and self.svgf.feedback_pass >= 0:
             raise RtError(-1, "SvgfSequence: filter_at='full' filters an upsampled history, which is never fed back: feedback_pass must be -1")
         self.low_width, self.low_height = self.width // f, self.height // f
@@ -50,6 +59,8 @@ class SvgfSequence:
                 self.between = self._alloc(frame if filter_at == "low" else 2 * full)   # A: the filtered low-resolution frame; B: the upsampled history
             if rectify is not None:
                 self.fast, self.previous_fast = self._alloc(frame), self._alloc(frame)
+            if adaptive is not None:
+                self.counts = self._alloc(self.width * self.height)
         except RtError:
             self.close()
             raise
@@ -80,6 +91,18 @@ class SvgfSequence:
         c.render_aov_device(params, planes, pose=pose, stream=s)
         first = cut or not self._have_previous
         rp = None if first else make_reproject(camera=self.camera, pose=self._previous_pose, motion=motion, no_history_mask=no_history_mask)
+        self._accumulate(planes, previous, first, rp, W, H)
+        if self.adaptive is not None:                                  # more samples where the history asks for them, then the accumulation over again
+            c.sample_counts_device(self.accumulated, W, H, self.counts, params=self.adaptive, stream=s)
+            c.render_counts_device(params, self.counts, self.color, pose=pose, base_ptr=self.color, stream=s)
+            self._accumulate(planes, previous, first, rp, W, H)
+        if self.rectify is not None:
+            self.fast, self.previous_fast = self.previous_fast, self.fast
+        return self._filter(full, planes, previous, pose)
+
+    def _accumulate(self, planes, previous, first, rp, W, H):
+        """the accumulation of the colour frame into self.accumulated (and self.fast), with the clamp if the sequence has one"""
+        c, s = self.ctx, self.stream
         if self.rectify is None and first:
             c.temporal_accumulate_device(self.color, planes, None, None, W, H, self.accumulated, params=self.temporal, stream=s)
         elif self.rectify is None:
@@ -88,7 +111,10 @@ class SvgfSequence:
             c.temporal_accumulate_fast_device(self.color, planes, None if first else previous, None if first else self.history, None if first else self.previous_fast, W, H,
                                               self.accumulated, self.fast, reproject=rp, params=self.temporal, fast_history=self.fast_history, stream=s)
             c.history_rectify_device(self.accumulated, self.fast, planes, W, H, self.accumulated, params=self.rectify, stream=s)
-            self.fast, self.previous_fast = self.previous_fast, self.fast
+
+    def _filter(self, full, planes, previous, pose):
+        """the rest of the frame: the upsample's planes, the filter, the swaps"""
+        c, s, W, H, f = self.ctx, self.stream, self.low_width, self.low_height, self.upsample
         if f > 1:
             c.render_aov_device(full, self.full_planes, pose=pose, stream=s)
         if f > 1 and self.filter_at == "full":                         # B: the history goes up, the filter runs on it at full resolution

@@ -226,6 +226,18 @@ def main():
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
+    # adaptive sampling (rt_adaptive.hip.h): the LIST form of wf_advance by region, as the dense one above; the plan's three launches, the fold and the counts: whole kernels
+    mm = re.search(r"^(_ZN3rtk15wf_advance_listILb0E\w*):", asm, re.M)
+    if not mm:
+        raise SystemExit("static_counts: wf_advance_list<false> not found in the assembly")
+    res["wf_advance_list"] = advance_counts(kernel_text(asm, mm.group(1)))
+    for name, pattern in (("wf_advance_list_first", r"^(_ZN3rtk15wf_advance_listILb1E\w*):"), ("sample_plan_totals", r"^(_ZN3rtk18sample_plan_totals\w*):"),
+                          ("sample_plan_scan", r"^(_ZN3rtk16sample_plan_scan\w*):"), ("sample_plan_scatter", r"^(_ZN3rtk19sample_plan_scatter\w*):"),
+                          ("sample_fold", r"^(_ZN3rtk11sample_fold\w*):"), ("sample_counts", r"^(_ZN3rtk20sample_counts_kernel\w*):")):
+        mm = re.search(pattern, asm, re.M)
+        if not mm:
+            raise SystemExit(f"static_counts: {name} not found in the assembly")
+        res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
         json.dump(res, f, indent=1)
@@ -243,6 +255,9 @@ def main():
         res[k]["whole_kernel"][c] for k in ("upsample_1", "upsample_2") for c in ("valu", "lds", "vmem")))
     print("static_counts: accumulation with the fast history: %d / %d / %d, rectify radius 1 / 2 / 3: %d / %d / %d, %d / %d / %d, %d / %d / %d" % tuple(
         res[k]["whole_kernel"][c] for k in ("temporal_accumulate_fast", "history_rectify_1", "history_rectify_2", "history_rectify_3") for c in ("valu", "lds", "vmem")))
+    print("static_counts: wf_advance_list regions (valu / weight): " + ", ".join(f"{k} {v['valu']}/{v['valu_weight']}" for k, v in res["wf_advance_list"].items() if v))
+    print("static_counts: sample plan totals / scan / scatter, fold, counts (valu / lds / vmem): " + ", ".join(
+        "%d / %d / %d" % tuple(res[k]["whole_kernel"][c] for c in ("valu", "lds", "vmem")) for k in ("sample_plan_totals", "sample_plan_scan", "sample_plan_scatter", "sample_fold", "sample_counts")))
     t = res["wf_travq"]
     print("static_counts: wf_travq per step: BOX %d valu (weight %d) %d salu + leaf pushes %d / %d | TRI %d (%d) %d + %.0f per t-division block | round %d (%d) %d | fetch %d | retire %d | head+dispatch %d" % (
         t["box"]["valu"], t["box"]["valu_weight"], t["box"]["salu"], t["lpush"]["valu"], t["lpush2"]["valu"], t["tri"]["valu"], t["tri"]["valu_weight"], t["tri"]["salu"], t["tdiv"]["valu"],
