@@ -301,6 +301,15 @@ int rt_dead_channel_counts(rt_ctx *ctx, uint64_t out[4]);
  * their first traversal launch, chains whose first launch filled the cache, chains that were not eligible (jittered camera, batch, counting run, rt_stats_enable,
  * another pipeline, no mesh, knob off), and key comparisons that emptied a filled cache. */
 int rt_first_hit_cache_counts(const rt_ctx *ctx, uint64_t out[4]);
+/* The first-shadow cache beside it: under the same conditions the shadow ray of a pixel's FIRST segment depends on the camera ray, on what it hits
+ * and how that is shaded, on the light and on eps -- not on the sample or the seed -- so its traversal result is kept per pixel slot as well (8 bytes per pixel slot more:
+ * 16.6 MB per context at 1920x1080, allocated by the first eligible frame) and later chains hand no such ray to the traversal: every sample after the first of a frame,
+ * every frame of a still view under a still light.  Kept until the first-hit cache is emptied or the light, eps, a sphere, the object order, a material, the smooth normals,
+ * a texture or an elision knob (RT_TRAVQ_ANYHIT, RT_DEAD_CHANNELS) changes; a frame that misses traces and stores again.  RT_FIRST_SHADOW_CACHE=0 traces the rays in every
+ * chain, and so does RT_FIRST_HIT_CACHE=0 (the chain of a moving camera, launch for launch); frames are the same bit for bit.  Since the context was created: chains that
+ * read the cache, chains that filled it, chains that were not eligible (whatever makes the first-hit cache ineligible, or the knob), and key comparisons that emptied a
+ * filled cache.  rt_first_hit_cache_counts keeps its meaning: a light or sphere edit moves these counters, not those. */
+int rt_first_shadow_cache_counts(const rt_ctx *ctx, uint64_t out[4]);
 
 int rt_synchronize(rt_ctx *ctx);
 int rt_get_stats(rt_ctx *ctx, rt_stats *stats);        /* waits for the last render to finish */

@@ -110,6 +110,7 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     ctx->parts_valid = false;                                            // (the per-mesh records describe the scene this call installs, or none)
     ctx->tex_mask = 0;                                                   // a new scene is untextured, also when this call fails
+    ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
     ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
     if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(ctx, RT_ERR_INVALID, "bad sphere array");
     if (n_meshes < 0 || (n_meshes > 0 && !meshes)) return fail(ctx, RT_ERR_INVALID, "bad mesh array");
@@ -345,6 +346,12 @@ int rt_dead_channel_counts(rt_ctx *ctx, uint64_t out[4]) {
 int rt_first_hit_cache_counts(const rt_ctx *ctx, uint64_t out[4]) {
     if (!ctx || !out) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
     for (int k = 0; k < 4; ++k) out[k] = ctx->fh.counts[k];
+    return RT_OK;
+}
+
+int rt_first_shadow_cache_counts(const rt_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
+    for (int k = 0; k < 4; ++k) out[k] = ctx->fs.counts[k];
     return RT_OK;
 }
 

@@ -74,6 +74,8 @@ struct Knobs {
                                // rays only and the last the rows that hold shadow rays only, rt_qrows.h).  Bit-exact either way
     int first_hit_cache = 1;   // RT_FIRST_HIT_CACHE=0: every chain traces its camera rays (A/B, cross-check, and the figure of a moving camera; default: a still camera's primary mesh hits
                                // are traced once and kept, rt_host_render.hip.h FirstHit).  Bit-exact either way
+    int first_shadow_cache = 1; // RT_FIRST_SHADOW_CACHE=0: every chain traces the shadow rays of its first segment (A/B, cross-check, and the figure of a moving light; default: under a still
+                               // camera AND a still light, scene and shading state they are traced once and kept, rt_host_render.hip.h FirstShadow).  Off with RT_FIRST_HIT_CACHE=0.  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
     int qw_count = 0;          // RT_TRAVQ_QW_COUNT=1: rt_count_work runs the 4-wide kernel's counting instantiation (its own step counters; the box / node counts then describe
                                // THAT kernel, not the reference's traversal)
@@ -127,6 +129,7 @@ static Knobs read_knobs() {
     if (geti("RT_DEAD_CHANNELS", v)) k.dead_channels = v != 0;
     if (geti("RT_TRAVQ_ROWS", v)) k.travq_rows = v != 0;
     if (geti("RT_FIRST_HIT_CACHE", v)) k.first_hit_cache = v != 0;
+    if (geti("RT_FIRST_SHADOW_CACHE", v)) k.first_shadow_cache = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;
     { const char *e = getenv("RT_CHUNK_MPX"); if (e && *e) { const double d = atof(e); if (d >= 0 && d < 1e4) k.chunk_mpx = d; } }
@@ -220,10 +223,31 @@ struct rt_ctx {
             struct Part { int n_px, tiles_x, row0, n_rows, tile_step, pad; uint64_t pxbase; const void *stream; } part[8];
         } key;
         bool valid = false;                  // key describes what the filled parts of wfM0 hold
+        uint64_t gen = 0;                    // times the key was replaced (the first-shadow cache's key holds it: a first-hit miss empties that cache too)
         bool filled[8] = {};                 // part j's words were written by a launch enqueued under `key`, on key.part[j].stream
         uint64_t counts[4] = {};             // chains that skipped launch 0 / filled / were ineligible; key misses after a valid fill (rt_first_hit_cache_counts)
         FirstHit() { memset(&key, 0, sizeof(key)); }
     } fh;
+    // The FIRST-SHADOW CACHE: the traversal result of each pixel slot's segment-0 shadow ray, laid out like wfM0.  Under the first-hit cache's
+    // conditions that ray is a function of the camera ray (the first-hit key), of what it hits and how that is shaded (spheres, materials, normals, textures: whether a shadow
+    // ray leaves, and from where), of the light, of eps and of the elision rules in force -- everything in FirstShadow::Key, compared as bits.  What lives behind a pointer and
+    // is edited in place (normals, UVs, texels) is covered by shade_gen, bumped by every entry that writes it; mesh edits reach the key through FirstHit::gen.  The chain that
+    // fills traces the rays of its first sample's items and stores their words while it closes them; a chain that finds its part filled under the same key hands no segment-0
+    // shadow ray to the traversal.  The first-hit cache's state and counters are not touched by any of this.
+    DevBuf wfX0{bufs};
+    uint64_t shade_gen = 0;
+    struct FirstShadow {
+        struct Key {
+            uint64_t fh_gen, shade_gen; const void *buf;
+            uint32_t eps; int anyhit, deadch, tex_mask;
+            rtk::TexDesc tex[rtk::kMaxObjects];
+            rtk::Scene scn;                  // light, sphere table, object order, materials, smooth_mask, every pointer (the camera again)
+        } key;
+        bool valid = false;                  // key describes what the filled parts of wfX0 hold
+        bool filled[8] = {};                 // part j's words are written by a chain enqueued under `key`, on the stream of the first-hit key
+        uint64_t counts[4] = {};             // chains that read the cache / filled it / were ineligible; key misses after a valid fill (rt_first_shadow_cache_counts)
+        FirstShadow() { memset(&key, 0, sizeof(key)); }
+    } fs;
     DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
     DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum

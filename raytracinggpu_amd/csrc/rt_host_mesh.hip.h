@@ -86,6 +86,7 @@ static int set_part_normals(rt_ctx *ctx, rt_ctx::MeshPart &p, const float *norma
     if (int rc = gather_corners(ctx, p, "normal", nidx, index_stride, n_triangles, n_normals, vb, ni); rc != RT_OK) return rc;
     std::vector<float4> nr(ni.size());
     for (size_t i = 0; i < ni.size(); ++i) nr[i] = make_float4(normals_xyz[3 * (size_t)ni[i]], normals_xyz[3 * (size_t)ni[i] + 1], normals_xyz[3 * (size_t)ni[i] + 2], 0.f);
+    ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
     rtk::Scene &sc = ctx->scene;
     const size_t bytes = 3 * (size_t)sc.n_tris * sizeof(float4);
     if (sc.nrm == nullptr) {
@@ -106,6 +107,7 @@ int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, co
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
     if (!normals_xyz || !nidx) {                                                  // back to flat shading (every mesh)
+        ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
         ctx->scene.nrm = nullptr; ctx->scene.smooth_mask = 0;
         for (rt_ctx::MeshPart &p : ctx->parts) p.smooth = false;
         return RT_OK;
@@ -126,6 +128,7 @@ int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xy
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
     if (!normals_xyz || !nidx) {                                                    // this mesh flat again
+        ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
         rtk::Scene &sc = ctx->scene;
         p->smooth = false;
         sc.smooth_mask &= ~(1 << object_slot);

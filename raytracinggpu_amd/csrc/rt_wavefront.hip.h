@@ -200,6 +200,10 @@ struct WfState {
     unsigned char *DCH;       // [n_paths] dead channels of path i (bits 0..2) and whether one of its shadow rays was elided for them (bit 3); wf_advance<FIRST> zeroes it (deadch only)
     int deadch;               // any-hit is on and so is the dead-channel rule: a diffuse segment whose three channels are dead does not trace its shadow ray (wf_dead_channels)
     QRows win;                // wf_travq: the rows of the queue this launch enumerates (rt_qrows.h; slots_per_block is then a share of the window); all zero = every row, the slot index as it is
+    unsigned long long *X0;   // first-shadow cache (rt_host_ctx.hip.h FirstShadow): the part's block, one word per PIXEL SLOT -- what wf_travq wrote into M for the slot's segment-0 shadow ray
+    int x0;                   // ... 0 off, 1 fill, 2 read; non-zero in two wf_advance launches of an eligible chain and in no other.  The one that emits segment 0's shadow rays (m0 is
+                              // set there): a ray whose answer is cached (read), or is the first sample's ray of its pixel slot (fill, a later sample's item), gets its record without
+                              // PQ_TRAV.  The next one, which closes them: the result word is X0[slot] (read), or M of the first sample's ray, which a first-sample item also stores (fill)
 };
 
 // n / d for 0 <= n < 2^32 with m = floor(2^32 / d) from the host: the estimate mulhi(n, m) is the quotient or one below it
@@ -695,7 +699,10 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
     const float4 y1 = FIRST ? kDead : st.QR[2 * (size_t)qy + 1];      // (u.y, u.z, flag word, t of the nearest sphere) of the continuation ray in flight
     const int F = __float_as_int(y1.z);
-    if (!FIRST && !(F & PF_ALIVE)) return;                            // finished (or padding): its queue flags are already 0
+    if (!FIRST && !(F & PF_ALIVE)) {                                  // finished (or padding): its queue flags are already 0
+        if (st.x0 == 1 && !st.m0 && i < st.n_px) st.X0[i] = WF_NOHIT;  // (first-shadow fill: no word of a filled part is stale)
+        return;
+    }
     f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
     int refr_code = FIRST ? 0 : (F >> PQ_REFR_SHIFT) & 63;            // Ray::refraction_index = 1 (cpu:100)
     int d = 0, nrays = 0;
@@ -753,10 +760,16 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         // ---- (1) the shadow ray of segment d-1's hit came back: direct light or not (light_hidden) ----
         // cpu:615 compares |P' - P_adj|^2, P' = P_adj + t_min u, with |L - P_adj|^2; it is monotone in t_min (every rounding involved is),
         // so it holds iff it holds for the nearest sphere (decided when the ray was emitted: PF_XSPHERE) or for the nearest triangle
+        // first-shadow cache: in the launch that closes segment 0's shadow rays the word comes from the cache (read), or from the ray of the first sample's item of this pixel
+        // slot (fill: the ray every sample of the slot shares -- not from X0, which this launch writes).  Some accepted hit of the same ray decides as the nearest does.
+        const bool x_close0 = st.x0 != 0 && !st.m0;
+        unsigned long long xm = WF_NOHIT;
         if (F & PF_HASX) {
             bool shadowed = (F & PQ_XSPHERE) != 0;
             if (!shadowed && (F & PF_MESHX)) {
-                const unsigned long long m = st.M[rx];
+                const int first = s_rel * st.n_px;                    // (0 unless the chain traces several samples as items)
+                const unsigned long long m = !x_close0 ? st.M[rx] : st.x0 == 2 ? st.X0[i - first] : st.M[rx - first];
+                xm = m;
                 if (m != WF_NOHIT) {
                     const float4 x0 = st.QR[2 * (size_t)qx], x1 = st.QR[2 * (size_t)qx + 1];
                     const f3 Oxr = mk(x0.x, x0.y, x0.z), uxr = mk(x0.w, x1.x, x1.y);
@@ -765,6 +778,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             }
             if (shadowed) st.LS[(size_t)(d - 1) * st.n_paths + i] = 0.f;               // the l stored when the segment was shaded does not count
         }
+        if (x_close0 && st.x0 == 1 && s_rel == 0) st.X0[i] = xm;      // fill: every first-sample path, WF_NOHIT where no shadow ray of its went through the mesh
         ADV_MARK("closex_end");
         // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit ----
         if (F & PF_HASY) {
@@ -915,8 +929,10 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         if (!x_moot && (!(flags & PQ_XSPHERE) || !st.anyhit) && wf_root_test<STATS>(sc, st, rx, Ox, ux, wk)) {   // only then does anybody read the record: the traversal, and this kernel if the mesh is hit
             flags |= PF_MESHX;
             if (STATS) wk.trav_x++;
+            // first-shadow cache: the ray's answer is known (read) or is another item's (fill, a later sample) -- the record is written for the close, the traversal never fetches it
+            const int x_trav = (st.x0 != 0 && st.m0 && (st.x0 == 2 || s_rel != 0)) ? 0 : PQ_TRAV;
             st.QR[2 * (size_t)qx] = make_float4(Ox.x, Ox.y, Ox.z, ux.x);
-            st.QR[2 * (size_t)qx + 1] = make_float4(ux.y, ux.z, __int_as_float((int)((unsigned)(PQ_TRAV | (st.anyhit ? PQ_ANYHIT : 0) | (d << PF_DEPTH_SHIFT)) | (unsigned)st.nonce << PQ_NONCE_SHIFT)), x_bound);
+            st.QR[2 * (size_t)qx + 1] = make_float4(ux.y, ux.z, __int_as_float((int)((unsigned)(x_trav | (st.anyhit ? PQ_ANYHIT : 0) | (d << PF_DEPTH_SHIFT)) | (unsigned)st.nonce << PQ_NONCE_SHIFT)), x_bound);
         }
     }
     if (emitY) {
