@@ -465,6 +465,31 @@ int rt_mesh_transform_of(rt_ctx *ctx, int object_slot, const float rotation[9], 
 int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xyz, int n_normals, const int32_t *nidx, int index_stride, int n_triangles);
 int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out);
 
+/* --- deforming meshes (ABI 6, additive): new positions for every vertex of a mesh, in place -- a skinned, simulated or morphing mesh, once per frame.  n_vertices must
+ *     equal the count the mesh was uploaded with, the Vectors in the uploaded order.  Everything else stays: the triangle indices, the tree's topology and visit order
+ *     (a REFIT, not a rebuild), materials, the normals that were set, textures and UVs, the transforms applied so far (the new positions simply replace their result).
+ *     The entry then does on the device what rt_mesh_transform does after moving the vertices: the triangle records of the mesh, every box of the tree in use (a leaf's
+ *     box is compute_bbox, cpu_launcher.cpp:180-188, of its triangles; a forest's synthetic union nodes widened by one float step as an upload makes them), the
+ *     fixed-point layouts -- the layout equals, bit for bit, a fresh upload of (new vertices, same triangle order, the refitted tree), and both caches of a still view
+ *     are emptied.  The boxes are made across the whole chip (every leaf a thread, the internal nodes by a bottom-up climb in which no lane waits for another),
+ *     rt_mesh_transform's one-workgroup refit bit for bit; RT_REFIT_WIDE=0 selects that one here too.
+ *       rt_mesh_set_vertices         the scene's one mesh (RT_ERR_UNSUPPORTED on a scene of several, as rt_mesh_set_normals), xyz_host: n_vertices * 3 floats;
+ *       rt_mesh_set_vertices_of      the mesh at object_slot (= rt_mesh.object_slot at upload);
+ *       rt_mesh_set_vertices_device  positions in DEVICE memory, records stride_floats (3 or 4) floats apart, read on the context's own stream in the order of
+ *                                    the call (as rt_mesh_transform's launches are ordered: work the caller issued on ANOTHER stream is the caller's to finish
+ *                                    first); object_slot -1 = the scene's one mesh.
+ *     SMOOTH NORMALS ARE NOT RECOMPUTED: they are the caller's data, as in the reference (TriangleMesh::normals comes from the file).  A caller that deforms a
+ *     smooth mesh passes the normals of the new shape to rt_mesh_set_normals[_of] again.
+ *     The call WAITS on the context's stream once, for the refitted root box (32 bytes): it travels to the render kernels as an argument and the fixed-point grid
+ *     hangs on it -- the same wait rt_mesh_transform has.
+ *     A refit keeps the topology: after large deformations the boxes overlap more and a ray does more work, never different work's result.  Rebuild now and then
+ *     (rt_mesh_rebuild_mode(RT_BVH_LBVH)).
+ *     RT_ERR_INVALID (scene untouched): a NULL pointer, n_vertices different from the mesh's, a stride other than 3 or 4, object_slot outside the scene or a
+ *     sphere's.  A mesh without triangles: RT_OK, nothing happens.  RT_ERR_NO_SCENE: no upload, or (the _of and device forms) the last rt_scene_upload* failed. */
+int rt_mesh_set_vertices(rt_ctx *ctx, const float *xyz_host, int n_vertices);
+int rt_mesh_set_vertices_of(rt_ctx *ctx, int object_slot, const float *xyz_host, int n_vertices);
+int rt_mesh_set_vertices_device(rt_ctx *ctx, int object_slot, const void *xyz_dev, int stride_floats, int n_vertices);
+
 /* --- textured meshes (ABI 6, additive): MTL's map_Kd over OBJ's per-corner vt.  The albedo of a hit on a textured mesh is
  *     mesh albedo (.) sampled texel (Kd x map_Kd), a per-channel binary32 product with the mesh albedo first; it replaces the albedo
  *     of the fold (cpu:624, 642) and nothing else: the mesh stays diffuse, mirror or glass by its rt_mesh fields.  Every operation below

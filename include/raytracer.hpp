@@ -536,6 +536,16 @@ public:
         const float t[3] = {translation[0], translation[1], translation[2]};
         check(rt_mesh_transform_of(ctx_, mesh.id, rotation, t), "rt_mesh_transform_of");
     }
+    // A mesh that changed shape: the mesh's own `vertices` (same count and order as uploaded) replace the positions on the device; indices, tree topology, normals, UVs and
+    // textures stay, every box is refitted (rt_mesh_set_vertices[_of]).  Smooth normals are the caller's: call use_smooth_normals[_of] again with the new ones
+    void set_mesh_vertices(const TriangleMesh &mesh) {
+        const std::vector<float> v = flat_vertices_(mesh);
+        check(rt_mesh_set_vertices(ctx_, v.data(), (int)mesh.vertices.size()), "rt_mesh_set_vertices");
+    }
+    void set_mesh_vertices_of(const TriangleMesh &mesh) {
+        const std::vector<float> v = flat_vertices_(mesh);
+        check(rt_mesh_set_vertices_of(ctx_, mesh.id, v.data(), (int)mesh.vertices.size()), "rt_mesh_set_vertices_of");
+    }
     void use_smooth_normals_of(const TriangleMesh &mesh) {
         std::vector<float> n(mesh.normals.size() * 3);
         for (size_t i = 0; i < mesh.normals.size(); ++i)
@@ -705,6 +715,12 @@ private:
         DeviceBuffer &operator=(const DeviceBuffer &) = delete;
     };
     void check(int rc, const char *what) { if (rc != RT_OK) throw Error(rc, std::string(what) + ": " + rt_last_error(ctx_)); }
+    static std::vector<float> flat_vertices_(const TriangleMesh &mesh) {
+        std::vector<float> v(mesh.vertices.size() * 3);
+        for (size_t i = 0; i < mesh.vertices.size(); ++i)
+            for (int k = 0; k < 3; ++k) v[3 * i + k] = mesh.vertices[i][k];
+        return v;
+    }
     void texture_(const TriangleMesh &mesh, bool of, const uint8_t *texels, int w, int h, int channels, rt_tex_filter filter, rt_tex_wrap wrap, const float *decode) {
         for (size_t t = 0; t < mesh.indices.size(); ++t)
             if (mesh.indices[t].uvi < 0 || mesh.indices[t].uvj < 0 || mesh.indices[t].uvk < 0)

@@ -36,7 +36,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_upsample_device", "rt_upsample",
            "rt_temporal_accumulate_fast_device", "rt_temporal_accumulate_fast", "rt_history_rectify_device", "rt_history_rectify",
            "rt_dead_channel_counts", "rt_first_hit_cache_counts", "rt_first_shadow_cache_counts",
-           "rt_render_counts_device", "rt_render_counts", "rt_render_counts_info", "rt_sample_counts_device", "rt_sample_counts", "rt_kat_sample_plan"]
+           "rt_render_counts_device", "rt_render_counts", "rt_render_counts_info", "rt_sample_counts_device", "rt_sample_counts", "rt_kat_sample_plan",
+           "rt_mesh_set_vertices", "rt_mesh_set_vertices_of", "rt_mesh_set_vertices_device"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -400,6 +401,9 @@ def load():
     L.rt_mesh_transform_of.argtypes = [vp, C.c_int, fp3, fp3]
     L.rt_mesh_set_normals_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int]
     L.rt_mesh_rebuild_of.argtypes = [vp, C.c_int, C.c_int, fp3, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.rt_mesh_set_vertices.argtypes = [vp, fp3, C.c_int]
+    L.rt_mesh_set_vertices_of.argtypes = [vp, C.c_int, fp3, C.c_int]
+    L.rt_mesh_set_vertices_device.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_int]
     L.rt_mesh_set_texture.argtypes = [vp, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_mesh_set_texture_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_kat_surface.argtypes = [vp, fp3, C.c_int, C.c_float, fp3]
@@ -766,6 +770,23 @@ class Context:
             self._check(self._L.rt_mesh_transform(self._h, rp, tp))
         else:
             self._check(self._L.rt_mesh_transform_of(self._h, int(object_slot), rp, tp))
+
+    def mesh_set_vertices(self, vertices=None, object_slot=None, device_ptr=None, stride=3, n_vertices=None):
+        """A mesh that changes shape: new positions [n, 3] for every vertex, in the uploaded order (rt_mesh_set_vertices[_of]); indices, tree topology, normals, UVs and
+        textures stay and every box is refitted on the device.  Smooth normals are the caller's: pass the new ones to mesh_set_normals again.
+        device_ptr= (with n_vertices= and stride= 3 or 4 floats per record): the positions are in device memory and are read on the context's stream
+        (rt_mesh_set_vertices_device).  object_slot: the mesh at that position in Scene::objects; None = the scene's one mesh."""
+        if device_ptr is not None:
+            if vertices is not None or n_vertices is None:
+                raise ValueError("mesh_set_vertices: device_ptr= goes with n_vertices= and without an array")
+            self._check(self._L.rt_mesh_set_vertices_device(self._h, -1 if object_slot is None else int(object_slot), C.c_void_p(int(device_ptr)), int(stride), int(n_vertices)))
+            return
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        vp_ = v.ctypes.data_as(C.POINTER(C.c_float))
+        if object_slot is None:
+            self._check(self._L.rt_mesh_set_vertices(self._h, vp_, len(v)))
+        else:
+            self._check(self._L.rt_mesh_set_vertices_of(self._h, int(object_slot), vp_, len(v)))
 
     def mesh_rebuild(self, n_triangles, mode="reference", object_slot=None):
         """Device-side BVH build over the uploaded triangles and the current device vertices -> (bvh_arr10 [n_nodes, 10], order [n_triangles]).

@@ -76,6 +76,8 @@ struct Knobs {
                                // are traced once and kept, rt_host_render.hip.h FirstHit).  Bit-exact either way
     int first_shadow_cache = 1; // RT_FIRST_SHADOW_CACHE=0: every chain traces the shadow rays of its first segment (A/B, cross-check, and the figure of a moving light; default: under a still
                                // camera AND a still light, scene and shading state they are traced once and kept, rt_host_render.hip.h FirstShadow).  Off with RT_FIRST_HIT_CACHE=0.  Bit-exact either way
+    int refit_wide = 1;        // RT_REFIT_WIDE=0: rt_mesh_set_vertices* refits with the one-workgroup refit_kernel, as rt_mesh_transform does (A/B, cross-check; default: the climb across
+                               // the chip, rt_meshops.hip.h refit_up_kernel).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
     int qw_count = 0;          // RT_TRAVQ_QW_COUNT=1: rt_count_work runs the 4-wide kernel's counting instantiation (its own step counters; the box / node counts then describe
                                // THAT kernel, not the reference's traversal)
@@ -130,6 +132,7 @@ static Knobs read_knobs() {
     if (geti("RT_TRAVQ_ROWS", v)) k.travq_rows = v != 0;
     if (geti("RT_FIRST_HIT_CACHE", v)) k.first_hit_cache = v != 0;
     if (geti("RT_FIRST_SHADOW_CACHE", v)) k.first_shadow_cache = v != 0;
+    if (geti("RT_REFIT_WIDE", v)) k.refit_wide = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;
     { const char *e = getenv("RT_CHUNK_MPX"); if (e && *e) { const double d = atof(e); if (d >= 0 && d < 1e4) k.chunk_mpx = d; } }
@@ -174,6 +177,7 @@ struct rt_ctx {
     DevBuf tidx_up{bufs};                                             // the same on the device (int4 per triangle)
     DevBuf bb_idx{bufs}, bb_cnt{bufs}, bb_pa{bufs}, bb_pb{bufs}, bb_tmp{bufs}, bb_nodes_i{bufs}, bb_nodes_f{bufs}, bb_counter{bufs}, bb_lvl{bufs}, bb_size{bufs}, bb_pre{bufs}, bb_arr{bufs};   // device BVH build scratch
     DevBuf left_dev{bufs}, lvl_nodes{bufs}, lvl_off{bufs};           // tree topology for the device-side refit
+    DevBuf refit_parent{bufs}, refit_cnt{bufs};                      // the chip-wide refit of rt_mesh_set_vertices* (rt_meshops.hip.h refit_up_kernel): parent of every pre-order node, arrival counters
     DevBuf lb_pool{bufs}, lb_pool2{bufs}, perm_dev{bufs};            // LBVH builder / layout scratch (rt_lbvh.hip.h), carved pools; visit rank -> uploaded index on the device
     rtk::LbvhArgs lb_args{};                                         // the builder's arrays of the last LBVH build (valid until the next one)
     bool host_mesh_stale = false;                                    // tri_perm / up_indices describe an older layout: the device copies (perm_dev, tidx_up) are current

@@ -6,7 +6,9 @@
 
 // Every node box recomputed for the tree in use (refit_kernel: the forest's synthetic nodes widened as build_forest makes them), the root box and the box filter's
 // scene-wide quantities fetched, the fixed-point nodes derived again.  A whole-forest pass: the quantisation grid hangs on the root box.
-static int refit_and_requantize(rt_ctx *ctx) {
+// wide (rt_mesh_set_vertices* only): the boxes by the climb across the chip (rt_meshops.hip.h refit_up_kernel), bit for bit what refit_kernel makes of the same tree.
+// Either way the entry then waits on its stream for the root box (32 bytes): the box travels to the render kernels as an argument and the quantisation grid hangs on it.
+static int refit_and_requantize(rt_ctx *ctx, const bool wide = false) {
     ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
     rtk::Scene &sc = ctx->scene;
     rtk::RefitArgs a{};
@@ -18,7 +20,21 @@ static int refit_and_requantize(rt_ctx *ctx) {
     a.n_nodes = sc.n_nodes; a.n_levels = ctx->n_levels;
     a.n_syn = ctx->n_syn;
     for (int k = 0; k < ctx->n_syn; ++k) a.syn[k] = ctx->syn[k];
-    hipLaunchKernelGGL(rtk::refit_kernel, dim3(1), dim3(1024), 0, own_stream(ctx), a);
+    if (!wide) {
+        hipLaunchKernelGGL(rtk::refit_kernel, dim3(1), dim3(1024), 0, own_stream(ctx), a);
+    } else {
+        const size_t bytes = (size_t)sc.n_nodes * sizeof(int);
+        if (int rc = ensure(ctx, ctx->refit_parent, bytes); rc != RT_OK) return rc;
+        if (int rc = ensure(ctx, ctx->refit_cnt, bytes); rc != RT_OK) return rc;
+        rtk::RefitWide w{a, static_cast<int *>(ctx->refit_parent.p), static_cast<int *>(ctx->refit_cnt.p)};
+        hipStream_t q = own_stream(ctx);
+        RT_HIP(ctx, hipMemsetAsync(w.parent, 0xff, bytes, q));                      // -1: the root's parent, and that of a node no internal node names
+        RT_HIP(ctx, hipMemsetAsync(w.cnt, 0, bytes, q));
+        const dim3 gn((unsigned)((sc.n_nodes + 255) / 256)), gc((unsigned)((sc.n_nodes + 1 + 255) / 256)), blk(256);
+        hipLaunchKernelGGL(rtk::refit_parent_kernel, gn, blk, 0, q, w);
+        hipLaunchKernelGGL(rtk::refit_up_kernel, gn, blk, 0, q, w);
+        hipLaunchKernelGGL(rtk::refit_copy_kernel, gc, blk, 0, q, a);
+    }
     RT_HIP(ctx, hipGetLastError());
     // the root box travels as a kernel argument (uniform root-box pre-test): fetch the refitted one
     float4 root[2];
@@ -183,6 +199,75 @@ int rt_mesh_transform_of(rt_ctx *ctx, int object_slot, const float rotation[9], 
     if (!p) return RT_OK;                                                           // a mesh without triangles: nothing to move
     const size_t k = p - ctx->parts.data();
     return transform_parts(ctx, k, k + 1, rotation, translation);
+}
+
+// New positions for every vertex of one part (a mesh that changes shape: skinned, simulated, morphing), from the host (xyz_host: nv * 3 floats) or from device memory (xyz_dev:
+// records `stride` floats apart, read on the context's stream); then what transform_parts does after its transform_kernel: the triangle records of the part's visit range and
+// the whole-forest refit.  Indices, topology, visit order, materials, normals, UVs and textures stay.  The arguments were checked by the entries.
+static int set_part_vertices(rt_ctx *ctx, const rt_ctx::MeshPart &p, const float *xyz_host, const void *xyz_dev, int stride) {
+    rtk::Scene &sc = ctx->scene;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t q = own_stream(ctx);
+    float4 *dst = static_cast<float4 *>(ctx->verts.p) + p.voff;
+    if (xyz_host) {
+        std::vector<float4> hv((size_t)p.nv);
+        for (int i = 0; i < p.nv; ++i) hv[i] = make_float4(xyz_host[3 * (size_t)i], xyz_host[3 * (size_t)i + 1], xyz_host[3 * (size_t)i + 2], 0.f);
+        RT_HIP(ctx, hipMemcpyAsync(dst, hv.data(), hv.size() * sizeof(float4), hipMemcpyHostToDevice, q));
+        RT_HIP(ctx, hipStreamSynchronize(q));                                       // (the source lives on this stack frame)
+    } else {
+        hipLaunchKernelGGL(rtk::repack_vertices_kernel, dim3((unsigned)((p.nv + 255) / 256)), dim3(256), 0, q, static_cast<const float *>(xyz_dev), stride, dst, p.nv);
+    }
+    int vb, ve;
+    visit_range(sc, p.obj, vb, ve);
+    if (ve > vb)
+        hipLaunchKernelGGL(rtk::retri_kernel, dim3((unsigned)((ve - vb + 255) / 256)), dim3(256), 0, q,
+                           static_cast<const int4 *>(ctx->tidx.p) + vb, static_cast<const float4 *>(ctx->verts.p), static_cast<float4 *>(ctx->tri.p) + 3 * (size_t)vb, ve - vb);
+    RT_HIP(ctx, hipGetLastError());
+    return refit_and_requantize(ctx, ctx->knobs.refit_wide != 0);
+}
+
+static int set_vertices_checked(rt_ctx *ctx, const rt_ctx::MeshPart *p, const float *xyz_host, const void *xyz_dev, int stride, int n_vertices) {
+    if (!p) return RT_OK;                                                           // a mesh without triangles: never hit, no box depends on it
+    if (n_vertices != p->nv) return fail(ctx, RT_ERR_INVALID, "n_vertices %d differs from the %d vertices the mesh at object_slot %d was uploaded with", n_vertices, p->nv, p->obj);
+    return set_part_vertices(ctx, *p, xyz_host, xyz_dev, stride);
+}
+
+// the scene's one mesh, for the entries that take no slot: refused on a forest as rt_mesh_set_normals is
+static int the_one_part(rt_ctx *ctx, rt_ctx::MeshPart *&part) {
+    part = nullptr;
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (ctx->parts.size() > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "the scene holds %d meshes: name ONE TriangleMesh by its object slot (rt_mesh_set_vertices_of)", (int)ctx->parts.size());
+    if (ctx->scene.mesh_slot < 0) return fail(ctx, RT_ERR_INVALID, "the scene has no mesh");
+    if (!ctx->parts.empty()) part = &ctx->parts[0];
+    return RT_OK;
+}
+
+int rt_mesh_set_vertices(rt_ctx *ctx, const float *xyz_host, int n_vertices) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = the_one_part(ctx, p); rc != RT_OK) return rc;
+    if (!xyz_host) return fail(ctx, RT_ERR_INVALID, "xyz_host is NULL");
+    return set_vertices_checked(ctx, p, xyz_host, nullptr, 3, n_vertices);
+}
+
+int rt_mesh_set_vertices_of(rt_ctx *ctx, int object_slot, const float *xyz_host, int n_vertices) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!xyz_host) return fail(ctx, RT_ERR_INVALID, "xyz_host is NULL");
+    return set_vertices_checked(ctx, p, xyz_host, nullptr, 3, n_vertices);
+}
+
+int rt_mesh_set_vertices_device(rt_ctx *ctx, int object_slot, const void *xyz_dev, int stride_floats, int n_vertices) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = object_slot == -1 ? the_one_part(ctx, p) : find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!xyz_dev) return fail(ctx, RT_ERR_INVALID, "xyz_dev is NULL");
+    if (stride_floats != 3 && stride_floats != 4) return fail(ctx, RT_ERR_INVALID, "stride_floats %d: positions are xyz (3) or xyzw (4) records", stride_floats);
+    return set_vertices_checked(ctx, p, nullptr, xyz_dev, stride_floats, n_vertices);
 }
 
 // TriangleMesh::buildBVH on the device, bit for bit (rt_bvhbuild.hip.h): leaves the flat tree in ctx->bb_arr and the triangle order in ctx->bb_idx
