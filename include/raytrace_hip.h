@@ -310,6 +310,15 @@ int rt_first_hit_cache_counts(const rt_ctx *ctx, uint64_t out[4]);
  * read the cache, chains that filled it, chains that were not eligible (whatever makes the first-hit cache ineligible, or the knob), and key comparisons that emptied a
  * filled cache.  rt_first_hit_cache_counts keeps its meaning: a light or sphere edit moves these counters, not those. */
 int rt_first_shadow_cache_counts(const rt_ctx *ctx, uint64_t out[4]);
+/* The first-shade cache on top of it: once the first-shadow cache's key has held for two chains, the state of a pixel slot's path after its first
+ * hit is shaded and its shadow ray decided -- everything before the bounce direction, the first thing that reads the seed -- is kept as well (32 bytes per pixel slot more:
+ * 66 MB per context at 1920x1080, allocated by the first chain that fills it), and later chains open with one launch that resumes every path there, in place of the
+ * launch that sets up the camera rays and the one that closes segment 0.  It lives under the first-shadow cache's key and is emptied with it.  RT_FIRST_SHADE_CACHE=0
+ * turns it off, and so does either older knob; a scene with a textured mesh is not eligible.  Frames are the same bit for bit.  Since the context was created: chains
+ * that resumed, chains that filled the cache, chains that were not eligible (whatever makes the first-shadow cache ineligible, a textured mesh, or the knob), and
+ * replacements of the key that emptied a filled cache.  A resumed chain counts as a skip in rt_first_hit_cache_counts and rt_first_shadow_cache_counts: both keep their
+ * meaning. */
+int rt_first_shade_cache_counts(const rt_ctx *ctx, uint64_t out[4]);
 
 int rt_synchronize(rt_ctx *ctx);
 int rt_get_stats(rt_ctx *ctx, rt_stats *stats);        /* waits for the last render to finish */

@@ -35,7 +35,7 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_render_aov_surface_device", "rt_render_aov_surface", "rt_demodulate_device", "rt_demodulate", "rt_modulate_device", "rt_modulate",
            "rt_upsample_device", "rt_upsample",
            "rt_temporal_accumulate_fast_device", "rt_temporal_accumulate_fast", "rt_history_rectify_device", "rt_history_rectify",
-           "rt_dead_channel_counts", "rt_first_hit_cache_counts", "rt_first_shadow_cache_counts",
+           "rt_dead_channel_counts", "rt_first_hit_cache_counts", "rt_first_shadow_cache_counts", "rt_first_shade_cache_counts",
            "rt_render_counts_device", "rt_render_counts", "rt_render_counts_info", "rt_sample_counts_device", "rt_sample_counts", "rt_kat_sample_plan",
            "rt_mesh_set_vertices", "rt_mesh_set_vertices_of", "rt_mesh_set_vertices_device"]
 MAX_OBJECTS = 16
@@ -368,6 +368,7 @@ def load():
     L.rt_dead_channel_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_first_hit_cache_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_first_shadow_cache_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rt_first_shade_cache_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_synchronize.argtypes = [vp]
     L.rt_ctx_selfcheck.argtypes = [vp]
     L.rt_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -732,6 +733,13 @@ class Context:
         fc = (C.c_uint64 * 4)()
         self._check(self._L.rt_first_shadow_cache_counts(self._h, fc))
         return dict(zip(("skipped", "filled", "ineligible", "key_misses"), (int(v) for v in fc)))
+
+    def first_shade_cache_counts(self):
+        """rt_first_shade_cache_counts: launch chains of this context that resumed their paths at the shaded first hit (one launch in place of the camera-ray launch and the
+        close of segment 0), that filled the cache, that were not eligible, and replacements of the first-shadow cache's key that emptied a filled cache."""
+        fc = (C.c_uint64 * 4)()
+        self._check(self._L.rt_first_shade_cache_counts(self._h, fc))
+        return dict(zip(("resumed", "filled", "ineligible", "key_misses"), (int(v) for v in fc)))
 
     def set_pipelining(self, on=True):
         """rt_ctx_set_pipelining: consecutive render_device calls on one stream into alternating buffers overlap at the frame boundary."""

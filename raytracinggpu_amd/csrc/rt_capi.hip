@@ -355,6 +355,12 @@ int rt_first_shadow_cache_counts(const rt_ctx *ctx, uint64_t out[4]) {
     return RT_OK;
 }
 
+int rt_first_shade_cache_counts(const rt_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
+    for (int k = 0; k < 4; ++k) out[k] = ctx->fsh.counts[k];
+    return RT_OK;
+}
+
 int rt_camera_basis(const rt_camera_pose *pose, float bx[3], float by[3], float bz[3]) {
     if (!pose || !bx || !by || !bz) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
     camera_basis(pose->yaw, pose->pitch, bx, by, bz);

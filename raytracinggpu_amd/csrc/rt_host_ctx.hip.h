@@ -76,6 +76,9 @@ struct Knobs {
                                // are traced once and kept, rt_host_render.hip.h FirstHit).  Bit-exact either way
     int first_shadow_cache = 1; // RT_FIRST_SHADOW_CACHE=0: every chain traces the shadow rays of its first segment (A/B, cross-check, and the figure of a moving light; default: under a still
                                // camera AND a still light, scene and shading state they are traced once and kept, rt_host_render.hip.h FirstShadow).  Off with RT_FIRST_HIT_CACHE=0.  Bit-exact either way
+    int first_shade_cache = 1; // RT_FIRST_SHADE_CACHE=0: every chain of a still view opens with wf_advance<FIRST> and closes segment 0 (A/B, cross-check; default: once the first-shadow cache has held
+                               // for two chains, a path's state after its shaded first hit is kept and later chains resume from it, rt_host_render.hip.h FirstShade).  Off with either older
+                               // knob at 0, and for scenes with a textured mesh.  Bit-exact either way
     int refit_wide = 1;        // RT_REFIT_WIDE=0: rt_mesh_set_vertices* refits with the one-workgroup refit_kernel, as rt_mesh_transform does (A/B, cross-check; default: the climb across
                                // the chip, rt_meshops.hip.h refit_up_kernel).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
@@ -132,6 +135,7 @@ static Knobs read_knobs() {
     if (geti("RT_TRAVQ_ROWS", v)) k.travq_rows = v != 0;
     if (geti("RT_FIRST_HIT_CACHE", v)) k.first_hit_cache = v != 0;
     if (geti("RT_FIRST_SHADOW_CACHE", v)) k.first_shadow_cache = v != 0;
+    if (geti("RT_FIRST_SHADE_CACHE", v)) k.first_shade_cache = v != 0;
     if (geti("RT_REFIT_WIDE", v)) k.refit_wide = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;
@@ -252,6 +256,17 @@ struct rt_ctx {
         uint64_t counts[4] = {};             // chains that read the cache / filled it / were ineligible; key misses after a valid fill (rt_first_shadow_cache_counts)
         FirstShadow() { memset(&key, 0, sizeof(key)); }
     } fs;
+    // The FIRST-SHADE CACHE: one 32-byte record per pixel slot, laid out like wfM0 and wfX0 -- the slot's path after segment 0 is shaded and its
+    // shadow ray decided, before the bounce direction (rtk::WfShade).  With sigma == 0 nothing of it depends on the seed or the sample: it depends on what FirstShadow::Key
+    // compares, so the cache has no key of its own -- one flag per part, cleared whenever that key is replaced.  A chain fills it only when it READS the first-shadow
+    // cache and finds its part's records not yet stored (the key has then held for two chains: a light that moves every frame never pays for a fill); a chain that finds
+    // them stored opens with wf_advance_resume instead of wf_advance<FIRST> and the launch that closes segment 0.  Scenes with a textured mesh are not eligible.
+    DevBuf wfS0{bufs};
+    struct FirstShade {
+        const void *buf = nullptr;           // the allocation the filled parts' records live in (a new one empties the cache)
+        bool filled[8] = {};                 // part j's records are written by a chain enqueued under fs.key, on the stream of the first-hit key
+        uint64_t counts[4] = {};             // chains that resumed / filled / were ineligible; replacements of the key after a valid fill (rt_first_shade_cache_counts)
+    } fsh;
     DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
     DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum

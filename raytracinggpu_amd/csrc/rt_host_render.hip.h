@@ -430,6 +430,7 @@ struct WfCut {
     uint64_t q_sig, layout_sig;     // what the queue's zero fill / the whole state layout depend on
     bool first_hit = false;         // the chunk's chains go through the first-hit cache (first_hit_eligible; its key is settled by first_hit_begin)
     bool first_shadow = false;      // ... and through the first-shadow cache (first_hit && RT_FIRST_SHADOW_CACHE; first_shadow_begin)
+    bool first_shade = false;       // ... and through the first-shade cache (first_shadow && RT_FIRST_SHADE_CACHE && no textured mesh; the first-shadow cache's key)
 };
 // begin, (trav, advance) x 2*segments per sample; path state SoA in HBM, tile-order path index.
 // The rows are cut into `parts` independent sub-frames (interleaved tiles), each running its own kernel
@@ -532,6 +533,12 @@ void first_hit_begin(rt_ctx *ctx, const Chunk &c, const TravPlan &t, const WfCut
 // on the part's one stream, as wfM0's are -- the stream is part of the first-hit key, whose every replacement reaches this key through FirstHit::gen -- so stream order keeps a
 // reading chain behind the launch that stored its part's words, also under the relaxed start of pipelined frames (frame k + 1's chain of a part follows frame k's on that
 // part's stream).  The Scene is compared whole, as bits: a wrong miss costs a refill, a wrong hit a silently wrong frame.
+void first_shade_clear(rt_ctx *ctx) {
+    rt_ctx::FirstShade &sh = ctx->fsh;
+    bool any = false;
+    for (bool &f : sh.filled) { any = any || f; f = false; }
+    if (any) ++sh.counts[3];
+}
 void first_shadow_begin(rt_ctx *ctx, const Chunk &c, const WfCut &w) {
     rt_ctx::FirstShadow &fs = ctx->fs;
     rt_ctx::FirstShadow::Key k;
@@ -546,6 +553,7 @@ void first_shadow_begin(rt_ctx *ctx, const Chunk &c, const WfCut &w) {
     if (fs.valid) ++fs.counts[3];
     memcpy(&fs.key, &k, sizeof(k)); fs.valid = true;
     for (bool &f : fs.filled) f = false;
+    first_shade_clear(ctx);                                           // the first-shade cache lives under this key
 }
 
 // Every buffer of the chunk at its size, before anything is enqueued.  qr_grown: the traversal queue is a new allocation.
@@ -563,6 +571,14 @@ int size_wavefront(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool &qr_grown) 
     if (ctx->tex_mask != 0 && (rc = ensure(ctx, ctx->wfALB, np * 16 * nseg)) != RT_OK) return rc;   // a textured mesh: the per-segment albedo store of wf_advance_tex
     if (w.first_hit && (rc = ensure(ctx, ctx->wfM0, w.px * 8)) != RT_OK) return rc;   // allocated by the first eligible frame; a new allocation is a new key (Key::buf)
     if (w.first_shadow && (rc = ensure(ctx, ctx->wfX0, w.px * 8)) != RT_OK) return rc;   // the same for the first-shadow cache
+    // the first-shade cache's records: allocated by the first chunk one of whose chains may fill them -- the first-shadow cache holds a part's words (a chain may read them)
+    // and its key's scene is this chunk's (the full comparison is first_shadow_begin's, after the chains' streams are settled).  A light that moves every frame allocates nothing
+    if (w.first_shade && ctx->fs.valid && memcmp(&ctx->fs.key.scn, &c.scn, sizeof(c.scn)) == 0) {
+        bool any = false;
+        for (bool f : ctx->fs.filled) any = any || f;
+        if (any && (rc = ensure(ctx, ctx->wfS0, w.px * 32)) != RT_OK) return rc;
+    }
+    if (ctx->fsh.buf != ctx->wfS0.p) { first_shade_clear(ctx); ctx->fsh.buf = ctx->wfS0.p; }
     const size_t had = ctx->wfQR.bytes;
     if ((rc = ensure(ctx, ctx->wfQR, w.q_slots * 32)) != RT_OK) return rc;
     qr_grown = ctx->wfQR.bytes != had;
@@ -684,6 +700,15 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     const int x0 = !w.first_shadow ? 0 : fs.filled[j] ? 2 : 1;
     ++fs.counts[x0 == 0 ? 2 : x0 == 2 ? 0 : 1];
     if (w.first_shadow) fs.filled[j] = true;
+    // first-shade cache: 2 = this part's records were stored under that key (resume), 1 = this chain reads the first-shadow cache and stores them (fill), 0 = neither.
+    // Marked at enqueue, as fs.filled is.  A resumed chain skipped launch 0 and read no segment-0 shadow ray from the traversal: the two older counters were moved so above
+    rt_ctx::FirstShade &fsh = ctx->fsh;
+    const bool shade_ok = w.first_shade && x0 == 2 && ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32;
+    const int s0 = !shade_ok ? 0 : fsh.filled[j] ? 2 : 1;
+    if (!w.first_shade || s0 != 0) ++fsh.counts[!w.first_shade ? 2 : s0 == 2 ? 0 : 1];   // (an eligible chain that neither fills nor resumes -- the key is younger than two chains -- counts nowhere)
+    if (s0 == 1) fsh.filled[j] = true;
+    rtk::WfShade shade{};
+    if (s0 != 0) shade.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase;
     pt.st.nonce = (int)(++ctx->chain_nonce[j] & (unsigned)rtk::PQ_NONCE_MASK);
     if (c.batch) {                                                // this sub-frame's frames, at the head of its chain
         rtk::Batch bj{};
@@ -700,13 +725,21 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
         hipLaunchKernelGGL(rtk::anim_store_kernel, dim3(1), dim3(rtk::kAnimStore * rtk::kMaxSpheres), 0, q, as, pt.anim + k0);
     }
     const auto begin = counting ? rtk::wf_advance<true, true> : rtk::wf_advance<false, true>;
-    if (anim) hipLaunchKernelGGL(rtk::wf_advance_anim<true>, pg, pb, 0, q, c.scn, pt.fr, pt.st, static_cast<const rtk::AnimFrame *>(pt.anim));
+    // a resumed chain: one launch in place of wf_advance<FIRST> and the launch that closes segment 0.  Its traversal launch 1 carries continuation rays only and takes the Y
+    // window; where there is none, the resume kernel clears its items' X slots (rtk::wq_live)
+    const rtk::QRows win_y = rtk::qrows_y(pt.st.n_paths, pt.st.log2S, pt.st.Q);
+    const bool resume_win = t.queue && kn.travq_rows && win_y.rows != 0;
+    if (s0 == 2) {
+        pt.st.m0 = 0;
+        shade.kill_x = resume_win ? 0 : 1;
+        hipLaunchKernelGGL(rtk::wf_advance_resume, pg, pb, 0, q, c.scn, pt.fr, pt.st, shade);
+    } else if (anim) hipLaunchKernelGGL(rtk::wf_advance_anim<true>, pg, pb, 0, q, c.scn, pt.fr, pt.st, static_cast<const rtk::AnimFrame *>(pt.anim));
     else hipLaunchKernelGGL(begin, pg, pb, 0, q, c.scn, pt.fr, pt.st);
     pt.st.m0 = 0;
     const auto advance = counting ? rtk::wf_advance<true, false> : rtk::wf_advance<false, false>;
     const auto advance_tex = counting ? rtk::wf_advance_tex<true> : rtk::wf_advance_tex<false>;
     const bool timed = ctx->stats_on && j == 0 && s + w.chunk >= fr.spp;   // on request (rt_stats_enable): time part 0's launches of the last chain
-    for (int it = 0; it < (c.segs > 0 ? c.segs + 1 : 0); ++it) {
+    for (int it = s0 == 2 ? 1 : 0; it < (c.segs > 0 ? c.segs + 1 : 0); ++it) {
         pt.st.epoch = it;
         // (a reading chain of one segment: the second launch would trace segment 0's shadow rays and nothing else -- no record is live, it is not enqueued)
         if (t.have_mesh && !(it == 0 && fh_skip) && !(it == 1 && x0 == 2 && c.segs == 1)) {
@@ -717,8 +750,8 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
             // wf_travq's first launch can meet no shadow ray (their records carry depth >= 1, this launch looks for depth 0) and its last no continuation ray (emitted with
             // depth <= segs - 1 only): those launches enumerate the rows of the queue that hold the other kind (rt_qrows.h) -- the same grid, shares of the window
             rtk::WfState tst = pt.st;
-            if (t.queue && kn.travq_rows && (it == 0 || it == c.segs)) {
-                tst.win = it == 0 ? rtk::qrows_y(tst.n_paths, tst.log2S, tst.Q) : rtk::qrows_x(tst.n_paths, tst.log2S, tst.Q);
+            if (t.queue && kn.travq_rows && (it == 0 || it == c.segs || (it == 1 && s0 == 2))) {
+                tst.win = (it == 0 || (it == 1 && s0 == 2)) ? win_y : rtk::qrows_x(tst.n_paths, tst.log2S, tst.Q);
                 if (tst.win.rows != 0) tst.slots_per_block = rtk::qrows_share(rtk::qrows_slots(tst.win, tst.Q), pt.tblocks);
             }
             if (it == 0 && w.first_hit) tst.M = M0;              // only continuation rays of the first sample's items are live in this launch: ray index < n_px
@@ -729,7 +762,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
         if (timed) RT_HIP(ctx, hipEventRecord(ctx->ev_adv[2 * it], q));
         rtk::WfState ast = pt.st;                                 // the launch that closes segment 0 reads the camera rays' results from the cache (no shadow ray is in flight: M is read for Y alone)
         if (it == 0 && w.first_hit) { ast.M = M0; ast.m0 = 1; }
-        if (it <= 1 && x0 != 0) { ast.X0 = static_cast<unsigned long long *>(ctx->wfX0.p) + pt.pxbase; ast.x0 = x0; }   // the launch that emits segment 0's shadow rays (m0 set) and the one that closes them
+        if (it <= 1 && x0 != 0 && s0 != 2) { ast.X0 = static_cast<unsigned long long *>(ctx->wfX0.p) + pt.pxbase; ast.x0 = x0; }   // the launch that emits segment 0's shadow rays (m0 set) and the one that closes them
         if (tex) {
             rtk::TexScene ts = tex_scene(ctx);
             ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg;   // ALB[d * n_paths + i] inside the part's block, as LS
@@ -737,6 +770,8 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
             else hipLaunchKernelGGL(advance_tex, pg, pb, 0, q, c.scn, pt.fr, ast, ts);
         } else if (anim) {
             hipLaunchKernelGGL(rtk::wf_advance_anim<false>, pg, pb, 0, q, c.scn, pt.fr, ast, static_cast<const rtk::AnimFrame *>(pt.anim));
+        } else if (it == 0 && s0 == 1) {                           // ... and stores the part's first-shade records
+            hipLaunchKernelGGL(rtk::wf_advance_fill, pg, pb, 0, q, c.scn, pt.fr, ast, shade);
         } else {
             hipLaunchKernelGGL(advance, pg, pb, 0, q, c.scn, pt.fr, ast);
         }
@@ -763,6 +798,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
     if ((rc = plan_trav(ctx, v, c.work_dev != nullptr, kn.travq_lds, t)) != RT_OK || (rc = cut_wavefront(ctx, c, t, w)) != RT_OK) return rc;
     w.first_hit = first_hit_eligible(ctx, c, t);
     w.first_shadow = w.first_hit && kn.first_shadow_cache != 0;
+    w.first_shade = w.first_shadow && kn.first_shade_cache != 0 && ctx->tex_mask == 0;
     if ((rc = size_wavefront(ctx, c, w, qr_grown)) != RT_OK) return rc;
     const int parts = (int)w.pv.size();
     for (int j = 0; j < parts; ++j) {

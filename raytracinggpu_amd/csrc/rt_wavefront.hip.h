@@ -60,7 +60,9 @@ constexpr int PQ_NONCE_SHIFT = 30, PQ_NONCE_MASK = 3;        // (either slot) th
 constexpr int PQ_LIVE_MASK = (int)((unsigned)PQ_TRAV | ((unsigned)PF_DEPTH_MASK << PF_DEPTH_SHIFT) | ((unsigned)PQ_NONCE_MASK << PQ_NONCE_SHIFT));
 // the record is live for traversal launch `epoch` of the chain numbered `nonce`: one masked compare.  A stale shadow record that passes (written four chains ago at the
 // same depth into a slot nobody wrote since) costs one wasted traversal and nothing else: wf_advance reads a shadow ray's result only if ITS OWN flag word says the
-// ray went to the mesh (PF_MESHX)
+// ray went to the mesh (PF_MESHX).  A RESUMED chain (first-shade cache, wf_advance_resume) writes no depth-1 shadow record at all, so a stale one of that depth would pass
+// every fourth chain for as long as the view stands still: the chain's traversal launch 1 carries continuation rays only and enumerates the Y window (rt_qrows.h), in which
+// only the one mixed row can hold such a record; where there is no window the resume kernel writes the dead second half into its item's X slot (WfShade::kill_x)
 __device__ __forceinline__ bool wq_live(int w0, int epoch, int nonce) {
     return (w0 & PQ_LIVE_MASK) == (int)((unsigned)PQ_TRAV | (unsigned)epoch << PF_DEPTH_SHIFT | (unsigned)nonce << PQ_NONCE_SHIFT);
 }
@@ -691,20 +693,57 @@ struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
     int n;                       // items of this chain (n_paths is n rounded up to 64)
 };
-template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false>
+// The FIRST-SHADE cache (rt_host_ctx.hip.h FirstShade; wf_advance_fill, wf_advance_resume): one 32-byte record per PIXEL SLOT, the part's block -- the slot's path after
+// segment 0 is shaded and its shadow ray decided, before the bounce direction (the first thing that reads the sample's key).  rec[2 k] = (origin of the continuation ray:
+// P_adjusted of a diffuse hit, the mirrored / refracted origin otherwise; V.x), rec[2 k + 1] = (V.y, V.z, l0, word): V the normal of a diffuse hit, the continuation
+// direction of a specular one; l0 the FINAL direct term of segment 0 (lvis, or +0 where a sphere or the mesh shades it; a moot or elided ray keeps lvis, as LS does);
+// word = kind | SID byte << 8 | refr_code << 16 | DCH byte after segment 0 << 22 | rays counted so far (the continuation ray not among them) << 26.
+constexpr int kShadeMiss = 0, kShadeDiffuse = 1, kShadeSpecular = 2;
+constexpr int SH_SID_SHIFT = 8, SH_REFR_SHIFT = 16, SH_DCH_SHIFT = 22, SH_RAYS_SHIFT = 26;
+struct WfShade {
+    float4 *rec;                 // [2 n_px]
+    int kill_x;                  // (resume) the chain's traversal launch 1 scans shadow rows: every item writes the dead second half into its X slot (see wq_live)
+};
+__device__ __forceinline__ void wf_shade_store(const WfShade &sh, int slot, int kind, f3 O, f3 V, float l0, int sid, int refr_code, int dch, int nrays) {
+    const int word = kind | (sid << SH_SID_SHIFT) | (refr_code << SH_REFR_SHIFT) | (dch << SH_DCH_SHIFT) | (int)((unsigned)nrays << SH_RAYS_SHIFT);
+    sh.rec[2 * (size_t)slot] = make_float4(O.x, O.y, O.z, V.x);
+    sh.rec[2 * (size_t)slot + 1] = make_float4(V.y, V.z, l0, __int_as_float(word));
+}
+// Whether the shadow ray of a path with flag word F is blocked (cpu:615): by a sphere (decided at emission: PQ_XSPHERE), or by the triangle of its traversal word.  The close
+// of the X query and the first-shade fill both decide through this one function: load_m() is the ray's word (read only if the ray went to the mesh), load_ray(O, u) the ray;
+// xm: the word if it was read.
+template <class LoadM, class LoadRay>
+__device__ __forceinline__ bool wf_x_shadowed(int F, f3 L, LoadM load_m, LoadRay load_ray, unsigned long long &xm) {
+    bool shadowed = (F & PQ_XSPHERE) != 0;
+    if (!shadowed && (F & PF_MESHX)) {
+        const unsigned long long m = load_m();
+        xm = m;
+        if (m != WF_NOHIT) {
+            f3 Oxr, uxr;
+            load_ray(Oxr, uxr);
+            shadowed = light_hidden(Oxr, uxr, __uint_as_float((unsigned int)(m >> 32)), L);   // (Ox is P_adjusted)
+        }
+    }
+    return shadowed;
+}
+// SHADE 1 (wf_advance_fill): the launch that emits segment 0's shadow rays in a chain that READS the first-shadow cache also stores the first-shade records of its
+// first-sample items.  SHADE 2 (wf_advance_resume): the launch that opens a chain whose part's records are stored -- in place of wf_advance<FIRST> and the launch that closes
+// segment 0.  The other instantiations never look at `sh`.
+template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr,
-                                                const WfList &list = WfList{}) {
+                                                const WfList &list = WfList{}, const WfShade &sh = WfShade{}) {
+    constexpr bool FILL = SHADE == 1, RESUME = SHADE == 2;
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
-    const float4 y1 = FIRST ? kDead : st.QR[2 * (size_t)qy + 1];      // (u.y, u.z, flag word, t of the nearest sphere) of the continuation ray in flight
+    const float4 y1 = (FIRST || RESUME) ? kDead : st.QR[2 * (size_t)qy + 1];      // (u.y, u.z, flag word, t of the nearest sphere) of the continuation ray in flight
     const int F = __float_as_int(y1.z);
-    if (!FIRST && !(F & PF_ALIVE)) {                                  // finished (or padding): its queue flags are already 0
+    if (!FIRST && !RESUME && !(F & PF_ALIVE)) {                                  // finished (or padding): its queue flags are already 0
         if (st.x0 == 1 && !st.m0 && i < st.n_px) st.X0[i] = WF_NOHIT;  // (first-shadow fill: no word of a filled part is stale)
         return;
     }
     f3 L = mk(sc.Lx, sc.Ly, sc.Lz);
-    int refr_code = FIRST ? 0 : (F >> PQ_REFR_SHIFT) & 63;            // Ray::refraction_index = 1 (cpu:100)
+    int refr_code = (FIRST || RESUME) ? 0 : (F >> PQ_REFR_SHIFT) & 63;            // Ray::refraction_index = 1 (cpu:100)
     int d = 0, nrays = 0;
     bool emitY = false, emitX = false, finished = false;
     float x_bound = -__builtin_inff();                                // any-hit bound of the shadow ray (wf_anyhit_bound)
@@ -741,6 +780,16 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         valid = valid && i < list.n;
     }
     const int row = image_row(fr, lrow);
+    // (FILL) what the slot's record holds, gathered while segment 0 is shaded; (RESUME) the record
+    f3 shO = mk(0, 0, 0), shV = mk(0, 0, 1);
+    float sh_l = 0.f;
+    int sh_kind = kShadeMiss, sh_sid = 0xff, sh_dch = 0, sh_rays = 0;
+    float4 ra = kDead, rb = kDead;
+    if (RESUME) {
+        if (!valid) { st.QR[2 * (size_t)qy + 1] = kDead; return; }       // as wf_advance<FIRST> leaves a pixel slot outside the frame
+        if (sh.kill_x) st.QR[2 * (size_t)qx + 1] = kDead;
+        ra = sh.rec[2 * (size_t)(i - s_rel * st.n_px)]; rb = sh.rec[2 * (size_t)(i - s_rel * st.n_px) + 1];
+    }
 
     if (FIRST) {
         if (!valid) { st.QR[2 * (size_t)qy + 1] = kDead; return; }       // (the X slot of a pixel outside the frame is never written: zero from the layout's memset)
@@ -757,6 +806,13 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         ADV_MARK("closex_begin");
         d = (F >> PF_DEPTH_SHIFT) & PF_DEPTH_MASK;                    // segment of the continuation ray in flight
         nrays = (F >> PF_RAYS_SHIFT) & PF_RAYS_MASK;
+        if (RESUME) {                                                 // segment 0 is shaded and its shadow ray decided: the record's state
+            const int rw = __float_as_int(rb.w);
+            sh_kind = rw & 3;
+            nrays = (int)((unsigned)rw >> SH_RAYS_SHIFT);
+            refr_code = (rw >> SH_REFR_SHIFT) & 63;
+            if (st.deadch) st.DCH[i] = (unsigned char)((rw >> SH_DCH_SHIFT) & 15);
+        }
         // ---- (1) the shadow ray of segment d-1's hit came back: direct light or not (light_hidden) ----
         // cpu:615 compares |P' - P_adj|^2, P' = P_adj + t_min u, with |L - P_adj|^2; it is monotone in t_min (every rounding involved is),
         // so it holds iff it holds for the nearest sphere (decided when the ray was emitted: PF_XSPHERE) or for the nearest triangle
@@ -764,33 +820,30 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         // slot (fill: the ray every sample of the slot shares -- not from X0, which this launch writes).  Some accepted hit of the same ray decides as the nearest does.
         const bool x_close0 = st.x0 != 0 && !st.m0;
         unsigned long long xm = WF_NOHIT;
-        if (F & PF_HASX) {
-            bool shadowed = (F & PQ_XSPHERE) != 0;
-            if (!shadowed && (F & PF_MESHX)) {
+        if (!RESUME && (F & PF_HASX)) {
+            const bool shadowed = wf_x_shadowed(F, L, [&] {
                 const int first = s_rel * st.n_px;                    // (0 unless the chain traces several samples as items)
-                const unsigned long long m = !x_close0 ? st.M[rx] : st.x0 == 2 ? st.X0[i - first] : st.M[rx - first];
-                xm = m;
-                if (m != WF_NOHIT) {
-                    const float4 x0 = st.QR[2 * (size_t)qx], x1 = st.QR[2 * (size_t)qx + 1];
-                    const f3 Oxr = mk(x0.x, x0.y, x0.z), uxr = mk(x0.w, x1.x, x1.y);
-                    shadowed = light_hidden(Oxr, uxr, __uint_as_float((unsigned int)(m >> 32)), L);   // (Ox is P_adjusted)
-                }
-            }
+                return !x_close0 ? st.M[rx] : st.x0 == 2 ? st.X0[i - first] : st.M[rx - first];
+            }, [&](f3 &Oxr, f3 &uxr) {
+                const float4 x0 = st.QR[2 * (size_t)qx], x1 = st.QR[2 * (size_t)qx + 1];
+                Oxr = mk(x0.x, x0.y, x0.z); uxr = mk(x0.w, x1.x, x1.y);
+            }, xm);
             if (shadowed) st.LS[(size_t)(d - 1) * st.n_paths + i] = 0.f;               // the l stored when the segment was shaded does not count
         }
-        if (x_close0 && st.x0 == 1 && s_rel == 0) st.X0[i] = xm;      // fill: every first-sample path, WF_NOHIT where no shadow ray of its went through the mesh
+        if (!RESUME && x_close0 && st.x0 == 1 && s_rel == 0) st.X0[i] = xm;      // fill: every first-sample path, WF_NOHIT where no shadow ray of its went through the mesh
         ADV_MARK("closex_end");
         // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit ----
-        if (F & PF_HASY) {
+        if (RESUME || (F & PF_HASY)) {
             ADV_MARK("closey_begin");
-            const float4 r0 = st.QR[2 * (size_t)qy];
-            f3 O = mk(r0.x, r0.y, r0.z), u = mk(r0.w, y1.x, y1.y);
+            const float4 r0 = RESUME ? ra : st.QR[2 * (size_t)qy];
+            f3 O = mk(r0.x, r0.y, r0.z), u = RESUME ? mk(ra.w, rb.x, rb.y) : mk(r0.w, y1.x, y1.y);   // (RESUME: the continuation ray of a specular hit; P_adjusted and N of a diffuse one)
             int sid = 0xff;                                           // object id if the hit is diffuse
             // Scene::intersect_all's running minimum (strict '<' in object order, cpu:554) = the lexicographic minimum over (t, position in Scene::objects):
             // the spheres' own winner was decided at emission (spheres_near2), the meshes' by the traversal; between the two a tie goes to the earlier object
             float t_min = y1.w;
             int win = ((F >> PQ_WIN_SHIFT) & 31) - 1, tri_win = -1;
-            if (F & PF_MESHY) {
+            if (RESUME) win = sh_kind == kShadeMiss ? -1 : 0;         // (which object: the record's SID says, to the fold)
+            if (!RESUME && (F & PF_MESHY)) {
                 const unsigned long long m = st.M[st.m0 ? i - s_rel * st.n_px : i];   // (m0: the camera ray's result, kept per pixel slot)
                 if (m != WF_NOHIT) {
                     const float tm = __uint_as_float((unsigned int)(m >> 32));
@@ -803,15 +856,18 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 Bary bary{0.f, 0.f, 0.f};                             // (TEX) the smooth normal's barycentrics, shared with the texture lookup
                 bool have_bary = false;
                 f3 N;
-                if (ANIM && tri_win < 0) { const float4 c = af->ctr[win]; N = normalize(P - mk(c.x, c.y, c.z)); }   // sphere_normal (cpu:524-525) about this frame's centre
+                if (RESUME) N = u;
+                else if (ANIM && tri_win < 0) { const float4 c = af->ctr[win]; N = normalize(P - mk(c.x, c.y, c.z)); }   // sphere_normal (cpu:524-525) about this frame's centre
                 else N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
                 const Material m = material_of(sc, win);
                 ADV_MARK("closey_end");
                 bool cont = false;                                    // a continuation ray of segment d+1 was built in (O,u)
-                if (m.mirror) {
+                if (!RESUME && m.mirror) {
                     mirror_step(fr.eps, P, N, O, u);
                     cont = true;
-                } else if (m.n_in != m.n_out) {
+                } else if (RESUME && sh_kind == kShadeSpecular) {     // the record's ray (O, u) and refr_code are the continuation's
+                    cont = true;
+                } else if (!RESUME && m.n_in != m.n_out) {
                     float refr = 1.f;                                 // the ray's index: 1, or the n_in / n_out of the surface it last crossed
                     if (refr_code != 0) { const Material mr = material_of(sc, (refr_code >> 1) - 1); refr = (refr_code & 1) ? mr.n_out : mr.n_in; }
                     const Refraction r = refract_step(m, refr, fr.eps, P, N, O, u);
@@ -819,41 +875,48 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     cont = true;
                 } else {                                              // diffuse
                     ADV_MARK("diffuse_begin");
-                    const f3 Pa = P + fr.eps * N;
-                    float nl;
-                    Ox = Pa; ux = shadow_dir(L, Pa, nl);                // the shadow ray of segment d
-                    x_bound = wf_anyhit_bound(Pa, nl);
-                    nrays += 1;
-                    // the segment's direct term if the light turns out to be visible; kept until the shadow ray is back
-                    const float lvis = ANIM ? direct_term(intensity, L, P, N) : direct_term(sc, L, P, N);
-                    st.LS[(size_t)d * st.n_paths + i] = lvis;
-                    // A surface that faces away from the light (mx = 0) has the direct term +0 whether the light is visible or not: shaded, cpu:616 stores the literal 0; lit,
-                    // cpu:623 computes l = +0 -- the same 32 bits (a NaN or a -0 from a degenerate light is not +0 and keeps its ray).  The reference still calls intersect_all
-                    // for it (the ray is counted), but nothing of its answer can reach the pixel: with any-hit on the ray is neither set up nor traced.  These are the shadow
-                    // rays that start on the mesh's far side and run through its whole body: 4.7 % of a headline frame's traversal work.
-                    // (The path still spends a launch on the ray -- PF_HASX without PF_MESHX, closed as a ray that missed the mesh -- so that it finishes in the launch it always
-                    // finished in: folding a launch early costs the uniform kernel more than the traversal saves.)
-                    emitX = true;
-                    x_moot = st.anyhit && __float_as_uint(lvis) == 0u;
-                    sid = win;
-                    f3 alb = mk(m.ar, m.ag, m.ab);                    // the albedo the fold will use
-                    if (TEX && tri_win >= 0 && ((ts.mask >> win) & 1)) {   // a textured mesh: this segment's albedo, evaluated once, for the fold
-                        if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
-                        float2 uv;
-                        alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
-                        ts.ALB[(size_t)d * st.n_paths + i] = make_float4(alb.x, alb.y, alb.z, 0.f);
-                        sid = kSidTextured;
-                    }
-                    // Every channel dead, this segment's albedo counted: lvis or +0, the pixel is the same (wf_dead_channels) -- moot for a second reason
-                    if (st.deadch) {
-                        const int was = st.DCH[i];
-                        int now = (was & 8) | wf_dead_channels(was & 7, alb, lvis);
-                        if ((now & 7) == 7 && !x_moot) {
-                            x_moot = true;
-                            now |= 8;
-                            if (STATS) wk.dead_elided++;
+                    const f3 Pa = RESUME ? O : P + fr.eps * N;
+                    if (RESUME) {
+                        st.LS[i] = rb.z;                              // final: no shadow ray of segment 0 is in flight
+                        sid = (__float_as_int(rb.w) >> SH_SID_SHIFT) & 255;
+                    } else {
+                        float nl;
+                        Ox = Pa; ux = shadow_dir(L, Pa, nl);                // the shadow ray of segment d
+                        x_bound = wf_anyhit_bound(Pa, nl);
+                        nrays += 1;
+                        // the segment's direct term if the light turns out to be visible; kept until the shadow ray is back
+                        const float lvis = ANIM ? direct_term(intensity, L, P, N) : direct_term(sc, L, P, N);
+                        st.LS[(size_t)d * st.n_paths + i] = lvis;
+                        // A surface that faces away from the light (mx = 0) has the direct term +0 whether the light is visible or not: shaded, cpu:616 stores the literal 0; lit,
+                        // cpu:623 computes l = +0 -- the same 32 bits (a NaN or a -0 from a degenerate light is not +0 and keeps its ray).  The reference still calls intersect_all
+                        // for it (the ray is counted), but nothing of its answer can reach the pixel: with any-hit on the ray is neither set up nor traced.  These are the shadow
+                        // rays that start on the mesh's far side and run through its whole body: 4.7 % of a headline frame's traversal work.
+                        // (The path still spends a launch on the ray -- PF_HASX without PF_MESHX, closed as a ray that missed the mesh -- so that it finishes in the launch it always
+                        // finished in: folding a launch early costs the uniform kernel more than the traversal saves.)
+                        emitX = true;
+                        x_moot = st.anyhit && __float_as_uint(lvis) == 0u;
+                        sid = win;
+                        f3 alb = mk(m.ar, m.ag, m.ab);                    // the albedo the fold will use
+                        if (TEX && tri_win >= 0 && ((ts.mask >> win) & 1)) {   // a textured mesh: this segment's albedo, evaluated once, for the fold
+                            if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
+                            float2 uv;
+                            alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
+                            ts.ALB[(size_t)d * st.n_paths + i] = make_float4(alb.x, alb.y, alb.z, 0.f);
+                            sid = kSidTextured;
                         }
-                        if (now != was) st.DCH[i] = (unsigned char)now;
+                        // Every channel dead, this segment's albedo counted: lvis or +0, the pixel is the same (wf_dead_channels) -- moot for a second reason
+                        if (st.deadch) {
+                            const int was = st.DCH[i];
+                            int now = (was & 8) | wf_dead_channels(was & 7, alb, lvis);
+                            if ((now & 7) == 7 && !x_moot) {
+                                x_moot = true;
+                                now |= 8;
+                                if (STATS) wk.dead_elided++;
+                            }
+                            if (now != was) st.DCH[i] = (unsigned char)now;
+                            if (FILL) sh_dch = now;
+                        }
+                        if (FILL) { shO = Pa; shV = N; sh_l = lvis; sh_kind = kShadeDiffuse; sh_sid = sid; }
                     }
                     ADV_MARK("diffuse_end");
                     if (d + 1 < fr.segs) {                            // the bounce ray: needs the sample's key and N only
@@ -865,6 +928,8 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         ADV_MARK("bounce_end");
                     }
                 }
+                if (FILL && sid == 0xff) { shO = O; shV = u; sh_kind = kShadeSpecular; }   // mirror or glass: the continuation ray
+                if (FILL) sh_rays = nrays;
                 if (cont && d + 1 < fr.segs) {
                     emitY = true; Oy = O; uy = u;                     // continuation ray of segment d+1
                     nrays += 1;
@@ -878,6 +943,8 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
 
     if (finished) {   // nothing in flight: fold the path back to front, accumulate the sample (cpu:711)
         ADV_MARK("fold_begin");
+        if (FILL && s_rel == 0)                                       // no shadow ray left: a miss, or a specular hit of a one-segment path
+            wf_shade_store(sh, i, sh_kind, shO, shV, 0.f, 0xff, sh_kind == kShadeSpecular ? refr_code : 0, 0, sh_kind == kShadeMiss ? nrays : sh_rays);
         f3 ans = mk(0, 0, 0);
         bool fold_sure = true;                                        // (counting instantiation) every folded segment passed wf_fold_bounded
         const int nseg = d < fr.segs ? d : fr.segs;
@@ -935,6 +1002,12 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             st.QR[2 * (size_t)qx + 1] = make_float4(ux.y, ux.z, __int_as_float((int)((unsigned)(x_trav | (st.anyhit ? PQ_ANYHIT : 0) | (d << PF_DEPTH_SHIFT)) | (unsigned)st.nonce << PQ_NONCE_SHIFT)), x_bound);
         }
     }
+    if (FILL && s_rel == 0) {                                         // the slot's record, with the shadow ray decided as the next launch's close decides it: from the cached word
+        float l0 = sh_l;
+        unsigned long long xw = WF_NOHIT;
+        if (emitX && wf_x_shadowed(flags, L, [&] { return st.X0[i]; }, [&](f3 &Oxr, f3 &uxr) { Oxr = Ox; uxr = ux; }, xw)) l0 = 0.f;
+        wf_shade_store(sh, i, sh_kind, shO, shV, l0, sh_sid, sh_kind == kShadeSpecular ? refr_code : 0, sh_dch, sh_rays);
+    }
     if (emitY) {
         t_sph = h.t;
         flags |= PF_HASY | (((h.obj + 1) & 31) << PQ_WIN_SHIFT);
@@ -962,6 +1035,17 @@ __global__ __launch_bounds__(256, 8) void wf_advance_tex(const Scene sc, const F
     Work wk;
     if (i < st.n_paths) wf_advance_path<STATS, false, true>(sc, fr, st, i, wk, ts);
     wf_flush_work<STATS>(fr, wk);
+}
+// the first-shade cache's two (never counting, textured or a batch: such chains are not eligible)
+__global__ __launch_bounds__(256, 8) void wf_advance_fill(const Scene sc, const Frame fr, const WfState st, const WfShade sh) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 1>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, sh);
+}
+__global__ __launch_bounds__(256, 8) void wf_advance_resume(const Scene sc, const Frame fr, const WfState st, const WfShade sh) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 2>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, sh);
 }
 // the two for a frame of an animated batch (a batch never counts work: no STATS form)
 template <bool FIRST>

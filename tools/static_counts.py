@@ -238,6 +238,12 @@ def main():
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
+    # the first-shade cache (rt_wavefront.hip.h WfShade): the launch that also stores the records by region, as wf_advance; the launch that resumes from them, whole
+    for name, pattern in (("wf_advance_fill", r"^(_ZN3rtk15wf_advance_fillE\w*):"), ("wf_advance_resume", r"^(_ZN3rtk17wf_advance_resumeE\w*):")):
+        mm = re.search(pattern, asm, re.M)
+        if not mm:
+            raise SystemExit(f"static_counts: {name} not found in the assembly")
+        res[name] = advance_counts(kernel_text(asm, mm.group(1))) if name == "wf_advance_fill" else {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
         json.dump(res, f, indent=1)
@@ -256,6 +262,8 @@ def main():
     print("static_counts: accumulation with the fast history: %d / %d / %d, rectify radius 1 / 2 / 3: %d / %d / %d, %d / %d / %d, %d / %d / %d" % tuple(
         res[k]["whole_kernel"][c] for k in ("temporal_accumulate_fast", "history_rectify_1", "history_rectify_2", "history_rectify_3") for c in ("valu", "lds", "vmem")))
     print("static_counts: wf_advance_list regions (valu / weight): " + ", ".join(f"{k} {v['valu']}/{v['valu_weight']}" for k, v in res["wf_advance_list"].items() if v))
+    print("static_counts: wf_advance_fill regions (valu / weight): " + ", ".join(f"{k} {v['valu']}/{v['valu_weight']}" for k, v in res["wf_advance_fill"].items() if v) +
+          "; wf_advance_resume whole kernel: %d / %d" % tuple(res["wf_advance_resume"]["whole_kernel"][c] for c in ("valu", "valu_weight")))
     print("static_counts: sample plan totals / scan / scatter, fold, counts (valu / lds / vmem): " + ", ".join(
         "%d / %d / %d" % tuple(res[k]["whole_kernel"][c] for c in ("valu", "lds", "vmem")) for k in ("sample_plan_totals", "sample_plan_scan", "sample_plan_scatter", "sample_fold", "sample_counts")))
     t = res["wf_travq"]
