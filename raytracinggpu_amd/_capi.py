@@ -366,9 +366,8 @@ def load():
     L.rt_render_rgb8.argtypes = [vp, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     L.rt_count_work.argtypes = [vp, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(Work)]
     L.rt_dead_channel_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.rt_first_hit_cache_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.rt_first_shadow_cache_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.rt_first_shade_cache_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    for n in ("rt_first_hit_cache_counts", "rt_first_shadow_cache_counts", "rt_first_shade_cache_counts"):
+        getattr(L, n).argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_synchronize.argtypes = [vp]
     L.rt_ctx_selfcheck.argtypes = [vp]
     L.rt_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -720,26 +719,26 @@ class Context:
         """trav_ms / trav_launches of stats() are measured only while enabled (production frames record no per-launch events)."""
         self._check(self._L.rt_stats_enable(self._h, 1 if on else 0))
 
+    def _still_counts(self, entry, first):
+        """the four counters of one level of the still view (csrc/rt_still.h)"""
+        fc = (C.c_uint64 * 4)()
+        self._check(getattr(self._L, entry)(self._h, fc))
+        return dict(zip((first, "filled", "ineligible", "key_misses"), (int(v) for v in fc)))
+
     def first_hit_cache_counts(self):
         """rt_first_hit_cache_counts: launch chains of this context that skipped their first traversal launch, that filled the cache, that were not eligible, and
         key comparisons that emptied a filled cache."""
-        fc = (C.c_uint64 * 4)()
-        self._check(self._L.rt_first_hit_cache_counts(self._h, fc))
-        return dict(zip(("skipped", "filled", "ineligible", "key_misses"), (int(v) for v in fc)))
+        return self._still_counts("rt_first_hit_cache_counts", "skipped")
 
     def first_shadow_cache_counts(self):
         """rt_first_shadow_cache_counts: launch chains of this context that handed no shadow ray of their first segment to the traversal (the cached answers were read),
         that filled the cache, that were not eligible, and key comparisons that emptied a filled cache."""
-        fc = (C.c_uint64 * 4)()
-        self._check(self._L.rt_first_shadow_cache_counts(self._h, fc))
-        return dict(zip(("skipped", "filled", "ineligible", "key_misses"), (int(v) for v in fc)))
+        return self._still_counts("rt_first_shadow_cache_counts", "skipped")
 
     def first_shade_cache_counts(self):
         """rt_first_shade_cache_counts: launch chains of this context that resumed their paths at the shaded first hit (one launch in place of the camera-ray launch and the
         close of segment 0), that filled the cache, that were not eligible, and replacements of the first-shadow cache's key that emptied a filled cache."""
-        fc = (C.c_uint64 * 4)()
-        self._check(self._L.rt_first_shade_cache_counts(self._h, fc))
-        return dict(zip(("resumed", "filled", "ineligible", "key_misses"), (int(v) for v in fc)))
+        return self._still_counts("rt_first_shade_cache_counts", "resumed")
 
     def set_pipelining(self, on=True):
         """rt_ctx_set_pipelining: consecutive render_device calls on one stream into alternating buffers overlap at the frame boundary."""

@@ -2,6 +2,7 @@
 #include "../../../include/raytracer_host.h"
 #include "../../../include/raytracer.hpp"
 #include "../rt_qrows.h"
+#include "../rt_still.h"
 
 using namespace raytracer;
 
@@ -74,6 +75,42 @@ int64_t rth_qrows_enumerate(int n_paths, int log2S, int Q, int tblocks, int whic
             if (slots && n < cap) slots[n] = w.rows != 0 ? qrows_slot(w, log2S, (int)v) : (int32_t)v;
         }
     }
+    return n;
+}
+
+// the still view's state machine and chain plan (rt_still.h) without a device.  The events stand for what the render path does per chunk and per chain: op 0 sizes the
+// three buffers as size_wavefront does (the records only when StillView::may_store_records says so) and calls begin with 8-byte keys made of the ids
+int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32_t *rows, int64_t cap) {
+    using namespace rtk;
+    StillView v;
+    int64_t buf[3] = {0, 0, 0}, next_buf = 1, n = 0;                        // the allocations of the three levels as made-up addresses (0: none yet)
+    auto at = [](int64_t id) { return reinterpret_cast<const void *>((intptr_t)id); };
+    for (int e = 0; e < n_ev; ++e) {
+        const int32_t *x = ev + 5 * e;
+        if (x[0] == 0) {                                                    // a chunk of level x[1]: ray key x[2], Scene x[3], the rest of the shading key x[4]
+            const int64_t ray = x[2], shade[2] = {x[3], x[4]};
+            if (x[1] >= 1 && !buf[0]) buf[0] = next_buf++;
+            if (x[1] >= 2 && !buf[1]) buf[1] = next_buf++;
+            if (x[1] >= 3 && !buf[2] && v.may_store_records(&shade[0], sizeof(shade[0]))) buf[2] = next_buf++;
+            v.begin(x[1], &ray, sizeof(ray), shade, sizeof(shade), at(buf[0]), at(buf[1]), at(buf[2]));
+        } else if (x[0] == 1) {                                             // a chain of part x[1] with x[2] segments; x[3]: 1 a mesh, 2 row windows, 4 a Y window
+            const StillChain c = v.chain(x[1], buf[2] != 0);
+            const StillPlan p = still_plan(c, x[2], (x[3] & 1) != 0, (x[3] & 2) != 0, (x[3] & 4) != 0);
+            for (int it = p.first - 1; it < (p.n > p.first ? p.n : p.first); ++it, ++n) {
+                if (!rows || n >= cap) continue;
+                int32_t *r = rows + 12 * n;
+                const bool open = it == p.first - 1;                        // the opening launch, then the positions
+                const StillStep z{false, kWinNone, false, p.open_m0, 0, p.open};
+                const StillStep &s = open ? z : p.step[it];
+                const int32_t row[12] = {e, open ? -1 : it, s.trav, s.win, s.trav_m0, s.m0, s.x0, s.adv, open ? p.kill_x : 0, c.hit, c.shadow, c.records};
+                memcpy(r, row, sizeof(row));
+            }
+        } else if (x[0] == 2) v.mesh_changed();
+        else if (x[0] == 3) v.shading_changed();
+        else if (x[0] == 4 && buf[x[1]]) buf[x[1]] = next_buf++;            // level x[1]'s buffer is a new allocation
+    }
+    const StillLevel *lv[3] = {&v.hit, &v.shadow, &v.records};
+    for (int k = 0; k < 12; ++k) counts[k] = lv[k / 4]->counts[k % 4];
     return n;
 }
 

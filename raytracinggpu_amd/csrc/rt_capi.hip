@@ -12,6 +12,7 @@
 #include "rt_bvhbuild.hip.h"
 #include "rt_lbvh.hip.h"
 #include "rt_adaptive.hip.h"
+#include "rt_still.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -110,8 +111,8 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     ctx->parts_valid = false;                                            // (the per-mesh records describe the scene this call installs, or none)
     ctx->tex_mask = 0;                                                   // a new scene is untextured, also when this call fails
-    ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
-    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
+    ctx->still.shading_changed();
+    ctx->still.mesh_changed();
     if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(ctx, RT_ERR_INVALID, "bad sphere array");
     if (n_meshes < 0 || (n_meshes > 0 && !meshes)) return fail(ctx, RT_ERR_INVALID, "bad mesh array");
     if (!light || !camera) return fail(ctx, RT_ERR_INVALID, "light/camera is NULL");
@@ -343,23 +344,15 @@ int rt_dead_channel_counts(rt_ctx *ctx, uint64_t out[4]) {
 #include "rt_host_tex.hip.h"      // rt_mesh_set_texture[_of]
 #include "rt_host_edit.hip.h"     // rt_scene_get / set / move: the light and the spheres of the scene in use
 
-int rt_first_hit_cache_counts(const rt_ctx *ctx, uint64_t out[4]) {
+// the four counters of one level of the still view (rt_still.h StillLevel::counts)
+static int still_counts(const rt_ctx *ctx, rtk::StillLevel rtk::StillView::*level, uint64_t out[4]) {
     if (!ctx || !out) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
-    for (int k = 0; k < 4; ++k) out[k] = ctx->fh.counts[k];
+    for (int k = 0; k < 4; ++k) out[k] = (ctx->still.*level).counts[k];
     return RT_OK;
 }
-
-int rt_first_shadow_cache_counts(const rt_ctx *ctx, uint64_t out[4]) {
-    if (!ctx || !out) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
-    for (int k = 0; k < 4; ++k) out[k] = ctx->fs.counts[k];
-    return RT_OK;
-}
-
-int rt_first_shade_cache_counts(const rt_ctx *ctx, uint64_t out[4]) {
-    if (!ctx || !out) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
-    for (int k = 0; k < 4; ++k) out[k] = ctx->fsh.counts[k];
-    return RT_OK;
-}
+int rt_first_hit_cache_counts(const rt_ctx *ctx, uint64_t out[4]) { return still_counts(ctx, &rtk::StillView::hit, out); }
+int rt_first_shadow_cache_counts(const rt_ctx *ctx, uint64_t out[4]) { return still_counts(ctx, &rtk::StillView::shadow, out); }
+int rt_first_shade_cache_counts(const rt_ctx *ctx, uint64_t out[4]) { return still_counts(ctx, &rtk::StillView::records, out); }
 
 int rt_camera_basis(const rt_camera_pose *pose, float bx[3], float by[3], float bz[3]) {
     if (!pose || !bx || !by || !bz) return fail(nullptr, RT_ERR_INVALID, "bad arguments");

@@ -73,11 +73,11 @@ struct Knobs {
     int travq_rows = 1;        // RT_TRAVQ_ROWS=0: every wf_travq launch scans the whole queue (A/B, cross-check; default: the first launch of a chain enumerates the rows that hold continuation
                                // rays only and the last the rows that hold shadow rays only, rt_qrows.h).  Bit-exact either way
     int first_hit_cache = 1;   // RT_FIRST_HIT_CACHE=0: every chain traces its camera rays (A/B, cross-check, and the figure of a moving camera; default: a still camera's primary mesh hits
-                               // are traced once and kept, rt_host_render.hip.h FirstHit).  Bit-exact either way
+                               // are traced once and kept, rt_still.h).  Bit-exact either way
     int first_shadow_cache = 1; // RT_FIRST_SHADOW_CACHE=0: every chain traces the shadow rays of its first segment (A/B, cross-check, and the figure of a moving light; default: under a still
-                               // camera AND a still light, scene and shading state they are traced once and kept, rt_host_render.hip.h FirstShadow).  Off with RT_FIRST_HIT_CACHE=0.  Bit-exact either way
+                               // camera AND a still light, scene and shading state they are traced once and kept, rt_still.h).  Off with RT_FIRST_HIT_CACHE=0.  Bit-exact either way
     int first_shade_cache = 1; // RT_FIRST_SHADE_CACHE=0: every chain of a still view opens with wf_advance<FIRST> and closes segment 0 (A/B, cross-check; default: once the first-shadow cache has held
-                               // for two chains, a path's state after its shaded first hit is kept and later chains resume from it, rt_host_render.hip.h FirstShade).  Off with either older
+                               // for two chains, a path's state after its shaded first hit is kept and later chains resume from it, rt_still.h).  Off with either older
                                // knob at 0, and for scenes with a textured mesh.  Bit-exact either way
     int refit_wide = 1;        // RT_REFIT_WIDE=0: rt_mesh_set_vertices* refits with the one-workgroup refit_kernel, as rt_mesh_transform does (A/B, cross-check; default: the climb across
                                // the chip, rt_meshops.hip.h refit_up_kernel).  Bit-exact either way
@@ -217,56 +217,11 @@ struct rt_ctx {
     DevBuf wfM{bufs}, wfT{bufs}, wfLS{bufs}, wfSID{bufs}, wfSamp{bufs};   // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
     DevBuf wfDCH{bufs};                                             // ... the dead-channel byte of each path (wf_dead_channels)
     unsigned long long dead_counts[4] = {};                          // of the last rt_count_work: rt_dead_channel_counts
-    // The FIRST-HIT CACHE: the traversal results of the camera rays, one word per pixel slot of each sub-frame at its pxbase.  With sigma == 0 a camera
-    // ray is a function of camera, frame geometry and pixel, and its nearest triangle of that ray, the mesh, its tree and tri_tmin: everything in FirstHit::Key.  The chain's
-    // first wf_travq launch writes wfM0 instead of wfM (a fill), the wf_advance that closes segment 0 reads it, and a chain that finds its part filled under the same key does
-    // not enqueue that launch at all (a skip).  Every field is compared as bits; mesh_gen is bumped by every entry that can change a triangle, the visit order or the tree.
-    DevBuf wfM0{bufs};
-    uint64_t mesh_gen = 0;
-    struct FirstHit {
-        struct Key {
-            uint64_t mesh_gen; const void *buf;
-            uint32_t cam[3], z, tri_tmin, basis[9];
-            int cam_mode, W, H, row0, n_rows, tile_rows, tile_step, parts, variant, travq_mode;
-            struct Part { int n_px, tiles_x, row0, n_rows, tile_step, pad; uint64_t pxbase; const void *stream; } part[8];
-        } key;
-        bool valid = false;                  // key describes what the filled parts of wfM0 hold
-        uint64_t gen = 0;                    // times the key was replaced (the first-shadow cache's key holds it: a first-hit miss empties that cache too)
-        bool filled[8] = {};                 // part j's words were written by a launch enqueued under `key`, on key.part[j].stream
-        uint64_t counts[4] = {};             // chains that skipped launch 0 / filled / were ineligible; key misses after a valid fill (rt_first_hit_cache_counts)
-        FirstHit() { memset(&key, 0, sizeof(key)); }
-    } fh;
-    // The FIRST-SHADOW CACHE: the traversal result of each pixel slot's segment-0 shadow ray, laid out like wfM0.  Under the first-hit cache's
-    // conditions that ray is a function of the camera ray (the first-hit key), of what it hits and how that is shaded (spheres, materials, normals, textures: whether a shadow
-    // ray leaves, and from where), of the light, of eps and of the elision rules in force -- everything in FirstShadow::Key, compared as bits.  What lives behind a pointer and
-    // is edited in place (normals, UVs, texels) is covered by shade_gen, bumped by every entry that writes it; mesh edits reach the key through FirstHit::gen.  The chain that
-    // fills traces the rays of its first sample's items and stores their words while it closes them; a chain that finds its part filled under the same key hands no segment-0
-    // shadow ray to the traversal.  The first-hit cache's state and counters are not touched by any of this.
-    DevBuf wfX0{bufs};
-    uint64_t shade_gen = 0;
-    struct FirstShadow {
-        struct Key {
-            uint64_t fh_gen, shade_gen; const void *buf;
-            uint32_t eps; int anyhit, deadch, tex_mask;
-            rtk::TexDesc tex[rtk::kMaxObjects];
-            rtk::Scene scn;                  // light, sphere table, object order, materials, smooth_mask, every pointer (the camera again)
-        } key;
-        bool valid = false;                  // key describes what the filled parts of wfX0 hold
-        bool filled[8] = {};                 // part j's words are written by a chain enqueued under `key`, on the stream of the first-hit key
-        uint64_t counts[4] = {};             // chains that read the cache / filled it / were ineligible; key misses after a valid fill (rt_first_shadow_cache_counts)
-        FirstShadow() { memset(&key, 0, sizeof(key)); }
-    } fs;
-    // The FIRST-SHADE CACHE: one 32-byte record per pixel slot, laid out like wfM0 and wfX0 -- the slot's path after segment 0 is shaded and its
-    // shadow ray decided, before the bounce direction (rtk::WfShade).  With sigma == 0 nothing of it depends on the seed or the sample: it depends on what FirstShadow::Key
-    // compares, so the cache has no key of its own -- one flag per part, cleared whenever that key is replaced.  A chain fills it only when it READS the first-shadow
-    // cache and finds its part's records not yet stored (the key has then held for two chains: a light that moves every frame never pays for a fill); a chain that finds
-    // them stored opens with wf_advance_resume instead of wf_advance<FIRST> and the launch that closes segment 0.  Scenes with a textured mesh are not eligible.
-    DevBuf wfS0{bufs};
-    struct FirstShade {
-        const void *buf = nullptr;           // the allocation the filled parts' records live in (a new one empties the cache)
-        bool filled[8] = {};                 // part j's records are written by a chain enqueued under fs.key, on the stream of the first-hit key
-        uint64_t counts[4] = {};             // chains that resumed / filled / were ineligible; replacements of the key after a valid fill (rt_first_shade_cache_counts)
-    } fsh;
+    // A still view's three levels (rt_still.h): per pixel slot of each sub-frame at its pxbase, the traversal result of the camera ray (8 bytes), of
+    // segment 0's shadow ray (8 bytes) and the path after its shaded first hit (32 bytes, rtk::WfShade; allocated only once a chain may store it).  `still` says which
+    // parts of them hold what, under which keys (rt_host_render.hip.h still_begin)
+    DevBuf wfM0{bufs}, wfX0{bufs}, wfS0{bufs};
+    rtk::StillView still;
     DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
     DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum

@@ -9,7 +9,7 @@
 // wide (rt_mesh_set_vertices* only): the boxes by the climb across the chip (rt_meshops.hip.h refit_up_kernel), bit for bit what refit_kernel makes of the same tree.
 // Either way the entry then waits on its stream for the root box (32 bytes): the box travels to the render kernels as an argument and the quantisation grid hangs on it.
 static int refit_and_requantize(rt_ctx *ctx, const bool wide = false) {
-    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
+    ctx->still.mesh_changed();
     rtk::Scene &sc = ctx->scene;
     rtk::RefitArgs a{};
     a.node_lo = static_cast<float4 *>(ctx->node_lo.p); a.node_hi = static_cast<float4 *>(ctx->node_hi.p);
@@ -102,7 +102,7 @@ static int set_part_normals(rt_ctx *ctx, rt_ctx::MeshPart &p, const float *norma
     if (int rc = gather_corners(ctx, p, "normal", nidx, index_stride, n_triangles, n_normals, vb, ni); rc != RT_OK) return rc;
     std::vector<float4> nr(ni.size());
     for (size_t i = 0; i < ni.size(); ++i) nr[i] = make_float4(normals_xyz[3 * (size_t)ni[i]], normals_xyz[3 * (size_t)ni[i] + 1], normals_xyz[3 * (size_t)ni[i] + 2], 0.f);
-    ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
+    ctx->still.shading_changed();
     rtk::Scene &sc = ctx->scene;
     const size_t bytes = 3 * (size_t)sc.n_tris * sizeof(float4);
     if (sc.nrm == nullptr) {
@@ -123,7 +123,7 @@ int rt_mesh_set_normals(rt_ctx *ctx, const float *normals_xyz, int n_normals, co
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
     if (!normals_xyz || !nidx) {                                                  // back to flat shading (every mesh)
-        ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
+        ctx->still.shading_changed();
         ctx->scene.nrm = nullptr; ctx->scene.smooth_mask = 0;
         for (rt_ctx::MeshPart &p : ctx->parts) p.smooth = false;
         return RT_OK;
@@ -144,7 +144,7 @@ int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xy
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
     if (!normals_xyz || !nidx) {                                                    // this mesh flat again
-        ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
+        ctx->still.shading_changed();
         rtk::Scene &sc = ctx->scene;
         p->smooth = false;
         sc.smooth_mask &= ~(1 << object_slot);
@@ -160,7 +160,7 @@ int rt_mesh_set_normals_of(rt_ctx *ctx, int object_slot, const float *normals_xy
 // visit range; then the whole-forest refit.
 static int transform_parts(rt_ctx *ctx, size_t first, size_t last, const float rotation[9], const float translation[3]) {
     rtk::Scene &sc = ctx->scene;
-    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
+    ctx->still.mesh_changed();
     if (sc.n_nodes <= 0 || sc.n_verts <= 0) return RT_OK;                           // no mesh, or no triangle in any leaf: nothing to move or refit
     RT_HIP(ctx, hipSetDevice(ctx->device));
     rtk::Mat3 m;
@@ -409,7 +409,7 @@ static int rebuild_lbvh_tree(rt_ctx *ctx, const int nt, int &n_nodes_out, const 
 // The render kernels' formats from the LBVH builder's arrays, on the device (rt_lbvh.hip.h, second half): what install_scene does on the
 // host for an uploaded tree.  A scene of ONE part only (the builder ran over the whole of tidx_up).  `old`: the scene in use (spheres, light, camera, albedo, mesh slot carry over).
 static int install_lbvh_device(rt_ctx *ctx, const rtk::Scene &old, const int n_nodes) {
-    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
+    ctx->still.mesh_changed();
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t q = own_stream(ctx);
     const rtk::LbvhArgs &a = ctx->lb_args;
@@ -531,7 +531,7 @@ extern "C++" template <class T> static std::vector<T> carry_corners(const std::v
 static int rebuild_part(rt_ctx *ctx, size_t pi, int mode, float *bvh_arr10_out, int32_t *tri_order_out, int32_t *n_nodes_out) {
     const std::vector<rt_ctx::MeshPart> parts = ctx->parts;
     const rt_ctx::MeshPart P = parts[pi];
-    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
+    ctx->still.mesh_changed();
     const rtk::Scene old = ctx->scene;
     const int K = (int)parts.size();
     const bool was_valid = ctx->parts_valid;

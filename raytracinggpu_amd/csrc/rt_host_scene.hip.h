@@ -151,7 +151,7 @@ void mesh_table_single(rtk::Scene &sc, int real_obj) {
 // n_meshes + 1 entries; its first n_syn nodes are the synthetic union nodes) -- or nullptr.
 int install_scene(rt_ctx *ctx, rtk::Scene sc, const rt_mesh *mesh, const std::vector<int> *tri_offsets = nullptr, int n_syn = 0) {
     PhaseClock pc;
-    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
+    ctx->still.mesh_changed();
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->stream_) RT_HIP(ctx, hipStreamSynchronize(ctx->stream_));   // (renders issued on a caller's stream are the caller's to order)
     ctx->have_scene = false;
@@ -458,7 +458,7 @@ int install_meshes(rt_ctx *ctx, const rtk::Scene &sc, const rt_mesh *meshes, con
     Forest f;                                                           // (K <= 1: stays empty, every offset is 0)
     int rc;
     ctx->parts_valid = false;
-    ++ctx->mesh_gen;                                                  // first-hit cache: a triangle, the visit order or the tree may change (rt_ctx::FirstHit)
+    ctx->still.mesh_changed();
     if (K <= 1) {                                                       // build_forest would take a lone mesh's root for a synthetic node
         rc = install_scene(ctx, sc, K ? &meshes[real[0]] : if_none);
     } else {

@@ -12,7 +12,7 @@ int rt_mesh_set_texture_of(rt_ctx *ctx, int object_slot, const float *uvs, int n
     if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, hipDeviceSynchronize());                                            // frames in flight may read the records and buffers replaced below
-    ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
+    ctx->still.shading_changed();
     const int bit = 1 << object_slot;
     if (!uvs || !uvidx || !tex) {                                                   // this mesh untextured again
         ctx->tex_mask &= ~bit;
@@ -54,7 +54,7 @@ int rt_mesh_set_texture(rt_ctx *ctx, const float *uvs, int n_uvs, const int32_t 
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
     if (!uvs || !uvidx || !tex) {                                                   // every mesh untextured again
-        ++ctx->shade_gen;                                                 // first-shadow cache: normals, UVs or texels behind a pointer may change (rt_ctx::FirstShadow)
+        ctx->still.shading_changed();
         ctx->tex_mask = 0;
         return RT_OK;
     }

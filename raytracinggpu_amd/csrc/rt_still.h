@@ -1,0 +1,161 @@
+// rt_still.h -- what a launch chain of a STILL VIEW may skip: the state of the three levels kept between frames, and the launches of one chain.
+//
+// With sigma == 0 the start of every path repeats from frame to frame as long as nothing it depends on changes.  Three levels are kept per pixel slot, each in a buffer of its
+// own laid out by the parts' pxbase, each level resting on the one before:
+//     hit     (wfM0)  the traversal result of the camera ray.               Depends on the RAY KEY: camera, frame geometry, the cut into parts, tri_tmin, the mesh.
+//     shadow  (wfX0)  the traversal result of segment 0's shadow ray.       Depends on the SHADING KEY: the ray key, the whole Scene, eps, textures, the elision rules.
+//     records (wfS0)  the path after its shaded first hit (rtk::WfShade).   Depends on the shading key too: it has no key of its own.
+// A chain of part j FILLS a level (traces as ever and stores), USES it (the launch that would have produced the words is not enqueued, or reads them) or leaves it OFF.
+// The records are stored only by a chain that USES the shadow level -- the key has then held for two chains: a light that moves every frame never pays for a fill.
+//
+// The rules, each enforced in one place below:
+//   - A part's words are written and read on ONE stream, inside chains only, and that stream is part of the ray key.  mark() is called at ENQUEUE: the next chain of the part
+//     runs behind this one on the same stream, also under the relaxed start of pipelined frames (frame k + 1's chain of a part follows frame k's on the part's own stream).
+//     A call whose chains run on other streams is a miss.                                                                             (StillLevel::chain, the caller's key)
+//   - Replacing the ray key replaces the shading key; replacing the shading key empties the records; a new allocation of a level's buffer empties that level.  (begin)
+//   - Keys are compared as bits: the caller zeroes its key's padding and puts the whole Scene in.  A wrong miss costs a refill, a wrong hit a silently wrong frame.  (StillKey::same)
+//   - What lives behind a pointer of the keys and is edited in place reaches them through two generation counters.                    (mesh_changed, shading_changed)
+//   - The eligibility levels nest: 0 none, 1 hit, 2 hit + shadow, 3 all three.  Chains of level 0 count as ineligible and touch nothing else; the list chains of
+//     rt_render_counts* do not come here at all.                                                                                      (begin, chain)
+// Plain C++: the library and the host library (rth_still_replay, tests/test_still_view_model.py) compile the same text.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+#include <vector>
+
+namespace rtk {
+
+enum StillMode { kStillOff = 0, kStillFill = 1, kStillUse = 2 };
+constexpr int kStillParts = 8;                       // rt_ctx::kMaxParts
+constexpr int kStillMaxSteps = 17;                   // RT_MAX_SEGMENTS + 1
+
+// One level: which parts hold words stored under the key in force, and its four counters -- chains that used the level / filled it / were ineligible; times the level was
+// emptied while it held something (rt_first_{hit,shadow,shade}_cache_counts)
+struct StillLevel {
+    bool filled[kStillParts] = {};
+    uint64_t counts[4] = {};
+    void clear() {
+        bool any = false;
+        for (bool &f : filled) { any = any || f; f = false; }
+        if (any) ++counts[3];
+    }
+    void mark(int j) { filled[j] = true; }
+    // one chain of part j.  eligible: the chunk's level reaches this one; ready: what the level rests on is there (a chain that is eligible but not ready leaves the level
+    // off and counts nowhere)
+    StillMode chain(int j, bool eligible, bool ready = true) {
+        if (!eligible) { ++counts[2]; return kStillOff; }
+        if (!ready) return kStillOff;
+        if (filled[j]) { ++counts[0]; return kStillUse; }
+        ++counts[1]; mark(j);
+        return kStillFill;
+    }
+};
+
+// What a level's words were stored under: the caller's bytes, the generations and the allocation
+struct StillKey {
+    std::vector<unsigned char> bytes;                // empty: no key yet
+    uint64_t gen[2] = {};
+    const void *buf = nullptr;
+    bool same(const void *p, size_t n, uint64_t g0, uint64_t g1, const void *b) const {
+        return bytes.size() == n && n != 0 && memcmp(bytes.data(), p, n) == 0 && gen[0] == g0 && gen[1] == g1 && buf == b;
+    }
+    void set(const void *p, size_t n, uint64_t g0, uint64_t g1, const void *b) {
+        bytes.assign(static_cast<const unsigned char *>(p), static_cast<const unsigned char *>(p) + n);   // (no allocation once it has held a key of this size)
+        gen[0] = g0; gen[1] = g1; buf = b;
+    }
+};
+
+struct StillChain { StillMode hit, shadow, records; };
+
+struct StillView {
+    StillLevel hit, shadow, records;
+    // Every entry that can change a triangle, the visit order or the tree calls this: the hit words are stale (and with them everything above)
+    void mesh_changed() { ++mesh_gen; }
+    // Every entry that writes what shading reads behind a pointer of the Scene -- normals, UVs, texels, texture records: the shadow words and the records are stale
+    void shading_changed() { ++shade_gen; }
+
+    // Before a chunk's chains are enqueued, after their streams are settled.  level: what the chunk is eligible for; the keys are read up to that level only; M0 / X0 / S0: where
+    // the three buffers are now.  Any difference from what a level was stored under empties it and every level above.
+    void begin(int level, const void *ray, size_t ray_n, const void *shade, size_t shade_n, const void *M0, const void *X0, const void *S0) {
+        if (rec_buf != S0) { records.clear(); rec_buf = S0; }
+        if (level >= 1 && !ray_key.same(ray, ray_n, mesh_gen, 0, M0)) {
+            hit.clear();
+            ray_key.set(ray, ray_n, mesh_gen, 0, M0);
+            ++ray_gen;
+        }
+        if (level >= 2 && !shade_key.same(shade, shade_n, ray_gen, shade_gen, X0)) {
+            shadow.clear();
+            shade_key.set(shade, shade_n, ray_gen, shade_gen, X0);
+            records.clear();
+        }
+        lvl = level;
+    }
+    // Whether a chain of the coming chunk may store records, asked BEFORE begin (the buffers are sized before the streams are settled): the shadow level holds a part's
+    // words, so a chain may use it, and its key's Scene -- the head of the shading key -- is this chunk's.  A light that moves every frame allocates nothing.
+    bool may_store_records(const void *scene, size_t n) const {
+        bool any = false;
+        for (bool f : shadow.filled) any = any || f;
+        return any && shade_key.bytes.size() >= n && memcmp(shade_key.bytes.data(), scene, n) == 0;
+    }
+    // One chain of part j under the level of the last begin; records_ok: the records' buffer exists at this chunk's size.  A chain that resumes from the records also
+    // counts as having used the two levels below: it enqueued neither their launches.
+    StillChain chain(int j, bool records_ok) {
+        StillChain c;
+        c.hit = hit.chain(j, lvl >= 1);
+        c.shadow = shadow.chain(j, lvl >= 2);
+        c.records = records.chain(j, lvl >= 3, c.shadow == kStillUse && records_ok);
+        return c;
+    }
+
+  private:
+    StillKey ray_key, shade_key;
+    const void *rec_buf = nullptr;
+    uint64_t mesh_gen = 0, shade_gen = 0, ray_gen = 0;
+    int lvl = 0;
+};
+
+// The launches of one chain.  It opens with one wf_advance -- begin, or resume from the records -- and goes on through positions first .. n - 1: at position `it` a
+// traversal launch (if any) and the wf_advance that closes what it traced.
+enum StillWin { kWinNone = 0, kWinY = 1, kWinX = 2 };            // the rows of the queue a traversal launch enumerates (rt_qrows.h)
+enum StillAdv { kAdvBegin = 0, kAdvResume = 1, kAdvPlain = 2, kAdvFill = 3 };
+struct StillStep {
+    bool trav;                // the traversal launch is enqueued
+    int win;                  // ... over this window
+    bool trav_m0;             // ... and writes the part's block of the hit level instead of M
+    int m0, x0;               // WfState::m0 / x0 of the wf_advance: it reads the hit level; 1 stores / 2 reads the shadow level
+    int adv;                  // kAdvPlain, or kAdvFill: it stores the part's records
+};
+struct StillPlan {
+    int open;                 // kAdvBegin or kAdvResume
+    int open_m0;              // WfState::m0 of the opening launch (only the first sample's camera rays go to the traversal)
+    int kill_x;               // WfShade::kill_x: a resumed chain without a Y window clears its items' shadow slots instead
+    int first, n;
+    StillStep step[kStillMaxSteps];
+};
+// segs: ray segments of a path (0: the chain has no position at all); rows: traversal launches take windows (the work-stack kernel under RT_TRAVQ_ROWS);
+// has_y: this part's queue has a Y window that is not every row
+inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool rows, bool has_y) {
+    StillPlan p;
+    const bool resume = c.records == kStillUse;
+    p.open = resume ? kAdvResume : kAdvBegin;
+    p.open_m0 = (!resume && c.hit != kStillOff) ? 1 : 0;
+    p.kill_x = (resume && !(rows && has_y)) ? 1 : 0;
+    p.first = resume ? 1 : 0;                                     // a resumed chain starts where segment 0 is closed
+    p.n = segs > 0 ? segs + 1 : 0;
+    for (int it = 0; it < p.n; ++it) {
+        StillStep &s = p.step[it];
+        // the first launch of a chain that uses the hit level has nothing to trace; the second launch of a chain of one segment that uses the shadow level would trace
+        // segment 0's shadow rays and nothing else
+        s.trav = have_mesh && !(it == 0 && c.hit == kStillUse) && !(it == 1 && segs == 1 && c.shadow == kStillUse);
+        // the first launch can meet no shadow ray and the last no continuation ray; neither can the first launch of a resumed chain, at position 1
+        const bool only_y = it == 0 || (it == 1 && resume);
+        s.win = !(rows && s.trav) ? kWinNone : only_y ? (has_y ? kWinY : kWinNone) : it == segs ? kWinX : kWinNone;
+        s.trav_m0 = s.trav && it == 0 && c.hit != kStillOff;
+        s.m0 = (it == 0 && c.hit != kStillOff) ? 1 : 0;            // the launch that closes segment 0 reads the camera rays' results from the hit level
+        s.x0 = (it <= 1 && !resume) ? (int)c.shadow : 0;           // the launch that emits segment 0's shadow rays and the one that closes them
+        s.adv = (it == 0 && c.records == kStillFill) ? kAdvFill : kAdvPlain;
+    }
+    return p;
+}
+
+}  // namespace rtk

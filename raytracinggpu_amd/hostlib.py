@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RT_HOST_LIB") or os.path.join(HERE, "libraytrace_host.so")   # RT_HOST_LIB: the sanitizer build (tools/sanitize_cpu.sh)
 EXPORTS = ["rth_mesh_new", "rth_mesh_free", "rth_mesh_read_obj", "rth_mesh_set_arrays", "rth_mesh_rescale",
            "rth_mesh_build_bvh", "rth_mesh_num_vertices", "rth_mesh_num_triangles", "rth_mesh_num_nodes",
-           "rth_mesh_get_vertices", "rth_mesh_get_indices", "rth_mesh_get_bvh_array", "rth_write_png", "rth_qrows_enumerate"]
+           "rth_mesh_get_vertices", "rth_mesh_get_indices", "rth_mesh_get_bvh_array", "rth_write_png", "rth_qrows_enumerate", "rth_still_replay"]
 _lib = None
 
 
@@ -34,6 +34,8 @@ def load():
         L.rth_write_png.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_uint8)]
         L.rth_qrows_enumerate.restype = C.c_int64
         L.rth_qrows_enumerate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int64]
+        L.rth_still_replay.restype = C.c_int64
+        L.rth_still_replay.argtypes = [ip, C.c_int, C.POINTER(C.c_uint64), ip, C.c_int64]
         _lib = L
     return _lib
 
@@ -115,6 +117,19 @@ def qrows_enumerate(n_paths, log2S, Q, tblocks, which):
     slots = np.zeros(n, np.int32)
     L.rth_qrows_enumerate(n_paths, log2S, Q, tblocks, which, info.ctypes.data_as(ip), blk_len.ctypes.data_as(ip), slots.ctypes.data_as(ip), n)
     return dict(row0=int(info[0]), rows=int(info[1]), share=int(info[2]), total=int(info[3])), blk_len, slots
+
+
+def still_replay(events):
+    """The still view's state machine (csrc/rt_still.h) after `events` (rth_still_replay, include/raytracer_host.h): the counters of the three levels as a 3 x 4 array and
+    the launch rows of every chain, 12 numbers each."""
+    L = load()
+    ip = C.POINTER(C.c_int32)
+    ev = np.zeros((len(events), 5), np.int32)
+    for k, e in enumerate(events):
+        ev[k, :len(e)] = e
+    counts, rows = np.zeros(12, np.uint64), np.zeros((18 * len(events), 12), np.int32)      # at most an opening launch and RT_MAX_SEGMENTS + 1 positions per chain
+    n = L.rth_still_replay(ev.ctypes.data_as(ip), len(ev), counts.ctypes.data_as(C.POINTER(C.c_uint64)), rows.ctypes.data_as(ip), len(rows))
+    return counts.reshape(3, 4).astype(np.int64), rows[:n]
 
 
 def write_png(path, rgb8):

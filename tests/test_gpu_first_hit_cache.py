@@ -1,12 +1,12 @@
-"""The first-hit cache on the device (rt_ctx::FirstHit, enqueue_chain, wf_advance's close of segment 0): a default context against one created under
+"""The first-hit cache on the device (the hit level of csrc/rt_still.h, enqueue_chain, wf_advance's close of segment 0): a default context against one created under
 RT_FIRST_HIT_CACHE=0, word for word, colour and .w -- and rt_first_hit_cache_counts, which says whether a chain skipped its first traversal launch, filled the cache or
-was not eligible, so that every comparison below is known to have gone through the path it names.  -m gpu.
+was not eligible, so that every comparison below is known to have gone through the path it names.  -m gpu.  The helpers
+all three files of this kind share are tests/still_view.py; the state machine alone is replayed without a device in tests/test_still_view_model.py.
 
 The cat at 64 x 48 (two sub-frames of three 8-row tiles: two launch chains per frame and sample chunk).  The reference of every comparison is the second context, never
 the cached one.  The library has no entry that edits vertices in place or refits on its own (a refit happens inside rt_mesh_transform); those two cases of the mesh-edit
 list do not exist here."""
-import os
-from contextlib import contextmanager
+from functools import partial
 
 import numpy as np
 import pytest
@@ -14,109 +14,25 @@ import pytest
 import raytracinggpu_amd as rt
 
 from . import material_scenes as ms
+from . import still_view as sv
+from .still_view import B, H
 
 pytestmark = pytest.mark.gpu
 
-W, H, B = 64, 48, 2
-OFF = dict(RT_FIRST_HIT_CACHE="0")
-ZERO = dict(skipped=0, filled=0, ineligible=0, key_misses=0)
-
-
-@contextmanager
-def _env(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update(kw)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _context(**kw):
-    with _env(**kw):                                   # the knobs are read once, when the context is created
-        return rt.Context(0)
+LEVEL = sv.HIT
+_bits_equal, _cat, _params, _upload, _chunk, _render_rows = sv.bits_equal, sv.cat, sv.params, sv.upload, sv.chunk, sv.render_rows
+_pair, _delta, _frame = partial(sv.pair, LEVEL), partial(sv.delta, LEVEL), partial(sv.frame, LEVEL)
 
 
 @pytest.fixture(scope="module")
 def pair():
-    on, off = _context(), _context(**OFF)
-    yield on, off
-    on.close()
-    off.close()
+    yield from _pair()
 
 
 @pytest.fixture(scope="module")
 def pair_one_sample_per_chain():
     """RT_PATH_SAMP_MB=1: a chain's state may take 1 MB; a sample of 64 x 48 with 13 segments takes 0.73: one sample per chain"""
-    kw = dict(RT_PATH_SAMP_MB="1")
-    on, off = _context(**kw), _context(**kw, **OFF)
-    yield on, off
-    on.close()
-    off.close()
-
-
-def _bits_equal(a, b, msg=""):
-    np.testing.assert_array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32), err_msg=msg)
-
-
-def _cat(cat_golden, slot=6, albedo=rt.scenes.CAT_ALBEDO, scale=1.0):
-    v = np.asarray(cat_golden["vertices"], np.float32)
-    bv = np.array(cat_golden["bvh_arr10"], np.float32)
-    if scale != 1.0:                                   # another mesh: the same topology, every coordinate (and every box) scaled by a power of two
-        v = v * np.float32(scale)
-        bv[:, 2:8] *= np.float32(scale)
-    return dict(vertices=v, indices=cat_golden["tri_bvh_order"], bvh_arr10=bv, albedo=albedo, object_slot=slot)
-
-
-def _params(w=W, h=H, b=B, spp=1, **kw):
-    d = dict(rt.scenes.CPU_LAUNCHER)
-    d.update(kw)
-    return rt.make_params(w, h, spp, b, **d)
-
-
-def _upload(pair, cat_golden, **kw):
-    for c in pair:
-        c.scene_upload(rt.scenes.spheres("cpu"), _cat(cat_golden), **kw)
-
-
-def _delta(ctx, fn):
-    """(what fn returns, how far each counter of ctx moved meanwhile)"""
-    before = ctx.first_hit_cache_counts()
-    r = fn()
-    after = ctx.first_hit_cache_counts()
-    return r, {k: after[k] - before[k] for k in after}
-
-
-def _parts(ctx):
-    return ctx.stats()["parts"]
-
-
-def _expect(d, **kw):
-    want = dict(ZERO)
-    want.update(kw)
-    assert d == want, (d, want)
-
-
-def _frame(pair, p, render=None, cold=False, **expect):
-    """one frame on both contexts: equal word for word, the cached context's counters moved by `expect` (in chains per sub-frame), the reference context's chains all
-    ineligible.  cold: the first frame after an upload -- a key miss if an earlier test left the context's cache filled, none on a new context: not compared"""
-    on, off = pair
-    render = render or (lambda c: c.render(p))
-    got, d = _delta(on, lambda: render(on))
-    exp, e = _delta(off, lambda: render(off))
-    _bits_equal(got, exp)
-    n = _parts(on)
-    assert n == 2
-    if cold:
-        d["key_misses"] = 0
-    _expect(d, **{k: v * n if k != "key_misses" else v for k, v in expect.items()})
-    assert e["skipped"] == e["filled"] == e["key_misses"] == 0 and e["ineligible"] > 0
-    assert got[..., 3].sum() > 0
-    return got
+    yield from _pair(RT_PATH_SAMP_MB="1")
 
 
 def test_the_same_frame_three_times(pair, cat_golden):
@@ -257,15 +173,6 @@ def test_a_texture_change_keeps_the_cache(pair, cat_golden):
     assert not np.array_equal(a, b)
 
 
-def _chunk(spp, samp_bytes, b, w=W, h=H, parts=2):
-    """cut_wavefront's samples per chain"""
-    px_all = ((w + 7) // 8) * ((h + 7) // 8 + parts) * 64
-    per_item = 16 + 16 + 64 + 16 + 5 * (b + 1)
-    cmax = max(1, min(spp, samp_bytes // (px_all * per_item), ((1 << 29) - 1) // (px_all // parts + 64)))
-    chains = (spp + cmax - 1) // cmax
-    return (spp + chains - 1) // chains
-
-
 @pytest.mark.parametrize("which", ["default_chunk", "one_sample_per_chain"])
 def test_five_samples_per_pixel(pair, pair_one_sample_per_chain, cat_golden, which):
     cs = pair if which == "default_chunk" else pair_one_sample_per_chain
@@ -288,14 +195,6 @@ def test_five_samples_per_pixel(pair, pair_one_sample_per_chain, cat_golden, whi
     _frame(cs, p, skipped=chains)                      # ... and leaves it as it was
 
 
-def _render_rows(c, p, rows, n_rows):
-    import torch
-    buf = torch.zeros((n_rows, p.width, 4), dtype=torch.float32, device="cuda")
-    c.render_device(p, rows, buf.data_ptr())
-    c.synchronize()
-    return buf.cpu().numpy()
-
-
 def test_row_shares_and_sizes_alternate(pair, cat_golden):
     _upload(pair, cat_golden)
     p = _params()
@@ -314,45 +213,14 @@ def test_row_shares_and_sizes_alternate(pair, cat_golden):
 
 
 def test_pipelined_frames_into_two_buffers(pair, cat_golden):
-    import torch
-    _upload(pair, cat_golden)
-    on, off = pair
-    rows = rt._capi.Rows(0, H, H, 1)
-    bufs = [torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-    seeds = [11, 12, 13, 14, 15, 16]
-    exp = [off.render(_params(seed=s)) for s in seeds]
-    on.set_pipelining(True)
-    try:
-        got = []
-
-        def six():
-            for k, s in enumerate(seeds):
-                on.render_device(_params(seed=s), rows, bufs[k % 2].data_ptr())
-                if k % 2 == 1:                         # both buffers hold a frame: read them before the next two overwrite them
-                    on.synchronize()
-                    got.extend(b.cpu().numpy() for b in bufs)
-        _, d = _delta(on, six)
-    finally:
-        on.set_pipelining(False)
-    n = _parts(on)
-    assert d["filled"] == n and d["skipped"] == 5 * n and d["ineligible"] == 0, d
-    for g, e in zip(got, exp):
-        _bits_equal(g, e)
+    sv.pipelined_frames(LEVEL, pair, cat_golden, filled=1, used=5)
 
 
 def test_a_batch_with_a_camera_per_frame_is_ineligible(pair, cat_golden):
-    import torch
     _upload(pair, cat_golden)
     p = _params()
-    rows = rt._capi.Rows(0, H, H, 1)
-
-    def batch(c):
-        bufs = [torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(3)]
-        c.render_device_batch(p, rows, [(bf.data_ptr(), (0.5 * k, 0.0, 55.0 - 3 * k), None, 40 + k) for k, bf in enumerate(bufs)])
-        c.synchronize()
-        return np.stack([bf.cpu().numpy() for bf in bufs])
-    got, d = _delta(pair[0], lambda: batch(pair[0]))
-    _bits_equal(got, batch(pair[1]))
+    got, d = _delta(pair[0], lambda: sv.batch_of_three(pair[0], p))
+    _bits_equal(got, sv.batch_of_three(pair[1], p))
     assert d["ineligible"] > 0 and d["skipped"] == d["filled"] == 0, d
     assert not np.array_equal(got[0], got[1])
 

@@ -1,12 +1,11 @@
-"""The first-shadow cache on the device (rt_ctx::FirstShadow, enqueue_chain, the two wf_advance launches that emit and close segment 0's shadow rays): a default context
+"""The first-shadow cache on the device (the shadow level of csrc/rt_still.h, enqueue_chain, the two wf_advance launches that emit and close segment 0's shadow rays): a default context
 against one created under RT_FIRST_SHADOW_CACHE=0, word for word, colour and .w -- and rt_first_shadow_cache_counts, which says whether a chain read the cache, filled it
 or was not eligible, so that every comparison below is known to have gone through the path it names.  -m gpu.
 
 The cat at 64 x 48 with num_bounce 2 (two sub-frames of three 8-row tiles: two launch chains per frame and sample chunk), the shapes of test_gpu_first_hit_cache.py.  The
 reference of every comparison is the knob-off context, never the cached one.  The scenes of tests/material_scenes.py hold no mirror or glass SPHERE: the three used here
 show the camera a mirror mesh, a glass mesh and two meshes (one of them a mirror) -- first hits without a shadow ray next to first hits with one."""
-import os
-from contextlib import contextmanager
+from functools import partial
 
 import numpy as np
 import pytest
@@ -14,40 +13,15 @@ import pytest
 import raytracinggpu_amd as rt
 
 from . import material_scenes as ms
+from . import still_view as sv
+from .still_view import B, H, W
 
 pytestmark = pytest.mark.gpu
 
-W, H, B = 64, 48, 2
-OFF = dict(RT_FIRST_SHADOW_CACHE="0")
-ZERO = dict(skipped=0, filled=0, ineligible=0, key_misses=0)
-
-
-@contextmanager
-def _env(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update(kw)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _context(**kw):
-    with _env(**kw):                                   # the knobs are read once, when the context is created
-        return rt.Context(0)
-
-
-def _pair(on_kw=None, **both):
-    on, off = _context(**both, **(on_kw or {})), _context(**both, **OFF)
-    try:
-        yield on, off
-    finally:
-        on.close()
-        off.close()
+LEVEL = sv.SHADOW
+ZERO = sv.zero(LEVEL)
+_bits_equal, _params, _upload, _chunk, _render_rows = sv.bits_equal, sv.params, sv.upload, sv.chunk, sv.render_rows
+_pair, _delta, _expect, _frame = partial(sv.pair, LEVEL), partial(sv.delta, LEVEL), partial(sv.expect, LEVEL), partial(sv.frame, LEVEL)
 
 
 @pytest.fixture(scope="module")
@@ -59,58 +33,6 @@ def pair():
 def pair_one_sample_per_chain():
     """RT_PATH_SAMP_MB=1: a chain's state may take 1 MB; a sample of 64 x 48 with 13 segments takes 0.73: one sample per chain"""
     yield from _pair(RT_PATH_SAMP_MB="1")
-
-
-def _bits_equal(a, b, msg=""):
-    np.testing.assert_array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32), err_msg=msg)
-
-
-def _cat(cat_golden, slot=6, albedo=rt.scenes.CAT_ALBEDO):
-    return dict(vertices=np.asarray(cat_golden["vertices"], np.float32), indices=cat_golden["tri_bvh_order"], bvh_arr10=cat_golden["bvh_arr10"], albedo=albedo,
-                object_slot=slot)
-
-
-def _params(w=W, h=H, b=B, spp=1, **kw):
-    d = dict(rt.scenes.CPU_LAUNCHER)
-    d.update(kw)
-    return rt.make_params(w, h, spp, b, **d)
-
-
-def _upload(pair, cat_golden, albedo=rt.scenes.CAT_ALBEDO, **kw):
-    for c in pair:
-        c.scene_upload(rt.scenes.spheres("cpu"), _cat(cat_golden, albedo=albedo), **kw)
-
-
-def _delta(ctx, fn, counts="first_shadow_cache_counts"):
-    """(what fn returns, how far each counter of ctx moved meanwhile)"""
-    before = getattr(ctx, counts)()
-    r = fn()
-    after = getattr(ctx, counts)()
-    return r, {k: after[k] - before[k] for k in after}
-
-
-def _expect(d, **kw):
-    want = dict(ZERO)
-    want.update(kw)
-    assert d == want, (d, want)
-
-
-def _frame(pair, p, render=None, cold=False, **expect):
-    """one frame on both contexts: equal word for word, the cached context's counters moved by `expect` (in chains per sub-frame), the reference context's chains all
-    ineligible.  cold: the first frame after an upload -- a key miss if an earlier test left the context's cache filled, none on a new context: not compared"""
-    on, off = pair
-    render = render or (lambda c: c.render(p))
-    got, d = _delta(on, lambda: render(on))
-    exp, e = _delta(off, lambda: render(off))
-    _bits_equal(got, exp)
-    n = on.stats()["parts"]
-    assert n == 2
-    if cold:
-        d["key_misses"] = 0
-    _expect(d, **{k: v * n if k != "key_misses" else v for k, v in expect.items()})
-    assert e["skipped"] == e["filled"] == e["key_misses"] == 0 and e["ineligible"] > 0
-    assert got[..., 3].sum() > 0
-    return got
 
 
 def _miss_then_skip(pair, p, render=None):
@@ -235,15 +157,6 @@ def test_frame_camera_and_mesh_edits_miss(pair, cat_golden):
     assert not np.array_equal(a, b)
 
 
-def _chunk(spp, samp_bytes, b, w=W, h=H, parts=2):
-    """cut_wavefront's samples per chain"""
-    px_all = ((w + 7) // 8) * ((h + 7) // 8 + parts) * 64
-    per_item = 16 + 16 + 64 + 16 + 5 * (b + 1)
-    cmax = max(1, min(spp, samp_bytes // (px_all * per_item), ((1 << 29) - 1) // (px_all // parts + 64)))
-    chains = (spp + cmax - 1) // cmax
-    return (spp + chains - 1) // chains
-
-
 @pytest.mark.parametrize("which", ["default_chunk", "one_sample_per_chain"])
 def test_five_samples_per_pixel(pair, pair_one_sample_per_chain, cat_golden, which):
     cs = pair if which == "default_chunk" else pair_one_sample_per_chain
@@ -296,14 +209,6 @@ def test_without_the_first_hit_cache_it_is_off(cat_golden):
         assert cs[0].first_shadow_cache_counts() == dict(ZERO, ineligible=6)
 
 
-def _render_rows(c, p, rows, n_rows):
-    import torch
-    buf = torch.zeros((n_rows, p.width, 4), dtype=torch.float32, device="cuda")
-    c.render_device(p, rows, buf.data_ptr())
-    c.synchronize()
-    return buf.cpu().numpy()
-
-
 def test_row_shares_and_sizes_alternate(pair, cat_golden):
     _upload(pair, cat_golden)
     p = _params()
@@ -322,47 +227,16 @@ def test_row_shares_and_sizes_alternate(pair, cat_golden):
 
 
 def test_pipelined_frames_into_two_buffers(pair, cat_golden):
-    import torch
-    _upload(pair, cat_golden)
-    on, off = pair
-    rows = rt._capi.Rows(0, H, H, 1)
-    bufs = [torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
-    seeds = [11, 12, 13, 14, 15, 16]
-    exp = [off.render(_params(seed=s)) for s in seeds]
-    on.set_pipelining(True)
-    try:
-        got = []
-
-        def six():
-            for k, s in enumerate(seeds):
-                on.render_device(_params(seed=s), rows, bufs[k % 2].data_ptr())
-                if k % 2 == 1:                         # both buffers hold a frame: read them before the next two overwrite them
-                    on.synchronize()
-                    got.extend(b.cpu().numpy() for b in bufs)
-        _, d = _delta(on, six)
-    finally:
-        on.set_pipelining(False)
-    n = on.stats()["parts"]
-    assert d["filled"] == n and d["skipped"] == 5 * n and d["ineligible"] == 0, d
-    for g, e in zip(got, exp):
-        _bits_equal(g, e)
+    sv.pipelined_frames(LEVEL, pair, cat_golden, filled=1, used=5)
 
 
 def test_batches_stats_and_count_lists_go_round_the_cache(pair, cat_golden):
-    import torch
     _upload(pair, cat_golden)
     on, off = pair
     p = _params()
-    rows = rt._capi.Rows(0, H, H, 1)
     base = _frame(pair, p, cold=True, filled=1)
-
-    def batch(c):
-        bufs = [torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(3)]
-        c.render_device_batch(p, rows, [(bf.data_ptr(), (0.5 * k, 0.0, 55.0 - 3 * k), None, 40 + k) for k, bf in enumerate(bufs)])
-        c.synchronize()
-        return np.stack([bf.cpu().numpy() for bf in bufs])
-    got, d = _delta(on, lambda: batch(on))
-    _bits_equal(got, batch(off))
+    got, d = _delta(on, lambda: sv.batch_of_three(on, p))
+    _bits_equal(got, sv.batch_of_three(off, p))
     assert d["ineligible"] > 0 and d["skipped"] == d["filled"] == d["key_misses"] == 0, d
     _frame(pair, p, skipped=1)
     on.stats_enable(True)

@@ -1,15 +1,16 @@
-"""GPU box: what the first-shade cache (RT_FIRST_SHADE_CACHE, rt_ctx::FirstShade) takes off a frame of a still view under a still light.
+"""GPU box: what one level of the still view (csrc/rt_still.h) takes off a frame -- --knob RT_FIRST_HIT_CACHE (a still camera),
+RT_FIRST_SHADOW_CACHE or RT_FIRST_SHADE_CACHE (a still view under a still light) -- and whether a change of the host code moved a frame at all.
 
 For the headline frame and then for BASELINE config 2 (--width 512 --height 512 --spp 8), each step a process of its own under its own time limit, the first failure
 ending the run:
-  1. (--stage inproc) the counters of the three caches over five frames of the workload on one context (the first-shadow cache fills, the records are stored, then
-     every chain resumes), so that the figures below are known to be a resumed frame's; then, in one process, 40 pipelined frames of a still view against 40 frames
-     that each miss -- the light's x alternates between two neighbouring floats: a first-shadow miss and a refill every frame, no first-shade fill ever -- with the
-     knob on and off, three times; the same stage once more on the parent commit's library (--parent-lib, through RT_LIB), for the parent's figure of the moving light;
+  1. (--stage inproc) the counters of the three levels over five frames of the workload on one context (fill, read and store, then every chain resumes), so that the
+     figures below are known to be a resumed frame's; then, in one process, 40 pipelined frames of a still view against 40 frames that each miss the knob's level and
+     nothing below it -- tri_tmin (first-hit) or the light's x (the other two) alternates between two neighbouring floats -- with the knob on and off, three times;
+     the same stage once more on the parent commit's library (--parent-lib, through RT_LIB);
   2. bench.py --gpus 1 --steps 60 --warmup 5, interleaved, --runs (at least five) each in a fresh process: this build, the parent commit's library and this build with
-     RT_FIRST_SHADE_CACHE=0; with --dump-dir the first run of this build and of the parent also write --dump-outputs, and frame.npy of the two is compared bit for bit.
+     the knob off; with --dump-dir the first run of this build and of the parent also write --dump-outputs, and frame.npy of the two is compared bit for bit.
 
-usage: python tools/first_shade_cache_ab.py --parent-lib PATH [--runs 5] [--dump-dir DIR] [--only headline|spp8] > profiles/first_shade_cache/ab_bench.txt"""
+usage: python tools/still_view_ab.py --knob RT_FIRST_SHADE_CACHE --parent-lib PATH [--runs 5] [--dump-dir DIR] [--only headline|spp8] > profiles/still_view/ab_bench.txt"""
 import argparse
 import json
 import os
@@ -18,8 +19,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-KNOB = "RT_FIRST_SHADE_CACHE"
+KNOBS = ["RT_FIRST_HIT_CACHE", "RT_FIRST_SHADOW_CACHE", "RT_FIRST_SHADE_CACHE"]
 ap = argparse.ArgumentParser()
+ap.add_argument("--knob", required=True, choices=KNOBS)
 ap.add_argument("--parent-lib", default="")
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--dump-dir", default="")
@@ -30,6 +32,7 @@ ap.add_argument("--height", type=int, default=1080)
 ap.add_argument("--spp", type=int, default=1)
 ap.add_argument("--bounces", type=int, default=3)
 args = ap.parse_args()
+KNOB = args.knob
 
 
 def inproc():
@@ -40,22 +43,26 @@ def inproc():
     from raytracinggpu_amd._capi import Rows
     v, t = rt.scenes.load_cat_arrays()
     mesh = hostlib.build_mesh(v, t, albedo=rt.scenes.CAT_ALBEDO, object_slot=rt.scenes.mesh_slot("cpu"))
-    p = rt.make_params(args.width, args.height, args.spp, args.bounces, **rt.scenes.CPU_LAUNCHER)
+    params = lambda **kw: rt.make_params(args.width, args.height, args.spp, args.bounces, **dict(rt.scenes.CPU_LAUNCHER, **kw))
+    p = params()
     c = rt.Context(0)
     c.scene_upload(rt.scenes.spheres("cpu"), mesh)
     which = "parent library" if os.environ.get("RT_LIB") else "this build"
 
     def counters(ctx):
-        shade = json.dumps(ctx.first_shade_cache_counts()) if hasattr(ctx._L, "rt_first_shade_cache_counts") and not os.environ.get("RT_LIB") else "(no such entry)"
-        return "first-shade %s, first-shadow %s, first-hit %s" % (shade, json.dumps(ctx.first_shadow_cache_counts()), json.dumps(ctx.first_hit_cache_counts()))
+        return ", ".join("%s %s" % (k[3:-6].lower().replace("_", "-"), json.dumps(getattr(ctx, k[3:].lower() + "_counts")())) for k in reversed(KNOBS))
     for k in range(5):
         c.render(p)
         print("%s, frame %d on one context: %s" % (which, k, counters(c)), flush=True)
     c.close()
     (lx, ly, lz), intensity = (-10.0, 20.0, 40.0), 3e10                # scene_upload's light
     lx1 = float(np.nextafter(np.float32(lx), np.float32(0.0)))
+    t_a = 1e-4
+    t_b = float(np.nextafter(np.float32(t_a), np.float32(1.0)))
+    # what a frame that misses alternates: (params, light x) of frame k
+    miss = [(params(tri_tmin=t_a), lx), (params(tri_tmin=t_b), lx)] if KNOB == KNOBS[0] else [(p, lx), (p, lx1)]
 
-    def per_frame(ctx, lights, warm=10, n=40):
+    def per_frame(ctx, frames, warm=10, n=40):
         rows = Rows(0, args.height, args.height, 1)
         bufs = [torch.zeros((args.height, args.width, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
         stream = torch.cuda.Stream()
@@ -64,8 +71,9 @@ def inproc():
         for k in range(warm + n):
             if k == warm:
                 t0.record(stream)
-            ctx.set_light((lights[k % len(lights)], ly, lz), intensity)   # (a host-side edit of the scene the next frame's launches carry: the still view sets the same light again)
-            ctx.render_device(p, rows, bufs[k % 2].data_ptr(), stream.cuda_stream)
+            q, x = frames[k % len(frames)]
+            ctx.set_light((x, ly, lz), intensity)       # (a host-side edit of the scene the next frame's launches carry: the still view sets the same light again)
+            ctx.render_device(q, rows, bufs[k % 2].data_ptr(), stream.cuda_stream)
         t1.record(stream)
         t1.synchronize()
         ctx.set_pipelining(False)
@@ -76,8 +84,8 @@ def inproc():
         c = rt.Context(0)
         c.scene_upload(rt.scenes.spheres("cpu"), mesh)
         for rep in range(3):
-            a, b = per_frame(c, [lx]), per_frame(c, [lx, lx1])
-            print("%s, %s=%s in one process, 40 pipelined frames: still light %.4f ms per frame, every frame a miss %.4f ms" % (which, KNOB, knob, a, b), flush=True)
+            a, b = per_frame(c, [(p, lx)]), per_frame(c, miss)
+            print("%s, %s=%s in one process, 40 pipelined frames: still view %.4f ms per frame, every frame a miss %.4f ms" % (which, KNOB, knob, a, b), flush=True)
         print("%s, %s=%s counters: %s" % (which, KNOB, knob, counters(c)), flush=True)
         c.close()
 
@@ -98,9 +106,10 @@ def step(cmd, env, limit):
 def workload(width, height, spp, bounces, dump_dir):
     shape = ["--width", str(width), "--height", str(height), "--spp", str(spp), "--bounces", str(bounces)]
     print("workload: cat %dx%d, %d sample(s), %d bounces; bench.py --gpus 1 --steps 60 --warmup 5" % (width, height, spp, bounces), flush=True)
-    print(step([sys.executable, os.path.abspath(__file__), "--stage", "inproc"] + shape, dict(os.environ), 240), end="", flush=True)
+    stage = [sys.executable, os.path.abspath(__file__), "--knob", KNOB, "--stage", "inproc"] + shape
+    print(step(stage, dict(os.environ), 240), end="", flush=True)
     if args.parent_lib:
-        print(step([sys.executable, os.path.abspath(__file__), "--stage", "inproc"] + shape, dict(os.environ, RT_LIB=os.path.abspath(args.parent_lib)), 240), end="", flush=True)
+        print(step(stage, dict(os.environ, RT_LIB=os.path.abspath(args.parent_lib)), 240), end="", flush=True)
     off = "branch %s=0" % KNOB
     builds = [("branch", {}), (off, {KNOB: "0"})]
     if args.parent_lib:
@@ -121,10 +130,10 @@ def workload(width, height, spp, bounces, dump_dir):
         print("%-32s median %.4f ms (min %.4f, max %.4f, spread %.4f)" % (name + ":", med[name], x[0], x[-1], x[-1] - x[0]))
     if args.parent_lib:
         sp = max(ms["parent"]) - min(ms["parent"])
-        print("branch - parent: %+.4f ms (%+.2f %%); three times the parent's spread: %.4f ms; every run of the branch below every run of the parent: %s" % (
-            med["branch"] - med["parent"], 100 * (med["branch"] / med["parent"] - 1), 3 * sp, max(ms["branch"]) < min(ms["parent"])))
-        print("knob off - parent: %+.4f ms (%+.2f %%); three times the parent's spread: %.4f ms" % (med[off] - med["parent"], 100 * (med[off] / med["parent"] - 1), 3 * sp))
-    print("the cache alone (branch - %s): %+.4f ms (%+.2f %%)" % (off, med["branch"] - med[off], 100 * (med["branch"] / med[off] - 1)))
+        print("branch - parent: %+.4f ms (%+.2f %%); the parent's spread: %.4f ms, three times the parent's spread: %.4f ms; every run of the branch below every run of the "
+              "parent: %s" % (med["branch"] - med["parent"], 100 * (med["branch"] / med["parent"] - 1), sp, 3 * sp, max(ms["branch"]) < min(ms["parent"])))
+        print("knob off - parent: %+.4f ms (%+.2f %%)" % (med[off] - med["parent"], 100 * (med[off] / med["parent"] - 1)))
+    print("the level alone (branch - %s): %+.4f ms (%+.2f %%)" % (off, med["branch"] - med[off], 100 * (med["branch"] / med[off] - 1)))
     if args.parent_lib and dump_dir:
         import numpy as np
         a, b = (np.load(os.path.join(dump_dir, n, "frame.npy")) for n in ("branch", "parent"))
