@@ -45,6 +45,15 @@ int64_t rth_qrows_enumerate(int n_paths, int log2S, int Q, int tblocks, int whic
  * 0 none 1 Y 2 X, it writes the hit block, m0, x0, wf_advance 0 begin 1 resume 2 plain 3 fill, kill_x, and the chain's modes of the three levels 0 off 1 fill 2 use). */
 int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32_t *rows, int64_t cap);
 
+/* Test entries of the cut of a call's rows (csrc/rt_rowcut.h, shared with the render path).  rth_row_cut: n cases of seven numbers -- an rt_rows (row0, n_rows, tile_rows,
+ * tile_step), the sub-frames wanted (RT_PARTS), one (a counting run: one sub-frame), whole (a batch cut by frames: every sub-frame holds all rows) -- each give 52 numbers:
+ * (parts, R, G, T) and per sub-frame the row fields of its frame (row0, n_rows, tile_rows, tile_step, out_tile0, out_tile_step), zero past `parts`.
+ * rth_row_chunks: n cases of six numbers -- an rt_rows, the frame's width, the chunk size in pixels (RT_CHUNK_MPX * 1e6) -- each give 3 + 5 * cap numbers: (unit, per,
+ * chunks; 0, n_rows, 1 for a call that is not cut) and per chunk, up to cap of them, (its first local row of the call, and the rt_rows it is rendered as).  Returns the
+ * largest number of chunks of a case. */
+void rth_row_cut(const int32_t *cases, int n, int32_t *out);
+int rth_row_chunks(const int32_t *cases, int n, int32_t *out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 #include "../../../include/raytracer.hpp"
 #include "../rt_qrows.h"
 #include "../rt_still.h"
+#include "../rt_rowcut.h"
 
 using namespace raytracer;
 
@@ -112,6 +113,47 @@ int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32
     const StillLevel *lv[3] = {&v.hit, &v.shadow, &v.records};
     for (int k = 0; k < 12; ++k) counts[k] = lv[k / 4]->counts[k % 4];
     return n;
+}
+
+// the cut of a call's rows into sub-frames (rt_rowcut.h), as cut_wavefront and launch_path ask for it
+void rth_row_cut(const int32_t *cases, int n, int32_t *out) {
+    using namespace rtk;
+    for (int i = 0; i < n; ++i) {
+        const int32_t *x = cases + 7 * i;
+        int32_t *o = out + 52 * i;
+        const Rows rows{x[0], x[1], x[2], x[3]};
+        const RowCut c = split_rows(rows, x[4], x[5] != 0);
+        memset(o, 0, 52 * sizeof(int32_t));
+        o[0] = c.parts; o[1] = c.R; o[2] = c.G; o[3] = c.T;
+        for (int j = 0; j < c.parts && j < kRowCutMaxParts; ++j) {
+            const RowPart p = c.part(rows, j, x[6] != 0);
+            const int32_t row[6] = {p.row0, p.n_rows, p.tile_rows, p.tile_step, p.out_tile0, p.out_tile_step};
+            memcpy(o + 4 + 6 * j, row, sizeof(row));
+        }
+    }
+}
+
+// ... and into chunks, as launch_render walks them
+int rth_row_chunks(const int32_t *cases, int n, int32_t *out, int cap) {
+    using namespace rtk;
+    int most = 0;
+    for (int i = 0; i < n; ++i) {
+        const int32_t *x = cases + 6 * i;
+        int32_t *o = out + (size_t)(3 + 5 * cap) * i;
+        const Rows rows{x[0], x[1], x[2], x[3]};
+        memset(o, 0, (size_t)(3 + 5 * cap) * sizeof(int32_t));
+        RowChunks ch{0, rows.n_rows, 1};
+        const bool cut = rows_need_chunks(rows, x[4], x[5]);
+        if (cut) ch = chunk_rows(rows, x[4], x[5]);
+        o[0] = ch.unit; o[1] = ch.per; o[2] = ch.n;
+        most = ch.n > most ? ch.n : most;
+        for (int k = 0; k < ch.n && k < cap; ++k) {
+            const Rows r = cut ? ch.chunk(rows, k) : rows;
+            const int32_t row[5] = {cut ? ch.first(k) : 0, r.row0, r.n_rows, r.tile_rows, r.tile_step};
+            memcpy(o + 3 + 5 * k, row, sizeof(row));
+        }
+    }
+    return most;
 }
 
 }  // extern "C"

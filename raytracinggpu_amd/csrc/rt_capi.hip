@@ -13,6 +13,7 @@
 #include "rt_lbvh.hip.h"
 #include "rt_adaptive.hip.h"
 #include "rt_still.h"
+#include "rt_rowcut.h"
 
 #include <cmath>
 #include <cstdarg>

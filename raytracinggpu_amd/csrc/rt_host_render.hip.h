@@ -108,26 +108,12 @@ int blocks_per_cu(rt_ctx *ctx, int slot, const void *fn, int threads, size_t lds
     return RT_OK;
 }
 
-// The cut of a call's rows into `parts` independent sub-frames of interleaved tiles (R rows high, every G-th tile of the image; T of them in this call)
-struct RowCut {
-    int parts, R, G, T;
-    // sub-frame j's rows (local tiles j, j + parts, ...) and where its tiles lie in the call's output; whole: every sub-frame holds all rows (a batch cut by frames)
-    void part(const rt_rows &rows, int j, bool whole, rtk::Frame &fr) const {
-        const int of = whole ? 1 : parts;
-        if (whole) j = 0;
-        const int Tj = (T - j + of - 1) / of;
-        int n = Tj * R;
-        if (Tj > 0 && (T - 1) % of == j) n -= T * R - rows.n_rows;   // the last local tile may be partial
-        fr.row0 = rows.row0 + j * R * G; fr.n_rows = n; fr.tile_rows = R; fr.tile_step = G * of; fr.out_tile0 = j; fr.out_tile_step = of;
-    }
-};
-RowCut split_rows(const rt_rows &rows, int want, bool one) {
-    RowCut c{std::min(want, (int)rt_ctx::kMaxParts), rows.tile_rows, rows.tile_step, 0};
-    if (c.G == 1) c.R = 8;                                        // contiguous rows: any tile height describes them
-    c.T = (rows.n_rows + c.R - 1) / c.R;                          // local tiles of this call
-    if (c.R % 8 != 0 || one) c.parts = 1;
-    if (c.parts > c.T) c.parts = c.T > 0 ? c.T : 1;
-    return c;
+// The cut of a call's rows into sub-frames (rt_rowcut.h): sub-frame j of the cut as the row fields of its Frame
+static_assert(rt_ctx::kMaxParts == rtk::kRowCutMaxParts, "rt_rowcut.h");
+rtk::Rows as_rows(const rt_rows &r) { return rtk::Rows{r.row0, r.n_rows, r.tile_rows, r.tile_step}; }
+void cut_part(const rtk::RowCut &cut, const rt_rows &rows, int j, bool whole, rtk::Frame &fr) {
+    const rtk::RowPart p = cut.part(as_rows(rows), j, whole);
+    fr.row0 = p.row0; fr.n_rows = p.n_rows; fr.tile_rows = p.tile_rows; fr.tile_step = p.tile_step; fr.out_tile0 = p.out_tile0; fr.out_tile_step = p.out_tile_step;
 }
 
 // LDS of the node-staging per-lane traversal kernel (wavefront_lds): all nodes + 16 per-wave carves in one 1024-thread workgroup
@@ -251,7 +237,7 @@ int launch_path(rt_ctx *ctx, const Chunk &c) {
     RT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, rtk::kQBlock, lds));
     if (nb < 1) return fail(ctx, RT_ERR_UNSUPPORTED, "wf_path does not fit a CU with %zu bytes of LDS per workgroup", lds);
     const int bpc = std::min(kn.path_bpc, nb);
-    const RowCut cut = split_rows(*c.rows, kn.path_parts, c.work_dev != nullptr);
+    const rtk::RowCut cut = rtk::split_rows(as_rows(*c.rows), kn.path_parts, c.work_dev != nullptr);
     const int parts = cut.parts;
     const int tiles_x = (c.p->width + 7) / 8;
     const int qcap = capped_stack(kn, rtk::kPStack);
@@ -260,7 +246,7 @@ int launch_path(rt_ctx *ctx, const Chunk &c) {
     size_t np_total = 0;
     for (int j = 0; j < parts; ++j) {
         pv[j].fr = fr;
-        cut.part(*c.rows, j, false, pv[j].fr);
+        cut_part(cut, *c.rows, j, false, pv[j].fr);
         const int64_t n_paths64 = (int64_t)tiles_x * ((pv[j].fr.n_rows + 7) / 8) * 64;
         if (n_paths64 >= ((int64_t)1 << 29)) return fail(ctx, RT_ERR_INVALID, "image too large: %lld pixel slots per sub-frame (limit 2^29)", (long long)n_paths64);
         pv[j].n_paths = (int)n_paths64; pv[j].base = np_total;
@@ -441,7 +427,7 @@ int cut_wavefront(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w) {
     const rtk::Frame &fr = c.fr;
     const rtk::Batch *batch = c.batch;
     // (one sub-frame for SMALL frames was measured in round 6: 512x512 back to back 0.297 -> 0.328 ms at one sample, 0.82 -> 1.03 ms at eight: two stay, profiles/round6/small_frame_parts.txt)
-    const RowCut cut = split_rows(*c.rows, kn.parts, c.work_dev || kn.debug_trav != -2);
+    const rtk::RowCut cut = rtk::split_rows(as_rows(*c.rows), kn.parts, c.work_dev || kn.debug_trav != -2);
     const int parts = cut.parts;
     w.tiles_x = (c.p->width + 7) / 8;
     // samples of a pixel are independent paths: a launch chain traces `chunk` of them at once (bigger launches, fewer tails) as
@@ -463,7 +449,7 @@ int cut_wavefront(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w) {
     for (int j = 0; j < parts; ++j) {
         WfPart &pt = w.pv[j];
         pt.fr = fr;
-        cut.part(*c.rows, j, by_frames, pt.fr);
+        cut_part(cut, *c.rows, j, by_frames, pt.fr);
         const int chunk_j = by_frames ? batch->n / parts : w.chunk;
         pt.batch0 = by_frames ? j * chunk_j : 0;
         pt.batch_n = by_frames ? chunk_j : batch ? batch->n : 0;
@@ -814,8 +800,7 @@ int launch_render_chunk(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, vo
     if (rows->n_rows < 0 || rows->row0 < 0 || rows->tile_rows <= 0 || rows->tile_step <= 0)
         return fail(ctx, RT_ERR_INVALID, "bad row specification");
     if (rows->n_rows > 0) {
-        const int64_t last = rows->n_rows - 1;
-        const int64_t last_row = rows->row0 + (last / rows->tile_rows) * rows->tile_rows * (int64_t)rows->tile_step + (last % rows->tile_rows);
+        const int64_t last_row = rtk::rows_image_row(as_rows(*rows), rows->n_rows - 1);
         if (last_row >= p->height) return fail(ctx, RT_ERR_INVALID, "rows reach image row %lld >= height %d", (long long)last_row, p->height);
     }
     Variant v;
@@ -859,25 +844,17 @@ int launch_render(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, void *ou
     rt_ctx::Pipe &pl = ctx->pipe;
     const uint8_t *out_lo = static_cast<const uint8_t *>(out_dev);
     const BetweenGuard between = begin_render_call(pl, out_lo, out_lo + ((p && rows && p->width > 0 && rows->n_rows > 0) ? (size_t)rows->n_rows * p->width * sizeof(float4) : 0));
-    if (!p || !rows || !wf || chunk_px <= 0 || p->width <= 0 || rows->tile_rows <= 0 || (int64_t)rows->n_rows * p->width <= chunk_px * 5 / 4) {
+    if (!p || !rows || !wf || p->width <= 0 || rows->tile_rows <= 0 || !rtk::rows_need_chunks(as_rows(*rows), p->width, chunk_px)) {
         return launch_render_chunk(ctx, p, rows, out_dev, stream, work_dev, pose, true, true);
     }
-    // rows per chunk: whole tiles (and whole 8-row wave tiles for contiguous rows), two sub-frames' worth at least
-    // (contiguous rows: tile_rows only says how the caller described them -- rt_render passes one tile of n_rows -- and every chunk is
-    // re-described below; only interleaved tiles must be cut at tile boundaries)
-    int unit = rows->tile_step == 1 ? 16 : rows->tile_rows * 2;
-    if (rows->tile_step != 1 && unit % rows->tile_rows != 0) unit *= rows->tile_rows;
-    const int64_t n_chunks = ((int64_t)rows->n_rows * p->width + chunk_px - 1) / chunk_px;
-    int per = (int)(((int64_t)rows->n_rows + n_chunks - 1) / n_chunks);
-    per = (per + unit - 1) / unit * unit;
+    const rtk::RowChunks ch = rtk::chunk_rows(as_rows(*rows), p->width, chunk_px);   // (rt_rowcut.h)
     uint64_t pixels = 0;
-    pl.call_chunks = (rows->n_rows + per - 1) / per;
-    for (int a = 0; a < rows->n_rows; a += per, ++pl.call_chunk) {
-        const int nr = std::min(per, rows->n_rows - a);
-        rt_rows rc{rows->row0 + (a / rows->tile_rows) * rows->tile_rows * rows->tile_step, nr, rows->tile_rows, rows->tile_step};
-        if (rows->tile_step == 1) { rc.row0 = rows->row0 + a; rc.tile_rows = nr; }      // contiguous rows: one tile of any height describes them
-        const int r = launch_render_chunk(ctx, p, &rc, static_cast<uint8_t *>(out_dev) + (size_t)a * p->width * sizeof(float4), stream, work_dev, pose,
-                                          a == 0, a + per >= rows->n_rows);
+    pl.call_chunks = ch.n;
+    for (int k = 0; k < ch.n; ++k, ++pl.call_chunk) {
+        const rtk::Rows cr = ch.chunk(as_rows(*rows), k);
+        const rt_rows rc{cr.row0, cr.n_rows, cr.tile_rows, cr.tile_step};
+        const int r = launch_render_chunk(ctx, p, &rc, static_cast<uint8_t *>(out_dev) + (size_t)ch.first(k) * p->width * sizeof(float4), stream, work_dev, pose,
+                                          k == 0, k + 1 == ch.n);
         if (r != RT_OK) {                                                 // chains of earlier chunks may be running on their own streams: wait for them
             for (hipStream_t q : ctx->part_stream) if (q) (void)hipStreamSynchronize(q);
             pl.valid = false; pl.call_chunk = 0; pl.call_chunks = 1; pl.open_parts = 0;

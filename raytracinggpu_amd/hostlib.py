@@ -9,7 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RT_HOST_LIB") or os.path.join(HERE, "libraytrace_host.so")   # RT_HOST_LIB: the sanitizer build (tools/sanitize_cpu.sh)
 EXPORTS = ["rth_mesh_new", "rth_mesh_free", "rth_mesh_read_obj", "rth_mesh_set_arrays", "rth_mesh_rescale",
            "rth_mesh_build_bvh", "rth_mesh_num_vertices", "rth_mesh_num_triangles", "rth_mesh_num_nodes",
-           "rth_mesh_get_vertices", "rth_mesh_get_indices", "rth_mesh_get_bvh_array", "rth_write_png", "rth_qrows_enumerate", "rth_still_replay"]
+           "rth_mesh_get_vertices", "rth_mesh_get_indices", "rth_mesh_get_bvh_array", "rth_write_png", "rth_qrows_enumerate", "rth_still_replay",
+           "rth_row_cut", "rth_row_chunks"]
 _lib = None
 
 
@@ -36,6 +37,9 @@ def load():
         L.rth_qrows_enumerate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int64]
         L.rth_still_replay.restype = C.c_int64
         L.rth_still_replay.argtypes = [ip, C.c_int, C.POINTER(C.c_uint64), ip, C.c_int64]
+        L.rth_row_cut.restype = None
+        L.rth_row_cut.argtypes = [ip, C.c_int, ip]
+        L.rth_row_chunks.argtypes = [ip, C.c_int, ip, C.c_int]
         _lib = L
     return _lib
 
@@ -130,6 +134,29 @@ def still_replay(events):
     counts, rows = np.zeros(12, np.uint64), np.zeros((18 * len(events), 12), np.int32)      # at most an opening launch and RT_MAX_SEGMENTS + 1 positions per chain
     n = L.rth_still_replay(ev.ctypes.data_as(ip), len(ev), counts.ctypes.data_as(C.POINTER(C.c_uint64)), rows.ctypes.data_as(ip), len(rows))
     return counts.reshape(3, 4).astype(np.int64), rows[:n]
+
+
+def row_cut(cases):
+    """The cut of calls' rows into sub-frames (csrc/rt_rowcut.h, rth_row_cut): cases [n, 7] of (row0, n_rows, tile_rows, tile_step, parts wanted, one, whole) ->
+    ([n, 4] of (parts, R, G, T), [n, 8, 6] of the sub-frames' (row0, n_rows, tile_rows, tile_step, out_tile0, out_tile_step), zero past `parts`)."""
+    L = load()
+    ip = C.POINTER(C.c_int32)
+    x = np.ascontiguousarray(cases, np.int32).reshape(-1, 7)
+    out = np.zeros((len(x), 52), np.int32)
+    L.rth_row_cut(x.ctypes.data_as(ip), len(x), out.ctypes.data_as(ip))
+    return out[:, :4], out[:, 4:].reshape(-1, 8, 6)
+
+
+def row_chunks(cases, cap=32):
+    """The cut of calls' rows into sequential chunks (csrc/rt_rowcut.h, rth_row_chunks): cases [n, 6] of (row0, n_rows, tile_rows, tile_step, width, chunk pixels) ->
+    ([n, 3] of (unit, per, chunks), [n, cap, 5] of the chunks' (first local row, row0, n_rows, tile_rows, tile_step), zero past `chunks`)."""
+    L = load()
+    ip = C.POINTER(C.c_int32)
+    x = np.ascontiguousarray(cases, np.int32).reshape(-1, 6)
+    out = np.zeros((len(x), 3 + 5 * cap), np.int32)
+    most = L.rth_row_chunks(x.ctypes.data_as(ip), len(x), out.ctypes.data_as(ip), cap)
+    assert most <= cap, (most, cap)
+    return out[:, :3], out[:, 3:].reshape(-1, cap, 5)
 
 
 def write_png(path, rgb8):

@@ -87,16 +87,16 @@ def expect(level, d, **kw):
     assert d == want, (d, want)
 
 
-def frame(level, cs, p, render=None, cold=False, **want):
-    """one frame on both contexts: equal word for word, the cached context's counters moved by `want` (in chains per sub-frame), the reference context's chains all
-    ineligible.  cold: the first frame after an upload -- a key miss if an earlier test left the context's level filled, none on a new context: not compared"""
+def frame(level, cs, p, render=None, cold=False, parts=2, **want):
+    """one frame on both contexts: equal word for word, the cached context's counters moved by `want` (in chains per sub-frame, `parts` of them), the reference context's
+    chains all ineligible.  cold: the first frame after an upload -- a key miss if an earlier test left the context's level filled, none on a new context: not compared"""
     on, off = cs
     render = render or (lambda c: c.render(p))
     got, d = delta(level, on, lambda: render(on))
     exp, e = delta(level, off, lambda: render(off))
     bits_equal(got, exp)
     n = on.stats()["parts"]
-    assert n == 2
+    assert n == parts
     if cold:
         d["key_misses"] = 0
     expect(level, d, **{k: v * n if k != "key_misses" else v for k, v in want.items()})
@@ -132,23 +132,23 @@ def batch_of_three(c, p):
     return np.stack([bf.cpu().numpy() for bf in bufs])
 
 
-def pipelined_frames(level, cs, cat_golden, filled, used):
-    """six frames of a still view, pipelined into two buffers: equal to the reference context's, and in chains per sub-frame `filled` of them filled the level and `used`
-    used it (stream order alone keeps a chain behind the one that stored its part's words)"""
+def pipelined_frames(level, cs, cat_golden, filled, used, parts=2, w=W, h=H):
+    """six frames of a still view, pipelined into two buffers: equal to the reference context's, and in chains per sub-frame (`parts` of them) `filled` of them filled the
+    level and `used` used it (stream order alone keeps a chain behind the one that stored its part's words).  Returns (seeds, frames)."""
     import torch
     upload(cs, cat_golden)
     on, off = cs
-    rows = rt._capi.Rows(0, H, H, 1)
-    bufs = [torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+    rows = rt._capi.Rows(0, h, h, 1)
+    bufs = [torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
     seeds = [11, 12, 13, 14, 15, 16]
-    exp = [off.render(params(seed=s)) for s in seeds]
+    exp = [off.render(params(w, h, seed=s)) for s in seeds]
     on.set_pipelining(True)
     try:
         got = []
 
         def six():
             for k, s in enumerate(seeds):
-                on.render_device(params(seed=s), rows, bufs[k % 2].data_ptr())
+                on.render_device(params(w, h, seed=s), rows, bufs[k % 2].data_ptr())
                 if k % 2 == 1:                         # both buffers hold a frame: read them before the next two overwrite them
                     on.synchronize()
                     got.extend(b.cpu().numpy() for b in bufs)
@@ -156,6 +156,8 @@ def pipelined_frames(level, cs, cat_golden, filled, used):
     finally:
         on.set_pipelining(False)
     n = on.stats()["parts"]
+    assert n == parts
     assert d["filled"] == filled * n and d[level.used] == used * n and d["ineligible"] == 0, d
     for g, e in zip(got, exp):
         bits_equal(g, e)
+    return seeds, got
