@@ -701,6 +701,46 @@ typedef struct rt_svgf_params {
 int rt_svgf_filter_device(rt_ctx *ctx, const void *history_dev, const void *aov_dev, int width, int height, const rt_svgf_params *sp, void *out_rgba_dev, void *out_history_dev, void *stream);
 int rt_svgf_filter(rt_ctx *ctx, const float *history_host, const float *aov_host, int width, int height, const rt_svgf_params *sp, float *out_rgba_host, float *out_history_host);
 
+/* --- reprojecting a DEFORMING mesh: vertex snapshots and previous-frame planes (ABI 6, additive).  A motion record is rigid; a mesh that rt_mesh_set_vertices*
+ *     reshapes has none.  But a surface point of a mesh is named by (triangle, barycentrics), and where it was a frame ago is the same barycentric combination of
+ *     that triangle's PREVIOUS corners.  So the library keeps a mesh's previous vertices, and the call that writes the planes also writes where every pixel's point
+ *     and normal were in the previous frame -- two planes in the layout of planes 0 and 1, which rt_temporal_accumulate[_fast]* takes as its `aov` argument with
+ *     rp->motion == NULL: that kernel reads the current frame's point and normal from nowhere else, and moves them by nothing.
+ *     rt_mesh_snapshot_vertices(keep = 1): the current device positions of the mesh at object_slot (-1: of every mesh with triangles) are copied into a buffer of
+ *     the context's with the indexing of the vertices themselves, device to device on the context's own stream, in the order of the call (as
+ *     rt_mesh_set_vertices_device's read is ordered); the host does not wait (an rt_render_aov_motion_device issued on ANOTHER stream waits for the copy on
+ *     that stream); the object's bit of the snapshot mask is set.  keep = 0 clears the bit: the object
+ *     follows the motion table again.  rt_mesh_snapshot_mask reports the bits.  Call it once per frame BEFORE that frame's edits (any number of
+ *     rt_mesh_set_vertices* and rt_mesh_transform* calls; neither touches a snapshot).  rt_scene_upload* drops every snapshot; rt_mesh_rebuild* keeps them, in both
+ *     modes (a rebuild reorders triangles, not vertices).  A snapshot is nothing a render reads: the caches of a still view and their counters are as they were.
+ *     RT_ERR_NO_SCENE: no upload, or the last one failed.  RT_ERR_INVALID, nothing changed: keep outside {0, 1}, a sphere's slot, a slot outside the scene.  A mesh
+ *     without triangles: RT_OK, nothing happens.  rt_multi_* contexts have no snapshots.
+ *     rt_render_aov_motion*: rays, rows, stream, pipelining and errors as rt_render_aov*; ONE traversal.  out_aov: the three planes of rt_render_aov*, word for
+ *     word.  out_prev: two dense planes of n_rows * width float4, consecutive: plane 0 = (N', id), plane 1 = (P', 1); a miss writes (0, 0, 0, -1) and (0, 0, 0, 0).
+ *     The arithmetic is the contract -- binary32, one rounding per operation, no contraction, sums left to right.  Per pixel with a hit (id, N, P: what planes 0
+ *     and 1 get; (O, u): its camera ray):
+ *       a MESH hit on triangle tri (visit order) while bit id of the snapshot mask is set:
+ *         (alpha, beta, gamma) exactly as smooth shading and the texture lookup compute them (see textured meshes above), from the CURRENT triangle;
+ *         A', B', C' = the snapshot's positions of the triangle's three corners;   P' = (alpha A' + beta B') + gamma C' per component;
+ *         N' = N where the mesh shades with interpolated normals (the previous shading normals are the caller's and are not kept: min_normal_dot then bounds how
+ *         far a shading normal may turn in a frame), else N' = normalize(cross(B' - A', C' - A')): bit for bit the normal the previous frame's plane 0 held for
+ *         this triangle;
+ *       otherwise, motion != NULL (RT_MAX_OBJECTS records by object id, copied by the call): rt_temporal_accumulate's expressions with record id,
+ *         P' = ((R0 P.x + R1 P.y) + R2 P.z) + T0 (rows 1, 2 likewise), N' = (R0 N.x + R1 N.y) + R2 N.z;
+ *       otherwise P' = P, N' = N.
+ *     A snapshot takes precedence over the object's motion record.  NON-FINITE: a degenerate previous triangle (two corners equal) gives N' = NaN, which reuses
+ *     no history (rt_temporal_accumulate: a NaN in N' rejects every tap); a NaN barycentric gives a NaN P' likewise.
+ *     THE RECIPE, per frame:  (1) rt_mesh_snapshot_vertices;  (2) the frame's edits;  (3) rt_render*;  (4) rt_render_aov_motion* with the table for the spheres and
+ *     the rigid meshes;  (5) rt_temporal_accumulate[_fast]* with aov = THE TWO PREVIOUS-FRAME PLANES, prev_aov = the previous frame's CURRENT planes 0 and 1 and
+ *     rp->motion = NULL.  Everything else -- rt_denoise*, rt_svgf_filter*, rt_history_rectify*, rt_demodulate*, rt_upsample*, rt_sample_counts* -- keeps taking
+ *     the current planes.
+ *     RT_ERR_INVALID, both outputs untouched: everything rt_render_aov* refuses; out_prev NULL; out_prev overlapping out_aov.
+ *     Not covered: the previous shading normals of a smooth deforming mesh, what a mirror or glass surface shows, rt_render_aov_surface*, rt_multi_*, batches. --- */
+int rt_mesh_snapshot_vertices(rt_ctx *ctx, int object_slot, int keep);
+int rt_mesh_snapshot_mask(const rt_ctx *ctx, uint32_t *mask);
+int rt_render_aov_motion_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, const rt_motion *motion, void *out_aov_dev, void *out_prev_dev, void *stream);
+int rt_render_aov_motion(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, const rt_motion *motion, float *out_aov_host, float *out_prev_host);
+
 /* --- the planes of the first DIFFUSE surface, and filtering irradiance instead of colour (ABI 6, additive).  The specular branches of Scene::getColor
  *     (cpu:573-604) draw no random number -- reflection, total reflection or refraction, no Fresnel coin -- so the chain of the pixel-centre ray from the camera to
  *     its first diffuse surface is a function of the scene alone, the colour is handed through it unchanged, and that surface's albedo factors out of the pixel:

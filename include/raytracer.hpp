@@ -546,6 +546,16 @@ public:
         const std::vector<float> v = flat_vertices_(mesh);
         check(rt_mesh_set_vertices_of(ctx_, mesh.id, v.data(), (int)mesh.vertices.size()), "rt_mesh_set_vertices_of");
     }
+    // Reprojecting a mesh that changes shape (rt_mesh_snapshot_vertices): keep the positions the mesh has on the device NOW as its previous ones -- once per frame, before
+    // that frame's set_mesh_vertices_of / transform_mesh_of -- for render_aov_motion; forget_mesh_snapshot_of hands the mesh back to the rigid motion table
+    void snapshot_mesh_vertices_of(const TriangleMesh &mesh) { check(rt_mesh_snapshot_vertices(ctx_, mesh.id, 1), "rt_mesh_snapshot_vertices"); }
+    void snapshot_mesh_vertices() { check(rt_mesh_snapshot_vertices(ctx_, -1, 1), "rt_mesh_snapshot_vertices"); }   // every mesh
+    void forget_mesh_snapshot_of(const TriangleMesh &mesh) { check(rt_mesh_snapshot_vertices(ctx_, mesh.id, 0), "rt_mesh_snapshot_vertices"); }
+    uint32_t mesh_snapshot_mask() {
+        uint32_t m = 0;
+        check(rt_mesh_snapshot_mask(ctx_, &m), "rt_mesh_snapshot_mask");
+        return m;
+    }
     void use_smooth_normals_of(const TriangleMesh &mesh) {
         std::vector<float> n(mesh.normals.size() * 3);
         for (size_t i = 0; i < mesh.normals.size(); ++i)
@@ -611,6 +621,17 @@ public:
         const rt_params p = params(s);
         std::vector<float> planes((size_t)3 * s.W * s.H * 4);
         check(rt_render_aov(ctx_, &p, pose, nullptr, planes.data()), "rt_render_aov");
+        return planes;
+    }
+    // The same planes and, from the same traversal, the two PREVIOUS-FRAME planes (rt_render_aov_motion): (N', id) and (P', 1 / 0), where each pixel's point and normal
+    // were a frame ago -- by the vertex snapshot of a deforming mesh, else by motion (RT_MAX_OBJECTS records, nullptr = static).  temporal_accumulate takes *prev as
+    // its aov with a reprojection record whose motion is nullptr
+    std::vector<float> render_aov_motion(const RenderSettings &s, std::vector<float> *prev, const rt_motion *motion = nullptr, const rt_camera_pose *pose = nullptr) {
+        if (!prev) throw Error(RT_ERR_INVALID, "render_aov_motion: prev is where the previous-frame planes go");
+        const rt_params p = params(s);
+        std::vector<float> planes((size_t)3 * s.W * s.H * 4);
+        prev->assign((size_t)2 * s.W * s.H * 4, 0.f);
+        check(rt_render_aov_motion(ctx_, &p, pose, nullptr, motion, planes.data(), prev->data()), "rt_render_aov_motion");
         return planes;
     }
     // ... and the edge-avoiding a-trous filter they guide (rt_denoise): color = W * H float4 as render_float gives it, aov = render_aov of the same frame

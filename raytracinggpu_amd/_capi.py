@@ -37,7 +37,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_temporal_accumulate_fast_device", "rt_temporal_accumulate_fast", "rt_history_rectify_device", "rt_history_rectify",
            "rt_dead_channel_counts", "rt_first_hit_cache_counts", "rt_first_shadow_cache_counts", "rt_first_shade_cache_counts",
            "rt_render_counts_device", "rt_render_counts", "rt_render_counts_info", "rt_sample_counts_device", "rt_sample_counts", "rt_kat_sample_plan",
-           "rt_mesh_set_vertices", "rt_mesh_set_vertices_of", "rt_mesh_set_vertices_device"]
+           "rt_mesh_set_vertices", "rt_mesh_set_vertices_of", "rt_mesh_set_vertices_device",
+           "rt_mesh_snapshot_vertices", "rt_mesh_snapshot_mask", "rt_render_aov_motion_device", "rt_render_aov_motion"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -404,6 +405,8 @@ def load():
     L.rt_mesh_set_vertices.argtypes = [vp, fp3, C.c_int]
     L.rt_mesh_set_vertices_of.argtypes = [vp, C.c_int, fp3, C.c_int]
     L.rt_mesh_set_vertices_device.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    L.rt_mesh_snapshot_vertices.argtypes = [vp, C.c_int, C.c_int]
+    L.rt_mesh_snapshot_mask.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.rt_mesh_set_texture.argtypes = [vp, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_mesh_set_texture_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_kat_surface.argtypes = [vp, fp3, C.c_int, C.c_float, fp3]
@@ -417,6 +420,8 @@ def load():
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
+    L.rt_render_aov_motion_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), C.POINTER(Motion), vp, vp, vp]
+    L.rt_render_aov_motion.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), C.POINTER(Motion), fp3, fp3]
     L.rt_denoise_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(DenoiseParams), vp, vp]
     L.rt_denoise.argtypes = [vp, fp3, fp3, C.c_int, C.c_int, C.POINTER(DenoiseParams), fp3]
     L.rt_temporal_accumulate_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(TemporalParams), C.POINTER(Reproject), vp, vp]
@@ -795,6 +800,18 @@ class Context:
         else:
             self._check(self._L.rt_mesh_set_vertices_of(self._h, int(object_slot), vp_, len(v)))
 
+    def mesh_snapshot_vertices(self, object_slot=None, keep=True):
+        """rt_mesh_snapshot_vertices: keep the positions a mesh has NOW as its previous ones, for render_aov_motion -- once per frame, before that frame's
+        mesh_set_vertices / mesh_transform calls.  object_slot: the mesh at that position in Scene::objects; None = every mesh with triangles.  keep=False drops the
+        snapshot: the object follows the rigid motion table again.  A device-to-device copy on the context's stream; the host does not wait."""
+        self._check(self._L.rt_mesh_snapshot_vertices(self._h, -1 if object_slot is None else int(object_slot), int(keep)))
+
+    def mesh_snapshot_mask(self):
+        """rt_mesh_snapshot_mask: bit i set = object i holds a vertex snapshot."""
+        m = C.c_uint32(0)
+        self._check(self._L.rt_mesh_snapshot_mask(self._h, C.byref(m)))
+        return int(m.value)
+
     def mesh_rebuild(self, n_triangles, mode="reference", object_slot=None):
         """Device-side BVH build over the uploaded triangles and the current device vertices -> (bvh_arr10 [n_nodes, 10], order [n_triangles]).
         mode "reference": TriangleMesh::buildBVH bit for bit; "lbvh": Morton sort + parallel hierarchy, leaves cut by the surface-area heuristic (at most 32 triangles).
@@ -902,6 +919,36 @@ class Context:
         """rt_render_aov_device: the same three planes into device memory (3 * n_rows * W float4), asynchronous on `stream`."""
         self._check(self._L.rt_render_aov_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(self._rows_or_whole(params, rows)),
                                                  C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def _motion_table(name, motion):
+        """(the [MAX_OBJECTS, 12] float32 table kept alive, its rt_motion pointer) of a motion= argument; None = (None, None)"""
+        if motion is None:
+            return None, None
+        m = np.ascontiguousarray(motion, np.float32)
+        if m.shape != (MAX_OBJECTS, 12):
+            raise RtError(-1, f"{name}: motion {m.shape} must be [{MAX_OBJECTS}, 12]")
+        return m, m.ctypes.data_as(C.POINTER(Motion))
+
+    def render_aov_motion(self, params, pose=None, rows=None, motion=None):
+        """rt_render_aov_motion: render_aov's three planes and, from the same traversal, the two PREVIOUS-FRAME planes -> (aov [3, n_rows, W, 4], prev [2, n_rows, W, 4]):
+        prev[0] = (N', object id or -1), prev[1] = (P', 1 / 0): where each pixel's surface point and normal were in the previous frame -- a mesh with a vertex snapshot
+        (mesh_snapshot_vertices) by its triangle's previous corners, every other object by its record of motion ([MAX_OBJECTS, 12] as static_motion() lays it out;
+        None = static).  temporal_accumulate takes prev as its aov, with a reprojection record whose motion is None."""
+        n_rows = params.height if rows is None else rows.n_rows
+        out = np.zeros((3, max(n_rows, 0), params.width, 4), np.float32)
+        prev = np.zeros((2, max(n_rows, 0), params.width, 4), np.float32)
+        _keep, mp = self._motion_table("render_aov_motion", motion)
+        self._check(self._L.rt_render_aov_motion(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(rows) if rows is not None else None,
+                                                 mp, out.ctypes.data_as(C.POINTER(C.c_float)), prev.ctypes.data_as(C.POINTER(C.c_float))))
+        return out, prev
+
+    def render_aov_motion_device(self, params, out_ptr, prev_ptr, pose=None, rows=None, motion=None, stream=None):
+        """rt_render_aov_motion_device: the three planes (3 * n_rows * W float4 at out_ptr) and the two previous-frame planes (2 * n_rows * W float4 at prev_ptr) into
+        device memory, asynchronous on `stream`.  The motion table is copied by the call."""
+        _keep, mp = self._motion_table("render_aov_motion_device", motion)
+        self._check(self._L.rt_render_aov_motion_device(self._h, C.byref(params), C.byref(pose) if pose is not None else None, C.byref(self._rows_or_whole(params, rows)),
+                                                        mp, C.c_void_p(out_ptr), C.c_void_p(prev_ptr), C.c_void_p(stream) if stream else None))
 
     def denoise(self, color, aov, n_passes=None, k_normal=None, k_position=None, k_albedo=None, k_color=None, out=None):
         """rt_denoise: the a-trous filter over color [H, W, 4] guided by aov [3, H, W, 4] (render_aov of the same frame) -> [H, W, 4].  Parameters as

@@ -1,4 +1,5 @@
-// rt_aov.hip.h -- rt_render_aov[_device]: the first-hit feature buffers (G-buffer) of a frame, for the edge-avoiding filter of rt_denoise.hip.h.
+// rt_aov.hip.h -- rt_render_aov[_device]: the first-hit feature buffers (G-buffer) of a frame, for the edge-avoiding filter of rt_denoise.hip.h; and
+// rt_render_aov_motion[_device]: the same planes with the two previous-frame planes a deforming or moving scene is reprojected from.
 // Included at the end of rt_capi.hip, after rt_trace.hip.h (same translation unit: it runs the traversal launch of rt_trace_rays, trace_queue; the host half uses
 // rt_host_post.hip.h).  The device functions and the host prologue here are rt_aov_surface.hip.h's too.
 //
@@ -61,13 +62,31 @@ __global__ __launch_bounds__(256) void aov_emit_kernel(const Scene sc, const Fra
 }
 
 // closes the query as wf_advance closes a continuation ray's and writes the three planes (n float4 each, consecutive)
-__global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Frame fr, const TexScene ts, const unsigned long long *__restrict__ M, int n, float4 *__restrict__ out) {
+// MOTION (rt_render_aov_motion*): the same pixel also writes the two PREVIOUS-FRAME planes -- (N', id) and (P', 1) in the layout of planes 0 and 1 -- that
+// rt_temporal_accumulate* takes as its `aov` with no motion table.  Its one argument -- the snapshot vertices, the two planes, the snapshot mask, the rigid table --
+// exists in that instantiation alone, so aov_close_kernel<false> has the arguments and the instructions the kernel always had.  A hit on a mesh whose bit is set gathers
+// one int4 and three float4 of verts_prev, as coherent as the image is: neighbouring pixels hit the same or neighbouring triangles.  The table sits in the
+// kernel-argument segment and a lane reads the record of its own object, as temporal_accumulate_kernel does.
+struct AovRigid { float r[9], t[3]; };                               // previous = r (row-major) * current + t
+struct AovMotion {
+    const float4 *__restrict__ verts_prev;                            // Scene::verts as rt_mesh_snapshot_vertices kept them (read only where a bit of snap_mask is set)
+    float4 *__restrict__ prev;                                        // 2 n float4
+    uint32_t snap_mask;
+    int have_motion;
+    AovRigid m[RT_MAX_OBJECTS];
+};
+template <bool MOTION, class... Mo>
+__global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Frame fr, const TexScene ts, const unsigned long long *__restrict__ M, int n, float4 *__restrict__ out,
+                                                        const Mo... mo) {
+    static_assert(sizeof...(Mo) == (MOTION ? 1 : 0), "the motion instantiation takes one AovMotion");
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     f3 O, u;
     aov_ray(sc, fr, r, O, u);
     const AovHit h = aov_close_query(sc, O, u, M[r]);
     float4 o0 = make_float4(0.f, 0.f, 0.f, -1.f), o1 = make_float4(0.f, 0.f, 0.f, 0.f), o2 = o1;
+    [[maybe_unused]] float4 p0, p1;
+    if constexpr (MOTION) { p0 = make_float4(0.f, 0.f, 0.f, -1.f); p1 = make_float4(0.f, 0.f, 0.f, 0.f); }   // a miss
     if (h.obj >= 0) {
         const f3 P = O + h.t * u;                                     // cpu:560
         Bary bary{0.f, 0.f, 0.f};
@@ -77,10 +96,35 @@ __global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Fr
         o0 = make_float4(N.x, N.y, N.z, (float)h.obj);
         o1 = make_float4(P.x, P.y, P.z, 1.f);
         o2 = make_float4(alb.x, alb.y, alb.z, 0.f);
+        if constexpr (MOTION) {
+            const AovMotion &am = (mo, ...);
+            f3 Np = N, Pp = P;
+            if (h.tri >= 0 && ((am.snap_mask >> h.obj) & 1u)) {       // the same barycentric point of the triangle's previous corners
+                const bool smooth = have_bary;                        // (hit_normal: have_bary == smooth_hit)
+                if (!have_bary) bary = tri_bary(sc, h.tri, O, u);
+                const int4 ix = sc.tidx[h.tri];
+                const float4 a = am.verts_prev[ix.x], b = am.verts_prev[ix.y], c = am.verts_prev[ix.z];
+                const f3 A = mk(a.x, a.y, a.z), B = mk(b.x, b.y, b.z), C = mk(c.x, c.y, c.z);
+                Pp = (bary.alpha * A + bary.beta * B) + bary.gamma * C;
+                if (!smooth) Np = normalize(cross(B - A, C - A));     // retri_kernel's and flat_normal's operations: the previous frame's plane 0, bit for bit
+            } else if (am.have_motion) {                              // temporal_accumulate_kernel's expressions with the record of this object
+                const AovRigid &m = am.m[h.obj & (RT_MAX_OBJECTS - 1)];
+                Pp = mk(((m.r[0] * P.x + m.r[1] * P.y) + m.r[2] * P.z) + m.t[0], ((m.r[3] * P.x + m.r[4] * P.y) + m.r[5] * P.z) + m.t[1],
+                        ((m.r[6] * P.x + m.r[7] * P.y) + m.r[8] * P.z) + m.t[2]);
+                Np = mk((m.r[0] * N.x + m.r[1] * N.y) + m.r[2] * N.z, (m.r[3] * N.x + m.r[4] * N.y) + m.r[5] * N.z, (m.r[6] * N.x + m.r[7] * N.y) + m.r[8] * N.z);
+            }
+            p0 = make_float4(Np.x, Np.y, Np.z, (float)h.obj);
+            p1 = make_float4(Pp.x, Pp.y, Pp.z, 1.f);
+        }
     }
     out[r] = o0;
     out[(size_t)n + r] = o1;
     out[2 * (size_t)n + r] = o2;
+    if constexpr (MOTION) {
+        const AovMotion &am = (mo, ...);
+        am.prev[r] = p0;
+        am.prev[(size_t)n + r] = p1;
+    }
 }
 
 }  // namespace rtk
@@ -135,7 +179,7 @@ extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_ca
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     AovCall a;
     if (int rc = aov_begin(ctx, p, pose, rows, out_aov_dev, stream, 0, a); rc != RT_OK || a.n == 0) return rc;
-    hipLaunchKernelGGL(rtk::aov_close_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, a.q, a.scn, a.fr, tex_scene(ctx), a.tl.st.M, a.n, static_cast<float4 *>(out_aov_dev));
+    hipLaunchKernelGGL(rtk::aov_close_kernel<false>, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, a.q, a.scn, a.fr, tex_scene(ctx), a.tl.st.M, a.n, static_cast<float4 *>(out_aov_dev));
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -143,4 +187,51 @@ extern "C" int rt_render_aov_device(rt_ctx *ctx, const rt_params *p, const rt_ca
 extern "C" int rt_render_aov(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, float *out_aov_host) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     return aov_to_host(ctx, p, rows, out_aov_host, [&](const rt_rows *r, void *dev) { return rt_render_aov_device(ctx, p, pose, r, dev, nullptr); });
+}
+
+// ---- rt_render_aov_motion[_device]: the same call, which also writes the previous-frame planes of a deforming or moving scene (raytrace_hip.h; the kernel's MOTION form) ----
+extern "C" int rt_render_aov_motion_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, const rt_motion *motion, void *out_aov_dev,
+                                           void *out_prev_dev, void *stream) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    int n = 0;
+    if (int rc = aov_check(ctx, p, rows, out_aov_dev, n); rc != RT_OK) return rc;
+    if (!out_prev_dev) return fail(ctx, RT_ERR_INVALID, "out_prev is NULL");
+    if (overlaps(out_aov_dev, 3 * (size_t)n * sizeof(float4), out_prev_dev, 2 * (size_t)n * sizeof(float4))) return fail(ctx, RT_ERR_INVALID, "out_prev overlaps out_aov");
+    AovCall a;
+    if (int rc = aov_begin(ctx, p, pose, rows, out_aov_dev, stream, 0, a); rc != RT_OK || a.n == 0) return rc;
+    note_between(ctx, a.q, {{out_prev_dev, 2 * (size_t)a.n * sizeof(float4)}});
+    rtk::AovMotion am{};
+    am.verts_prev = static_cast<const float4 *>(ctx->verts_prev.p);
+    am.prev = static_cast<float4 *>(out_prev_dev);
+    am.snap_mask = ctx->verts_prev.p ? ctx->snap_mask : 0u;           // (a set bit means the buffer exists: rt_mesh_snapshot_vertices)
+    if (am.snap_mask && ctx->snap_ev && a.q != ctx->stream_) RT_HIP(ctx, hipStreamWaitEvent(a.q, ctx->snap_ev, 0));   // the snapshot's copy ran on the context's stream
+    if (motion) {
+        am.have_motion = 1;
+        for (int k = 0; k < RT_MAX_OBJECTS; ++k) {
+            for (int c = 0; c < 9; ++c) am.m[k].r[c] = motion[k].rotation[c];
+            for (int c = 0; c < 3; ++c) am.m[k].t[c] = motion[k].translation[c];
+        }
+    }
+    hipLaunchKernelGGL((rtk::aov_close_kernel<true, rtk::AovMotion>), dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, a.q, a.scn, a.fr, tex_scene(ctx), a.tl.st.M, a.n,
+                       static_cast<float4 *>(out_aov_dev), am);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+extern "C" int rt_render_aov_motion(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, const rt_motion *motion, float *out_aov_host,
+                                    float *out_prev_host) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!p || !out_aov_host || !out_prev_host) return fail(ctx, RT_ERR_INVALID, "params/out/out_prev is NULL");
+    const rt_rows whole{0, p->height, p->height > 0 ? p->height : 1, 1};
+    if (!rows) rows = &whole;
+    const size_t plane = (size_t)(rows->n_rows > 0 ? rows->n_rows : 0) * (p->width > 0 ? p->width : 0) * sizeof(float4);
+    if (overlaps(out_aov_host, 3 * plane, out_prev_host, 2 * plane)) return fail(ctx, RT_ERR_INVALID, "out_prev overlaps out_aov");
+    // the previous-frame planes, then the three planes (the result staged copies out)
+    return staged(ctx, {}, 2 * plane, 3 * plane, out_aov_host, [&](uint8_t *d) {
+        const int r = rt_render_aov_motion_device(ctx, p, pose, rows, motion, d + 2 * plane, d, nullptr);
+        if (r != RT_OK) return r;
+        if (plane) RT_HIP(ctx, hipMemcpyAsync(out_prev_host, d, 2 * plane, hipMemcpyDeviceToHost, own_stream(ctx)));   // (staged waits for the stream)
+        return (int)RT_OK;
+    });
 }

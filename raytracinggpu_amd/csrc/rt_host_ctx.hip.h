@@ -213,6 +213,11 @@ struct rt_ctx {
     std::vector<int> pre_of;                                        // forest_arr index -> pre-order index of the same node on the device (node_lo / node_hi hold its current box)
     int n_syn = 0, syn[rtk::kMaxSynthetic] = {};                    // the forest's synthetic union nodes (pre-order indices): refit_kernel widens them as build_forest does
     DevBuf node_lo{bufs}, node_hi{bufs}, nodes2{bufs}, nodesq{bufs}, nodesb{bufs}, q2thr{bufs}, tri{bufs}, verts{bufs}, tidx{bufs}, scratch_rgba{bufs}, scratch_rgb8{bufs}, work{bufs}, queue{bufs};
+    // rt_mesh_snapshot_vertices: `verts` as they were when a mesh was last snapshotted (n_verts float4, the same indexing; allocated by the first snapshot) and the objects
+    // whose range of it is current.  Read by rt_render_aov_motion* alone: nothing a render reads, so no still-view cache hangs on it.  rt_scene_upload* clears the mask.
+    DevBuf verts_prev{bufs};
+    uint32_t snap_mask = 0;
+    Event snap_ev;                                                   // the last snapshot's copy on the context's stream: a motion call on ANOTHER stream waits for it
     int n_cus = 0;
     DevBuf wfM{bufs}, wfT{bufs}, wfLS{bufs}, wfSID{bufs}, wfSamp{bufs};   // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
     DevBuf wfDCH{bufs};                                             // ... the dead-channel byte of each path (wf_dead_channels)

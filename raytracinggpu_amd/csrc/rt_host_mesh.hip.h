@@ -270,6 +270,41 @@ int rt_mesh_set_vertices_device(rt_ctx *ctx, int object_slot, const void *xyz_de
     return set_vertices_checked(ctx, p, nullptr, xyz_dev, stride_floats, n_vertices);
 }
 
+// The positions of a mesh as they are now, kept for rt_render_aov_motion* (the previous corners of a deforming mesh's triangles): the part's range of `verts` copied into the
+// same range of verts_prev, device to device on the context's stream -- behind the edits issued so far, ahead of those to come; the host does not wait.  A snapshot is
+// nothing a render reads: the still-view state is not told.  A rebuild keeps it (it permutes tidx, and re-uploads `verts` value for value in the same order).
+int rt_mesh_snapshot_vertices(rt_ctx *ctx, int object_slot, int keep) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
+    if (keep != 0 && keep != 1) return fail(ctx, RT_ERR_INVALID, "keep %d is neither 0 nor 1", keep);
+    rt_ctx::MeshPart *one = nullptr;
+    if (object_slot != -1) {
+        if (int rc = find_part(ctx, object_slot, one); rc != RT_OK) return rc;
+        if (!one) return RT_OK;                                                     // a mesh without triangles: never hit, nothing to keep
+    }
+    uint32_t bits = 0;
+    for (const rt_ctx::MeshPart &p : ctx->parts) if (!one || &p == one) bits |= 1u << p.obj;
+    if (!keep) { ctx->snap_mask &= ~bits; return RT_OK; }
+    if (!bits) return RT_OK;
+    if (int rc = ensure(ctx, ctx->verts_prev, (size_t)ctx->scene.n_verts * sizeof(float4)); rc != RT_OK) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    for (const rt_ctx::MeshPart &p : ctx->parts)
+        if ((!one || &p == one) && p.nv > 0)
+            RT_HIP(ctx, hipMemcpyAsync(static_cast<float4 *>(ctx->verts_prev.p) + p.voff, static_cast<const float4 *>(ctx->verts.p) + p.voff, (size_t)p.nv * sizeof(float4),
+                                       hipMemcpyDeviceToDevice, own_stream(ctx)));
+    if (!ctx->snap_ev) RT_HIP(ctx, ctx->snap_ev.create(hipEventDisableTiming));
+    RT_HIP(ctx, hipEventRecord(ctx->snap_ev, own_stream(ctx)));
+    ctx->snap_mask |= bits;
+    return RT_OK;
+}
+
+int rt_mesh_snapshot_mask(const rt_ctx *ctx, uint32_t *mask) {
+    if (!ctx || !mask) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
+    *mask = ctx->snap_mask;
+    return RT_OK;
+}
+
 // TriangleMesh::buildBVH on the device, bit for bit (rt_bvhbuild.hip.h): leaves the flat tree in ctx->bb_arr and the triangle order in ctx->bb_idx
 // (up_off: the mesh's first triangle in tidx_up -- a forest's member; its vertex indices are global, the outputs are local to the mesh)
 static int rebuild_reference_tree(rt_ctx *ctx, const int nt, int &n_nodes_out, const int up_off = 0) {

@@ -16,7 +16,12 @@ in place (history_rectify_device) before the filter, or before the upsample of p
 adaptive = make_sample_count_params(...) (off by default; only at upsample == 1) spends more samples where the history says the frame is bad: after the accumulation
 sample_counts_device turns the accumulated history into per-pixel counts, render_counts_device adds the missing samples to the colour frame in place (base = the
 one-sample frame), and the accumulation runs again from the same previous history into the same buffer; then the chain goes on as without the option (DESIGN.md
-section 5.13).  render_counts_device waits on the stream once per frame."""
+section 5.13).  render_counts_device waits on the stream once per frame.
+
+deforming = True (off by default) follows meshes that change shape (mesh_set_vertices) as well as rigid motion: render_aov_motion_device takes render_aov_device's
+place and also writes the PREVIOUS-FRAME planes -- where each pixel's surface point and normal were a frame ago, by the vertex snapshot of a deforming mesh
+(the caller's mesh_snapshot_vertices, once per frame before its edits) or by the motion table -- and the accumulation reprojects from those with a record whose
+motion is None.  Everything else (the clamp, the filter, the upsample, the sample counts) keeps taking the current planes."""
 from ._capi import FAST_HISTORY_DEFAULT, CameraPose, Params, RtError, make_reproject, make_svgf_params, make_temporal_params
 
 
@@ -28,10 +33,11 @@ class SvgfSequence:
     (position, fov) the scene was uploaded with, for frames without a pose (None: scene_upload's default).  stream: the stream of every call (None: the context's).
     upsample, filter_at: see the module; up_k_normal, up_k_position: the upsample's weights (None: UPSAMPLE_DEFAULTS).  rectify: None, or the RectifyParams of the
     clamp (the sequence then owns two fast planes more and swaps them); fast_history: the fast history's length limit.  adaptive: None, or the SampleCountParams of
-    the per-pixel sample counts (the sequence then owns a plane of counts, one byte per pixel)."""
+    the per-pixel sample counts (the sequence then owns a plane of counts, one byte per pixel).  deforming: the accumulation reprojects from previous-frame planes
+    (the sequence then owns two planes more at the working resolution); motion= of frame() then goes to render_aov_motion_device."""
 
     def __init__(self, ctx, width, height, svgf=None, temporal=None, camera=None, stream=None, upsample=1, filter_at="low", up_k_normal=None, up_k_position=None,
-                 rectify=None, fast_history=FAST_HISTORY_DEFAULT, adaptive=None):
+                 rectify=None, fast_history=FAST_HISTORY_DEFAULT, adaptive=None, deforming=False):
         self.ctx, self.width, self.height, self.stream = ctx, int(width), int(height), stream
         self.svgf = make_svgf_params() if svgf is None else svgf
         self.temporal = make_temporal_params() if temporal is None else temporal
@@ -39,6 +45,7 @@ class SvgfSequence:
         self.upsample, self.filter_at, self.up_k = int(upsample), filter_at, (up_k_normal, up_k_position)
         self.rectify, self.fast_history = rectify, int(fast_history)
         self.adaptive = adaptive
+        self.deforming = bool(deforming)
         f = self.upsample
         if f < 1 or f > 4 or filter_at not in ("low", "full"):
             raise RtError(-1, f"SvgfSequence: upsample {upsample} must be 1 .. 4 and filter_at {filter_at!r} 'low' or 'full'")
@@ -61,6 +68,8 @@ class SvgfSequence:
                 self.fast, self.previous_fast = self._alloc(frame), self._alloc(frame)
             if adaptive is not None:
                 self.counts = self._alloc(self.width * self.height)
+            if self.deforming:
+                self.previous_frame_planes = self._alloc(2 * frame)
         except RtError:
             self.close()
             raise
@@ -88,27 +97,34 @@ class SvgfSequence:
             c.render_pose_device(params, pose, self.color, stream=s)
         else:
             c.render_device(params, c._rows_or_whole(params, None), self.color, stream=s)
-        c.render_aov_device(params, planes, pose=pose, stream=s)
+        source = planes                                                # the planes the accumulation reprojects from
+        if self.deforming:                                             # ... are the previous-frame planes: the motion is in them, the record carries none
+            source = self.previous_frame_planes
+            c.render_aov_motion_device(params, planes, source, pose=pose, motion=motion, stream=s)
+            motion = None
+        else:
+            c.render_aov_device(params, planes, pose=pose, stream=s)
         first = cut or not self._have_previous
         rp = None if first else make_reproject(camera=self.camera, pose=self._previous_pose, motion=motion, no_history_mask=no_history_mask)
-        self._accumulate(planes, previous, first, rp, W, H)
+        self._accumulate(source, planes, previous, first, rp, W, H)
         if self.adaptive is not None:                                  # more samples where the history asks for them, then the accumulation over again
             c.sample_counts_device(self.accumulated, W, H, self.counts, params=self.adaptive, stream=s)
             c.render_counts_device(params, self.counts, self.color, pose=pose, base_ptr=self.color, stream=s)
-            self._accumulate(planes, previous, first, rp, W, H)
+            self._accumulate(source, planes, previous, first, rp, W, H)
         if self.rectify is not None:
             self.fast, self.previous_fast = self.previous_fast, self.fast
         return self._filter(full, planes, previous, pose)
 
-    def _accumulate(self, planes, previous, first, rp, W, H):
-        """the accumulation of the colour frame into self.accumulated (and self.fast), with the clamp if the sequence has one"""
+    def _accumulate(self, source, planes, previous, first, rp, W, H):
+        """the accumulation of the colour frame into self.accumulated (and self.fast), with the clamp if the sequence has one.  source: the planes it reprojects from
+        (the current planes, or the previous-frame planes of a deforming sequence); planes: the current ones, which the clamp keeps taking"""
         c, s = self.ctx, self.stream
         if self.rectify is None and first:
-            c.temporal_accumulate_device(self.color, planes, None, None, W, H, self.accumulated, params=self.temporal, stream=s)
+            c.temporal_accumulate_device(self.color, source, None, None, W, H, self.accumulated, params=self.temporal, stream=s)
         elif self.rectify is None:
-            c.temporal_accumulate_device(self.color, planes, previous, self.history, W, H, self.accumulated, reproject=rp, params=self.temporal, stream=s)
+            c.temporal_accumulate_device(self.color, source, previous, self.history, W, H, self.accumulated, reproject=rp, params=self.temporal, stream=s)
         else:                                                          # the fast history beside the long one, then the long one clamped to it, in place
-            c.temporal_accumulate_fast_device(self.color, planes, None if first else previous, None if first else self.history, None if first else self.previous_fast, W, H,
+            c.temporal_accumulate_fast_device(self.color, source, None if first else previous, None if first else self.history, None if first else self.previous_fast, W, H,
                                               self.accumulated, self.fast, reproject=rp, params=self.temporal, fast_history=self.fast_history, stream=s)
             c.history_rectify_device(self.accumulated, self.fast, planes, W, H, self.accumulated, params=self.rectify, stream=s)
 

@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Did a change move an existing kernel?  Compares two gfx950 device assemblies of rt_capi.hip function by function.
+
+usage: hipcc <the build's flags without -fPIC -shared> -S --cuda-device-only -o parent.s raytracinggpu_amd/csrc/rt_capi.hip   (once in each tree)
+       python tools/asm_compare.py parent.s this.s [old_name=new_name ...]
+
+A function is the text from its label to its .Lfunc_end, comments dropped; what the compiler numbers per translation unit (.LBB<n>_, .Ltmp<n>, the
+__hip_cuid symbol) is normalised, and a function's own name is replaced by a placeholder, so that a kernel that only changed its name (old=new on the command
+line, or a unique match by the name in front of the template arguments) still compares instruction for instruction.  Section directives are not instructions
+and are dropped.  Prints one line per function that differs, is missing or is new, and a summary; exit status 1 if an existing function differs or is missing."""
+import re
+import sys
+
+
+def functions(path):
+    out, cur, closed = {}, None, set()
+    for line in open(path):
+        m = re.match(r"^(_Z\w+):", line)
+        if m and cur is None:
+            cur = m.group(1)
+            out[cur] = []
+            continue
+        if cur is None:
+            continue
+        if line.startswith(".Lfunc_end"):
+            closed.add(cur)
+            cur = None
+            continue
+        t = line.split(";")[0].rstrip()
+        t = re.sub(r"\.LBB\d+_", ".LBB_", t)
+        t = re.sub(r"\.Ltmp\d+", ".Ltmp", t)
+        t = re.sub(r"__hip_cuid_\w+", "__hip_cuid", t)
+        if t.strip() and not t.lstrip().startswith((".section", ".text")):
+            out[cur].append(t.replace(cur, "<self>"))
+    return {k: v for k, v in out.items() if k in closed}             # (a label that never reaches .Lfunc_end is an object, not a function)
+
+
+def base(name):
+    m = re.match(r"_ZN(\d+)rtk(\d+)", name)
+    return name[:m.end() + int(m.group(2))] if m else name
+
+
+def main():
+    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    renamed = dict(x.split("=") for x in sys.argv[3:])
+    bad = same = 0
+    for k, body in a.items():
+        to = renamed.get(k, k)
+        if to not in b:
+            cands = [n for n in b if n not in a and base(n) == base(k) and b[n] == body]
+            to = cands[0] if len(cands) == 1 else None
+        if to is None:
+            print("MISSING in the new assembly:", k)
+            bad += 1
+        elif b[to] != body:
+            print(f"DIFFERS: {k} ({len(body)} lines against {len(b[to])})")
+            bad += 1
+        else:
+            same += 1
+            if to != k:
+                print(f"identical under a new name ({len(body)} lines): {k} -> {to}")
+    matched = set(a) | {n for n in b if any(base(n) == base(k) and b[n] == a[k] for k in a if k not in b)}
+    for k in b:
+        if k not in matched:
+            print(f"NEW: {k} ({len(b[k])} lines)")
+    print(f"{len(a)} functions in the old assembly: {same} identical, {bad} differing or missing; {len(b)} functions in the new one")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -212,7 +212,9 @@ def main():
         if t:
             res[name] = advance_counts(t) if name in ("wf_advance", "wf_advance_anim") else {"whole_kernel": count(t)}
     # the first-hit planes, the a-trous filter's three instantiations and the temporal accumulation (rt_aov.hip.h, rt_denoise.hip.h, rt_temporal.hip.h): whole kernels
-    for name, pattern in (("aov_emit", r"^(_ZN3rtk15aov_emit_kernel\w*):"), ("aov_close", r"^(_ZN3rtk16aov_close_kernel\w*):"),
+    for name, pattern in (("aov_emit", r"^(_ZN3rtk15aov_emit_kernel\w*):"), ("aov_close", r"^(_ZN3rtk16aov_close_kernelILb0E\w*):"),
+                          # ... and the form that also writes the previous-frame planes (rt_render_aov_motion*)
+                          ("aov_close_motion", r"^(_ZN3rtk16aov_close_kernelILb1E\w*):"),
                           ("denoise_pass", r"^(_ZN3rtk19denoise_pass_kernelILb0E\w*):"), ("denoise_var_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_5DnVarEE\w*):"),
                           ("svgf_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_6DnSvgfEE\w*):"),
                           ("temporal_accumulate", r"^(_ZN3rtk26temporal_accumulate_kernelILb0E\w*):"),
