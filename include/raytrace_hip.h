@@ -487,8 +487,9 @@ int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_
  *       rt_mesh_set_vertices_device  positions in DEVICE memory, records stride_floats (3 or 4) floats apart, read on the context's own stream in the order of
  *                                    the call (as rt_mesh_transform's launches are ordered: work the caller issued on ANOTHER stream is the caller's to finish
  *                                    first); object_slot -1 = the scene's one mesh.
- *     SMOOTH NORMALS ARE NOT RECOMPUTED: they are the caller's data, as in the reference (TriangleMesh::normals comes from the file).  A caller that deforms a
- *     smooth mesh passes the normals of the new shape to rt_mesh_set_normals[_of] again.
+ *     SMOOTH NORMALS ARE THE CALLER'S DATA, as in the reference (TriangleMesh::normals comes from the file), and these entries leave them alone.  A caller that
+ *     deforms a smooth mesh either passes the normals of the new shape to rt_mesh_set_normals[_of] again, or has them made on the device from the new shape:
+ *     rt_mesh_compute_normals[_of] below.
  *     The call WAITS on the context's stream once, for the refitted root box (32 bytes): it travels to the render kernels as an argument and the fixed-point grid
  *     hangs on it -- the same wait rt_mesh_transform has.
  *     A refit keeps the topology: after large deformations the boxes overlap more and a ray does more work, never different work's result.  Rebuild now and then
@@ -498,6 +499,35 @@ int rt_mesh_rebuild_of(rt_ctx *ctx, int object_slot, int mode, float *bvh_arr10_
 int rt_mesh_set_vertices(rt_ctx *ctx, const float *xyz_host, int n_vertices);
 int rt_mesh_set_vertices_of(rt_ctx *ctx, int object_slot, const float *xyz_host, int n_vertices);
 int rt_mesh_set_vertices_device(rt_ctx *ctx, int object_slot, const void *xyz_dev, int stride_floats, int n_vertices);
+
+/* --- vertex normals of a mesh's CURRENT shape, computed on the device (ABI 6, additive).  The mesh gets one normal per POSITION vertex -- the area-weighted sum of the
+ *     face normals of its incident triangles, normalised -- and then shades with them exactly as if the caller had passed that array to rt_mesh_set_normals[_of] with the
+ *     triangles' own vertex indices as nidx.  The reference has no such computation; the arithmetic below is the contract (binary32, one rounding per operation in the
+ *     order written, no contraction):
+ *       N(t) = cross(B - A, C - A) of triangle t's CURRENT corners (cpu_launcher.cpp:227-229: the N of the triangle's record; twice the area long, so the sum is
+ *              area-weighted);
+ *       S(v) = the N of the first corner that names v, then S = S + N component by component over the others, in ascending order of the mesh's own triangle order --
+ *              as uploaded, or as the last rt_mesh_rebuild* reported: the order rt_mesh_set_normals_of's nidx rows follow -- corners 0, 1, 2 within a triangle; a
+ *              triangle that names v twice contributes twice.  (A triangle that lies in no leaf of the tree is never hit and takes no part.)
+ *       n(v) = S / sqrt((S.x S.x + S.y S.y) + S.z S.z) with the correctly rounded square root and divisions of every normalisation here (cpu:58-63), or (0, 0, 0)
+ *              where that sum of squares is not > 0: a vertex no triangle names, faces that cancel or are all degenerate, a NaN.  A zero vertex normal drops out of
+ *              the interpolation of get_smooth_normal;
+ *       every corner k of every triangle t of the mesh then shades with n(vertex k of t).
+ *     The work runs on the context's own stream in the order of the call, behind the rt_mesh_set_vertices* / rt_mesh_transform* issued so far (work the caller issued on
+ *     ANOTHER stream is the caller's to finish first).  The FIRST call after an upload or a rebuild builds the mesh's adjacency on the host and uploads it; later calls
+ *     enqueue two launches and do not wait.  The shading-level caches of a still view are emptied, as by rt_mesh_set_normals.
+ *       rt_mesh_compute_normals      the scene's one mesh (RT_ERR_UNSUPPORTED on a scene of several, as rt_mesh_set_normals);
+ *       rt_mesh_compute_normals_of   the mesh at object_slot; the other meshes' normals and shading stay.
+ *     What follows from the normals being ordinary smooth normals: rt_mesh_transform* rotates AND translates them as any others (the reference's kernel does); a rebuild
+ *     carries them with their triangles; rt_mesh_set_normals_of(.., NULL, ..) returns the mesh to flat shading; a later rt_mesh_set_normals_of with the caller's own array
+ *     replaces them; textures and UVs stay.  THE RECIPE for a smooth mesh that changes shape: rt_mesh_set_vertices*, then rt_mesh_compute_normals*, then the frame.
+ *     rt_mesh_get_vertex_normals copies the per-vertex normals (n_vertices * 3 floats, the uploaded vertex order) to the host as the last rt_mesh_compute_normals* of
+ *     that mesh wrote them, with one wait on the stream; object_slot -1 = the scene's one mesh.  It does NOT follow a later rt_mesh_transform* (which moves the corners'
+ *     copies, not this array).  RT_ERR_INVALID: none was computed for the mesh since the upload, n_vertices is not the mesh's, a NULL pointer.
+ *     Errors otherwise as rt_mesh_set_vertices*; a mesh without triangles: RT_OK, nothing happens. */
+int rt_mesh_compute_normals(rt_ctx *ctx);
+int rt_mesh_compute_normals_of(rt_ctx *ctx, int object_slot);
+int rt_mesh_get_vertex_normals(rt_ctx *ctx, int object_slot, float *out_xyz, int n_vertices);
 
 /* --- textured meshes (ABI 6, additive): MTL's map_Kd over OBJ's per-corner vt.  The albedo of a hit on a textured mesh is
  *     mesh albedo (.) sampled texel (Kd x map_Kd), a per-channel binary32 product with the mesh albedo first; it replaces the albedo
@@ -722,22 +752,33 @@ int rt_svgf_filter(rt_ctx *ctx, const float *history_host, const float *aov_host
  *       a MESH hit on triangle tri (visit order) while bit id of the snapshot mask is set:
  *         (alpha, beta, gamma) exactly as smooth shading and the texture lookup compute them (see textured meshes above), from the CURRENT triangle;
  *         A', B', C' = the snapshot's positions of the triangle's three corners;   P' = (alpha A' + beta B') + gamma C' per component;
- *         N' = N where the mesh shades with interpolated normals (the previous shading normals are the caller's and are not kept: min_normal_dot then bounds how
- *         far a shading normal may turn in a frame), else N' = normalize(cross(B' - A', C' - A')): bit for bit the normal the previous frame's plane 0 held for
- *         this triangle;
+ *         N' = N where the mesh shades with interpolated normals (unless it holds a NORMAL snapshot, below; without one min_normal_dot bounds how far a shading
+ *         normal may turn in a frame), else N' = normalize(cross(B' - A', C' - A')): bit for bit the normal the previous frame's plane 0 held for this triangle;
  *       otherwise, motion != NULL (RT_MAX_OBJECTS records by object id, copied by the call): rt_temporal_accumulate's expressions with record id,
  *         P' = ((R0 P.x + R1 P.y) + R2 P.z) + T0 (rows 1, 2 likewise), N' = (R0 N.x + R1 N.y) + R2 N.z;
  *       otherwise P' = P, N' = N.
+ *       and, whichever of the three decided P': a hit on a mesh that shades with interpolated normals while bit id of the NORMAL-snapshot mask is set gets
+ *         N' = normalize((alpha n'_a + beta n'_b) + gamma n'_c), n' = the snapshot's three corner normals of triangle tri: get_smooth_normal's expression with the
+ *         barycentrics above -- bit for bit what the previous frame's plane 0 held at this barycentric point of this triangle.  It takes precedence over the
+ *         record's rotation of N.
+ *     rt_mesh_snapshot_normals(keep = 1) is rt_mesh_snapshot_vertices' twin for the shading normals: the mesh's corner normals as they are NOW (3 float4 per
+ *     triangle) are copied into a buffer of the context's, device to device on the context's own stream, the host does not wait, the object's bit of a second mask
+ *     is set; on a mesh that shades flat it does nothing and the bit stays clear.  keep = 0 clears the bit; rt_mesh_normal_snapshot_mask reports the bits.  The
+ *     copy is indexed by the triangles' position in the tree's visit order, so rt_scene_upload* AND EVERY rt_mesh_rebuild* CLEAR THE WHOLE NORMAL-SNAPSHOT MASK
+ *     (the vertex snapshots survive a rebuild as before): snapshot again in the frame after a rebuild.  Nothing a render reads; errors as rt_mesh_snapshot_vertices.
  *     A snapshot takes precedence over the object's motion record.  NON-FINITE: a degenerate previous triangle (two corners equal) gives N' = NaN, which reuses
  *     no history (rt_temporal_accumulate: a NaN in N' rejects every tap); a NaN barycentric gives a NaN P' likewise.
- *     THE RECIPE, per frame:  (1) rt_mesh_snapshot_vertices;  (2) the frame's edits;  (3) rt_render*;  (4) rt_render_aov_motion* with the table for the spheres and
+ *     THE RECIPE, per frame:  (1) rt_mesh_snapshot_vertices and, for a smooth mesh, rt_mesh_snapshot_normals;  (2) the frame's edits, for a smooth mesh closed by
+ *     rt_mesh_compute_normals* (or rt_mesh_set_normals*);  (3) rt_render*;  (4) rt_render_aov_motion* with the table for the spheres and
  *     the rigid meshes;  (5) rt_temporal_accumulate[_fast]* with aov = THE TWO PREVIOUS-FRAME PLANES, prev_aov = the previous frame's CURRENT planes 0 and 1 and
  *     rp->motion = NULL.  Everything else -- rt_denoise*, rt_svgf_filter*, rt_history_rectify*, rt_demodulate*, rt_upsample*, rt_sample_counts* -- keeps taking
  *     the current planes.
  *     RT_ERR_INVALID, both outputs untouched: everything rt_render_aov* refuses; out_prev NULL; out_prev overlapping out_aov.
- *     Not covered: the previous shading normals of a smooth deforming mesh, what a mirror or glass surface shows, rt_render_aov_surface*, rt_multi_*, batches. --- */
+ *     Not covered: what a mirror or glass surface shows, rt_render_aov_surface*, rt_multi_*, batches. --- */
 int rt_mesh_snapshot_vertices(rt_ctx *ctx, int object_slot, int keep);
 int rt_mesh_snapshot_mask(const rt_ctx *ctx, uint32_t *mask);
+int rt_mesh_snapshot_normals(rt_ctx *ctx, int object_slot, int keep);
+int rt_mesh_normal_snapshot_mask(const rt_ctx *ctx, uint32_t *mask);
 int rt_render_aov_motion_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, const rt_motion *motion, void *out_aov_dev, void *out_prev_dev, void *stream);
 int rt_render_aov_motion(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, const rt_rows *rows, const rt_motion *motion, float *out_aov_host, float *out_prev_host);
 

@@ -556,6 +556,28 @@ public:
         check(rt_mesh_snapshot_mask(ctx_, &m), "rt_mesh_snapshot_mask");
         return m;
     }
+    // Smooth normals of the shape the mesh has on the device NOW (rt_mesh_compute_normals[_of]): one normal per position vertex, the area-weighted sum of its triangles'
+    // face normals, normalised; the mesh then shades with them.  After set_mesh_vertices[_of], before the frame; after the first call the host does not wait
+    void compute_mesh_normals() { check(rt_mesh_compute_normals(ctx_), "rt_mesh_compute_normals"); }   // the scene's one mesh
+    void compute_mesh_normals_of(const TriangleMesh &mesh) { check(rt_mesh_compute_normals_of(ctx_, mesh.id), "rt_mesh_compute_normals_of"); }
+    // ... and those normals on the host, one per vertex of `mesh` in its own order (a later transform_mesh is not followed)
+    std::vector<Vector> mesh_vertex_normals_of(const TriangleMesh &mesh) {
+        std::vector<float> n(mesh.vertices.size() * 3);
+        check(rt_mesh_get_vertex_normals(ctx_, mesh.id, n.data(), (int)mesh.vertices.size()), "rt_mesh_get_vertex_normals");
+        std::vector<Vector> out(mesh.vertices.size());
+        for (size_t i = 0; i < out.size(); ++i) out[i] = Vector(n[3 * i], n[3 * i + 1], n[3 * i + 2]);
+        return out;
+    }
+    // The shading normals a smooth mesh has NOW kept as its previous ones (rt_mesh_snapshot_normals), beside snapshot_mesh_vertices[_of]: render_aov_motion then writes the
+    // normal the previous frame shaded with.  An upload and every rebuild forget all of them
+    void snapshot_mesh_normals_of(const TriangleMesh &mesh) { check(rt_mesh_snapshot_normals(ctx_, mesh.id, 1), "rt_mesh_snapshot_normals"); }
+    void snapshot_mesh_normals() { check(rt_mesh_snapshot_normals(ctx_, -1, 1), "rt_mesh_snapshot_normals"); }   // every smooth mesh
+    void forget_mesh_normal_snapshot_of(const TriangleMesh &mesh) { check(rt_mesh_snapshot_normals(ctx_, mesh.id, 0), "rt_mesh_snapshot_normals"); }
+    uint32_t mesh_normal_snapshot_mask() {
+        uint32_t m = 0;
+        check(rt_mesh_normal_snapshot_mask(ctx_, &m), "rt_mesh_normal_snapshot_mask");
+        return m;
+    }
     void use_smooth_normals_of(const TriangleMesh &mesh) {
         std::vector<float> n(mesh.normals.size() * 3);
         for (size_t i = 0; i < mesh.normals.size(); ++i)

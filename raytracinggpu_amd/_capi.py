@@ -38,7 +38,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_dead_channel_counts", "rt_first_hit_cache_counts", "rt_first_shadow_cache_counts", "rt_first_shade_cache_counts",
            "rt_render_counts_device", "rt_render_counts", "rt_render_counts_info", "rt_sample_counts_device", "rt_sample_counts", "rt_kat_sample_plan",
            "rt_mesh_set_vertices", "rt_mesh_set_vertices_of", "rt_mesh_set_vertices_device",
-           "rt_mesh_snapshot_vertices", "rt_mesh_snapshot_mask", "rt_render_aov_motion_device", "rt_render_aov_motion"]
+           "rt_mesh_snapshot_vertices", "rt_mesh_snapshot_mask", "rt_render_aov_motion_device", "rt_render_aov_motion",
+           "rt_mesh_compute_normals", "rt_mesh_compute_normals_of", "rt_mesh_get_vertex_normals", "rt_mesh_snapshot_normals", "rt_mesh_normal_snapshot_mask"]
 MAX_OBJECTS = 16
 MAX_DEVICES = 16
 
@@ -407,6 +408,11 @@ def load():
     L.rt_mesh_set_vertices_device.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_int]
     L.rt_mesh_snapshot_vertices.argtypes = [vp, C.c_int, C.c_int]
     L.rt_mesh_snapshot_mask.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.rt_mesh_compute_normals.argtypes = [vp]
+    L.rt_mesh_compute_normals_of.argtypes = [vp, C.c_int]
+    L.rt_mesh_get_vertex_normals.argtypes = [vp, C.c_int, fp3, C.c_int]
+    L.rt_mesh_snapshot_normals.argtypes = [vp, C.c_int, C.c_int]
+    L.rt_mesh_normal_snapshot_mask.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.rt_mesh_set_texture.argtypes = [vp, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_mesh_set_texture_of.argtypes = [vp, C.c_int, fp3, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(Texture)]
     L.rt_kat_surface.argtypes = [vp, fp3, C.c_int, C.c_float, fp3]
@@ -604,6 +610,7 @@ class Context:
         mesh: dict(vertices, indices, bvh_arr10, albedo, object_slot[, mirror, in_refraction_index, out_refraction_index]) with the reference's array
         layouts, or a list of such dicts (several TriangleMesh objects in Scene::objects: rt_scene_upload_meshes)."""
         arr, n, marr, nm, lt, cam, self._keep = _marshal_scene(spheres, mesh, light, camera)
+        self._mesh_nv = {int(marr[k].object_slot): int(marr[k].n_vertices) for k in range(nm)}   # (mesh_vertex_normals sizes its result by it)
         if nm <= 1 and not isinstance(mesh, (list, tuple)):
             self._check(self._L.rt_scene_upload(self._h, arr, n, marr if nm else None, C.byref(lt), C.byref(cam)))
         else:
@@ -785,7 +792,7 @@ class Context:
 
     def mesh_set_vertices(self, vertices=None, object_slot=None, device_ptr=None, stride=3, n_vertices=None):
         """A mesh that changes shape: new positions [n, 3] for every vertex, in the uploaded order (rt_mesh_set_vertices[_of]); indices, tree topology, normals, UVs and
-        textures stay and every box is refitted on the device.  Smooth normals are the caller's: pass the new ones to mesh_set_normals again.
+        textures stay and every box is refitted on the device.  Smooth normals are the caller's: pass the new ones to mesh_set_normals again, or call mesh_compute_normals.
         device_ptr= (with n_vertices= and stride= 3 or 4 floats per record): the positions are in device memory and are read on the context's stream
         (rt_mesh_set_vertices_device).  object_slot: the mesh at that position in Scene::objects; None = the scene's one mesh."""
         if device_ptr is not None:
@@ -810,6 +817,41 @@ class Context:
         """rt_mesh_snapshot_mask: bit i set = object i holds a vertex snapshot."""
         m = C.c_uint32(0)
         self._check(self._L.rt_mesh_snapshot_mask(self._h, C.byref(m)))
+        return int(m.value)
+
+    def mesh_compute_normals(self, object_slot=None):
+        """rt_mesh_compute_normals[_of]: the mesh gets one normal per position vertex -- the area-weighted sum of its incident triangles' face normals, normalised, of the
+        shape the mesh has NOW on the device -- and shades with them as after mesh_set_normals(those, the triangles' vertex indices).  On the context's stream behind the
+        mesh_set_vertices / mesh_transform calls issued so far; after the first call the host does not wait.  object_slot: the mesh at that position in
+        Scene::objects (rt_mesh_compute_normals_of); None = the scene's one mesh."""
+        if object_slot is None:
+            self._check(self._L.rt_mesh_compute_normals(self._h))
+        else:
+            self._check(self._L.rt_mesh_compute_normals_of(self._h, int(object_slot)))
+
+    def mesh_vertex_normals(self, object_slot=None, n_vertices=None):
+        """rt_mesh_get_vertex_normals -> [nv, 3] float32: the per-vertex normals as the last mesh_compute_normals of that mesh wrote them (a later mesh_transform is not
+        followed).  object_slot None = the scene's one mesh.  n_vertices: the mesh's vertex count; None = the count it was uploaded with through this Context."""
+        nv = n_vertices
+        if nv is None:
+            known = getattr(self, "_mesh_nv", {})
+            nv = known.get(int(object_slot)) if object_slot is not None else (next(iter(known.values())) if len(known) == 1 else None)
+        if nv is None:
+            raise RtError(-1, "mesh_vertex_normals: pass n_vertices= (this Context uploaded no such mesh)")
+        out = np.zeros((int(nv), 3), np.float32)
+        self._check(self._L.rt_mesh_get_vertex_normals(self._h, -1 if object_slot is None else int(object_slot), out.ctypes.data_as(C.POINTER(C.c_float)), int(nv)))
+        return out
+
+    def mesh_snapshot_normals(self, object_slot=None, keep=True):
+        """rt_mesh_snapshot_normals: keep the shading normals a smooth mesh has NOW as its previous ones, for render_aov_motion's N' -- once per frame beside
+        mesh_snapshot_vertices, before that frame's edits and its mesh_compute_normals.  object_slot None = every smooth mesh; a flat mesh: nothing happens.
+        keep=False drops the snapshot.  An upload and every mesh_rebuild drop all of them.  A device-to-device copy on the context's stream; the host does not wait."""
+        self._check(self._L.rt_mesh_snapshot_normals(self._h, -1 if object_slot is None else int(object_slot), int(keep)))
+
+    def mesh_normal_snapshot_mask(self):
+        """rt_mesh_normal_snapshot_mask: bit i set = object i holds a normal snapshot."""
+        m = C.c_uint32(0)
+        self._check(self._L.rt_mesh_normal_snapshot_mask(self._h, C.byref(m)))
         return int(m.value)
 
     def mesh_rebuild(self, n_triangles, mode="reference", object_slot=None):

@@ -75,10 +75,18 @@ struct AovMotion {
     int have_motion;
     AovRigid m[RT_MAX_OBJECTS];
 };
+// ... and the form the host picks only while a SMOOTH mesh holds a normal snapshot (rt_mesh_snapshot_normals): N' of a hit on such a mesh is smooth_normal's expression over
+// the snapshot's three corner normals -- the previous frame's plane 0 at this barycentric point of this triangle, bit for bit -- a 48-byte gather per such pixel.  A third
+// instantiation, told apart by the argument's type: the two older ones keep their names, their arguments and their instructions.
+struct AovMotionNormals : AovMotion {
+    const float4 *__restrict__ nrm_prev;                              // Scene::nrm as rt_mesh_snapshot_normals kept it (read only where a bit of nsnap_mask is set)
+    uint32_t nsnap_mask;
+};
 template <bool MOTION, class... Mo>
 __global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Frame fr, const TexScene ts, const unsigned long long *__restrict__ M, int n, float4 *__restrict__ out,
                                                         const Mo... mo) {
     static_assert(sizeof...(Mo) == (MOTION ? 1 : 0), "the motion instantiation takes one AovMotion");
+    constexpr bool NPREV = (std::is_same_v<Mo, AovMotionNormals> || ...);
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     f3 O, u;
@@ -112,6 +120,13 @@ __global__ __launch_bounds__(256) void aov_close_kernel(const Scene sc, const Fr
                 Pp = mk(((m.r[0] * P.x + m.r[1] * P.y) + m.r[2] * P.z) + m.t[0], ((m.r[3] * P.x + m.r[4] * P.y) + m.r[5] * P.z) + m.t[1],
                         ((m.r[6] * P.x + m.r[7] * P.y) + m.r[8] * P.z) + m.t[2]);
                 Np = mk((m.r[0] * N.x + m.r[1] * N.y) + m.r[2] * N.z, (m.r[3] * N.x + m.r[4] * N.y) + m.r[5] * N.z, (m.r[6] * N.x + m.r[7] * N.y) + m.r[8] * N.z);
+            }
+            if constexpr (NPREV) {                                    // ahead of the record's rotation and of N' = N: the normal the previous frame shaded with
+                const AovMotionNormals &an = (mo, ...);
+                if (have_bary && ((an.nsnap_mask >> h.obj) & 1u)) {
+                    const float4 na = an.nrm_prev[3 * h.tri], nb = an.nrm_prev[3 * h.tri + 1], nc = an.nrm_prev[3 * h.tri + 2];
+                    Np = normalize((bary.alpha * mk(na.x, na.y, na.z) + bary.beta * mk(nb.x, nb.y, nb.z)) + bary.gamma * mk(nc.x, nc.y, nc.z));
+                }
             }
             p0 = make_float4(Np.x, Np.y, Np.z, (float)h.obj);
             p1 = make_float4(Pp.x, Pp.y, Pp.z, 1.f);
@@ -200,7 +215,7 @@ extern "C" int rt_render_aov_motion_device(rt_ctx *ctx, const rt_params *p, cons
     AovCall a;
     if (int rc = aov_begin(ctx, p, pose, rows, out_aov_dev, stream, 0, a); rc != RT_OK || a.n == 0) return rc;
     note_between(ctx, a.q, {{out_prev_dev, 2 * (size_t)a.n * sizeof(float4)}});
-    rtk::AovMotion am{};
+    rtk::AovMotionNormals am{};
     am.verts_prev = static_cast<const float4 *>(ctx->verts_prev.p);
     am.prev = static_cast<float4 *>(out_prev_dev);
     am.snap_mask = ctx->verts_prev.p ? ctx->snap_mask : 0u;           // (a set bit means the buffer exists: rt_mesh_snapshot_vertices)
@@ -212,8 +227,17 @@ extern "C" int rt_render_aov_motion_device(rt_ctx *ctx, const rt_params *p, cons
             for (int c = 0; c < 3; ++c) am.m[k].t[c] = motion[k].translation[c];
         }
     }
-    hipLaunchKernelGGL((rtk::aov_close_kernel<true, rtk::AovMotion>), dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, a.q, a.scn, a.fr, tex_scene(ctx), a.tl.st.M, a.n,
-                       static_cast<float4 *>(out_aov_dev), am);
+    // the previous shading normals: only while a mesh that shades smoothly holds a normal snapshot (a set bit means nrm_prev exists: rt_mesh_snapshot_normals)
+    am.nsnap_mask = ctx->nrm_prev.p ? ctx->nsnap_mask & (uint32_t)a.scn.smooth_mask : 0u;
+    const dim3 grid((unsigned)((a.n + 255) / 256));
+    if (am.nsnap_mask) {
+        am.nrm_prev = static_cast<const float4 *>(ctx->nrm_prev.p);
+        if (ctx->nsnap_ev && a.q != ctx->stream_) RT_HIP(ctx, hipStreamWaitEvent(a.q, ctx->nsnap_ev, 0));
+        hipLaunchKernelGGL((rtk::aov_close_kernel<true, rtk::AovMotionNormals>), grid, dim3(256), 0, a.q, a.scn, a.fr, tex_scene(ctx), a.tl.st.M, a.n, static_cast<float4 *>(out_aov_dev), am);
+    } else {
+        const rtk::AovMotion plain = am;                              // (the argument the kernel always had)
+        hipLaunchKernelGGL((rtk::aov_close_kernel<true, rtk::AovMotion>), grid, dim3(256), 0, a.q, a.scn, a.fr, tex_scene(ctx), a.tl.st.M, a.n, static_cast<float4 *>(out_aov_dev), plain);
+    }
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }

@@ -8,6 +8,7 @@
 #include "rt_travq.hip.h"
 #include "rt_path.hip.h"
 #include "rt_meshops.hip.h"
+#include "rt_normals.hip.h"
 #include "rt_qnodes.hip.h"
 #include "rt_bvhbuild.hip.h"
 #include "rt_lbvh.hip.h"
@@ -112,7 +113,9 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     ctx->parts_valid = false;                                            // (the per-mesh records describe the scene this call installs, or none)
     ctx->tex_mask = 0;                                                   // a new scene is untextured, also when this call fails
-    ctx->snap_mask = 0;                                                  // ... and holds no vertex snapshot (rt_mesh_snapshot_vertices)
+    ctx->snap_mask = 0;                                                  // ... and holds no vertex snapshot (rt_mesh_snapshot_vertices),
+    ctx->nsnap_mask = 0; ctx->vnrm_mask = 0;                             // no normal snapshot and no computed vertex normals (rt_mesh_snapshot_normals, rt_mesh_compute_normals*)
+    ctx->vcsr_valid = false;
     ctx->still.shading_changed();
     ctx->still.mesh_changed();
     if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(ctx, RT_ERR_INVALID, "bad sphere array");

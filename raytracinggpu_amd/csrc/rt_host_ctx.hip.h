@@ -218,6 +218,18 @@ struct rt_ctx {
     DevBuf verts_prev{bufs};
     uint32_t snap_mask = 0;
     Event snap_ev;                                                   // the last snapshot's copy on the context's stream: a motion call on ANOTHER stream waits for it
+    // rt_mesh_compute_normals[_of] (rt_normals.hip.h): the adjacency of the scene's position vertices in CSR form -- vcsr_off: n_verts + 1 offsets; vcsr_rank: per vertex the
+    // visit ranks of the corners that name it, ascending in the uploaded triangle order -- built on the host by the first call and kept until the triangle order or the
+    // visit order changes (rt_scene_upload*, every rebuild); vnrm: the normals it computes (n_verts float4, indexed like `verts`) and vnrm_mask the objects whose range of
+    // it was written since the upload (rt_mesh_get_vertex_normals).
+    DevBuf vcsr_off{bufs}, vcsr_rank{bufs}, vnrm{bufs};
+    bool vcsr_valid = false;
+    uint32_t vnrm_mask = 0;
+    // rt_mesh_snapshot_normals: `nrm` as it was when a smooth mesh was last snapshotted (3 n_tris float4, by visit rank; allocated by the first snapshot), the objects whose
+    // range of it is current, and the event of the last copy.  Read by rt_render_aov_motion* alone.  Indexed by visit rank: an upload AND every rebuild clear the mask.
+    DevBuf nrm_prev{bufs};
+    uint32_t nsnap_mask = 0;
+    Event nsnap_ev;
     int n_cus = 0;
     DevBuf wfM{bufs}, wfT{bufs}, wfLS{bufs}, wfSID{bufs}, wfSamp{bufs};   // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
     DevBuf wfDCH{bufs};                                             // ... the dead-channel byte of each path (wf_dead_channels)

@@ -305,6 +305,152 @@ int rt_mesh_snapshot_mask(const rt_ctx *ctx, uint32_t *mask) {
     return RT_OK;
 }
 
+// The adjacency rt_mesh_compute_normals* walks (rt_normals.hip.h), for every vertex of the scene at once: a counting sort of the corners by the vertex they name, the
+// triangles taken in ascending uploaded order (up_indices: as uploaded, or as the last rebuild reported -- the order gather_corners calls `src`), corners 0, 1, 2; what is
+// stored is the triangle's visit rank (the inverse of tri_perm), where retri_kernel keeps its face normal.  A triangle in no leaf has no rank, no record and no part in
+// any sum.  Built and uploaded once; install_scene and install_lbvh_device drop it.
+static int ensure_vertex_csr(rt_ctx *ctx) {
+    if (ctx->vcsr_valid) return RT_OK;
+    if (int rr = refresh_host_mesh(ctx); rr != RT_OK) return rr;
+    const int nv = ctx->scene.n_verts;
+    const size_t nt = ctx->tri_perm.size();
+    if (nt != (size_t)ctx->scene.n_tris || ctx->up_indices.size() != 3 * (size_t)ctx->n_up_tris) return fail(ctx, RT_ERR_INTERNAL, "the host's triangle orders do not describe the scene in use");
+    std::vector<int> visit_of((size_t)ctx->n_up_tris, -1), off((size_t)nv + 1, 0), rank(3 * nt);
+    for (size_t t = 0; t < nt; ++t) {
+        const int g = ctx->tri_perm[t];
+        if (g < 0 || g >= ctx->n_up_tris) return fail(ctx, RT_ERR_INTERNAL, "visit rank %zu names triangle %d outside [0,%d)", t, g, ctx->n_up_tris);
+        visit_of[g] = (int)t;
+    }
+    size_t n_corners = 0;
+    for (int g = 0; g < ctx->n_up_tris; ++g) {
+        if (visit_of[g] < 0) continue;
+        for (int k = 0; k < 3; ++k) {
+            const int v = ctx->up_indices[3 * (size_t)g + k];
+            if (v < 0 || v >= nv) return fail(ctx, RT_ERR_INTERNAL, "triangle %d references vertex %d outside [0,%d)", g, v, nv);
+            ++off[(size_t)v + 1];
+            ++n_corners;
+        }
+    }
+    if (n_corners > rank.size()) return fail(ctx, RT_ERR_INTERNAL, "two visit ranks name one triangle");   // (cannot happen: visit_of holds one rank per triangle)
+    for (int v = 0; v < nv; ++v) off[(size_t)v + 1] += off[v];
+    std::vector<int> cur(off.begin(), off.end() - 1);
+    for (int g = 0; g < ctx->n_up_tris; ++g) {
+        if (visit_of[g] < 0) continue;
+        for (int k = 0; k < 3; ++k) rank[(size_t)cur[ctx->up_indices[3 * (size_t)g + k]]++] = visit_of[g];
+    }
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));                            // (an earlier adjacency may still be read by a launch on the stream)
+    if (int rc = upload(ctx, ctx->vcsr_off, off.data(), off.size() * sizeof(int)); rc != RT_OK) return rc;
+    if (int rc = upload(ctx, ctx->vcsr_rank, rank.data(), rank.size() * sizeof(int)); rc != RT_OK) return rc;
+    ctx->vcsr_valid = true;
+    return RT_OK;
+}
+
+// The vertex normals of one part's current shape, and the part shading with them: two launches on the context's stream behind the retri_kernel of the edits issued so far.
+// After the first call (the adjacency, the buffers) the host waits for nothing.
+static int compute_part_normals(rt_ctx *ctx, rt_ctx::MeshPart &p) {
+    if (int rc = ensure_vertex_csr(ctx); rc != RT_OK) return rc;
+    rtk::Scene &sc = ctx->scene;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t q = own_stream(ctx);
+    if (int rc = ensure(ctx, ctx->vnrm, (size_t)sc.n_verts * sizeof(float4)); rc != RT_OK) return rc;
+    const size_t bytes = 3 * (size_t)sc.n_tris * sizeof(float4);
+    if (sc.nrm == nullptr) {                                                        // no smooth mesh so far: the other meshes' entries read as zeros, as set_part_normals leaves them
+        if (int rc = ensure(ctx, ctx->nrm, bytes); rc != RT_OK) return rc;
+        RT_HIP(ctx, hipMemsetAsync(ctx->nrm.p, 0, bytes, q));
+    }
+    ctx->still.shading_changed();
+    int vb, ve;
+    visit_range(sc, p.obj, vb, ve);
+    if (p.nv > 0)
+        hipLaunchKernelGGL(rtk::vertex_normals_kernel, dim3((unsigned)((p.nv + 255) / 256)), dim3(256), 0, q, static_cast<const int *>(ctx->vcsr_off.p),
+                           static_cast<const int *>(ctx->vcsr_rank.p), static_cast<const float4 *>(ctx->tri.p), sc.n_tris, static_cast<float4 *>(ctx->vnrm.p), p.voff, p.nv);
+    if (ve > vb)
+        hipLaunchKernelGGL(rtk::corner_normals_kernel, dim3((unsigned)((3 * (size_t)(ve - vb) + 255) / 256)), dim3(256), 0, q, static_cast<const int4 *>(ctx->tidx.p) + vb,
+                           static_cast<const float4 *>(ctx->vnrm.p), sc.n_verts, static_cast<float4 *>(ctx->nrm.p) + 3 * (size_t)vb, 3 * (ve - vb));
+    RT_HIP(ctx, hipGetLastError());
+    p.smooth = true;
+    sc.smooth_mask |= 1 << p.obj;
+    sc.nrm = static_cast<const float4 *>(ctx->nrm.p);
+    ctx->vnrm_mask |= 1u << p.obj;
+    return RT_OK;
+}
+
+int rt_mesh_compute_normals(rt_ctx *ctx) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = the_one_part(ctx, p); rc != RT_OK) return rc;
+    if (!p) return RT_OK;                                                           // a mesh without triangles: never hit, nothing to shade
+    return compute_part_normals(ctx, *p);
+}
+
+int rt_mesh_compute_normals_of(rt_ctx *ctx, int object_slot) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!p) return RT_OK;
+    return compute_part_normals(ctx, *p);
+}
+
+// The per-vertex normals as the last rt_mesh_compute_normals* of that mesh wrote them (a later rt_mesh_transform* moves the corners' copies in `nrm`, not these)
+int rt_mesh_get_vertex_normals(rt_ctx *ctx, int object_slot, float *out_xyz, int n_vertices) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    rt_ctx::MeshPart *p = nullptr;
+    if (int rc = object_slot == -1 ? the_one_part(ctx, p) : find_part(ctx, object_slot, p); rc != RT_OK) return rc;
+    if (!out_xyz) return fail(ctx, RT_ERR_INVALID, "out_xyz is NULL");
+    if (!p || !((ctx->vnrm_mask >> p->obj) & 1u) || !ctx->vnrm.p) return fail(ctx, RT_ERR_INVALID, "no vertex normals were computed for this mesh since the upload (rt_mesh_compute_normals*)");
+    if (n_vertices != p->nv) return fail(ctx, RT_ERR_INVALID, "n_vertices %d differs from the %d vertices the mesh at object_slot %d was uploaded with", n_vertices, p->nv, p->obj);
+    std::vector<float4> hv((size_t)p->nv);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipMemcpyAsync(hv.data(), static_cast<const float4 *>(ctx->vnrm.p) + p->voff, hv.size() * sizeof(float4), hipMemcpyDeviceToHost, own_stream(ctx)));
+    RT_HIP(ctx, hipStreamSynchronize(own_stream(ctx)));
+    for (int i = 0; i < p->nv; ++i) { out_xyz[3 * (size_t)i] = hv[i].x; out_xyz[3 * (size_t)i + 1] = hv[i].y; out_xyz[3 * (size_t)i + 2] = hv[i].z; }
+    return RT_OK;
+}
+
+// The shading normals of a smooth mesh as they are now, kept for rt_render_aov_motion* (N' of a smooth deforming mesh): the part's visit range of `nrm` copied into the same
+// range of nrm_prev, as rt_mesh_snapshot_vertices copies `verts`.  A flat mesh has no shading normals to keep: its bit stays clear.  Nothing a render reads.
+int rt_mesh_snapshot_normals(rt_ctx *ctx, int object_slot, int keep) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
+    if (keep != 0 && keep != 1) return fail(ctx, RT_ERR_INVALID, "keep %d is neither 0 nor 1", keep);
+    rt_ctx::MeshPart *one = nullptr;
+    if (object_slot != -1) {
+        if (int rc = find_part(ctx, object_slot, one); rc != RT_OK) return rc;
+        if (!one) return RT_OK;                                                     // a mesh without triangles: never hit, nothing to keep
+    }
+    const rtk::Scene &sc = ctx->scene;
+    uint32_t bits = 0;
+    for (const rt_ctx::MeshPart &p : ctx->parts)
+        if ((!one || &p == one) && (!keep || (p.smooth && sc.nrm != nullptr))) bits |= 1u << p.obj;
+    if (!keep) { ctx->nsnap_mask &= ~bits; return RT_OK; }
+    if (!bits) return RT_OK;
+    if (int rc = ensure(ctx, ctx->nrm_prev, 3 * (size_t)sc.n_tris * sizeof(float4)); rc != RT_OK) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    for (const rt_ctx::MeshPart &p : ctx->parts) {
+        if (!((bits >> p.obj) & 1u)) continue;
+        int vb, ve;
+        visit_range(sc, p.obj, vb, ve);
+        if (ve > vb)
+            RT_HIP(ctx, hipMemcpyAsync(static_cast<float4 *>(ctx->nrm_prev.p) + 3 * (size_t)vb, static_cast<const float4 *>(ctx->nrm.p) + 3 * (size_t)vb,
+                                       3 * (size_t)(ve - vb) * sizeof(float4), hipMemcpyDeviceToDevice, own_stream(ctx)));
+    }
+    if (!ctx->nsnap_ev) RT_HIP(ctx, ctx->nsnap_ev.create(hipEventDisableTiming));
+    RT_HIP(ctx, hipEventRecord(ctx->nsnap_ev, own_stream(ctx)));
+    ctx->nsnap_mask |= bits;
+    return RT_OK;
+}
+
+int rt_mesh_normal_snapshot_mask(const rt_ctx *ctx, uint32_t *mask) {
+    if (!ctx || !mask) return fail(nullptr, RT_ERR_INVALID, "bad arguments");
+    *mask = ctx->nsnap_mask;
+    return RT_OK;
+}
+
 // TriangleMesh::buildBVH on the device, bit for bit (rt_bvhbuild.hip.h): leaves the flat tree in ctx->bb_arr and the triangle order in ctx->bb_idx
 // (up_off: the mesh's first triangle in tidx_up -- a forest's member; its vertex indices are global, the outputs are local to the mesh)
 static int rebuild_reference_tree(rt_ctx *ctx, const int nt, int &n_nodes_out, const int up_off = 0) {
@@ -533,6 +679,8 @@ static int install_lbvh_device(rt_ctx *ctx, const rtk::Scene &old, const int n_n
     ctx->travq_ok = n_nodes + 2 < (1 << rtk::kQNodeBits) && (uint64_t)n * 48 < ((uint64_t)1 << 32);   // leaves hold at most kLbvhLeaf triangles
     ctx->scene = sc;
     ctx->host_mesh_stale = true;                                                 // tri_perm / up_indices: on the device now (perm_dev, tidx_up)
+    ctx->vcsr_valid = false;                                                     // both orders changed: the adjacency of rt_mesh_compute_normals is rebuilt when next needed,
+    ctx->nsnap_mask = 0;                                                         // and a normal snapshot (by visit rank) describes the old layout
     ctx->have_scene = true;
     ctx->q16_topo_ok = true;                                                     // boxes are unions, bottom-up: they nest
     ctx->qw_topo_ok = true;                                                      // (an LBVH leaf holds at least one triangle)

@@ -157,6 +157,8 @@ int install_scene(rt_ctx *ctx, rtk::Scene sc, const rt_mesh *mesh, const std::ve
     ctx->have_scene = false;
     ctx->host_mesh_stale = false;                                     // what follows rewrites tri_perm / up_indices
     ctx->tri_perm.clear();
+    ctx->vcsr_valid = false;                                          // ... and with them the triangle order and the visit order: rt_mesh_compute_normals' adjacency,
+    ctx->nsnap_mask = 0;                                              // and the normal snapshots, which are indexed by visit rank (an upload and every host-side rebuild pass here)
     ctx->n_syn = 0;
     ctx->pre_of.clear();
     std::vector<float4> lo, hi, tri, verts;

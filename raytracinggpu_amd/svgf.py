@@ -34,7 +34,13 @@ class SvgfSequence:
     upsample, filter_at: see the module; up_k_normal, up_k_position: the upsample's weights (None: UPSAMPLE_DEFAULTS).  rectify: None, or the RectifyParams of the
     clamp (the sequence then owns two fast planes more and swaps them); fast_history: the fast history's length limit.  adaptive: None, or the SampleCountParams of
     the per-pixel sample counts (the sequence then owns a plane of counts, one byte per pixel).  deforming: the accumulation reprojects from previous-frame planes
-    (the sequence then owns two planes more at the working resolution); motion= of frame() then goes to render_aov_motion_device."""
+    (the sequence then owns two planes more at the working resolution); motion= of frame() then goes to render_aov_motion_device.
+
+    The per-frame recipe of a deforming sequence with a SMOOTH mesh, all on the context: ctx.mesh_snapshot_vertices(); ctx.mesh_snapshot_normals(); the frame's edits
+    (ctx.mesh_set_vertices(...), ctx.mesh_transform(...)); ctx.mesh_compute_normals() (or mesh_set_normals with the caller's own); then frame(...).  The sequence
+    itself issues no other call for it: render_aov_motion_device honours the context's normal-snapshot mask, and N' of the smooth mesh is the normal the previous
+    frame shaded with instead of the current one (without the snapshot min_normal_dot throws the history away wherever the surface turned).
+    A flat mesh needs the vertex snapshot alone."""
 
     def __init__(self, ctx, width, height, svgf=None, temporal=None, camera=None, stream=None, upsample=1, filter_at="low", up_k_normal=None, up_k_position=None,
                  rectify=None, fast_history=FAST_HISTORY_DEFAULT, adaptive=None, deforming=False):

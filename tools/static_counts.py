@@ -214,7 +214,11 @@ def main():
     # the first-hit planes, the a-trous filter's three instantiations and the temporal accumulation (rt_aov.hip.h, rt_denoise.hip.h, rt_temporal.hip.h): whole kernels
     for name, pattern in (("aov_emit", r"^(_ZN3rtk15aov_emit_kernel\w*):"), ("aov_close", r"^(_ZN3rtk16aov_close_kernelILb0E\w*):"),
                           # ... and the form that also writes the previous-frame planes (rt_render_aov_motion*)
-                          ("aov_close_motion", r"^(_ZN3rtk16aov_close_kernelILb1E\w*):"),
+                          ("aov_close_motion", r"^(_ZN3rtk16aov_close_kernelILb1EJNS_9AovMotionEE\w*):"),
+                          # ... the one that reads a smooth mesh's previous shading normals too (rt_mesh_snapshot_normals), and the two launches of
+                          # rt_mesh_compute_normals* (rt_normals.hip.h)
+                          ("aov_close_motion_normals", r"^(_ZN3rtk16aov_close_kernelILb1EJNS_16AovMotionNormalsEE\w*):"),
+                          ("vertex_normals", r"^(_ZN3rtk21vertex_normals_kernel\w*):"), ("corner_normals", r"^(_ZN3rtk21corner_normals_kernel\w*):"),
                           ("denoise_pass", r"^(_ZN3rtk19denoise_pass_kernelILb0E\w*):"), ("denoise_var_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_5DnVarEE\w*):"),
                           ("svgf_pass", r"^(_ZN3rtk19denoise_pass_kernelILb1EJNS_6DnSvgfEE\w*):"),
                           ("temporal_accumulate", r"^(_ZN3rtk26temporal_accumulate_kernelILb0E\w*):"),
