@@ -242,6 +242,41 @@ int rt_scene_move_light(rt_ctx *ctx, float angular_speed, float dt);            
 int rt_scene_move_sphere(rt_ctx *ctx, int object_slot, const float v[3], float dt);        /* MoveObject, realtime:1092-1098 (dt there: 0.2)         */
 int rt_light_orbit(const rt_light *in, float angular_speed, float dt, rt_light *out);      /* in == out is allowed                                    */
 
+/* --- SEVERAL POINT LIGHTS (ABI 6, additive).  A scene holds n lights, 1 <= n <= RT_MAX_LIGHTS.  A diffuse segment still emits ONE shadow ray: to the light that the
+ *     sample's key picks with probability proportional to its intensity.  With that choice the estimator's weight I_k / p_k is the same number for every light -- the
+ *     total intensity -- so the frame is an unbiased estimate of the sum of the n one-light frames (direct AND indirect light) at the cost of one of them.
+ *     THE RULE, in binary32 with one rounding per operation:
+ *       prefix[0] = I_0;  prefix[k] = fl(prefix[k - 1] + I_k);  total = prefix[n - 1].
+ *       Segment d of a path whose sample key is hs = sample_hash(pixel_hash(...), samp) -- the key the segment's bounce already uses -- draws
+ *       r = uniform01(hs, d + 1, 2),  x = fl(r * total),  and k = the least index with prefix[k] >= x and prefix[k] > 0.
+ *       (Depth d + 1 with dim 2 collides with nothing: the jitter reads depth 0 with dims 2 and 3, the bounce of segment d depth d with dims 0 and 1.)
+ *       The segment's shadow ray goes to L_k and its direct term is direct_term(total, L_k, P, N): the position is L_k's, the only intensity the shading sees is `total`,
+ *       I_k is never used on its own.  Everything else is the one-light code on the operand L_k (shadow direction, any-hit bound, sphere shadowing, cpu:615, the moot-ray
+ *       and dead-channel rules).  The launch that closes the shadow ray picks k again from (hs, d): no path state is added.
+ *     What follows from the rule:
+ *       r lies in (0, 1], so x <= total and a k always exists;
+ *       a light of intensity 0 is never picked, whatever r is (prefix[k] == prefix[k - 1] >= x would have picked an earlier light; in front, prefix[k] > 0 fails);
+ *       GRANULARITY: a light that the running sum absorbs (prefix[k] == prefix[k - 1], as 1 after 1e10) is never picked either -- order a list of very unequal
+ *       lights by rising intensity.
+ *     The list is host state like the one light: no device memory is written, and a frame in flight keeps the table its launches captured.
+ *       rt_scene_upload*        leaves a list of the one uploaded light;        rt_scene_set_light   replaces the list with one light;
+ *       rt_scene_get_light      answers light 0;                                rt_scene_set_lights  replaces the list (n == 1: rt_scene_set_light);
+ *       rt_scene_get_lights     n always receives the count; out receives the list if cap >= count, cap == 0 asks for the count alone (out may be NULL);
+ *       rt_scene_set_light_at   replaces light k of the list;                   rt_scene_move_light_at  get, rt_light_orbit on light k, set.
+ *     With n == 1 every call and every frame is what it is without these entries, launch for launch.  RT_ERR_INVALID, list untouched: a NULL pointer, n outside
+ *     [1, RT_MAX_LIGHTS], k outside the list, cap below the count; and for a list of several: an intensity whose sign bit is set or that is not finite, a total that is
+ *     not finite or is 0.  (One light: whatever rt_scene_set_light accepts.)
+ *     While n > 1: rt_render*, _device, _device_batch, _async, _pose*, rt_progressive_frame render it through the wavefront variants (auto, wavefront, wavefront_lds,
+ *     wavefront_queue, lds_*; auto never resolves to lockstep); several samples, row shares and a posed camera included.  A still view keeps and uses the camera rays'
+ *     hits but neither the first shadow rays nor the shaded first hits: segment 0's shadow ray depends on the sample.  RT_ERR_UNSUPPORTED, outputs untouched:
+ *     rt_render_device_batch_scenes with scenes, rt_render_counts*, rt_count_work, the variants path, lockstep and global.  rt_multi_* contexts have no such
+ *     entries and always hold one light. */
+#define RT_MAX_LIGHTS 16
+int rt_scene_set_lights(rt_ctx *ctx, const rt_light *lights, int n);
+int rt_scene_get_lights(const rt_ctx *ctx, rt_light *out, int cap, int *n);
+int rt_scene_set_light_at(rt_ctx *ctx, int k, const rt_light *light);
+int rt_scene_move_light_at(rt_ctx *ctx, int k, float angular_speed, float dt);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

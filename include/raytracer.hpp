@@ -624,6 +624,20 @@ public:
         check(rt_scene_set_sphere(ctx_, s.id, &r), "rt_scene_set_sphere");
     }
     void move_light(float angular_speed, float dt = 2e-2f) { check(rt_scene_move_light(ctx_, angular_speed, dt), "rt_scene_move_light"); }
+    // Several point lights (rt_scene_set_lights): a diffuse hit picks one of them by intensity and shades it at the intensity of all.  1 .. RT_MAX_LIGHTS lights.
+    void set_lights(const std::vector<rt_light> &lights) { check(rt_scene_set_lights(ctx_, lights.data(), (int)lights.size()), "rt_scene_set_lights"); }
+    std::vector<rt_light> lights() {
+        std::vector<rt_light> l(RT_MAX_LIGHTS);
+        int n = 0;
+        check(rt_scene_get_lights(ctx_, l.data(), RT_MAX_LIGHTS, &n), "rt_scene_get_lights");
+        l.resize((size_t)n);
+        return l;
+    }
+    void set_light_at(int k, const Vector &L, float intensity) {
+        const rt_light l{{L[0], L[1], L[2]}, intensity};
+        check(rt_scene_set_light_at(ctx_, k, &l), "rt_scene_set_light_at");
+    }
+    void move_light_at(int k, float angular_speed, float dt = 2e-2f) { check(rt_scene_move_light_at(ctx_, k, angular_speed, dt), "rt_scene_move_light_at"); }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

@@ -39,8 +39,10 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_render_counts_device", "rt_render_counts", "rt_render_counts_info", "rt_sample_counts_device", "rt_sample_counts", "rt_kat_sample_plan",
            "rt_mesh_set_vertices", "rt_mesh_set_vertices_of", "rt_mesh_set_vertices_device",
            "rt_mesh_snapshot_vertices", "rt_mesh_snapshot_mask", "rt_render_aov_motion_device", "rt_render_aov_motion",
-           "rt_mesh_compute_normals", "rt_mesh_compute_normals_of", "rt_mesh_get_vertex_normals", "rt_mesh_snapshot_normals", "rt_mesh_normal_snapshot_mask"]
+           "rt_mesh_compute_normals", "rt_mesh_compute_normals_of", "rt_mesh_get_vertex_normals", "rt_mesh_snapshot_normals", "rt_mesh_normal_snapshot_mask",
+           "rt_scene_set_lights", "rt_scene_get_lights", "rt_scene_set_light_at", "rt_scene_move_light_at"]
 MAX_OBJECTS = 16
+MAX_LIGHTS = 16
 MAX_DEVICES = 16
 
 
@@ -423,6 +425,10 @@ def load():
     L.rt_scene_move_light.argtypes = [vp, C.c_float, C.c_float]
     L.rt_scene_move_sphere.argtypes = [vp, C.c_int, fp3, C.c_float]
     L.rt_light_orbit.argtypes = [C.POINTER(Light), C.c_float, C.c_float, C.POINTER(Light)]
+    L.rt_scene_set_lights.argtypes = [vp, C.POINTER(Light), C.c_int]
+    L.rt_scene_get_lights.argtypes = [vp, C.POINTER(Light), C.c_int, C.POINTER(C.c_int)]
+    L.rt_scene_set_light_at.argtypes = [vp, C.c_int, C.POINTER(Light)]
+    L.rt_scene_move_light_at.argtypes = [vp, C.c_int, C.c_float, C.c_float]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -678,6 +684,34 @@ class Context:
         l.position[:] = position
         l.intensity = intensity
         self._check(self._L.rt_scene_set_light(self._h, C.byref(l)))
+
+    # --- several point lights (rt_scene_set_lights): one picked per diffuse hit, by intensity; a light is (position, intensity)
+    def set_lights(self, lights):
+        """rt_scene_set_lights: the scene's lights become this list of (position, intensity), 1 .. MAX_LIGHTS of them"""
+        lights = list(lights)
+        arr = (Light * max(len(lights), 1))()
+        for l, (position, intensity) in zip(arr, lights):
+            l.position[:] = position
+            l.intensity = intensity
+        self._check(self._L.rt_scene_set_lights(self._h, arr, len(lights)))
+
+    def lights(self):
+        """rt_scene_get_lights -> [(position, intensity), ...]"""
+        arr = (Light * MAX_LIGHTS)()
+        n = C.c_int(0)
+        self._check(self._L.rt_scene_get_lights(self._h, arr, MAX_LIGHTS, C.byref(n)))
+        return [(tuple(float(x) for x in arr[k].position), float(arr[k].intensity)) for k in range(n.value)]
+
+    def set_light_at(self, k, position, intensity):
+        """rt_scene_set_light_at: light k of the list"""
+        l = Light()
+        l.position[:] = position
+        l.intensity = intensity
+        self._check(self._L.rt_scene_set_light_at(self._h, int(k), C.byref(l)))
+
+    def move_light_at(self, k, angular_speed, dt=2e-2):
+        """MoveLightSource (realtime_render.cu:1072-1090) on light k of the list"""
+        self._check(self._L.rt_scene_move_light_at(self._h, int(k), C.c_float(angular_speed), C.c_float(dt)))
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

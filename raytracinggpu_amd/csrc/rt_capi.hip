@@ -153,6 +153,7 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     sc.n_objects = n_objects;
     sc.mesh_slot = n_meshes > 0 ? sc.mesh[0].obj : -1;
     put_light(sc, *light);
+    ctx->n_lights = 1;                                                   // the scene this call installs has the one uploaded light (rt_scene_set_lights)
     sc.camx = camera->position[0]; sc.camy = camera->position[1]; sc.camz = camera->position[2]; sc.fov = camera->fov;
 
     PhaseClock pc;

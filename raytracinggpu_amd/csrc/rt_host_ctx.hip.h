@@ -168,6 +168,11 @@ struct rt_ctx {
     std::vector<DevBuf *> bufs;                                      // every device buffer of the context: each one's declaration below puts it here (rt_ctx_selfcheck)
     bool have_scene = false, have_kernel_time = false, have_tonemap_time = false;
     rtk::Scene scene{};
+    // The scene's lights (rt_scene_set_lights, rt_host_edit.hip.h).  One light lives in `scene` alone, as ever; a list of several is kept here, its first entry also in
+    // `scene` (rt_scene_get_light answers it), and reaches the kernels as the rtk::WfLights argument make_frame derives from it.  rt_scene_upload* and rt_scene_set_light
+    // set n_lights back to 1.
+    rt_light lights[rtk::kMaxLights] = {};
+    int n_lights = 1;
     DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.

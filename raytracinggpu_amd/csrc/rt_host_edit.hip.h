@@ -43,7 +43,84 @@ int rt_scene_set_light(rt_ctx *ctx, const rt_light *light) {
     if (!light) return fail(ctx, RT_ERR_INVALID, "light is NULL");
     if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
     put_light(ctx->scene, *light);
+    ctx->n_lights = 1;                                                   // the list is this one light
     return RT_OK;
+}
+
+// ---- several point lights (raytrace_hip.h "several point lights"): the list is host state too; a frame's launches capture the table make_frame derives from it ----
+// prefix[0] = I_0, prefix[k] = fl(prefix[k - 1] + I_k): one binary32 addition each (-ffp-contract=off), in index order
+static_assert(RT_MAX_LIGHTS == rtk::kMaxLights, "rtk::WfLights holds RT_MAX_LIGHTS lights");
+static void light_prefix(const rt_light *lights, int n, float *prefix) {
+    for (int k = 0; k < n; ++k) prefix[k] = k == 0 ? lights[0].intensity : prefix[k - 1] + lights[k].intensity;
+}
+// what a list of several must satisfy for the pick to be defined: non-negative finite intensities (sign bit clear: no -0), a finite total above 0
+static int lights_check(rt_ctx *ctx, const rt_light *lights, int n) {
+    float prefix[RT_MAX_LIGHTS];
+    for (int k = 0; k < n; ++k) {
+        const float I = lights[k].intensity;
+        if (std::signbit(I) || !std::isfinite(I)) return fail(ctx, RT_ERR_INVALID, "light %d: intensity %g has its sign bit set or is not finite", k, (double)I);
+    }
+    light_prefix(lights, n, prefix);
+    if (!std::isfinite(prefix[n - 1]) || prefix[n - 1] == 0.f) return fail(ctx, RT_ERR_INVALID, "the lights' total intensity %g is not finite or is 0", (double)prefix[n - 1]);
+    return RT_OK;
+}
+// the list becomes these n lights (checked by the caller)
+static void put_lights(rt_ctx *ctx, const rt_light *lights, int n) {
+    rt_light tmp[RT_MAX_LIGHTS];
+    memcpy(tmp, lights, (size_t)n * sizeof(rt_light));                   // (lights may point into ctx->lights)
+    memcpy(ctx->lights, tmp, (size_t)n * sizeof(rt_light));
+    put_light(ctx->scene, tmp[0]);
+    ctx->n_lights = n;
+}
+
+int rt_scene_set_lights(rt_ctx *ctx, const rt_light *lights, int n) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!lights) return fail(ctx, RT_ERR_INVALID, "lights is NULL");
+    if (n < 1 || n > RT_MAX_LIGHTS) return fail(ctx, RT_ERR_INVALID, "n %d outside [1,%d]", n, RT_MAX_LIGHTS);
+    if (n == 1) return rt_scene_set_light(ctx, lights);                  // one light: whatever rt_scene_set_light accepts
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (int rc = lights_check(ctx, lights, n); rc != RT_OK) return rc;
+    put_lights(ctx, lights, n);
+    return RT_OK;
+}
+
+int rt_scene_get_lights(const rt_ctx *ctx, rt_light *out, int cap, int *n) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!n) return fail(c, RT_ERR_INVALID, "n is NULL");
+    if (cap < 0 || (cap > 0 && !out)) return fail(c, RT_ERR_INVALID, "out is NULL with cap %d", cap);
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    *n = ctx->n_lights;
+    if (cap == 0) return RT_OK;                                          // the count alone
+    if (cap < ctx->n_lights) return fail(c, RT_ERR_INVALID, "cap %d is below the scene's %d lights", cap, ctx->n_lights);
+    if (ctx->n_lights == 1) return rt_scene_get_light(ctx, out);
+    memcpy(out, ctx->lights, (size_t)ctx->n_lights * sizeof(rt_light));
+    return RT_OK;
+}
+
+int rt_scene_set_light_at(rt_ctx *ctx, int k, const rt_light *light) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!light) return fail(ctx, RT_ERR_INVALID, "light is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (k < 0 || k >= ctx->n_lights) return fail(ctx, RT_ERR_INVALID, "light %d outside the scene's %d", k, ctx->n_lights);
+    if (ctx->n_lights == 1) return rt_scene_set_light(ctx, light);
+    rt_light l[RT_MAX_LIGHTS];
+    memcpy(l, ctx->lights, sizeof(l));
+    l[k] = *light;
+    if (int rc = lights_check(ctx, l, ctx->n_lights); rc != RT_OK) return rc;
+    put_lights(ctx, l, ctx->n_lights);
+    return RT_OK;
+}
+
+int rt_scene_move_light_at(rt_ctx *ctx, int k, float angular_speed, float dt) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_light l[RT_MAX_LIGHTS];
+    int n = 0;
+    int rc = rt_scene_get_lights(ctx, l, RT_MAX_LIGHTS, &n);
+    if (rc != RT_OK) return rc;
+    if (k < 0 || k >= n) return fail(ctx, RT_ERR_INVALID, "light %d outside the scene's %d", k, n);
+    if ((rc = rt_light_orbit(&l[k], angular_speed, dt, &l[k])) != RT_OK) return rc;
+    return rt_scene_set_light_at(ctx, k, &l[k]);
 }
 
 int rt_scene_get_sphere(const rt_ctx *ctx, int object_slot, rt_sphere *out) {

@@ -18,6 +18,12 @@ int check_params(rt_ctx *ctx, const rt_params *p, int &segs) {
     return RT_OK;
 }
 
+// While the scene holds several lights, only the kernels that take the table may render it: every other entry refuses (outputs untouched)
+int lights_refuse(rt_ctx *ctx, const char *what) {
+    if (ctx && ctx->n_lights > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene holds %d lights; only wf_advance takes more than one (rt_scene_set_lights)", what, ctx->n_lights);
+    return RT_OK;
+}
+
 // wf_travq instantiations: [STATS][R == 32][LDSN][LDSV]
 using TravqFn = void (*)(const rtk::Scene, const rtk::Frame, const rtk::WfState, const int, const int, const int, const int);
 template <bool S, int R> TravqFn travq_pick(bool ldsn, bool ldsv) {
@@ -132,7 +138,7 @@ Variant ask_variant(const rt_ctx *ctx, int variant, const rt_camera_pose *pose, 
     // own structure, the lock-step kernel) keeps a path in registers instead of streaming it through HBM once per bounce -- BASELINE config 2, 1920x1080 b 3: 0.198 against
     // 0.220 ms per frame (profiles/round5/ab_spheres_only.txt).  A posed camera exists in the wavefront family only.
     if (variant == RT_VARIANT_AUTO) {
-        const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch;
+        const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1;
         variant = lockstep ? RT_VARIANT_LOCKSTEP : RT_VARIANT_WAVEFRONT_QUEUE;
     }
     // BASELINE config 4 / north star: "hot triangle vertices and top BVH levels staged in LDS" = the work-stack traversal kernel
@@ -166,6 +172,7 @@ int resolve_variant(rt_ctx *ctx, int variant, const rt_camera_pose *pose, bool b
     if (ctx->tex_mask != 0 && !(v.wf_family && v.variant != RT_VARIANT_PATH))
         return fail(ctx, RT_ERR_UNSUPPORTED, "a textured mesh needs a variant that runs wf_advance (auto, wavefront, wavefront_lds, wavefront_queue, lds_*)");
     if (pose && !v.wf_family) return fail(ctx, RT_ERR_UNSUPPORTED, "a camera pose needs a wavefront or path variant");
+    if (!(v.wf_family && v.variant != RT_VARIANT_PATH)) return lights_refuse(ctx, "this variant");   // several lights: wf_advance_lights shades (auto, wavefront, wavefront_lds, wavefront_queue, lds_*)
     return RT_OK;
 }
 
@@ -176,6 +183,7 @@ struct Chunk {
     const rt_params *p; const rt_rows *rows; hipStream_t stream; unsigned long long *work_dev; const rtk::Batch *batch; bool rec_begin; int segs, nseg;
     rtk::Frame fr; rtk::Scene scn;
     const rtk::AnimSrc *anim = nullptr;
+    rtk::WfLights lt{};                                               // lt.n > 1: the scene holds several lights -- the argument of wf_advance_lights (make_frame)
 };
 void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Chunk &c) {
     const rt_params *p = c.p;
@@ -196,6 +204,17 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
         c.scn.camx = pose->position[0]; c.scn.camy = pose->position[1]; c.scn.camz = pose->position[2];
         fr.z = -(float)p->width / (2 * (float)std::tan((double)(pose->fov / 2)));   // realtime:1112, evaluated as cpu:694 is here
         fr.inv_n = (float)(1. / p->num_rays);                         // realtime:1131
+    }
+    if (ctx->n_lights > 1) {                                          // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
+        rtk::WfLights &lt = c.lt;
+        float prefix = 0.f;
+        for (int k = 0; k < rtk::kMaxLights; ++k) {
+            const rt_light &l = ctx->lights[std::min(k, ctx->n_lights - 1)];
+            if (k < ctx->n_lights) prefix = k == 0 ? l.intensity : prefix + l.intensity;   // one binary32 addition per light, in index order
+            lt.pos[k] = make_float4(l.position[0], l.position[1], l.position[2], prefix);
+        }
+        lt.total = prefix;
+        lt.n = ctx->n_lights;
     }
 }
 
@@ -652,6 +671,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     if (pt.st.n_paths == 0) return RT_OK;
     const bool counting = c.work_dev != nullptr;
     const bool tex = ctx->tex_mask != 0;                          // a textured mesh: wf_advance_tex, and the per-segment albedo store
+    const bool lights = c.lt.n > 1;                               // several lights: wf_advance_lights / wf_advance_tex_lights after the opening launch (never counting, never animated)
     const dim3 pg(pt.pblocks), pb(kn.adv_block);
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
@@ -715,9 +735,12 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
             rtk::TexScene ts = tex_scene(ctx);
             ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg;   // ALB[d * n_paths + i] inside the part's block, as LS
             if (anim) hipLaunchKernelGGL(rtk::wf_advance_tex_anim, pg, pb, 0, q, c.scn, pt.fr, ast, ts, static_cast<const rtk::AnimFrame *>(pt.anim));
+            else if (lights) hipLaunchKernelGGL(rtk::wf_advance_tex_lights, pg, pb, 0, q, c.scn, pt.fr, ast, ts, c.lt);
             else hipLaunchKernelGGL(advance_tex, pg, pb, 0, q, c.scn, pt.fr, ast, ts);
         } else if (anim) {
             hipLaunchKernelGGL(rtk::wf_advance_anim<false>, pg, pb, 0, q, c.scn, pt.fr, ast, static_cast<const rtk::AnimFrame *>(pt.anim));
+        } else if (lights) {
+            hipLaunchKernelGGL(rtk::wf_advance_lights, pg, pb, 0, q, c.scn, pt.fr, ast, c.lt);
         } else {
             hipLaunchKernelGGL(advance, pg, pb, 0, q, c.scn, pt.fr, ast);
         }
@@ -743,7 +766,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
     int rc;
     if ((rc = plan_trav(ctx, v, c.work_dev != nullptr, kn.travq_lds, t)) != RT_OK || (rc = cut_wavefront(ctx, c, t, w)) != RT_OK) return rc;
     w.still = still_eligible(ctx, c, t) ? 1 : 0;
-    w.still += w.still == 1 && kn.first_shadow_cache != 0;
+    w.still += w.still == 1 && kn.first_shadow_cache != 0 && c.lt.n <= 1;   // several lights: segment 0's shadow ray depends on the sample -- the hit level only
     w.still += w.still == 2 && kn.first_shade_cache != 0 && ctx->tex_mask == 0;
     if ((rc = size_wavefront(ctx, c, w, qr_grown)) != RT_OK) return rc;
     const int parts = (int)w.pv.size();
@@ -805,6 +828,8 @@ int launch_render_chunk(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, vo
     }
     Variant v;
     if ((rc = resolve_variant(ctx, p->variant, pose, batch != nullptr, v)) != RT_OK) return rc;
+    if (work_dev && (rc = lights_refuse(ctx, "rt_count_work")) != RT_OK) return rc;
+    if (batch && anim && (rc = lights_refuse(ctx, "rt_render_device_batch_scenes")) != RT_OK) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     Chunk c{p, rows, stream, work_dev, batch, rec_begin, segs, segs > 0 ? segs : 1, {}, {}, batch ? anim : nullptr};
     make_frame(ctx, out_dev, pose, c);
@@ -898,6 +923,7 @@ int plan_samples(rt_ctx *ctx, const uint8_t *counts_dev, int width, int height, 
 // look at the first-hit cache (m0 = 0; rt_ctx::fh is not touched) and enumerate every row of their queue.  No items: no chain, and the fold still writes the frame.
 int launch_render_counts(rt_ctx *ctx, const rt_params *p_in, const rt_camera_pose *pose, const uint8_t *counts_dev, const void *base_dev, void *out_dev, hipStream_t stream) {
     if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (int rl = lights_refuse(ctx, "rt_render_counts"); rl != RT_OK) return rl;
     const Knobs &kn = ctx->knobs;
     rt_params p = *p_in;
     p.num_rays = 1;                                                   // (not read: every pixel has its own)

@@ -687,7 +687,9 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #ifdef RT_NO_MARKS
 #define ADV_MARK(name) do { } while (0)
 #else
-#define ADV_MARK(name) asm volatile("rt_mark_adv_" name "_%=:" ::)
+// (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
+// them its text, stay what they were before those two existed -- tools/asm_compare.py)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -729,9 +731,28 @@ __device__ __forceinline__ bool wf_x_shadowed(int F, f3 L, LoadM load_m, LoadRay
 // SHADE 1 (wf_advance_fill): the launch that emits segment 0's shadow rays in a chain that READS the first-shadow cache also stores the first-shade records of its
 // first-sample items.  SHADE 2 (wf_advance_resume): the launch that opens a chain whose part's records are stored -- in place of wf_advance<FIRST> and the launch that closes
 // segment 0.  The other instantiations never look at `sh`.
-template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0>
+// SEVERAL POINT LIGHTS (rt_scene_set_lights; the rule: raytrace_hip.h "several point lights").  A diffuse segment still emits ONE shadow ray: to the light the sample's key
+// picks with probability proportional to its intensity, so that the estimator's weight I_k / p_k is the same number for every light -- the total.  The table is a kernel
+// argument of the two instantiations that read it (wf_advance_lights, wf_advance_tex_lights: LIGHTS) and of no other kernel: rtk::Scene does not grow.
+constexpr int kMaxLights = 16;               // RT_MAX_LIGHTS
+struct WfLights {
+    float4 pos[kMaxLights];                  // (position of light k, prefix[k] = fl(prefix[k - 1] + I_k)); entries from n on repeat the last one
+    float total;                             // prefix[n - 1]: the only intensity the shading sees
+    int n;
+};
+// the light of segment `seg` of the path whose sample key is hs: r = uniform01(hs, seg + 1, 2), x = fl(r total), the least k with prefix[k] >= x and prefix[k] > 0.  The
+// prefix sums do not decrease and r is in (0, 1], so both conditions hold from some k <= n - 1 on: k is the number of entries that fail.  The loop reads the table with a
+// wave-uniform index (scalar loads); the one per-lane read is the position, from the argument segment.
+__device__ __forceinline__ f3 wf_light_pick(const WfLights &lt, uint32_t hs, int seg) {
+    const float x = uniform01(hs, (uint32_t)(seg + 1), 2) * lt.total;
+    int k = 0;
+    for (int j = 0; j < lt.n; ++j) k += (lt.pos[j].w >= x && lt.pos[j].w > 0.f) ? 0 : 1;
+    const float4 p = lt.pos[k < kMaxLights - 1 ? k : kMaxLights - 1];
+    return mk(p.x, p.y, p.z);
+}
+template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, bool LIGHTS = false>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr,
-                                                const WfList &list = WfList{}, const WfShade &sh = WfShade{}) {
+                                                const WfList &list = WfList{}, const WfShade &sh = WfShade{}, const WfLights *__restrict__ lt = nullptr) {
     constexpr bool FILL = SHADE == 1, RESUME = SHADE == 2;
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
@@ -820,6 +841,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         // slot (fill: the ray every sample of the slot shares -- not from X0, which this launch writes).  Some accepted hit of the same ray decides as the nearest does.
         const bool x_close0 = st.x0 != 0 && !st.m0;
         unsigned long long xm = WF_NOHIT;
+        if (LIGHTS && (F & PF_HASX)) L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // the light segment d-1's shadow ray went to, picked again
         if (!RESUME && (F & PF_HASX)) {
             const bool shadowed = wf_x_shadowed(F, L, [&] {
                 const int first = s_rel * st.n_px;                    // (0 unless the chain traces several samples as items)
@@ -881,11 +903,12 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         sid = (__float_as_int(rb.w) >> SH_SID_SHIFT) & 255;
                     } else {
                         float nl;
+                        if (LIGHTS) { L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d); intensity = lt->total; }   // this segment's light, at the intensity of all
                         Ox = Pa; ux = shadow_dir(L, Pa, nl);                // the shadow ray of segment d
                         x_bound = wf_anyhit_bound(Pa, nl);
                         nrays += 1;
                         // the segment's direct term if the light turns out to be visible; kept until the shadow ray is back
-                        const float lvis = ANIM ? direct_term(intensity, L, P, N) : direct_term(sc, L, P, N);
+                        const float lvis = (ANIM || LIGHTS) ? direct_term(intensity, L, P, N) : direct_term(sc, L, P, N);
                         st.LS[(size_t)d * st.n_paths + i] = lvis;
                         // A surface that faces away from the light (mx = 0) has the direct term +0 whether the light is visible or not: shaded, cpu:616 stores the literal 0; lit,
                         // cpu:623 computes l = +0 -- the same 32 bits (a NaN or a -0 from a degenerate light is not +0 and keeps its ray).  The reference still calls intersect_all
@@ -1046,6 +1069,17 @@ __global__ __launch_bounds__(256, 8) void wf_advance_resume(const Scene sc, cons
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 2>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, sh);
+}
+// the two for a scene of several lights (never counting, never an animated batch or a list; the opening launch is wf_advance<false, true>: a camera ray knows no light)
+__global__ __launch_bounds__(256, 8) void wf_advance_lights(const Scene sc, const Frame fr, const WfState st, const WfLights lt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 0, true>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, &lt);
+}
+__global__ __launch_bounds__(256, 8) void wf_advance_tex_lights(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const WfLights lt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, false, true, false, false, 0, true>(sc, fr, st, i, wk, ts, nullptr, WfList{}, WfShade{}, &lt);
 }
 // the two for a frame of an animated batch (a batch never counts work: no STATS form)
 template <bool FIRST>

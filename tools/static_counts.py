@@ -250,6 +250,12 @@ def main():
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = advance_counts(kernel_text(asm, mm.group(1))) if name == "wf_advance_fill" else {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
+    # several point lights (rt_wavefront.hip.h WfLights): the two launches that pick a light per diffuse segment, whole (they plant no labels)
+    for name, pattern in (("wf_advance_lights", r"^(_ZN3rtk17wf_advance_lightsE\w*):"), ("wf_advance_tex_lights", r"^(_ZN3rtk21wf_advance_tex_lightsE\w*):")):
+        mm = re.search(pattern, asm, re.M)
+        if not mm:
+            raise SystemExit(f"static_counts: {name} not found in the assembly")
+        res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
         json.dump(res, f, indent=1)
