@@ -277,6 +277,37 @@ int rt_scene_get_lights(const rt_ctx *ctx, rt_light *out, int cap, int *n);
 int rt_scene_set_light_at(rt_ctx *ctx, int k, const rt_light *light);
 int rt_scene_move_light_at(rt_ctx *ctx, int k, float angular_speed, float dt);
 
+/* --- SOFT SHADOWS: point lights with a radius (ABI 6, additive).  Light k of the list has a radius rho_k >= 0: it is a shell of isotropic point emitters of total
+ *     intensity I_k on the sphere of radius rho_k about L_k.  It is NOT geometry: camera, bounce and shadow rays pass through it and it occludes nothing.  A diffuse
+ *     segment still emits ONE shadow ray, to one point of the shell of the light it picks, so the frame is an unbiased estimate of the sum, over the shell, of the
+ *     point-light frames ("several point lights" above): nothing of Scene::getColor is restated differently.
+ *     THE RULE.  Segment d of the path with sample key hs picks k as above.  While any radius of the list is above 0 it then does, in binary32 with one rounding per
+ *     operation:
+ *       r1 = uniform01(hs, D + d, 0),  r2 = uniform01(hs, D + d, 1)  with D = 1u << 29.  (The RNG keys on depth * 4 + dim modulo 2^32: these draws sit at 2^31 + 4 d + dim.
+ *       Every draw in use -- jitter, bounce, pick -- sits below 4 (segs + 1): nothing collides.  Dim 3 at depth d + 1 alone would give only one free number.)
+ *       z = 1 - 2 r1                           in [-1, 1): -1 is reached (r1 = 1), 1 is not (r1 > 0); exact
+ *       s = rt_sqrtf(1 - z z)                  (z z <= 1: never negative)
+ *       (sn, cs) = rt_sincos_2pi(2 pi (double)r2)
+ *       x = (float)(cs (double)s),  y = (float)(sn (double)s)                      -- the forms cosine_bounce uses
+ *       L' = L_k + rho_k (x, y, z)             per component, the product first.
+ *     The shadow ray goes to L' and the direct term is direct_term(total, L', P, N); everything else is the one-light code on the operand L' (shadow direction, any-hit
+ *     bound, the sphere decision at emission, cpu:615 at the close, the moot-ray and dead-channel rules).  The launch that closes the shadow ray derives L' again from
+ *     (hs, d): no path state is added.  A light of rho_k == 0 in a soft list uses L_k itself: the addition is skipped, a -0 coordinate keeps its bits.
+ *     The radii are host state beside the list; a frame in flight keeps what its launches captured.
+ *       rt_scene_upload*, rt_scene_set_light, rt_scene_set_lights            leave every radius 0: the new light replaces the old;
+ *       rt_scene_set_light_at, rt_scene_move_light_at, rt_scene_move_light   keep the radius of the light they touch, in a list of one too: a lamp that moves keeps its size;
+ *       rt_scene_set_light_radii       n must equal the list's count;        rt_scene_set_light_radius_at   the radius of light k;
+ *       rt_scene_get_light_radii       the cap / count convention of rt_scene_get_lights.
+ *     RT_ERR_INVALID, radii and list untouched: a NULL pointer, n different from the count, k outside the list, cap below the count, a radius whose sign bit is set or
+ *     that is not finite.  A list of ONE soft light takes whatever intensity rt_scene_set_light takes.
+ *     "Soft": some radius of the list is above 0.  With every radius 0 every call and every frame is what it is without these entries, launch for launch.  A soft scene
+ *     behaves everywhere as a scene of several lights does, a list of one included: the wavefront variants render it (auto never resolves to lockstep), a still view keeps
+ *     and uses the camera rays' hits only, and rt_render_device_batch_scenes with scenes, rt_render_counts*, rt_count_work and the variants path, lockstep and global
+ *     answer RT_ERR_UNSUPPORTED with their outputs untouched.  A radius that changes counts as a light change for the still view.  rt_multi_* contexts have no such entries. */
+int rt_scene_set_light_radii(rt_ctx *ctx, const float *radii, int n);
+int rt_scene_get_light_radii(const rt_ctx *ctx, float *out, int cap, int *n);
+int rt_scene_set_light_radius_at(rt_ctx *ctx, int k, float radius);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

@@ -638,6 +638,16 @@ public:
         check(rt_scene_set_light_at(ctx_, k, &l), "rt_scene_set_light_at");
     }
     void move_light_at(int k, float angular_speed, float dt = 2e-2f) { check(rt_scene_move_light_at(ctx_, k, angular_speed, dt), "rt_scene_move_light_at"); }
+    // Soft shadows (rt_scene_set_light_radii): light k is a shell of radius radii[k] about its position, sampled once per shadow ray.  One radius per light of the list.
+    void set_light_radii(const std::vector<float> &radii) { check(rt_scene_set_light_radii(ctx_, radii.data(), (int)radii.size()), "rt_scene_set_light_radii"); }
+    std::vector<float> light_radii() {
+        std::vector<float> r(RT_MAX_LIGHTS);
+        int n = 0;
+        check(rt_scene_get_light_radii(ctx_, r.data(), RT_MAX_LIGHTS, &n), "rt_scene_get_light_radii");
+        r.resize((size_t)n);
+        return r;
+    }
+    void set_light_radius_at(int k, float radius) { check(rt_scene_set_light_radius_at(ctx_, k, radius), "rt_scene_set_light_radius_at"); }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

@@ -40,7 +40,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_mesh_set_vertices", "rt_mesh_set_vertices_of", "rt_mesh_set_vertices_device",
            "rt_mesh_snapshot_vertices", "rt_mesh_snapshot_mask", "rt_render_aov_motion_device", "rt_render_aov_motion",
            "rt_mesh_compute_normals", "rt_mesh_compute_normals_of", "rt_mesh_get_vertex_normals", "rt_mesh_snapshot_normals", "rt_mesh_normal_snapshot_mask",
-           "rt_scene_set_lights", "rt_scene_get_lights", "rt_scene_set_light_at", "rt_scene_move_light_at"]
+           "rt_scene_set_lights", "rt_scene_get_lights", "rt_scene_set_light_at", "rt_scene_move_light_at",
+           "rt_scene_set_light_radii", "rt_scene_get_light_radii", "rt_scene_set_light_radius_at"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -429,6 +430,9 @@ def load():
     L.rt_scene_get_lights.argtypes = [vp, C.POINTER(Light), C.c_int, C.POINTER(C.c_int)]
     L.rt_scene_set_light_at.argtypes = [vp, C.c_int, C.POINTER(Light)]
     L.rt_scene_move_light_at.argtypes = [vp, C.c_int, C.c_float, C.c_float]
+    L.rt_scene_set_light_radii.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    L.rt_scene_get_light_radii.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
+    L.rt_scene_set_light_radius_at.argtypes = [vp, C.c_int, C.c_float]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -712,6 +716,24 @@ class Context:
     def move_light_at(self, k, angular_speed, dt=2e-2):
         """MoveLightSource (realtime_render.cu:1072-1090) on light k of the list"""
         self._check(self._L.rt_scene_move_light_at(self._h, int(k), C.c_float(angular_speed), C.c_float(dt)))
+
+    # --- soft shadows (rt_scene_set_light_radii): light k is a shell of radius radii[k] about its position, one point of it per shadow ray
+    def set_light_radii(self, radii):
+        """rt_scene_set_light_radii: one radius per light of the list"""
+        radii = [float(r) for r in radii]
+        arr = (C.c_float * max(len(radii), 1))(*radii)
+        self._check(self._L.rt_scene_set_light_radii(self._h, arr, len(radii)))
+
+    def light_radii(self):
+        """rt_scene_get_light_radii -> [radius, ...]"""
+        arr = (C.c_float * MAX_LIGHTS)()
+        n = C.c_int(0)
+        self._check(self._L.rt_scene_get_light_radii(self._h, arr, MAX_LIGHTS, C.byref(n)))
+        return [float(arr[k]) for k in range(n.value)]
+
+    def set_light_radius_at(self, k, radius):
+        """rt_scene_set_light_radius_at: the radius of light k of the list"""
+        self._check(self._L.rt_scene_set_light_radius_at(self._h, int(k), C.c_float(radius)))
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

@@ -173,6 +173,8 @@ struct rt_ctx {
     // set n_lights back to 1.
     rt_light lights[rtk::kMaxLights] = {};
     int n_lights = 1;
+    // ... and their radii (rt_scene_set_light_radii): entry k belongs to light k of the list, a list of one included; all 0 unless that entry set them
+    float light_radii[rtk::kMaxLights] = {};
     DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.

@@ -38,14 +38,29 @@ int rt_scene_get_light(const rt_ctx *ctx, rt_light *out) {
     return RT_OK;
 }
 
-int rt_scene_set_light(rt_ctx *ctx, const rt_light *light) {
+// The radii of the list (raytrace_hip.h "soft shadows") become these n, the rest 0.  A radius that changes is a light change for the still view: which levels a chain may
+// keep depends on it, and the shadow words of a point light are not a shell's.
+static void put_radii(rt_ctx *ctx, const float *radii, int n) {
+    bool changed = false;
+    for (int k = 0; k < RT_MAX_LIGHTS; ++k) {
+        const float r = k < n ? radii[k] : 0.f;
+        changed = changed || memcmp(&r, &ctx->light_radii[k], sizeof(float)) != 0;
+        ctx->light_radii[k] = r;
+    }
+    if (changed) ctx->still.shading_changed();
+}
+// the list becomes this one light; keep_radius: it is the light that was there, moved or edited (a lamp that moves keeps its size) -- otherwise a new light, a point
+static int set_one_light(rt_ctx *ctx, const rt_light *light, bool keep_radius) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     if (!light) return fail(ctx, RT_ERR_INVALID, "light is NULL");
     if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
     put_light(ctx->scene, *light);
     ctx->n_lights = 1;                                                   // the list is this one light
+    put_radii(ctx, ctx->light_radii, keep_radius ? 1 : 0);
     return RT_OK;
 }
+
+int rt_scene_set_light(rt_ctx *ctx, const rt_light *light) { return set_one_light(ctx, light, false); }
 
 // ---- several point lights (raytrace_hip.h "several point lights"): the list is host state too; a frame's launches capture the table make_frame derives from it ----
 // prefix[0] = I_0, prefix[k] = fl(prefix[k - 1] + I_k): one binary32 addition each (-ffp-contract=off), in index order
@@ -81,6 +96,7 @@ int rt_scene_set_lights(rt_ctx *ctx, const rt_light *lights, int n) {
     if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
     if (int rc = lights_check(ctx, lights, n); rc != RT_OK) return rc;
     put_lights(ctx, lights, n);
+    put_radii(ctx, nullptr, 0);                                          // new lights: points
     return RT_OK;
 }
 
@@ -103,7 +119,7 @@ int rt_scene_set_light_at(rt_ctx *ctx, int k, const rt_light *light) {
     if (!light) return fail(ctx, RT_ERR_INVALID, "light is NULL");
     if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
     if (k < 0 || k >= ctx->n_lights) return fail(ctx, RT_ERR_INVALID, "light %d outside the scene's %d", k, ctx->n_lights);
-    if (ctx->n_lights == 1) return rt_scene_set_light(ctx, light);
+    if (ctx->n_lights == 1) return set_one_light(ctx, light, true);
     rt_light l[RT_MAX_LIGHTS];
     memcpy(l, ctx->lights, sizeof(l));
     l[k] = *light;
@@ -121,6 +137,49 @@ int rt_scene_move_light_at(rt_ctx *ctx, int k, float angular_speed, float dt) {
     if (k < 0 || k >= n) return fail(ctx, RT_ERR_INVALID, "light %d outside the scene's %d", k, n);
     if ((rc = rt_light_orbit(&l[k], angular_speed, dt, &l[k])) != RT_OK) return rc;
     return rt_scene_set_light_at(ctx, k, &l[k]);
+}
+
+// ---- lights with a radius (raytrace_hip.h "soft shadows"): one radius per light of the list, host state beside it ----
+static int radius_check(rt_ctx *ctx, int k, float r) {
+    if (std::signbit(r) || !std::isfinite(r)) return fail(ctx, RT_ERR_INVALID, "light %d: radius %g has its sign bit set or is not finite", k, (double)r);
+    return RT_OK;
+}
+
+int rt_scene_set_light_radii(rt_ctx *ctx, const float *radii, int n) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!radii) return fail(ctx, RT_ERR_INVALID, "radii is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (n != ctx->n_lights) return fail(ctx, RT_ERR_INVALID, "n %d is not the scene's %d lights", n, ctx->n_lights);
+    for (int k = 0; k < n; ++k) if (int rc = radius_check(ctx, k, radii[k]); rc != RT_OK) return rc;
+    float r[RT_MAX_LIGHTS];
+    memcpy(r, radii, (size_t)n * sizeof(float));                         // (radii may point into ctx->light_radii)
+    put_radii(ctx, r, n);
+    return RT_OK;
+}
+
+int rt_scene_get_light_radii(const rt_ctx *ctx, float *out, int cap, int *n) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!n) return fail(c, RT_ERR_INVALID, "n is NULL");
+    if (cap < 0 || (cap > 0 && !out)) return fail(c, RT_ERR_INVALID, "out is NULL with cap %d", cap);
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    *n = ctx->n_lights;
+    if (cap == 0) return RT_OK;                                          // the count alone
+    if (cap < ctx->n_lights) return fail(c, RT_ERR_INVALID, "cap %d is below the scene's %d lights", cap, ctx->n_lights);
+    memcpy(out, ctx->light_radii, (size_t)ctx->n_lights * sizeof(float));
+    return RT_OK;
+}
+
+int rt_scene_set_light_radius_at(rt_ctx *ctx, int k, float radius) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (k < 0 || k >= ctx->n_lights) return fail(ctx, RT_ERR_INVALID, "light %d outside the scene's %d", k, ctx->n_lights);
+    if (int rc = radius_check(ctx, k, radius); rc != RT_OK) return rc;
+    float r[RT_MAX_LIGHTS];
+    memcpy(r, ctx->light_radii, sizeof(r));
+    r[k] = radius;
+    put_radii(ctx, r, ctx->n_lights);
+    return RT_OK;
 }
 
 int rt_scene_get_sphere(const rt_ctx *ctx, int object_slot, rt_sphere *out) {
@@ -153,7 +212,7 @@ int rt_scene_move_light(rt_ctx *ctx, float angular_speed, float dt) {
     rt_light l;
     int rc = rt_scene_get_light(ctx, &l);
     if (rc == RT_OK) rc = rt_light_orbit(&l, angular_speed, dt, &l);
-    if (rc == RT_OK) rc = rt_scene_set_light(ctx, &l);
+    if (rc == RT_OK) rc = set_one_light(ctx, &l, true);                  // light 0, moved: it keeps its radius
     return rc;
 }
 

@@ -18,9 +18,15 @@ int check_params(rt_ctx *ctx, const rt_params *p, int &segs) {
     return RT_OK;
 }
 
-// While the scene holds several lights, only the kernels that take the table may render it: every other entry refuses (outputs untouched)
+// "soft": some light of the list has a radius above 0 (rt_scene_set_light_radii).  A soft scene behaves everywhere as a scene of several lights does, a list of one included
+bool lights_soft(const rt_ctx *ctx) {
+    for (int k = 0; k < ctx->n_lights; ++k) if (ctx->light_radii[k] > 0.f) return true;
+    return false;
+}
+// While the scene holds several lights, or a light with a radius, only the kernels that take the table may render it: every other entry refuses (outputs untouched)
 int lights_refuse(rt_ctx *ctx, const char *what) {
     if (ctx && ctx->n_lights > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene holds %d lights; only wf_advance takes more than one (rt_scene_set_lights)", what, ctx->n_lights);
+    if (ctx && lights_soft(ctx)) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene's light has a radius; only wf_advance samples it (rt_scene_set_light_radii)", what);
     return RT_OK;
 }
 
@@ -138,7 +144,7 @@ Variant ask_variant(const rt_ctx *ctx, int variant, const rt_camera_pose *pose, 
     // own structure, the lock-step kernel) keeps a path in registers instead of streaming it through HBM once per bounce -- BASELINE config 2, 1920x1080 b 3: 0.198 against
     // 0.220 ms per frame (profiles/round5/ab_spheres_only.txt).  A posed camera exists in the wavefront family only.
     if (variant == RT_VARIANT_AUTO) {
-        const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1;
+        const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1 && !lights_soft(ctx);
         variant = lockstep ? RT_VARIANT_LOCKSTEP : RT_VARIANT_WAVEFRONT_QUEUE;
     }
     // BASELINE config 4 / north star: "hot triangle vertices and top BVH levels staged in LDS" = the work-stack traversal kernel
@@ -183,7 +189,8 @@ struct Chunk {
     const rt_params *p; const rt_rows *rows; hipStream_t stream; unsigned long long *work_dev; const rtk::Batch *batch; bool rec_begin; int segs, nseg;
     rtk::Frame fr; rtk::Scene scn;
     const rtk::AnimSrc *anim = nullptr;
-    rtk::WfLights lt{};                                               // lt.n > 1: the scene holds several lights -- the argument of wf_advance_lights (make_frame)
+    rtk::WfSoftLights sl{};                                           // sl.lt.n > 1: the scene holds several lights -- sl.lt is the argument of wf_advance_lights (make_frame)
+    bool soft = false;                                                // some light has a radius: sl, radii included, is the argument of wf_advance_soft
 };
 void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Chunk &c) {
     const rt_params *p = c.p;
@@ -205,13 +212,17 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
         fr.z = -(float)p->width / (2 * (float)std::tan((double)(pose->fov / 2)));   // realtime:1112, evaluated as cpu:694 is here
         fr.inv_n = (float)(1. / p->num_rays);                         // realtime:1131
     }
-    if (ctx->n_lights > 1) {                                          // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
-        rtk::WfLights &lt = c.lt;
+    c.soft = lights_soft(ctx);
+    if (ctx->n_lights > 1 || c.soft) {                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
+        rtk::WfLights &lt = c.sl.lt;
+        const rt_light one{{ctx->scene.Lx, ctx->scene.Ly, ctx->scene.Lz}, ctx->scene.intensity};   // a soft list of one lives in `scene` alone, as every list of one
         float prefix = 0.f;
         for (int k = 0; k < rtk::kMaxLights; ++k) {
-            const rt_light &l = ctx->lights[std::min(k, ctx->n_lights - 1)];
+            const int kk = std::min(k, ctx->n_lights - 1);
+            const rt_light &l = ctx->n_lights > 1 ? ctx->lights[kk] : one;
             if (k < ctx->n_lights) prefix = k == 0 ? l.intensity : prefix + l.intensity;   // one binary32 addition per light, in index order
             lt.pos[k] = make_float4(l.position[0], l.position[1], l.position[2], prefix);
+            c.sl.radius[k] = ctx->light_radii[kk];                     // (entries from n on repeat the last one, as the positions do)
         }
         lt.total = prefix;
         lt.n = ctx->n_lights;
@@ -671,7 +682,8 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     if (pt.st.n_paths == 0) return RT_OK;
     const bool counting = c.work_dev != nullptr;
     const bool tex = ctx->tex_mask != 0;                          // a textured mesh: wf_advance_tex, and the per-segment albedo store
-    const bool lights = c.lt.n > 1;                               // several lights: wf_advance_lights / wf_advance_tex_lights after the opening launch (never counting, never animated)
+    const bool lights = c.sl.lt.n > 1 && !c.soft;                 // several lights: wf_advance_lights / wf_advance_tex_lights after the opening launch (never counting, never animated)
+    const bool soft = c.soft;                                     // ... some with a radius (or one with a radius): wf_advance_soft / wf_advance_tex_soft in their place
     const dim3 pg(pt.pblocks), pb(kn.adv_block);
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
@@ -735,12 +747,15 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
             rtk::TexScene ts = tex_scene(ctx);
             ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg;   // ALB[d * n_paths + i] inside the part's block, as LS
             if (anim) hipLaunchKernelGGL(rtk::wf_advance_tex_anim, pg, pb, 0, q, c.scn, pt.fr, ast, ts, static_cast<const rtk::AnimFrame *>(pt.anim));
-            else if (lights) hipLaunchKernelGGL(rtk::wf_advance_tex_lights, pg, pb, 0, q, c.scn, pt.fr, ast, ts, c.lt);
+            else if (soft) hipLaunchKernelGGL(rtk::wf_advance_tex_soft, pg, pb, 0, q, c.scn, pt.fr, ast, ts, c.sl);
+            else if (lights) hipLaunchKernelGGL(rtk::wf_advance_tex_lights, pg, pb, 0, q, c.scn, pt.fr, ast, ts, c.sl.lt);
             else hipLaunchKernelGGL(advance_tex, pg, pb, 0, q, c.scn, pt.fr, ast, ts);
         } else if (anim) {
             hipLaunchKernelGGL(rtk::wf_advance_anim<false>, pg, pb, 0, q, c.scn, pt.fr, ast, static_cast<const rtk::AnimFrame *>(pt.anim));
+        } else if (soft) {
+            hipLaunchKernelGGL(rtk::wf_advance_soft, pg, pb, 0, q, c.scn, pt.fr, ast, c.sl);
         } else if (lights) {
-            hipLaunchKernelGGL(rtk::wf_advance_lights, pg, pb, 0, q, c.scn, pt.fr, ast, c.lt);
+            hipLaunchKernelGGL(rtk::wf_advance_lights, pg, pb, 0, q, c.scn, pt.fr, ast, c.sl.lt);
         } else {
             hipLaunchKernelGGL(advance, pg, pb, 0, q, c.scn, pt.fr, ast);
         }
@@ -766,7 +781,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
     int rc;
     if ((rc = plan_trav(ctx, v, c.work_dev != nullptr, kn.travq_lds, t)) != RT_OK || (rc = cut_wavefront(ctx, c, t, w)) != RT_OK) return rc;
     w.still = still_eligible(ctx, c, t) ? 1 : 0;
-    w.still += w.still == 1 && kn.first_shadow_cache != 0 && c.lt.n <= 1;   // several lights: segment 0's shadow ray depends on the sample -- the hit level only
+    w.still += w.still == 1 && kn.first_shadow_cache != 0 && c.sl.lt.n <= 1 && !c.soft;   // several lights, or one with a radius: segment 0's shadow ray depends on the sample -- the hit level only
     w.still += w.still == 2 && kn.first_shade_cache != 0 && ctx->tex_mask == 0;
     if ((rc = size_wavefront(ctx, c, w, qr_grown)) != RT_OK) return rc;
     const int parts = (int)w.pv.size();

@@ -750,9 +750,41 @@ __device__ __forceinline__ f3 wf_light_pick(const WfLights &lt, uint32_t hs, int
     const float4 p = lt.pos[k < kMaxLights - 1 ? k : kMaxLights - 1];
     return mk(p.x, p.y, p.z);
 }
-template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, bool LIGHTS = false>
+// LIGHTS WITH A RADIUS (rt_scene_set_light_radii; the rule: raytrace_hip.h "soft shadows").  Light k is a shell of point emitters of radius rho_k about L_k; a segment's
+// operand is one point of it, L' = L_k + rho_k w(hs, seg), and everything downstream is the point-light code on L'.  The two instantiations that read the radii
+// (wf_advance_soft, wf_advance_tex_soft: LIGHTS == 2) take the table extended by them; WfLights as the LIGHTS == 1 kernels receive it is what it was.
+struct WfSoftLights {
+    WfLights lt;
+    float radius[kMaxLights];                // rho_k; entries from n on repeat the last one
+};
+// the point of the picked light that segment `seg` sees: w uniform on the unit sphere from the two draws at depth 2^29 + seg (the RNG keys on depth * 4 + dim modulo 2^32:
+// 2^31 + 4 seg + dim, which no jitter, bounce or pick draw reaches), in the forms cosine_bounce uses; a light of radius 0 is L_k itself, bit for bit (-0 included).  A soft
+// list of ONE light has every entry of the table equal: whatever its intensity is -- zero, negative, NaN -- the index lands on it.
+__device__ __forceinline__ f3 wf_light_point(const WfSoftLights &sl, uint32_t hs, int seg) {
+    const float xk = uniform01(hs, (uint32_t)(seg + 1), 2) * sl.lt.total;   // wf_light_pick's k (that function, as the LIGHTS == 1 kernels compile it, stays as it is)
+    int k = 0;
+    for (int j = 0; j < sl.lt.n; ++j) k += (sl.lt.pos[j].w >= xk && sl.lt.pos[j].w > 0.f) ? 0 : 1;
+    k = k < kMaxLights - 1 ? k : kMaxLights - 1;
+    const float4 p = sl.lt.pos[k];
+    const float rho = sl.radius[k];
+    f3 L = mk(p.x, p.y, p.z);
+    if (rho > 0.f) {
+        const float r1 = uniform01(hs, (1u << 29) + (uint32_t)seg, 0);
+        const float r2 = uniform01(hs, (1u << 29) + (uint32_t)seg, 1);
+        const float z = 1 - 2 * r1;                                   // [-1, 1), exact
+        const float s = rt_sqrtf(1 - z * z);
+        double sn, cs;
+        rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r2, sn, cs);
+        const float x = (float)(cs * (double)s);
+        const float y = (float)(sn * (double)s);
+        L = mk(L.x + rho * x, L.y + rho * y, L.z + rho * z);
+    }
+    return L;
+}
+template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, int LIGHTS = 0>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr,
-                                                const WfList &list = WfList{}, const WfShade &sh = WfShade{}, const WfLights *__restrict__ lt = nullptr) {
+                                                const WfList &list = WfList{}, const WfShade &sh = WfShade{}, const WfLights *__restrict__ lt = nullptr,
+                                                const WfSoftLights *__restrict__ sl = nullptr) {
     constexpr bool FILL = SHADE == 1, RESUME = SHADE == 2;
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
@@ -841,7 +873,8 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         // slot (fill: the ray every sample of the slot shares -- not from X0, which this launch writes).  Some accepted hit of the same ray decides as the nearest does.
         const bool x_close0 = st.x0 != 0 && !st.m0;
         unsigned long long xm = WF_NOHIT;
-        if (LIGHTS && (F & PF_HASX)) L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // the light segment d-1's shadow ray went to, picked again
+        if (LIGHTS == 1 && (F & PF_HASX)) L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // the light segment d-1's shadow ray went to, picked again
+        if (LIGHTS == 2 && (F & PF_HASX)) L = wf_light_point(*sl, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // ... and the point of its shell
         if (!RESUME && (F & PF_HASX)) {
             const bool shadowed = wf_x_shadowed(F, L, [&] {
                 const int first = s_rel * st.n_px;                    // (0 unless the chain traces several samples as items)
@@ -903,7 +936,8 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         sid = (__float_as_int(rb.w) >> SH_SID_SHIFT) & 255;
                     } else {
                         float nl;
-                        if (LIGHTS) { L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d); intensity = lt->total; }   // this segment's light, at the intensity of all
+                        if (LIGHTS == 1) { L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d); intensity = lt->total; }   // this segment's light, at the intensity of all
+                        if (LIGHTS == 2) { L = wf_light_point(*sl, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d); intensity = sl->lt.total; }   // ... a point of its shell
                         Ox = Pa; ux = shadow_dir(L, Pa, nl);                // the shadow ray of segment d
                         x_bound = wf_anyhit_bound(Pa, nl);
                         nrays += 1;
@@ -1074,12 +1108,24 @@ __global__ __launch_bounds__(256, 8) void wf_advance_resume(const Scene sc, cons
 __global__ __launch_bounds__(256, 8) void wf_advance_lights(const Scene sc, const Frame fr, const WfState st, const WfLights lt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 0, true>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, &lt);
+    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 0, 1>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, &lt);
 }
 __global__ __launch_bounds__(256, 8) void wf_advance_tex_lights(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const WfLights lt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, true, false, false, 0, true>(sc, fr, st, i, wk, ts, nullptr, WfList{}, WfShade{}, &lt);
+    if (i < st.n_paths) wf_advance_path<false, false, true, false, false, 0, 1>(sc, fr, st, i, wk, ts, nullptr, WfList{}, WfShade{}, &lt);
+}
+// the two for a scene whose lights have a radius (as the two above; a soft list of one light comes here too)
+__global__ __launch_bounds__(256, 8) void wf_advance_soft(const Scene sc, const Frame fr, const WfState st, const WfSoftLights sl) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 0, 2>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, nullptr, &sl);
+}
+// (the texture lookup's live values and a second binary64 sincos do not fit 64 registers together: 8 spilled.  Seven waves per SIMD, 72 registers, no scratch.)
+__global__ __launch_bounds__(256, 7) void wf_advance_tex_soft(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const WfSoftLights sl) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, false, true, false, false, 0, 2>(sc, fr, st, i, wk, ts, nullptr, WfList{}, WfShade{}, nullptr, &sl);
 }
 // the two for a frame of an animated batch (a batch never counts work: no STATS form)
 template <bool FIRST>

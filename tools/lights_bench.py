@@ -8,7 +8,11 @@
   quality   the four-light cat scene at 640 x 360, b = 3: RMSE in the tonemap's [0, 1] scale against a 1024-sample frame -- of a one-sample frame, and of the default
             SvgfSequence after eight frames; beside the same for ONE light of the total intensity at the first light's place.
 
-usage: python tools/lights_bench.py [--only frame|quality] > profiles/lights/lights_bench.txt"""
+  --radius R   (R > 0) lights with a radius (rt_scene_set_light_radii): `frame` gains the four lights at radius R -- the SAME context, the radii
+            switched between windows -- and its wf_advance_soft / traversal launches; `quality` gains the four soft lights against their own 1024-sample frame, with
+            the SvgfSequence's error after the first and after the last frame.
+
+usage: python tools/lights_bench.py [--only frame|quality] [--radius R] > profiles/lights/lights_bench.txt"""
 import argparse
 import os
 import statistics
@@ -22,6 +26,7 @@ ap.add_argument("--only", default="")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--calls", type=int, default=40)
 ap.add_argument("--windows", type=int, default=5)
+ap.add_argument("--radius", type=float, default=0.0)
 args = ap.parse_args()
 
 import numpy as np
@@ -71,6 +76,9 @@ def frame():
     c = context(RT_FIRST_SHADOW_CACHE="0")
     c.scene_upload(rt.scenes.spheres("cpu"), mesh)
     lights = {"four lights": lambda: c.set_lights(FOUR), "one light, RT_FIRST_SHADOW_CACHE=0": lambda: c.set_light(FOUR[0][0], TOTAL)}
+    soft = f"four lights of radius {args.radius:g}"
+    if args.radius > 0:
+        lights[soft] = lambda: (c.set_lights(FOUR), c.set_light_radii([args.radius] * len(FOUR)))
     rows = Rows(0, H, H, 1)
     buf = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
     p = params(123456, W, H)
@@ -95,6 +103,8 @@ def frame():
         print(f"  {name:36s} per round {' / '.join('%.4f' % x for x in r)} -> {spread(r)}", flush=True)
     a, b = statistics.median(runs["four lights"]), statistics.median(runs["one light, RT_FIRST_SHADOW_CACHE=0"])
     print(f"  four lights / one light: {a / b:.4f}", flush=True)
+    if args.radius > 0:
+        print(f"  {soft} / four lights: {statistics.median(runs[soft]) / a:.4f}", flush=True)
     print("per launch, under rt_stats_enable (the whole chain enqueued, part 0's launches bracketed by events); mean over 20 frames:", flush=True)
     for name, set_up in lights.items():
         set_up()
@@ -108,7 +118,7 @@ def frame():
             trav.append(s["trav_ms"] / max(s["trav_launches"], 1))
             ker.append(s["kernel_ms"])
         c.stats_enable(False)
-        print(f"  {name.split(',')[0]:12s} wf_advance {statistics.median(adv) * 1e3:.1f} us per launch ({s['adv_launches']} launches, {s['adv_paths']} paths, min {min(adv) * 1e3:.1f}, max {max(adv) * 1e3:.1f}); "
+        print(f"  {name.split(', RT')[0]:12s} wf_advance {statistics.median(adv) * 1e3:.1f} us per launch ({s['adv_launches']} launches, {s['adv_paths']} paths, min {min(adv) * 1e3:.1f}, max {max(adv) * 1e3:.1f}); "
               f"traversal {statistics.median(trav) * 1e3:.1f} us per launch ({s['trav_launches']}); kernel_ms {statistics.median(ker):.4f}", flush=True)
     c.close()
 
@@ -123,19 +133,36 @@ def quality():
     mesh = cat_mesh()
     ctx = context()
     print(f"quality: cat scene {w}x{h}, b = {B}; RMSE in the tonemap's [0, 1] scale against a 1024-sample frame of the same lights", flush=True)
-    for name, set_up in (("four lights", lambda: ctx.set_lights(FOUR)), ("one light of the total", lambda: ctx.set_light(FOUR[0][0], TOTAL))):
+    cases = [("four lights", lambda: ctx.set_lights(FOUR)), ("one light of the total", lambda: ctx.set_light(FOUR[0][0], TOTAL))]
+    if args.radius > 0:
+        cases.append((f"four lights of radius {args.radius:g}", lambda: (ctx.set_lights(FOUR), ctx.set_light_radii([args.radius] * len(FOUR)))))
+    kept = {}
+    for name, set_up in cases:
         ctx.scene_upload(rt.scenes.spheres("cpu"), mesh)
         set_up()
         ref = tonemap(ctx.render(params(7000, w, h, 1024)))
-        one = [float(np.sqrt(np.mean((tonemap(ctx.render(params(100 + i, w, h))) - ref) ** 2))) for i in range(frames)]
-        errs = []
+        ones = [tonemap(ctx.render(params(100 + i, w, h))) for i in range(frames)]
+        one = [float(np.sqrt(np.mean((f - ref) ** 2))) for f in ones]
+        errs, outs = [], []
         with rt.SvgfSequence(ctx, w, h) as seq:
             for i in range(frames):
                 out = seq.frame(params(100 + i, w, h))
                 ctx.synchronize()
-                errs.append(float(np.sqrt(np.mean((tonemap(ctx.device_to_host(out, (h, w, 4))) - ref) ** 2))))
-        print(f"  {name:24s} one sample: {np.mean(one):.5f} (mean of {frames} seeds, min {min(one):.5f}, max {max(one):.5f});  SvgfSequence after {frames} frames: {errs[-1]:.5f}  "
+                outs.append(tonemap(ctx.device_to_host(out, (h, w, 4))))
+                errs.append(float(np.sqrt(np.mean((outs[-1] - ref) ** 2))))
+        kept[name] = (ref, ones, outs)
+        print(f"  {name:24s} one sample: {np.mean(one):.5f} (mean of {frames} seeds, min {min(one):.5f}, max {max(one):.5f});  SvgfSequence after the first frame: {errs[0]:.5f}, after {frames} frames: {errs[-1]:.5f}  "
               "per frame " + " ".join(f"{e:.5f}" for e in errs), flush=True)
+    if args.radius > 0:
+        # the penumbrae alone: the pixels where the soft lights' 1024-sample frame departs from the point lights' by more than 0.02 in some channel
+        (ref, ones, outs), point = kept[cases[-1][0]], kept["four lights"][0]
+        mask = np.abs(ref - point).max(-1) > 0.02
+        rm = lambda a, m: float(np.sqrt(np.mean((a[m] - ref[m]) ** 2)))
+        print(f"  penumbra pixels (soft and point 1024-sample frames more than 0.02 apart): {int(mask.sum())} of {mask.size}; there the two references differ by "
+              f"{float(np.sqrt(np.mean((ref[mask] - point[mask]) ** 2))):.5f} RMS -- what a hard-edged answer would miss", flush=True)
+        for what, m in (("inside", mask), ("outside", ~mask)):
+            print(f"  {what:8s} one sample: {np.mean([rm(f, m) for f in ones]):.5f};  SvgfSequence after the first frame: {rm(outs[0], m):.5f}, after {frames} frames: {rm(outs[-1], m):.5f};  "
+                  f"mean signed error after {frames} frames: {float(np.mean(outs[-1][m] - ref[m])):+.5f}", flush=True)
     ctx.close()
 
 

@@ -251,7 +251,9 @@ def main():
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = advance_counts(kernel_text(asm, mm.group(1))) if name == "wf_advance_fill" else {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
     # several point lights (rt_wavefront.hip.h WfLights): the two launches that pick a light per diffuse segment, whole (they plant no labels)
-    for name, pattern in (("wf_advance_lights", r"^(_ZN3rtk17wf_advance_lightsE\w*):"), ("wf_advance_tex_lights", r"^(_ZN3rtk21wf_advance_tex_lightsE\w*):")):
+    # ... and the two for lights with a radius (WfSoftLights): the pick and a point of the picked light's shell
+    for name, pattern in (("wf_advance_lights", r"^(_ZN3rtk17wf_advance_lightsE\w*):"), ("wf_advance_tex_lights", r"^(_ZN3rtk21wf_advance_tex_lightsE\w*):"),
+                          ("wf_advance_soft", r"^(_ZN3rtk15wf_advance_softE\w*):"), ("wf_advance_tex_soft", r"^(_ZN3rtk19wf_advance_tex_softE\w*):")):
         mm = re.search(pattern, asm, re.M)
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
