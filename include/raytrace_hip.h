@@ -308,6 +308,46 @@ int rt_scene_set_light_radii(rt_ctx *ctx, const float *radii, int n);
 int rt_scene_get_light_radii(const rt_ctx *ctx, float *out, int cap, int *n);
 int rt_scene_set_light_radius_at(rt_ctx *ctx, int k, float radius);
 
+/* --- THIN LENS: a camera with an aperture and a focus distance (ABI 6, additive).  The context carries a lens: an aperture radius R >= 0 and a focus distance f > 0, both in
+ *     scene units; f is measured along the optical axis, so the plane of focus is perpendicular to the axis.  A point on the plane of focus is seen at the pinhole's pixel
+ *     from every point of the lens; everything else spreads over its circle of confusion.  No counterpart in the reference: its cameras are pinholes.
+ *     "Lens on": R > 0.  With R == 0 every call and every frame is what it is without these entries, launch for launch.
+ *     THE RULE.  With the lens on, sample samp of pixel (px, row) does, in binary32 with one rounding per operation, with the key hs = sample_hash(pixel_hash(fr, row, px,
+ *     seed), samp), O the camera position (the uploaded camera, a batch frame's camera, the pose's position), u = camera_dir(...) the unit direction as it is without a
+ *     lens, jitter included (the lens composes with sigma != 0), and the basis  ex = (1,0,0), ey = (0,1,0), a = (0,0,-1)  of the fixed camera or  ex = bx, ey = by,
+ *     a = -bz  of a posed one (z is negative, so the view axis is -bz; the negation is exact):
+ *       c = dot(u, a)                          in dot's operand order: (u.x a.x + u.y a.y) + u.z a.z
+ *       if !(c > 0) the ray stays (O, u).      (The posed camera keeps its position inside the direction -- posed_dir, the reference's own quirk: the rule is stated on u,
+ *                                              whatever it is.  There c has the sign of |z| - dot(C, bz), |z| = W / (2 tan(fov / 2)), for every pixel alike: from the
+ *                                              reference's default pose, C = (0, 0, 55) with fov pi / 2, a frame less than about 105 pixels wide is the pinhole's.)
+ *       t = f / c                              a correctly rounded quotient
+ *       F = O + t u                            per component, the product first
+ *       r1 = uniform01(hs, D, 0),  r2 = uniform01(hs, D, 1)  with D = 1u << 28.  (The RNG keys on depth * 4 + dim modulo 2^32: these draws sit at 2^30 + dim.  Jitter, bounce
+ *                                              and pick draws sit below 4 (segs + 1), the shell draws of soft shadows at 2^31 + 4 d + dim: nothing collides.)
+ *       s = rt_sqrtf(r1)                       in (0, 1]
+ *       (sn, cs) = rt_sincos_2pi(2 pi (double)r2)
+ *       dx = (float)(cs (double)s),  dy = (float)(sn (double)s)                    -- the forms cosine_bounce uses; (dx, dy) is uniform on the unit disc by area
+ *       lx = R dx,  ly = R dy
+ *       O' = (O + lx ex) + ly ey               per component, the products first.  The fixed camera uses the same expression with the literal basis, so a -0 coordinate
+ *                                              of O may become +0 (-0 + (+0) = +0).
+ *       u' = normalize(F - O')
+ *     The path starts with the ray (O', u'): the sphere decision at emission, the traversal, shading and ray counts are the pinhole code on that ray; a camera ray still
+ *     counts as one ray.  One kernel knows the rule: wf_advance_lens, the opening launch of every chain while the lens is on; the later launches are whichever kernels the
+ *     scene picks without a lens (several lights, soft lights, textures, smooth normals).
+ *     The lens is host state; a frame in flight keeps what its launches captured.  rt_scene_upload* leaves a pinhole (R = 0, f = 1): the camera comes with the upload.
+ *     RT_ERR_INVALID, the lens untouched: a NULL pointer, a radius whose sign bit is set or that is not finite, and with R > 0 a focus distance that is not finite or not
+ *     above 0 (with R == 0 the focus distance is stored as given and never read).
+ *     Lens on is rendered by every entry that runs wf_advance -- rt_render*, _device, _device_batch (each frame's own camera), _async, _pose*, rt_progressive_frame -- under
+ *     the variants auto, wavefront, wavefront_lds, wavefront_queue and lds_* (auto never resolves to lockstep), with several samples, row shares, RT_PARTS cuts and
+ *     pipelining.  RT_ERR_UNSUPPORTED, outputs untouched: rt_render_device_batch_scenes with scenes, rt_render_counts*, rt_count_work and the variants path, lockstep and
+ *     global.  rt_multi_* contexts have no such entries.
+ *     STILL VIEWS.  With a lens a pixel's camera ray depends on the sample whatever sigma is: while the lens is on no chain fills or uses the first-hit, first-shadow or
+ *     first-shade cache and none of their counters moves.  Turning the lens on or off empties all three: the first pinhole frame afterwards is a cold frame.
+ *     FEATURE BUFFERS.  rt_render_aov*, _motion and _surface keep the pixel-centre pinhole ray and the reprojection keeps the pinhole camera: the guides of a defocused frame
+ *     are sharp. */
+int rt_camera_set_lens(rt_ctx *ctx, float aperture_radius, float focus_distance);
+int rt_camera_get_lens(const rt_ctx *ctx, float *aperture_radius, float *focus_distance);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

@@ -22,6 +22,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -648,6 +649,13 @@ public:
         return r;
     }
     void set_light_radius_at(int k, float radius) { check(rt_scene_set_light_radius_at(ctx_, k, radius), "rt_scene_set_light_radius_at"); }
+    // Thin lens (rt_camera_set_lens): aperture radius and focus distance along the view axis, in scene units; radius 0 is the pinhole.  lens() -> (radius, focus)
+    void set_lens(float aperture_radius, float focus_distance) { check(rt_camera_set_lens(ctx_, aperture_radius, focus_distance), "rt_camera_set_lens"); }
+    std::pair<float, float> lens() {
+        float r = 0.f, f = 0.f;
+        check(rt_camera_get_lens(ctx_, &r, &f), "rt_camera_get_lens");
+        return {r, f};
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

@@ -41,7 +41,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_mesh_snapshot_vertices", "rt_mesh_snapshot_mask", "rt_render_aov_motion_device", "rt_render_aov_motion",
            "rt_mesh_compute_normals", "rt_mesh_compute_normals_of", "rt_mesh_get_vertex_normals", "rt_mesh_snapshot_normals", "rt_mesh_normal_snapshot_mask",
            "rt_scene_set_lights", "rt_scene_get_lights", "rt_scene_set_light_at", "rt_scene_move_light_at",
-           "rt_scene_set_light_radii", "rt_scene_get_light_radii", "rt_scene_set_light_radius_at"]
+           "rt_scene_set_light_radii", "rt_scene_get_light_radii", "rt_scene_set_light_radius_at",
+           "rt_camera_set_lens", "rt_camera_get_lens"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -433,6 +434,8 @@ def load():
     L.rt_scene_set_light_radii.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
     L.rt_scene_get_light_radii.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.rt_scene_set_light_radius_at.argtypes = [vp, C.c_int, C.c_float]
+    L.rt_camera_set_lens.argtypes = [vp, C.c_float, C.c_float]
+    L.rt_camera_get_lens.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -734,6 +737,17 @@ class Context:
     def set_light_radius_at(self, k, radius):
         """rt_scene_set_light_radius_at: the radius of light k of the list"""
         self._check(self._L.rt_scene_set_light_radius_at(self._h, int(k), C.c_float(radius)))
+
+    # --- thin lens (rt_camera_set_lens): an aperture radius and a focus distance; radius 0 is the pinhole
+    def set_lens(self, radius, focus):
+        """rt_camera_set_lens: aperture radius and focus distance along the view axis, in scene units"""
+        self._check(self._L.rt_camera_set_lens(self._h, C.c_float(radius), C.c_float(focus)))
+
+    def lens(self):
+        """rt_camera_get_lens -> (radius, focus)"""
+        r, f = C.c_float(0), C.c_float(0)
+        self._check(self._L.rt_camera_get_lens(self._h, C.byref(r), C.byref(f)))
+        return float(r.value), float(f.value)
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

@@ -175,6 +175,9 @@ struct rt_ctx {
     int n_lights = 1;
     // ... and their radii (rt_scene_set_light_radii): entry k belongs to light k of the list, a list of one included; all 0 unless that entry set them
     float light_radii[rtk::kMaxLights] = {};
+    // The camera's thin lens (rt_camera_set_lens): aperture radius and focus distance in scene units.  Host state like the lights: make_frame captures it by value, and a
+    // radius above 0 makes every chain open with wf_advance_lens.  rt_scene_upload* leaves a pinhole: the camera comes with the upload.
+    float lens_radius = 0.f, lens_focus = 1.f;
     DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.

@@ -182,6 +182,27 @@ int rt_scene_set_light_radius_at(rt_ctx *ctx, int k, float radius) {
     return RT_OK;
 }
 
+// ---- the camera's thin lens (raytrace_hip.h "thin lens"): host state; the opening launch of every chain captures it ----
+int rt_camera_set_lens(rt_ctx *ctx, float aperture_radius, float focus_distance) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (std::signbit(aperture_radius) || !std::isfinite(aperture_radius))
+        return fail(ctx, RT_ERR_INVALID, "aperture radius %g has its sign bit set or is not finite", (double)aperture_radius);
+    if (aperture_radius > 0.f && !(std::isfinite(focus_distance) && focus_distance > 0.f))
+        return fail(ctx, RT_ERR_INVALID, "focus distance %g is not finite or not above 0", (double)focus_distance);
+    if ((aperture_radius > 0.f) != (ctx->lens_radius > 0.f)) ctx->still.lens_changed();   // on or off: the still view's levels are emptied (rt_still.h)
+    ctx->lens_radius = aperture_radius;
+    ctx->lens_focus = focus_distance;
+    return RT_OK;
+}
+
+int rt_camera_get_lens(const rt_ctx *ctx, float *aperture_radius, float *focus_distance) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!aperture_radius || !focus_distance) return fail(const_cast<rt_ctx *>(ctx), RT_ERR_INVALID, "aperture_radius / focus_distance is NULL");
+    *aperture_radius = ctx->lens_radius;
+    *focus_distance = ctx->lens_focus;
+    return RT_OK;
+}
+
 int rt_scene_get_sphere(const rt_ctx *ctx, int object_slot, rt_sphere *out) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     rt_ctx *c = const_cast<rt_ctx *>(ctx);

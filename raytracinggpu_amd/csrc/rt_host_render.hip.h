@@ -27,6 +27,8 @@ bool lights_soft(const rt_ctx *ctx) {
 int lights_refuse(rt_ctx *ctx, const char *what) {
     if (ctx && ctx->n_lights > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene holds %d lights; only wf_advance takes more than one (rt_scene_set_lights)", what, ctx->n_lights);
     if (ctx && lights_soft(ctx)) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene's light has a radius; only wf_advance samples it (rt_scene_set_light_radii)", what);
+    // ... and while the camera has a lens, only a chain that opens with wf_advance_lens may render it
+    if (ctx && ctx->lens_radius > 0.f) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the camera has a lens; only wf_advance_lens samples it (rt_camera_set_lens)", what);
     return RT_OK;
 }
 
@@ -144,7 +146,8 @@ Variant ask_variant(const rt_ctx *ctx, int variant, const rt_camera_pose *pose, 
     // own structure, the lock-step kernel) keeps a path in registers instead of streaming it through HBM once per bounce -- BASELINE config 2, 1920x1080 b 3: 0.198 against
     // 0.220 ms per frame (profiles/round5/ab_spheres_only.txt).  A posed camera exists in the wavefront family only.
     if (variant == RT_VARIANT_AUTO) {
-        const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1 && !lights_soft(ctx);
+        const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1 && !lights_soft(ctx) &&
+                              !(ctx->lens_radius > 0.f);
         variant = lockstep ? RT_VARIANT_LOCKSTEP : RT_VARIANT_WAVEFRONT_QUEUE;
     }
     // BASELINE config 4 / north star: "hot triangle vertices and top BVH levels staged in LDS" = the work-stack traversal kernel
@@ -191,6 +194,7 @@ struct Chunk {
     const rtk::AnimSrc *anim = nullptr;
     rtk::WfSoftLights sl{};                                           // sl.lt.n > 1: the scene holds several lights -- sl.lt is the argument of wf_advance_lights (make_frame)
     bool soft = false;                                                // some light has a radius: sl, radii included, is the argument of wf_advance_soft
+    rtk::WfLens lens{};                                               // lens.radius > 0: the camera has a lens -- the argument of wf_advance_lens, the opening launch of every chain
 };
 void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Chunk &c) {
     const rt_params *p = c.p;
@@ -212,6 +216,7 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
         fr.z = -(float)p->width / (2 * (float)std::tan((double)(pose->fov / 2)));   // realtime:1112, evaluated as cpu:694 is here
         fr.inv_n = (float)(1. / p->num_rays);                         // realtime:1131
     }
+    c.lens = rtk::WfLens{ctx->lens_radius, ctx->lens_focus};          // (rt_camera_set_lens) captured by value, as the lights are
     c.soft = lights_soft(ctx);
     if (ctx->n_lights > 1 || c.soft) {                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
         rtk::WfLights &lt = c.sl.lt;
@@ -511,8 +516,10 @@ hipStream_t chain_stream(const rt_ctx *ctx, const Chunk &c, bool own0, int j);
 // Still views (rt_still.h).  A chunk's chains are eligible when the camera ray of a pixel cannot depend on the sample (sigma == 0: jitter_dir does not read the
 // key), one camera serves the whole chain (no batch), the traversal is the work-stack kernel's (it writes M itself: init_m == 0) and every launch is wanted for its own sake
 // by nobody: a counting run and a frame under rt_stats_enable trace every launch, so that their counters and their event brackets describe the full chain.
+// A camera with a lens (rt_camera_set_lens) draws a lens point per sample: its camera ray depends on the sample whatever sigma is.  Such a chunk is not only ineligible: its
+// chains stay away from the still view altogether (launch_wavefront, enqueue_chain), so that no level is filled or used and no counter moves.
 bool still_eligible(const rt_ctx *ctx, const Chunk &c, const TravPlan &t) {
-    return ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
+    return !(c.lens.radius > 0.f) && ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
            ctx->knobs.debug_trav == -2;
 }
 // What the camera rays' hits depend on besides the mesh, bit for bit (the RAY KEY), and what segment 0's shading and shadow rays depend on besides the ray key and what is
@@ -688,7 +695,8 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
     const rtk::QRows win_y = rtk::qrows_y(pt.st.n_paths, pt.st.log2S, pt.st.Q);
-    const rtk::StillChain sc = ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
+    const bool lens = c.lens.radius > 0.f;                        // the camera has a lens: the chain opens with wf_advance_lens and knows no still view
+    const rtk::StillChain sc = lens ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
     const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0);
     auto block = [&](const DevBuf &b) { return static_cast<unsigned long long *>(b.p) + pt.pxbase; };   // the part's block of a level
     auto records = [&] { rtk::WfShade sh{}; sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; sh.kill_x = plan.kill_x; return sh; };
@@ -713,6 +721,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     ost.m0 = plan.open_m0;
     if (plan.open == rtk::kAdvResume) hipLaunchKernelGGL(rtk::wf_advance_resume, pg, pb, 0, q, c.scn, pt.fr, ost, records());
     else if (anim) hipLaunchKernelGGL(rtk::wf_advance_anim<true>, pg, pb, 0, q, c.scn, pt.fr, ost, static_cast<const rtk::AnimFrame *>(pt.anim));
+    else if (lens) hipLaunchKernelGGL(rtk::wf_advance_lens, pg, pb, 0, q, c.scn, pt.fr, ost, c.lens);   // (never counting, never animated: lights_refuse)
     else hipLaunchKernelGGL(begin, pg, pb, 0, q, c.scn, pt.fr, ost);
     const auto advance = counting ? rtk::wf_advance<true, false> : rtk::wf_advance<false, false>;
     const auto advance_tex = counting ? rtk::wf_advance_tex<true> : rtk::wf_advance_tex<false>;
@@ -803,7 +812,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
     }
     ctx->stats.lds_bytes = (int)t.lds; ctx->stats.block_threads = t.tb; ctx->stats.grid_blocks = (int)w.pv[0].tblocks; ctx->stats.parts = parts; ctx->stats.travq_mode = t.travq_mode;
     if ((rc = start_chains(ctx, c, w, qr_grown, own0)) != RT_OK) return rc;
-    still_begin(ctx, c, t, w, own0);
+    if (!(c.lens.radius > 0.f)) still_begin(ctx, c, t, w, own0);
     // The chains of ONE sample chunk are issued for all sub-frames before the next chunk's.
     // (Rounds 2-4 issued all chunks of sub-frame 0 first: with hundreds of chains the host was still feeding stream 0 while stream 1 sat empty, the
     // sub-frames ran one after the other instead of side by side, and a 256-sample 1080p frame cost 1.26 ms per sample against 0.94 at 32 samples --

@@ -53,6 +53,30 @@ __device__ __forceinline__ f3 camera_dir(const Frame &fr, f3 C, float z, int px,
     if (fr.cam_mode == 1) v = posed_dir(fr, C, v);
     return jitter_dir(fr, v, hs);
 }
+// The THIN LENS (rt_camera_set_lens; the rule: raytrace_hip.h "thin lens"): the camera ray (O, u) of the sample with key hs becomes the ray from a point of the lens -- the
+// disc of radius R about O, perpendicular to the view axis a -- through the point where (O, u) meets the plane of focus at distance f along a.  The two draws sit at depth
+// 2^28 (the RNG keys on depth * 4 + dim modulo 2^32: 2^30 + dim, which no jitter, bounce, pick or shell draw reaches), in the forms cosine_bounce uses.  A ray that does not
+// look along the axis (c <= 0 or a NaN) stays as it is.  The fixed camera's basis is the literal one in the same expressions: a -0 coordinate of O may become +0.
+__device__ __forceinline__ void lens_ray(const Frame &fr, float R, float f, uint32_t hs, f3 &O, f3 &u) {
+    const bool posed = fr.cam_mode == 1;
+    const f3 ex = posed ? mk(fr.bx[0], fr.bx[1], fr.bx[2]) : mk(1.f, 0.f, 0.f);
+    const f3 ey = posed ? mk(fr.by[0], fr.by[1], fr.by[2]) : mk(0.f, 1.f, 0.f);
+    const f3 a = posed ? mk(-fr.bz[0], -fr.bz[1], -fr.bz[2]) : mk(0.f, 0.f, -1.f);   // z is negative: the view axis is -bz
+    const float c = dot(u, a);
+    if (!(c > 0.f)) return;
+    const float t = f / c;
+    const f3 F = O + t * u;
+    const float r1 = uniform01(hs, 1u << 28, 0);
+    const float r2 = uniform01(hs, 1u << 28, 1);
+    const float s = rt_sqrtf(r1);                                     // (0, 1]: uniform on the disc by area
+    double sn, cs;
+    rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r2, sn, cs);
+    const float dx = (float)(cs * (double)s);
+    const float dy = (float)(sn * (double)s);
+    const float lx = R * dx, ly = R * dy;
+    O = (O + lx * ex) + ly * ey;
+    u = normalize(F - O);
+}
 
 // ---- the hit ----
 // alpha, beta, gamma of triangle `tri` (visit order) for the ray (O, u): get_smooth_normal's expressions (realtime_render.cu:221-245).  The smooth normal, the

@@ -16,7 +16,7 @@
 //   - Keys are compared as bits: the caller zeroes its key's padding and puts the whole Scene in.  A wrong miss costs a refill, a wrong hit a silently wrong frame.  (StillKey::same)
 //   - What lives behind a pointer of the keys and is edited in place reaches them through two generation counters.                    (mesh_changed, shading_changed)
 //   - The eligibility levels nest: 0 none, 1 hit, 2 hit + shadow, 3 all three.  Chains of level 0 count as ineligible and touch nothing else; the list chains of
-//     rt_render_counts* do not come here at all.                                                                                      (begin, chain)
+//     rt_render_counts* do not come here at all, nor do the chains of a frame whose camera has a lens (lens_changed).                 (begin, chain)
 // Plain C++: the library and the host library (rth_still_replay, tests/test_still_view_model.py) compile the same text.
 #pragma once
 #include <stdint.h>
@@ -73,6 +73,9 @@ struct StillView {
     void mesh_changed() { ++mesh_gen; }
     // Every entry that writes what shading reads behind a pointer of the Scene -- normals, UVs, texels, texture records: the shadow words and the records are stale
     void shading_changed() { ++shade_gen; }
+    // rt_camera_set_lens turning the lens on or off.  Chains of a frame with the lens on do not come here at all (neither begin nor chain: no counter moves), so nothing
+    // else would tell the first pinhole frame after them that frames went by in between: every level is stale
+    void lens_changed() { ++mesh_gen; }
 
     // Before a chunk's chains are enqueued, after their streams are settled.  level: what the chunk is eligible for; the keys are read up to that level only; M0 / X0 / S0: where
     // the three buffers are now.  Any difference from what a level was stored under empties it and every level above.

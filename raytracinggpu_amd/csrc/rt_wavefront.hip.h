@@ -688,8 +688,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #define ADV_MARK(name) do { } while (0)
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
-// them its text, stay what they were before those two existed -- tools/asm_compare.py)
-#define ADV_MARK(name) do { if constexpr (!LIGHTS) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
+// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -781,10 +781,14 @@ __device__ __forceinline__ f3 wf_light_point(const WfSoftLights &sl, uint32_t hs
     }
     return L;
 }
-template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, int LIGHTS = 0>
+// A THIN LENS (rt_camera_set_lens; the rule: raytrace_hip.h "thin lens", the step: lens_ray in rt_shade.hip.h).  The camera ray is built in one place, the opening launch of a
+// chain: with the lens on that launch is wf_advance_lens (LENS, always FIRST), which takes the lens by value; every later launch of the chain is whichever kernel the scene
+// picks without a lens.  rtk::Scene and rtk::Frame do not grow.
+struct WfLens { float radius, focus; };
+template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, int LIGHTS = 0, bool LENS = false>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr,
                                                 const WfList &list = WfList{}, const WfShade &sh = WfShade{}, const WfLights *__restrict__ lt = nullptr,
-                                                const WfSoftLights *__restrict__ sl = nullptr) {
+                                                const WfSoftLights *__restrict__ sl = nullptr, const WfLens *__restrict__ ln = nullptr) {
     constexpr bool FILL = SHADE == 1, RESUME = SHADE == 2;
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
@@ -852,6 +856,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         } else {
             Oy = mk(camx, camy, camz);
             uy = camera_dir(fr, Oy, fr_z, px, row, sample_hash(pixel_hash(fr, row, px, fr_seed), samp));
+            if (LENS) lens_ray(fr, ln->radius, ln->focus, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), Oy, uy);   // from a point of the lens through the pinhole ray's point of focus
             emitY = true;                                             // continuation ray of segment 0
             nrays = 1;
         }
@@ -1126,6 +1131,12 @@ __global__ __launch_bounds__(256, 7) void wf_advance_tex_soft(const Scene sc, co
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths) wf_advance_path<false, false, true, false, false, 0, 2>(sc, fr, st, i, wk, ts, nullptr, WfList{}, WfShade{}, nullptr, &sl);
+}
+// the opening launch of a chain whose camera has a lens (never counting, never an animated batch or a list; the later launches are the scene's own)
+__global__ __launch_bounds__(256, 8) void wf_advance_lens(const Scene sc, const Frame fr, const WfState st, const WfLens ln) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<false, true, false, false, false, 0, 0, true>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, nullptr, nullptr, &ln);
 }
 // the two for a frame of an animated batch (a batch never counts work: no STATS form)
 template <bool FIRST>

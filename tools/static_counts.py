@@ -258,6 +258,11 @@ def main():
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
+    # the thin lens (rt_wavefront.hip.h WfLens): the opening launch of a chain whose camera has an aperture, whole (it plants no labels)
+    mm = re.search(r"^(_ZN3rtk15wf_advance_lensE\w*):", asm, re.M)
+    if not mm:
+        raise SystemExit("static_counts: wf_advance_lens not found in the assembly")
+    res["wf_advance_lens"] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
         json.dump(res, f, indent=1)
