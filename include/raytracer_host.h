@@ -39,10 +39,10 @@ int rth_write_png(const char *path, int W, int H, const uint8_t *rgb);
 int64_t rth_qrows_enumerate(int n_paths, int log2S, int Q, int tblocks, int which, int32_t info[4], int32_t *blk_len, int32_t *slots, int64_t cap);
 
 /* Test entry of the still view's state machine and chain plan (csrc/rt_still.h, shared with the render path): replays n_ev events of five numbers each on a new
- * state -- {0, level, ray key, scene, rest of the shading key}: a chunk begins; {1, part, segments, 1 a mesh | 2 row windows | 4 a Y window}: a chain is enqueued;
+ * state -- {0, level, ray key, scene, rest of the shading key}: a chunk begins; {1, part, segments, 1 a mesh | 2 row windows | 4 a Y window | 8 a plain chain under RT_CHAIN_ENDS}: a chain is enqueued;
  * {2}: a mesh edit; {3}: a shading edit; {4, level}: that level's buffer moved.  counts: the four counters of the three levels as they stand afterwards.  rows (up to
  * cap of 12 numbers each, returns how many there are): per chain its opening launch (position -1) and then its positions as (event, position, traversal launch, window
- * 0 none 1 Y 2 X, it writes the hit block, m0, x0, wf_advance 0 begin 1 resume 2 plain 3 fill, kill_x, and the chain's modes of the three levels 0 off 1 fill 2 use). */
+ * 0 none 1 Y 2 X, it writes the hit block, m0, x0, wf_advance 0 begin 1 resume 2 plain 3 fill 4 close, kill_x, and the chain's modes of the three levels 0 off 1 fill 2 use). */
 int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32_t *rows, int64_t cap);
 
 /* Test entries of the cut of a call's rows (csrc/rt_rowcut.h, shared with the render path).  rth_row_cut: n cases of seven numbers -- an rt_rows (row0, n_rows, tile_rows,

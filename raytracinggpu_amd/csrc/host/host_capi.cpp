@@ -94,9 +94,9 @@ int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32
             if (x[1] >= 2 && !buf[1]) buf[1] = next_buf++;
             if (x[1] >= 3 && !buf[2] && v.may_store_records(&shade[0], sizeof(shade[0]))) buf[2] = next_buf++;
             v.begin(x[1], &ray, sizeof(ray), shade, sizeof(shade), at(buf[0]), at(buf[1]), at(buf[2]));
-        } else if (x[0] == 1) {                                             // a chain of part x[1] with x[2] segments; x[3]: 1 a mesh, 2 row windows, 4 a Y window
+        } else if (x[0] == 1) {                                             // a chain of part x[1] with x[2] segments; x[3]: 1 a mesh, 2 row windows, 4 a Y window, 8 a plain chain that takes the closing kernel
             const StillChain c = v.chain(x[1], buf[2] != 0);
-            const StillPlan p = still_plan(c, x[2], (x[3] & 1) != 0, (x[3] & 2) != 0, (x[3] & 4) != 0);
+            const StillPlan p = still_plan(c, x[2], (x[3] & 1) != 0, (x[3] & 2) != 0, (x[3] & 4) != 0, (x[3] & 8) != 0);
             for (int it = p.first - 1; it < (p.n > p.first ? p.n : p.first); ++it, ++n) {
                 if (!rows || n >= cap) continue;
                 int32_t *r = rows + 12 * n;

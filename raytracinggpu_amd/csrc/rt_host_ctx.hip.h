@@ -79,6 +79,8 @@ struct Knobs {
     int first_shade_cache = 1; // RT_FIRST_SHADE_CACHE=0: every chain of a still view opens with wf_advance<FIRST> and closes segment 0 (A/B, cross-check; default: once the first-shadow cache has held
                                // for two chains, a path's state after its shaded first hit is kept and later chains resume from it, rt_still.h).  Off with either older
                                // knob at 0, and for scenes with a textured mesh.  Bit-exact either way
+    int chain_ends = 1;        // RT_CHAIN_ENDS=0: the last wf_advance launch of a plain chain is the generic kernel (A/B, cross-check; default: wf_advance_close, which only closes
+                               // the last segment's shadow rays and folds, rt_wavefront.hip.h CLOSE, rt_still.h kAdvClose).  Bit-exact either way
     int refit_wide = 1;        // RT_REFIT_WIDE=0: rt_mesh_set_vertices* refits with the one-workgroup refit_kernel, as rt_mesh_transform does (A/B, cross-check; default: the climb across
                                // the chip, rt_meshops.hip.h refit_up_kernel).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
@@ -136,6 +138,7 @@ static Knobs read_knobs() {
     if (geti("RT_FIRST_HIT_CACHE", v)) k.first_hit_cache = v != 0;
     if (geti("RT_FIRST_SHADOW_CACHE", v)) k.first_shadow_cache = v != 0;
     if (geti("RT_FIRST_SHADE_CACHE", v)) k.first_shade_cache = v != 0;
+    if (geti("RT_CHAIN_ENDS", v)) k.chain_ends = v != 0;
     if (geti("RT_REFIT_WIDE", v)) k.refit_wide = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;

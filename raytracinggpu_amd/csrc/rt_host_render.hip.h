@@ -697,7 +697,9 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     const rtk::QRows win_y = rtk::qrows_y(pt.st.n_paths, pt.st.log2S, pt.st.Q);
     const bool lens = c.lens.radius > 0.f;                        // the camera has a lens: the chain opens with wf_advance_lens and knows no still view
     const rtk::StillChain sc = lens ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
-    const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0);
+    // the plain chain -- every launch after the opening one wf_advance<STATS, false> (or the launch that stores the records) -- takes the closing kernel at its last position
+    const bool plain = t.queue && !tex && !lights && !soft && !lens && !(c.batch && c.anim);
+    const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0, plain && kn.chain_ends != 0);
     auto block = [&](const DevBuf &b) { return static_cast<unsigned long long *>(b.p) + pt.pxbase; };   // the part's block of a level
     auto records = [&] { rtk::WfShade sh{}; sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; sh.kill_x = plan.kill_x; return sh; };
     pt.st.nonce = (int)(++ctx->chain_nonce[j] & (unsigned)rtk::PQ_NONCE_MASK);
@@ -725,6 +727,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     else hipLaunchKernelGGL(begin, pg, pb, 0, q, c.scn, pt.fr, ost);
     const auto advance = counting ? rtk::wf_advance<true, false> : rtk::wf_advance<false, false>;
     const auto advance_tex = counting ? rtk::wf_advance_tex<true> : rtk::wf_advance_tex<false>;
+    const auto advance_close = counting ? rtk::wf_advance_close<true> : rtk::wf_advance_close<false>;
     const bool timed = ctx->stats_on && j == 0 && s + w.chunk >= fr.spp;   // on request (rt_stats_enable): time part 0's launches of the last chain
     for (int it = plan.first; it < plan.n; ++it) {
         const rtk::StillStep &sp = plan.step[it];
@@ -752,6 +755,8 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
         if (sp.x0) { ast.X0 = block(ctx->wfX0); ast.x0 = sp.x0; }
         if (sp.adv == rtk::kAdvFill) {                            // (never a textured scene, never a batch: WfCut::still)
             hipLaunchKernelGGL(rtk::wf_advance_fill, pg, pb, 0, q, c.scn, pt.fr, ast, records());
+        } else if (sp.adv == rtk::kAdvClose) {                    // (a plain chain only: still_plan)
+            hipLaunchKernelGGL(advance_close, pg, pb, 0, q, c.scn, pt.fr, ast);
         } else if (tex) {
             rtk::TexScene ts = tex_scene(ctx);
             ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg;   // ALB[d * n_paths + i] inside the part's block, as LS

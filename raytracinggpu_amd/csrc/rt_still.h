@@ -120,13 +120,13 @@ struct StillView {
 // The launches of one chain.  It opens with one wf_advance -- begin, or resume from the records -- and goes on through positions first .. n - 1: at position `it` a
 // traversal launch (if any) and the wf_advance that closes what it traced.
 enum StillWin { kWinNone = 0, kWinY = 1, kWinX = 2 };            // the rows of the queue a traversal launch enumerates (rt_qrows.h)
-enum StillAdv { kAdvBegin = 0, kAdvResume = 1, kAdvPlain = 2, kAdvFill = 3 };
+enum StillAdv { kAdvBegin = 0, kAdvResume = 1, kAdvPlain = 2, kAdvFill = 3, kAdvClose = 4 };
 struct StillStep {
     bool trav;                // the traversal launch is enqueued
     int win;                  // ... over this window
     bool trav_m0;             // ... and writes the part's block of the hit level instead of M
     int m0, x0;               // WfState::m0 / x0 of the wf_advance: it reads the hit level; 1 stores / 2 reads the shadow level
-    int adv;                  // kAdvPlain, or kAdvFill: it stores the part's records
+    int adv;                  // kAdvPlain, or kAdvFill: it stores the part's records; kAdvClose: the kernel of a plain chain's last position (RT_CHAIN_ENDS; rt_wavefront.hip.h wf_advance_close)
 };
 struct StillPlan {
     int open;                 // kAdvBegin or kAdvResume
@@ -136,8 +136,8 @@ struct StillPlan {
     StillStep step[kStillMaxSteps];
 };
 // segs: ray segments of a path (0: the chain has no position at all); rows: traversal launches take windows (the work-stack kernel under RT_TRAVQ_ROWS);
-// has_y: this part's queue has a Y window that is not every row
-inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool rows, bool has_y) {
+// has_y: this part's queue has a Y window that is not every row; ends: the chain is a plain one (enqueue_chain) and takes the closing kernel
+inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool rows, bool has_y, bool ends = false) {
     StillPlan p;
     const bool resume = c.records == kStillUse;
     p.open = resume ? kAdvResume : kAdvBegin;
@@ -158,6 +158,8 @@ inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool 
         s.x0 = (it <= 1 && !resume) ? (int)c.shadow : 0;           // the launch that emits segment 0's shadow rays and the one that closes them
         s.adv = (it == 0 && c.records == kStillFill) ? kAdvFill : kAdvPlain;
     }
+    // The last launch meets no continuation ray: it closes segment segs - 1's shadow rays and folds (never the launch that stores the records: that one is at position 0)
+    if (ends && segs > 0) p.step[segs].adv = kAdvClose;
     return p;
 }
 

@@ -785,7 +785,11 @@ __device__ __forceinline__ f3 wf_light_point(const WfSoftLights &sl, uint32_t hs
 // chain: with the lens on that launch is wf_advance_lens (LENS, always FIRST), which takes the lens by value; every later launch of the chain is whichever kernel the scene
 // picks without a lens.  rtk::Scene and rtk::Frame do not grow.
 struct WfLens { float radius, focus; };
-template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, int LIGHTS = 0, bool LENS = false>
+// THE CHAIN'S CLOSE (wf_advance_close: CLOSE; the plain chain only, rt_still.h still_plan).  The chain's last launch, at position segs, meets no continuation ray: it closes
+// the shadow rays of segment segs - 1 and folds -- the close of a continuation ray, the shading and the emission are compiled out, and so is the dead half-record of a
+// finished path (see the fold).  (Folding a path a launch early, in the last shading launch, where its shadow ray is not handed to the traversal, was built beside it
+// and lost: DESIGN.md section 11.)
+template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, int LIGHTS = 0, bool LENS = false, bool CLOSE = false>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr,
                                                 const WfList &list = WfList{}, const WfShade &sh = WfShade{}, const WfLights *__restrict__ lt = nullptr,
                                                 const WfSoftLights *__restrict__ sl = nullptr, const WfLens *__restrict__ ln = nullptr) {
@@ -893,7 +897,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         if (!RESUME && x_close0 && st.x0 == 1 && s_rel == 0) st.X0[i] = xm;      // fill: every first-sample path, WF_NOHIT where no shadow ray of its went through the mesh
         ADV_MARK("closex_end");
         // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit ----
-        if (RESUME || (F & PF_HASY)) {
+        if (!CLOSE && (RESUME || (F & PF_HASY))) {                    // (CLOSE: no continuation ray reaches the chain's last launch)
             ADV_MARK("closey_begin");
             const float4 r0 = RESUME ? ra : st.QR[2 * (size_t)qy];
             f3 O = mk(r0.x, r0.y, r0.z), u = RESUME ? mk(ra.w, rb.x, rb.y) : mk(r0.w, y1.x, y1.y);   // (RESUME: the continuation ray of a specular hit; P_adjusted and N of a diffuse one)
@@ -1037,7 +1041,13 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             const float n = fr.cam_mode == 1 ? 1.f : (float)fr.spp;
             fr_out[out_index(fr, lrow, px)] = make_float4(t.x / n, t.y / n, t.z / n, t.w);
         }
-        st.QR[2 * (size_t)qy + 1] = kDead;                            // the path is over; its X slot keeps a record of an older launch, which no later one takes for its own
+        // The path is over; its X slot keeps a record of an older launch, which no later one takes for its own.  (CLOSE: the chain is over too, and the store is dropped.
+        // Whatever the Y slot's second half holds then -- a flag word without PQ_TRAV, so no traversal launch takes it for a ray -- the next chain of this part of the queue
+        // rewrites before any of its traversal launches runs, for EVERY item i < n_paths of its opening launch: wf_advance<FIRST> and its animated and lens forms store kDead
+        // for an item that is not valid (outside the frame, past spp, past the batch), fold an item of a chain of no segments, which stores kDead, and store the record's
+        // state for every other; wf_advance_resume stores kDead for an item that is not valid and folds or emits every other, never taking the early return of a path that
+        // is not alive.  A chain of another layout starts behind the queue's zero fill (start_chains: q_sig); the list chains have a queue of their own.)
+        if (!CLOSE) st.QR[2 * (size_t)qy + 1] = kDead;
         ADV_MARK("fold_end");
         return;
     }
@@ -1149,6 +1159,14 @@ __global__ __launch_bounds__(256, 8) void wf_advance_tex_anim(const Scene sc, co
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths) wf_advance_path<false, false, true, true>(sc, fr, st, i, wk, ts, anim);
+}
+// the last launch of the plain chain (CLOSE)
+template <bool STATS>
+__global__ __launch_bounds__(256, 8) void wf_advance_close(const Scene sc, const Frame fr, const WfState st) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    Work wk;
+    if (i < st.n_paths) wf_advance_path<STATS, false, false, false, false, 0, 0, false, true>(sc, fr, st, i, wk, TexScene{});
+    wf_flush_work<STATS>(fr, wk);
 }
 
 }  // namespace rtk

@@ -30,6 +30,7 @@ def functions(path):
         t = re.sub(r"\.LBB\d+_", ".LBB_", t)
         t = re.sub(r"\.Ltmp\d+", ".Ltmp", t)
         t = re.sub(r"__hip_cuid_\w+", "__hip_cuid", t)
+        t = re.sub(r"^(\s*rt_mark_\w+?)_\d+:", r"\1:", t)            # the kernels' code-object markers (ADV_MARK, WQ_MARK): labels numbered through the translation unit too
         if t.strip() and not t.lstrip().startswith((".section", ".text")):
             out[cur].append(t.replace(cur, "<self>"))
     return {k: v for k, v in out.items() if k in closed}             # (a label that never reaches .Lfunc_end is an object, not a function)

@@ -250,6 +250,11 @@ def main():
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = advance_counts(kernel_text(asm, mm.group(1))) if name == "wf_advance_fill" else {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
+    # the closing launch of a plain chain (rt_wavefront.hip.h CLOSE): by region, as wf_advance -- closex and fold are all it keeps
+    mm = re.search(r"^(_ZN3rtk16wf_advance_closeILb0E\w*):", asm, re.M)
+    if not mm:
+        raise SystemExit("static_counts: wf_advance_close<false> not found in the assembly")
+    res["wf_advance_close"] = advance_counts(kernel_text(asm, mm.group(1)))
     # several point lights (rt_wavefront.hip.h WfLights): the two launches that pick a light per diffuse segment, whole (they plant no labels)
     # ... and the two for lights with a radius (WfSoftLights): the pick and a point of the picked light's shell
     for name, pattern in (("wf_advance_lights", r"^(_ZN3rtk17wf_advance_lightsE\w*):"), ("wf_advance_tex_lights", r"^(_ZN3rtk21wf_advance_tex_lightsE\w*):"),
@@ -283,6 +288,7 @@ def main():
     print("static_counts: wf_advance_list regions (valu / weight): " + ", ".join(f"{k} {v['valu']}/{v['valu_weight']}" for k, v in res["wf_advance_list"].items() if v))
     print("static_counts: wf_advance_fill regions (valu / weight): " + ", ".join(f"{k} {v['valu']}/{v['valu_weight']}" for k, v in res["wf_advance_fill"].items() if v) +
           "; wf_advance_resume whole kernel: %d / %d" % tuple(res["wf_advance_resume"]["whole_kernel"][c] for c in ("valu", "valu_weight")))
+    print("static_counts: wf_advance_close regions (valu / weight): " + ", ".join(f"{k} {v['valu']}/{v['valu_weight']}" for k, v in res["wf_advance_close"].items() if v))
     print("static_counts: sample plan totals / scan / scatter, fold, counts (valu / lds / vmem): " + ", ".join(
         "%d / %d / %d" % tuple(res[k]["whole_kernel"][c] for c in ("valu", "lds", "vmem")) for k in ("sample_plan_totals", "sample_plan_scan", "sample_plan_scatter", "sample_fold", "sample_counts")))
     t = res["wf_travq"]

@@ -1,5 +1,7 @@
 """GPU box: what one level of the still view (csrc/rt_still.h) takes off a frame -- --knob RT_FIRST_HIT_CACHE (a still camera),
-RT_FIRST_SHADOW_CACHE or RT_FIRST_SHADE_CACHE (a still view under a still light) -- and whether a change of the host code moved a frame at all.
+RT_FIRST_SHADOW_CACHE or RT_FIRST_SHADE_CACHE (a still view under a still light) -- and whether a change of the host code moved a frame at all.  --knob RT_CHAIN_ENDS:
+the same steps for the kernel of a plain chain's last launch (csrc/rt_wavefront.hip.h CLOSE), which every frame runs, a still view or not.  --also V[,V] adds this
+build with the knob at each further value to the interleaved runs (an experimental build that knows more than on and off).
 
 For the headline frame and then for BASELINE config 2 (--width 512 --height 512 --spp 8), each step a process of its own under its own time limit, the first failure
 ending the run:
@@ -19,10 +21,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-KNOBS = ["RT_FIRST_HIT_CACHE", "RT_FIRST_SHADOW_CACHE", "RT_FIRST_SHADE_CACHE"]
+CACHES = ["RT_FIRST_HIT_CACHE", "RT_FIRST_SHADOW_CACHE", "RT_FIRST_SHADE_CACHE"]
+KNOBS = CACHES + ["RT_CHAIN_ENDS"]
 ap = argparse.ArgumentParser()
 ap.add_argument("--knob", required=True, choices=KNOBS)
 ap.add_argument("--parent-lib", default="")
+ap.add_argument("--also", default="", help="further values of the knob, comma separated: a build each in the interleaved runs")
 ap.add_argument("--runs", type=int, default=5)
 ap.add_argument("--dump-dir", default="")
 ap.add_argument("--only", default="", choices=["", "headline", "spp8"])
@@ -50,7 +54,7 @@ def inproc():
     which = "parent library" if os.environ.get("RT_LIB") else "this build"
 
     def counters(ctx):
-        return ", ".join("%s %s" % (k[3:-6].lower().replace("_", "-"), json.dumps(getattr(ctx, k[3:].lower() + "_counts")())) for k in reversed(KNOBS))
+        return ", ".join("%s %s" % (k[3:-6].lower().replace("_", "-"), json.dumps(getattr(ctx, k[3:].lower() + "_counts")())) for k in reversed(CACHES))
     for k in range(5):
         c.render(p)
         print("%s, frame %d on one context: %s" % (which, k, counters(c)), flush=True)
@@ -111,7 +115,7 @@ def workload(width, height, spp, bounces, dump_dir):
     if args.parent_lib:
         print(step(stage, dict(os.environ, RT_LIB=os.path.abspath(args.parent_lib)), 240), end="", flush=True)
     off = "branch %s=0" % KNOB
-    builds = [("branch", {}), (off, {KNOB: "0"})]
+    builds = [("branch", {}), (off, {KNOB: "0"})] + [("branch %s=%s" % (KNOB, v), {KNOB: v}) for v in args.also.split(",") if v]
     if args.parent_lib:
         builds.insert(1, ("parent", {"RT_LIB": os.path.abspath(args.parent_lib)}))
     ms = {name: [] for name, _ in builds}
@@ -134,6 +138,9 @@ def workload(width, height, spp, bounces, dump_dir):
               "parent: %s" % (med["branch"] - med["parent"], 100 * (med["branch"] / med["parent"] - 1), sp, 3 * sp, max(ms["branch"]) < min(ms["parent"])))
         print("knob off - parent: %+.4f ms (%+.2f %%)" % (med[off] - med["parent"], 100 * (med[off] / med["parent"] - 1)))
     print("the level alone (branch - %s): %+.4f ms (%+.2f %%)" % (off, med["branch"] - med[off], 100 * (med["branch"] / med[off] - 1)))
+    for name, _ in builds[3 if args.parent_lib else 2:]:
+        print("branch - %s: %+.4f ms (%+.2f %%); every run of the branch below every run of it: %s" % (
+            name, med["branch"] - med[name], 100 * (med["branch"] / med[name] - 1), max(ms["branch"]) < min(ms[name])))
     if args.parent_lib and dump_dir:
         import numpy as np
         a, b = (np.load(os.path.join(dump_dir, n, "frame.npy")) for n in ("branch", "parent"))
