@@ -332,7 +332,7 @@ int rt_scene_set_light_radius_at(rt_ctx *ctx, int k, float radius);
  *                                              of O may become +0 (-0 + (+0) = +0).
  *       u' = normalize(F - O')
  *     The path starts with the ray (O', u'): the sphere decision at emission, the traversal, shading and ray counts are the pinhole code on that ray; a camera ray still
- *     counts as one ray.  One kernel knows the rule: wf_advance_lens, the opening launch of every chain while the lens is on; the later launches are whichever kernels the
+ *     counts as one ray.  One kernel knows the rule: wf_advance<kFormFirst | kFormLens>, the opening launch of every chain while the lens is on; the later launches are whichever kernels the
  *     scene picks without a lens (several lights, soft lights, textures, smooth normals).
  *     The lens is host state; a frame in flight keeps what its launches captured.  rt_scene_upload* leaves a pinhole (R = 0, f = 1): the camera comes with the upload.
  *     RT_ERR_INVALID, the lens untouched: a NULL pointer, a radius whose sign bit is set or that is not finite, and with R > 0 a focus distance that is not finite or not

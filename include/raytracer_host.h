@@ -44,6 +44,10 @@ int64_t rth_qrows_enumerate(int n_paths, int log2S, int Q, int tblocks, int whic
  * cap of 12 numbers each, returns how many there are): per chain its opening launch (position -1) and then its positions as (event, position, traversal launch, window
  * 0 none 1 Y 2 X, it writes the hit block, m0, x0, wf_advance 0 begin 1 resume 2 plain 3 fill 4 close, kill_x, and the chain's modes of the three levels 0 off 1 fill 2 use). */
 int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32_t *rows, int64_t cap);
+/* The form word (csrc/rt_still.h kForm*: bit 0 stats, 1 first, 2 tex, 3 anim, 4 list, 5 fill, 6 resume, 7 lights, 8 soft, 9 lens, 10 close) of the wf_advance launch that a
+ * chain enqueues for step adv (0 begin, 1 resume, 2 plain, 3 fill, 4 close), from the chain's facts; lights: 0 one point light, 1 several, 2 some with a radius.
+ * -1: no entry asks for that launch, and no kernel is built for it. */
+int64_t rth_advance_form(int counting, int tex, int anim, int list, int lens, int lights, int adv);
 
 /* Test entries of the cut of a call's rows (csrc/rt_rowcut.h, shared with the render path).  rth_row_cut: n cases of seven numbers -- an rt_rows (row0, n_rows, tile_rows,
  * tile_step), the sub-frames wanted (RT_PARTS), one (a counting run: one sub-frame), whole (a batch cut by frames: every sub-frame holds all rows) -- each give 52 numbers:

@@ -115,6 +115,13 @@ int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32
     return n;
 }
 
+// the form of the wf_advance launch that a chain of these facts enqueues for step `adv` (rt_still.h adv_form, as enqueue_chain and launch_render_counts ask for it);
+// lights: 0 one point light, 1 several, 2 some with a radius; adv: StillAdv.  -1: not built
+int64_t rth_advance_form(int counting, int tex, int anim, int list, int lens, int lights, int adv) {
+    const unsigned form = rtk::adv_form(rtk::AdvFacts{counting != 0, tex != 0, anim != 0, list != 0, lens != 0, lights}, adv);
+    return form == rtk::kFormNotBuilt ? -1 : (int64_t)form;
+}
+
 // the cut of a call's rows into sub-frames (rt_rowcut.h), as cut_wavefront and launch_path ask for it
 void rth_row_cut(const int32_t *cases, int n, int32_t *out) {
     using namespace rtk;

@@ -8,7 +8,7 @@
 //                                   slot << 6 | sample of its samples, slot-major then sample, written by the whole wave (coalesced)
 //            Nothing waits for another workgroup and no atomic decides an order: the list is a function of the counts.  The host reads the grand total back once
 //            (it sizes the list and the chains) between the scan and the scatter.
-//   chain    wf_advance_list<FIRST> / wf_advance_list_tex: wf_advance_path's LIST form -- (px, lrow, samp, valid) come from the item record; every item writes its
+//   chain    wf_advance<kFormList [| kFormFirst | kFormTex]> (rt_wavefront.hip.h): the LIST form -- (px, lrow, samp, valid) come from the item record; every item writes its
 //            colour to samp_out[i].  The launches between are the dense chain's own (wf_travq and all).
 //   fold     sample_fold: one lane per pixel slot adds its items' colours in sample order (cpu:711), from `base` if the caller brought the first sample, divides as
 //            path_reduce does with the pixel's own count, and stores the pixel.  A list cut into several chains is folded chain by chain (T carries the sum).
@@ -110,19 +110,6 @@ __global__ __launch_bounds__(kPlanBlock) void sample_plan_scatter(const PlanArgs
         const unsigned int excl = lo > 0 ? wincl[wave][lo - 1] : 0u;
         items[(size_t)wbase + j] = (unsigned int)(slot0 + lo) << kItemShift | ((unsigned int)a.first + (j - excl));
     }
-}
-
-// ---- the chain: wf_advance_path's LIST form ----
-template <bool FIRST>
-__global__ __launch_bounds__(256, 8) void wf_advance_list(const Scene sc, const Frame fr, const WfState st, const WfList list) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, FIRST, false, false, true>(sc, fr, st, i, wk, TexScene{}, nullptr, list);
-}
-__global__ __launch_bounds__(256, 8) void wf_advance_list_tex(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const WfList list) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, true, false, true>(sc, fr, st, i, wk, ts, nullptr, list);
 }
 
 // ---- the fold ----

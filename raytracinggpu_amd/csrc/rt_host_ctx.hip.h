@@ -76,10 +76,10 @@ struct Knobs {
                                // are traced once and kept, rt_still.h).  Bit-exact either way
     int first_shadow_cache = 1; // RT_FIRST_SHADOW_CACHE=0: every chain traces the shadow rays of its first segment (A/B, cross-check, and the figure of a moving light; default: under a still
                                // camera AND a still light, scene and shading state they are traced once and kept, rt_still.h).  Off with RT_FIRST_HIT_CACHE=0.  Bit-exact either way
-    int first_shade_cache = 1; // RT_FIRST_SHADE_CACHE=0: every chain of a still view opens with wf_advance<FIRST> and closes segment 0 (A/B, cross-check; default: once the first-shadow cache has held
+    int first_shade_cache = 1; // RT_FIRST_SHADE_CACHE=0: every chain of a still view opens with wf_advance<kFormFirst> and closes segment 0 (A/B, cross-check; default: once the first-shadow cache has held
                                // for two chains, a path's state after its shaded first hit is kept and later chains resume from it, rt_still.h).  Off with either older
                                // knob at 0, and for scenes with a textured mesh.  Bit-exact either way
-    int chain_ends = 1;        // RT_CHAIN_ENDS=0: the last wf_advance launch of a plain chain is the generic kernel (A/B, cross-check; default: wf_advance_close, which only closes
+    int chain_ends = 1;        // RT_CHAIN_ENDS=0: the last wf_advance launch of a plain chain is the generic kernel (A/B, cross-check; default: wf_advance<kFormClose>, which only closes
                                // the last segment's shadow rays and folds, rt_wavefront.hip.h CLOSE, rt_still.h kAdvClose).  Bit-exact either way
     int refit_wide = 1;        // RT_REFIT_WIDE=0: rt_mesh_set_vertices* refits with the one-workgroup refit_kernel, as rt_mesh_transform does (A/B, cross-check; default: the climb across
                                // the chip, rt_meshops.hip.h refit_up_kernel).  Bit-exact either way
@@ -179,7 +179,7 @@ struct rt_ctx {
     // ... and their radii (rt_scene_set_light_radii): entry k belongs to light k of the list, a list of one included; all 0 unless that entry set them
     float light_radii[rtk::kMaxLights] = {};
     // The camera's thin lens (rt_camera_set_lens): aperture radius and focus distance in scene units.  Host state like the lights: make_frame captures it by value, and a
-    // radius above 0 makes every chain open with wf_advance_lens.  rt_scene_upload* leaves a pinhole: the camera comes with the upload.
+    // radius above 0 makes every chain open with wf_advance<kFormFirst | kFormLens>.  rt_scene_upload* leaves a pinhole: the camera comes with the upload.
     float lens_radius = 0.f, lens_focus = 1.f;
     DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
@@ -252,7 +252,7 @@ struct rt_ctx {
     // parts of them hold what, under which keys (rt_host_render.hip.h still_begin)
     DevBuf wfM0{bufs}, wfX0{bufs}, wfS0{bufs};
     rtk::StillView still;
-    DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance_tex; allocated by the first textured frame)
+    DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance<kFormTex>; allocated by the first textured frame)
     DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum
     DevBuf dbgbuf{bufs};                                            // -DRT_DEBUG builds: per-wave traversal records
@@ -396,7 +396,7 @@ int ensure(rt_ctx *ctx, DevBuf &b, size_t bytes) {
     return RT_OK;
 }
 
-// what wf_advance_tex and kat_surface_kernel read of the textures (ALB: set per launch)
+// what wf_advance<kFormTex> and kat_surface_kernel read of the textures (ALB: set per launch)
 rtk::TexScene tex_scene(const rt_ctx *ctx) {
     rtk::TexScene ts{};
     ts.uv = static_cast<const float2 *>(ctx->tex_uv.p);

@@ -27,7 +27,7 @@ bool lights_soft(const rt_ctx *ctx) {
 int lights_refuse(rt_ctx *ctx, const char *what) {
     if (ctx && ctx->n_lights > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene holds %d lights; only wf_advance takes more than one (rt_scene_set_lights)", what, ctx->n_lights);
     if (ctx && lights_soft(ctx)) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene's light has a radius; only wf_advance samples it (rt_scene_set_light_radii)", what);
-    // ... and while the camera has a lens, only a chain that opens with wf_advance_lens may render it
+    // ... and while the camera has a lens, only a chain that opens with wf_advance<kFormFirst | kFormLens> may render it
     if (ctx && ctx->lens_radius > 0.f) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the camera has a lens; only wf_advance_lens samples it (rt_camera_set_lens)", what);
     return RT_OK;
 }
@@ -181,7 +181,7 @@ int resolve_variant(rt_ctx *ctx, int variant, const rt_camera_pose *pose, bool b
     if (ctx->tex_mask != 0 && !(v.wf_family && v.variant != RT_VARIANT_PATH))
         return fail(ctx, RT_ERR_UNSUPPORTED, "a textured mesh needs a variant that runs wf_advance (auto, wavefront, wavefront_lds, wavefront_queue, lds_*)");
     if (pose && !v.wf_family) return fail(ctx, RT_ERR_UNSUPPORTED, "a camera pose needs a wavefront or path variant");
-    if (!(v.wf_family && v.variant != RT_VARIANT_PATH)) return lights_refuse(ctx, "this variant");   // several lights: wf_advance_lights shades (auto, wavefront, wavefront_lds, wavefront_queue, lds_*)
+    if (!(v.wf_family && v.variant != RT_VARIANT_PATH)) return lights_refuse(ctx, "this variant");   // several lights: wf_advance<kFormLights> shades (auto, wavefront, wavefront_lds, wavefront_queue, lds_*)
     return RT_OK;
 }
 
@@ -192,9 +192,9 @@ struct Chunk {
     const rt_params *p; const rt_rows *rows; hipStream_t stream; unsigned long long *work_dev; const rtk::Batch *batch; bool rec_begin; int segs, nseg;
     rtk::Frame fr; rtk::Scene scn;
     const rtk::AnimSrc *anim = nullptr;
-    rtk::WfSoftLights sl{};                                           // sl.lt.n > 1: the scene holds several lights -- sl.lt is the argument of wf_advance_lights (make_frame)
-    bool soft = false;                                                // some light has a radius: sl, radii included, is the argument of wf_advance_soft
-    rtk::WfLens lens{};                                               // lens.radius > 0: the camera has a lens -- the argument of wf_advance_lens, the opening launch of every chain
+    rtk::WfSoftLights sl{};                                           // sl.lt.n > 1: the scene holds several lights -- sl.lt is the argument of wf_advance<kFormLights> (make_frame)
+    bool soft = false;                                                // some light has a radius: sl, radii included, is the argument of wf_advance<kFormSoft>
+    rtk::WfLens lens{};                                               // lens.radius > 0: the camera has a lens -- the argument of wf_advance<kFormFirst | kFormLens>, the opening launch of every chain
 };
 void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Chunk &c) {
     const rt_params *p = c.p;
@@ -577,7 +577,7 @@ int size_wavefront(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool &qr_grown) 
         (rc = ensure(ctx, ctx->wfT, (samples ? w.px : 1) * 16)) != RT_OK || (rc = ensure(ctx, ctx->wfSamp, (samples ? np : 1) * 16)) != RT_OK ||
         (rc = ensure(ctx, ctx->wfSID, np * nseg)) != RT_OK || (rc = ensure(ctx, ctx->wfDCH, np)) != RT_OK || (rc = ensure(ctx, ctx->wfLS, np * 4 * nseg)) != RT_OK)
         return rc;
-    if (ctx->tex_mask != 0 && (rc = ensure(ctx, ctx->wfALB, np * 16 * nseg)) != RT_OK) return rc;   // a textured mesh: the per-segment albedo store of wf_advance_tex
+    if (ctx->tex_mask != 0 && (rc = ensure(ctx, ctx->wfALB, np * 16 * nseg)) != RT_OK) return rc;   // a textured mesh: the per-segment albedo store of wf_advance<kFormTex>
     // a still view's levels: the first two allocated by the first eligible frame, the records by the first chunk one of whose chains may store them (a new allocation
     // empties its level: StillView::begin)
     if (w.still >= 1 && (rc = ensure(ctx, ctx->wfM0, w.px * 8)) != RT_OK) return rc;
@@ -681,27 +681,68 @@ int end_chains(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool own0) {
     return RT_OK;
 }
 
+// What a chain's wf_advance launches may take beyond (Scene, Frame, WfState): each form takes the ones its bits name (rt_still.h kForm*), in this order (sl.lt: the table of
+// the forms without radii)
+struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; };
+struct AdvLaunch {
+    dim3 grid, block; hipStream_t q; const rtk::Scene &scn; const rtk::Frame &fr; const rtk::WfState &st;
+    template <unsigned FORM, class... Extra> void go(const Extra &... extra) const { hipLaunchKernelGGL((rtk::wf_advance<FORM, Extra...>), grid, block, 0, q, scn, fr, st, extra...); }
+};
+// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 21 instantiations, one case each (DESIGN.md section 5.2 says who launches
+// each and which test runs it).  The entries refuse what has no form before a chain is planned (lights_refuse, resolve_variant), so the default is not reached.
+int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_t q, const rtk::Scene &scn, const rtk::Frame &fr, const rtk::WfState &st, const AdvArgs &a) {
+    using namespace rtk;
+    const AdvLaunch l{grid, block, q, scn, fr, st};
+    switch (form) {
+    case kFormFill: l.go<kFormFill>(a.sh); break;
+    case kFormResume: l.go<kFormResume>(a.sh); break;
+    case kFormLights: l.go<kFormLights>(a.sl.lt); break;
+    case kFormTex | kFormLights: l.go<kFormTex | kFormLights>(a.ts, a.sl.lt); break;
+    case kFormSoft: l.go<kFormSoft>(a.sl); break;
+    case kFormTex | kFormSoft: l.go<kFormTex | kFormSoft>(a.ts, a.sl); break;
+    case kFormFirst | kFormLens: l.go<kFormFirst | kFormLens>(a.ln); break;
+    case kFormTex | kFormAnim: l.go<kFormTex | kFormAnim>(a.ts, a.anim); break;
+    case kFormTex | kFormList: l.go<kFormTex | kFormList>(a.ts, a.list); break;
+    case kFormFirst | kFormStats: l.go<kFormFirst | kFormStats>(); break;
+    case kFormFirst: l.go<kFormFirst>(); break;
+    case kFormFirst | kFormAnim: l.go<kFormFirst | kFormAnim>(a.anim); break;
+    case kFormStats: l.go<kFormStats>(); break;
+    case 0u: l.go<0u>(); break;
+    case kFormTex | kFormStats: l.go<kFormTex | kFormStats>(a.ts); break;
+    case kFormTex: l.go<kFormTex>(a.ts); break;
+    case kFormClose | kFormStats: l.go<kFormClose | kFormStats>(); break;
+    case kFormClose: l.go<kFormClose>(); break;
+    case kFormAnim: l.go<kFormAnim>(a.anim); break;
+    case kFormFirst | kFormList: l.go<kFormFirst | kFormList>(a.list); break;
+    case kFormList: l.go<kFormList>(a.list); break;
+    default: return fail(ctx, RT_ERR_UNSUPPORTED, "no wf_advance kernel of form 0x%x is built", form);
+    }
+    return RT_OK;
+}
+
 // One launch chain: samples s .. s + chunk of sub-frame j (all frames of its share of a batch) on stream q
 int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int j, int s, hipStream_t q) {
     const Knobs &kn = ctx->knobs;
     const rtk::Frame &fr = c.fr;
     WfPart &pt = w.pv[j];
     if (pt.st.n_paths == 0) return RT_OK;
-    const bool counting = c.work_dev != nullptr;
-    const bool tex = ctx->tex_mask != 0;                          // a textured mesh: wf_advance_tex, and the per-segment albedo store
-    const bool lights = c.sl.lt.n > 1 && !c.soft;                 // several lights: wf_advance_lights / wf_advance_tex_lights after the opening launch (never counting, never animated)
-    const bool soft = c.soft;                                     // ... some with a radius (or one with a radius): wf_advance_soft / wf_advance_tex_soft in their place
+    // the chain's facts: with the step they decide the form of each wf_advance launch (rt_still.h adv_form)
+    const bool anim = c.batch && c.anim;                          // an animated batch: the frames' lights and spheres too
+    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0};
     const dim3 pg(pt.pblocks), pb(kn.adv_block);
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
     const rtk::QRows win_y = rtk::qrows_y(pt.st.n_paths, pt.st.log2S, pt.st.Q);
-    const bool lens = c.lens.radius > 0.f;                        // the camera has a lens: the chain opens with wf_advance_lens and knows no still view
-    const rtk::StillChain sc = lens ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
-    // the plain chain -- every launch after the opening one wf_advance<STATS, false> (or the launch that stores the records) -- takes the closing kernel at its last position
-    const bool plain = t.queue && !tex && !lights && !soft && !lens && !(c.batch && c.anim);
+    // (the camera has a lens: the chain opens with the lens form and knows no still view)
+    const rtk::StillChain sc = facts.lens ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
+    // the plain chain takes the closing kernel at its last position
+    const bool plain = t.queue && rtk::adv_plain_chain(facts);
     const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0, plain && kn.chain_ends != 0);
     auto block = [&](const DevBuf &b) { return static_cast<unsigned long long *>(b.p) + pt.pxbase; };   // the part's block of a level
-    auto records = [&] { rtk::WfShade sh{}; sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; sh.kill_x = plan.kill_x; return sh; };
+    AdvArgs aa;
+    aa.anim = pt.anim; aa.sl = c.sl; aa.ln = c.lens;
+    if (sc.records != rtk::kStillOff) { aa.sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; aa.sh.kill_x = plan.kill_x; }
+    if (facts.tex) { aa.ts = tex_scene(ctx); aa.ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg; }   // ALB[d * n_paths + i] inside the part's block, as LS
     pt.st.nonce = (int)(++ctx->chain_nonce[j] & (unsigned)rtk::PQ_NONCE_MASK);
     if (c.batch) {                                                // this sub-frame's frames, at the head of its chain
         rtk::Batch bj{};
@@ -709,25 +750,17 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
         for (int k = 0; k < pt.batch_n; ++k) bj.f[k] = c.batch->f[pt.batch0 + k];
         hipLaunchKernelGGL(rtk::batch_store_kernel, dim3(1), dim3(64), 0, q, bj, const_cast<rtk::BatchFrame *>(pt.st.batch));
     }
-    const bool anim = c.batch && c.anim;                          // their lights and spheres too: kAnimStore frames' records fit one launch's arguments
-    for (int k0 = 0; anim && k0 < pt.batch_n; k0 += rtk::kAnimStore) {
+    for (int k0 = 0; anim && k0 < pt.batch_n; k0 += rtk::kAnimStore) {   // (kAnimStore frames' records fit one launch's arguments)
         rtk::AnimStore as{};
         as.n = std::min(rtk::kAnimStore, pt.batch_n - k0); as.n_spheres = c.scn.n_spheres;
         for (int k = 0; k < c.scn.n_spheres; ++k) as.obj[k] = c.scn.sph[k].obj;
         for (int k = 0; k < as.n; ++k) as.f[k] = c.anim[pt.batch0 + k0 + k];
         hipLaunchKernelGGL(rtk::anim_store_kernel, dim3(1), dim3(rtk::kAnimStore * rtk::kMaxSpheres), 0, q, as, pt.anim + k0);
     }
-    const auto begin = counting ? rtk::wf_advance<true, true> : rtk::wf_advance<false, true>;
-    // the opening launch.  A resumed chain: one launch in place of wf_advance<FIRST> and the launch that closes segment 0
+    // the opening launch.  A resumed chain: one launch in place of the opening form and the launch that closes segment 0
     rtk::WfState ost = pt.st;
     ost.m0 = plan.open_m0;
-    if (plan.open == rtk::kAdvResume) hipLaunchKernelGGL(rtk::wf_advance_resume, pg, pb, 0, q, c.scn, pt.fr, ost, records());
-    else if (anim) hipLaunchKernelGGL(rtk::wf_advance_anim<true>, pg, pb, 0, q, c.scn, pt.fr, ost, static_cast<const rtk::AnimFrame *>(pt.anim));
-    else if (lens) hipLaunchKernelGGL(rtk::wf_advance_lens, pg, pb, 0, q, c.scn, pt.fr, ost, c.lens);   // (never counting, never animated: lights_refuse)
-    else hipLaunchKernelGGL(begin, pg, pb, 0, q, c.scn, pt.fr, ost);
-    const auto advance = counting ? rtk::wf_advance<true, false> : rtk::wf_advance<false, false>;
-    const auto advance_tex = counting ? rtk::wf_advance_tex<true> : rtk::wf_advance_tex<false>;
-    const auto advance_close = counting ? rtk::wf_advance_close<true> : rtk::wf_advance_close<false>;
+    if (int rc = launch_advance(ctx, rtk::adv_form(facts, plan.open), pg, pb, q, c.scn, pt.fr, ost, aa); rc != RT_OK) return rc;
     const bool timed = ctx->stats_on && j == 0 && s + w.chunk >= fr.spp;   // on request (rt_stats_enable): time part 0's launches of the last chain
     for (int it = plan.first; it < plan.n; ++it) {
         const rtk::StillStep &sp = plan.step[it];
@@ -753,26 +786,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
         rtk::WfState ast = pt.st;
         if (sp.m0) { ast.M = block(ctx->wfM0); ast.m0 = 1; }      // (no shadow ray is in flight: M is read for Y alone)
         if (sp.x0) { ast.X0 = block(ctx->wfX0); ast.x0 = sp.x0; }
-        if (sp.adv == rtk::kAdvFill) {                            // (never a textured scene, never a batch: WfCut::still)
-            hipLaunchKernelGGL(rtk::wf_advance_fill, pg, pb, 0, q, c.scn, pt.fr, ast, records());
-        } else if (sp.adv == rtk::kAdvClose) {                    // (a plain chain only: still_plan)
-            hipLaunchKernelGGL(advance_close, pg, pb, 0, q, c.scn, pt.fr, ast);
-        } else if (tex) {
-            rtk::TexScene ts = tex_scene(ctx);
-            ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg;   // ALB[d * n_paths + i] inside the part's block, as LS
-            if (anim) hipLaunchKernelGGL(rtk::wf_advance_tex_anim, pg, pb, 0, q, c.scn, pt.fr, ast, ts, static_cast<const rtk::AnimFrame *>(pt.anim));
-            else if (soft) hipLaunchKernelGGL(rtk::wf_advance_tex_soft, pg, pb, 0, q, c.scn, pt.fr, ast, ts, c.sl);
-            else if (lights) hipLaunchKernelGGL(rtk::wf_advance_tex_lights, pg, pb, 0, q, c.scn, pt.fr, ast, ts, c.sl.lt);
-            else hipLaunchKernelGGL(advance_tex, pg, pb, 0, q, c.scn, pt.fr, ast, ts);
-        } else if (anim) {
-            hipLaunchKernelGGL(rtk::wf_advance_anim<false>, pg, pb, 0, q, c.scn, pt.fr, ast, static_cast<const rtk::AnimFrame *>(pt.anim));
-        } else if (soft) {
-            hipLaunchKernelGGL(rtk::wf_advance_soft, pg, pb, 0, q, c.scn, pt.fr, ast, c.sl);
-        } else if (lights) {
-            hipLaunchKernelGGL(rtk::wf_advance_lights, pg, pb, 0, q, c.scn, pt.fr, ast, c.sl.lt);
-        } else {
-            hipLaunchKernelGGL(advance, pg, pb, 0, q, c.scn, pt.fr, ast);
-        }
+        if (int rc = launch_advance(ctx, rtk::adv_form(facts, sp.adv), pg, pb, q, c.scn, pt.fr, ast, aa); rc != RT_OK) return rc;
         if (timed) { RT_HIP(ctx, hipEventRecord(ctx->ev_adv[2 * it + 1], q)); ctx->n_adv_events = it + 1; ctx->adv_paths = pt.st.n_paths; }
     }
     if (fr.spp > 1)                                               // the chain's samples, added in sample order (cpu:711), into the running sum / the frame
@@ -948,7 +962,7 @@ int plan_samples(rt_ctx *ctx, const uint8_t *counts_dev, int width, int height, 
 }
 
 // rt_render_counts_device: the plan, then the list cut into consecutive chains at multiples of 64 items (a chain's state stays under RT_PATH_SAMP_MB and 2^29 paths, as a
-// dense chain's), each chain one sub-frame on the caller's stream -- wf_advance_list<FIRST>, (wf_travq, wf_advance_list) x (segments + 1), sample_fold.  The chains never
+// dense chain's), each chain one sub-frame on the caller's stream -- wf_advance<kFormFirst | kFormList>, (wf_travq, wf_advance<kFormList>) x (segments + 1), sample_fold.  The chains never
 // look at the first-hit cache (m0 = 0; rt_ctx::fh is not touched) and enumerate every row of their queue.  No items: no chain, and the fold still writes the frame.
 int launch_render_counts(rt_ctx *ctx, const rt_params *p_in, const rt_camera_pose *pose, const uint8_t *counts_dev, const void *base_dev, void *out_dev, hipStream_t stream) {
     if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
@@ -980,7 +994,8 @@ int launch_render_counts(rt_ctx *ctx, const rt_params *p_in, const rt_camera_pos
     const int64_t n_chains = ((int64_t)total + cmax - 1) / cmax;
     const int64_t per = n_chains > 0 ? (((int64_t)total + n_chains - 1) / n_chains + 63) / 64 * 64 : 0;
     const size_t np = (size_t)per, nseg = (size_t)c.nseg;
-    const bool tex = ctx->tex_mask != 0;
+    const rtk::AdvFacts facts{false, ctx->tex_mask != 0, false, true, false, 0};   // list chains (lights_refuse above: one point light, no lens)
+    const bool tex = facts.tex;
     auto geometry = [&](int64_t n_items, rtk::WfState &st) {          // n_paths and the traversal launch's shares of one chain -> its grid
         st = rtk::WfState{};
         st.tiles_x = pa.tiles_x; st.tiles_x_m = rtk::wf_div_magic(pa.tiles_x);
@@ -1030,19 +1045,15 @@ int launch_render_counts(rt_ctx *ctx, const rt_params *p_in, const rt_camera_pos
         st.anyhit = kn.anyhit ? 1 : 0;
         st.deadch = (st.anyhit && kn.dead_channels) ? 1 : 0;
         st.nonce = (int)(++ctx->ad_nonce & (unsigned)rtk::PQ_NONCE_MASK);
-        const rtk::WfList list{static_cast<const unsigned int *>(ctx->adItems.p) + i0, (int)n};
+        AdvArgs aa;
+        aa.list = rtk::WfList{static_cast<const unsigned int *>(ctx->adItems.p) + i0, (int)n};
+        if (tex) { aa.ts = tex_scene(ctx); aa.ts.ALB = static_cast<float4 *>(ctx->wfALB.p); }
         const dim3 pg((unsigned)((st.n_paths + kn.adv_block - 1) / kn.adv_block)), pb(kn.adv_block);
-        hipLaunchKernelGGL(rtk::wf_advance_list<true>, pg, pb, 0, stream, c.scn, c.fr, st, list);
+        if ((rc = launch_advance(ctx, rtk::adv_form(facts, rtk::kAdvBegin), pg, pb, stream, c.scn, c.fr, st, aa)) != RT_OK) return rc;
         for (int it = 0; it < (segs > 0 ? segs + 1 : 0); ++it) {
             st.epoch = it;
             if (t.have_mesh) launch_trav(t, tblocks, stream, c.scn, c.fr, st);
-            if (tex) {
-                rtk::TexScene ts = tex_scene(ctx);
-                ts.ALB = static_cast<float4 *>(ctx->wfALB.p);
-                hipLaunchKernelGGL(rtk::wf_advance_list_tex, pg, pb, 0, stream, c.scn, c.fr, st, ts, list);
-            } else {
-                hipLaunchKernelGGL(rtk::wf_advance_list<false>, pg, pb, 0, stream, c.scn, c.fr, st, list);
-            }
+            if ((rc = launch_advance(ctx, rtk::adv_form(facts, rtk::kAdvPlain), pg, pb, stream, c.scn, c.fr, st, aa)) != RT_OK) return rc;
         }
         fa.i0 = (unsigned int)i0; fa.i1 = (unsigned int)(i0 + n); fa.last = k + 1 == n_chains ? 1 : 0;
         hipLaunchKernelGGL(rtk::sample_fold, fg, fb, 0, stream, c.fr, fa);

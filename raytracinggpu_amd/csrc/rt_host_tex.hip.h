@@ -1,6 +1,6 @@
 // rt_host_tex.hip.h -- host side (inside rt_capi.hip's extern "C" block): textured meshes.  rt_mesh_set_texture[_of] store a mesh's per-corner UVs in visit order
 // (as rt_mesh_set_normals[_of] store normals), its texels as 8-bit bytes and its decode table on the device, and set its bit in tex_mask: frames then run
-// wf_advance_tex (rt_wavefront.hip.h).  rt_mesh_rebuild* carry the UVs with their triangles (rt_host_mesh.hip.h, which also has the gather both share); rt_mesh_transform* leave them alone.
+// wf_advance<kFormTex> (rt_wavefront.hip.h).  rt_mesh_rebuild* carry the UVs with their triangles (rt_host_mesh.hip.h, which also has the gather both share); rt_mesh_transform* leave them alone.
 #pragma once
 
 static_assert(rtk::kMaxObjects == RT_MAX_OBJECTS, "the texture table is indexed by object id");

@@ -126,7 +126,7 @@ struct StillStep {
     int win;                  // ... over this window
     bool trav_m0;             // ... and writes the part's block of the hit level instead of M
     int m0, x0;               // WfState::m0 / x0 of the wf_advance: it reads the hit level; 1 stores / 2 reads the shadow level
-    int adv;                  // kAdvPlain, or kAdvFill: it stores the part's records; kAdvClose: the kernel of a plain chain's last position (RT_CHAIN_ENDS; rt_wavefront.hip.h wf_advance_close)
+    int adv;                  // kAdvPlain, or kAdvFill: it stores the part's records; kAdvClose: the kernel of a plain chain's last position (RT_CHAIN_ENDS; rt_wavefront.hip.h wf_advance<kFormClose>)
 };
 struct StillPlan {
     int open;                 // kAdvBegin or kAdvResume
@@ -161,6 +161,41 @@ inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool 
     // The last launch meets no continuation ray: it closes segment segs - 1's shadow rays and folds (never the launch that stores the records: that one is at position 0)
     if (ends && segs > 0) p.step[segs].adv = kAdvClose;
     return p;
+}
+
+// ---- the FORM of a wf_advance launch: which instantiation of rt_wavefront.hip.h's one kernel template it runs ----
+// One word of flag bits, the kernel's first template argument.  What each bit compiles in is told at wf_advance_path; which words are built at all is the switch of
+// launch_advance (rt_host_render.hip.h) and the table of DESIGN.md section 5.2.
+// stats: counts work (rt_count_work), Work is filled and flushed; first: the opening launch, camera rays instead of closing queries; close: the last launch of a plain chain;
+// and the bits that bring the kernel an extra argument -- tex: textured meshes (TexScene); anim: a frame of an animated batch (const AnimFrame *__restrict__); list: the items
+// are (pixel slot, sample) records (WfList); fill / resume: stores the first-shade records / opens a chain from them (WfShade); lights: several point lights (WfLights); soft:
+// lights with a radius (WfSoftLights; in place of lights, never both); lens: the thin lens, with first (WfLens)
+constexpr unsigned kFormStats = 1u << 0, kFormFirst = 1u << 1, kFormTex = 1u << 2, kFormAnim = 1u << 3, kFormList = 1u << 4, kFormFill = 1u << 5, kFormResume = 1u << 6,
+                   kFormLights = 1u << 7, kFormSoft = 1u << 8, kFormLens = 1u << 9, kFormClose = 1u << 10;
+constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks for this launch, and no kernel exists for it
+
+// What decides the form besides the step: the chain's facts.  counting: rt_count_work; anim: a batch with per-frame scenes; list: rt_render_counts*; lights: 0 the Scene's
+// one point light, 1 several, 2 some with a radius
+struct AdvFacts { bool counting, tex, anim, list, lens; int lights; };
+// The plain chain -- every launch after the opening one the form 0 or kFormStats (or the launch that stores the records): still_plan's `ends`, for a work-stack chain
+inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0; }
+// The form of the launch a chain of these facts enqueues for `adv` (StillAdv: StillPlan::open for the opening launch, StillStep::adv for the later ones)
+inline unsigned adv_form(const AdvFacts &f, int adv) {
+    // counting, a list and an animated batch exclude one another, and each refuses several lights, a radius and the lens before a chain is planned (lights_refuse)
+    const int special = (f.counting ? 1 : 0) + (f.anim ? 1 : 0) + (f.list ? 1 : 0);
+    if (f.lights < 0 || f.lights > 2 || special > 1 || (special == 1 && (f.lights != 0 || f.lens))) return kFormNotBuilt;
+    const unsigned stats = f.counting ? kFormStats : 0u;
+    switch (adv) {
+    case kAdvBegin: return kFormFirst | (f.anim ? kFormAnim : f.list ? kFormList : f.lens ? kFormLens : stats);   // a camera ray knows no texture and no light
+    case kAdvResume:
+    case kAdvFill:                                    // the records level: a still view (never counting, a batch, a list or a lens) of one point light and no texture
+        if (special != 0 || f.lens || f.lights != 0 || f.tex) return kFormNotBuilt;
+        return adv == kAdvFill ? kFormFill : kFormResume;
+    case kAdvClose: return adv_plain_chain(f) ? kFormClose | stats : kFormNotBuilt;
+    case kAdvPlain:                                   // (a lens chain's later launches are the scene's own)
+        return (f.tex ? kFormTex : 0u) | (f.anim ? kFormAnim : f.list ? kFormList : f.lights == 2 ? kFormSoft : f.lights == 1 ? kFormLights : stats);
+    }
+    return kFormNotBuilt;
 }
 
 }  // namespace rtk

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void trace_close_kernel(const Scene sc, const 
     o[0] = 1.f; o[1] = __uint_as_float((unsigned int)(m >> 32)); o[2] = N.x; o[3] = N.y; o[4] = N.z;
 }
 
-// rt_kat_surface: the mesh hit of each ray (the production traversal's result) and what wf_advance_tex makes of it -- tex_albedo, the one device function both call.
+// rt_kat_surface: the mesh hit of each ray (the production traversal's result) and what wf_advance<kFormTex> makes of it -- tex_albedo, the one device function both call.
 // out[r] = (object slot or -1, triangle in its mesh's uploaded order, t, u, v, albedo rgb); an untextured mesh reports uv (0, 0) and its constant albedo.
 __global__ __launch_bounds__(256) void kat_surface_kernel(const Scene sc, const TexScene ts, const unsigned long long *__restrict__ M, const float *__restrict__ rays,
                                                           const int *__restrict__ visit2local, int n, float *__restrict__ out) {

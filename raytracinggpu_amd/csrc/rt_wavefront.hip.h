@@ -3,7 +3,7 @@
 // The per-pixel render of cpu_launcher.cpp:693-718 / KernelLaunch (optimized.cu:670-772) split by
 // divergence behaviour instead of by pixel:
 //
-//   wf_advance<FIRST>  one lane per pixel, uniform: camera ray of sample s, its ray/sphere tests
+//   wf_advance<kFormFirst>  one lane per pixel, uniform: camera ray of sample s, its ray/sphere tests
 //              (cpu:512-527) and the mesh's root-box test (cpu:279); path record initialised
 //   wf_travq   (rt_travq.hip.h; the pipeline's traversal kernel by default) the BVH traversal as a per-wave work stack of
 //              (ray slot, sibling pair) entries: BoundingBox::intersect cpu:146-157, moller_trumbore cpu:226-236, traversal
@@ -37,6 +37,8 @@
 #pragma once
 #include "rt_kernels.hip.h"
 #include "rt_qrows.h"
+#include "rt_still.h"
+#include <type_traits>
 
 namespace rtk {
 
@@ -56,11 +58,11 @@ constexpr int PQ_REFR_SHIFT = 23;                           // 6 bits: Ray::refr
 constexpr int PQ_TRAV = 1 << 29;                            // (either slot) the record's ray passed the mesh's root box: the traversal launch whose number (WfState::epoch) equals the
                                                             // record's depth field picks it up.  A shadow ray that misses the root box is not written at all: what its slot still
                                                             // holds is an older launch's record (other depth or another chain's number), or the zero of the layout's memset
-constexpr int PQ_NONCE_SHIFT = 30, PQ_NONCE_MASK = 3;        // (either slot) the launch chain's number mod 4, so that wf_advance<FIRST> need not clear the shadow slots of the previous chain
+constexpr int PQ_NONCE_SHIFT = 30, PQ_NONCE_MASK = 3;        // (either slot) the launch chain's number mod 4, so that wf_advance<kFormFirst> need not clear the shadow slots of the previous chain
 constexpr int PQ_LIVE_MASK = (int)((unsigned)PQ_TRAV | ((unsigned)PF_DEPTH_MASK << PF_DEPTH_SHIFT) | ((unsigned)PQ_NONCE_MASK << PQ_NONCE_SHIFT));
 // the record is live for traversal launch `epoch` of the chain numbered `nonce`: one masked compare.  A stale shadow record that passes (written four chains ago at the
 // same depth into a slot nobody wrote since) costs one wasted traversal and nothing else: wf_advance reads a shadow ray's result only if ITS OWN flag word says the
-// ray went to the mesh (PF_MESHX).  A RESUMED chain (first-shade cache, wf_advance_resume) writes no depth-1 shadow record at all, so a stale one of that depth would pass
+// ray went to the mesh (PF_MESHX).  A RESUMED chain (first-shade cache, wf_advance<kFormResume>) writes no depth-1 shadow record at all, so a stale one of that depth would pass
 // every fourth chain for as long as the view stands still: the chain's traversal launch 1 carries continuation rays only and enumerates the Y window (rt_qrows.h), in which
 // only the one mixed row can hold such a record; where there is no window the resume kernel writes the dead second half into its item's X slot (WfShade::kill_x)
 __device__ __forceinline__ bool wq_live(int w0, int epoch, int nonce) {
@@ -101,7 +103,7 @@ __device__ __forceinline__ float wf_anyhit_bound(f3 Pa, float nl) {
 // frame, tests/test_gpu_scene_fuzz.py light_edge seed 19).  The counting instantiation still reports paths with an elided ray whose fold leaves that old range
 // (wf_fold_bounded, rt_dead_channel_counts: unsure) -- a statistic now, their pixels are the reference's.  tests/test_dead_channels.py restates guard and fold in numpy
 // binary32 and compares every chain with an elided ray.
-// State: one byte per path, WfState::DCH[i] (bits 0..2: the dead channels, bit 3: a ray was elided), zeroed by wf_advance<FIRST>, read by every diffuse segment and written
+// State: one byte per path, WfState::DCH[i] (bits 0..2: the dead channels, bit 3: a ray was elided), zeroed by wf_advance<kFormFirst>, read by every diffuse segment and written
 // when it changes (at most 4 times per path): 1 B written per path and chain, <= 1 B read per path and launch.  (Bit 21 of the Y slot's flag word is NOT free for it: wf_travq
 // tests PQ_ANYHIT on every record it fetches, continuation rays included, and would take the nearest sphere's t for an any-hit bound.)
 constexpr unsigned kDeadAlbedoMax = 0x3f800000u;            // bits of 1: the largest albedo component of a segment that counts
@@ -185,13 +187,13 @@ struct WfState {
     int log2S, Q, n_groups;   // n_groups = 2 n_paths / 4 (ray groups);  S * Q >= n_groups
     int slots_per_block;      // multiple of 4: ray slots owned by one workgroup, handed to its waves on demand
     int nonce;                // number of the launch chain mod 4 (from a counter of the context): part of every live record's flag word
-    int epoch;                // index of the traversal launch inside its chain (0 after wf_advance<FIRST>): a queue record is live iff its flag word carries PQ_TRAV and this number
+    int epoch;                // index of the traversal launch inside its chain (0 after wf_advance<kFormFirst>): a queue record is live iff its flag word carries PQ_TRAV and this number
     int init_m;               // the traversal kernel merges partial results with atomicMin (wf_trav's work splitting): emitters initialise M
     unsigned long long *dbg;  // optional per-wave debug record (-DRT_DEBUG)
     int anyhit;               // shadow rays carry their any-hit bound (PQ_ANYHIT): the fixed-point instantiations of wf_travq stop a shadow ray at the first accepted triangle that certainly
                               // shades; a shadow ray that a sphere shades already is not traced through the mesh; a shadow ray whose segment has the direct term +0 either way is not traced
     int m0;                   // first-hit cache (rt_host_ctx.hip.h FirstHit), set in two launches of an eligible chain and zero in every other: M is the part's block of the cache, one word per
-                              // PIXEL SLOT.  wf_advance<FIRST>: only the items of the chain's first sample are handed to the traversal; the launch that closes segment 0: the Y result of item i
+                              // PIXEL SLOT.  wf_advance<kFormFirst>: only the items of the chain's first sample are handed to the traversal; the launch that closes segment 0: the Y result of item i
                               // is M[i - s_rel * n_px].  (The field sits in what was padding before `batch`: no kernel's argument layout moves.)
     const BatchFrame *batch;  // rt_render_device_batch: n_batch frame descriptors in device memory (item i belongs to frame i / n_px); nullptr / 0 = the launch's own camera, seed, output
     int n_batch;
@@ -199,7 +201,7 @@ struct WfState {
     // round trip brings flag and record
     float4 *QR;               // [2 slots] record of slot q: QR[2q] = (O.xyz, u.x), QR[2q+1] = (u.y, u.z, bits(W0), W1).  Y slot (ray r < n_paths): W0 = the path's
                               // flag word (PF_* | PQ_*; 0 = no path), W1 = t of the Y ray's nearest sphere; X slot: W0 = PQ_TRAV | depth | chain number (| PQ_ANYHIT: W1 = the any-hit bound), written only when the ray needs traversal
-    unsigned char *DCH;       // [n_paths] dead channels of path i (bits 0..2) and whether one of its shadow rays was elided for them (bit 3); wf_advance<FIRST> zeroes it (deadch only)
+    unsigned char *DCH;       // [n_paths] dead channels of path i (bits 0..2) and whether one of its shadow rays was elided for them (bit 3); wf_advance<kFormFirst> zeroes it (deadch only)
     int deadch;               // any-hit is on and so is the dead-channel rule: a diffuse segment whose three channels are dead does not trace its shadow ray (wf_dead_channels)
     QRows win;                // wf_travq: the rows of the queue this launch enumerates (rt_qrows.h; slots_per_block is then a share of the window); all zero = every row, the slot index as it is
     unsigned long long *X0;   // first-shadow cache (rt_host_ctx.hip.h FirstShadow): the part's block, one word per PIXEL SLOT -- what wf_travq wrote into M for the slot's segment-0 shadow ray
@@ -615,7 +617,7 @@ finished:
 // ---- textured meshes (rt_mesh_set_texture[_of], raytrace_hip.h) ----------------------------------------------
 // A texture is the first material property that changes from one hit to the next: a diffuse segment of a textured mesh stores its albedo
 // (mesh albedo (.) sampled texel, MTL's Kd x map_Kd) in ALB when it is shaded and the fold reads it there (SID == kSidTextured) instead of
-// looking the object's constant albedo up.  Only wf_advance_tex carries this code; frames without a textured mesh run wf_advance unchanged.
+// looking the object's constant albedo up.  Only wf_advance<kFormTex> carries this code; frames without a textured mesh run wf_advance unchanged.
 constexpr int kMaxObjects = 16;              // RT_MAX_OBJECTS: the texture table is indexed by object id
 constexpr int kSidTextured = 0xfe;           // SID of a textured diffuse segment (object ids are < kMaxObjects, 0xff = not diffuse)
 struct TexDesc {                             // the texture of one object
@@ -662,7 +664,7 @@ __device__ __forceinline__ f3 tex_sample(const TexDesc &td, float u, float v) {
               (t00.y * gx + t10.y * fx) * gy + (t01.y * gx + t11.y * fx) * fy,
               (t00.z * gx + t10.z * fx) * gy + (t01.z * gx + t11.z * fx) * fy);
 }
-// albedo of a hit on triangle `tri` of textured object `obj`: uv = (alpha uv_a + beta uv_b) + gamma uv_c, then mesh albedo (.) texture(uv).  wf_advance_tex and
+// albedo of a hit on triangle `tri` of textured object `obj`: uv = (alpha uv_a + beta uv_b) + gamma uv_c, then mesh albedo (.) texture(uv).  wf_advance<kFormTex> and
 // rt_kat_surface call this one function.
 __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, int obj, int tri, const Bary &b, float2 &uv) {
     const float2 ua = ts.uv[3 * tri], ub = ts.uv[3 * tri + 1], uc = ts.uv[3 * tri + 2];
@@ -676,10 +678,10 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 
 // ---- wf_advance: close the queries, shade, emit the next rays -----------------------------------------------
 // FIRST: the launch that opens the chain's samples -- camera rays instead of closing queries.
-// TEX (wf_advance_tex, never FIRST): textured meshes -- the albedo of a textured diffuse hit goes to ts.ALB and the fold reads it from there.
-// ANIM (wf_advance_anim, wf_advance_tex_anim; batches only): the frame's light and sphere poses come from anim[frame] instead of the Scene -- the same device functions on
+// TEX (wf_advance<kFormTex>, never FIRST): textured meshes -- the albedo of a textured diffuse hit goes to ts.ALB and the fold reads it from there.
+// ANIM (wf_advance<kFormAnim>, wf_advance<kFormTex | kFormAnim>; batches only): the frame's light and sphere poses come from anim[frame] instead of the Scene -- the same device functions on
 // other operands; the other instantiations never look at `anim`.
-// LIST (wf_advance_list, wf_advance_list_tex: rt_adaptive.hip.h): the chain's items are a list of (pixel slot, sample) records instead of the grid "pixel slot x sample" --
+// LIST (wf_advance<kFormList>, wf_advance<kFormTex | kFormList>; the chains of rt_adaptive.hip.h): the chain's items are a list of (pixel slot, sample) records instead of the grid "pixel slot x sample" --
 // pixel, sample and validity come from list.items[i]; every item writes samp_out[i]; the other instantiations never look at `list`.
 // The samples of a pixel are independent paths (the reference's loop cpu:701-712 carries nothing but the sum): a chain traces
 // several of them at once as items, each writes its colour, and path_reduce adds the colours in sample order.
@@ -695,7 +697,7 @@ struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
     int n;                       // items of this chain (n_paths is n rounded up to 64)
 };
-// The FIRST-SHADE cache (rt_host_ctx.hip.h FirstShade; wf_advance_fill, wf_advance_resume): one 32-byte record per PIXEL SLOT, the part's block -- the slot's path after
+// The FIRST-SHADE cache (rt_host_ctx.hip.h FirstShade; wf_advance<kFormFill>, wf_advance<kFormResume>): one 32-byte record per PIXEL SLOT, the part's block -- the slot's path after
 // segment 0 is shaded and its shadow ray decided, before the bounce direction (the first thing that reads the sample's key).  rec[2 k] = (origin of the continuation ray:
 // P_adjusted of a diffuse hit, the mirrored / refracted origin otherwise; V.x), rec[2 k + 1] = (V.y, V.z, l0, word): V the normal of a diffuse hit, the continuation
 // direction of a specular one; l0 the FINAL direct term of segment 0 (lvis, or +0 where a sphere or the mesh shades it; a moot or elided ray keeps lvis, as LS does);
@@ -728,12 +730,12 @@ __device__ __forceinline__ bool wf_x_shadowed(int F, f3 L, LoadM load_m, LoadRay
     }
     return shadowed;
 }
-// SHADE 1 (wf_advance_fill): the launch that emits segment 0's shadow rays in a chain that READS the first-shadow cache also stores the first-shade records of its
-// first-sample items.  SHADE 2 (wf_advance_resume): the launch that opens a chain whose part's records are stored -- in place of wf_advance<FIRST> and the launch that closes
+// SHADE 1 (wf_advance<kFormFill>): the launch that emits segment 0's shadow rays in a chain that READS the first-shadow cache also stores the first-shade records of its
+// first-sample items.  SHADE 2 (wf_advance<kFormResume>): the launch that opens a chain whose part's records are stored -- in place of wf_advance<kFormFirst> and the launch that closes
 // segment 0.  The other instantiations never look at `sh`.
 // SEVERAL POINT LIGHTS (rt_scene_set_lights; the rule: raytrace_hip.h "several point lights").  A diffuse segment still emits ONE shadow ray: to the light the sample's key
 // picks with probability proportional to its intensity, so that the estimator's weight I_k / p_k is the same number for every light -- the total.  The table is a kernel
-// argument of the two instantiations that read it (wf_advance_lights, wf_advance_tex_lights: LIGHTS) and of no other kernel: rtk::Scene does not grow.
+// argument of the two instantiations that read it (wf_advance<kFormLights>, wf_advance<kFormTex | kFormLights>: LIGHTS) and of no other kernel: rtk::Scene does not grow.
 constexpr int kMaxLights = 16;               // RT_MAX_LIGHTS
 struct WfLights {
     float4 pos[kMaxLights];                  // (position of light k, prefix[k] = fl(prefix[k - 1] + I_k)); entries from n on repeat the last one
@@ -752,7 +754,7 @@ __device__ __forceinline__ f3 wf_light_pick(const WfLights &lt, uint32_t hs, int
 }
 // LIGHTS WITH A RADIUS (rt_scene_set_light_radii; the rule: raytrace_hip.h "soft shadows").  Light k is a shell of point emitters of radius rho_k about L_k; a segment's
 // operand is one point of it, L' = L_k + rho_k w(hs, seg), and everything downstream is the point-light code on L'.  The two instantiations that read the radii
-// (wf_advance_soft, wf_advance_tex_soft: LIGHTS == 2) take the table extended by them; WfLights as the LIGHTS == 1 kernels receive it is what it was.
+// (wf_advance<kFormSoft>, wf_advance<kFormTex | kFormSoft>: LIGHTS == 2) take the table extended by them; WfLights as the LIGHTS == 1 kernels receive it is what it was.
 struct WfSoftLights {
     WfLights lt;
     float radius[kMaxLights];                // rho_k; entries from n on repeat the last one
@@ -782,18 +784,24 @@ __device__ __forceinline__ f3 wf_light_point(const WfSoftLights &sl, uint32_t hs
     return L;
 }
 // A THIN LENS (rt_camera_set_lens; the rule: raytrace_hip.h "thin lens", the step: lens_ray in rt_shade.hip.h).  The camera ray is built in one place, the opening launch of a
-// chain: with the lens on that launch is wf_advance_lens (LENS, always FIRST), which takes the lens by value; every later launch of the chain is whichever kernel the scene
+// chain: with the lens on that launch is wf_advance<kFormFirst | kFormLens> (LENS, always FIRST), which takes the lens by value; every later launch of the chain is whichever kernel the scene
 // picks without a lens.  rtk::Scene and rtk::Frame do not grow.
 struct WfLens { float radius, focus; };
-// THE CHAIN'S CLOSE (wf_advance_close: CLOSE; the plain chain only, rt_still.h still_plan).  The chain's last launch, at position segs, meets no continuation ray: it closes
+// THE CHAIN'S CLOSE (wf_advance<kFormClose>: CLOSE; the plain chain only, rt_still.h still_plan).  The chain's last launch, at position segs, meets no continuation ray: it closes
 // the shadow rays of segment segs - 1 and folds -- the close of a continuation ray, the shading and the emission are compiled out, and so is the dead half-record of a
 // finished path (see the fold).  (Folding a path a launch early, in the last shading launch, where its shadow ray is not handed to the traversal, was built beside it
 // and lost: DESIGN.md section 11.)
-template <bool STATS, bool FIRST, bool TEX = false, bool ANIM = false, bool LIST = false, int SHADE = 0, int LIGHTS = 0, bool LENS = false, bool CLOSE = false>
-__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim = nullptr,
-                                                const WfList &list = WfList{}, const WfShade &sh = WfShade{}, const WfLights *__restrict__ lt = nullptr,
-                                                const WfSoftLights *__restrict__ sl = nullptr, const WfLens *__restrict__ ln = nullptr) {
-    constexpr bool FILL = SHADE == 1, RESUME = SHADE == 2;
+// THE FORM (rt_still.h kForm*): one word says which of the above a launch compiles in, and the kernel's extra arguments follow from it -- after (sc, fr, st) a kernel takes,
+// in this order, the TexScene (kFormTex), the AnimFrame table (kFormAnim), the WfList (kFormList), the WfShade (kFormFill, kFormResume), the WfLights (kFormLights) or the
+// WfSoftLights (kFormSoft), the WfLens (kFormLens), each only if its bit is set.  The path takes all seven; what a form does not take it never reads (the kernel below
+// passes an empty one or null).
+using AnimTable = const AnimFrame *__restrict__;                      // (the qualifier is part of the kernel's parameter type: without it the loads of wf_advance<kFormTex | kFormAnim> come in another order)
+template <unsigned FORM>
+__device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim,
+                                                const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln) {
+    constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
+    constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose;
+    constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
@@ -847,7 +855,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     int sh_kind = kShadeMiss, sh_sid = 0xff, sh_dch = 0, sh_rays = 0;
     float4 ra = kDead, rb = kDead;
     if (RESUME) {
-        if (!valid) { st.QR[2 * (size_t)qy + 1] = kDead; return; }       // as wf_advance<FIRST> leaves a pixel slot outside the frame
+        if (!valid) { st.QR[2 * (size_t)qy + 1] = kDead; return; }       // as wf_advance<kFormFirst> leaves a pixel slot outside the frame
         if (sh.kill_x) st.QR[2 * (size_t)qx + 1] = kDead;
         ra = sh.rec[2 * (size_t)(i - s_rel * st.n_px)]; rb = sh.rec[2 * (size_t)(i - s_rel * st.n_px) + 1];
     }
@@ -1043,9 +1051,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         }
         // The path is over; its X slot keeps a record of an older launch, which no later one takes for its own.  (CLOSE: the chain is over too, and the store is dropped.
         // Whatever the Y slot's second half holds then -- a flag word without PQ_TRAV, so no traversal launch takes it for a ray -- the next chain of this part of the queue
-        // rewrites before any of its traversal launches runs, for EVERY item i < n_paths of its opening launch: wf_advance<FIRST> and its animated and lens forms store kDead
+        // rewrites before any of its traversal launches runs, for EVERY item i < n_paths of its opening launch: wf_advance<kFormFirst> and its animated and lens forms store kDead
         // for an item that is not valid (outside the frame, past spp, past the batch), fold an item of a chain of no segments, which stores kDead, and store the record's
-        // state for every other; wf_advance_resume stores kDead for an item that is not valid and folds or emits every other, never taking the early return of a path that
+        // state for every other; wf_advance<kFormResume> stores kDead for an item that is not valid and folds or emits every other, never taking the early return of a path that
         // is not alive.  A chain of another layout starts behind the queue's zero fill (start_chains: q_sig); the list chains have a queue of their own.)
         if (!CLOSE) st.QR[2 * (size_t)qy + 1] = kDead;
         ADV_MARK("fold_end");
@@ -1093,80 +1101,32 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     st.QR[2 * (size_t)qy + 1] = make_float4(emitY ? uy.y : 0.f, emitY ? uy.z : 0.f, __int_as_float(flags), t_sph);   // the path's state travels with its Y slot
 }
 
-template <bool STATS, bool FIRST>
-__global__ __launch_bounds__(256, 8) void wf_advance(const Scene sc, const Frame fr, const WfState st) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<STATS, FIRST>(sc, fr, st, i, wk, TexScene{});
-    wf_flush_work<STATS>(fr, wk);                                     // every lane of the wave arrives here (wave-level sums)
+// The one kernel.  Its extras are found by type: adv_extra_or the one of type T among them, or `none`; adv_extra its address, or null.  (The kernel itself hands them to the
+// path, with nothing in between: through one more function the counting forms come out with two counters' registers swapped -- profiles/advance_forms.)
+template <class T> __device__ __forceinline__ const T &adv_extra_or(const T &none) { return none; }
+template <class T, class E, class... Rest> __device__ __forceinline__ const T &adv_extra_or(const T &none, const E &e, const Rest &... rest) {
+    if constexpr (std::is_same_v<T, E>) return e; else return adv_extra_or(none, rest...);
 }
-// the same for a scene with a textured mesh (the launches after the first: wf_advance<STATS, true> shades nothing)
-template <bool STATS>
-__global__ __launch_bounds__(256, 8) void wf_advance_tex(const Scene sc, const Frame fr, const WfState st, const TexScene ts) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<STATS, false, true>(sc, fr, st, i, wk, ts);
-    wf_flush_work<STATS>(fr, wk);
+template <class T> __device__ __forceinline__ const T *adv_extra() { return nullptr; }
+template <class T, class E, class... Rest> __device__ __forceinline__ const T *adv_extra(const E &e, const Rest &... rest) {
+    if constexpr (std::is_same_v<T, E>) return &e; else return adv_extra<T>(rest...);
 }
-// the first-shade cache's two (never counting, textured or a batch: such chains are not eligible)
-__global__ __launch_bounds__(256, 8) void wf_advance_fill(const Scene sc, const Frame fr, const WfState st, const WfShade sh) {
+template <class T, class... Extra> constexpr bool adv_takes = (std::is_same_v<T, Extra> || ...);
+// Eight waves per SIMD (64 registers) for every form but one: in wf_advance<kFormTex | kFormSoft> the texture lookup's live values and a second binary64 sincos do not fit
+// 64 registers together: 8 spilled.  Seven waves per SIMD, 72 registers, no scratch.
+constexpr int adv_waves(unsigned form) { return (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
+template <unsigned FORM, class... Extra>
+__global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene sc, const Frame fr, const WfState st, const Extra... extra) {
+    static_assert(adv_takes<TexScene, Extra...> == ((FORM & kFormTex) != 0) && adv_takes<AnimTable, Extra...> == ((FORM & kFormAnim) != 0) &&
+                  adv_takes<WfList, Extra...> == ((FORM & kFormList) != 0) && adv_takes<WfShade, Extra...> == ((FORM & (kFormFill | kFormResume)) != 0) &&
+                  adv_takes<WfLights, Extra...> == ((FORM & kFormLights) != 0) && adv_takes<WfSoftLights, Extra...> == ((FORM & kFormSoft) != 0) &&
+                  adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0), "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 1>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, sh);
-}
-__global__ __launch_bounds__(256, 8) void wf_advance_resume(const Scene sc, const Frame fr, const WfState st, const WfShade sh) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 2>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, sh);
-}
-// the two for a scene of several lights (never counting, never an animated batch or a list; the opening launch is wf_advance<false, true>: a camera ray knows no light)
-__global__ __launch_bounds__(256, 8) void wf_advance_lights(const Scene sc, const Frame fr, const WfState st, const WfLights lt) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 0, 1>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, &lt);
-}
-__global__ __launch_bounds__(256, 8) void wf_advance_tex_lights(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const WfLights lt) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, true, false, false, 0, 1>(sc, fr, st, i, wk, ts, nullptr, WfList{}, WfShade{}, &lt);
-}
-// the two for a scene whose lights have a radius (as the two above; a soft list of one light comes here too)
-__global__ __launch_bounds__(256, 8) void wf_advance_soft(const Scene sc, const Frame fr, const WfState st, const WfSoftLights sl) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, false, false, false, 0, 2>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, nullptr, &sl);
-}
-// (the texture lookup's live values and a second binary64 sincos do not fit 64 registers together: 8 spilled.  Seven waves per SIMD, 72 registers, no scratch.)
-__global__ __launch_bounds__(256, 7) void wf_advance_tex_soft(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const WfSoftLights sl) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, true, false, false, 0, 2>(sc, fr, st, i, wk, ts, nullptr, WfList{}, WfShade{}, nullptr, &sl);
-}
-// the opening launch of a chain whose camera has a lens (never counting, never an animated batch or a list; the later launches are the scene's own)
-__global__ __launch_bounds__(256, 8) void wf_advance_lens(const Scene sc, const Frame fr, const WfState st, const WfLens ln) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, true, false, false, false, 0, 0, true>(sc, fr, st, i, wk, TexScene{}, nullptr, WfList{}, WfShade{}, nullptr, nullptr, &ln);
-}
-// the two for a frame of an animated batch (a batch never counts work: no STATS form)
-template <bool FIRST>
-__global__ __launch_bounds__(256, 8) void wf_advance_anim(const Scene sc, const Frame fr, const WfState st, const AnimFrame *__restrict__ anim) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, FIRST, false, true>(sc, fr, st, i, wk, TexScene{}, anim);
-}
-__global__ __launch_bounds__(256, 8) void wf_advance_tex_anim(const Scene sc, const Frame fr, const WfState st, const TexScene ts, const AnimFrame *__restrict__ anim) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<false, false, true, true>(sc, fr, st, i, wk, ts, anim);
-}
-// the last launch of the plain chain (CLOSE)
-template <bool STATS>
-__global__ __launch_bounds__(256, 8) void wf_advance_close(const Scene sc, const Frame fr, const WfState st) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    Work wk;
-    if (i < st.n_paths) wf_advance_path<STATS, false, false, false, false, 0, 0, false, true>(sc, fr, st, i, wk, TexScene{});
-    wf_flush_work<STATS>(fr, wk);
+    if (i < st.n_paths)
+        wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
+                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...));
+    wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 
 }  // namespace rtk

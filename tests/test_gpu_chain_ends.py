@@ -1,4 +1,4 @@
-"""The kernel of a plain chain's last position on the device (csrc/rt_wavefront.hip.h wf_advance_close, csrc/rt_still.h kAdvClose, enqueue_chain): a default context against
+"""The kernel of a plain chain's last position on the device (csrc/rt_wavefront.hip.h wf_advance<kFormClose>, csrc/rt_still.h kAdvClose, enqueue_chain): a default context against
 one created under RT_CHAIN_ENDS=0, which runs the generic wf_advance at every position, word for word, colour and the ray count in .w.  -m gpu.
 
 The reference of every comparison is the knob-off context; the cat and the two sphere presets are compared to the CPU oracle besides.  The shapes are the smallest that can
@@ -51,7 +51,7 @@ def _both(cs, p, render=None):
 @pytest.mark.parametrize("spp", [1, 3])
 @pytest.mark.parametrize("w,h", SIZES)
 def test_every_depth(pair, cat_golden, w, h, spp):
-    """a new camera height per depth: every frame a miss of every still-view level, the chains open with wf_advance<FIRST>"""
+    """a new camera height per depth: every frame a miss of every still-view level, the chains open with wf_advance<kFormFirst>"""
     for k, b in enumerate(BOUNCES):
         for c in pair:
             c.scene_upload(rt.scenes.spheres("cpu"), _cat(cat_golden), camera=((0.0, 0.25 * k, 55.0), None))

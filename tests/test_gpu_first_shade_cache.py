@@ -1,4 +1,4 @@
-"""The first-shade cache on the device (the records level of csrc/rt_still.h, enqueue_chain, wf_advance_fill and wf_advance_resume): a default context against one created under
+"""The first-shade cache on the device (the records level of csrc/rt_still.h, enqueue_chain, wf_advance<kFormFill> and wf_advance<kFormResume>): a default context against one created under
 RT_FIRST_SHADE_CACHE=0, word for word, colour and .w -- and rt_first_shade_cache_counts, which says whether a chain resumed its paths at the shaded first hit, stored the
 records or was not eligible, so that every comparison below is known to have gone through the path it names.  -m gpu.
 

@@ -1,4 +1,4 @@
-"""The thin lens on the device (rt_camera_set_lens: wf_advance_lens opens every chain while the aperture radius is above 0).  -m gpu.
+"""The thin lens on the device (rt_camera_set_lens: wf_advance<kFormFirst | kFormLens> opens every chain while the aperture radius is above 0).  -m gpu.
 
 Every comparison is on uint32 views, .w (the ray count) included.  References, none of them the code under test:
   what exists   a radius of 0, set at once or after a lens was on, against a context that never heard of the lens: frames and all three still-view counters;
@@ -113,7 +113,7 @@ def test_three_lights_with_radii_equal_the_model(ctx, oracle, oracle_cat, cat_go
     ctx.set_light_radii(THREE_R)
     ctx.set_lens(*LENS)
     _bits_equal(ctx.render(_params(2)), _model(oracle, oracle_cat, cat_golden, "cat", 2, lights=THREE, radii=THREE_R))
-    ctx.set_light_radii([0.0, 0.0, 0.0])                              # ... and as points: wf_advance_lights behind the same opening launch
+    ctx.set_light_radii([0.0, 0.0, 0.0])                              # ... and as points: wf_advance<kFormLights> behind the same opening launch
     pts = ctx.render(_params(1))
     _upload(ctx, "cat", cat_golden)
     assert ctx.lens() == (0.0, 1.0)                                   # the upload left a pinhole

@@ -468,7 +468,7 @@ def test_animated_batch_is_the_lone_frames(ctx, ref, oracle, oracle_cat, cat_gol
     got = _batch(ctx, _params(2, w=w2, h=h2), rows2, seq16, bufs, st)
     for k in (0, 7, 15):
         _bits_equal(got[k], _lone(ref, base, mesh, lambda seed: _params(2, w=w2, h=h2, seed=seed), rows2, seq16[k], one, st), f"frame {k} of 16")
-    # the cat textured and smooth-shaded (wf_advance_tex's animated form), against lone frames with the same texture and normals applied again
+    # the cat textured and smooth-shaded (wf_advance<kFormTex>'s animated form), against lone frames with the same texture and normals applied again
     rng = np.random.default_rng(22)
     px, dec = rng.integers(0, 256, size=(23, 37, 4), dtype=np.uint8), rng.random(256).astype(np.float32)
     dress = lambda c_: _dress(c_, cat_golden, px, dec)

@@ -319,3 +319,22 @@ def test_errors_leave_the_state_unchanged(ctx, cat_golden):
             ctx.mesh_set_texture(a["uvs"], a["uvidx"], a["texels"], filter=a["filter"], wrap=a["wrap"], object_slot=a["object_slot"])
         assert e.value.code == -1, case
         _bits_equal(ctx.render(_params(2)), before)
+
+
+def test_count_work_on_a_textured_scene(ctx, cat_golden):
+    """rt_count_work with a textured mesh (wf_advance<kFormTex | kFormStats>, the one form no other test launches): a default counting run has any-hit and the
+    dead-channel rule off, so a texture changes albedos and nothing else -- the reference's work is that of the same scene with the texture cleared.  64 x 48: 12 tiles,
+    two sub-frames for the frames beside it; one sample, two bounces."""
+    rng = np.random.default_rng(29)
+    v, tv = cat_golden["vertices"], np.asarray(cat_golden["tri_bvh_order"])[:, :3]
+    px = rng.integers(0, 256, size=(23, 37, 3), dtype=np.uint8)
+    p = rt.make_params(64, 48, 1, 2, **rt.scenes.CPU_LAUNCHER)
+    ctx.scene_upload(rt.scenes.spheres("cpu"), _cat(cat_golden))
+    plain_frame, plain = ctx.render(p), ctx.count_work(p)
+    assert plain["rays"] > 64 * 48 and plain["tri_tests"] > 0, plain   # the cat is in the picture
+    ctx.mesh_set_texture(_spherical_uv(v), tv, px, filter="bilinear")
+    assert (ctx.render(p)[..., :3] != plain_frame[..., :3]).any()      # ... and the texture on it
+    got = ctx.count_work(p)
+    ctx.mesh_set_texture(None, None, None)
+    assert {k: got[k] for k in ("rays", "box_tests", "nodes", "tri_tests")} == {k: plain[k] for k in ("rays", "box_tests", "nodes", "tri_tests")}
+    assert ctx.count_work(p) == plain

@@ -1,8 +1,9 @@
 """Per-position averages of a launch chain's kernels from a rocprofv3 kernel trace (CPU only).
 
 `rocprofv3 --kernel-trace --stats` averages wf_travq and wf_advance over the five launches of the headline's chain, which differ by a factor of three; this splits the trace
-by queue, restarts the position at every wf_advance<FIRST> and averages each position on its own -- what the first and the last launch of the chain cost.  A resumed
-chain (first-shade cache) opens with wf_advance_resume, which stands for wf_advance<FIRST> and the launch at position 0: its launches are filed from position 1 on.
+by queue, restarts the position at every opening launch (form `first`) and averages each position on its own -- what the first and the last launch of the chain cost.  A
+resumed chain (first-shade cache) opens with the form `resume`, which stands for the opening launch and the launch at position 0: its launches are filed from position 1 on.
+Which form a wf_advance launch is: tools/advance_forms.py (the names of before the one kernel template too).
 
 The last line files the wf_travq launches at position 1 by their chain's number on its queue mod 4 -- the two bits of WfState::nonce: a stale shadow record that a launch
 takes for its own every fourth chain would show as one class slower than the other three.
@@ -12,6 +13,8 @@ import collections
 import csv
 import glob
 import sys
+
+from advance_forms import form, form_of
 
 fs = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)
 if not fs:
@@ -27,11 +30,12 @@ for rs in per.values():
     kt = ka = chain = -1
     for r in rs:
         name, dur = r["Kernel_Name"], int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-        if "wf_advance<false, true>" in name:
+        f = form_of(name)
+        if f == form("first"):
             kt = ka = 0
             chain += 1
             acc["wf_advance<FIRST>"][0].append(dur)
-        elif "wf_advance_resume" in name:
+        elif f == form("resume"):
             kt = ka = 1
             chain += 1
             acc["wf_advance_resume"][0].append(dur)
@@ -40,7 +44,7 @@ for rs in per.values():
                 turn[chain & 3].append(dur)
             acc["wf_travq"][ka].append(dur)                      # the launch before wf_advance number ka: a chain that skipped its first traversal launch (first-hit cache) has none at 0
             kt += 1
-        elif ka >= 0 and "wf_advance" in name:
+        elif ka >= 0 and f is not None:
             acc["wf_advance"][ka].append(dur)
             ka += 1
 for kind, a in acc.items():

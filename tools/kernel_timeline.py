@@ -1,13 +1,13 @@
 """One frame's launches from a rocprofv3 kernel trace: per stream (queue), start / end relative to the frame's first launch,
 and for every traversal launch what ran beside it.  usage: python3 tools/kernel_timeline.py kernel_trace.csv"""
 import csv, sys, collections
+from advance_forms import BITS, form_of
 rows = list(csv.DictReader(open(sys.argv[1])))
 ev = []
 for r in rows:
     name = r["Kernel_Name"]
-    short = "T" if "wf_travq" in name else "F" if "wf_advance" in name and "true>" in name.replace(" ", "") and name.replace(" ", "").endswith("true>(rtk::Scene,rtk::Frame,rtk::WfState)") else "A" if "wf_advance" in name else None
-    if "wf_advance" in name:
-        short = "F" if name.replace(" ", "").split("wf_advance<")[1].split(">")[0].endswith("true") else "A"
+    f = form_of(name)
+    short = "T" if "wf_travq" in name else None if f is None else "F" if f & BITS["first"] else "A"   # F: an opening launch
     if short is None:
         continue
     ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short, r.get("Queue_Id", r.get("Stream_Id", "?"))))

@@ -36,14 +36,16 @@ args = ap.parse_args()
 
 
 def reduce_trace(path):
-    """mean / median duration of the two opening kernels in a rocprofv3 kernel trace"""
+    """mean / median duration of the two opening kernels in a rocprofv3 kernel trace (printed under the names they had as kernels of their own: profiles/lens)"""
+    from advance_forms import form, form_of
     dur = {"wf_advance_lens": [], "wf_advance<false, true>": []}
     for r in csv.DictReader(open(path)):
         name = r["Kernel_Name"].replace(" ", "")
         d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-        if "wf_advance_lens" in name:
+        f = form_of(name)
+        if f == form("first", "lens"):
             dur["wf_advance_lens"].append(d)
-        elif "wf_advance<false,true>" in name:
+        elif f == form("first"):
             dur["wf_advance<false, true>"].append(d)
     print("the opening launch of a chain (one of two sub-frames of 1920 x 1080), us, from a rocprofv3 kernel trace:")
     for k, v in dur.items():

@@ -2,6 +2,7 @@
 profiles/<round>/summary.json -- the per-kernel figures bench.py quotes in its `roofline.binding` object.
 usage: python tools/make_profile_summary.py profiles/round2"""
 import csv, json, os, sys
+from advance_forms import form_of
 
 d = sys.argv[1]
 HBM_PEAK = 8.0e12
@@ -21,11 +22,11 @@ res = {"source": {"bench_kernel_stats": "rocprofv3 --kernel-trace --stats -- pyt
                   "pmc": "rocprofv3 --kernel-trace --pmc <group> (one group per pass), RT_PARTS=1; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950",
                   "files": sorted(os.listdir(d))},
        "kernels": {}}
-for key, pat in (("wf_travq", "wf_travq<false"), ("wf_advance", "wf_advance<false, false>")):
+for key, is_it in (("wf_travq", lambda k: "wf_travq<false" in k), ("wf_advance", lambda k: form_of(k) == 0)):
     pm = json.load(open(os.path.join(d, "pmc_%s.json" % key)))
     c, dv = pm["counters_avg_per_dispatch"], pm["derived"]
-    n2 = next(v for k, v in two.items() if pat in k)
-    n1 = next(v for k, v in one.items() if pat in k)
+    n2 = next(v for k, v in two.items() if is_it(k))
+    n1 = next(v for k, v in one.items() if is_it(k))
     hbm = dv.get("hbm_read_bytes_corrected", 0) + dv.get("hbm_write_bytes", 0)
     res["kernels"][key] = {
         "rocprof_avg_us_two_streams": round(n2["avg_us"], 2), "share_of_gpu_time": round(n2["share_of_gpu_time"], 4),

@@ -11,7 +11,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
   RT_PARTS=1 timeout -k 5 120 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/p$i -o pmc -- python3 bench.py --no-cpu-baseline --no-end-to-end --large-steps 0 --prewarm-ms 0 --steps 4 --warmup 1 > $out/p$i.json 2> $out/p$i.err || { echo "pass $i ($grp) failed"; tail -5 $out/p$i.err; }
 done
-python3 tools/pmc_summary.py $out "wf_advance<false, false>" > $out/pmc_wf_advance.json || true
+python3 tools/pmc_summary.py $out "wf_advance<0u>" > $out/pmc_wf_advance.json || true
 python3 - <<P
 import json
 d=json.load(open("$out/pmc_wf_advance.json"))["derived"]; print({k: d[k] for k in d if "hbm" in k})
@@ -24,7 +24,7 @@ P
 python3 - <<P
 import csv, glob
 for f in sorted(glob.glob("$out/p*/**/*counter_collection.csv", recursive=True)):
-    rows=[r for r in csv.DictReader(open(f)) if "wf_advance<false" in r["Kernel_Name"] or "wf_travq<false" in r["Kernel_Name"]]
+    rows=[r for r in csv.DictReader(open(f)) if "wf_advance<0u>" in r["Kernel_Name"] or "wf_advance<2u>" in r["Kernel_Name"] or "wf_travq<false" in r["Kernel_Name"]]
     rows.sort(key=lambda r:int(r["Dispatch_Id"]))
     print(f.split("/")[-3] if "/" in f else f, [(r["Kernel_Name"][8:18], r["Counter_Name"], round(float(r["Counter_Value"])/1024*(2 if r["Counter_Name"]=="FETCH_SIZE" else 1),1)) for r in rows[-20:]])
 P

@@ -24,7 +24,7 @@ for grp in \
   RT_PARTS=1 timeout -k 5 120 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $out/p$i -o pmc -- python3 bench.py --no-cpu-baseline --no-end-to-end --large-steps 0 --prewarm-ms 0 --steps 4 --warmup 1 > $out/p$i.json 2> $out/p$i.err || { echo "pass $i ($grp) failed"; tail -5 $out/p$i.err; }
 done
 python3 tools/pmc_summary.py $out "wf_travq<false" > $out/pmc_wf_travq.json
-python3 tools/pmc_summary.py $out "wf_advance<false, false>" > $out/pmc_wf_advance.json
+python3 tools/pmc_summary.py $out "wf_advance<0u>" > $out/pmc_wf_advance.json
 python3 bench.py --full --steps 30 --warmup 5 > $out/bench_n1.json 2> $out/bench_n1.err
 rm -rf $out/t1 $out/t2 $out/p[0-9]*
 head -6 $out/bench_kernel_stats.csv; head -6 $out/single_stream_kernel_stats.csv

@@ -167,7 +167,7 @@ def travq_qw_counts(lines):
 
 
 def advance_counts(lines):
-    """wf_advance<false, false>: what a path pays for per launch, region by region (ADV_MARK labels of rt_wavefront.hip.h).  A region's instructions execute for the lanes
+    """wf_advance<0> and the other forms counted by region: what a path pays for per launch, region by region (ADV_MARK labels of rt_wavefront.hip.h).  A region's instructions execute for the lanes
     (paths) that take its branch; `rest` = decode, record reads and writes, the emission's root-box tests and flag words."""
     marks = regions(lines)
     pos = {}
@@ -187,6 +187,35 @@ def advance_counts(lines):
     return out
 
 
+# The forms of wf_advance that are counted (rt_wavefront.hip.h, one kernel template; tools/advance_forms.py): key of static_counts.json -> (form, by region).  By region:
+# cut at the ADV_MARK labels, as advance_counts says; the forms of several lights, of lights with a radius and of the lens plant no labels and are counted whole.
+ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
+           # the same regions of the form an animated batch runs (rt_render_device_batch_scenes): what the per-frame light and spheres cost
+           "wf_advance_anim": (("anim",), True), "wf_advance_anim_first": (("first", "anim"), False),
+           # adaptive sampling (rt_adaptive.hip.h): the LIST form by region, as the dense one
+           "wf_advance_list": (("list",), True), "wf_advance_list_first": (("first", "list"), False),
+           # the first-shade cache (WfShade): the launch that also stores the records by region; the launch that resumes from them, whole
+           "wf_advance_fill": (("fill",), True), "wf_advance_resume": (("resume",), False),
+           # the closing launch of a plain chain: by region -- closex and fold are all it keeps
+           "wf_advance_close": (("close",), True),
+           "wf_advance_lights": (("lights",), False), "wf_advance_tex_lights": (("tex", "lights"), False),
+           "wf_advance_soft": (("soft",), False), "wf_advance_tex_soft": (("tex", "soft"), False), "wf_advance_lens": (("first", "lens"), False)}
+
+
+def advance_forms_counts(asm):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import advance_forms
+    out = {}
+    for key, (bits, by_region) in ADVANCE.items():
+        f = advance_forms.form(*bits)
+        mm = re.search(r"^(%s\w*):" % re.escape(advance_forms.mangled_prefix(f)), asm, re.M)
+        if not mm:
+            raise SystemExit(f"static_counts: {advance_forms.describe(f)} ({key}) not found in the assembly")
+        t = kernel_text(asm, mm.group(1))
+        out[key] = advance_counts(t) if by_region else {"whole_kernel": count(t)}
+    return out
+
+
 def main():
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     sys.path.insert(0, ROOT)
@@ -203,14 +232,9 @@ def main():
     if not tw:
         raise SystemExit("static_counts: wf_travq<false, 64, false, false, true, true> (the 4-wide BOX step) not found in the assembly")
     res["wf_travq_qw"] = travq_qw_counts(tw)
-    for name, mangled in (("wf_advance", "_ZN3rtk10wf_advanceILb0ELb0EEEvNS_5SceneENS_5FrameENS_7WfStateE"),
-                          ("wf_advance_first", "_ZN3rtk10wf_advanceILb0ELb1EEEvNS_5SceneENS_5FrameENS_7WfStateE"),
-                          # the same regions of the instantiation an animated batch runs (rt_render_device_batch_scenes): what the per-frame light and spheres cost
-                          ("wf_advance_anim", "_ZN3rtk15wf_advance_animILb0EEEvNS_5SceneENS_5FrameENS_7WfStateEPKNS_9AnimFrameE"),
-                          ("wf_advance_anim_first", "_ZN3rtk15wf_advance_animILb1EEEvNS_5SceneENS_5FrameENS_7WfStateEPKNS_9AnimFrameE")):
-        t = kernel_text(asm, mangled)
-        if t:
-            res[name] = advance_counts(t) if name in ("wf_advance", "wf_advance_anim") else {"whole_kernel": count(t)}
+    adv = advance_forms_counts(asm)
+    for name in ("wf_advance", "wf_advance_first", "wf_advance_anim", "wf_advance_anim_first"):
+        res[name] = adv[name]
     # the first-hit planes, the a-trous filter's three instantiations and the temporal accumulation (rt_aov.hip.h, rt_denoise.hip.h, rt_temporal.hip.h): whole kernels
     for name, pattern in (("aov_emit", r"^(_ZN3rtk15aov_emit_kernel\w*):"), ("aov_close", r"^(_ZN3rtk16aov_close_kernelILb0E\w*):"),
                           # ... and the form that also writes the previous-frame planes (rt_render_aov_motion*)
@@ -232,42 +256,18 @@ def main():
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
-    # adaptive sampling (rt_adaptive.hip.h): the LIST form of wf_advance by region, as the dense one above; the plan's three launches, the fold and the counts: whole kernels
-    mm = re.search(r"^(_ZN3rtk15wf_advance_listILb0E\w*):", asm, re.M)
-    if not mm:
-        raise SystemExit("static_counts: wf_advance_list<false> not found in the assembly")
-    res["wf_advance_list"] = advance_counts(kernel_text(asm, mm.group(1)))
-    for name, pattern in (("wf_advance_list_first", r"^(_ZN3rtk15wf_advance_listILb1E\w*):"), ("sample_plan_totals", r"^(_ZN3rtk18sample_plan_totals\w*):"),
+    # adaptive sampling (rt_adaptive.hip.h): the LIST forms of wf_advance; the plan's three launches, the fold and the counts: whole kernels
+    res["wf_advance_list"], res["wf_advance_list_first"] = adv["wf_advance_list"], adv["wf_advance_list_first"]
+    for name, pattern in (("sample_plan_totals", r"^(_ZN3rtk18sample_plan_totals\w*):"),
                           ("sample_plan_scan", r"^(_ZN3rtk16sample_plan_scan\w*):"), ("sample_plan_scatter", r"^(_ZN3rtk19sample_plan_scatter\w*):"),
                           ("sample_fold", r"^(_ZN3rtk11sample_fold\w*):"), ("sample_counts", r"^(_ZN3rtk20sample_counts_kernel\w*):")):
         mm = re.search(pattern, asm, re.M)
         if not mm:
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
-    # the first-shade cache (rt_wavefront.hip.h WfShade): the launch that also stores the records by region, as wf_advance; the launch that resumes from them, whole
-    for name, pattern in (("wf_advance_fill", r"^(_ZN3rtk15wf_advance_fillE\w*):"), ("wf_advance_resume", r"^(_ZN3rtk17wf_advance_resumeE\w*):")):
-        mm = re.search(pattern, asm, re.M)
-        if not mm:
-            raise SystemExit(f"static_counts: {name} not found in the assembly")
-        res[name] = advance_counts(kernel_text(asm, mm.group(1))) if name == "wf_advance_fill" else {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
-    # the closing launch of a plain chain (rt_wavefront.hip.h CLOSE): by region, as wf_advance -- closex and fold are all it keeps
-    mm = re.search(r"^(_ZN3rtk16wf_advance_closeILb0E\w*):", asm, re.M)
-    if not mm:
-        raise SystemExit("static_counts: wf_advance_close<false> not found in the assembly")
-    res["wf_advance_close"] = advance_counts(kernel_text(asm, mm.group(1)))
-    # several point lights (rt_wavefront.hip.h WfLights): the two launches that pick a light per diffuse segment, whole (they plant no labels)
-    # ... and the two for lights with a radius (WfSoftLights): the pick and a point of the picked light's shell
-    for name, pattern in (("wf_advance_lights", r"^(_ZN3rtk17wf_advance_lightsE\w*):"), ("wf_advance_tex_lights", r"^(_ZN3rtk21wf_advance_tex_lightsE\w*):"),
-                          ("wf_advance_soft", r"^(_ZN3rtk15wf_advance_softE\w*):"), ("wf_advance_tex_soft", r"^(_ZN3rtk19wf_advance_tex_softE\w*):")):
-        mm = re.search(pattern, asm, re.M)
-        if not mm:
-            raise SystemExit(f"static_counts: {name} not found in the assembly")
-        res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
-    # the thin lens (rt_wavefront.hip.h WfLens): the opening launch of a chain whose camera has an aperture, whole (it plants no labels)
-    mm = re.search(r"^(_ZN3rtk15wf_advance_lensE\w*):", asm, re.M)
-    if not mm:
-        raise SystemExit("static_counts: wf_advance_lens not found in the assembly")
-    res["wf_advance_lens"] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
+    # the first-shade cache, the closing launch of a plain chain, several lights, lights with a radius, the thin lens (ADVANCE)
+    for name in ("wf_advance_fill", "wf_advance_resume", "wf_advance_close", "wf_advance_lights", "wf_advance_tex_lights", "wf_advance_soft", "wf_advance_tex_soft", "wf_advance_lens"):
+        res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
         json.dump(res, f, indent=1)
