@@ -348,6 +348,36 @@ int rt_scene_set_light_radius_at(rt_ctx *ctx, int k, float radius);
 int rt_camera_set_lens(rt_ctx *ctx, float aperture_radius, float focus_distance);
 int rt_camera_get_lens(const rt_ctx *ctx, float *aperture_radius, float *focus_distance);
 
+/* --- SHUTTER: motion blur -- the spheres and the light move within one frame's exposure (ABI 6, additive).  The context carries a shutter motion: a displacement dL of the
+ *     light over the exposure and a displacement dC[slot] for every object slot of Scene::objects.  No counterpart in the reference: its frames are instants
+ *     (MoveLightSource / MoveObject act between two frames).
+ *     "Shutter on": some component of some displacement is not +-0.  With the shutter off every call and every frame is what it is without these entries, launch for launch.
+ *     THE RULE.  Sample samp of pixel (px, row) has the key hs = sample_hash(pixel_hash(fr, row, px, seed), samp).  Its time is
+ *       tau = uniform01(hs, 1u << 28, 2)       in (0, 1].  (The RNG keys on depth * 4 + dim modulo 2^32: the draw sits at 2^30 + 2.  The lens uses 2^30 + 0 and 2^30 + 1;
+ *                                              jitter, bounce and pick draws sit below 4 (segs + 1), the shell draws of soft shadows at 2^31 + ...: nothing collides.)
+ *     Every launch of the path draws tau again from hs: no path state grows.  In binary32, one rounding per operation, the product first, no fused multiply-add:
+ *       C' = C + dC tau                        per component, for every sphere -- MoveObject's arithmetic (realtime:1096): rt_scene_move_sphere(v = dC, dt = 1) gives the
+ *                                              tau = 1 pose exactly
+ *       L' = L + dL tau                        the light, in the same form (linear, not the orbit of rt_scene_move_light)
+ *     R * R and the materials do not move.  For that path every sphere test, sphere normal, shadow direction, the comparison that decides whether the light is hidden, and
+ *     the direct term use C' and L', in every segment: one path sees one instant, so nested glass stays consistent.  Meshes do not move within an exposure: their slots'
+ *     displacements must be +-0.  The camera does not move.  The step is shutter_time / shutter_pose in rt_shade.hip.h; four forms of wf_advance know it
+ *     (kFormShutter: the two opening launches, with and without the lens, and the later launches with and without textures).
+ *     The motion is host state: make_frame captures it as it captures the lens, and a frame in flight keeps what its launches captured.  rt_scene_upload* leaves the
+ *     shutter closed; rt_scene_set_sphere, rt_scene_move_sphere, rt_scene_set_light and rt_scene_move_light keep it.  rt_scene_set_shutter(ctx, NULL) closes it.
+ *     RT_ERR_INVALID, the state untouched: a component that is not finite, a displacement that is not +-0 for a mesh's slot or for a slot beyond the scene's objects, a
+ *     NULL out.  RT_ERR_NO_SCENE: no upload, or the last rt_scene_upload* failed.  A refused get writes nothing.
+ *     Shutter on is rendered by every entry that runs wf_advance -- rt_render*, _device, _device_batch, _async, _pose*, rt_progressive_frame -- under the variants auto
+ *     (never lockstep), wavefront, wavefront_lds, wavefront_queue and lds_*, with several samples, row shares, RT_PARTS cuts and pipelining, with or without the lens.
+ *     RT_ERR_UNSUPPORTED, outputs untouched, "shutter" in the error text: rt_render_device_batch_scenes with scenes, rt_render_counts*, rt_count_work, the variants
+ *     path, lockstep and global, and every render while the scene holds several lights or a light with a radius above 0.
+ *     STILL VIEWS.  A path's spheres and light depend on the sample: while the shutter is on no chain fills or uses the first-hit, first-shadow or first-shade cache and
+ *     none of their counters moves.  Turning the shutter on or off empties all three.
+ *     FEATURE BUFFERS and rt_trace_rays see the start-of-exposure pose (C, L): the scene as it is stored. */
+typedef struct { float light[3]; float object[RT_MAX_OBJECTS][3]; } rt_shutter;
+int rt_scene_set_shutter(rt_ctx *ctx, const rt_shutter *shutter);
+int rt_scene_get_shutter(const rt_ctx *ctx, rt_shutter *out);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

@@ -656,6 +656,15 @@ public:
         check(rt_camera_get_lens(ctx_, &r, &f), "rt_camera_get_lens");
         return {r, f};
     }
+    // Shutter (rt_scene_set_shutter): what the light and every object slot travel over one frame's exposure; a sample sees the scene at its own time in (0, 1].
+    // close_shutter(): the frames are instants again.  shutter() -> the motion as stored
+    void set_shutter(const rt_shutter &motion) { check(rt_scene_set_shutter(ctx_, &motion), "rt_scene_set_shutter"); }
+    void close_shutter() { check(rt_scene_set_shutter(ctx_, nullptr), "rt_scene_set_shutter"); }
+    rt_shutter shutter() {
+        rt_shutter s = {};
+        check(rt_scene_get_shutter(ctx_, &s), "rt_scene_get_shutter");
+        return s;
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

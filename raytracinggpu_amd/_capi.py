@@ -42,7 +42,7 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_mesh_compute_normals", "rt_mesh_compute_normals_of", "rt_mesh_get_vertex_normals", "rt_mesh_snapshot_normals", "rt_mesh_normal_snapshot_mask",
            "rt_scene_set_lights", "rt_scene_get_lights", "rt_scene_set_light_at", "rt_scene_move_light_at",
            "rt_scene_set_light_radii", "rt_scene_get_light_radii", "rt_scene_set_light_radius_at",
-           "rt_camera_set_lens", "rt_camera_get_lens"]
+           "rt_camera_set_lens", "rt_camera_get_lens", "rt_scene_set_shutter", "rt_scene_get_shutter"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -95,6 +95,11 @@ MAX_SPHERES = 16
 
 class SpherePose(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("radius", C.c_float)]
+
+
+class Shutter(C.Structure):
+    """what the light and every object slot travel over one frame's exposure (rt_shutter)"""
+    _fields_ = [("light", C.c_float * 3), ("object", (C.c_float * 3) * MAX_OBJECTS)]
 
 
 class FrameScene(C.Structure):
@@ -436,6 +441,8 @@ def load():
     L.rt_scene_set_light_radius_at.argtypes = [vp, C.c_int, C.c_float]
     L.rt_camera_set_lens.argtypes = [vp, C.c_float, C.c_float]
     L.rt_camera_get_lens.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.rt_scene_set_shutter.argtypes = [vp, C.POINTER(Shutter)]
+    L.rt_scene_get_shutter.argtypes = [vp, C.POINTER(Shutter)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -748,6 +755,24 @@ class Context:
         r, f = C.c_float(0), C.c_float(0)
         self._check(self._L.rt_camera_get_lens(self._h, C.byref(r), C.byref(f)))
         return float(r.value), float(f.value)
+
+    # --- shutter (rt_scene_set_shutter): what the light and the spheres travel within one frame's exposure; all zero is the closed shutter
+    def set_shutter(self, light=None, objects=None):
+        """rt_scene_set_shutter: light = the light's displacement over the exposure, objects = {object_slot: displacement}; neither: NULL, the shutter is closed"""
+        if light is None and objects is None:
+            self._check(self._L.rt_scene_set_shutter(self._h, None))
+            return
+        s = Shutter()
+        s.light[:] = [float(x) for x in (light if light is not None else (0.0, 0.0, 0.0))]
+        for slot, v in (objects or {}).items():
+            s.object[int(slot)][:] = [float(x) for x in v]
+        self._check(self._L.rt_scene_set_shutter(self._h, C.byref(s)))
+
+    def shutter(self):
+        """rt_scene_get_shutter -> (light [3], objects [MAX_OBJECTS, 3]) as float32 arrays"""
+        s = Shutter()
+        self._check(self._L.rt_scene_get_shutter(self._h, C.byref(s)))
+        return np.array(s.light, np.float32), np.array([list(o) for o in s.object], np.float32)
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

@@ -156,6 +156,7 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     ctx->n_lights = 1;                                                   // the scene this call installs has the one uploaded light (rt_scene_set_lights)
     memset(ctx->light_radii, 0, sizeof(ctx->light_radii));               // ... a point (rt_scene_set_light_radii; the still view: shading_changed above)
     ctx->lens_radius = 0.f; ctx->lens_focus = 1.f;                       // ... seen through a pinhole (rt_camera_set_lens; the still view: mesh_changed above)
+    ctx->shutter = rt_shutter{}; ctx->shutter_on = false;                // ... at one instant (rt_scene_set_shutter)
     sc.camx = camera->position[0]; sc.camy = camera->position[1]; sc.camz = camera->position[2]; sc.fov = camera->fov;
 
     PhaseClock pc;

@@ -181,6 +181,10 @@ struct rt_ctx {
     // The camera's thin lens (rt_camera_set_lens): aperture radius and focus distance in scene units.  Host state like the lights: make_frame captures it by value, and a
     // radius above 0 makes every chain open with wf_advance<kFormFirst | kFormLens>.  rt_scene_upload* leaves a pinhole: the camera comes with the upload.
     float lens_radius = 0.f, lens_focus = 1.f;
+    // The shutter motion (rt_scene_set_shutter): what the light and every object slot travel over one frame's exposure.  Host state like the lens: make_frame captures it by
+    // value.  shutter_on: some component is not +-0 -- every launch of every chain is then a kFormShutter form.  rt_scene_upload* closes it.
+    rt_shutter shutter = {};
+    bool shutter_on = false;
     DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.

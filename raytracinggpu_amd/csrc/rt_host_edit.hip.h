@@ -203,6 +203,42 @@ int rt_camera_get_lens(const rt_ctx *ctx, float *aperture_radius, float *focus_d
     return RT_OK;
 }
 
+// ---- the shutter motion (raytrace_hip.h "shutter"): host state; every launch of a chain captures the table make_frame derives from it ----
+int rt_scene_set_shutter(rt_ctx *ctx, const rt_shutter *shutter) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    const rt_shutter closed = {};
+    const rt_shutter &s = shutter ? *shutter : closed;                   // NULL closes the shutter
+    bool on = false;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(s.light[a])) return fail(ctx, RT_ERR_INVALID, "shutter: the light's displacement has a component that is not finite");
+        on = on || s.light[a] != 0.f;
+    }
+    for (int slot = 0; slot < RT_MAX_OBJECTS; ++slot) {
+        bool moves = false;
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(s.object[slot][a])) return fail(ctx, RT_ERR_INVALID, "shutter: the displacement of object_slot %d has a component that is not finite", slot);
+            moves = moves || s.object[slot][a] != 0.f;
+        }
+        if (moves && slot >= ctx->scene.n_objects) return fail(ctx, RT_ERR_INVALID, "shutter: object_slot %d moves, beyond the scene's %d objects", slot, ctx->scene.n_objects);
+        if (moves && sphere_at(ctx->scene, slot) < 0) return fail(ctx, RT_ERR_INVALID, "shutter: object_slot %d is a mesh: meshes do not move within an exposure", slot);
+        on = on || moves;
+    }
+    if (on != ctx->shutter_on) ctx->still.shutter_changed();             // on or off: the still view's levels are emptied (rt_still.h)
+    ctx->shutter = s;
+    ctx->shutter_on = on;
+    return RT_OK;
+}
+
+int rt_scene_get_shutter(const rt_ctx *ctx, rt_shutter *out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!out) return fail(c, RT_ERR_INVALID, "out is NULL");
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    *out = ctx->shutter;
+    return RT_OK;
+}
+
 int rt_scene_get_sphere(const rt_ctx *ctx, int object_slot, rt_sphere *out) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     rt_ctx *c = const_cast<rt_ctx *>(ctx);

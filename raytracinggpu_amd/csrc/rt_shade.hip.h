@@ -77,6 +77,11 @@ __device__ __forceinline__ void lens_ray(const Frame &fr, float R, float f, uint
     O = (O + lx * ex) + ly * ey;
     u = normalize(F - O);
 }
+// The SHUTTER (rt_scene_set_shutter; the rule: raytrace_hip.h "shutter"): the time of the sample with key hs, in (0, 1] -- the one draw at depth 2^28, dim 2 (key 2^30 + 2,
+// beside the lens's two) -- and where a point that travels d over the exposure is at that time: C + d tau per component, the product first, each rounded once
+// (MoveObject's arithmetic, realtime:1096).  Every launch of a path draws tau again from hs: no path state grows.
+__device__ __forceinline__ float shutter_time(uint32_t hs) { return uniform01(hs, 1u << 28, 2); }
+__device__ __forceinline__ f3 shutter_pose(f3 C, f3 d, float tau) { return mk(C.x + d.x * tau, C.y + d.y * tau, C.z + d.z * tau); }
 
 // ---- the hit ----
 // alpha, beta, gamma of triangle `tri` (visit order) for the ray (O, u): get_smooth_normal's expressions (realtime_render.cu:221-245).  The smooth normal, the

@@ -690,8 +690,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #define ADV_MARK(name) do { } while (0)
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
-// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation)
-#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
+// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -787,20 +787,33 @@ __device__ __forceinline__ f3 wf_light_point(const WfSoftLights &sl, uint32_t hs
 // chain: with the lens on that launch is wf_advance<kFormFirst | kFormLens> (LENS, always FIRST), which takes the lens by value; every later launch of the chain is whichever kernel the scene
 // picks without a lens.  rtk::Scene and rtk::Frame do not grow.
 struct WfLens { float radius, focus; };
+// THE SHUTTER (rt_scene_set_shutter; the rule: raytrace_hip.h "shutter", the step: shutter_time / shutter_pose in rt_shade.hip.h).  Over the exposure the light travels dL and
+// sphere k travels its displacement; a path sees the scene at ONE time tau, drawn from its sample's key, and every launch of its chain -- the SHUTTER forms, kFormShutter --
+// draws tau again and forms the light and the centres at that time where the Scene's would be read: the close of a shadow ray, the sphere normal, the shadow direction and
+// the direct term, the sphere tests at emission.  R2 and the materials do not move; meshes do not move.  The table is a kernel argument of the four forms that read it.
+// (BatchFrame's hazard -- an argument array indexed per lane goes to scratch -- is met as WfLights::pos[k] meets it: the loop over the spheres reads sph[] with a wave-uniform
+// index; the one per-lane read is obj[] with the hit object's id.)
+struct WfShutter {
+    float4 light;                            // dL (w unused)
+    float4 sph[kMaxSpheres];                 // the displacement of sphere k, in the order of Scene::sph
+    float4 obj[kMaxSpheres];                 // the same displacements by OBJECT id (a mesh's entry is 0), for the normal
+};
+__device__ __forceinline__ f3 wf_xyz(float4 v) { return mk(v.x, v.y, v.z); }
 // THE CHAIN'S CLOSE (wf_advance<kFormClose>: CLOSE; the plain chain only, rt_still.h still_plan).  The chain's last launch, at position segs, meets no continuation ray: it closes
 // the shadow rays of segment segs - 1 and folds -- the close of a continuation ray, the shading and the emission are compiled out, and so is the dead half-record of a
 // finished path (see the fold).  (Folding a path a launch early, in the last shading launch, where its shadow ray is not handed to the traversal, was built beside it
 // and lost: DESIGN.md section 11.)
 // THE FORM (rt_still.h kForm*): one word says which of the above a launch compiles in, and the kernel's extra arguments follow from it -- after (sc, fr, st) a kernel takes,
 // in this order, the TexScene (kFormTex), the AnimFrame table (kFormAnim), the WfList (kFormList), the WfShade (kFormFill, kFormResume), the WfLights (kFormLights) or the
-// WfSoftLights (kFormSoft), the WfLens (kFormLens), each only if its bit is set.  The path takes all seven; what a form does not take it never reads (the kernel below
-// passes an empty one or null).
+// WfSoftLights (kFormSoft), the WfLens (kFormLens), the WfShutter (kFormShutter), each only if its bit is set.  The path takes all eight; what a form does not take it never
+// reads (the kernel below passes an empty one or null).
 using AnimTable = const AnimFrame *__restrict__;                      // (the qualifier is part of the kernel's parameter type: without it the loads of wf_advance<kFormTex | kFormAnim> come in another order)
 template <unsigned FORM>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim,
-                                                const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln) {
+                                                const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln,
+                                                const WfShutter *__restrict__ shu) {
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
-    constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose;
+    constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
@@ -849,6 +862,11 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         valid = valid && i < list.n;
     }
     const int row = image_row(fr, lrow);
+    float tau = 0.f;                                                  // (SHUTTER) the path's time, and the light where it is then
+    if constexpr (SHUTTER) {
+        tau = shutter_time(sample_hash(pixel_hash(fr, row, px, fr_seed), samp));
+        L = shutter_pose(L, wf_xyz(shu->light), tau);
+    }
     // (FILL) what the slot's record holds, gathered while segment 0 is shaded; (RESUME) the record
     f3 shO = mk(0, 0, 0), shV = mk(0, 0, 1);
     float sh_l = 0.f;
@@ -930,6 +948,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 f3 N;
                 if (RESUME) N = u;
                 else if (ANIM && tri_win < 0) { const float4 c = af->ctr[win]; N = normalize(P - mk(c.x, c.y, c.z)); }   // sphere_normal (cpu:524-525) about this frame's centre
+                else if (SHUTTER && tri_win < 0) N = normalize(P - shutter_pose(sphere_centre_of(sc, win), wf_xyz(shu->obj[win]), tau));   // ... about the centre at the path's time
                 else N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
                 const Material m = material_of(sc, win);
                 ADV_MARK("closey_end");
@@ -1065,6 +1084,12 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     SphereNear h, hx;
     ADV_MARK("spheres_begin");
     if (ANIM) spheres_near2(sc, af->sph, emitX ? Ox : Oy, uy, emitY, ux, emitX && !x_moot, h, hx);
+    else if constexpr (SHUTTER)                                       // the spheres where they are at the path's time (k is wave-uniform: scalar loads)
+        spheres_near2(sc.n_spheres, [&](int k) {
+            const Sphere &s0 = sc.sph[k];
+            const f3 c = shutter_pose(mk(s0.cx, s0.cy, s0.cz), wf_xyz(shu->sph[k]), tau);
+            return Sphere{c.x, c.y, c.z, s0.R, s0.R2, s0.obj};
+        }, emitX ? Ox : Oy, uy, emitY, ux, emitX && !x_moot, h, hx);
     else spheres_near2(sc, emitX ? Ox : Oy, uy, emitY, ux, emitX && !x_moot, h, hx);   // a shadow ray and a bounce ray leave the same point (Oy == Ox == P_adjusted)
     ADV_MARK("spheres_end");
     float t_sph = 0.f;
@@ -1120,12 +1145,13 @@ __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene s
     static_assert(adv_takes<TexScene, Extra...> == ((FORM & kFormTex) != 0) && adv_takes<AnimTable, Extra...> == ((FORM & kFormAnim) != 0) &&
                   adv_takes<WfList, Extra...> == ((FORM & kFormList) != 0) && adv_takes<WfShade, Extra...> == ((FORM & (kFormFill | kFormResume)) != 0) &&
                   adv_takes<WfLights, Extra...> == ((FORM & kFormLights) != 0) && adv_takes<WfSoftLights, Extra...> == ((FORM & kFormSoft) != 0) &&
-                  adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0), "a form's extras are the ones its bits name");
+                  adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0),
+                  "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths)
         wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
-                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...));
+                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...));
     wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 

@@ -6,7 +6,7 @@ here and nowhere else.  form_of(name) -> the word, or None for another kernel.""
 import re
 
 BITS = {"stats": 1 << 0, "first": 1 << 1, "tex": 1 << 2, "anim": 1 << 3, "list": 1 << 4, "fill": 1 << 5, "resume": 1 << 6, "lights": 1 << 7, "soft": 1 << 8,
-        "lens": 1 << 9, "close": 1 << 10}
+        "lens": 1 << 9, "close": 1 << 10, "shutter": 1 << 11}
 _B = BITS
 # the names the forms had as kernels of their own (demangled, spaces dropped)
 OLD = {"wf_advance<false,false>": 0, "wf_advance<true,false>": _B["stats"], "wf_advance<false,true>": _B["first"], "wf_advance<true,true>": _B["first"] | _B["stats"],
@@ -15,7 +15,9 @@ OLD = {"wf_advance<false,false>": 0, "wf_advance<true,false>": _B["stats"], "wf_
        "wf_advance_lens": _B["first"] | _B["lens"], "wf_advance_anim<false>": _B["anim"], "wf_advance_anim<true>": _B["first"] | _B["anim"],
        "wf_advance_tex_anim": _B["tex"] | _B["anim"], "wf_advance_close<false>": _B["close"], "wf_advance_close<true>": _B["close"] | _B["stats"],
        "wf_advance_list<false>": _B["list"], "wf_advance_list<true>": _B["first"] | _B["list"], "wf_advance_list_tex": _B["tex"] | _B["list"]}
-FORMS = sorted(set(OLD.values()))                                      # the 21 that are built
+# the forms that came after the one template and never had a kernel name of their own: the four of the shutter
+LATER = [_B["first"] | _B["shutter"], _B["first"] | _B["lens"] | _B["shutter"], _B["shutter"], _B["tex"] | _B["shutter"]]
+FORMS = sorted(set(OLD.values()) | set(LATER))                         # the 25 that are built
 
 
 def form(*names):

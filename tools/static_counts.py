@@ -199,7 +199,10 @@ ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
            # the closing launch of a plain chain: by region -- closex and fold are all it keeps
            "wf_advance_close": (("close",), True),
            "wf_advance_lights": (("lights",), False), "wf_advance_tex_lights": (("tex", "lights"), False),
-           "wf_advance_soft": (("soft",), False), "wf_advance_tex_soft": (("tex", "soft"), False), "wf_advance_lens": (("first", "lens"), False)}
+           "wf_advance_soft": (("soft",), False), "wf_advance_tex_soft": (("tex", "soft"), False), "wf_advance_lens": (("first", "lens"), False),
+           # the shutter (WfShutter): the two opening launches and the two later ones, whole (they plant no labels either)
+           "wf_advance_shutter_first": (("first", "shutter"), False), "wf_advance_lens_shutter_first": (("first", "lens", "shutter"), False),
+           "wf_advance_shutter": (("shutter",), False), "wf_advance_tex_shutter": (("tex", "shutter"), False)}
 
 
 def advance_forms_counts(asm):
@@ -266,7 +269,8 @@ def main():
             raise SystemExit(f"static_counts: {name} not found in the assembly")
         res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
     # the first-shade cache, the closing launch of a plain chain, several lights, lights with a radius, the thin lens (ADVANCE)
-    for name in ("wf_advance_fill", "wf_advance_resume", "wf_advance_close", "wf_advance_lights", "wf_advance_tex_lights", "wf_advance_soft", "wf_advance_tex_soft", "wf_advance_lens"):
+    for name in ("wf_advance_fill", "wf_advance_resume", "wf_advance_close", "wf_advance_lights", "wf_advance_tex_lights", "wf_advance_soft", "wf_advance_tex_soft", "wf_advance_lens",
+                 "wf_advance_shutter_first", "wf_advance_lens_shutter_first", "wf_advance_shutter", "wf_advance_tex_shutter"):
         res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
