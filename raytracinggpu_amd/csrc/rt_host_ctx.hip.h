@@ -81,6 +81,9 @@ struct Knobs {
                                // knob at 0, and for scenes with a textured mesh.  Bit-exact either way
     int chain_ends = 1;        // RT_CHAIN_ENDS=0: the last wf_advance launch of a plain chain is the generic kernel (A/B, cross-check; default: wf_advance<kFormClose>, which only closes
                                // the last segment's shadow rays and folds, rt_wavefront.hip.h CLOSE, rt_still.h kAdvClose).  Bit-exact either way
+    int stream_policy = 3;     // RT_STREAM_POLICY: a bit per group of use-once streams whose accesses in wf_advance go past the Infinity Cache (rt_wavefront.hip.h kPol*: 1 the
+                               // first-shade records a resumed chain loads, 2 the pixel store of the fold); 0: every access the plain instruction, the code of before the policy
+                               // (A/B, cross-check).  Bit-exact whatever the value; headline -1.1 ... -1.4 %
     int refit_wide = 1;        // RT_REFIT_WIDE=0: rt_mesh_set_vertices* refits with the one-workgroup refit_kernel, as rt_mesh_transform does (A/B, cross-check; default: the climb across
                                // the chip, rt_meshops.hip.h refit_up_kernel).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
@@ -139,6 +142,7 @@ static Knobs read_knobs() {
     if (geti("RT_FIRST_SHADOW_CACHE", v)) k.first_shadow_cache = v != 0;
     if (geti("RT_FIRST_SHADE_CACHE", v)) k.first_shade_cache = v != 0;
     if (geti("RT_CHAIN_ENDS", v)) k.chain_ends = v != 0;
+    if (geti("RT_STREAM_POLICY", v) && v >= 0 && v <= 3) k.stream_policy = v;
     if (geti("RT_REFIT_WIDE", v)) k.refit_wide = v != 0;
     if (geti("RT_PARTS", v) && v >= 1 && v <= 8) k.parts = v;
     if (geti("RT_PART_PRIO", v)) k.part_prio = v != 0;

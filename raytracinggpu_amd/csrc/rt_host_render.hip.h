@@ -853,6 +853,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
         w.pv[j].anim = c.anim ? static_cast<rtk::AnimFrame *>(ctx->anim_dev.p) + j * rtk::kMaxBatch : nullptr;
         st.anyhit = (kn.anyhit && (c.work_dev == nullptr || t.qw)) ? 1 : 0;   // a run that counts the REFERENCE's work (the float-pair counting instantiation) traces every shadow ray to the end
         st.deadch = (st.anyhit && kn.dead_channels) ? 1 : 0;
+        st.policy = kn.stream_policy;
     }
     ctx->stats.lds_bytes = (int)t.lds; ctx->stats.block_threads = t.tb; ctx->stats.grid_blocks = (int)w.pv[0].tblocks; ctx->stats.parts = parts; ctx->stats.travq_mode = t.travq_mode;
     if ((rc = start_chains(ctx, c, w, qr_grown, own0)) != RT_OK) return rc;

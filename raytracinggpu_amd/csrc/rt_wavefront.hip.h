@@ -197,6 +197,8 @@ struct WfState {
                               // is M[i - s_rel * n_px].  (The field sits in what was padding before `batch`: no kernel's argument layout moves.)
     const BatchFrame *batch;  // rt_render_device_batch: n_batch frame descriptors in device memory (item i belongs to frame i / n_px); nullptr / 0 = the launch's own camera, seed, output
     int n_batch;
+    int policy;               // stream policy (kPol*, RT_STREAM_POLICY): which use-once streams of wf_advance go past the Infinity Cache; 0 = every access the plain instruction.  Wave-uniform;
+                              // only wf_advance_path reads it.  (The field sits in what was padding before `QR`: no kernel's argument layout moves.)
     // traversal queue: the rays in TRAVERSAL-SLOT order, so that the slots a traversal workgroup owns are contiguous and one
     // round trip brings flag and record
     float4 *QR;               // [2 slots] record of slot q: QR[2q] = (O.xyz, u.x), QR[2q+1] = (u.y, u.z, bits(W0), W1).  Y slot (ray r < n_paths): W0 = the path's
@@ -209,6 +211,23 @@ struct WfState {
                               // set there): a ray whose answer is cached (read), or is the first sample's ray of its pixel slot (fill, a later sample's item), gets its record without
                               // PQ_TRAV.  The next one, which closes them: the result word is X0[slot] (read), or M of the first sample's ray, which a first-sample item also stores (fill)
 };
+
+// THE STREAM POLICY (WfState::policy; DESIGN.md section 4 "which streams deserve the Infinity Cache", tools/stream_reuse.py).  The path state that one launch writes and the
+// next reads -- QR, M, DCH -- lives on hits of the 256 MiB Infinity Cache; a stream whose next use is a whole frame away cannot hit and only evicts it.  A set bit marks
+// the accesses of one such group non-temporal (__builtin_nontemporal_load / _store: the `nt` bit of the global instruction); a clear bit leaves the plain instruction.
+// The bit is wave-uniform (a kernel argument): a scalar branch around either form of the same access, never a different address or value.  Two groups are kept; the two
+// that were measured and taken out again (LS / SID of the segments folded out of reach, what a still view stores once): DESIGN.md section 11.
+constexpr int kPolRecords = 1;                               // the first-shade records wf_advance<kFormResume> loads: once per frame (a chain of one sample per pixel slot)
+constexpr int kPolPixels = 2;                                // the pixel store of the fold: no launch of the chain reads the frame
+typedef float pol_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 pol_load(const float4 *p, bool nt) {
+    if (nt) { const pol_f4 v = __builtin_nontemporal_load(reinterpret_cast<const pol_f4 *>(p)); return make_float4(v.x, v.y, v.z, v.w); }
+    return *p;
+}
+__device__ __forceinline__ void pol_store(float4 *p, float4 v, bool nt) {
+    if (nt) { pol_f4 w; w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w; __builtin_nontemporal_store(w, reinterpret_cast<pol_f4 *>(p)); }
+    else *p = v;
+}
 
 // n / d for 0 <= n < 2^32 with m = floor(2^32 / d) from the host: the estimate mulhi(n, m) is the quotient or one below it
 // (n * m / 2^32 > n / d - 1), so one correction makes it exact -- 5 vector instructions instead of the ~22 of an integer division.
@@ -815,6 +834,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
     constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
+    // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
+    // of the store (16 bytes of scratch) and keeps the plain one
+    constexpr bool POL_PIXELS = !(TEX && ANIM);
     const float4 kDead = make_float4(0, 0, 0, 0);                     // second half of a queue record without a ray (and, in a Y slot, without a path)
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
@@ -875,7 +897,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     if (RESUME) {
         if (!valid) { st.QR[2 * (size_t)qy + 1] = kDead; return; }       // as wf_advance<kFormFirst> leaves a pixel slot outside the frame
         if (sh.kill_x) st.QR[2 * (size_t)qx + 1] = kDead;
-        ra = sh.rec[2 * (size_t)(i - s_rel * st.n_px)]; rb = sh.rec[2 * (size_t)(i - s_rel * st.n_px) + 1];
+        // (a chain that traces several samples as items reads a slot's record once per sample in this one launch: not a use-once stream, the plain load)
+        const bool nt_rec = (st.policy & kPolRecords) != 0 && st.n_paths == st.n_px;
+        ra = pol_load(&sh.rec[2 * (size_t)(i - s_rel * st.n_px)], nt_rec); rb = pol_load(&sh.rec[2 * (size_t)(i - s_rel * st.n_px) + 1], nt_rec);
     }
 
     if (FIRST) {
@@ -1066,7 +1090,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             else { t.x += ans.x; t.y += ans.y; t.z += ans.z; }
             t.w += (float)nrays;
             const float n = fr.cam_mode == 1 ? 1.f : (float)fr.spp;
-            fr_out[out_index(fr, lrow, px)] = make_float4(t.x / n, t.y / n, t.z / n, t.w);
+            pol_store(&fr_out[out_index(fr, lrow, px)], make_float4(t.x / n, t.y / n, t.z / n, t.w), POL_PIXELS && (st.policy & kPolPixels) != 0);
         }
         // The path is over; its X slot keeps a record of an older launch, which no later one takes for its own.  (CLOSE: the chain is over too, and the store is dropped.
         // Whatever the Y slot's second half holds then -- a flag word without PQ_TRAV, so no traversal launch takes it for a ray -- the next chain of this part of the queue

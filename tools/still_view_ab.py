@@ -1,6 +1,7 @@
 """GPU box: what one level of the still view (csrc/rt_still.h) takes off a frame -- --knob RT_FIRST_HIT_CACHE (a still camera),
 RT_FIRST_SHADOW_CACHE or RT_FIRST_SHADE_CACHE (a still view under a still light) -- and whether a change of the host code moved a frame at all.  --knob RT_CHAIN_ENDS:
-the same steps for the kernel of a plain chain's last launch (csrc/rt_wavefront.hip.h CLOSE), which every frame runs, a still view or not.  --also V[,V] adds this
+the same steps for the kernel of a plain chain's last launch (csrc/rt_wavefront.hip.h CLOSE), which every frame runs, a still view or not.  --knob RT_STREAM_POLICY: the
+same steps for the cache policy of wf_advance's use-once streams (kPol*), on = both groups (the default), --also 1,2 each group alone.  --also V[,V] adds this
 build with the knob at each further value to the interleaved runs (an experimental build that knows more than on and off).
 
 For the headline frame and then for BASELINE config 2 (--width 512 --height 512 --spp 8), each step a process of its own under its own time limit, the first failure
@@ -22,7 +23,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CACHES = ["RT_FIRST_HIT_CACHE", "RT_FIRST_SHADOW_CACHE", "RT_FIRST_SHADE_CACHE"]
-KNOBS = CACHES + ["RT_CHAIN_ENDS"]
+KNOBS = CACHES + ["RT_CHAIN_ENDS", "RT_STREAM_POLICY"]
 ap = argparse.ArgumentParser()
 ap.add_argument("--knob", required=True, choices=KNOBS)
 ap.add_argument("--parent-lib", default="")
@@ -37,6 +38,7 @@ ap.add_argument("--spp", type=int, default=1)
 ap.add_argument("--bounces", type=int, default=3)
 args = ap.parse_args()
 KNOB = args.knob
+ON = "3" if KNOB == "RT_STREAM_POLICY" else "1"                       # the knob's value that turns on all there is
 
 
 def inproc():
@@ -83,7 +85,7 @@ def inproc():
         ctx.set_pipelining(False)
         return t0.elapsed_time(t1) / n
 
-    for knob in ("1", "0") if not os.environ.get("RT_LIB") else ("1",):
+    for knob in (ON, "0") if not os.environ.get("RT_LIB") else (ON,):
         os.environ[KNOB] = knob
         c = rt.Context(0)
         c.scene_upload(rt.scenes.spheres("cpu"), mesh)
