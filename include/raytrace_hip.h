@@ -378,6 +378,50 @@ typedef struct { float light[3]; float object[RT_MAX_OBJECTS][3]; } rt_shutter;
 int rt_scene_set_shutter(rt_ctx *ctx, const rt_shutter *shutter);
 int rt_scene_get_shutter(const rt_ctx *ctx, rt_shutter *out);
 
+/* --- ENVIRONMENT: a radiance map for the rays that miss the scene (ABI 6, additive).  No counterpart in the reference, whose room is closed: a miss is black there
+ *     (cpu:571).  The context may hold an environment: a square map of n x n texels, 1 <= n <= RT_MAX_ENVIRONMENT, each three binary32 radiances (on the device a float4,
+ *     16 B per texel).  The layout is octahedral with +y as the pole: the lookup needs no transcendental function and is bit for bit.  "Environment on": a map is set.  An
+ *     all-zero map is still on; a 1 x 1 map is a constant sky.
+ *     THE LOOKUP.  E = sky_radiance(u) for a ray direction u as the queue record holds it, not renormalised.  Binary32, one rounding per operation, no fused
+ *     multiply-add; the quotients are the correctly rounded ones (rt_div.h).  |v| is v with its sign bit cleared.
+ *       1. s = (|ux| + |uy|) + |uz|.  If s is not a finite number above 0 (NaN included): E = (+0, +0, +0).
+ *       2. px = ux / s, pz = uz / s.
+ *       3. If uy < 0:  qx = (1 - |pz|) * sg(px),  qz = (1 - |px|) * sg(pz),  sg(v) = v < 0 ? -1 : 1  (so sg(-0) = sg(+0) = 1; the products are formed).  Otherwise q = p
+ *          (uy = -0 and uy = +0 included).
+ *       4. a = qx * 0.5 + 0.5,  b = qz * 0.5 + 0.5: the product first.  The centre of the map is the zenith (+y), its corners are the nadir (-y), the left and right
+ *          mid-edges are -x and +x, the top mid-edge (row 0) is -z, the way the fixed camera looks, the bottom mid-edge +z.
+ *       5. sx = a * (float)n - 0.5,  sy = b * (float)n - 0.5: the product first.  Then the bilinear form of the textures on the float texels:
+ *          x0 = floor(sx), fx = sx - x0 (tex_floor), likewise y0, fy;  xa = clamp(x0), xb = clamp(x0 + 1) to [0, n - 1] (tex_wrap, RT_TEX_CLAMP), likewise ya, yb;
+ *          gx = 1 - fx, gy = 1 - fy;  per channel  E = (t[ya][xa] * gx + t[ya][xb] * fx) * gy + (t[yb][xa] * gx + t[yb][xb] * fx) * fy  -- tex_sample's expression.
+ *          Clamping at the border instead of wrapping to the octahedral neighbour is part of the rule: along the border of the map, which is the lower hemisphere's
+ *          fold lines from the horizon down to the nadir, the lookup is up to half a texel short of the interpolation a wrap would give.
+ *     The step is sky_radiance in rt_shade.hip.h; the model is tests/sky_model.py.
+ *     WHERE IT ENTERS.  When the close of a camera or continuation ray of segment d finds no object, the path's fold starts from ans = E instead of (0, 0, 0).
+ *     Everything else is as without a map: the ray counts (.w), the order of the fold, the sampling.  A path of no segments traces no ray and stays black.  The bounce ray
+ *     of the last segment is never built, so it meets no sky.  Shadow rays do not see the environment: it lights surfaces through the cosine bounces only.  The point
+ *     light is still there; intensity 0 gives a scene lit by the sky alone.  Mirrors and glass show the environment: their continuation rays are ordinary rays.
+ *     WHAT A TEXEL MAY BE.  Finite, sign bit clear, below 2^96: as an unsigned integer its bits are < 0x6f800000.  The bilinear sum stays finite and the dead-channel
+ *     elision exact.
+ *     rt_scene_set_environment(ctx, n, rgb): n * n * 3 floats, row 0 first; rgb == NULL or n == 0 removes the map.  rt_scene_get_environment(ctx, &n, rgb_or_NULL): n (0: no
+ *     map) and, if rgb is not NULL, the n * n * 3 floats as stored.  The map is host state plus one device buffer of the context's.  A frame captures the buffer when it is
+ *     enqueued and keeps it: replacing a map allocates a new buffer, and the old one is released after the frames that captured it.  rt_scene_upload* removes the
+ *     environment: it belongs to the scene.  The sphere, light, lens and shutter edits keep it.
+ *     RT_ERR_INVALID, the state untouched: n < 0 or n > RT_MAX_ENVIRONMENT, n > 0 with a NULL rgb, a texel that fails the bit test (NaN, +-inf, negative, -0, >= 2^96), a
+ *     NULL n of the get.  RT_ERR_NO_SCENE: no upload, or the last rt_scene_upload* failed.  A refused get writes nothing.
+ *     Environment on is rendered by every entry that runs wf_advance -- rt_render*, _device, _device_batch, _async, _pose*, rt_progressive_frame -- under the variants auto
+ *     (never lockstep), wavefront, wavefront_lds, wavefront_queue and lds_*, with several samples, row shares, RT_PARTS cuts and pipelining, with or without the lens, with
+ *     one light, a list of lights or lights with radii (a list without a radius renders through the soft forms with radii 0: the same light, bit for bit).
+ *     RT_ERR_UNSUPPORTED, outputs untouched, "environment" in the error text: rt_render_device_batch_scenes with scenes, rt_render_counts*, rt_count_work, the variants
+ *     path, lockstep and global, and every render while the shutter is on.
+ *     STILL VIEWS.  While the environment is on no chain fills or uses the first-hit, first-shadow or first-shade cache and none of their counters moves.  Setting,
+ *     replacing or removing a map empties all three.
+ *     FEATURE BUFFERS, rt_trace_rays, the filters and the SVGF sequence do not change: a pixel that sees the sky still has no object. */
+#define RT_MAX_ENVIRONMENT 1024
+int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb);
+int rt_scene_get_environment(const rt_ctx *ctx, int *n, float *rgb);
+/* known answers of the lookup: sky_radiance on n_dirs explicit directions (n_dirs x 3 in, n_dirs x 3 out) against the map the context holds; RT_ERR_INVALID without one */
+int rt_kat_environment(rt_ctx *ctx, int n_dirs, const float *dirs, float *rgb_out);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

@@ -665,6 +665,21 @@ public:
         check(rt_scene_get_shutter(ctx_, &s), "rt_scene_get_shutter");
         return s;
     }
+    // Environment (rt_scene_set_environment): an n x n octahedral map of radiances (n * n * 3 floats, row 0 first) for the rays that leave the scene; it lights the scene
+    // through the bounces.  clear_environment(): a miss is black again.  environment() -> {n, the floats as stored}; n == 0: no map
+    void set_environment(int n, const float *rgb) { check(rt_scene_set_environment(ctx_, n, rgb), "rt_scene_set_environment"); }
+    void set_environment(int n, const std::vector<float> &rgb) {
+        if (n < 0 || rgb.size() != (size_t)n * (size_t)n * 3) throw std::invalid_argument("set_environment: rgb holds n * n * 3 floats");
+        set_environment(n, rgb.data());
+    }
+    void clear_environment() { check(rt_scene_set_environment(ctx_, 0, nullptr), "rt_scene_set_environment"); }
+    std::pair<int, std::vector<float>> environment() {
+        int n = 0;
+        check(rt_scene_get_environment(ctx_, &n, nullptr), "rt_scene_get_environment");
+        std::vector<float> rgb((size_t)n * (size_t)n * 3);
+        if (n > 0) check(rt_scene_get_environment(ctx_, &n, rgb.data()), "rt_scene_get_environment");
+        return {n, rgb};
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

@@ -50,6 +50,8 @@ int64_t rth_still_replay(const int32_t *ev, int n_ev, uint64_t counts[12], int32
 int64_t rth_advance_form(int counting, int tex, int anim, int list, int lens, int lights, int adv);
 /* ... with the fact that came later: shutter (the shutter is on, rt_scene_set_shutter; bit 11 of the word).  shutter == 0 is rth_advance_form. */
 int64_t rth_advance_form_shutter(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int adv);
+/* ... and with the one after it: sky (the scene has an environment, rt_scene_set_environment; bit 12 of the word).  sky == 0 is rth_advance_form_shutter. */
+int64_t rth_advance_form_sky(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int adv);
 
 /* Test entries of the cut of a call's rows (csrc/rt_rowcut.h, shared with the render path).  rth_row_cut: n cases of seven numbers -- an rt_rows (row0, n_rows, tile_rows,
  * tile_step), the sub-frames wanted (RT_PARTS), one (a counting run: one sub-frame), whole (a batch cut by frames: every sub-frame holds all rows) -- each give 52 numbers:

@@ -42,7 +42,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_mesh_compute_normals", "rt_mesh_compute_normals_of", "rt_mesh_get_vertex_normals", "rt_mesh_snapshot_normals", "rt_mesh_normal_snapshot_mask",
            "rt_scene_set_lights", "rt_scene_get_lights", "rt_scene_set_light_at", "rt_scene_move_light_at",
            "rt_scene_set_light_radii", "rt_scene_get_light_radii", "rt_scene_set_light_radius_at",
-           "rt_camera_set_lens", "rt_camera_get_lens", "rt_scene_set_shutter", "rt_scene_get_shutter"]
+           "rt_camera_set_lens", "rt_camera_get_lens", "rt_scene_set_shutter", "rt_scene_get_shutter",
+           "rt_scene_set_environment", "rt_scene_get_environment", "rt_kat_environment"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -443,6 +444,9 @@ def load():
     L.rt_camera_get_lens.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rt_scene_set_shutter.argtypes = [vp, C.POINTER(Shutter)]
     L.rt_scene_get_shutter.argtypes = [vp, C.POINTER(Shutter)]
+    L.rt_scene_set_environment.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    L.rt_scene_get_environment.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    L.rt_kat_environment.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -773,6 +777,35 @@ class Context:
         s = Shutter()
         self._check(self._L.rt_scene_get_shutter(self._h, C.byref(s)))
         return np.array(s.light, np.float32), np.array([list(o) for o in s.object], np.float32)
+
+    # --- environment (rt_scene_set_environment): an octahedral radiance map for the rays that miss the scene
+    def set_environment(self, rgb=None):
+        """rt_scene_set_environment: rgb = an [n, n, 3] float32 array, row 0 first (environment.py makes them); None: the map is removed"""
+        if rgb is None:
+            self._check(self._L.rt_scene_set_environment(self._h, 0, None))
+            return
+        a = np.ascontiguousarray(rgb, dtype=np.float32)
+        if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 3:
+            raise ValueError(f"an environment is an [n, n, 3] array, not {a.shape}")
+        self._check(self._L.rt_scene_set_environment(self._h, int(a.shape[0]), a.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def environment(self):
+        """rt_scene_get_environment -> the [n, n, 3] float32 array as stored, or None without a map"""
+        n = C.c_int(0)
+        self._check(self._L.rt_scene_get_environment(self._h, C.byref(n), None))
+        if n.value == 0:
+            return None
+        out = np.empty((n.value, n.value, 3), np.float32)
+        self._check(self._L.rt_scene_get_environment(self._h, C.byref(n), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def kat_environment(self, dirs):
+        """rt_kat_environment: sky_radiance on [n, 3] explicit directions against the context's map -> [n, 3] float32"""
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros_like(d)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_kat_environment(self._h, int(d.shape[0]), d.ctypes.data_as(fp), out.ctypes.data_as(fp)))
+        return out
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

@@ -116,6 +116,7 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     ctx->snap_mask = 0;                                                  // ... and holds no vertex snapshot (rt_mesh_snapshot_vertices),
     ctx->nsnap_mask = 0; ctx->vnrm_mask = 0;                             // no normal snapshot and no computed vertex normals (rt_mesh_snapshot_normals, rt_mesh_compute_normals*)
     ctx->vcsr_valid = false;
+    ctx->env_n = 0; ctx->env_rgb.clear();                                // ... and has no environment (rt_scene_set_environment; the buffer stays for the frames in flight; the still view: below)
     ctx->still.shading_changed();
     ctx->still.mesh_changed();
     if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(ctx, RT_ERR_INVALID, "bad sphere array");

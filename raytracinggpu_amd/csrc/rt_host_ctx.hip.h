@@ -189,6 +189,12 @@ struct rt_ctx {
     // value.  shutter_on: some component is not +-0 -- every launch of every chain is then a kFormShutter form.  rt_scene_upload* closes it.
     rt_shutter shutter = {};
     bool shutter_on = false;
+    // The environment map (rt_scene_set_environment): env_n x env_n texels, host copy (3 floats each, row 0 first) and the device's (float4 each).  env_n == 0: no
+    // environment.  make_frame captures pointer and size by value; a new map gets a new buffer, and the old one is given back once no frame in flight can read it.
+    // rt_scene_upload* removes it: it belongs to the scene.
+    int env_n = 0;
+    std::vector<float> env_rgb;
+    DevBuf env{bufs};
     DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.

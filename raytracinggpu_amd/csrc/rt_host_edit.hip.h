@@ -239,6 +239,50 @@ int rt_scene_get_shutter(const rt_ctx *ctx, rt_shutter *out) {
     return RT_OK;
 }
 
+// ---- the environment map (raytrace_hip.h "environment"): host state plus one device buffer of the context's; make_frame captures pointer and size ----
+int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (n < 0 || n > RT_MAX_ENVIRONMENT) return fail(ctx, RT_ERR_INVALID, "environment: n %d outside [0,%d]", n, RT_MAX_ENVIRONMENT);
+    if (n > 0 && !rgb) return fail(ctx, RT_ERR_INVALID, "environment: rgb is NULL with n %d", n);
+    if (n == 0 || !rgb) {                                                // removed (the buffer stays until the next map: frames in flight may read it)
+        if (ctx->env_n > 0) ctx->still.sky_changed();
+        ctx->env_n = 0; ctx->env_rgb.clear();
+        return RT_OK;
+    }
+    const size_t count = (size_t)n * (size_t)n;
+    std::vector<float4> texels(count);
+    for (size_t k = 0; k < count; ++k) {
+        for (int a = 0; a < 3; ++a) {
+            uint32_t bits;
+            memcpy(&bits, &rgb[3 * k + a], sizeof(bits));
+            // finite, sign bit clear, below 2^96: the bilinear sum stays finite and the dead-channel elision exact (rt_wavefront.hip.h wf_dead_channels)
+            if (bits >= rtk::kDeadDirectEnd)
+                return fail(ctx, RT_ERR_INVALID, "environment: texel (%d, %d) channel %d is %g: a radiance is finite, has a clear sign bit and is below 2^96", (int)(k % n), (int)(k / n), a, (double)rgb[3 * k + a]);
+        }
+        texels[k] = make_float4(rgb[3 * k], rgb[3 * k + 1], rgb[3 * k + 2], 0.f);
+    }
+    // A new map gets a new buffer; the old one is given back after the frames that captured it (the rule of rt_mesh_set_texture_of: the device is idle first)
+    DevBuf fresh;
+    if (int rc = upload(ctx, fresh, texels.data(), count * sizeof(float4)); rc != RT_OK) return rc;
+    RT_HIP(ctx, hipDeviceSynchronize());
+    ctx->env = std::move(fresh);
+    ctx->env_rgb.assign(rgb, rgb + 3 * count);
+    ctx->env_n = n;
+    ctx->still.sky_changed();
+    return RT_OK;
+}
+
+int rt_scene_get_environment(const rt_ctx *ctx, int *n, float *rgb) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!n) return fail(c, RT_ERR_INVALID, "n is NULL");
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    *n = ctx->env_n;
+    if (rgb && ctx->env_n > 0) memcpy(rgb, ctx->env_rgb.data(), ctx->env_rgb.size() * sizeof(float));
+    return RT_OK;
+}
+
 int rt_scene_get_sphere(const rt_ctx *ctx, int object_slot, rt_sphere *out) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
     rt_ctx *c = const_cast<rt_ctx *>(ctx);

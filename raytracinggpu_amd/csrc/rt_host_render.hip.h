@@ -26,12 +26,16 @@ bool lights_soft(const rt_ctx *ctx) {
 // While the scene holds several lights, or a light with a radius, only the kernels that take the table may render it: every other entry refuses (outputs untouched)
 // wf_chain: the caller is a frame's own chain of wf_advance launches, which takes all of the above -- but not the shutter together with a light list or a radius: the four
 // shutter forms are built for the Scene's one point light
+// The environment (rt_scene_set_environment) is rendered by the chain's four kFormSky forms alone: not with the shutter on, and by no other entry
 int lights_refuse(rt_ctx *ctx, const char *what, bool wf_chain = false) {
     if (wf_chain) {
+        if (ctx && ctx->env_n > 0 && ctx->shutter_on)
+            return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene has an environment and the shutter is on; no wf_advance form takes both (rt_scene_set_environment)", what);
         if (ctx && ctx->shutter_on && (ctx->n_lights > 1 || lights_soft(ctx)))
             return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the shutter is on and the scene holds several lights or a light with a radius; no wf_advance form takes both (rt_scene_set_shutter)", what);
         return RT_OK;
     }
+    if (ctx && ctx->env_n > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene has an environment; only wf_advance's sky forms meet it (rt_scene_set_environment)", what);
     // ... and while the shutter is on, only a chain of the shutter forms may render it
     if (ctx && ctx->shutter_on) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the shutter is on; only wf_advance's shutter forms move the scene within a frame (rt_scene_set_shutter)", what);
     if (ctx && ctx->n_lights > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene holds %d lights; only wf_advance takes more than one (rt_scene_set_lights)", what, ctx->n_lights);
@@ -156,7 +160,7 @@ Variant ask_variant(const rt_ctx *ctx, int variant, const rt_camera_pose *pose, 
     // 0.220 ms per frame (profiles/round5/ab_spheres_only.txt).  A posed camera exists in the wavefront family only.
     if (variant == RT_VARIANT_AUTO) {
         const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1 && !lights_soft(ctx) &&
-                              !(ctx->lens_radius > 0.f) && !ctx->shutter_on;
+                              !(ctx->lens_radius > 0.f) && !ctx->shutter_on && ctx->env_n == 0;
         variant = lockstep ? RT_VARIANT_LOCKSTEP : RT_VARIANT_WAVEFRONT_QUEUE;
     }
     // BASELINE config 4 / north star: "hot triangle vertices and top BVH levels staged in LDS" = the work-stack traversal kernel
@@ -206,6 +210,7 @@ struct Chunk {
     rtk::WfLens lens{};                                               // lens.radius > 0: the camera has a lens -- the argument of wf_advance<kFormFirst | kFormLens>, the opening launch of every chain
     rtk::WfShutter shutter{};                                         // shutter_on: the shutter motion -- the argument of every wf_advance launch of the chunk (the kFormShutter forms)
     bool shutter_on = false;
+    rtk::WfSky sky{};                                                 // sky.n > 0: the scene has an environment -- the argument of the chunk's kFormSky launches (every one after the opening)
 };
 void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Chunk &c) {
     const rt_params *p = c.p;
@@ -237,6 +242,7 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
             c.shutter.sph[k] = c.shutter.obj[slot] = make_float4(m.object[slot][0], m.object[slot][1], m.object[slot][2], 0.f);
         }
     }
+    c.sky = rtk::WfSky{ctx->env_n > 0 ? static_cast<const float4 *>(ctx->env.p) : nullptr, ctx->env_n};   // (rt_scene_set_environment) the map's buffer as it is now: a new map gets a new one
     c.soft = lights_soft(ctx);
     if (ctx->n_lights > 1 || c.soft) {                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
         rtk::WfLights &lt = c.sl.lt;
@@ -538,9 +544,10 @@ hipStream_t chain_stream(const rt_ctx *ctx, const Chunk &c, bool own0, int j);
 // by nobody: a counting run and a frame under rt_stats_enable trace every launch, so that their counters and their event brackets describe the full chain.
 // A camera with a lens (rt_camera_set_lens) draws a lens point per sample: its camera ray depends on the sample whatever sigma is.  Such a chunk is not only ineligible: its
 // chains stay away from the still view altogether (launch_wavefront, enqueue_chain), so that no level is filled or used and no counter moves.
-// The same holds while the shutter is on (rt_scene_set_shutter): a path's spheres and light depend on its sample.
+// The same holds while the shutter is on (rt_scene_set_shutter): a path's spheres and light depend on its sample.  And under an environment (rt_scene_set_environment): the
+// records know no miss that shines and no sky form resumes from them.  (The first-hit level would stay valid; DESIGN.md section 5.21 keeps that for later.)
 bool still_eligible(const rt_ctx *ctx, const Chunk &c, const TravPlan &t) {
-    return !(c.lens.radius > 0.f) && !c.shutter_on && ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
+    return !(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
            ctx->knobs.debug_trav == -2;
 }
 // What the camera rays' hits depend on besides the mesh, bit for bit (the RAY KEY), and what segment 0's shading and shadow rays depend on besides the ray key and what is
@@ -704,12 +711,12 @@ int end_chains(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool own0) {
 
 // What a chain's wf_advance launches may take beyond (Scene, Frame, WfState): each form takes the ones its bits name (rt_still.h kForm*), in this order (sl.lt: the table of
 // the forms without radii)
-struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; };
+struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; rtk::WfSky sky{}; };
 struct AdvLaunch {
     dim3 grid, block; hipStream_t q; const rtk::Scene &scn; const rtk::Frame &fr; const rtk::WfState &st;
     template <unsigned FORM, class... Extra> void go(const Extra &... extra) const { hipLaunchKernelGGL((rtk::wf_advance<FORM, Extra...>), grid, block, 0, q, scn, fr, st, extra...); }
 };
-// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 25 instantiations, one case each (DESIGN.md section 5.2 says who launches
+// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 29 instantiations, one case each (DESIGN.md section 5.2 says who launches
 // each and which test runs it).  The entries refuse what has no form before a chain is planned (lights_refuse, resolve_variant), so the default is not reached.
 int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_t q, const rtk::Scene &scn, const rtk::Frame &fr, const rtk::WfState &st, const AdvArgs &a) {
     using namespace rtk;
@@ -726,6 +733,10 @@ int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_
     case kFormFirst | kFormLens | kFormShutter: l.go<kFormFirst | kFormLens | kFormShutter>(a.ln, a.shu); break;
     case kFormShutter: l.go<kFormShutter>(a.shu); break;
     case kFormTex | kFormShutter: l.go<kFormTex | kFormShutter>(a.ts, a.shu); break;
+    case kFormSky: l.go<kFormSky>(a.sky); break;
+    case kFormTex | kFormSky: l.go<kFormTex | kFormSky>(a.ts, a.sky); break;
+    case kFormSoft | kFormSky: l.go<kFormSoft | kFormSky>(a.sl, a.sky); break;
+    case kFormTex | kFormSoft | kFormSky: l.go<kFormTex | kFormSoft | kFormSky>(a.ts, a.sl, a.sky); break;
     case kFormTex | kFormAnim: l.go<kFormTex | kFormAnim>(a.ts, a.anim); break;
     case kFormTex | kFormList: l.go<kFormTex | kFormList>(a.ts, a.list); break;
     case kFormFirst | kFormStats: l.go<kFormFirst | kFormStats>(); break;
@@ -753,19 +764,19 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     if (pt.st.n_paths == 0) return RT_OK;
     // the chain's facts: with the step they decide the form of each wf_advance launch (rt_still.h adv_form)
     const bool anim = c.batch && c.anim;                          // an animated batch: the frames' lights and spheres too
-    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on};
+    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on, c.sky.n > 0};
     const dim3 pg(pt.pblocks), pb(kn.adv_block);
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
     const rtk::QRows win_y = rtk::qrows_y(pt.st.n_paths, pt.st.log2S, pt.st.Q);
-    // (the camera has a lens: the chain opens with the lens form and knows no still view; nor does a chain of the shutter forms)
-    const rtk::StillChain sc = (facts.lens || facts.shutter) ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
+    // (the camera has a lens: the chain opens with the lens form and knows no still view; nor does a chain of the shutter forms, nor one of the sky forms)
+    const rtk::StillChain sc = (facts.lens || facts.shutter || facts.sky) ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
     // the plain chain takes the closing kernel at its last position
     const bool plain = t.queue && rtk::adv_plain_chain(facts);
     const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0, plain && kn.chain_ends != 0);
     auto block = [&](const DevBuf &b) { return static_cast<unsigned long long *>(b.p) + pt.pxbase; };   // the part's block of a level
     AdvArgs aa;
-    aa.anim = pt.anim; aa.sl = c.sl; aa.ln = c.lens; aa.shu = c.shutter;
+    aa.anim = pt.anim; aa.sl = c.sl; aa.ln = c.lens; aa.shu = c.shutter; aa.sky = c.sky;
     if (sc.records != rtk::kStillOff) { aa.sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; aa.sh.kill_x = plan.kill_x; }
     if (facts.tex) { aa.ts = tex_scene(ctx); aa.ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg; }   // ALB[d * n_paths + i] inside the part's block, as LS
     pt.st.nonce = (int)(++ctx->chain_nonce[j] & (unsigned)rtk::PQ_NONCE_MASK);
@@ -857,7 +868,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
     }
     ctx->stats.lds_bytes = (int)t.lds; ctx->stats.block_threads = t.tb; ctx->stats.grid_blocks = (int)w.pv[0].tblocks; ctx->stats.parts = parts; ctx->stats.travq_mode = t.travq_mode;
     if ((rc = start_chains(ctx, c, w, qr_grown, own0)) != RT_OK) return rc;
-    if (!(c.lens.radius > 0.f) && !c.shutter_on) still_begin(ctx, c, t, w, own0);
+    if (!(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0)) still_begin(ctx, c, t, w, own0);
     // The chains of ONE sample chunk are issued for all sub-frames before the next chunk's.
     // (Rounds 2-4 issued all chunks of sub-frame 0 first: with hundreds of chains the host was still feeding stream 0 while stream 1 sat empty, the
     // sub-frames ran one after the other instead of side by side, and a 256-sample 1080p frame cost 1.26 ms per sample against 0.94 at 32 samples --

@@ -173,6 +173,14 @@ __global__ __launch_bounds__(256) void kat_mesh_kernel(const Scene sc, const flo
     }
 }
 
+// in: u[3]; out: E[3] = sky_radiance(u) of the map the context holds (the lookup of wf_advance's kFormSky forms, on explicit directions)
+__global__ __launch_bounds__(256) void kat_sky_kernel(const WfSky sky, const float *__restrict__ in, int n, float *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 E = sky_radiance(sky, mk(in[3 * (size_t)i], in[3 * (size_t)i + 1], in[3 * (size_t)i + 2]));
+    out[3 * (size_t)i] = E.x; out[3 * (size_t)i + 1] = E.y; out[3 * (size_t)i + 2] = E.z;
+}
+
 }  // namespace rtk
 
 namespace {
@@ -240,6 +248,14 @@ int rt_kat_mesh(rt_ctx *ctx, const float *in, int n, float tri_tmin, int route, 
     if (route < 0 || route > 1) return fail(ctx, RT_ERR_INVALID, "route must be 0 (work-stack primitives) or 1 (stackless mesh_intersect)");
     return kat_run(ctx, in, n, 6, out, 5, counts, [&](const float *di, float *dres, unsigned long long *dc, dim3 g, dim3 b) {
         hipLaunchKernelGGL(rtk::kat_mesh_kernel, g, b, 0, own_stream(ctx), ctx->scene, di, n, tri_tmin, route, dres, dc);
+    });
+}
+
+int rt_kat_environment(rt_ctx *ctx, int n_dirs, const float *dirs, float *rgb_out) {
+    if (ctx && !ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (ctx && ctx->env_n <= 0) return fail(ctx, RT_ERR_INVALID, "the scene has no environment (rt_scene_set_environment)");
+    return kat_run(ctx, dirs, n_dirs, 3, rgb_out, 3, nullptr, [&](const float *di, float *dres, unsigned long long *, dim3 g, dim3 b) {
+        hipLaunchKernelGGL(rtk::kat_sky_kernel, g, b, 0, own_stream(ctx), rtk::WfSky{static_cast<const float4 *>(ctx->env.p), ctx->env_n}, di, n_dirs, dres);
     });
 }
 

@@ -83,6 +83,54 @@ __device__ __forceinline__ void lens_ray(const Frame &fr, float R, float f, uint
 __device__ __forceinline__ float shutter_time(uint32_t hs) { return uniform01(hs, 1u << 28, 2); }
 __device__ __forceinline__ f3 shutter_pose(f3 C, f3 d, float tau) { return mk(C.x + d.x * tau, C.y + d.y * tau, C.z + d.z * tau); }
 
+// ---- texel coordinates (the textures of rt_wavefront.hip.h and the environment map below) ----
+// floor of a texel coordinate as an int, and the fraction c - floor(c).  A coordinate outside [-2^31, 2^31) -- NaN and +-inf included -- is index 0 with fraction 0.
+__device__ __forceinline__ int tex_floor(float c, float &frac) {
+    const bool ok = c >= -2147483648.f && c < 2147483648.f;
+    const float f = floorf(c);
+    frac = ok ? c - f : 0.f;
+    return ok ? (int)f : 0;
+}
+__device__ __forceinline__ int tex_wrap(int i, int n, int wrap) {
+    if (wrap != 0) return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);        // clamp
+    const int r = i % n;                                               // repeat: non-negative modulo
+    return r < 0 ? r + n : r;
+}
+
+// The ENVIRONMENT (rt_scene_set_environment; the rule: raytrace_hip.h "environment"): the radiance a ray of direction u meets when it leaves the scene.  The map is n x n
+// float4 texels (w unused), octahedral with +y as the pole: no transcendental function, every operation one binary32 rounding, the two quotients correctly rounded
+// (rt_div.h: one reciprocal for both, the literal divisions outside its range).  Bilinear in tex_sample's form, clamped at the border.  A direction whose 1-norm is not a
+// finite number above 0 meets nothing: +0.  The map is small and read again and again: plain loads, no stream policy.  (n <= 1024: the index mask says so to the compiler.)
+struct WfSky { const float4 *texels; int n; };
+__device__ __forceinline__ f3 sky_radiance(const WfSky &sky, f3 u) {
+    const float s = (fabsf(u.x) + fabsf(u.y)) + fabsf(u.z);
+    if (!(s > 0.f && s < __builtin_inff())) return mk(0.f, 0.f, 0.f);
+    const bool fast = div_in_range(u.x) && div_in_range(u.z) && div_in_range(s);
+    const float r1 = div_refine(s, __builtin_amdgcn_rcpf(s));
+    float px = div_by(u.x, s, r1), pz = div_by(u.z, s, r1);
+    if (__builtin_expect(__ballot(!fast) != 0ull, 0)) {
+        if (!fast) { px = u.x / s; pz = u.z / s; }
+    }
+    float qx = px, qz = pz;
+    if (u.y < 0.f) {                                                   // the lower hemisphere folds outwards, to the corners
+        qx = (1.f - fabsf(pz)) * (px < 0.f ? -1.f : 1.f);
+        qz = (1.f - fabsf(px)) * (pz < 0.f ? -1.f : 1.f);
+    }
+    const float a = qx * 0.5f + 0.5f, b = qz * 0.5f + 0.5f;            // [0, 1]: the centre is the zenith, row 0 is -z
+    const int n = sky.n;
+    const float nf = (float)n;
+    float fx, fy;
+    const int x0 = tex_floor(a * nf - 0.5f, fx), y0 = tex_floor(b * nf - 0.5f, fy);
+    const int xa = tex_wrap(x0, n, 1), xb = tex_wrap(x0 + 1, n, 1), ya = tex_wrap(y0, n, 1), yb = tex_wrap(y0 + 1, n, 1);
+    constexpr unsigned kMask = (1u << 20) - 1;                         // n * n - 1 at n = 1024
+    const float4 t00 = sky.texels[(unsigned)(ya * n + xa) & kMask], t10 = sky.texels[(unsigned)(ya * n + xb) & kMask];
+    const float4 t01 = sky.texels[(unsigned)(yb * n + xa) & kMask], t11 = sky.texels[(unsigned)(yb * n + xb) & kMask];
+    const float gx = 1.f - fx, gy = 1.f - fy;
+    return mk((t00.x * gx + t10.x * fx) * gy + (t01.x * gx + t11.x * fx) * fy,
+              (t00.y * gx + t10.y * fx) * gy + (t01.y * gx + t11.y * fx) * fy,
+              (t00.z * gx + t10.z * fx) * gy + (t01.z * gx + t11.z * fx) * fy);
+}
+
 // ---- the hit ----
 // alpha, beta, gamma of triangle `tri` (visit order) for the ray (O, u): get_smooth_normal's expressions (realtime_render.cu:221-245).  The smooth normal, the
 // texture lookup (tex_albedo, rt_wavefront.hip.h) and rt_kat_surface read these.

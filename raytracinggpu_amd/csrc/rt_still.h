@@ -16,7 +16,7 @@
 //   - Keys are compared as bits: the caller zeroes its key's padding and puts the whole Scene in.  A wrong miss costs a refill, a wrong hit a silently wrong frame.  (StillKey::same)
 //   - What lives behind a pointer of the keys and is edited in place reaches them through two generation counters.                    (mesh_changed, shading_changed)
 //   - The eligibility levels nest: 0 none, 1 hit, 2 hit + shadow, 3 all three.  Chains of level 0 count as ineligible and touch nothing else; the list chains of
-//     rt_render_counts* do not come here at all, nor do the chains of a frame whose camera has a lens or whose shutter is on (lens_changed).   (begin, chain)
+//     rt_render_counts* do not come here at all, nor do the chains of a frame whose camera has a lens, whose shutter is on or whose scene has an environment (lens_changed).   (begin, chain)
 // Plain C++: the library and the host library (rth_still_replay, tests/test_still_view_model.py) compile the same text.
 #pragma once
 #include <stdint.h>
@@ -78,6 +78,9 @@ struct StillView {
     void lens_changed() { ++mesh_gen; }
     // rt_scene_set_shutter turning the shutter on or off: the same, for the same reason (a shutter frame's chains do not come here either)
     void shutter_changed() { ++mesh_gen; }
+    // rt_scene_set_environment setting, replacing or removing the map: the same again (a chain under an environment does not come here; a replaced map between two such
+    // frames costs the next frame without one nothing more than the refill it owes anyway)
+    void sky_changed() { ++mesh_gen; }
 
     // Before a chunk's chains are enqueued, after their streams are settled.  level: what the chunk is eligible for; the keys are read up to that level only; M0 / X0 / S0: where
     // the three buffers are now.  Any difference from what a level was stored under empties it and every level above.
@@ -172,16 +175,17 @@ inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool 
 // and the bits that bring the kernel an extra argument -- tex: textured meshes (TexScene); anim: a frame of an animated batch (const AnimFrame *__restrict__); list: the items
 // are (pixel slot, sample) records (WfList); fill / resume: stores the first-shade records / opens a chain from them (WfShade); lights: several point lights (WfLights); soft:
 // lights with a radius (WfSoftLights; in place of lights, never both); lens: the thin lens, with first (WfLens); shutter: the spheres and the light at the sample's own
-// time (WfShutter), in every launch of the chain
+// time (WfShutter), in every launch of the chain; sky: a ray that misses meets the environment map (WfSky), in every launch after the opening one -- its extra comes last
 constexpr unsigned kFormStats = 1u << 0, kFormFirst = 1u << 1, kFormTex = 1u << 2, kFormAnim = 1u << 3, kFormList = 1u << 4, kFormFill = 1u << 5, kFormResume = 1u << 6,
-                   kFormLights = 1u << 7, kFormSoft = 1u << 8, kFormLens = 1u << 9, kFormClose = 1u << 10, kFormShutter = 1u << 11;
+                   kFormLights = 1u << 7, kFormSoft = 1u << 8, kFormLens = 1u << 9, kFormClose = 1u << 10, kFormShutter = 1u << 11, kFormSky = 1u << 12;
 constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks for this launch, and no kernel exists for it
 
 // What decides the form besides the step: the chain's facts.  counting: rt_count_work; anim: a batch with per-frame scenes; list: rt_render_counts*; lights: 0 the Scene's
-// one point light, 1 several, 2 some with a radius; shutter: the shutter is on (rt_scene_set_shutter) -- last and defaulted: a chain without one is written as before
-struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; };
+// one point light, 1 several, 2 some with a radius; shutter: the shutter is on (rt_scene_set_shutter) -- defaulted: a chain without one is written as before; sky: the scene has an
+// environment (rt_scene_set_environment) -- last and defaulted, for the same reason
+struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; };
 // The plain chain -- every launch after the opening one the form 0 or kFormStats (or the launch that stores the records): still_plan's `ends`, for a work-stack chain
-inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter; }
+inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky; }
 // The form of the launch a chain of these facts enqueues for `adv` (StillAdv: StillPlan::open for the opening launch, StillStep::adv for the later ones)
 inline unsigned adv_form(const AdvFacts &f, int adv) {
     // counting, a list and an animated batch exclude one another, and each refuses several lights, a radius and the lens before a chain is planned (lights_refuse)
@@ -189,6 +193,15 @@ inline unsigned adv_form(const AdvFacts &f, int adv) {
     if (f.lights < 0 || f.lights > 2 || special > 1 || (special == 1 && (f.lights != 0 || f.lens))) return kFormNotBuilt;
     // The shutter: every launch of the chain forms the sample's pose, so every launch has the bit.  Built for a frame of one point light alone: counting, a list, an
     // animated batch, several lights and a radius refuse it (lights_refuse); no still view (no records), and the closing kernel reads the Scene's L: not a plain chain
+    // The environment: a ray meets it where it is closed, so the opening launch is what it was and every later launch has the bit.  Counting, a list, an animated batch and
+    // the shutter refuse it (lights_refuse); no still view (no fill, no resume), and the closing kernel closes no continuation ray: not a plain chain.  A light list without
+    // a radius goes through the soft forms with radii 0 (a radius-0 light is the light itself, bit for bit): four later forms, not six
+    if (f.sky) {
+        if (special != 0 || f.shutter) return kFormNotBuilt;
+        if (adv == kAdvBegin) return kFormFirst | (f.lens ? kFormLens : 0u);
+        if (adv == kAdvPlain) return (f.tex ? kFormTex : 0u) | (f.lights != 0 ? kFormSoft : 0u) | kFormSky;
+        return kFormNotBuilt;
+    }
     if (f.shutter) {
         if (special != 0 || f.lights != 0) return kFormNotBuilt;
         if (adv == kAdvBegin) return kFormFirst | (f.lens ? kFormLens : 0u) | kFormShutter;

@@ -94,7 +94,9 @@ __device__ __forceinline__ float wf_anyhit_bound(f3 Pa, float nl) {
 //       bits <= 0x3f800000 and < 0x6f800000, which rules out negative numbers, -0, inf and every NaN at once.  A segment that fails clears the mask (wf_dead_channels): kills
 //       before it are forgotten, so a run of segments from the earliest kill in use to the last elided segment after it holds guarded segments only.
 //   (2) inside such a run the two chains differ by the elided direct terms alone, and what enters the run from below (Z, the ans of the segment after it) is the same in
-//       both: deeper runs hand up what they were handed (each channel passes a kill of its own run).  Z non-finite: both chains carry an inf of one sign or a NaN through the
+//       both: deeper runs hand up what they were handed (each channel passes a kill of its own run), and below the deepest run Z is what the fold starts from -- +0, or
+//       under an environment the E the path's last ray met (sky_radiance), computed at the miss from the ray alone, before and apart from any elision: the same in both
+//       chains too, and finite with a clear sign bit (every texel lies in [+0, 2^96), rt_scene_set_environment, and the four bilinear weights lie in [0, 1]: the sum stays below 2^98).  Z non-finite: both chains carry an inf of one sign or a NaN through the
 //       run (alb Z is the same product in both, a finite direct term changes neither), so x is non-finite in both.  Z finite: a product with an albedo <= 1 cannot
 //       overflow, and a sum cannot either -- a direct term below 2^96 / pi is less than half an ulp of anything from 2^127 on and leaves it as it is, and below 2^127 the
 //       sum stays below 2^127 + 2^96 -- so x is finite in both and the dead channels are +0 in both.  Above the run the two chains fold the same numbers.
@@ -650,18 +652,7 @@ struct TexScene {
     float4 *ALB;                             // albedo of textured diffuse segment d of path i: ALB[d * n_paths + i]
     int mask;                                // bit k: object k is a textured mesh
 };
-// floor of a texel coordinate as an int, and the fraction c - floor(c).  A coordinate outside [-2^31, 2^31) -- NaN and +-inf included -- is index 0 with fraction 0.
-__device__ __forceinline__ int tex_floor(float c, float &frac) {
-    const bool ok = c >= -2147483648.f && c < 2147483648.f;
-    const float f = floorf(c);
-    frac = ok ? c - f : 0.f;
-    return ok ? (int)f : 0;
-}
-__device__ __forceinline__ int tex_wrap(int i, int n, int wrap) {
-    if (wrap != 0) return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);        // clamp
-    const int r = i % n;                                               // repeat: non-negative modulo
-    return r < 0 ? r + n : r;
-}
+// (tex_floor and tex_wrap, the texel coordinate's floor and its wrap, are in rt_shade.hip.h: the environment map's lookup shares them)
 __device__ __forceinline__ f3 tex_texel(const TexDesc &td, int x, int y) {
     const uint8_t *p = td.texels + ((size_t)y * (size_t)td.w + (size_t)x) * (size_t)td.ch;
     return mk(td.decode[p[0]], td.decode[p[1]], td.decode[p[2]]);
@@ -709,8 +700,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #define ADV_MARK(name) do { } while (0)
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
-// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones)
-#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
+// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -824,15 +815,18 @@ __device__ __forceinline__ f3 wf_xyz(float4 v) { return mk(v.x, v.y, v.z); }
 // and lost: DESIGN.md section 11.)
 // THE FORM (rt_still.h kForm*): one word says which of the above a launch compiles in, and the kernel's extra arguments follow from it -- after (sc, fr, st) a kernel takes,
 // in this order, the TexScene (kFormTex), the AnimFrame table (kFormAnim), the WfList (kFormList), the WfShade (kFormFill, kFormResume), the WfLights (kFormLights) or the
-// WfSoftLights (kFormSoft), the WfLens (kFormLens), the WfShutter (kFormShutter), each only if its bit is set.  The path takes all eight; what a form does not take it never
-// reads (the kernel below passes an empty one or null).
+// WfSoftLights (kFormSoft), the WfLens (kFormLens), the WfShutter (kFormShutter), the WfSky (kFormSky), each only if its bit is set.  The path takes all nine; what a form
+// does not take it never reads (the kernel below passes an empty one or null).
+// THE ENVIRONMENT (rt_scene_set_environment; the rule: raytrace_hip.h "environment", the lookup: sky_radiance in rt_shade.hip.h).  A miss is seen in one place, the close of
+// a continuation ray; a path that misses emits nothing more and folds in the same launch, so the radiance it met lives in registers from the miss to the fold, which
+// starts from it instead of from black (SKY: the later launches' forms kFormSky, with and without textures and the soft lights' table).  No path state grows.
 using AnimTable = const AnimFrame *__restrict__;                      // (the qualifier is part of the kernel's parameter type: without it the loads of wf_advance<kFormTex | kFormAnim> come in another order)
 template <unsigned FORM>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim,
                                                 const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln,
-                                                const WfShutter *__restrict__ shu) {
+                                                const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky) {
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
-    constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter;
+    constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter, SKY = FORM & kFormSky;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
     // of the store (16 bytes of scratch) and keeps the plain one
@@ -853,6 +847,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     float x_bound = -__builtin_inff();                                // any-hit bound of the shadow ray (wf_anyhit_bound)
     bool x_moot = false;                                              // the shadow ray's answer cannot reach the pixel (direct term +0 either way, or every channel dead)
     f3 Oy = mk(0, 0, 0), uy = mk(0, 0, 1), Ox = mk(0, 0, 0), ux = mk(0, 0, 1);
+    f3 E = mk(0, 0, 0);                                               // (SKY) what the path's last ray met beyond the scene: the fold starts from it
     int px, lrow; bool valid;
     int s_rel = 0;
     if (st.n_paths != st.n_px) s_rel = wf_div(i, st.n_px, st.n_px_m);
@@ -965,7 +960,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     if (mesh_beats_sphere(t_min, win, tm, mobj)) { t_min = tm; win = mobj; tri_win = (int)(unsigned int)m; }   // a tie goes to whichever comes first in Scene::objects (no sphere: win = -1, 1e9 > tm)
                 }
             }
-            if (win >= 0) {                                           // a miss is black (cpu:571): nothing to emit
+            if (win >= 0) {                                           // a miss emits nothing: black (cpu:571), or under an environment E below
                 const f3 P = O + t_min * u;                           // cpu:560
                 Bary bary{0.f, 0.f, 0.f};                             // (TEX) the smooth normal's barycentrics, shared with the texture lookup
                 bool have_bary = false;
@@ -1051,6 +1046,8 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     emitY = true; Oy = O; uy = u;                     // continuation ray of segment d+1
                     nrays += 1;
                 }
+            } else if constexpr (SKY) {
+                E = sky_radiance(*sky, u);                            // the environment, in the direction the record holds
             }
             st.SID[(size_t)d * st.n_paths + i] = (unsigned char)sid;
             d = d + 1;
@@ -1062,7 +1059,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         ADV_MARK("fold_begin");
         if (FILL && s_rel == 0)                                       // no shadow ray left: a miss, or a specular hit of a one-segment path
             wf_shade_store(sh, i, sh_kind, shO, shV, 0.f, 0xff, sh_kind == kShadeSpecular ? refr_code : 0, 0, sh_kind == kShadeMiss ? nrays : sh_rays);
-        f3 ans = mk(0, 0, 0);
+        f3 ans = SKY ? E : mk(0, 0, 0);
         bool fold_sure = true;                                        // (counting instantiation) every folded segment passed wf_fold_bounded
         const int nseg = d < fr.segs ? d : fr.segs;
         for (int k = nseg - 1; k >= 0; --k) {
@@ -1169,13 +1166,14 @@ __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene s
     static_assert(adv_takes<TexScene, Extra...> == ((FORM & kFormTex) != 0) && adv_takes<AnimTable, Extra...> == ((FORM & kFormAnim) != 0) &&
                   adv_takes<WfList, Extra...> == ((FORM & kFormList) != 0) && adv_takes<WfShade, Extra...> == ((FORM & (kFormFill | kFormResume)) != 0) &&
                   adv_takes<WfLights, Extra...> == ((FORM & kFormLights) != 0) && adv_takes<WfSoftLights, Extra...> == ((FORM & kFormSoft) != 0) &&
-                  adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0),
+                  adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0) &&
+                  adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0),
                   "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths)
         wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
-                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...));
+                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...));
     wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 

@@ -202,7 +202,10 @@ ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
            "wf_advance_soft": (("soft",), False), "wf_advance_tex_soft": (("tex", "soft"), False), "wf_advance_lens": (("first", "lens"), False),
            # the shutter (WfShutter): the two opening launches and the two later ones, whole (they plant no labels either)
            "wf_advance_shutter_first": (("first", "shutter"), False), "wf_advance_lens_shutter_first": (("first", "lens", "shutter"), False),
-           "wf_advance_shutter": (("shutter",), False), "wf_advance_tex_shutter": (("tex", "shutter"), False)}
+           "wf_advance_shutter": (("shutter",), False), "wf_advance_tex_shutter": (("tex", "shutter"), False),
+           # the environment (WfSky): the four later launches of a chain under a map, whole (no labels)
+           "wf_advance_sky": (("sky",), False), "wf_advance_tex_sky": (("tex", "sky"), False),
+           "wf_advance_soft_sky": (("soft", "sky"), False), "wf_advance_tex_soft_sky": (("tex", "soft", "sky"), False)}
 
 
 def advance_forms_counts(asm):
@@ -270,7 +273,8 @@ def main():
         res[name] = {"whole_kernel": count(kernel_text(asm, mm.group(1)))}
     # the first-shade cache, the closing launch of a plain chain, several lights, lights with a radius, the thin lens (ADVANCE)
     for name in ("wf_advance_fill", "wf_advance_resume", "wf_advance_close", "wf_advance_lights", "wf_advance_tex_lights", "wf_advance_soft", "wf_advance_tex_soft", "wf_advance_lens",
-                 "wf_advance_shutter_first", "wf_advance_lens_shutter_first", "wf_advance_shutter", "wf_advance_tex_shutter"):
+                 "wf_advance_shutter_first", "wf_advance_lens_shutter_first", "wf_advance_shutter", "wf_advance_tex_shutter",
+                 "wf_advance_sky", "wf_advance_tex_sky", "wf_advance_soft_sky", "wf_advance_tex_soft_sky"):
         res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
