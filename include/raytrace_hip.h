@@ -422,6 +422,56 @@ int rt_scene_get_environment(const rt_ctx *ctx, int *n, float *rgb);
 /* known answers of the lookup: sky_radiance on n_dirs explicit directions (n_dirs x 3 in, n_dirs x 3 out) against the map the context holds; RT_ERR_INVALID without one */
 int rt_kat_environment(rt_ctx *ctx, int n_dirs, const float *dirs, float *rgb_out);
 
+/* --- SKY SAMPLING: directions drawn from the environment map by radiance (ABI 6, additive).  Under a map whose energy sits in a small bright region -- a sun -- a cosine
+ *     bounce finds the light about as often as the region's share of the sphere.  The context therefore carries a share in [0, 1] (default 0: off) and, while the share is
+ *     positive and a map is set, a SAMPLING TABLE built on the device from the map.  A diffuse segment still emits ONE shadow ray; the sky is one more thing it may go to.  The
+ *     device steps are sky_draw and sky_weight in rt_shade.hip.h, beside sky_radiance; the model is tests/sky_sample_model.py.  With share 0, without a map, or under an
+ *     all-zero map (empty table) every frame is launch for launch what it is without this call.
+ *     Binary32 with one rounding per operation, no fused multiply-add, quotients correctly rounded (rt_div.h), unless stated otherwise.
+ *     THE TABLE.  Texels t = y * n + x, row-major.
+ *       1. Y(t) = fl(fl(R + G) + B).
+ *       2. B9(t) = the sum of Y over the 3 x 3 neighbourhood, indices clamped to the map, dy = -1..1 outer, dx = -1..1 inner, added in that order.  The bilinear taps of
+ *          every direction whose lookup lands in texel t's square lie inside it: B9(t) = 0 only where the lookup is 0 throughout, and the lookup never exceeds B9(t).
+ *       3. The solid-angle factor at the texel's centre: ax = fl(fl(x + 0.5) / n), qx = fl(2 ax - 1), likewise qz from y.  The octahedral point p of (qx, qz), 1-norm 1:
+ *          py = fl(fl(1 - |qx|) - |qz|) in both hemispheres; where py < 0 (below the horizon) px = fl(1 - |qz|) * sg(qx), pz = fl(1 - |qx|) * sg(qz), sg(v) = v < 0 ? -1 : 1,
+ *          otherwise px = qx, pz = qz.  (The fold is decided by the sign of the rounded py, not by |qx| + |qz| > 1: one expression serves both.)
+ *          m = fl(fl(fl(px px) + fl(py py)) + fl(pz pz)), W(t) = fl(B9(t) / fl(m * rt_sqrtf(m))).  A texel of the q-square, area 4 / n^2, subtends (4 / n^2) / |p|^3.
+ *       4. Wmax = max W(t).  Wmax == 0: the table is EMPTY.  Otherwise c(t) = W(t) > 0 ? max(1, (uint32)(fl(W(t) / Wmax) * 2^31)) : 0.
+ *       5. prefix[t] = the inclusive 64-bit sum of c; total = prefix[n n - 1] <= 2^51.  Integer sums: any parallel scan gives the same table.
+ *     THE DRAW of segment d of the path whose sample key is hs: four draws at depth (3 << 28) + d, dims 0 to 3 (keys 3 2^30 + 4 d + dim; the lens and the shutter sit at
+ *     2^30 + {0, 1, 2}, the shells at 2^31 + 4 d + {0, 1}).  ka, kb = the 24-bit integers behind draws 0 and 1 (uniform01 = (k + 1) 2^-24); K = ka 2^24 + kb;
+ *     X = ((K * total) >> 48) + 1, the product 128 bits wide, X in [1, total]; t = the least texel with prefix[t] >= X (so c(t) > 0).  How the device searches is not part
+ *     of the rule.
+ *     THE DIRECTION.  jx, jz = draws 2 and 3; ax = fl(fl(x + jx) / n), qx = fl(2 ax - 1), likewise qz from the row and jz; p and m as in step 3; r = rt_sqrtf(m);
+ *     w = p / r in normalize()'s form (three correctly rounded quotients).
+ *     THE ESTIMATE.  With mx = max(dot(N, w), 0) and E = sky_radiance(w):  g = (float)((((double)mx * 4.0) * (double)total) / ((((double)c(t) * (double)(n n)) * (double)m) *
+ *     (double)r)) -- binary64, rounded to binary32 once -- which is mx / pdf, pdf = c(t) / total * n^2 / 4 * |p|^3; the direct term is g * E per channel.  It is unbiased for
+ *     the environment as sky_radiance looks it up.  A draw that rounds onto a neighbouring texel's edge (jx = 1) is evaluated with c(t) of the texel it was drawn from: a set
+ *     of measure zero.
+ *     THE SHARE.  The effective share s is 0 if the table is empty, 1 if the lights' total intensity is +-0, the share otherwise.  Segment d of sample key hs draws
+ *     r_s = uniform01(hs, d + 1, 3) (key 4 (d + 1) + 3, which no jitter, bounce or pick draw reaches); its one shadow ray goes to the sky iff r_s <= s.  Then the direct term
+ *     is l_rgb = w_sky * (g * E) per channel, w_sky = fl(1 / s).  Otherwise the ray goes to the light the list picks, unchanged, and its l is multiplied by w_light =
+ *     fl(1 / (1 - s)); the term is (l, l, l).  Both weights are computed on the host.  At s = 1 the lights are never sampled.
+ *     THE RAY to the sky starts at P_adjusted with direction w and has no far end: it is blocked iff any sphere or any accepted triangle is hit (with any-hit on its bound is
+ *     +inf: the first accepted triangle ends it), and a blocked ray's term is +0 in the three channels.  It is not traced when the three words of l_rgb are +0.  The launch
+ *     that closes it knows it went to the sky from r_s alone.  It counts in .w as any shadow ray: .w of a sampled frame is .w at share 0.
+ *     THE MISS.  While s > 0 a continuation ray that left a DIFFUSE segment and leaves the scene starts the fold from +0 -- the shadow rays have accounted for the sky there;
+ *     a camera ray and the continuation of a mirror or glass hit still start from E.  THE FOLD runs with the per-channel term: fl(fl(l_c alb_c) / pi) + fl(alb_c ans_c).
+ *     DEAD CHANNELS: a segment whose ray goes to the sky clears the path's mask, as a segment that fails the guard does; a light's weighted term is guarded as before.
+ *     Rendered by what renders the environment (the wavefront variants, any lights -- always through the soft lights' table --, the lens, poses, row shares, RT_PARTS,
+ *     batches, rt_render_async, pipelining); refused by what refuses the environment, with "environment sampling" in the error text while the share is positive.
+ *     rt_scene_set_environment_sampling(ctx, share): RT_ERR_INVALID, the state untouched, for a share outside [0, 1] or NaN; RT_ERR_NO_SCENE without an upload.  The table is
+ *     built when the share becomes positive while a map is set and when a map is set or replaced while the share is positive; removing the map or a share of 0 drops it.  A
+ *     replaced table is released after the frames in flight, as the map's own buffer is; a call that fails leaves share, map and table as they were.  rt_scene_upload* resets the share to 0; setting, replacing or removing a map and
+ *     the sphere, light, lens and shutter edits keep it.  Every change empties the still view's caches.  rt_scene_get_environment_sampling(ctx, &share): the share as set.
+ *     Known answers: rt_kat_environment_table reads the table back -- c and prefix, n * n each, either may be NULL, and the total; an empty table is total 0 and zeros;
+ *     RT_ERR_INVALID without a map or with share 0.  rt_kat_environment_sample runs the draw on `count` explicit (hs, seg) pairs: the texel, the direction (count x 3) and g
+ *     at mx = 1; RT_ERR_INVALID without a table to draw from. */
+int rt_scene_set_environment_sampling(rt_ctx *ctx, float share);
+int rt_scene_get_environment_sampling(const rt_ctx *ctx, float *share);
+int rt_kat_environment_table(rt_ctx *ctx, uint32_t *c_out, uint64_t *prefix_out, uint64_t *total);
+int rt_kat_environment_sample(rt_ctx *ctx, int count, const uint32_t *hs, const int32_t *seg, uint32_t *texel_out, float *dir_out, float *g_out);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

@@ -680,6 +680,13 @@ public:
         if (n > 0) check(rt_scene_get_environment(ctx_, &n, rgb.data()), "rt_scene_get_environment");
         return {n, rgb};
     }
+    // Sky sampling (rt_scene_set_environment_sampling): the share in [0, 1] of the shadow rays drawn from the environment map by radiance; 0 is off
+    void set_environment_sampling(float share) { check(rt_scene_set_environment_sampling(ctx_, share), "rt_scene_set_environment_sampling"); }
+    float environment_sampling() {
+        float share = 0.f;
+        check(rt_scene_get_environment_sampling(ctx_, &share), "rt_scene_get_environment_sampling");
+        return share;
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

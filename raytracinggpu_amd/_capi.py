@@ -43,7 +43,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_scene_set_lights", "rt_scene_get_lights", "rt_scene_set_light_at", "rt_scene_move_light_at",
            "rt_scene_set_light_radii", "rt_scene_get_light_radii", "rt_scene_set_light_radius_at",
            "rt_camera_set_lens", "rt_camera_get_lens", "rt_scene_set_shutter", "rt_scene_get_shutter",
-           "rt_scene_set_environment", "rt_scene_get_environment", "rt_kat_environment"]
+           "rt_scene_set_environment", "rt_scene_get_environment", "rt_kat_environment",
+           "rt_scene_set_environment_sampling", "rt_scene_get_environment_sampling", "rt_kat_environment_table", "rt_kat_environment_sample"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -447,6 +448,10 @@ def load():
     L.rt_scene_set_environment.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.rt_scene_get_environment.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]
     L.rt_kat_environment.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.rt_scene_set_environment_sampling.argtypes = [vp, C.c_float]
+    L.rt_scene_get_environment_sampling.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rt_kat_environment_table.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.rt_kat_environment_sample.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -806,6 +811,38 @@ class Context:
         fp = C.POINTER(C.c_float)
         self._check(self._L.rt_kat_environment(self._h, int(d.shape[0]), d.ctypes.data_as(fp), out.ctypes.data_as(fp)))
         return out
+
+    # --- sky sampling (rt_scene_set_environment_sampling): the share of the shadow rays drawn from the map by radiance, and the table's known answers
+    def set_environment_sampling(self, share):
+        """rt_scene_set_environment_sampling: share in [0, 1]; 0 is off"""
+        self._check(self._L.rt_scene_set_environment_sampling(self._h, C.c_float(share)))
+
+    def environment_sampling(self):
+        """rt_scene_get_environment_sampling -> the share as set"""
+        s = C.c_float(0)
+        self._check(self._L.rt_scene_get_environment_sampling(self._h, C.byref(s)))
+        return float(s.value)
+
+    def kat_environment_table(self):
+        """rt_kat_environment_table for the context's n x n map -> (c [n * n] uint32, prefix [n * n] uint64, total); an empty table: zeros and 0"""
+        nn = C.c_int(0)
+        self._check(self._L.rt_scene_get_environment(self._h, C.byref(nn), None))
+        n = nn.value
+        c = np.zeros(int(n) * int(n), np.uint32)
+        prefix = np.zeros(int(n) * int(n), np.uint64)
+        total = C.c_uint64(0)
+        self._check(self._L.rt_kat_environment_table(self._h, c.ctypes.data_as(C.POINTER(C.c_uint32)), prefix.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+        return c, prefix, int(total.value)
+
+    def kat_environment_sample(self, hs, seg):
+        """rt_kat_environment_sample: the draw on explicit sample keys hs [k] uint32 and segments seg [k] -> (texel [k] uint32, direction [k, 3] float32, g at mx = 1 [k] float32)"""
+        h = np.ascontiguousarray(hs, dtype=np.uint32).ravel()
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(seg, np.int32), h.shape), dtype=np.int32)
+        texel, dirs, g = np.zeros(h.size, np.uint32), np.zeros((h.size, 3), np.float32), np.zeros(h.size, np.float32)
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        self._check(self._L.rt_kat_environment_sample(self._h, int(h.size), h.ctypes.data_as(up), d.ctypes.data_as(C.POINTER(C.c_int32)), texel.ctypes.data_as(up),
+                                                      dirs.ctypes.data_as(fp), g.ctypes.data_as(fp)))
+        return texel, dirs, g
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

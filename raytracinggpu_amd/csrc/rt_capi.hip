@@ -13,6 +13,7 @@
 #include "rt_bvhbuild.hip.h"
 #include "rt_lbvh.hip.h"
 #include "rt_adaptive.hip.h"
+#include "rt_skydist.hip.h"
 #include "rt_still.h"
 #include "rt_rowcut.h"
 
@@ -116,6 +117,7 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     ctx->snap_mask = 0;                                                  // ... and holds no vertex snapshot (rt_mesh_snapshot_vertices),
     ctx->nsnap_mask = 0; ctx->vnrm_mask = 0;                             // no normal snapshot and no computed vertex normals (rt_mesh_snapshot_normals, rt_mesh_compute_normals*)
     ctx->vcsr_valid = false;
+    ctx->env_share = 0.f; ctx->env_total = 0;                            // ... draws no shadow rays towards one (rt_scene_set_environment_sampling)
     ctx->env_n = 0; ctx->env_rgb.clear();                                // ... and has no environment (rt_scene_set_environment; the buffer stays for the frames in flight; the still view: below)
     ctx->still.shading_changed();
     ctx->still.mesh_changed();

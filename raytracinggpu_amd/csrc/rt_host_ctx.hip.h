@@ -84,6 +84,8 @@ struct Knobs {
     int stream_policy = 3;     // RT_STREAM_POLICY: a bit per group of use-once streams whose accesses in wf_advance go past the Infinity Cache (rt_wavefront.hip.h kPol*: 1 the
                                // first-shade records a resumed chain loads, 2 the pixel store of the fold); 0: every access the plain instruction, the code of before the policy
                                // (A/B, cross-check).  Bit-exact whatever the value; headline -1.1 ... -1.4 %
+    int sky_search = 1;        // RT_SKY_SEARCH=0: the draw of rt_kat_environment_sample searches the prefixes with one flat binary search (A/B, cross-check; default: the block level
+                               // first, then inside one block, rt_shade.hip.h sky_pick).  Bit-exact either way
     int refit_wide = 1;        // RT_REFIT_WIDE=0: rt_mesh_set_vertices* refits with the one-workgroup refit_kernel, as rt_mesh_transform does (A/B, cross-check; default: the climb across
                                // the chip, rt_meshops.hip.h refit_up_kernel).  Bit-exact either way
     int auto_lockstep = 1;     // RT_AUTO_LOCKSTEP=0: RT_VARIANT_AUTO stays the wavefront pipeline for scenes without a mesh (A/B; default: the lock-step kernel renders them)
@@ -137,6 +139,7 @@ static Knobs read_knobs() {
     if (geti("RT_TRAVQ_QSEL", v)) k.quad_sel = v != 0;
     if (geti("RT_TRAVQ_ANYHIT", v)) k.anyhit = v != 0;
     if (geti("RT_DEAD_CHANNELS", v)) k.dead_channels = v != 0;
+    if (geti("RT_SKY_SEARCH", v)) k.sky_search = v != 0;
     if (geti("RT_TRAVQ_ROWS", v)) k.travq_rows = v != 0;
     if (geti("RT_FIRST_HIT_CACHE", v)) k.first_hit_cache = v != 0;
     if (geti("RT_FIRST_SHADOW_CACHE", v)) k.first_shadow_cache = v != 0;
@@ -195,6 +198,13 @@ struct rt_ctx {
     int env_n = 0;
     std::vector<float> env_rgb;
     DevBuf env{bufs};
+    // Sky sampling (rt_scene_set_environment_sampling): the share of the shadow rays that go to the map, and the table the draws search -- one buffer, the prefixes
+    // (n * n of 64 bits), the block level (env_dist_nb) and c (n * n of 32 bits) in this order.  env_total == 0: no table (the share is 0, no map, or the map is zero
+    // throughout).  A rebuilt table gets a new buffer, as a new map does.  rt_scene_upload* resets the share.
+    float env_share = 0.f;
+    unsigned long long env_total = 0;
+    int env_dist_nb = 0;
+    DevBuf env_dist{bufs};
     DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.
@@ -266,6 +276,7 @@ struct rt_ctx {
     // parts of them hold what, under which keys (rt_host_render.hip.h still_begin)
     DevBuf wfM0{bufs}, wfX0{bufs}, wfS0{bufs};
     rtk::StillView still;
+    DevBuf wfL3{bufs};                                              // ... and the three-channel direct term of each diffuse segment (wf_advance<kFormSkySample>; allocated by the first sampling frame)
     DevBuf wfALB{bufs};                                             // ... and the albedo of each textured diffuse segment (wf_advance<kFormTex>; allocated by the first textured frame)
     DevBuf wfQR{bufs};                                              // traversal queue in slot order: the rays (32 B each)
     DevBuf pathSamp{bufs}, pathT{bufs};                             // wf_path with num_rays > 1: per-sample colours, running sum

@@ -239,6 +239,75 @@ int rt_scene_get_shutter(const rt_ctx *ctx, rt_shutter *out) {
     return RT_OK;
 }
 
+// ---- sky sampling (raytrace_hip.h "sky sampling"): the table of the map the context holds, for a share `share` (rt_skydist.hip.h) ----
+// The table of the n x n map at `texels` (device memory) for a share `share`, built into `built`: a buffer of its own and the total; total 0 -- no map, share 0 or a map
+// that is zero throughout -- is no table.  Nothing of the context changes here: the caller installs what was built once every step has succeeded (SkyDistBuilt::install),
+// and a failure leaves the state as it was.  The device is idle when this returns with a table (the frames that captured the old one are done: the rule of the map's buffer).
+struct SkyDistBuilt {
+    DevBuf buf; unsigned long long total = 0; int nb = 0;
+    void install(rt_ctx *ctx) { ctx->env_total = total; if (total > 0) { ctx->env_dist = std::move(buf); ctx->env_dist_nb = nb; } }
+};
+static int sky_dist_build(rt_ctx *ctx, const void *texels, int n_map, float share, SkyDistBuilt &built) {
+    if (n_map <= 0 || !(share > 0.f)) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_OWN_STREAM(ctx);
+    hipStream_t q = own_stream(ctx);
+    const int n = n_map, count = n * n, nb = (count + rtk::kSkyBlock - 1) / rtk::kSkyBlock;
+    DevBuf tmp;
+    DevBuf &fresh = built.buf;
+    int rc;
+    if ((rc = ensure(ctx, tmp, (size_t)count * sizeof(float) + 16)) != RT_OK || (rc = ensure(ctx, fresh, (size_t)count * 12 + (size_t)nb * 8)) != RT_OK) return rc;
+    float *W = static_cast<float *>(tmp.p);
+    unsigned int *wmax = reinterpret_cast<unsigned int *>(W + count);
+    unsigned long long *prefix = static_cast<unsigned long long *>(fresh.p), *blk = prefix + count;
+    unsigned int *c = reinterpret_cast<unsigned int *>(blk + nb);
+    const dim3 g((unsigned)nb), b(rtk::kSkyBlock);
+    RT_HIP(ctx, hipMemsetAsync(wmax, 0, sizeof(unsigned int), q));
+    hipLaunchKernelGGL(rtk::sky_dist_weights, g, b, 0, q, static_cast<const float4 *>(texels), n, W, wmax);
+    RT_HIP(ctx, hipGetLastError());
+    unsigned int wmax_bits = 0;
+    RT_HIP(ctx, hipMemcpyAsync(&wmax_bits, wmax, sizeof(wmax_bits), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipStreamSynchronize(q));
+    if (wmax_bits == 0) return RT_OK;                                  // the lookup is 0 throughout: the table is empty
+    hipLaunchKernelGGL(rtk::sky_dist_quantise, g, b, 0, q, W, count, wmax, c, blk);
+    hipLaunchKernelGGL(rtk::sky_dist_scan, dim3(1), dim3(rtk::kSkyScanLevel), 0, q, blk, nb);
+    hipLaunchKernelGGL(rtk::sky_dist_prefix, g, b, 0, q, c, count, blk, prefix);
+    RT_HIP(ctx, hipGetLastError());
+    unsigned long long total = 0;
+    RT_HIP(ctx, hipMemcpyAsync(&total, blk + (nb - 1), sizeof(total), hipMemcpyDeviceToHost, q));
+    RT_HIP(ctx, hipStreamSynchronize(q));
+    RT_HIP(ctx, hipDeviceSynchronize());
+    built.nb = nb;
+    built.total = total;
+    return RT_OK;
+}
+
+int rt_scene_set_environment_sampling(rt_ctx *ctx, float share) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (!(share >= 0.f && share <= 1.f)) return fail(ctx, RT_ERR_INVALID, "environment sampling: the share %g is outside [0, 1]", (double)share);
+    if (share == 0.f) share = 0.f;                                     // (-0 is 0)
+    if (share == ctx->env_share) return RT_OK;
+    // the table depends on the map alone: it is built when the share becomes positive and dropped when it becomes 0
+    if (!(share > 0.f) || !(ctx->env_share > 0.f)) {
+        SkyDistBuilt built;
+        if (int rc = sky_dist_build(ctx, ctx->env.p, ctx->env_n, share, built); rc != RT_OK) return rc;   // (a failure: share and table as they were)
+        built.install(ctx);
+    }
+    ctx->env_share = share;
+    ctx->still.sky_changed();
+    return RT_OK;
+}
+
+int rt_scene_get_environment_sampling(const rt_ctx *ctx, float *share) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!share) return fail(c, RT_ERR_INVALID, "share is NULL");
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    *share = ctx->env_share;
+    return RT_OK;
+}
+
 // ---- the environment map (raytrace_hip.h "environment"): host state plus one device buffer of the context's; make_frame captures pointer and size ----
 int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
@@ -248,6 +317,7 @@ int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb) {
     if (n == 0 || !rgb) {                                                // removed (the buffer stays until the next map: frames in flight may read it)
         if (ctx->env_n > 0) ctx->still.sky_changed();
         ctx->env_n = 0; ctx->env_rgb.clear();
+        ctx->env_total = 0;                                              // ... and its table with it; the share stays
         return RT_OK;
     }
     const size_t count = (size_t)n * (size_t)n;
@@ -266,11 +336,14 @@ int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb) {
     DevBuf fresh;
     if (int rc = upload(ctx, fresh, texels.data(), count * sizeof(float4)); rc != RT_OK) return rc;
     RT_HIP(ctx, hipDeviceSynchronize());
+    SkyDistBuilt built;                                                  // the new map's table, if the share is positive: before anything of the context changes
+    if (int rc = sky_dist_build(ctx, fresh.p, n, ctx->env_share, built); rc != RT_OK) return rc;
+    built.install(ctx);
     ctx->env = std::move(fresh);
     ctx->env_rgb.assign(rgb, rgb + 3 * count);
     ctx->env_n = n;
     ctx->still.sky_changed();
-    return RT_OK;
+    return RT_OK;                                                      // (the share stays)
 }
 
 int rt_scene_get_environment(const rt_ctx *ctx, int *n, float *rgb) {

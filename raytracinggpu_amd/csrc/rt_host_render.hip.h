@@ -27,15 +27,18 @@ bool lights_soft(const rt_ctx *ctx) {
 // wf_chain: the caller is a frame's own chain of wf_advance launches, which takes all of the above -- but not the shutter together with a light list or a radius: the four
 // shutter forms are built for the Scene's one point light
 // The environment (rt_scene_set_environment) is rendered by the chain's four kFormSky forms alone: not with the shutter on, and by no other entry
+// Sky sampling (rt_scene_set_environment_sampling) is rendered by the chain's two kFormSkySample forms and refused wherever the environment is; with the share positive
+// the refusal says "environment sampling"
 int lights_refuse(rt_ctx *ctx, const char *what, bool wf_chain = false) {
+    const char *env_what = ctx && ctx->env_share > 0.f ? "an environment with environment sampling on" : "an environment";
     if (wf_chain) {
         if (ctx && ctx->env_n > 0 && ctx->shutter_on)
-            return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene has an environment and the shutter is on; no wf_advance form takes both (rt_scene_set_environment)", what);
+            return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene has %s and the shutter is on; no wf_advance form takes both (rt_scene_set_environment)", what, env_what);
         if (ctx && ctx->shutter_on && (ctx->n_lights > 1 || lights_soft(ctx)))
             return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the shutter is on and the scene holds several lights or a light with a radius; no wf_advance form takes both (rt_scene_set_shutter)", what);
         return RT_OK;
     }
-    if (ctx && ctx->env_n > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene has an environment; only wf_advance's sky forms meet it (rt_scene_set_environment)", what);
+    if (ctx && ctx->env_n > 0) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene has %s; only wf_advance's sky forms meet it (rt_scene_set_environment)", what, env_what);
     // ... and while the shutter is on, only a chain of the shutter forms may render it
     if (ctx && ctx->shutter_on) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the shutter is on; only wf_advance's shutter forms move the scene within a frame (rt_scene_set_shutter)", what);
     if (ctx && ctx->n_lights > 1) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: the scene holds %d lights; only wf_advance takes more than one (rt_scene_set_lights)", what, ctx->n_lights);
@@ -211,7 +214,14 @@ struct Chunk {
     rtk::WfShutter shutter{};                                         // shutter_on: the shutter motion -- the argument of every wf_advance launch of the chunk (the kFormShutter forms)
     bool shutter_on = false;
     rtk::WfSky sky{};                                                 // sky.n > 0: the scene has an environment -- the argument of the chunk's kFormSky launches (every one after the opening)
+    rtk::WfSkyDist sd{};                                              // sd.s > 0: sky sampling is in effect -- the table, the effective share and the weights of the kFormSkySample launches (L3: per part)
 };
+// what the draws read of the context's table (env_total > 0)
+static rtk::WfSkyDist sky_dist_of(const rt_ctx *ctx) {
+    const size_t count = (size_t)ctx->env_n * (size_t)ctx->env_n;
+    const unsigned long long *prefix = static_cast<const unsigned long long *>(ctx->env_dist.p);
+    return rtk::WfSkyDist{prefix, prefix + count, reinterpret_cast<const unsigned int *>(prefix + count + ctx->env_dist_nb), ctx->env_total, ctx->env_n, ctx->env_dist_nb};
+}
 void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Chunk &c) {
     const rt_params *p = c.p;
     rtk::Frame &fr = c.fr;
@@ -244,7 +254,8 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
     }
     c.sky = rtk::WfSky{ctx->env_n > 0 ? static_cast<const float4 *>(ctx->env.p) : nullptr, ctx->env_n};   // (rt_scene_set_environment) the map's buffer as it is now: a new map gets a new one
     c.soft = lights_soft(ctx);
-    if (ctx->n_lights > 1 || c.soft) {                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
+    const bool sampling = ctx->env_n > 0 && ctx->env_share > 0.f && ctx->env_total > 0;   // (an empty table: the effective share is 0)
+    if (ctx->n_lights > 1 || c.soft || sampling) {                    // (sky sampling takes the soft route with any lights: one point light is a soft list of one)                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
         rtk::WfLights &lt = c.sl.lt;
         const rt_light one{{ctx->scene.Lx, ctx->scene.Ly, ctx->scene.Lz}, ctx->scene.intensity};   // a soft list of one lives in `scene` alone, as every list of one
         float prefix = 0.f;
@@ -257,6 +268,12 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
         }
         lt.total = prefix;
         lt.n = ctx->n_lights;
+    }
+    if (sampling) {                                                   // the effective share: 1 if the lights give nothing (total +-0), the share otherwise; the weights, one division each
+        c.sd = sky_dist_of(ctx);
+        c.sd.s = c.sl.lt.total == 0.f ? 1.f : ctx->env_share;
+        c.sd.w_sky = 1.f / c.sd.s;
+        c.sd.w_light = c.sd.s < 1.f ? 1.f / (1.f - c.sd.s) : 0.f;     // (at s = 1 the lights are never sampled)
     }
 }
 
@@ -606,6 +623,7 @@ int size_wavefront(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool &qr_grown) 
         (rc = ensure(ctx, ctx->wfSID, np * nseg)) != RT_OK || (rc = ensure(ctx, ctx->wfDCH, np)) != RT_OK || (rc = ensure(ctx, ctx->wfLS, np * 4 * nseg)) != RT_OK)
         return rc;
     if (ctx->tex_mask != 0 && (rc = ensure(ctx, ctx->wfALB, np * 16 * nseg)) != RT_OK) return rc;   // a textured mesh: the per-segment albedo store of wf_advance<kFormTex>
+    if (c.sd.s > 0.f && (rc = ensure(ctx, ctx->wfL3, np * 16 * nseg)) != RT_OK) return rc;          // sky sampling: the three-channel direct term of every diffuse segment
     // a still view's levels: the first two allocated by the first eligible frame, the records by the first chunk one of whose chains may store them (a new allocation
     // empties its level: StillView::begin)
     if (w.still >= 1 && (rc = ensure(ctx, ctx->wfM0, w.px * 8)) != RT_OK) return rc;
@@ -711,12 +729,12 @@ int end_chains(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool own0) {
 
 // What a chain's wf_advance launches may take beyond (Scene, Frame, WfState): each form takes the ones its bits name (rt_still.h kForm*), in this order (sl.lt: the table of
 // the forms without radii)
-struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; rtk::WfSky sky{}; };
+struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; rtk::WfSky sky{}; rtk::WfSkyDist sd{}; };
 struct AdvLaunch {
     dim3 grid, block; hipStream_t q; const rtk::Scene &scn; const rtk::Frame &fr; const rtk::WfState &st;
     template <unsigned FORM, class... Extra> void go(const Extra &... extra) const { hipLaunchKernelGGL((rtk::wf_advance<FORM, Extra...>), grid, block, 0, q, scn, fr, st, extra...); }
 };
-// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 29 instantiations, one case each (DESIGN.md section 5.2 says who launches
+// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 31 instantiations, one case each (DESIGN.md section 5.2 says who launches
 // each and which test runs it).  The entries refuse what has no form before a chain is planned (lights_refuse, resolve_variant), so the default is not reached.
 int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_t q, const rtk::Scene &scn, const rtk::Frame &fr, const rtk::WfState &st, const AdvArgs &a) {
     using namespace rtk;
@@ -737,6 +755,8 @@ int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_
     case kFormTex | kFormSky: l.go<kFormTex | kFormSky>(a.ts, a.sky); break;
     case kFormSoft | kFormSky: l.go<kFormSoft | kFormSky>(a.sl, a.sky); break;
     case kFormTex | kFormSoft | kFormSky: l.go<kFormTex | kFormSoft | kFormSky>(a.ts, a.sl, a.sky); break;
+    case kFormSoft | kFormSky | kFormSkySample: l.go<kFormSoft | kFormSky | kFormSkySample>(a.sl, a.sky, a.sd); break;
+    case kFormTex | kFormSoft | kFormSky | kFormSkySample: l.go<kFormTex | kFormSoft | kFormSky | kFormSkySample>(a.ts, a.sl, a.sky, a.sd); break;
     case kFormTex | kFormAnim: l.go<kFormTex | kFormAnim>(a.ts, a.anim); break;
     case kFormTex | kFormList: l.go<kFormTex | kFormList>(a.ts, a.list); break;
     case kFormFirst | kFormStats: l.go<kFormFirst | kFormStats>(); break;
@@ -764,7 +784,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     if (pt.st.n_paths == 0) return RT_OK;
     // the chain's facts: with the step they decide the form of each wf_advance launch (rt_still.h adv_form)
     const bool anim = c.batch && c.anim;                          // an animated batch: the frames' lights and spheres too
-    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on, c.sky.n > 0};
+    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on, c.sky.n > 0, c.sd.s > 0.f};
     const dim3 pg(pt.pblocks), pb(kn.adv_block);
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
@@ -777,6 +797,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     auto block = [&](const DevBuf &b) { return static_cast<unsigned long long *>(b.p) + pt.pxbase; };   // the part's block of a level
     AdvArgs aa;
     aa.anim = pt.anim; aa.sl = c.sl; aa.ln = c.lens; aa.shu = c.shutter; aa.sky = c.sky;
+    if (facts.sample) { aa.sd = c.sd; aa.sd.L3 = static_cast<float4 *>(ctx->wfL3.p) + pt.base * (size_t)c.nseg; }   // L3[d * n_paths + i] inside the part's block, as ALB
     if (sc.records != rtk::kStillOff) { aa.sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; aa.sh.kill_x = plan.kill_x; }
     if (facts.tex) { aa.ts = tex_scene(ctx); aa.ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg; }   // ALB[d * n_paths + i] inside the part's block, as LS
     pt.st.nonce = (int)(++ctx->chain_nonce[j] & (unsigned)rtk::PQ_NONCE_MASK);

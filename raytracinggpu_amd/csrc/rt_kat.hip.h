@@ -181,6 +181,18 @@ __global__ __launch_bounds__(256) void kat_sky_kernel(const WfSky sky, const flo
     out[3 * (size_t)i] = E.x; out[3 * (size_t)i + 1] = E.y; out[3 * (size_t)i + 2] = E.z;
 }
 
+// in: hs, seg; out: the texel, the direction and g at mx = 1 of sky_draw / sky_weight (the draw a sky-sampling wf_advance form makes per diffuse segment)
+template <bool FLAT>
+__global__ __launch_bounds__(256) void kat_sky_sample_kernel(const WfSkyDist sd, const uint32_t *__restrict__ hs, const int *__restrict__ seg, int count, uint32_t *__restrict__ texel,
+                                                             float *__restrict__ dir, float *__restrict__ g) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const SkyDraw s = sky_draw<FLAT>(sd, hs[i], seg[i]);
+    texel[i] = s.t;
+    dir[3 * (size_t)i] = s.w.x; dir[3 * (size_t)i + 1] = s.w.y; dir[3 * (size_t)i + 2] = s.w.z;
+    g[i] = sky_weight(sd, s.t, s.m, s.r, 1.f);
+}
+
 }  // namespace rtk
 
 namespace {
@@ -257,6 +269,53 @@ int rt_kat_environment(rt_ctx *ctx, int n_dirs, const float *dirs, float *rgb_ou
     return kat_run(ctx, dirs, n_dirs, 3, rgb_out, 3, nullptr, [&](const float *di, float *dres, unsigned long long *, dim3 g, dim3 b) {
         hipLaunchKernelGGL(rtk::kat_sky_kernel, g, b, 0, own_stream(ctx), rtk::WfSky{static_cast<const float4 *>(ctx->env.p), ctx->env_n}, di, n_dirs, dres);
     });
+}
+
+// the sampling table as the device built it: c and prefix (n * n each, either may be NULL) and the total; an empty table is total 0 and zeros
+int rt_kat_environment_table(rt_ctx *ctx, uint32_t *c_out, uint64_t *prefix_out, uint64_t *total) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (!total) return fail(ctx, RT_ERR_INVALID, "total is NULL");
+    if (ctx->env_n <= 0 || !(ctx->env_share > 0.f)) return fail(ctx, RT_ERR_INVALID, "no table: the scene has no environment or the share is 0 (rt_scene_set_environment_sampling)");
+    const size_t count = (size_t)ctx->env_n * (size_t)ctx->env_n;
+    if (ctx->env_total == 0) {
+        if (c_out) memset(c_out, 0, count * sizeof(uint32_t));
+        if (prefix_out) memset(prefix_out, 0, count * sizeof(uint64_t));
+        *total = 0;
+        return RT_OK;
+    }
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const rtk::WfSkyDist sd = sky_dist_of(ctx);
+    if (c_out) RT_HIP(ctx, hipMemcpy(c_out, sd.c, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (prefix_out) RT_HIP(ctx, hipMemcpy(prefix_out, sd.prefix, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    *total = ctx->env_total;
+    return RT_OK;
+}
+
+int rt_kat_environment_sample(rt_ctx *ctx, int count, const uint32_t *hs, const int32_t *seg, uint32_t *texel_out, float *dir_out, float *g_out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!ctx->have_scene) return fail(ctx, RT_ERR_NO_SCENE, "rt_scene_upload has not been called");
+    if (count < 0 || (count > 0 && (!hs || !seg || !texel_out || !dir_out || !g_out))) return fail(ctx, RT_ERR_INVALID, "bad KAT arguments");
+    if (ctx->env_n <= 0 || ctx->env_total == 0) return fail(ctx, RT_ERR_INVALID, "no table to draw from: no environment, share 0 or a map that is zero throughout (rt_scene_set_environment_sampling)");
+    if (count == 0) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_OWN_STREAM(ctx);
+    hipStream_t q = own_stream(ctx);
+    DevBuf dhs, dseg, dout;                                            // out: the texel, three floats of direction and g per draw
+    int rc;
+    if ((rc = upload(ctx, dhs, hs, (size_t)count * 4)) != RT_OK || (rc = upload(ctx, dseg, seg, (size_t)count * 4)) != RT_OK || (rc = ensure(ctx, dout, (size_t)count * 20)) != RT_OK) return rc;
+    uint32_t *dt = static_cast<uint32_t *>(dout.p);
+    float *dd = reinterpret_cast<float *>(dt + count), *dg = dd + 3 * (size_t)count;
+    const auto kernel = ctx->knobs.sky_search != 0 ? rtk::kat_sky_sample_kernel<false> : rtk::kat_sky_sample_kernel<true>;   // (RT_SKY_SEARCH=0: the flat search)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, q, sky_dist_of(ctx), static_cast<const uint32_t *>(dhs.p),
+                       static_cast<const int *>(dseg.p), count, dt, dd, dg);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(texel_out, dt, (size_t)count * 4, hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(dir_out, dd, (size_t)count * 12, hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(g_out, dg, (size_t)count * 4, hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "KAT launch: %s", hipGetErrorString(e));
+    return RT_OK;
 }
 
 // FNV-1a over the device arrays the traversal kernels read: out[0] the float sibling pairs (nodesb), [1] the 16-bit fixed-point pairs (nodesh), [2] the 4-wide quads

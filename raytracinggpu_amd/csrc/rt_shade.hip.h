@@ -131,6 +131,78 @@ __device__ __forceinline__ f3 sky_radiance(const WfSky &sky, f3 u) {
               (t00.z * gx + t10.z * fx) * gy + (t01.z * gx + t11.z * fx) * fy);
 }
 
+// SKY SAMPLING (rt_scene_set_environment_sampling; the rule: raytrace_hip.h "sky sampling"): a direction drawn from the map by radiance.  The table is integers -- c(t) per
+// texel, its inclusive 64-bit sums, their total -- built on the device (rt_skydist.hip.h), so the texel of a draw is a function of the table alone.  blk is the coarse
+// level of the search: the prefix at the last texel of every kSkyBlock texels (at most 4096 words, 32 KB: they stay in cache), then a search inside one block.
+constexpr int kSkyBlock = 256;
+struct WfSkyDist {
+    const unsigned long long *prefix;        // [n * n] inclusive sums of c, texel t = y * n + x
+    const unsigned long long *blk;           // [nb] blk[b] = prefix[min((b + 1) * kSkyBlock, n * n) - 1]
+    const unsigned int *c;                   // [n * n]
+    unsigned long long total;                // prefix[n * n - 1], in [1, 2^51]
+    int n, nb;
+    // ... and what a frame's sampling forms take with it (wf_advance<kFormSkySample>; zero in the known-answer entries): the effective share s in (0, 1], the two
+    // weights fl(1 / s) and fl(1 / (1 - s)) (the latter unused at s = 1), and the three-channel direct term of diffuse segment d of path i, L3[d * n_paths + i]
+    float s, w_sky, w_light;
+    float4 *L3;
+};
+// the 24-bit integer k behind a draw: uniform01 = (k + 1) * 2^-24
+__device__ __forceinline__ uint32_t uniform24(uint32_t hs, uint32_t depth, uint32_t dim) { return mix32(hs ^ ((depth * 4U + dim) * 0x85EBCA77U)) >> 8; }
+// q = 2 a - 1 with a = fl(xs / n), the quotient correctly rounded (2 a is exact: one rounding each)
+__device__ __forceinline__ float sky_q(float xs, float nf) { return div_quot(xs, nf) * 2.f - 1.f; }
+// the octahedral point of (qx, qz), 1-norm 1, not normalised: py = fl(fl(1 - |qx|) - |qz|) in both hemispheres, and where py < 0 the fold of sky_radiance's step 3 undone
+__device__ __forceinline__ f3 sky_oct_point(float qx, float qz) {
+    const float h = (1.f - fabsf(qx)) - fabsf(qz);
+    float px = qx, pz = qz;
+    if (h < 0.f) {
+        px = (1.f - fabsf(qz)) * (qx < 0.f ? -1.f : 1.f);
+        pz = (1.f - fabsf(qx)) * (qz < 0.f ? -1.f : 1.f);
+    }
+    return mk(px, h, pz);
+}
+// the least texel t with prefix[t] >= X, for X in [1, total]: the least block whose last prefix reaches X, then the least texel inside it.  Every index stays inside
+// [0, nb) and [0, n * n) whatever X is.
+// FLAT: one binary search over all n * n prefixes, 20 dependent loads at n = 1024 (RT_SKY_SEARCH=0: the form the two levels are measured against; the same texel).
+template <bool FLAT = false>
+__device__ __forceinline__ unsigned int sky_pick(const WfSkyDist &sd, unsigned long long X) {
+    int lo = 0, hi = sd.nb - 1;
+    while (!FLAT && lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sd.blk[mid] >= X) hi = mid; else lo = mid + 1;
+    }
+    const int count = sd.n * sd.n;
+    int tlo = lo * kSkyBlock, thi = tlo + kSkyBlock < count ? tlo + kSkyBlock - 1 : count - 1;
+    if (FLAT) { tlo = 0; thi = count - 1; }
+    while (tlo < thi) {
+        const int mid = (tlo + thi) >> 1;
+        if (sd.prefix[mid] >= X) thi = mid; else tlo = mid + 1;
+    }
+    return (unsigned int)tlo;
+}
+// the draw of segment `seg` of the path whose sample key is hs: the texel, the unit direction, and m = |p|^2, r = |p| of the octahedral point p behind it
+struct SkyDraw { unsigned int t; f3 w; float m, r; };
+template <bool FLAT = false>
+__device__ __forceinline__ SkyDraw sky_draw(const WfSkyDist &sd, uint32_t hs, int seg) {
+    const uint32_t depth = (3u << 28) + (uint32_t)seg;
+    const unsigned long long K = ((unsigned long long)uniform24(hs, depth, 0) << 24) | (unsigned long long)uniform24(hs, depth, 1);
+    const unsigned long long X = ((__umul64hi(K, sd.total) << 16) | ((K * sd.total) >> 48)) + 1ull;   // (K total >> 48) + 1: K < 2^48 and total <= 2^51, the high word is below 2^35
+    SkyDraw s;
+    s.t = sky_pick<FLAT>(sd, X);
+    const unsigned int y = s.t / (unsigned int)sd.n, x = s.t - y * (unsigned int)sd.n;
+    const float nf = (float)sd.n;
+    const float jx = uniform01(hs, depth, 2), jz = uniform01(hs, depth, 3);
+    const f3 p = sky_oct_point(sky_q((float)x + jx, nf), sky_q((float)y + jz, nf));
+    s.m = norm2(p);
+    s.w = normalize(p, s.r);
+    return s;
+}
+// g = mx / pdf in binary64, rounded once: pdf = c(t) / total * n^2 / 4 * |p|^3
+__device__ __forceinline__ float sky_weight(const WfSkyDist &sd, unsigned int t, float m, float r, float mx) {
+    const double num = ((double)mx * 4.0) * (double)sd.total;
+    const double den = (((double)sd.c[t] * (double)(sd.n * sd.n)) * (double)m) * (double)r;
+    return (float)(num / den);
+}
+
 // ---- the hit ----
 // alpha, beta, gamma of triangle `tri` (visit order) for the ray (O, u): get_smooth_normal's expressions (realtime_render.cu:221-245).  The smooth normal, the
 // texture lookup (tex_albedo, rt_wavefront.hip.h) and rt_kat_surface read these.
@@ -228,6 +300,11 @@ __device__ __forceinline__ f3 cosine_bounce(f3 N, uint32_t hs, int d) {
 }
 // cpu:624, 642-644: the colour of a path from a diffuse segment on -- its direct light l * albedo / pi plus albedo (.) the colour `ans` of what follows it
 __device__ __forceinline__ f3 fold_segment(f3 ans, float l, f3 alb) {
+    const float PI_F = (float)3.14159265358979323846;
+    return (l * alb) / PI_F + alb * ans;
+}
+// ... with a direct term per channel (sky sampling: the environment's estimate has three); (l, l, l) gives the same words as the scalar form
+__device__ __forceinline__ f3 fold_segment(f3 ans, f3 l, f3 alb) {
     const float PI_F = (float)3.14159265358979323846;
     return (l * alb) / PI_F + alb * ans;
 }

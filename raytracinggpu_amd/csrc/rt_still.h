@@ -177,13 +177,14 @@ inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool 
 // lights with a radius (WfSoftLights; in place of lights, never both); lens: the thin lens, with first (WfLens); shutter: the spheres and the light at the sample's own
 // time (WfShutter), in every launch of the chain; sky: a ray that misses meets the environment map (WfSky), in every launch after the opening one -- its extra comes last
 constexpr unsigned kFormStats = 1u << 0, kFormFirst = 1u << 1, kFormTex = 1u << 2, kFormAnim = 1u << 3, kFormList = 1u << 4, kFormFill = 1u << 5, kFormResume = 1u << 6,
-                   kFormLights = 1u << 7, kFormSoft = 1u << 8, kFormLens = 1u << 9, kFormClose = 1u << 10, kFormShutter = 1u << 11, kFormSky = 1u << 12;
+                   kFormLights = 1u << 7, kFormSoft = 1u << 8, kFormLens = 1u << 9, kFormClose = 1u << 10, kFormShutter = 1u << 11, kFormSky = 1u << 12,
+                   kFormSkySample = 1u << 13;                // sky sampling: a segment's shadow ray may go to the environment, drawn from its table (WfSkyDist, after the WfSky)
 constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks for this launch, and no kernel exists for it
 
 // What decides the form besides the step: the chain's facts.  counting: rt_count_work; anim: a batch with per-frame scenes; list: rt_render_counts*; lights: 0 the Scene's
 // one point light, 1 several, 2 some with a radius; shutter: the shutter is on (rt_scene_set_shutter) -- defaulted: a chain without one is written as before; sky: the scene has an
 // environment (rt_scene_set_environment) -- last and defaulted, for the same reason
-struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; };
+struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; bool sample = false; };   // sample: sky sampling is in effect (with sky), last and defaulted too
 // The plain chain -- every launch after the opening one the form 0 or kFormStats (or the launch that stores the records): still_plan's `ends`, for a work-stack chain
 inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky; }
 // The form of the launch a chain of these facts enqueues for `adv` (StillAdv: StillPlan::open for the opening launch, StillStep::adv for the later ones)
@@ -196,9 +197,12 @@ inline unsigned adv_form(const AdvFacts &f, int adv) {
     // The environment: a ray meets it where it is closed, so the opening launch is what it was and every later launch has the bit.  Counting, a list, an animated batch and
     // the shutter refuse it (lights_refuse); no still view (no fill, no resume), and the closing kernel closes no continuation ray: not a plain chain.  A light list without
     // a radius goes through the soft forms with radii 0 (a radius-0 light is the light itself, bit for bit): four later forms, not six
+    if (f.sample && !f.sky) return kFormNotBuilt;
     if (f.sky) {
         if (special != 0 || f.shutter) return kFormNotBuilt;
         if (adv == kAdvBegin) return kFormFirst | (f.lens ? kFormLens : 0u);
+        // sky sampling: any light configuration takes the soft route (one point light is a soft list of one at radius 0): two forms
+        if (adv == kAdvPlain && f.sample) return (f.tex ? kFormTex : 0u) | kFormSoft | kFormSky | kFormSkySample;
         if (adv == kAdvPlain) return (f.tex ? kFormTex : 0u) | (f.lights != 0 ? kFormSoft : 0u) | kFormSky;
         return kFormNotBuilt;
     }

@@ -701,7 +701,7 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
 // them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones)
-#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -824,9 +824,10 @@ using AnimTable = const AnimFrame *__restrict__;                      // (the qu
 template <unsigned FORM>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim,
                                                 const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln,
-                                                const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky) {
+                                                const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky, const WfSkyDist *__restrict__ sd = nullptr) {
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
     constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter, SKY = FORM & kFormSky;
+    constexpr bool SAMPLE = FORM & kFormSkySample;                     // sky sampling: a segment's one shadow ray may go to the environment (always with SKY and the soft lights' table)
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
     // of the store (16 bytes of scratch) and keeps the plain one
@@ -845,6 +846,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     int d = 0, nrays = 0;
     bool emitY = false, emitX = false, finished = false;
     float x_bound = -__builtin_inff();                                // any-hit bound of the shadow ray (wf_anyhit_bound)
+    bool x_sky = false;                                               // (SAMPLE) the shadow ray in question -- closed, then emitted -- goes to the sky
     bool x_moot = false;                                              // the shadow ray's answer cannot reach the pixel (direct term +0 either way, or every channel dead)
     f3 Oy = mk(0, 0, 0), uy = mk(0, 0, 1), Ox = mk(0, 0, 0), ux = mk(0, 0, 1);
     f3 E = mk(0, 0, 0);                                               // (SKY) what the path's last ray met beyond the scene: the fold starts from it
@@ -928,7 +930,20 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         const bool x_close0 = st.x0 != 0 && !st.m0;
         unsigned long long xm = WF_NOHIT;
         if (LIGHTS == 1 && (F & PF_HASX)) L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // the light segment d-1's shadow ray went to, picked again
-        if (LIGHTS == 2 && (F & PF_HASX)) L = wf_light_point(*sl, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // ... and the point of its shell
+        // (SAMPLE) segment d-1's shadow ray went to the sky: known from its share draw alone, no search
+        if constexpr (SAMPLE) x_sky = (F & PF_HASX) && uniform01(sample_hash(pixel_hash(fr, row, px, fr_seed), samp), (uint32_t)d, 3) <= sd->s;
+        if (LIGHTS == 2 && (F & PF_HASX) && !(SAMPLE && x_sky)) L = wf_light_point(*sl, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // ... and the point of its shell
+        if constexpr (SAMPLE) {                                       // the stored three-channel term does not count if the ray was blocked: a sky ray by anything at all
+            if (F & PF_HASX) {
+                bool shadowed;
+                if (x_sky) shadowed = (F & PQ_XSPHERE) != 0 || ((F & PF_MESHX) != 0 && st.M[rx] != WF_NOHIT);
+                else shadowed = wf_x_shadowed(F, L, [&] { return st.M[rx]; }, [&](f3 &Oxr, f3 &uxr) {
+                    const float4 x0 = st.QR[2 * (size_t)qx], x1 = st.QR[2 * (size_t)qx + 1];
+                    Oxr = mk(x0.x, x0.y, x0.z); uxr = mk(x0.w, x1.x, x1.y);
+                }, xm);
+                if (shadowed) sd->L3[(size_t)(d - 1) * st.n_paths + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        } else
         if (!RESUME && (F & PF_HASX)) {
             const bool shadowed = wf_x_shadowed(F, L, [&] {
                 const int first = s_rel * st.n_px;                    // (0 unless the chain traces several samples as items)
@@ -989,6 +1004,48 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     if (RESUME) {
                         st.LS[i] = rb.z;                              // final: no shadow ray of segment 0 is in flight
                         sid = (__float_as_int(rb.w) >> SH_SID_SHIFT) & 255;
+                    } else if constexpr (SAMPLE) {
+                        const uint32_t hs = sample_hash(pixel_hash(fr, row, px, fr_seed), samp);
+                        x_sky = uniform01(hs, (uint32_t)(d + 1), 3) <= sd->s;   // this segment's one shadow ray goes to the sky, or to the light the list picks
+                        f3 l3;
+                        Ox = Pa;
+                        if (x_sky) {
+                            const SkyDraw dr = sky_draw(*sd, hs, d);
+                            ux = dr.w;
+                            x_bound = __builtin_inff();               // no far end: the first accepted triangle ends it
+                            const float dn = dot(N, dr.w);
+                            const float g = sky_weight(*sd, dr.t, dr.m, dr.r, (dn < 0.f) ? 0.f : dn);
+                            const f3 Es = sky_radiance(*sky, dr.w);
+                            l3 = mk(sd->w_sky * (g * Es.x), sd->w_sky * (g * Es.y), sd->w_sky * (g * Es.z));
+                        } else {
+                            float nl;
+                            L = wf_light_point(*sl, hs, d);
+                            ux = shadow_dir(L, Pa, nl);
+                            x_bound = wf_anyhit_bound(Pa, nl);
+                            const float lv = direct_term(sl->lt.total, L, P, N) * sd->w_light;
+                            l3 = mk(lv, lv, lv);
+                        }
+                        nrays += 1;
+                        sd->L3[(size_t)d * st.n_paths + i] = make_float4(l3.x, l3.y, l3.z, 0.f);
+                        emitX = true;
+                        x_moot = st.anyhit && (__float_as_uint(l3.x) | __float_as_uint(l3.y) | __float_as_uint(l3.z)) == 0u;
+                        sid = win;
+                        f3 alb = mk(m.ar, m.ag, m.ab);
+                        if (TEX && tri_win >= 0 && ((ts.mask >> win) & 1)) {
+                            if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
+                            float2 uv;
+                            alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
+                            ts.ALB[(size_t)d * st.n_paths + i] = make_float4(alb.x, alb.y, alb.z, 0.f);
+                            sid = kSidTextured;
+                        }
+                        // the dead channels: the guard's argument is about a scalar term in [+0, 2^96) -- a light's weighted term is one; a segment whose ray goes to the
+                        // sky clears the mask, as a segment that fails the guard does
+                        if (st.deadch) {
+                            const int was = st.DCH[i];
+                            int now = (was & 8) | (x_sky ? 0 : wf_dead_channels(was & 7, alb, l3.x));
+                            if ((now & 7) == 7 && !x_moot) { x_moot = true; now |= 8; }
+                            if (now != was) st.DCH[i] = (unsigned char)now;
+                        }
                     } else {
                         float nl;
                         if (LIGHTS == 1) { L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d); intensity = lt->total; }   // this segment's light, at the intensity of all
@@ -1047,7 +1104,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     nrays += 1;
                 }
             } else if constexpr (SKY) {
-                E = sky_radiance(*sky, u);                            // the environment, in the direction the record holds
+                // (SAMPLE) a ray that left a diffuse segment starts the fold from +0: that segment's shadow rays have accounted for the sky
+                if (!SAMPLE || d == 0 || st.SID[(size_t)(d - 1) * st.n_paths + i] == 0xff)
+                    E = sky_radiance(*sky, u);                        // the environment, in the direction the record holds
             }
             st.SID[(size_t)d * st.n_paths + i] = (unsigned char)sid;
             d = d + 1;
@@ -1073,9 +1132,14 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     const Material m = material_of(sc, sid);
                     alb = mk(m.ar, m.ag, m.ab);
                 }
+                if constexpr (SAMPLE) {                               // the segment's three-channel term
+                    const float4 l4 = sd->L3[(size_t)k * st.n_paths + i];
+                    ans = fold_segment(ans, mk(l4.x, l4.y, l4.z), alb);
+                } else {
                 const float l = st.LS[(size_t)k * st.n_paths + i];
                 ans = fold_segment(ans, l, alb);
                 if (STATS && !wf_fold_bounded(ans, l, alb)) fold_sure = false;
+                }
             }
         }
         if (STATS && !fold_sure && st.deadch && (st.DCH[i] & 8)) wk.dead_unsure++;   // a ray of this path was elided and its chain leaves what the elision was argued for
@@ -1117,7 +1181,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     if (emitX) {
         const float tS = hx.t;                                        // only the value of the shadow ray's nearest hit matters
         flags |= PF_HASX;
-        if (!x_moot && light_hidden(Ox, ux, tS, L)) flags |= PQ_XSPHERE;      // cpu:615 holds for the sphere already: whatever the mesh says, the segment is shaded (the comparison is monotone in t)
+        if (!x_moot && ((SAMPLE && x_sky) ? hx.obj >= 0 : light_hidden(Ox, ux, tS, L))) flags |= PQ_XSPHERE;      // cpu:615 holds for the sphere already: whatever the mesh says, the segment is shaded (the comparison is monotone in t)
         // ... so with any-hit on that ray is not traced through the mesh at all (intersect_all does: a run that counts the reference's work has any-hit off)
         if (!x_moot && (!(flags & PQ_XSPHERE) || !st.anyhit) && wf_root_test<STATS>(sc, st, rx, Ox, ux, wk)) {   // only then does anybody read the record: the traversal, and this kernel if the mesh is hit
             flags |= PF_MESHX;
@@ -1160,20 +1224,21 @@ template <class T, class E, class... Rest> __device__ __forceinline__ const T *a
 template <class T, class... Extra> constexpr bool adv_takes = (std::is_same_v<T, Extra> || ...);
 // Eight waves per SIMD (64 registers) for every form but one: in wf_advance<kFormTex | kFormSoft> the texture lookup's live values and a second binary64 sincos do not fit
 // 64 registers together: 8 spilled.  Seven waves per SIMD, 72 registers, no scratch.
-constexpr int adv_waves(unsigned form) { return (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
+// The sampling forms carry the draw (a 64-bit search, a binary64 quotient) beside the soft lights' sincos: six waves per SIMD, 80 registers.
+constexpr int adv_waves(unsigned form) { return (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
 template <unsigned FORM, class... Extra>
 __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene sc, const Frame fr, const WfState st, const Extra... extra) {
     static_assert(adv_takes<TexScene, Extra...> == ((FORM & kFormTex) != 0) && adv_takes<AnimTable, Extra...> == ((FORM & kFormAnim) != 0) &&
                   adv_takes<WfList, Extra...> == ((FORM & kFormList) != 0) && adv_takes<WfShade, Extra...> == ((FORM & (kFormFill | kFormResume)) != 0) &&
                   adv_takes<WfLights, Extra...> == ((FORM & kFormLights) != 0) && adv_takes<WfSoftLights, Extra...> == ((FORM & kFormSoft) != 0) &&
                   adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0) &&
-                  adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0),
+                  adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0) && adv_takes<WfSkyDist, Extra...> == ((FORM & kFormSkySample) != 0),
                   "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths)
         wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
-                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...));
+                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...), adv_extra<WfSkyDist>(extra...));
     wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 

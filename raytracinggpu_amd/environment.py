@@ -67,6 +67,43 @@ def from_latlong(img, n):
     return _as_map(out, n)
 
 
+def texel_solid_angles(n):
+    """[n, n] float64: the solid angle of every texel, (4 / n^2) / |p|^3 at its centre (p the octahedral point of 1-norm 1); the sum tends to 4 pi"""
+    n = _check_n(n)
+    c = (np.arange(n, dtype=np.float64) + 0.5) / n * 2.0 - 1.0
+    qx, qz = np.meshgrid(c, c, indexing="xy")
+    py = 1.0 - np.abs(qx) - np.abs(qz)
+    low = py < 0
+    px = np.where(low, (1.0 - np.abs(qz)) * np.where(qx < 0, -1.0, 1.0), qx)
+    pz = np.where(low, (1.0 - np.abs(qx)) * np.where(qz < 0, -1.0, 1.0), qz)
+    return (4.0 / (n * n)) / (px * px + py * py + pz * pz) ** 1.5
+
+
+def add_sun(rgb, direction, half_angle, radiance):
+    """a copy of the map rgb [n, n, 3] with a disc of `radiance` (a number or three) added: every texel whose centre lies within half_angle (radians) of `direction`.
+    A disc that holds no centre goes to the nearest texel, its radiance scaled by the disc's solid angle over the texel's: the energy stays what was asked for."""
+    a = np.array(rgb, np.float32)
+    if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 3:
+        raise ValueError(f"an environment is an [n, n, 3] array, not {a.shape}")
+    n = _check_n(a.shape[0])
+    d = np.asarray(direction, np.float64)
+    if d.shape != (3,) or not np.isfinite(d).all() or not np.linalg.norm(d) > 0:
+        raise ValueError("the sun's direction is three finite numbers, not all zero")
+    if not 0 < half_angle <= np.pi:
+        raise ValueError("the sun's half-angle lies in (0, pi]")
+    d = d / np.linalg.norm(d)
+    rad = np.broadcast_to(np.asarray(radiance, np.float64), (3,))
+    cosang = texel_directions(n).astype(np.float64) @ d
+    inside = cosang >= np.cos(half_angle)
+    if inside.any():
+        a[inside] = (a[inside].astype(np.float64) + rad).astype(np.float32)
+    else:
+        y, x = np.unravel_index(np.argmax(cosang), cosang.shape)
+        scale = 2.0 * np.pi * (1.0 - np.cos(half_angle)) / texel_solid_angles(n)[y, x]
+        a[y, x] = (a[y, x].astype(np.float64) + rad * scale).astype(np.float32)
+    return _as_map(a, n)
+
+
 def gradient_sky(zenith, horizon, ground, n):
     """horizon -> zenith with the height above the horizon, horizon -> ground below it (linear in y)"""
     zenith, horizon, ground = (np.asarray(c, np.float64) for c in (zenith, horizon, ground))

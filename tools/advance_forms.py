@@ -6,7 +6,7 @@ here and nowhere else.  form_of(name) -> the word, or None for another kernel.""
 import re
 
 BITS = {"stats": 1 << 0, "first": 1 << 1, "tex": 1 << 2, "anim": 1 << 3, "list": 1 << 4, "fill": 1 << 5, "resume": 1 << 6, "lights": 1 << 7, "soft": 1 << 8,
-        "lens": 1 << 9, "close": 1 << 10, "shutter": 1 << 11, "sky": 1 << 12}
+        "lens": 1 << 9, "close": 1 << 10, "shutter": 1 << 11, "sky": 1 << 12, "sample": 1 << 13}
 _B = BITS
 # the names the forms had as kernels of their own (demangled, spaces dropped)
 OLD = {"wf_advance<false,false>": 0, "wf_advance<true,false>": _B["stats"], "wf_advance<false,true>": _B["first"], "wf_advance<true,true>": _B["first"] | _B["stats"],
@@ -20,7 +20,9 @@ LATER = [_B["first"] | _B["shutter"], _B["first"] | _B["lens"] | _B["shutter"], 
 FORMS = sorted(set(OLD.values()) | set(LATER))                         # the 25 built for a scene without an environment (tests/test_shutter_forms.py holds the number)
 # ... and the four of the environment (kFormSky: the later launches of a chain under a map)
 SKY_FORMS = sorted([_B["sky"], _B["tex"] | _B["sky"], _B["soft"] | _B["sky"], _B["tex"] | _B["soft"] | _B["sky"]])
-ALL_FORMS = sorted(FORMS + SKY_FORMS)                                  # the 29 that are built
+ALL_FORMS = sorted(FORMS + SKY_FORMS)                                  # the 29 that are built without sky sampling (tests/test_sky_forms.py holds the number)
+# ... and the two of sky sampling (kFormSkySample: the later launches of a chain whose shadow rays may go to the environment; any lights take the soft route)
+SKY_SAMPLE_FORMS = sorted([_B["soft"] | _B["sky"] | _B["sample"], _B["tex"] | _B["soft"] | _B["sky"] | _B["sample"]])
 
 
 def form(*names):

@@ -205,7 +205,9 @@ ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
            "wf_advance_shutter": (("shutter",), False), "wf_advance_tex_shutter": (("tex", "shutter"), False),
            # the environment (WfSky): the four later launches of a chain under a map, whole (no labels)
            "wf_advance_sky": (("sky",), False), "wf_advance_tex_sky": (("tex", "sky"), False),
-           "wf_advance_soft_sky": (("soft", "sky"), False), "wf_advance_tex_soft_sky": (("tex", "soft", "sky"), False)}
+           "wf_advance_soft_sky": (("soft", "sky"), False), "wf_advance_tex_soft_sky": (("tex", "soft", "sky"), False),
+           # sky sampling (WfSkyDist): the two later launches of a sampling chain, whole (no labels)
+           "wf_advance_soft_sky_sample": (("soft", "sky", "sample"), False), "wf_advance_tex_soft_sky_sample": (("tex", "soft", "sky", "sample"), False)}
 
 
 def advance_forms_counts(asm):
@@ -274,7 +276,8 @@ def main():
     # the first-shade cache, the closing launch of a plain chain, several lights, lights with a radius, the thin lens (ADVANCE)
     for name in ("wf_advance_fill", "wf_advance_resume", "wf_advance_close", "wf_advance_lights", "wf_advance_tex_lights", "wf_advance_soft", "wf_advance_tex_soft", "wf_advance_lens",
                  "wf_advance_shutter_first", "wf_advance_lens_shutter_first", "wf_advance_shutter", "wf_advance_tex_shutter",
-                 "wf_advance_sky", "wf_advance_tex_sky", "wf_advance_soft_sky", "wf_advance_tex_soft_sky"):
+                 "wf_advance_sky", "wf_advance_tex_sky", "wf_advance_soft_sky", "wf_advance_tex_soft_sky",
+                 "wf_advance_soft_sky_sample", "wf_advance_tex_soft_sky_sample"):
         res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
