@@ -472,6 +472,63 @@ int rt_scene_get_environment_sampling(const rt_ctx *ctx, float *share);
 int rt_kat_environment_table(rt_ctx *ctx, uint32_t *c_out, uint64_t *prefix_out, uint64_t *total);
 int rt_kat_environment_sample(rt_ctx *ctx, int count, const uint32_t *hs, const int32_t *seg, uint32_t *texel_out, float *dir_out, float *g_out);
 
+/* --- EMISSIVE MESHES: area lights seen by paths and sampled by shadow rays (ABI 6, additive).  A mesh object may carry a radiance Le = (r, g, b), every component in
+ *     [+0, 2^96) as the environment's texels; Le all +0: the mesh does not emit.  Spheres cannot emit.  An emitter is two-sided and is geometry like any other mesh: it
+ *     occludes every ray.  It absorbs: its albedo, mirror flag, refraction indices, smooth normals and texture are not read by the render chain.  With no emitter set every
+ *     frame is launch for launch what it is without these entries, and no new kernel runs.  The device steps are emit_draw and emit_weight in rt_shade.hip.h, beside
+ *     sky_draw and sky_weight; the model is tests/emission_model.py.
+ *     Binary32 with one rounding per operation, no fused multiply-add, quotients correctly rounded (rt_div.h), unless stated otherwise.
+ *     THE HIT.  A continuation ray of segment d whose nearest object -- mesh and sphere winners decided as ever -- is an emitter ends its path there: no shadow ray and no
+ *     continuation ray are emitted, SID[d] = 0xff, and the fold starts from E: E = Le if d == 0, or SID[d - 1] == 0xff (a mirror or glass hit), or the effective share s
+ *     is 0; otherwise E = +0 -- the segment's shadow rays have accounted for the emitters (the rule of sky sampling's miss).  The ray counts in .w as any continuation ray.
+ *     THE TABLE runs over all triangles of the scene in stored (visit) order: the leaves of each mesh's tree as the traversal reaches them (the right child before the left,
+ *     ascending inside a leaf; after a rebuild the order tri_order_out and the new tree give), the meshes one after the other in object order.
+ *       1. A2(t) = rt_sqrtf(norm2(Nt)), Nt the record's raw cross(e1, e2): twice the area.
+ *       2. Y(obj) = fl(fl(r + g) + b) of the mesh's radiance.
+ *       3. W(t) = fl(A2(t) Y(obj of t)); +0 for the triangles of a mesh that does not emit.  Every W(t) must be finite: a W that overflows (a radiance near 2^96 on a
+ *          triangle whose A2 is 2^32 or more) would make every quotient of step 4 zero or NaN and the table flat, so the build refuses it -- RT_ERR_INVALID, "emission"
+ *          in the text, from the frame or known answer that asked for the table, until a radiance is lowered.
+ *       4. and 5. are steps 4 and 5 of the sky table, word for word: Wmax = max W(t), Wmax == 0: the table is EMPTY; c(t) = W(t) > 0 ? max(1, (uint32)(fl(W(t) / Wmax)
+ *          * 2^31)) : 0; prefix[t] = the inclusive 64-bit sum of c; total = the last prefix <= 2^51.
+ *     THE DRAW of segment d of the path whose sample key is hs: four draws at depth (1 << 27) + d, dims 0 to 3 (keys 2^29 + 4 d + dim; the jitter, bounce, pick and share
+ *     draws sit at 4 d' + dim with d' <= RT_MAX_SEGMENTS, the lens and the shutter at 2^30 + {0, 1, 2}, the shells at 2^31 + 4 d + {0, 1}, the sky's draws at 3 2^30 + 4 d +
+ *     dim: none reaches these).  K, X and the triangle t as in the sky's draw (uniform24 of dims 0 and 1; the least t with prefix[t] >= X, so c(t) > 0).  r1, r2 =
+ *     uniform01 of dims 2 and 3; if fl(r1 + r2) > 1 then r1 = fl(1 - r1), r2 = fl(1 - r2).  Q = fl(fl(A + fl(r1 e1)) + fl(r2 e2)) per component, from t's record.
+ *     THE ESTIMATE at a diffuse hit P with normal N: v = Q - P, d2 = norm2(v), wl = normalize(v), mx = max(dot(N, wl), 0), cl = |dot(normalize(Nt), wl)|,
+ *     g = (float)(((((double)mx (double)cl) (double)A2) (double)total) / ((2.0 (double)c(t)) (double)d2)) -- binary64, rounded to binary32 once -- which is mx cl / d2
+ *     over the area density c / total * 2 / A2.  The direct term is l_c = w_emit * (g * Le_c) per channel, Le the radiance of t's mesh.
+ *     THE RAY starts at Pa = P + eps N and aims at L' = Q + kappa (Pa - Q), kappa = 2^-10: per component fl(Q_k + fl(kappa fl(Pa_k - Q_k))).  From there on it is a point
+ *     light's shadow ray to L': shadow_dir, the any-hit bound of (Pa, nl), the spheres, and it is blocked iff light_hidden(Pa, Pp, L').  Why kappa: the ray meets the
+ *     emitter's own plane at nl / (1 - kappa), nl = |L' - Pa| -- a relative margin of 2^-10 in length, 2^-9 in the squared lengths light_hidden compares, over the 2^-20
+ *     or so of rounding that comparison carries, whatever the scene's scale and eps are: the emitter never shadows its own sample.  The price is a known blind band: an
+ *     occluder within 0.1 % of the distance in front of the emitter is not seen by that ray.  The ray is not traced when the three words of l are +0 and any-hit is on.  It
+ *     counts in .w as any shadow ray.
+ *     THE SHARE.  The context holds a share in [0, 1]; the default is 0.5 and rt_scene_upload* resets it to 0.5.  The effective s is 0 if the table is empty or the share
+ *     is 0, 1 if the lights' total intensity is +-0, the share otherwise.  Segment d draws r_s = uniform01(hs, d + 1, 3); its one shadow ray goes to an emitter iff r_s <= s,
+ *     with w_emit = fl(1 / s); otherwise to the light the list picks (a point of its shell), unchanged, and its l is multiplied by w_light = fl(1 / (1 - s)), the term
+ *     (l, l, l).  Both weights are host divisions.  THE FOLD runs per channel, as under sky sampling.
+ *     DEAD CHANNELS: a segment whose ray goes to an emitter clears the path's mask; a light's weighted term is guarded as before.  RT_DEAD_CHANNELS=0 renders the same words.
+ *     Rendered by the wavefront variants' launch chain (two forms of wf_advance, kFormEmit; any lights, always through the soft lights' table; the lens, poses, row
+ *     shares, RT_PARTS, batches, rt_render_async, pipelining), which keeps no still-view cache while a mesh emits.  RT_ERR_UNSUPPORTED, outputs untouched, "emission" in the
+ *     error text: the variants path, lockstep and global, rt_count_work, rt_render_counts*, rt_render_device_batch_scenes with scenes, and any frame while the scene also
+ *     has an environment or the shutter is on.  The feature-buffer and denoiser entries see an emitter as the ordinary object it is.  rt_multi_* contexts have no such entries.
+ *     rt_scene_set_emission(ctx, object_slot, rgb): RT_ERR_INVALID, the state untouched, for a sphere's slot, a slot outside the scene, a NULL rgb, a component outside
+ *     [+0, 2^96) or NaN (-0 included); RT_ERR_NO_SCENE without an upload.  rt_scene_get_emission: the radiance as set, zeros for a mesh that does not emit.
+ *     rt_scene_set_emission_sampling(ctx, share): RT_ERR_INVALID for a share outside [0, 1] or NaN.  A refused get writes nothing.  rt_scene_upload* clears all emission.
+ *     Neither call touches the still view: a chain under an emitter neither reads nor writes its caches, and a scene whose emission was set and removed again finds
+ *     them as it left them -- its frames and its cache counters are those of a context that never heard of these calls.
+ *     The table is rebuilt, into a buffer of its own that replaces the old one after a device-wide wait, before the next frame or known answer that follows a change of
+ *     an emission or of the scene's triangles (rt_mesh_transform[_of], rt_mesh_rebuild[_of|_mode], rt_mesh_set_vertices*).
+ *     Known answers: rt_kat_emission_table reads the table back -- c and prefix, n_triangles each (the scene's count, written to *n_triangles: either array may be NULL,
+ *     a first call with both NULL asks for the count) and the total; no emitter or an empty table: total 0 and zeros.  rt_kat_emission_sample runs the draw on `count`
+ *     explicit (hs, seg) pairs: the triangle and the point Q (count x 3); RT_ERR_INVALID without a table to draw from. */
+int rt_scene_set_emission(rt_ctx *ctx, int object_slot, const float rgb[3]);
+int rt_scene_get_emission(const rt_ctx *ctx, int object_slot, float rgb[3]);
+int rt_scene_set_emission_sampling(rt_ctx *ctx, float share);
+int rt_scene_get_emission_sampling(const rt_ctx *ctx, float *share);
+int rt_kat_emission_table(rt_ctx *ctx, uint32_t *c_out, uint64_t *prefix_out, uint64_t *total, int32_t *n_triangles);
+int rt_kat_emission_sample(rt_ctx *ctx, int count, const uint32_t *hs, const int32_t *seg, uint32_t *tri_out, float *point_out);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

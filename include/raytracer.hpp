@@ -687,6 +687,23 @@ public:
         check(rt_scene_get_environment_sampling(ctx_, &share), "rt_scene_get_environment_sampling");
         return share;
     }
+    // Emissive meshes (rt_scene_set_emission): the radiance of the mesh at an object position, (0, 0, 0) for none; and the share in [0, 1] of the shadow rays drawn
+    // towards the emitters (rt_scene_set_emission_sampling; an upload sets 0.5)
+    void set_emission(int object_slot, const Vector &rgb) {
+        const float v[3] = {rgb[0], rgb[1], rgb[2]};
+        check(rt_scene_set_emission(ctx_, object_slot, v), "rt_scene_set_emission");
+    }
+    Vector emission(int object_slot) {
+        float v[3] = {0.f, 0.f, 0.f};
+        check(rt_scene_get_emission(ctx_, object_slot, v), "rt_scene_get_emission");
+        return Vector(v[0], v[1], v[2]);
+    }
+    void set_emission_sampling(float share) { check(rt_scene_set_emission_sampling(ctx_, share), "rt_scene_set_emission_sampling"); }
+    float emission_sampling() {
+        float share = 0.f;
+        check(rt_scene_get_emission_sampling(ctx_, &share), "rt_scene_get_emission_sampling");
+        return share;
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

@@ -44,7 +44,9 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_scene_set_light_radii", "rt_scene_get_light_radii", "rt_scene_set_light_radius_at",
            "rt_camera_set_lens", "rt_camera_get_lens", "rt_scene_set_shutter", "rt_scene_get_shutter",
            "rt_scene_set_environment", "rt_scene_get_environment", "rt_kat_environment",
-           "rt_scene_set_environment_sampling", "rt_scene_get_environment_sampling", "rt_kat_environment_table", "rt_kat_environment_sample"]
+           "rt_scene_set_environment_sampling", "rt_scene_get_environment_sampling", "rt_kat_environment_table", "rt_kat_environment_sample",
+           "rt_scene_set_emission", "rt_scene_get_emission", "rt_scene_set_emission_sampling", "rt_scene_get_emission_sampling",
+           "rt_kat_emission_table", "rt_kat_emission_sample"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -452,6 +454,12 @@ def load():
     L.rt_scene_get_environment_sampling.argtypes = [vp, C.POINTER(C.c_float)]
     L.rt_kat_environment_table.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rt_kat_environment_sample.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.rt_scene_set_emission.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    L.rt_scene_get_emission.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    L.rt_scene_set_emission_sampling.argtypes = [vp, C.c_float]
+    L.rt_scene_get_emission_sampling.argtypes = [vp, C.POINTER(C.c_float)]
+    L.rt_kat_emission_table.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+    L.rt_kat_emission_sample.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -843,6 +851,47 @@ class Context:
         self._check(self._L.rt_kat_environment_sample(self._h, int(h.size), h.ctypes.data_as(up), d.ctypes.data_as(C.POINTER(C.c_int32)), texel.ctypes.data_as(up),
                                                       dirs.ctypes.data_as(fp), g.ctypes.data_as(fp)))
         return texel, dirs, g
+
+    # --- emissive meshes (rt_scene_set_emission): a mesh's radiance, the share of the shadow rays drawn towards the emitters, and the table's known answers
+    def set_emission(self, object_slot, rgb):
+        """rt_scene_set_emission: the radiance (r, g, b) of the mesh at object_slot; (0, 0, 0): it does not emit"""
+        v = (C.c_float * 3)(*[float(x) for x in rgb])
+        self._check(self._L.rt_scene_set_emission(self._h, int(object_slot), v))
+
+    def emission(self, object_slot):
+        """rt_scene_get_emission -> (r, g, b) as set"""
+        v = (C.c_float * 3)()
+        self._check(self._L.rt_scene_get_emission(self._h, int(object_slot), v))
+        return tuple(float(x) for x in v)
+
+    def set_emission_sampling(self, share):
+        """rt_scene_set_emission_sampling: share in [0, 1]; an upload sets 0.5"""
+        self._check(self._L.rt_scene_set_emission_sampling(self._h, C.c_float(share)))
+
+    def emission_sampling(self):
+        """rt_scene_get_emission_sampling -> the share as set"""
+        s = C.c_float(0)
+        self._check(self._L.rt_scene_get_emission_sampling(self._h, C.byref(s)))
+        return float(s.value)
+
+    def kat_emission_table(self):
+        """rt_kat_emission_table -> (c [n_triangles] uint32, prefix [n_triangles] uint64, total) over the scene's triangles in stored order; no emitter or an empty table: zeros and 0"""
+        total, nt = C.c_uint64(0), C.c_int32(0)
+        self._check(self._L.rt_kat_emission_table(self._h, None, None, C.byref(total), C.byref(nt)))
+        c = np.zeros(int(nt.value), np.uint32)
+        prefix = np.zeros(int(nt.value), np.uint64)
+        self._check(self._L.rt_kat_emission_table(self._h, c.ctypes.data_as(C.POINTER(C.c_uint32)), prefix.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total), C.byref(nt)))
+        return c, prefix, int(total.value)
+
+    def kat_emission_sample(self, hs, seg):
+        """rt_kat_emission_sample: the draw on explicit sample keys hs [k] uint32 and segments seg [k] -> (triangle [k] uint32 in stored order, point [k, 3] float32)"""
+        h = np.ascontiguousarray(hs, dtype=np.uint32).ravel()
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(seg, np.int32), h.shape), dtype=np.int32)
+        tri, point = np.zeros(h.size, np.uint32), np.zeros((h.size, 3), np.float32)
+        up = C.POINTER(C.c_uint32)
+        self._check(self._L.rt_kat_emission_sample(self._h, int(h.size), h.ctypes.data_as(up), d.ctypes.data_as(C.POINTER(C.c_int32)), tri.ctypes.data_as(up),
+                                                   point.ctypes.data_as(C.POINTER(C.c_float))))
+        return tri, point
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

@@ -119,6 +119,8 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     ctx->vcsr_valid = false;
     ctx->env_share = 0.f; ctx->env_total = 0;                            // ... draws no shadow rays towards one (rt_scene_set_environment_sampling)
     ctx->env_n = 0; ctx->env_rgb.clear();                                // ... and has no environment (rt_scene_set_environment; the buffer stays for the frames in flight; the still view: below)
+    memset(ctx->emit_le, 0, sizeof(ctx->emit_le)); ctx->emit_mask = 0;    // ... and no mesh of it emits (rt_scene_set_emission; the buffer stays for the frames in flight),
+    ctx->emit_total = 0; ctx->emit_dirty = false; ctx->emit_share = 0.5f; // the share at its default
     ctx->still.shading_changed();
     ctx->still.mesh_changed();
     if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(ctx, RT_ERR_INVALID, "bad sphere array");

@@ -205,7 +205,20 @@ struct rt_ctx {
     unsigned long long env_total = 0;
     int env_dist_nb = 0;
     DevBuf env_dist{bufs};
-    DevBuf nrm{bufs};                                                  // smooth shading: 3 normals per triangle, visit order
+    // Emissive meshes (rt_scene_set_emission): the radiance of every object position (zeros: it does not emit), the mask of the emitting ones, the share of the shadow
+    // rays that go to them, and the table the draws search -- one buffer: the prefixes (emit_nt of 64 bits), the block level (emit_nb), c (emit_nt of 32 bits) and, at the
+    // next multiple of 16 bytes, the radiances (kMaxObjects float4: r, g, b, Y).  emit_total == 0: no table.  The table is stale while emit_dirty is set or emit_gen is
+    // not the still view's triangle generation (every entry that changes a triangle or the visit order moves that, and nothing else does); emit_refresh (rt_host_render.hip.h) rebuilds it, into a
+    // new buffer, before anything reads it.  rt_scene_upload* clears the emission and sets the share to 0.5.
+    float emit_le[rtk::kMaxObjects][3] = {};
+    unsigned emit_mask = 0;
+    float emit_share = 0.5f;
+    bool emit_dirty = false;
+    uint64_t emit_gen = 0;
+    unsigned long long emit_total = 0;
+    int emit_nt = 0, emit_nb = 0;
+    DevBuf emit_dist{bufs};
+    DevBuf nrm{bufs};                                                 // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.
     DevBuf tex_uv{bufs}, tex_table{bufs};

@@ -308,6 +308,63 @@ int rt_scene_get_environment_sampling(const rt_ctx *ctx, float *share) {
     return RT_OK;
 }
 
+// ---- emissive meshes (raytrace_hip.h "emissive meshes"): host state plus the table over the scene's triangles (rt_skydist.hip.h) ----
+// index into Scene::mesh of the mesh at position object_slot of Scene::objects; -1: outside the scene, or a sphere's position
+static int mesh_at(const rtk::Scene &sc, int object_slot) {
+    for (int k = 0; k < sc.n_meshes; ++k) if (sc.mesh[k].obj == object_slot) return k;
+    return -1;
+}
+// (the table itself: emit_dist_of and emit_refresh in rt_host_render.hip.h, where a frame's chain asks for it)
+
+// a component of a radiance: in [+0, 2^96), the range of the environment's texels (NaN, +-inf, negative and -0 fail the bit test)
+static bool emit_component_ok(float v) { return __builtin_bit_cast(uint32_t, v) < 0x6f800000u; }
+
+int rt_scene_set_emission(rt_ctx *ctx, int object_slot, const float rgb[3]) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (!rgb) return fail(ctx, RT_ERR_INVALID, "emission: rgb is NULL");
+    if (mesh_at(ctx->scene, object_slot) < 0) return fail(ctx, RT_ERR_INVALID, "emission: object_slot %d is outside the scene or a sphere's; only a mesh emits", object_slot);
+    for (int k = 0; k < 3; ++k)
+        if (!emit_component_ok(rgb[k])) return fail(ctx, RT_ERR_INVALID, "emission: component %d (%g) is outside [+0, 2^96)", k, (double)rgb[k]);
+    float *le = ctx->emit_le[object_slot];
+    if (memcmp(le, rgb, 3 * sizeof(float)) == 0) return RT_OK;
+    memcpy(le, rgb, 3 * sizeof(float));
+    const bool emits = rgb[0] > 0.f || rgb[1] > 0.f || rgb[2] > 0.f;
+    ctx->emit_mask = emits ? ctx->emit_mask | (1u << object_slot) : ctx->emit_mask & ~(1u << object_slot);
+    ctx->emit_dirty = true;
+    // (The still view is left alone.  Its keys hold nothing an emission changes, a chain under an emitter neither reads nor writes its three buffers -- no begin, every
+    // level off -- and the scene without its emitter is the scene the levels were stored for: a scene that lost its last emitter finds them as it left them.)
+    return RT_OK;
+}
+
+int rt_scene_get_emission(const rt_ctx *ctx, int object_slot, float rgb[3]) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!rgb) return fail(c, RT_ERR_INVALID, "emission: rgb is NULL");
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    if (mesh_at(ctx->scene, object_slot) < 0) return fail(c, RT_ERR_INVALID, "emission: object_slot %d is outside the scene or a sphere's; only a mesh emits", object_slot);
+    memcpy(rgb, ctx->emit_le[object_slot], 3 * sizeof(float));
+    return RT_OK;
+}
+
+int rt_scene_set_emission_sampling(rt_ctx *ctx, float share) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (!(share >= 0.f && share <= 1.f)) return fail(ctx, RT_ERR_INVALID, "emission sampling: the share %g is outside [0, 1]", (double)share);
+    if (share == 0.f) share = 0.f;                                     // (-0 is 0)
+    ctx->emit_share = share;                                           // (the table depends on the scene and the radiances alone)
+    return RT_OK;
+}
+
+int rt_scene_get_emission_sampling(const rt_ctx *ctx, float *share) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (!share) return fail(c, RT_ERR_INVALID, "share is NULL");
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    *share = ctx->emit_share;
+    return RT_OK;
+}
+
 // ---- the environment map (raytrace_hip.h "environment"): host state plus one device buffer of the context's; make_frame captures pointer and size ----
 int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");

@@ -23,13 +23,90 @@ bool lights_soft(const rt_ctx *ctx) {
     for (int k = 0; k < ctx->n_lights; ++k) if (ctx->light_radii[k] > 0.f) return true;
     return false;
 }
+// Emissive meshes (rt_scene_set_emission): what the draws and the hits read of the context's table (a mesh emits and the scene has triangles: the buffer exists)
+static rtk::WfEmit emit_dist_of(const rt_ctx *ctx) {
+    const unsigned long long *prefix = static_cast<const unsigned long long *>(ctx->emit_dist.p);
+    const unsigned int *c = reinterpret_cast<const unsigned int *>(prefix + ctx->emit_nt + ctx->emit_nb);
+    const size_t le_off = (((size_t)ctx->emit_nt * 12 + (size_t)ctx->emit_nb * 8) + 15) & ~(size_t)15;
+    return rtk::WfEmit{prefix, prefix + ctx->emit_nt, c, reinterpret_cast<const float4 *>(static_cast<const char *>(ctx->emit_dist.p) + le_off), ctx->emit_total, ctx->emit_nt, ctx->emit_nb};
+}
+// The table as the scene and the radiances are now, if it is stale: before a chain is planned and before a known answer is read.  A rebuilt table gets a buffer of its
+// own, installed after a device-wide wait (the frames that captured the old one are done: the rule of the environment's buffer); a failure leaves the old state, still stale.
+// RT_ERR_INVALID, and so the frame or known answer that asked: a weight W(t) that is not finite.
+static int emit_refresh(rt_ctx *ctx) {
+    if (!ctx->emit_dirty && ctx->emit_gen == ctx->still.triangle_generation()) return RT_OK;
+    const rtk::Scene &sc = ctx->scene;
+    unsigned long long total = 0;
+    int nb = 0;
+    const int nt = sc.n_tris;
+    DevBuf fresh;
+    if (ctx->emit_mask != 0 && nt > 0 && sc.tri) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        RT_OWN_STREAM(ctx);
+        hipStream_t q = own_stream(ctx);
+        nb = (nt + rtk::kSkyBlock - 1) / rtk::kSkyBlock;
+        rtk::EmitMeshes em{};
+        float4 le[rtk::kMaxObjects] = {};
+        em.n = sc.n_meshes;
+        for (int k = 0; k < sc.n_meshes; ++k) {
+            const float *v = ctx->emit_le[sc.mesh[k].obj];
+            const float Y = (v[0] + v[1]) + v[2];                       // (one rounding per sum: this file is compiled without contraction)
+            em.tri_begin[k] = sc.mesh[k].tri_begin;
+            em.Y[k] = Y;
+            le[sc.mesh[k].obj] = make_float4(v[0], v[1], v[2], Y);
+        }
+        const size_t le_off = (((size_t)nt * 12 + (size_t)nb * 8) + 15) & ~(size_t)15;
+        DevBuf tmp;
+        int rc;
+        if ((rc = ensure(ctx, tmp, (size_t)nt * sizeof(float) + 16)) != RT_OK || (rc = ensure(ctx, fresh, le_off + sizeof(le))) != RT_OK) return rc;
+        float *W = static_cast<float *>(tmp.p);
+        unsigned int *wmax = reinterpret_cast<unsigned int *>(W + nt);
+        unsigned long long *prefix = static_cast<unsigned long long *>(fresh.p), *blk = prefix + nt;
+        unsigned int *c = reinterpret_cast<unsigned int *>(blk + nb);
+        const dim3 g((unsigned)nb), b(rtk::kSkyBlock);
+        RT_HIP(ctx, hipMemsetAsync(wmax, 0, sizeof(unsigned int), q));
+        RT_HIP(ctx, hipMemcpyAsync(static_cast<char *>(fresh.p) + le_off, le, sizeof(le), hipMemcpyHostToDevice, q));
+        hipLaunchKernelGGL(rtk::emit_dist_weights, g, b, 0, q, sc.tri, nt, em, W, wmax);
+        RT_HIP(ctx, hipGetLastError());
+        unsigned int wmax_bits = 0;
+        RT_HIP(ctx, hipMemcpyAsync(&wmax_bits, wmax, sizeof(wmax_bits), hipMemcpyDeviceToHost, q));
+        RT_HIP(ctx, hipStreamSynchronize(q));
+        // area times radiance overflowed (a radiance near 2^96 on a triangle of 2^32 or more): every quotient W / Wmax would be 0 or NaN and the table silently flat
+        if (wmax_bits >= 0x7f800000u)
+            return fail(ctx, RT_ERR_INVALID, "emission: the weight of a triangle, twice its area times the sum of its mesh's radiance, is not finite; lower the radiance (rt_scene_set_emission)");
+        if (wmax_bits != 0) {                                          // (zero: every emitting triangle is degenerate -- the table is empty)
+            hipLaunchKernelGGL(rtk::sky_dist_quantise, g, b, 0, q, W, nt, wmax, c, blk);
+            hipLaunchKernelGGL(rtk::sky_dist_scan, dim3(1), dim3(rtk::kSkyScanLevel), 0, q, blk, nb);
+            hipLaunchKernelGGL(rtk::sky_dist_prefix, g, b, 0, q, c, nt, blk, prefix);
+            RT_HIP(ctx, hipGetLastError());
+            RT_HIP(ctx, hipMemcpyAsync(&total, blk + (nb - 1), sizeof(total), hipMemcpyDeviceToHost, q));
+            RT_HIP(ctx, hipStreamSynchronize(q));
+        }
+        RT_HIP(ctx, hipDeviceSynchronize());
+    }
+    ctx->emit_total = total;
+    if (fresh.p) { ctx->emit_dist = std::move(fresh); ctx->emit_nt = nt; ctx->emit_nb = nb; }   // (also under an empty table: the radiances live in it, and a ray may hit an emitter)
+    ctx->emit_dirty = false;
+    ctx->emit_gen = ctx->still.triangle_generation();
+    return RT_OK;
+}
+
 // While the scene holds several lights, or a light with a radius, only the kernels that take the table may render it: every other entry refuses (outputs untouched)
 // wf_chain: the caller is a frame's own chain of wf_advance launches, which takes all of the above -- but not the shutter together with a light list or a radius: the four
 // shutter forms are built for the Scene's one point light
 // The environment (rt_scene_set_environment) is rendered by the chain's four kFormSky forms alone: not with the shutter on, and by no other entry
 // Sky sampling (rt_scene_set_environment_sampling) is rendered by the chain's two kFormSkySample forms and refused wherever the environment is; with the share positive
 // the refusal says "environment sampling"
+// Emissive meshes (rt_scene_set_emission) are rendered by the chain's two kFormEmit forms alone: not under an environment, not with the shutter on, and by no other entry;
+// the refusal says "emission".  The chain's own call brings the sampling table up to date first (emit_refresh)
 int lights_refuse(rt_ctx *ctx, const char *what, bool wf_chain = false) {
+    if (ctx && ctx->emit_mask != 0) {
+        if (!wf_chain) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: a mesh of the scene has an emission; only wf_advance's emission forms meet it (rt_scene_set_emission)", what);
+        if (ctx->env_n > 0 || ctx->shutter_on)
+            return fail(ctx, RT_ERR_UNSUPPORTED, "%s: a mesh of the scene has an emission and %s; no wf_advance form takes both (rt_scene_set_emission)", what,
+                        ctx->env_n > 0 ? "the scene has an environment" : "the shutter is on");
+        if (int rc = emit_refresh(ctx); rc != RT_OK) return rc;
+    }
     const char *env_what = ctx && ctx->env_share > 0.f ? "an environment with environment sampling on" : "an environment";
     if (wf_chain) {
         if (ctx && ctx->env_n > 0 && ctx->shutter_on)
@@ -163,7 +240,7 @@ Variant ask_variant(const rt_ctx *ctx, int variant, const rt_camera_pose *pose, 
     // 0.220 ms per frame (profiles/round5/ab_spheres_only.txt).  A posed camera exists in the wavefront family only.
     if (variant == RT_VARIANT_AUTO) {
         const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1 && !lights_soft(ctx) &&
-                              !(ctx->lens_radius > 0.f) && !ctx->shutter_on && ctx->env_n == 0;
+                              !(ctx->lens_radius > 0.f) && !ctx->shutter_on && ctx->env_n == 0 && ctx->emit_mask == 0;
         variant = lockstep ? RT_VARIANT_LOCKSTEP : RT_VARIANT_WAVEFRONT_QUEUE;
     }
     // BASELINE config 4 / north star: "hot triangle vertices and top BVH levels staged in LDS" = the work-stack traversal kernel
@@ -215,6 +292,7 @@ struct Chunk {
     bool shutter_on = false;
     rtk::WfSky sky{};                                                 // sky.n > 0: the scene has an environment -- the argument of the chunk's kFormSky launches (every one after the opening)
     rtk::WfSkyDist sd{};                                              // sd.s > 0: sky sampling is in effect -- the table, the effective share and the weights of the kFormSkySample launches (L3: per part)
+    rtk::WfEmit em{};                                                 // em.mask != 0: a mesh emits -- the table, the effective share, the weights and the mask of the kFormEmit launches (L3: per part)
 };
 // what the draws read of the context's table (env_total > 0)
 static rtk::WfSkyDist sky_dist_of(const rt_ctx *ctx) {
@@ -255,7 +333,8 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
     c.sky = rtk::WfSky{ctx->env_n > 0 ? static_cast<const float4 *>(ctx->env.p) : nullptr, ctx->env_n};   // (rt_scene_set_environment) the map's buffer as it is now: a new map gets a new one
     c.soft = lights_soft(ctx);
     const bool sampling = ctx->env_n > 0 && ctx->env_share > 0.f && ctx->env_total > 0;   // (an empty table: the effective share is 0)
-    if (ctx->n_lights > 1 || c.soft || sampling) {                    // (sky sampling takes the soft route with any lights: one point light is a soft list of one)                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
+    const bool emit = ctx->emit_mask != 0;                            // (emissive meshes take the soft route too)
+    if (ctx->n_lights > 1 || c.soft || sampling || emit) {                    // (sky sampling takes the soft route with any lights: one point light is a soft list of one)                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
         rtk::WfLights &lt = c.sl.lt;
         const rt_light one{{ctx->scene.Lx, ctx->scene.Ly, ctx->scene.Lz}, ctx->scene.intensity};   // a soft list of one lives in `scene` alone, as every list of one
         float prefix = 0.f;
@@ -274,6 +353,14 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
         c.sd.s = c.sl.lt.total == 0.f ? 1.f : ctx->env_share;
         c.sd.w_sky = 1.f / c.sd.s;
         c.sd.w_light = c.sd.s < 1.f ? 1.f / (1.f - c.sd.s) : 0.f;     // (at s = 1 the lights are never sampled)
+    }
+    if (emit) {                                                       // (lights_refuse brought the table up to date: emit_refresh)
+        // the effective share: 0 if the table is empty or the share is 0, 1 if the lights give nothing (total +-0), the share otherwise; the weights, one division each
+        c.em = emit_dist_of(ctx);
+        c.em.mask = ctx->emit_mask;
+        c.em.s = (ctx->emit_total == 0 || !(ctx->emit_share > 0.f)) ? 0.f : c.sl.lt.total == 0.f ? 1.f : ctx->emit_share;
+        c.em.w_emit = c.em.s > 0.f ? 1.f / c.em.s : 0.f;
+        c.em.w_light = c.em.s < 1.f ? 1.f / (1.f - c.em.s) : 0.f;
     }
 }
 
@@ -564,7 +651,7 @@ hipStream_t chain_stream(const rt_ctx *ctx, const Chunk &c, bool own0, int j);
 // The same holds while the shutter is on (rt_scene_set_shutter): a path's spheres and light depend on its sample.  And under an environment (rt_scene_set_environment): the
 // records know no miss that shines and no sky form resumes from them.  (The first-hit level would stay valid; DESIGN.md section 5.21 keeps that for later.)
 bool still_eligible(const rt_ctx *ctx, const Chunk &c, const TravPlan &t) {
-    return !(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
+    return !(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && c.em.mask == 0 && ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
            ctx->knobs.debug_trav == -2;
 }
 // What the camera rays' hits depend on besides the mesh, bit for bit (the RAY KEY), and what segment 0's shading and shadow rays depend on besides the ray key and what is
@@ -623,7 +710,7 @@ int size_wavefront(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool &qr_grown) 
         (rc = ensure(ctx, ctx->wfSID, np * nseg)) != RT_OK || (rc = ensure(ctx, ctx->wfDCH, np)) != RT_OK || (rc = ensure(ctx, ctx->wfLS, np * 4 * nseg)) != RT_OK)
         return rc;
     if (ctx->tex_mask != 0 && (rc = ensure(ctx, ctx->wfALB, np * 16 * nseg)) != RT_OK) return rc;   // a textured mesh: the per-segment albedo store of wf_advance<kFormTex>
-    if (c.sd.s > 0.f && (rc = ensure(ctx, ctx->wfL3, np * 16 * nseg)) != RT_OK) return rc;          // sky sampling: the three-channel direct term of every diffuse segment
+    if ((c.sd.s > 0.f || c.em.mask != 0) && (rc = ensure(ctx, ctx->wfL3, np * 16 * nseg)) != RT_OK) return rc;   // sky sampling, emissive meshes: the three-channel direct term of every diffuse segment
     // a still view's levels: the first two allocated by the first eligible frame, the records by the first chunk one of whose chains may store them (a new allocation
     // empties its level: StillView::begin)
     if (w.still >= 1 && (rc = ensure(ctx, ctx->wfM0, w.px * 8)) != RT_OK) return rc;
@@ -729,12 +816,12 @@ int end_chains(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool own0) {
 
 // What a chain's wf_advance launches may take beyond (Scene, Frame, WfState): each form takes the ones its bits name (rt_still.h kForm*), in this order (sl.lt: the table of
 // the forms without radii)
-struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; rtk::WfSky sky{}; rtk::WfSkyDist sd{}; };
+struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; rtk::WfSky sky{}; rtk::WfSkyDist sd{}; rtk::WfEmit em{}; };
 struct AdvLaunch {
     dim3 grid, block; hipStream_t q; const rtk::Scene &scn; const rtk::Frame &fr; const rtk::WfState &st;
     template <unsigned FORM, class... Extra> void go(const Extra &... extra) const { hipLaunchKernelGGL((rtk::wf_advance<FORM, Extra...>), grid, block, 0, q, scn, fr, st, extra...); }
 };
-// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 31 instantiations, one case each (DESIGN.md section 5.2 says who launches
+// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 33 instantiations, one case each (DESIGN.md section 5.2 says who launches
 // each and which test runs it).  The entries refuse what has no form before a chain is planned (lights_refuse, resolve_variant), so the default is not reached.
 int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_t q, const rtk::Scene &scn, const rtk::Frame &fr, const rtk::WfState &st, const AdvArgs &a) {
     using namespace rtk;
@@ -757,6 +844,8 @@ int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_
     case kFormTex | kFormSoft | kFormSky: l.go<kFormTex | kFormSoft | kFormSky>(a.ts, a.sl, a.sky); break;
     case kFormSoft | kFormSky | kFormSkySample: l.go<kFormSoft | kFormSky | kFormSkySample>(a.sl, a.sky, a.sd); break;
     case kFormTex | kFormSoft | kFormSky | kFormSkySample: l.go<kFormTex | kFormSoft | kFormSky | kFormSkySample>(a.ts, a.sl, a.sky, a.sd); break;
+    case kFormSoft | kFormEmit: l.go<kFormSoft | kFormEmit>(a.sl, a.em); break;
+    case kFormTex | kFormSoft | kFormEmit: l.go<kFormTex | kFormSoft | kFormEmit>(a.ts, a.sl, a.em); break;
     case kFormTex | kFormAnim: l.go<kFormTex | kFormAnim>(a.ts, a.anim); break;
     case kFormTex | kFormList: l.go<kFormTex | kFormList>(a.ts, a.list); break;
     case kFormFirst | kFormStats: l.go<kFormFirst | kFormStats>(); break;
@@ -784,13 +873,13 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     if (pt.st.n_paths == 0) return RT_OK;
     // the chain's facts: with the step they decide the form of each wf_advance launch (rt_still.h adv_form)
     const bool anim = c.batch && c.anim;                          // an animated batch: the frames' lights and spheres too
-    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on, c.sky.n > 0, c.sd.s > 0.f};
+    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on, c.sky.n > 0, c.sd.s > 0.f, c.em.mask != 0};
     const dim3 pg(pt.pblocks), pb(kn.adv_block);
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
     const rtk::QRows win_y = rtk::qrows_y(pt.st.n_paths, pt.st.log2S, pt.st.Q);
-    // (the camera has a lens: the chain opens with the lens form and knows no still view; nor does a chain of the shutter forms, nor one of the sky forms)
-    const rtk::StillChain sc = (facts.lens || facts.shutter || facts.sky) ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
+    // (the camera has a lens: the chain opens with the lens form and knows no still view; nor does a chain of the shutter forms, nor one of the sky forms, nor one of the emission forms)
+    const rtk::StillChain sc = (facts.lens || facts.shutter || facts.sky || facts.emit) ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
     // the plain chain takes the closing kernel at its last position
     const bool plain = t.queue && rtk::adv_plain_chain(facts);
     const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0, plain && kn.chain_ends != 0);
@@ -798,6 +887,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     AdvArgs aa;
     aa.anim = pt.anim; aa.sl = c.sl; aa.ln = c.lens; aa.shu = c.shutter; aa.sky = c.sky;
     if (facts.sample) { aa.sd = c.sd; aa.sd.L3 = static_cast<float4 *>(ctx->wfL3.p) + pt.base * (size_t)c.nseg; }   // L3[d * n_paths + i] inside the part's block, as ALB
+    if (facts.emit) { aa.em = c.em; aa.em.L3 = static_cast<float4 *>(ctx->wfL3.p) + pt.base * (size_t)c.nseg; }       // ... and likewise
     if (sc.records != rtk::kStillOff) { aa.sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; aa.sh.kill_x = plan.kill_x; }
     if (facts.tex) { aa.ts = tex_scene(ctx); aa.ts.ALB = static_cast<float4 *>(ctx->wfALB.p) + pt.base * (size_t)c.nseg; }   // ALB[d * n_paths + i] inside the part's block, as LS
     pt.st.nonce = (int)(++ctx->chain_nonce[j] & (unsigned)rtk::PQ_NONCE_MASK);
@@ -889,7 +979,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
     }
     ctx->stats.lds_bytes = (int)t.lds; ctx->stats.block_threads = t.tb; ctx->stats.grid_blocks = (int)w.pv[0].tblocks; ctx->stats.parts = parts; ctx->stats.travq_mode = t.travq_mode;
     if ((rc = start_chains(ctx, c, w, qr_grown, own0)) != RT_OK) return rc;
-    if (!(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0)) still_begin(ctx, c, t, w, own0);
+    if (!(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && c.em.mask == 0) still_begin(ctx, c, t, w, own0);
     // The chains of ONE sample chunk are issued for all sub-frames before the next chunk's.
     // (Rounds 2-4 issued all chunks of sub-frame 0 first: with hundreds of chains the host was still feeding stream 0 while stream 1 sat empty, the
     // sub-frames ran one after the other instead of side by side, and a 256-sample 1080p frame cost 1.26 ms per sample against 0.94 at 32 samples --

@@ -193,6 +193,16 @@ __global__ __launch_bounds__(256) void kat_sky_sample_kernel(const WfSkyDist sd,
     g[i] = sky_weight(sd, s.t, s.m, s.r, 1.f);
 }
 
+// in: hs, seg; out: the triangle (visit order) and the point of emit_draw (the draw of a shadow ray towards the emissive meshes)
+__global__ __launch_bounds__(256) void kat_emit_sample_kernel(const WfEmit em, const float4 *__restrict__ tri_rec, const uint32_t *__restrict__ hs, const int *__restrict__ seg, int count,
+                                                              uint32_t *__restrict__ tri, float *__restrict__ point) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const EmitDraw s = emit_draw(em, tri_rec, hs[i], seg[i]);
+    tri[i] = s.t;
+    point[3 * (size_t)i] = s.Q.x; point[3 * (size_t)i + 1] = s.Q.y; point[3 * (size_t)i + 2] = s.Q.z;
+}
+
 }  // namespace rtk
 
 namespace {
@@ -313,6 +323,53 @@ int rt_kat_environment_sample(rt_ctx *ctx, int count, const uint32_t *hs, const 
     if (e == hipSuccess) e = hipMemcpyAsync(texel_out, dt, (size_t)count * 4, hipMemcpyDeviceToHost, q);
     if (e == hipSuccess) e = hipMemcpyAsync(dir_out, dd, (size_t)count * 12, hipMemcpyDeviceToHost, q);
     if (e == hipSuccess) e = hipMemcpyAsync(g_out, dg, (size_t)count * 4, hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipStreamSynchronize(q);
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "KAT launch: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
+// the emitters' sampling table as the device built it: c and prefix (n_triangles each, either may be NULL: a first call with both NULL asks for the count) and the total;
+// no emitter, or an empty table: total 0 and zeros
+int rt_kat_emission_table(rt_ctx *ctx, uint32_t *c_out, uint64_t *prefix_out, uint64_t *total, int32_t *n_triangles) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
+    if (!total || !n_triangles) return fail(ctx, RT_ERR_INVALID, "total or n_triangles is NULL");
+    if (int rc = emit_refresh(ctx); rc != RT_OK) return rc;
+    const size_t count = (size_t)(ctx->scene.n_tris > 0 ? ctx->scene.n_tris : 0);
+    if (ctx->emit_total == 0) {
+        if (c_out) memset(c_out, 0, count * sizeof(uint32_t));
+        if (prefix_out) memset(prefix_out, 0, count * sizeof(uint64_t));
+    } else {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const rtk::WfEmit em = emit_dist_of(ctx);
+        if (c_out) RT_HIP(ctx, hipMemcpy(c_out, em.c, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (prefix_out) RT_HIP(ctx, hipMemcpy(prefix_out, em.prefix, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    *total = ctx->emit_total;
+    *n_triangles = (int32_t)count;
+    return RT_OK;
+}
+
+int rt_kat_emission_sample(rt_ctx *ctx, int count, const uint32_t *hs, const int32_t *seg, uint32_t *tri_out, float *point_out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (!ctx->have_scene || !ctx->parts_valid) return fail(ctx, RT_ERR_NO_SCENE, "no scene: rt_scene_upload* has not been called or the last call failed");
+    if (count < 0 || (count > 0 && (!hs || !seg || !tri_out || !point_out))) return fail(ctx, RT_ERR_INVALID, "bad KAT arguments");
+    if (int rc = emit_refresh(ctx); rc != RT_OK) return rc;
+    if (ctx->emit_total == 0) return fail(ctx, RT_ERR_INVALID, "no table to draw from: no mesh emits, or every emitting triangle has no area (rt_scene_set_emission)");
+    if (count == 0) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_OWN_STREAM(ctx);
+    hipStream_t q = own_stream(ctx);
+    DevBuf dhs, dseg, dout;                                            // out: the triangle and three floats of the point per draw
+    int rc;
+    if ((rc = upload(ctx, dhs, hs, (size_t)count * 4)) != RT_OK || (rc = upload(ctx, dseg, seg, (size_t)count * 4)) != RT_OK || (rc = ensure(ctx, dout, (size_t)count * 16)) != RT_OK) return rc;
+    uint32_t *dt = static_cast<uint32_t *>(dout.p);
+    float *dq = reinterpret_cast<float *>(dt + count);
+    hipLaunchKernelGGL(rtk::kat_emit_sample_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, q, emit_dist_of(ctx), ctx->scene.tri, static_cast<const uint32_t *>(dhs.p),
+                       static_cast<const int *>(dseg.p), count, dt, dq);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(tri_out, dt, (size_t)count * 4, hipMemcpyDeviceToHost, q);
+    if (e == hipSuccess) e = hipMemcpyAsync(point_out, dq, (size_t)count * 12, hipMemcpyDeviceToHost, q);
     if (e == hipSuccess) e = hipStreamSynchronize(q);
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "KAT launch: %s", hipGetErrorString(e));
     return RT_OK;

@@ -203,6 +203,64 @@ __device__ __forceinline__ float sky_weight(const WfSkyDist &sd, unsigned int t,
     return (float)(num / den);
 }
 
+// EMISSIVE MESHES (rt_scene_set_emission; the rule: raytrace_hip.h "emissive meshes"): a point drawn from the emitting triangles by area times radiance.  The table has the
+// sky table's form -- c(t) per triangle of the scene in stored (visit) order, its inclusive 64-bit sums, their total, a block level of kSkyBlock -- and is built by the
+// same kernels from other weights (rt_skydist.hip.h emit_dist_weights).
+struct WfEmit {
+    const unsigned long long *prefix;        // [nt] inclusive sums of c, triangle t in visit order (Scene::tri)
+    const unsigned long long *blk;           // [nb] blk[b] = prefix[min((b + 1) * kSkyBlock, nt) - 1]
+    const unsigned int *c;                   // [nt]
+    const float4 *le;                        // [kMaxObjects] by OBJECT position: (Le r, g, b, Y = fl(fl(r + g) + b)); zeros for what does not emit
+    unsigned long long total;                // prefix[nt - 1], in [1, 2^51]; 0: no table (then s is 0 and nothing above is read)
+    int nt, nb;
+    // ... and what a frame's emission forms take with it (wf_advance<kFormEmit>; zero in the known-answer entries): the effective share s in [0, 1], the two weights
+    // fl(1 / s) and fl(1 / (1 - s)) (each unused where its rays are never drawn), the mask of the emitting object positions, and per diffuse segment d of path i
+    // L3[d * n_paths + i] = (the three-channel direct term, norm2(L' - Pa): the far end of the segment's shadow ray as light_hidden compares it)
+    float s, w_emit, w_light;
+    unsigned int mask;
+    float4 *L3;
+};
+constexpr float kEmitKappa = 0x1p-10f;       // a shadow ray towards the point Q of an emitter aims at L' = Q + kappa (Pa - Q): raytrace_hip.h "emissive meshes" says why
+// the least triangle t with prefix[t] >= X, for X in [1, total] (so c(t) > 0): sky_pick's two levels over nt entries; every index stays inside [0, nb) and [0, nt)
+__device__ __forceinline__ unsigned int emit_pick(const WfEmit &em, unsigned long long X) {
+    int lo = 0, hi = em.nb - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (em.blk[mid] >= X) hi = mid; else lo = mid + 1;
+    }
+    int tlo = lo * kSkyBlock, thi = tlo + kSkyBlock < em.nt ? tlo + kSkyBlock - 1 : em.nt - 1;
+    while (tlo < thi) {
+        const int mid = (tlo + thi) >> 1;
+        if (em.prefix[mid] >= X) thi = mid; else tlo = mid + 1;
+    }
+    return (unsigned int)tlo;
+}
+// the draw of segment `seg` of the path whose sample key is hs: the triangle, the point Q on it, and the record's raw normal Nt = cross(e1, e2)
+struct EmitDraw { unsigned int t; f3 Q, Nt; };
+__device__ __forceinline__ EmitDraw emit_draw(const WfEmit &em, const float4 *__restrict__ tri, uint32_t hs, int seg) {
+    const uint32_t depth = (1u << 27) + (uint32_t)seg;
+    const unsigned long long K = ((unsigned long long)uniform24(hs, depth, 0) << 24) | (unsigned long long)uniform24(hs, depth, 1);
+    const unsigned long long X = ((__umul64hi(K, em.total) << 16) | ((K * em.total) >> 48)) + 1ull;   // (K total >> 48) + 1, as sky_draw
+    EmitDraw s;
+    s.t = emit_pick(em, X);
+    float r1 = uniform01(hs, depth, 2), r2 = uniform01(hs, depth, 3);
+    if (r1 + r2 > 1.f) { r1 = 1.f - r1; r2 = 1.f - r2; }               // the other half of the parallelogram, folded back
+    const float4 q0 = tri[3 * (size_t)s.t], q1 = tri[3 * (size_t)s.t + 1], q2 = tri[3 * (size_t)s.t + 2];
+    const f3 A = mk(q0.x, q0.y, q0.z), e1 = mk(q0.w, q1.x, q1.y), e2 = mk(q1.z, q1.w, q2.x);
+    s.Q = (A + r1 * e1) + r2 * e2;
+    s.Nt = mk(q2.y, q2.z, q2.w);
+    return s;
+}
+// g = mx cl / d2 over the area density c(t) / total * 2 / A2, in binary64, rounded once: mx = max(dot(N, wl), 0) at the shaded point, wl the unit vector towards Q,
+// d2 = |Q - P|^2, cl = |dot(normalize(Nt), wl)| and A2 = rt_sqrtf(norm2(Nt)) (twice the triangle's area)
+__device__ __forceinline__ float emit_weight(const WfEmit &em, const EmitDraw &s, f3 wl, float d2, float mx) {
+    float A2;                                                          // (normalize's own norm: rt_sqrtf(norm2(Nt)))
+    const float cl = fabsf(dot(normalize(s.Nt, A2), wl));
+    const double num = (((double)mx * (double)cl) * (double)A2) * (double)em.total;
+    const double den = (2.0 * (double)em.c[s.t]) * (double)d2;
+    return (float)(num / den);
+}
+
 // ---- the hit ----
 // alpha, beta, gamma of triangle `tri` (visit order) for the ray (O, u): get_smooth_normal's expressions (realtime_render.cu:221-245).  The smooth normal, the
 // texture lookup (tex_albedo, rt_wavefront.hip.h) and rt_kat_surface read these.
@@ -272,6 +330,8 @@ __device__ __forceinline__ f3 shadow_dir(f3 L, f3 Pa) { float nl; return shadow_
 // cpu:615: is the light hidden from P_adjusted, given the shadow ray's nearest hit point Pp (cpu:560) -- or its ray (Pa, u) and the hit's t?
 __device__ __forceinline__ bool light_hidden(f3 Pa, f3 Pp, f3 L) { return norm2(Pp - Pa) <= norm2(L - Pa); }
 __device__ __forceinline__ bool light_hidden(f3 Pa, f3 u, float t, f3 L) { return light_hidden(Pa, Pa + t * u, L); }
+// ... with the right-hand side norm2(L - Pa) formed where the ray was emitted and carried to its close (the emission forms: WfEmit::L3's fourth word)
+__device__ __forceinline__ bool light_hidden_far2(f3 Pa, f3 u, float t, float far2) { return norm2((Pa + t * u) - Pa) <= far2; }
 // cpu:620-623: the scalar l of a diffuse hit at P with normal N under a visible light (the quotient and the product in binary64, as the reference's promotions make them)
 __device__ __forceinline__ float direct_term(float intensity, f3 L, f3 P, f3 N) {
     const f3 wl = normalize(L - P);

@@ -43,6 +43,30 @@ __global__ __launch_bounds__(kSkyBlock) void sky_dist_weights(const float4 *__re
     if (threadIdx.x == 0) atomicMax(wmax_bits, smax[0]);
 }
 
+// The weights of the table of the EMISSIVE MESHES (raytrace_hip.h "emissive meshes"; the draw: emit_draw in rt_shade.hip.h) over the scene's triangles in visit order:
+// W(t) = fl(A2(t) Y(obj of t)), A2 = rt_sqrtf(norm2(Nt)) of the record's raw normal, +0 for a triangle of a mesh that does not emit; the maximum as above.  The other
+// three launches are the sky's, unchanged.  The meshes' triangle ranges come as an argument read in a wave-uniform loop (mesh_of_tri's): no lane indexes it.
+struct EmitMeshes { int n; int tri_begin[kMaxMeshes]; float Y[kMaxMeshes]; };   // in object order, as Scene::mesh; Y of each mesh's radiance
+__global__ __launch_bounds__(kSkyBlock) void emit_dist_weights(const float4 *__restrict__ tri, int nt, const EmitMeshes em, float *__restrict__ W, unsigned int *__restrict__ wmax_bits) {
+    __shared__ unsigned int smax[kSkyBlock];
+    const int t = blockIdx.x * kSkyBlock + (int)threadIdx.x;
+    float w = 0.f;
+    if (t < nt) {
+        float Y = em.Y[0];
+        for (int k = 1; k < em.n; ++k) Y = (t >= em.tri_begin[k]) ? em.Y[k] : Y;
+        const float4 q2 = tri[3 * (size_t)t + 2];
+        if (Y > 0.f) w = rt_sqrtf(norm2(mk(q2.y, q2.z, q2.w))) * Y;
+        W[t] = w;
+    }
+    smax[threadIdx.x] = __float_as_uint(w);
+    __syncthreads();
+    for (int s = kSkyBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) { const unsigned int o = smax[threadIdx.x + s]; if (o > smax[threadIdx.x]) smax[threadIdx.x] = o; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(wmax_bits, smax[0]);
+}
+
 __global__ __launch_bounds__(kSkyBlock) void sky_dist_quantise(const float *__restrict__ W, int count, const unsigned int *__restrict__ wmax_bits, unsigned int *__restrict__ c,
                                                                unsigned long long *__restrict__ blk) {
     __shared__ unsigned long long ssum[kSkyBlock];

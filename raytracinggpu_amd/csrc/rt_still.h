@@ -70,7 +70,7 @@ struct StillChain { StillMode hit, shadow, records; };
 struct StillView {
     StillLevel hit, shadow, records;
     // Every entry that can change a triangle, the visit order or the tree calls this: the hit words are stale (and with them everything above)
-    void mesh_changed() { ++mesh_gen; }
+    void mesh_changed() { ++mesh_gen; ++tri_gen; }
     // Every entry that writes what shading reads behind a pointer of the Scene -- normals, UVs, texels, texture records: the shadow words and the records are stale
     void shading_changed() { ++shade_gen; }
     // rt_camera_set_lens turning the lens on or off.  Chains of a frame with the lens on do not come here at all (neither begin nor chain: no counter moves), so nothing
@@ -81,6 +81,9 @@ struct StillView {
     // rt_scene_set_environment setting, replacing or removing the map: the same again (a chain under an environment does not come here; a replaced map between two such
     // frames costs the next frame without one nothing more than the refill it owes anyway)
     void sky_changed() { ++mesh_gen; }
+    // what mesh_changed alone has counted -- the triangles, not the lens, the shutter or the sky: the emitters' sampling table is rebuilt when it moved
+    // (rt_host_render.hip.h emit_refresh)
+    uint64_t triangle_generation() const { return tri_gen; }
 
     // Before a chunk's chains are enqueued, after their streams are settled.  level: what the chunk is eligible for; the keys are read up to that level only; M0 / X0 / S0: where
     // the three buffers are now.  Any difference from what a level was stored under empties it and every level above.
@@ -118,7 +121,7 @@ struct StillView {
   private:
     StillKey ray_key, shade_key;
     const void *rec_buf = nullptr;
-    uint64_t mesh_gen = 0, shade_gen = 0, ray_gen = 0;
+    uint64_t mesh_gen = 0, shade_gen = 0, ray_gen = 0, tri_gen = 0;
     int lvl = 0;
 };
 
@@ -178,15 +181,17 @@ inline StillPlan still_plan(const StillChain &c, int segs, bool have_mesh, bool 
 // time (WfShutter), in every launch of the chain; sky: a ray that misses meets the environment map (WfSky), in every launch after the opening one -- its extra comes last
 constexpr unsigned kFormStats = 1u << 0, kFormFirst = 1u << 1, kFormTex = 1u << 2, kFormAnim = 1u << 3, kFormList = 1u << 4, kFormFill = 1u << 5, kFormResume = 1u << 6,
                    kFormLights = 1u << 7, kFormSoft = 1u << 8, kFormLens = 1u << 9, kFormClose = 1u << 10, kFormShutter = 1u << 11, kFormSky = 1u << 12,
-                   kFormSkySample = 1u << 13;                // sky sampling: a segment's shadow ray may go to the environment, drawn from its table (WfSkyDist, after the WfSky)
+                   kFormSkySample = 1u << 13,                // sky sampling: a segment's shadow ray may go to the environment, drawn from its table (WfSkyDist, after the WfSky)
+                   kFormEmit = 1u << 14;                     // emissive meshes: a ray that hits an emitter ends there, a segment's shadow ray may go to one (WfEmit, after the WfSoftLights)
 constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks for this launch, and no kernel exists for it
 
 // What decides the form besides the step: the chain's facts.  counting: rt_count_work; anim: a batch with per-frame scenes; list: rt_render_counts*; lights: 0 the Scene's
 // one point light, 1 several, 2 some with a radius; shutter: the shutter is on (rt_scene_set_shutter) -- defaulted: a chain without one is written as before; sky: the scene has an
 // environment (rt_scene_set_environment) -- last and defaulted, for the same reason
-struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; bool sample = false; };   // sample: sky sampling is in effect (with sky), last and defaulted too
+// emit: a mesh of the scene emits (rt_scene_set_emission) -- last and defaulted as well
+struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; bool sample = false; bool emit = false; };   // sample: sky sampling is in effect (with sky), last and defaulted too
 // The plain chain -- every launch after the opening one the form 0 or kFormStats (or the launch that stores the records): still_plan's `ends`, for a work-stack chain
-inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky; }
+inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky && !f.emit; }
 // The form of the launch a chain of these facts enqueues for `adv` (StillAdv: StillPlan::open for the opening launch, StillStep::adv for the later ones)
 inline unsigned adv_form(const AdvFacts &f, int adv) {
     // counting, a list and an animated batch exclude one another, and each refuses several lights, a radius and the lens before a chain is planned (lights_refuse)
@@ -198,6 +203,15 @@ inline unsigned adv_form(const AdvFacts &f, int adv) {
     // the shutter refuse it (lights_refuse); no still view (no fill, no resume), and the closing kernel closes no continuation ray: not a plain chain.  A light list without
     // a radius goes through the soft forms with radii 0 (a radius-0 light is the light itself, bit for bit): four later forms, not six
     if (f.sample && !f.sky) return kFormNotBuilt;
+    // Emissive meshes: an emitter is met where a continuation ray is closed and sampled where a segment is shaded, so the opening launch is what it was and every later
+    // launch has the bit.  An environment, the shutter, counting, a list and an animated batch refuse it (lights_refuse); no still view, not a plain chain; any light
+    // configuration takes the soft route, as under sky sampling: two forms
+    if (f.emit) {
+        if (special != 0 || f.shutter || f.sky) return kFormNotBuilt;
+        if (adv == kAdvBegin) return kFormFirst | (f.lens ? kFormLens : 0u);
+        if (adv == kAdvPlain) return (f.tex ? kFormTex : 0u) | kFormSoft | kFormEmit;
+        return kFormNotBuilt;
+    }
     if (f.sky) {
         if (special != 0 || f.shutter) return kFormNotBuilt;
         if (adv == kAdvBegin) return kFormFirst | (f.lens ? kFormLens : 0u);

@@ -700,8 +700,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #define ADV_MARK(name) do { } while (0)
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
-// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones)
-#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
+// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones, nor the EMIT ones)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE && !EMIT) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -824,10 +824,14 @@ using AnimTable = const AnimFrame *__restrict__;                      // (the qu
 template <unsigned FORM>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim,
                                                 const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln,
-                                                const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky, const WfSkyDist *__restrict__ sd = nullptr) {
+                                                const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky, const WfSkyDist *__restrict__ sd = nullptr,
+                                                const WfEmit *__restrict__ em = nullptr) {
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
     constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter, SKY = FORM & kFormSky;
     constexpr bool SAMPLE = FORM & kFormSkySample;                     // sky sampling: a segment's one shadow ray may go to the environment (always with SKY and the soft lights' table)
+    // emissive meshes: a continuation ray that hits an emitter ends its path there, and a segment's one shadow ray may go to a point of one (always with the soft lights'
+    // table, never with SKY)
+    constexpr bool EMIT = FORM & kFormEmit;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
     // of the store (16 bytes of scratch) and keeps the plain one
@@ -849,7 +853,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     bool x_sky = false;                                               // (SAMPLE) the shadow ray in question -- closed, then emitted -- goes to the sky
     bool x_moot = false;                                              // the shadow ray's answer cannot reach the pixel (direct term +0 either way, or every channel dead)
     f3 Oy = mk(0, 0, 0), uy = mk(0, 0, 1), Ox = mk(0, 0, 0), ux = mk(0, 0, 1);
-    f3 E = mk(0, 0, 0);                                               // (SKY) what the path's last ray met beyond the scene: the fold starts from it
+    f3 E = mk(0, 0, 0);                                               // (SKY) what the path's last ray met beyond the scene, (EMIT) the radiance of the emitter it hit: the fold starts from it
     int px, lrow; bool valid;
     int s_rel = 0;
     if (st.n_paths != st.n_px) s_rel = wf_div(i, st.n_px, st.n_px_m);
@@ -932,6 +936,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         if (LIGHTS == 1 && (F & PF_HASX)) L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // the light segment d-1's shadow ray went to, picked again
         // (SAMPLE) segment d-1's shadow ray went to the sky: known from its share draw alone, no search
         if constexpr (SAMPLE) x_sky = (F & PF_HASX) && uniform01(sample_hash(pixel_hash(fr, row, px, fr_seed), samp), (uint32_t)d, 3) <= sd->s;
+        if constexpr (!EMIT)                                          // (EMIT: the far end of the ray travels with its term, no second draw)
         if (LIGHTS == 2 && (F & PF_HASX) && !(SAMPLE && x_sky)) L = wf_light_point(*sl, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d - 1);   // ... and the point of its shell
         if constexpr (SAMPLE) {                                       // the stored three-channel term does not count if the ray was blocked: a sky ray by anything at all
             if (F & PF_HASX) {
@@ -942,6 +947,20 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     Oxr = mk(x0.x, x0.y, x0.z); uxr = mk(x0.w, x1.x, x1.y);
                 }, xm);
                 if (shadowed) sd->L3[(size_t)(d - 1) * st.n_paths + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        } else if constexpr (EMIT) {                                  // ... to a light or to an emitter: the far end travels with the term, no second draw
+            if (F & PF_HASX) {
+                bool shadowed = (F & PQ_XSPHERE) != 0;
+                float4 l4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!shadowed && (F & PF_MESHX)) {
+                    const unsigned long long m = st.M[rx];
+                    if (m != WF_NOHIT) {
+                        const float4 x0 = st.QR[2 * (size_t)qx], x1 = st.QR[2 * (size_t)qx + 1];
+                        l4 = em->L3[(size_t)(d - 1) * st.n_paths + i];
+                        shadowed = light_hidden_far2(mk(x0.x, x0.y, x0.z), mk(x0.w, x1.x, x1.y), __uint_as_float((unsigned int)(m >> 32)), l4.w);
+                    }
+                }
+                if (shadowed) em->L3[(size_t)(d - 1) * st.n_paths + i] = make_float4(0.f, 0.f, 0.f, l4.w);
             }
         } else
         if (!RESUME && (F & PF_HASX)) {
@@ -973,6 +992,18 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                     const float tm = __uint_as_float((unsigned int)(m >> 32));
                     const int mobj = mesh_obj_of_tri(sc, (int)(unsigned int)m);   // the meshes' own winner: minimum over (t, object position, scan rank) by the order the triangles are stored in
                     if (mesh_beats_sphere(t_min, win, tm, mobj)) { t_min = tm; win = mobj; tri_win = (int)(unsigned int)m; }   // a tie goes to whichever comes first in Scene::objects (no sphere: win = -1, 1e9 > tm)
+                }
+            }
+            if constexpr (EMIT) {
+                // The nearest object emits: the path ends here, as at a miss (no shadow ray, no continuation ray, SID 0xff), and the fold starts from the emitter's
+                // radiance -- unless the ray left a diffuse segment while emitters are sampled: that segment's shadow rays have accounted for them (the rule of sky
+                // sampling's miss)
+                if (win >= 0 && ((em->mask >> win) & 1u) != 0) {
+                    if (d == 0 || !(em->s > 0.f) || st.SID[(size_t)(d - 1) * st.n_paths + i] == 0xff) {
+                        const float4 le = em->le[win];
+                        E = mk(le.x, le.y, le.z);
+                    }
+                    win = -1;
                 }
             }
             if (win >= 0) {                                           // a miss emits nothing: black (cpu:571), or under an environment E below
@@ -1043,6 +1074,48 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         if (st.deadch) {
                             const int was = st.DCH[i];
                             int now = (was & 8) | (x_sky ? 0 : wf_dead_channels(was & 7, alb, l3.x));
+                            if ((now & 7) == 7 && !x_moot) { x_moot = true; now |= 8; }
+                            if (now != was) st.DCH[i] = (unsigned char)now;
+                        }
+                    } else if constexpr (EMIT) {
+                        const uint32_t hs = sample_hash(pixel_hash(fr, row, px, fr_seed), samp);
+                        const bool x_emit = uniform01(hs, (uint32_t)(d + 1), 3) <= em->s;   // this segment's one shadow ray goes to an emitter, or to the light the list picks
+                        f3 l3;
+                        if (x_emit) {
+                            const EmitDraw dr = emit_draw(*em, sc.tri, hs, d);
+                            const f3 v = dr.Q - P;
+                            const float d2 = norm2(v);
+                            const f3 wl = normalize(v);
+                            const float dn = dot(N, wl);
+                            const float g = emit_weight(*em, dr, wl, d2, (dn < 0.f) ? 0.f : dn);
+                            const float4 le = em->le[mesh_obj_of_tri(sc, (int)dr.t)];
+                            l3 = mk(em->w_emit * (g * le.x), em->w_emit * (g * le.y), em->w_emit * (g * le.z));
+                            L = dr.Q + kEmitKappa * (Pa - dr.Q);      // short of the emitter's own plane
+                        } else {
+                            L = wf_light_point(*sl, hs, d);
+                            const float lv = direct_term(sl->lt.total, L, P, N) * em->w_light;
+                            l3 = mk(lv, lv, lv);
+                        }
+                        float nl;
+                        Ox = Pa; ux = shadow_dir(L, Pa, nl);          // from here on a point light's shadow ray
+                        x_bound = wf_anyhit_bound(Pa, nl);
+                        nrays += 1;
+                        em->L3[(size_t)d * st.n_paths + i] = make_float4(l3.x, l3.y, l3.z, norm2(L - Pa));
+                        emitX = true;
+                        x_moot = st.anyhit && (__float_as_uint(l3.x) | __float_as_uint(l3.y) | __float_as_uint(l3.z)) == 0u;
+                        sid = win;
+                        f3 alb = mk(m.ar, m.ag, m.ab);
+                        if (TEX && tri_win >= 0 && ((ts.mask >> win) & 1)) {
+                            if (!have_bary) bary = tri_bary(sc, tri_win, O, u);
+                            float2 uv;
+                            alb = tex_albedo(sc, ts, win, tri_win, bary, uv);
+                            ts.ALB[(size_t)d * st.n_paths + i] = make_float4(alb.x, alb.y, alb.z, 0.f);
+                            sid = kSidTextured;
+                        }
+                        // the dead channels, as under sky sampling: a segment whose ray goes to an emitter clears the mask, a light's weighted term is guarded as before
+                        if (st.deadch) {
+                            const int was = st.DCH[i];
+                            int now = (was & 8) | (x_emit ? 0 : wf_dead_channels(was & 7, alb, l3.x));
                             if ((now & 7) == 7 && !x_moot) { x_moot = true; now |= 8; }
                             if (now != was) st.DCH[i] = (unsigned char)now;
                         }
@@ -1118,7 +1191,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         ADV_MARK("fold_begin");
         if (FILL && s_rel == 0)                                       // no shadow ray left: a miss, or a specular hit of a one-segment path
             wf_shade_store(sh, i, sh_kind, shO, shV, 0.f, 0xff, sh_kind == kShadeSpecular ? refr_code : 0, 0, sh_kind == kShadeMiss ? nrays : sh_rays);
-        f3 ans = SKY ? E : mk(0, 0, 0);
+        f3 ans = (SKY || EMIT) ? E : mk(0, 0, 0);
         bool fold_sure = true;                                        // (counting instantiation) every folded segment passed wf_fold_bounded
         const int nseg = d < fr.segs ? d : fr.segs;
         for (int k = nseg - 1; k >= 0; --k) {
@@ -1134,6 +1207,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 }
                 if constexpr (SAMPLE) {                               // the segment's three-channel term
                     const float4 l4 = sd->L3[(size_t)k * st.n_paths + i];
+                    ans = fold_segment(ans, mk(l4.x, l4.y, l4.z), alb);
+                } else if constexpr (EMIT) {
+                    const float4 l4 = em->L3[(size_t)k * st.n_paths + i];
                     ans = fold_segment(ans, mk(l4.x, l4.y, l4.z), alb);
                 } else {
                 const float l = st.LS[(size_t)k * st.n_paths + i];
@@ -1225,20 +1301,24 @@ template <class T, class... Extra> constexpr bool adv_takes = (std::is_same_v<T,
 // Eight waves per SIMD (64 registers) for every form but one: in wf_advance<kFormTex | kFormSoft> the texture lookup's live values and a second binary64 sincos do not fit
 // 64 registers together: 8 spilled.  Seven waves per SIMD, 72 registers, no scratch.
 // The sampling forms carry the draw (a 64-bit search, a binary64 quotient) beside the soft lights' sincos: six waves per SIMD, 80 registers.
-constexpr int adv_waves(unsigned form) { return (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
+// The emission forms carry the same kind of draw.  soft | emit: at eight waves 4 scalar registers spill, at seven nothing does (60 registers); tex | soft | emit: 32 bytes of
+// scratch at eight, 16 at seven, none at six (74 registers).
+constexpr int adv_waves(unsigned form) { return (form & kFormEmit) ? ((form & kFormTex) ? 6 : 7) : (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
 template <unsigned FORM, class... Extra>
 __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene sc, const Frame fr, const WfState st, const Extra... extra) {
     static_assert(adv_takes<TexScene, Extra...> == ((FORM & kFormTex) != 0) && adv_takes<AnimTable, Extra...> == ((FORM & kFormAnim) != 0) &&
                   adv_takes<WfList, Extra...> == ((FORM & kFormList) != 0) && adv_takes<WfShade, Extra...> == ((FORM & (kFormFill | kFormResume)) != 0) &&
                   adv_takes<WfLights, Extra...> == ((FORM & kFormLights) != 0) && adv_takes<WfSoftLights, Extra...> == ((FORM & kFormSoft) != 0) &&
                   adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0) &&
-                  adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0) && adv_takes<WfSkyDist, Extra...> == ((FORM & kFormSkySample) != 0),
+                  adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0) && adv_takes<WfSkyDist, Extra...> == ((FORM & kFormSkySample) != 0) &&
+                  adv_takes<WfEmit, Extra...> == ((FORM & kFormEmit) != 0),
                   "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths)
         wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
-                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...), adv_extra<WfSkyDist>(extra...));
+                              adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...), adv_extra<WfSkyDist>(extra...),
+                              adv_extra<WfEmit>(extra...));
     wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 

@@ -32,6 +32,17 @@ def load_cat_arrays(path=CAT_FIXTURE):
     return np.array(g["vertices"], np.float32), np.array(g["tri_obj_order"], np.int32)
 
 
+def panel(corner, edge_u, edge_v):
+    """A parallelogram as a two-triangle mesh -> (positions [4, 3] float32, indices [2, 3] int32): corner, corner + edge_u, corner + edge_u + edge_v,
+    corner + edge_v.  The shape of a ceiling panel or a window for rt_scene_set_emission (an emitter is two-sided: the winding does not matter).  Tilt it a little out of
+    the axis planes: the box test of the reference programs is strict, and a box without thickness -- an axis-aligned panel's -- is entered by no ray."""
+    c, u, v = (np.asarray(a, np.float32) for a in (corner, edge_u, edge_v))
+    if c.shape != (3,) or u.shape != (3,) or v.shape != (3,):
+        raise ValueError("a panel is a corner and two edges of three numbers each")
+    positions = np.stack([c, c + u, (c + u).astype(np.float32) + v, c + v]).astype(np.float32)
+    return positions, np.array([[0, 1, 2], [0, 2, 3]], np.int32)
+
+
 def spheres(name):
     if name == "demo10":
         return list(DEMO) + list(WALLS)

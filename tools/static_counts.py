@@ -207,7 +207,9 @@ ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
            "wf_advance_sky": (("sky",), False), "wf_advance_tex_sky": (("tex", "sky"), False),
            "wf_advance_soft_sky": (("soft", "sky"), False), "wf_advance_tex_soft_sky": (("tex", "soft", "sky"), False),
            # sky sampling (WfSkyDist): the two later launches of a sampling chain, whole (no labels)
-           "wf_advance_soft_sky_sample": (("soft", "sky", "sample"), False), "wf_advance_tex_soft_sky_sample": (("tex", "soft", "sky", "sample"), False)}
+           "wf_advance_soft_sky_sample": (("soft", "sky", "sample"), False), "wf_advance_tex_soft_sky_sample": (("tex", "soft", "sky", "sample"), False),
+           # emissive meshes (WfEmit): the two later launches of a chain in whose scene a mesh emits, whole (no labels)
+           "wf_advance_soft_emit": (("soft", "emit"), False), "wf_advance_tex_soft_emit": (("tex", "soft", "emit"), False)}
 
 
 def advance_forms_counts(asm):
@@ -277,7 +279,7 @@ def main():
     for name in ("wf_advance_fill", "wf_advance_resume", "wf_advance_close", "wf_advance_lights", "wf_advance_tex_lights", "wf_advance_soft", "wf_advance_tex_soft", "wf_advance_lens",
                  "wf_advance_shutter_first", "wf_advance_lens_shutter_first", "wf_advance_shutter", "wf_advance_tex_shutter",
                  "wf_advance_sky", "wf_advance_tex_sky", "wf_advance_soft_sky", "wf_advance_tex_soft_sky",
-                 "wf_advance_soft_sky_sample", "wf_advance_tex_soft_sky_sample"):
+                 "wf_advance_soft_sky_sample", "wf_advance_tex_soft_sky_sample", "wf_advance_soft_emit", "wf_advance_tex_soft_emit"):
         res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
