@@ -112,6 +112,7 @@ int rt_device_name(const rt_ctx *ctx, char *buf, size_t buflen) {
 int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres, const rt_mesh *meshes, int n_meshes,
                            const rt_light *light, const rt_camera *camera) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    ctx->have_scene = false;                                             // a call that fails, for whatever reason, leaves NO scene (install_scene sets it): what follows has dropped half of the old one
     ctx->parts_valid = false;                                            // (the per-mesh records describe the scene this call installs, or none)
     ctx->tex_mask = 0;                                                   // a new scene is untextured, also when this call fails
     ctx->snap_mask = 0;                                                  // ... and holds no vertex snapshot (rt_mesh_snapshot_vertices),
