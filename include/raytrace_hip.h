@@ -529,6 +529,48 @@ int rt_scene_get_emission_sampling(const rt_ctx *ctx, float *share);
 int rt_kat_emission_table(rt_ctx *ctx, uint32_t *c_out, uint64_t *prefix_out, uint64_t *total, int32_t *n_triangles);
 int rt_kat_emission_sample(rt_ctx *ctx, int count, const uint32_t *hs, const int32_t *seg, uint32_t *tri_out, float *point_out);
 
+/* --- FRESNEL DIELECTRICS: glass reflects or refracts, chosen per sample (ABI 6, additive).  The reference's glass only ever refracts (cpu:580-604) and reflects only at
+ *     total internal reflection.  An object whose flag is set reflects with probability R, the unpolarised Fresnel reflectance of its surface, and refracts otherwise;
+ *     either ray carries weight R / R = (1 - R) / (1 - R) = 1, so no throughput is stored and no path state grows.  Off by default and per object; with no EFFECTIVE
+ *     flag every frame is launch for launch what it is without these entries, and no new kernel runs.  The device step is fresnel_step in rt_shade.hip.h, beside
+ *     refract_step; the model is tests/fresnel_model.py.
+ *     Binary32 with one rounding per operation, no fused multiply-add, quotients correctly rounded, fl() one rounding.
+ *     THE FLAG.  The context holds one bit per object position (up to RT_MAX_OBJECTS = 16).  rt_material_set_fresnel(ctx, object_slot, on) sets it (on != 0) or clears it,
+ *     rt_material_get_fresnel reads it (1 or 0).  Any slot of the uploaded scene is accepted, sphere or mesh.  RT_ERR_NO_SCENE without an upload; RT_ERR_INVALID, the state
+ *     and the output untouched, for a slot outside the scene or a NULL output.  rt_scene_upload* clears every bit.  A bit is EFFECTIVE only where a hit would take the
+ *     reference's refraction branch: mirror == 0 and n_in != n_out, read from the materials as they are when a frame's chain is planned (rt_scene_set_sphere may change a
+ *     material after the flag was set).  A flag on a mirror or on a diffuse object changes nothing.
+ *     THE HIT.  The continuation ray (O, u) of segment d, whose index is refr, hits an effectively flagged object at P with normal N.
+ *       1. out2in = (refr == n_out); ratio = out2in ? n_out / n_in : n_in / n_out, and N = -N if not out2in; un = dot(u, N); k = fl(fl(ratio ratio) fl(1 - fl(un un))).
+ *          If ((out2in and refr > n_in) or (not out2in and refr > n_out)) and k > 1 the ray is TOTALLY REFLECTED: O = P + eps N, u = u - fl(2 un) N, the index stays.  All
+ *          of this is refract_step's, word for word.
+ *       2. Otherwise n1 = out2in ? n_out : n_in, n2 = out2in ? n_in : n_out, ci = |un|, ct = rt_sqrtf(fl(1 - k)) -- the value the refracted direction uses --
+ *          a = fl(n1 ci), b = fl(n2 ct), c = fl(n1 ct), e = fl(n2 ci), rs = fl(fl(a - b) / fl(a + b)), rp = fl(fl(c - e) / fl(c + e)),
+ *          R = fl(0.5 fl(fl(rs rs) + fl(rp rp))): the Fresnel equations themselves, not Schlick's approximation; two quotients, no pow.
+ *       3. r_f = uniform01(hs, (1u << 26) + d, 0), hs the sample's key: the RNG keys on depth * 4 + dim, so this draw sits at 2^28 + 4 d -- above the jitter, bounce, pick
+ *          and share draws (4 d' + dim, d' <= RT_MAX_SEGMENTS + 1: below 2^7) and below the emitters' draws (2^29 + 4 d + dim); the lens and the shutter sit at
+ *          2^30 + {0, 1, 2}, the shells at 2^31 + 4 d + {0, 1}, the sky's draws at 3 2^30 + 4 d + dim.  With d <= RT_MAX_SEGMENTS the key stays below 2^28 + 2^7: none of
+ *          the others reaches it.
+ *       4. REFLECT iff r_f <= R: the reflected ray is the total-reflection branch's own, O = P + eps N, u = u - fl(2 un) N; the ray's index and its refr code stay.
+ *          Otherwise the refracted ray is exactly the reference's: O = P - eps N, u = fl(-ct) N + ratio (u - un N), the index becomes out2in ? n_in : n_out.  A NaN R
+ *          refracts (the comparison is false): a negative radicand in nested glass with unmatched indices (the reference's quirk: k > 1 where the index test fails), or
+ *          0 / 0 at ci = ct = 0 -- the reference's ray, so an unflagged frame and a flagged one agree on such a hit.
+ *     Nothing else of the path changes: a specular segment emits no shadow ray, SID[d] = 0xff, .w counts one continuation ray, and shadow rays still stop at glass.
+ *     R is in [0, 1] outside total reflection, exactly 1 at ci = 0 from the thin side, and 0.040000003 (0x3D23D70B) at normal incidence for 1 <-> 1.5.
+ *     Rendered by the wavefront variants' launch chain (four forms of wf_advance, kFormFresnel: with and without textures, with and without the soft lights' table, which
+ *     any light list or radius takes; the lens, poses, row shares, RT_PARTS, plain batches, rt_render_async, pipelining), which keeps no still-view cache under an effective
+ *     flag; setting and removing a flag leaves the caches as they were -- frames and cache counters are those of a context that never heard of these calls.
+ *     RT_ERR_UNSUPPORTED, outputs untouched, "fresnel" in the error text, under an effective flag: the variants path, lockstep and global, rt_count_work,
+ *     rt_render_counts*, rt_render_device_batch_scenes with scenes, and any frame while the scene also has an environment, the shutter is on or a mesh emits.
+ *     The feature-buffer entries (rt_render_aov*, rt_render_aov_surface*) keep following the refracted branch: no virtual image of a reflection.  rt_multi_* contexts have
+ *     no such entries.
+ *     Known answer: rt_kat_fresnel runs the device step on `count` explicit items; it needs no scene.  items: 16 32-bit words per item -- binary32 n_in, n_out, the ray's
+ *     index, eps, P (3), N (3), u (3), then the integers hs and seg, then one unused word.  out: 9 words per item -- binary32 R (+0 for a totally reflected ray), the
+ *     integer code (0 refracted, 1 reflected, 2 totally reflected), the new O (3) and u (3), the index after. */
+int rt_material_set_fresnel(rt_ctx *ctx, int object_slot, int on);
+int rt_material_get_fresnel(const rt_ctx *ctx, int object_slot, int *on);
+int rt_kat_fresnel(rt_ctx *ctx, int count, const uint32_t *items, uint32_t *out);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

@@ -704,6 +704,14 @@ public:
         check(rt_scene_get_emission_sampling(ctx_, &share), "rt_scene_get_emission_sampling");
         return share;
     }
+    // Fresnel dielectrics (rt_material_set_fresnel): the object at an object position reflects with its Fresnel reflectance and refracts otherwise, chosen per sample;
+    // effective on glass alone (mirror == 0, n_in != n_out); an upload clears every flag
+    void set_fresnel(int object_slot, bool on) { check(rt_material_set_fresnel(ctx_, object_slot, on ? 1 : 0), "rt_material_set_fresnel"); }
+    bool fresnel(int object_slot) {
+        int on = 0;
+        check(rt_material_get_fresnel(ctx_, object_slot, &on), "rt_material_get_fresnel");
+        return on != 0;
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

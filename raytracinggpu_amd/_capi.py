@@ -46,7 +46,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_scene_set_environment", "rt_scene_get_environment", "rt_kat_environment",
            "rt_scene_set_environment_sampling", "rt_scene_get_environment_sampling", "rt_kat_environment_table", "rt_kat_environment_sample",
            "rt_scene_set_emission", "rt_scene_get_emission", "rt_scene_set_emission_sampling", "rt_scene_get_emission_sampling",
-           "rt_kat_emission_table", "rt_kat_emission_sample"]
+           "rt_kat_emission_table", "rt_kat_emission_sample",
+           "rt_material_set_fresnel", "rt_material_get_fresnel", "rt_kat_fresnel"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -460,6 +461,9 @@ def load():
     L.rt_scene_get_emission_sampling.argtypes = [vp, C.POINTER(C.c_float)]
     L.rt_kat_emission_table.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.rt_kat_emission_sample.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.rt_material_set_fresnel.argtypes = [vp, C.c_int, C.c_int]
+    L.rt_material_get_fresnel.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.rt_kat_fresnel.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -892,6 +896,34 @@ class Context:
         self._check(self._L.rt_kat_emission_sample(self._h, int(h.size), h.ctypes.data_as(up), d.ctypes.data_as(C.POINTER(C.c_int32)), tri.ctypes.data_as(up),
                                                    point.ctypes.data_as(C.POINTER(C.c_float))))
         return tri, point
+
+    # --- Fresnel dielectrics (rt_material_set_fresnel): the per-object flag and the device step's known answer
+    def set_fresnel(self, object_slot, on=True):
+        """rt_material_set_fresnel: the object at object_slot reflects with its Fresnel reflectance and refracts otherwise (effective on glass alone); an upload clears it"""
+        self._check(self._L.rt_material_set_fresnel(self._h, int(object_slot), int(bool(on))))
+
+    def fresnel(self, object_slot):
+        """rt_material_get_fresnel -> the flag as set"""
+        on = C.c_int(0)
+        self._check(self._L.rt_material_get_fresnel(self._h, int(object_slot), C.byref(on)))
+        return bool(on.value)
+
+    def kat_fresnel(self, n_in, n_out, refr, eps, P, N, u, hs, seg):
+        """rt_kat_fresnel: the device step on k explicit items (scalars broadcast; P, N, u [k, 3]) -> (R [k] float32, code [k] int32: 0 refracted, 1 reflected,
+        2 totally reflected, O [k, 3], u [k, 3], the index after [k])"""
+        h = np.ascontiguousarray(hs, dtype=np.uint32).ravel()
+        k = h.size
+        items = np.zeros((k, 16), np.uint32)
+        f = items.view(np.float32)
+        f[:, 0], f[:, 1], f[:, 2], f[:, 3] = n_in, n_out, refr, eps
+        f[:, 4:7], f[:, 7:10], f[:, 10:13] = np.asarray(P, np.float32).reshape(-1, 3), np.asarray(N, np.float32).reshape(-1, 3), np.asarray(u, np.float32).reshape(-1, 3)
+        items[:, 13] = h
+        items[:, 14] = np.broadcast_to(np.asarray(seg, np.int32), (k,)).view(np.uint32) if np.ndim(seg) else np.uint32(int(seg))
+        out = np.zeros((k, 9), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        self._check(self._L.rt_kat_fresnel(self._h, int(k), items.ctypes.data_as(up), out.ctypes.data_as(up)))
+        g = out.view(np.float32)
+        return g[:, 0].copy(), out[:, 1].astype(np.int32), g[:, 2:5].copy(), g[:, 5:8].copy(), g[:, 8].copy()
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

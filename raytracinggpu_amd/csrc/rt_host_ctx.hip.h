@@ -218,6 +218,9 @@ struct rt_ctx {
     unsigned long long emit_total = 0;
     int emit_nt = 0, emit_nb = 0;
     DevBuf emit_dist{bufs};
+    // Fresnel dielectrics (rt_material_set_fresnel): one bit per object position.  A bit is EFFECTIVE only where the object's material takes the refraction branch, read
+    // when a chain is planned (fresnel_effective, rt_host_render.hip.h).  rt_scene_upload* clears every bit.
+    unsigned fresnel_mask = 0;
     DevBuf nrm{bufs};                                                 // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.

@@ -203,6 +203,22 @@ __global__ __launch_bounds__(256) void kat_emit_sample_kernel(const WfEmit em, c
     point[3 * (size_t)i] = s.Q.x; point[3 * (size_t)i + 1] = s.Q.y; point[3 * (size_t)i + 2] = s.Q.z;
 }
 
+// in: 16 words per item -- n_in, n_out, the ray's index, eps, P, N, u as binary32, then hs and seg as 32-bit integers, one word of padding; out: 9 words per item -- R,
+// the code (kFresnel*, an integer), the new O and u, the index after: fresnel_step (the step a wf_advance fresnel form takes at a flagged hit) on explicit items
+__global__ __launch_bounds__(256) void kat_fresnel_kernel(const float *__restrict__ in, int count, float *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const float *a = in + 16 * (size_t)i;
+    Material m{};
+    m.n_in = a[0]; m.n_out = a[1];
+    f3 O = mk(0.f, 0.f, 0.f), u = mk(a[10], a[11], a[12]);
+    const FresnelStep s = fresnel_step(m, a[2], a[3], mk(a[4], a[5], a[6]), mk(a[7], a[8], a[9]), O, u, __float_as_uint(a[13]), __float_as_int(a[14]));
+    float *o = out + 9 * (size_t)i;
+    o[0] = s.R; o[1] = __int_as_float(s.code);
+    o[2] = O.x; o[3] = O.y; o[4] = O.z; o[5] = u.x; o[6] = u.y; o[7] = u.z;
+    o[8] = s.r.refr_after;
+}
+
 }  // namespace rtk
 
 namespace {
@@ -270,6 +286,13 @@ int rt_kat_mesh(rt_ctx *ctx, const float *in, int n, float tri_tmin, int route, 
     if (route < 0 || route > 1) return fail(ctx, RT_ERR_INVALID, "route must be 0 (work-stack primitives) or 1 (stackless mesh_intersect)");
     return kat_run(ctx, in, n, 6, out, 5, counts, [&](const float *di, float *dres, unsigned long long *dc, dim3 g, dim3 b) {
         hipLaunchKernelGGL(rtk::kat_mesh_kernel, g, b, 0, own_stream(ctx), ctx->scene, di, n, tri_tmin, route, dres, dc);
+    });
+}
+
+// the Fresnel step on explicit items (raytrace_hip.h "fresnel"): needs a context, not a scene
+int rt_kat_fresnel(rt_ctx *ctx, int count, const uint32_t *items, uint32_t *out) {
+    return kat_run(ctx, reinterpret_cast<const float *>(items), count, 16, reinterpret_cast<float *>(out), 9, nullptr, [&](const float *di, float *dres, unsigned long long *, dim3 g, dim3 b) {
+        hipLaunchKernelGGL(rtk::kat_fresnel_kernel, g, b, 0, own_stream(ctx), di, count, dres);
     });
 }
 

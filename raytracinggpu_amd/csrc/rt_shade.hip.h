@@ -323,6 +323,51 @@ __device__ __forceinline__ Refraction refract_step(const Material &m, float refr
     }
     return r;
 }
+// FRESNEL DIELECTRICS (rt_material_set_fresnel; the rule: raytrace_hip.h "fresnel"): refract_step for a flagged object -- outside total reflection the ray is reflected
+// with probability R, the unpolarised Fresnel reflectance of the interface, and refracted otherwise; either ray carries weight 1, so nothing of the path's state grows.
+// The one draw sits at depth 2^26 + seg (key 2^28 + 4 seg).  A NaN R refracts (r_f <= NaN is false): the reference's ray.
+struct WfFresnel { unsigned int mask; };     // bit k: the object at position k is EFFECTIVELY flagged (its bit is set, mirror == 0 and n_in != n_out: formed on the host)
+constexpr int kFresnelRefracted = 0, kFresnelReflected = 1, kFresnelTotal = 2;
+__device__ __forceinline__ float fresnel_reflectance(float n1, float n2, float ci, float ct) {
+    const float a = n1 * ci, b = n2 * ct, c = n1 * ct, e = n2 * ci;
+    const float rs = (a - b) / (a + b), rp = (c - e) / (c + e);
+    return 0.5f * (rs * rs + rp * rp);
+}
+// R: the reflectance (+0 where the ray is totally reflected: none is formed); code: kFresnel*
+struct FresnelStep { Refraction r; float R; int code; };
+__device__ __forceinline__ FresnelStep fresnel_step(const Material &m, float refr, float eps, f3 P, f3 N, f3 &O, f3 &u, uint32_t hs, int seg) {
+    FresnelStep s;
+    Refraction &r = s.r;
+    float ratio;
+    r.out2in = refr == m.n_out;
+    if (r.out2in) ratio = m.n_out / m.n_in;
+    else { ratio = m.n_in / m.n_out; N = -N; }
+    const float un = dot(u, N);
+    const float k = (ratio * ratio) * (1 - un * un);
+    s.R = 0.f;
+    bool reflect = ((r.out2in && refr > m.n_in) || (!r.out2in && refr > m.n_out)) && k > 1;
+    s.code = reflect ? kFresnelTotal : kFresnelRefracted;
+    const float ct = rt_sqrtf(1 - k);                                  // (a NaN under total reflection: not read there)
+    if (!reflect) {
+        s.R = fresnel_reflectance(r.out2in ? m.n_out : m.n_in, r.out2in ? m.n_in : m.n_out, fabsf(un), ct);
+        reflect = uniform01(hs, (1u << 26) + (uint32_t)seg, 0) <= s.R;
+        if (reflect) s.code = kFresnelReflected;
+    }
+    if (reflect) {
+        O = P + eps * N;
+        u = u - (2 * un) * N;
+        r.crossed = false;
+        r.refr_after = refr;
+    } else {
+        O = P - eps * N;
+        const f3 Nc = (-ct) * N;
+        const f3 Tc = ratio * (u - un * N);
+        u = Nc + Tc;
+        r.crossed = true;
+        r.refr_after = r.out2in ? m.n_in : m.n_out;
+    }
+    return s;
+}
 
 // cpu:614: the shadow ray from P_adjusted to the light, NORMED_VEC (cpu:30): (L - Pa) / nl with nl = sqrt(norm2(L - Pa))
 __device__ __forceinline__ f3 shadow_dir(f3 L, f3 Pa, float &nl) { return normalize(L - Pa, nl); }

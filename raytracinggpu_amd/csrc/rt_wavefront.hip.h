@@ -700,8 +700,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #define ADV_MARK(name) do { } while (0)
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
-// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones, nor the EMIT ones)
-#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE && !EMIT) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
+// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones, nor the EMIT ones, nor the FRESNEL ones)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE && !EMIT && !FRESNEL) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -825,13 +825,16 @@ template <unsigned FORM>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim,
                                                 const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln,
                                                 const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky, const WfSkyDist *__restrict__ sd = nullptr,
-                                                const WfEmit *__restrict__ em = nullptr) {
+                                                const WfEmit *__restrict__ em = nullptr, const WfFresnel *__restrict__ fz = nullptr) {
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
     constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter, SKY = FORM & kFormSky;
     constexpr bool SAMPLE = FORM & kFormSkySample;                     // sky sampling: a segment's one shadow ray may go to the environment (always with SKY and the soft lights' table)
     // emissive meshes: a continuation ray that hits an emitter ends its path there, and a segment's one shadow ray may go to a point of one (always with the soft lights'
     // table, never with SKY)
     constexpr bool EMIT = FORM & kFormEmit;
+    // Fresnel dielectrics: a continuation ray that hits an effectively flagged object is reflected or refracted, one draw (fresnel_step beside refract_step; never with
+    // SKY, SHUTTER or EMIT, and in the later launches of a chain alone)
+    constexpr bool FRESNEL = FORM & kFormFresnel;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
     // of the store (16 bytes of scratch) and keeps the plain one
@@ -1018,9 +1021,19 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 const Material m = material_of(sc, win);
                 ADV_MARK("closey_end");
                 bool cont = false;                                    // a continuation ray of segment d+1 was built in (O,u)
+                bool fresnel_hit = false;                             // (FRESNEL) the object is effectively flagged: glass that reflects or refracts, chosen by one draw
+                if constexpr (FRESNEL) fresnel_hit = ((fz->mask >> win) & 1u) != 0;
                 if (!RESUME && m.mirror) {
                     mirror_step(fr.eps, P, N, O, u);
                     cont = true;
+                } else if (fresnel_hit) {
+                    if constexpr (FRESNEL) {                          // the refraction branch below with fresnel_step in refract_step's place
+                        float refr = 1.f;
+                        if (refr_code != 0) { const Material mr = material_of(sc, (refr_code >> 1) - 1); refr = (refr_code & 1) ? mr.n_out : mr.n_in; }
+                        const Refraction r = fresnel_step(m, refr, fr.eps, P, N, O, u, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d).r;
+                        if (r.crossed) refr_code = (win + 1) << 1 | (r.out2in ? 0 : 1);
+                        cont = true;
+                    }
                 } else if (RESUME && sh_kind == kShadeSpecular) {     // the record's ray (O, u) and refr_code are the continuation's
                     cont = true;
                 } else if (!RESUME && m.n_in != m.n_out) {
@@ -1303,7 +1316,9 @@ template <class T, class... Extra> constexpr bool adv_takes = (std::is_same_v<T,
 // The sampling forms carry the draw (a 64-bit search, a binary64 quotient) beside the soft lights' sincos: six waves per SIMD, 80 registers.
 // The emission forms carry the same kind of draw.  soft | emit: at eight waves 4 scalar registers spill, at seven nothing does (60 registers); tex | soft | emit: 32 bytes of
 // scratch at eight, 16 at seven, none at six (74 registers).
-constexpr int adv_waves(unsigned form) { return (form & kFormEmit) ? ((form & kFormTex) ? 6 : 7) : (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
+// The fresnel forms carry one draw and two quotients more than their counterparts.  fresnel and soft | fresnel: eight waves, 52 and 54 registers, nothing spills;
+// tex | fresnel: at eight waves 2 scalar registers spill, at seven nothing does; tex | soft | fresnel: seven, as its counterpart.
+constexpr int adv_waves(unsigned form) { return (form & kFormFresnel) ? ((form & kFormTex) ? 7 : 8) : (form & kFormEmit) ? ((form & kFormTex) ? 6 : 7) : (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
 template <unsigned FORM, class... Extra>
 __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene sc, const Frame fr, const WfState st, const Extra... extra) {
     static_assert(adv_takes<TexScene, Extra...> == ((FORM & kFormTex) != 0) && adv_takes<AnimTable, Extra...> == ((FORM & kFormAnim) != 0) &&
@@ -1311,14 +1326,14 @@ __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene s
                   adv_takes<WfLights, Extra...> == ((FORM & kFormLights) != 0) && adv_takes<WfSoftLights, Extra...> == ((FORM & kFormSoft) != 0) &&
                   adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0) &&
                   adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0) && adv_takes<WfSkyDist, Extra...> == ((FORM & kFormSkySample) != 0) &&
-                  adv_takes<WfEmit, Extra...> == ((FORM & kFormEmit) != 0),
+                  adv_takes<WfEmit, Extra...> == ((FORM & kFormEmit) != 0) && adv_takes<WfFresnel, Extra...> == ((FORM & kFormFresnel) != 0),
                   "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths)
         wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
                               adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...), adv_extra<WfSkyDist>(extra...),
-                              adv_extra<WfEmit>(extra...));
+                              adv_extra<WfEmit>(extra...), adv_extra<WfFresnel>(extra...));
     wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 

@@ -6,7 +6,7 @@ here and nowhere else.  form_of(name) -> the word, or None for another kernel.""
 import re
 
 BITS = {"stats": 1 << 0, "first": 1 << 1, "tex": 1 << 2, "anim": 1 << 3, "list": 1 << 4, "fill": 1 << 5, "resume": 1 << 6, "lights": 1 << 7, "soft": 1 << 8,
-        "lens": 1 << 9, "close": 1 << 10, "shutter": 1 << 11, "sky": 1 << 12, "sample": 1 << 13, "emit": 1 << 14}
+        "lens": 1 << 9, "close": 1 << 10, "shutter": 1 << 11, "sky": 1 << 12, "sample": 1 << 13, "emit": 1 << 14, "fresnel": 1 << 15}
 _B = BITS
 # the names the forms had as kernels of their own (demangled, spaces dropped)
 OLD = {"wf_advance<false,false>": 0, "wf_advance<true,false>": _B["stats"], "wf_advance<false,true>": _B["first"], "wf_advance<true,true>": _B["first"] | _B["stats"],
@@ -25,6 +25,8 @@ ALL_FORMS = sorted(FORMS + SKY_FORMS)                                  # the 29 
 SKY_SAMPLE_FORMS = sorted([_B["soft"] | _B["sky"] | _B["sample"], _B["tex"] | _B["soft"] | _B["sky"] | _B["sample"]])
 # ... and the two of the emissive meshes (kFormEmit: the later launches of a chain in whose scene a mesh emits; any lights take the soft route)
 EMISSION_FORMS = sorted([_B["soft"] | _B["emit"], _B["tex"] | _B["soft"] | _B["emit"]])
+# ... and the four of the Fresnel dielectrics (kFormFresnel: the later launches of a chain in whose scene an object is effectively flagged; a light list or a radius takes the soft route)
+FRESNEL_FORMS = sorted([_B["fresnel"], _B["tex"] | _B["fresnel"], _B["soft"] | _B["fresnel"], _B["tex"] | _B["soft"] | _B["fresnel"]])
 
 
 def form(*names):

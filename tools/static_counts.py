@@ -209,7 +209,10 @@ ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
            # sky sampling (WfSkyDist): the two later launches of a sampling chain, whole (no labels)
            "wf_advance_soft_sky_sample": (("soft", "sky", "sample"), False), "wf_advance_tex_soft_sky_sample": (("tex", "soft", "sky", "sample"), False),
            # emissive meshes (WfEmit): the two later launches of a chain in whose scene a mesh emits, whole (no labels)
-           "wf_advance_soft_emit": (("soft", "emit"), False), "wf_advance_tex_soft_emit": (("tex", "soft", "emit"), False)}
+           "wf_advance_soft_emit": (("soft", "emit"), False), "wf_advance_tex_soft_emit": (("tex", "soft", "emit"), False),
+           # Fresnel dielectrics (WfFresnel): the four later launches of a chain in whose scene an object is effectively flagged, whole (no labels)
+           "wf_advance_fresnel": (("fresnel",), False), "wf_advance_tex_fresnel": (("tex", "fresnel"), False),
+           "wf_advance_soft_fresnel": (("soft", "fresnel"), False), "wf_advance_tex_soft_fresnel": (("tex", "soft", "fresnel"), False)}
 
 
 def advance_forms_counts(asm):
@@ -279,7 +282,8 @@ def main():
     for name in ("wf_advance_fill", "wf_advance_resume", "wf_advance_close", "wf_advance_lights", "wf_advance_tex_lights", "wf_advance_soft", "wf_advance_tex_soft", "wf_advance_lens",
                  "wf_advance_shutter_first", "wf_advance_lens_shutter_first", "wf_advance_shutter", "wf_advance_tex_shutter",
                  "wf_advance_sky", "wf_advance_tex_sky", "wf_advance_soft_sky", "wf_advance_tex_soft_sky",
-                 "wf_advance_soft_sky_sample", "wf_advance_tex_soft_sky_sample", "wf_advance_soft_emit", "wf_advance_tex_soft_emit"):
+                 "wf_advance_soft_sky_sample", "wf_advance_tex_soft_sky_sample", "wf_advance_soft_emit", "wf_advance_tex_soft_emit",
+                 "wf_advance_fresnel", "wf_advance_tex_fresnel", "wf_advance_soft_fresnel", "wf_advance_tex_soft_fresnel"):
         res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
