@@ -624,6 +624,14 @@ int rt_count_work(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, r
  * such a ray whose fold met a negative or non-finite operand or a colour of 2^126 and more (a statistic: their pixels are the reference's all the same; 0 in any scene
  * with finite non-negative albedos and colours below 2^126).  The rule needs any-hit: the last two are 0 unless RT_TRAVQ_QW_COUNT=1. */
 int rt_dead_channel_counts(rt_ctx *ctx, uint64_t out[4]);
+/* Beside them, of the same rt_count_work: continuation rays (they passed the root box, and are among the first counter above) that the dead-last rule leaves out of
+ * the traversal in a frame of the same scene and knobs (the counting run itself traces them all).  The rule: in a chain of three segments or more, the LAST continuation ray of a path whose three colour channels are dead after the segment that
+ * emits it, and which the sphere tests show to hit a sphere for certain, is closed as that sphere's hit -- the pixel is +0 in every channel and the ray count the same
+ * whatever the mesh would have said.  Only where the scene allows it, decided at every call from the scene as it is then: every object diffuse with albedo components
+ * in [0, 1], no mesh shading with vertex normals, a finite light that stays clear of every sphere's surface and of the mesh's root box (csrc/rt_deadlast.h); only the plain chain (no
+ * texture, light list, lens, shutter, environment, emitter, fresnel flag, batch scenes or list).  RT_DEAD_LAST=0 traces the rays; frames are the same bit for bit.
+ * Needs any-hit and the dead-channel rule: 0 unless RT_TRAVQ_QW_COUNT=1. */
+int rt_dead_last_count(rt_ctx *ctx, uint64_t *out);
 /* The first-hit cache of the default pipeline: with sigma == 0 the camera ray of a pixel does not depend on the sample, so the mesh hits of a still
  * camera's primary rays are traced once per context and kept until the camera, the frame geometry, the row share, tri_tmin, the traversal form, the stream or the mesh
  * changes (RT_FIRST_HIT_CACHE=0 traces them in every chain; frames are the same bit for bit).  Since the context was created: launch chains that did not enqueue

@@ -68,6 +68,12 @@ int64_t rth_advance_form_fresnel(int counting, int tex, int anim, int list, int 
 void rth_row_cut(const int32_t *cases, int n, int32_t *out);
 int rth_row_chunks(const int32_t *cases, int n, int32_t *out, int cap);
 
+/* Test entry of the dead-last permission (csrc/rt_deadlast.h, shared with the render path): n cases of four facts -- the chain is a plain one, any-hit is on, the
+ * dead-channel rule is on, the knob RT_DEAD_LAST -- and n scenes (rtk::DeadLastScene, rth_dead_last_scene_size bytes each: n_spheres, n_objects, 16 x (centre, R),
+ * 16 x albedo, 16 x mirror, 16 x n_in, 16 x n_out, the light and its intensity, have_box, the root box's two corners, smooth; 4-byte fields) give n answers, 1 = permitted. */
+int rth_dead_last_scene_size(void);
+void rth_dead_last_permit(const int32_t *facts, const void *scenes, int n, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,7 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_scene_set_environment_sampling", "rt_scene_get_environment_sampling", "rt_kat_environment_table", "rt_kat_environment_sample",
            "rt_scene_set_emission", "rt_scene_get_emission", "rt_scene_set_emission_sampling", "rt_scene_get_emission_sampling",
            "rt_kat_emission_table", "rt_kat_emission_sample",
-           "rt_material_set_fresnel", "rt_material_get_fresnel", "rt_kat_fresnel"]
+           "rt_material_set_fresnel", "rt_material_get_fresnel", "rt_kat_fresnel", "rt_dead_last_count"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -362,9 +362,13 @@ def load():
     if os.environ.get("RT_LIB"):      # an experimental / older build may lack the newest entry points: give them inert stand-ins
         class _Missing:
             argtypes = restype = None
+
+        class _MissingCounter(_Missing):      # an entry that only reads counters (rt_*_count[s]): RT_OK and nothing written, the caller's zeros stand
+            def __call__(self, *args):
+                return 0
         for name in EXPORTS:
             if not hasattr(L, name):
-                setattr(L, name, _Missing())
+                setattr(L, name, _MissingCounter() if name.endswith(("_count", "_counts")) else _Missing())
     vp = C.c_void_p
     L.rt_abi_version.restype = C.c_int
     L.rt_device_count.argtypes = [C.POINTER(C.c_int)]
@@ -382,6 +386,7 @@ def load():
     L.rt_render_rgb8.argtypes = [vp, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     L.rt_count_work.argtypes = [vp, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(Work)]
     L.rt_dead_channel_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.rt_dead_last_count.argtypes = [vp, C.POINTER(C.c_uint64)]
     for n in ("rt_first_hit_cache_counts", "rt_first_shadow_cache_counts", "rt_first_shade_cache_counts"):
         getattr(L, n).argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_synchronize.argtypes = [vp]
@@ -1020,6 +1025,9 @@ class Context:
         dc = (C.c_uint64 * 4)()
         self._check(self._L.rt_dead_channel_counts(self._h, dc))
         out["dead_channels"] = dict(zip(("trav_continuation", "trav_shadow", "elided", "unsure"), (int(v) for v in dc)))   # rt_dead_channel_counts
+        dl = C.c_uint64(0)
+        self._check(self._L.rt_dead_last_count(self._h, C.byref(dl)))
+        out["dead_last"] = int(dl.value)                              # rt_dead_last_count
         out["steps"] = dict(zip(("iterations", "refill_passes", "refill_rounds", "fetches", "tri_steps", "box_steps", "literal_box_fallbacks", "serial_drains",
                                  "tdiv_blocks", "leaf_push_blocks", "leaf_push2_blocks", "anyhit_stop_steps"),
                                 (int(v) for v in w.steps)))

@@ -4,6 +4,7 @@
 #include "../rt_qrows.h"
 #include "../rt_still.h"
 #include "../rt_rowcut.h"
+#include "../rt_deadlast.h"
 
 using namespace raytracer;
 
@@ -181,6 +182,16 @@ int rth_row_chunks(const int32_t *cases, int n, int32_t *out, int cap) {
         }
     }
     return most;
+}
+
+// the dead-last permission (rt_deadlast.h), as enqueue_chain asks for it
+int rth_dead_last_scene_size(void) { return (int)sizeof(rtk::DeadLastScene); }
+void rth_dead_last_permit(const int32_t *facts, const void *scenes, int n, int32_t *out) {
+    const rtk::DeadLastScene *s = static_cast<const rtk::DeadLastScene *>(scenes);
+    for (int i = 0; i < n; ++i) {
+        const int32_t *f = facts + 4 * i;
+        out[i] = rtk::dead_last_permit(f[0] != 0, f[1] != 0, f[2] != 0, f[3], s[i]) ? 1 : 0;
+    }
 }
 
 }  // extern "C"

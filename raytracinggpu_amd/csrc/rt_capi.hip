@@ -345,6 +345,7 @@ int rt_count_work(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, r
     out->box_literal = h[5]; out->tri_literal = h[6];
     for (int k = 0; k < 12; ++k) out->steps[k] = h[8 + k];
     for (int k = 0; k < 4; ++k) ctx->dead_counts[k] = h[20 + k];
+    ctx->dead_last_count = h[7];
     // the counting instantiation checks every index that reaches an address (rt_travq.hip.h WQ_CHECK, rt_path.hip.h)
     if (h[4] != 0) return fail(ctx, RT_ERR_INTERNAL, "traversal invariant violated (mask 0x%llx: 1 path, 2 triangle, 4 node, 8 stack, 16 leaf queue, 32 staging)", h[4]);
     return RT_OK;
@@ -353,6 +354,12 @@ int rt_count_work(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, r
 int rt_dead_channel_counts(rt_ctx *ctx, uint64_t out[4]) {
     if (!ctx || !out) return fail(ctx, RT_ERR_INVALID, "bad arguments");
     for (int k = 0; k < 4; ++k) out[k] = ctx->dead_counts[k];
+    return RT_OK;
+}
+
+int rt_dead_last_count(rt_ctx *ctx, uint64_t *out) {
+    if (!ctx || !out) return fail(ctx, RT_ERR_INVALID, "bad arguments");
+    *out = ctx->dead_last_count;
     return RT_OK;
 }
 

@@ -70,6 +70,8 @@ struct Knobs {
                                // first accepted triangle that certainly shades, rt_wavefront.hip.h wf_anyhit_bound).  Bit-exact either way
     int dead_channels = 1;     // RT_DEAD_CHANNELS=0: a diffuse segment whose three colour channels are dead (a zero albedo component earlier on the path in each) still traces its
                                // shadow ray (A/B, cross-check; default: with any-hit on it does not, rt_wavefront.hip.h wf_dead_channels).  Bit-exact either way
+    int dead_last = 1;         // RT_DEAD_LAST=0: the last continuation ray of a path whose three colour channels are dead is traced through the mesh like every other (A/B, cross-check;
+                               // default: where the scene allows it and the ray certainly hits a sphere it is not, rt_deadlast.h, rt_wavefront.hip.h kPolDeadLast).  Bit-exact either way
     int travq_rows = 1;        // RT_TRAVQ_ROWS=0: every wf_travq launch scans the whole queue (A/B, cross-check; default: the first launch of a chain enumerates the rows that hold continuation
                                // rays only and the last the rows that hold shadow rays only, rt_qrows.h).  Bit-exact either way
     int first_hit_cache = 1;   // RT_FIRST_HIT_CACHE=0: every chain traces its camera rays (A/B, cross-check, and the figure of a moving camera; default: a still camera's primary mesh hits
@@ -139,6 +141,7 @@ static Knobs read_knobs() {
     if (geti("RT_TRAVQ_QSEL", v)) k.quad_sel = v != 0;
     if (geti("RT_TRAVQ_ANYHIT", v)) k.anyhit = v != 0;
     if (geti("RT_DEAD_CHANNELS", v)) k.dead_channels = v != 0;
+    if (geti("RT_DEAD_LAST", v)) k.dead_last = v != 0;
     if (geti("RT_SKY_SEARCH", v)) k.sky_search = v != 0;
     if (geti("RT_TRAVQ_ROWS", v)) k.travq_rows = v != 0;
     if (geti("RT_FIRST_HIT_CACHE", v)) k.first_hit_cache = v != 0;
@@ -287,6 +290,7 @@ struct rt_ctx {
     DevBuf wfM{bufs}, wfT{bufs}, wfLS{bufs}, wfSID{bufs}, wfSamp{bufs};   // wavefront path state (HBM); wfSamp / wfT: per-sample colours and their running sum (num_rays > 1)
     DevBuf wfDCH{bufs};                                             // ... the dead-channel byte of each path (wf_dead_channels)
     unsigned long long dead_counts[4] = {};                          // of the last rt_count_work: rt_dead_channel_counts
+    unsigned long long dead_last_count = 0;                          // ... and rt_dead_last_count
     // A still view's three levels (rt_still.h): per pixel slot of each sub-frame at its pxbase, the traversal result of the camera ray (8 bytes), of
     // segment 0's shadow ray (8 bytes) and the path after its shaded first hit (32 bytes, rtk::WfShade; allocated only once a chain may store it).  `still` says which
     // parts of them hold what, under which keys (rt_host_render.hip.h still_begin)

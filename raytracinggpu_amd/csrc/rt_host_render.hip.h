@@ -1,8 +1,27 @@
 // rt_host_render.hip.h -- host side, part 2 of 4: one frame (or a batch of frames) as launches -- variant choice, launch geometry of the wavefront pipeline, the two
 // sub-frames and their streams, pipelining across calls, chunking of big frames, tone mapping.
 #pragma once
+#include "rt_deadlast.h"
 
 namespace {
+
+// What the dead-last permission reads of the Scene a chain's launches are about to take (rt_deadlast.h)
+rtk::DeadLastScene dead_last_scene(const rtk::Scene &sc) {
+    rtk::DeadLastScene s{};
+    s.n_spheres = sc.n_spheres; s.n_objects = sc.n_objects;
+    for (int k = 0; k < sc.n_spheres && k < rtk::kDeadLastMaxObjects; ++k) { const rtk::Sphere &p = sc.sph[k]; s.sph[k][0] = p.cx; s.sph[k][1] = p.cy; s.sph[k][2] = p.cz; s.sph[k][3] = p.R; }
+    for (int k = 0; k < sc.n_objects && k < rtk::kDeadLastMaxObjects; ++k) {
+        s.alb[k][0] = sc.obj_b[k].x; s.alb[k][1] = sc.obj_b[k].y; s.alb[k][2] = sc.obj_b[k].z;
+        s.mirror[k] = __builtin_bit_cast(int, sc.obj_a[k].w);
+        s.n_in[k] = sc.obj_n[k].x; s.n_out[k] = sc.obj_n[k].y;
+    }
+    s.L[0] = sc.Lx; s.L[1] = sc.Ly; s.L[2] = sc.Lz; s.intensity = sc.intensity;
+    s.have_box = (sc.mesh_slot >= 0 && sc.n_nodes > 0) ? 1 : 0;   // wf_root_test's own condition
+    s.lo[0] = sc.root_lo.x; s.lo[1] = sc.root_lo.y; s.lo[2] = sc.root_lo.z;
+    s.hi[0] = sc.root_hi.x; s.hi[1] = sc.root_hi.y; s.hi[2] = sc.root_hi.z;
+    s.smooth = (sc.smooth_mask != 0 || sc.nrm != nullptr) ? 1 : 0;
+    return s;
+}
 
 int check_params(rt_ctx *ctx, const rt_params *p, int &segs) {
     if (!p) return fail(ctx, RT_ERR_INVALID, "params is NULL");
@@ -906,6 +925,10 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     const rtk::StillChain sc = (facts.lens || facts.shutter || facts.sky || facts.emit || facts.fresnel) ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
     // the plain chain takes the closing kernel at its last position
     const bool plain = t.queue && rtk::adv_plain_chain(facts);
+    // ... and, where the Scene of THIS enqueue allows it, leaves the last continuation ray of a dead path that hits a sphere out of the traversal (rt_deadlast.h; a counting
+    // chain counts those rays and traces them)
+    const bool dead_last = rtk::dead_last_permit(plain, pt.st.anyhit != 0, pt.st.deadch != 0, kn.dead_last, dead_last_scene(c.scn));
+    pt.st.policy = (pt.st.policy & ~rtk::kPolDeadLast) | (dead_last ? rtk::kPolDeadLast : 0);
     const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0, plain && kn.chain_ends != 0);
     auto block = [&](const DevBuf &b) { return static_cast<unsigned long long *>(b.p) + pt.pxbase; };   // the part's block of a level
     AdvArgs aa;

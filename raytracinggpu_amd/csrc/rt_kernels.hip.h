@@ -96,7 +96,7 @@ struct Frame {
     uint32_t seed;
     int row0, n_rows, tile_rows, tile_step;
     float4 *out;
-    unsigned long long *work;   // STATS kernels only: [24] {rays, box_tests, nodes, tri_tests, invariant mask, literal box tests, literal triangle tests, -,
+    unsigned long long *work;   // STATS kernels only: [24] {rays, box_tests, nodes, tri_tests, invariant mask, literal box tests, literal triangle tests, dead-last rays (wf_advance),
                                 // wf_travq step counters [8..19]: loop iterations, refill passes, refill rounds, queue fetches, TRI steps, BOX steps, literal-box fall-backs,
                                 // serial drains, t-division blocks, first / second leaf pushes, TRI steps that stopped a shadow ray (any-hit)}
     int out_tile0, out_tile_step;   // local row r is stored at output row ((r / tile_rows) * out_tile_step + out_tile0) * tile_rows + r % tile_rows
@@ -112,7 +112,7 @@ __device__ __forceinline__ size_t out_index(const Frame &fr, int lrow, int px) {
 }
 
 // per-lane traversal work counters (STATS instantiation only; SURVEY 8d accounting)
-struct Work { uint32_t box = 0, nodes = 0, tris = 0, rays = 0, lit_box = 0, lit_tri = 0, trav_y = 0, trav_x = 0, dead_elided = 0, dead_unsure = 0; };   // lit_*: tests decided by the literal divisions (filter undecided)
+struct Work { uint32_t box = 0, nodes = 0, tris = 0, rays = 0, lit_box = 0, lit_tri = 0, trav_y = 0, trav_x = 0, dead_elided = 0, dead_unsure = 0, dead_last = 0; };   // lit_*: tests decided by the literal divisions (filter undecided)
 
 struct f3 { float x, y, z; };
 __device__ __forceinline__ f3 mk(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }

@@ -221,6 +221,16 @@ struct WfState {
 // that were measured and taken out again (LS / SID of the segments folded out of reach, what a still view stores once): DESIGN.md section 11.
 constexpr int kPolRecords = 1;                               // the first-shade records wf_advance<kFormResume> loads: once per frame (a chain of one sample per pixel slot)
 constexpr int kPolPixels = 2;                                // the pixel store of the fold: no launch of the chain reads the frame
+// DEAD LAST (rt_deadlast.h: the permission, decided by the host at every enqueue; DESIGN.md section 5.1 "Dead paths").  One more wave-uniform bit of the same word, not a
+// stream group: the chain's LAST continuation ray (segment segs - 1) of a path whose three channels are dead after the segment that emits it, and whose sphere tests found
+// a hit, is not given its root test.  It leaves without PF_MESHY | PQ_TRAV, exactly as a ray that failed the root test: the next launch closes it as the sphere's hit,
+// stores that sphere's SID and lvis, elides and counts the segment's shadow ray as the dead-channel rule does (the mask stays 7: the permission keeps lvis below 2^96;
+// a -0 from a surface edge-on to the light clears it and traces the shadow ray, finite all the same)
+// and the path finishes in the launch it always finished in.  The frame cannot tell: each channel's kill sits at a segment <= segs - 2 and turns any FINITE ans of the last
+// segment into +0 -- finite for whatever the ray would really have hit and for the sphere shaded in its place is what the permission promises -- and .w counts the ray at
+// emission, then one shadow ray for the hit, which is certain (a sphere is hit, whatever the mesh says) and diffuse (every object is).  Only the plain later launch (form 0)
+// skips; its counting twin (kFormStats) traces every ray and counts the ones the rule would have kept from the traversal, those that pass the root box (Work::dead_last).
+constexpr int kPolDeadLast = 1 << 8;
 typedef float pol_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 pol_load(const float4 *p, bool nt) {
     if (nt) { const pol_f4 v = __builtin_nontemporal_load(reinterpret_cast<const pol_f4 *>(p)); return make_float4(v.x, v.y, v.z, v.w); }
@@ -308,6 +318,7 @@ __device__ __forceinline__ void wf_flush_work(const Frame &fr, Work &wk) {
         const uint32_t b = wave_sum(wk.box), n = wave_sum(wk.nodes), t = wave_sum(wk.tris), lb = wave_sum(wk.lit_box), lt = wave_sum(wk.lit_tri);
         // rays handed to the traversal (continuation, shadow), shadow rays the dead-channel rule elided, paths outside its guarantee: rt_dead_channel_counts
         const uint32_t ty = wave_sum(wk.trav_y), tx = wave_sum(wk.trav_x), de = wave_sum(wk.dead_elided), du = wave_sum(wk.dead_unsure);
+        const uint32_t dl = wave_sum(wk.dead_last);                    // continuation rays the dead-last rule would skip (kPolDeadLast): rt_dead_last_count
         if ((threadIdx.x & 63) == 0) {
             atomicAdd(&fr.work[1], (unsigned long long)b);
             atomicAdd(&fr.work[2], (unsigned long long)n); atomicAdd(&fr.work[3], (unsigned long long)t);
@@ -317,6 +328,7 @@ __device__ __forceinline__ void wf_flush_work(const Frame &fr, Work &wk) {
             if (tx) atomicAdd(&fr.work[21], (unsigned long long)tx);
             if (de) atomicAdd(&fr.work[22], (unsigned long long)de);
             if (du) atomicAdd(&fr.work[23], (unsigned long long)du);
+            if (dl) atomicAdd(&fr.work[7], (unsigned long long)dl);
         }
     }
 }
@@ -836,6 +848,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     // SKY, SHUTTER or EMIT, and in the later launches of a chain alone)
     constexpr bool FRESNEL = FORM & kFormFresnel;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
+    constexpr bool DEAD_LAST = (FORM & ~kFormStats) == 0u;             // the plain later launch and its counting twin: the one form with the dead-last rule (kPolDeadLast)
     // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
     // of the store (16 bytes of scratch) and keeps the plain one
     constexpr bool POL_PIXELS = !(TEX && ANIM);
@@ -855,6 +868,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     float x_bound = -__builtin_inff();                                // any-hit bound of the shadow ray (wf_anyhit_bound)
     bool x_sky = false;                                               // (SAMPLE) the shadow ray in question -- closed, then emitted -- goes to the sky
     bool x_moot = false;                                              // the shadow ray's answer cannot reach the pixel (direct term +0 either way, or every channel dead)
+    bool y_dead = false;                                              // (DEAD_LAST) the bounce ray leaves a diffuse segment after which every channel of the path is dead
     f3 Oy = mk(0, 0, 0), uy = mk(0, 0, 1), Ox = mk(0, 0, 0), ux = mk(0, 0, 1);
     f3 E = mk(0, 0, 0);                                               // (SKY) what the path's last ray met beyond the scene, (EMIT) the radiance of the emitter it hit: the fold starts from it
     int px, lrow; bool valid;
@@ -1170,6 +1184,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                             }
                             if (now != was) st.DCH[i] = (unsigned char)now;
                             if (FILL) sh_dch = now;
+                            if (DEAD_LAST) y_dead = (now & 7) == 7;
                         }
                         if (FILL) { shO = Pa; shV = N; sh_l = lvis; sh_kind = kShadeDiffuse; sh_sid = sid; }
                     }
@@ -1290,10 +1305,15 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     if (emitY) {
         t_sph = h.t;
         flags |= PF_HASY | (((h.obj + 1) & 31) << PQ_WIN_SHIFT);
-        if (wf_root_test<STATS>(sc, st, i, Oy, uy, wk)) {
+        // dead last: the chain's last continuation ray of a dead path that hits a sphere for certain (d is the emitted ray's segment; a chain of fewer than three
+        // segments is left alone)
+        bool dead_y = false;
+        if constexpr (DEAD_LAST) dead_y = (st.policy & kPolDeadLast) != 0 && y_dead && d == fr.segs - 1 && fr.segs >= 3 && h.obj >= 0;
+        if (!(dead_y && !STATS) && wf_root_test<STATS>(sc, st, i, Oy, uy, wk)) {
             flags |= PF_MESHY | PQ_TRAV;
             if (FIRST && st.m0 && s_rel != 0) flags &= ~PQ_TRAV;      // the same camera ray as the first sample's item of this pixel slot: closed from its word, never fetched by the traversal
             if (STATS) wk.trav_y++;
+            if (STATS && dead_y) wk.dead_last++;                      // (the counting form) the rule takes this ray out of the traversal
         }
     }
     st.QR[2 * (size_t)qy] = make_float4(Oy.x, Oy.y, Oy.z, uy.x);    // whole sectors also when no continuation ray leaves (then nobody reads this half)

@@ -10,7 +10,8 @@ LIB_PATH = os.environ.get("RT_HOST_LIB") or os.path.join(HERE, "libraytrace_host
 EXPORTS = ["rth_mesh_new", "rth_mesh_free", "rth_mesh_read_obj", "rth_mesh_set_arrays", "rth_mesh_rescale",
            "rth_mesh_build_bvh", "rth_mesh_num_vertices", "rth_mesh_num_triangles", "rth_mesh_num_nodes",
            "rth_mesh_get_vertices", "rth_mesh_get_indices", "rth_mesh_get_bvh_array", "rth_write_png", "rth_qrows_enumerate", "rth_still_replay",
-           "rth_row_cut", "rth_row_chunks", "rth_advance_form", "rth_advance_form_shutter", "rth_advance_form_sky", "rth_advance_form_sky_sample", "rth_advance_form_emit", "rth_advance_form_fresnel"]
+           "rth_row_cut", "rth_row_chunks", "rth_advance_form", "rth_advance_form_shutter", "rth_advance_form_sky", "rth_advance_form_sky_sample", "rth_advance_form_emit", "rth_advance_form_fresnel",
+           "rth_dead_last_scene_size", "rth_dead_last_permit"]
 _lib = None
 
 
@@ -52,6 +53,8 @@ def load():
         L.rth_row_cut.restype = None
         L.rth_row_cut.argtypes = [ip, C.c_int, ip]
         L.rth_row_chunks.argtypes = [ip, C.c_int, ip, C.c_int]
+        L.rth_dead_last_permit.restype = None
+        L.rth_dead_last_permit.argtypes = [ip, vp, C.c_int, ip]
         _lib = L
     return _lib
 
@@ -189,6 +192,27 @@ def row_chunks(cases, cap=32):
     most = L.rth_row_chunks(x.ctypes.data_as(ip), len(x), out.ctypes.data_as(ip), cap)
     assert most <= cap, (most, cap)
     return out[:, :3], out[:, 3:].reshape(-1, cap, 5)
+
+
+# rtk::DeadLastScene (csrc/rt_deadlast.h), field for field
+DEAD_LAST_SCENE = np.dtype([("n_spheres", np.int32), ("n_objects", np.int32), ("sph", np.float32, (16, 4)), ("alb", np.float32, (16, 3)), ("mirror", np.int32, (16,)),
+                            ("n_in", np.float32, (16,)), ("n_out", np.float32, (16,)), ("L", np.float32, (3,)), ("intensity", np.float32), ("have_box", np.int32),
+                            ("lo", np.float32, (3,)), ("hi", np.float32, (3,)), ("smooth", np.int32)])
+
+
+def dead_last_permit(scenes, plain=1, anyhit=1, deadch=1, knob=1):
+    """The dead-last permission (csrc/rt_deadlast.h dead_last_permit, rth_dead_last_permit) of every scene of a DEAD_LAST_SCENE array under the chain's four facts
+    (scalars, or one per scene) -> bool [n]."""
+    L = load()
+    s = np.ascontiguousarray(np.atleast_1d(scenes), DEAD_LAST_SCENE)
+    assert L.rth_dead_last_scene_size() == DEAD_LAST_SCENE.itemsize, (L.rth_dead_last_scene_size(), DEAD_LAST_SCENE.itemsize)
+    facts = np.zeros((len(s), 4), np.int32)
+    for k, f in enumerate((plain, anyhit, deadch, knob)):
+        facts[:, k] = f
+    out = np.zeros(len(s), np.int32)
+    ip = C.POINTER(C.c_int32)
+    L.rth_dead_last_permit(facts.ctypes.data_as(ip), s.ctypes.data_as(C.c_void_p), len(s), out.ctypes.data_as(ip))
+    return out != 0
 
 
 def write_png(path, rgb8):

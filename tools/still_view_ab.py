@@ -1,7 +1,8 @@
 """GPU box: what one level of the still view (csrc/rt_still.h) takes off a frame -- --knob RT_FIRST_HIT_CACHE (a still camera),
 RT_FIRST_SHADOW_CACHE or RT_FIRST_SHADE_CACHE (a still view under a still light) -- and whether a change of the host code moved a frame at all.  --knob RT_CHAIN_ENDS:
 the same steps for the kernel of a plain chain's last launch (csrc/rt_wavefront.hip.h CLOSE), which every frame runs, a still view or not.  --knob RT_STREAM_POLICY: the
-same steps for the cache policy of wf_advance's use-once streams (kPol*), on = both groups (the default), --also 1,2 each group alone.  --also V[,V] adds this
+same steps for the cache policy of wf_advance's use-once streams (kPol*), on = both groups (the default), --also 1,2 each group alone.  --knob RT_DEAD_LAST: the same
+steps for the rule that leaves a dead path's last continuation ray out of the traversal (csrc/rt_deadlast.h), which every frame of a permitted scene runs.  --also V[,V] adds this
 build with the knob at each further value to the interleaved runs (an experimental build that knows more than on and off).
 
 For the headline frame and then for BASELINE config 2 (--width 512 --height 512 --spp 8), each step a process of its own under its own time limit, the first failure
@@ -23,7 +24,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CACHES = ["RT_FIRST_HIT_CACHE", "RT_FIRST_SHADOW_CACHE", "RT_FIRST_SHADE_CACHE"]
-KNOBS = CACHES + ["RT_CHAIN_ENDS", "RT_STREAM_POLICY"]
+KNOBS = CACHES + ["RT_CHAIN_ENDS", "RT_STREAM_POLICY", "RT_DEAD_LAST"]
 ap = argparse.ArgumentParser()
 ap.add_argument("--knob", required=True, choices=KNOBS)
 ap.add_argument("--parent-lib", default="")
