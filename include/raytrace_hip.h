@@ -571,6 +571,57 @@ int rt_material_set_fresnel(rt_ctx *ctx, int object_slot, int on);
 int rt_material_get_fresnel(const rt_ctx *ctx, int object_slot, int *on);
 int rt_kat_fresnel(rt_ctx *ctx, int count, const uint32_t *items, uint32_t *out);
 
+/* --- ROUGH MIRRORS: a GGX roughness per object, one facet drawn per hit (ABI 6, additive).  The reference's mirror is perfect (cpu:573-579).  An object with a roughness
+ *     alpha reflects each ray about a facet normal h drawn per hit instead of about the shading normal N; the reflected ray carries weight 1, so no throughput is stored
+ *     and no path state grows.  Off by default and per object; with no EFFECTIVE roughness every frame is launch for launch what it is without these entries, and no new
+ *     kernel runs.  The device step is gloss_step in rt_shade.hip.h, beside mirror_step; the model is tests/gloss_model.py.
+ *     THE LOBE, honestly: facet normals GGX-distributed with width alpha about the shading normal (h is drawn with density D(h) (n.h)), reflectance 1, NO
+ *     shadowing-masking term; a ray that a facet would send below the surface is folded back above it (mirrored about N).  This conserves energy -- every ray leaves
+ *     with weight 1 -- and is not reciprocal.
+ *     Binary32 with one rounding per operation, no fused multiply-add, quotients correctly rounded, fl() one rounding; the square roots are rt_sqrtf; sine and cosine are
+ *     rt_sincos_2pi on the binary64 product, in cosine_bounce's forms.
+ *     THE VALUE.  The context holds one binary32 alpha per object position (up to RT_MAX_OBJECTS = 16).  rt_material_set_roughness(ctx, object_slot, alpha) sets it,
+ *     rt_material_get_roughness reads it as set.  Accepted: 0 (smooth, the default; -0 is stored as +0) and [2^-12, 1].  Any slot of the uploaded scene is accepted, sphere
+ *     or mesh.  RT_ERR_NO_SCENE without an upload; RT_ERR_INVALID, the state and the output untouched, for a slot outside the scene, a NULL output or any other value, NaN
+ *     included.  rt_scene_upload* clears every value.  A value is EFFECTIVE only where alpha > 0 and the object's material takes the mirror branch (mirror != 0), read
+ *     from the materials as they are when a frame's chain is planned (rt_scene_set_sphere may change a material after the value was set).  A roughness on a diffuse or a
+ *     glass object changes nothing.
+ *     THE HIT.  The continuation ray (O, u) of segment d hits an object with an effective roughness at P with normal N, where the mirror's arm runs otherwise.
+ *       1. N is the hit's normal exactly as mirror_step receives it, NOT oriented towards the ray.  un = dot(u, N).  O = fl(P + eps N): mirror_step's, word for word.
+ *       2. r1 = uniform01(hs, 2^25 + d, 0), r2 = uniform01(hs, 2^25 + d, 1), hs the sample's key: the RNG keys on depth * 4 + dim, so the draws sit at 2^27 + 4 d + dim --
+ *          above the jitter, bounce, pick and share draws (4 d' + dim, d' <= RT_MAX_SEGMENTS + 1: below 2^7) and below Fresnel's 2^28 + 4 d, the emitters' 2^29 + 4 d + dim, the lens and the
+ *          shutter at 2^30 + {0, 1, 2}, the shells' 2^31 + 4 d + {0, 1} and the sky's 3 2^30 + 4 d + dim.  With d <= RT_MAX_SEGMENTS the key stays below
+ *          2^27 + 2^7: none of the others reaches it.
+ *       3. The facet's polar angle, which samples D(h) (n.h):  a2 = fl(alpha alpha), m = fl(a2 - 1), c2 = fl(fl(1 - r1) / fl(1 + fl(m r1))), c = rt_sqrtf(c2),
+ *          s = rt_sqrtf(fl(1 - c2)).  THE RANGE, for alpha in [2^-12, 1] and r1 a multiple of 2^-24 in (0, 1]: 1 - r1 is exact (a multiple of 2^-24 in [0, 1)).  m is in
+ *          [-1, 0] (a2 is in [2^-24, 1], and a2 - 1 rounds to no less than -1), so the exact 1 + m r1 is >= 1 - r1 >= 0, and rounding is monotone and 1 - r1 is
+ *          representable: fl(m r1) >= -r1 and the denominator is >= 1 - r1.  It is positive: at r1 < 1 it is >= 1 - r1 >= 2^-24; at r1 = 1 it is fl(1 + m) = fl(a2),
+ *          at least 2^-24 (exactly 2^-24 at alpha = 2^-12; m = fl(2^-24 - 1) = -(1 - 2^-24) is exact).  So the quotient is in [0, 1], c2 is in [0, 1], 1 - c2 is in
+ *          [0, 1], and neither root sees a negative operand.
+ *       4. The azimuth and the facet: (sn, cs) = rt_sincos_2pi(2 pi (double) r2); x = (float)(cs (double) s), y = (float)(sn (double) s); T1, T2 are cosine_bounce's
+ *          tangent frame about N, the same expressions (T1 = normalize((-Ny, Nx, 0)) if Nx != 0 and Ny != 0, else normalize((-Nz, 0, Nx)); T2 = cross(N, T1));
+ *          h = (x T1 + y T2) + c N.  (A normal of exactly (0, +-1, 0) has no tangent frame -- the second vector is zero, its quotient 0 / 0 -- for a facet as for a
+ *          diffuse bounce: h and the ray are NaN there.)
+ *       5. Reflect about the facet: uh = dot(u, h); u' = u - fl(2 uh) h.
+ *       6. Keep the ray above the surface: vn = dot(u', N); if vn != 0 and (vn < 0) == (un < 0), the facet sent the ray into the surface, and it is mirrored back
+ *          out: u' = u' - fl(2 vn) N (FOLDED BACK).
+ *       7. The ray is not renormalised (the mirror's is not either); its index and its refr code stay, as at a mirror.  No shadow ray is emitted, SID[d] = 0xff, .w
+ *          counts one continuation ray, and shadow rays still stop at the object.
+ *     Rendered by the wavefront variants' launch chain (four forms of wf_advance, kFormGloss: with and without textures, with and without the soft lights' table, which
+ *     any light list or radius takes; the lens, poses, row shares, RT_PARTS, plain batches, rt_render_async, pipelining), which keeps no still-view cache under an effective
+ *     roughness; setting and removing a value leaves the caches as they were -- frames and cache counters are those of a context that never heard of these calls.  Under
+ *     RT_VARIANT_AUTO a scene of spheres alone takes the wavefront chain while a roughness is effective.
+ *     RT_ERR_UNSUPPORTED, outputs untouched, "roughness" in the error text, under an effective roughness: the variants path, lockstep and global, rt_count_work,
+ *     rt_render_counts*, rt_render_device_batch_scenes with scenes, and any frame while the scene also has an environment, the shutter is on, a mesh emits or a Fresnel
+ *     flag is effective.  The feature-buffer entries (rt_render_aov*, rt_render_aov_surface*) keep following the smooth mirror ray.  rt_multi_* contexts have no such
+ *     entries.
+ *     Known answer: rt_kat_gloss runs the device step on `count` explicit items; it needs no scene.  items: 16 32-bit words per item -- binary32 alpha, eps, P (3), N (3),
+ *     u (3) at words 0 to 10, then the integers hs (word 11) and seg (word 12), then three unused words.  out: 12 words per item -- binary32 h (3) at words 0 to 2, the
+ *     integer code at word 3 (0 plain, 1 folded back), the new O (3) at words 4 to 6 and u (3) at words 7 to 9, then two unused words, written as 0. */
+int rt_material_set_roughness(rt_ctx *ctx, int object_slot, float alpha);
+int rt_material_get_roughness(const rt_ctx *ctx, int object_slot, float *alpha);
+int rt_kat_gloss(rt_ctx *ctx, int count, const uint32_t *items, uint32_t *out);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

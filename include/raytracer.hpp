@@ -712,6 +712,14 @@ public:
         check(rt_material_get_fresnel(ctx_, object_slot, &on), "rt_material_get_fresnel");
         return on != 0;
     }
+    // Rough mirrors (rt_material_set_roughness): the object at an object position reflects about a GGX facet of width alpha, drawn per hit; 0 is smooth, other values
+    // lie in [2^-12, 1]; effective on mirrors alone; an upload clears every value
+    void set_roughness(int object_slot, float alpha) { check(rt_material_set_roughness(ctx_, object_slot, alpha), "rt_material_set_roughness"); }
+    float roughness(int object_slot) {
+        float alpha = 0.f;
+        check(rt_material_get_roughness(ctx_, object_slot, &alpha), "rt_material_get_roughness");
+        return alpha;
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

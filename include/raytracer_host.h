@@ -58,6 +58,8 @@ int64_t rth_advance_form_sky_sample(int counting, int tex, int anim, int list, i
 int64_t rth_advance_form_emit(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int sample, int emit, int adv);
 /* ... and the next: fresnel (an object of the scene is effectively flagged, rt_material_set_fresnel; bit 15 of the word).  fresnel == 0 is rth_advance_form_emit. */
 int64_t rth_advance_form_fresnel(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int sample, int emit, int fresnel, int adv);
+/* ... and the next: gloss (a mirror of the scene has an effective roughness, rt_material_set_roughness; bit 16 of the word).  gloss == 0 is rth_advance_form_fresnel. */
+int64_t rth_advance_form_gloss(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int sample, int emit, int fresnel, int gloss, int adv);
 
 /* Test entries of the cut of a call's rows (csrc/rt_rowcut.h, shared with the render path).  rth_row_cut: n cases of seven numbers -- an rt_rows (row0, n_rows, tile_rows,
  * tile_step), the sub-frames wanted (RT_PARTS), one (a counting run: one sub-frame), whole (a batch cut by frames: every sub-frame holds all rows) -- each give 52 numbers:

@@ -47,7 +47,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_scene_set_environment_sampling", "rt_scene_get_environment_sampling", "rt_kat_environment_table", "rt_kat_environment_sample",
            "rt_scene_set_emission", "rt_scene_get_emission", "rt_scene_set_emission_sampling", "rt_scene_get_emission_sampling",
            "rt_kat_emission_table", "rt_kat_emission_sample",
-           "rt_material_set_fresnel", "rt_material_get_fresnel", "rt_kat_fresnel", "rt_dead_last_count"]
+           "rt_material_set_fresnel", "rt_material_get_fresnel", "rt_kat_fresnel", "rt_dead_last_count",
+           "rt_material_set_roughness", "rt_material_get_roughness", "rt_kat_gloss"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -469,6 +470,9 @@ def load():
     L.rt_material_set_fresnel.argtypes = [vp, C.c_int, C.c_int]
     L.rt_material_get_fresnel.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.rt_kat_fresnel.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.rt_material_set_roughness.argtypes = [vp, C.c_int, C.c_float]
+    L.rt_material_get_roughness.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    L.rt_kat_gloss.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -929,6 +933,34 @@ class Context:
         self._check(self._L.rt_kat_fresnel(self._h, int(k), items.ctypes.data_as(up), out.ctypes.data_as(up)))
         g = out.view(np.float32)
         return g[:, 0].copy(), out[:, 1].astype(np.int32), g[:, 2:5].copy(), g[:, 5:8].copy(), g[:, 8].copy()
+
+    # --- rough mirrors (rt_material_set_roughness): the per-object GGX roughness and the device step's known answer
+    def set_roughness(self, object_slot, alpha):
+        """rt_material_set_roughness: the object at object_slot reflects about a GGX facet of width alpha (0: smooth; effective on mirrors alone); an upload clears it"""
+        self._check(self._L.rt_material_set_roughness(self._h, int(object_slot), float(alpha)))
+
+    def roughness(self, object_slot):
+        """rt_material_get_roughness -> alpha as set"""
+        a = C.c_float(0)
+        self._check(self._L.rt_material_get_roughness(self._h, int(object_slot), C.byref(a)))
+        return float(a.value)
+
+    def kat_gloss(self, alpha, eps, P, N, u, hs, seg):
+        """rt_kat_gloss: the device step on k explicit items (scalars broadcast; P, N, u [k, 3]) -> (h [k, 3] float32, code [k] int32: 0 plain, 1 folded back,
+        O [k, 3], u [k, 3])"""
+        h = np.ascontiguousarray(hs, dtype=np.uint32).ravel()
+        k = h.size
+        items = np.zeros((k, 16), np.uint32)
+        f = items.view(np.float32)
+        f[:, 0], f[:, 1] = alpha, eps
+        f[:, 2:5], f[:, 5:8], f[:, 8:11] = np.asarray(P, np.float32).reshape(-1, 3), np.asarray(N, np.float32).reshape(-1, 3), np.asarray(u, np.float32).reshape(-1, 3)
+        items[:, 11] = h
+        items[:, 12] = np.broadcast_to(np.asarray(seg, np.int32), (k,)).view(np.uint32) if np.ndim(seg) else np.uint32(int(seg))
+        out = np.zeros((k, 12), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        self._check(self._L.rt_kat_gloss(self._h, int(k), items.ctypes.data_as(up), out.ctypes.data_as(up)))
+        g = out.view(np.float32)
+        return g[:, 0:3].copy(), out[:, 3].astype(np.int32), g[:, 4:7].copy(), g[:, 7:10].copy()
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

@@ -386,6 +386,28 @@ int rt_material_get_fresnel(const rt_ctx *ctx, int object_slot, int *on) {
     return RT_OK;
 }
 
+// ---- rough mirrors (raytrace_hip.h "roughness"): one alpha per object position, host state alone ----
+// (Whether a value is effective is decided when a chain is planned, from the materials as they are then: gloss_effective in rt_host_render.hip.h.  The still view is
+// left alone, as by rt_material_set_fresnel: a chain under an effective roughness neither reads nor writes its buffers.)
+int rt_material_set_roughness(rt_ctx *ctx, int object_slot, float alpha) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (object_slot < 0 || object_slot >= ctx->scene.n_objects) return fail(ctx, RT_ERR_INVALID, "roughness: object_slot %d is outside the scene", object_slot);
+    if (!(alpha == 0.f || (alpha >= 0x1p-12f && alpha <= 1.f))) return fail(ctx, RT_ERR_INVALID, "roughness: alpha %g is neither 0 nor in [2^-12, 1]", (double)alpha);
+    ctx->gloss_alpha[object_slot] = alpha == 0.f ? 0.f : alpha;          // (-0 is stored as +0)
+    return RT_OK;
+}
+
+int rt_material_get_roughness(const rt_ctx *ctx, int object_slot, float *alpha) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    if (!alpha) return fail(c, RT_ERR_INVALID, "roughness: alpha is NULL");
+    if (object_slot < 0 || object_slot >= ctx->scene.n_objects) return fail(c, RT_ERR_INVALID, "roughness: object_slot %d is outside the scene", object_slot);
+    *alpha = ctx->gloss_alpha[object_slot];
+    return RT_OK;
+}
+
 // ---- the environment map (raytrace_hip.h "environment"): host state plus one device buffer of the context's; make_frame captures pointer and size ----
 int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");

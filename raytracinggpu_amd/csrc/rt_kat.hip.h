@@ -219,6 +219,20 @@ __global__ __launch_bounds__(256) void kat_fresnel_kernel(const float *__restric
     o[8] = s.r.refr_after;
 }
 
+// in: 16 words per item -- alpha, eps, P, N, u as binary32, then hs and seg as 32-bit integers, three words of padding; out: 12 words per item -- h, the code (kGloss*,
+// an integer), the new O and u, two words of padding: gloss_step (the step a wf_advance gloss form takes at a rough mirror) on explicit items
+__global__ __launch_bounds__(256) void kat_gloss_kernel(const float *__restrict__ in, int count, float *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const float *a = in + 16 * (size_t)i;
+    f3 O = mk(0.f, 0.f, 0.f), u = mk(a[8], a[9], a[10]);
+    const GlossStep s = gloss_step(a[1], a[0], mk(a[2], a[3], a[4]), mk(a[5], a[6], a[7]), O, u, __float_as_uint(a[11]), __float_as_int(a[12]));
+    float *o = out + 12 * (size_t)i;
+    o[0] = s.h.x; o[1] = s.h.y; o[2] = s.h.z; o[3] = __int_as_float(s.code);
+    o[4] = O.x; o[5] = O.y; o[6] = O.z; o[7] = u.x; o[8] = u.y; o[9] = u.z;
+    o[10] = 0.f; o[11] = 0.f;
+}
+
 }  // namespace rtk
 
 namespace {
@@ -293,6 +307,13 @@ int rt_kat_mesh(rt_ctx *ctx, const float *in, int n, float tri_tmin, int route, 
 int rt_kat_fresnel(rt_ctx *ctx, int count, const uint32_t *items, uint32_t *out) {
     return kat_run(ctx, reinterpret_cast<const float *>(items), count, 16, reinterpret_cast<float *>(out), 9, nullptr, [&](const float *di, float *dres, unsigned long long *, dim3 g, dim3 b) {
         hipLaunchKernelGGL(rtk::kat_fresnel_kernel, g, b, 0, own_stream(ctx), di, count, dres);
+    });
+}
+
+// the rough mirror's step on explicit items (raytrace_hip.h "roughness"): needs a context, not a scene
+int rt_kat_gloss(rt_ctx *ctx, int count, const uint32_t *items, uint32_t *out) {
+    return kat_run(ctx, reinterpret_cast<const float *>(items), count, 16, reinterpret_cast<float *>(out), 12, nullptr, [&](const float *di, float *dres, unsigned long long *, dim3 g, dim3 b) {
+        hipLaunchKernelGGL(rtk::kat_gloss_kernel, g, b, 0, own_stream(ctx), di, count, dres);
     });
 }
 

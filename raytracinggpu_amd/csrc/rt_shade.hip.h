@@ -403,6 +403,43 @@ __device__ __forceinline__ f3 cosine_bounce(f3 N, uint32_t hs, int d) {
     const f3 T2 = cross(N, T1);
     return x * T1 + y * T2 + zz * N;                                  // cpu:641
 }
+// ROUGH MIRRORS (rt_material_set_roughness; the rule: raytrace_hip.h "roughness"): mirror_step for an object with an effective roughness alpha -- the ray is reflected
+// about a facet normal h drawn from the GGX distribution D(h) (n.h) of width alpha about N, from the two draws at depth 2^25 + seg (keys 2^27 + 4 seg + {0, 1}), in
+// cosine_bounce's forms and tangent frame; a ray the facet sends into the surface is mirrored back out about N.  The ray carries weight 1: nothing of the path's state
+// grows.  1 - r1 is exact, the denominator is >= 1 - r1 > 0 or 2^-24 at r1 = 1: c2 is in [0, 1] and neither root sees a negative operand.
+constexpr int kGlossPlain = 0, kGlossFolded = 1;
+// h: the facet's normal; code: kGloss*
+struct GlossStep { f3 h; int code; };
+__device__ __forceinline__ GlossStep gloss_step(float eps, float alpha, f3 P, f3 N, f3 &O, f3 &u, uint32_t hs, int seg) {
+    GlossStep g;
+    const float un = dot(u, N);
+    O = P + eps * N;
+    const float r1 = uniform01(hs, (1u << 25) + (uint32_t)seg, 0);
+    const float r2 = uniform01(hs, (1u << 25) + (uint32_t)seg, 1);
+    const float a2 = alpha * alpha;
+    const float m = a2 - 1;
+    const float c2 = (1 - r1) / (1 + m * r1);
+    const float c = rt_sqrtf(c2);
+    const float s = rt_sqrtf(1 - c2);
+    double sn, cs;
+    rt_sincos_2pi(2 * 3.14159265358979323846 * (double)r2, sn, cs);
+    const float x = (float)(cs * (double)s);
+    const float y = (float)(sn * (double)s);
+    const bool t1a = N.y != 0 && N.x != 0;                            // cosine_bounce's tangent frame
+    float t1p, t1q, t1z;
+    normalize_pq0(t1a ? -N.y : -N.z, N.x, t1p, t1q, t1z);
+    const f3 T1 = t1a ? mk(t1p, t1q, t1z) : mk(t1p, t1z, t1q);
+    const f3 T2 = cross(N, T1);
+    g.h = x * T1 + y * T2 + c * N;
+    u = u - (2 * dot(u, g.h)) * g.h;
+    const float vn = dot(u, N);
+    g.code = kGlossPlain;
+    if (vn != 0 && (vn < 0) == (un < 0)) {                            // the facet sent the ray into the surface: back out
+        u = u - (2 * vn) * N;
+        g.code = kGlossFolded;
+    }
+    return g;
+}
 // cpu:624, 642-644: the colour of a path from a diffuse segment on -- its direct light l * albedo / pi plus albedo (.) the colour `ans` of what follows it
 __device__ __forceinline__ f3 fold_segment(f3 ans, float l, f3 alb) {
     const float PI_F = (float)3.14159265358979323846;

@@ -183,7 +183,8 @@ constexpr unsigned kFormStats = 1u << 0, kFormFirst = 1u << 1, kFormTex = 1u << 
                    kFormLights = 1u << 7, kFormSoft = 1u << 8, kFormLens = 1u << 9, kFormClose = 1u << 10, kFormShutter = 1u << 11, kFormSky = 1u << 12,
                    kFormSkySample = 1u << 13,                // sky sampling: a segment's shadow ray may go to the environment, drawn from its table (WfSkyDist, after the WfSky)
                    kFormEmit = 1u << 14,                     // emissive meshes: a ray that hits an emitter ends there, a segment's shadow ray may go to one (WfEmit, after the WfSoftLights)
-                   kFormFresnel = 1u << 15;                  // Fresnel dielectrics: a ray that hits a flagged glass object is reflected or refracted, one draw (WfFresnel, last)
+                   kFormFresnel = 1u << 15,                  // Fresnel dielectrics: a ray that hits a flagged glass object is reflected or refracted, one draw (WfFresnel, last)
+                   kFormGloss = 1u << 16;                    // rough mirrors: a ray that hits a mirror with a roughness is reflected about a GGX facet, two draws (WfGloss, last)
 constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks for this launch, and no kernel exists for it
 
 // What decides the form besides the step: the chain's facts.  counting: rt_count_work; anim: a batch with per-frame scenes; list: rt_render_counts*; lights: 0 the Scene's
@@ -191,9 +192,10 @@ constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks 
 // environment (rt_scene_set_environment) -- last and defaulted, for the same reason
 // emit: a mesh of the scene emits (rt_scene_set_emission) -- last and defaulted as well
 // fresnel: an object of the scene is effectively flagged (rt_material_set_fresnel) -- last and defaulted as well
-struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; bool sample = false; bool emit = false; bool fresnel = false; };   // sample: sky sampling is in effect (with sky), last and defaulted too
+// gloss: an object of the scene has an effective roughness (rt_material_set_roughness) -- last and defaulted as well
+struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; bool sample = false; bool emit = false; bool fresnel = false; bool gloss = false; };   // sample: sky sampling is in effect (with sky), last and defaulted too
 // The plain chain -- every launch after the opening one the form 0 or kFormStats (or the launch that stores the records): still_plan's `ends`, for a work-stack chain
-inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky && !f.emit && !f.fresnel; }
+inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky && !f.emit && !f.fresnel && !f.gloss; }
 // The form of the launch a chain of these facts enqueues for `adv` (StillAdv: StillPlan::open for the opening launch, StillStep::adv for the later ones)
 inline unsigned adv_form(const AdvFacts &f, int adv) {
     // counting, a list and an animated batch exclude one another, and each refuses several lights, a radius and the lens before a chain is planned (lights_refuse)
@@ -205,6 +207,16 @@ inline unsigned adv_form(const AdvFacts &f, int adv) {
     // the shutter refuse it (lights_refuse); no still view (no fill, no resume), and the closing kernel closes no continuation ray: not a plain chain.  A light list without
     // a radius goes through the soft forms with radii 0 (a radius-0 light is the light itself, bit for bit): four later forms, not six
     if (f.sample && !f.sky) return kFormNotBuilt;
+    // Rough mirrors: the facet is drawn where a continuation ray is closed, so the opening launch is what it was (the lens included) and every later launch has the
+    // bit.  Counting, a list, an animated batch, the shutter, an environment, an emitter and an effective Fresnel flag refuse it (lights_refuse); no still view (no
+    // fill, no resume: the records hold one continuation ray per pixel slot, a rough first hit has one per sample) and not a plain chain.  A light list or a radius
+    // takes the soft route: four forms
+    if (f.gloss) {
+        if (special != 0 || f.shutter || f.sky || f.emit || f.fresnel) return kFormNotBuilt;
+        if (adv == kAdvBegin) return kFormFirst | (f.lens ? kFormLens : 0u);
+        if (adv == kAdvPlain) return (f.tex ? kFormTex : 0u) | (f.lights != 0 ? kFormSoft : 0u) | kFormGloss;
+        return kFormNotBuilt;
+    }
     // Fresnel dielectrics: the choice is made where a continuation ray is closed, so the opening launch is what it was (the lens included) and every later launch has
     // the bit.  Counting, a list, an animated batch, the shutter, an environment and an emitter refuse it (lights_refuse); no still view (no fill, no resume: the records
     // hold one continuation ray per pixel slot, a flagged hit has one per sample) and not a plain chain.  A light list or a radius takes the soft route: four forms

@@ -712,8 +712,8 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #define ADV_MARK(name) do { } while (0)
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
-// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones, nor the EMIT ones, nor the FRESNEL ones)
-#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE && !EMIT && !FRESNEL) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
+// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones, nor the EMIT ones, nor the FRESNEL ones, nor the GLOSS ones)
+#define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE && !EMIT && !FRESNEL && !GLOSS) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
     const unsigned int *items;   // [n_paths] pixel slot << 6 | sample index; entries from n on are padding
@@ -809,6 +809,12 @@ __device__ __forceinline__ f3 wf_light_point(const WfSoftLights &sl, uint32_t hs
 // chain: with the lens on that launch is wf_advance<kFormFirst | kFormLens> (LENS, always FIRST), which takes the lens by value; every later launch of the chain is whichever kernel the scene
 // picks without a lens.  rtk::Scene and rtk::Frame do not grow.
 struct WfLens { float radius, focus; };
+// ROUGH MIRRORS (rt_material_set_roughness; the rule: raytrace_hip.h "roughness", the step: gloss_step in rt_shade.hip.h).  The table is a kernel argument of the four
+// forms that read it (kFormGloss) and of no other kernel; the one per-lane read is alpha[] with the hit object's id, from the argument segment, as WfSoftLights::radius[k].
+struct WfGloss {
+    unsigned int mask;                       // bit k: the object at position k has an EFFECTIVE roughness (alpha > 0 and mirror != 0: formed on the host)
+    float alpha[kMaxObjects];                // the roughness by object id; read only where the bit is set
+};
 // THE SHUTTER (rt_scene_set_shutter; the rule: raytrace_hip.h "shutter", the step: shutter_time / shutter_pose in rt_shade.hip.h).  Over the exposure the light travels dL and
 // sphere k travels its displacement; a path sees the scene at ONE time tau, drawn from its sample's key, and every launch of its chain -- the SHUTTER forms, kFormShutter --
 // draws tau again and forms the light and the centres at that time where the Scene's would be read: the close of a shadow ray, the sphere normal, the shadow direction and
@@ -837,7 +843,8 @@ template <unsigned FORM>
 __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr, const WfState &st, const int i, Work &wk, const TexScene &ts, const AnimFrame *__restrict__ anim,
                                                 const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln,
                                                 const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky, const WfSkyDist *__restrict__ sd = nullptr,
-                                                const WfEmit *__restrict__ em = nullptr, const WfFresnel *__restrict__ fz = nullptr) {
+                                                const WfEmit *__restrict__ em = nullptr, const WfFresnel *__restrict__ fz = nullptr,
+                                                const WfGloss *__restrict__ gz = nullptr) {
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
     constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter, SKY = FORM & kFormSky;
     constexpr bool SAMPLE = FORM & kFormSkySample;                     // sky sampling: a segment's one shadow ray may go to the environment (always with SKY and the soft lights' table)
@@ -847,6 +854,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     // Fresnel dielectrics: a continuation ray that hits an effectively flagged object is reflected or refracted, one draw (fresnel_step beside refract_step; never with
     // SKY, SHUTTER or EMIT, and in the later launches of a chain alone)
     constexpr bool FRESNEL = FORM & kFormFresnel;
+    // rough mirrors: a continuation ray that hits a mirror with an effective roughness is reflected about a facet, two draws (gloss_step beside mirror_step; never with
+    // SKY, SHUTTER, EMIT or FRESNEL, and in the later launches of a chain alone)
+    constexpr bool GLOSS = FORM & kFormGloss;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     constexpr bool DEAD_LAST = (FORM & ~kFormStats) == 0u;             // the plain later launch and its counting twin: the one form with the dead-last rule (kPolDeadLast)
     // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
@@ -1037,7 +1047,14 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 bool cont = false;                                    // a continuation ray of segment d+1 was built in (O,u)
                 bool fresnel_hit = false;                             // (FRESNEL) the object is effectively flagged: glass that reflects or refracts, chosen by one draw
                 if constexpr (FRESNEL) fresnel_hit = ((fz->mask >> win) & 1u) != 0;
-                if (!RESUME && m.mirror) {
+                bool gloss_hit = false;                               // (GLOSS) the object is a mirror with an effective roughness
+                if constexpr (GLOSS) gloss_hit = ((gz->mask >> win) & 1u) != 0;
+                if (gloss_hit) {
+                    if constexpr (GLOSS) {                            // the mirror branch below with gloss_step in mirror_step's place
+                        gloss_step(fr.eps, gz->alpha[win], P, N, O, u, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d);
+                        cont = true;
+                    }
+                } else if (!RESUME && m.mirror) {
                     mirror_step(fr.eps, P, N, O, u);
                     cont = true;
                 } else if (fresnel_hit) {
@@ -1338,7 +1355,10 @@ template <class T, class... Extra> constexpr bool adv_takes = (std::is_same_v<T,
 // scratch at eight, 16 at seven, none at six (74 registers).
 // The fresnel forms carry one draw and two quotients more than their counterparts.  fresnel and soft | fresnel: eight waves, 52 and 54 registers, nothing spills;
 // tex | fresnel: at eight waves 2 scalar registers spill, at seven nothing does; tex | soft | fresnel: seven, as its counterpart.
-constexpr int adv_waves(unsigned form) { return (form & kFormFresnel) ? ((form & kFormTex) ? 7 : 8) : (form & kFormEmit) ? ((form & kFormTex) ? 6 : 7) : (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
+// The gloss forms carry two draws, one quotient, two roots, the sincos and the tangent frame more than their counterparts (+ 385 vector instructions).  gloss and
+// soft | gloss: eight waves, 52 and 54 registers, nothing spills; tex | gloss: at eight waves 2 scalar registers spill, at seven nothing does; tex | soft | gloss:
+// seven, as its counterpart.
+constexpr int adv_waves(unsigned form) { return (form & kFormGloss) ? ((form & kFormTex) ? 7 : 8) : (form & kFormFresnel) ? ((form & kFormTex) ? 7 : 8) : (form & kFormEmit) ? ((form & kFormTex) ? 6 : 7) : (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
 template <unsigned FORM, class... Extra>
 __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene sc, const Frame fr, const WfState st, const Extra... extra) {
     static_assert(adv_takes<TexScene, Extra...> == ((FORM & kFormTex) != 0) && adv_takes<AnimTable, Extra...> == ((FORM & kFormAnim) != 0) &&
@@ -1346,14 +1366,15 @@ __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene s
                   adv_takes<WfLights, Extra...> == ((FORM & kFormLights) != 0) && adv_takes<WfSoftLights, Extra...> == ((FORM & kFormSoft) != 0) &&
                   adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0) &&
                   adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0) && adv_takes<WfSkyDist, Extra...> == ((FORM & kFormSkySample) != 0) &&
-                  adv_takes<WfEmit, Extra...> == ((FORM & kFormEmit) != 0) && adv_takes<WfFresnel, Extra...> == ((FORM & kFormFresnel) != 0),
+                  adv_takes<WfEmit, Extra...> == ((FORM & kFormEmit) != 0) && adv_takes<WfFresnel, Extra...> == ((FORM & kFormFresnel) != 0) &&
+                  adv_takes<WfGloss, Extra...> == ((FORM & kFormGloss) != 0),
                   "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths)
         wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
                               adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...), adv_extra<WfSkyDist>(extra...),
-                              adv_extra<WfEmit>(extra...), adv_extra<WfFresnel>(extra...));
+                              adv_extra<WfEmit>(extra...), adv_extra<WfFresnel>(extra...), adv_extra<WfGloss>(extra...));
     wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 

@@ -212,7 +212,10 @@ ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
            "wf_advance_soft_emit": (("soft", "emit"), False), "wf_advance_tex_soft_emit": (("tex", "soft", "emit"), False),
            # Fresnel dielectrics (WfFresnel): the four later launches of a chain in whose scene an object is effectively flagged, whole (no labels)
            "wf_advance_fresnel": (("fresnel",), False), "wf_advance_tex_fresnel": (("tex", "fresnel"), False),
-           "wf_advance_soft_fresnel": (("soft", "fresnel"), False), "wf_advance_tex_soft_fresnel": (("tex", "soft", "fresnel"), False)}
+           "wf_advance_soft_fresnel": (("soft", "fresnel"), False), "wf_advance_tex_soft_fresnel": (("tex", "soft", "fresnel"), False),
+           # rough mirrors (WfGloss): the four later launches of a chain in whose scene a mirror has an effective roughness, whole (no labels)
+           "wf_advance_gloss": (("gloss",), False), "wf_advance_tex_gloss": (("tex", "gloss"), False),
+           "wf_advance_soft_gloss": (("soft", "gloss"), False), "wf_advance_tex_soft_gloss": (("tex", "soft", "gloss"), False)}
 
 
 def advance_forms_counts(asm):
@@ -283,7 +286,8 @@ def main():
                  "wf_advance_shutter_first", "wf_advance_lens_shutter_first", "wf_advance_shutter", "wf_advance_tex_shutter",
                  "wf_advance_sky", "wf_advance_tex_sky", "wf_advance_soft_sky", "wf_advance_tex_soft_sky",
                  "wf_advance_soft_sky_sample", "wf_advance_tex_soft_sky_sample", "wf_advance_soft_emit", "wf_advance_tex_soft_emit",
-                 "wf_advance_fresnel", "wf_advance_tex_fresnel", "wf_advance_soft_fresnel", "wf_advance_tex_soft_fresnel"):
+                 "wf_advance_fresnel", "wf_advance_tex_fresnel", "wf_advance_soft_fresnel", "wf_advance_tex_soft_fresnel",
+                 "wf_advance_gloss", "wf_advance_tex_gloss", "wf_advance_soft_gloss", "wf_advance_tex_soft_gloss"):
         res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
