@@ -398,14 +398,20 @@ __device__ __forceinline__ bool intersect_all(const Scene &sc, f3 O, f3 u, float
 struct Material { float ar, ag, ab; int mirror; float n_in, n_out; };
 // Geometry's fields (cpu:106-118) of object `obj`, sphere or mesh: Scene::getColor reads them for whichever object was hit (cpu:573-606).  (Callers use a
 // part of the record: the loads of the rest are dropped.)
-__device__ __forceinline__ Material material_of(const Scene &sc, int obj) {
+// The object's three records as loaded (obj_a: centre and mirror flag, obj_b: albedo, obj_n: the two indices) -- the one place that knows their layout: material_of and
+// sphere_centre_of below, and wf_advance_path's plain forms, which load the records themselves in one round (rt_wavefront.hip.h)
+__device__ __forceinline__ Material material_from(float4 a, float4 b, float2 n) {
     Material m;
-    const float4 a = sc.obj_a[obj], b = sc.obj_b[obj];
-    const float2 n = sc.obj_n[obj];
     m.ar = b.x; m.ag = b.y; m.ab = b.z; m.mirror = __float_as_int(a.w); m.n_in = n.x; m.n_out = n.y;
     return m;
 }
-__device__ __forceinline__ f3 sphere_centre_of(const Scene &sc, int obj) { const float4 a = sc.obj_a[obj]; return mk(a.x, a.y, a.z); }
+__device__ __forceinline__ f3 sphere_centre_from(float4 a) { return mk(a.x, a.y, a.z); }
+__device__ __forceinline__ Material material_of(const Scene &sc, int obj) {
+    const float4 a = sc.obj_a[obj], b = sc.obj_b[obj];
+    const float2 n = sc.obj_n[obj];
+    return material_from(a, b, n);
+}
+__device__ __forceinline__ f3 sphere_centre_of(const Scene &sc, int obj) { return sphere_centre_from(sc.obj_a[obj]); }
 
 }  // namespace rtk
 

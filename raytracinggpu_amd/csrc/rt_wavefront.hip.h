@@ -859,6 +859,10 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     constexpr bool GLOSS = FORM & kFormGloss;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     constexpr bool DEAD_LAST = (FORM & ~kFormStats) == 0u;             // the plain later launch and its counting twin: the one form with the dead-last rule (kPolDeadLast)
+    // The plain chain's later launches (form 0, the closing kernel, their counting twins) ask for a path's words in ROUNDS, not one dependent load after the other: the Y
+    // record whole, then -- the flag word known -- the mesh words and the dead-channel byte together, and the shadow ray is formed again from the Y record and the light
+    // instead of being read back.  Every other form keeps the order it had.
+    constexpr bool PLAIN = (FORM & ~(kFormStats | kFormClose)) == 0u;
     // the stream policy's store in the fold (kPolPixels), in every form but the textured animated batch's: at 64 registers that kernel has no room for the second form
     // of the store (16 bytes of scratch) and keeps the plain one
     constexpr bool POL_PIXELS = !(TEX && ANIM);
@@ -866,6 +870,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     const int rx = st.n_paths + i;                                    // ray index of this path's shadow ray
     const int qy = wf_ray_to_slot(st, i), qx = wf_ray_to_slot(st, rx);
     const float4 y1 = (FIRST || RESUME) ? kDead : st.QR[2 * (size_t)qy + 1];      // (u.y, u.z, flag word, t of the nearest sphere) of the continuation ray in flight
+    // (PLAIN) the other half of the Y record's sector, asked for in the same round: behind the return below the compiler may not issue it until y1 is back
+    float4 y0 = kDead;
+    if constexpr (PLAIN && !CLOSE) y0 = st.QR[2 * (size_t)qy];
     const int F = __float_as_int(y1.z);
     if (!FIRST && !RESUME && !(F & PF_ALIVE)) {                                  // finished (or padding): its queue flags are already 0
         if (st.x0 == 1 && !st.m0 && i < st.n_px) st.X0[i] = WF_NOHIT;  // (first-shadow fill: no word of a filled part is stale)
@@ -884,6 +891,32 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     int px, lrow; bool valid;
     int s_rel = 0;
     if (st.n_paths != st.n_px) s_rel = wf_div(i, st.n_px, st.n_px_m);
+    // (PLAIN) the round behind the flag word: the continuation ray's mesh word, the shadow ray's (from where x_close0 and x0 below say) and the dead-channel byte, each only
+    // for the path that consumes it, none consumed before all are asked for.  (CLOSE) the fold's SID and LS words ride in the same round: their addresses need i and the
+    // segment alone.  kFoldRound segments, back to front from the last one, are held in registers; a longer chain folds the rest as it always did.
+    constexpr int kFoldRound = 3;
+    unsigned long long pre_ym = WF_NOHIT, pre_xm = WF_NOHIT;
+    int pre_dch = 0;
+    int pre_sid[kFoldRound];
+    float pre_ls[kFoldRound];
+    if constexpr (PLAIN) {
+        if (!CLOSE && (F & (PF_HASY | PF_MESHY)) == (PF_HASY | PF_MESHY)) pre_ym = st.M[st.m0 ? i - s_rel * st.n_px : i];
+        if ((F & (PF_HASX | PQ_XSPHERE | PF_MESHX)) == (PF_HASX | PF_MESHX)) {   // the condition under which wf_x_shadowed asks for the word
+            const int first = s_rel * st.n_px;
+            pre_xm = !(st.x0 != 0 && !st.m0) ? st.M[rx] : st.x0 == 2 ? st.X0[i - first] : st.M[rx - first];
+        }
+        if (!CLOSE && st.deadch) pre_dch = st.DCH[i];
+        if constexpr (CLOSE) {
+            const int dF = (F >> PF_DEPTH_SHIFT) & PF_DEPTH_MASK;
+            const int nsegF = dF < fr.segs ? dF : fr.segs;
+#pragma unroll
+            for (int j = 0; j < kFoldRound; ++j) {
+                const int k = nsegF - 1 - j;
+                pre_sid[j] = 0xff; pre_ls[j] = 0.f;
+                if (k >= 0) { pre_sid[j] = st.SID[(size_t)k * st.n_paths + i]; pre_ls[j] = st.LS[(size_t)k * st.n_paths + i]; }
+            }
+        }
+    }
     // a batch: item i belongs to frame s_rel (a wave's 64 items share it: n_px is a multiple of 64), whose camera, seed and output replace the launch's -- from scalar registers
     float camx = sc.camx, camy = sc.camy, camz = sc.camz, fr_z = fr.z;
     uint32_t fr_seed = fr.seed;
@@ -989,6 +1022,29 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 }
                 if (shadowed) em->L3[(size_t)(d - 1) * st.n_paths + i] = make_float4(0.f, 0.f, 0.f, l4.w);
             }
+        } else if constexpr (PLAIN) {
+            // The word is in flight since the round behind the flags.  The ray: in these forms a shadow ray leaves a diffuse hit alone, from the point the continuation
+            // ray leaves (Ox == Oy == P_adjusted), towards the Scene's light: the origin is the Y record's first half -- which the launch that shades the chain's last
+            // segment stores for this purpose, where no continuation ray leaves -- and the direction is shadow_dir of the operands the emission gave it, the same
+            // function on the same 32-bit words.  One route keeps the read-back: a chain of ONE segment whose shadow rays the launch that stores the first-shade
+            // records emitted (x_close0 at the last position): that form leaves the default origin in the Y record.
+            if (F & PF_HASX) {
+                const bool x_readback = x_close0 && fr.segs == 1;
+                const bool shadowed = wf_x_shadowed(F, L, [&] { return pre_xm; }, [&](f3 &Oxr, f3 &uxr) {
+                    if (x_readback) {
+                        const float4 x0 = st.QR[2 * (size_t)qx], x1 = st.QR[2 * (size_t)qx + 1];
+                        Oxr = mk(x0.x, x0.y, x0.z); uxr = mk(x0.w, x1.x, x1.y);
+                    } else {
+                        if constexpr (CLOSE) y0 = st.QR[2 * (size_t)qy];
+                        float nl;
+                        Oxr = mk(y0.x, y0.y, y0.z); uxr = shadow_dir(L, Oxr, nl);
+                    }
+                }, xm);
+                if (shadowed) {
+                    st.LS[(size_t)(d - 1) * st.n_paths + i] = 0.f;
+                    if constexpr (CLOSE) if (d <= fr.segs) pre_ls[0] = 0.f;       // segment d - 1 is the first the fold takes: the word held for it
+                }
+            }
         } else
         if (!RESUME && (F & PF_HASX)) {
             const bool shadowed = wf_x_shadowed(F, L, [&] {
@@ -1005,7 +1061,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         // ---- (2) the continuation ray of segment d came back: Scene::getColor's branch for its hit ----
         if (!CLOSE && (RESUME || (F & PF_HASY))) {                    // (CLOSE: no continuation ray reaches the chain's last launch)
             ADV_MARK("closey_begin");
-            const float4 r0 = RESUME ? ra : st.QR[2 * (size_t)qy];
+            const float4 r0 = RESUME ? ra : PLAIN ? y0 : st.QR[2 * (size_t)qy];
             f3 O = mk(r0.x, r0.y, r0.z), u = RESUME ? mk(ra.w, rb.x, rb.y) : mk(r0.w, y1.x, y1.y);   // (RESUME: the continuation ray of a specular hit; P_adjusted and N of a diffuse one)
             int sid = 0xff;                                           // object id if the hit is diffuse
             // Scene::intersect_all's running minimum (strict '<' in object order, cpu:554) = the lexicographic minimum over (t, position in Scene::objects):
@@ -1014,7 +1070,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             int win = ((F >> PQ_WIN_SHIFT) & 31) - 1, tri_win = -1;
             if (RESUME) win = sh_kind == kShadeMiss ? -1 : 0;         // (which object: the record's SID says, to the fold)
             if (!RESUME && (F & PF_MESHY)) {
-                const unsigned long long m = st.M[st.m0 ? i - s_rel * st.n_px : i];   // (m0: the camera ray's result, kept per pixel slot)
+                const unsigned long long m = PLAIN ? pre_ym : st.M[st.m0 ? i - s_rel * st.n_px : i];   // (m0: the camera ray's result, kept per pixel slot)
                 if (m != WF_NOHIT) {
                     const float tm = __uint_as_float((unsigned int)(m >> 32));
                     const int mobj = mesh_obj_of_tri(sc, (int)(unsigned int)m);   // the meshes' own winner: minimum over (t, object position, scan rank) by the order the triangles are stored in
@@ -1038,11 +1094,22 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                 Bary bary{0.f, 0.f, 0.f};                             // (TEX) the smooth normal's barycentrics, shared with the texture lookup
                 bool have_bary = false;
                 f3 N;
+                Material m_plain{};
                 if (RESUME) N = u;
                 else if (ANIM && tri_win < 0) { const float4 c = af->ctr[win]; N = normalize(P - mk(c.x, c.y, c.z)); }   // sphere_normal (cpu:524-525) about this frame's centre
                 else if (SHUTTER && tri_win < 0) N = normalize(P - shutter_pose(sphere_centre_of(sc, win), wf_xyz(shu->obj[win]), tau));   // ... about the centre at the path's time
+                else if constexpr (PLAIN) {
+                    // The hit object's three records in ONE round, asked for before the triangle's: left to itself the compiler moves each load into the branch that
+                    // reads it -- the centre, then the mirror flag of the same record, then the indices, then the albedo: four dependent trips for a wall.  The empty
+                    // statement below reads every word where the normal is done, so all are in flight together (it has no instruction of its own).
+                    const float4 oa = sc.obj_a[win], ob = sc.obj_b[win];
+                    const float2 on = sc.obj_n[win];
+                    N = tri_win >= 0 ? hit_normal(sc, win, tri_win, O, u, P, bary, have_bary) : normalize(P - sphere_centre_from(oa));   // (sphere_normal on the words of its record)
+                    asm volatile("" :: "v"(oa.w), "v"(ob.x), "v"(ob.y), "v"(ob.z), "v"(on.x), "v"(on.y));
+                    m_plain = material_from(oa, ob, on);
+                }
                 else N = hit_normal(sc, win, tri_win, O, u, P, bary, have_bary);
-                const Material m = material_of(sc, win);
+                const Material m = PLAIN ? m_plain : material_of(sc, win);
                 ADV_MARK("closey_end");
                 bool cont = false;                                    // a continuation ray of segment d+1 was built in (O,u)
                 bool fresnel_hit = false;                             // (FRESNEL) the object is effectively flagged: glass that reflects or refracts, chosen by one draw
@@ -1168,6 +1235,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         if (LIGHTS == 1) { L = wf_light_pick(*lt, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d); intensity = lt->total; }   // this segment's light, at the intensity of all
                         if (LIGHTS == 2) { L = wf_light_point(*sl, sample_hash(pixel_hash(fr, row, px, fr_seed), samp), d); intensity = sl->lt.total; }   // ... a point of its shell
                         Ox = Pa; ux = shadow_dir(L, Pa, nl);                // the shadow ray of segment d
+                        if constexpr (PLAIN) Oy = Pa;                       // ... whose origin the launch that closes it takes from the Y record, continuation ray or none
                         x_bound = wf_anyhit_bound(Pa, nl);
                         nrays += 1;
                         // the segment's direct term if the light turns out to be visible; kept until the shadow ray is back
@@ -1192,7 +1260,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         }
                         // Every channel dead, this segment's albedo counted: lvis or +0, the pixel is the same (wf_dead_channels) -- moot for a second reason
                         if (st.deadch) {
-                            const int was = st.DCH[i];
+                            const int was = PLAIN ? pre_dch : st.DCH[i];
                             int now = (was & 8) | wf_dead_channels(was & 7, alb, lvis);
                             if ((now & 7) == 7 && !x_moot) {
                                 x_moot = true;
@@ -1239,7 +1307,28 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
         f3 ans = (SKY || EMIT) ? E : mk(0, 0, 0);
         bool fold_sure = true;                                        // (counting instantiation) every folded segment passed wf_fold_bounded
         const int nseg = d < fr.segs ? d : fr.segs;
-        for (int k = nseg - 1; k >= 0; --k) {
+        if constexpr (PLAIN && CLOSE) {                               // the segments whose words the round behind the flags asked for, in the fold's order
+            // ... and their albedos in one round as well (a segment without one asks for object 0's; the empty statement keeps the loads where they are written)
+            f3 pre_alb[kFoldRound];
+#pragma unroll
+            for (int j = 0; j < kFoldRound; ++j) {
+                const float4 b = sc.obj_b[pre_sid[j] != 0xff ? pre_sid[j] : 0];
+                pre_alb[j] = mk(b.x, b.y, b.z);
+            }
+            static_assert(kFoldRound == 3, "the statement below names every albedo");
+            asm volatile("" :: "v"(pre_alb[0].x), "v"(pre_alb[1].x), "v"(pre_alb[2].x));
+#pragma unroll
+            for (int j = 0; j < kFoldRound; ++j) {
+                const int sid = pre_sid[j];                           // (0xff past the path's first segment)
+                if (sid != 0xff) {
+                    const f3 alb = pre_alb[j];
+                    const float l = pre_ls[j];
+                    ans = fold_segment(ans, l, alb);
+                    if (STATS && !wf_fold_bounded(ans, l, alb)) fold_sure = false;
+                }
+            }
+        }
+        for (int k = nseg - 1 - ((PLAIN && CLOSE) ? kFoldRound : 0); k >= 0; --k) {
             const int sid = st.SID[(size_t)k * st.n_paths + i];
             if (sid != 0xff) {
                 f3 alb;
@@ -1333,7 +1422,10 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
             if (STATS && dead_y) wk.dead_last++;                      // (the counting form) the rule takes this ray out of the traversal
         }
     }
-    st.QR[2 * (size_t)qy] = make_float4(Oy.x, Oy.y, Oy.z, uy.x);    // whole sectors also when no continuation ray leaves (then nobody reads this half)
+    // whole sectors also when no continuation ray leaves.  (PLAIN) the half is read then as well: a shadow ray that leaves alone has its origin here (Oy = P_adjusted, set
+    // in the diffuse branch), and the launch that closes it -- the closing kernel, or form 0 in its place -- takes it from this store instead of reading the X record back.
+    // In the other forms nobody reads the half of a path without a continuation ray.
+    st.QR[2 * (size_t)qy] = make_float4(Oy.x, Oy.y, Oy.z, uy.x);
     st.QR[2 * (size_t)qy + 1] = make_float4(emitY ? uy.y : 0.f, emitY ? uy.z : 0.f, __int_as_float(flags), t_sph);   // the path's state travels with its Y slot
 }
 
