@@ -638,7 +638,12 @@ typedef struct rt_frame_scene {    /* what differs from the uploaded scene in ON
 int rt_render_device_batch_scenes(rt_ctx *ctx, const rt_params *p, const rt_rows *rows, const rt_frame_desc *frames,
                                   const rt_frame_scene *scenes, int n_spheres, int n_frames, void *stream);
 
-/* --- tonemap: cpu:714-716 (gamma 1/2.2 in binary64, min 255, truncate) ------- */
+/* --- tonemap: cpu:714-716 (gamma 1/2.2 in binary64, min 255, truncate) -------
+ *     byte = (unsigned char)min(pow((double)c, 1./2.2), 255.) of .x, .y, .z; .w is not read.  Special values, as the oracle records them: NaN -> 0; a finite
+ *     negative c (-1e-45 included) -> pow is NaN -> 0; +-0 -> 0; +inf -> 255; -inf -> 255 (pow(-inf, y) is +inf for this y).  Denormals are ordinary inputs: 0.
+ *     rgb8_dev may be any address: an image that starts on a 4-byte boundary is written as 32-bit words, any other byte by byte; either way exactly
+ *     3 * n_pixels bytes are written.  n_pixels == 0 writes nothing.  tests/test_gpu_gamma_bytes.py holds the bytes to the exactly rounded power at every code
+ *     boundary (tests/gamma_model.py). */
 int rt_tonemap_device(rt_ctx *ctx, const void *rgba_dev, int64_t n_pixels, void *rgb8_dev, void *stream);
 /* render + tonemap + D2H of the interleaved RGB8 image (what stbi_write_png gets, cpu:719) */
 int rt_render_rgb8(rt_ctx *ctx, const rt_params *p, int row_begin, int row_end, uint8_t *out_rgb8_host);
@@ -980,6 +985,14 @@ int rt_render_pose_device(rt_ctx *ctx, const rt_params *p, const rt_camera_pose 
 int rt_progressive_reset(rt_ctx *ctx);
 int rt_progressive_frame(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *pose, float *display_rgba_host, uint8_t *rgb8_host);
 int rt_progressive_frames(const rt_ctx *ctx, int *frames);
+/* The 8-bit image of rt_progressive_frame is realtime:1136-1147, in binary32: v = (double)powf(c, 1 / 2.2f); if (!(v < 255.)) v = 255.; (unsigned char)v.
+ * Its exponent is the binary32 1 / 2.2f, not 1./2.2: its code boundaries are not rt_tonemap_device's.  Special values, as the reference's own kernel recorded them
+ * (tests/golden/ref_realtime.npz): NaN -> 255 (it fails the `<`); a negative c, -1e-45 and -inf included -> powf is NaN -> 255; +-0 -> 0; +inf -> 255.
+ * Known answer (ABI 6, additive): rt_kat_progressive runs the production kernel of rt_progressive_frame on the caller's values.  n float4 of accumbuffer and of the
+ * new frame in; accumbuffer + frame, the display values (accumbuffer * (1.0f / framenumber), .w = accumbuffer.w) and the n * 3 bytes out, each may be NULL.  Host
+ * memory; no scene is needed, and the context's own progressive state (rt_progressive_frames, its buffers) is untouched.  RT_ERR_INVALID: n < 0, framenumber < 1,
+ * a NULL input with n > 0.  n == 0 writes nothing. */
+int rt_kat_progressive(rt_ctx *ctx, const float *accum_in, const float *frame, int n, int framenumber, float *accum_out, float *display_out, uint8_t *rgb8_out);
 
 /* --- first-hit feature buffers (G-buffer) and an edge-avoiding denoiser (ABI 6, additive).  A frame of one sample per pixel is noise; the remedy that needs
  *     no further frames is a filter guided by what the camera ray of each pixel hit first.

@@ -76,6 +76,10 @@ int rth_row_chunks(const int32_t *cases, int n, int32_t *out, int cap);
 int rth_dead_last_scene_size(void);
 void rth_dead_last_permit(const int32_t *facts, const void *scenes, int n, int32_t *out);
 
+/* Test entry of the progressive path's float -> byte conversion (csrc/rt_gamma.h, shared with accumulate_kernel): n binary32 values give n bytes, each the byte of the
+ * correctly rounded powf(c, 1 / 2.2f) under realtime:1136-1147, read off the committed thresholds. */
+void rth_gamma_byte(const float *c, int n, uint8_t *out);
+
 #ifdef __cplusplus
 }
 #endif

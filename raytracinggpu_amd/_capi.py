@@ -48,7 +48,8 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_scene_set_emission", "rt_scene_get_emission", "rt_scene_set_emission_sampling", "rt_scene_get_emission_sampling",
            "rt_kat_emission_table", "rt_kat_emission_sample",
            "rt_material_set_fresnel", "rt_material_get_fresnel", "rt_kat_fresnel", "rt_dead_last_count",
-           "rt_material_set_roughness", "rt_material_get_roughness", "rt_kat_gloss"]
+           "rt_material_set_roughness", "rt_material_get_roughness", "rt_kat_gloss",
+           "rt_kat_progressive"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -473,6 +474,7 @@ def load():
     L.rt_material_set_roughness.argtypes = [vp, C.c_int, C.c_float]
     L.rt_material_get_roughness.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.rt_kat_gloss.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.rt_kat_progressive.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
     L.rt_render_aov.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), fp3]
@@ -1616,6 +1618,19 @@ class Context:
         n = C.c_int(0)
         self._check(self._L.rt_progressive_frames(self._h, C.byref(n)))
         return n.value
+
+    def kat_progressive(self, accum, frame, framenumber):
+        """rt_kat_progressive: the progressive kernel on explicit values, accum and frame [n, 4] float32 -> (accum + frame [n, 4], display [n, 4], rgb8 [n, 3]);
+        the context's own progressive state is not touched"""
+        a = np.ascontiguousarray(accum, np.float32).reshape(-1, 4)
+        f = np.ascontiguousarray(frame, np.float32).reshape(-1, 4)
+        if a.shape != f.shape:
+            raise ValueError(f"accum {a.shape} and frame {f.shape} differ")
+        acc, disp, rgb8 = np.empty_like(a), np.empty_like(a), np.empty((len(a), 3), np.uint8)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.rt_kat_progressive(self._h, a.ctypes.data_as(fp), f.ctypes.data_as(fp), len(a), int(framenumber), acc.ctypes.data_as(fp),
+                                               disp.ctypes.data_as(fp), rgb8.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return acc, disp, rgb8
 
     def synchronize(self):
         self._check(self._L.rt_synchronize(self._h))

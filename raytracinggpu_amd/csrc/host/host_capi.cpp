@@ -5,6 +5,7 @@
 #include "../rt_still.h"
 #include "../rt_rowcut.h"
 #include "../rt_deadlast.h"
+#include "../rt_gamma.h"
 
 using namespace raytracer;
 
@@ -196,6 +197,11 @@ void rth_dead_last_permit(const int32_t *facts, const void *scenes, int n, int32
         const int32_t *f = facts + 4 * i;
         out[i] = rtk::dead_last_permit(f[0] != 0, f[1] != 0, f[2] != 0, f[3], s[i]) ? 1 : 0;
     }
+}
+
+// the progressive path's byte (rt_gamma.h), as accumulate_kernel computes it
+void rth_gamma_byte(const float *c, int n, uint8_t *out) {
+    for (int i = 0; i < n; ++i) out[i] = (uint8_t)rtk::gamma_byte_f(c[i]);
 }
 
 }  // extern "C"

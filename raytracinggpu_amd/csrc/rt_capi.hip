@@ -541,6 +541,34 @@ int rt_progressive_frame(rt_ctx *ctx, const rt_params *p, const rt_camera_pose *
     return copy_back(ctx, rgb8_host, ctx->scratch_rgb8.p, rgb8_host ? (size_t)npix * 3 : 0);
 }
 
+// accumulate_kernel itself on the caller's values: buffers of the call's own, so no scene is needed and the context's progressive state is not touched.  The bytes land
+// between two guards of 16 bytes of 0xA5 on the device, which must come back as they were.
+int rt_kat_progressive(rt_ctx *ctx, const float *accum_in, const float *frame, int n, int framenumber, float *accum_out, float *display_out, uint8_t *rgb8_out) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    RT_OWN_STREAM(ctx);
+    if (n < 0 || framenumber < 1 || (n > 0 && (!accum_in || !frame))) return fail(ctx, RT_ERR_INVALID, "bad KAT arguments");
+    if (n == 0) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * sizeof(float4), guard = 16, nb = (size_t)n * 3;
+    DevBuf dacc, dfr, ddisp, d8;
+    int rc;
+    if ((rc = upload(ctx, dacc, accum_in, bytes)) != RT_OK || (rc = upload(ctx, dfr, frame, bytes)) != RT_OK || (rc = ensure(ctx, ddisp, bytes)) != RT_OK ||
+        (rc = ensure(ctx, d8, nb + 2 * guard)) != RT_OK)
+        return rc;
+    RT_HIP(ctx, hipMemsetAsync(d8.p, 0xA5, nb + 2 * guard, own_stream(ctx)));
+    hipLaunchKernelGGL(rtk::accumulate_kernel, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, own_stream(ctx), static_cast<const float4 *>(dfr.p),
+                       static_cast<float4 *>(dacc.p), static_cast<float4 *>(ddisp.p), static_cast<uint8_t *>(d8.p) + guard, (int64_t)n, framenumber);
+    RT_HIP(ctx, hipGetLastError());
+    if (accum_out) RT_HIP(ctx, hipMemcpyAsync(accum_out, dacc.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
+    if (display_out) RT_HIP(ctx, hipMemcpyAsync(display_out, ddisp.p, bytes, hipMemcpyDeviceToHost, own_stream(ctx)));
+    std::vector<uint8_t> h8(nb + 2 * guard);
+    if ((rc = copy_back(ctx, h8.data(), d8.p, h8.size())) != RT_OK) return rc;
+    for (size_t k = 0; k < guard; ++k)
+        if (h8[k] != 0xA5 || h8[guard + nb + k] != 0xA5) return fail(ctx, RT_ERR_INTERNAL, "accumulate_kernel wrote outside its %zu bytes", nb);
+    if (rgb8_out) memcpy(rgb8_out, h8.data() + guard, nb);
+    return RT_OK;
+}
+
 int rt_host_alloc(void **ptr, size_t bytes) {
     if (!ptr) return fail(nullptr, RT_ERR_INVALID, "ptr is NULL");
     *ptr = nullptr;

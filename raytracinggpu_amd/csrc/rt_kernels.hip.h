@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include "rt_sincos.h"
 #include "rt_div.h"
+#include "rt_gamma.h"
 
 namespace rtk {
 
@@ -507,7 +508,8 @@ __global__ __launch_bounds__(kBlockThreads) void render_kernel(const Scene sc, c
 }
 
 // cpu:714-716: std::min(std::pow(c, 1./2.2), 255.) -> unsigned char.  4 pixels per lane,
-// 12 output bytes written as three dwords.
+// 12 output bytes written as three dwords where `out` is 4-byte aligned, else byte by byte.
+// NaN -> 0 (as the oracle's tonemap1), so a finite negative c -> 0; +-0 -> 0; +-inf -> 255 (pow(-inf, y) is +inf).
 __device__ __forceinline__ uint32_t tone1(float c) {
     double v = pow((double)c, 1. / 2.2);
     if (255. < v) v = 255.;
@@ -524,19 +526,22 @@ __global__ __launch_bounds__(256) void tonemap_kernel(const float4 *__restrict__
         float4 c = (p0 + k < npix) ? rgba[p0 + k] : make_float4(0, 0, 0, 0);
         b[3 * k + 0] = tone1(c.x); b[3 * k + 1] = tone1(c.y); b[3 * k + 2] = tone1(c.z);
     }
-    if (p0 + 4 <= npix) {
-        uint32_t *o = reinterpret_cast<uint32_t *>(out + 3 * p0);   // 12*q bytes: 4-byte aligned
+    const bool words = (reinterpret_cast<uintptr_t>(out) & 3u) == 0;   // an argument: the same for every lane
+    if (p0 + 4 <= npix && words) {
+        uint32_t *o = reinterpret_cast<uint32_t *>(out + 3 * p0);   // out + 12*q bytes: 4-byte aligned where out is
         o[0] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
         o[1] = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
         o[2] = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
-    } else {
-        for (int64_t k = 0; p0 + k < npix; ++k)
+    } else {                                                         // the frame's last 1 to 3 pixels, or an image that starts off a 4-byte boundary: byte by byte
+        for (int64_t k = 0; k < 4 && p0 + k < npix; ++k)
             for (int ch = 0; ch < 3; ++ch) out[3 * (p0 + k) + ch] = (uint8_t)b[3 * k + ch];
     }
 }
 
 // Progressive accumulation, realtime_render.cu:1136-1147: accumbuffer += frame; display = accumbuffer / framenumber
 // (cutil_math: a * (1.0f / s)); 8-bit image = (unsigned char)min(powf(c, 1 / 2.2f), 255.).  .w carries the ray counts.
+// The byte is that of the CORRECTLY ROUNDED powf, read off the committed thresholds of rt_gamma.h, not computed with the device's powf (which is not correctly
+// rounded and wrote another byte next to code boundaries).  NaN and every negative c (-1e-45, -inf) -> 255, +-0 -> 0, +inf -> 255.
 __global__ __launch_bounds__(256) void accumulate_kernel(const float4 *__restrict__ frame, float4 *__restrict__ accum, float4 *__restrict__ display,
                                                          uint8_t *__restrict__ rgb8, int64_t npix, int framenumber) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -548,12 +553,9 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const float4 *__restric
     const float inv = 1.0f / (float)framenumber;
     const float4 d = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w);
     display[i] = d;
-    const float c[3] = {d.x, d.y, d.z};
-    for (int k = 0; k < 3; ++k) {
-        double v = (double)powf(c[k], 1 / 2.2f);
-        if (!(v < 255.)) v = 255.;
-        rgb8[3 * i + k] = (uint8_t)v;
-    }
+    rgb8[3 * i + 0] = (uint8_t)gamma_byte_f(d.x);
+    rgb8[3 * i + 1] = (uint8_t)gamma_byte_f(d.y);
+    rgb8[3 * i + 2] = (uint8_t)gamma_byte_f(d.z);
 }
 
 }  // namespace rtk

@@ -11,7 +11,7 @@ EXPORTS = ["rth_mesh_new", "rth_mesh_free", "rth_mesh_read_obj", "rth_mesh_set_a
            "rth_mesh_build_bvh", "rth_mesh_num_vertices", "rth_mesh_num_triangles", "rth_mesh_num_nodes",
            "rth_mesh_get_vertices", "rth_mesh_get_indices", "rth_mesh_get_bvh_array", "rth_write_png", "rth_qrows_enumerate", "rth_still_replay",
            "rth_row_cut", "rth_row_chunks", "rth_advance_form", "rth_advance_form_shutter", "rth_advance_form_sky", "rth_advance_form_sky_sample", "rth_advance_form_emit", "rth_advance_form_fresnel", "rth_advance_form_gloss",
-           "rth_dead_last_scene_size", "rth_dead_last_permit"]
+           "rth_dead_last_scene_size", "rth_dead_last_permit", "rth_gamma_byte"]
 _lib = None
 
 
@@ -57,6 +57,8 @@ def load():
         L.rth_row_chunks.argtypes = [ip, C.c_int, ip, C.c_int]
         L.rth_dead_last_permit.restype = None
         L.rth_dead_last_permit.argtypes = [ip, vp, C.c_int, ip]
+        L.rth_gamma_byte.restype = None
+        L.rth_gamma_byte.argtypes = [fp, C.c_int, C.POINTER(C.c_uint8)]
         _lib = L
     return _lib
 
@@ -218,6 +220,14 @@ def dead_last_permit(scenes, plain=1, anyhit=1, deadch=1, knob=1):
     ip = C.POINTER(C.c_int32)
     L.rth_dead_last_permit(facts.ctypes.data_as(ip), s.ctypes.data_as(C.c_void_p), len(s), out.ctypes.data_as(ip))
     return out != 0
+
+
+def gamma_byte(values):
+    """The progressive path's byte (csrc/rt_gamma.h gamma_byte_f, rth_gamma_byte) of every binary32 of `values` -> uint8 of the same shape."""
+    a = np.ascontiguousarray(values, np.float32)
+    out = np.zeros(a.shape, np.uint8)
+    load().rth_gamma_byte(a.ctypes.data_as(C.POINTER(C.c_float)), a.size, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return out
 
 
 def write_png(path, rgb8):

@@ -503,8 +503,7 @@ def test_posed_camera_and_progressive_accumulation(ctx, oracle, oracle_cat, cat_
             assert ctx.progressive_frames() == frame
             edisp, ergb8 = oracle.progressive_accumulate(accum, got, frame)
             np.testing.assert_array_equal(disp.view(np.uint32), edisp.view(np.uint32))
-            assert np.abs(rgb8.astype(int) - ergb8.astype(int)).max() <= 1      # device powf vs glibc powf at a truncation boundary
-            assert (rgb8 != ergb8).mean() < 1e-3
+            np.testing.assert_array_equal(rgb8, ergb8)                 # every float near a code boundary is pinned by tests/test_gpu_gamma_bytes.py
     # the pose really is used: yawing the camera changes the image; variants without the pose path refuse
     a = ctx.render_pose(rt.make_params(W, H, 1, 0, **rt.scenes.CPU_LAUNCHER), rt.make_pose(yaw=0.0))
     b2 = ctx.render_pose(rt.make_params(W, H, 1, 0, **rt.scenes.CPU_LAUNCHER), rt.make_pose(yaw=0.5))
