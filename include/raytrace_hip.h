@@ -622,6 +622,45 @@ int rt_material_set_roughness(rt_ctx *ctx, int object_slot, float alpha);
 int rt_material_get_roughness(const rt_ctx *ctx, int object_slot, float *alpha);
 int rt_kat_gloss(rt_ctx *ctx, int count, const uint32_t *items, uint32_t *out);
 
+/* --- TINT: a specular colour per object, carried by the fold (ABI 6, additive).  The reference ignores the albedo of a mirror and of glass (cpu:573-607): every
+ *     mirror is silver and every glass ball clear.  A flagged mirror or glass object multiplies what is seen in it or through it by its own albedo, per channel.  The
+ *     path stores no new state for that: the throughput of a path IS its fold, fold_segment(ans, l, alb) = fl(fl(fl(l alb) / pi) + fl(alb ans)) per channel back to
+ *     front over the segments that are not marked 0xff, and a tinted specular segment is recorded as a segment of direct term +0.  Off by default and per object; with
+ *     no EFFECTIVE flag every frame is launch for launch what it is without these entries, and no new kernel runs.  The model is tests/tint_model.py.
+ *     THE FLAG.  The context holds one bit per object position (up to RT_MAX_OBJECTS = 16).  rt_material_set_tint(ctx, object_slot, on) sets it (on != 0) or clears it,
+ *     rt_material_get_tint reads it (1 or 0).  Any slot of the uploaded scene is accepted, sphere or mesh.  RT_ERR_NO_SCENE without an upload; RT_ERR_INVALID, the state
+ *     and the output untouched, for a slot outside the scene or a NULL output.  rt_scene_upload* clears every flag.
+ *     EFFECTIVE.  A flag is effective only where it is set and the object's material takes a specular arm: mirror != 0 (smooth, or rough by rt_material_set_roughness), or
+ *     n_in != n_out -- read from the materials as they are when a frame's chain is planned (rt_scene_set_sphere may change a material after the flag was set: a flag on
+ *     a diffuse sphere does nothing and starts to act when the sphere is made a mirror).
+ *     THE COLOUR is the object's albedo as the material table holds it: from the upload, from rt_scene_set_sphere, a mesh's uploaded albedo.  A texture is not sampled at
+ *     a specular hit: a textured mirror mesh is tinted by its material albedo.  The colour is meant to lie in [+0, 1] per channel; the fold is applied to whatever the
+ *     table holds (a component of -0 or below gives the direct term's fl(fl(0 alb) / pi) the sign bit: -0 + x is x unless x is -0).
+ *     THE HIT.  The continuation ray of segment d hits an effectively tinted object.  It takes exactly the arm it takes without the flag (mirror_step, gloss_step,
+ *     refract_step) and builds the same ray; it emits no shadow ray; .w counts what it counted.  It records SID[d] = the object's id and LS[d] = +0 where an unflagged
+ *     specular hit records SID[d] = 0xff.  The fold then forms, for that segment, fl(fl(fl((+0) alb) / pi) + fl(alb ans)) = fl(alb ans) per channel for alb >= +0:
+ *     what follows the hit, times the tint, one rounding.  A path whose first hit is a tinted mirror of tint t over a remainder X is fl(t X) per channel.
+ *     GLASS.  Every crossing of an interface is a hit, so glass is tinted PER INTERFACE: a ball seen through is tinted twice, once in and once out, fl(t fl(t X)); a
+ *     ray that is totally reflected inside is tinted once more per reflection.  This is a SURFACE tint, NOT Beer's law: the colour does not depend on the distance
+ *     travelled inside the object, and a thick and a thin part of a mesh are tinted alike.
+ *     DEAD CHANNELS.  The tinted segment goes through the dead-channel rule exactly as a diffuse segment of albedo alb and direct term +0 does
+ *     (wf_dead_channels(dead, alb, +0)): a zero channel of the tint kills that channel for the shadow rays of the segments behind it, a component above 1 resets the
+ *     mask.  To the fold the segment IS such a diffuse segment, so the argument for the elided shadow rays holds word for word, and frames under RT_DEAD_CHANNELS=0
+ *     are the default's words.  RT_DEAD_LAST applies only where every object is diffuse (csrc/rt_deadlast.h, condition (1)) and only in the plain chain: never here.
+ *     THE CLOSE OF A SHADOW RAY.  The launch after segment d decides whether a shadow ray of segment d is in flight from the path's flag word (PF_HASX, set where the
+ *     ray was emitted) and never from SID: a tinted segment, which emits none, is not taken for one that did, and its LS[d] stays +0.
+ *     Rendered by the wavefront variants' launch chain (four forms of wf_advance, kFormTint, each with the rough mirrors' arm compiled in -- a scene without an
+ *     effective roughness runs them with an empty roughness mask and takes the smooth mirror arm: with and without textures, with and without the soft lights' table,
+ *     which any light list or radius takes; the lens, poses, row shares, RT_PARTS, plain batches, rt_render_async, pipelining), which keeps no still-view cache under an
+ *     effective tint; setting and removing a flag leaves the caches as they were -- frames and cache counters are those of a context that never heard of these calls.
+ *     Under RT_VARIANT_AUTO a scene of spheres alone takes the wavefront chain while a tint is effective.
+ *     RT_ERR_UNSUPPORTED, outputs untouched, "tint" in the error text, under an effective tint: the variants path, lockstep and global, rt_count_work,
+ *     rt_render_counts*, rt_render_device_batch_scenes with scenes, and any frame while the scene also has an environment, the shutter is on, a mesh emits or a Fresnel
+ *     flag is effective.  The feature-buffer entries (rt_render_aov*, rt_render_aov_surface*) are unchanged: their albedo plane is not demodulated by a tint.
+ *     rt_multi_* contexts have no such entries.  There is no known-answer entry: no new device step exists for one to call. */
+int rt_material_set_tint(rt_ctx *ctx, int object_slot, int on);
+int rt_material_get_tint(const rt_ctx *ctx, int object_slot, int *on);
+
 /* --- ... and per FRAME of a batch: a sequence in which the light orbits and spheres move, at the throughput of rt_render_device_batch.  Frame k's buffer holds
  *     exactly what rt_render_device writes after the scene is uploaded with frames[k].camera, scenes[k].light and the uploaded spheres moved to
  *     scenes[k].spheres[0 .. n_spheres) (in the order of the uploaded spheres array; materials, object positions and meshes as uploaded), p->seed =

@@ -720,6 +720,14 @@ public:
         check(rt_material_get_roughness(ctx_, object_slot, &alpha), "rt_material_get_roughness");
         return alpha;
     }
+    // Tinted mirrors and glass (rt_material_set_tint): what is seen in or through the object at an object position is multiplied by its albedo, per interface (a surface
+    // tint, not Beer's law); effective on mirrors and glass alone; an upload clears every flag
+    void set_tint(int object_slot, bool on = true) { check(rt_material_set_tint(ctx_, object_slot, on ? 1 : 0), "rt_material_set_tint"); }
+    bool tint(int object_slot) {
+        int on = 0;
+        check(rt_material_get_tint(ctx_, object_slot, &on), "rt_material_get_tint");
+        return on != 0;
+    }
     void move_object(int index, const Vector &v, float dt = 0.2f) {
         const float vv[3] = {v[0], v[1], v[2]};
         check(rt_scene_move_sphere(ctx_, index, vv, dt), "rt_scene_move_sphere");

@@ -60,6 +60,8 @@ int64_t rth_advance_form_emit(int counting, int tex, int anim, int list, int len
 int64_t rth_advance_form_fresnel(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int sample, int emit, int fresnel, int adv);
 /* ... and the next: gloss (a mirror of the scene has an effective roughness, rt_material_set_roughness; bit 16 of the word).  gloss == 0 is rth_advance_form_fresnel. */
 int64_t rth_advance_form_gloss(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int sample, int emit, int fresnel, int gloss, int adv);
+/* ... and the next: tint (an object of the scene is effectively tinted, rt_material_set_tint; bit 17 of the word, always beside bit 16).  tint == 0 is rth_advance_form_gloss. */
+int64_t rth_advance_form_tint(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int sample, int emit, int fresnel, int gloss, int tint, int adv);
 
 /* Test entries of the cut of a call's rows (csrc/rt_rowcut.h, shared with the render path).  rth_row_cut: n cases of seven numbers -- an rt_rows (row0, n_rows, tile_rows,
  * tile_step), the sub-frames wanted (RT_PARTS), one (a counting run: one sub-frame), whole (a batch cut by frames: every sub-frame holds all rows) -- each give 52 numbers:

@@ -49,7 +49,7 @@ EXPORTS = ["rt_abi_version", "rt_device_count", "rt_ctx_create", "rt_ctx_destroy
            "rt_kat_emission_table", "rt_kat_emission_sample",
            "rt_material_set_fresnel", "rt_material_get_fresnel", "rt_kat_fresnel", "rt_dead_last_count",
            "rt_material_set_roughness", "rt_material_get_roughness", "rt_kat_gloss",
-           "rt_kat_progressive"]
+           "rt_kat_progressive", "rt_material_set_tint", "rt_material_get_tint"]
 MAX_OBJECTS = 16
 MAX_LIGHTS = 16
 MAX_DEVICES = 16
@@ -474,6 +474,8 @@ def load():
     L.rt_material_set_roughness.argtypes = [vp, C.c_int, C.c_float]
     L.rt_material_get_roughness.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.rt_kat_gloss.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.rt_material_set_tint.argtypes = [vp, C.c_int, C.c_int]
+    L.rt_material_get_tint.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.rt_kat_progressive.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
     L.rt_render_device_batch_scenes.argtypes = [vp, C.POINTER(Params), C.POINTER(Rows), C.POINTER(FrameDesc), C.POINTER(FrameScene), C.c_int, C.c_int, vp]
     L.rt_render_aov_device.argtypes = [vp, C.POINTER(Params), C.POINTER(CameraPose), C.POINTER(Rows), vp, vp]
@@ -963,6 +965,18 @@ class Context:
         self._check(self._L.rt_kat_gloss(self._h, int(k), items.ctypes.data_as(up), out.ctypes.data_as(up)))
         g = out.view(np.float32)
         return g[:, 0:3].copy(), out[:, 3].astype(np.int32), g[:, 4:7].copy(), g[:, 7:10].copy()
+
+    # --- tinted mirrors and glass (rt_material_set_tint): the per-object flag
+    def set_tint(self, object_slot, on=True):
+        """rt_material_set_tint: what is seen in or through the mirror or glass object at object_slot is multiplied by its albedo (effective on mirrors and glass alone);
+        an upload clears it"""
+        self._check(self._L.rt_material_set_tint(self._h, int(object_slot), 1 if on else 0))
+
+    def tint(self, object_slot):
+        """rt_material_get_tint -> bool"""
+        v = C.c_int(0)
+        self._check(self._L.rt_material_get_tint(self._h, int(object_slot), C.byref(v)))
+        return bool(v.value)
 
     def sphere(self, object_slot):
         """rt_scene_get_sphere -> (centre, radius, albedo, mirror, n_in, n_out): the tuple scene_upload takes"""

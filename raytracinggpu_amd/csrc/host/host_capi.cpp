@@ -147,6 +147,10 @@ int64_t rth_advance_form_gloss(int counting, int tex, int anim, int list, int le
     const unsigned form = rtk::adv_form(rtk::AdvFacts{counting != 0, tex != 0, anim != 0, list != 0, lens != 0, lights, shutter != 0, sky != 0, sample != 0, emit != 0, fresnel != 0, gloss != 0}, adv);
     return form == rtk::kFormNotBuilt ? -1 : (int64_t)form;
 }
+int64_t rth_advance_form_tint(int counting, int tex, int anim, int list, int lens, int lights, int shutter, int sky, int sample, int emit, int fresnel, int gloss, int tint, int adv) {
+    const unsigned form = rtk::adv_form(rtk::AdvFacts{counting != 0, tex != 0, anim != 0, list != 0, lens != 0, lights, shutter != 0, sky != 0, sample != 0, emit != 0, fresnel != 0, gloss != 0, tint != 0}, adv);
+    return form == rtk::kFormNotBuilt ? -1 : (int64_t)form;
+}
 
 // the cut of a call's rows into sub-frames (rt_rowcut.h), as cut_wavefront and launch_path ask for it
 void rth_row_cut(const int32_t *cases, int n, int32_t *out) {

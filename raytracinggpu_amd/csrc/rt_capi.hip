@@ -124,6 +124,7 @@ int rt_scene_upload_meshes(rt_ctx *ctx, const rt_sphere *spheres, int n_spheres,
     ctx->emit_total = 0; ctx->emit_dirty = false; ctx->emit_share = 0.5f; // the share at its default
     ctx->fresnel_mask = 0;                                               // ... and none of its objects is flagged (rt_material_set_fresnel)
     memset(ctx->gloss_alpha, 0, sizeof(ctx->gloss_alpha));               // ... and none has a roughness (rt_material_set_roughness)
+    ctx->tint_mask = 0;                                                  // ... and none is tinted (rt_material_set_tint)
     ctx->still.shading_changed();
     ctx->still.mesh_changed();
     if (n_spheres < 0 || (n_spheres > 0 && !spheres)) return fail(ctx, RT_ERR_INVALID, "bad sphere array");

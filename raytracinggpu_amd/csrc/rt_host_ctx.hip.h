@@ -227,6 +227,9 @@ struct rt_ctx {
     // Rough mirrors (rt_material_set_roughness): one binary32 alpha per object position, 0 (smooth) or in [2^-12, 1].  A value is EFFECTIVE only where the object's
     // material takes the mirror branch, read when a chain is planned (gloss_effective, rt_host_render.hip.h).  rt_scene_upload* clears every value.
     float gloss_alpha[rtk::kMaxObjects] = {};
+    // Tinted mirrors and glass (rt_material_set_tint): one bit per object position.  A bit is EFFECTIVE only where the object's material takes a specular arm, read when a
+    // chain is planned (tint_effective, rt_host_render.hip.h).  rt_scene_upload* clears every bit.
+    unsigned tint_mask = 0;
     DevBuf nrm{bufs};                                                 // smooth shading: 3 normals per triangle, visit order
     // textured meshes (rt_mesh_set_texture[_of]): 3 UVs per triangle in visit order (one buffer for the forest; a mesh's entries are read only while its bit is set),
     // the device copy of the per-object records, and per object its decode table (256 floats) followed by its texels.  rt_scene_upload* clears tex_mask first.

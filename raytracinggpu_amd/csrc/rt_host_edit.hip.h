@@ -408,6 +408,27 @@ int rt_material_get_roughness(const rt_ctx *ctx, int object_slot, float *alpha) 
     return RT_OK;
 }
 
+// ---- tinted mirrors and glass (raytrace_hip.h "tint"): one bit per object position, host state alone ----
+// (Whether a bit is effective is decided when a chain is planned, from the materials as they are then: tint_effective in rt_host_render.hip.h.  The still view is left
+// alone, as by rt_material_set_fresnel: a chain under an effective tint neither reads nor writes its buffers, and the scene without the bit is the scene they were stored for.)
+int rt_material_set_tint(rt_ctx *ctx, int object_slot, int on) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    if (int rc = edit_scene_check(ctx); rc != RT_OK) return rc;
+    if (object_slot < 0 || object_slot >= ctx->scene.n_objects) return fail(ctx, RT_ERR_INVALID, "tint: object_slot %d is outside the scene", object_slot);
+    ctx->tint_mask = on ? ctx->tint_mask | (1u << object_slot) : ctx->tint_mask & ~(1u << object_slot);
+    return RT_OK;
+}
+
+int rt_material_get_tint(const rt_ctx *ctx, int object_slot, int *on) {
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");
+    rt_ctx *c = const_cast<rt_ctx *>(ctx);
+    if (int rc = edit_scene_check(c); rc != RT_OK) return rc;
+    if (!on) return fail(c, RT_ERR_INVALID, "tint: on is NULL");
+    if (object_slot < 0 || object_slot >= ctx->scene.n_objects) return fail(c, RT_ERR_INVALID, "tint: object_slot %d is outside the scene", object_slot);
+    *on = (int)((ctx->tint_mask >> object_slot) & 1u);
+    return RT_OK;
+}
+
 // ---- the environment map (raytrace_hip.h "environment"): host state plus one device buffer of the context's; make_frame captures pointer and size ----
 int rt_scene_set_environment(rt_ctx *ctx, int n, const float *rgb) {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID, "ctx is NULL");

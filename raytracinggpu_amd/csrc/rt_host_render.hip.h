@@ -62,6 +62,16 @@ unsigned gloss_effective(const rt_ctx *ctx) {
         if (ctx->gloss_alpha[k] > 0.f && __builtin_bit_cast(int, sc.obj_a[k].w) != 0) eff |= 1u << k;
     return eff;
 }
+// Tinted mirrors and glass (rt_material_set_tint): the EFFECTIVE flags -- a flagged object whose material, as it is now, takes a specular arm (mirror != 0, smooth or rough,
+// or n_in != n_out).  Read when a chain is planned and by every entry that refuses, as gloss_effective.
+unsigned tint_effective(const rt_ctx *ctx) {
+    unsigned eff = 0;
+    const rtk::Scene &sc = ctx->scene;
+    if (!ctx->have_scene) return 0;
+    for (int k = 0; k < sc.n_objects && k < rtk::kMaxSpheres; ++k)
+        if (((ctx->tint_mask >> k) & 1u) != 0 && (__builtin_bit_cast(int, sc.obj_a[k].w) != 0 || sc.obj_n[k].x != sc.obj_n[k].y)) eff |= 1u << k;
+    return eff;
+}
 // Emissive meshes (rt_scene_set_emission): what the draws and the hits read of the context's table (a mesh emits and the scene has triangles: the buffer exists)
 static rtk::WfEmit emit_dist_of(const rt_ctx *ctx) {
     const unsigned long long *prefix = static_cast<const unsigned long long *>(ctx->emit_dist.p);
@@ -142,7 +152,16 @@ static int emit_refresh(rt_ctx *ctx) {
 // emitter, and by no other entry; the refusal says "fresnel".  Only an effective bit counts (fresnel_effective)
 // Rough mirrors (rt_material_set_roughness) are rendered by the chain's four kFormGloss forms alone: not under an environment, not with the shutter on, not beside an
 // emitter or an effective Fresnel flag, and by no other entry; the refusal says "roughness".  Only an effective value counts (gloss_effective)
+// Tinted mirrors and glass (rt_material_set_tint) are rendered by the chain's four kFormTint forms alone: not under an environment, not with the shutter on, not beside an
+// emitter or an effective Fresnel flag, and by no other entry; the refusal says "tint".  Only an effective flag counts (tint_effective); asked first, so that a scene with
+// a tint and a roughness says "tint"
 int lights_refuse(rt_ctx *ctx, const char *what, bool wf_chain = false) {
+    if (ctx && tint_effective(ctx) != 0) {
+        if (!wf_chain) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: an object of the scene has a tint; only wf_advance's tint forms meet it (rt_material_set_tint)", what);
+        if (ctx->env_n > 0 || ctx->shutter_on || ctx->emit_mask != 0 || fresnel_effective(ctx) != 0)
+            return fail(ctx, RT_ERR_UNSUPPORTED, "%s: an object of the scene has a tint and %s; no wf_advance form takes both (rt_material_set_tint)", what,
+                        ctx->env_n > 0 ? "the scene has an environment" : ctx->shutter_on ? "the shutter is on" : ctx->emit_mask != 0 ? "a mesh of the scene has an emission" : "an object is a fresnel dielectric");
+    }
     if (ctx && gloss_effective(ctx) != 0) {
         if (!wf_chain) return fail(ctx, RT_ERR_UNSUPPORTED, "%s: a mirror of the scene has a roughness; only wf_advance's gloss forms meet it (rt_material_set_roughness)", what);
         if (ctx->env_n > 0 || ctx->shutter_on || ctx->emit_mask != 0 || fresnel_effective(ctx) != 0)
@@ -295,7 +314,7 @@ Variant ask_variant(const rt_ctx *ctx, int variant, const rt_camera_pose *pose, 
     // 0.220 ms per frame (profiles/round5/ab_spheres_only.txt).  A posed camera exists in the wavefront family only.
     if (variant == RT_VARIANT_AUTO) {
         const bool lockstep = ctx->knobs.auto_lockstep != 0 && ctx->have_scene && ctx->scene.mesh_slot < 0 && ctx->scene.nrm == nullptr && pose == nullptr && !batch && ctx->n_lights == 1 && !lights_soft(ctx) &&
-                              !(ctx->lens_radius > 0.f) && !ctx->shutter_on && ctx->env_n == 0 && ctx->emit_mask == 0 && fresnel_effective(ctx) == 0 && gloss_effective(ctx) == 0;
+                              !(ctx->lens_radius > 0.f) && !ctx->shutter_on && ctx->env_n == 0 && ctx->emit_mask == 0 && fresnel_effective(ctx) == 0 && gloss_effective(ctx) == 0 && tint_effective(ctx) == 0;
         variant = lockstep ? RT_VARIANT_LOCKSTEP : RT_VARIANT_WAVEFRONT_QUEUE;
     }
     // BASELINE config 4 / north star: "hot triangle vertices and top BVH levels staged in LDS" = the work-stack traversal kernel
@@ -349,6 +368,7 @@ struct Chunk {
     rtk::WfSkyDist sd{};                                              // sd.s > 0: sky sampling is in effect -- the table, the effective share and the weights of the kFormSkySample launches (L3: per part)
     rtk::WfEmit em{};                                                 // em.mask != 0: a mesh emits -- the table, the effective share, the weights and the mask of the kFormEmit launches (L3: per part)
     rtk::WfGloss gz{};                                                // gz.mask != 0: the objects with an effective roughness and their alphas (rt_material_set_roughness) -- the argument of the kFormGloss launches (every one after the opening)
+    rtk::WfTint tz{};                                                 // tz.mask != 0: the effectively tinted objects (rt_material_set_tint) -- the argument of the kFormTint launches (every one after the opening)
     rtk::WfFresnel fz{};                                              // fz.mask != 0: the effectively flagged objects (rt_material_set_fresnel) -- the argument of the kFormFresnel launches (every one after the opening)
 };
 // what the draws read of the context's table (env_total > 0)
@@ -392,6 +412,7 @@ void make_frame(const rt_ctx *ctx, void *out_dev, const rt_camera_pose *pose, Ch
     c.fz.mask = fresnel_effective(ctx);                               // (rt_material_set_fresnel) the materials as they are now
     c.gz.mask = gloss_effective(ctx);                                 // (rt_material_set_roughness) likewise; the alphas by value, read only where the bit is set
     for (int k = 0; k < rtk::kMaxObjects; ++k) c.gz.alpha[k] = ((c.gz.mask >> k) & 1u) != 0 ? ctx->gloss_alpha[k] : 0.f;
+    c.tz.mask = tint_effective(ctx);                                  // (rt_material_set_tint) likewise
     const bool sampling = ctx->env_n > 0 && ctx->env_share > 0.f && ctx->env_total > 0;   // (an empty table: the effective share is 0)
     const bool emit = ctx->emit_mask != 0;                            // (emissive meshes take the soft route too)
     if (ctx->n_lights > 1 || c.soft || sampling || emit) {                    // (sky sampling takes the soft route with any lights: one point light is a soft list of one)                                // positions and the running sum of the intensities (raytrace_hip.h "several point lights"), captured by value
@@ -711,7 +732,7 @@ hipStream_t chain_stream(const rt_ctx *ctx, const Chunk &c, bool own0, int j);
 // The same holds while the shutter is on (rt_scene_set_shutter): a path's spheres and light depend on its sample.  And under an environment (rt_scene_set_environment): the
 // records know no miss that shines and no sky form resumes from them.  (The first-hit level would stay valid; DESIGN.md section 5.21 keeps that for later.)
 bool still_eligible(const rt_ctx *ctx, const Chunk &c, const TravPlan &t) {
-    return !(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && c.em.mask == 0 && c.fz.mask == 0 && c.gz.mask == 0 && ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
+    return !(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && c.em.mask == 0 && c.fz.mask == 0 && c.gz.mask == 0 && c.tz.mask == 0 && ctx->knobs.first_hit_cache != 0 && t.queue && t.have_mesh && c.work_dev == nullptr && !ctx->stats_on && c.fr.sigma == 0.f && c.batch == nullptr && c.segs > 0 &&
            ctx->knobs.debug_trav == -2;
 }
 // What the camera rays' hits depend on besides the mesh, bit for bit (the RAY KEY), and what segment 0's shading and shadow rays depend on besides the ray key and what is
@@ -876,12 +897,12 @@ int end_chains(rt_ctx *ctx, const Chunk &c, const WfCut &w, bool own0) {
 
 // What a chain's wf_advance launches may take beyond (Scene, Frame, WfState): each form takes the ones its bits name (rt_still.h kForm*), in this order (sl.lt: the table of
 // the forms without radii)
-struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; rtk::WfSky sky{}; rtk::WfSkyDist sd{}; rtk::WfEmit em{}; rtk::WfFresnel fz{}; rtk::WfGloss gz{}; };
+struct AdvArgs { rtk::TexScene ts{}; rtk::AnimTable anim = nullptr; rtk::WfList list{}; rtk::WfShade sh{}; rtk::WfSoftLights sl{}; rtk::WfLens ln{}; rtk::WfShutter shu{}; rtk::WfSky sky{}; rtk::WfSkyDist sd{}; rtk::WfEmit em{}; rtk::WfFresnel fz{}; rtk::WfGloss gz{}; rtk::WfTint tz{}; };
 struct AdvLaunch {
     dim3 grid, block; hipStream_t q; const rtk::Scene &scn; const rtk::Frame &fr; const rtk::WfState &st;
     template <unsigned FORM, class... Extra> void go(const Extra &... extra) const { hipLaunchKernelGGL((rtk::wf_advance<FORM, Extra...>), grid, block, 0, q, scn, fr, st, extra...); }
 };
-// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 41 instantiations, one case each (DESIGN.md section 5.2 says who launches
+// One wf_advance launch of form `form` (rtk::adv_form).  THE LIST OF THE FORMS THAT ARE BUILT: 45 instantiations, one case each (DESIGN.md section 5.2 says who launches
 // each and which test runs it).  The entries refuse what has no form before a chain is planned (lights_refuse, resolve_variant), so the default is not reached.
 int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_t q, const rtk::Scene &scn, const rtk::Frame &fr, const rtk::WfState &st, const AdvArgs &a) {
     using namespace rtk;
@@ -914,6 +935,10 @@ int launch_advance(rt_ctx *ctx, unsigned form, dim3 grid, dim3 block, hipStream_
     case kFormTex | kFormGloss: l.go<kFormTex | kFormGloss>(a.ts, a.gz); break;
     case kFormSoft | kFormGloss: l.go<kFormSoft | kFormGloss>(a.sl, a.gz); break;
     case kFormTex | kFormSoft | kFormGloss: l.go<kFormTex | kFormSoft | kFormGloss>(a.ts, a.sl, a.gz); break;
+    case kFormGloss | kFormTint: l.go<kFormGloss | kFormTint>(a.gz, a.tz); break;
+    case kFormTex | kFormGloss | kFormTint: l.go<kFormTex | kFormGloss | kFormTint>(a.ts, a.gz, a.tz); break;
+    case kFormSoft | kFormGloss | kFormTint: l.go<kFormSoft | kFormGloss | kFormTint>(a.sl, a.gz, a.tz); break;
+    case kFormTex | kFormSoft | kFormGloss | kFormTint: l.go<kFormTex | kFormSoft | kFormGloss | kFormTint>(a.ts, a.sl, a.gz, a.tz); break;
     case kFormTex | kFormAnim: l.go<kFormTex | kFormAnim>(a.ts, a.anim); break;
     case kFormTex | kFormList: l.go<kFormTex | kFormList>(a.ts, a.list); break;
     case kFormFirst | kFormStats: l.go<kFormFirst | kFormStats>(); break;
@@ -941,13 +966,13 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     if (pt.st.n_paths == 0) return RT_OK;
     // the chain's facts: with the step they decide the form of each wf_advance launch (rt_still.h adv_form)
     const bool anim = c.batch && c.anim;                          // an animated batch: the frames' lights and spheres too
-    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on, c.sky.n > 0, c.sd.s > 0.f, c.em.mask != 0, c.fz.mask != 0, c.gz.mask != 0};
+    const rtk::AdvFacts facts{c.work_dev != nullptr, ctx->tex_mask != 0, anim, false, c.lens.radius > 0.f, c.soft ? 2 : c.sl.lt.n > 1 ? 1 : 0, c.shutter_on, c.sky.n > 0, c.sd.s > 0.f, c.em.mask != 0, c.fz.mask != 0, c.gz.mask != 0, c.tz.mask != 0};
     const dim3 pg(pt.pblocks), pb(kn.adv_block);
     pt.st.samp0 = s; pt.st.epoch = 0;
     // what the chain fills or uses of a still view, and its launches from there (rt_still.h: the state is marked here, at enqueue)
     const rtk::QRows win_y = rtk::qrows_y(pt.st.n_paths, pt.st.log2S, pt.st.Q);
-    // (the camera has a lens: the chain opens with the lens form and knows no still view; nor does a chain of the shutter forms, nor one of the sky forms, nor one of the emission forms, nor one of the fresnel forms, nor one of the gloss forms)
-    const rtk::StillChain sc = (facts.lens || facts.shutter || facts.sky || facts.emit || facts.fresnel || facts.gloss) ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
+    // (the camera has a lens: the chain opens with the lens form and knows no still view; nor does a chain of the shutter forms, nor one of the sky forms, nor one of the emission forms, nor one of the fresnel forms, nor one of the gloss forms, nor one of the tint forms)
+    const rtk::StillChain sc = (facts.lens || facts.shutter || facts.sky || facts.emit || facts.fresnel || facts.gloss || facts.tint) ? rtk::StillChain{rtk::kStillOff, rtk::kStillOff, rtk::kStillOff} : ctx->still.chain(j, ctx->wfS0.p != nullptr && ctx->wfS0.bytes >= w.px * 32);
     // the plain chain takes the closing kernel at its last position
     const bool plain = t.queue && rtk::adv_plain_chain(facts);
     // ... and, where the Scene of THIS enqueue allows it, leaves the last continuation ray of a dead path that hits a sphere out of the traversal (rt_deadlast.h; a counting
@@ -957,7 +982,7 @@ int enqueue_chain(rt_ctx *ctx, const Chunk &c, const TravPlan &t, WfCut &w, int 
     const rtk::StillPlan plan = rtk::still_plan(sc, c.segs, t.have_mesh, t.queue && kn.travq_rows, win_y.rows != 0, plain && kn.chain_ends != 0);
     auto block = [&](const DevBuf &b) { return static_cast<unsigned long long *>(b.p) + pt.pxbase; };   // the part's block of a level
     AdvArgs aa;
-    aa.anim = pt.anim; aa.sl = c.sl; aa.ln = c.lens; aa.shu = c.shutter; aa.sky = c.sky; aa.fz = c.fz; aa.gz = c.gz;
+    aa.anim = pt.anim; aa.sl = c.sl; aa.ln = c.lens; aa.shu = c.shutter; aa.sky = c.sky; aa.fz = c.fz; aa.gz = c.gz; aa.tz = c.tz;
     if (facts.sample) { aa.sd = c.sd; aa.sd.L3 = static_cast<float4 *>(ctx->wfL3.p) + pt.base * (size_t)c.nseg; }   // L3[d * n_paths + i] inside the part's block, as ALB
     if (facts.emit) { aa.em = c.em; aa.em.L3 = static_cast<float4 *>(ctx->wfL3.p) + pt.base * (size_t)c.nseg; }       // ... and likewise
     if (sc.records != rtk::kStillOff) { aa.sh.rec = static_cast<float4 *>(ctx->wfS0.p) + 2 * pt.pxbase; aa.sh.kill_x = plan.kill_x; }
@@ -1051,7 +1076,7 @@ int launch_wavefront(rt_ctx *ctx, const Chunk &c, const Variant &v) {
     }
     ctx->stats.lds_bytes = (int)t.lds; ctx->stats.block_threads = t.tb; ctx->stats.grid_blocks = (int)w.pv[0].tblocks; ctx->stats.parts = parts; ctx->stats.travq_mode = t.travq_mode;
     if ((rc = start_chains(ctx, c, w, qr_grown, own0)) != RT_OK) return rc;
-    if (!(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && c.em.mask == 0 && c.fz.mask == 0 && c.gz.mask == 0) still_begin(ctx, c, t, w, own0);
+    if (!(c.lens.radius > 0.f) && !c.shutter_on && !(c.sky.n > 0) && c.em.mask == 0 && c.fz.mask == 0 && c.gz.mask == 0 && c.tz.mask == 0) still_begin(ctx, c, t, w, own0);
     // The chains of ONE sample chunk are issued for all sub-frames before the next chunk's.
     // (Rounds 2-4 issued all chunks of sub-frame 0 first: with hundreds of chains the host was still feeding stream 0 while stream 1 sat empty, the
     // sub-frames ran one after the other instead of side by side, and a 256-sample 1080p frame cost 1.26 ms per sample against 0.94 at 32 samples --

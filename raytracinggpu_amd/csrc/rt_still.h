@@ -184,7 +184,8 @@ constexpr unsigned kFormStats = 1u << 0, kFormFirst = 1u << 1, kFormTex = 1u << 
                    kFormSkySample = 1u << 13,                // sky sampling: a segment's shadow ray may go to the environment, drawn from its table (WfSkyDist, after the WfSky)
                    kFormEmit = 1u << 14,                     // emissive meshes: a ray that hits an emitter ends there, a segment's shadow ray may go to one (WfEmit, after the WfSoftLights)
                    kFormFresnel = 1u << 15,                  // Fresnel dielectrics: a ray that hits a flagged glass object is reflected or refracted, one draw (WfFresnel, last)
-                   kFormGloss = 1u << 16;                    // rough mirrors: a ray that hits a mirror with a roughness is reflected about a GGX facet, two draws (WfGloss, last)
+                   kFormGloss = 1u << 16,                    // rough mirrors: a ray that hits a mirror with a roughness is reflected about a GGX facet, two draws (WfGloss, last)
+                   kFormTint = 1u << 17;                     // tinted mirrors and glass: a specular segment of a flagged object is folded with the object's albedo (WfTint, last; always with kFormGloss)
 constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks for this launch, and no kernel exists for it
 
 // What decides the form besides the step: the chain's facts.  counting: rt_count_work; anim: a batch with per-frame scenes; list: rt_render_counts*; lights: 0 the Scene's
@@ -193,9 +194,10 @@ constexpr unsigned kFormNotBuilt = ~0u;              // adv_form: no entry asks 
 // emit: a mesh of the scene emits (rt_scene_set_emission) -- last and defaulted as well
 // fresnel: an object of the scene is effectively flagged (rt_material_set_fresnel) -- last and defaulted as well
 // gloss: an object of the scene has an effective roughness (rt_material_set_roughness) -- last and defaulted as well
-struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; bool sample = false; bool emit = false; bool fresnel = false; bool gloss = false; };   // sample: sky sampling is in effect (with sky), last and defaulted too
+// tint: an object of the scene is effectively tinted (rt_material_set_tint) -- last and defaulted as well
+struct AdvFacts { bool counting, tex, anim, list, lens; int lights; bool shutter = false; bool sky = false; bool sample = false; bool emit = false; bool fresnel = false; bool gloss = false; bool tint = false; };   // sample: sky sampling is in effect (with sky), last and defaulted too
 // The plain chain -- every launch after the opening one the form 0 or kFormStats (or the launch that stores the records): still_plan's `ends`, for a work-stack chain
-inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky && !f.emit && !f.fresnel && !f.gloss; }
+inline bool adv_plain_chain(const AdvFacts &f) { return !f.tex && !f.anim && !f.list && !f.lens && f.lights == 0 && !f.shutter && !f.sky && !f.emit && !f.fresnel && !f.gloss && !f.tint; }
 // The form of the launch a chain of these facts enqueues for `adv` (StillAdv: StillPlan::open for the opening launch, StillStep::adv for the later ones)
 inline unsigned adv_form(const AdvFacts &f, int adv) {
     // counting, a list and an animated batch exclude one another, and each refuses several lights, a radius and the lens before a chain is planned (lights_refuse)
@@ -207,6 +209,16 @@ inline unsigned adv_form(const AdvFacts &f, int adv) {
     // the shutter refuse it (lights_refuse); no still view (no fill, no resume), and the closing kernel closes no continuation ray: not a plain chain.  A light list without
     // a radius goes through the soft forms with radii 0 (a radius-0 light is the light itself, bit for bit): four later forms, not six
     if (f.sample && !f.sky) return kFormNotBuilt;
+    // Tinted mirrors and glass: the specular segment is recorded where a continuation ray is closed, so the opening launch is what it was (the lens included) and every
+    // later launch has the bit -- together with kFormGloss, whether a mirror of the scene is rough or not (an empty WfGloss mask: the smooth mirror arm): four forms, not
+    // eight.  Counting, a list, an animated batch, the shutter, an environment, an emitter and an effective Fresnel flag refuse it (lights_refuse); no still view (the
+    // records hold no segment but the first, and the closing kernel's fold would have to be a tint form too) and not a plain chain
+    if (f.tint) {
+        if (special != 0 || f.shutter || f.sky || f.emit || f.fresnel) return kFormNotBuilt;
+        if (adv == kAdvBegin) return kFormFirst | (f.lens ? kFormLens : 0u);
+        if (adv == kAdvPlain) return (f.tex ? kFormTex : 0u) | (f.lights != 0 ? kFormSoft : 0u) | kFormGloss | kFormTint;
+        return kFormNotBuilt;
+    }
     // Rough mirrors: the facet is drawn where a continuation ray is closed, so the opening launch is what it was (the lens included) and every later launch has the
     // bit.  Counting, a list, an animated batch, the shutter, an environment, an emitter and an effective Fresnel flag refuse it (lights_refuse); no still view (no
     // fill, no resume: the records hold one continuation ray per pixel slot, a rough first hit has one per sample) and not a plain chain.  A light list or a radius

@@ -712,7 +712,7 @@ __device__ __forceinline__ f3 tex_albedo(const Scene &sc, const TexScene &ts, in
 #define ADV_MARK(name) do { } while (0)
 #else
 // (the compiler numbers the labels through the translation unit: the LIGHTS instantiations of wf_advance_path plant none, so that every other kernel's labels, and with
-// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones, nor the EMIT ones, nor the FRESNEL ones, nor the GLOSS ones)
+// them its text, stay what they were before those two existed -- tools/asm_compare.py; neither does the LENS instantiation, nor the SHUTTER ones, nor the SKY ones, nor the EMIT ones, nor the FRESNEL ones, nor the GLOSS ones -- the TINT ones are GLOSS ones)
 #define ADV_MARK(name) do { if constexpr (!LIGHTS && !LENS && !SHUTTER && !SKY && !SAMPLE && !EMIT && !FRESNEL && !GLOSS) asm volatile("rt_mark_adv_" name "_%=:" ::); } while (0)
 #endif
 struct WfList {
@@ -815,6 +815,14 @@ struct WfGloss {
     unsigned int mask;                       // bit k: the object at position k has an EFFECTIVE roughness (alpha > 0 and mirror != 0: formed on the host)
     float alpha[kMaxObjects];                // the roughness by object id; read only where the bit is set
 };
+// TINTED MIRRORS AND GLASS (rt_material_set_tint; the rule: raytrace_hip.h "tint").  The path's throughput is the fold: a specular hit of segment d on an effectively
+// tinted object writes SID[d] = its object id and LS[d] = +0 where any other specular hit writes SID[d] = 0xff, and the fold -- which does not change -- then takes the
+// segment for a diffuse one of direct term +0: fl(fl(fl(0 alb) / pi) + fl(alb ans)) = fl(alb ans) per channel, the object's albedo as a tint.  No shadow ray leaves the
+// segment and none is taken to have left it: the launch that closes segment d's shadow ray asks the path's flag word (PF_HASX, set at emission where emitX is), never SID.
+// The mask is a kernel argument of the four forms that read it (kFormTint, always with kFormGloss) and of no other kernel.
+struct WfTint {
+    unsigned int mask;                       // bit k: the object at position k is EFFECTIVELY tinted (flagged and mirror != 0 or n_in != n_out: formed on the host)
+};
 // THE SHUTTER (rt_scene_set_shutter; the rule: raytrace_hip.h "shutter", the step: shutter_time / shutter_pose in rt_shade.hip.h).  Over the exposure the light travels dL and
 // sphere k travels its displacement; a path sees the scene at ONE time tau, drawn from its sample's key, and every launch of its chain -- the SHUTTER forms, kFormShutter --
 // draws tau again and forms the light and the centres at that time where the Scene's would be read: the close of a shadow ray, the sphere normal, the shadow direction and
@@ -844,7 +852,7 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                                                 const WfList &list, const WfShade &sh, const WfLights *__restrict__ lt, const WfSoftLights *__restrict__ sl, const WfLens *__restrict__ ln,
                                                 const WfShutter *__restrict__ shu, const WfSky *__restrict__ sky, const WfSkyDist *__restrict__ sd = nullptr,
                                                 const WfEmit *__restrict__ em = nullptr, const WfFresnel *__restrict__ fz = nullptr,
-                                                const WfGloss *__restrict__ gz = nullptr) {
+                                                const WfGloss *__restrict__ gz = nullptr, const WfTint *__restrict__ tz = nullptr) {
     constexpr bool STATS = FORM & kFormStats, FIRST = FORM & kFormFirst, TEX = FORM & kFormTex, ANIM = FORM & kFormAnim, LIST = FORM & kFormList;
     constexpr bool FILL = FORM & kFormFill, RESUME = FORM & kFormResume, LENS = FORM & kFormLens, CLOSE = FORM & kFormClose, SHUTTER = FORM & kFormShutter, SKY = FORM & kFormSky;
     constexpr bool SAMPLE = FORM & kFormSkySample;                     // sky sampling: a segment's one shadow ray may go to the environment (always with SKY and the soft lights' table)
@@ -857,6 +865,9 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
     // rough mirrors: a continuation ray that hits a mirror with an effective roughness is reflected about a facet, two draws (gloss_step beside mirror_step; never with
     // SKY, SHUTTER, EMIT or FRESNEL, and in the later launches of a chain alone)
     constexpr bool GLOSS = FORM & kFormGloss;
+    // tinted mirrors and glass: a specular hit of an effectively tinted object is recorded as a segment of the object's albedo and direct term +0 (always with GLOSS,
+    // whose mask may be empty; never with SKY, SHUTTER, EMIT or FRESNEL, and in the later launches of a chain alone)
+    constexpr bool TINT = FORM & kFormTint;
     constexpr int LIGHTS = (FORM & kFormSoft) ? 2 : (FORM & kFormLights) ? 1 : 0;
     constexpr bool DEAD_LAST = (FORM & ~kFormStats) == 0u;             // the plain later launch and its counting twin: the one form with the dead-last rule (kPolDeadLast)
     // The plain chain's later launches (form 0, the closing kernel, their counting twins) ask for a path's words in ROUNDS, not one dependent load after the other: the Y
@@ -1283,6 +1294,19 @@ __device__ __forceinline__ void wf_advance_path(const Scene &sc, const Frame &fr
                         ADV_MARK("bounce_end");
                     }
                 }
+                if constexpr (TINT) {
+                    // The arm above was a specular one (the mask holds effective bits alone) and built the ray it always builds; no shadow ray leaves.  To the fold the
+                    // segment is a diffuse one of this albedo and direct term +0, and so it is to the dead channels (the material table's albedo, textured or not)
+                    if (((tz->mask >> win) & 1u) != 0) {
+                        sid = win;
+                        st.LS[(size_t)d * st.n_paths + i] = 0.f;
+                        if (st.deadch) {
+                            const int was = st.DCH[i];
+                            const int now = (was & 8) | wf_dead_channels(was & 7, mk(m.ar, m.ag, m.ab), 0.f);
+                            if (now != was) st.DCH[i] = (unsigned char)now;
+                        }
+                    }
+                }
                 if (FILL && sid == 0xff) { shO = O; shV = u; sh_kind = kShadeSpecular; }   // mirror or glass: the continuation ray
                 if (FILL) sh_rays = nrays;
                 if (cont && d + 1 < fr.segs) {
@@ -1450,6 +1474,7 @@ template <class T, class... Extra> constexpr bool adv_takes = (std::is_same_v<T,
 // The gloss forms carry two draws, one quotient, two roots, the sincos and the tangent frame more than their counterparts (+ 385 vector instructions).  gloss and
 // soft | gloss: eight waves, 52 and 54 registers, nothing spills; tex | gloss: at eight waves 2 scalar registers spill, at seven nothing does; tex | soft | gloss:
 // seven, as its counterpart.
+// The tint forms are the gloss forms with one mask test, two stores and the dead-channel byte's update more: the same waves as their counterparts.
 constexpr int adv_waves(unsigned form) { return (form & kFormGloss) ? ((form & kFormTex) ? 7 : 8) : (form & kFormFresnel) ? ((form & kFormTex) ? 7 : 8) : (form & kFormEmit) ? ((form & kFormTex) ? 6 : 7) : (form & kFormSkySample) ? 6 : (form & kFormTex) && (form & kFormSoft) ? 7 : 8; }
 template <unsigned FORM, class... Extra>
 __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene sc, const Frame fr, const WfState st, const Extra... extra) {
@@ -1459,14 +1484,14 @@ __global__ __launch_bounds__(256, adv_waves(FORM)) void wf_advance(const Scene s
                   adv_takes<WfLens, Extra...> == ((FORM & kFormLens) != 0) && adv_takes<WfShutter, Extra...> == ((FORM & kFormShutter) != 0) &&
                   adv_takes<WfSky, Extra...> == ((FORM & kFormSky) != 0) && adv_takes<WfSkyDist, Extra...> == ((FORM & kFormSkySample) != 0) &&
                   adv_takes<WfEmit, Extra...> == ((FORM & kFormEmit) != 0) && adv_takes<WfFresnel, Extra...> == ((FORM & kFormFresnel) != 0) &&
-                  adv_takes<WfGloss, Extra...> == ((FORM & kFormGloss) != 0),
+                  adv_takes<WfGloss, Extra...> == ((FORM & kFormGloss) != 0) && adv_takes<WfTint, Extra...> == ((FORM & kFormTint) != 0),
                   "a form's extras are the ones its bits name");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     Work wk;
     if (i < st.n_paths)
         wf_advance_path<FORM>(sc, fr, st, i, wk, adv_extra_or(TexScene{}, extra...), adv_extra_or<AnimTable>(nullptr, extra...), adv_extra_or(WfList{}, extra...), adv_extra_or(WfShade{}, extra...),
                               adv_extra<WfLights>(extra...), adv_extra<WfSoftLights>(extra...), adv_extra<WfLens>(extra...), adv_extra<WfShutter>(extra...), adv_extra<WfSky>(extra...), adv_extra<WfSkyDist>(extra...),
-                              adv_extra<WfEmit>(extra...), adv_extra<WfFresnel>(extra...), adv_extra<WfGloss>(extra...));
+                              adv_extra<WfEmit>(extra...), adv_extra<WfFresnel>(extra...), adv_extra<WfGloss>(extra...), adv_extra<WfTint>(extra...));
     wf_flush_work<(FORM & kFormStats) != 0>(fr, wk);                  // (the counting forms) every lane of the wave arrives here (wave-level sums)
 }
 

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("RT_HOST_LIB") or os.path.join(HERE, "libraytrace_host
 EXPORTS = ["rth_mesh_new", "rth_mesh_free", "rth_mesh_read_obj", "rth_mesh_set_arrays", "rth_mesh_rescale",
            "rth_mesh_build_bvh", "rth_mesh_num_vertices", "rth_mesh_num_triangles", "rth_mesh_num_nodes",
            "rth_mesh_get_vertices", "rth_mesh_get_indices", "rth_mesh_get_bvh_array", "rth_write_png", "rth_qrows_enumerate", "rth_still_replay",
-           "rth_row_cut", "rth_row_chunks", "rth_advance_form", "rth_advance_form_shutter", "rth_advance_form_sky", "rth_advance_form_sky_sample", "rth_advance_form_emit", "rth_advance_form_fresnel", "rth_advance_form_gloss",
+           "rth_row_cut", "rth_row_chunks", "rth_advance_form", "rth_advance_form_shutter", "rth_advance_form_sky", "rth_advance_form_sky_sample", "rth_advance_form_emit", "rth_advance_form_fresnel", "rth_advance_form_gloss", "rth_advance_form_tint",
            "rth_dead_last_scene_size", "rth_dead_last_permit", "rth_gamma_byte"]
 _lib = None
 
@@ -52,6 +52,8 @@ def load():
         L.rth_advance_form_fresnel.argtypes = [C.c_int] * 12
         L.rth_advance_form_gloss.restype = C.c_int64
         L.rth_advance_form_gloss.argtypes = [C.c_int] * 13
+        L.rth_advance_form_tint.restype = C.c_int64
+        L.rth_advance_form_tint.argtypes = [C.c_int] * 14
         L.rth_row_cut.restype = None
         L.rth_row_cut.argtypes = [ip, C.c_int, ip]
         L.rth_row_chunks.argtypes = [ip, C.c_int, ip, C.c_int]
@@ -155,11 +157,14 @@ def still_replay(events):
     return counts.reshape(3, 4).astype(np.int64), rows[:n]
 
 
-def advance_form(counting, tex, anim, list_, lens, lights, adv, shutter=None, sky=None, sample=None, emit=None, fresnel=None, gloss=None):
+def advance_form(counting, tex, anim, list_, lens, lights, adv, shutter=None, sky=None, sample=None, emit=None, fresnel=None, gloss=None, tint=None):
     """The form word of the wf_advance launch a chain of these facts enqueues for step `adv` (csrc/rt_still.h adv_form, rth_advance_form); None: not built.
     shutter: the fact that came later (rth_advance_form_shutter); left out, the call is the one it was.  sky: the one after it (rth_advance_form_sky), likewise;
-    then sample (rth_advance_form_sky_sample), emit (rth_advance_form_emit), fresnel (rth_advance_form_fresnel) and gloss (rth_advance_form_gloss), each through the entry that first knew it."""
-    if gloss is not None:
+    then sample (rth_advance_form_sky_sample), emit (rth_advance_form_emit), fresnel (rth_advance_form_fresnel), gloss (rth_advance_form_gloss) and tint (rth_advance_form_tint), each through the entry that first knew it."""
+    if tint is not None:
+        f = load().rth_advance_form_tint(int(counting), int(tex), int(anim), int(list_), int(lens), int(lights), int(bool(shutter)), int(bool(sky)), int(bool(sample)), int(bool(emit)),
+                                         int(bool(fresnel)), int(bool(gloss)), int(tint), int(adv))
+    elif gloss is not None:
         f = load().rth_advance_form_gloss(int(counting), int(tex), int(anim), int(list_), int(lens), int(lights), int(bool(shutter)), int(bool(sky)), int(bool(sample)), int(bool(emit)),
                                           int(bool(fresnel)), int(gloss), int(adv))
     elif fresnel is not None:

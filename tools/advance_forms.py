@@ -6,7 +6,7 @@ here and nowhere else.  form_of(name) -> the word, or None for another kernel.""
 import re
 
 BITS = {"stats": 1 << 0, "first": 1 << 1, "tex": 1 << 2, "anim": 1 << 3, "list": 1 << 4, "fill": 1 << 5, "resume": 1 << 6, "lights": 1 << 7, "soft": 1 << 8,
-        "lens": 1 << 9, "close": 1 << 10, "shutter": 1 << 11, "sky": 1 << 12, "sample": 1 << 13, "emit": 1 << 14, "fresnel": 1 << 15, "gloss": 1 << 16}
+        "lens": 1 << 9, "close": 1 << 10, "shutter": 1 << 11, "sky": 1 << 12, "sample": 1 << 13, "emit": 1 << 14, "fresnel": 1 << 15, "gloss": 1 << 16, "tint": 1 << 17}
 _B = BITS
 # the names the forms had as kernels of their own (demangled, spaces dropped)
 OLD = {"wf_advance<false,false>": 0, "wf_advance<true,false>": _B["stats"], "wf_advance<false,true>": _B["first"], "wf_advance<true,true>": _B["first"] | _B["stats"],
@@ -29,6 +29,8 @@ EMISSION_FORMS = sorted([_B["soft"] | _B["emit"], _B["tex"] | _B["soft"] | _B["e
 FRESNEL_FORMS = sorted([_B["fresnel"], _B["tex"] | _B["fresnel"], _B["soft"] | _B["fresnel"], _B["tex"] | _B["soft"] | _B["fresnel"]])
 # ... and the four of the rough mirrors (kFormGloss: the later launches of a chain in whose scene a mirror has an effective roughness; a light list or a radius takes the soft route)
 GLOSS_FORMS = sorted([_B["gloss"], _B["tex"] | _B["gloss"], _B["soft"] | _B["gloss"], _B["tex"] | _B["soft"] | _B["gloss"]])
+# ... and the four of the tinted mirrors and glass (kFormTint, always beside kFormGloss: the later launches of a chain in whose scene an object is effectively tinted, a mirror of it rough or not)
+TINT_FORMS = sorted([g | _B["tint"] for g in GLOSS_FORMS])
 
 
 def form(*names):

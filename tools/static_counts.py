@@ -215,7 +215,10 @@ ADVANCE = {"wf_advance": ((), True), "wf_advance_first": (("first",), False),
            "wf_advance_soft_fresnel": (("soft", "fresnel"), False), "wf_advance_tex_soft_fresnel": (("tex", "soft", "fresnel"), False),
            # rough mirrors (WfGloss): the four later launches of a chain in whose scene a mirror has an effective roughness, whole (no labels)
            "wf_advance_gloss": (("gloss",), False), "wf_advance_tex_gloss": (("tex", "gloss"), False),
-           "wf_advance_soft_gloss": (("soft", "gloss"), False), "wf_advance_tex_soft_gloss": (("tex", "soft", "gloss"), False)}
+           "wf_advance_soft_gloss": (("soft", "gloss"), False), "wf_advance_tex_soft_gloss": (("tex", "soft", "gloss"), False),
+           # tinted mirrors and glass (WfTint, beside the WfGloss): the four later launches of a chain in whose scene an object is effectively tinted, whole (no labels)
+           "wf_advance_gloss_tint": (("gloss", "tint"), False), "wf_advance_tex_gloss_tint": (("tex", "gloss", "tint"), False),
+           "wf_advance_soft_gloss_tint": (("soft", "gloss", "tint"), False), "wf_advance_tex_soft_gloss_tint": (("tex", "soft", "gloss", "tint"), False)}
 
 
 def advance_forms_counts(asm):
@@ -287,7 +290,8 @@ def main():
                  "wf_advance_sky", "wf_advance_tex_sky", "wf_advance_soft_sky", "wf_advance_tex_soft_sky",
                  "wf_advance_soft_sky_sample", "wf_advance_tex_soft_sky_sample", "wf_advance_soft_emit", "wf_advance_tex_soft_emit",
                  "wf_advance_fresnel", "wf_advance_tex_fresnel", "wf_advance_soft_fresnel", "wf_advance_tex_soft_fresnel",
-                 "wf_advance_gloss", "wf_advance_tex_gloss", "wf_advance_soft_gloss", "wf_advance_tex_soft_gloss"):
+                 "wf_advance_gloss", "wf_advance_tex_gloss", "wf_advance_soft_gloss", "wf_advance_tex_soft_gloss",
+                 "wf_advance_gloss_tint", "wf_advance_tex_gloss_tint", "wf_advance_soft_gloss_tint", "wf_advance_tex_soft_gloss_tint"):
         res[name] = adv[name]
     m = re.search(r"\.name:\s+_ZN3rtk8wf_travqILb0ELi64ELb0ELb0EEE.*?\n(.*?)\.wavefront_size", asm, re.S)
     with open(OUT, "w") as f:
